@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the MI355X fingerprint hot path.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 Metric (BASELINE.json): audio-seconds fingerprinted per second, 44.1 kHz mono int16; second half: query match
-latency against a 1M-song table (the `match_1M` extra, N = 1 only).
+latency against a 1M-song table (the `match_1M` extra of --full, N = 1 only).
 Workload (BASELINE configs[1]): per GPU a batch of 1,000 synthetic 30 s clips resident in HBM,
 fingerprint-only: PCM -> STFT -> dB -> 21x21 peaks -> pair hashes (key32, t1) compacted on
 the device.  One "step" = one pass over that batch.  N > 1 is weak scaling: every rank fingerprints its own
@@ -12,10 +12,18 @@ the device.  One "step" = one pass over that batch.  N > 1 is weak scaling: ever
 torch.distributed.run (RANK / WORLD_SIZE in the environment) or, when --gpus N > 1 is given without that
 environment, by this script itself: N child processes, one per GPU, started before any HIP call.
 
-Beside the headline line the JSON carries
+A plain run sets up, warms up, times the K steps, writes the outputs if asked and prints the result line.  Beside the
+headline figures that line carries
   roofline      dominant kernel: ALGORITHMIC bytes (4,096 B PCM + 8 B per hash, per frame) per launch over
                 its HIP-event duration vs the HBM peak (`achieved`, `frac`); the bytes the kernel itself moves per
-                launch (`staged_*`), the PMC-measured traffic (`traffic`) and the whole step's figure beside it
+                launch (`staged_*`), the PMC-measured traffic (`traffic`) and the whole step's figure beside it -- from the
+                HIP events of the timed steps themselves, no run of its own
+--dump-outputs DIR writes what the last timed step computed (rank 0), as float64 .npy files (exact for uint32):
+  hash_off      per-clip offsets into the step's hashes, every clip
+  sample_clips  the clips sampled below: a fixed seeded choice of at most 128 clips, the same at every run
+                with the same --clips and --seconds
+  key32, t1     the hashes of the sampled clips, clip after clip (the whole step's would be ~190 MB)
+--full adds every other measurement, outside the timed region (each also has an --no-* or size option to leave it out):
   cpu_baseline  the reference's numpy/scipy/mlab call sequence (oracle/thirdparty_ref.py)
                 timed on this box's host cores over a bounded sample (rank 0, N = 1 only)
   db_build      fingerprints -> HBM table (with the RCCL all-gather when N > 1), untimed extra
@@ -559,6 +567,25 @@ def match_1m(ctx, songs, info):
     return o
 
 
+DUMP_CLIPS = 128            # at most; 128 x 645 frames (30 s) x ~19 hashes x 16 B = 24 MB
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, kbuf, tbuf, hash_off, frames_per_clip):
+    """The last timed step's outputs as a caller of the step receives them (key32, t1, hash_off), as float64 .npy files:
+    hash_off whole, the hashes of a fixed seeded sample of clips.  The sample depends on the clip count and length only
+    (sized at 24 hashes a frame, the step's output capacity), so two builds dump the same clips."""
+    nc = len(hash_off) - 1
+    n_pick = max(1, min(nc, DUMP_CLIPS, (DUMP_LIMIT_BYTES // 2) // (frames_per_clip * 24 * 16)))
+    clips = np.sort(np.random.default_rng(2024).choice(nc, n_pick, replace=False))
+    ho = hash_off.astype(np.int64)
+    key, t1 = kbuf.download(np.uint32, int(ho[-1])), tbuf.download(np.uint32, int(ho[-1]))
+    idx = np.concatenate([np.arange(ho[c], ho[c + 1]) for c in clips])[:(DUMP_LIMIT_BYTES // 2) // 16]
+    os.makedirs(path, exist_ok=True)
+    for name, arr in (("hash_off", hash_off), ("sample_clips", clips), ("key32", key[idx]), ("t1", t1[idx])):
+        np.save(os.path.join(path, f"{name}.npy"), arr.astype(np.float64))
+
+
 def self_launch(a):
     """`python bench.py --gpus N` without a launcher: start N ranks of this script (one per GPU) before this process
     touches HIP, relay their output, exit with the worst return code."""
@@ -585,8 +612,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--clips", type=int, default=1000, help="clips per GPU per step")
     ap.add_argument("--seconds", type=float, default=30.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs (rank 0) to DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true", help="beside the headline, every other measurement: CPU baseline, table build, "
+                    "match, host-fed rate, single query, two contexts, match_1M, db_build_scaling")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: leave out everything after the timed steps")
     ap.add_argument("--queries", type=int, default=2000)
     ap.add_argument("--match-songs", type=int, default=1000000, help="tracks of the match_1M extra (0 = skip)")
     ap.add_argument("--ws-limit-mb", type=float, default=0.0, help="cap on the extraction workspace (shz_set_workspace_limit): "
@@ -626,7 +656,7 @@ def main():
 
     n_samples = int(round(a.seconds * FS))
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         cpu = cpu_baseline(n_samples)   # before any HIP call: the Pool forks from a GPU-free process
 
     from shazam_amd import _ffi
@@ -658,6 +688,8 @@ def main():
     elapsed = time.perf_counter() - t0
     kms = ctx.kernel_ms()
     ctx.set_profiling(False)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, kbuf, tbuf, hash_off, frames_per_clip)
     if dist:
         import torch
         tt = torch.tensor([elapsed], dtype=torch.float64)
@@ -730,7 +762,7 @@ def main():
 
     # ---- extras (outside the timed region).  A watchdog prints the headline line if the extras (RCCL init /
     # all-gather on an unknown node) hang, so the measured value is never lost -- and exits NON-ZERO: a hang is a failure.
-    if not a.no_extras:
+    if a.full and not a.no_extras:
         import threading
 
         def on_timeout():   # runs in its own thread: a hung RCCL call inside ctypes cannot block it
