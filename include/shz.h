@@ -227,8 +227,7 @@ uint32_t shz_frame_count_hop(uint64_t n_samples, uint32_t hop);
 /* Staging precision of shz_peaks / shz_fingerprint_batch.  Default (0): the power spectrogram is staged in fp32 and
  * the cells fp32 cannot decide (shared window maxima, threshold within 1e-7) are re-derived in fp64; results are
  * those of the fp64 path bit for bit.  1: stage fp64 and decide everything in the peak kernel (twice the HBM traffic;
- * what a clip falls back to on stationary / plateau material, and always used for amp_min < 0).
- * Env SHZ_STAGE_F64=1 forces it process-wide. */
+ * what a clip falls back to on stationary / plateau material, and always used for amp_min < 0). */
 int32_t shz_set_stage_f64(shz_ctx* ctx, int32_t enabled);
 /* Counters since ctx creation: cells left undecided by the fp32 pass, those that needed fp64 values, FFT frames
  * recomputed for them, whole passes repeated with fp64 staging, single clips re-run with fp64 staging (windows with more
@@ -358,11 +357,11 @@ int32_t shz_comm_destroy(shz_comm* c);
  *   (more than 32 runs: the smallest are merged first).  No rank sorts another rank's rows.  Afterwards every rank
  *   holds the same table.  Which rows travel: everything inserted since the table was last finalized / gathered --
  *   staged rows and sealed runs.
- * The column path: when any rank's table already holds rows, or its song ids + offsets need more than 32 bits, or
- *   SHZ_ALLGATHER=columns is set, the ranks' STAGED rows travel as unsorted columns and finalize sorts them into the
- *   table each rank holds.  Every rank takes it if any rank needs it.  Sealed runs do not travel on it: if any rank
- *   holds one, or its seal_run has already moved rows into segments (a table not reserved with SHZ_RESERVE_GATHER that
- *   sealed past a segment's worth), EVERY rank returns SHZ_E_STATE -- never a table that differs between ranks.
+ * The column path: when any rank's table already holds rows, or its song ids + offsets need more than 32 bits, the
+ *   ranks' STAGED rows travel as unsorted columns and finalize sorts them into the table each rank holds.  Every rank
+ *   takes it if any rank needs it.  Sealed runs do not travel on it: if any rank holds one, or its seal_run has already
+ *   moved rows into segments (a table not reserved with SHZ_RESERVE_GATHER that sealed past a segment's worth), EVERY
+ *   rank returns SHZ_E_STATE -- never a table that differs between ranks.
  * bytes_recv: payload bytes this rank received (all rounds of this build). */
 int32_t shz_table_exchange_run(shz_table* t, shz_comm* c);
 int32_t shz_table_allgather(shz_table* t, shz_comm* c, uint64_t* bytes_recv);

@@ -737,8 +737,7 @@ extern "C" int32_t shz_table_finalize(shz_table* t) {
   shz_ctx* ctx = t->ctx;
   SHZ_HIP(ctx, hipSetDevice(ctx->device));
   if (t->broken) SHZ_FAIL(ctx, SHZ_E_STATE, "table lost rows in a failed finalize");
-  static const bool no_runs = [] { const char* e = getenv("SHZ_BUILD_RUNS"); return e && atoi(e) == 0; }();
-  if (t->n == 0 && (t->ns || !t->runs.empty()) && (!no_runs || !t->runs.empty())) {
+  if (t->n == 0 && (t->ns || !t->runs.empty())) {
     // the bulk path: an empty active segment takes the rows as sorted runs and one k-way merge
     bool packed = false;
     SHZ_TRY(seal_staged(t, nullptr, 0, &packed));
@@ -1206,8 +1205,7 @@ extern "C" int32_t shz_table_reserve(shz_table* t, uint64_t rows_hint, uint64_t 
   }
   t->job = j;
   j->th = std::thread(reserve_worker, j);
-  static const bool sync_alloc = [] { const char* e = getenv("SHZ_RESERVE_SYNC"); return e && atoi(e) != 0; }();
-  if (sync_alloc || (flags & SHZ_RESERVE_WAIT)) reserve_wait(t, RJ_SLAB);   // the allocations on the caller's clock, nothing beside them
+  if (flags & SHZ_RESERVE_WAIT) reserve_wait(t, RJ_SLAB);   // the allocations on the caller's clock, nothing beside them
   return SHZ_OK;
 }
 
@@ -2203,17 +2201,16 @@ extern "C" int32_t shz_table_allgather(shz_table* t, shz_comm* c, uint64_t* byte
   SHZ_HIP(ctx, hipSetDevice(ctx->device));
   if (shz_comm_ctx(c) != ctx) SHZ_FAIL(ctx, SHZ_E_INVALID, "allgather: table and communicator belong to different contexts");
   if (bytes_recv) *bytes_recv = 0;
-  static const bool force_cols = [] { const char* e = getenv("SHZ_ALLGATHER"); return e && !strcmp(e, "columns"); }();
   t->bs_sort = t->bs_exchange = t->bs_merge = t->bs_segments = 0.0;
   // 1) A first round with nothing sealed here yet: does ANY rank need the column path (its table holds rows, ids too
-  //    wide, SHZ_ALLGATHER=columns)?  Then the staged rows must stay staged -- on every rank -- to travel as columns.  The
+  //    wide)?  Then the staged rows must stay staged -- on every rank -- to travel as columns.  The
   //    block carries the staged rows' maxima, so the layout agreed in this round already covers them.
   double t0 = now_s();
   uint32_t mm[3] = {0u, 0u, 0xFFFFFFFFu};
   int32_t rc_local = SHZ_OK;
   if (t->ns) rc_local = staged_minmax(t, 0, t->ns, mm);
   const uint32_t lmax_sid = std::max(t->max_sid, mm[0]), lmax_off = std::max(t->max_off, mm[1]);
-  const bool local_general = t->n || !t->done.empty() || force_cols || (t->ns && bits_for(lmax_sid) + bits_for(lmax_off) > 32);
+  const bool local_general = t->n || !t->done.empty() || (t->ns && bits_for(lmax_sid) + bits_for(lmax_off) > 32);
   std::string err_local = ctx->err;
   gx_verdict v;
   SHZ_TRY(gx_round(t, c, true, local_general, rc_local != SHZ_OK, t->ns != 0, mm[0], mm[1], &v));

@@ -21,7 +21,6 @@ struct rccl_api {
   ncclResult_t (*CommInitRank)(ncclComm_t*, int, ncclUniqueId, int) = nullptr;
   ncclResult_t (*CommDestroy)(ncclComm_t) = nullptr;
   ncclResult_t (*AllGather)(const void*, void*, size_t, int, ncclComm_t, hipStream_t) = nullptr;
-  ncclResult_t (*Broadcast)(const void*, void*, size_t, int, int, ncclComm_t, hipStream_t) = nullptr;
   ncclResult_t (*Send)(const void*, size_t, int, int, ncclComm_t, hipStream_t) = nullptr;
   ncclResult_t (*Recv)(void*, size_t, int, int, ncclComm_t, hipStream_t) = nullptr;
   ncclResult_t (*GroupStart)() = nullptr;
@@ -44,13 +43,12 @@ static rccl_api* rccl() {
       *(void**)&api.CommInitRank = dlsym(api.lib, "ncclCommInitRank");
       *(void**)&api.CommDestroy = dlsym(api.lib, "ncclCommDestroy");
       *(void**)&api.AllGather = dlsym(api.lib, "ncclAllGather");
-      *(void**)&api.Broadcast = dlsym(api.lib, "ncclBroadcast");
       *(void**)&api.Send = dlsym(api.lib, "ncclSend");
       *(void**)&api.Recv = dlsym(api.lib, "ncclRecv");
       *(void**)&api.GroupStart = dlsym(api.lib, "ncclGroupStart");
       *(void**)&api.GroupEnd = dlsym(api.lib, "ncclGroupEnd");
       *(void**)&api.GetErrorString = dlsym(api.lib, "ncclGetErrorString");
-      if (!api.GetUniqueId || !api.CommInitRank || !api.CommDestroy || !api.AllGather || !api.Broadcast) {
+      if (!api.GetUniqueId || !api.CommInitRank || !api.CommDestroy || !api.AllGather) {
         dlclose(api.lib);
         api.lib = nullptr;
       }
@@ -335,10 +333,8 @@ int32_t shz_comm_allgather_lists_on(shz_comm* c, hipStream_t s, const std::vecto
 
 // Variable-size all-gather: rank r's block lands at d_recv + displ[r] on every rank.  Moved in pieces of <= 1 GB
 // (SURVEY 8e), each piece one RCCL group in which all ranks' transfers are in flight together, so that every pair of
-// GPUs uses its own xGMI link instead of a ring bound by one link.  Two exchange patterns, selected by SHZ_ALLGATHER:
-//   sendrecv (default)  every rank ncclSend-s its piece to each peer and ncclRecv-s each peer's piece: an explicit mesh
-//   bcast               one ncclBroadcast per root
-// Whatever fails inside a group, the group is closed before the error is returned.
+// GPUs uses its own xGMI link instead of a ring bound by one link: every rank ncclSend-s its piece to each peer and
+// ncclRecv-s each peer's piece, an explicit mesh.  Whatever fails inside a group, the group is closed before the error is returned.
 int32_t shz_comm_allgatherv_bytes(shz_comm* c, const void* d_send, void* d_recv, const uint64_t* counts,
                                   const uint64_t* displ) {
   shz_ctx* ctx = c->ctx;
@@ -347,31 +343,24 @@ int32_t shz_comm_allgatherv_bytes(shz_comm* c, const void* d_send, void* d_recv,
       return counts[p] ? hipMemcpyAsync((char*)d_recv + displ[p], sp, counts[p], hipMemcpyDefault, ctx->stream) : hipSuccess;
     });
   rccl_api* r = rccl();
-  static const bool use_bcast = [] { const char* e = getenv("SHZ_ALLGATHER"); return e && !strcmp(e, "bcast"); }();
   const uint64_t PIECE = 1ull << 30;
   uint64_t longest = 0;
   for (int p = 0; p < c->nranks; ++p) longest = std::max(longest, counts[p]);
   if (counts[c->rank])   // the rank's own block: a device copy
     SHZ_HIP(ctx, shz_memcpy(ctx, (char*)d_recv + displ[c->rank], d_send, counts[c->rank], hipMemcpyDeviceToDevice));
   if (c->nranks == 1) return SHZ_OK;
-  if (!r->GroupStart || !r->GroupEnd) SHZ_FAIL(ctx, SHZ_E_RCCL, "librccl.so lacks ncclGroupStart/End");
-  if (!use_bcast && (!r->Send || !r->Recv)) SHZ_FAIL(ctx, SHZ_E_RCCL, "librccl.so lacks ncclSend/ncclRecv");
+  if (!r->Send || !r->Recv || !r->GroupStart || !r->GroupEnd) SHZ_FAIL(ctx, SHZ_E_RCCL, "librccl.so lacks ncclSend/ncclRecv");
   for (uint64_t o = 0; o < longest; o += PIECE) {
     ncclResult_t bad = (ncclResult_t)0;
     const char* what = "";
     auto step = [&](ncclResult_t rc, const char* w) { if (rc != 0 && bad == 0) { bad = rc; what = w; } };
     step(r->GroupStart(), "ncclGroupStart");
     for (int p = 0; p < c->nranks && bad == 0; ++p) {
+      if (p == c->rank) continue;
       const uint64_t mine = counts[c->rank] > o ? std::min(PIECE, counts[c->rank] - o) : 0;
       const uint64_t theirs = counts[p] > o ? std::min(PIECE, counts[p] - o) : 0;
-      if (use_bcast) {
-        if (!theirs) continue;
-        char* dst = (char*)d_recv + displ[p] + o;
-        step(r->Broadcast(dst, dst, theirs, NCCL_U8, p, c->comm, ctx->stream), "ncclBroadcast");   // in place: root holds it
-      } else if (p != c->rank) {
-        if (mine) step(r->Send((const char*)d_send + o, mine, NCCL_U8, p, c->comm, ctx->stream), "ncclSend");
-        if (theirs) step(r->Recv((char*)d_recv + displ[p] + o, theirs, NCCL_U8, p, c->comm, ctx->stream), "ncclRecv");
-      }
+      if (mine) step(r->Send((const char*)d_send + o, mine, NCCL_U8, p, c->comm, ctx->stream), "ncclSend");
+      if (theirs) step(r->Recv((char*)d_recv + displ[p] + o, theirs, NCCL_U8, p, c->comm, ctx->stream), "ncclRecv");
     }
     step(r->GroupEnd(), "ncclGroupEnd");
     if (bad != 0) SHZ_FAIL(ctx, SHZ_E_RCCL, "%s failed: %s", what, r->GetErrorString ? r->GetErrorString(bad) : "rccl error");

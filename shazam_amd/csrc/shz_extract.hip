@@ -163,22 +163,10 @@ __device__ __forceinline__ void dft8f_tail(cplx b0, cplx b1, cplx b2, cplx b3, c
 // it is 6: two fewer per twiddled pair -- 32 of the 373 fp64 operations of a frame (passes 2 and 3: the four pairs of each
 // radix-8 butterfly, pass 4: two per radix-4 butterfly, the post-pass: one per bin pair).  The values differ from the
 // unfused form in the last bits, as any two correct transforms do; what decides ties is the reference's own arithmetic
-// (np_fft4096), not this kernel's.  STFT_FUSED=0 builds the unfused form (A/B).
-#ifndef STFT_FUSED
-#define STFT_FUSED 1
-#endif
-#ifndef STFT_TW3_DERIVE
-#define STFT_TW3_DERIVE 0   // 1: four of pass 3's seven twiddles as products of the other three (4 LDS reads less, 16 operations more): 3.806 -> 3.827 ms, off
-#endif
+// (np_fft4096), not this kernel's.  (The unfused form was measured against it and removed: DESIGN.md 3.1.)
 __device__ __forceinline__ void cmul_pm(cplx a, cplx w, cplx b, cplx& r, cplx& s) {   // r = a + w b, s = a - w b
-#if STFT_FUSED
   r = make_double2(fma(-w.y, b.y, fma(w.x, b.x, a.x)), fma(w.y, b.x, fma(w.x, b.y, a.y)));
   s = make_double2(fma(2.0, a.x, -r.x), fma(2.0, a.y, -r.y));
-#else
-  const cplx t = cmul(b, w);
-  r = cadd(a, t);
-  s = csub(a, t);
-#endif
 }
 // dft8f of v[0], w[0] v[1], ..., w[6] v[7]
 __device__ __forceinline__ void dft8f_tw(cplx* v, const cplx (&w)[7]) {
@@ -219,15 +207,9 @@ __device__ __forceinline__ void dft8f_win(const int (&pw)[8], const double2 (&ww
   for (int t = 0; t < 4; ++t) {
     const double x0 = (double)(short)(pw[t] & 0xFFFF), y0 = (double)(pw[t] >> 16);
     const double x4 = (double)(short)(pw[t + 4] & 0xFFFF), y4 = (double)(pw[t + 4] >> 16);
-#if STFT_FUSED
     const double px = x0 * ww[t].x, py = y0 * ww[t].y;
     b[t] = make_double2(fma(x4, ww[t + 4].x, px), fma(y4, ww[t + 4].y, py));
     b[t + 4] = make_double2(fma(-x4, ww[t + 4].x, px), fma(-y4, ww[t + 4].y, py));
-#else
-    const cplx v0 = make_double2(x0 * ww[t].x, y0 * ww[t].y), v4 = make_double2(x4 * ww[t + 4].x, y4 * ww[t + 4].y);
-    b[t] = cadd(v0, v4);
-    b[t + 4] = csub(v0, v4);
-#endif
   }
   dft8f_tail(b[0], b[1], b[2], b[3], b[4], b[5], b[6], b[7], v);
 }
@@ -356,14 +338,9 @@ __device__ __forceinline__ void stft_p3_rest(cplx (&v)[8], cplx* buf, const stft
   const int q0 = b3, q1 = (b3 ^ (9 << 4)) + (32 << 4), q2 = (b3 ^ (4 << 4)) + (64 << 4), q3 = (b3 ^ (13 << 4)) + (96 << 4);
   const int k = j & 63;
   cplx w[7];
-#if STFT_TW3_DERIVE
-  // three of the seven twiddles from the table, the others as their products (four LDS reads less, sixteen operations more)
-  w[0] = T.tw3[k]; w[1] = T.tw3[64 + k]; w[3] = T.tw3[3 * 64 + k];
-  w[2] = cmul(w[0], w[1]); w[4] = cmul(w[0], w[3]); w[5] = cmul(w[1], w[3]); w[6] = cmul(w[2], w[3]);
-#else
+  // (four of the seven as products of the other three -- 4 LDS reads less, 16 operations more -- was 3.806 -> 3.827 ms)
 #pragma unroll
   for (int t = 1; t < 8; ++t) w[t - 1] = T.tw3[(t - 1) * 64 + k];
-#endif
   dft8f_tw(v, w);
 #pragma unroll
   for (int r = 0; r < 8; ++r) lds_at(buf, ((r & 3) == 0 ? q0 : (r & 3) == 1 ? q1 : (r & 3) == 2 ? q2 : q3) + (r >> 2) * (128 << 4)) = v[r];
@@ -578,9 +555,7 @@ __global__ __launch_bounds__(256) void stft_np_kernel(stft_args a) {
 }
 
 #define P32_STRIDE 2064  // floats per fp32 row: 2049 bins padded so every row starts 64-byte aligned
-#ifndef STFT_OCC
 #define STFT_OCC 3
-#endif
 
 template <typename T>
 __global__ __launch_bounds__(256, STFT_OCC) void stft_psd_kernel(stft_args a) {
@@ -1321,21 +1296,14 @@ extern "C" uint32_t shz_frame_count(uint64_t n) {
 #define PK_SEG_SHORT 42  // ... and when a handful of workgroups is all there is: 2 blocks
 
 static const mask_geom MG_F64 = {(SHZ_NBINS + PK_SW - 1) / PK_SW, 4, 63, PK_SW};
-static mask_geom mg_f32(int nw) {
-  const uint32_t sw = 61u * nw - 17u;
-  return mask_geom{(SHZ_NBINS + sw - 1) / sw, (uint32_t)nw, 61u, sw};
-}
 // waves per peak_pick32 workgroup (slab = 61 nw - 17 bins).  Measured on 644,000 frames: 7 waves (5 slabs) 3.93 ms,
 // 6: 4.47, 4 (10 slabs): 2.65, 3: 2.56, 2 (20 slabs of 105 bins, 19 % halo): 2.05, 1: 2.22 -- small workgroups win
-// although they re-read more halo: the two barriers per 7 frames cost more than the columns
-static int p32_nw() {
-  static const int nw = [] {
-    const char* e = getenv("SHZ_PEAK_NW");
-    const int v = e ? atoi(e) : 2;
-    return (v >= 1 && v <= 7 && v != 5) ? v : 2;
-  }();
-  return nw;
-}
+// although they re-read more halo: the two barriers per 7 frames cost more than the columns.
+// Waves per SIMD: 4 (128 VGPRs): 2.12 ms vs 2.49 at 3.
+#define P32_NW 2
+#define P32_OCC 4
+#define P32_SW (61 * P32_NW - 17)
+static const mask_geom MG_F32 = {(SHZ_NBINS + P32_SW - 1) / P32_SW, P32_NW, 61, P32_SW};
 
 struct sub_batch {
   uint32_t c0, c1;        // clips [c0, c1)
@@ -1343,9 +1311,8 @@ struct sub_batch {
 };
 
 static int32_t plan_sub_batches(shz_ctx* ctx, const uint64_t* clip_off, uint32_t n_clips, uint64_t bytes_per_frame,
-                                std::vector<sub_batch>& out, uint64_t frame_cap = 0) {
+                                std::vector<sub_batch>& out) {
   uint64_t max_frames = ctx->ws_limit / bytes_per_frame;
-  if (frame_cap && frame_cap < max_frames) max_frames = frame_cap;
   if (max_frames > (1u << 20)) max_frames = 1u << 20;  // mask words, peaks < 2^32 (hash count checked per sub-batch)
   if (max_frames < 64) max_frames = 64;
   sub_batch cur{0, 0, 0};
@@ -1380,8 +1347,7 @@ struct sub_dev {
 // No host synchronisation: the host-side image of the tables is handed to `keep`, which the caller holds until the
 // call's final sync (a small pageable hipMemcpyAsync may or may not have staged its source when it returns).
 static int32_t upload_meta(shz_ctx* ctx, const uint64_t* clip_off, const sub_batch& sb, uint64_t pcm_base_off,
-                           uint32_t n_slabs, uint32_t wg_per_cu, sub_dev& sd, std::vector<std::vector<uint64_t>>& keep,
-                           int slot = SHZ_WS_META) {
+                           uint32_t n_slabs, uint32_t wg_per_cu, sub_dev& sd, std::vector<std::vector<uint64_t>>& keep) {
   const uint32_t nc = sb.c1 - sb.c0;
   sd.foff.assign(nc + 1, 0);
   std::vector<peak_seg> segs;
@@ -1409,7 +1375,7 @@ static int32_t upload_meta(shz_ctx* ctx, const uint64_t* clip_off, const sub_bat
   memcpy(&blob[2 * (uint64_t)nc], sd.foff.data(), (nc + 1) * 4);
   if (!segs.empty()) memcpy(&blob[2 * (uint64_t)nc + foff_words], segs.data(), segs.size() * sizeof(peak_seg));
   void* p0;
-  SHZ_TRY(shz_ws_reserve(ctx, slot, blob.size() * 8 + 64, &p0));
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_META, blob.size() * 8 + 64, &p0));
   sd.d_soff = (uint64_t*)p0;
   sd.d_len = sd.d_soff + nc;
   sd.d_foff = (uint32_t*)(sd.d_len + nc);
@@ -1421,7 +1387,7 @@ static int32_t upload_meta(shz_ctx* ctx, const uint64_t* clip_off, const sub_bat
 
 // PCM of the sub-batch on the device: either the caller's device buffer or a staged copy
 static int32_t stage_pcm(shz_ctx* ctx, const int16_t* pcm, const uint64_t* clip_off, const sub_batch& sb,
-                         uint32_t flags, const int16_t** d_pcm, uint64_t* base_off, int slot = SHZ_WS_PCM) {
+                         uint32_t flags, const int16_t** d_pcm, uint64_t* base_off) {
   const uint64_t s0 = clip_off[sb.c0], s1 = clip_off[sb.c1];
   if (flags & SHZ_PCM_DEVICE) {
     *d_pcm = pcm;
@@ -1429,7 +1395,7 @@ static int32_t stage_pcm(shz_ctx* ctx, const int16_t* pcm, const uint64_t* clip_
     return SHZ_OK;
   }
   void* p;
-  SHZ_TRY(shz_ws_reserve(ctx, slot, (s1 - s0) * 2 + 64, &p));
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_PCM, (s1 - s0) * 2 + 64, &p));
   if (s1 > s0) SHZ_HIP(ctx, shz_memcpy(ctx, p, pcm + s0, (s1 - s0) * 2, hipMemcpyHostToDevice));
   *d_pcm = (const int16_t*)p;
   *base_off = s0;
@@ -1462,36 +1428,32 @@ static stft_args make_stft_args(shz_ctx* ctx, const int16_t* d_pcm, const sub_de
   return a;
 }
 
-template <typename T>
-static int32_t launch_stft(shz_ctx* ctx, const stft_args& a, int wgs_override = 0, bool persistent = false) {
+// fp32 staging: stft_psd_kernel<float>
+static int32_t launch_stft(shz_ctx* ctx, const stft_args& a, bool persistent) {
   shz_prof_scope ps(ctx, 0);
-  static const int wgs_per_cu = [] {  // tuning knob: resident stft workgroups per CU (LDS allows 3)
-    const char* e = getenv("SHZ_STFT_WGS_PER_CU");
-    const int v = e ? atoi(e) : 3;
-    return v >= 1 && v <= 3 ? v : 3;
-  }();
-  uint32_t grid = (uint32_t)ctx->prop.multiProcessorCount * (wgs_override ? wgs_override : wgs_per_cu);
+  constexpr uint32_t WGS_PER_CU = 3, CHUNK_FRAMES = 32;   // resident workgroups per CU of the persistent grid (LDS allows 3)
+  uint32_t grid = (uint32_t)ctx->prop.multiProcessorCount * WGS_PER_CU;
   if (grid > a.total_frames) grid = a.total_frames;
   grid = (grid + 7) & ~7u;  // multiple of 8: see the XCD-aware frame map in the kernel
-  static const uint32_t chunk_frames = [] { const char* e = getenv("SHZ_STFT_CHUNK"); const int v = e ? atoi(e) : 32; return (uint32_t)(v > 0 ? v : 0); }();
   stft_args b = a;
   // One pipeline: workgroups of 32 consecutive frames (the halves neighbouring frames share stay in the workgroup's L1,
   // and CU slots turn over): 4.00 ms per 644,000 frames against 4.35 persistent (4: 4.53, 8: 4.22, 16: 4.05, 64: 4.03).
   // Two pipelines side by side prefer the persistent grid (6.48 vs 6.55 ms per step).
-  if (!persistent && chunk_frames && a.total_frames > (uint64_t)grid * chunk_frames) {
-    b.frames_per_wg = chunk_frames;
-    grid = (a.total_frames + chunk_frames - 1) / chunk_frames;
+  if (!persistent && a.total_frames > (uint64_t)grid * CHUNK_FRAMES) {
+    b.frames_per_wg = CHUNK_FRAMES;
+    grid = (a.total_frames + CHUNK_FRAMES - 1) / CHUNK_FRAMES;
   }
-  // fp64 staging follows numpy's arithmetic (stft_np_kernel); SHZ_F64_OWN_FFT=1: this file's own transform, as before round 4
-  static const bool own_f64 = [] { const char* e = getenv("SHZ_F64_OWN_FFT"); return e && atoi(e) != 0; }();
-  if (sizeof(T) == 8 && !own_f64) {
-    stft_args c = a;   // a clip or two (the per-clip fallback): one frame a workgroup, so that the whole chip takes part
-    c.frames_per_wg = a.total_frames >= 4u * NP_FRAMES_PER_WG * (uint32_t)ctx->prop.multiProcessorCount ? NP_FRAMES_PER_WG : 1u;
-    hipLaunchKernelGGL(stft_np_kernel, dim3((a.total_frames + c.frames_per_wg - 1) / c.frames_per_wg), dim3(256), 0, ctx->stream, c);
-    SHZ_HIP(ctx, hipGetLastError());
-    return SHZ_OK;
-  }
-  hipLaunchKernelGGL(stft_psd_kernel<T>, dim3(grid), dim3(256), 0, ctx->stream, b);
+  hipLaunchKernelGGL(stft_psd_kernel<float>, dim3(grid), dim3(256), 0, ctx->stream, b);
+  SHZ_HIP(ctx, hipGetLastError());
+  return SHZ_OK;
+}
+
+// fp64 staging follows numpy's arithmetic: stft_np_kernel
+static int32_t launch_stft_np(shz_ctx* ctx, const stft_args& a) {
+  shz_prof_scope ps(ctx, 0);
+  stft_args c = a;   // a clip or two (the per-clip fallback): one frame a workgroup, so that the whole chip takes part
+  c.frames_per_wg = a.total_frames >= 4u * NP_FRAMES_PER_WG * (uint32_t)ctx->prop.multiProcessorCount ? NP_FRAMES_PER_WG : 1u;
+  hipLaunchKernelGGL(stft_np_kernel, dim3((a.total_frames + c.frames_per_wg - 1) / c.frames_per_wg), dim3(256), 0, ctx->stream, c);
   SHZ_HIP(ctx, hipGetLastError());
   return SHZ_OK;
 }
@@ -1632,7 +1594,7 @@ extern "C" int32_t shz_stft_db(shz_ctx* ctx, const int16_t* pcm, const uint64_t*
     SHZ_TRY(upload_meta(ctx, clip_off, sb, base, MG_F64.n_slabs, 3, sd, keep));
     void *d_db, *d_tr;
     SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_DB, (uint64_t)sb.frames * DB_STRIDE * 8, &d_db));
-    SHZ_TRY(launch_stft<double>(ctx, make_stft_args(ctx, d_pcm, sd, nc, sb.frames, fs, d_db)));
+    SHZ_TRY(launch_stft_np(ctx, make_stft_args(ctx, d_pcm, sd, nc, sb.frames, fs, d_db)));
     SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_MISC3, (uint64_t)sb.frames * SHZ_NBINS * 8, &d_tr));
     uint64_t tr_pos = 0;
     for (uint32_t i = 0; i < nc; ++i) {
@@ -1801,16 +1763,6 @@ struct xparams {
 
 #define UND_CAP (1u << 20)
 
-template <int NW, int OCC, int AH = 1>
-static void launch_pick32(shz_ctx* ctx, const p32_args& pa, uint32_t n_segs) {
-  const uint32_t per_xcd = (n_segs + 7) >> 3;   // segments per XCD; 8 * per_xcd * n_slabs workgroups, see the kernel's work map
-  hipLaunchKernelGGL((peak_pick32_kernel<NW, OCC, AH>), dim3(8 * per_xcd * pa.n_slabs), dim3(64 * NW), 0, ctx->stream, pa);
-}
-static int p32_occ() {
-  static const int v = [] { const char* e = getenv("SHZ_PEAK_OCC"); const int x = e ? atoi(e) : 4; return x >= 3 && x <= 6 ? x : 4; }();
-  return v;
-}
-
 // what extract_enqueue leaves for extract_finish: where the read-back lands and where the entries are
 struct pass_tail {
   char* mp = nullptr;                      // pinned mailbox: xctl | offsets | (small host outputs) entries
@@ -1828,34 +1780,10 @@ static int32_t extract_enqueue(shz_ctx* ctx, const int16_t* pcm, const uint64_t*
                                uint16_t* peak_f, uint32_t* peak_t, uint32_t* key32, uint32_t* t1, uint64_t cap, bool stay,
                                pass_tail* pt) {
   const bool out_dev = (flags & SHZ_OUT_DEVICE) != 0 && !stay;
-  const mask_geom mg = xp.f32 ? mg_f32(p32_nw()) : MG_F64;
-  // Two-stream pipeline (fp32 staging; OFF unless SHZ_OVERLAP_SPLIT >= 2): the batch is cut into that many sub-batches
-  // and the STFT of sub-batch i+1 runs on a second stream beside peak picking and pair hashing of sub-batch i.
-  // stft_psd is VALU/LDS-bound with HBM idle, peak_pick32 waits on memory with the VALU idle, and at two STFT workgroups
-  // per CU both fit a CU together -- but measured on 1,000 x 30 s clips the step does not get shorter: 7.07 ms in
-  // sequence, 7.10 with 2 sub-batches, 8.05 with 4, 7.58 with 8, 9.03 with 16.  peak_pick32 hides its memory latency
-  // with many waves, and beside the STFT it gets one wave per SIMD (2.1 -> 4-6 ms while the STFT goes 4.4 -> 4.7).
-  static const int ov_split = [] { const char* e = getenv("SHZ_OVERLAP_SPLIT"); const int v = e ? atoi(e) : 0; return v < 0 ? 0 : v; }();
-  uint64_t frames_total = 0;
-  for (uint32_t c = 0; c < n_clips; ++c) frames_total += frames_hop(clip_off[c + 1] - clip_off[c], ctx->hop);
-  const bool want_overlap = xp.f32 && ov_split >= 2 && frames_total >= 65536;
+  const mask_geom mg = xp.f32 ? MG_F32 : MG_F64;
+  const uint64_t pw_bytes_per_frame = xp.f32 ? (uint64_t)P32_STRIDE * 4 : (uint64_t)DB_STRIDE * 8;
   std::vector<sub_batch> subs;
-  SHZ_TRY(plan_sub_batches(ctx, clip_off, n_clips, xp.f32 ? (uint64_t)P32_STRIDE * 4 : (uint64_t)DB_STRIDE * 8, subs,
-                           want_overlap ? (frames_total + ov_split - 1) / ov_split : 0));
-  const bool overlap = want_overlap && subs.size() >= 2;
-  if (overlap && !ctx->stream2) {
-    SHZ_HIP(ctx, hipStreamCreateWithFlags(&ctx->stream2, hipStreamNonBlocking));
-    for (int i = 0; i < 2; ++i) {
-      SHZ_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_stft[i], hipEventDisableTiming));
-      SHZ_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_free[i], hipEventDisableTiming));
-    }
-  }
-  if (overlap) {  // the second stream starts behind everything queued on the first one (the caller's PCM may still be in the making)
-    SHZ_HIP(ctx, hipEventRecord(ctx->ev_free[0], ctx->stream));
-    SHZ_HIP(ctx, hipStreamWaitEvent(ctx->stream2, ctx->ev_free[0], 0));
-  }
-  // whatever way this pass ends, the second stream is idle afterwards (workspace slots may be re-allocated by the next call)
-  struct s2_guard { shz_ctx* c; bool on; ~s2_guard() { if (on && c->stream2) (void)hipStreamSynchronize(c->stream2); } } s2g{ctx, overlap};
+  SHZ_TRY(plan_sub_batches(ctx, clip_off, n_clips, pw_bytes_per_frame, subs));
   void *p_ctl, *p_offs;
   const uint64_t fb_words = ((uint64_t)n_clips + 31) / 32;   // bitmap of clips that need fp64 staging, behind the control block
   // A small pass with host outputs keeps everything that is read back in ONE device block, laid out like the mailbox:
@@ -1896,59 +1824,20 @@ static int32_t extract_enqueue(shz_ctx* ctx, const int16_t* pcm, const uint64_t*
   double p_lo, p_hi;
   threshold_band(amp_min, &p_lo, &p_hi);
   std::vector<std::vector<uint64_t>> keep;
-  // stage A of a sub-batch: PCM + tables on the device, STFT.  With the pipeline on it is issued on the second stream,
-  // into the buffers of the sub-batch's parity, one sub-batch ahead of stage B.
-  struct sub_state { sub_dev sd; const int16_t* d_pcm; void* d_pw; stft_args sa; };
-  std::vector<sub_state> st(subs.size());
-  const uint64_t pw_bytes_per_frame = xp.f32 ? (uint64_t)P32_STRIDE * 4 : (uint64_t)DB_STRIDE * 8;
-  if (overlap) {  // every buffer of both parities at its final size before anything is in flight on two streams
-    uint64_t fmax = 0, smax = 0, cmax = 0;
-    for (const sub_batch& sb : subs) {
-      fmax = std::max<uint64_t>(fmax, sb.frames);
-      smax = std::max<uint64_t>(smax, clip_off[sb.c1] - clip_off[sb.c0]);
-      cmax = std::max<uint64_t>(cmax, sb.c1 - sb.c0);
-    }
-    void* dummy;
-    const uint64_t meta_bound = (3 * cmax + fmax / PK_SEG + cmax + 64) * 16;
-    for (int par = 0; par < 2; ++par) {
-      SHZ_TRY(shz_ws_reserve(ctx, par ? SHZ_WS_DB2 : SHZ_WS_DB, fmax * pw_bytes_per_frame, &dummy));
-      SHZ_TRY(shz_ws_reserve(ctx, par ? SHZ_WS_META_B : SHZ_WS_META, meta_bound, &dummy));
-      if (!(flags & SHZ_PCM_DEVICE)) SHZ_TRY(shz_ws_reserve(ctx, par ? SHZ_WS_PCM_B : SHZ_WS_PCM, smax * 2 + 64, &dummy));
-    }
-  }
-  auto stage_a = [&](size_t i) -> int32_t {
-    const sub_batch& sb = subs[i];
-    const int par = overlap ? (int)(i & 1) : 0;
-    hipStream_t main_stream = ctx->stream;
-    struct swap_guard { shz_ctx* c; hipStream_t keep; ~swap_guard() { c->stream = keep; } } sg{ctx, main_stream};
-    if (overlap) {
-      ctx->stream = ctx->stream2;   // copies, profiling events and the launch below go to the second stream
-      if (i >= 2) SHZ_HIP(ctx, hipStreamWaitEvent(ctx->stream2, ctx->ev_free[par], 0));   // stage B of sub-batch i-2 is done with these buffers
-    }
-    sub_state& x = st[i];
-    uint64_t base;
-    SHZ_TRY(stage_pcm(ctx, pcm, clip_off, sb, flags, &x.d_pcm, &base, par ? SHZ_WS_PCM_B : SHZ_WS_PCM));
-    SHZ_TRY(upload_meta(ctx, clip_off, sb, base, mg.n_slabs, xp.f32 ? 12 / mg.nw : 3, x.sd, keep, par ? SHZ_WS_META_B : SHZ_WS_META));
-    SHZ_TRY(shz_ws_reserve(ctx, par ? SHZ_WS_DB2 : SHZ_WS_DB, (uint64_t)sb.frames * pw_bytes_per_frame, &x.d_pw));
-    x.sa = make_stft_args(ctx, x.d_pcm, x.sd, sb.c1 - sb.c0, sb.frames, fs, x.d_pw);
-    static const int ov_wgs = [] { const char* e = getenv("SHZ_OVERLAP_STFT_WGS"); const int v = e ? atoi(e) : 2; return v >= 1 && v <= 3 ? v : 2; }();
-    if (xp.f32) SHZ_TRY(launch_stft<float>(ctx, x.sa, overlap ? ov_wgs : 0, xp.persistent_stft || overlap));
-    else SHZ_TRY(launch_stft<double>(ctx, x.sa, 0, xp.persistent_stft));
-    if (overlap) SHZ_HIP(ctx, hipEventRecord(ctx->ev_stft[par], ctx->stream2));
-    return SHZ_OK;
-  };
-  SHZ_TRY(stage_a(0));
   for (size_t si = 0; si < subs.size(); ++si) {
     const sub_batch& sb = subs[si];
-    if (overlap) {
-      if (si + 1 < subs.size()) SHZ_TRY(stage_a(si + 1));
-      SHZ_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_stft[si & 1], 0));
-    } else if (si > 0) {
-      SHZ_TRY(stage_a(si));
-    }
     const uint32_t nc = sb.c1 - sb.c0;
-    const sub_dev& sd = st[si].sd;
-    void* d_pw = st[si].d_pw;
+    // PCM + tables on the device, STFT
+    sub_dev sd;
+    const int16_t* d_pcm;
+    uint64_t base;
+    void* d_pw;
+    SHZ_TRY(stage_pcm(ctx, pcm, clip_off, sb, flags, &d_pcm, &base));
+    SHZ_TRY(upload_meta(ctx, clip_off, sb, base, mg.n_slabs, xp.f32 ? 12 / mg.nw : 3, sd, keep));
+    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_DB, (uint64_t)sb.frames * pw_bytes_per_frame, &d_pw));
+    const stft_args sa = make_stft_args(ctx, d_pcm, sd, nc, sb.frames, fs, d_pw);
+    if (xp.f32) SHZ_TRY(launch_stft(ctx, sa, xp.persistent_stft));
+    else SHZ_TRY(launch_stft_np(ctx, sa));
     const uint64_t n_words = (uint64_t)sb.frames * mg.n_slabs * mg.nw;
     if (n_words >= (1ull << 32)) SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "too many mask words in one sub-batch");
     const uint64_t cap_peaks64 = (uint64_t)sb.frames * xp.peaks_per_frame + 4096;
@@ -1962,9 +1851,7 @@ static int32_t extract_enqueue(shz_ctx* ctx, const int16_t* pcm, const uint64_t*
     SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_PEAK_T, (uint64_t)cap_peaks * 4 + 64, &pt));
     SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_PEAK_CLIP, (uint64_t)(nc + 1) * 4 + 64, &pc));
     SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_MISC1, (uint64_t)sb.frames * 4 + 64, &ft));
-    const stft_args& sa = st[si].sa;
-    static const bool no_small_tail = [] { const char* e = getenv("SHZ_NO_SMALL_TAIL"); return e && atoi(e) != 0; }();
-    const bool small_tail = want_hashes && !no_small_tail && n_words && n_words <= XT_MAX_WORDS && cap_peaks <= XT_MAX_PEAKS;
+    const bool small_tail = want_hashes && n_words && n_words <= XT_MAX_WORDS && cap_peaks <= XT_MAX_PEAKS;
     if (xp.f32) {
       SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_UND, (uint64_t)UND_CAP * 8, &d_und));
       if (si) hipLaunchKernelGGL(xctl_begin_sub_kernel, dim3(1), dim3(1), 0, ctx->stream, d_ctl);   // (the block starts zeroed)
@@ -1985,22 +1872,8 @@ static int32_t extract_enqueue(shz_ctx* ctx, const int16_t* pcm, const uint64_t*
         pa.ctl = d_ctl;
         pa.und_cap = UND_CAP;
         pa.frame_cnt = (uint32_t*)d_fcnt;
-        static const int p32_ahead = [] { const char* e = getenv("SHZ_PEAK_AHEAD"); return e ? atoi(e) : 1; }();
-        if (p32_ahead == 2 && mg.nw == 2) {   // experiment: 14 rows in flight per lane (3 or 4 waves per SIMD by SHZ_PEAK_OCC)
-          if (p32_occ() == 3) launch_pick32<2, 3, 2>(ctx, pa, sd.n_segs); else launch_pick32<2, 4, 2>(ctx, pa, sd.n_segs);
-        } else
-        switch (mg.nw * 10 + p32_occ()) {
-          case 13: launch_pick32<1, 3>(ctx, pa, sd.n_segs); break;
-          case 14: launch_pick32<1, 4>(ctx, pa, sd.n_segs); break;
-          case 23: launch_pick32<2, 3>(ctx, pa, sd.n_segs); break;
-          case 33: launch_pick32<3, 3>(ctx, pa, sd.n_segs); break;
-          case 34: launch_pick32<3, 4>(ctx, pa, sd.n_segs); break;
-          case 43: launch_pick32<4, 3>(ctx, pa, sd.n_segs); break;
-          case 44: launch_pick32<4, 4>(ctx, pa, sd.n_segs); break;
-          case 63: launch_pick32<6, 3>(ctx, pa, sd.n_segs); break;
-          case 73: launch_pick32<7, 3>(ctx, pa, sd.n_segs); break;
-          default: launch_pick32<2, 4>(ctx, pa, sd.n_segs); break;  // 128 VGPRs, 4 waves per SIMD: 2.12 ms vs 2.49 at 3
-        }
+        const uint32_t per_xcd = (sd.n_segs + 7) >> 3;   // segments per XCD; 8 * per_xcd * n_slabs workgroups, see the kernel's work map
+        hipLaunchKernelGGL((peak_pick32_kernel<P32_NW, P32_OCC>), dim3(8 * per_xcd * pa.n_slabs), dim3(64 * P32_NW), 0, ctx->stream, pa);
         SHZ_HIP(ctx, hipGetLastError());
       }
       {
@@ -2047,7 +1920,6 @@ static int32_t extract_enqueue(shz_ctx* ctx, const int16_t* pcm, const uint64_t*
                          (uint32_t)n_words, mg, (const uint32_t*)sd.d_foff, nc, sb.c0, d_ctl, cap_peaks, (uint32_t)UND_CAP, fan,
                          (uint16_t*)pf, (uint32_t*)pt, (uint32_t*)pc, (uint32_t*)d_hoff, (uint32_t*)o_a, (uint32_t*)o_b, o_cap, d_offs);
       SHZ_HIP(ctx, hipGetLastError());
-      if (overlap) SHZ_HIP(ctx, hipEventRecord(ctx->ev_free[si & 1], ctx->stream));
       continue;
     }
     {
@@ -2082,7 +1954,6 @@ static int32_t extract_enqueue(shz_ctx* ctx, const int16_t* pcm, const uint64_t*
                          (const uint16_t*)pf, (const uint32_t*)pt, cap_peaks, (uint16_t*)o_a, (uint32_t*)o_b, o_cap);
       hipLaunchKernelGGL(xctl_advance_kernel, dim3(1), dim3(1), 0, ctx->stream, d_ctl, cap_peaks, false);
       SHZ_HIP(ctx, hipGetLastError());
-      if (overlap) SHZ_HIP(ctx, hipEventRecord(ctx->ev_free[si & 1], ctx->stream));   // this parity's buffers are free again
       continue;
     }
     {
@@ -2107,7 +1978,6 @@ static int32_t extract_enqueue(shz_ctx* ctx, const int16_t* pcm, const uint64_t*
       hipLaunchKernelGGL(xctl_advance_kernel, dim3(1), dim3(1), 0, ctx->stream, d_ctl, cap_peaks, true);
       SHZ_HIP(ctx, hipGetLastError());
     }
-    if (overlap) SHZ_HIP(ctx, hipEventRecord(ctx->ev_free[si & 1], ctx->stream));   // this parity's buffers are free again
   }
   // The one read-back of the pass, into pinned memory: control block | per-clip offsets | for small host outputs the
   // entries themselves (they ride along instead of costing a second round trip once the count is known).
@@ -2133,7 +2003,6 @@ static int32_t extract_enqueue(shz_ctx* ctx, const int16_t* pcm, const uint64_t*
     SHZ_HIP(ctx, hipMemcpyAsync(pt->mp, d_ctl, sizeof(xctl), hipMemcpyDeviceToHost, ctx->stream));
     SHZ_HIP(ctx, hipMemcpyAsync(pt->mp + pt->off_offs, d_offs, (uint64_t)(n_clips + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
   }
-  s2g.on = false;   // the caller's extract_finish synchronises (both streams are joined by the events above)
   return SHZ_OK;
 }
 
@@ -2141,7 +2010,6 @@ static int32_t extract_enqueue(shz_ctx* ctx, const int16_t* pcm, const uint64_t*
 static int32_t extract_finish(shz_ctx* ctx, const pass_tail& pt, uint16_t* peak_f, uint32_t* peak_t, uint32_t* key32,
                               uint32_t* t1, uint64_t* offs_out, uint64_t cap, xctl* hctl) {
   SHZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (ctx->stream2) SHZ_HIP(ctx, hipStreamSynchronize(ctx->stream2));
   memcpy(hctl, pt.mp, sizeof(xctl));
   if (offs_out) memcpy(offs_out, pt.mp + pt.off_offs, (uint64_t)(pt.n_clips + 1) * 8);
   const uint64_t total = pt.want_hashes ? hctl->hash_base : hctl->peak_base;
@@ -2364,11 +2232,10 @@ static int32_t extract_driver(shz_ctx* ctx, const int16_t* pcm, const uint64_t* 
   if (n_clips == 0) return SHZ_OK;
   uint64_t frames = 0;
   for (uint32_t c = 0; c < n_clips; ++c) frames += frames_hop(clip_off[c + 1] - clip_off[c], ctx->hop);
-  static const bool force_f64 = [] { const char* e = getenv("SHZ_STAGE_F64"); return e && atoi(e) != 0; }();
   xparams xp;
   // fp32 staging needs the threshold to be a positive normal fp32 power well inside the range; amp_min < 0 also needs
   // the zero-plateau rule (peak_zero_plateau_kernel), which reads the fp64 array
-  xp.f32 = !force_f64 && !ctx->stage_f64 && amp_min >= 0.0 && amp_min <= 300.0;
+  xp.f32 = !ctx->stage_f64 && amp_min >= 0.0 && amp_min <= 300.0;
   xp.peaks_per_frame = 12;                                      // 4.6 per frame on noise and music-like input
   const uint64_t per_frame_out = want_hashes ? (uint64_t)xp.peaks_per_frame * (fan > 1 ? fan - 1 : 0) : xp.peaks_per_frame;
   xp.stage_cap = std::min<uint64_t>(cap, frames * per_frame_out + 4096);
@@ -2376,8 +2243,8 @@ static int32_t extract_driver(shz_ctx* ctx, const int16_t* pcm, const uint64_t* 
   // Dual pass: the clips are cut in two halves by frames and each half runs as a pass of its own -- the first on this
   // context, the second on a twin context (own stream, own workspace) whose entries are appended behind the first
   // half's afterwards.  Two independent pipelines fill each other's stalls (STFT is VALU/LDS-bound, peak picking waits
-  // on memory): 7.0 -> 6.48 ms on 1,000 x 30 s clips with the persistent STFT grid, which the stage-by-stage pipeline of
-  // SHZ_OVERLAP_SPLIT does not reach.
+  // on memory): 7.0 -> 6.48 ms on 1,000 x 30 s clips with the persistent STFT grid, which the stage-by-stage two-stream
+  // pipeline did not reach (removed).
   // Opt-in (SHZ_DUAL=1): with the STFT in short-lived workgroups one pipeline reaches 6.62 ms per 1,000 x 30 s clips and
   // two reach 6.48-6.50 -- 2 % for twice the workspace and kernel durations that no longer mean one kernel's own time.
   static const bool dual_on = [] { const char* e = getenv("SHZ_DUAL"); return e && atoi(e) != 0; }();
@@ -2419,7 +2286,6 @@ static int32_t extract_driver(shz_ctx* ctx, const int16_t* pcm, const uint64_t* 
     if (rc == SHZ_OK) rc = extract_finish(ctx, ta, peak_f, peak_t, key32, t1, offs, cap, &ha);
     if (rcb == SHZ_OK && rc == SHZ_OK) rcb = extract_finish(tw, tb, nullptr, nullptr, nullptr, nullptr, offs_b.data(), 0, &hb);
     (void)hipStreamSynchronize(tw->stream);   // whatever happened, nothing of the twin is in flight past this point
-    if (tw->stream2) (void)hipStreamSynchronize(tw->stream2);
     if (rcb != SHZ_OK && rc == SHZ_OK) { ctx->err = tw->err; rc = rcb; }
     SHZ_TRY(rc);
     ctx->st_und += ha.und_total + hb.und_total;
@@ -2612,8 +2478,7 @@ static int32_t extract_streamed(shz_ctx* ctx, const int16_t* pcm, const uint64_t
 static int32_t extract_any(shz_ctx* ctx, const int16_t* pcm, const uint64_t* clip_off, uint32_t n_clips, uint32_t fs,
                            double amp_min, uint32_t fan, uint32_t flags, bool want_hashes, uint16_t* peak_f, uint32_t* peak_t,
                            uint64_t* peak_off, uint32_t* key32, uint32_t* t1, uint64_t* hash_off, uint64_t cap, uint64_t* count) {
-  static const bool off = [] { const char* e = getenv("SHZ_UPLOAD_PIPELINE"); return e && atoi(e) == 0; }();
-  if (!off && ctx && pcm && clip_off && !(flags & SHZ_PCM_DEVICE) && n_clips >= 2) {
+  if (ctx && pcm && clip_off && !(flags & SHZ_PCM_DEVICE) && n_clips >= 2) {
     bool ok = true;
     for (uint32_t c = 0; c < n_clips && ok; ++c) ok = clip_off[c + 1] >= clip_off[c];
     if (ok && (clip_off[n_clips] - clip_off[0]) * 2 >= UP_MIN_BYTES)

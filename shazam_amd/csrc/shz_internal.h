@@ -70,9 +70,7 @@ enum {
   SHZ_WS_SORT_C,
   SHZ_WS_SORT_D,
   SHZ_WS_SORT_H,
-  SHZ_WS_DB2,        // second staged spectrogram: stft of sub-batch i+1 runs beside peak picking of sub-batch i
-  SHZ_WS_META_B,
-  SHZ_WS_PCM_B,
+  SHZ_WS_PCM_B,      // second PCM buffer of the chunked host upload (extract_streamed)
   SHZ_WS_CTL,        // device control block of the extraction pass (xctl)
   SHZ_WS_OFFS,       // per-clip output offsets (u64)
   SHZ_WS_UND,        // undecided cells of fp32 peak picking
@@ -128,11 +126,9 @@ struct shz_ctx {
   void* pin[2] = {nullptr, nullptr};
   hipEvent_t pin_ev[2] = {nullptr, nullptr};
   bool pin_busy[2] = {false, false};
-  hipStream_t stream2 = nullptr;   // second stream of the extraction pipeline (created on first use)
   hipStream_t stream_up = nullptr; // uploads of host PCM, chunk by chunk beside the kernels of the chunk before (created on first use)
   uint64_t st_up_chunks = 0, st_up_bytes = 0;   // chunks / bytes that went through that pipeline
   double st_up_copy_s = 0.0, st_up_wait_s = 0.0;   // seconds the upload thread spent copying / the main thread waited for a chunk
-  hipEvent_t ev_stft[2] = {nullptr, nullptr}, ev_free[2] = {nullptr, nullptr};
   shz_ctx* twin = nullptr;         // second pipeline of a dual extraction pass: own stream, own workspace (created on first use)
   hipEvent_t ev_twin = nullptr;
   void* mail = nullptr;         // shz_mailbox

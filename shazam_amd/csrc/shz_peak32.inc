@@ -72,24 +72,15 @@ struct p32_args {
 // finds a lane whose centre is within one step of its window maximum -- one wave-row in eight -- can work out there and
 // then whether that lane is alone (second-largest row maximum of the window, 20 max) or has to be listed.
 // The mask buffer is zeroed by the host; only non-zero words are written.
-// AH: groups of P32_PF rows whose loads are in flight ahead of the group being worked on (1: the next group's).  AH = 2
-// (SHZ_PEAK_AHEAD=2: 14 rows in flight per lane) was measured in round 4 on 644,000 frames: 2.13 ms -> 2.38 at 4 waves per
-// SIMD (the 7 extra registers spill) and 2.41 at 3 -- the kernel is bound by instruction issue, not by loads in flight.
-template <int NW, int OCC, int AH = 1>
+// The loads of the next group of P32_PF rows are in flight while a group is worked on.  Two groups ahead (14 rows in
+// flight per lane) was measured in round 4 on 644,000 frames: 2.13 ms -> 2.38 at 4 waves per SIMD (the 7 extra registers
+// spill) and 2.41 at 3 -- the kernel is bound by instruction issue, not by loads in flight.
+template <int NW, int OCC>
 __global__ __launch_bounds__(64 * NW, OCC) void peak_pick32_kernel(p32_args a) {
   constexpr int TH = 64 * NW, SW = 61 * NW - 17;
-#ifndef P32_UNMASKED_STORES
-#define P32_UNMASKED_STORES 1
-#endif
-#ifndef P32_UNMASKED_LOADS
-#define P32_UNMASKED_LOADS 1
-#endif
-#ifndef P32_ROW_POINTER
-#define P32_ROW_POINTER 0
-#endif
-  // lanes 61..63 of a wave hold no column of their own (their pair / quad maxima are the next wave's): with
-  // P32_UNMASKED_STORES they store into a dump column behind the row instead of being masked off row by row
-  constexpr int TW = P32_UNMASKED_STORES ? TH + 64 : TH;
+  // lanes 61..63 of a wave hold no column of their own (their pair / quad maxima are the next wave's): they store into a
+  // dump column behind the row instead of being masked off row by row
+  constexpr int TW = TH + 64;
   __shared__ float r2[P32_PF][TW];
   __shared__ float r4[P32_PF][TW];
   // XCD-aware work map (a speed choice only): workgroups b, b+8, b+16, ... share an XCD and its L2 (round-robin
@@ -113,9 +104,9 @@ __global__ __launch_bounds__(64 * NW, OCC) void peak_pick32_kernel(p32_args a) {
   const uint32_t coff = loads ? (uint32_t)col : 0u;
   const float* base = a.A + (uint64_t)sg.gframe0 * P32_STRIDE;   // uniform; rows are added as uniform offsets
   const int o = owns ? li - 10 : 0;                              // other lanes read columns 0..17: valid, ignored
-  const int wcol = lane < 61 ? li : TH + lane;                   // (P32_UNMASKED_STORES) where this lane stores its row values
+  const int wcol = lane < 61 ? li : TH + lane;                   // where this lane stores its row values
 
-  float S1[21], cur[21], prev[21], pre[AH][P32_PF];
+  float S1[21], cur[21], prev[21], pre[P32_PF];
   uint32_t qc[3] = {0, 0, 0}, qp[3] = {0, 0, 0};  // 3-bit row classes of the current / previous block, 7 rows per word
   float R1 = NEG;
 #pragma unroll
@@ -124,15 +115,10 @@ __global__ __launch_bounds__(64 * NW, OCC) void peak_pick32_kernel(p32_args a) {
   // existence asked once per group, lanes outside the spectrum loading a clamped column and dropping the value -- 10 of the
   // ~50 instructions of a row by the listing: 2.14 -> 2.22 ms on the same box.  The masked loads below stay.)
 #pragma unroll
-  for (int h = 0; h < AH; ++h)
-#pragma unroll
-    for (int p = 0; p < P32_PF; ++p) {
-      const int t = lo + h * P32_PF + p;
-      pre[h][p] = (loads && t < hi) ? (base + (uint64_t)t * P32_STRIDE)[coff] : NEG;
-    }
-#if P32_ROW_POINTER
-  const float* rowp = base + (uint64_t)(lo + AH * P32_PF) * P32_STRIDE;   // the next row the loop loads (behind the AH groups above)
-#endif
+  for (int p = 0; p < P32_PF; ++p) {
+    const int t = lo + p;
+    pre[p] = (loads && t < hi) ? (base + (uint64_t)t * P32_STRIDE)[coff] : NEG;
+  }
   for (int tb = lo; tb < end; tb += 21) {
     // which of the block's 21 centre frames tb - 10 + u lie inside the segment: one scalar word per block, one bit test per
     // row (the two compares and the mask logic per row were a third of the scalar instructions of this loop)
@@ -142,48 +128,21 @@ __global__ __launch_bounds__(64 * NW, OCC) void peak_pick32_kernel(p32_args a) {
     for (int g3 = 0; g3 < 21 / P32_PF; ++g3) {
       float v[P32_PF], mx[P32_PF];
 #pragma unroll
-      for (int i = 0; i < P32_PF; ++i) {
-        v[i] = pre[0][i];
-#pragma unroll
-        for (int h = 0; h + 1 < AH; ++h) pre[h][i] = pre[h + 1][i];
-      }
-#if P32_UNMASKED_LOADS == 2
-      // ... and ONE uniform test for the whole group of rows where all of them exist (all but a segment's last groups)
-      if (tb + P32_PF * (g3 + AH) + P32_PF <= hi) {
-#pragma unroll
-        for (int i = 0; i < P32_PF; ++i) {
-          const float x = (base + (uint64_t)(tb + P32_PF * (g3 + AH) + i) * P32_STRIDE)[coff];
-          pre[AH - 1][i] = loads ? x : NEG;
-        }
-      } else
-#endif
+      for (int i = 0; i < P32_PF; ++i) v[i] = pre[i];
 #pragma unroll
       for (int i = 0; i < P32_PF; ++i) {
-        const int tn = tb + P32_PF * (g3 + AH) + i;  // the frame AH groups ahead: keeps AH x P32_PF rows in flight
-#if P32_UNMASKED_LOADS
+        const int tn = tb + P32_PF * (g3 + 1) + i;  // the frame one group ahead: keeps P32_PF rows in flight
         // every lane loads (a lane outside the spectrum: column 0, dropped by a select) behind ONE uniform test
         float x = NEG;
-#if P32_ROW_POINTER
-        if (tn < hi) x = rowp[coff];     // rows are loaded in order: one uniform pointer that moves on by a row
-        rowp += P32_STRIDE;
-#else
         if (tn < hi) x = (base + (uint64_t)tn * P32_STRIDE)[coff];
-#endif
-        pre[AH - 1][i] = loads ? x : NEG;
-#else
-        pre[AH - 1][i] = (loads && tn < hi) ? (base + (uint64_t)tn * P32_STRIDE)[coff] : NEG;
-#endif
+        pre[i] = loads ? x : NEG;
       }
       __syncthreads();  // every wave is done reading the previous group's rows
 #pragma unroll
       for (int i = 0; i < P32_PF; ++i) {
         const float p2 = fmaxf(v[i], f_wave_shl1(v[i]));                 // columns li, li+1     (valid: lane < 63)
         const float p4 = fmaxf(p2, f_wave_shl1(f_wave_shl1(p2)));        // columns li .. li+3   (valid: lane < 61)
-#if P32_UNMASKED_STORES
         r2[i][wcol] = p2; r4[i][wcol] = p4;
-#else
-        if (lane < 61) { r2[i][li] = p2; r4[i][li] = p4; }
-#endif
       }
       __syncthreads();
 #pragma unroll

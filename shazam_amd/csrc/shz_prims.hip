@@ -886,10 +886,8 @@ static void seg_pass(shz_ctx* ctx, int wb, uint32_t nblocks, const uint32_t* kin
 // digit leave as one run, 128 bytes on average instead of 64 (the scatter is bound by its partial-line writes)
 // (16,384: 64 keys per thread in registers, 0.185 -> 0.222 ms/query at 1M songs)
 uint32_t shz_seg_tile(uint64_t n) {
-  static const int tile_env = [] { const char* e = getenv("SHZ_SEG_TILE"); return e ? atoi(e) : 0; }();
   // (fewer than ~2,000 large blocks leave CUs idle: one 10 s query at 1M songs 0.393 -> 0.399 ms)
-  const bool big = tile_env ? tile_env >= 8192 : n >= (1ull << 24);
-  return big ? 8192u : 4096u;
+  return n >= (1ull << 24) ? 8192u : 4096u;
 }
 
 void shz_seg_blocks(shz_seg_plan* sp, uint32_t tile) {

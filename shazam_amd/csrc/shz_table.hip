@@ -1088,9 +1088,7 @@ __global__ __launch_bounds__(256) void m_topn_final_kernel(const uint64_t* __res
 #define VT_MAX_DBITS 12
 #define VT_MAX_DSPLIT 8        // delta bits above those a sweep may split by (vt_fold_kernel): tracks of up to 2^20 frames
 #define VT_EMPTY 0xFFFFFFFFu
-#ifndef VT_ORDERED_BITS
 #define VT_ORDERED_BITS 16     // upper bits of a vote the radix passes order (two passes of 8)
-#endif
 #define VT_ONE_WG_MAX 32768     // votes of a single query that one workgroup folds without any radix pass
 
 struct vt_plan {
@@ -1100,7 +1098,7 @@ struct vt_plan {
   int g_lo;                    // lowest bit the radix passes ordered: tiles are cut where bits >= g_lo change
   int dbits, sb;               // layout of a vote: flag | delta (dbits) | song id (sb) | query
   uint32_t tile;               // nominal votes per tile
-  uint32_t flush;              // votes a batch of vt_stream_kernel holds before it may end at a group border
+  uint32_t flush;              // votes a batch of vt_stream2_kernel holds before it may end at a group border
 };
 
 __device__ __forceinline__ uint32_t vt_query_of_tile(const vt_plan& pl, uint32_t g) {
@@ -1203,7 +1201,7 @@ __device__ __forceinline__ void vt_slots(uint32_t* key1, uint32_t* key2, const u
   };
   // The first rounds are straight-line code: at the fill levels the callers keep, two or three rounds settle a row, and
   // outside a loop the lanes' states (pending, fresh) stay lane masks in scalar registers -- as loop-carried values of a
-  // divergent loop they were re-materialised per round (35 VALU instructions per round; vt_stream_kernel is bound by VALU
+  // divergent loop they were re-materialised per round (35 VALU instructions per round; round 3's fold was bound by VALU
   // issue).  Whatever is still pending goes round a wave-uniform loop.
   constexpr uint32_t STRAIGHT = 3;
   round();                                   // (probe_limit >= 1)
@@ -1474,167 +1472,13 @@ __global__ __launch_bounds__(VT_THREADS) void vt_fold_kernel(const uint32_t* __r
 static_assert(VW_LIMIT1 + 64 < VW_S1, "a probe must find a free slot");
 static_assert(VW_FLUSH + 64 <= VT_TILE, "a range handed to vt_fold_kernel has less than VT_TILE votes before its last group");
 
-template <int VW_B2, bool QR = true>
-__global__ __launch_bounds__(64) void vt_stream_kernel(const uint32_t* __restrict__ k, const uint32_t* __restrict__ tile_start,
-                                                       vt_plan pl, uint32_t topn, uint64_t* __restrict__ c_pack,
-                                                       uint32_t* __restrict__ c_delta, uint32_t* __restrict__ c_dedup,
-                                                       uint32_t* __restrict__ n_heavy, uint2* __restrict__ heavy,
-                                                       uint32_t* __restrict__ heavy_q, uint32_t heavy_cap,
-                                                       uint32_t probe_limit, uint32_t* __restrict__ err) {
-  constexpr int VW_S2 = 1 << VW_B2;
-  constexpr uint32_t VW_LIMIT2 = VW_S2 - 68;        // + one row of new songs stays below VW_S2
-  static_assert(VW_LIMIT2 + 64 < (uint32_t)VW_S2 && VW_LIMIT1 + 64 < VW_S1, "a probe must find a free slot in either table");
-  __shared__ uint4 t1[VW_S1 / 2];                    // key1[VW_S1] | cnt[VW_S1]
-  __shared__ uint4 t2[VW_S2];                        // key2[VW_S2] | ded[VW_S2] | best[VW_S2] (8 bytes each)
-  uint32_t* const key1 = (uint32_t*)t1;
-  uint32_t* const cnt = key1 + VW_S1;
-  uint32_t* const key2 = (uint32_t*)t2;
-  uint32_t* const ded = key2 + VW_S2;
-  unsigned long long* const best = (unsigned long long*)(ded + VW_S2);
-  const uint32_t g = blockIdx.x, lane = threadIdx.x;
-  const uint32_t a = tile_start[g], b = tile_start[g + 1];
-  const uint32_t dmask = (1u << pl.dbits) - 1u, smask = (pl.sb >= 32 ? ~0u : (1u << pl.sb) - 1u);
-  uint64_t cp = 0;                                   // lane n < topn: candidate n of this tile
-  uint32_t cdl = 0, cdd = 0;
-  auto clear = [&]() {
-#pragma unroll
-    for (int i = 0; i < VW_S1 / 4 / 64; ++i) t1[lane + 64 * i] = make_uint4(VT_EMPTY, VT_EMPTY, VT_EMPTY, VT_EMPTY);
-#pragma unroll
-    for (int i = 0; i < VW_S1 / 4 / 64; ++i) t1[VW_S1 / 4 + lane + 64 * i] = make_uint4(0, 0, 0, 0);
-#pragma unroll
-    for (int i = 0; i < (VW_S2 + 63) / 64; ++i) {     // key2 (VW_S2 / 4 vectors of EMPTY), then ded and best (zero)
-      const uint32_t e = lane + 64 * i;
-      if (e < VW_S2) t2[e] = e < VW_S2 / 4 ? make_uint4(VT_EMPTY, VT_EMPTY, VT_EMPTY, VT_EMPTY) : make_uint4(0, 0, 0, 0);
-    }
-  };
-  if (a < b) {
-    clear();
-    uint32_t n1 = 0, n2 = 0, batch_start = a, batch_votes = 0, last_hi = 0xFFFFFFFFu;   // wave-uniform
-    bool skip = false;                               // the current batch goes to vt_fold_kernel: look for its end
-    auto insert = [&](bool act, uint32_t v) {        // whole wave
-      const uint32_t x1[1] = {v >> 1}, x2[1] = {(v >> 1) >> pl.dbits};
-      uint32_t s1[1], s2[1];
-      bool f1[1], f2[1];
-      const bool ok[1] = {act};
-      vt_slots<1, VW_B1, VW_B2>(key1, key2, x1, x2, ok, s1, s2, f1, f2, probe_limit, err);
-      if (act) {
-        const uint32_t c = atomicAdd(&cnt[s1[0]], 1u);
-        atomicMax(&best[s2[0]], ((unsigned long long)(c + 1u) << 32) | (dmask - (x1[0] & dmask)));
-        if (v & 1u) atomicAdd(&ded[s2[0]], 1u);
-      }
-      n2 += (uint32_t)__popcll(__ballot(f2[0]));
-      n1 += (uint32_t)__popcll(__ballot(f1[0]));
-      batch_votes += (uint32_t)__popcll(__ballot(act));
-    };
-    auto flush = [&]() {                             // the batch's songs into the running top-n; tables emptied
-      if (n2 != 0) {
-        constexpr int CE = VW_S2 / 64;               // every slot of table 2: CE per lane
-        uint64_t pk[CE];
-#pragma unroll
-        for (int u = 0; u < CE; ++u) {
-          const uint32_t s = lane + 64 * u, kk = key2[s];
-          pk[u] = kk == VT_EMPTY ? 0ull : ((best[s] >> 32) << 32) | (0xFFFFFFFFu - (kk & smask));
-        }
-        // the usual batch changes nothing: its best song ranks below the n-th candidate (noise votes count 1 each, and
-        // the votes arrive by ascending song id, so among equal counts the earlier batches win) -- one maximum says so
-        // (a song lies in one group, hence in one batch: the candidates are other songs, packs are unique)
-        if (QR) {
-          uint64_t bm = pk[0];
-#pragma unroll
-          for (int u = 1; u < CE; ++u) bm = pk[u] > bm ? pk[u] : bm;
-          const uint32_t bh = vt_wave_max((uint32_t)(bm >> 32));
-          const uint32_t bl = vt_wave_max((uint32_t)(bm >> 32) == bh ? (uint32_t)bm : 0u);
-          const uint32_t nth_hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(cp >> 32), (int)topn - 1);
-          const uint32_t nth_lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)cp, (int)topn - 1);
-          if ((((uint64_t)bh << 32) | bl) < (((uint64_t)nth_hi << 32) | nth_lo)) { clear(); n1 = n2 = 0; return; }
-        }
-        uint64_t prev = ~0ull, ncp = 0;
-        uint32_t ncdl = 0, ncdd = 0;
-        for (uint32_t n = 0; n < topn; ++n) {
-          uint64_t m = cp < prev ? cp : 0ull;        // (lanes >= topn hold 0)
-          int mu = -1;                               // entry of m, -1: the old candidate
-#pragma unroll
-          for (int u = 0; u < CE; ++u)
-            if (pk[u] < prev && pk[u] > m) { m = pk[u]; mu = u; }
-          const uint32_t cmax = vt_wave_max((uint32_t)(m >> 32));
-          const uint32_t lo = vt_wave_max((uint32_t)(m >> 32) == cmax ? (uint32_t)m : 0u);
-          const uint64_t w = ((uint64_t)cmax << 32) | lo;
-          if (w == 0) break;                         // uniform: nothing ranks below prev
-          const int win = __ffsll((long long)__ballot(m == w)) - 1;   // one lane: packs are unique
-          uint32_t wdl = cdl, wdd = cdd;
-          if ((int)lane == win && mu >= 0) { const uint32_t s = lane + 64 * mu; wdl = dmask - ((uint32_t)best[s] & dmask); wdd = ded[s]; }
-          wdl = (uint32_t)__shfl((int)wdl, win, 64);
-          wdd = (uint32_t)__shfl((int)wdd, win, 64);
-          if (lane == n) { ncp = w; ncdl = wdl; ncdd = wdd; }
-          prev = w;
-        }
-        cp = ncp; cdl = ncdl; cdd = ncdd;
-      }
-      clear();
-      n1 = n2 = 0;
-    };
-    auto hand_over = [&](uint32_t e) {               // [batch_start, e) to vt_fold_kernel
-      if (lane == 0) {
-        const uint32_t idx = atomicAdd(n_heavy, 1u);
-        if (idx < heavy_cap) { heavy[idx] = make_uint2(batch_start, e); heavy_q[idx] = vt_query_of_tile(pl, g); }
-        else atomicOr(err, 4u);                      // no room in the list: the range's votes would be lost -> the pass is repeated
-      }
-    };
-    uint32_t r0, r1, r2, r3;                         // the next four rows of votes: loads in flight
-    { uint32_t i = a + lane; r0 = i < b ? k[i] : 0u; i += 64; r1 = i < b ? k[i] : 0u; i += 64; r2 = i < b ? k[i] : 0u; i += 64; r3 = i < b ? k[i] : 0u; }
-    for (uint32_t base = a; base < b; base += 64) {
-      const uint32_t v = r0;
-      r0 = r1; r1 = r2; r2 = r3;
-      { const uint32_t i = base + 256 + lane; r3 = i < b ? k[i] : 0u; }
-      const bool valid = base + lane < b;
-      const uint32_t hi = v >> pl.g_lo;
-      // the neighbour lane's upper bits (lane 0: the previous row's last) -- a DPP wave shift, not a trip through the LDS crossbar
-      const uint32_t hp = (uint32_t)__builtin_amdgcn_update_dpp((int)last_hi, (int)hi, 0x138 /* wave_shr:1 */, 0xF, 0xF, false);
-      const unsigned long long mg = __ballot(valid && hi != hp);     // lanes that open a group
-      last_hi = (uint32_t)__builtin_amdgcn_readlane((int)hi, 63);    // (the last row is the only partial one)
-      uint32_t lo = 0;                               // first lane of the row not dealt with yet
-      while (lo < 64) {                              // uniform
-        const unsigned long long rest = mg & ~((1ull << lo) - 1ull);
-        if (skip) {
-          if (!rest) break;
-          lo = (uint32_t)__ffsll((long long)rest) - 1;
-          hand_over(base + lo);
-          skip = false;
-          batch_start = base + lo;
-          batch_votes = 0;
-          continue;
-        }
-        uint32_t cut = 64;                           // the batch may end at the next group border once it is large enough
-        if (batch_votes >= pl.flush && rest) cut = (uint32_t)__ffsll((long long)rest) - 1;
-        if (cut == lo) { flush(); batch_start = base + lo; batch_votes = 0; continue; }
-        insert(valid && lane >= lo && lane < cut, v);
-        const bool over = n1 > VW_LIMIT1 || n2 > VW_LIMIT2;
-        if (over) {
-          clear();
-          n1 = n2 = 0;
-          if (cut < 64) { hand_over(base + cut); batch_start = base + cut; batch_votes = 0; }
-          else skip = true;
-        } else if (cut < 64) { flush(); batch_start = base + cut; batch_votes = 0; }
-        lo = cut;
-      }
-    }
-    if (skip) hand_over(b); else flush();
-  }
-  if (lane < topn) {
-    const uint64_t o = (uint64_t)g * topn + lane;
-    c_pack[o] = cp;
-    c_delta[o] = cdl;
-    c_dedup[o] = cdd;
-  }
-}
-
-// ---- the same tile, filter first (round 4).  What decides a query's top-n are the (song, delta) pairs that many votes
+// ---- filter first (round 4).  What decides a query's top-n are the (song, delta) pairs that many votes
 // agree on; of the ~140 votes of a batch (a group of 16 songs against 1M songs: ~9 votes a song over ~1,000 deltas) nearly
-// all are alone with their pair or share it with one other.  vt_stream_kernel pays two compare-and-swap probe chains, a
-// 64-bit maximum and a table scan for every one of them, and is bound by instruction issue (171 vector + 211 scalar
-// instructions per row of 64 votes, both ports ~70 % busy: profiles/r03f_pmc_match.json).  Here a batch first goes through
-// a KEYLESS COUNTING FILTER: table 1's 4 KB as 4,096 eight-bit counters, one ds_add_rtn per vote on the counter its
-// (song | delta) hashes to.  A counter is an upper bound of the count of every pair that maps to it -- never below -- so
+// all are alone with their pair or share it with one other.  Round 3's fold (vt_stream_kernel, since removed) paid two
+// compare-and-swap probe chains, a 64-bit maximum and a table scan for every one of them, and was bound by instruction
+// issue (171 vector + 211 scalar instructions per row of 64 votes, both ports ~70 % busy: profiles/r03f_pmc_match.json).
+// Here a batch first goes through a KEYLESS COUNTING FILTER: table 1's 4 KB as 4,096 eight-bit counters, one ds_add_rtn
+// per vote on the counter its (song | delta) hashes to.  A counter is an upper bound of the count of every pair that maps to it -- never below -- so
 // "no counter of the batch reached the bar" proves that no pair of the batch did: the batch is finished, with no probe
 // loop, no key compare, no per-lane state (the test is one compare per row, OR-ed into a scalar mask).
 // The bar is the larger of the tile's own n-th candidate and the QUERY's bar: every tile publishes its n-th candidate
@@ -1642,7 +1486,7 @@ __global__ __launch_bounds__(64) void vt_stream_kernel(const uint32_t* __restric
 // all of them -- a song below it is not in the query's top-n whatever its tile's list holds.  So a tile does not climb from
 // zero: after a query's first tiles the bar stands at the noise ceiling.  A batch that MAY reach it (no bar yet; a counter
 // got there -- by a real pair or by pairs sharing a counter; the filter says nothing about ties, so "reached" includes
-// "equalled") is read again and folded by the exact code of vt_stream_kernel: every candidate's count, smallest delta
+// "equalled") is read again and folded by the exact code of round 3's fold: every candidate's count, smallest delta
 // and row sum come from there, so the results are the same arrays (which tile reports a song, and whether a tile reports
 // songs that end below the final top-n, depends on timing; the ranking of vt_rank_kernel does not).
 __device__ __forceinline__ uint64_t vt_wave_max64(uint64_t v) {
@@ -1651,9 +1495,7 @@ __device__ __forceinline__ uint64_t vt_wave_max64(uint64_t v) {
   return ((uint64_t)h << 32) | l;
 }
 // counter of a (song | delta) key, 12 bits: the multiply is 24-bit (full rate); the bits above 24 are folded in first
-#ifndef VW_SEED_TILES
 #define VW_SEED_TILES 64u      // tiles at the head of a query that fold undecided batches on the spot (vt_stream2_kernel)
-#endif
 #define VW_FILTER_MAX 200u     // a counter that gets here sends its batch to the exact fold whatever the bar (8 bits wrap at 256)
 __device__ __forceinline__ uint32_t vw_hash_filter(uint32_t x) { return (__umul24((x ^ (x >> 13)) & 0xFFFFFFu, 0x9E3779u) >> 11) & 4095u; }
 static_assert(VW_S1 * 8 == 4096, "table 1 (keys + counts) is 4 KB: 4,096 eight-bit counters");
@@ -1706,7 +1548,7 @@ __global__ __launch_bounds__(64) void vt_stream2_kernel(const uint32_t* __restri
     clear_filter();
     clear2();                                        // (table 2 is left empty by whoever used it)
     uint32_t n1 = 0, n2 = 0;                         // wave-uniform (exact fold only)
-    // ---------------- the exact fold of one batch [s, e): vt_stream_kernel's, on a range that is known
+    // ---------------- the exact fold of one batch [s, e): round 3's, on a range that is known
     auto insert = [&](bool act, uint32_t v) {        // whole wave
       const uint32_t x1[1] = {v >> 1}, x2[1] = {(v >> 1) >> pl.dbits};
       uint32_t s1[1], s2[1];
@@ -1894,10 +1736,7 @@ __global__ __launch_bounds__(64) void vt_stream2_kernel(const uint32_t* __restri
     // the next VW_AHEAD rows of votes: loads in flight.  The wave waits for memory, not for issue slots (SQ counters: 90 % of
     // its cycles) -- 26 waves a CU with 4 rows each in flight are 6.8 MB on the whole chip, what ~3 us of loaded latency
     // turn into ~2 TB/s at best
-#ifndef VW_AHEAD_N
-#define VW_AHEAD_N 8
-#endif
-    constexpr int VW_AHEAD = VW_AHEAD_N;
+    constexpr int VW_AHEAD = 8;
     uint32_t rr[VW_AHEAD];
 #pragma unroll
     for (int j = 0; j < VW_AHEAD; ++j) { const uint32_t i = a + lane + 64u * j; rr[j] = i < b ? k[i] : 0u; }
@@ -1919,7 +1758,7 @@ __global__ __launch_bounds__(64) void vt_stream2_kernel(const uint32_t* __restri
         last_hi = (uint32_t)__builtin_amdgcn_readlane((int)hi, 63);  // (the last row is the only partial one)
         if (base == a) set_thr((uint32_t)__builtin_amdgcn_readfirstlane((int)hi));
         if (mg == 0ull || batch_votes < pl.flush) {                  // no border in the row, or none that may end the batch (it is
-          // still below its flush size when the row begins: the whole row joins it, as in vt_stream_kernel): one piece
+          // still below its flush size when the row begins: the whole row joins it, as in round 3's fold): one piece
           if (base + 64u <= b) {                                     // a whole row: issued now, looked at with the next row
             const uint32_t h = vw_hash_filter(v >> 1), sh = (h & 3u) << 3;
             const uint32_t old = atomicAdd(&filt[h >> 2], 1u << sh);
@@ -2126,20 +1965,17 @@ static void vt_make_plan(const uint64_t* counts, uint32_t nqp, const m_bits& mbp
   // 2,048, 0.141 at 4,096, 0.138 at 8,192, 0.136 at 16,384 -- but the chip wants ~2 rounds of tiles (256 CUs x 26 waves).
   // (Those were the fold of mid round 4; with deferred batches and batches of 128: 0.1365 at 2,048, 0.1348 at 4,096, 0.132 at
   // 8,192, 0.1348 at 16,384, 0.1418 at 32,768: the cap is 8,192.)
-  static const uint32_t chunk_env = [] { const char* e = getenv("SHZ_VW_CHUNK"); const int v = e ? atoi(e) : 0; return v >= 1024 && v <= 65536 ? (uint32_t)v : 0u; }();
   uint64_t all_votes = 0;
   for (uint32_t i = 0; i < nqp; ++i) all_votes += counts[i];
   uint32_t chunk = VW_CHUNK;
   while (chunk < 8192u && all_votes / (2ull * chunk) >= 13312ull) chunk *= 2;
   // (one query of 8.9 M votes, fewer tiles than wave slots: 1,024 votes a tile 0.379 ms, 2,048: 0.354, 4,096: 0.349 -- smaller tiles
   // do not shorten the pass, every tile pays its start)
-  if (chunk_env) chunk = chunk_env;
   pl.tile = chunk;
-  static const uint32_t flush_env = [] { const char* e = getenv("SHZ_VW_FLUSH"); const int v = e ? atoi(e) : 0; return v >= 16 && v <= 256 ? (uint32_t)v : 0u; }();
   // votes a batch holds before it may end at a group border: 64 where tiles are small (one query: more, smaller batches let
   // the bar settle sooner: 0.281 ms against 0.300 with 128), 128 in the large passes of a batch of queries (fewer batch ends
   // to pay for: 0.1365 -> 0.1339 ms a query at 1M songs; 192: the same)
-  pl.flush = flush_env ? flush_env : (chunk >= 8192 ? 2 * VW_FLUSH : VW_FLUSH);
+  pl.flush = chunk >= 8192 ? 2 * VW_FLUSH : VW_FLUSH;
   pl.qv[0] = pl.tb[0] = sp.qv[0] = sp.bq[0] = 0;
   for (uint32_t i = 0; i < nqp; ++i) {
     const uint64_t c = counts[i];
@@ -2179,17 +2015,11 @@ static int32_t vt_run_pass(shz_ctx* ctx, uint32_t* k32, uint32_t* k32_alt, uint6
   uint32_t* n_heavy = tile_start + nt + 1;
   uint2* heavy = (uint2*)(tile_start + ((nt + 2 + 1) & ~1u));   // 8-byte aligned
   uint32_t* heavy_q = (uint32_t*)(heavy + hcap);
-  static const int vt_fast = [] { const char* e = getenv("SHZ_VT_FAST"); return e ? atoi(e) : 1; }();   // 0: the fold of round 3 (A/B)
-  static const bool no_qr = [] { const char* e = getenv("SHZ_VT_NO_REJECT"); return e && atoi(e) != 0; }();
-  unsigned long long* d_qbar = nullptr;   // the bar of every query of the pass (its tiles' n-th candidates, atomicMax); zeroed by vt_bounds_kernel
-  if (vt_fast && !no_qr) {
-    void* p;
-    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_VT6, 8ull * (VT_MAXQ + 1), &p));
-    d_qbar = (unsigned long long*)p;
-  }
-  static const bool keep_bar = [] { const char* e = getenv("SHZ_VT_KEEPBAR"); return e && atoi(e) != 0; }();   // EXPERIMENT
+  void* qb;   // the bar of every query of the pass (its tiles' n-th candidates, atomicMax); zeroed by vt_bounds_kernel
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_VT6, 8ull * (VT_MAXQ + 1), &qb));
+  unsigned long long* d_qbar = (unsigned long long*)qb;
   hipLaunchKernelGGL(vt_bounds_kernel, dim3(nblk(std::max<uint64_t>(((uint64_t)nt + 1) * 64, (uint64_t)VT_MAXQ + 1))), dim3(256), 0, ctx->stream, ks, pl, tile_start,
-                     n_heavy, keep_bar ? nullptr : d_qbar);
+                     n_heavy, d_qbar);
   // songs a batch is expected to hold: the 2^slb ids of a group + the ids that fill 64 votes
   const int slb_ = pl.g_lo - 1 - mbp.dbits;
   const double per_song = std::max(1.0, (double)pp / nqp / std::max<uint32_t>(max_sid, 1u));
@@ -2203,22 +2033,12 @@ static int32_t vt_run_pass(shz_ctx* ctx, uint32_t* k32, uint32_t* k32_alt, uint6
     d_stats = (unsigned long long*)p;
     SHZ_HIP(ctx, hipMemsetAsync(d_stats, 0, 64, ctx->stream));
   }
-  if (vt_fast && !no_qr) {
-    if (few_songs)
-      hipLaunchKernelGGL(vt_stream2_kernel<7>, dim3(nt), dim3(64), 0, ctx->stream, ks, (const uint32_t*)tile_start, pl, topn,
-                         (uint64_t*)cp, (uint32_t*)cd, (uint32_t*)cdd, n_heavy, heavy, heavy_q, hcap, plim, d_qbar, d_vt_err, d_stats);
-    else
-      hipLaunchKernelGGL(vt_stream2_kernel<8>, dim3(nt), dim3(64), 0, ctx->stream, ks, (const uint32_t*)tile_start, pl, topn,
-                         (uint64_t*)cp, (uint32_t*)cd, (uint32_t*)cdd, n_heavy, heavy, heavy_q, hcap, plim, d_qbar, d_vt_err, d_stats);
-  } else if (no_qr)
-    hipLaunchKernelGGL((vt_stream_kernel<7, false>), dim3(nt), dim3(64), 0, ctx->stream, ks, (const uint32_t*)tile_start, pl, topn,
-                       (uint64_t*)cp, (uint32_t*)cd, (uint32_t*)cdd, n_heavy, heavy, heavy_q, hcap, plim, d_vt_err);
-  else if (few_songs)
-    hipLaunchKernelGGL(vt_stream_kernel<7>, dim3(nt), dim3(64), 0, ctx->stream, ks, (const uint32_t*)tile_start, pl, topn,
-                       (uint64_t*)cp, (uint32_t*)cd, (uint32_t*)cdd, n_heavy, heavy, heavy_q, hcap, plim, d_vt_err);
+  if (few_songs)
+    hipLaunchKernelGGL(vt_stream2_kernel<7>, dim3(nt), dim3(64), 0, ctx->stream, ks, (const uint32_t*)tile_start, pl, topn,
+                       (uint64_t*)cp, (uint32_t*)cd, (uint32_t*)cdd, n_heavy, heavy, heavy_q, hcap, plim, d_qbar, d_vt_err, d_stats);
   else
-    hipLaunchKernelGGL(vt_stream_kernel<8>, dim3(nt), dim3(64), 0, ctx->stream, ks, (const uint32_t*)tile_start, pl, topn,
-                       (uint64_t*)cp, (uint32_t*)cd, (uint32_t*)cdd, n_heavy, heavy, heavy_q, hcap, plim, d_vt_err);
+    hipLaunchKernelGGL(vt_stream2_kernel<8>, dim3(nt), dim3(64), 0, ctx->stream, ks, (const uint32_t*)tile_start, pl, topn,
+                       (uint64_t*)cp, (uint32_t*)cd, (uint32_t*)cdd, n_heavy, heavy, heavy_q, hcap, plim, d_qbar, d_vt_err, d_stats);
   if (d_stats) {
     unsigned long long h[8];
     SHZ_HIP(ctx, hipMemcpyAsync(h, d_stats, 64, hipMemcpyDeviceToHost, ctx->stream));
@@ -2378,8 +2198,7 @@ static int32_t match_core(shz_ctx* ctx, shz_table* t, const uint32_t* key32, con
     SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_M6, nx_bound * 8, &gpairs));
     SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_M7, nx_bound * 8, &po));
     uint64_t* E;
-    static const bool no_small_head = [] { const char* e = getenv("SHZ_MATCH_NO_SMALL_HEAD"); return e && atoi(e) != 0; }();
-    if (f_nsh == 1 && m <= MH_MAX && !no_small_head) {
+    if (f_nsh == 1 && m <= MH_MAX) {
       E = (uint64_t*)c1;
       hipLaunchKernelGGL(m_head_small_kernel, dim3(1), dim3(MH_THREADS), 0, ctx->stream, d_key, d_qo, (const uint64_t*)d_qoff,
                          nq, (uint32_t)m, QIDX_SHIFT + mb.qb, E, (uint32_t*)gs, d_ctl);
@@ -2428,10 +2247,9 @@ static int32_t match_core(shz_ctx* ctx, shz_table* t, const uint32_t* key32, con
     // which the host has
     static const int tiles_env = [] { const char* e = getenv("SHZ_VOTE_TILES"); return e ? atoi(e) : -1; }();   // 0 never
     static const int force32 = [] { const char* e = getenv("SHZ_VOTE32"); return e ? atoi(e) : -1; }();   // 0 never, 1 whenever it fits
-    static const bool no_spec = [] { const char* e = getenv("SHZ_MATCH_NO_SPEC"); return e && atoi(e) != 0; }();
     bool spec = false;
     uint32_t spec_bias = 0;
-    if (!vs_out && nq == 1 && f_nsh == 1 && m <= MH_MAX && !no_small_head && !no_spec && !(flags & SHZ_IN_DEVICE) &&
+    if (!vs_out && nq == 1 && f_nsh == 1 && m <= MH_MAX && !(flags & SHZ_IN_DEVICE) &&
         !(flags_sub & SHZ_MATCH_FULL_SORT) && tiles_env != 0 && force32 != 1 && topn <= VT_MAXTOPN &&
         (double)m * t->votes_per_hash <= 2.0 * VT_ONE_WG_MAX) {   // (a table whose last query had far more votes: not worth queueing)
       const uint64_t a0 = query_off[q0], a1 = query_off[q0 + 1];
@@ -2586,10 +2404,9 @@ static int32_t match_core(shz_ctx* ctx, shz_table* t, const uint32_t* key32, con
       SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SORT_D, pmax * 8, &v1));
       // vote tiles: the expand runs by the blocks of the segmented sort and counts the first pass's digits (no tile starts
       // here: m_chunk_start_kernel per pass)
-      static const bool no_fuse = [] { const char* e = getenv("SHZ_NO_EXPAND_HIST"); return e && atoi(e) != 0; }();
       const int Bt_all = mb.sb + mb.dbits + 1, g_lo_all = std::max(1 + mb.dbits, Bt_all - VT_ORDERED_BITS);
       uint32_t fuse_dmask = 0;
-      const bool fuse = tiles && use32 && !no_fuse && shz_seg_first_pass(g_lo_all, Bt_all, &fuse_dmask) == 8;
+      const bool fuse = tiles && use32 && shz_seg_first_pass(g_lo_all, Bt_all, &fuse_dmask) == 8;
       // the sub-group of every expand tile's first pair, for all passes in one launch: pass table (votes, first entry)
       // up, one kernel
       std::vector<uint32_t> toff(passes.size() + 1, 0);

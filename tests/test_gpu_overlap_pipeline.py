@@ -1,7 +1,7 @@
-"""GPU: the two-stream extraction pipeline (SHZ_OVERLAP_SPLIT >= 2: STFT of sub-batch i+1 on a second stream beside
-peak picking of sub-batch i) gives the hashes of the sequential pass.  The switch is read once per process, so the
-pipelined run happens in a child process; both fingerprint the same device-generated clips twice in a row (the second
-call starts while nothing has synchronised the generator of its input: the second stream has to wait for it)."""
+"""GPU: the dual extraction pass (SHZ_DUAL=1: the two halves of a large batch as two passes on twin contexts) gives the
+hashes of the single pass.  The switch is read once per process, so each run happens in a child process; both fingerprint
+the same device-generated clips several times in a row (each call starts while nothing has synchronised the generator of
+its input: the pass has to order itself behind it)."""
 import os
 import subprocess
 import sys
@@ -31,20 +31,6 @@ print(h.hexdigest(), ctx.extract_stats()["f64_passes"])
 """
 
 
-def _run(split, dual=0):
-    env = dict(os.environ, SHZ_OVERLAP_SPLIT=str(split), SHZ_DUAL=str(dual))
-    out = subprocess.run([sys.executable, "-c", CHILD % ROOT], env=env, capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0, out.stderr[-2000:]
-    return out.stdout.strip().split()
-
-
-def test_pipelined_pass_equals_sequential_pass():
-    seq = _run(0)
-    for split in (2, 5):
-        assert _run(split) == seq, split
-    assert seq[1] == "0"
-
-
 def test_dual_pass_equals_single_pass():
     """SHZ_DUAL=1: the two halves of the batch as two passes on two contexts, entries of the second appended behind the
     first's -- same hashes, same offsets (the child fingerprints 130 x 30 s = 83,720 frames... below the dual threshold
@@ -52,7 +38,7 @@ def test_dual_pass_equals_single_pass():
     child_big = CHILD.replace("n, nc = 30 * 44100, 130", "n, nc = 30 * 44100, 260")
     outs = []
     for dual in (0, 1):
-        env = dict(os.environ, SHZ_OVERLAP_SPLIT="0", SHZ_DUAL=str(dual))
+        env = dict(os.environ, SHZ_DUAL=str(dual))
         out = subprocess.run([sys.executable, "-c", child_big % ROOT], env=env, capture_output=True, text=True, timeout=300)
         assert out.returncode == 0, out.stderr[-2000:]
         outs.append(out.stdout.strip().split())
