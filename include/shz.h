@@ -267,18 +267,19 @@ int32_t shz_table_finalize(shz_table* t);
  * peers') until shz_table_finalize / shz_table_allgather merges all of them at once -- seal_run never cuts a segment on
  * the way, so every row can still travel, and the one merge cuts segments by KEY RANGE (a query hash is then looked up
  * in one segment, not in all).  The flag takes effect with rows_hint = 0 too (nothing is allocated ahead then).
- * shz_table_seal_run turns the staged rows into a sorted run (bounded scratch: one batch; more than 2^32 - 4096 staged
- * rows become several runs) WITHOUT making them visible to queries.  Without SHZ_RESERVE_GATHER full segments are cut as
- * soon as enough rows wait (bounded arena).  shz_table_finalize merges what is left (k-way merge of the runs, 8 bytes
+ * shz_table_seal_run turns the staged rows into a sorted run (bounded scratch: one batch; a run holds at most 2^32 - 4096
+ * rows, more staged rows become several runs) WITHOUT making them visible to queries.  Without SHZ_RESERVE_GATHER full
+ * segments are cut as soon as enough rows wait (bounded arena).  shz_table_finalize merges what is left (k-way merge of the runs, 8 bytes
  * read + 12 written per row) and makes everything visible.  On a table whose active segment holds rows, or whose song
  * ids + offsets need more than 32 bits, seal_run is finalize -- on a table that holds its runs it is SHZ_E_UNSUPPORTED
  * instead and the rows stay staged (rows put into segments could not travel any more). */
 int32_t shz_table_reserve(shz_table* t, uint64_t rows_hint, uint64_t batch_rows_hint, uint32_t flags);
 int32_t shz_table_seal_run(shz_table* t);
-/* rows one sealed run may hold (0 = the limit of a radix sort, 2^32 - 4096); small values make many runs of few rows (tests) */
+/* rows one sealed run may hold (0 = the hard limit, at most 2^32 - 4096 rows, which larger values are clamped to); small
+ * values make many runs of few rows (tests) */
 int32_t shz_table_set_run_rows(shz_table* t, uint64_t rows);
-/* A table is a list of sorted segments (each one radix sort, < 2^32 rows) that every probe visits; rows
- * beyond `rows` per segment open a new one at finalize.  Default 2^31; smaller values only for tests.
+/* A table is a list of sorted segments (each one radix sort, < 2^32 rows; one cut from sealed runs holds at most
+ * min(rows, 2^32 - 4096)) that every probe visits; rows beyond `rows` per segment open a new one at finalize.  Default 2^31; smaller values only for tests.
  * UNIQUE(song_id, offset, hash) + INSERT IGNORE (mysql_database.py:54-55, 62-68) hold across segments: staged rows
  * that already sit in a frozen segment are dropped at finalize, duplicates inside the batch by the sort. */
 int32_t shz_table_set_segment_rows(shz_table* t, uint64_t rows);
@@ -322,6 +323,10 @@ int32_t shz_match_batch(shz_ctx* ctx, shz_table* t, const uint32_t* key32, const
  * shz_match_vt_redo: how many sub-batches went that way since the context was created. */
 #define SHZ_DEBUG_VT_TINY_HEAVY 1u
 #define SHZ_DEBUG_VT_PROBE1 2u
+/* Test switch of the table build: the most rows a sealed run or a segment cut from runs may hold drops from 2^32 - 4096
+ * to 65,536 (run cut, shz_table_set_run_rows clamp, segment cut, the size check of an exchange round), so that tests reach
+ * the cuts at the limit with few rows.  Set it before the table's first call; every rank of a gathered build alike. */
+#define SHZ_DEBUG_RUN_LIMIT_SMALL 4u
 int32_t shz_set_debug(shz_ctx* ctx, uint32_t flags);
 int32_t shz_match_vt_redo(shz_ctx* ctx, uint64_t* count);
 /* A single query of at most 8,192 hashes handed over in host memory has its vote kernels queued before the number of its

@@ -12,6 +12,9 @@ LIB_PATH = os.environ.get("SHZ_LIB") or os.path.join(_HERE, "libshz.so")  # SHZ_
 
 OK, E_INVALID, E_HIP, E_CAPACITY, E_NOMEM, E_UNSUPPORTED, E_RCCL, E_STATE = 0, -1, -2, -3, -4, -5, -6, -7
 PCM_DEVICE, OUT_DEVICE, IN_DEVICE, STFT_POWER, MATCH_FULL_SORT, RESERVE_GATHER, RESERVE_WAIT = 1, 2, 4, 8, 16, 32, 64
+# shz_set_debug test switches (include/shz.h); RUN_ROWS_MAX[_SMALL]: the most rows a run / a segment cut from runs holds
+DEBUG_VT_TINY_HEAVY, DEBUG_VT_PROBE1, DEBUG_RUN_LIMIT_SMALL = 1, 2, 4
+RUN_ROWS_MAX, RUN_ROWS_MAX_SMALL = (1 << 32) - 4096, 65536
 NFFT, HOP, NBINS = 4096, 2048, 2049
 
 u8p, u16p, u32p, i32p, u64p, i16p, f64p = (C.POINTER(t) for t in (
@@ -250,7 +253,8 @@ class Context:
         return {"name": name.value.decode(), "hbm_bytes": hbm.value, "compute_units": cus.value, "clock_khz": clk.value}
 
     def set_debug(self, flags: int):
-        """SHZ_DEBUG_* test switches (1: tiny hand-over list, 2: LDS probes give up after one round)."""
+        """SHZ_DEBUG_* test switches (1: tiny hand-over list, 2: LDS probes give up after one round, 4: runs and segments cut
+        from runs hold at most RUN_ROWS_MAX_SMALL rows)."""
         self.check(lib().shz_set_debug(self.h, int(flags)))
 
     def vt_redo_count(self) -> int:

@@ -1175,7 +1175,7 @@ extern "C" int32_t shz_table_reserve(shz_table* t, uint64_t rows_hint, uint64_t 
   if (rows_hint == 0) return SHZ_OK;
   SHZ_HIP(ctx, hipSetDevice(ctx->device));
   if (batch_rows_hint == 0) batch_rows_hint = rows_hint;
-  batch_rows_hint = std::min<uint64_t>(batch_rows_hint, (1ull << 32) - 4096);
+  batch_rows_hint = std::min<uint64_t>(batch_rows_hint, run_rows_max(ctx));
   shz_reserve_job* j = new shz_reserve_job();
   j->device = ctx->device;
   j->ctx = ctx;
@@ -1557,7 +1557,8 @@ static int32_t seal_rows(shz_table* t, const uint32_t* key, const uint32_t* sid,
                          uint32_t sid_hi) {
   shz_ctx* ctx = t->ctx;
   if (n == 0) return SHZ_OK;
-  if (n >= (1ull << 32) - 4096) SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "a run is limited to < 2^32 rows (have %llu)", (unsigned long long)n);
+  if (n > run_rows_max(ctx))
+    SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "a run holds at most %llu rows (have %llu)", (unsigned long long)run_rows_max(ctx), (unsigned long long)n);
   ph_clock pc(t);
   const uint64_t tail = (runs_end(t) + 31) & ~31ull;   // runs start 256-byte aligned (the sort loads 16 bytes per lane)
   SHZ_TRY(rbuf_reserve(t, tail + n));
@@ -1807,7 +1808,7 @@ static int32_t flush_runs(shz_table* t, bool final) {
   uint32_t sid_lo = 0xFFFFFFFFu, sid_hi = 0;
   for (const shz_run& r : t->runs)
     if (r.n) { sid_lo = std::min(sid_lo, r.sid_lo); sid_hi = std::max(sid_hi, r.sid_hi); }
-  const uint64_t L = std::min<uint64_t>(t->seg_limit, (1ull << 32) - 4096);
+  const uint64_t L = std::min<uint64_t>(t->seg_limit, run_rows_max(ctx));
   if (final) {
     SHZ_TRY(kway_merge(t, ptr, t->runs, dedup, L, 0xFFFFFFFFu, true, nullptr, 0, nullptr));
     t->runs.clear();
@@ -1849,9 +1850,9 @@ static int32_t staged_minmax(shz_table* t, uint64_t lo, uint64_t n, uint32_t out
   return SHZ_OK;
 }
 
-// rows a run may hold when it is made (a debug limit forces several runs out of few rows: tests)
+// rows a run may hold when it is made, at most (a smaller run_limit forces several runs out of few rows: tests)
 static uint64_t run_rows_limit(const shz_table* t) {
-  const uint64_t hard = (1ull << 32) - 4096;
+  const uint64_t hard = run_rows_max(t->ctx);
   return t->run_limit ? std::min<uint64_t>(t->run_limit, hard) : hard;
 }
 
@@ -1927,7 +1928,7 @@ extern "C" int32_t shz_table_seal_run(shz_table* t) {
     return rc;
   }
   if (t->hold_runs) return SHZ_OK;   // runs wait in the arena: one merge at finalize / allgather cuts segments by key range
-  while (runs_rows(t) >= std::min<uint64_t>(t->seg_limit, (1ull << 32) - 4096)) {
+  while (runs_rows(t) >= std::min<uint64_t>(t->seg_limit, run_rows_max(ctx))) {
     const uint64_t before = runs_rows(t);
     SHZ_TRY(flush_runs(t, false));
     t->rows_cut += before - runs_rows(t);
@@ -2017,7 +2018,11 @@ static int32_t gx_round(shz_table* t, shz_comm* c, bool finishing, bool local_ge
     v->any_broken |= (b[4] & GXF_BROKEN) != 0;
     v->all_finishing &= (b[4] & GXF_FINISHING) != 0;
     if (b[5] > GX_MAXR) SHZ_FAIL(ctx, SHZ_E_STATE, "exchange round: rank %d announces %llu runs", r, (unsigned long long)b[5]);
-    for (uint64_t j = 0; j < b[5]; ++j) v->rows_sent += b[GX_HDR + 2 * j];
+    for (uint64_t j = 0; j < b[5]; ++j) {   // (this rank's own runs too: every rank reaches the same verdict)
+      if (b[GX_HDR + 2 * j] > run_rows_max(ctx))
+        SHZ_FAIL(ctx, SHZ_E_STATE, "exchange round: rank %d announces a run of %llu rows", r, (unsigned long long)b[GX_HDR + 2 * j]);
+      v->rows_sent += b[GX_HDR + 2 * j];
+    }
   }
   if (bits_for(gmax_sid) + bits_for(gmax_off) > 32) v->any_general = true;
   if (v->any_general || v->any_cut || v->any_broken) return SHZ_OK;   // nothing travels: the caller decides (alike on every rank)
@@ -2038,7 +2043,6 @@ static int32_t gx_round(shz_table* t, shz_comm* c, bool finishing, bool local_ge
     const uint64_t* b = &all[(size_t)GX_BLOCK * r];
     for (uint64_t j = 0; j < b[5]; ++j) {
       const uint64_t n = b[GX_HDR + 2 * j];
-      if (n >= (1ull << 32) - 4096) SHZ_FAIL(ctx, SHZ_E_STATE, "exchange round: rank %d announces a run of %llu rows", r, (unsigned long long)n);
       shz_run nr{at, n, (uint32_t)b[GX_HDR + 2 * j + 1], (uint32_t)(b[GX_HDR + 2 * j + 1] >> 32)};
       nr.where = RUN_RECV;
       arrivals.push_back(nr);
@@ -2267,7 +2271,8 @@ extern "C" int32_t shz_table_finalize_runs(shz_table* t, const uint64_t* run_row
   return rc == SHZ_I_GENERAL_PATH ? shz_table_finalize(t) : rc;   // not an empty table / ids too wide
 }
 
-/* rows a sealed run may hold (0: the hard limit, 2^32 - 4096): small values force several runs out of few rows (tests) */
+/* rows a sealed run may hold (0: the hard limit, SHZ_RUN_ROWS_MAX; larger values are clamped to it): small values force several
+   runs out of few rows (tests) */
 extern "C" int32_t shz_table_set_run_rows(shz_table* t, uint64_t rows) {
   if (!t) return SHZ_E_INVALID;
   if (rows && rows < 16) SHZ_FAIL(t->ctx, SHZ_E_INVALID, "run rows must be 0 or >= 16");

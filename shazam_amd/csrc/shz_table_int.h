@@ -27,6 +27,15 @@ struct shz_seg_dev {  // what the match kernels see
 static inline shz_seg_dev seg_dev_of(const shz_seg& g) { return shz_seg_dev{g.key, g.sid, g.off, g.bucket, (uint32_t)g.n, g.key_lo, g.nbuckets}; }
 #define SHZ_MAX_SEGS 32
 
+// The most rows one sorted run or one segment cut from runs may hold (inclusive): a radix sort takes < 2^32 keys, and the
+// 4096 rows below that are the margin of its tiles.  SHZ_DEBUG_RUN_LIMIT_SMALL (tests) lowers it to
+// SHZ_RUN_ROWS_MAX_SMALL, so that the cuts at the limit are reached with few rows.
+#define SHZ_RUN_ROWS_MAX ((1ull << 32) - 4096)
+#define SHZ_RUN_ROWS_MAX_SMALL 65536ull
+static inline uint64_t run_rows_max(const shz_ctx* ctx) {
+  return (ctx->debug & SHZ_DEBUG_RUN_LIMIT_SMALL) ? SHZ_RUN_ROWS_MAX_SMALL : SHZ_RUN_ROWS_MAX;
+}
+
 #define SHZ_TABLE_PHASES 24
 
 // a sorted run of packed rows (key << (sb + ob) | sid << ob | off) waiting in the run arena for the k-way merge
@@ -70,7 +79,7 @@ struct shz_table {
   // ---- gathered build (shz_table_exchange_run / shz_table_allgather)
   bool hold_runs = false;                               // sealed runs wait in the arena until finalize / allgather, seal_run never cuts a segment (until the final merge)
   bool hold_reserved = false;                           // ... asked for by shz_table_reserve(SHZ_RESERVE_GATHER): every bulk build of this table holds its runs
-  uint64_t run_limit = 0;                               // rows a sealed run may hold (0: 2^32 - 4096); small values force many runs (tests)
+  uint64_t run_limit = 0;                               // rows a sealed run may hold (0: run_rows_max); small values force many runs (tests)
   uint64_t rows_cut = 0;                                // rows seal_run moved into segments since the last allgather / clear: they cannot travel any more
   uint64_t gx_recv_bytes = 0, gx_rounds = 0;            // payload received / exchange rounds since the last allgather
   double gx_wait_s = 0.0, gx_xfer_s = 0.0;              // host seconds waiting for peers / transfers inside exchange rounds; queueing (in-process transport: making) the transfers
