@@ -436,6 +436,42 @@ int32_t shz_pairs_vote(shz_ctx* ctx, uint64_t* d_pairs, uint64_t n, uint32_t n_q
                        uint32_t delta_bits, uint32_t bias, uint32_t topn, uint32_t* out_sid, int32_t* out_delta,
                        uint32_t* out_aligned, uint32_t* out_dedup, uint32_t* out_nres);
 
+/* ---- live streams (new; the reference's recogniser reads its input CHUNK = 8192 samples at a time per channel,
+ * recognizer.py:21-25, 357-392) --------------------------------------------------------------------------------------
+ * n_streams independent streams on one ctx.  The hashes a stream has emitted, concatenated over all its pushes, are
+ * those of shz_fingerprint_batch on its whole signal, bit for bit and in order.  A frame t is SETTLED once frame t + 10
+ * exists (its 21x21 peak window is complete; at the stream's end every frame is); a push extracts, per stream, one window
+ * clip from frame max(0, settled - 10) to its last complete frame and keeps the peaks of the newly settled frames.  A
+ * settled peak emits all its hashes once fan_value - 1 settled peaks follow it, or once the settled horizon H exceeds its
+ * frame + 200, or when the stream ends; the rest (at most fan_value - 1 peaks) waits for the next push.
+ * hop = the ctx's hop (shz_set_overlap) at creation; if it changes afterwards, calls return SHZ_E_STATE.
+ * fan_value in [1, 64]; n_streams in [1, 65535].  Not thread-safe, like the ctx. */
+typedef struct shz_streams shz_streams;
+int32_t shz_streams_create(shz_ctx* ctx, uint32_t n_streams, uint32_t fs, double amp_min, uint32_t fan_value,
+                           shz_streams** out);
+int32_t shz_streams_destroy(shz_streams* s);
+/* Append pcm[chunk_off[i] .. chunk_off[i+1]) to stream i (empty chunks allowed; chunk_off must not decrease); streams whose
+ * bit is set in `end` (n_streams bits, may be NULL) end after this chunk -- a stream of fewer than 4096 samples emits the
+ * hashes of its one zero-padded frame.  Outputs: the hashes that became final in this push, (key32, t1) with t1 in
+ * absolute frames of the stream, stream i's at [hash_off[i], hash_off[i+1]) (hash_off: n_streams + 1, HOST).
+ * SHZ_PCM_DEVICE / SHZ_OUT_DEVICE as for shz_fingerprint_batch.  SHZ_E_CAPACITY: *count = required and NO stream has
+ * changed (repeat the call with room).  A stream that has ended: SHZ_E_STATE if it gets samples or an end bit, left alone
+ * otherwise. */
+int32_t shz_streams_push(shz_streams* s, const int16_t* pcm, const uint64_t* chunk_off, const uint32_t* end,
+                         uint32_t flags, uint32_t* key32, uint32_t* t1, uint64_t* hash_off, uint64_t cap, uint64_t* count);
+/* start stream slots afresh (ended or not): sample 0, nothing pending */
+int32_t shz_streams_reset(shz_streams* s, const uint32_t* which, uint32_t n);
+/* stream i: samples received, settled frames H, peaks pending, hashes emitted so far (any pointer may be NULL) */
+int32_t shz_streams_state(shz_streams* s, uint32_t i, uint64_t* samples, uint64_t* settled, uint64_t* pending,
+                          uint64_t* emitted);
+/* No GPU, no ctx (like shz_frame_count_hop): the window plan of one push of a stream that had samples_before samples and
+ * settled_before settled frames and has samples_after now (ending: it ends with them).  win_frame0 = first frame of the
+ * window clip, [win_s0, win_s1) its samples, settled_after = the new horizon H (settled_after == settled_before: nothing
+ * settles, no window; a stream that ends with 0 samples has one window of 0 samples, its one zero-padded frame).  SHZ_E_INVALID for hop outside [1, 4096], samples_after < samples_before or a settled_before that is not a
+ * horizon of the stream. */
+int32_t shz_stream_plan(uint64_t samples_before, uint64_t samples_after, uint64_t settled_before, uint32_t hop,
+                        int32_t ending, uint64_t* win_frame0, uint64_t* win_s0, uint64_t* win_s1, uint64_t* settled_after);
+
 #ifdef __cplusplus
 }
 #endif

@@ -275,3 +275,7 @@ def recognize(channels_or_samples, db=None, Fs: int = RATE, topn: int = TOPN):
     q = [np.asarray(x)] if (not isinstance(x, (list, tuple)) or (len(x) and np.isscalar(x[0]))) else list(x)
     results, tm = recognize_batch([q], db, Fs, topn)
     return results[0], tm["fingerprint_time"], tm["query_time"], tm["align_time"]
+
+
+# live streams (recognizer.py:21-25, 357-392): incremental fingerprints and recognition of chunked input
+from .stream import StreamFingerprinter, StreamRecognizer, fingerprint_stream  # noqa: E402,F401

@@ -117,6 +117,12 @@ SIGNATURES = {
     "shz_pairs_allgather": (C.c_int32, [vp, C.c_uint64, vp, vp, C.c_uint64, u64p]),
     "shz_pairs_vote": (C.c_int32, [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                    vp, vp, vp, vp, vp]),
+    "shz_streams_create": (C.c_int32, [vp, C.c_uint32, C.c_uint32, C.c_double, C.c_uint32, C.POINTER(vp)]),
+    "shz_streams_destroy": (C.c_int32, [vp]),
+    "shz_streams_push": (C.c_int32, [vp, vp, u64p, vp, C.c_uint32, vp, vp, u64p, C.c_uint64, u64p]),
+    "shz_streams_reset": (C.c_int32, [vp, vp, C.c_uint32]),
+    "shz_streams_state": (C.c_int32, [vp, C.c_uint32, u64p, u64p, u64p, u64p]),
+    "shz_stream_plan": (C.c_int32, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int32, u64p, u64p, u64p, u64p]),
 }
 
 
@@ -751,3 +757,90 @@ class Comm:
         if self.h and self.ctx.h:
             lib().shz_comm_destroy(self.h)
         self.h = None
+
+
+def stream_plan(samples_before: int, samples_after: int, settled_before: int, hop: int = HOP, ending: bool = False):
+    """shz_stream_plan (host only): (win_frame0, win_s0, win_s1, settled_after) of one push of a stream."""
+    v = [C.c_uint64() for _ in range(4)]
+    rc = lib().shz_stream_plan(int(samples_before), int(samples_after), int(settled_before), int(hop), 1 if ending else 0,
+                               *[C.byref(x) for x in v])
+    if rc != OK:
+        raise ShzError(rc, "shz_stream_plan: invalid arguments")
+    return tuple(int(x.value) for x in v)
+
+
+class Streams:
+    """n independent live streams on one context (shz_streams_*): push chunks, get the hashes that became final."""
+
+    def __init__(self, ctx: Context, n_streams: int, fs: int = 44100, amp_min: float = 10.0, fan_value: int = 5):
+        self.ctx, self.h, self.n = ctx, None, int(n_streams)
+        h = vp()
+        ctx.check(lib().shz_streams_create(ctx.h, self.n, int(fs), float(amp_min), int(fan_value), C.byref(h)))
+        self.h, self.fan_value = h, int(fan_value)
+        self.hop = int(getattr(ctx, "hop", HOP))
+        self.cap = 4096
+
+    def close(self):
+        if self.h and self.ctx.h:
+            lib().shz_streams_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _end_bits(self, end):
+        if end is None:
+            return None
+        words = np.zeros((self.n + 31) // 32, np.uint32)
+        for i in (range(self.n) if end is True else end):
+            words[int(i) >> 5] |= np.uint32(1 << (int(i) & 31))
+        return words
+
+    def push_raw(self, pcm, chunk_off, end=None, cap=None, pcm_device=False, out_key: DevBuf = None, out_t1: DevBuf = None):
+        """One shz_streams_push as it is: returns (rc, key32, t1, hash_off, count) without retrying."""
+        co = np.ascontiguousarray(chunk_off, np.uint64)
+        assert len(co) == self.n + 1
+        ew = self._end_bits(end)
+        ho, cnt = np.zeros(self.n + 1, np.uint64), C.c_uint64()
+        flags = PCM_DEVICE if pcm_device else 0
+        if out_key is not None:
+            cap = int(cap if cap is not None else out_key.nbytes // 4)
+            rc = lib().shz_streams_push(self.h, ptr(pcm), co.ctypes.data_as(u64p), ptr(ew), flags | OUT_DEVICE, ptr(out_key),
+                                        ptr(out_t1), ho.ctypes.data_as(u64p), cap, C.byref(cnt))
+            return rc, None, None, ho, int(cnt.value)
+        cap = int(self.cap if cap is None else cap)
+        k, t1 = np.empty(max(cap, 1), np.uint32), np.empty(max(cap, 1), np.uint32)
+        rc = lib().shz_streams_push(self.h, ptr(pcm), co.ctypes.data_as(u64p), ptr(ew), flags, ptr(k), ptr(t1),
+                                    ho.ctypes.data_as(u64p), cap, C.byref(cnt))
+        n = int(cnt.value)
+        return rc, k[:n], t1[:n], ho, n
+
+    def push(self, chunks, end=None):
+        """chunks: one 1-D int16 array per stream (None / empty: nothing for it).  end: stream indices that end after this
+        chunk (True: all).  Returns (key32, t1, hash_off) of the hashes that became final, stream i's at
+        [hash_off[i], hash_off[i+1]); retries with the required capacity on E_CAPACITY like Context.fingerprint_batch."""
+        assert len(chunks) == self.n
+        arrs = [np.zeros(0, np.int16) if c is None else np.ascontiguousarray(c, np.int16) for c in chunks]
+        off = np.zeros(self.n + 1, np.uint64)
+        off[1:] = np.cumsum([len(a) for a in arrs])
+        pcm = np.concatenate(arrs) if off[-1] else np.zeros(1, np.int16)
+        while True:
+            rc, k, t1, ho, n = self.push_raw(pcm, off, end)
+            if rc == E_CAPACITY:
+                self.cap = max(n, 2 * self.cap)
+                continue
+            self.ctx.check(rc)
+            return k.copy(), t1.copy(), ho
+
+    def reset(self, which=None):
+        """Start streams afresh (default: all of them)."""
+        w = np.ascontiguousarray(range(self.n) if which is None else which, np.uint32)
+        self.ctx.check(lib().shz_streams_reset(self.h, ptr(w), len(w)))
+
+    def state(self, i: int) -> dict:
+        v = [C.c_uint64() for _ in range(4)]
+        self.ctx.check(lib().shz_streams_state(self.h, int(i), *[C.byref(x) for x in v]))
+        return dict(zip(("samples", "settled", "pending", "emitted"), (int(x.value) for x in v)))

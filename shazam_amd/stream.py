@@ -1,0 +1,156 @@
+"""Live streams: fingerprint and recognise audio that arrives chunk by chunk.
+
+The reference's recogniser reads the microphone in CHUNK = 8192-sample pieces per channel, fingerprints the channels,
+unions their hashes, matches and aligns (recognizer.py:21-25, 357-392).  Here many such sources advance at once on the
+GPU (shz_streams_*, csrc/shz_stream.hip): a push settles what the new samples complete and returns the hashes that became
+final, so that what a stream has emitted is always a prefix of fingerprint() of everything it received, in the
+reference's generation order."""
+from __future__ import annotations
+
+import numpy as np
+
+from . import _ffi
+from ._ffi import HOP
+
+RATE = 44100
+TOPN = 2
+
+
+def _ctx(ctx):
+    if ctx is not None:
+        return ctx
+    from . import get_context
+    return get_context()
+
+
+class StreamFingerprinter:
+    """n_streams independent streams on one context.  push(chunks, end) -> (key32, t1, hash_off): the hashes that became
+    final, stream i's at [hash_off[i], hash_off[i+1]), t1 in frames from the stream's first sample.  The hop is the
+    context's at creation (Context.set_overlap before creating for another wratio)."""
+
+    def __init__(self, n_streams: int, Fs: int = RATE, fan_value: int = 5, amp_min=10, ctx=None):
+        self.ctx = _ctx(ctx)
+        self.n_streams = int(n_streams)
+        self.streams = _ffi.Streams(self.ctx, self.n_streams, int(Fs), float(amp_min), int(fan_value))
+
+    def push(self, chunks, end=None):
+        return self.streams.push([None if c is None else _as_pcm(c) for c in chunks], end)
+
+    def push_hex(self, chunks, end=None):
+        """push() with the reference's return type: per stream list[(hex20, t1)]."""
+        from . import hex_of_keys
+        k, t1, ho = self.push(chunks, end)
+        hexes = hex_of_keys(self.ctx, k) if len(k) else []
+        t = t1.tolist()
+        return [list(zip(hexes[ho[i]:ho[i + 1]], t[ho[i]:ho[i + 1]])) for i in range(self.n_streams)]
+
+    def reset(self, which=None):
+        self.streams.reset(which)
+
+    def state(self, i: int) -> dict:
+        """samples received, settled frames, peaks pending, hashes emitted so far."""
+        return self.streams.state(i)
+
+    def close(self):
+        self.streams.close()
+
+
+def _as_pcm(x):
+    from . import _as_pcm as conv
+    return conv(x)
+
+
+def fingerprint_stream(chunks, Fs: int = RATE, fan_value: int = 5, amp_min=10, ctx=None):
+    """Generator: yields list[(hex20, t1)] per chunk of `chunks` (any iterable of 1-D int16 arrays); the stream ends with
+    the last chunk.  The concatenation of what it yields equals fingerprint(np.concatenate(chunks))."""
+    fp = StreamFingerprinter(1, Fs, fan_value, amp_min, ctx)
+    try:
+        it = iter(chunks)
+        try:
+            cur = next(it)
+        except StopIteration:
+            return
+        while True:
+            try:
+                nxt = next(it)
+            except StopIteration:
+                yield fp.push_hex([cur], end=[0])[0]
+                return
+            yield fp.push_hex([cur])[0]
+            cur = nxt
+    finally:
+        fp.close()
+
+
+class StreamRecognizer:
+    """n_listeners live listeners against a HipFingerprintDB.  A listener is `channels` streams whose hashes are unioned
+    (recognizer.py:377-382).  push(chunks_per_listener) returns per listener (results, w0): the reference-shaped result
+    dicts of align_matches over the settled hashes with t1 >= w0 = max(0, H - window_frames), query offsets t1 - w0, for
+    all listeners in ONE batched match -- `offset` means what it means for a clip recorded from frame w0.  H is the
+    smallest settled horizon of the listener's channels; window_frames = int(window_seconds * 44100 / hop).  Listeners
+    with no hashes in the window get []."""
+
+    def __init__(self, db, n_listeners: int, channels: int = 1, window_seconds: float = 5, topn: int = TOPN,
+                 fan_value: int = 5, amp_min=10):
+        self.db, self.n, self.channels, self.topn = db, int(n_listeners), int(channels), int(topn)
+        self.fp = StreamFingerprinter(self.n * self.channels, RATE, fan_value, amp_min, db.ctx)
+        self.window_frames = int(float(window_seconds) * RATE / self.fp.streams.hop)
+        self._k = [np.zeros(0, np.uint32) for _ in range(self.n)]
+        self._t = [np.zeros(0, np.uint32) for _ in range(self.n)]
+
+    def _flat(self, per_listener):
+        out = []
+        for lc in per_listener:
+            if self.channels == 1 and (lc is None or (isinstance(lc, np.ndarray) and lc.ndim == 1)):
+                lc = [lc]
+            if lc is None:
+                lc = [None] * self.channels
+            assert len(lc) == self.channels, "one chunk per channel"
+            out.extend(lc)
+        return out
+
+    def horizon(self, listener: int) -> int:
+        c = self.channels
+        return min(self.fp.state(listener * c + j)["settled"] for j in range(c))
+
+    def push(self, chunks_per_listener, end=None):
+        """chunks_per_listener[l]: list of `channels` 1-D int16 arrays (a bare array when channels == 1; None: nothing).
+        end: listeners whose channels all end after this chunk.  Returns [(results, w0)] per listener."""
+        assert len(chunks_per_listener) == self.n
+        ends = None if end is None else [l * self.channels + j for l in (range(self.n) if end is True else end)
+                                         for j in range(self.channels)]
+        k, t1, ho = self.fp.push(self._flat(chunks_per_listener), ends)
+        keys, qoffs, qoff, w0s = [], [], [0], []
+        for l in range(self.n):
+            s0, s1 = int(ho[l * self.channels]), int(ho[(l + 1) * self.channels])
+            H = self.horizon(l)
+            w0 = max(0, H - self.window_frames)
+            kk = np.concatenate([self._k[l], k[s0:s1]])
+            tt = np.concatenate([self._t[l], t1[s0:s1]])
+            keep = tt >= w0
+            self._k[l], self._t[l] = kk[keep], tt[keep]
+            keys.append(self._k[l])
+            qoffs.append((self._t[l] - np.uint32(w0)).astype(np.uint32))
+            qoff.append(qoff[-1] + len(self._k[l]))
+            w0s.append(w0)
+        results = [[] for _ in range(self.n)]
+        live = [l for l in range(self.n) if qoff[l + 1] > qoff[l]]
+        if live:
+            from . import _result_dicts
+            qo = np.zeros(len(live) + 1, np.uint64)
+            qo[1:] = np.cumsum([qoff[l + 1] - qoff[l] for l in live])
+            res = self.db.match(np.concatenate([keys[l] for l in live]), np.concatenate([qoffs[l] for l in live]), qo,
+                                self.topn)
+            for q, l in enumerate(live):
+                results[l] = _result_dicts(self.db, res, q, int(res["nhash"][q]))
+        return list(zip(results, w0s))
+
+    def reset(self, listeners=None):
+        ls = range(self.n) if listeners is None else listeners
+        self.fp.reset([l * self.channels + j for l in ls for j in range(self.channels)])
+        for l in ls:
+            self._k[l] = np.zeros(0, np.uint32)
+            self._t[l] = np.zeros(0, np.uint32)
+
+    def close(self):
+        self.fp.close()
