@@ -311,6 +311,13 @@ int32_t shz_table_song_rows(shz_table* t, uint32_t sid, uint64_t* n_rows);
  *   out_nres   [n_queries]       results valid for q
  *   out_nhash  [n_queries]       len(set(hashes)) = queried_hashes (recognizer.py:389)
  *   out_npairs [n_queries]       len(matches)
+ * Votes are packed as (query, song id, delta + bias, flag) with sb = bits(largest song id), dbits = bits(largest table
+ * offset + largest query offset of the sub-batch), qb = bits(queries of the sub-batch - 1), at least 1 bit each.
+ * SHZ_E_UNSUPPORTED, exactly when (n_queries > 0):
+ *   - the table holds an offset >= 2^31 (shz_table_maxima; out_delta is int32_t -- the reference's INT UNSIGNED
+ *     column allows up to 2^32 - 1), or a query offset is >= 2^20;
+ *   - a query with hashes does not fit the 64-bit key alone: 1 + sb + bits(largest table offset + its largest query
+ *     offset) + 1 > 64.  Queries that fit alone but not together are split into smaller sub-batches; results are exact.
  */
 int32_t shz_match_batch(shz_ctx* ctx, shz_table* t, const uint32_t* key32, const uint32_t* q_off,
                         const uint64_t* query_off, uint32_t n_queries, uint32_t topn, uint32_t flags,
@@ -413,7 +420,7 @@ int32_t shz_table_shard_exchange(shz_table* t, shz_comm* c, uint64_t* bytes_recv
  *   ((query << sid_bits | song_id) << delta_bits | (db_off - q_off) + bias) << 1 | counts-a-DB-row-once flag
  * sid_bits >= bits of the largest song id of the WHOLE table, bias >= the largest q_off of the batch,
  * delta_bits >= bits of (largest offset of the whole table + bias); bits(n_queries-1) + sid_bits + delta_bits + 1
- * must fit 64.  shz_table_maxima gives a table's largest song id / offset (after shz_table_shard_exchange:
+ * must fit 64, and delta_bits <= 32 (tables hold offsets < 2^31, as for shz_match_batch); else SHZ_E_UNSUPPORTED.  shz_table_maxima gives a table's largest song id / offset (after shz_table_shard_exchange:
  * of the whole sharded table). */
 int32_t shz_table_maxima(shz_table* t, uint32_t* max_sid, uint32_t* max_off);
 /* probe + expand only (the head of shz_match_batch): the votes of this table's rows for the queries, appended

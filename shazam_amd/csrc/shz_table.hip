@@ -388,9 +388,11 @@ __global__ void m_query_stats_kernel(const uint64_t* __restrict__ E, const mctl*
     while (l < h) { uint32_t mid = l + ((h - l) >> 1); if (E[gs[mid]] < target) l = mid + 1; else h = mid; }
     return l;
   };
+  // (q + 1) << 52 wraps to 0 for query 4,095 of a full sub-batch (MAX_Q_SUB): its elements run to the end of E
   const uint64_t a = (uint64_t)q << QIDX_SHIFT, b = (uint64_t)(q + 1) << QIDX_SHIFT;
-  nhash[q] = lb_e(b) - lb_e(a);
-  npairs[q] = po[(uint64_t)lb_g(b) * nseg] - po[(uint64_t)lb_g(a) * nseg];
+  const bool to_end = ((q + 1) >> (64 - QIDX_SHIFT)) != 0;
+  nhash[q] = (to_end ? mu : lb_e(b)) - lb_e(a);
+  npairs[q] = po[(uint64_t)(to_end ? ng : lb_g(b)) * nseg] - po[(uint64_t)lb_g(a) * nseg];
 }
 
 struct m_bits { int sb, dbits, qb; uint32_t bias; };  // bias = max query offset of the sub-batch: delta + bias >= 0
@@ -2065,6 +2067,9 @@ static int32_t match_core(shz_ctx* ctx, shz_table* t, const uint32_t* key32, con
   if (t->ctx != ctx) SHZ_FAIL(ctx, SHZ_E_INVALID, "table belongs to another ctx");
   if (pending_rows(t) || (!t->bucket && t->done.empty())) SHZ_FAIL(ctx, SHZ_E_STATE, "table not finalized");
   if (n_queries == 0) return SHZ_OK;
+  // offsets < 2^31: every delta fits out_delta's int32_t and, biased by a query offset < 2^20, 32 bits
+  if (t->max_off >= (1u << 31))
+    SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "match: the table holds offset %u; offsets must be < 2^31", t->max_off);
   if (!query_off) SHZ_FAIL(ctx, SHZ_E_INVALID, "match: query_off is NULL");
   if (!vs_out && (!out_sid || !out_delta || !out_aligned || !out_dedup || !out_nres))
     SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_match_batch: NULL buffer");
@@ -2133,7 +2138,9 @@ static int32_t match_core(shz_ctx* ctx, shz_table* t, const uint32_t* key32, con
   }
   (void)h0;
   uint32_t q0 = 0;
-  uint32_t step = std::min<uint32_t>(n_queries, MAX_Q_SUB);
+  // a shard's compose marks hashes it does not own with the query index nq (sorted behind all queries): nq << 52 must
+  // not wrap, so its sub-batches stay below MAX_Q_SUB
+  uint32_t step = std::min<uint32_t>(n_queries, (vs_out && vs_out->nshards > 1) ? MAX_Q_SUB - 1 : MAX_Q_SUB);
   bool redo_full_sort = false;   // the vote tiles of this sub-batch flagged an overflow: once more, through the full sort
   const uint32_t vt_probe_limit_1 = (ctx->debug & SHZ_DEBUG_VT_PROBE1) ? 1u : 0u;   // debug: a probe gives up after one round
   while (q0 < n_queries) {
@@ -2589,7 +2596,8 @@ extern "C" int32_t shz_match_pairs(shz_ctx* ctx, shz_table* t, const uint32_t* k
   if (!ctx || !count) return SHZ_E_INVALID;
   if (cap && !d_pairs) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_match_pairs: NULL buffer");
   if (nshards == 0 || shard >= nshards) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_match_pairs: shard %u of %u", shard, nshards);
-  if (sid_bits < 1 || delta_bits < 1 || bits_for(n_queries ? n_queries - 1 : 0) + sid_bits + delta_bits + 1 > 64)
+  if (sid_bits < 1 || delta_bits < 1 || delta_bits > 32 ||
+      bits_for(n_queries ? n_queries - 1 : 0) + sid_bits + delta_bits + 1 > 64)
     SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "shz_match_pairs: %u queries x %u sid bits x %u delta bits do not fit 64 bits", n_queries, sid_bits, delta_bits);
   pair_sink sink{d_pairs, cap, 0, m_bits{(int)sid_bits, (int)delta_bits, 0, bias}, shard, nshards};
   SHZ_TRY(match_core(ctx, t, key32, q_off, query_off, n_queries, 1, flags, nullptr, nullptr, nullptr, nullptr, nullptr,
@@ -2748,6 +2756,7 @@ extern "C" int32_t shz_pairs_vote(shz_ctx* ctx, uint64_t* d_pairs, uint64_t n, u
   if (n >= (1ull << 32)) SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "shz_pairs_vote: %llu votes (limit 2^32); vote fewer queries per call", (unsigned long long)n);
   m_bits mb{(int)sid_bits, (int)delta_bits, bits_for(n_queries - 1), bias};
   if (sid_bits < 1 || delta_bits < 1 || mb.qb + mb.sb + mb.dbits + 1 > 64) SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "shz_pairs_vote: key layout does not fit 64 bits");
+  if (delta_bits > 32) SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "shz_pairs_vote: %u delta bits (at most 32)", delta_bits);
   const uint64_t nres = (uint64_t)n_queries * topn;
   memset(out_sid, 0, nres * 4); memset(out_delta, 0, nres * 4); memset(out_aligned, 0, nres * 4);
   memset(out_dedup, 0, nres * 4); memset(out_nres, 0, (uint64_t)n_queries * 4);

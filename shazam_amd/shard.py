@@ -50,10 +50,17 @@ def table_maxima(table: "_ffi.Table"):
     return a.value, b.value
 
 
+def _check_offsets(max_off: int):
+    if max_off >= 1 << 31:
+        raise _ffi.ShzError(_ffi.E_UNSUPPORTED, f"the table holds offset {max_off}; offsets must be < 2^31")
+
+
 def vote_layout(max_sid: int, max_off: int, q_off, n_queries: int):
-    """(sid_bits, delta_bits, bias) every shard packs its votes with; raises if the key does not fit 64 bits."""
+    """(sid_bits, delta_bits, bias) every shard packs its votes with; raises if the table holds an offset >= 2^31 (a
+    delta must fit int32) or the key does not fit 64 bits."""
     q_off = np.asarray(q_off)
     bias = int(q_off.max()) if q_off.size else 0
+    _check_offsets(max_off)
     sid_bits, delta_bits = _bits(max_sid), _bits(max_off + bias)
     if _bits(max(n_queries - 1, 0)) + sid_bits + delta_bits + 1 > 64:
         raise _ffi.ShzError(_ffi.E_UNSUPPORTED, f"{n_queries} queries x {sid_bits} song-id bits x {delta_bits} offset bits "
@@ -198,18 +205,46 @@ class ShardedTable:
         self._pbuf, self._pcap = self.ctx.alloc(cap * 8), cap
 
     def match(self, key32, q_off, query_off, topn=2):
-        """Same result dict as ``Table.match`` on the union of all shards."""
-        ctx = self.ctx
+        """Same result dict as ``Table.match`` on the union of all shards.  Like ``Table.match``, queries whose votes do
+        not fit one 64-bit key together are matched in halves; a query with hashes that does not fit alone raises."""
         k = np.ascontiguousarray(key32, np.uint32)
         o = np.ascontiguousarray(q_off, np.uint32)
         qo = np.ascontiguousarray(query_off, np.uint64)
         nq = len(qo) - 1
         mx = [table_maxima(t) for t in self.tables]     # after a shard exchange: maxima of the whole table
-        layout = vote_layout(max(a for a, _ in mx), max(b for _, b in mx), o, nq)
+        max_sid, max_off = max(a for a, _ in mx), max(b for _, b in mx)
+        if nq:
+            _check_offsets(max_off)                     # the table's own limit, whatever the queries (as Table.match)
+        res = {"sid": np.zeros((nq, topn), np.uint32), "delta": np.zeros((nq, topn), np.int32),
+               "aligned": np.zeros((nq, topn), np.uint32), "dedup": np.zeros((nq, topn), np.uint32),
+               "nres": np.zeros(nq, np.uint32), "nhash": np.zeros(nq, np.uint32), "npairs": np.zeros(nq, np.uint64)}
+        self.last_votes = 0
+        todo = [(0, nq)] if nq else []
+        while todo:                                     # ranges of queries, in order (with a communicator: SPMD)
+            qa, qb = todo.pop(0)
+            a, b = int(qo[qa]), int(qo[qb])
+            if a == b:                                  # no hashes: nothing to vote, as in Table.match
+                continue
+            try:
+                layout = vote_layout(max_sid, max_off, o[a:b], qb - qa)
+            except _ffi.ShzError:
+                if qb - qa == 1:
+                    raise
+                mid = qa + (qb - qa) // 2
+                todo[:0] = [(qa, mid), (mid, qb)]
+                continue
+            r = self._match_range(k[a:b], o[a:b], qo[qa:qb + 1] - np.uint64(a), layout, topn)
+            for name in res:
+                res[name][qa:qb] = r[name]
+        return res
+
+    def _match_range(self, k, o, qo, layout, topn):
+        ctx = self.ctx
+        nq = len(qo) - 1
         if self.comm is None:
             n, nhash, npairs = self._votes_into(k, o, qo, nq, layout, list(enumerate(self.tables)))
             res = pairs_vote(ctx, self._pbuf, n, nq, layout, topn)
-            self.last_votes = n
+            self.last_votes += n
         else:
             n, nhash, npairs = self._votes_into(k, o, qo, nq, layout, [(self.comm.rank, self.tables[0])])
             tot = C.c_uint64()
@@ -223,7 +258,7 @@ class ShardedTable:
                 ctx.check(lib().shz_pairs_allgather(self.comm.h, n, ptr(self._pbuf), ptr(gathered), total, C.byref(tot)))
             res = pairs_vote(ctx, gathered, total, nq, layout, topn)
             gathered.free()
-            self.last_votes = total
+            self.last_votes += total
             # nhash / npairs: this rank's share; their sum over the ranks is the unsharded table's value
         res["nhash"], res["npairs"] = nhash, npairs
         return res

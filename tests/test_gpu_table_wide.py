@@ -3,6 +3,8 @@ goes through the generic two-sort path; both must give the same sorted unique ro
 import numpy as np
 import pytest
 
+from test_match_layout_ref import expected_match
+
 pytestmark = pytest.mark.gpu
 
 
@@ -27,7 +29,12 @@ def test_finalize_wide_and_narrow(sid_hi, off_hi):
     qk, qo = key[:50].copy(), (off[:50] % 1000).astype(np.uint32)
     try:
         r = t.match(qk, qo, np.array([0, 50], np.uint64), 3)
-        assert int(r["nhash"][0]) == len(set(zip(qk.tolist(), qo.tolist())))
+        want = expected_match(key, sid, off, qk, qo, np.array([0, 50]), 3)
+        n = int(want["nres"][0])
+        for f in ("nres", "nhash", "npairs"):
+            assert np.array_equal(r[f].astype(np.int64), want[f]), f
+        for f in ("sid", "delta", "aligned", "dedup"):
+            assert np.array_equal(r[f][0, :n].astype(np.int64), want[f][0, :n]), f
     except S.ShzError as e:
         assert e.code == -5
     t.close()
