@@ -1889,29 +1889,48 @@ struct pair_sink {
   uint32_t shard, nshards;  // nshards > 1: only the query hashes this shard owns are looked up
 };
 
-// sort the packed votes, fold every (query, sid) group into one record and pick the top-n per query into device
-// result arrays (r_*: nq*topn / nq entries, zeroed by the caller).  v0 holds the P votes, v1 is scratch of the same size.
-static int32_t vote_fold(shz_ctx* ctx, const uint64_t* vs, uint64_t P, uint32_t nq, m_bits mb, uint32_t topn,
-                         uint64_t* d_tot, uint32_t* r_sid, int32_t* r_delta, uint32_t* r_al, uint32_t* r_dd, uint32_t* r_n);
+// ---- switches: each is read once per process (the tests run every mode in a child process of its own)
+static int env_int(const char* name, int unset) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : unset;
+}
+struct vote_switches {
+  int tiles;    // SHZ_VOTE_TILES: 0 never (neither the vote tiles nor the one-workgroup fold)
+  int vote32;   // SHZ_VOTE32: 0 never, 1 whenever it fits
+};
+static const vote_switches& vote_env() { static const vote_switches sw{env_int("SHZ_VOTE_TILES", -1), env_int("SHZ_VOTE32", -1)}; return sw; }
+static bool vt_stats_env() { static const bool on = env_int("SHZ_VT_STATS", 0) != 0; return on; }
+static bool trace_match_env() { static const bool on = env_int("SHZ_TRACE_MATCH", 0) != 0; return on; }
+// rounds a probe of an LDS table of `slots` entries may take (debug: it gives up after one)
+static uint32_t vt_probe_limit(const shz_ctx* ctx, uint32_t slots) { return (ctx->debug & SHZ_DEBUG_VT_PROBE1) ? 1u : slots; }
 
-static int32_t vote_tail(shz_ctx* ctx, uint64_t* v0, uint64_t* v1, uint64_t P, uint32_t nq, m_bits mb, uint32_t topn,
-                         uint64_t* d_tot, uint32_t* r_sid, int32_t* r_delta, uint32_t* r_al, uint32_t* r_dd, uint32_t* r_n) {
-  int sel = 0;
-  // bit 0 (the first-offset flag) is only counted by the fold, never compared: it stays out of the sort
-  if (P <= MH_MAX) {
-    hipLaunchKernelGGL(m_sort_small_kernel, dim3(1), dim3(MH_THREADS), 0, ctx->stream, (const uint64_t*)v0, v1, (uint32_t)P, 1,
-                       mb.qb + mb.sb + mb.dbits + 1);
-    SHZ_HIP(ctx, hipGetLastError());
-    sel = 1;
-  } else {
-    SHZ_TRY(shz_sort_u64(ctx, v0, v1, nullptr, nullptr, 0, P, 1, mb.qb + mb.sb + mb.dbits + 1, &sel));
-  }
-  return vote_fold(ctx, sel ? v1 : v0, P, nq, mb, topn, d_tot, r_sid, r_delta, r_al, r_dd, r_n);
+// ---- the results and per-query counters of a sub-batch live in ONE block, on the device (zeroed by the probe) and in
+// the host copy of it:  npairs[nq] u64 | sid, delta, aligned, dedup [nres = nq * topn] u32 each | nres[nq] | nhash[nq] |
+// vt_err (and a pad word).  Callers with arrays of their own (shz_pairs_vote) fill the same views by hand.
+struct res_block {
+  uint64_t* npairs;
+  uint32_t* sid;
+  int32_t* delta;
+  uint32_t *aligned, *dedup, *nres, *nhash;
+  uint32_t* vt_err;   // set by a vote-tile kernel whose LDS table or range list overflowed: the votes go through the full sort again
+};
+static uint64_t res_block_bytes(uint32_t nq, uint64_t nres) { return (uint64_t)nq * 8 + nres * 16 + (uint64_t)nq * 8 + 8; }
+static res_block res_block_at(void* base, uint32_t nq, uint64_t nres) {
+  uint32_t* w = (uint32_t*)((uint64_t*)base + nq);
+  return res_block{(uint64_t*)base, w, (int32_t*)(w + nres), w + 2 * nres, w + 3 * nres, w + 4 * nres, w + 4 * nres + nq,
+                   w + 4 * nres + 2 * (uint64_t)nq};
+}
+// the rows of query qa and those behind it (what a vote pass over [qa, qb) writes)
+static res_block res_rows(res_block r, uint32_t qa, uint32_t topn) {
+  const uint64_t o = (uint64_t)qa * topn;
+  r.sid += o; r.delta += o; r.aligned += o; r.dedup += o;
+  r.nres += qa;
+  return r;
 }
 
-// sorted votes -> one record per (query, song) group -> top-n per query
-static int32_t vote_fold(shz_ctx* ctx, const uint64_t* vs, uint64_t P, uint32_t nq, m_bits mb, uint32_t topn,
-                         uint64_t* d_tot, uint32_t* r_sid, int32_t* r_delta, uint32_t* r_al, uint32_t* r_dd, uint32_t* r_n) {
+// sorted votes -> one record per (query, song) group -> top-n per query, into the device rows r (zeroed by the caller)
+static int32_t vote_fold(shz_ctx* ctx, const uint64_t* vs, uint64_t P, uint32_t nq, m_bits mb, uint32_t topn, uint64_t* d_tot,
+                         const res_block& r) {
   // group heads per wave -> first record slot of every wave -> one record per (query, sid) group
   const uint32_t nb = nblk((P + RG_PER - 1) / RG_PER), nw = nb * 4;
   void *wc, *gh, *gd, *gdd;
@@ -1938,7 +1957,7 @@ static int32_t vote_fold(shz_ctx* ctx, const uint64_t* vs, uint64_t P, uint32_t 
   const uint32_t C = (uint32_t)std::min<uint64_t>(512, (P / nq + 16383) / 16384);
   if (C <= 1) {
     hipLaunchKernelGGL(m_topn_kernel, dim3(nq), dim3(256), 0, ctx->stream, (const uint32_t*)qstart, d_G, mb, (const uint64_t*)gh,
-                       (const uint32_t*)gd, (const uint32_t*)gdd, nq, topn, r_sid, r_delta, r_al, r_dd, r_n);
+                       (const uint32_t*)gd, (const uint32_t*)gdd, nq, topn, r.sid, r.delta, r.aligned, r.dedup, r.nres);
   } else {
     void *pp, *pr;
     const uint64_t ncand = (uint64_t)C * topn;
@@ -1947,10 +1966,27 @@ static int32_t vote_fold(shz_ctx* ctx, const uint64_t* vs, uint64_t P, uint32_t 
     hipLaunchKernelGGL(m_topn_partial_kernel, dim3(C, nq), dim3(256), 0, ctx->stream, (const uint32_t*)qstart, d_G, nq,
                        (const uint64_t*)gh, topn, (uint64_t*)pp, (uint32_t*)pr);
     hipLaunchKernelGGL(m_topn_final_kernel, dim3(nq), dim3(256), 0, ctx->stream, (const uint64_t*)pp, (const uint32_t*)pr,
-                       (uint32_t)ncand, mb, (const uint32_t*)gd, (const uint32_t*)gdd, nq, topn, r_sid, r_delta, r_al, r_dd, r_n);
+                       (uint32_t)ncand, mb, (const uint32_t*)gd, (const uint32_t*)gdd, nq, topn, r.sid, r.delta, r.aligned, r.dedup,
+                       r.nres);
   }
   SHZ_HIP(ctx, hipGetLastError());
   return SHZ_OK;
+}
+
+// the full sort: sort the packed 8-byte votes, then vote_fold.  v0 holds the P votes, v1 is scratch of the same size.
+static int32_t vote_tail(shz_ctx* ctx, uint64_t* v0, uint64_t* v1, uint64_t P, uint32_t nq, m_bits mb, uint32_t topn,
+                         uint64_t* d_tot, const res_block& r) {
+  int sel = 0;
+  // bit 0 (the first-offset flag) is only counted by the fold, never compared: it stays out of the sort
+  if (P <= MH_MAX) {
+    hipLaunchKernelGGL(m_sort_small_kernel, dim3(1), dim3(MH_THREADS), 0, ctx->stream, (const uint64_t*)v0, v1, (uint32_t)P, 1,
+                       mb.qb + mb.sb + mb.dbits + 1);
+    SHZ_HIP(ctx, hipGetLastError());
+    sel = 1;
+  } else {
+    SHZ_TRY(shz_sort_u64(ctx, v0, v1, nullptr, nullptr, 0, P, 1, mb.qb + mb.sb + mb.dbits + 1, &sel));
+  }
+  return vote_fold(ctx, sel ? v1 : v0, P, nq, mb, topn, d_tot, r);
 }
 
 // ---- one vote-tile pass, in two steps so that the producer of the votes may use the plan (m_expand_blocks_kernel counts the
@@ -1993,15 +2029,13 @@ static void vt_make_plan(const uint64_t* counts, uint32_t nqp, const m_bits& mbp
 }
 
 // the pass itself: the pp votes in k32 (4 bytes each, no query bits, query by query as the plan says; k32_alt = the second
-// buffer of the sort) -> two radix passes (the first one already counted: hist0) -> tiles -> per-query top-n in
-// rs / rdl / ra / rd / rn (rows of the pass's first query).  *d_vt_err is set when a tile gave up (the caller repeats the
-// votes through the full sort).
+// buffer of the sort) -> two radix passes (the first one already counted: hist0) -> tiles -> per-query top-n in the rows r
+// (those of the pass's first query).  *r.vt_err is set when a tile gave up (the caller repeats the votes through the full
+// sort).
 static int32_t vt_run_pass(shz_ctx* ctx, uint32_t* k32, uint32_t* k32_alt, uint64_t pp, const vt_plan& pl, const shz_seg_plan& sp,
-                           const m_bits& mbp, uint32_t topn, bool hist0, uint32_t max_sid, uint32_t* d_vt_err, uint32_t* rs,
-                           int32_t* rdl, uint32_t* ra, uint32_t* rd, uint32_t* rn) {
+                           const m_bits& mbp, uint32_t topn, bool hist0, uint32_t max_sid, const res_block& r) {
   const uint32_t nqp = pl.nq;
   const int Bt = mbp.sb + mbp.dbits + 1;
-  const uint32_t vt_probe_limit_1 = (ctx->debug & SHZ_DEBUG_VT_PROBE1) ? 1u : 0u;   // debug: a probe gives up after one round
   const uint32_t nt = pl.tb[nqp], hcap = (ctx->debug & SHZ_DEBUG_VT_TINY_HEAVY) ? 1u : nt * (VW_HEAVY_PER_TILE * ((pl.tile + VW_CHUNK - 1) / VW_CHUNK));
   int sel = 0;
   SHZ_TRY(shz_sort_u32_seg(ctx, k32, k32_alt, pp, pl.g_lo, Bt, sp, &sel, hist0));
@@ -2026,10 +2060,9 @@ static int32_t vt_run_pass(shz_ctx* ctx, uint32_t* k32, uint32_t* k32_alt, uint6
   const int slb_ = pl.g_lo - 1 - mbp.dbits;
   const double per_song = std::max(1.0, (double)pp / nqp / std::max<uint32_t>(max_sid, 1u));
   const bool few_songs = (double)(1u << slb_) + (double)pl.flush / per_song <= 40.0;
-  const uint32_t plim = vt_probe_limit_1 ? vt_probe_limit_1 : (uint32_t)VW_S1;
-  static const bool vt_stats = [] { const char* e = getenv("SHZ_VT_STATS"); return e && atoi(e) != 0; }();
+  const uint32_t plim = vt_probe_limit(ctx, VW_S1);
   unsigned long long* d_stats = nullptr;
-  if (vt_stats) {
+  if (vt_stats_env()) {
     void* p;
     SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_MISC3, 64, &p));
     d_stats = (unsigned long long*)p;
@@ -2037,10 +2070,10 @@ static int32_t vt_run_pass(shz_ctx* ctx, uint32_t* k32, uint32_t* k32_alt, uint6
   }
   if (few_songs)
     hipLaunchKernelGGL(vt_stream2_kernel<7>, dim3(nt), dim3(64), 0, ctx->stream, ks, (const uint32_t*)tile_start, pl, topn,
-                       (uint64_t*)cp, (uint32_t*)cd, (uint32_t*)cdd, n_heavy, heavy, heavy_q, hcap, plim, d_qbar, d_vt_err, d_stats);
+                       (uint64_t*)cp, (uint32_t*)cd, (uint32_t*)cdd, n_heavy, heavy, heavy_q, hcap, plim, d_qbar, r.vt_err, d_stats);
   else
     hipLaunchKernelGGL(vt_stream2_kernel<8>, dim3(nt), dim3(64), 0, ctx->stream, ks, (const uint32_t*)tile_start, pl, topn,
-                       (uint64_t*)cp, (uint32_t*)cd, (uint32_t*)cdd, n_heavy, heavy, heavy_q, hcap, plim, d_qbar, d_vt_err, d_stats);
+                       (uint64_t*)cp, (uint32_t*)cd, (uint32_t*)cdd, n_heavy, heavy, heavy_q, hcap, plim, d_qbar, r.vt_err, d_stats);
   if (d_stats) {
     unsigned long long h[8];
     SHZ_HIP(ctx, hipMemcpyAsync(h, d_stats, 64, hipMemcpyDeviceToHost, ctx->stream));
@@ -2051,524 +2084,710 @@ static int32_t vt_run_pass(shz_ctx* ctx, uint32_t* k32, uint32_t* k32_alt, uint6
   hipLaunchKernelGGL(vt_fold_kernel, dim3(std::min<uint32_t>(hcap, 64u)),
                      dim3(VT_THREADS), 0, ctx->stream, ks, (const uint2*)heavy, (const uint32_t*)n_heavy, hcap, pl, topn,
                      (uint64_t*)cp + (uint64_t)nt * topn, (uint32_t*)cd + (uint64_t)nt * topn,
-                     (uint32_t*)cdd + (uint64_t)nt * topn, vt_probe_limit_1 ? vt_probe_limit_1 : (uint32_t)VT_SLOTS, d_vt_err);
+                     (uint32_t*)cdd + (uint64_t)nt * topn, vt_probe_limit(ctx, VT_SLOTS), r.vt_err);
   hipLaunchKernelGGL(vt_rank_kernel, dim3(nqp), dim3(VR_THREADS), 0, ctx->stream, pl, topn, mbp, (const uint64_t*)cp,
                      (const uint32_t*)cd, (const uint32_t*)cdd, (const uint32_t*)n_heavy, (const uint32_t*)heavy_q, hcap,
-                     rs, rdl, ra, rd, rn);
+                     r.sid, r.delta, r.aligned, r.dedup, r.nres);
   SHZ_HIP(ctx, hipGetLastError());
   return SHZ_OK;
 }
 
-static int32_t match_core(shz_ctx* ctx, shz_table* t, const uint32_t* key32, const uint32_t* q_off,
-                          const uint64_t* query_off, uint32_t n_queries, uint32_t topn, uint32_t flags,
-                          uint32_t* out_sid, int32_t* out_delta, uint32_t* out_aligned, uint32_t* out_dedup,
-                          uint32_t* out_nres, uint32_t* out_nhash, uint64_t* out_npairs, pair_sink* vs_out) {
-  if (!ctx || !t) return SHZ_E_INVALID;
-  if (t->ctx != ctx) SHZ_FAIL(ctx, SHZ_E_INVALID, "table belongs to another ctx");
-  if (pending_rows(t) || (!t->bucket && t->done.empty())) SHZ_FAIL(ctx, SHZ_E_STATE, "table not finalized");
-  if (n_queries == 0) return SHZ_OK;
-  // offsets < 2^31: every delta fits out_delta's int32_t and, biased by a query offset < 2^20, 32 bits
-  if (t->max_off >= (1u << 31))
-    SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "match: the table holds offset %u; offsets must be < 2^31", t->max_off);
-  if (!query_off) SHZ_FAIL(ctx, SHZ_E_INVALID, "match: query_off is NULL");
-  if (!vs_out && (!out_sid || !out_delta || !out_aligned || !out_dedup || !out_nres))
-    SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_match_batch: NULL buffer");
-  if (!vs_out && (topn < 1 || topn > 64)) SHZ_FAIL(ctx, SHZ_E_INVALID, "topn must be in [1,64]");
-  SHZ_HIP(ctx, hipSetDevice(ctx->device));
-  ctx->st_rows = ctx->st_pairs = ctx->st_keys = 0;
-  const uint64_t P_BUDGET = 1ull << 28;     // votes of one vote pass (its buffers: 2 x 4 or 8 bytes per vote)
-  // votes of one sub-batch of queries (one head: compose, sort, probe, one round trip): up to 2^30 where the device has
-  // the memory for it (a sub-batch that ends up on the 8-byte path needs ~32 bytes per vote of workspace)
-  uint64_t SUB_BUDGET = P_BUDGET;
-  if (n_queries > 32) {
-    size_t mem_free = 0, mem_total = 0;
-    if (hipMemGetInfo(&mem_free, &mem_total) == hipSuccess)
-      SUB_BUDGET = std::min<uint64_t>(1ull << 30, std::max<uint64_t>(P_BUDGET, (uint64_t)mem_free / 64));
+// ---- ONE workgroup folds the unordered 4-byte votes of ONE query without any radix pass: vt_fold_kernel over a single
+// range (no tiles), then vt_rank_kernel.  The caller expands the votes and sends the range's end to the device between
+// the two steps below: from the host once the count is known (vt_one_range_kernel), or on the device before it is
+// (m_spec_plan_kernel, the queued fold).
+struct one_wg_fold {
+  vt_plan pl;
+  uint32_t* n_heavy;   // 1 range ...
+  uint2* heavy;        // ... [0, end) ...
+  uint32_t* heavy_q;   // ... of query 0
+  uint64_t* c_pack;    // the range's candidates
+  uint32_t *c_al, *c_dd;
+};
+// pp: the votes of the range where the host knows them (else 0: its end is heavy[0] alone)
+static int32_t one_wg_prepare(shz_ctx* ctx, const m_bits& mb, uint32_t topn, uint32_t pp, one_wg_fold* w) {
+  void *ts, *cp, *cd, *cdd;
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_VT0, 64, &ts));
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_VT1, (uint64_t)topn * 8, &cp));
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_VT2, (uint64_t)topn * 4, &cd));
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_VT3, (uint64_t)topn * 4, &cdd));
+  w->n_heavy = (uint32_t*)ts;
+  w->heavy = (uint2*)(w->n_heavy + 2);
+  w->heavy_q = w->n_heavy + 4;
+  w->c_pack = (uint64_t*)cp;
+  w->c_al = (uint32_t*)cd;
+  w->c_dd = (uint32_t*)cdd;
+  vt_plan& pl = w->pl;
+  pl.nq = 1;
+  pl.dbits = mb.dbits;
+  pl.sb = mb.sb;
+  pl.g_lo = mb.sb + mb.dbits + 1;   // no bit is ordered: a sweep may split by any song-id bit
+  pl.tile = VW_CHUNK;
+  pl.flush = VW_FLUSH;
+  for (uint32_t i = 0; i <= VT_MAXQ; ++i) { pl.qv[i] = i ? pp : 0u; pl.tb[i] = 0; }   // no tiles, one range
+  return SHZ_OK;
+}
+static int32_t one_wg_run(shz_ctx* ctx, const one_wg_fold& w, const uint32_t* k32, const m_bits& mb, uint32_t topn,
+                          const res_block& r) {
+  hipLaunchKernelGGL(vt_fold_kernel, dim3(1), dim3(VT_THREADS), 0, ctx->stream, k32, (const uint2*)w.heavy,
+                     (const uint32_t*)w.n_heavy, 1u, w.pl, topn, w.c_pack, w.c_al, w.c_dd, vt_probe_limit(ctx, VT_SLOTS), r.vt_err);
+  hipLaunchKernelGGL(vt_rank_kernel, dim3(1), dim3(VR_THREADS), 0, ctx->stream, w.pl, topn, mb, (const uint64_t*)w.c_pack,
+                     (const uint32_t*)w.c_al, (const uint32_t*)w.c_dd, (const uint32_t*)w.n_heavy, (const uint32_t*)w.heavy_q, 1u,
+                     r.sid, r.delta, r.aligned, r.dedup, r.nres);
+  SHZ_HIP(ctx, hipGetLastError());
+  return SHZ_OK;
+}
+
+// ---- which way the votes of a sub-batch go: decided HERE, from numbers alone
+enum vote_route {
+  ROUTE_NONE,          // no votes: the zeroed result block is the answer
+  ROUTE_QUEUED,        // ONE small host-fed query: folded by one workgroup, queued before its vote count was known
+  ROUTE_SINK,          // shz_match_pairs: 8-byte votes in the caller's layout, into the caller's buffer
+  ROUTE_ONE_WG,        // ONE query with few votes: expand, one workgroup folds the unordered 4-byte votes
+  ROUTE_TILES_FUSED,   // 4-byte votes through the vote tiles; the expand runs by the sort's blocks and counts its first pass
+  ROUTE_TILES,         // 4-byte votes through the vote tiles, expand and sort apart
+  ROUTE_WIDEN,         // 4-byte votes (query bits inside), sorted and widened into the full sort's fold
+  ROUTE_SORT64,        // 8-byte votes through the full sort, one pass over all queries
+};
+struct vote_pass { uint32_t qa, qb; uint64_t v_lo, v_hi; };   // queries [qa, qb), their votes [v_lo, v_hi) of the sub-batch
+struct vote_plan {
+  vote_route route = ROUTE_NONE;
+  uint32_t fuse_dmask = 0;          // ROUTE_TILES_FUSED: digit mask of the sort's first pass
+  std::vector<vote_pass> passes;
+};
+struct vote_case {
+  uint32_t nq;             // queries of the sub-batch
+  uint64_t P;              // its votes ...
+  const uint64_t* votes;   // ... per query
+  m_bits mb;
+  uint32_t topn;
+  bool full_sort;          // SHZ_MATCH_FULL_SORT, or the tiles gave up on these queries: once more, through the full sort
+  bool sink;               // the votes leave as they are (shz_match_pairs)
+  bool queued_held;        // the fold queued ahead of the count ran on the right layout
+  vote_switches sw;
+};
+
+static const uint64_t VOTE_PASS_MAX = 1ull << 28;   // votes of one vote pass (its buffers: 2 x 4 or 8 bytes per vote)
+
+// song id, biased delta and the flag bit of a vote in vote_bits bits (the query bits not counted)
+static bool vote_fits_bits(const m_bits& mb, int vote_bits) { return mb.sb + mb.dbits + 1 <= vote_bits; }
+// what the LDS folds (vt_fold_kernel: the vote tiles, the one-workgroup fold) take: a 4-byte vote, top-n and delta bits
+// within their tables' reach.  vote_bits: 32 where the expand writes the votes; 31 for the gathered votes of a sharded
+// match, which have always kept one bit in hand (shz_pairs_vote chooses as it did before it shared this rule).
+static bool vt_layout_fits(const m_bits& mb, uint32_t topn, const vote_switches& sw, int vote_bits = 32) {
+  return vote_fits_bits(mb, vote_bits) && topn <= VT_MAXTOPN && mb.dbits <= VT_MAX_DBITS + VT_MAX_DSPLIT && sw.tiles != 0;
+}
+// ... and of them the one-workgroup fold: a single query, unless the full sort is asked for.  (Its vote limit,
+// VT_ONE_WG_MAX, is the caller's to check: the queued fold decides before the count exists.)
+static bool one_wg_fits(uint32_t nq, const m_bits& mb, uint32_t topn, bool full_sort, const vote_switches& sw) {
+  return nq == 1 && !full_sort && vt_layout_fits(mb, topn, sw);
+}
+
+// the next vote pass behind *vp (first call: all zero): as many queries as q_max and VOTE_PASS_MAX votes allow, one query
+// at the least.  The rule of every route that votes in passes; a pass may come out without votes.  false: no query is left.
+static bool next_vote_pass(const uint64_t* votes, uint32_t nq, uint32_t q_max, vote_pass* vp) {
+  if (vp->qb >= nq) return false;
+  vp->qa = vp->qb;
+  vp->v_lo = vp->v_hi;
+  do vp->v_hi += votes[vp->qb++];
+  while (vp->qb < nq && vp->qb - vp->qa < q_max && vp->v_hi - vp->v_lo + votes[vp->qb] <= VOTE_PASS_MAX);
+  return true;
+}
+
+static void vote_plan_make(const vote_case& c, vote_plan* plan) {
+  plan->passes.clear();
+  plan->fuse_dmask = 0;
+  if (c.queued_held) { plan->route = ROUTE_QUEUED; return; }
+  if (c.P == 0) { plan->route = ROUTE_NONE; return; }
+  if (c.sink) { plan->route = ROUTE_SINK; return; }
+  // expand -> sort -> groups -> top-n, in vote passes over ranges of queries.  4-BYTE votes when a pass's query
+  // index, the song id and the biased delta fit 31 bits (1M songs x 10 s queries: 1 + 20 + 10): half the bytes
+  // through expand and the sort passes, whose last pass widens to the 64-bit layout the fold reads.  Worth it only
+  // while a pass still has millions of votes; else one 8-byte pass over all queries.
+  const int qbits32 = 31 - c.mb.sb - c.mb.dbits;
+  bool use32 = vote_fits_bits(c.mb, 32) && c.P > MH_MAX && c.sw.vote32 != 0 && !c.full_sort;
+  // vote tiles (vt_fold_kernel): two radix passes + an LDS fold per tile instead of four passes + the record chain
+  const bool tiles = use32 && vt_layout_fits(c.mb, c.topn, c.sw);
+  if (use32) {
+    const uint32_t q_max = tiles ? (uint32_t)VT_MAXQ : (1u << std::min(qbits32, 30));   // tiles: no query bits in the vote
+    vote_pass vp{0, 0, 0, 0};
+    while (next_vote_pass(c.votes, c.nq, q_max, &vp))
+      if (vp.v_hi > vp.v_lo) plan->passes.push_back(vp);
+    if (c.sw.vote32 != 1 && c.P / std::max<size_t>(plan->passes.size(), 1) < (1ull << 22)) use32 = false;   // small passes: launch-bound
   }
+  if (!use32) {
+    plan->passes.clear();
+    plan->passes.push_back(vote_pass{0, c.nq, 0, c.P});
+    // ONE query with few votes (a 5-10 s query against thousands of songs): expand, then one workgroup folds the
+    // unordered votes (vt_fold_kernel over the single range [0, P)) -- 5 launches instead of the 9 of sort + fold,
+    // and the launches are what such a match costs
+    const bool one_wg = c.P <= VT_ONE_WG_MAX && one_wg_fits(c.nq, c.mb, c.topn, c.full_sort, c.sw);
+    plan->route = one_wg ? ROUTE_ONE_WG : ROUTE_SORT64;
+    return;
+  }
+  if (!tiles) { plan->route = ROUTE_WIDEN; return; }
+  // vote tiles: where the sort's first pass takes 8 bits, the expand runs by the blocks of the segmented sort and counts
+  // that pass's digits (no tile starts then: m_chunk_start_kernel per pass)
+  const int Bt = c.mb.sb + c.mb.dbits + 1, g_lo = std::max(1 + c.mb.dbits, Bt - VT_ORDERED_BITS);
+  plan->route = shz_seg_first_pass(g_lo, Bt, &plan->fuse_dmask) == 8 ? ROUTE_TILES_FUSED : ROUTE_TILES;
+}
+
+// ---- a match call, and what one of its sub-batches carries from stage to stage
+struct match_call {
+  shz_ctx* ctx;
+  shz_table* t;
+  const uint32_t *key32, *q_off;   // host or device (SHZ_IN_DEVICE)
+  const uint64_t* query_off;       // host
+  uint32_t n_queries, topn, flags;
+  uint32_t* out_sid;
+  int32_t* out_delta;
+  uint32_t *out_aligned, *out_dedup, *out_nres, *out_nhash;
+  uint64_t* out_npairs;
+  pair_sink* sink;
+  // the query set on the device (match_upload)
+  const uint32_t *d_key, *d_qo;
+  const shz_seg_dev* d_segs;
+  uint32_t nseg;
+  const uint64_t* d_qoff_all;   // query_off[0 .. n_queries] on the device, when it went with the packed upload
+  mctl* d_ctl_packed;           // ... and a zeroed control block for the first sub-batch
+  uint64_t sub_budget;          // votes of one sub-batch
+};
+enum sub_next {
+  SUB_GO,          // on to the next stage
+  SUB_EMPTY,       // no hash of these queries is looked up here: their counters are zero, on to the next queries
+  SUB_FEWER,       // too much for one sub-batch: the same queries' first half
+  SUB_FULL_SORT,   // the LDS fold gave up (its results are void): the same queries again, through the full sort
+  SUB_DONE,        // results and counters are with the caller
+};
+struct match_sub {
+  uint32_t q0, nq;
+  uint64_t m;                // hashes of the queries [q0, q0 + nq)
+  bool redo, full_sort;      // second visit after SUB_FULL_SORT; ... or the caller asked for the full sort
+  m_bits mb;                 // sb from the table, qb from nq; bias and dbits once the counts are back
+  // head
+  const uint64_t* d_qoff;
+  mctl* d_ctl;
+  uint64_t nx_bound;         // sub-groups (group x segment) + sentinel, from the bound groups <= m
+  uint64_t* E;               // unique (query, key, offset) elements
+  uint32_t *gs, *glo;        // first element of every group; first row of every sub-group
+  uint64_t* po;              // votes in front of every sub-group
+  void* rb;                  // the result block ...
+  uint64_t nres, rb_bytes;
+  res_block r;               // ... and its views
+  bool queued;               // one-workgroup fold queued ahead of the count ...
+  uint32_t queued_bias;      // ... on this bias
+  // counts (sub_read_counts)
+  void* mail;                // control block | votes per query | result block of a queued fold
+  uint64_t mu, P, nx, rows_total;
+  uint32_t ng;
+  std::vector<uint64_t> votes;   // per query
+  double tr[4];              // SHZ_TRACE_MATCH: start, head queued, counts back, votes queued
+};
+
+// The query set on the device, once.  Host input of moderate size travels as ONE copy from pinned memory:
+// segment descriptors | query offsets | keys | offsets | a zeroed mctl (every separate small copy costs ~20 us of latency)
+static int32_t match_upload(match_call& mc) {
+  shz_ctx* ctx = mc.ctx;
   // segment descriptors for the kernels (an empty table probes one empty segment)
   std::vector<shz_seg_dev> hsegs;
-  for (const shz_seg& g : all_segs(t)) hsegs.push_back(seg_dev_of(g));
-  if (hsegs.empty()) hsegs.push_back(shz_seg_dev{nullptr, nullptr, nullptr, t->bucket, 0u, 0u, 0ull});
-  const int nseg = (int)hsegs.size();
-  m_bits mb;
-  mb.sb = bits_for(t->max_sid);
-  mb.dbits = 0;
-  mb.bias = 0;
-  // the query set on the device once.  Host input of moderate size travels as ONE copy from pinned memory:
-  // segment descriptors | query offsets | keys | offsets (every separate small copy costs ~20 us of latency)
-  const uint64_t h0 = query_off[0], h1 = query_off[n_queries];
-  const uint32_t *d_key = key32, *d_qo = q_off;
-  void* d_segs;
-  const uint64_t* d_qoff_all = nullptr;   // query_off[0 .. n_queries] on the device, when it went with the packed upload
-  mctl* d_ctl_packed = nullptr;           // ... and a zeroed control block for the first sub-batch
+  for (const shz_seg& g : all_segs(mc.t)) hsegs.push_back(seg_dev_of(g));
+  if (hsegs.empty()) hsegs.push_back(shz_seg_dev{nullptr, nullptr, nullptr, mc.t->bucket, 0u, 0u, 0ull});
+  const uint32_t nseg = mc.nseg = (uint32_t)hsegs.size();
+  const bool host_in = !(mc.flags & SHZ_IN_DEVICE);
+  const uint64_t h1 = mc.query_off[mc.n_queries];
+  mc.d_key = mc.key32;
+  mc.d_qo = mc.q_off;
+  mc.d_qoff_all = nullptr;
+  mc.d_ctl_packed = nullptr;
   const uint64_t seg_bytes = (sizeof(shz_seg_dev) * (uint64_t)nseg + 255) & ~255ull;
-  const uint64_t qoff_bytes = (((uint64_t)n_queries + 1) * 8 + 255) & ~255ull;
-  const uint64_t pk_bytes = seg_bytes + qoff_bytes + ((h1 * 4 + 255) & ~255ull) * 2 + 256;   // + a zeroed mctl at the end
-  if (!(flags & SHZ_IN_DEVICE) && pk_bytes <= (4ull << 20)) {
+  const uint64_t qoff_bytes = (((uint64_t)mc.n_queries + 1) * 8 + 255) & ~255ull;
+  const uint64_t col_bytes = (h1 * 4 + 255) & ~255ull;
+  const uint64_t pk_bytes = seg_bytes + qoff_bytes + col_bytes * 2 + 256;
+  void* d_segs;
+  if (host_in && pk_bytes <= (4ull << 20)) {
     void *hm, *dm;
     SHZ_TRY(shz_mailbox(ctx, pk_bytes, &hm));
     SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_KEY, pk_bytes, &dm));
     char* hp = (char*)hm;
     memcpy(hp, hsegs.data(), sizeof(shz_seg_dev) * nseg);
-    memcpy(hp + seg_bytes, query_off, ((uint64_t)n_queries + 1) * 8);
-    const uint64_t ko = seg_bytes + qoff_bytes, oo = ko + ((h1 * 4 + 255) & ~255ull);
+    memcpy(hp + seg_bytes, mc.query_off, ((uint64_t)mc.n_queries + 1) * 8);
+    const uint64_t ko = seg_bytes + qoff_bytes, oo = ko + col_bytes;
     if (h1) {
-      memcpy(hp + ko, key32, h1 * 4);
-      memcpy(hp + oo, q_off, h1 * 4);
+      memcpy(hp + ko, mc.key32, h1 * 4);
+      memcpy(hp + oo, mc.q_off, h1 * 4);
     }
     memset(hp + pk_bytes - 256, 0, 256);
-    d_ctl_packed = (mctl*)((char*)dm + pk_bytes - 256);
     SHZ_HIP(ctx, hipMemcpyAsync(dm, hm, pk_bytes, hipMemcpyHostToDevice, ctx->stream));
     d_segs = dm;
-    d_qoff_all = (const uint64_t*)((char*)dm + seg_bytes);
-    d_key = (const uint32_t*)((char*)dm + ko);
-    d_qo = (const uint32_t*)((char*)dm + oo);
+    mc.d_qoff_all = (const uint64_t*)((char*)dm + seg_bytes);
+    mc.d_key = (const uint32_t*)((char*)dm + ko);
+    mc.d_qo = (const uint32_t*)((char*)dm + oo);
+    mc.d_ctl_packed = (mctl*)((char*)dm + pk_bytes - 256);
   } else {
     SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_META, sizeof(shz_seg_dev) * SHZ_MAX_SEGS, &d_segs));
     SHZ_HIP(ctx, shz_memcpy(ctx, d_segs, hsegs.data(), sizeof(shz_seg_dev) * nseg, hipMemcpyHostToDevice));
-    if (!(flags & SHZ_IN_DEVICE) && h1 > 0) {
+    if (host_in && h1 > 0) {
       void *a, *b;
       SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_KEY, h1 * 4, &a));
       SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_T1, h1 * 4, &b));
-      SHZ_HIP(ctx, shz_memcpy(ctx, a, key32, h1 * 4, hipMemcpyHostToDevice));
-      SHZ_HIP(ctx, shz_memcpy(ctx, b, q_off, h1 * 4, hipMemcpyHostToDevice));
-      d_key = (const uint32_t*)a;
-      d_qo = (const uint32_t*)b;
+      SHZ_HIP(ctx, shz_memcpy(ctx, a, mc.key32, h1 * 4, hipMemcpyHostToDevice));
+      SHZ_HIP(ctx, shz_memcpy(ctx, b, mc.q_off, h1 * 4, hipMemcpyHostToDevice));
+      mc.d_key = (const uint32_t*)a;
+      mc.d_qo = (const uint32_t*)b;
     }
   }
-  (void)h0;
-  uint32_t q0 = 0;
+  mc.d_segs = (const shz_seg_dev*)d_segs;
+  return SHZ_OK;
+}
+
+// queries of the next sub-batch: at most `step`, fewer where the votes or the hashes would be too many
+static uint32_t sub_queries(const match_call& mc, uint32_t q0, uint32_t step) {
+  const uint64_t* query_off = mc.query_off;
+  uint32_t nq = std::min<uint32_t>(step, mc.n_queries - q0);
+  // the vote budget: sized from what a hash yielded in the last sub-batch, so that the head (compose, sort, probe: a
+  // round trip) is not run on 200 queries, then 100, then 50 to find that 25 fit
+  if (mc.ctx->m_votes_per_hash > 0.0 && nq > 1) {
+    const double hashes = (double)mc.sub_budget / (1.05 * mc.ctx->m_votes_per_hash);
+    uint32_t lo = 1, hi = nq;   // largest count whose hashes stay under the estimate
+    while (lo < hi) {
+      const uint32_t mid = (lo + hi + 1) >> 1;
+      if ((double)(query_off[q0 + mid] - query_off[q0]) <= hashes) lo = mid; else hi = mid - 1;
+    }
+    nq = lo;
+  }
+  // shrink so the element count stays sortable
+  while (nq > 1 && query_off[q0 + nq] - query_off[q0] >= (1ull << 31)) nq /= 2;
+  return nq;
+}
+
+// many hashes: compose (query, key, offset) elements, sort, unique -> E (mu of them); groups = distinct (query, key) -> gs
+// (ng of them) -- queued without a host round trip in between: every launch is sized by the bound m, the counts are read
+// on the device (mctl)
+static int32_t head_sorted(const match_call& mc, match_sub& s, void* c0, void* c1) {
+  shz_ctx* ctx = mc.ctx;
+  const uint64_t m = s.m;
+  const uint32_t f_nsh = mc.sink ? mc.sink->nshards : 1u, f_sh = mc.sink ? mc.sink->shard : 0u;
+  uint64_t* tot = (uint64_t*)s.d_ctl;   // tot[0..1] = mu, ng
+  void *fl, *ps;
+  hipLaunchKernelGGL(m_compose_kernel, dim3(nblk(m)), dim3(256), 0, ctx->stream, mc.d_key, mc.d_qo, s.d_qoff, s.nq, m, f_nsh,
+                     f_sh, (uint64_t*)c0, s.d_ctl->err);
+  SHZ_HIP(ctx, hipGetLastError());
+  int sel = 0;
+  SHZ_TRY(shz_sort_u64(ctx, (uint64_t*)c0, (uint64_t*)c1, nullptr, nullptr, 0, m, 0,
+                       QIDX_SHIFT + (f_nsh > 1 ? bits_for(s.nq) : s.mb.qb), &sel));
+  const uint64_t* cs = sel ? (uint64_t*)c1 : (uint64_t*)c0;   // sorted
+  uint64_t* E = s.E = sel ? (uint64_t*)c0 : (uint64_t*)c1;    // unique elements go to the other buffer
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_M1, m * 4, &fl));
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_M2, m * 4, &ps));
+  hipLaunchKernelGGL(m_head_flag_kernel, dim3(nblk(m)), dim3(256), 0, ctx->stream, cs, m, 0, (uint32_t*)fl);
+  SHZ_TRY(shz_scan_u32(ctx, (const uint32_t*)fl, (uint32_t*)ps, m, tot));
+  hipLaunchKernelGGL(m_compact_vals_kernel, dim3(nblk(m)), dim3(256), 0, ctx->stream, cs, (const uint32_t*)fl,
+                     (const uint32_t*)ps, m, E);
+  hipLaunchKernelGGL(m_fix_mu_kernel, dim3(1), dim3(1), 0, ctx->stream, s.d_ctl, (unsigned long long)m);
+  hipLaunchKernelGGL(m_head_flag_dn_kernel, dim3(nblk(m)), dim3(256), 0, ctx->stream, (const uint64_t*)E, &s.d_ctl->mu, m,
+                     QKEY_SHIFT, (uint32_t*)fl);
+  SHZ_TRY(shz_scan_u32(ctx, (const uint32_t*)fl, (uint32_t*)ps, m, tot + 1));
+  hipLaunchKernelGGL(m_compact_idx_kernel, dim3(nblk(m)), dim3(256), 0, ctx->stream, (const uint32_t*)fl, (const uint32_t*)ps,
+                     &s.d_ctl->mu, m, &s.d_ctl->ng, s.gs);
+  return SHZ_OK;
+}
+
+// head of a sub-batch: its query offsets and a zeroed control block; elements and groups (head_sorted, or
+// m_head_small_kernel in one launch); the probe, which also zeroes the result block; the scan of the votes per sub-group
+static int32_t sub_head(match_call& mc, match_sub& s, sub_next* next) {
+  shz_ctx* ctx = mc.ctx;
+  const uint32_t q0 = s.q0, nq = s.nq;
+  const uint64_t m = s.m;
+  if (mc.d_qoff_all) {
+    s.d_qoff = mc.d_qoff_all + q0;
+  } else {
+    void* p;
+    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_M0, (uint64_t)(nq + 1) * 8, &p));
+    SHZ_HIP(ctx, shz_memcpy(ctx, p, mc.query_off + q0, (uint64_t)(nq + 1) * 8, hipMemcpyHostToDevice));
+    s.d_qoff = (const uint64_t*)p;
+  }
+  if (mc.d_ctl_packed && q0 == 0) {
+    s.d_ctl = mc.d_ctl_packed;          // arrived zeroed with the upload
+    mc.d_ctl_packed = nullptr;          // (a retry with fewer queries, or a later sub-batch, zeroes its own)
+  } else {
+    void* p;
+    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_MISC0, 256, &p));
+    SHZ_HIP(ctx, hipMemsetAsync(p, 0, 256, ctx->stream));
+    s.d_ctl = (mctl*)p;
+  }
+  if (m == 0) { *next = SUB_EMPTY; return SHZ_OK; }
+  s.nx_bound = m * (uint64_t)mc.nseg + 1;
+  if (s.nx_bound >= (1ull << 32)) {
+    if (nq > 1) { *next = SUB_FEWER; return SHZ_OK; }
+    SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "query %u: %llu hashes x %u segments", q0, (unsigned long long)m, mc.nseg);
+  }
+  void *c0, *c1, *gs, *glo, *gpairs, *po;
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SORT_A, m * 8, &c0));
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SORT_B, m * 8, &c1));
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_M3, (m + 1) * 4, &gs));
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_M4, s.nx_bound * 4, &glo));
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_M6, s.nx_bound * 8, &gpairs));
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_M7, s.nx_bound * 8, &po));
+  s.gs = (uint32_t*)gs;
+  s.glo = (uint32_t*)glo;
+  s.po = (uint64_t*)po;
+  if (!(mc.sink && mc.sink->nshards > 1) && m <= MH_MAX) {
+    s.E = (uint64_t*)c1;
+    hipLaunchKernelGGL(m_head_small_kernel, dim3(1), dim3(MH_THREADS), 0, ctx->stream, mc.d_key, mc.d_qo, s.d_qoff, nq,
+                       (uint32_t)m, QIDX_SHIFT + s.mb.qb, s.E, s.gs, s.d_ctl);
+    SHZ_HIP(ctx, hipGetLastError());
+  } else {
+    SHZ_TRY(head_sorted(mc, s, c0, c1));
+  }
+  s.nres = (uint64_t)nq * (mc.sink ? 0 : mc.topn);
+  s.rb_bytes = res_block_bytes(nq, s.nres);
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_PEAK_F, s.rb_bytes + 64, &s.rb));
+  s.r = res_block_at(s.rb, nq, s.nres);
+  hipLaunchKernelGGL(m_probe_kernel, dim3(nblk(s.nx_bound)), dim3(256), 0, ctx->stream, (const uint64_t*)s.E,
+                     (const uint32_t*)s.gs, &s.d_ctl->ng, s.nx_bound, mc.d_segs, mc.nseg, s.glo, (uint64_t*)gpairs,
+                     (unsigned long long*)s.d_ctl + 16, (uint32_t*)s.rb, (uint32_t)((s.rb_bytes + 3) / 4));
+  SHZ_HIP(ctx, hipGetLastError());
+  SHZ_TRY(shz_scan_u64(ctx, (const uint64_t*)gpairs, s.po, s.nx_bound, (uint64_t*)&s.d_ctl->P));
+  return SHZ_OK;
+}
+
+// ONE small query from host memory: its votes are queued now, before their number is known (m_spec_plan_kernel puts the
+// range's end where the one-workgroup fold reads it, and voids the fold where the votes exceed VT_ONE_WG_MAX), under the
+// conditions of ROUTE_ONE_WG.  What differs from that route is what the host cannot know yet: the vote count (the table's
+// last match stands in for it), and the bias, which it has to take from the query itself -- so host input only.
+static int32_t sub_queue_fold(const match_call& mc, match_sub& s) {
+  shz_ctx* ctx = mc.ctx;
+  const vote_switches& sw = vote_env();
+  s.queued = false;
+  s.queued_bias = 0;
+  // (vote32 == 1 would send P > MH_MAX votes through a 4-byte pass instead; the layout test with the bias still 0 is the
+  // least it can need: it saves the walk over the offsets)
+  if (mc.sink || (mc.flags & SHZ_IN_DEVICE) || s.m > MH_MAX || sw.vote32 == 1 ||
+      !one_wg_fits(s.nq, s.mb, mc.topn, s.full_sort, sw) ||
+      (double)s.m * mc.t->votes_per_hash > 2.0 * VT_ONE_WG_MAX)   // (a table whose last query had far more votes: not worth queueing)
+    return SHZ_OK;
+  bool wide = false;
+  for (uint64_t i = mc.query_off[s.q0]; i < mc.query_off[s.q0 + 1]; ++i) {
+    s.queued_bias = std::max(s.queued_bias, mc.q_off[i]);
+    wide |= mc.q_off[i] >= (1u << QOFF_BITS);
+  }
+  m_bits ms = s.mb;
+  ms.qb = 0;
+  ms.bias = s.queued_bias;
+  ms.dbits = bits_for((uint64_t)mc.t->max_off + ms.bias);
+  if (wide || !one_wg_fits(s.nq, ms, mc.topn, s.full_sort, sw)) return SHZ_OK;
+  s.queued = true;
+  ++ctx->st_spec_queued;
+  const uint64_t cap = VT_ONE_WG_MAX;
+  const uint32_t cap_tiles = (uint32_t)((cap + M_EXP_TILE - 1) / M_EXP_TILE);
+  void *tx, *k32;
+  one_wg_fold w;
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_HCNT, ((uint64_t)cap_tiles + 1) * 4, &tx));
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SORT_C, cap * 8 + 16, &k32));
+  SHZ_TRY(one_wg_prepare(ctx, ms, mc.topn, 0u, &w));
+  hipLaunchKernelGGL(m_spec_plan_kernel, dim3(1), dim3(64), 0, ctx->stream, (const uint64_t*)s.po, (const mctl*)s.d_ctl, mc.nseg,
+                     cap, (uint32_t*)tx, w.n_heavy, w.heavy, w.heavy_q, (uint32_t*)s.rb, (uint32_t)(s.rb_bytes / 4));
+  hipLaunchKernelGGL(m_expand_spec_kernel, dim3(cap_tiles), dim3(256), 0, ctx->stream, (const uint64_t*)s.E, (const uint32_t*)s.gs,
+                     (const uint32_t*)tx, (const uint64_t*)s.po, (const uint32_t*)s.glo, mc.d_segs, mc.nseg, (const mctl*)s.d_ctl,
+                     cap, ms, (uint32_t*)k32);
+  return one_wg_run(ctx, w, (const uint32_t*)k32, ms, mc.topn, s.r);
+}
+
+// the one read-back before the votes: their number sizes the vote buffers and the sort, their number per query
+// plans the vote passes (behind a queued small query: its results come along)
+static int32_t sub_read_counts(const match_call& mc, match_sub& s, sub_next* next) {
+  shz_ctx* ctx = mc.ctx;
+  const uint32_t nq = s.nq;
+  if (nq > 1) {   // one query: its counts are the totals
+    hipLaunchKernelGGL(m_query_stats_kernel, dim3(nblk(nq)), dim3(256), 0, ctx->stream, (const uint64_t*)s.E, (const mctl*)s.d_ctl,
+                       (const uint32_t*)s.gs, (const uint64_t*)s.po, mc.nseg, nq, s.r.nhash, s.r.npairs);
+    SHZ_HIP(ctx, hipGetLastError());
+  }
+  SHZ_TRY(shz_mailbox(ctx, 256 + (uint64_t)nq * 8 + (s.queued ? s.rb_bytes : 0), &s.mail));
+  char* mail = (char*)s.mail;
+  SHZ_HIP(ctx, hipMemcpyAsync(mail, s.d_ctl, 256, hipMemcpyDeviceToHost, ctx->stream));
+  if (nq > 1) SHZ_HIP(ctx, hipMemcpyAsync(mail + 256, s.r.npairs, (uint64_t)nq * 8, hipMemcpyDeviceToHost, ctx->stream));
+  if (s.queued) SHZ_HIP(ctx, hipMemcpyAsync(mail + 256 + 8, s.rb, s.rb_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  if (trace_match_env()) s.tr[1] = now_s();
+  SHZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (trace_match_env()) s.tr[2] = now_s();
+  const mctl h = *(const mctl*)mail;
+  if (h.err[0]) SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "query offsets must be < 2^%d frames", QOFF_BITS);
+  s.mu = h.mu;
+  if (s.mu == 0) { *next = SUB_EMPTY; return SHZ_OK; }   // nothing of this sub-batch belongs to this shard
+  s.mb.bias = h.err[1];
+  s.mb.dbits = bits_for((uint64_t)mc.t->max_off + s.mb.bias);
+  if (mc.sink) {  // the caller's layout must hold this table's ids and offsets and these queries' offsets
+    const m_bits& L = mc.sink->lay;
+    if (h.err[1] > L.bias || bits_for(mc.t->max_sid) > L.sb || bits_for((uint64_t)mc.t->max_off + L.bias) > L.dbits)
+      SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_match_pairs: layout (sid_bits %d, delta_bits %d, bias %u) too small for this table / these queries", L.sb, L.dbits, L.bias);
+  } else if (s.mb.qb + s.mb.sb + s.mb.dbits + 1 > 64) {
+    if (nq > 1) { *next = SUB_FEWER; return SHZ_OK; }
+    SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "song id / offset range too wide for the packed vote key");
+  }
+  s.ng = (uint32_t)h.ng;
+  s.nx = (uint64_t)s.ng * mc.nseg;   // sub-groups: (query, key) group x segment
+  s.P = h.P;
+  s.rows_total = 0;
+  for (int i = 0; i < M_ROW_STRIPES; ++i) s.rows_total += ((const uint64_t*)mail)[16 + i];
+  ctx->m_votes_per_hash = mc.t->votes_per_hash = (double)s.P / (double)s.mu;
+  if (s.P > mc.sub_budget && nq > 1) { *next = SUB_FEWER; return SHZ_OK; }   // too many votes for one sub-batch
+  if (s.P >= (1ull << 32)) SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "query %u alone produces %llu matches (limit 2^32)", s.q0, (unsigned long long)s.P);
+  s.votes.assign(nq, s.P);
+  if (nq > 1) memcpy(s.votes.data(), mail + 256, (uint64_t)nq * 8);
+  return SHZ_OK;
+}
+
+// the votes [v_lo, v_hi) of a sub-batch, packed by the layout mb with the query index + q_base on top, into `out`
+// (tile_x: the sub-group of every M_EXP_TILE-th vote's first pair, from m_tile_start_kernel)
+template <typename VT>
+static int32_t expand_votes(const match_call& mc, const match_sub& s, const uint32_t* tile_x, uint64_t v_lo, uint64_t v_hi,
+                            const m_bits& mb, int64_t q_base, VT* out) {
+  const uint32_t ntiles = (uint32_t)((v_hi - v_lo + M_EXP_TILE - 1) / M_EXP_TILE);
+  hipLaunchKernelGGL(m_expand_kernel<VT>, dim3(ntiles), dim3(256), 0, mc.ctx->stream, (const uint64_t*)s.E, (const uint32_t*)s.gs,
+                     tile_x, (const uint64_t*)s.po, (const uint32_t*)s.glo, mc.d_segs, mc.nseg, v_lo, v_hi, mb, q_base, out);
+  SHZ_HIP(mc.ctx, hipGetLastError());
+  return SHZ_OK;
+}
+
+// ROUTE_SINK: hand the votes over -- expand straight into the caller's buffer, in the shared layout, with global query
+// indices
+static int32_t vote_to_sink(const match_call& mc, const match_sub& s) {
+  pair_sink* sink = mc.sink;
+  if (sink->count + s.P <= sink->cap) {
+    const uint32_t ntiles = (uint32_t)((s.P + M_EXP_TILE - 1) / M_EXP_TILE);
+    void* tile_x;
+    SHZ_TRY(shz_ws_reserve(mc.ctx, SHZ_WS_HCNT, ((uint64_t)ntiles + 1) * 4, &tile_x));
+    hipLaunchKernelGGL(m_tile_start_kernel, dim3(nblk((uint64_t)ntiles + 1)), dim3(256), 0, mc.ctx->stream, (const uint64_t*)s.po,
+                       (uint32_t)s.nx, (uint64_t)0, s.P, ntiles, (uint32_t*)tile_x);
+    SHZ_TRY(expand_votes<uint64_t>(mc, s, (const uint32_t*)tile_x, 0, s.P, sink->lay, (int64_t)s.q0, sink->d_pairs + sink->count));
+  }
+  sink->count += s.P;  // keeps counting past cap: the caller learns the size it needs
+  return SHZ_OK;
+}
+
+// the vote buffers of the passes of a plan: v0 | (4-byte votes: a second buffer at v0 + pmax4 entries), v1
+struct vote_bufs { void *v0, *v1; uint64_t pmax4; };
+
+// one pass of the plan: expand its votes, then sort / fold / rank as the route says, into the rows of its first query
+static int32_t vote_run_pass(const match_call& mc, const match_sub& s, const vote_plan& plan, const vote_pass& vp,
+                             const uint32_t* tile_x, const vote_bufs& b) {
+  shz_ctx* ctx = mc.ctx;
+  const uint32_t topn = mc.topn, nqp = vp.qb - vp.qa;
+  const uint64_t pp = vp.v_hi - vp.v_lo;
+  const res_block r = res_rows(s.r, vp.qa, topn);
+  uint64_t* d_G = (uint64_t*)&s.d_ctl->G;
+  m_bits mbp = s.mb;
+  uint32_t* k32 = (uint32_t*)b.v0;   // 4-byte votes: two buffers in SORT_C (the widened result in SORT_D)
+  switch (plan.route) {
+    case ROUTE_ONE_WG: {
+      one_wg_fold w;
+      SHZ_TRY(expand_votes<uint32_t>(mc, s, tile_x, vp.v_lo, vp.v_hi, mbp, (int64_t)0, k32));
+      SHZ_TRY(one_wg_prepare(ctx, mbp, topn, (uint32_t)pp, &w));
+      hipLaunchKernelGGL(vt_one_range_kernel, dim3(1), dim3(1), 0, ctx->stream, w.n_heavy, w.heavy, w.heavy_q, (uint32_t)pp);
+      return one_wg_run(ctx, w, k32, mbp, topn, r);
+    }
+    case ROUTE_TILES_FUSED:
+    case ROUTE_TILES: {
+      mbp.qb = 0;   // the votes of a tile pass carry no query bits: their place in the pass says it
+      vt_plan pl;
+      shz_seg_plan sp;
+      vt_make_plan(s.votes.data() + vp.qa, nqp, mbp, pl, sp);
+      if (plan.route == ROUTE_TILES) {
+        SHZ_TRY(expand_votes<uint32_t>(mc, s, tile_x, vp.v_lo, vp.v_hi, mbp, M_NO_QUERY_BITS, k32));
+      } else {
+        const uint32_t stile = shz_seg_tile(pp), cpb = stile / M_EXP_TILE;
+        shz_seg_blocks(&sp, stile);
+        const uint32_t nsb = sp.bq[nqp];
+        void *cxp, *hist;
+        SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_VT5, (uint64_t)nsb * (cpb + 1) * 4, &cxp));
+        SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SORT_H, ((uint64_t)nsb << 8) * 4, &hist));   // (the sort asks for the same)
+        hipLaunchKernelGGL(m_chunk_start_kernel, dim3(nblk((uint64_t)nsb * (cpb + 1))), dim3(256), 0, ctx->stream,
+                           (const uint64_t*)s.po, (uint32_t)s.nx, sp, stile, vp.v_lo, vp.v_hi, (uint32_t*)cxp);
+        hipLaunchKernelGGL(m_expand_blocks_kernel, dim3(nsb), dim3(256), 0, ctx->stream, (const uint64_t*)s.E,
+                           (const uint32_t*)s.gs, (const uint32_t*)cxp, (const uint64_t*)s.po, (const uint32_t*)s.glo, mc.d_segs,
+                           mc.nseg, vp.v_lo, sp, stile, mbp, pl.g_lo, plan.fuse_dmask, k32, (uint32_t*)hist);
+        SHZ_HIP(ctx, hipGetLastError());
+      }
+      return vt_run_pass(ctx, k32, k32 + b.pmax4, pp, pl, sp, mbp, topn, plan.route == ROUTE_TILES_FUSED, mc.t->max_sid, r);
+    }
+    case ROUTE_WIDEN:
+      mbp.qb = nqp > 1 ? bits_for(nqp - 1) : 0;   // the query index inside the pass
+      SHZ_TRY(expand_votes<uint32_t>(mc, s, tile_x, vp.v_lo, vp.v_hi, mbp, -(int64_t)vp.qa, k32));
+      SHZ_TRY(shz_sort_u32_widen(ctx, k32, k32 + b.pmax4, (uint64_t*)b.v1, pp, 1, mbp.qb + mbp.sb + mbp.dbits + 1, 0, nullptr));
+      return vote_fold(ctx, (const uint64_t*)b.v1, pp, nqp, mbp, topn, d_G, r);
+    case ROUTE_SORT64:
+      SHZ_TRY(expand_votes<uint64_t>(mc, s, tile_x, vp.v_lo, vp.v_hi, mbp, (int64_t)0, (uint64_t*)b.v0));
+      return vote_tail(ctx, (uint64_t*)b.v0, (uint64_t*)b.v1, pp, nqp, mbp, topn, d_G, r);
+    default:
+      return SHZ_OK;   // (the routes without passes)
+  }
+}
+
+// the votes of a sub-batch, by the plan's route: vote buffers, the expand tiles' starts for all passes, then pass by pass
+static int32_t sub_vote(const match_call& mc, const match_sub& s, const vote_plan& plan) {
+  shz_ctx* ctx = mc.ctx;
+  if (plan.route == ROUTE_SINK) return vote_to_sink(mc, s);
+  const std::vector<vote_pass>& passes = plan.passes;
+  if (passes.empty()) return SHZ_OK;   // ROUTE_NONE, ROUTE_QUEUED
+  uint64_t pmax = 0;
+  for (const vote_pass& vp : passes) pmax = std::max(pmax, vp.v_hi - vp.v_lo);
+  vote_bufs b;   // E lives in one of SORT_A/B; the vote buffers use SORT_C/D
+  b.pmax4 = (pmax + 3) & ~3ull;   // second 4-byte vote buffer of a pass: 16-byte aligned behind the first
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SORT_C, pmax * 8 + 16, &b.v0));
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SORT_D, pmax * 8, &b.v1));
+  // the sub-group of every expand tile's first pair, for all passes in one launch: pass table (votes, first entry)
+  // up, one kernel
+  std::vector<uint32_t> toff(passes.size() + 1, 0);
+  std::vector<uint64_t> ptab(passes.size() * 2 + (passes.size() + 2) / 2);   // pv[2 n_pass] | toff[n_pass + 1] (u32)
+  for (size_t i = 0; i < passes.size(); ++i) {
+    ptab[2 * i] = passes[i].v_lo;
+    ptab[2 * i + 1] = passes[i].v_hi;
+    toff[i + 1] = toff[i] + (uint32_t)((passes[i].v_hi - passes[i].v_lo + M_EXP_TILE - 1) / M_EXP_TILE) + 1;
+  }
+  memcpy(ptab.data() + passes.size() * 2, toff.data(), toff.size() * 4);
+  void* tile_starts;
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_HCNT, (uint64_t)toff.back() * 4, &tile_starts));   // (M5 belongs to the fold)
+  const bool by_blocks = plan.route == ROUTE_TILES_FUSED;   // its expand goes by the sort's blocks: m_chunk_start_kernel per pass
+  if (!by_blocks && passes.size() == 1) {   // no table to send up
+    hipLaunchKernelGGL(m_tile_start_kernel, dim3(nblk(toff.back())), dim3(256), 0, ctx->stream, (const uint64_t*)s.po, (uint32_t)s.nx,
+                       passes[0].v_lo, passes[0].v_hi, toff.back() - 1, (uint32_t*)tile_starts);
+  } else if (!by_blocks) {
+    void* d_ptab;
+    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_VT4, ptab.size() * 8, &d_ptab));
+    SHZ_HIP(ctx, shz_memcpy(ctx, d_ptab, ptab.data(), ptab.size() * 8, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(m_tile_start_all_kernel, dim3(nblk(toff.back())), dim3(256), 0, ctx->stream, (const uint64_t*)s.po, (uint32_t)s.nx,
+                       (const uint64_t*)d_ptab, (const uint32_t*)((const uint64_t*)d_ptab + passes.size() * 2),
+                       (uint32_t)passes.size(), (uint32_t*)tile_starts);
+  }
+  SHZ_HIP(ctx, hipGetLastError());
+  for (size_t i = 0; i < passes.size(); ++i)
+    SHZ_TRY(vote_run_pass(mc, s, plan, passes[i], (const uint32_t*)tile_starts + toff[i], b));
+  return SHZ_OK;
+}
+
+// no hash of the queries is looked up here (none given, or all of them another shard's): zero counters, no results
+static void sub_commit_empty(const match_call& mc, const match_sub& s) {
+  for (uint32_t q = s.q0; q < s.q0 + s.nq; ++q) {
+    if (mc.out_nres) mc.out_nres[q] = 0;
+    if (mc.out_nhash) mc.out_nhash[q] = 0;
+    if (mc.out_npairs) mc.out_npairs[q] = 0;
+  }
+}
+
+// the result block back (with the counts already, where the queued fold held) and out to the caller -- unless the LDS fold
+// flagged an overflow: then nothing is committed and the queries go round again
+static int32_t sub_commit(const match_call& mc, const match_sub& s, vote_route route, sub_next* next) {
+  shz_ctx* ctx = mc.ctx;
+  const uint32_t q0 = s.q0, nq = s.nq;
+  void* hb;
+  double tr3 = 0.0;
+  if (route == ROUTE_QUEUED) {
+    ++ctx->st_spec_used;
+    hb = (char*)s.mail + 256 + 8;   // came with the first read-back
+    if (trace_match_env()) tr3 = now_s();
+  } else {
+    SHZ_TRY(shz_mailbox(ctx, s.rb_bytes, &hb));
+    SHZ_HIP(ctx, hipMemcpyAsync(hb, s.rb, s.rb_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (trace_match_env()) tr3 = now_s();
+    SHZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  if (trace_match_env())
+    fprintf(stderr, "match trace: head enqueue %.1f us, wait %.1f us, tail enqueue %.1f us, wait %.1f us (P %llu)\n",
+            (s.tr[1] - s.tr[0]) * 1e6, (s.tr[2] - s.tr[1]) * 1e6, (tr3 - s.tr[2]) * 1e6, (now_s() - tr3) * 1e6, (unsigned long long)s.P);
+  const res_block h = res_block_at(hb, nq, s.nres);
+  if (*h.vt_err != 0 && !s.redo) {
+    ++ctx->st_vt_redo;
+    *next = SUB_FULL_SORT;
+    return SHZ_OK;
+  }
+  ctx->st_rows += s.rows_total;
+  ctx->st_pairs += s.P;
+  ctx->st_keys += s.ng;
+  if (nq == 1) {
+    if (mc.out_npairs) mc.out_npairs[q0] = s.P;
+    if (mc.out_nhash) mc.out_nhash[q0] = (uint32_t)s.mu;
+  } else {
+    if (mc.out_npairs) memcpy(mc.out_npairs + q0, h.npairs, (uint64_t)nq * 8);
+    if (mc.out_nhash) memcpy(mc.out_nhash + q0, h.nhash, (uint64_t)nq * 4);
+  }
+  if (!mc.sink) {
+    const uint64_t o0 = (uint64_t)q0 * mc.topn;
+    memcpy(mc.out_sid + o0, h.sid, s.nres * 4);
+    memcpy(mc.out_delta + o0, h.delta, s.nres * 4);
+    memcpy(mc.out_aligned + o0, h.aligned, s.nres * 4);
+    memcpy(mc.out_dedup + o0, h.dedup, s.nres * 4);
+    memcpy(mc.out_nres + q0, h.nres, (uint64_t)nq * 4);
+  }
+  *next = SUB_DONE;
+  return SHZ_OK;
+}
+
+// one visit of the sub-batch s: head -> (queued fold) -> counts -> route -> votes -> results
+static int32_t match_sub_run(match_call& mc, match_sub& s, sub_next* next) {
+  *next = SUB_GO;
+  if (trace_match_env()) s.tr[0] = now_s();
+  SHZ_TRY(sub_head(mc, s, next));
+  if (*next != SUB_GO) return SHZ_OK;
+  SHZ_TRY(sub_queue_fold(mc, s));
+  SHZ_TRY(sub_read_counts(mc, s, next));
+  if (*next != SUB_GO) return SHZ_OK;
+  // the queued small query ran when its votes fit and the bias was the query's own (else its kernels did nothing, or
+  // their results are overwritten, and the passes run as ever)
+  vote_case c{s.nq, s.P, s.votes.data(), s.mb, mc.topn, s.full_sort, mc.sink != nullptr,
+              s.queued && s.P <= VT_ONE_WG_MAX && s.mb.bias == s.queued_bias, vote_env()};
+  vote_plan plan;
+  vote_plan_make(c, &plan);
+  SHZ_TRY(sub_vote(mc, s, plan));
+  return sub_commit(mc, s, plan.route, next);
+}
+
+static int32_t match_core(match_call& mc) {
+  shz_ctx* ctx = mc.ctx;
+  shz_table* t = mc.t;
+  if (!ctx || !t) return SHZ_E_INVALID;
+  if (t->ctx != ctx) SHZ_FAIL(ctx, SHZ_E_INVALID, "table belongs to another ctx");
+  if (pending_rows(t) || (!t->bucket && t->done.empty())) SHZ_FAIL(ctx, SHZ_E_STATE, "table not finalized");
+  if (mc.n_queries == 0) return SHZ_OK;
+  // offsets < 2^31: every delta fits out_delta's int32_t and, biased by a query offset < 2^20, 32 bits
+  if (t->max_off >= (1u << 31))
+    SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "match: the table holds offset %u; offsets must be < 2^31", t->max_off);
+  if (!mc.query_off) SHZ_FAIL(ctx, SHZ_E_INVALID, "match: query_off is NULL");
+  if (!mc.sink && (!mc.out_sid || !mc.out_delta || !mc.out_aligned || !mc.out_dedup || !mc.out_nres))
+    SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_match_batch: NULL buffer");
+  if (!mc.sink && (mc.topn < 1 || mc.topn > 64)) SHZ_FAIL(ctx, SHZ_E_INVALID, "topn must be in [1,64]");
+  SHZ_HIP(ctx, hipSetDevice(ctx->device));
+  ctx->st_rows = ctx->st_pairs = ctx->st_keys = 0;
+  // votes of one sub-batch of queries (one head: compose, sort, probe, one round trip): up to 2^30 where the device has
+  // the memory for it (a sub-batch that ends up on the 8-byte path needs ~32 bytes per vote of workspace)
+  mc.sub_budget = VOTE_PASS_MAX;
+  if (mc.n_queries > 32) {
+    size_t mem_free = 0, mem_total = 0;
+    if (hipMemGetInfo(&mem_free, &mem_total) == hipSuccess)
+      mc.sub_budget = std::min<uint64_t>(1ull << 30, std::max<uint64_t>(VOTE_PASS_MAX, (uint64_t)mem_free / 64));
+  }
+  SHZ_TRY(match_upload(mc));
   // a shard's compose marks hashes it does not own with the query index nq (sorted behind all queries): nq << 52 must
   // not wrap, so its sub-batches stay below MAX_Q_SUB
-  uint32_t step = std::min<uint32_t>(n_queries, (vs_out && vs_out->nshards > 1) ? MAX_Q_SUB - 1 : MAX_Q_SUB);
-  bool redo_full_sort = false;   // the vote tiles of this sub-batch flagged an overflow: once more, through the full sort
-  const uint32_t vt_probe_limit_1 = (ctx->debug & SHZ_DEBUG_VT_PROBE1) ? 1u : 0u;   // debug: a probe gives up after one round
-  while (q0 < n_queries) {
-    const uint32_t flags_sub = flags | (redo_full_sort ? SHZ_MATCH_FULL_SORT : 0u);
-    uint32_t nq = std::min<uint32_t>(step, n_queries - q0);
-    // the vote budget: sized from what a hash yielded in the last sub-batch, so that the head (compose, sort, probe: a
-    // round trip) is not run on 200 queries, then 100, then 50 to find that 25 fit
-    if (ctx->m_votes_per_hash > 0.0 && nq > 1) {
-      const double hashes = (double)SUB_BUDGET / (1.05 * ctx->m_votes_per_hash);
-      uint32_t lo = 1, hi = nq;   // largest count whose hashes stay under the estimate
-      while (lo < hi) {
-        const uint32_t mid = (lo + hi + 1) >> 1;
-        if ((double)(query_off[q0 + mid] - query_off[q0]) <= hashes) lo = mid; else hi = mid - 1;
-      }
-      nq = lo;
+  uint32_t step = std::min<uint32_t>(mc.n_queries, (mc.sink && mc.sink->nshards > 1) ? MAX_Q_SUB - 1 : MAX_Q_SUB);
+  bool redo = false;
+  for (uint32_t q0 = 0; q0 < mc.n_queries;) {
+    match_sub s{};
+    s.q0 = q0;
+    s.nq = sub_queries(mc, q0, step);
+    s.m = mc.query_off[q0 + s.nq] - mc.query_off[q0];
+    if (s.m >= (1ull << 31)) SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "query %u has too many hashes", q0);
+    s.redo = redo;
+    s.full_sort = redo || (mc.flags & SHZ_MATCH_FULL_SORT);
+    s.mb = m_bits{bits_for(t->max_sid), 0, bits_for(s.nq - 1), 0};
+    sub_next next;
+    SHZ_TRY(match_sub_run(mc, s, &next));
+    switch (next) {
+      case SUB_FEWER: step = s.nq / 2; break;
+      case SUB_FULL_SORT: redo = true; break;
+      case SUB_EMPTY: sub_commit_empty(mc, s); q0 += s.nq; break;
+      default: redo = false; q0 += s.nq; break;   // SUB_DONE
     }
-    // shrink so the element count stays sortable
-    while (nq > 1 && query_off[q0 + nq] - query_off[q0] >= (1ull << 31)) nq /= 2;
-    const uint64_t m = query_off[q0 + nq] - query_off[q0];
-    if (m >= (1ull << 31)) SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "query %u has too many hashes", q0);
-    mb.qb = bits_for(nq - 1);
-    static const bool trace = [] { const char* e = getenv("SHZ_TRACE_MATCH"); return e && atoi(e) != 0; }();
-    const double tr0 = trace ? now_s() : 0.0;
-    double tr1 = 0, tr2 = 0, tr3 = 0;
-    void *d_qoff, *c0, *c1, *fl, *ps, *ctl_p;
-    if (d_qoff_all) {
-      d_qoff = (void*)(d_qoff_all + q0);
-    } else {
-      SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_M0, (uint64_t)(nq + 1) * 8, &d_qoff));
-      SHZ_HIP(ctx, shz_memcpy(ctx, d_qoff, query_off + q0, (uint64_t)(nq + 1) * 8, hipMemcpyHostToDevice));
-    }
-    if (d_ctl_packed && q0 == 0) {
-      ctl_p = d_ctl_packed;               // arrived zeroed with the upload
-      d_ctl_packed = nullptr;             // (a retry with fewer queries, or a later sub-batch, zeroes its own)
-    } else {
-      SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_MISC0, 256, &ctl_p));
-      SHZ_HIP(ctx, hipMemsetAsync(ctl_p, 0, 256, ctx->stream));
-    }
-    mctl* d_ctl = (mctl*)ctl_p;
-    uint64_t* tot = (uint64_t*)ctl_p;      // tot[0..4] = mu, ng, rows, P, G
-    uint32_t* err = d_ctl->err;
-    if (m == 0) {
-      for (uint32_t q = 0; q < nq; ++q) {
-        if (out_nres) out_nres[q0 + q] = 0;
-        if (out_nhash) out_nhash[q0 + q] = 0;
-        if (out_npairs) out_npairs[q0 + q] = 0;
-      }
-      q0 += nq;
-      continue;
-    }
-    const uint64_t nx_bound = m * (uint64_t)nseg + 1;   // sub-groups (group x segment) + sentinel, from the bound groups <= m
-    if (nx_bound >= (1ull << 32)) {
-      if (nq > 1) { step = nq / 2; continue; }
-      SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "query %u: %llu hashes x %d segments", q0, (unsigned long long)m, nseg);
-    }
-    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SORT_A, m * 8, &c0));
-    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SORT_B, m * 8, &c1));
-    const uint32_t f_nsh = vs_out ? vs_out->nshards : 1u, f_sh = vs_out ? vs_out->shard : 0u;
-    void *gs, *glo, *gpairs, *po;
-    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_M3, (m + 1) * 4, &gs));
-    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_M4, nx_bound * 4, &glo));
-    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_M6, nx_bound * 8, &gpairs));
-    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_M7, nx_bound * 8, &po));
-    uint64_t* E;
-    if (f_nsh == 1 && m <= MH_MAX) {
-      E = (uint64_t*)c1;
-      hipLaunchKernelGGL(m_head_small_kernel, dim3(1), dim3(MH_THREADS), 0, ctx->stream, d_key, d_qo, (const uint64_t*)d_qoff,
-                         nq, (uint32_t)m, QIDX_SHIFT + mb.qb, E, (uint32_t*)gs, d_ctl);
-      SHZ_HIP(ctx, hipGetLastError());
-    } else {
-    hipLaunchKernelGGL(m_compose_kernel, dim3(nblk(m)), dim3(256), 0, ctx->stream, d_key, d_qo, (const uint64_t*)d_qoff, nq,
-                       m, f_nsh, f_sh, (uint64_t*)c0, err);
-    SHZ_HIP(ctx, hipGetLastError());
-    int sel = 0;
-    SHZ_TRY(shz_sort_u64(ctx, (uint64_t*)c0, (uint64_t*)c1, nullptr, nullptr, 0, m, 0,
-                         QIDX_SHIFT + (f_nsh > 1 ? bits_for(nq) : mb.qb), &sel));
-    uint64_t* cs = sel ? (uint64_t*)c1 : (uint64_t*)c0;   // sorted
-    E = sel ? (uint64_t*)c0 : (uint64_t*)c1;              // unique elements go to the other buffer
-    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_M1, m * 4, &fl));
-    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_M2, m * 4, &ps));
-    // unique (query, key, off): mu of them; groups = distinct (query, key): ng of them; probe; pairs -- queued without a
-    // host round trip in between: every launch is sized by the bound m, the counts are read on the device (mctl)
-    hipLaunchKernelGGL(m_head_flag_kernel, dim3(nblk(m)), dim3(256), 0, ctx->stream, (const uint64_t*)cs, m, 0, (uint32_t*)fl);
-    SHZ_TRY(shz_scan_u32(ctx, (const uint32_t*)fl, (uint32_t*)ps, m, tot));
-    hipLaunchKernelGGL(m_compact_vals_kernel, dim3(nblk(m)), dim3(256), 0, ctx->stream, (const uint64_t*)cs,
-                       (const uint32_t*)fl, (const uint32_t*)ps, m, E);
-    hipLaunchKernelGGL(m_fix_mu_kernel, dim3(1), dim3(1), 0, ctx->stream, d_ctl, (unsigned long long)m);
-    hipLaunchKernelGGL(m_head_flag_dn_kernel, dim3(nblk(m)), dim3(256), 0, ctx->stream, (const uint64_t*)E, &d_ctl->mu, m,
-                       QKEY_SHIFT, (uint32_t*)fl);
-    SHZ_TRY(shz_scan_u32(ctx, (const uint32_t*)fl, (uint32_t*)ps, m, tot + 1));
-    hipLaunchKernelGGL(m_compact_idx_kernel, dim3(nblk(m)), dim3(256), 0, ctx->stream, (const uint32_t*)fl,
-                       (const uint32_t*)ps, &d_ctl->mu, m, &d_ctl->ng, (uint32_t*)gs);
-    }
-    // results and per-query counters in ONE device block: zeroed by the probe, one copy after.
-    // layout: npairs[nq] u64 | sid, delta, aligned, dedup [nq * topn] u32 each | nres[nq] | nhash[nq]
-    const uint64_t nres = (uint64_t)nq * (vs_out ? 0 : topn);
-    const uint64_t rb_bytes = (uint64_t)nq * 8 + nres * 16 + (uint64_t)nq * 8 + 8;   // + the vote tiles' flag word (and a pad)
-    void* rb;
-    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_PEAK_F, rb_bytes + 64, &rb));
-    hipLaunchKernelGGL(m_probe_kernel, dim3(nblk(nx_bound)), dim3(256), 0, ctx->stream, (const uint64_t*)E,
-                       (const uint32_t*)gs, &d_ctl->ng, nx_bound, (const shz_seg_dev*)d_segs, (uint32_t)nseg, (uint32_t*)glo,
-                       (uint64_t*)gpairs, (unsigned long long*)ctl_p + 16, (uint32_t*)rb, (uint32_t)((rb_bytes + 3) / 4));
-    SHZ_HIP(ctx, hipGetLastError());
-    SHZ_TRY(shz_scan_u64(ctx, (const uint64_t*)gpairs, (uint64_t*)po, nx_bound, tot + 3));
-    uint64_t* d_np = (uint64_t*)rb;
-    uint32_t* r_sid = (uint32_t*)(d_np + nq);
-    uint32_t *r_delta = r_sid + nres, *r_al = r_delta + nres, *r_dd = r_al + nres, *r_n = r_dd + nres, *d_nh = r_n + nq;
-    uint32_t* d_vt_err = d_nh + nq;   // set by a vote-tile kernel whose LDS table or range list overflowed: the sub-batch is voted again by the full sort
-    // ONE small query from host memory: its votes are queued now, before their number is known (m_spec_plan_kernel),
-    // through the one-workgroup path below and with that path's conditions; the layout needs the largest query offset,
-    // which the host has
-    static const int tiles_env = [] { const char* e = getenv("SHZ_VOTE_TILES"); return e ? atoi(e) : -1; }();   // 0 never
-    static const int force32 = [] { const char* e = getenv("SHZ_VOTE32"); return e ? atoi(e) : -1; }();   // 0 never, 1 whenever it fits
-    bool spec = false;
-    uint32_t spec_bias = 0;
-    if (!vs_out && nq == 1 && f_nsh == 1 && m <= MH_MAX && !(flags & SHZ_IN_DEVICE) &&
-        !(flags_sub & SHZ_MATCH_FULL_SORT) && tiles_env != 0 && force32 != 1 && topn <= VT_MAXTOPN &&
-        (double)m * t->votes_per_hash <= 2.0 * VT_ONE_WG_MAX) {   // (a table whose last query had far more votes: not worth queueing)
-      const uint64_t a0 = query_off[q0], a1 = query_off[q0 + 1];
-      bool wide = false;
-      for (uint64_t i = a0; i < a1; ++i) {
-        spec_bias = std::max(spec_bias, q_off[i]);
-        wide |= q_off[i] >= (1u << QOFF_BITS);
-      }
-      m_bits ms = mb;
-      ms.qb = 0;
-      ms.bias = spec_bias;
-      ms.dbits = bits_for((uint64_t)t->max_off + spec_bias);
-      if (!wide && 31 - ms.sb - ms.dbits >= 0 && ms.dbits <= VT_MAX_DBITS + VT_MAX_DSPLIT) {
-        spec = true;
-        ++ctx->st_spec_queued;
-        const uint64_t cap = VT_ONE_WG_MAX;
-        const uint32_t cap_tiles = (uint32_t)((cap + M_EXP_TILE - 1) / M_EXP_TILE);
-        void *tx, *k32, *ts, *cp, *cd, *cdd;
-        SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_HCNT, ((uint64_t)cap_tiles + 1) * 4, &tx));
-        SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SORT_C, cap * 8 + 16, &k32));
-        SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_VT0, 64, &ts));
-        SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_VT1, (uint64_t)topn * 8, &cp));
-        SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_VT2, (uint64_t)topn * 4, &cd));
-        SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_VT3, (uint64_t)topn * 4, &cdd));
-        uint32_t* n_heavy = (uint32_t*)ts;
-        uint2* heavy = (uint2*)(n_heavy + 2);
-        uint32_t* heavy_q = n_heavy + 4;
-        vt_plan pl;
-        pl.nq = 1;
-        pl.dbits = ms.dbits;
-        pl.sb = ms.sb;
-        pl.g_lo = ms.sb + ms.dbits + 1;   // no bit is ordered: a sweep may split by any song-id bit
-        pl.tile = VW_CHUNK;
-        pl.flush = VW_FLUSH;
-        for (uint32_t i = 0; i <= VT_MAXQ; ++i) { pl.qv[i] = 0u; pl.tb[i] = 0; }   // no tiles, one range (its end: heavy[0])
-        hipLaunchKernelGGL(m_spec_plan_kernel, dim3(1), dim3(64), 0, ctx->stream, (const uint64_t*)po, (const mctl*)d_ctl,
-                           (uint32_t)nseg, cap, (uint32_t*)tx, n_heavy, heavy, heavy_q, (uint32_t*)rb, (uint32_t)(rb_bytes / 4));
-        hipLaunchKernelGGL(m_expand_spec_kernel, dim3(cap_tiles), dim3(256), 0, ctx->stream, (const uint64_t*)E,
-                           (const uint32_t*)gs, (const uint32_t*)tx, (const uint64_t*)po, (const uint32_t*)glo,
-                           (const shz_seg_dev*)d_segs, (uint32_t)nseg, (const mctl*)d_ctl, cap, ms, (uint32_t*)k32);
-        hipLaunchKernelGGL(vt_fold_kernel, dim3(1), dim3(VT_THREADS), 0, ctx->stream, (const uint32_t*)k32, (const uint2*)heavy,
-                           (const uint32_t*)n_heavy, 1u, pl, topn, (uint64_t*)cp, (uint32_t*)cd, (uint32_t*)cdd,
-                           vt_probe_limit_1 ? vt_probe_limit_1 : (uint32_t)VT_SLOTS, d_vt_err);
-        hipLaunchKernelGGL(vt_rank_kernel, dim3(1), dim3(VR_THREADS), 0, ctx->stream, pl, topn, ms, (const uint64_t*)cp,
-                           (const uint32_t*)cd, (const uint32_t*)cdd, (const uint32_t*)n_heavy, (const uint32_t*)heavy_q, 1u,
-                           r_sid, (int32_t*)r_delta, r_al, r_dd, r_n);
-        SHZ_HIP(ctx, hipGetLastError());
-      }
-    }
-    if (nq > 1) {   // one query: its counts are the totals
-      hipLaunchKernelGGL(m_query_stats_kernel, dim3(nblk(nq)), dim3(256), 0, ctx->stream, (const uint64_t*)E, (const mctl*)d_ctl,
-                         (const uint32_t*)gs, (const uint64_t*)po, (uint32_t)nseg, nq, d_nh, d_np);
-      SHZ_HIP(ctx, hipGetLastError());
-    }
-    // the one read-back before the votes: their number sizes the vote buffers and the sort, their number per query
-    // plans the vote passes (behind a queued small query: its results come along)
-    void* mailp;
-    SHZ_TRY(shz_mailbox(ctx, 256 + (uint64_t)nq * 8 + (spec ? rb_bytes : 0), &mailp));
-    SHZ_HIP(ctx, hipMemcpyAsync(mailp, d_ctl, 256, hipMemcpyDeviceToHost, ctx->stream));
-    if (nq > 1) SHZ_HIP(ctx, hipMemcpyAsync((char*)mailp + 256, d_np, (uint64_t)nq * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (spec) SHZ_HIP(ctx, hipMemcpyAsync((char*)mailp + 256 + 8, rb, rb_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    if (trace) tr1 = now_s();
-    SHZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (trace) tr2 = now_s();
-    const mctl h = *(const mctl*)mailp;
-    if (h.err[0]) SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "query offsets must be < 2^%d frames", QOFF_BITS);
-    const uint64_t mu = h.mu;
-    if (mu == 0) {          // nothing of this sub-batch belongs to this shard
-      for (uint32_t q = 0; q < nq; ++q) {
-        if (out_nhash) out_nhash[q0 + q] = 0;
-        if (out_npairs) out_npairs[q0 + q] = 0;
-      }
-      q0 += nq;
-      continue;
-    }
-    mb.bias = h.err[1];
-    mb.dbits = bits_for((uint64_t)t->max_off + mb.bias);
-    if (vs_out) {  // the caller's layout must hold this table's ids and offsets and these queries' offsets
-      const m_bits& L = vs_out->lay;
-      if (h.err[1] > L.bias || bits_for(t->max_sid) > L.sb || bits_for((uint64_t)t->max_off + L.bias) > L.dbits)
-        SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_match_pairs: layout (sid_bits %d, delta_bits %d, bias %u) too small for this table / these queries", L.sb, L.dbits, L.bias);
-    } else if (mb.qb + mb.sb + mb.dbits + 1 > 64) {
-      if (nq > 1) { step = nq / 2; continue; }
-      SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "song id / offset range too wide for the packed vote key");
-    }
-    const uint32_t ng = (uint32_t)h.ng;
-    const uint64_t nx = (uint64_t)ng * nseg;   // sub-groups: (query, key) group x segment
-    const uint64_t P = h.P;
-    uint64_t rows_total = 0;
-    for (int i = 0; i < M_ROW_STRIPES; ++i) rows_total += ((const uint64_t*)mailp)[16 + i];
-    if (mu) ctx->m_votes_per_hash = t->votes_per_hash = (double)P / (double)mu;
-    if (P > SUB_BUDGET && nq > 1) {  // too many pairs for one sub-batch: retry with fewer queries
-      step = std::max<uint32_t>(1, nq / 2);
-      continue;
-    }
-    if (P >= (1ull << 32)) SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "query %u alone produces %llu matches (limit 2^32)", q0, (unsigned long long)P);
-    std::vector<uint64_t> h_votes(nq, P);   // votes per query (read back with the counts)
-    if (nq > 1) memcpy(h_votes.data(), (const char*)mailp + 256, (uint64_t)nq * 8);
-    void* tile_x = nullptr;
-    // the queued small query ran when its votes fit (else its kernels did nothing, and the passes below run as ever)
-    const bool spec_done = spec && P <= VT_ONE_WG_MAX && mb.bias == spec_bias;
-    if (spec_done) {
-    } else if (P > 0 && vs_out) {
-      // hand the votes over: expand straight into the caller's buffer, in the shared layout, with global query indices
-      if (vs_out->count + P <= vs_out->cap) {
-        const uint32_t ntiles = (uint32_t)((P + M_EXP_TILE - 1) / M_EXP_TILE);
-        SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_HCNT, ((uint64_t)ntiles + 1) * 4, &tile_x));
-        hipLaunchKernelGGL(m_tile_start_kernel, dim3(nblk((uint64_t)ntiles + 1)), dim3(256), 0, ctx->stream, (const uint64_t*)po,
-                           (uint32_t)nx, (uint64_t)0, P, ntiles, (uint32_t*)tile_x);
-        hipLaunchKernelGGL(m_expand_kernel<uint64_t>, dim3(ntiles), dim3(256), 0, ctx->stream, (const uint64_t*)E,
-                           (const uint32_t*)gs, (const uint32_t*)tile_x, (const uint64_t*)po, (const uint32_t*)glo,
-                           (const shz_seg_dev*)d_segs, (uint32_t)nseg, (uint64_t)0, P, vs_out->lay, (int64_t)q0,
-                           vs_out->d_pairs + vs_out->count);
-        SHZ_HIP(ctx, hipGetLastError());
-      }
-      vs_out->count += P;  // keeps counting past cap: the caller learns the size it needs
-    } else if (P > 0) {
-      // expand -> sort -> groups -> top-n, in vote passes over ranges of queries.  4-BYTE votes when a pass's query
-      // index, the song id and the biased delta fit 31 bits (1M songs x 10 s queries: 1 + 20 + 10): half the bytes
-      // through expand and the sort passes, whose last pass widens to the 64-bit layout the fold reads.  Worth it only
-      // while a pass still has millions of votes; else one 8-byte pass over all queries.
-      struct vpass { uint32_t qa, qb; uint64_t v_lo, v_hi; };
-      std::vector<vpass> passes;
-      const int qbits32 = 31 - mb.sb - mb.dbits;
-      bool use32 = qbits32 >= 0 && P > MH_MAX && force32 != 0 && !(flags_sub & SHZ_MATCH_FULL_SORT);
-      // vote tiles (vt_fold_kernel): two radix passes + an LDS fold per tile instead of four passes + the record chain
-      const bool tiles = use32 && tiles_env != 0 && topn <= VT_MAXTOPN && mb.dbits <= VT_MAX_DBITS + VT_MAX_DSPLIT;
-      if (use32) {
-        const uint32_t q_per_pass = tiles ? (uint32_t)VT_MAXQ : (1u << std::min(qbits32, 30));   // tiles: no query bits in the vote
-        uint64_t v = 0;
-        for (uint32_t qa = 0; qa < nq;) {
-          uint32_t qb = qa;
-          uint64_t pv = 0;
-          while (qb < nq && (qb - qa) < q_per_pass && (qb == qa || pv + h_votes[qb] <= P_BUDGET)) pv += h_votes[qb++];
-          if (pv) passes.push_back(vpass{qa, qb, v, v + pv});
-          v += pv;
-          qa = qb;
-        }
-        if (force32 != 1 && P / std::max<size_t>(passes.size(), 1) < (1ull << 22)) use32 = false;   // small passes: launch-bound
-      }
-      if (!use32) { passes.clear(); passes.push_back(vpass{0, nq, 0, P}); }
-      // ONE query with few votes (a 5-10 s query against thousands of songs): expand, then one workgroup folds the
-      // unordered votes (vt_fold_kernel over the single range [0, P)) -- 5 launches instead of the 9 of sort + fold,
-      // and the launches are what such a match costs
-      const bool one_wg = !use32 && !(flags_sub & SHZ_MATCH_FULL_SORT) && nq == 1 && P <= VT_ONE_WG_MAX && qbits32 >= 0 && tiles_env != 0 && topn <= VT_MAXTOPN &&
-                          mb.dbits <= VT_MAX_DBITS + VT_MAX_DSPLIT;
-      uint64_t pmax = 0;
-      for (const vpass& vp : passes) pmax = std::max(pmax, vp.v_hi - vp.v_lo);
-      void *v0, *v1;   // E lives in one of SORT_A/B; the vote buffers use SORT_C/D
-      const uint64_t pmax4 = (pmax + 3) & ~3ull;   // second 4-byte vote buffer of a pass: 16-byte aligned behind the first
-      SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SORT_C, pmax * 8 + 16, &v0));
-      SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SORT_D, pmax * 8, &v1));
-      // vote tiles: the expand runs by the blocks of the segmented sort and counts the first pass's digits (no tile starts
-      // here: m_chunk_start_kernel per pass)
-      const int Bt_all = mb.sb + mb.dbits + 1, g_lo_all = std::max(1 + mb.dbits, Bt_all - VT_ORDERED_BITS);
-      uint32_t fuse_dmask = 0;
-      const bool fuse = tiles && use32 && shz_seg_first_pass(g_lo_all, Bt_all, &fuse_dmask) == 8;
-      // the sub-group of every expand tile's first pair, for all passes in one launch: pass table (votes, first entry)
-      // up, one kernel
-      std::vector<uint32_t> toff(passes.size() + 1, 0);
-      std::vector<uint64_t> ptab(passes.size() * 2 + (passes.size() + 2) / 2);   // pv[2 n_pass] | toff[n_pass + 1] (u32)
-      for (size_t i = 0; i < passes.size(); ++i) {
-        ptab[2 * i] = passes[i].v_lo;
-        ptab[2 * i + 1] = passes[i].v_hi;
-        toff[i + 1] = toff[i] + (uint32_t)((passes[i].v_hi - passes[i].v_lo + M_EXP_TILE - 1) / M_EXP_TILE) + 1;
-      }
-      memcpy(ptab.data() + passes.size() * 2, toff.data(), toff.size() * 4);
-      SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_HCNT, (uint64_t)toff.back() * 4, &tile_x));   // (M5 belongs to the fold)
-      if (fuse) {
-      } else if (passes.size() == 1) {   // no table to send up
-        hipLaunchKernelGGL(m_tile_start_kernel, dim3(nblk(toff.back())), dim3(256), 0, ctx->stream, (const uint64_t*)po, (uint32_t)nx,
-                           passes[0].v_lo, passes[0].v_hi, toff.back() - 1, (uint32_t*)tile_x);
-      } else {
-        void* d_ptab;
-        SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_VT4, ptab.size() * 8, &d_ptab));
-        SHZ_HIP(ctx, shz_memcpy(ctx, d_ptab, ptab.data(), ptab.size() * 8, hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(m_tile_start_all_kernel, dim3(nblk(toff.back())), dim3(256), 0, ctx->stream, (const uint64_t*)po, (uint32_t)nx,
-                           (const uint64_t*)d_ptab, (const uint32_t*)((const uint64_t*)d_ptab + passes.size() * 2),
-                           (uint32_t)passes.size(), (uint32_t*)tile_x);
-      }
-      SHZ_HIP(ctx, hipGetLastError());
-      void* const tile_x_all = tile_x;
-      size_t pass_i = 0;
-      for (const vpass& vp : passes) {
-        const uint64_t pp = vp.v_hi - vp.v_lo;
-        const uint32_t nqp = vp.qb - vp.qa;
-        const uint32_t ntiles = (uint32_t)((pp + M_EXP_TILE - 1) / M_EXP_TILE);
-        m_bits mbp = mb;
-        if (use32) mbp.qb = (nqp > 1 && !tiles) ? bits_for(nqp - 1) : 0;
-        tile_x = (uint32_t*)tile_x_all + toff[pass_i++];
-        uint32_t *rs = r_sid + (uint64_t)vp.qa * topn, *ra = r_al + (uint64_t)vp.qa * topn, *rd = r_dd + (uint64_t)vp.qa * topn;
-        int32_t* rdl = (int32_t*)r_delta + (uint64_t)vp.qa * topn;
-        if (one_wg) {
-          uint32_t* k32 = (uint32_t*)v0;
-          hipLaunchKernelGGL(m_expand_kernel<uint32_t>, dim3(ntiles), dim3(256), 0, ctx->stream, (const uint64_t*)E,
-                             (const uint32_t*)gs, (const uint32_t*)tile_x, (const uint64_t*)po, (const uint32_t*)glo,
-                             (const shz_seg_dev*)d_segs, (uint32_t)nseg, vp.v_lo, vp.v_hi, mbp, (int64_t)0, k32);
-          vt_plan pl;
-          pl.nq = 1;
-          pl.dbits = mbp.dbits;
-          pl.sb = mbp.sb;
-          pl.g_lo = mbp.sb + mbp.dbits + 1;   // no bit is ordered: a sweep may split by any song-id bit
-          pl.tile = VW_CHUNK;
-          pl.flush = VW_FLUSH;
-          for (uint32_t i = 0; i <= VT_MAXQ; ++i) { pl.qv[i] = i ? (uint32_t)pp : 0u; pl.tb[i] = 0; }   // no tiles, one range
-          void *ts, *cp, *cd, *cdd;
-          SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_VT0, 64, &ts));
-          SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_VT1, (uint64_t)topn * 8, &cp));
-          SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_VT2, (uint64_t)topn * 4, &cd));
-          SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_VT3, (uint64_t)topn * 4, &cdd));
-          uint32_t* n_heavy = (uint32_t*)ts;
-          uint2* heavy = (uint2*)(n_heavy + 2);
-          uint32_t* heavy_q = n_heavy + 4;
-          hipLaunchKernelGGL(vt_one_range_kernel, dim3(1), dim3(1), 0, ctx->stream, n_heavy, heavy, heavy_q, (uint32_t)pp);
-          hipLaunchKernelGGL(vt_fold_kernel, dim3(1), dim3(VT_THREADS), 0, ctx->stream, (const uint32_t*)k32, (const uint2*)heavy,
-                             (const uint32_t*)n_heavy, 1u, pl, topn, (uint64_t*)cp, (uint32_t*)cd, (uint32_t*)cdd,
-                             vt_probe_limit_1 ? vt_probe_limit_1 : (uint32_t)VT_SLOTS, d_vt_err);
-          hipLaunchKernelGGL(vt_rank_kernel, dim3(1), dim3(VR_THREADS), 0, ctx->stream, pl, topn, mbp, (const uint64_t*)cp,
-                             (const uint32_t*)cd, (const uint32_t*)cdd, (const uint32_t*)n_heavy, (const uint32_t*)heavy_q, 1u,
-                             rs, rdl, ra, rd, r_n + vp.qa);
-          SHZ_HIP(ctx, hipGetLastError());
-        } else if (use32) {
-          uint32_t* k32 = (uint32_t*)v0;   // two 4-byte buffers in SORT_C, the widened result in SORT_D
-          if (!fuse) {
-            hipLaunchKernelGGL(m_expand_kernel<uint32_t>, dim3(ntiles), dim3(256), 0, ctx->stream, (const uint64_t*)E,
-                               (const uint32_t*)gs, (const uint32_t*)tile_x, (const uint64_t*)po, (const uint32_t*)glo,
-                               (const shz_seg_dev*)d_segs, (uint32_t)nseg, vp.v_lo, vp.v_hi, mbp,
-                               tiles ? M_NO_QUERY_BITS : -(int64_t)vp.qa, k32);
-            SHZ_HIP(ctx, hipGetLastError());
-          }
-          const int B = mbp.qb + mbp.sb + mbp.dbits + 1;
-          if (tiles) {
-            vt_plan pl;
-            shz_seg_plan sp;
-            std::vector<uint64_t> counts(nqp);
-            for (uint32_t i = 0; i < nqp; ++i) counts[i] = nq > 1 ? h_votes[vp.qa + i] : pp;
-            vt_make_plan(counts.data(), nqp, mbp, pl, sp);
-            const int Bt = mbp.sb + mbp.dbits + 1;   // the votes of a tile pass carry no query bits
-            (void)Bt;
-            if (fuse) {
-              const uint32_t stile = shz_seg_tile(pp), cpb = stile / M_EXP_TILE;
-              shz_seg_blocks(&sp, stile);
-              const uint32_t nsb = sp.bq[nqp];
-              void *cxp, *hist;
-              SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_VT5, (uint64_t)nsb * (cpb + 1) * 4, &cxp));
-              SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SORT_H, ((uint64_t)nsb << 8) * 4, &hist));   // (the sort asks for the same)
-              hipLaunchKernelGGL(m_chunk_start_kernel, dim3(nblk((uint64_t)nsb * (cpb + 1))), dim3(256), 0, ctx->stream,
-                                 (const uint64_t*)po, (uint32_t)nx, sp, stile, vp.v_lo, vp.v_hi, (uint32_t*)cxp);
-              hipLaunchKernelGGL(m_expand_blocks_kernel, dim3(nsb), dim3(256), 0, ctx->stream, (const uint64_t*)E,
-                                 (const uint32_t*)gs, (const uint32_t*)cxp, (const uint64_t*)po, (const uint32_t*)glo,
-                                 (const shz_seg_dev*)d_segs, (uint32_t)nseg, vp.v_lo, sp, stile, mbp, pl.g_lo, fuse_dmask, k32,
-                                 (uint32_t*)hist);
-              SHZ_HIP(ctx, hipGetLastError());
-            }
-            SHZ_TRY(vt_run_pass(ctx, k32, k32 + pmax4, pp, pl, sp, mbp, topn, fuse, t->max_sid, d_vt_err, rs, rdl, ra, rd, r_n + vp.qa));
-          } else {
-            SHZ_TRY(shz_sort_u32_widen(ctx, k32, k32 + pmax4, (uint64_t*)v1, pp, 1, B, 0, nullptr));
-            SHZ_TRY(vote_fold(ctx, (const uint64_t*)v1, pp, nqp, mbp, topn, tot + 4, rs, rdl, ra, rd, r_n + vp.qa));
-          }
-        } else {
-          hipLaunchKernelGGL(m_expand_kernel<uint64_t>, dim3(ntiles), dim3(256), 0, ctx->stream, (const uint64_t*)E,
-                             (const uint32_t*)gs, (const uint32_t*)tile_x, (const uint64_t*)po, (const uint32_t*)glo,
-                             (const shz_seg_dev*)d_segs, (uint32_t)nseg, vp.v_lo, vp.v_hi, mbp, (int64_t)0, (uint64_t*)v0);
-          SHZ_HIP(ctx, hipGetLastError());
-          SHZ_TRY(vote_tail(ctx, (uint64_t*)v0, (uint64_t*)v1, pp, nqp, mbp, topn, tot + 4, rs, rdl, ra, rd, r_n + vp.qa));
-        }
-      }
-    }
-    {
-      void* hb;
-      if (spec_done) {
-        ++ctx->st_spec_used;
-        hb = (char*)mailp + 256 + 8;   // came with the first read-back
-        if (trace) tr3 = now_s();
-      } else {
-        SHZ_TRY(shz_mailbox(ctx, rb_bytes, &hb));
-        SHZ_HIP(ctx, hipMemcpyAsync(hb, rb, rb_bytes, hipMemcpyDeviceToHost, ctx->stream));
-        if (trace) tr3 = now_s();
-        SHZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
-      }
-      if (trace)
-        fprintf(stderr, "match trace: head enqueue %.1f us, wait %.1f us, tail enqueue %.1f us, wait %.1f us (P %llu)\n",
-                (tr1 - tr0) * 1e6, (tr2 - tr1) * 1e6, (tr3 - tr2) * 1e6, (now_s() - tr3) * 1e6, (unsigned long long)P);
-      const uint64_t* h_np = (const uint64_t*)hb;
-      const uint32_t* h_sid = (const uint32_t*)(h_np + nq);
-      const uint32_t *h_delta = h_sid + nres, *h_al = h_delta + nres, *h_dd = h_al + nres, *h_n = h_dd + nres, *h_nh = h_n + nq;
-      if (h_nh[nq] != 0 && !redo_full_sort) {   // a vote tile overflowed (its results are void): the same queries again, full sort
-        ++ctx->st_vt_redo;
-        redo_full_sort = true;
-        continue;
-      }
-      redo_full_sort = false;
-      ctx->st_rows += rows_total;
-      ctx->st_pairs += P;
-      ctx->st_keys += ng;
-      if (nq == 1) {
-        if (out_npairs) out_npairs[q0] = P;
-        if (out_nhash) out_nhash[q0] = (uint32_t)mu;
-      } else {
-        if (out_npairs) memcpy(out_npairs + q0, h_np, (uint64_t)nq * 8);
-        if (out_nhash) memcpy(out_nhash + q0, h_nh, (uint64_t)nq * 4);
-      }
-      if (!vs_out) {
-        const uint64_t o0 = (uint64_t)q0 * topn;
-        memcpy(out_sid + o0, h_sid, nres * 4);
-        memcpy(out_delta + o0, h_delta, nres * 4);
-        memcpy(out_aligned + o0, h_al, nres * 4);
-        memcpy(out_dedup + o0, h_dd, nres * 4);
-        memcpy(out_nres + q0, h_n, (uint64_t)nq * 4);
-      }
-    }
-    q0 += nq;
   }
   return SHZ_OK;
 }
@@ -2577,8 +2796,9 @@ extern "C" int32_t shz_match_batch(shz_ctx* ctx, shz_table* t, const uint32_t* k
                                    const uint64_t* query_off, uint32_t n_queries, uint32_t topn, uint32_t flags,
                                    uint32_t* out_sid, int32_t* out_delta, uint32_t* out_aligned, uint32_t* out_dedup,
                                    uint32_t* out_nres, uint32_t* out_nhash, uint64_t* out_npairs) {
-  return match_core(ctx, t, key32, q_off, query_off, n_queries, topn, flags, out_sid, out_delta, out_aligned, out_dedup,
-                    out_nres, out_nhash, out_npairs, nullptr);
+  match_call mc{ctx, t, key32, q_off, query_off, n_queries, topn, flags, out_sid, out_delta, out_aligned, out_dedup,
+                out_nres, out_nhash, out_npairs, nullptr};
+  return match_core(mc);
 }
 
 extern "C" int32_t shz_table_maxima(shz_table* t, uint32_t* max_sid, uint32_t* max_off) {
@@ -2600,8 +2820,9 @@ extern "C" int32_t shz_match_pairs(shz_ctx* ctx, shz_table* t, const uint32_t* k
       bits_for(n_queries ? n_queries - 1 : 0) + sid_bits + delta_bits + 1 > 64)
     SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "shz_match_pairs: %u queries x %u sid bits x %u delta bits do not fit 64 bits", n_queries, sid_bits, delta_bits);
   pair_sink sink{d_pairs, cap, 0, m_bits{(int)sid_bits, (int)delta_bits, 0, bias}, shard, nshards};
-  SHZ_TRY(match_core(ctx, t, key32, q_off, query_off, n_queries, 1, flags, nullptr, nullptr, nullptr, nullptr, nullptr,
-                     out_nhash, out_npairs, &sink));
+  match_call mc{ctx, t, key32, q_off, query_off, n_queries, 1, flags, nullptr, nullptr, nullptr, nullptr, nullptr,
+                out_nhash, out_npairs, &sink};
+  SHZ_TRY(match_core(mc));
   *count = sink.count;
   if (sink.count > cap) SHZ_FAIL(ctx, SHZ_E_CAPACITY, "shz_match_pairs: %llu votes, capacity %llu", (unsigned long long)sink.count, (unsigned long long)cap);
   return SHZ_OK;
@@ -2678,19 +2899,21 @@ __global__ void pv_narrow_kernel(const uint64_t* __restrict__ pairs, uint64_t n,
     k32[i] = (uint32_t)pairs[i] & mask;
 }
 
+enum pv_tiles { PV_NOT_TAKEN /* nothing written */, PV_DONE, PV_REDO /* a tile gave up: the rows written are void */ };
+
 // Votes of shz_match_pairs (8 bytes, query index on top) -> results, by the path of the unsharded match: ONE stable sort
 // by the query bits (one or two passes over 8 bytes instead of the five of the full key), the query bits dropped, then
-// the vote-tile passes over 4-byte votes.  Returns false (nothing written) when the layout does not fit the tiles; *redo is
-// set when a tile gave up and the votes have to go through the full sort after all.
+// the vote-tile passes over 4-byte votes.  Where it is not taken or gives up, the votes go through the full sort.
+// It is ROUTE_TILES with another producer of the votes, and chosen by vote_plan_make's terms for that route: the 4-byte
+// switch, the tile layout (one bit tighter: vt_layout_fits), 2^22 votes -- but over the whole call, not per pass: the sort
+// by query and the read-back of the counts are paid before the passes are known.
 static int32_t pairs_vote_tiles(shz_ctx* ctx, uint64_t* d_pairs, uint64_t* d_alt, uint64_t n, uint32_t nq, const m_bits& mb,
-                                uint32_t topn, uint32_t* r_sid, int32_t* r_delta, uint32_t* r_al, uint32_t* r_dd, uint32_t* r_n,
-                                bool* done, bool* redo) {
-  *done = *redo = false;
+                                uint32_t topn, res_block r, pv_tiles* outcome) {
+  *outcome = PV_NOT_TAKEN;
+  const vote_switches& sw = vote_env();
   const int Bt = mb.sb + mb.dbits + 1;
-  static const int tiles_env = [] { const char* e = getenv("SHZ_VOTE_TILES"); return e ? atoi(e) : -1; }();
-  static const int force32 = [] { const char* e = getenv("SHZ_VOTE32"); return e ? atoi(e) : -1; }();   // 0 never, 1 whenever it fits
-  if (tiles_env == 0 || force32 == 0 || Bt > 31 || topn > VT_MAXTOPN || mb.dbits > VT_MAX_DBITS + VT_MAX_DSPLIT) return SHZ_OK;
-  if (force32 != 1 && n < (1ull << 22)) return SHZ_OK;   // few votes: the passes' launches cost more than the full sort's extra bytes
+  if (sw.vote32 == 0 || !vt_layout_fits(mb, topn, sw, 31)) return SHZ_OK;
+  if (sw.vote32 != 1 && n < (1ull << 22)) return SHZ_OK;   // few votes: the passes' launches cost more than the full sort's extra bytes
   // 1. by query (stable: the order inside a query does not matter to the tiles)
   int sel = 0;
   if (mb.qb > 0) SHZ_TRY(shz_sort_u64(ctx, d_pairs, d_alt, nullptr, nullptr, 0, n, Bt, Bt + mb.qb, &sel));
@@ -2700,12 +2923,14 @@ static int32_t pairs_vote_tiles(shz_ctx* ctx, uint64_t* d_pairs, uint64_t* d_alt
   SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_M0, ((uint64_t)nq + 1) * 8, &qs));
   SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_M1, 64, &flag));
   SHZ_HIP(ctx, hipMemsetAsync(flag, 0, 64, ctx->stream));
+  r.vt_err = (uint32_t*)flag;   // the tiles' error word: this call has no block to keep it in
   hipLaunchKernelGGL(pv_qstart_kernel, dim3(nblk((uint64_t)nq + 1)), dim3(256), 0, ctx->stream, sorted, n, Bt, nq,
                      (unsigned long long*)qs);
   SHZ_HIP(ctx, hipGetLastError());
-  std::vector<uint64_t> h_qs((size_t)nq + 1);
-  SHZ_HIP(ctx, shz_memcpy(ctx, h_qs.data(), qs, ((uint64_t)nq + 1) * 8, hipMemcpyDeviceToHost));
+  std::vector<uint64_t> votes((size_t)nq + 1);   // first vote of every query, then their numbers
+  SHZ_HIP(ctx, shz_memcpy(ctx, votes.data(), qs, ((uint64_t)nq + 1) * 8, hipMemcpyDeviceToHost));
   SHZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  for (uint32_t q = 0; q < nq; ++q) votes[q] = votes[q + 1] - votes[q];
   // 3. 4-byte votes; the other half of the buffer is the sort's second one
   void* kb;
   const uint64_t n4 = (n + 3) & ~3ull;
@@ -2717,32 +2942,34 @@ static int32_t pairs_vote_tiles(shz_ctx* ctx, uint64_t* d_pairs, uint64_t* d_alt
   // 4. passes of up to VT_MAXQ queries and 2^28 votes
   m_bits mbp = mb;
   mbp.qb = 0;
-  const uint64_t P_PASS = 1ull << 28;
-  for (uint32_t qa = 0; qa < nq;) {
-    uint32_t qb = qa;
-    while (qb < nq && qb - qa < (uint32_t)VT_MAXQ && (qb == qa || h_qs[qb + 1] - h_qs[qa] <= P_PASS)) ++qb;
-    const uint64_t v_lo = h_qs[qa], pp = h_qs[qb] - v_lo;
+  vote_pass vp{0, 0, 0, 0};
+  while (next_vote_pass(votes.data(), nq, (uint32_t)VT_MAXQ, &vp)) {
+    const uint64_t pp = vp.v_hi - vp.v_lo;
     if (pp >= (1ull << 32)) return SHZ_OK;   // (one query with 2^32 votes: the full sort's error message)
-    if (pp) {
-      const uint32_t nqp = qb - qa;
-      std::vector<uint64_t> counts(nqp);
-      for (uint32_t i = 0; i < nqp; ++i) counts[i] = h_qs[qa + i + 1] - h_qs[qa + i];
-      vt_plan pl;
-      shz_seg_plan sp;
-      vt_make_plan(counts.data(), nqp, mbp, pl, sp);
-      // the pass sorts inside [v_lo, v_lo + pp) of k32 and of the second buffer; both offsets 16-byte aligned by address
-      // is not required (the counting kernel aligns by address)
-      SHZ_TRY(vt_run_pass(ctx, k32 + v_lo, k32 + n4 + v_lo, pp, pl, sp, mbp, topn, false, mb.sb >= 31 ? 0x7FFFFFFFu : (1u << mb.sb),
-                          (uint32_t*)flag, r_sid + (uint64_t)qa * topn, r_delta + (uint64_t)qa * topn, r_al + (uint64_t)qa * topn,
-                          r_dd + (uint64_t)qa * topn, r_n + qa));
-    }
-    qa = qb;
+    if (pp == 0) continue;
+    vt_plan pl;
+    shz_seg_plan sp;
+    vt_make_plan(votes.data() + vp.qa, vp.qb - vp.qa, mbp, pl, sp);
+    // the pass sorts inside [v_lo, v_lo + pp) of k32 and of the second buffer; both offsets 16-byte aligned by address
+    // is not required (the counting kernel aligns by address)
+    SHZ_TRY(vt_run_pass(ctx, k32 + vp.v_lo, k32 + n4 + vp.v_lo, pp, pl, sp, mbp, topn, false,
+                        mb.sb >= 31 ? 0x7FFFFFFFu : (1u << mb.sb), res_rows(r, vp.qa, topn)));
   }
   uint32_t h_flag = 0;
-  SHZ_HIP(ctx, shz_memcpy(ctx, &h_flag, flag, 4, hipMemcpyDeviceToHost));
+  SHZ_HIP(ctx, shz_memcpy(ctx, &h_flag, r.vt_err, 4, hipMemcpyDeviceToHost));
   SHZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (h_flag) { ++ctx->st_vt_redo; *redo = true; return SHZ_OK; }
-  *done = true;
+  if (h_flag) ++ctx->st_vt_redo;
+  *outcome = h_flag ? PV_REDO : PV_DONE;
+  return SHZ_OK;
+}
+
+// (five arrays of shz_pairs_vote's own, not match_core's block that the probe zeroes along: the call has no probe)
+static int32_t pv_zero_results(shz_ctx* ctx, const res_block& r, uint32_t nq, uint64_t nres) {
+  SHZ_HIP(ctx, hipMemsetAsync(r.sid, 0, nres * 4, ctx->stream));
+  SHZ_HIP(ctx, hipMemsetAsync(r.delta, 0, nres * 4, ctx->stream));
+  SHZ_HIP(ctx, hipMemsetAsync(r.aligned, 0, nres * 4, ctx->stream));
+  SHZ_HIP(ctx, hipMemsetAsync(r.dedup, 0, nres * 4, ctx->stream));
+  SHZ_HIP(ctx, hipMemsetAsync(r.nres, 0, (uint64_t)nq * 4, ctx->stream));
   return SHZ_OK;
 }
 
@@ -2772,25 +2999,14 @@ extern "C" int32_t shz_pairs_vote(shz_ctx* ctx, uint64_t* d_pairs, uint64_t n, u
   SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_PEAK_CLIP, nres * 4, &r_al));
   SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_MISC1, nres * 4, &r_dd));
   SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_MISC2, (uint64_t)n_queries * 4, &r_n));
-  SHZ_HIP(ctx, hipMemsetAsync(r_sid, 0, nres * 4, ctx->stream));
-  SHZ_HIP(ctx, hipMemsetAsync(r_delta, 0, nres * 4, ctx->stream));
-  SHZ_HIP(ctx, hipMemsetAsync(r_al, 0, nres * 4, ctx->stream));
-  SHZ_HIP(ctx, hipMemsetAsync(r_dd, 0, nres * 4, ctx->stream));
-  SHZ_HIP(ctx, hipMemsetAsync(r_n, 0, (uint64_t)n_queries * 4, ctx->stream));
-  bool done = false, redo = false;
-  SHZ_TRY(pairs_vote_tiles(ctx, d_pairs, (uint64_t*)v1, n, n_queries, mb, topn, (uint32_t*)r_sid, (int32_t*)r_delta, (uint32_t*)r_al,
-                           (uint32_t*)r_dd, (uint32_t*)r_n, &done, &redo));
-  if (redo) {   // a tile gave up: its rows of the result arrays are void
-    SHZ_HIP(ctx, hipMemsetAsync(r_sid, 0, nres * 4, ctx->stream));
-    SHZ_HIP(ctx, hipMemsetAsync(r_delta, 0, nres * 4, ctx->stream));
-    SHZ_HIP(ctx, hipMemsetAsync(r_al, 0, nres * 4, ctx->stream));
-    SHZ_HIP(ctx, hipMemsetAsync(r_dd, 0, nres * 4, ctx->stream));
-    SHZ_HIP(ctx, hipMemsetAsync(r_n, 0, (uint64_t)n_queries * 4, ctx->stream));
-  }
+  const res_block r{nullptr, (uint32_t*)r_sid, (int32_t*)r_delta, (uint32_t*)r_al, (uint32_t*)r_dd, (uint32_t*)r_n, nullptr,
+                    nullptr};
+  SHZ_TRY(pv_zero_results(ctx, r, n_queries, nres));
+  pv_tiles tiles;
+  SHZ_TRY(pairs_vote_tiles(ctx, d_pairs, (uint64_t*)v1, n, n_queries, mb, topn, r, &tiles));
+  if (tiles == PV_REDO) SHZ_TRY(pv_zero_results(ctx, r, n_queries, nres));
   // (the full sort orders any permutation of the votes: whatever the sort by query left in d_pairs / v1 is fine for it)
-  if (!done)
-    SHZ_TRY(vote_tail(ctx, d_pairs, (uint64_t*)v1, n, n_queries, mb, topn, (uint64_t*)tot, (uint32_t*)r_sid, (int32_t*)r_delta,
-                      (uint32_t*)r_al, (uint32_t*)r_dd, (uint32_t*)r_n));
+  if (tiles != PV_DONE) SHZ_TRY(vote_tail(ctx, d_pairs, (uint64_t*)v1, n, n_queries, mb, topn, (uint64_t*)tot, r));
   SHZ_HIP(ctx, shz_memcpy(ctx, out_sid, r_sid, nres * 4, hipMemcpyDeviceToHost));
   SHZ_HIP(ctx, shz_memcpy(ctx, out_delta, r_delta, nres * 4, hipMemcpyDeviceToHost));
   SHZ_HIP(ctx, shz_memcpy(ctx, out_aligned, r_al, nres * 4, hipMemcpyDeviceToHost));
@@ -2799,4 +3015,3 @@ extern "C" int32_t shz_pairs_vote(shz_ctx* ctx, uint64_t* d_pairs, uint64_t n, u
   SHZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return SHZ_OK;
 }
-
