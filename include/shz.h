@@ -323,6 +323,25 @@ int32_t shz_match_batch(shz_ctx* ctx, shz_table* t, const uint32_t* key32, const
                         const uint64_t* query_off, uint32_t n_queries, uint32_t topn, uint32_t flags,
                         uint32_t* out_sid, int32_t* out_delta, uint32_t* out_aligned, uint32_t* out_dedup,
                         uint32_t* out_nres, uint32_t* out_nhash, uint64_t* out_npairs);
+/* recognize() for a batch of queries in one call (recognizer.py:377-392: fingerprint every channel, union the hashes,
+ * return_matches, align_matches): shz_fingerprint_batch and shz_match_batch joined on the device -- the hashes are written
+ * to buffers the library owns and matched there, none crosses the bus.  Clips as for shz_fingerprint_batch (pcm host, or
+ * device with SHZ_PCM_DEVICE); query q owns the adjacent clips (its channels) [query_clip0[q], query_clip0[q + 1]):
+ * query_clip0 has n_queries + 1 entries, starts at 0, does not decrease and ends at n_clips, else SHZ_E_INVALID before
+ * anything is launched (as for topn outside [1, 64] or a table that is not finalized: SHZ_E_STATE).  There is no capacity
+ * to pass and no SHZ_E_CAPACITY: the buffers are sized from the frame counts (shz_recognize_estimate) and the extraction
+ * is repeated once with the room it asked for.  flags: SHZ_PCM_DEVICE, SHZ_MATCH_FULL_SORT.  Outputs: the seven of
+ * shz_match_batch, same shapes and meaning -- the same arrays as the two calls give.  A single small query keeps the
+ * queued one-workgroup fold (shz_match_spec_stats): its bias is the largest frame count of the clips - 1, which bounds
+ * every t1.  ms_extract / ms_match (may be NULL): hipEvent times of the two halves on the ctx stream. */
+int32_t shz_recognize_batch(shz_ctx* ctx, shz_table* t, const int16_t* pcm, const uint64_t* clip_off, uint32_t n_clips,
+                            const uint32_t* query_clip0, uint32_t n_queries, uint32_t fs, double amp_min, uint32_t fan_value,
+                            uint32_t topn, uint32_t flags, uint32_t* out_sid, int32_t* out_delta, uint32_t* out_aligned,
+                            uint32_t* out_dedup, uint32_t* out_nres, uint32_t* out_nhash, uint64_t* out_npairs,
+                            float* ms_extract, float* ms_match);
+/* No GPU, no ctx: the entries the first extraction pass of shz_recognize_batch has room for, for clips of `frames` frames
+ * in all (an input with more hashes takes the repeated pass). */
+uint64_t shz_recognize_estimate(uint64_t frames, uint32_t fan_value);
 /* Test switches that force the vote tiles' rare paths (never set in production): SHZ_DEBUG_VT_TINY_HEAVY gives the list
  * of ranges handed from vt_stream to vt_fold room for ONE range; SHZ_DEBUG_VT_PROBE1 lets an LDS hash probe give up
  * after one round (what a full table would cause).  Either way the pass's flag word is set, and the sub-batch is voted
@@ -478,6 +497,37 @@ int32_t shz_streams_state(shz_streams* s, uint32_t i, uint64_t* samples, uint64_
  * horizon of the stream. */
 int32_t shz_stream_plan(uint64_t samples_before, uint64_t samples_after, uint64_t settled_before, uint32_t hop,
                         int32_t ending, uint64_t* win_frame0, uint64_t* win_s0, uint64_t* win_s1, uint64_t* settled_after);
+
+
+/* ---- device-resident listeners (new; the loop around recognize() that reads a microphone, recognizer.py:357-392, for many
+ * listeners at once) ---------------------------------------------------------------------------------------------------
+ * n_listeners listeners over the streams of `s`: listener l is the `channels` = n_streams / n_listeners adjacent streams
+ * [l channels, (l + 1) channels) (n_listeners must divide the streams: else SHZ_E_INVALID), whose hashes are unioned
+ * (recognizer.py:377-382).  Each listener keeps, ON THE DEVICE, the window of its settled hashes (key32, absolute t1) with
+ * t1 >= w0 = max(0, H - window_frames), H the smallest settled horizon of its channels (shz_listener_window).  The object
+ * does not own the streams or the table; both must outlive it and belong to one ctx.  While it exists, push and reset the
+ * streams through it only.  Not thread-safe, like the ctx. */
+typedef struct shz_listeners shz_listeners;
+int32_t shz_listeners_create(shz_streams* s, shz_table* t, uint32_t n_listeners, uint32_t window_frames, shz_listeners** out);
+int32_t shz_listeners_destroy(shz_listeners* L);
+/* One shz_streams_push (pcm, chunk_off, end: per STREAM, as there; device output into buffers of the object, repeated with
+ * room on its SHZ_E_CAPACITY), the new hashes merged into the windows and the expired ones dropped on the device, and ALL
+ * listeners recognised in one match on the device-resident windows with query offsets t1 - w0: what `offset` means for a
+ * clip recorded from frame w0.  Outputs as shz_match_batch with n_queries = n_listeners (a listener whose window is empty:
+ * nres = nhash = 0; an ended listener keeps its window and is matched again), plus out_w0[n_listeners] (may be NULL).
+ * flags: SHZ_PCM_DEVICE, SHZ_MATCH_FULL_SORT.  Bad arguments, topn outside [1, 64], a table that is not finalized, a hop
+ * that changed since the streams were created (SHZ_E_STATE) and whatever shz_streams_push refuses leave every stream and
+ * every window as they were. */
+int32_t shz_listeners_push(shz_listeners* L, const int16_t* pcm, const uint64_t* chunk_off, const uint32_t* end, uint32_t topn,
+                           uint32_t flags, uint32_t* out_sid, int32_t* out_delta, uint32_t* out_aligned, uint32_t* out_dedup,
+                           uint32_t* out_nres, uint32_t* out_nhash, uint64_t* out_npairs, uint32_t* out_w0);
+/* start LISTENERS afresh: their streams (shz_streams_reset) and their windows */
+int32_t shz_listeners_reset(shz_listeners* L, const uint32_t* which, uint32_t n);
+/* listener l: hashes in its window, and the w0 of its last push (any pointer may be NULL) */
+int32_t shz_listeners_state(shz_listeners* L, uint32_t l, uint64_t* window_hashes, uint64_t* w0);
+/* No GPU, no ctx (like shz_stream_plan): the window of a listener whose channels have settled[0 .. channels) frames:
+ * *horizon = their minimum H, *w0 = max(0, H - window_frames). */
+int32_t shz_listener_window(const uint64_t* settled, uint32_t channels, uint32_t window_frames, uint64_t* horizon, uint64_t* w0);
 
 #ifdef __cplusplus
 }

@@ -240,15 +240,43 @@ def _result_dicts(db, res, q, queried_hashes):
     return out
 
 
-def recognize_batch(queries, db, Fs: int = RATE, topn: int = TOPN):
+def _recognize_fused(queries, chans, owner, db, Fs, topn):
+    """recognize_batch through shz_recognize_batch: one call, the hashes never leave the device."""
+    if not hasattr(db.table, "h"):
+        raise NotImplementedError("fused recognition takes the unsharded table (shards=1)")
+    ctx = db.ctx
+    if getattr(ctx, "hop", HOP) != HOP:
+        ctx.set_overlap(NFFT - HOP)
+    db.finalize()
+    arrs = [_as_pcm(c) for c in chans]
+    off = np.zeros(len(arrs) + 1, np.uint64)
+    if arrs:
+        off[1:] = np.cumsum([len(a) for a in arrs])
+    pcm = np.concatenate(arrs) if off[-1] else np.zeros(1, np.int16)
+    nq = len(queries)
+    first = np.searchsorted(np.asarray(owner, np.int64), np.arange(nq + 1)).astype(np.uint32)
+    res, ms_extract, ms_match = ctx.recognize_batch(db.table, pcm, off, first, fs=int(Fs), amp_min=float(DEFAULT_AMP_MIN),
+                                                    fan_value=DEFAULT_FAN_VALUE, topn=int(topn))
+    t0 = time()
+    results = [_result_dicts(db, res, q, int(res["nhash"][q])) for q in range(nq)]
+    align_time = time() - t0
+    return results, {"fingerprint_time": ms_extract * 1e-3, "query_time": ms_match * 1e-3, "align_time": align_time,
+                     "n_matches": res["npairs"], "n_hashes": res["nhash"]}
+
+
+def recognize_batch(queries, db, Fs: int = RATE, topn: int = TOPN, fused: bool = False):
     """Recognise flow (recognizer.py:377-392) for many queries at once.  Each query is a list of
-    channels (1-D int16 arrays) or a single 1-D array.  Returns (results_per_query, timings)."""
+    channels (1-D int16 arrays) or a single 1-D array.  Returns (results_per_query, timings).
+    fused: fingerprint and match in ONE library call with the hashes staying on the device (shz_recognize_batch);
+    same results, fingerprint_time / query_time are then the device times of the two halves."""
     ctx = db.ctx
     chans, owner = [], []
     for qi, q in enumerate(queries):
         cs = [q] if (isinstance(q, np.ndarray) and q.ndim == 1) else list(q)
         chans.extend(cs)
         owner.extend([qi] * len(cs))
+    if fused:
+        return _recognize_fused(queries, chans, owner, db, Fs, topn)
     t0 = time()
     k, t1, ho = fingerprint_batch(chans, Fs, ctx=ctx)
     fingerprint_time = time() - t0
@@ -267,13 +295,13 @@ def recognize_batch(queries, db, Fs: int = RATE, topn: int = TOPN):
                      "n_matches": res["npairs"], "n_hashes": res["nhash"]}
 
 
-def recognize(channels_or_samples, db=None, Fs: int = RATE, topn: int = TOPN):
-    """recognizer.py:377-396: (final_results, fingerprint_time, query_time, align_time)."""
+def recognize(channels_or_samples, db=None, Fs: int = RATE, topn: int = TOPN, fused: bool = False):
+    """recognizer.py:377-396: (final_results, fingerprint_time, query_time, align_time).  fused: see recognize_batch."""
     if db is None:
         raise ValueError("recognize() needs the HipFingerprintDB holding the fingerprints")
     x = channels_or_samples
     q = [np.asarray(x)] if (not isinstance(x, (list, tuple)) or (len(x) and np.isscalar(x[0]))) else list(x)
-    results, tm = recognize_batch([q], db, Fs, topn)
+    results, tm = recognize_batch([q], db, Fs, topn, fused)
     return results[0], tm["fingerprint_time"], tm["query_time"], tm["align_time"]
 
 

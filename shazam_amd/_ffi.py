@@ -87,6 +87,10 @@ SIGNATURES = {
     "shz_table_song_rows": (C.c_int32, [vp, C.c_uint32, u64p]),
     "shz_match_batch": (C.c_int32, [vp, vp, vp, vp, u64p, C.c_uint32, C.c_uint32, C.c_uint32,
                                     vp, vp, vp, vp, vp, vp, vp]),
+    "shz_recognize_batch": (C.c_int32, [vp, vp, vp, u64p, C.c_uint32, u32p, C.c_uint32, C.c_uint32, C.c_double, C.c_uint32,
+                                        C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, C.POINTER(C.c_float),
+                                        C.POINTER(C.c_float)]),
+    "shz_recognize_estimate": (C.c_uint64, [C.c_uint64, C.c_uint32]),
     "shz_match_stats": (C.c_int32, [vp, u64p, u64p, u64p]),
     "shz_set_debug": (C.c_int32, [vp, C.c_uint32]),
     "shz_match_vt_redo": (C.c_int32, [vp, u64p]),
@@ -123,6 +127,12 @@ SIGNATURES = {
     "shz_streams_reset": (C.c_int32, [vp, vp, C.c_uint32]),
     "shz_streams_state": (C.c_int32, [vp, C.c_uint32, u64p, u64p, u64p, u64p]),
     "shz_stream_plan": (C.c_int32, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int32, u64p, u64p, u64p, u64p]),
+    "shz_listeners_create": (C.c_int32, [vp, vp, C.c_uint32, C.c_uint32, C.POINTER(vp)]),
+    "shz_listeners_destroy": (C.c_int32, [vp]),
+    "shz_listeners_push": (C.c_int32, [vp, vp, u64p, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "shz_listeners_reset": (C.c_int32, [vp, vp, C.c_uint32]),
+    "shz_listeners_state": (C.c_int32, [vp, C.c_uint32, u64p, u64p]),
+    "shz_listener_window": (C.c_int32, [u64p, C.c_uint32, C.c_uint32, u64p, u64p]),
 }
 
 
@@ -537,6 +547,22 @@ class Context:
             n = int(cnt.value)
             return k[:n], t1[:n], ho, n
 
+    def recognize_batch(self, table: "Table", pcm, clip_off, query_clip0, fs=44100, amp_min=10.0, fan_value=5, topn=2,
+                        pcm_device=False, full_sort=False):
+        """shz_recognize_batch: fingerprint the clips and match query q = clips [query_clip0[q], query_clip0[q + 1]) in one
+        call, the hashes staying on the device.  Returns (res, ms_extract, ms_match), res as Table.match."""
+        co, nc = self._clip_off(clip_off)
+        qc = np.ascontiguousarray(query_clip0, np.uint32)
+        nq = len(qc) - 1
+        res = _match_result(nq, topn)
+        me, mm = C.c_float(), C.c_float()
+        self.check(lib().shz_recognize_batch(self.h, table.h, ptr(pcm), co.ctypes.data_as(u64p), nc, qc.ctypes.data_as(u32p), nq,
+                                             int(fs), float(amp_min), int(fan_value), int(topn),
+                                             (PCM_DEVICE if pcm_device else 0) | (MATCH_FULL_SORT if full_sort else 0),
+                                             ptr(res["sid"]), ptr(res["delta"]), ptr(res["aligned"]), ptr(res["dedup"]),
+                                             ptr(res["nres"]), ptr(res["nhash"]), ptr(res["npairs"]), C.byref(me), C.byref(mm)))
+        return res, float(me.value), float(mm.value)
+
     def sha1_prefix(self, key32, device=False, n=None) -> np.ndarray:
         if not device:
             key32 = np.ascontiguousarray(key32, np.uint32)
@@ -555,6 +581,19 @@ def _sha1_invert(self, digests10: np.ndarray) -> np.ndarray:
 
 
 Context.sha1_invert = _sha1_invert
+
+
+def _match_result(nq: int, topn: int) -> dict:
+    """Zeroed output arrays of a match over nq queries (include/shz.h at shz_match_batch)."""
+    return {
+        "sid": np.zeros((nq, topn), np.uint32), "delta": np.zeros((nq, topn), np.int32),
+        "aligned": np.zeros((nq, topn), np.uint32), "dedup": np.zeros((nq, topn), np.uint32),
+        "nres": np.zeros(nq, np.uint32), "nhash": np.zeros(nq, np.uint32), "npairs": np.zeros(nq, np.uint64)}
+
+
+def recognize_estimate(frames: int, fan_value: int = 5) -> int:
+    """shz_recognize_estimate (host only): entries the first extraction pass of the fused call has room for."""
+    return int(lib().shz_recognize_estimate(int(frames), int(fan_value)))
 
 
 class Table:
@@ -701,10 +740,7 @@ class Table:
         o = np.ascontiguousarray(q_off, np.uint32)
         qo = np.ascontiguousarray(query_off, np.uint64)
         nq = len(qo) - 1
-        res = {
-            "sid": np.zeros((nq, topn), np.uint32), "delta": np.zeros((nq, topn), np.int32),
-            "aligned": np.zeros((nq, topn), np.uint32), "dedup": np.zeros((nq, topn), np.uint32),
-            "nres": np.zeros(nq, np.uint32), "nhash": np.zeros(nq, np.uint32), "npairs": np.zeros(nq, np.uint64)}
+        res = _match_result(nq, topn)
         self.ctx.check(lib().shz_match_batch(self.ctx.h, self.h, ptr(k), ptr(o), qo.ctypes.data_as(u64p), nq, topn,
                                              MATCH_FULL_SORT if full_sort else 0,
                                              ptr(res["sid"]), ptr(res["delta"]), ptr(res["aligned"]), ptr(res["dedup"]),
@@ -844,3 +880,68 @@ class Streams:
         v = [C.c_uint64() for _ in range(4)]
         self.ctx.check(lib().shz_streams_state(self.h, int(i), *[C.byref(x) for x in v]))
         return dict(zip(("samples", "settled", "pending", "emitted"), (int(x.value) for x in v)))
+
+
+def listener_window(settled, window_frames: int):
+    """shz_listener_window (host only): (H, w0) of a listener whose channels have settled[c] frames."""
+    st = np.ascontiguousarray(settled, np.uint64)
+    h, w0 = C.c_uint64(), C.c_uint64()
+    rc = lib().shz_listener_window(st.ctypes.data_as(u64p), len(st), int(window_frames), C.byref(h), C.byref(w0))
+    if rc != OK:
+        raise ShzError(rc, "shz_listener_window: invalid arguments")
+    return int(h.value), int(w0.value)
+
+
+class Listeners:
+    """Device-resident listeners over a Streams object and a Table (shz_listeners_*): listener l = the adjacent streams
+    [l channels, (l + 1) channels); its window of settled hashes stays on the device between pushes."""
+
+    def __init__(self, streams: Streams, table: Table, n_listeners: int, window_frames: int):
+        self.ctx, self.streams, self.table, self.h, self.n = streams.ctx, streams, table, None, int(n_listeners)
+        h = vp()
+        self.ctx.check(lib().shz_listeners_create(streams.h, table.h, self.n, int(window_frames), C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if self.h and self.ctx.h and self.streams.h:
+            lib().shz_listeners_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def push_raw(self, pcm, chunk_off, end=None, topn=2, pcm_device=False, full_sort=False):
+        """One shz_listeners_push as it is: (rc, res, w0) with res as Table.match over the listeners."""
+        co = np.ascontiguousarray(chunk_off, np.uint64)
+        assert len(co) == self.streams.n + 1
+        ew = self.streams._end_bits(end)
+        res, w0 = _match_result(self.n, topn), np.zeros(self.n, np.uint32)
+        rc = lib().shz_listeners_push(self.h, ptr(pcm), co.ctypes.data_as(u64p), ptr(ew), int(topn),
+                                      (PCM_DEVICE if pcm_device else 0) | (MATCH_FULL_SORT if full_sort else 0),
+                                      ptr(res["sid"]), ptr(res["delta"]), ptr(res["aligned"]), ptr(res["dedup"]),
+                                      ptr(res["nres"]), ptr(res["nhash"]), ptr(res["npairs"]), ptr(w0))
+        return rc, res, w0
+
+    def push(self, chunks, end=None, topn=2):
+        """chunks: one 1-D int16 array per STREAM (None / empty: nothing for it); end: stream indices that end after this
+        chunk.  Returns (res, w0)."""
+        assert len(chunks) == self.streams.n
+        arrs = [np.zeros(0, np.int16) if c is None else np.ascontiguousarray(c, np.int16) for c in chunks]
+        off = np.zeros(self.streams.n + 1, np.uint64)
+        off[1:] = np.cumsum([len(a) for a in arrs])
+        pcm = np.concatenate(arrs) if off[-1] else np.zeros(1, np.int16)
+        rc, res, w0 = self.push_raw(pcm, off, end, topn)
+        self.ctx.check(rc)
+        return res, w0
+
+    def reset(self, which=None):
+        w = np.ascontiguousarray(range(self.n) if which is None else which, np.uint32)
+        self.ctx.check(lib().shz_listeners_reset(self.h, ptr(w), len(w)))
+
+    def state(self, l: int) -> dict:
+        a, b = C.c_uint64(), C.c_uint64()
+        self.ctx.check(lib().shz_listeners_state(self.h, int(l), C.byref(a), C.byref(b)))
+        return {"window_hashes": int(a.value), "w0": int(b.value)}

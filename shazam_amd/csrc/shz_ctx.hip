@@ -366,6 +366,8 @@ extern "C" int32_t shz_ctx_destroy(shz_ctx* ctx) {
     if (ctx->pin[i]) (void)hipHostFree(ctx->pin[i]);
     if (ctx->pin_ev[i]) (void)hipEventDestroy(ctx->pin_ev[i]);
   }
+  for (hipEvent_t e : ctx->rq_ev)
+    if (e) (void)hipEventDestroy(e);
   if (ctx->tev_init)
     for (auto& e : ctx->tev) {
       (void)hipEventDestroy(e[0]);

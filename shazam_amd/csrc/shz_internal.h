@@ -80,6 +80,7 @@ enum {
   SHZ_WS_VT4,        // table of the vote passes
   SHZ_WS_VT5,        // sub-group of every expand chunk's first vote (expand by sort blocks)
   SHZ_WS_VT6,        // the bar of every query of a vote pass (vt_stream2_kernel)
+  SHZ_WS_RQ_KEY, SHZ_WS_RQ_T1,   // hashes of shz_recognize_batch between its extraction and its match (neither reserves them)
   SHZ_WS_COUNT
 };
 
@@ -107,6 +108,7 @@ struct shz_ctx {
   // timers / profiling
   hipEvent_t tev[16][2];
   bool tev_init = false;
+  hipEvent_t rq_ev[3] = {nullptr, nullptr, nullptr};   // shz_recognize_batch: start, extraction done, match done (created on first use)
   bool profiling = false;
   float kernel_ms[8] = {0};
   uint32_t kernel_launches[8] = {0};
@@ -202,6 +204,13 @@ void shz_seg_blocks(shz_seg_plan* sp, uint32_t tile);       // bq from nq, qv
 int shz_seg_first_pass(int bit_lo, int bit_hi, uint32_t* dmask);   // digit width (8 or 9) and mask of the first pass
 int32_t shz_sort_u32_widen(shz_ctx* ctx, uint32_t* k0, uint32_t* k1, uint64_t* out64, uint64_t n, int bit_lo, int bit_hi,
                            uint64_t add, int* sel);
+
+// ---- match on device columns the library owns (shz_table.hip) ------------------------------
+int32_t shz_match_device(shz_ctx* ctx, shz_table* t, const uint32_t* d_key32, const uint32_t* d_q_off, const uint64_t* query_off,
+                         uint32_t n_queries, uint32_t topn, uint32_t flags, int64_t bias_bound, uint32_t* out_sid,
+                         int32_t* out_delta, uint32_t* out_aligned, uint32_t* out_dedup, uint32_t* out_nres, uint32_t* out_nhash,
+                         uint64_t* out_npairs);
+int32_t shz_match_ready(shz_ctx* ctx, shz_table* t, uint32_t topn);
 
 // ---- RCCL helpers (shz_comm.hip) ----------------------------------------------------------
 int32_t shz_comm_info(shz_comm* c, int* rank, int* nranks);

@@ -20,6 +20,7 @@
 #include <algorithm>
 
 #include "shz_internal.h"
+#include "shz_table_int.h"
 
 #define ST_PEND 64            // carried peaks per stream slot: at most fan - 1 <= 63 after a push (rule (a))
 #define ST_THREADS 256
@@ -572,4 +573,270 @@ extern "C" int32_t shz_streams_push(shz_streams* s, const int16_t* pcm, const ui
     if (j.ending) s->ended[i] = 1;
   }
   return SHZ_OK;
+}
+
+// ---- device-resident listeners -------------------------------------------------------------------------------------
+// A listener is `channels` adjacent streams whose settled hashes are unioned (recognizer.py:377-382) and recognised from a
+// sliding window: the hashes with t1 >= w0 = max(0, H - window_frames), H the smallest settled horizon of its channels,
+// query offsets t1 - w0.  The windows live on the device as two packed slots of (key32, absolute t1) columns, listener l's
+// entries at [w_at[l], w_at[l] + w_n[l]) of the current slot.  One push: the streams' push with device output, one small
+// upload (per listener: where its old and its new entries are, and w0), listener_count_kernel, a scan over the listeners,
+// listener_write_kernel -- kept old entries, then kept new ones, compacted in order into the OTHER slot, and in the same
+// pass the query offsets t1 - w0 beside them (the query's key column is the new window's) -- one read-back of the counts,
+// which are the match's query_off, and the match on device input.  The slots flip once the counts are back, so a push that
+// fails before leaves every window as it was.
+
+#define LS_THREADS 256
+
+struct ls_job {
+  uint64_t old_at, new_at;   // first old entry in the current window slot; first new entry in the push's hashes
+  uint32_t old_n, new_n;
+  uint32_t w0, pad;
+};
+
+struct shz_listeners {
+  shz_streams* s = nullptr;
+  shz_table* t = nullptr;
+  shz_ctx* ctx = nullptr;
+  uint32_t n = 0, channels = 0, window_frames = 0;
+  shz_buf wk[2], wt[2];            // the two window slots
+  uint32_t cur = 0;                // the slot that holds the windows
+  std::vector<uint64_t> w_at;
+  std::vector<uint32_t> w_n, w0;
+  shz_buf nk, nt;                  // the hashes of a push
+  uint64_t new_cap = 0;            // entries nk / nt hold
+  shz_buf qo, jobs, ctl;           // query offsets; ls_job per listener; total | counts | offsets
+};
+
+// entry i of a listener's old-then-new list and whether the window keeps it
+__device__ __forceinline__ bool ls_entry(const ls_job& j, uint32_t i, const uint32_t* __restrict__ wk, const uint32_t* __restrict__ wt,
+                                         const uint32_t* __restrict__ nk, const uint32_t* __restrict__ nt, uint32_t* k, uint32_t* t) {
+  if (i >= j.old_n + j.new_n) return false;
+  if (i < j.old_n) {
+    *t = wt[j.old_at + i];
+    if (k) *k = wk[j.old_at + i];
+  } else {
+    *t = nt[j.new_at + (i - j.old_n)];
+    if (k) *k = nk[j.new_at + (i - j.old_n)];
+  }
+  return *t >= j.w0;
+}
+
+// per listener: entries its window keeps (one ballot per 64 entries, the waves' sums through LDS)
+__global__ __launch_bounds__(LS_THREADS) void listener_count_kernel(const ls_job* __restrict__ jobs, const uint32_t* __restrict__ wt,
+                                                                    const uint32_t* __restrict__ nt, uint64_t* __restrict__ cnt) {
+  const ls_job j = jobs[blockIdx.x];
+  const uint32_t n = j.old_n + j.new_n;
+  __shared__ uint32_t s_w[LS_THREADS / 64];
+  uint32_t c = 0;   // (the same in every lane of a wave)
+  for (uint32_t i0 = 0; i0 < n; i0 += LS_THREADS) {
+    uint32_t t;
+    const bool keep = ls_entry(j, i0 + threadIdx.x, nullptr, wt, nullptr, nt, nullptr, &t);
+    c += (uint32_t)__popcll(__ballot(keep));
+  }
+  if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = c;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t all = 0;
+    for (uint32_t i = 0; i < LS_THREADS / 64; ++i) all += s_w[i];
+    cnt[blockIdx.x] = all;
+  }
+}
+
+// per listener: the kept entries, in order, at offs[listener] of the other window slot, and their query offsets
+__global__ __launch_bounds__(LS_THREADS) void listener_write_kernel(const ls_job* __restrict__ jobs, const uint32_t* __restrict__ wk,
+                                                                    const uint32_t* __restrict__ wt, const uint32_t* __restrict__ nk,
+                                                                    const uint32_t* __restrict__ nt, const uint64_t* __restrict__ offs,
+                                                                    const unsigned long long* __restrict__ total, uint64_t cap,
+                                                                    uint32_t* __restrict__ wk_out, uint32_t* __restrict__ wt_out,
+                                                                    uint32_t* __restrict__ qo) {
+  if (*total > cap) return;   // (uniform; the host sizes the slots by a bound, so this never holds: it keeps a wrong bound harmless)
+  const ls_job j = jobs[blockIdx.x];
+  const uint32_t n = j.old_n + j.new_n, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  __shared__ uint32_t s_w[2][LS_THREADS / 64];
+  uint64_t o = offs[blockIdx.x];
+  for (uint32_t i0 = 0, it = 0; i0 < n; i0 += LS_THREADS, ++it) {
+    uint32_t k = 0, t = 0;
+    const bool keep = ls_entry(j, i0 + threadIdx.x, wk, wt, nk, nt, &k, &t);
+    const unsigned long long b = __ballot(keep);
+    const uint32_t pre = __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
+    uint32_t* sw = s_w[it & 1];   // (two rows: a wave may start the next round while another still reads this one's sums)
+    if (lane == 0) sw[w] = (uint32_t)__popcll(b);
+    __syncthreads();
+    uint32_t base = 0, all = 0;
+    for (uint32_t i = 0; i < LS_THREADS / 64; ++i) {
+      const uint32_t v = sw[i];
+      if (i < w) base += v;
+      all += v;
+    }
+    if (keep) {
+      const uint64_t p = o + base + pre;
+      wk_out[p] = k;
+      wt_out[p] = t;
+      qo[p] = t - j.w0;
+    }
+    o += all;
+  }
+}
+
+extern "C" int32_t shz_listeners_create(shz_streams* s, shz_table* t, uint32_t n_listeners, uint32_t window_frames,
+                                        shz_listeners** out) {
+  if (!s || !s->ctx || !out) return SHZ_E_INVALID;
+  *out = nullptr;
+  shz_ctx* ctx = s->ctx;
+  if (!t || t->ctx != ctx) SHZ_FAIL(ctx, SHZ_E_INVALID, "listeners: the table must belong to the streams' ctx");
+  if (n_listeners == 0 || s->n % n_listeners != 0)
+    SHZ_FAIL(ctx, SHZ_E_INVALID, "listeners: %u listeners do not divide %u streams into channels", n_listeners, s->n);
+  if (window_frames >= (1u << 20)) SHZ_FAIL(ctx, SHZ_E_INVALID, "listeners: window_frames must be < 2^20 (query offsets)");
+  shz_listeners* L = new shz_listeners();
+  L->s = s;
+  L->t = t;
+  L->ctx = ctx;
+  L->n = n_listeners;
+  L->channels = s->n / n_listeners;
+  L->window_frames = window_frames;
+  L->w_at.assign(n_listeners, 0);
+  L->w_n.assign(n_listeners, 0);
+  L->w0.assign(n_listeners, 0);
+  *out = L;
+  return SHZ_OK;
+}
+
+extern "C" int32_t shz_listeners_destroy(shz_listeners* L) {
+  if (!L) return SHZ_E_INVALID;
+  if (L->ctx) {
+    (void)hipSetDevice(L->ctx->device);
+    (void)hipStreamSynchronize(L->ctx->stream);
+  }
+  for (shz_buf* b : {&L->wk[0], &L->wk[1], &L->wt[0], &L->wt[1], &L->nk, &L->nt, &L->qo, &L->jobs, &L->ctl}) st_free(*b);
+  delete L;
+  return SHZ_OK;
+}
+
+static int32_t ls_check(shz_listeners* L) {
+  if (!L || !L->s) return SHZ_E_INVALID;
+  return st_check(L->s);
+}
+
+extern "C" int32_t shz_listeners_reset(shz_listeners* L, const uint32_t* which, uint32_t n) {
+  SHZ_TRY(ls_check(L));
+  if (n && !which) SHZ_FAIL(L->ctx, SHZ_E_INVALID, "which is NULL");
+  for (uint32_t i = 0; i < n; ++i)
+    if (which[i] >= L->n) SHZ_FAIL(L->ctx, SHZ_E_INVALID, "listener %u out of range (%u listeners)", which[i], L->n);
+  std::vector<uint32_t> streams;
+  for (uint32_t i = 0; i < n; ++i)
+    for (uint32_t c = 0; c < L->channels; ++c) streams.push_back(which[i] * L->channels + c);
+  SHZ_TRY(shz_streams_reset(L->s, streams.data(), (uint32_t)streams.size()));
+  for (uint32_t i = 0; i < n; ++i) L->w_n[which[i]] = L->w0[which[i]] = 0;
+  return SHZ_OK;
+}
+
+extern "C" int32_t shz_listeners_state(shz_listeners* L, uint32_t l, uint64_t* window_hashes, uint64_t* w0) {
+  SHZ_TRY(ls_check(L));
+  if (l >= L->n) SHZ_FAIL(L->ctx, SHZ_E_INVALID, "listener %u out of range (%u listeners)", l, L->n);
+  if (window_hashes) *window_hashes = L->w_n[l];
+  if (w0) *w0 = L->w0[l];
+  return SHZ_OK;
+}
+
+extern "C" int32_t shz_listener_window(const uint64_t* settled, uint32_t channels, uint32_t window_frames, uint64_t* horizon,
+                                       uint64_t* w0) {
+  if (!settled || channels == 0) return SHZ_E_INVALID;
+  uint64_t h = settled[0];
+  for (uint32_t c = 1; c < channels; ++c) h = std::min(h, settled[c]);
+  if (horizon) *horizon = h;
+  if (w0) *w0 = h > window_frames ? h - window_frames : 0;
+  return SHZ_OK;
+}
+
+extern "C" int32_t shz_listeners_push(shz_listeners* L, const int16_t* pcm, const uint64_t* chunk_off, const uint32_t* end,
+                                      uint32_t topn, uint32_t flags, uint32_t* out_sid, int32_t* out_delta, uint32_t* out_aligned,
+                                      uint32_t* out_dedup, uint32_t* out_nres, uint32_t* out_nhash, uint64_t* out_npairs,
+                                      uint32_t* out_w0) {
+  SHZ_TRY(ls_check(L));
+  shz_ctx* ctx = L->ctx;
+  shz_streams* s = L->s;
+  const uint32_t n = L->n, ch = L->channels;
+  // what the match would refuse is refused here, before any stream advances
+  if (flags & ~(SHZ_PCM_DEVICE | SHZ_MATCH_FULL_SORT)) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_listeners_push: flags may hold SHZ_PCM_DEVICE and SHZ_MATCH_FULL_SORT");
+  if (!out_sid || !out_delta || !out_aligned || !out_dedup || !out_nres) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_listeners_push: NULL buffer");
+  SHZ_TRY(shz_match_ready(ctx, L->t, topn));
+  SHZ_HIP(ctx, hipSetDevice(ctx->device));
+  // 1) the streams' push, hashes to the object's own device buffers; its SHZ_E_CAPACITY changes no stream and names the room
+  std::vector<uint64_t> hash_off((size_t)s->n + 1, 0);
+  uint64_t count = 0;
+  void *d_nk, *d_nt;
+  if (L->new_cap == 0) L->new_cap = (uint64_t)s->n * 256 + 4096;
+  for (int attempt = 0;; ++attempt) {
+    SHZ_TRY(st_reserve(ctx, L->nk, L->new_cap * 4 + 64, &d_nk));
+    SHZ_TRY(st_reserve(ctx, L->nt, L->new_cap * 4 + 64, &d_nt));
+    const int32_t rc = shz_streams_push(s, pcm, chunk_off, end, (flags & SHZ_PCM_DEVICE) | SHZ_OUT_DEVICE, (uint32_t*)d_nk,
+                                        (uint32_t*)d_nt, hash_off.data(), L->new_cap, &count);
+    if (rc == SHZ_E_CAPACITY && attempt < 2 && count > L->new_cap) {
+      L->new_cap = count + count / 4;
+      continue;
+    }
+    SHZ_TRY(rc);
+    break;
+  }
+  // 2) w0 of every listener from the horizons, where its entries are, and a bound of what the windows can hold
+  void* mailp;
+  const uint64_t jb = ((uint64_t)n * sizeof(ls_job) + 255) & ~255ull, rb = 64 + (uint64_t)n * 8;
+  SHZ_TRY(shz_mailbox(ctx, jb + rb, &mailp));
+  ls_job* hj = (ls_job*)mailp;
+  uint64_t bound = 0, bias = 0;
+  std::vector<uint32_t> w0_new(n);
+  for (uint32_t l = 0; l < n; ++l) {
+    uint64_t h, w0, top = 0;
+    SHZ_TRY(shz_listener_window(s->settled.data() + (size_t)l * ch, ch, L->window_frames, &h, &w0));
+    for (uint32_t c = 0; c < ch; ++c) top = std::max(top, s->settled[(size_t)l * ch + c]);
+    const uint64_t a = hash_off[(size_t)l * ch], b = hash_off[(size_t)(l + 1) * ch];
+    hj[l] = ls_job{L->w_at[l], a, L->w_n[l], (uint32_t)(b - a), (uint32_t)w0, 0u};
+    w0_new[l] = (uint32_t)w0;
+    bound += (uint64_t)L->w_n[l] + (b - a);
+    if ((uint64_t)L->w_n[l] + (b - a) >= (1ull << 31)) SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "listener %u: 2^31 hashes in its window", l);
+    // every t1 of a channel is below that channel's horizon: the largest query offset of the push is below this
+    if (top > w0) bias = std::max(bias, top - w0 - 1);
+  }
+  const uint32_t out = L->cur ^ 1u;
+  void *d_wk, *d_wt, *d_qo, *d_jobs, *d_ctl;
+  SHZ_TRY(st_reserve(ctx, L->wk[out], bound * 4 + 64, &d_wk));
+  SHZ_TRY(st_reserve(ctx, L->wt[out], bound * 4 + 64, &d_wt));
+  SHZ_TRY(st_reserve(ctx, L->qo, bound * 4 + 64, &d_qo));
+  SHZ_TRY(st_reserve(ctx, L->jobs, jb, &d_jobs));
+  SHZ_TRY(st_reserve(ctx, L->ctl, 64 + (uint64_t)n * 16, &d_ctl));
+  const uint32_t *d_wk_in = (const uint32_t*)L->wk[L->cur].p, *d_wt_in = (const uint32_t*)L->wt[L->cur].p;
+  unsigned long long* d_total = (unsigned long long*)d_ctl;
+  uint64_t *d_cnt = (uint64_t*)((char*)d_ctl + 64), *d_offs = d_cnt + n;
+  SHZ_HIP(ctx, hipMemcpyAsync(d_jobs, hj, (uint64_t)n * sizeof(ls_job), hipMemcpyHostToDevice, ctx->stream));
+  // 3) count, scan over the listeners, compact into the other slot
+  hipLaunchKernelGGL(listener_count_kernel, dim3(n), dim3(LS_THREADS), 0, ctx->stream, (const ls_job*)d_jobs, d_wt_in,
+                     (const uint32_t*)d_nt, d_cnt);
+  SHZ_HIP(ctx, hipGetLastError());
+  SHZ_TRY(shz_scan_u64(ctx, d_cnt, d_offs, n, (uint64_t*)d_total));
+  hipLaunchKernelGGL(listener_write_kernel, dim3(n), dim3(LS_THREADS), 0, ctx->stream, (const ls_job*)d_jobs, d_wk_in, d_wt_in,
+                     (const uint32_t*)d_nk, (const uint32_t*)d_nt, (const uint64_t*)d_offs, (const unsigned long long*)d_total, bound,
+                     (uint32_t*)d_wk, (uint32_t*)d_wt, (uint32_t*)d_qo);
+  SHZ_HIP(ctx, hipGetLastError());
+  // 4) one read-back: the counts are the match's query_off
+  char* hr = (char*)mailp + jb;
+  SHZ_HIP(ctx, hipMemcpyAsync(hr, d_ctl, rb, hipMemcpyDeviceToHost, ctx->stream));
+  SHZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  const uint64_t total = *(const uint64_t*)hr;
+  const uint64_t* hc = (const uint64_t*)(hr + 64);
+  if (total > bound) SHZ_FAIL(ctx, SHZ_E_STATE, "listeners: %llu window entries exceed their bound %llu", (unsigned long long)total, (unsigned long long)bound);
+  std::vector<uint64_t> query_off((size_t)n + 1, 0);
+  for (uint32_t l = 0; l < n; ++l) query_off[l + 1] = query_off[l] + hc[l];
+  // the windows advance: the streams have
+  L->cur = out;
+  for (uint32_t l = 0; l < n; ++l) {
+    L->w_at[l] = query_off[l];
+    L->w_n[l] = (uint32_t)hc[l];
+    L->w0[l] = w0_new[l];
+    if (out_w0) out_w0[l] = w0_new[l];
+  }
+  // 5) all listeners in one match, on the columns where they are (a listener without hashes: nres = 0)
+  return shz_match_device(ctx, L->t, (const uint32_t*)d_wk, (const uint32_t*)d_qo, query_off.data(), n, topn,
+                          flags & SHZ_MATCH_FULL_SORT, (int64_t)bias, out_sid, out_delta, out_aligned, out_dedup, out_nres, out_nhash,
+                          out_npairs);
 }

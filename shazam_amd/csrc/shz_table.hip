@@ -2251,6 +2251,10 @@ struct match_call {
   const uint64_t* d_qoff_all;   // query_off[0 .. n_queries] on the device, when it went with the packed upload
   mctl* d_ctl_packed;           // ... and a zeroed control block for the first sub-batch
   uint64_t sub_budget;          // votes of one sub-batch
+  // device input handed over inside the library (shz_match_device: the fused recognise call, the listeners)
+  bool has_bias_bound;          // the caller knows a bound of the query offsets without looking at them ...
+  uint32_t bias_bound;          // ... every q_off <= bias_bound: the queued fold may take it for its bias
+  bool pack_small;              // segment descriptors | query offsets | control block travel as one pinned copy
 };
 enum sub_next {
   SUB_GO,          // on to the next stage
@@ -2301,18 +2305,18 @@ static int32_t match_upload(match_call& mc) {
   mc.d_ctl_packed = nullptr;
   const uint64_t seg_bytes = (sizeof(shz_seg_dev) * (uint64_t)nseg + 255) & ~255ull;
   const uint64_t qoff_bytes = (((uint64_t)mc.n_queries + 1) * 8 + 255) & ~255ull;
-  const uint64_t col_bytes = (h1 * 4 + 255) & ~255ull;
+  const uint64_t col_bytes = host_in ? (h1 * 4 + 255) & ~255ull : 0;   // (device input: the columns stay where they are)
   const uint64_t pk_bytes = seg_bytes + qoff_bytes + col_bytes * 2 + 256;
   void* d_segs;
-  if (host_in && pk_bytes <= (4ull << 20)) {
+  if ((host_in || mc.pack_small) && pk_bytes <= (4ull << 20)) {
     void *hm, *dm;
     SHZ_TRY(shz_mailbox(ctx, pk_bytes, &hm));
-    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_KEY, pk_bytes, &dm));
+    SHZ_TRY(shz_ws_reserve(ctx, host_in ? SHZ_WS_KEY : SHZ_WS_META, pk_bytes, &dm));
     char* hp = (char*)hm;
     memcpy(hp, hsegs.data(), sizeof(shz_seg_dev) * nseg);
     memcpy(hp + seg_bytes, mc.query_off, ((uint64_t)mc.n_queries + 1) * 8);
     const uint64_t ko = seg_bytes + qoff_bytes, oo = ko + col_bytes;
-    if (h1) {
+    if (h1 && host_in) {
       memcpy(hp + ko, mc.key32, h1 * 4);
       memcpy(hp + oo, mc.q_off, h1 * 4);
     }
@@ -2320,8 +2324,10 @@ static int32_t match_upload(match_call& mc) {
     SHZ_HIP(ctx, hipMemcpyAsync(dm, hm, pk_bytes, hipMemcpyHostToDevice, ctx->stream));
     d_segs = dm;
     mc.d_qoff_all = (const uint64_t*)((char*)dm + seg_bytes);
-    mc.d_key = (const uint32_t*)((char*)dm + ko);
-    mc.d_qo = (const uint32_t*)((char*)dm + oo);
+    if (host_in) {
+      mc.d_key = (const uint32_t*)((char*)dm + ko);
+      mc.d_qo = (const uint32_t*)((char*)dm + oo);
+    }
     mc.d_ctl_packed = (mctl*)((char*)dm + pk_bytes - 256);
   } else {
     SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_META, sizeof(shz_seg_dev) * SHZ_MAX_SEGS, &d_segs));
@@ -2454,7 +2460,9 @@ static int32_t sub_head(match_call& mc, match_sub& s, sub_next* next) {
 // ONE small query from host memory: its votes are queued now, before their number is known (m_spec_plan_kernel puts the
 // range's end where the one-workgroup fold reads it, and voids the fold where the votes exceed VT_ONE_WG_MAX), under the
 // conditions of ROUTE_ONE_WG.  What differs from that route is what the host cannot know yet: the vote count (the table's
-// last match stands in for it), and the bias, which it has to take from the query itself -- so host input only.
+// last match stands in for it), and the bias, which it has to take from the query itself -- so host input, or device
+// input whose caller hands a bound of the offsets over (match_call::bias_bound: any bias >= the largest offset is a valid
+// layout, include/shz.h at shz_match_pairs).
 static int32_t sub_queue_fold(const match_call& mc, match_sub& s) {
   shz_ctx* ctx = mc.ctx;
   const vote_switches& sw = vote_env();
@@ -2462,14 +2470,20 @@ static int32_t sub_queue_fold(const match_call& mc, match_sub& s) {
   s.queued_bias = 0;
   // (vote32 == 1 would send P > MH_MAX votes through a 4-byte pass instead; the layout test with the bias still 0 is the
   // least it can need: it saves the walk over the offsets)
-  if (mc.sink || (mc.flags & SHZ_IN_DEVICE) || s.m > MH_MAX || sw.vote32 == 1 ||
+  const bool dev_in = (mc.flags & SHZ_IN_DEVICE) != 0;
+  if (mc.sink || (dev_in && !mc.has_bias_bound) || s.m > MH_MAX || sw.vote32 == 1 ||
       !one_wg_fits(s.nq, s.mb, mc.topn, s.full_sort, sw) ||
       (double)s.m * mc.t->votes_per_hash > 2.0 * VT_ONE_WG_MAX)   // (a table whose last query had far more votes: not worth queueing)
     return SHZ_OK;
   bool wide = false;
-  for (uint64_t i = mc.query_off[s.q0]; i < mc.query_off[s.q0 + 1]; ++i) {
-    s.queued_bias = std::max(s.queued_bias, mc.q_off[i]);
-    wide |= mc.q_off[i] >= (1u << QOFF_BITS);
+  if (dev_in) {
+    s.queued_bias = mc.bias_bound;
+    wide = mc.bias_bound >= (1u << QOFF_BITS);
+  } else {
+    for (uint64_t i = mc.query_off[s.q0]; i < mc.query_off[s.q0 + 1]; ++i) {
+      s.queued_bias = std::max(s.queued_bias, mc.q_off[i]);
+      wide |= mc.q_off[i] >= (1u << QOFF_BITS);
+    }
   }
   m_bits ms = s.mb;
   ms.qb = 0;
@@ -2732,10 +2746,11 @@ static int32_t match_sub_run(match_call& mc, match_sub& s, sub_next* next) {
   SHZ_TRY(sub_queue_fold(mc, s));
   SHZ_TRY(sub_read_counts(mc, s, next));
   if (*next != SUB_GO) return SHZ_OK;
-  // the queued small query ran when its votes fit and the bias was the query's own (else its kernels did nothing, or
-  // their results are overwritten, and the passes run as ever)
+  // the queued small query ran when its votes fit and the bias was the query's own -- or, for device input, the caller's
+  // bound and no offset above it (else its kernels did nothing, or their results are overwritten, and the passes run as ever)
+  const bool bias_held = (mc.flags & SHZ_IN_DEVICE) ? s.mb.bias <= s.queued_bias : s.mb.bias == s.queued_bias;
   vote_case c{s.nq, s.P, s.votes.data(), s.mb, mc.topn, s.full_sort, mc.sink != nullptr,
-              s.queued && s.P <= VT_ONE_WG_MAX && s.mb.bias == s.queued_bias, vote_env()};
+              s.queued && s.P <= VT_ONE_WG_MAX && bias_held, vote_env()};
   vote_plan plan;
   vote_plan_make(c, &plan);
   SHZ_TRY(sub_vote(mc, s, plan));
@@ -2799,6 +2814,31 @@ extern "C" int32_t shz_match_batch(shz_ctx* ctx, shz_table* t, const uint32_t* k
   match_call mc{ctx, t, key32, q_off, query_off, n_queries, topn, flags, out_sid, out_delta, out_aligned, out_dedup,
                 out_nres, out_nhash, out_npairs, nullptr};
   return match_core(mc);
+}
+
+// match_core on query columns that are already on the device and belong to the library (the fused recognise call, the
+// listeners): query_off is the host's; bias_bound >= every q_off, or < 0 where the caller knows none
+int32_t shz_match_device(shz_ctx* ctx, shz_table* t, const uint32_t* d_key32, const uint32_t* d_q_off, const uint64_t* query_off,
+                         uint32_t n_queries, uint32_t topn, uint32_t flags, int64_t bias_bound, uint32_t* out_sid,
+                         int32_t* out_delta, uint32_t* out_aligned, uint32_t* out_dedup, uint32_t* out_nres, uint32_t* out_nhash,
+                         uint64_t* out_npairs) {
+  match_call mc{ctx, t, d_key32, d_q_off, query_off, n_queries, topn, (flags & SHZ_MATCH_FULL_SORT) | SHZ_IN_DEVICE, out_sid,
+                out_delta, out_aligned, out_dedup, out_nres, out_nhash, out_npairs, nullptr};
+  mc.has_bias_bound = bias_bound >= 0 && bias_bound < (int64_t)1 << 32;
+  mc.bias_bound = mc.has_bias_bound ? (uint32_t)bias_bound : 0u;
+  mc.pack_small = true;
+  return match_core(mc);
+}
+
+// what match_core refuses before it launches anything, for callers that must know before they change state of their own
+int32_t shz_match_ready(shz_ctx* ctx, shz_table* t, uint32_t topn) {
+  if (!ctx || !t) return SHZ_E_INVALID;
+  if (t->ctx != ctx) SHZ_FAIL(ctx, SHZ_E_INVALID, "table belongs to another ctx");
+  if (topn < 1 || topn > 64) SHZ_FAIL(ctx, SHZ_E_INVALID, "topn must be in [1,64]");
+  if (pending_rows(t) || (!t->bucket && t->done.empty())) SHZ_FAIL(ctx, SHZ_E_STATE, "table not finalized");
+  if (t->max_off >= (1u << 31))
+    SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "match: the table holds offset %u; offsets must be < 2^31", t->max_off);
+  return SHZ_OK;
 }
 
 extern "C" int32_t shz_table_maxima(shz_table* t, uint32_t* max_sid, uint32_t* max_off) {

@@ -88,15 +88,21 @@ class StreamRecognizer:
     dicts of align_matches over the settled hashes with t1 >= w0 = max(0, H - window_frames), query offsets t1 - w0, for
     all listeners in ONE batched match -- `offset` means what it means for a clip recorded from frame w0.  H is the
     smallest settled horizon of the listener's channels; window_frames = int(window_seconds * 44100 / hop).  Listeners
-    with no hashes in the window get []."""
+    with no hashes in the window get [].  device=True keeps the windows on the GPU (shz_listeners_*): one library call per
+    push, no hash crosses the bus, same return value."""
 
     def __init__(self, db, n_listeners: int, channels: int = 1, window_seconds: float = 5, topn: int = TOPN,
-                 fan_value: int = 5, amp_min=10):
+                 fan_value: int = 5, amp_min=10, device: bool = False):
         self.db, self.n, self.channels, self.topn = db, int(n_listeners), int(channels), int(topn)
         self.fp = StreamFingerprinter(self.n * self.channels, RATE, fan_value, amp_min, db.ctx)
         self.window_frames = int(float(window_seconds) * RATE / self.fp.streams.hop)
         self._k = [np.zeros(0, np.uint32) for _ in range(self.n)]
         self._t = [np.zeros(0, np.uint32) for _ in range(self.n)]
+        self.listeners = None
+        if device:
+            if not hasattr(db.table, "h"):
+                raise NotImplementedError("device-resident listeners take the unsharded table (shards=1)")
+            self.listeners = _ffi.Listeners(self.fp.streams, db.table, self.n, self.window_frames)
 
     def _flat(self, per_listener):
         out = []
@@ -119,6 +125,8 @@ class StreamRecognizer:
         assert len(chunks_per_listener) == self.n
         ends = None if end is None else [l * self.channels + j for l in (range(self.n) if end is True else end)
                                          for j in range(self.channels)]
+        if self.listeners is not None:
+            return self._push_device(self._flat(chunks_per_listener), ends)
         k, t1, ho = self.fp.push(self._flat(chunks_per_listener), ends)
         keys, qoffs, qoff, w0s = [], [], [0], []
         for l in range(self.n):
@@ -145,12 +153,30 @@ class StreamRecognizer:
                 results[l] = _result_dicts(self.db, res, q, int(res["nhash"][q]))
         return list(zip(results, w0s))
 
+    def _push_device(self, chunks, ends):
+        from . import _result_dicts
+        self.db.finalize()
+        res, w0 = self.listeners.push([None if c is None else _as_pcm(c) for c in chunks], ends, self.topn)
+        nhash = res["nhash"].tolist()
+        return [(_result_dicts(self.db, res, l, nhash[l]) if nhash[l] else [], int(w0[l])) for l in range(self.n)]
+
+    def window_hashes(self, listener: int) -> int:
+        """Hashes in the listener's window after the last push."""
+        if self.listeners is not None:
+            return self.listeners.state(listener)["window_hashes"]
+        return len(self._k[listener])
+
     def reset(self, listeners=None):
-        ls = range(self.n) if listeners is None else listeners
+        ls = range(self.n) if listeners is None else list(listeners)
+        if self.listeners is not None:
+            self.listeners.reset(ls)
+            return
         self.fp.reset([l * self.channels + j for l in ls for j in range(self.channels)])
         for l in ls:
             self._k[l] = np.zeros(0, np.uint32)
             self._t[l] = np.zeros(0, np.uint32)
 
     def close(self):
+        if self.listeners is not None:
+            self.listeners.close()
         self.fp.close()
