@@ -81,7 +81,7 @@ int32_t shz_release_workspace(shz_ctx* ctx, uint64_t* freed_bytes);
 int32_t shz_timer_start(shz_ctx* ctx, int32_t slot);
 int32_t shz_timer_stop(shz_ctx* ctx, int32_t slot, float* elapsed_ms);
 /* per-kernel accumulated device time of the last profiled call (see shz_set_profiling).
- * which: 0 stft_psd, 1 peak_pick, 2 peak_expand(+scan), 3 pair_hash(+scan) */
+ * which: 0 stft_psd, 1 peak_pick, 2 peak_expand(+scan), 3 pair_hash(+scan), 4 peak_verify, 5 resample */
 int32_t shz_set_profiling(shz_ctx* ctx, int32_t enabled);
 int32_t shz_get_kernel_ms(shz_ctx* ctx, int32_t which, float* total_ms, uint32_t* launches);
 
@@ -528,6 +528,28 @@ int32_t shz_listeners_state(shz_listeners* L, uint32_t l, uint64_t* window_hashe
 /* No GPU, no ctx (like shz_stream_plan): the window of a listener whose channels have settled[0 .. channels) frames:
  * *horizon = their minimum H, *w0 = max(0, H - window_frames). */
 int32_t shz_listener_window(const uint64_t* settled, uint32_t channels, uint32_t window_frames, uint64_t* horizon, uint64_t* w0);
+
+/* ---- resampling (new; the reference hands a file's frame_rate through and fixes the microphone at 44.1 kHz,
+ * __init__.py:70-113, recognizer.py:21-27, so audio at another rate never meets the table) ---------------------------
+ * Rational resampling fs_in -> fs_out of a batch of clips by an integer polyphase filter: g = gcd(fs_in, fs_out),
+ * L = fs_out / g, M = fs_in / g, taps[L][T] int32 in Q30 (HOST, row p = phase p).  With x the clip (zero outside it),
+ * p = (m M) mod L and i0 = (m M) div L + T / 2:
+ *     out[m] = sat16((sum_{k < T} taps[p][k] * x[i0 - k] + 2^29) >> 30)      (arithmetic shift, sum exact in 64 bits)
+ * clips as for shz_fingerprint_batch (pcm host, or device with SHZ_PCM_DEVICE; clip_off: n_clips + 1 sample offsets, HOST);
+ * clips never read each other's samples.  Per clip and optional (NULL: 0, and every output m in [0, ceil(n L / M))):
+ * in_base[c] = absolute index of the clip buffer's first sample -- x[i] is buffer[i - in_base] inside the buffer and 0
+ * elsewhere -- and the outputs wanted, m in [m_first[c], m_end[c]) (both or neither): a chunk of a stream with the tail of
+ * the chunk before in front of it gives the samples the whole stream gives.  out: int16 (host, or device with
+ * SHZ_OUT_DEVICE), clip c's at [out_off[c], out_off[c + 1]) (out_off: HOST); cap in samples, SHZ_E_CAPACITY with *count =
+ * required.  SHZ_E_INVALID before anything is launched: L, M or T of 0, odd T, T > SHZ_RESAMPLE_MAX_TAPS, a clip_off that
+ * decreases, m_end < m_first.  SHZ_E_UNSUPPORTED: L or M above SHZ_RESAMPLE_MAX_RATIO, L * T above SHZ_RESAMPLE_MAX_TABLE.
+ * shz_get_kernel_ms(which = 5) accumulates the kernel's time. */
+#define SHZ_RESAMPLE_MAX_TAPS 4096u
+#define SHZ_RESAMPLE_MAX_RATIO (1u << 24)
+#define SHZ_RESAMPLE_MAX_TABLE (1u << 24)
+int32_t shz_resample_i16(shz_ctx* ctx, const int16_t* pcm, const uint64_t* clip_off, uint32_t n_clips, uint32_t L, uint32_t M,
+                         uint32_t T, const int32_t* taps, const uint64_t* in_base, const uint64_t* m_first, const uint64_t* m_end,
+                         uint32_t flags, int16_t* out, uint64_t* out_off, uint64_t cap, uint64_t* count);
 
 #ifdef __cplusplus
 }

@@ -156,10 +156,18 @@ def _check_window(wsize, wratio) -> int:
 
 
 def fingerprint_batch(clips, Fs: int = RATE, fan_value: int = DEFAULT_FAN_VALUE, amp_min=DEFAULT_AMP_MIN, ctx: Context = None,
-                      wratio: float = DEFAULT_OVERLAP_RATIO):
+                      wratio: float = DEFAULT_OVERLAP_RATIO, resample_to: int = None):
     """Batched fingerprint(): clips = list of 1-D int16 arrays (or a 2-D array).
-    Returns (key32, t1, hash_off): hashes of clip c are [hash_off[c], hash_off[c+1])."""
+    Returns (key32, t1, hash_off): hashes of clip c are [hash_off[c], hash_off[c+1]).
+    resample_to: the clips are at Fs and the table at resample_to -- they are resampled on the device (shz_resample_i16) and
+    fingerprinted there at Fs = resample_to; the resampled PCM never visits the host."""
     ctx = ctx or get_context()
+    if resample_to is not None and int(resample_to) != int(Fs):
+        buf, off = resample_to_device(clips, int(Fs), int(resample_to), ctx)
+        try:
+            return _fingerprint_device(buf, off, int(resample_to), fan_value, amp_min, ctx, wratio)
+        finally:
+            buf.free()
     noverlap = _check_window(DEFAULT_WINDOW_SIZE, wratio)
     if NFFT - noverlap != getattr(ctx, "hop", HOP):
         ctx.set_overlap(noverlap)
@@ -178,12 +186,32 @@ def fingerprint_batch(clips, Fs: int = RATE, fan_value: int = DEFAULT_FAN_VALUE,
     return k, t1, ho
 
 
+def _fingerprint_device(buf, off, Fs, fan_value, amp_min, ctx, wratio):
+    """fingerprint_batch of device-resident clips (buf: DevBuf of int16, off: sample offsets)."""
+    noverlap = _check_window(DEFAULT_WINDOW_SIZE, wratio)
+    other_hop = NFFT - noverlap != getattr(ctx, "hop", HOP)
+    if other_hop:
+        ctx.set_overlap(noverlap)
+    try:
+        k, t1, ho, _ = ctx.fingerprint_batch(buf, off, fs=int(Fs), amp_min=float(amp_min), fan_value=int(fan_value), pcm_device=True)
+        return k, t1, ho
+    finally:
+        if other_hop:
+            ctx.set_overlap(NFFT - HOP)
+
+
 def fingerprint(channel_samples, Fs: int = RATE, wsize: int = DEFAULT_WINDOW_SIZE, wratio: float = DEFAULT_OVERLAP_RATIO,
-                fan_value: int = DEFAULT_FAN_VALUE, amp_min: int = DEFAULT_AMP_MIN):
+                fan_value: int = DEFAULT_FAN_VALUE, amp_min: int = DEFAULT_AMP_MIN, resample_to: int = None):
     """__init__.py:212-245: FFT the channel, log transform, local maxima, pair hashes.
-    Returns list[(hex20, t1)] in the reference's generation order."""
+    Returns list[(hex20, t1)] in the reference's generation order.  resample_to: see fingerprint_batch; it goes with the
+    window size 4096 only (NotImplementedError otherwise: resample_batch first, then fingerprint(wsize=...))."""
     noverlap = _check_window(wsize, wratio)
     ctx = get_context()
+    if resample_to is not None and int(resample_to) != int(Fs):
+        if int(wsize) != DEFAULT_WINDOW_SIZE:
+            raise NotImplementedError("resample_to goes with the window size 4096")
+        k, t1, _ = fingerprint_batch([channel_samples], Fs, fan_value, amp_min, ctx, wratio, resample_to)
+        return list(zip(hex_of_keys(ctx, k), t1.tolist()))
     if int(wsize) != DEFAULT_WINDOW_SIZE:
         # another window size: the reference's own composition (__init__.py:232-245) of GPU stages -- generic spectrogram,
         # get_2D_peaks on the dB array, generate_hashes on the peaks
@@ -240,7 +268,7 @@ def _result_dicts(db, res, q, queried_hashes):
     return out
 
 
-def _recognize_fused(queries, chans, owner, db, Fs, topn):
+def _recognize_fused(queries, chans, owner, db, Fs, topn, resample_to=None):
     """recognize_batch through shz_recognize_batch: one call, the hashes never leave the device."""
     if not hasattr(db.table, "h"):
         raise NotImplementedError("fused recognition takes the unsharded table (shards=1)")
@@ -248,15 +276,24 @@ def _recognize_fused(queries, chans, owner, db, Fs, topn):
     if getattr(ctx, "hop", HOP) != HOP:
         ctx.set_overlap(NFFT - HOP)
     db.finalize()
-    arrs = [_as_pcm(c) for c in chans]
-    off = np.zeros(len(arrs) + 1, np.uint64)
-    if arrs:
-        off[1:] = np.cumsum([len(a) for a in arrs])
-    pcm = np.concatenate(arrs) if off[-1] else np.zeros(1, np.int16)
     nq = len(queries)
     first = np.searchsorted(np.asarray(owner, np.int64), np.arange(nq + 1)).astype(np.uint32)
-    res, ms_extract, ms_match = ctx.recognize_batch(db.table, pcm, off, first, fs=int(Fs), amp_min=float(DEFAULT_AMP_MIN),
-                                                    fan_value=DEFAULT_FAN_VALUE, topn=int(topn))
+    if resample_to is not None and int(resample_to) != int(Fs):   # resampled on the device and handed on there
+        buf, off = resample_to_device(chans, int(Fs), int(resample_to), ctx)
+        try:
+            res, ms_extract, ms_match = ctx.recognize_batch(db.table, buf, off, first, fs=int(resample_to),
+                                                            amp_min=float(DEFAULT_AMP_MIN), fan_value=DEFAULT_FAN_VALUE,
+                                                            topn=int(topn), pcm_device=True)
+        finally:
+            buf.free()
+    else:
+        arrs = [_as_pcm(c) for c in chans]
+        off = np.zeros(len(arrs) + 1, np.uint64)
+        if arrs:
+            off[1:] = np.cumsum([len(a) for a in arrs])
+        pcm = np.concatenate(arrs) if off[-1] else np.zeros(1, np.int16)
+        res, ms_extract, ms_match = ctx.recognize_batch(db.table, pcm, off, first, fs=int(Fs), amp_min=float(DEFAULT_AMP_MIN),
+                                                        fan_value=DEFAULT_FAN_VALUE, topn=int(topn))
     t0 = time()
     results = [_result_dicts(db, res, q, int(res["nhash"][q])) for q in range(nq)]
     align_time = time() - t0
@@ -264,11 +301,12 @@ def _recognize_fused(queries, chans, owner, db, Fs, topn):
                      "n_matches": res["npairs"], "n_hashes": res["nhash"]}
 
 
-def recognize_batch(queries, db, Fs: int = RATE, topn: int = TOPN, fused: bool = False):
+def recognize_batch(queries, db, Fs: int = RATE, topn: int = TOPN, fused: bool = False, resample_to: int = None):
     """Recognise flow (recognizer.py:377-392) for many queries at once.  Each query is a list of
     channels (1-D int16 arrays) or a single 1-D array.  Returns (results_per_query, timings).
     fused: fingerprint and match in ONE library call with the hashes staying on the device (shz_recognize_batch);
-    same results, fingerprint_time / query_time are then the device times of the two halves."""
+    same results, fingerprint_time / query_time are then the device times of the two halves.
+    resample_to: the queries are at Fs, the table at resample_to (see fingerprint_batch); either path."""
     ctx = db.ctx
     chans, owner = [], []
     for qi, q in enumerate(queries):
@@ -276,9 +314,9 @@ def recognize_batch(queries, db, Fs: int = RATE, topn: int = TOPN, fused: bool =
         chans.extend(cs)
         owner.extend([qi] * len(cs))
     if fused:
-        return _recognize_fused(queries, chans, owner, db, Fs, topn)
+        return _recognize_fused(queries, chans, owner, db, Fs, topn, resample_to)
     t0 = time()
-    k, t1, ho = fingerprint_batch(chans, Fs, ctx=ctx)
+    k, t1, ho = fingerprint_batch(chans, Fs, ctx=ctx, resample_to=resample_to)
     fingerprint_time = time() - t0
     # channels of one query are adjacent, so the per-query CSR is a sub-sampling of hash_off
     owner = np.asarray(owner, np.int64)
@@ -295,15 +333,17 @@ def recognize_batch(queries, db, Fs: int = RATE, topn: int = TOPN, fused: bool =
                      "n_matches": res["npairs"], "n_hashes": res["nhash"]}
 
 
-def recognize(channels_or_samples, db=None, Fs: int = RATE, topn: int = TOPN, fused: bool = False):
-    """recognizer.py:377-396: (final_results, fingerprint_time, query_time, align_time).  fused: see recognize_batch."""
+def recognize(channels_or_samples, db=None, Fs: int = RATE, topn: int = TOPN, fused: bool = False, resample_to: int = None):
+    """recognizer.py:377-396: (final_results, fingerprint_time, query_time, align_time).  fused, resample_to: see recognize_batch."""
     if db is None:
         raise ValueError("recognize() needs the HipFingerprintDB holding the fingerprints")
     x = channels_or_samples
     q = [np.asarray(x)] if (not isinstance(x, (list, tuple)) or (len(x) and np.isscalar(x[0]))) else list(x)
-    results, tm = recognize_batch([q], db, Fs, topn, fused)
+    results, tm = recognize_batch([q], db, Fs, topn, fused, resample_to)
     return results[0], tm["fingerprint_time"], tm["query_time"], tm["align_time"]
 
 
 # live streams (recognizer.py:21-25, 357-392): incremental fingerprints and recognition of chunked input
 from .stream import StreamFingerprinter, StreamRecognizer, fingerprint_stream  # noqa: E402,F401
+# sample-rate conversion (csrc/shz_resample.hip): audio at any rate against a table at another
+from .resample import StreamResampler, resample_batch, resample_plan, resample_to_device  # noqa: E402,F401

@@ -133,6 +133,8 @@ SIGNATURES = {
     "shz_listeners_reset": (C.c_int32, [vp, vp, C.c_uint32]),
     "shz_listeners_state": (C.c_int32, [vp, C.c_uint32, u64p, u64p]),
     "shz_listener_window": (C.c_int32, [u64p, C.c_uint32, C.c_uint32, u64p, u64p]),
+    "shz_resample_i16": (C.c_int32, [vp, vp, u64p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.c_uint32,
+                                     vp, u64p, C.c_uint64, u64p]),
 }
 
 
@@ -562,6 +564,51 @@ class Context:
                                              ptr(res["sid"]), ptr(res["delta"]), ptr(res["aligned"]), ptr(res["dedup"]),
                                              ptr(res["nres"]), ptr(res["nhash"]), ptr(res["npairs"]), C.byref(me), C.byref(mm)))
         return res, float(me.value), float(mm.value)
+
+    def resample_raw(self, pcm, clip_off, L, M, T, taps, in_base=None, m_first=None, m_end=None, pcm_device=False,
+                     out: DevBuf = None, cap=None):
+        """One shz_resample_i16 as it is: (rc, out, out_off, count) without retrying.  taps: int32 [L, T] in Q30.  With `out`
+        a DevBuf the samples stay on the device (cap in samples, default its size) and the returned array is None; else
+        a host array of cap samples is filled."""
+        co, nc = self._clip_off(clip_off)
+        tp = np.ascontiguousarray(taps, np.int32)
+        opt = [None if a is None else np.ascontiguousarray(a, np.uint64) for a in (in_base, m_first, m_end)]
+        oo, cnt = np.zeros(nc + 1, np.uint64), C.c_uint64()
+        flags = PCM_DEVICE if pcm_device else 0
+        if out is not None:
+            cap = int(out.nbytes // 2 if cap is None else cap)
+            host = None
+        else:
+            if cap is None:   # room for every output asked for
+                cap = (int(np.sum(opt[2] - opt[1])) if opt[1] is not None and opt[2] is not None else
+                       sum(-(-int(co[i + 1] - co[i]) * int(L) // max(int(M), 1)) for i in range(nc)))
+            host = np.empty(max(int(cap), 1), np.int16)
+        rc = lib().shz_resample_i16(self.h, ptr(pcm), co.ctypes.data_as(u64p), nc, int(L), int(M), int(T), ptr(tp), ptr(opt[0]),
+                                    ptr(opt[1]), ptr(opt[2]), flags | (OUT_DEVICE if out is not None else 0),
+                                    ptr(out if out is not None else host), oo.ctypes.data_as(u64p), int(cap), C.byref(cnt))
+        n = int(cnt.value)
+        return rc, (None if host is None else host[:min(n, int(cap))]), oo, n
+
+    def resample(self, pcm, clip_off, L, M, T, taps, in_base=None, m_first=None, m_end=None, pcm_device=False, device_out=False):
+        """Polyphase resampling of a batch (shz_resample_i16): (samples, out_off), clip c's at [out_off[c], out_off[c + 1]).
+        device_out: samples is a DevBuf the caller frees, and the PCM never visits the host."""
+        co, nc = self._clip_off(clip_off)
+        if m_first is not None:
+            total = int(np.sum(np.asarray(m_end, np.uint64) - np.asarray(m_first, np.uint64)))
+        else:
+            total = sum(-(-int(co[i + 1] - co[i]) * int(L) // int(M)) for i in range(nc))
+        buf = self.alloc(max(total, 1) * 2) if device_out else None
+        rc, out, oo, _ = self.resample_raw(pcm, co, L, M, T, taps, in_base, m_first, m_end, pcm_device, buf, total)
+        if rc != OK and buf is not None:
+            buf.free()
+        self.check(rc)
+        return (buf if device_out else out), oo
+
+    def resample_kernel_ms(self):
+        """(ms, launches) of the resample kernel since set_profiling(True) (shz_get_kernel_ms slot 5)."""
+        ms, k = C.c_float(), C.c_uint32()
+        self.check(lib().shz_get_kernel_ms(self.h, 5, C.byref(ms), C.byref(k)))
+        return ms.value, k.value
 
     def sha1_prefix(self, key32, device=False, n=None) -> np.ndarray:
         if not device:

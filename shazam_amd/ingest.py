@@ -345,12 +345,14 @@ def load_fingerprinted_audio_hashes(db, songhashes_set=None):
 
 
 def fingerprint_directory(path: str, extensions, db, songhashes_set=None, limit: int = None, batch_files: int = 64,
-                          reader=read):
+                          reader=read, target_fs: int = None):
     """Fingerprint every matching file not yet in ``db`` (by file SHA-1) and insert it, with the
     reference's bookkeeping (__init__.py:325-393): per file the fingerprints of all channels are
     united as a set (:254-265), ``insert_song(name, sha1, len(set))`` (:381), ``insert_hashes``,
     ``set_song_fingerprinted``.  Files are decoded on the host and fingerprinted ``batch_files`` at a
-    time in one GPU batch instead of one process-pool task per file.  Returns [(song_id, name, n)]."""
+    time in one GPU batch instead of one process-pool task per file.  Returns [(song_id, name, n)].
+    target_fs: files at other rates are resampled to it on the GPU (shazam_amd.resample), so that one table holds every
+    file at one rate; without it a file's hashes are those of its own rate and meet only queries at that rate."""
     import shazam_amd as S
     songhashes_set = load_fingerprinted_audio_hashes(db, songhashes_set)
     todo = []
@@ -371,13 +373,14 @@ def fingerprint_directory(path: str, extensions, db, songhashes_set=None, limit:
             meta.append((fi, fn, fs, file_hash, len(chans), len(channels)))
             chans.extend(channels)
             rates.append(fs)
-        # one GPU batch per distinct sample rate (Fs only scales the spectrogram; hashes do not depend on it)
+        # one GPU batch per distinct sample rate (Fs only scales the spectrogram: the hashes of a clip do not depend on the
+        # number, but the same music sampled at two rates has different ones -- hence target_fs)
         for fs in sorted(set(rates)):
             sel = [m for m in meta if m[2] == fs]
             flat = [c for m in sel for c in chans[m[4]:m[4] + m[5]]]
             if not flat:
                 continue
-            k, t1, ho = S.fingerprint_batch(flat, Fs=fs, ctx=db.ctx)
+            k, t1, ho = S.fingerprint_batch(flat, Fs=fs, ctx=db.ctx, resample_to=target_fs)
             pos = 0
             for (_fi, fn, _fs, file_hash, _c0, nch) in sel:
                 lo, hi = int(ho[pos]), int(ho[pos + nch])

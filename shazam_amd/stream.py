@@ -28,13 +28,23 @@ class StreamFingerprinter:
     final, stream i's at [hash_off[i], hash_off[i+1]), t1 in frames from the stream's first sample.  The hop is the
     context's at creation (Context.set_overlap before creating for another wratio)."""
 
-    def __init__(self, n_streams: int, Fs: int = RATE, fan_value: int = 5, amp_min=10, ctx=None):
+    def __init__(self, n_streams: int, Fs: int = RATE, fan_value: int = 5, amp_min=10, ctx=None, fs_in: int = None):
         self.ctx = _ctx(ctx)
         self.n_streams = int(n_streams)
         self.streams = _ffi.Streams(self.ctx, self.n_streams, int(Fs), float(amp_min), int(fan_value))
+        self.resampler = None   # fs_in: the chunks arrive at fs_in and are resampled to Fs in front of push
+        if fs_in is not None and int(fs_in) != int(Fs):
+            from .resample import StreamResampler
+            self.resampler = StreamResampler(self.n_streams, int(fs_in), int(Fs), self.ctx)
+
+    def _pcm(self, chunks, end):
+        """The chunks as the streams take them: int16, at the streams' rate."""
+        if self.resampler is not None:
+            return self.resampler.push(chunks, end)
+        return [None if c is None else _as_pcm(c) for c in chunks]
 
     def push(self, chunks, end=None):
-        return self.streams.push([None if c is None else _as_pcm(c) for c in chunks], end)
+        return self.streams.push(self._pcm(chunks, end), end)
 
     def push_hex(self, chunks, end=None):
         """push() with the reference's return type: per stream list[(hex20, t1)]."""
@@ -46,6 +56,8 @@ class StreamFingerprinter:
 
     def reset(self, which=None):
         self.streams.reset(which)
+        if self.resampler is not None:
+            self.resampler.reset(which)
 
     def state(self, i: int) -> dict:
         """samples received, settled frames, peaks pending, hashes emitted so far."""
@@ -89,12 +101,13 @@ class StreamRecognizer:
     all listeners in ONE batched match -- `offset` means what it means for a clip recorded from frame w0.  H is the
     smallest settled horizon of the listener's channels; window_frames = int(window_seconds * 44100 / hop).  Listeners
     with no hashes in the window get [].  device=True keeps the windows on the GPU (shz_listeners_*): one library call per
-    push, no hash crosses the bus, same return value."""
+    push, no hash crosses the bus, same return value.  fs_in: the listeners' audio is at fs_in and the table at 44.1 kHz; the
+    chunks go through a StreamResampler first."""
 
     def __init__(self, db, n_listeners: int, channels: int = 1, window_seconds: float = 5, topn: int = TOPN,
-                 fan_value: int = 5, amp_min=10, device: bool = False):
+                 fan_value: int = 5, amp_min=10, device: bool = False, fs_in: int = None):
         self.db, self.n, self.channels, self.topn = db, int(n_listeners), int(channels), int(topn)
-        self.fp = StreamFingerprinter(self.n * self.channels, RATE, fan_value, amp_min, db.ctx)
+        self.fp = StreamFingerprinter(self.n * self.channels, RATE, fan_value, amp_min, db.ctx, fs_in)
         self.window_frames = int(float(window_seconds) * RATE / self.fp.streams.hop)
         self._k = [np.zeros(0, np.uint32) for _ in range(self.n)]
         self._t = [np.zeros(0, np.uint32) for _ in range(self.n)]
@@ -156,7 +169,7 @@ class StreamRecognizer:
     def _push_device(self, chunks, ends):
         from . import _result_dicts
         self.db.finalize()
-        res, w0 = self.listeners.push([None if c is None else _as_pcm(c) for c in chunks], ends, self.topn)
+        res, w0 = self.listeners.push(self.fp._pcm(chunks, ends), ends, self.topn)
         nhash = res["nhash"].tolist()
         return [(_result_dicts(self.db, res, l, nhash[l]) if nhash[l] else [], int(w0[l])) for l in range(self.n)]
 
@@ -170,6 +183,8 @@ class StreamRecognizer:
         ls = range(self.n) if listeners is None else list(listeners)
         if self.listeners is not None:
             self.listeners.reset(ls)
+            if self.fp.resampler is not None:
+                self.fp.resampler.reset([l * self.channels + j for l in ls for j in range(self.channels)])
             return
         self.fp.reset([l * self.channels + j for l in ls for j in range(self.channels)])
         for l in ls:
