@@ -1465,97 +1465,130 @@ static void threshold_band(double amp_min, double* p_lo, double* p_hi) {
   *p_hi = thr * (1.0 + 1e-9);
 }
 
-// peaks of a frame-major fp64 buffer -> device peak list (ws PEAK_F / PEAK_T) + per-clip offsets (ws PEAK_CLIP).
-// Host-synchronous helper of the stage APIs (shz_peaks_from_db); the batch path is extract_pass below.
-static int32_t run_peaks(shz_ctx* ctx, const double* d_db, uint32_t row_stride, uint32_t n_bins, const sub_dev& sd,
-                         uint32_t nc, uint32_t frames, double amp_min, bool is_power, uint16_t** d_pf, uint32_t** d_pt,
-                         uint32_t** d_pcoff, uint32_t* n_peaks) {
+// ---- stages shared by the batch path (extract_enqueue) and the host-synchronous stage API (run_peaks / run_pairs) ----
+// A stage queues one group of launches on ctx->stream.  Where a count lives (a device word) and how much the lists hold
+// are the caller's: the batch path counts in its control block and sizes its lists by estimate, the stage API reads the
+// count back between the stages and sizes them exactly.
+enum scan_of { SCAN_FRAME_COUNTS, SCAN_WORD_POPCOUNTS };   // what the exclusive scan beside a mask was taken over
+struct f64_source { const double* A; uint32_t row_stride, n_bins; bool is_power; };   // frame-major fp64 staging array
+struct peak_mask {             // the picked cells of a sub-batch and what indexes them
+  const uint64_t* mask;
+  uint64_t n_words;
+  mask_geom mg;
+  const uint32_t* scan;        // exclusive scan of the frames' peak counts or of the words' popcounts:
+  scan_of what;                // ... which of the two
+  uint32_t frames;
+  uint32_t* ft;                // scratch, one word per frame: its time within its clip
+};
+struct peak_lists { uint16_t* pf; uint32_t *pt, *pc; uint32_t cap; };   // peaks (f, t), per-clip offsets (nc + 1); capacity
+struct hash_dest { uint32_t *key, *t1; uint64_t base; const unsigned long long* d_base; uint64_t cap; };   // entries at base + *d_base
+
+// fp64 staging: the exact test in the kernel, then the zero-plateau rule of amp_min < 0
+static int32_t pick_f64(shz_ctx* ctx, const f64_source& src, const sub_dev& sd, uint32_t nc, const mask_geom& mg,
+                        uint64_t n_words, double amp_min, uint64_t* d_mask) {
+  double p_lo = 0.0, p_hi = 0.0;
+  if (src.is_power) threshold_band(amp_min, &p_lo, &p_hi);
+  {
+    shz_prof_scope ps(ctx, 1);
+    if (src.is_power)
+      hipLaunchKernelGGL(peak_pick_kernel<true>, dim3(mg.n_slabs, sd.n_segs), dim3(256), 0, ctx->stream, src.A, src.row_stride,
+                         src.n_bins, sd.d_segs, mg.n_slabs, amp_min, p_lo, p_hi, d_mask);
+    else
+      hipLaunchKernelGGL(peak_pick_kernel<false>, dim3(mg.n_slabs, sd.n_segs), dim3(256), 0, ctx->stream, src.A, src.row_stride,
+                         src.n_bins, sd.d_segs, mg.n_slabs, amp_min, p_lo, p_hi, d_mask);
+    SHZ_HIP(ctx, hipGetLastError());
+  }
+  if (amp_min < 0.0 && n_words) {  // see peak_zero_plateau_kernel
+    hipLaunchKernelGGL(peak_zero_plateau_kernel, dim3((unsigned)((n_words + 255) / 256)), dim3(256), 0, ctx->stream, d_mask,
+                       n_words, mg, src.A, src.row_stride, src.n_bins, src.is_power ? 1.0 : 0.0, sd.d_foff, nc);
+    SHZ_HIP(ctx, hipGetLastError());
+  }
+  return SHZ_OK;
+}
+
+// scanned mask -> peak lists and per-clip peak offsets (clamped to `clamp`); *d_count = the scan's total
+static int32_t expand_peaks(shz_ctx* ctx, const peak_mask& pm, const sub_dev& sd, uint32_t nc, const uint64_t* d_count,
+                            const peak_lists& pl, uint32_t clamp) {
+  const bool by_frame = pm.what == SCAN_FRAME_COUNTS;
+  if (pm.n_words) {
+    hipLaunchKernelGGL(frame_time_kernel, dim3((pm.frames + 255) / 256), dim3(256), 0, ctx->stream, sd.d_foff, nc, pm.frames, pm.ft);
+    if (by_frame)
+      hipLaunchKernelGGL(peak_expand_frames_kernel, dim3((unsigned)((pm.n_words + 256 * PXF_PER - 1) / (256 * PXF_PER))), dim3(256), 0,
+                         ctx->stream, pm.mask, pm.scan, (uint32_t)pm.n_words, pm.mg, (const uint32_t*)pm.ft, pl.pf, pl.pt, pl.cap);
+    else
+      hipLaunchKernelGGL(peak_expand_kernel, dim3((unsigned)((pm.n_words + 255) / 256)), dim3(256), 0, ctx->stream, pm.mask, pm.scan,
+                         (uint32_t)pm.n_words, pm.mg, (const uint32_t*)pm.ft, pl.pf, pl.pt, pl.cap);
+  }
+  hipLaunchKernelGGL(gather_offsets_kernel, dim3((nc + 1 + 255) / 256), dim3(256), 0, ctx->stream, pm.scan, d_count, sd.d_foff,
+                     by_frame ? (uint64_t)1 : (uint64_t)pm.mg.n_slabs * pm.mg.nw, by_frame ? (uint64_t)pm.frames : pm.n_words, nc,
+                     pl.pc, clamp);
+  SHZ_HIP(ctx, hipGetLastError());
+  return SHZ_OK;
+}
+
+// peak lists (*d_n peaks, at most pl.cap) -> hashes at hd, their total in *d_total, per-clip hash offsets (nc + 1,
+// relative) in *d_choff: hoff[pcoff[c]] (pcoff is clamped to pl.cap; slot pl.cap of the scan = the total)
+static int32_t hash_pairs(shz_ctx* ctx, const peak_lists& pl, uint32_t nc, const unsigned long long* d_n, uint32_t fan,
+                          uint64_t* d_total, const hash_dest& hd, uint32_t** d_choff) {
+  void *d_cnt, *d_hoff, *p;
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_HCNT, (uint64_t)pl.cap * 4 + 64, &d_cnt));
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_HOFF, (uint64_t)pl.cap * 4 + 64, &d_hoff));
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_MISC2, (uint64_t)(nc + 1) * 4 + 64, &p));
+  *d_choff = (uint32_t*)p;
+  const unsigned nb = (pl.cap + 255) / 256;
+  if (pl.cap)
+    hipLaunchKernelGGL(pair_count_kernel, dim3(nb), dim3(256), 0, ctx->stream, (const uint32_t*)pl.pt, (const uint32_t*)pl.pc, nc,
+                       d_n, pl.cap, fan, (uint32_t*)d_cnt);
+  SHZ_TRY(shz_scan_u32(ctx, (const uint32_t*)d_cnt, (uint32_t*)d_hoff, pl.cap, d_total));
+  if (pl.cap)
+    hipLaunchKernelGGL(pair_write_kernel, dim3(nb), dim3(256), 0, ctx->stream, (const uint16_t*)pl.pf, (const uint32_t*)pl.pt,
+                       (const uint32_t*)pl.pc, nc, d_n, pl.cap, fan, (const uint32_t*)d_hoff, hd.key, hd.t1, hd.base, hd.d_base, hd.cap);
+  hipLaunchKernelGGL(gather_offsets_kernel, dim3((nc + 1 + 255) / 256), dim3(256), 0, ctx->stream, (const uint32_t*)d_hoff,
+                     (const uint64_t*)d_total, (const uint32_t*)pl.pc, (uint64_t)1, (uint64_t)pl.cap, nc, *d_choff, 0xFFFFFFFFu);
+  SHZ_HIP(ctx, hipGetLastError());
+  return SHZ_OK;
+}
+
+// peaks of a frame-major fp64 buffer -> device peak lists (ws PEAK_F / PEAK_T) + per-clip offsets (ws PEAK_CLIP), sized
+// to the count that is read back.  Host-synchronous helper of the stage API (shz_peaks_from_db).
+static int32_t run_peaks(shz_ctx* ctx, const f64_source& src, const sub_dev& sd, uint32_t nc, uint32_t frames, double amp_min,
+                         peak_lists* out) {
   mask_geom mg = MG_F64;
-  mg.n_slabs = (n_bins + PK_SW - 1) / PK_SW;
+  mg.n_slabs = (src.n_bins + PK_SW - 1) / PK_SW;
   const uint64_t n_words = (uint64_t)frames * mg.n_slabs * 4;
   void *d_mask, *d_woff, *d_tot;
   SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_MASK, n_words * 8, &d_mask));
   SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SCAN, n_words * 4, &d_woff));
   SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_MISC0, 64, &d_tot));
-  double p_lo, p_hi;
-  threshold_band(amp_min, &p_lo, &p_hi);
-  {
-    shz_prof_scope ps(ctx, 1);
-    if (is_power)
-      hipLaunchKernelGGL(peak_pick_kernel<true>, dim3(mg.n_slabs, sd.n_segs), dim3(256), 0, ctx->stream, d_db, row_stride,
-                         n_bins, sd.d_segs, mg.n_slabs, amp_min, p_lo, p_hi, (uint64_t*)d_mask);
-    else
-      hipLaunchKernelGGL(peak_pick_kernel<false>, dim3(mg.n_slabs, sd.n_segs), dim3(256), 0, ctx->stream, d_db, row_stride,
-                         n_bins, sd.d_segs, mg.n_slabs, amp_min, 0.0, 0.0, (uint64_t*)d_mask);
-    SHZ_HIP(ctx, hipGetLastError());
-  }
-  if (amp_min < 0.0 && n_words) {  // see peak_zero_plateau_kernel
-    hipLaunchKernelGGL(peak_zero_plateau_kernel, dim3((unsigned)((n_words + 255) / 256)), dim3(256), 0, ctx->stream,
-                       (uint64_t*)d_mask, n_words, mg, d_db, row_stride, n_bins, is_power ? 1.0 : 0.0, sd.d_foff, nc);
-    SHZ_HIP(ctx, hipGetLastError());
-  }
+  SHZ_TRY(pick_f64(ctx, src, sd, nc, mg, n_words, amp_min, (uint64_t*)d_mask));
+  shz_prof_scope ps(ctx, 2);
   uint64_t tot = 0;
-  {
-    shz_prof_scope ps(ctx, 2);
-    SHZ_TRY(shz_scan_popc64(ctx, (const uint64_t*)d_mask, (uint32_t*)d_woff, n_words, (uint64_t*)d_tot));
-    SHZ_HIP(ctx, shz_memcpy(ctx, &tot, d_tot, 8, hipMemcpyDeviceToHost));
-    SHZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    void *pf, *pt, *pc;
-    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_PEAK_F, tot * 2 + 64, &pf));
-    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_PEAK_T, tot * 4 + 64, &pt));
-    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_PEAK_CLIP, (uint64_t)(nc + 1) * 4 + 64, &pc));
-    if (n_words) {
-      if (n_words >= (1ull << 32)) SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "too many mask words in one sub-batch");
-      void* ft;
-      SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_MISC1, (uint64_t)frames * 4 + 64, &ft));
-      hipLaunchKernelGGL(frame_time_kernel, dim3((frames + 255) / 256), dim3(256), 0, ctx->stream, sd.d_foff, nc, frames,
-                         (uint32_t*)ft);
-      hipLaunchKernelGGL(peak_expand_kernel, dim3((unsigned)((n_words + 255) / 256)), dim3(256), 0, ctx->stream,
-                         (const uint64_t*)d_mask, (const uint32_t*)d_woff, (uint32_t)n_words, mg, (const uint32_t*)ft,
-                         (uint16_t*)pf, (uint32_t*)pt, (uint32_t)tot);
-      SHZ_HIP(ctx, hipGetLastError());
-    }
-    hipLaunchKernelGGL(gather_offsets_kernel, dim3((nc + 1 + 255) / 256), dim3(256), 0, ctx->stream,
-                       (const uint32_t*)d_woff, (const uint64_t*)d_tot, sd.d_foff, (uint64_t)mg.n_slabs * 4, n_words, nc,
-                       (uint32_t*)pc, 0xFFFFFFFFu);
-    SHZ_HIP(ctx, hipGetLastError());
-    *d_pf = (uint16_t*)pf;
-    *d_pt = (uint32_t*)pt;
-    *d_pcoff = (uint32_t*)pc;
+  SHZ_TRY(shz_scan_popc64(ctx, (const uint64_t*)d_mask, (uint32_t*)d_woff, n_words, (uint64_t*)d_tot));
+  SHZ_HIP(ctx, shz_memcpy(ctx, &tot, d_tot, 8, hipMemcpyDeviceToHost));
+  SHZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  void *pf, *pt, *pc, *ft = nullptr;
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_PEAK_F, tot * 2 + 64, &pf));
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_PEAK_T, tot * 4 + 64, &pt));
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_PEAK_CLIP, (uint64_t)(nc + 1) * 4 + 64, &pc));
+  if (n_words) {
+    if (n_words >= (1ull << 32)) SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "too many mask words in one sub-batch");
+    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_MISC1, (uint64_t)frames * 4 + 64, &ft));
   }
-  *n_peaks = (uint32_t)tot;
-  return SHZ_OK;
+  *out = peak_lists{(uint16_t*)pf, (uint32_t*)pt, (uint32_t*)pc, (uint32_t)tot};
+  const peak_mask pm = {(const uint64_t*)d_mask, n_words, mg, (const uint32_t*)d_woff, SCAN_WORD_POPCOUNTS, frames, (uint32_t*)ft};
+  return expand_peaks(ctx, pm, sd, nc, (const uint64_t*)d_tot, *out, 0xFFFFFFFFu);
 }
 
-// pair hashing of a device peak list (host-synchronous helper of shz_pair_hash); writes into (d_key, d_t1)
-static int32_t run_pairs(shz_ctx* ctx, const uint16_t* d_pf, const uint32_t* d_pt, const uint32_t* d_pcoff, uint32_t nc,
-                         uint32_t n_peaks, uint32_t fan, uint32_t* d_key, uint32_t* d_t1, uint64_t out_base, uint64_t cap,
-                         uint64_t* n_hashes, std::vector<uint32_t>* clip_hoff /* nc+1, relative */) {
+// pair hashing of device peak lists holding exactly pl.cap peaks (host-synchronous helper of shz_pair_hash)
+static int32_t run_pairs(shz_ctx* ctx, const peak_lists& pl, uint32_t nc, uint32_t fan, const hash_dest& hd, uint64_t* n_hashes,
+                         std::vector<uint32_t>* clip_hoff /* nc+1, relative */) {
   shz_prof_scope ps(ctx, 3);
-  void *d_cnt, *d_hoff, *d_tot, *d_choff;
-  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_HCNT, (uint64_t)n_peaks * 4 + 64, &d_cnt));
-  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_HOFF, (uint64_t)n_peaks * 4 + 64, &d_hoff));
+  void* d_tot;
   SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_MISC1, 64, &d_tot));
-  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_MISC2, (uint64_t)(nc + 1) * 4 + 64, &d_choff));
   unsigned long long* d_n = (unsigned long long*)d_tot + 1;
-  hipLaunchKernelGGL(set_u64_dev_kernel, dim3(1), dim3(1), 0, ctx->stream, d_n, (unsigned long long)n_peaks);
-  const unsigned nb = (n_peaks + 255) / 256;
-  if (n_peaks) {
-    hipLaunchKernelGGL(pair_count_kernel, dim3(nb), dim3(256), 0, ctx->stream, d_pt, d_pcoff, nc, d_n, n_peaks, fan,
-                       (uint32_t*)d_cnt);
-    SHZ_HIP(ctx, hipGetLastError());
-  }
-  SHZ_TRY(shz_scan_u32(ctx, (const uint32_t*)d_cnt, (uint32_t*)d_hoff, n_peaks, (uint64_t*)d_tot));
-  if (n_peaks) {
-    hipLaunchKernelGGL(pair_write_kernel, dim3(nb), dim3(256), 0, ctx->stream, d_pf, d_pt, d_pcoff, nc, d_n, n_peaks, fan,
-                       (const uint32_t*)d_hoff, d_key, d_t1, out_base, (const unsigned long long*)nullptr, cap);
-    SHZ_HIP(ctx, hipGetLastError());
-  }
-  // per-clip hash offsets: hoff[pcoff[c]]
-  hipLaunchKernelGGL(gather_offsets_kernel, dim3((nc + 1 + 255) / 256), dim3(256), 0, ctx->stream,
-                     (const uint32_t*)d_hoff, (const uint64_t*)d_tot, d_pcoff, (uint64_t)1, (uint64_t)n_peaks, nc,
-                     (uint32_t*)d_choff, 0xFFFFFFFFu);
-  SHZ_HIP(ctx, hipGetLastError());
+  hipLaunchKernelGGL(set_u64_dev_kernel, dim3(1), dim3(1), 0, ctx->stream, d_n, (unsigned long long)pl.cap);
+  uint32_t* d_choff;
+  SHZ_TRY(hash_pairs(ctx, pl, nc, d_n, fan, (uint64_t*)d_tot, hd, &d_choff));
   uint64_t tot = 0;
   clip_hoff->resize(nc + 1);
   SHZ_HIP(ctx, shz_memcpy(ctx, &tot, d_tot, 8, hipMemcpyDeviceToHost));
@@ -1754,615 +1787,667 @@ extern "C" int32_t shz_stft_db_any(shz_ctx* ctx, const int16_t* pcm, uint64_t n_
 // (xctl) and come back with ONE copy + sync at the end.  List capacities are estimates; a pass whose flags say that an
 // estimate was too small, or that fp32 staging cannot decide the input (XF_FALLBACK), is repeated with the measured
 // sizes / with fp64 staging.
+struct xreq {                  // what to fingerprint
+  const int16_t* pcm;
+  const uint64_t* clip_off;
+  uint32_t n_clips, fs;
+  double amp_min;
+  uint32_t fan, flags;
+  xreq clips(uint32_t c0, uint32_t n) const { xreq r = *this; r.clip_off += c0; r.n_clips = n; return r; }
+};
+struct xout {                  // where the entries go (host or device arrays): peaks (f: 2 bytes, t) or hashes (key32, t1)
+  void* a;
+  uint64_t b_a;                // bytes per entry of a
+  uint32_t* b;
+  uint64_t* offs;              // n_clips + 1, may be null
+  uint64_t cap;
+  bool hashes;
+  xout at(uint64_t n, uint64_t room, uint64_t* o) const {   // the arrays from entry n on, with `room` entries and offsets o
+    return xout{a ? (char*)a + n * b_a : nullptr, b_a, b ? b + n : nullptr, o, room, hashes};
+  }
+};
 struct xparams {
   bool persistent_stft = false;  // dual pass: persistent STFT grid
   bool f32;                    // fp32 staging + verification (default) or fp64 staging with the exact test in-kernel
   uint32_t peaks_per_frame;    // peak list capacity per frame of a sub-batch
   uint64_t stage_cap;          // host output: capacity of the device staging arrays (entries)
 };
+static uint64_t stage_estimate(uint64_t frames, const xparams& xp, bool hashes, uint32_t fan) {
+  return frames * (uint64_t)xp.peaks_per_frame * (hashes ? (fan > 1 ? fan - 1 : 0) : 1) + 4096;
+}
 
 #define UND_CAP (1u << 20)
 
-// what extract_enqueue leaves for extract_finish: where the read-back lands and where the entries are
+// What is read back at the end of a pass, as byte offsets: control block | clip bitmap | per-clip offsets | entries a |
+// entries b.  A small pass with host outputs (one_block) keeps all of it in ONE device block laid out like this and
+// copies it in one piece instead of four (a copy is ~5 us of a 120 us call), the entries riding along; otherwise the
+// mailbox holds control block | offsets, `spec` is 0 and the entries are fetched once the count is known.
+struct pass_layout {
+  bool one_block;
+  uint64_t fb_words;           // the bitmap of clips that need fp64 staging sits 256 bytes behind the control block
+  uint64_t fb, offs, a, b, bytes;
+  uint64_t spec;               // entries that ride along
+};
+static pass_layout make_pass_layout(uint32_t n_clips, uint64_t stage_cap, uint64_t b_a, bool one_block) {
+  static_assert(sizeof(xctl) <= 256, "the clip bitmap starts 256 bytes behind the control block");
+  const auto up = [](uint64_t v) { return (v + 255) & ~255ull; };
+  pass_layout l;
+  l.one_block = one_block;
+  l.fb_words = ((uint64_t)n_clips + 31) / 32;
+  l.fb = 256;
+  l.offs = one_block ? l.fb + up(l.fb_words * 4) : 256;
+  l.spec = one_block ? stage_cap : 0;
+  l.a = l.offs + up((uint64_t)(n_clips + 1) * 8);
+  l.b = l.a + up(l.spec * b_a);
+  l.bytes = l.b + l.spec * 4;
+  return l;
+}
+
+struct pass_dev {              // device side of a pass
+  void* block;                 // one_block: the block itself
+  xctl* ctl;
+  uint32_t* fb;                // bitmap of the clips flagged XF_FALLBACK_CLIP
+  unsigned long long* offs;
+  void *o_a, *o_b;             // where the entries are written: the caller's device arrays or staging
+  uint64_t o_cap;
+};
+// what extract_enqueue leaves for extract_finish
 struct pass_tail {
-  char* mp = nullptr;                      // pinned mailbox: xctl | offsets | (small host outputs) entries
-  uint64_t off_offs = 0, off_a = 0, off_b = 0, spec = 0, b_a = 4, o_cap = 0;
-  void *o_a = nullptr, *o_b = nullptr;     // device arrays the entries were written to
+  char* mp = nullptr;          // pinned mailbox
+  pass_layout lay;
+  pass_dev dev;
   uint32_t n_clips = 0;
-  bool out_dev = false, want_hashes = true, stay = false;
-  const uint32_t* d_fb = nullptr;          // device bitmap of the clips flagged XF_FALLBACK_CLIP
+  bool out_dev = false, stay = false;
 };
 
-// Queue one pass on ctx->stream, up to and including the asynchronous copies of its read-back.  `stay`: the entries stay
-// in the context's staging arrays (pt->o_a / o_b) whatever the flags say -- the second pipeline of a dual pass.
-static int32_t extract_enqueue(shz_ctx* ctx, const int16_t* pcm, const uint64_t* clip_off, uint32_t n_clips, uint32_t fs,
-                               double amp_min, uint32_t fan, uint32_t flags, bool want_hashes, const xparams& xp,
-                               uint16_t* peak_f, uint32_t* peak_t, uint32_t* key32, uint32_t* t1, uint64_t cap, bool stay,
-                               pass_tail* pt) {
-  const bool out_dev = (flags & SHZ_OUT_DEVICE) != 0 && !stay;
-  const mask_geom mg = xp.f32 ? MG_F32 : MG_F64;
-  const uint64_t pw_bytes_per_frame = xp.f32 ? (uint64_t)P32_STRIDE * 4 : (uint64_t)DB_STRIDE * 8;
-  std::vector<sub_batch> subs;
-  SHZ_TRY(plan_sub_batches(ctx, clip_off, n_clips, pw_bytes_per_frame, subs));
+// a sub-batch's route through the stages, chosen once
+struct sub_route {
+  bool f32;                    // staging mode
+  bool small_tail;             // the one-workgroup tail (hashes only) or the general one
+  bool hashes;
+  scan_of scan;                // what the general tail scans: fp32 staging counts peaks per frame, fp64 leaves the mask only
+};
+static sub_route choose_route(bool f32, bool hashes, uint64_t n_words, uint32_t cap_peaks) {
+  return sub_route{f32, hashes && n_words && n_words <= XT_MAX_WORDS && cap_peaks <= XT_MAX_PEAKS, hashes,
+                   f32 ? SCAN_FRAME_COUNTS : SCAN_WORD_POPCOUNTS};
+}
+// a staged sub-batch: its spectrogram and the buffers of the stages that follow
+struct sub_work {
+  sub_batch sb;
+  uint32_t nc;
+  sub_route rt;
+  mask_geom mg;
+  sub_dev sd;
+  stft_args sa;
+  uint64_t n_words;
+  uint32_t cap_peaks;
+  void* d_pw;
+  uint64_t* d_mask;
+  uint32_t *d_scan, *d_fcnt;
+  peak_lists pl;
+  uint32_t* ft;
+};
+
+static uint64_t pw_bytes_per_frame(bool f32) { return f32 ? (uint64_t)P32_STRIDE * 4 : (uint64_t)DB_STRIDE * 8; }
+
+// Device pointers of a pass from its layout; the control block and bitmap zeroed.  The entries go to the caller's device
+// arrays, or to staging arrays that are copied out after the final sync.
+static int32_t place_pass(shz_ctx* ctx, const pass_layout& l, const xout& out, bool out_dev, uint64_t stage_cap, uint32_t n_clips,
+                          pass_dev* pd) {
   void *p_ctl, *p_offs;
-  const uint64_t fb_words = ((uint64_t)n_clips + 31) / 32;   // bitmap of clips that need fp64 staging, behind the control block
-  // A small pass with host outputs keeps everything that is read back in ONE device block, laid out like the mailbox:
-  // control block | clip bitmap | per-clip offsets | entries a | entries b -- one copy at the end instead of four
-  // (a copy is ~5 us of a 120 us call).
-  const uint64_t b_a = want_hashes ? 4 : 2;
-  const bool one_block = !out_dev && !stay && xp.stage_cap <= (1u << 15);
-  const uint64_t ob_offs = 256 + ((fb_words * 4 + 255) & ~255ull);
-  const uint64_t ob_a = ob_offs + (((uint64_t)(n_clips + 1) * 8 + 255) & ~255ull);
-  const uint64_t ob_b = ob_a + ((xp.stage_cap * b_a + 255) & ~255ull);
-  const uint64_t ob_bytes = ob_b + xp.stage_cap * 4;
-  void* p_block = nullptr;
-  if (one_block) {
-    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_KEY, ob_bytes + 64, &p_block));
-    p_ctl = p_block;
-    p_offs = (char*)p_block + ob_offs;
+  pd->block = nullptr;
+  if (l.one_block) {
+    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_KEY, l.bytes + 64, &pd->block));
+    p_ctl = pd->block;
+    p_offs = (char*)pd->block + l.offs;
   } else {
-    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_CTL, 256 + fb_words * 4 + 64, &p_ctl));
+    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_CTL, 256 + l.fb_words * 4 + 64, &p_ctl));
     SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_OFFS, (uint64_t)(n_clips + 1) * 8 + 64, &p_offs));
   }
-  xctl* d_ctl = (xctl*)p_ctl;
-  unsigned long long* d_offs = (unsigned long long*)p_offs;
-  static_assert(sizeof(xctl) <= 256, "the clip bitmap starts 256 bytes behind the control block");
-  uint32_t* d_fb = (uint32_t*)((char*)p_ctl + 256);
-  SHZ_HIP(ctx, hipMemsetAsync(d_ctl, 0, 256 + ((fb_words * 4 + 63) & ~63ull), ctx->stream));   // (whole 64-byte lines: one fill, not a body and a tail)   // (offs[0] = 0 is written by xctl_offsets_kernel)
-  // where the entries go: the caller's device arrays, or staging arrays that are copied out after the final sync
-  void *o_a = want_hashes ? (void*)key32 : (void*)peak_f, *o_b = want_hashes ? (void*)t1 : (void*)peak_t;
-  uint64_t o_cap = cap;
-  if (one_block) {
-    o_cap = xp.stage_cap;
-    o_a = (char*)p_block + ob_a;
-    o_b = (char*)p_block + ob_b;
+  pd->ctl = (xctl*)p_ctl;
+  pd->offs = (unsigned long long*)p_offs;
+  pd->fb = (uint32_t*)((char*)p_ctl + l.fb);
+  SHZ_HIP(ctx, hipMemsetAsync(pd->ctl, 0, 256 + ((l.fb_words * 4 + 63) & ~63ull), ctx->stream));   // (whole 64-byte lines: one fill, not a body and a tail)   // (offs[0] = 0 is written by xctl_offsets_kernel)
+  pd->o_a = out.a;
+  pd->o_b = out.b;
+  pd->o_cap = out.cap;
+  if (l.one_block) {
+    pd->o_cap = stage_cap;
+    pd->o_a = (char*)pd->block + l.a;
+    pd->o_b = (char*)pd->block + l.b;
   } else if (!out_dev) {
-    o_cap = xp.stage_cap;
-    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_KEY, o_cap * 4 + 64, &o_a));
-    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_T1, o_cap * 4 + 64, &o_b));
+    pd->o_cap = stage_cap;
+    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_KEY, pd->o_cap * 4 + 64, &pd->o_a));
+    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_T1, pd->o_cap * 4 + 64, &pd->o_b));
   }
+  return SHZ_OK;
+}
+
+// stage: PCM + tables on the device, STFT, the buffers of the later stages, the route
+static int32_t stage_sub_batch(shz_ctx* ctx, const xreq& rq, bool hashes, const xparams& xp, const sub_batch& sb,
+                               std::vector<std::vector<uint64_t>>& keep, sub_work* w) {
+  w->sb = sb;
+  w->nc = sb.c1 - sb.c0;
+  w->mg = xp.f32 ? MG_F32 : MG_F64;
+  const int16_t* d_pcm;
+  uint64_t base;
+  SHZ_TRY(stage_pcm(ctx, rq.pcm, rq.clip_off, sb, rq.flags, &d_pcm, &base));
+  SHZ_TRY(upload_meta(ctx, rq.clip_off, sb, base, w->mg.n_slabs, xp.f32 ? 12 / w->mg.nw : 3, w->sd, keep));
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_DB, (uint64_t)sb.frames * pw_bytes_per_frame(xp.f32), &w->d_pw));
+  w->sa = make_stft_args(ctx, d_pcm, w->sd, w->nc, sb.frames, rq.fs, w->d_pw);
+  if (xp.f32) SHZ_TRY(launch_stft(ctx, w->sa, xp.persistent_stft));
+  else SHZ_TRY(launch_stft_np(ctx, w->sa));
+  w->n_words = (uint64_t)sb.frames * w->mg.n_slabs * w->mg.nw;
+  if (w->n_words >= (1ull << 32)) SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "too many mask words in one sub-batch");
+  const uint64_t cap_peaks64 = (uint64_t)sb.frames * xp.peaks_per_frame + 4096;
+  if (cap_peaks64 * (rq.fan > 1 ? rq.fan - 1 : 1) >= (1ull << 32))
+    SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "sub-batch of %u frames may yield 2^32 hashes; lower the workspace limit", sb.frames);
+  w->cap_peaks = (uint32_t)cap_peaks64;
+  void *d_mask, *d_scan, *pf, *pt, *pc, *ft;
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_MASK, w->n_words * 8, &d_mask));
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SCAN, w->n_words * 4, &d_scan));
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_PEAK_F, (uint64_t)w->cap_peaks * 2 + 64, &pf));
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_PEAK_T, (uint64_t)w->cap_peaks * 4 + 64, &pt));
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_PEAK_CLIP, (uint64_t)(w->nc + 1) * 4 + 64, &pc));
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_MISC1, (uint64_t)sb.frames * 4 + 64, &ft));
+  w->d_mask = (uint64_t*)d_mask;
+  w->d_scan = (uint32_t*)d_scan;
+  w->d_fcnt = nullptr;
+  if (xp.f32) {   // peaks per frame, counted by the fp32 pick
+    void* d_fcnt;
+    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_MISC3, (uint64_t)sb.frames * 4 + 64, &d_fcnt));
+    w->d_fcnt = (uint32_t*)d_fcnt;
+  }
+  w->pl = peak_lists{(uint16_t*)pf, (uint32_t*)pt, (uint32_t*)pc, w->cap_peaks};
+  w->ft = (uint32_t*)ft;
+  w->rt = choose_route(xp.f32, hashes, w->n_words, w->cap_peaks);
+  return SHZ_OK;
+}
+
+// stage: pick in fp32 staging -- fills, peak_pick32, the cells fp32 cannot decide verified on fp64 values
+static int32_t pick_f32(shz_ctx* ctx, const sub_work& w, const pass_dev& pd, double amp_min, bool first_sub) {
   double p_lo, p_hi;
   threshold_band(amp_min, &p_lo, &p_hi);
+  void* d_und;
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_UND, (uint64_t)UND_CAP * 8, &d_und));
+  if (!first_sub) hipLaunchKernelGGL(xctl_begin_sub_kernel, dim3(1), dim3(1), 0, ctx->stream, pd.ctl);   // (the block starts zeroed)
+  SHZ_HIP(ctx, hipMemsetAsync(w.d_mask, 0, w.n_words * 8, ctx->stream));  // peak_pick32 writes non-zero words only
+  if (!w.rt.small_tail) SHZ_HIP(ctx, hipMemsetAsync(w.d_fcnt, 0, (uint64_t)w.sb.frames * 4, ctx->stream));   // (the one-workgroup tail counts from the mask)
+  {
+    shz_prof_scope ps(ctx, 1);
+    p32_args pa;
+    pa.A = (const float*)w.d_pw;
+    pa.segs = w.sd.d_segs;
+    pa.n_slabs = w.mg.n_slabs;
+    pa.n_segs = w.sd.n_segs;
+    pa.p_lo = (float)p_lo;   // fp32(P) < fp32(p_lo) => P < p_lo; fp32(P) > fp32(p_hi) => P > p_hi (monotone rounding)
+    pa.p_hi = (float)p_hi;
+    pa.mask = w.d_mask;
+    pa.und_list = (uint64_t*)d_und;
+    pa.ctl = pd.ctl;
+    pa.und_cap = UND_CAP;
+    pa.frame_cnt = w.d_fcnt;
+    const uint32_t per_xcd = (w.sd.n_segs + 7) >> 3;   // segments per XCD; 8 * per_xcd * n_slabs workgroups, see the kernel's work map
+    hipLaunchKernelGGL((peak_pick32_kernel<P32_NW, P32_OCC>), dim3(8 * per_xcd * pa.n_slabs), dim3(64 * P32_NW), 0, ctx->stream, pa);
+    SHZ_HIP(ctx, hipGetLastError());
+  }
+  {
+    shz_prof_scope ps(ctx, 4);
+    verify_args va;
+    va.st = w.sa;
+    va.A = (const float*)w.d_pw;
+    va.mask = w.d_mask;
+    va.frame_cnt = w.d_fcnt;
+    va.mg = w.mg;
+    va.und_list = (const uint64_t*)d_und;
+    va.ctl = pd.ctl;
+    va.und_cap = UND_CAP;
+    va.p_hi32 = (float)p_hi;
+    va.p_lo = p_lo;
+    va.p_hi = p_hi;
+    va.amp_min = amp_min;
+    va.fb_clips = pd.fb;
+    va.clip0 = w.sb.c0;
+    hipLaunchKernelGGL(peak_verify_kernel, dim3((unsigned)ctx->prop.multiProcessorCount), dim3(256), 0, ctx->stream, va);
+    SHZ_HIP(ctx, hipGetLastError());
+  }
+  return SHZ_OK;
+}
+
+// stage: the whole tail of a small sub-batch (mask -> hashes and offsets) in one workgroup
+static int32_t tail_small(shz_ctx* ctx, const sub_work& w, const pass_dev& pd, uint32_t fan) {
+  shz_prof_scope ps(ctx, 3);
+  void* d_hoff;
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_HOFF, (uint64_t)w.cap_peaks * 4 + 64, &d_hoff));
+  hipLaunchKernelGGL(extract_tail_small_kernel, dim3(1), dim3(XT_THREADS), 0, ctx->stream, (const uint64_t*)w.d_mask,
+                     (uint32_t)w.n_words, w.mg, (const uint32_t*)w.sd.d_foff, w.nc, w.sb.c0, pd.ctl, w.cap_peaks, (uint32_t)UND_CAP, fan,
+                     w.pl.pf, w.pl.pt, w.pl.pc, (uint32_t*)d_hoff, (uint32_t*)pd.o_a, (uint32_t*)pd.o_b, pd.o_cap, pd.offs);
+  SHZ_HIP(ctx, hipGetLastError());
+  return SHZ_OK;
+}
+
+// stage: the general peak list -- scan (of what the route says), bookkeeping, expansion, per-clip peak offsets
+static int32_t list_peaks(shz_ctx* ctx, const sub_work& w, const pass_dev& pd) {
+  shz_prof_scope ps(ctx, 2);
+  uint64_t* d_count = (uint64_t*)&pd.ctl->sub_peaks;
+  if (w.rt.scan == SCAN_FRAME_COUNTS) SHZ_TRY(shz_scan_u32(ctx, w.d_fcnt, w.d_scan, w.sb.frames, d_count));
+  else SHZ_TRY(shz_scan_popc64(ctx, w.d_mask, w.d_scan, w.n_words, d_count));
+  hipLaunchKernelGGL(xctl_after_peaks_kernel, dim3(1), dim3(1), 0, ctx->stream, pd.ctl, w.cap_peaks, UND_CAP);
+  const peak_mask pm = {w.d_mask, w.n_words, w.mg, w.d_scan, w.rt.scan, w.sb.frames, w.ft};
+  return expand_peaks(ctx, pm, w.sd, w.nc, d_count, w.pl, w.cap_peaks);
+}
+
+// stage: peaks out -- offsets, entries, advance
+static int32_t peaks_out(shz_ctx* ctx, const sub_work& w, const pass_dev& pd) {
+  hipLaunchKernelGGL(xctl_offsets_kernel, dim3((w.nc + 255) / 256), dim3(256), 0, ctx->stream, pd.ctl, false,
+                     (const uint32_t*)w.pl.pc, w.nc, w.sb.c0, pd.offs);
+  hipLaunchKernelGGL(peaks_out_kernel, dim3((w.cap_peaks + 255) / 256), dim3(256), 0, ctx->stream, pd.ctl, (const uint16_t*)w.pl.pf,
+                     (const uint32_t*)w.pl.pt, w.cap_peaks, (uint16_t*)pd.o_a, (uint32_t*)pd.o_b, pd.o_cap);
+  hipLaunchKernelGGL(xctl_advance_kernel, dim3(1), dim3(1), 0, ctx->stream, pd.ctl, w.cap_peaks, false);
+  SHZ_HIP(ctx, hipGetLastError());
+  return SHZ_OK;
+}
+
+// stage: hashes out -- count, scan, write, per-clip hash offsets, offsets, advance
+static int32_t hashes_out(shz_ctx* ctx, const sub_work& w, const pass_dev& pd, uint32_t fan) {
+  shz_prof_scope ps(ctx, 3);
+  uint32_t* d_choff;
+  const hash_dest hd = {(uint32_t*)pd.o_a, (uint32_t*)pd.o_b, 0, &pd.ctl->hash_base, pd.o_cap};
+  SHZ_TRY(hash_pairs(ctx, w.pl, w.nc, &pd.ctl->sub_peaks, fan, (uint64_t*)&pd.ctl->sub_hashes, hd, &d_choff));
+  hipLaunchKernelGGL(xctl_offsets_kernel, dim3((w.nc + 255) / 256), dim3(256), 0, ctx->stream, pd.ctl, true,
+                     (const uint32_t*)d_choff, w.nc, w.sb.c0, pd.offs);
+  hipLaunchKernelGGL(xctl_advance_kernel, dim3(1), dim3(1), 0, ctx->stream, pd.ctl, w.cap_peaks, true);
+  SHZ_HIP(ctx, hipGetLastError());
+  return SHZ_OK;
+}
+
+// The one read-back of the pass, into pinned memory: control block | per-clip offsets | for small host outputs the
+// entries themselves (they ride along instead of costing a second round trip once the count is known).
+static int32_t queue_read_back(shz_ctx* ctx, pass_tail* pt) {
+  void* mailp;
+  SHZ_TRY(shz_mailbox(ctx, pt->lay.bytes, &mailp));
+  pt->mp = (char*)mailp;
+  if (pt->lay.one_block) {
+    SHZ_HIP(ctx, hipMemcpyAsync(pt->mp, pt->dev.block, pt->lay.bytes, hipMemcpyDeviceToHost, ctx->stream));
+  } else {
+    SHZ_HIP(ctx, hipMemcpyAsync(pt->mp, pt->dev.ctl, sizeof(xctl), hipMemcpyDeviceToHost, ctx->stream));
+    SHZ_HIP(ctx, hipMemcpyAsync(pt->mp + pt->lay.offs, pt->dev.offs, (uint64_t)(pt->n_clips + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
+  }
+  return SHZ_OK;
+}
+
+// Queue one pass on ctx->stream, up to and including the asynchronous copies of its read-back.  `stay`: the entries stay
+// in the context's staging arrays (pt->dev.o_a / o_b) whatever the flags say -- the second pipeline of a dual pass.
+static int32_t extract_enqueue(shz_ctx* ctx, const xreq& rq, const xout& out, const xparams& xp, bool stay, pass_tail* pt) {
+  pt->out_dev = (rq.flags & SHZ_OUT_DEVICE) != 0 && !stay;
+  pt->stay = stay;
+  pt->n_clips = rq.n_clips;
+  std::vector<sub_batch> subs;
+  SHZ_TRY(plan_sub_batches(ctx, rq.clip_off, rq.n_clips, pw_bytes_per_frame(xp.f32), subs));
+  pt->lay = make_pass_layout(rq.n_clips, xp.stage_cap, out.b_a, !pt->out_dev && !stay && xp.stage_cap <= (1u << 15));
+  SHZ_TRY(place_pass(ctx, pt->lay, out, pt->out_dev, xp.stage_cap, rq.n_clips, &pt->dev));
   std::vector<std::vector<uint64_t>> keep;
   for (size_t si = 0; si < subs.size(); ++si) {
-    const sub_batch& sb = subs[si];
-    const uint32_t nc = sb.c1 - sb.c0;
-    // PCM + tables on the device, STFT
-    sub_dev sd;
-    const int16_t* d_pcm;
-    uint64_t base;
-    void* d_pw;
-    SHZ_TRY(stage_pcm(ctx, pcm, clip_off, sb, flags, &d_pcm, &base));
-    SHZ_TRY(upload_meta(ctx, clip_off, sb, base, mg.n_slabs, xp.f32 ? 12 / mg.nw : 3, sd, keep));
-    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_DB, (uint64_t)sb.frames * pw_bytes_per_frame, &d_pw));
-    const stft_args sa = make_stft_args(ctx, d_pcm, sd, nc, sb.frames, fs, d_pw);
-    if (xp.f32) SHZ_TRY(launch_stft(ctx, sa, xp.persistent_stft));
-    else SHZ_TRY(launch_stft_np(ctx, sa));
-    const uint64_t n_words = (uint64_t)sb.frames * mg.n_slabs * mg.nw;
-    if (n_words >= (1ull << 32)) SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "too many mask words in one sub-batch");
-    const uint64_t cap_peaks64 = (uint64_t)sb.frames * xp.peaks_per_frame + 4096;
-    if (cap_peaks64 * (fan > 1 ? fan - 1 : 1) >= (1ull << 32))
-      SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "sub-batch of %u frames may yield 2^32 hashes; lower the workspace limit", sb.frames);
-    const uint32_t cap_peaks = (uint32_t)cap_peaks64;
-    void *d_mask, *d_woff, *d_und, *pf, *pt, *pc, *ft, *d_fcnt = nullptr;
-    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_MASK, n_words * 8, &d_mask));
-    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SCAN, n_words * 4, &d_woff));
-    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_PEAK_F, (uint64_t)cap_peaks * 2 + 64, &pf));
-    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_PEAK_T, (uint64_t)cap_peaks * 4 + 64, &pt));
-    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_PEAK_CLIP, (uint64_t)(nc + 1) * 4 + 64, &pc));
-    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_MISC1, (uint64_t)sb.frames * 4 + 64, &ft));
-    const bool small_tail = want_hashes && n_words && n_words <= XT_MAX_WORDS && cap_peaks <= XT_MAX_PEAKS;
-    if (xp.f32) {
-      SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_UND, (uint64_t)UND_CAP * 8, &d_und));
-      if (si) hipLaunchKernelGGL(xctl_begin_sub_kernel, dim3(1), dim3(1), 0, ctx->stream, d_ctl);   // (the block starts zeroed)
-      SHZ_HIP(ctx, hipMemsetAsync(d_mask, 0, n_words * 8, ctx->stream));  // peak_pick32 writes non-zero words only
-      SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_MISC3, (uint64_t)sb.frames * 4 + 64, &d_fcnt));
-      if (!small_tail) SHZ_HIP(ctx, hipMemsetAsync(d_fcnt, 0, (uint64_t)sb.frames * 4, ctx->stream));   // (the one-workgroup tail counts from the mask)
-      {
-        shz_prof_scope ps(ctx, 1);
-        p32_args pa;
-        pa.A = (const float*)d_pw;
-        pa.segs = sd.d_segs;
-        pa.n_slabs = mg.n_slabs;
-        pa.n_segs = sd.n_segs;
-        pa.p_lo = (float)p_lo;   // fp32(P) < fp32(p_lo) => P < p_lo; fp32(P) > fp32(p_hi) => P > p_hi (monotone rounding)
-        pa.p_hi = (float)p_hi;
-        pa.mask = (uint64_t*)d_mask;
-        pa.und_list = (uint64_t*)d_und;
-        pa.ctl = d_ctl;
-        pa.und_cap = UND_CAP;
-        pa.frame_cnt = (uint32_t*)d_fcnt;
-        const uint32_t per_xcd = (sd.n_segs + 7) >> 3;   // segments per XCD; 8 * per_xcd * n_slabs workgroups, see the kernel's work map
-        hipLaunchKernelGGL((peak_pick32_kernel<P32_NW, P32_OCC>), dim3(8 * per_xcd * pa.n_slabs), dim3(64 * P32_NW), 0, ctx->stream, pa);
-        SHZ_HIP(ctx, hipGetLastError());
-      }
-      {
-        shz_prof_scope ps(ctx, 4);
-        verify_args va;
-        va.st = sa;
-        va.A = (const float*)d_pw;
-        va.mask = (uint64_t*)d_mask;
-        va.frame_cnt = (uint32_t*)d_fcnt;
-        va.mg = mg;
-        va.und_list = (const uint64_t*)d_und;
-        va.ctl = d_ctl;
-        va.und_cap = UND_CAP;
-        va.p_hi32 = (float)p_hi;
-        va.p_lo = p_lo;
-        va.p_hi = p_hi;
-        va.amp_min = amp_min;
-        va.fb_clips = d_fb;
-        va.clip0 = sb.c0;
-        hipLaunchKernelGGL(peak_verify_kernel, dim3((unsigned)ctx->prop.multiProcessorCount), dim3(256), 0,
-                           ctx->stream, va);
-        SHZ_HIP(ctx, hipGetLastError());
-      }
-    } else {
-      {
-        shz_prof_scope ps(ctx, 1);
-        hipLaunchKernelGGL(peak_pick_kernel<true>, dim3(mg.n_slabs, sd.n_segs), dim3(256), 0, ctx->stream,
-                           (const double*)d_pw, (uint32_t)DB_STRIDE, (uint32_t)SHZ_NBINS, sd.d_segs, mg.n_slabs, amp_min,
-                           p_lo, p_hi, (uint64_t*)d_mask);
-        SHZ_HIP(ctx, hipGetLastError());
-      }
-      if (amp_min < 0.0 && n_words) {  // see peak_zero_plateau_kernel
-        hipLaunchKernelGGL(peak_zero_plateau_kernel, dim3((unsigned)((n_words + 255) / 256)), dim3(256), 0, ctx->stream,
-                           (uint64_t*)d_mask, n_words, mg, (const double*)d_pw, (uint32_t)DB_STRIDE, (uint32_t)SHZ_NBINS,
-                           1.0, sd.d_foff, nc);
-        SHZ_HIP(ctx, hipGetLastError());
-      }
-    }
-    if (small_tail) {
-      shz_prof_scope ps(ctx, 3);
-      void* d_hoff;
-      SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_HOFF, (uint64_t)cap_peaks * 4 + 64, &d_hoff));
-      hipLaunchKernelGGL(extract_tail_small_kernel, dim3(1), dim3(XT_THREADS), 0, ctx->stream, (const uint64_t*)d_mask,
-                         (uint32_t)n_words, mg, (const uint32_t*)sd.d_foff, nc, sb.c0, d_ctl, cap_peaks, (uint32_t)UND_CAP, fan,
-                         (uint16_t*)pf, (uint32_t*)pt, (uint32_t*)pc, (uint32_t*)d_hoff, (uint32_t*)o_a, (uint32_t*)o_b, o_cap, d_offs);
-      SHZ_HIP(ctx, hipGetLastError());
+    sub_work w;
+    SHZ_TRY(stage_sub_batch(ctx, rq, out.hashes, xp, subs[si], keep, &w));
+    if (w.rt.f32) SHZ_TRY(pick_f32(ctx, w, pt->dev, rq.amp_min, si == 0));
+    else SHZ_TRY(pick_f64(ctx, f64_source{(const double*)w.d_pw, (uint32_t)DB_STRIDE, (uint32_t)SHZ_NBINS, true}, w.sd, w.nc, w.mg,
+                          w.n_words, rq.amp_min, w.d_mask));
+    if (w.rt.small_tail) {
+      SHZ_TRY(tail_small(ctx, w, pt->dev, rq.fan));
       continue;
     }
-    {
-      shz_prof_scope ps(ctx, 2);
-      // offsets of the peaks: fp32 staging counted them per frame (d_woff = exclusive scan of the frames' counts),
-      // the fp64 kernels leave the mask only (d_woff = exclusive scan of the words' popcounts)
-      if (xp.f32) SHZ_TRY(shz_scan_u32(ctx, (const uint32_t*)d_fcnt, (uint32_t*)d_woff, sb.frames, (uint64_t*)&d_ctl->sub_peaks));
-      else SHZ_TRY(shz_scan_popc64(ctx, (const uint64_t*)d_mask, (uint32_t*)d_woff, n_words, (uint64_t*)&d_ctl->sub_peaks));
-      hipLaunchKernelGGL(xctl_after_peaks_kernel, dim3(1), dim3(1), 0, ctx->stream, d_ctl, cap_peaks, UND_CAP);
-      if (n_words) {
-        hipLaunchKernelGGL(frame_time_kernel, dim3((sb.frames + 255) / 256), dim3(256), 0, ctx->stream, sd.d_foff, nc,
-                           sb.frames, (uint32_t*)ft);
-        if (xp.f32)
-          hipLaunchKernelGGL(peak_expand_frames_kernel, dim3((unsigned)((n_words + 256 * PXF_PER - 1) / (256 * PXF_PER))), dim3(256), 0, ctx->stream,
-                             (const uint64_t*)d_mask, (const uint32_t*)d_woff, (uint32_t)n_words, mg, (const uint32_t*)ft,
-                             (uint16_t*)pf, (uint32_t*)pt, cap_peaks);
-        else
-          hipLaunchKernelGGL(peak_expand_kernel, dim3((unsigned)((n_words + 255) / 256)), dim3(256), 0, ctx->stream,
-                             (const uint64_t*)d_mask, (const uint32_t*)d_woff, (uint32_t)n_words, mg, (const uint32_t*)ft,
-                             (uint16_t*)pf, (uint32_t*)pt, cap_peaks);
-      }
-      hipLaunchKernelGGL(gather_offsets_kernel, dim3((nc + 1 + 255) / 256), dim3(256), 0, ctx->stream,
-                         (const uint32_t*)d_woff, (const uint64_t*)&d_ctl->sub_peaks, sd.d_foff,
-                         xp.f32 ? (uint64_t)1 : (uint64_t)mg.n_slabs * mg.nw, xp.f32 ? (uint64_t)sb.frames : n_words, nc,
-                         (uint32_t*)pc, cap_peaks);
-      SHZ_HIP(ctx, hipGetLastError());
-    }
-    if (!want_hashes) {
-      hipLaunchKernelGGL(xctl_offsets_kernel, dim3((nc + 255) / 256), dim3(256), 0, ctx->stream, d_ctl, false,
-                         (const uint32_t*)pc, nc, sb.c0, d_offs);
-      hipLaunchKernelGGL(peaks_out_kernel, dim3((cap_peaks + 255) / 256), dim3(256), 0, ctx->stream, d_ctl,
-                         (const uint16_t*)pf, (const uint32_t*)pt, cap_peaks, (uint16_t*)o_a, (uint32_t*)o_b, o_cap);
-      hipLaunchKernelGGL(xctl_advance_kernel, dim3(1), dim3(1), 0, ctx->stream, d_ctl, cap_peaks, false);
-      SHZ_HIP(ctx, hipGetLastError());
-      continue;
-    }
-    {
-      shz_prof_scope ps(ctx, 3);
-      void *d_cnt, *d_hoff, *d_choff;
-      SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_HCNT, (uint64_t)cap_peaks * 4 + 64, &d_cnt));
-      SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_HOFF, (uint64_t)cap_peaks * 4 + 64, &d_hoff));
-      SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_MISC2, (uint64_t)(nc + 1) * 4 + 64, &d_choff));
-      const unsigned nb = (cap_peaks + 255) / 256;
-      hipLaunchKernelGGL(pair_count_kernel, dim3(nb), dim3(256), 0, ctx->stream, (const uint32_t*)pt, (const uint32_t*)pc,
-                         nc, &d_ctl->sub_peaks, cap_peaks, fan, (uint32_t*)d_cnt);
-      SHZ_TRY(shz_scan_u32(ctx, (const uint32_t*)d_cnt, (uint32_t*)d_hoff, cap_peaks, (uint64_t*)&d_ctl->sub_hashes));
-      hipLaunchKernelGGL(pair_write_kernel, dim3(nb), dim3(256), 0, ctx->stream, (const uint16_t*)pf, (const uint32_t*)pt,
-                         (const uint32_t*)pc, nc, &d_ctl->sub_peaks, cap_peaks, fan, (const uint32_t*)d_hoff,
-                         (uint32_t*)o_a, (uint32_t*)o_b, (uint64_t)0, &d_ctl->hash_base, o_cap);
-      // per-clip hash offsets: hoff[pcoff[c]] (pcoff is clamped to cap_peaks; slot cap_peaks of the scan = the total)
-      hipLaunchKernelGGL(gather_offsets_kernel, dim3((nc + 1 + 255) / 256), dim3(256), 0, ctx->stream,
-                         (const uint32_t*)d_hoff, (const uint64_t*)&d_ctl->sub_hashes, (const uint32_t*)pc, (uint64_t)1,
-                         (uint64_t)cap_peaks, nc, (uint32_t*)d_choff, 0xFFFFFFFFu);
-      hipLaunchKernelGGL(xctl_offsets_kernel, dim3((nc + 255) / 256), dim3(256), 0, ctx->stream, d_ctl, true,
-                         (const uint32_t*)d_choff, nc, sb.c0, d_offs);
-      hipLaunchKernelGGL(xctl_advance_kernel, dim3(1), dim3(1), 0, ctx->stream, d_ctl, cap_peaks, true);
-      SHZ_HIP(ctx, hipGetLastError());
-    }
+    SHZ_TRY(list_peaks(ctx, w, pt->dev));
+    if (w.rt.hashes) SHZ_TRY(hashes_out(ctx, w, pt->dev, rq.fan));
+    else SHZ_TRY(peaks_out(ctx, w, pt->dev));
   }
-  // The one read-back of the pass, into pinned memory: control block | per-clip offsets | for small host outputs the
-  // entries themselves (they ride along instead of costing a second round trip once the count is known).
-  pt->b_a = b_a;
-  pt->spec = one_block ? o_cap : 0;
-  pt->off_offs = one_block ? ob_offs : 256;
-  pt->off_a = one_block ? ob_a : pt->off_offs + (((uint64_t)(n_clips + 1) * 8 + 255) & ~255ull);
-  pt->off_b = one_block ? ob_b : pt->off_a;
-  void* mailp;
-  SHZ_TRY(shz_mailbox(ctx, pt->off_b + pt->spec * 4, &mailp));
-  pt->mp = (char*)mailp;
-  pt->o_a = o_a;
-  pt->o_b = o_b;
-  pt->o_cap = o_cap;
-  pt->n_clips = n_clips;
-  pt->out_dev = out_dev;
-  pt->want_hashes = want_hashes;
-  pt->stay = stay;
-  pt->d_fb = d_fb;
-  if (one_block) {
-    SHZ_HIP(ctx, hipMemcpyAsync(pt->mp, p_block, ob_bytes, hipMemcpyDeviceToHost, ctx->stream));
-  } else {
-    SHZ_HIP(ctx, hipMemcpyAsync(pt->mp, d_ctl, sizeof(xctl), hipMemcpyDeviceToHost, ctx->stream));
-    SHZ_HIP(ctx, hipMemcpyAsync(pt->mp + pt->off_offs, d_offs, (uint64_t)(n_clips + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
-  }
-  return SHZ_OK;
+  return queue_read_back(ctx, pt);
 }
 
-// wait for a queued pass; control block to *hctl, offsets to offs_out (n_clips + 1, may be null), host outputs copied
-static int32_t extract_finish(shz_ctx* ctx, const pass_tail& pt, uint16_t* peak_f, uint32_t* peak_t, uint32_t* key32,
-                              uint32_t* t1, uint64_t* offs_out, uint64_t cap, xctl* hctl) {
+// wait for a queued pass; control block to *hctl, offsets to out.offs (may be null), host outputs copied
+static int32_t extract_finish(shz_ctx* ctx, const pass_tail& pt, const xout& out, xctl* hctl) {
   SHZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
   memcpy(hctl, pt.mp, sizeof(xctl));
-  if (offs_out) memcpy(offs_out, pt.mp + pt.off_offs, (uint64_t)(pt.n_clips + 1) * 8);
-  const uint64_t total = pt.want_hashes ? hctl->hash_base : hctl->peak_base;
+  if (out.offs) memcpy(out.offs, pt.mp + pt.lay.offs, (uint64_t)(pt.n_clips + 1) * 8);
+  const uint64_t total = out.hashes ? hctl->hash_base : hctl->peak_base;
   const bool clean = !(hctl->flags & (XF_FALLBACK | XF_PEAK_CAP));   // (XF_FALLBACK_CLIP: the other clips' entries stand)
-  if (clean && !pt.out_dev && !pt.stay && total <= cap && total <= pt.o_cap && total) {
-    void* ha = pt.want_hashes ? (void*)key32 : (void*)peak_f;
-    void* hb = pt.want_hashes ? (void*)t1 : (void*)peak_t;
-    if (total <= pt.spec) {
-      memcpy(ha, pt.mp + pt.off_a, total * pt.b_a);
-      memcpy(hb, pt.mp + pt.off_b, total * 4);
+  if (clean && !pt.out_dev && !pt.stay && total <= out.cap && total <= pt.dev.o_cap && total) {
+    if (total <= pt.lay.spec) {
+      memcpy(out.a, pt.mp + pt.lay.a, total * out.b_a);
+      memcpy(out.b, pt.mp + pt.lay.b, total * 4);
     } else {
-      SHZ_HIP(ctx, shz_memcpy(ctx, ha, pt.o_a, total * pt.b_a, hipMemcpyDeviceToHost));
-      SHZ_HIP(ctx, shz_memcpy(ctx, hb, pt.o_b, total * 4, hipMemcpyDeviceToHost));
+      SHZ_HIP(ctx, shz_memcpy(ctx, out.a, pt.dev.o_a, total * out.b_a, hipMemcpyDeviceToHost));
+      SHZ_HIP(ctx, shz_memcpy(ctx, out.b, pt.dev.o_b, total * 4, hipMemcpyDeviceToHost));
       SHZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
   }
   return SHZ_OK;
 }
 
-static int32_t extract_pass(shz_ctx* ctx, const int16_t* pcm, const uint64_t* clip_off, uint32_t n_clips, uint32_t fs,
-                            double amp_min, uint32_t fan, uint32_t flags, bool want_hashes, const xparams& xp,
-                            uint16_t* peak_f, uint32_t* peak_t, uint32_t* key32, uint32_t* t1, uint64_t* offs_out,
-                            uint64_t cap, xctl* hctl, std::vector<uint32_t>* flagged_clips = nullptr) {
+// one pass, queued and waited for; *flagged = the clips marked XF_FALLBACK_CLIP
+static int32_t extract_pass(shz_ctx* ctx, const xreq& rq, const xout& out, const xparams& xp, xctl* hctl,
+                            std::vector<uint32_t>* flagged) {
   pass_tail pt;
-  SHZ_TRY(extract_enqueue(ctx, pcm, clip_off, n_clips, fs, amp_min, fan, flags, want_hashes, xp, peak_f, peak_t, key32, t1,
-                          cap, false, &pt));
-  SHZ_TRY(extract_finish(ctx, pt, peak_f, peak_t, key32, t1, offs_out, cap, hctl));
-  if (flagged_clips) {
-    flagged_clips->clear();
-    if (hctl->flags & XF_FALLBACK_CLIP) {   // which clips: the bitmap behind the control block (a second, small read-back; rare)
-      std::vector<uint32_t> bm(((uint64_t)n_clips + 31) / 32);
-      SHZ_HIP(ctx, shz_memcpy(ctx, bm.data(), pt.d_fb, bm.size() * 4, hipMemcpyDeviceToHost));
-      SHZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
-      for (uint32_t c = 0; c < n_clips; ++c)
-        if ((bm[c >> 5] >> (c & 31)) & 1u) flagged_clips->push_back(c);
-    }
+  SHZ_TRY(extract_enqueue(ctx, rq, out, xp, false, &pt));
+  SHZ_TRY(extract_finish(ctx, pt, out, hctl));
+  flagged->clear();
+  if (hctl->flags & XF_FALLBACK_CLIP) {   // which clips: the bitmap behind the control block (a second, small read-back; rare)
+    std::vector<uint32_t> bm(pt.lay.fb_words);
+    SHZ_HIP(ctx, shz_memcpy(ctx, bm.data(), pt.dev.fb, bm.size() * 4, hipMemcpyDeviceToHost));
+    SHZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (uint32_t c = 0; c < rq.n_clips; ++c)
+      if ((bm[c >> 5] >> (c & 31)) & 1u) flagged->push_back(c);
   }
   return SHZ_OK;
 }
 
-static int32_t extract_driver(shz_ctx* ctx, const int16_t* pcm, const uint64_t* clip_off, uint32_t n_clips, uint32_t fs,
-                              double amp_min, uint32_t fan, uint32_t flags, bool want_hashes, uint16_t* peak_f, uint32_t* peak_t,
-                              uint64_t* peak_off, uint32_t* key32, uint32_t* t1, uint64_t* hash_off, uint64_t cap, uint64_t* count);
+static int32_t extract_driver(shz_ctx* ctx, const xreq& rq, const xout& out_in, uint64_t* count);   // (splice_f64_clips re-runs clips through it)
 
-// The clips fp32 staging could not settle (windows with more than PV_MAX_NEAR tied cells: a click per hop, a full-scale
-// plateau) are fingerprinted again ONE BY ONE with fp64 staging, and their entries replace what the fp32 pass left for
-// them -- the other 999 clips of a batch keep the entries they have.  A (2 or 4 bytes per entry) and B are the output
-// arrays (device or host), offs the n_clips + 1 offsets of the fp32 pass; *total is updated.
-static int32_t splice_f64_clips(shz_ctx* ctx, const int16_t* pcm, const uint64_t* clip_off, uint32_t fs, double amp_min,
-                                uint32_t fan, uint32_t flags, bool want_hashes, const std::vector<uint32_t>& flagged, void* A,
-                                void* B, uint64_t* offs, uint32_t n_clips, uint64_t cap, uint64_t* total) {
-  const bool out_dev = (flags & SHZ_OUT_DEVICE) != 0;
-  const uint64_t b_a = want_hashes ? 4 : 2;
+// The final arrays after some clips were re-run, as a list of segments in output order: a stretch of the batch's own
+// entries, or the entries of re-run clip `redo` (kept in the list when it has none: its old entries still go).  `offs` are
+// the offsets that go with it, `peak` the largest running total when the clips are replaced one by one from the back.
+struct splice_seg { int redo; uint64_t first, count; };   // redo < 0: entries [first, first + count) of the batch
+struct splice_plan { std::vector<splice_seg> segs; std::vector<uint64_t> offs; uint64_t total, peak; };
+static splice_plan plan_splice(const std::vector<uint32_t>& flagged, const std::vector<uint64_t>& redo_cnt, const uint64_t* offs,
+                               uint32_t n_clips, uint64_t total) {
+  splice_plan p;
+  p.offs.resize((size_t)n_clips + 1);
+  uint64_t src = 0, delta = 0;   // entries of the old arrays consumed; new minus old offset (mod 2^64)
+  uint32_t i = 0;
+  for (size_t fi = 0; fi < flagged.size(); ++fi) {
+    const uint32_t c = flagged[fi];
+    if (offs[c] > src) p.segs.push_back(splice_seg{-1, src, offs[c] - src});
+    p.segs.push_back(splice_seg{(int)fi, 0, redo_cnt[fi]});
+    for (; i <= c; ++i) p.offs[i] = offs[i] + delta;
+    delta += redo_cnt[fi] - (offs[c + 1] - offs[c]);
+    src = offs[c + 1];
+  }
+  if (total > src) p.segs.push_back(splice_seg{-1, src, total - src});
+  for (; i <= n_clips; ++i) p.offs[i] = offs[i] + delta;
+  p.total = total + delta;
+  uint64_t running = total;
+  p.peak = total;
+  for (size_t fi = flagged.size(); fi-- > 0;) {
+    running = running - (offs[flagged[fi] + 1] - offs[flagged[fi]]) + redo_cnt[fi];
+    p.peak = std::max(p.peak, running);
+  }
+  return p;
+}
+
+// where a re-run clip's entries wait for the splice: parked at entry dev_at of the caller's device arrays, or in host vectors
+struct splice_redo { uint64_t dev_at = 0; std::vector<char> a; std::vector<uint32_t> b; };
+
+// Every flagged clip once more, with fp64 staging; cnt[i] = its new number of entries.  Device outputs: the clip's new
+// entries go straight behind the batch's entries in the caller's arrays (the room is there or the call ends in
+// SHZ_E_CAPACITY anyway); host outputs: to host vectors, sized by estimate and once more by the count if that was too
+// small.  SHZ_E_CAPACITY also when the result does not fit: *total = what the caller has to provide, else unchanged.
+static int32_t rerun_flagged(shz_ctx* ctx, const xreq& rq, const xout& out, const std::vector<uint32_t>& flagged,
+                             std::vector<splice_redo>& R, std::vector<uint64_t>& cnt, uint64_t* total) {
+  const bool out_dev = (rq.flags & SHZ_OUT_DEVICE) != 0;
+  const uint64_t b_a = out.b_a, cap = out.cap;
+  const uint64_t* offs = out.offs;
   const bool saved = ctx->stage_f64;
   struct restore { shz_ctx* c; bool v; ~restore() { c->stage_f64 = v; } } rs{ctx, saved};
-  struct redo { uint64_t cnt = 0, dev_at = 0; bool on_dev = false; std::vector<uint32_t> b, a32; std::vector<uint16_t> a16; };
-  std::vector<redo> R(flagged.size());
-  // 1) every flagged clip once more, fp64 staging.  Device outputs: the clip's new entries go straight behind the batch's
-  // entries in the caller's arrays (the room is there or the call ends in SHZ_E_CAPACITY anyway) and are moved into place on
-  // the device; host outputs: to host vectors.
   uint64_t new_total = *total, dev_end = *total;
   for (size_t fi = 0; fi < flagged.size(); ++fi) {
     const uint32_t c = flagged[fi];
-    redo& r = R[fi];
-    const uint64_t frames_c = frames_hop(clip_off[c + 1] - clip_off[c], ctx->hop);
-    uint64_t cap_c = frames_c * 64 * (want_hashes ? (fan > 1 ? fan - 1 : 1) : 1) + 4096;
+    splice_redo& r = R[fi];
+    const uint64_t frames_c = frames_hop(rq.clip_off[c + 1] - rq.clip_off[c], ctx->hop), old = offs[c + 1] - offs[c];
+    uint64_t cap_c = frames_c * 64 * (out.hashes ? (rq.fan > 1 ? rq.fan - 1 : 1) : 1) + 4096;
     uint64_t o2[2] = {0, 0};
-    if (out_dev) {
-      const uint64_t at = (dev_end + 63) & ~63ull;   // (16-byte aligned for 2- and 4-byte entries)
-      if (at < cap) {
-        ctx->stage_f64 = true;
-        const int32_t rc = extract_driver(ctx, pcm, clip_off + c, 1, fs, amp_min, fan, flags, want_hashes,
-                                          want_hashes ? nullptr : (uint16_t*)A + at, want_hashes ? nullptr : (uint32_t*)B + at,
-                                          want_hashes ? nullptr : o2, want_hashes ? (uint32_t*)A + at : nullptr,
-                                          want_hashes ? (uint32_t*)B + at : nullptr, want_hashes ? o2 : nullptr, cap - at, &r.cnt);
-        ctx->stage_f64 = saved;
-        if (rc == SHZ_OK) {
-          r.on_dev = true;
-          r.dev_at = at;
-          dev_end = at + r.cnt;
-          ++ctx->st_f64_clips;
-          ctx->st_f64_frames += frames_c;
-          new_total = new_total - (offs[c + 1] - offs[c]) + r.cnt;
-          continue;
+    xreq one = rq.clips(c, 1);
+    for (int attempt = 0;; ++attempt) {
+      xout o;
+      if (out_dev) {
+        r.dev_at = (dev_end + 63) & ~63ull;   // (16-byte aligned for 2- and 4-byte entries)
+        if (r.dev_at >= cap) {
+          *total = cap + cap_c;
+          SHZ_FAIL(ctx, SHZ_E_CAPACITY, "output needs more than %llu entries", (unsigned long long)cap);
         }
-        if (rc != SHZ_E_CAPACITY) return rc;
-        // no room behind the batch: what the caller has to provide is at least this
-        *total = std::max(new_total - (offs[c + 1] - offs[c]) + r.cnt, at + r.cnt);
+        o = out.at(r.dev_at, cap - r.dev_at, o2);
+      } else {
+        r.a.resize(cap_c * b_a);
+        r.b.resize(cap_c);
+        one.flags = rq.flags & ~SHZ_OUT_DEVICE;
+        o = xout{r.a.data(), b_a, r.b.data(), o2, cap_c, out.hashes};
+      }
+      ctx->stage_f64 = true;
+      const int32_t rc = extract_driver(ctx, one, o, &cnt[fi]);
+      ctx->stage_f64 = saved;
+      if (rc == SHZ_E_CAPACITY && out_dev) {   // no room behind the batch: what the caller has to provide is at least this
+        *total = std::max(new_total - old + cnt[fi], r.dev_at + cnt[fi]);
         SHZ_FAIL(ctx, SHZ_E_CAPACITY, "output needs at least %llu entries, capacity %llu", (unsigned long long)*total, (unsigned long long)cap);
       }
-      *total = cap + cap_c;
-      SHZ_FAIL(ctx, SHZ_E_CAPACITY, "output needs more than %llu entries", (unsigned long long)cap);
-    }
-    for (int attempt = 0;; ++attempt) {
-      r.b.resize(cap_c);
-      if (want_hashes) r.a32.resize(cap_c); else r.a16.resize(cap_c);
-      ctx->stage_f64 = true;
-      const int32_t rc = extract_driver(ctx, pcm, clip_off + c, 1, fs, amp_min, fan, flags & ~SHZ_OUT_DEVICE, want_hashes,
-                                        want_hashes ? nullptr : r.a16.data(), want_hashes ? nullptr : r.b.data(),
-                                        want_hashes ? nullptr : o2, want_hashes ? r.a32.data() : nullptr,
-                                        want_hashes ? r.b.data() : nullptr, want_hashes ? o2 : nullptr, cap_c, &r.cnt);
-      ctx->stage_f64 = saved;
-      if (rc == SHZ_E_CAPACITY && attempt == 0) { cap_c = r.cnt + 64; continue; }
+      if (rc == SHZ_E_CAPACITY && attempt == 0) { cap_c = cnt[fi] + 64; continue; }
       SHZ_TRY(rc);
       break;
     }
+    if (out_dev) dev_end = r.dev_at + cnt[fi];
     ++ctx->st_f64_clips;
     ctx->st_f64_frames += frames_c;
-    new_total = new_total - (offs[c + 1] - offs[c]) + r.cnt;
+    new_total = new_total - old + cnt[fi];
   }
-  // 2) room for the result?  (*total = what the caller has to provide)
   if (new_total > cap || (out_dev && dev_end > cap)) {
     *total = new_total;
     SHZ_FAIL(ctx, SHZ_E_CAPACITY, "output needs %llu entries, capacity %llu", (unsigned long long)new_total, (unsigned long long)cap);
   }
-  // 3) splice
+  return SHZ_OK;
+}
+
+// The clips fp32 staging could not settle (windows with more than PV_MAX_NEAR tied cells: a click per hop, a full-scale
+// plateau) are fingerprinted again ONE BY ONE with fp64 staging, and their entries replace what the fp32 pass left for
+// them -- the other 999 clips of a batch keep the entries they have.  out: the output arrays (device or host) and the
+// n_clips + 1 offsets of the fp32 pass; *total is updated (on SHZ_E_CAPACITY: what the caller has to provide).
+static int32_t splice_f64_clips(shz_ctx* ctx, const xreq& rq, const xout& out, const std::vector<uint32_t>& flagged, uint64_t* total) {
+  const bool out_dev = (rq.flags & SHZ_OUT_DEVICE) != 0;
+  const uint64_t b_a = out.b_a, cap = out.cap;
+  uint64_t* offs = out.offs;
+  std::vector<splice_redo> R(flagged.size());
+  std::vector<uint64_t> cnt(flagged.size(), 0);
+  SHZ_TRY(rerun_flagged(ctx, rq, out, flagged, R, cnt, total));
+  // one list of segments, executed for array a and array b
+  const splice_plan plan = plan_splice(flagged, cnt, offs, rq.n_clips, *total);
+  char* const arr[2] = {(char*)out.a, (char*)out.b};
+  const uint64_t bs[2] = {b_a, 4};
+  const auto redo_src = [&](int k, const splice_seg& s) -> const char* {
+    if (out_dev) return arr[k] + R[s.redo].dev_at * bs[k];
+    return k == 0 ? R[s.redo].a.data() : (const char*)R[s.redo].b.data();
+  };
   if (out_dev) {
     // the final arrays are put together in scratch -- the stretches between flagged clips from the batch's entries, a
     // flagged clip's entries from where they were parked -- and copied back: 2 |flagged| + 2 device copies per array
     void* tmp;
-    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_MISC3, std::max<uint64_t>(new_total, 1) * 4 + 64, &tmp));
-    for (int arr = 0; arr < 2; ++arr) {
-      char* base = arr == 0 ? (char*)A : (char*)B;
-      const uint64_t bs = arr == 0 ? b_a : 4;
-      uint64_t src = 0, dst = 0;   // entries of the old arrays consumed / of the new arrays written
-      for (size_t fi = 0; fi < flagged.size(); ++fi) {
-        const uint32_t c = flagged[fi];
-        const uint64_t keep = offs[c] - src;   // unflagged entries in front of the clip
-        if (keep) SHZ_HIP(ctx, hipMemcpyAsync((char*)tmp + dst * bs, base + src * bs, keep * bs, hipMemcpyDeviceToDevice, ctx->stream));
-        dst += keep;
-        if (R[fi].cnt) SHZ_HIP(ctx, hipMemcpyAsync((char*)tmp + dst * bs, base + R[fi].dev_at * bs, R[fi].cnt * bs, hipMemcpyDeviceToDevice, ctx->stream));
-        dst += R[fi].cnt;
-        src = offs[c + 1];
+    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_MISC3, std::max<uint64_t>(plan.total, 1) * 4 + 64, &tmp));
+    for (int k = 0; k < 2; ++k) {
+      uint64_t dst = 0;
+      for (const splice_seg& s : plan.segs) {
+        const char* from = s.redo < 0 ? arr[k] + s.first * bs[k] : redo_src(k, s);
+        if (s.count) SHZ_HIP(ctx, hipMemcpyAsync((char*)tmp + dst * bs[k], from, s.count * bs[k], hipMemcpyDeviceToDevice, ctx->stream));
+        dst += s.count;
       }
-      const uint64_t rest = *total - src;
-      if (rest) SHZ_HIP(ctx, hipMemcpyAsync((char*)tmp + dst * bs, base + src * bs, rest * bs, hipMemcpyDeviceToDevice, ctx->stream));
-      dst += rest;
-      if (dst) SHZ_HIP(ctx, hipMemcpyAsync(base, tmp, dst * bs, hipMemcpyDeviceToDevice, ctx->stream));
+      if (dst) SHZ_HIP(ctx, hipMemcpyAsync(arr[k], tmp, dst * bs[k], hipMemcpyDeviceToDevice, ctx->stream));
     }
     SHZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    for (size_t fi = flagged.size(); fi-- > 0;) {
-      const uint32_t c = flagged[fi];
-      const uint64_t old = offs[c + 1] - offs[c];
-      for (uint32_t i = c + 1; i <= n_clips; ++i) offs[i] = offs[i] - old + R[fi].cnt;
-    }
-    *total = new_total;
-    return SHZ_OK;
-  }
-  // host arrays.  Spliced in place from the back (the offsets in front of a clip stay what they are) -- unless an
-  // INTERMEDIATE total would outgrow the caller's arrays although the final one fits (a late clip grows by k, an early one
-  // shrinks by k: the first move writes total + k entries): then the result is put together in scratch, front to
-  // back, and copied over once.
-  {
-    uint64_t running = *total, peak = *total;
-    for (size_t fi = flagged.size(); fi-- > 0;) {
-      const uint32_t c = flagged[fi];
-      running = running - (offs[c + 1] - offs[c]) + R[fi].cnt;
-      peak = std::max(peak, running);
-    }
-    if (peak > cap) {
-      std::vector<char> na(new_total * b_a), nb(new_total * 4);
-      uint64_t src = 0, dst = 0;
-      for (size_t fi = 0; fi < flagged.size(); ++fi) {
-        const uint32_t c = flagged[fi];
-        const redo& r = R[fi];
-        const uint64_t keep = offs[c] - src;
-        if (keep) { memcpy(na.data() + dst * b_a, (char*)A + src * b_a, keep * b_a); memcpy(nb.data() + dst * 4, (char*)B + src * 4, keep * 4); }
-        dst += keep;
-        if (r.cnt) {
-          memcpy(na.data() + dst * b_a, want_hashes ? (const void*)r.a32.data() : (const void*)r.a16.data(), r.cnt * b_a);
-          memcpy(nb.data() + dst * 4, r.b.data(), r.cnt * 4);
-        }
-        dst += r.cnt;
-        src = offs[c + 1];
+  } else if (plan.peak > cap) {
+    // host arrays whose INTERMEDIATE total would outgrow them in place although the final one fits (a late clip grows by
+    // k, an early one shrinks by k: the first move writes total + k entries): the result is put together in
+    // scratch, front to back, and copied over once
+    for (int k = 0; k < 2; ++k) {
+      std::vector<char> tmp(plan.total * bs[k]);
+      uint64_t dst = 0;
+      for (const splice_seg& s : plan.segs) {
+        if (s.count) memcpy(tmp.data() + dst * bs[k], s.redo < 0 ? arr[k] + s.first * bs[k] : redo_src(k, s), s.count * bs[k]);
+        dst += s.count;
       }
-      const uint64_t rest = *total - src;
-      if (rest) { memcpy(na.data() + dst * b_a, (char*)A + src * b_a, rest * b_a); memcpy(nb.data() + dst * 4, (char*)B + src * 4, rest * 4); }
-      dst += rest;
-      if (dst) { memcpy(A, na.data(), dst * b_a); memcpy(B, nb.data(), dst * 4); }
-      for (size_t fi = flagged.size(); fi-- > 0;) {
-        const uint32_t c = flagged[fi];
-        const uint64_t old = offs[c + 1] - offs[c];
-        for (uint32_t i = c + 1; i <= n_clips; ++i) offs[i] = offs[i] - old + R[fi].cnt;
+      if (dst) memcpy(arr[k], tmp.data(), dst * bs[k]);
+    }
+  } else {
+    // host arrays, in place from the back: what lies behind a re-run clip (already final) moves as one piece to where the
+    // clip's new entries end, then these are copied in
+    for (int k = 0; k < 2; ++k) {
+      uint64_t behind = 0;   // entries of the final arrays behind the segment
+      for (size_t si = plan.segs.size(); si-- > 0; behind += plan.segs[si].count) {
+        const splice_seg& s = plan.segs[si];
+        if (s.redo < 0) continue;
+        const uint64_t old0 = offs[flagged[s.redo]], old1 = offs[flagged[s.redo] + 1];
+        if (s.count != old1 - old0 && behind) memmove(arr[k] + (old0 + s.count) * bs[k], arr[k] + old1 * bs[k], behind * bs[k]);
+        if (s.count) memcpy(arr[k] + old0 * bs[k], redo_src(k, s), s.count * bs[k]);
       }
-      *total = new_total;
-      return SHZ_OK;
     }
   }
-  for (size_t fi = flagged.size(); fi-- > 0;) {
-    const uint32_t c = flagged[fi];
-    const redo& r = R[fi];
-    const uint64_t cnt = r.cnt, old0 = offs[c], old1 = offs[c + 1], tail = *total - old1;
-    const void* src_a = want_hashes ? (const void*)r.a32.data() : (const void*)r.a16.data();
-    if (cnt != old1 - old0 && tail) {
-      memmove((char*)A + (old0 + cnt) * b_a, (char*)A + old1 * b_a, tail * b_a);
-      memmove((char*)B + (old0 + cnt) * 4, (char*)B + old1 * 4, tail * 4);
-    }
-    if (cnt) {
-      memcpy((char*)A + old0 * b_a, src_a, cnt * b_a);
-      memcpy((char*)B + old0 * 4, r.b.data(), cnt * 4);
-    }
-    for (uint32_t i = c + 1; i <= n_clips; ++i) offs[i] = offs[i] - (old1 - old0) + cnt;
-    *total = *total - (old1 - old0) + cnt;
+  memcpy(offs, plan.offs.data(), plan.offs.size() * 8);
+  *total = plan.total;
+  return SHZ_OK;
+}
+
+// Dual pass: the clips are cut in two halves by frames and each half runs as a pass of its own -- the first on this
+// context, the second on a twin context (own stream, own workspace) whose entries are appended behind the first
+// half's afterwards.  Two independent pipelines fill each other's stalls (STFT is VALU/LDS-bound, peak picking waits
+// on memory): 7.0 -> 6.48 ms on 1,000 x 30 s clips with the persistent STFT grid, which the stage-by-stage two-stream
+// pipeline did not reach (removed).
+// Opt-in (SHZ_DUAL=1): with the STFT in short-lived workgroups one pipeline reaches 6.62 ms per 1,000 x 30 s clips and
+// two reach 6.48-6.50 -- 2 % for twice the workspace and kernel durations that no longer mean one kernel's own time.
+// *done: the call is answered (SHZ_OK or SHZ_E_CAPACITY); anything else -- fp64 fallback, a list too small -- is sorted
+// out by the single pass of the caller.
+static int32_t extract_dual(shz_ctx* ctx, const xreq& rq, const xout& out, const xparams& xp, uint64_t frames, uint64_t* count,
+                            bool* done) {
+  uint32_t hc = 1;
+  for (uint64_t f = 0; hc < rq.n_clips - 1; ++hc) {
+    f += frames_hop(rq.clip_off[hc] - rq.clip_off[hc - 1], ctx->hop);
+    if (2 * f >= frames) break;
+  }
+  if (!ctx->twin) {
+    SHZ_TRY(shz_ctx_create(ctx->device, &ctx->twin));
+    SHZ_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_twin, hipEventDisableTiming));
+    // the caller's numpy window (shz_set_numpy_window) goes with it
+    SHZ_HIP(ctx, hipMemcpy(ctx->twin->d_np_window, ctx->d_np_window, sizeof(double) * SHZ_NFFT, hipMemcpyDeviceToDevice));
+    ctx->twin->np_sumsq = ctx->np_sumsq;
+    ctx->twin->np_unfused = ctx->np_unfused;
+  }
+  shz_ctx* tw = ctx->twin;
+  tw->ws_limit = ctx->ws_limit;
+  tw->profiling = ctx->profiling;
+  tw->hop = ctx->hop;
+  // the twin starts behind everything queued on this context's stream (the caller's PCM may still be in the making)
+  SHZ_HIP(ctx, hipEventRecord(ctx->ev_twin, ctx->stream));
+  SHZ_HIP(ctx, hipStreamWaitEvent(tw->stream, ctx->ev_twin, 0));
+  xparams xa = xp, xb = xp;
+  xa.persistent_stft = xb.persistent_stft = true;
+  uint64_t fb = 0;
+  for (uint32_t c = hc; c < rq.n_clips; ++c) fb += frames_hop(rq.clip_off[c + 1] - rq.clip_off[c], ctx->hop);
+  xa.stage_cap = std::min<uint64_t>(out.cap, stage_estimate(frames - fb, xp, out.hashes, rq.fan));
+  xb.stage_cap = stage_estimate(fb, xp, out.hashes, rq.fan);
+  pass_tail ta, tb;
+  xctl ha, hb;
+  std::vector<uint64_t> offs_b(rq.n_clips - hc + 1);
+  const xout out_b = {nullptr, out.b_a, nullptr, offs_b.data(), 0, out.hashes};   // (stays in the twin's staging arrays)
+  int32_t rc = extract_enqueue(ctx, rq.clips(0, hc), out, xa, false, &ta);
+  int32_t rcb = rc == SHZ_OK ? extract_enqueue(tw, rq.clips(hc, rq.n_clips - hc), out_b, xb, true, &tb) : SHZ_OK;
+  if (rc == SHZ_OK) rc = extract_finish(ctx, ta, out, &ha);
+  if (rcb == SHZ_OK && rc == SHZ_OK) rcb = extract_finish(tw, tb, out_b, &hb);
+  (void)hipStreamSynchronize(tw->stream);   // whatever happened, nothing of the twin is in flight past this point
+  if (rcb != SHZ_OK && rc == SHZ_OK) { ctx->err = tw->err; rc = rcb; }
+  SHZ_TRY(rc);
+  ctx->st_und += ha.und_total + hb.und_total;
+  ctx->st_und_f64 += ha.und_f64 + hb.und_f64;
+  ctx->st_und_ffts += ha.und_ffts + hb.und_ffts;
+  const uint64_t na = out.hashes ? ha.hash_base : ha.peak_base, nb = out.hashes ? hb.hash_base : hb.peak_base;
+  const bool clean = !((ha.flags | hb.flags) & (XF_FALLBACK | XF_PEAK_CAP | XF_FALLBACK_CLIP)) && nb <= tb.dev.o_cap &&
+                     ((rq.flags & SHZ_OUT_DEVICE) || na <= ta.dev.o_cap || na > out.cap);
+  if (!clean) return SHZ_OK;
+  *done = true;
+  if (out.offs)
+    for (uint32_t c = hc; c < rq.n_clips; ++c) out.offs[c + 1] = na + offs_b[c - hc + 1];
+  if (count) *count = na + nb;
+  if (na + nb > out.cap) SHZ_FAIL(ctx, SHZ_E_CAPACITY, "output needs %llu entries, capacity %llu", (unsigned long long)(na + nb),
+                                  (unsigned long long)out.cap);
+  if (nb) {   // the second half's entries go behind the first half's
+    const hipMemcpyKind kd = (rq.flags & SHZ_OUT_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    const xout behind = out.at(na, out.cap - na, nullptr);
+    SHZ_HIP(ctx, shz_memcpy(ctx, behind.a, tb.dev.o_a, nb * out.b_a, kd));
+    SHZ_HIP(ctx, shz_memcpy(ctx, behind.b, tb.dev.o_b, nb * 4, kd));
+    if (kd == hipMemcpyDeviceToHost) SHZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
   }
   return SHZ_OK;
 }
 
-// shared driver for shz_peaks / shz_fingerprint_batch
-static int32_t extract_driver(shz_ctx* ctx, const int16_t* pcm, const uint64_t* clip_off, uint32_t n_clips, uint32_t fs,
-                              double amp_min, uint32_t fan, uint32_t flags, bool want_hashes,
-                              // peaks outputs
-                              uint16_t* peak_f, uint32_t* peak_t, uint64_t* peak_off,
-                              // hash outputs
-                              uint32_t* key32, uint32_t* t1, uint64_t* hash_off, uint64_t cap, uint64_t* count) {
-  SHZ_TRY(check_common(ctx, pcm, clip_off, n_clips, fs));
-  if (want_hashes && (fan < 1 || fan > 64)) SHZ_FAIL(ctx, SHZ_E_INVALID, "fan_value must be in [1,64]");
-  uint64_t* offs = want_hashes ? hash_off : peak_off;
-  if (offs) offs[0] = 0;
+// After a pass: does it have to be repeated with other sizes or with fp64 staging?  xp is updated for the next one.
+static bool pass_again(shz_ctx* ctx, const xreq& rq, const xout& out, xctl& h, size_t n_flagged, uint64_t frames, int attempt,
+                       xparams* xp) {
+  const uint64_t total = out.hashes ? h.hash_base : h.peak_base;
+  const bool out_dev = (rq.flags & SHZ_OUT_DEVICE) != 0;
+  bool again = false;
+  // many clips flagged: one fp64 pass over everything is cheaper than a pass per clip
+  if (xp->f32 && n_flagged > std::max<size_t>(8, rq.n_clips / 16)) h.flags |= XF_FALLBACK;
+  if (xp->f32 && (h.flags & XF_FALLBACK)) {  // stationary / plateau material: decide on fp64 values
+    xp->f32 = false;
+    ++ctx->st_fallbacks;
+    again = true;
+  }
+  if (h.flags & XF_PEAK_CAP) {
+    // a sub-batch had more peaks than estimated: size the lists for the densest one seen (per frame of the smallest
+    // sub-batch it could have been: all of them hold >= 64 frames or the whole call)
+    const uint64_t f_min = std::min<uint64_t>(frames, 64);
+    xp->peaks_per_frame = (uint32_t)std::min<uint64_t>(SHZ_NBINS, h.max_sub_peaks / f_min + 1);
+    if (attempt >= 1) xp->peaks_per_frame = SHZ_NBINS;  // every cell a peak: the bound
+    again = true;
+  }
+  if (!again && !out_dev && total > xp->stage_cap && total <= out.cap) {
+    xp->stage_cap = total;  // staging estimate too small, caller's arrays are not
+    again = true;
+  }
+  if (again && !out_dev)
+    xp->stage_cap = std::max(xp->stage_cap, std::min<uint64_t>(out.cap, stage_estimate(frames, *xp, out.hashes, rq.fan)));
+  return again;
+}
+
+// shared driver for shz_peaks / shz_fingerprint_batch: size, optional dual pass, pass-and-resize loop, splice
+static int32_t extract_driver(shz_ctx* ctx, const xreq& rq, const xout& out_in, uint64_t* count) {
+  SHZ_TRY(check_common(ctx, rq.pcm, rq.clip_off, rq.n_clips, rq.fs));
+  if (out_in.hashes && (rq.fan < 1 || rq.fan > 64)) SHZ_FAIL(ctx, SHZ_E_INVALID, "fan_value must be in [1,64]");
+  xout out = out_in;
+  if (out.offs) out.offs[0] = 0;
   if (count) *count = 0;
-  if (n_clips == 0) return SHZ_OK;
+  if (rq.n_clips == 0) return SHZ_OK;
   uint64_t frames = 0;
-  for (uint32_t c = 0; c < n_clips; ++c) frames += frames_hop(clip_off[c + 1] - clip_off[c], ctx->hop);
+  for (uint32_t c = 0; c < rq.n_clips; ++c) frames += frames_hop(rq.clip_off[c + 1] - rq.clip_off[c], ctx->hop);
   xparams xp;
   // fp32 staging needs the threshold to be a positive normal fp32 power well inside the range; amp_min < 0 also needs
   // the zero-plateau rule (peak_zero_plateau_kernel), which reads the fp64 array
-  xp.f32 = !ctx->stage_f64 && amp_min >= 0.0 && amp_min <= 300.0;
+  xp.f32 = !ctx->stage_f64 && rq.amp_min >= 0.0 && rq.amp_min <= 300.0;
   xp.peaks_per_frame = 12;                                      // 4.6 per frame on noise and music-like input
-  const uint64_t per_frame_out = want_hashes ? (uint64_t)xp.peaks_per_frame * (fan > 1 ? fan - 1 : 0) : xp.peaks_per_frame;
-  xp.stage_cap = std::min<uint64_t>(cap, frames * per_frame_out + 4096);
-  xctl h;
-  // Dual pass: the clips are cut in two halves by frames and each half runs as a pass of its own -- the first on this
-  // context, the second on a twin context (own stream, own workspace) whose entries are appended behind the first
-  // half's afterwards.  Two independent pipelines fill each other's stalls (STFT is VALU/LDS-bound, peak picking waits
-  // on memory): 7.0 -> 6.48 ms on 1,000 x 30 s clips with the persistent STFT grid, which the stage-by-stage two-stream
-  // pipeline did not reach (removed).
-  // Opt-in (SHZ_DUAL=1): with the STFT in short-lived workgroups one pipeline reaches 6.62 ms per 1,000 x 30 s clips and
-  // two reach 6.48-6.50 -- 2 % for twice the workspace and kernel durations that no longer mean one kernel's own time.
+  xp.stage_cap = std::min<uint64_t>(out.cap, stage_estimate(frames, xp, out.hashes, rq.fan));
   static const bool dual_on = [] { const char* e = getenv("SHZ_DUAL"); return e && atoi(e) != 0; }();
-  if (dual_on && n_clips >= 2 && frames >= 131072) {
-    uint32_t hc = 1;
-    for (uint64_t f = 0; hc < n_clips - 1; ++hc) {
-      f += frames_hop(clip_off[hc] - clip_off[hc - 1], ctx->hop);
-      if (2 * f >= frames) break;
-    }
-    if (!ctx->twin) {
-      SHZ_TRY(shz_ctx_create(ctx->device, &ctx->twin));
-      SHZ_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_twin, hipEventDisableTiming));
-      // the caller's numpy window (shz_set_numpy_window) goes with it
-      SHZ_HIP(ctx, hipMemcpy(ctx->twin->d_np_window, ctx->d_np_window, sizeof(double) * SHZ_NFFT, hipMemcpyDeviceToDevice));
-      ctx->twin->np_sumsq = ctx->np_sumsq;
-      ctx->twin->np_unfused = ctx->np_unfused;
-    }
-    shz_ctx* tw = ctx->twin;
-    tw->ws_limit = ctx->ws_limit;
-    tw->profiling = ctx->profiling;
-    tw->hop = ctx->hop;
-    // the twin starts behind everything queued on this context's stream (the caller's PCM may still be in the making)
-    SHZ_HIP(ctx, hipEventRecord(ctx->ev_twin, ctx->stream));
-    SHZ_HIP(ctx, hipStreamWaitEvent(tw->stream, ctx->ev_twin, 0));
-    xparams xa = xp, xb = xp;
-    xa.persistent_stft = xb.persistent_stft = true;
-    uint64_t fb = 0;
-    for (uint32_t c = hc; c < n_clips; ++c) fb += frames_hop(clip_off[c + 1] - clip_off[c], ctx->hop);
-    xa.stage_cap = std::min<uint64_t>(cap, (frames - fb) * per_frame_out + 4096);
-    xb.stage_cap = fb * per_frame_out + 4096;
-    pass_tail ta, tb;
-    xctl ha, hb;
-    std::vector<uint64_t> offs_b(n_clips - hc + 1);
-    int32_t rc = extract_enqueue(ctx, pcm, clip_off, hc, fs, amp_min, fan, flags, want_hashes, xa, peak_f, peak_t, key32, t1,
-                                 cap, false, &ta);
-    int32_t rcb = rc == SHZ_OK ? extract_enqueue(tw, pcm, clip_off + hc, n_clips - hc, fs, amp_min, fan, flags, want_hashes, xb,
-                                                 nullptr, nullptr, nullptr, nullptr, 0, true, &tb)
-                               : SHZ_OK;
-    if (rc == SHZ_OK) rc = extract_finish(ctx, ta, peak_f, peak_t, key32, t1, offs, cap, &ha);
-    if (rcb == SHZ_OK && rc == SHZ_OK) rcb = extract_finish(tw, tb, nullptr, nullptr, nullptr, nullptr, offs_b.data(), 0, &hb);
-    (void)hipStreamSynchronize(tw->stream);   // whatever happened, nothing of the twin is in flight past this point
-    if (rcb != SHZ_OK && rc == SHZ_OK) { ctx->err = tw->err; rc = rcb; }
-    SHZ_TRY(rc);
-    ctx->st_und += ha.und_total + hb.und_total;
-    ctx->st_und_f64 += ha.und_f64 + hb.und_f64;
-    ctx->st_und_ffts += ha.und_ffts + hb.und_ffts;
-    const uint64_t na = want_hashes ? ha.hash_base : ha.peak_base, nb = want_hashes ? hb.hash_base : hb.peak_base;
-    const bool clean = !((ha.flags | hb.flags) & (XF_FALLBACK | XF_PEAK_CAP | XF_FALLBACK_CLIP)) && nb <= tb.o_cap &&
-                       ((flags & SHZ_OUT_DEVICE) || na <= ta.o_cap || na > cap);
-    if (clean) {   // (anything else -- fp64 fallback, a list too small -- is sorted out by the single pass below)
-      if (offs)
-        for (uint32_t c = hc; c < n_clips; ++c) offs[c + 1] = na + offs_b[c - hc + 1];
-      if (count) *count = na + nb;
-      if (na + nb > cap) SHZ_FAIL(ctx, SHZ_E_CAPACITY, "output needs %llu entries, capacity %llu", (unsigned long long)(na + nb),
-                                  (unsigned long long)cap);
-      if (nb) {   // the second half's entries go behind the first half's
-        const hipMemcpyKind kd = (flags & SHZ_OUT_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-        char* da = want_hashes ? (char*)key32 : (char*)peak_f;
-        char* db = want_hashes ? (char*)t1 : (char*)peak_t;
-        SHZ_HIP(ctx, shz_memcpy(ctx, da + na * tb.b_a, tb.o_a, nb * tb.b_a, kd));
-        SHZ_HIP(ctx, shz_memcpy(ctx, db + na * 4, tb.o_b, nb * 4, kd));
-        if (kd == hipMemcpyDeviceToHost) SHZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
-      }
-      return SHZ_OK;
-    }
+  if (dual_on && rq.n_clips >= 2 && frames >= 131072) {
+    bool done = false;
+    SHZ_TRY(extract_dual(ctx, rq, out, xp, frames, count, &done));
+    if (done) return SHZ_OK;
   }
   std::vector<uint64_t> offs_own;   // the per-clip fallback needs the offsets whether the caller wants them or not
-  if (!offs) { offs_own.assign((size_t)n_clips + 1, 0); offs = offs_own.data(); }
+  if (!out.offs) { offs_own.assign((size_t)rq.n_clips + 1, 0); out.offs = offs_own.data(); }
   std::vector<uint32_t> flagged;
+  xctl h;
   for (int attempt = 0;; ++attempt) {
     static const bool xtrace = getenv("SHZ_TRACE_EXTRACT") != nullptr;
-    if (xtrace) fprintf(stderr, "extract: pass attempt %d clips %u f32 %d\n", attempt, n_clips, (int)xp.f32);
-    SHZ_TRY(extract_pass(ctx, pcm, clip_off, n_clips, fs, amp_min, fan, flags, want_hashes, xp, peak_f, peak_t, key32, t1,
-                         offs, cap, &h, &flagged));
+    if (xtrace) fprintf(stderr, "extract: pass attempt %d clips %u f32 %d\n", attempt, rq.n_clips, (int)xp.f32);
+    SHZ_TRY(extract_pass(ctx, rq, out, xp, &h, &flagged));
     if (xtrace) fprintf(stderr, "extract: pass done flags %u flagged %zu und %llu\n", h.flags, flagged.size(), (unsigned long long)h.und_total);
     ctx->st_und += h.und_total;
     ctx->st_und_f64 += h.und_f64;
     ctx->st_und_ffts += h.und_ffts;
-    uint64_t total = want_hashes ? h.hash_base : h.peak_base;
-    bool again = false;
-    // many clips flagged: one fp64 pass over everything is cheaper than a pass per clip
-    if (xp.f32 && !flagged.empty() && flagged.size() > std::max<size_t>(8, n_clips / 16)) h.flags |= XF_FALLBACK;
-    if (xp.f32 && (h.flags & XF_FALLBACK)) {  // stationary / plateau material: decide on fp64 values
-      xp.f32 = false;
-      ++ctx->st_fallbacks;
-      again = true;
-    }
-    if (h.flags & XF_PEAK_CAP) {
-      // a sub-batch had more peaks than estimated: size the lists for the densest one seen (per frame of the smallest
-      // sub-batch it could have been: all of them hold >= 64 frames or the whole call)
-      const uint64_t f_min = std::min<uint64_t>(frames, 64);
-      xp.peaks_per_frame = (uint32_t)std::min<uint64_t>(SHZ_NBINS, h.max_sub_peaks / f_min + 1);
-      if (attempt >= 1) xp.peaks_per_frame = SHZ_NBINS;  // every cell a peak: the bound
-      again = true;
-    }
-    if (!again && !(flags & SHZ_OUT_DEVICE) && total > xp.stage_cap && total <= cap) {
-      xp.stage_cap = total;  // staging estimate too small, caller's arrays are not
-      again = true;
-    }
-    if (again) {
-      if (attempt >= 4) SHZ_FAIL(ctx, SHZ_E_STATE, "extract: no stable sizing after %d passes", attempt + 1);
-      if (!(flags & SHZ_OUT_DEVICE))
-        xp.stage_cap = std::max(xp.stage_cap, std::min<uint64_t>(cap, frames * (uint64_t)xp.peaks_per_frame *
-                                                                          (want_hashes ? (fan > 1 ? fan - 1 : 0) : 1) + 4096));
-      continue;
-    }
-    if (count) *count = total;
-    if (total > cap) SHZ_FAIL(ctx, SHZ_E_CAPACITY, "output needs %llu entries, capacity %llu", (unsigned long long)total,
-                              (unsigned long long)cap);
-    if (xp.f32 && !flagged.empty()) {
-      const int32_t rc = splice_f64_clips(ctx, pcm, clip_off, fs, amp_min, fan, flags, want_hashes, flagged,
-                                          want_hashes ? (void*)key32 : (void*)peak_f, want_hashes ? (void*)t1 : (void*)peak_t, offs,
-                                          n_clips, cap, &total);
-      if (count) *count = total;   // (on SHZ_E_CAPACITY: what the caller has to provide)
-      SHZ_TRY(rc);
-    }
-    return SHZ_OK;
+    if (!pass_again(ctx, rq, out, h, flagged.size(), frames, attempt, &xp)) break;
+    if (attempt >= 4) SHZ_FAIL(ctx, SHZ_E_STATE, "extract: no stable sizing after %d passes", attempt + 1);
   }
+  uint64_t total = out.hashes ? h.hash_base : h.peak_base;
+  if (count) *count = total;
+  if (total > out.cap) SHZ_FAIL(ctx, SHZ_E_CAPACITY, "output needs %llu entries, capacity %llu", (unsigned long long)total,
+                                (unsigned long long)out.cap);
+  if (xp.f32 && !flagged.empty()) {
+    const int32_t rc = splice_f64_clips(ctx, rq, out, flagged, &total);
+    if (count) *count = total;   // (on SHZ_E_CAPACITY: what the caller has to provide)
+    SHZ_TRY(rc);
+  }
+  return SHZ_OK;
 }
 
 // ---- host-fed streaming --------------------------------------------------------------------------------------------
@@ -2379,11 +2464,12 @@ static int32_t extract_driver(shz_ctx* ctx, const int16_t* pcm, const uint64_t* 
                                        // reached 87 % of the link, the 2.2 ms of the first one and the pass of the last one exposed)
 #define UP_MIN_BYTES (192ull << 20)   // smaller batches: one copy, one pass (the pipeline's two buffers and thread buy nothing)
 
-static int32_t extract_streamed(shz_ctx* ctx, const int16_t* pcm, const uint64_t* clip_off, uint32_t n_clips, uint32_t fs,
-                                double amp_min, uint32_t fan, uint32_t flags, bool want_hashes, uint16_t* peak_f, uint32_t* peak_t,
-                                uint64_t* peak_off, uint32_t* key32, uint32_t* t1, uint64_t* hash_off, uint64_t cap, uint64_t* count) {
-  SHZ_TRY(check_common(ctx, pcm, clip_off, n_clips, fs));
-  uint64_t* offs = want_hashes ? hash_off : peak_off;
+static int32_t extract_streamed(shz_ctx* ctx, const xreq& rq, const xout& out, uint64_t* count) {
+  const int16_t* pcm = rq.pcm;
+  const uint64_t *clip_off = rq.clip_off, cap = out.cap;
+  const uint32_t n_clips = rq.n_clips;
+  SHZ_TRY(check_common(ctx, pcm, clip_off, n_clips, rq.fs));
+  uint64_t* offs = out.offs;
   // chunks of whole clips
   struct chunk { uint32_t c0, c1; };
   std::vector<chunk> chunks;
@@ -2452,9 +2538,8 @@ static int32_t extract_streamed(shz_ctx* ctx, const int16_t* pcm, const uint64_t
     coff.assign(nc + 1, 0);
     uint64_t cnt = 0;
     const uint64_t room = short_cap || total > cap ? 0 : cap - total;
-    const int32_t rc = extract_driver(ctx, (const int16_t*)dbuf[i & 1], rel.data(), nc, fs, amp_min, fan, flags | SHZ_PCM_DEVICE, want_hashes,
-                                      peak_f ? peak_f + total : nullptr, peak_t ? peak_t + total : nullptr, want_hashes ? nullptr : coff.data(),
-                                      key32 ? key32 + total : nullptr, t1 ? t1 + total : nullptr, want_hashes ? coff.data() : nullptr, room, &cnt);
+    const xreq chunk_rq = {(const int16_t*)dbuf[i & 1], rel.data(), nc, rq.fs, rq.amp_min, rq.fan, rq.flags | SHZ_PCM_DEVICE};
+    const int32_t rc = extract_driver(ctx, chunk_rq, out.at(total, room, coff.data()), &cnt);
     if (rc == SHZ_E_CAPACITY) short_cap = true;   // the chunks that follow are only counted: the caller learns what to provide
     else if (rc != SHZ_OK) return rc;
     if (offs && !short_cap)
@@ -2475,18 +2560,13 @@ static int32_t extract_streamed(shz_ctx* ctx, const int16_t* pcm, const uint64_t
 }
 
 // host PCM of a size worth pipelining -> extract_streamed; everything else -> one pass
-static int32_t extract_any(shz_ctx* ctx, const int16_t* pcm, const uint64_t* clip_off, uint32_t n_clips, uint32_t fs,
-                           double amp_min, uint32_t fan, uint32_t flags, bool want_hashes, uint16_t* peak_f, uint32_t* peak_t,
-                           uint64_t* peak_off, uint32_t* key32, uint32_t* t1, uint64_t* hash_off, uint64_t cap, uint64_t* count) {
-  if (ctx && pcm && clip_off && !(flags & SHZ_PCM_DEVICE) && n_clips >= 2) {
+static int32_t extract_any(shz_ctx* ctx, const xreq& rq, const xout& out, uint64_t* count) {
+  if (ctx && rq.pcm && rq.clip_off && !(rq.flags & SHZ_PCM_DEVICE) && rq.n_clips >= 2) {
     bool ok = true;
-    for (uint32_t c = 0; c < n_clips && ok; ++c) ok = clip_off[c + 1] >= clip_off[c];
-    if (ok && (clip_off[n_clips] - clip_off[0]) * 2 >= UP_MIN_BYTES)
-      return extract_streamed(ctx, pcm, clip_off, n_clips, fs, amp_min, fan, flags, want_hashes, peak_f, peak_t, peak_off, key32, t1,
-                              hash_off, cap, count);
+    for (uint32_t c = 0; c < rq.n_clips && ok; ++c) ok = rq.clip_off[c + 1] >= rq.clip_off[c];
+    if (ok && (rq.clip_off[rq.n_clips] - rq.clip_off[0]) * 2 >= UP_MIN_BYTES) return extract_streamed(ctx, rq, out, count);
   }
-  return extract_driver(ctx, pcm, clip_off, n_clips, fs, amp_min, fan, flags, want_hashes, peak_f, peak_t, peak_off, key32, t1, hash_off,
-                        cap, count);
+  return extract_driver(ctx, rq, out, count);
 }
 
 extern "C" int32_t shz_upload_stats(shz_ctx* ctx, uint64_t* chunks, uint64_t* bytes, double* copy_s, double* wait_s) {
@@ -2527,16 +2607,14 @@ extern "C" int32_t shz_extract_stats(shz_ctx* ctx, uint64_t* undecided, uint64_t
 extern "C" int32_t shz_peaks(shz_ctx* ctx, const int16_t* pcm, const uint64_t* clip_off, uint32_t n_clips, uint32_t fs,
                              double amp_min, uint32_t flags, uint16_t* peak_f, uint32_t* peak_t, uint64_t* peak_off,
                              uint64_t cap, uint64_t* count) {
-  return extract_any(ctx, pcm, clip_off, n_clips, fs, amp_min, 0, flags, false, peak_f, peak_t, peak_off, nullptr,
-                     nullptr, nullptr, cap, count);
+  return extract_any(ctx, xreq{pcm, clip_off, n_clips, fs, amp_min, 0, flags}, xout{peak_f, 2, peak_t, peak_off, cap, false}, count);
 }
 
 extern "C" int32_t shz_fingerprint_batch(shz_ctx* ctx, const int16_t* pcm, const uint64_t* clip_off, uint32_t n_clips,
                                          uint32_t fs, double amp_min, uint32_t fan_value, uint32_t flags,
                                          uint32_t* key32, uint32_t* t1, uint64_t* hash_off, uint64_t cap,
                                          uint64_t* count) {
-  return extract_any(ctx, pcm, clip_off, n_clips, fs, amp_min, fan_value, flags, true, nullptr, nullptr, nullptr,
-                     key32, t1, hash_off, cap, count);
+  return extract_any(ctx, xreq{pcm, clip_off, n_clips, fs, amp_min, fan_value, flags}, xout{key32, 4, t1, hash_off, cap, true}, count);
 }
 
 extern "C" int32_t shz_peaks_from_db(shz_ctx* ctx, const double* arr2d, uint32_t n_rows, uint32_t n_cols,
@@ -2570,16 +2648,16 @@ extern "C" int32_t shz_peaks_from_db(shz_ctx* ctx, const double* arr2d, uint32_t
   SHZ_HIP(ctx, shz_memcpy(ctx, sd.d_foff, foff, 8, hipMemcpyHostToDevice));
   SHZ_HIP(ctx, shz_memcpy(ctx, sd.d_segs, segs.data(), segs.size() * sizeof(peak_seg), hipMemcpyHostToDevice));
   SHZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  uint16_t* d_pf;
-  uint32_t *d_pt, *d_pcoff, n_peaks;
-  SHZ_TRY(run_peaks(ctx, (const double*)d_db, stride, n_rows, sd, 1, n_cols, amp_min, false, &d_pf, &d_pt, &d_pcoff, &n_peaks));
+  peak_lists pl;
+  SHZ_TRY(run_peaks(ctx, f64_source{(const double*)d_db, stride, n_rows, false}, sd, 1, n_cols, amp_min, &pl));
+  const uint32_t n_peaks = pl.cap;
   if (count) *count = n_peaks;
   if (n_peaks > cap) SHZ_FAIL(ctx, SHZ_E_CAPACITY, "need %u peaks", n_peaks);
   if (!n_peaks) return SHZ_OK;
   std::vector<uint16_t> pf(n_peaks);
   std::vector<uint32_t> pt(n_peaks), idx(n_peaks);
-  SHZ_HIP(ctx, shz_memcpy(ctx, pf.data(), d_pf, (uint64_t)n_peaks * 2, hipMemcpyDeviceToHost));
-  SHZ_HIP(ctx, shz_memcpy(ctx, pt.data(), d_pt, (uint64_t)n_peaks * 4, hipMemcpyDeviceToHost));
+  SHZ_HIP(ctx, shz_memcpy(ctx, pf.data(), pl.pf, (uint64_t)n_peaks * 2, hipMemcpyDeviceToHost));
+  SHZ_HIP(ctx, shz_memcpy(ctx, pt.data(), pl.pt, (uint64_t)n_peaks * 4, hipMemcpyDeviceToHost));
   SHZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
   // device order is (t asc, f asc); np.where order is (f asc, t asc): stable re-sort by f
   for (uint32_t i = 0; i < n_peaks; ++i) idx[i] = i;
@@ -2618,8 +2696,8 @@ extern "C" int32_t shz_pair_hash(shz_ctx* ctx, const uint16_t* peak_f, const uin
   SHZ_HIP(ctx, shz_memcpy(ctx, pc, pco.data(), (uint64_t)(n_clips + 1) * 4, hipMemcpyHostToDevice));
   uint64_t n_h = 0;
   std::vector<uint32_t> choff;
-  SHZ_TRY(run_pairs(ctx, (const uint16_t*)pf, (const uint32_t*)pt, (const uint32_t*)pc, n_clips, (uint32_t)n, fan_value,
-                    (uint32_t*)pk, (uint32_t*)pt1, 0, upper, &n_h, &choff));
+  SHZ_TRY(run_pairs(ctx, peak_lists{(uint16_t*)pf, (uint32_t*)pt, (uint32_t*)pc, (uint32_t)n}, n_clips, fan_value,
+                    hash_dest{(uint32_t*)pk, (uint32_t*)pt1, 0, nullptr, upper}, &n_h, &choff));
   if (hash_off)
     for (uint32_t c = 0; c < n_clips; ++c) hash_off[c + 1] = choff[c + 1];
   if (count) *count = n_h;
