@@ -353,6 +353,9 @@ uint64_t shz_recognize_estimate(uint64_t frames, uint32_t fan_value);
  * to 65,536 (run cut, shz_table_set_run_rows clamp, segment cut, the size check of an exchange round), so that tests reach
  * the cuts at the limit with few rows.  Set it before the table's first call; every rank of a gathered build alike. */
 #define SHZ_DEBUG_RUN_LIMIT_SMALL 4u
+/* Test switch of shz_scan_batch: a group of windows handed to the match holds at most 3 windows, so that tests reach the
+ * group borders with tiny inputs (results do not depend on the grouping). */
+#define SHZ_DEBUG_SCAN_SMALL_GROUPS 8u
 int32_t shz_set_debug(shz_ctx* ctx, uint32_t flags);
 int32_t shz_match_vt_redo(shz_ctx* ctx, uint64_t* count);
 /* A single query of at most 8,192 hashes handed over in host memory has its vote kernels queued before the number of its
@@ -550,6 +553,53 @@ int32_t shz_listener_window(const uint64_t* settled, uint32_t channels, uint32_t
 int32_t shz_resample_i16(shz_ctx* ctx, const int16_t* pcm, const uint64_t* clip_off, uint32_t n_clips, uint32_t L, uint32_t M,
                          uint32_t T, const int32_t* taps, const uint64_t* in_base, const uint64_t* m_first, const uint64_t* m_end,
                          uint32_t flags, int16_t* out, uint64_t* out_off, uint64_t cap, uint64_t* count);
+
+/* ---- scanning long recordings (new; the monitoring loop around recognize(), recognizer.py:357-392 -- record a stretch,
+ * fingerprint every channel, union the hashes, match, align -- for every overlapping stretch of a recording at once) -----
+ * "Which songs play in this recording, and when?"  Every recording is fingerprinted ONCE; its device-resident hash list is
+ * cut into overlapping time windows and all windows are matched together (hashes come out in generation order,
+ * recognizer.py:100-114: t1 never decreases inside a clip, so a window is a contiguous range of each channel's list).
+ * Recording r owns the adjacent clips (its channels) [rec_clip0[r], rec_clip0[r + 1]), as query_clip0 of
+ * shz_recognize_batch; F_r = the largest shz_frame_count_hop of its channels at the ctx's hop.  It has W_r =
+ * shz_scan_window_count(F_r, ...) windows: 0 without clips, 1 if F_r <= window_frames, else
+ * ceil((F_r - window_frames) / step_frames) + 1.  Window w starts at frame s = w step_frames; its query is the set, over all
+ * channels of the recording, of (key32, t1 - s) for the hashes with s <= t1 < s + window_frames, and the result of the scan
+ * is shz_match_batch on exactly those queries: the seven arrays, windows recording-major, win_off[n_recs + 1] their CSR
+ * (written whenever the arguments are valid, also with SHZ_E_CAPACITY).
+ * EDGES: a window's hashes are a SUBSET of the whole recording's hashes.  They are not what fingerprinting the cut audio
+ * would give: a peak near a cut is judged against its neighbours beyond the cut, a pair whose anchor lies in the window
+ * counts although its partner lies behind the window's end, and one whose anchor lies in front of it does not.
+ * window_frames >= F_r: the one window is the whole recording and the arrays are shz_recognize_batch's.
+ * Refused before anything is launched: rec_clip0 / clip_off that are not as for shz_recognize_batch, window_frames of 0 or
+ * >= 2^20 (the query offsets of the match), step_frames of 0, topn outside [1, 64] (SHZ_E_INVALID), a table that is not
+ * finalized (SHZ_E_STATE), cap_windows (the room of the outputs, in windows) below the total: SHZ_E_CAPACITY with *count =
+ * the total, which follows from the frame counts alone.  flags: SHZ_PCM_DEVICE, SHZ_MATCH_FULL_SORT.  Windows go to the
+ * match in groups whose replicated columns fit 1/8 of the workspace limit (shz_set_workspace_limit); a group never splits a
+ * window and the results do not depend on the grouping (SHZ_DEBUG_SCAN_SMALL_GROUPS).  A recording is extracted in one
+ * pass: one of more than 2^20 frames is refused as shz_fingerprint_batch refuses it.  ms_extract / ms_window / ms_match
+ * (may be NULL): hipEvent times of the extraction, of cutting the windows (bounds, scan, read-back, gathers) and of the
+ * matches.  out_nhash / out_npairs may be NULL. */
+uint64_t shz_scan_window_count(uint64_t frames, uint32_t window_frames, uint32_t step_frames);   /* no GPU, no ctx; frames 0: 0 */
+int32_t shz_scan_batch(shz_ctx* ctx, shz_table* t, const int16_t* pcm, const uint64_t* clip_off, uint32_t n_clips,
+                       const uint32_t* rec_clip0, uint32_t n_recs, uint32_t fs, double amp_min, uint32_t fan_value,
+                       uint32_t window_frames, uint32_t step_frames, uint32_t topn, uint32_t flags, uint64_t* win_off,
+                       uint32_t* out_sid, int32_t* out_delta, uint32_t* out_aligned, uint32_t* out_dedup, uint32_t* out_nres,
+                       uint32_t* out_nhash, uint64_t* out_npairs, uint64_t cap_windows, uint64_t* count, float* ms_extract,
+                       float* ms_window, float* ms_match);
+/* The timeline of a scan (no GPU, no ctx): the rank-0 answers folded into segments.  Inputs: win_off and out_sid / out_delta /
+ * out_aligned (stride topn, rank 0 is read) / out_nres of shz_scan_batch.  Window w of a recording (w counts from the
+ * recording's first window) is a HIT iff nres >= 1 and its rank-0 aligned >= min_aligned; its identity is (sid, shift),
+ * shift = delta - w step_frames in 64 bits: song frame minus recording frame, constant while one song plays.  The windows
+ * of a recording are visited in order with one open segment: a hit with the open segment's identity and
+ * w - w_last - 1 <= max_gap extends it; any other hit closes it and opens a new one; a window without a hit changes
+ * nothing; the recording's end closes it.  Per segment (recording-major, in order): recording, sid, shift, first and last
+ * window, hit windows, largest aligned count.  Two-call idiom: more than cap segments: SHZ_E_CAPACITY, *count = their
+ * number, the first cap are written (cap = 0: the seg_* pointers may be NULL). */
+int32_t shz_scan_timeline(const uint64_t* win_off, uint32_t n_recs, const uint32_t* out_sid, const int32_t* out_delta,
+                          const uint32_t* out_aligned, const uint32_t* out_nres, uint32_t topn, uint32_t step_frames,
+                          uint32_t min_aligned, uint32_t max_gap, uint32_t* seg_rec, uint32_t* seg_sid, int64_t* seg_shift,
+                          uint32_t* seg_first, uint32_t* seg_last, uint32_t* seg_hits, uint32_t* seg_best, uint64_t cap,
+                          uint64_t* count);
 
 #ifdef __cplusplus
 }

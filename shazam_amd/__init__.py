@@ -347,3 +347,5 @@ def recognize(channels_or_samples, db=None, Fs: int = RATE, topn: int = TOPN, fu
 from .stream import StreamFingerprinter, StreamRecognizer, fingerprint_stream  # noqa: E402,F401
 # sample-rate conversion (csrc/shz_resample.hip): audio at any rate against a table at another
 from .resample import StreamResampler, resample_batch, resample_plan, resample_to_device  # noqa: E402,F401
+# long recordings (csrc/shz_scan.hip): every window of a recording matched in one call, and the timeline of its songs
+from .scan import scan, scan_windows  # noqa: E402,F401

@@ -13,7 +13,7 @@ LIB_PATH = os.environ.get("SHZ_LIB") or os.path.join(_HERE, "libshz.so")  # SHZ_
 OK, E_INVALID, E_HIP, E_CAPACITY, E_NOMEM, E_UNSUPPORTED, E_RCCL, E_STATE = 0, -1, -2, -3, -4, -5, -6, -7
 PCM_DEVICE, OUT_DEVICE, IN_DEVICE, STFT_POWER, MATCH_FULL_SORT, RESERVE_GATHER, RESERVE_WAIT = 1, 2, 4, 8, 16, 32, 64
 # shz_set_debug test switches (include/shz.h); RUN_ROWS_MAX[_SMALL]: the most rows a run / a segment cut from runs holds
-DEBUG_VT_TINY_HEAVY, DEBUG_VT_PROBE1, DEBUG_RUN_LIMIT_SMALL = 1, 2, 4
+DEBUG_VT_TINY_HEAVY, DEBUG_VT_PROBE1, DEBUG_RUN_LIMIT_SMALL, DEBUG_SCAN_SMALL_GROUPS = 1, 2, 4, 8
 RUN_ROWS_MAX, RUN_ROWS_MAX_SMALL = (1 << 32) - 4096, 65536
 NFFT, HOP, NBINS = 4096, 2048, 2049
 
@@ -135,6 +135,12 @@ SIGNATURES = {
     "shz_listener_window": (C.c_int32, [u64p, C.c_uint32, C.c_uint32, u64p, u64p]),
     "shz_resample_i16": (C.c_int32, [vp, vp, u64p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.c_uint32,
                                      vp, u64p, C.c_uint64, u64p]),
+    "shz_scan_window_count": (C.c_uint64, [C.c_uint64, C.c_uint32, C.c_uint32]),
+    "shz_scan_batch": (C.c_int32, [vp, vp, vp, u64p, C.c_uint32, u32p, C.c_uint32, C.c_uint32, C.c_double, C.c_uint32,
+                                   C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, u64p, vp, vp, vp, vp, vp, vp, vp, C.c_uint64,
+                                   u64p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "shz_scan_timeline": (C.c_int32, [u64p, C.c_uint32, vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                      vp, vp, vp, vp, vp, vp, vp, C.c_uint64, u64p]),
 }
 
 
@@ -272,7 +278,7 @@ class Context:
 
     def set_debug(self, flags: int):
         """SHZ_DEBUG_* test switches (1: tiny hand-over list, 2: LDS probes give up after one round, 4: runs and segments cut
-        from runs hold at most RUN_ROWS_MAX_SMALL rows)."""
+        from runs hold at most RUN_ROWS_MAX_SMALL rows, 8: shz_scan_batch matches its windows in groups of at most 3)."""
         self.check(lib().shz_set_debug(self.h, int(flags)))
 
     def vt_redo_count(self) -> int:
@@ -565,6 +571,35 @@ class Context:
                                              ptr(res["nres"]), ptr(res["nhash"]), ptr(res["npairs"]), C.byref(me), C.byref(mm)))
         return res, float(me.value), float(mm.value)
 
+    def scan_batch(self, table: "Table", pcm, clip_off, rec_clip0, window_frames, step_frames, fs=44100, amp_min=10.0,
+                   fan_value=5, topn=2, pcm_device=False, full_sort=False, cap_windows=None):
+        """shz_scan_batch: fingerprint the clips once and match every window of recording r = clips [rec_clip0[r],
+        rec_clip0[r + 1]) in one call.  Returns (res, win_off, ms): res as Table.match over all windows, recording-major,
+        win_off their CSR over the recordings, ms = (extract, window, match) device times.  cap_windows: the room handed
+        to the library (default: what the frame counts give); too little raises E_CAPACITY, the total in the message."""
+        co, nc = self._clip_off(clip_off)
+        rc0 = np.ascontiguousarray(rec_clip0, np.uint32)
+        nr = len(rc0) - 1
+        flags = (PCM_DEVICE if pcm_device else 0) | (MATCH_FULL_SORT if full_sort else 0)
+        wo, cnt = np.zeros(nr + 1, np.uint64), C.c_uint64()
+        ms = [C.c_float(), C.c_float(), C.c_float()]
+
+        def call(res, cap):
+            return lib().shz_scan_batch(self.h, table.h, ptr(pcm), co.ctypes.data_as(u64p), nc, rc0.ctypes.data_as(u32p), nr,
+                                        int(fs), float(amp_min), int(fan_value), int(window_frames), int(step_frames), int(topn),
+                                        flags, wo.ctypes.data_as(u64p), ptr(res["sid"]), ptr(res["delta"]), ptr(res["aligned"]),
+                                        ptr(res["dedup"]), ptr(res["nres"]), ptr(res["nhash"]), ptr(res["npairs"]), int(cap),
+                                        C.byref(cnt), *[C.byref(m) for m in ms])
+        if cap_windows is None:   # the two-call idiom: the first call launches nothing and names the total
+            rc = call(_match_result(0, topn), 0)
+            if rc != E_CAPACITY:
+                self.check(rc)
+            cap_windows = int(cnt.value)
+        res = _match_result(int(cap_windows), topn)
+        self.check(call(res, cap_windows))
+        n = int(cnt.value)
+        return {k: v[:n] for k, v in res.items()}, wo, tuple(float(m.value) for m in ms)
+
     def resample_raw(self, pcm, clip_off, L, M, T, taps, in_base=None, m_first=None, m_end=None, pcm_device=False,
                      out: DevBuf = None, cap=None):
         """One shz_resample_i16 as it is: (rc, out, out_off, count) without retrying.  taps: int32 [L, T] in Q30.  With `out`
@@ -641,6 +676,42 @@ def _match_result(nq: int, topn: int) -> dict:
 def recognize_estimate(frames: int, fan_value: int = 5) -> int:
     """shz_recognize_estimate (host only): entries the first extraction pass of the fused call has room for."""
     return int(lib().shz_recognize_estimate(int(frames), int(fan_value)))
+
+
+def scan_window_count(frames: int, window_frames: int, step_frames: int) -> int:
+    """shz_scan_window_count (host only): windows of a recording of `frames` frames (0 frames: no clips, no window)."""
+    return int(lib().shz_scan_window_count(int(frames), int(window_frames), int(step_frames)))
+
+
+SEGMENT_FIELDS = (("rec", np.uint32), ("sid", np.uint32), ("shift", np.int64), ("first", np.uint32), ("last", np.uint32),
+                  ("hits", np.uint32), ("best", np.uint32))
+
+
+def scan_timeline_raw(win_off, sid, delta, aligned, nres, step_frames, min_aligned, max_gap=1, cap=0):
+    """One shz_scan_timeline as it is (host only): (rc, segments, count) with room for `cap` segments."""
+    wo = np.ascontiguousarray(win_off, np.uint64)
+    sid, delta, aligned = (np.ascontiguousarray(a, d) for a, d in ((sid, np.uint32), (delta, np.int32), (aligned, np.uint32)))
+    nres = np.ascontiguousarray(nres, np.uint32)
+    nw = len(nres)
+    topn = 1 if sid.ndim == 1 else int(sid.shape[1])
+    assert sid.shape == delta.shape == aligned.shape and sid.size == nw * topn and int(wo[-1]) - int(wo[0]) <= nw
+    seg = {k: np.zeros(int(cap), d) for k, d in SEGMENT_FIELDS}
+    cnt = C.c_uint64()
+    rc = lib().shz_scan_timeline(wo.ctypes.data_as(u64p), len(wo) - 1, ptr(sid), ptr(delta), ptr(aligned), ptr(nres), topn,
+                                 int(step_frames), int(min_aligned), int(max_gap),
+                                 *[ptr(seg[k]) if cap else None for k, _ in SEGMENT_FIELDS], int(cap), C.byref(cnt))
+    return rc, seg, int(cnt.value)
+
+
+def scan_timeline(win_off, sid, delta, aligned, nres, step_frames, min_aligned, max_gap=1) -> dict:
+    """shz_scan_timeline (host only, two calls): the rank-0 answers of a scan folded into segments -- arrays rec, sid, shift
+    (song frame - recording frame), first / last (windows of the recording), hits, best (largest aligned count)."""
+    rc, seg, n = scan_timeline_raw(win_off, sid, delta, aligned, nres, step_frames, min_aligned, max_gap, 0)
+    if rc == E_CAPACITY:
+        rc, seg, n = scan_timeline_raw(win_off, sid, delta, aligned, nres, step_frames, min_aligned, max_gap, n)
+    if rc != OK:
+        raise ShzError(rc, "shz_scan_timeline: bad arguments")
+    return seg
 
 
 class Table:

@@ -368,6 +368,8 @@ extern "C" int32_t shz_ctx_destroy(shz_ctx* ctx) {
   }
   for (hipEvent_t e : ctx->rq_ev)
     if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : ctx->sc_ev)
+    if (e) (void)hipEventDestroy(e);
   if (ctx->tev_init)
     for (auto& e : ctx->tev) {
       (void)hipEventDestroy(e[0]);

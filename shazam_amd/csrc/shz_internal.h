@@ -80,7 +80,10 @@ enum {
   SHZ_WS_VT4,        // table of the vote passes
   SHZ_WS_VT5,        // sub-group of every expand chunk's first vote (expand by sort blocks)
   SHZ_WS_VT6,        // the bar of every query of a vote pass (vt_stream2_kernel)
-  SHZ_WS_RQ_KEY, SHZ_WS_RQ_T1,   // hashes of shz_recognize_batch between its extraction and its match (neither reserves them)
+  SHZ_WS_RQ_KEY, SHZ_WS_RQ_T1,   // hashes of shz_recognize_batch / shz_scan_batch between their extraction and their match (neither reserves them)
+  SHZ_WS_SC_JOBS,    // shz_scan_batch: (window, channel) jobs | window jobs | hash_off of the clips
+  SHZ_WS_SC_CTL,     // ... first entry | count | offset of every (window, channel), the total behind the offsets
+  SHZ_WS_SC_KEY, SHZ_WS_SC_QO,   // ... the windows of one group: key32 and t1 - window start, window-major
   SHZ_WS_COUNT
 };
 
@@ -109,6 +112,7 @@ struct shz_ctx {
   hipEvent_t tev[16][2];
   bool tev_init = false;
   hipEvent_t rq_ev[3] = {nullptr, nullptr, nullptr};   // shz_recognize_batch: start, extraction done, match done (created on first use)
+  hipEvent_t sc_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // shz_scan_batch: start, extraction done, a group's gather begun / done, its match done (created on first use)
   bool profiling = false;
   float kernel_ms[8] = {0};
   uint32_t kernel_launches[8] = {0};
@@ -211,6 +215,14 @@ int32_t shz_match_device(shz_ctx* ctx, shz_table* t, const uint32_t* d_key32, co
                          int32_t* out_delta, uint32_t* out_aligned, uint32_t* out_dedup, uint32_t* out_nres, uint32_t* out_nhash,
                          uint64_t* out_npairs);
 int32_t shz_match_ready(shz_ctx* ctx, shz_table* t, uint32_t topn);
+
+// ---- extraction into buffers the library owns (shz_recognize.hip) ------------------------------
+// shz_fingerprint_batch of the clips into the slots SHZ_WS_RQ_KEY / SHZ_WS_RQ_T1, sized from the frame counts
+// (shz_recognize_estimate) and repeated with the room the pass asked for: *d_key / *d_t1 are the columns, hash_off[n_clips + 1]
+// (host) their CSR.  flags: SHZ_PCM_DEVICE.  who: the caller's name, for messages.  No clips: nothing runs, hash_off[0] = 0.
+int32_t shz_extract_owned(shz_ctx* ctx, const char* who, const int16_t* pcm, const uint64_t* clip_off, uint32_t n_clips,
+                          uint32_t fs, double amp_min, uint32_t fan_value, uint32_t flags, uint64_t* hash_off,
+                          const uint32_t** d_key, const uint32_t** d_t1);
 
 // ---- RCCL helpers (shz_comm.hip) ----------------------------------------------------------
 int32_t shz_comm_info(shz_comm* c, int* rank, int* nranks);

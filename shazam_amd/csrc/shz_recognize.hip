@@ -10,6 +10,44 @@
 
 #include "shz_internal.h"
 
+// The extraction half of the fused calls (shz_recognize_batch, shz_scan_batch): the hashes go to the slots SHZ_WS_RQ_KEY /
+// SHZ_WS_RQ_T1, sized from the frame counts (what the extraction pass itself estimates: 12 peaks a frame with all their
+// partners); the pass's SHZ_E_CAPACITY names the size that is enough
+int32_t shz_extract_owned(shz_ctx* ctx, const char* who, const int16_t* pcm, const uint64_t* clip_off, uint32_t n_clips,
+                          uint32_t fs, double amp_min, uint32_t fan_value, uint32_t flags, uint64_t* hash_off,
+                          const uint32_t** d_key_out, const uint32_t** d_t1_out) {
+  *d_key_out = *d_t1_out = nullptr;
+  hash_off[0] = 0;
+  if (n_clips == 0) return SHZ_OK;
+  uint64_t frames = 0;
+  for (uint32_t c = 0; c < n_clips; ++c) frames += shz_frame_count_hop(clip_off[c + 1] - clip_off[c], ctx->hop);
+  void *d_key = nullptr, *d_t1 = nullptr;
+  uint64_t cap = shz_recognize_estimate(frames, fan_value);
+  // (slots that an earlier, larger call has grown are used whole: no pass is repeated for room that is there)
+  const uint64_t have = std::min(ctx->ws[SHZ_WS_RQ_KEY].cap, ctx->ws[SHZ_WS_RQ_T1].cap);
+  if (have > 64) cap = std::max(cap, (have - 64) / 4);
+  for (int attempt = 0;; ++attempt) {
+    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_RQ_KEY, cap * 4 + 64, &d_key));
+    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_RQ_T1, cap * 4 + 64, &d_t1));
+    uint64_t count = 0;
+    const int32_t rc = shz_fingerprint_batch(ctx, pcm, clip_off, n_clips, fs, amp_min, fan_value,
+                                             (flags & SHZ_PCM_DEVICE) | SHZ_OUT_DEVICE, (uint32_t*)d_key, (uint32_t*)d_t1,
+                                             hash_off, cap, &count);
+    if (rc == SHZ_E_CAPACITY && attempt < 2 && count > cap) {
+      // twice what the pass counted: the per-clip fp64 splice parks a redone clip's entries behind the batch's before it
+      // moves them into place, so one repeat is enough whichever clips are redone (a second one is the safety net)
+      cap = 2 * count + 4096;
+      continue;
+    }
+    if (rc == SHZ_E_CAPACITY) SHZ_FAIL(ctx, SHZ_E_STATE, "%s: the extraction needs %llu entries after it was given %llu", who, (unsigned long long)count, (unsigned long long)cap);
+    SHZ_TRY(rc);
+    break;
+  }
+  *d_key_out = (const uint32_t*)d_key;
+  *d_t1_out = (const uint32_t*)d_t1;
+  return SHZ_OK;
+}
+
 extern "C" int32_t shz_recognize_batch(shz_ctx* ctx, shz_table* t, const int16_t* pcm, const uint64_t* clip_off, uint32_t n_clips,
                                        const uint32_t* query_clip0, uint32_t n_queries, uint32_t fs, double amp_min,
                                        uint32_t fan_value, uint32_t topn, uint32_t flags, uint32_t* out_sid, int32_t* out_delta,
@@ -43,43 +81,18 @@ extern "C" int32_t shz_recognize_batch(shz_ctx* ctx, shz_table* t, const int16_t
       if (!e) SHZ_HIP(ctx, hipEventCreate(&e));
     SHZ_HIP(ctx, hipEventRecord(ctx->rq_ev[0], ctx->stream));
   }
-  // 1) extraction into the library's own buffers, sized from the frame counts (what the extraction pass itself
-  // estimates: 12 peaks a frame with all their partners); its SHZ_E_CAPACITY names the size that is enough
-  uint64_t frames = 0, max_frames = 1;
-  for (uint32_t c = 0; c < n_clips; ++c) {
-    const uint64_t f = shz_frame_count_hop(clip_off[c + 1] - clip_off[c], ctx->hop);
-    frames += f;
-    max_frames = std::max(max_frames, f);
-  }
+  // 1) extraction into the library's own buffers
+  uint64_t max_frames = 1;
+  for (uint32_t c = 0; c < n_clips; ++c)
+    max_frames = std::max<uint64_t>(max_frames, shz_frame_count_hop(clip_off[c + 1] - clip_off[c], ctx->hop));
   std::vector<uint64_t> hash_off((size_t)n_clips + 1, 0), query_off((size_t)n_queries + 1, 0);
-  void *d_key = nullptr, *d_t1 = nullptr;
-  if (n_clips) {
-    uint64_t cap = shz_recognize_estimate(frames, fan_value);
-    // (slots that an earlier, larger call has grown are used whole: no pass is repeated for room that is there)
-    const uint64_t have = std::min(ctx->ws[SHZ_WS_RQ_KEY].cap, ctx->ws[SHZ_WS_RQ_T1].cap);
-    if (have > 64) cap = std::max(cap, (have - 64) / 4);
-    for (int attempt = 0;; ++attempt) {
-      SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_RQ_KEY, cap * 4 + 64, &d_key));
-      SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_RQ_T1, cap * 4 + 64, &d_t1));
-      uint64_t count = 0;
-      const int32_t rc = shz_fingerprint_batch(ctx, pcm, clip_off, n_clips, fs, amp_min, fan_value,
-                                               (flags & SHZ_PCM_DEVICE) | SHZ_OUT_DEVICE, (uint32_t*)d_key, (uint32_t*)d_t1,
-                                               hash_off.data(), cap, &count);
-      if (rc == SHZ_E_CAPACITY && attempt < 2 && count > cap) {
-        // twice what the pass counted: the per-clip fp64 splice parks a redone clip's entries behind the batch's before it
-        // moves them into place, so one repeat is enough whichever clips are redone (a second one is the safety net)
-        cap = 2 * count + 4096;
-        continue;
-      }
-      if (rc == SHZ_E_CAPACITY) SHZ_FAIL(ctx, SHZ_E_STATE, "shz_recognize_batch: the extraction needs %llu entries after it was given %llu", (unsigned long long)count, (unsigned long long)cap);
-      SHZ_TRY(rc);
-      break;
-    }
-  }
+  const uint32_t *d_key = nullptr, *d_t1 = nullptr;
+  SHZ_TRY(shz_extract_owned(ctx, "shz_recognize_batch", pcm, clip_off, n_clips, fs, amp_min, fan_value, flags & SHZ_PCM_DEVICE,
+                            hash_off.data(), &d_key, &d_t1));
   if (timed) SHZ_HIP(ctx, hipEventRecord(ctx->rq_ev[1], ctx->stream));
   // 2) the match on those buffers
   for (uint32_t q = 0; q <= n_queries; ++q) query_off[q] = hash_off[query_clip0[q]];
-  SHZ_TRY(shz_match_device(ctx, t, (const uint32_t*)d_key, (const uint32_t*)d_t1, query_off.data(), n_queries, topn,
+  SHZ_TRY(shz_match_device(ctx, t, d_key, d_t1, query_off.data(), n_queries, topn,
                            flags & SHZ_MATCH_FULL_SORT, (int64_t)max_frames - 1, out_sid, out_delta, out_aligned, out_dedup, out_nres,
                            out_nhash, out_npairs));
   if (timed) {

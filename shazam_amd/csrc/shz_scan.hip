@@ -1,0 +1,285 @@
+// Scanning long recordings (the loop a monitor puts around recognize(), recognizer.py:357-392: record a stretch, fingerprint
+// every channel, union the hashes, match, align -- here for every overlapping stretch of a recording at once): each recording
+// is fingerprinted ONCE, its device-resident hash list is cut into overlapping time windows, and all windows are matched
+// together, recording-major.
+//
+// Within a clip the hashes come out in generation order: peaks sorted by time, t1 the anchor's time (recognizer.py:100-114),
+// so t1 never decreases and the hashes of window [s, s + window_frames) are one contiguous range of every channel's list --
+// two lower-bound searches.  A window's query is the union over the recording's channels of (key32, t1 - s): what `offset`
+// means for a clip recorded from frame s, as the listeners have it.  The windows' columns are replicated ceil(window / step)
+// times, so they are written group by group into two slots and each group is matched where it lies.
+#include <algorithm>
+
+#include "shz_internal.h"
+
+#define SC_THREADS 256
+#define SC_SMALL_GROUP 3u   // windows of a group under SHZ_DEBUG_SCAN_SMALL_GROUPS
+
+struct sc_pair { uint32_t clip, s; };                 // one channel of one window: its clip, the window's first frame
+struct sc_win { uint64_t pair0; uint32_t nch, s; };   // one window: its first (window, channel) pair, its channels, its first frame
+
+extern "C" uint64_t shz_scan_window_count(uint64_t frames, uint32_t window_frames, uint32_t step_frames) {
+  if (frames == 0 || window_frames == 0 || step_frames == 0) return 0;
+  if (frames <= window_frames) return 1;
+  return (frames - window_frames + step_frames - 1) / step_frames + 1;
+}
+
+// first index in [a, b) whose t1 is >= v (t1 does not decrease inside a clip)
+__device__ __forceinline__ uint64_t sc_lower_bound(const uint32_t* __restrict__ t1, uint64_t a, uint64_t b, uint64_t v) {
+  while (a < b) {
+    const uint64_t mid = a + ((b - a) >> 1);
+    if ((uint64_t)t1[mid] < v) a = mid + 1; else b = mid;
+  }
+  return a;
+}
+
+// per (window, channel): where the window's hashes begin in the channel's list, and how many they are
+__global__ __launch_bounds__(SC_THREADS) void scan_bounds_kernel(const sc_pair* __restrict__ pairs, uint64_t n_pairs,
+                                                                 const uint64_t* __restrict__ hash_off, const uint32_t* __restrict__ t1,
+                                                                 uint32_t window_frames, uint64_t* __restrict__ first,
+                                                                 uint64_t* __restrict__ cnt) {
+  const uint64_t p = (uint64_t)blockIdx.x * SC_THREADS + threadIdx.x;
+  if (p >= n_pairs) return;
+  const sc_pair j = pairs[p];
+  const uint64_t a = hash_off[j.clip], b = hash_off[j.clip + 1];
+  const uint64_t lo = sc_lower_bound(t1, a, b, j.s);
+  const uint64_t hi = sc_lower_bound(t1, lo, b, (uint64_t)j.s + window_frames);
+  first[p] = lo;
+  cnt[p] = hi - lo;
+}
+
+// one workgroup per window of the group [w0, w0 + gridDim.x): its channels' ranges, one behind the other, to
+// offs[pair] - base of the group's columns (offs: exclusive scan of the counts, the total behind it)
+__global__ __launch_bounds__(SC_THREADS) void scan_gather_kernel(const sc_win* __restrict__ wins, uint64_t w0,
+                                                                 const uint64_t* __restrict__ first, const uint64_t* __restrict__ offs,
+                                                                 uint64_t base, uint64_t cap, const uint32_t* __restrict__ key,
+                                                                 const uint32_t* __restrict__ t1, uint32_t* __restrict__ out_key,
+                                                                 uint32_t* __restrict__ out_qo) {
+  const sc_win w = wins[w0 + blockIdx.x];
+  for (uint32_t c = 0; c < w.nch; ++c) {
+    const uint64_t p = w.pair0 + c;
+    const uint64_t src = first[p], dst = offs[p] - base, n = offs[p + 1] - offs[p];
+    if (dst + n > cap) return;   // (uniform; the host sizes the columns from the same offsets, so this never holds)
+    for (uint64_t i = threadIdx.x; i < n; i += SC_THREADS) {
+      out_key[dst + i] = key[src + i];
+      out_qo[dst + i] = t1[src + i] - w.s;
+    }
+  }
+}
+
+extern "C" int32_t shz_scan_batch(shz_ctx* ctx, shz_table* t, const int16_t* pcm, const uint64_t* clip_off, uint32_t n_clips,
+                                  const uint32_t* rec_clip0, uint32_t n_recs, uint32_t fs, double amp_min, uint32_t fan_value,
+                                  uint32_t window_frames, uint32_t step_frames, uint32_t topn, uint32_t flags, uint64_t* win_off,
+                                  uint32_t* out_sid, int32_t* out_delta, uint32_t* out_aligned, uint32_t* out_dedup,
+                                  uint32_t* out_nres, uint32_t* out_nhash, uint64_t* out_npairs, uint64_t cap_windows,
+                                  uint64_t* count, float* ms_extract, float* ms_window, float* ms_match) {
+  if (!ctx || !t) return SHZ_E_INVALID;
+  if (ms_extract) *ms_extract = 0.f;
+  if (ms_window) *ms_window = 0.f;
+  if (ms_match) *ms_match = 0.f;
+  if (count) *count = 0;
+  // everything that can be refused is refused before the first launch
+  if (flags & ~(SHZ_PCM_DEVICE | SHZ_MATCH_FULL_SORT)) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_scan_batch: flags may hold SHZ_PCM_DEVICE and SHZ_MATCH_FULL_SORT");
+  if (!win_off || !count) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_scan_batch: win_off or count is NULL");
+  if (window_frames == 0 || window_frames >= (1u << 20))
+    SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_scan_batch: window_frames must be in [1, 2^20) (query offsets), got %u", window_frames);
+  if (step_frames == 0) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_scan_batch: step_frames must be at least 1");
+  if (fan_value < 1 || fan_value > 64) SHZ_FAIL(ctx, SHZ_E_INVALID, "fan_value must be in [1,64]");
+  win_off[0] = 0;
+  if (n_recs == 0) {
+    if (n_clips) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_scan_batch: %u clips belong to no recording", n_clips);
+    return SHZ_OK;
+  }
+  if (!rec_clip0) SHZ_FAIL(ctx, SHZ_E_INVALID, "rec_clip0 is NULL");
+  if (rec_clip0[0] != 0 || rec_clip0[n_recs] != n_clips)
+    SHZ_FAIL(ctx, SHZ_E_INVALID, "rec_clip0 must start at 0 and end at n_clips = %u (it runs from %u to %u)", n_clips, rec_clip0[0],
+             rec_clip0[n_recs]);
+  for (uint32_t r = 0; r < n_recs; ++r)
+    if (rec_clip0[r + 1] < rec_clip0[r]) SHZ_FAIL(ctx, SHZ_E_INVALID, "rec_clip0 decreases at recording %u", r);
+  if (!clip_off) SHZ_FAIL(ctx, SHZ_E_INVALID, "clip_off is NULL");
+  for (uint32_t c = 0; c < n_clips; ++c)
+    if (clip_off[c + 1] < clip_off[c]) SHZ_FAIL(ctx, SHZ_E_INVALID, "clip_off decreases at clip %u", c);
+  SHZ_TRY(shz_match_ready(ctx, t, topn));
+  // the windows: their number follows from the frame counts alone
+  uint64_t n_wins = 0, n_pairs = 0;
+  for (uint32_t r = 0; r < n_recs; ++r) {
+    uint64_t f = 0;
+    for (uint32_t c = rec_clip0[r]; c < rec_clip0[r + 1]; ++c)
+      f = std::max<uint64_t>(f, shz_frame_count_hop(clip_off[c + 1] - clip_off[c], ctx->hop));
+    const uint64_t w = shz_scan_window_count(f, window_frames, step_frames);
+    n_wins += w;
+    n_pairs += w * (rec_clip0[r + 1] - rec_clip0[r]);
+    win_off[r + 1] = n_wins;
+  }
+  *count = n_wins;
+  if (n_wins > cap_windows)
+    SHZ_FAIL(ctx, SHZ_E_CAPACITY, "shz_scan_batch: %llu windows, room for %llu", (unsigned long long)n_wins, (unsigned long long)cap_windows);
+  if (n_wins == 0) return SHZ_OK;
+  if (!out_sid || !out_delta || !out_aligned || !out_dedup || !out_nres) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_scan_batch: NULL buffer");
+  SHZ_HIP(ctx, hipSetDevice(ctx->device));
+  const bool timed = ms_extract || ms_window || ms_match;
+  if (timed) {
+    for (hipEvent_t& e : ctx->sc_ev)
+      if (!e) SHZ_HIP(ctx, hipEventCreate(&e));
+    SHZ_HIP(ctx, hipEventRecord(ctx->sc_ev[0], ctx->stream));
+  }
+  // 1) every clip fingerprinted once, into the library's own buffers
+  std::vector<uint64_t> hash_off((size_t)n_clips + 1, 0);
+  const uint32_t *d_key = nullptr, *d_t1 = nullptr;
+  SHZ_TRY(shz_extract_owned(ctx, "shz_scan_batch", pcm, clip_off, n_clips, fs, amp_min, fan_value, flags & SHZ_PCM_DEVICE,
+                            hash_off.data(), &d_key, &d_t1));
+  if (timed) SHZ_HIP(ctx, hipEventRecord(ctx->sc_ev[1], ctx->stream));
+  // 2) the jobs: (window, channel) pairs | windows | hash_off, one block
+  const uint64_t pair_bytes = (n_pairs * sizeof(sc_pair) + 255) & ~255ull, win_bytes = (n_wins * sizeof(sc_win) + 255) & ~255ull;
+  const uint64_t job_bytes = pair_bytes + win_bytes + ((uint64_t)n_clips + 1) * 8;
+  std::vector<char> hjobs(job_bytes, 0);
+  sc_pair* hp = (sc_pair*)hjobs.data();
+  sc_win* hw = (sc_win*)(hjobs.data() + pair_bytes);
+  {
+    uint64_t p = 0, w = 0;
+    for (uint32_t r = 0; r < n_recs; ++r) {
+      const uint32_t c0 = rec_clip0[r], nch = rec_clip0[r + 1] - c0;
+      for (uint64_t i = 0; i < win_off[r + 1] - win_off[r]; ++i, ++w) {
+        // (with step > window the last window may start behind the recording's end: it is empty, and so is any start
+        // clamped to 2^32 - 1, which no t1 reaches)
+        const uint32_t s = (uint32_t)std::min<uint64_t>(i * step_frames, 0xFFFFFFFFull);
+        hw[w] = sc_win{p, nch, s};
+        for (uint32_t c = 0; c < nch; ++c) hp[p++] = sc_pair{c0 + c, s};
+      }
+    }
+  }
+  memcpy(hjobs.data() + pair_bytes + win_bytes, hash_off.data(), ((uint64_t)n_clips + 1) * 8);
+  void *d_jobs, *d_ctl;
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SC_JOBS, job_bytes, &d_jobs));
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SC_CTL, (3 * n_pairs + 1) * 8, &d_ctl));
+  const sc_pair* d_pairs = (const sc_pair*)d_jobs;
+  const sc_win* d_wins = (const sc_win*)((char*)d_jobs + pair_bytes);
+  const uint64_t* d_hoff = (const uint64_t*)((char*)d_jobs + pair_bytes + win_bytes);
+  uint64_t *d_first = (uint64_t*)d_ctl, *d_cnt = d_first + n_pairs, *d_offs = d_cnt + n_pairs;   // d_offs[n_pairs] = the total
+  SHZ_HIP(ctx, shz_memcpy(ctx, d_jobs, hjobs.data(), job_bytes, hipMemcpyHostToDevice));
+  // 3) bounds, 4) scan, 6) one read-back: the offsets of every pair (a recording with windows has a clip: n_pairs >= 1)
+  std::vector<uint64_t> offs((size_t)n_pairs + 1, 0);
+  hipLaunchKernelGGL(scan_bounds_kernel, dim3((unsigned)((n_pairs + SC_THREADS - 1) / SC_THREADS)), dim3(SC_THREADS), 0, ctx->stream,
+                     d_pairs, n_pairs, d_hoff, d_t1, window_frames, d_first, d_cnt);
+  SHZ_HIP(ctx, hipGetLastError());
+  SHZ_TRY(shz_scan_u64(ctx, d_cnt, d_offs, n_pairs, d_offs + n_pairs));
+  SHZ_HIP(ctx, shz_memcpy(ctx, offs.data(), d_offs, (n_pairs + 1) * 8, hipMemcpyDeviceToHost));
+  if (timed) SHZ_HIP(ctx, hipEventRecord(ctx->sc_ev[2], ctx->stream));
+  SHZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  float win_ms = 0.f, match_ms = 0.f;
+  if (timed) {
+    if (ms_extract) SHZ_HIP(ctx, hipEventElapsedTime(ms_extract, ctx->sc_ev[0], ctx->sc_ev[1]));
+    SHZ_HIP(ctx, hipEventElapsedTime(&win_ms, ctx->sc_ev[1], ctx->sc_ev[2]));
+  }
+  // a hash lies in at most ceil(window / step) windows
+  const uint64_t total = offs[n_pairs], rep = ((uint64_t)window_frames + step_frames - 1) / step_frames;
+  if (total > hash_off[n_clips] * rep)
+    SHZ_FAIL(ctx, SHZ_E_STATE, "shz_scan_batch: %llu window entries from %llu hashes", (unsigned long long)total,
+             (unsigned long long)hash_off[n_clips]);
+  auto win_at = [&](uint64_t w) { return w < n_wins ? offs[hw[w].pair0] : total; };
+  // 5) + 7) group by group: gather the windows' columns, match them where they lie.  A group's columns take at most 1/8 of
+  // the workspace limit (the match sizes its own sub-batches inside a group); a window is never split, so one larger than
+  // that is a group of its own
+  const uint64_t max_entries = std::min<uint64_t>(std::max<uint64_t>(ctx->ws_limit / 64, 1), 1ull << 30);
+  const uint64_t max_wins = (ctx->debug & SHZ_DEBUG_SCAN_SMALL_GROUPS) ? SC_SMALL_GROUP : (1ull << 24);
+  std::vector<uint64_t> groups{0};   // first window of every group, n_wins behind them
+  uint64_t m_max = 0;
+  for (uint64_t g0 = 0; g0 < n_wins;) {
+    uint64_t g1 = g0 + 1;
+    while (g1 < n_wins && g1 - g0 < max_wins && win_at(g1 + 1) - win_at(g0) <= max_entries) ++g1;
+    m_max = std::max(m_max, win_at(g1) - win_at(g0));
+    groups.push_back(g1);
+    g0 = g1;
+  }
+  void *d_gk, *d_gq;
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SC_KEY, m_max * 4 + 64, &d_gk));
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SC_QO, m_max * 4 + 64, &d_gq));
+  std::vector<uint64_t> query_off;
+  for (size_t g = 0; g + 1 < groups.size(); ++g) {
+    const uint64_t g0 = groups[g], nq = groups[g + 1] - g0, base = win_at(g0), m = win_at(g0 + nq) - base;
+    if (timed) SHZ_HIP(ctx, hipEventRecord(ctx->sc_ev[2], ctx->stream));
+    if (m) {
+      hipLaunchKernelGGL(scan_gather_kernel, dim3((unsigned)nq), dim3(SC_THREADS), 0, ctx->stream, d_wins, g0, (const uint64_t*)d_first,
+                         (const uint64_t*)d_offs, base, m, d_key, d_t1, (uint32_t*)d_gk, (uint32_t*)d_gq);
+      SHZ_HIP(ctx, hipGetLastError());
+    }
+    if (timed) SHZ_HIP(ctx, hipEventRecord(ctx->sc_ev[3], ctx->stream));
+    query_off.resize((size_t)nq + 1);
+    for (uint64_t w = 0; w <= nq; ++w) query_off[w] = win_at(g0 + w) - base;
+    const uint64_t o = g0 * topn;
+    SHZ_TRY(shz_match_device(ctx, t, (const uint32_t*)d_gk, (const uint32_t*)d_gq, query_off.data(), (uint32_t)nq, topn,
+                             flags & SHZ_MATCH_FULL_SORT, (int64_t)window_frames - 1, out_sid + o, out_delta + o, out_aligned + o,
+                             out_dedup + o, out_nres + g0, out_nhash ? out_nhash + g0 : nullptr,
+                             out_npairs ? out_npairs + g0 : nullptr));
+    if (timed) {
+      float a = 0.f, b = 0.f;
+      SHZ_HIP(ctx, hipEventRecord(ctx->sc_ev[4], ctx->stream));
+      SHZ_HIP(ctx, hipEventSynchronize(ctx->sc_ev[4]));
+      SHZ_HIP(ctx, hipEventElapsedTime(&a, ctx->sc_ev[2], ctx->sc_ev[3]));
+      SHZ_HIP(ctx, hipEventElapsedTime(&b, ctx->sc_ev[3], ctx->sc_ev[4]));
+      win_ms += a;
+      match_ms += b;
+    }
+  }
+  if (ms_window) *ms_window = win_ms;
+  if (ms_match) *ms_match = match_ms;
+  return SHZ_OK;
+}
+
+// The per-window answers of a scan folded into segments, on the host: "song X from window a to window b".
+extern "C" int32_t shz_scan_timeline(const uint64_t* win_off, uint32_t n_recs, const uint32_t* sid, const int32_t* delta,
+                                     const uint32_t* aligned, const uint32_t* nres, uint32_t topn, uint32_t step_frames,
+                                     uint32_t min_aligned, uint32_t max_gap, uint32_t* seg_rec, uint32_t* seg_sid, int64_t* seg_shift,
+                                     uint32_t* seg_first, uint32_t* seg_last, uint32_t* seg_hits, uint32_t* seg_best, uint64_t cap,
+                                     uint64_t* count) {
+  if (!count) return SHZ_E_INVALID;
+  *count = 0;
+  if (n_recs == 0) return SHZ_OK;
+  if (!win_off || topn == 0) return SHZ_E_INVALID;
+  for (uint32_t r = 0; r < n_recs; ++r)
+    if (win_off[r + 1] < win_off[r] || win_off[r + 1] - win_off[r] > 0xFFFFFFFFull) return SHZ_E_INVALID;
+  if (win_off[n_recs] > win_off[0] && (!sid || !delta || !aligned || !nres)) return SHZ_E_INVALID;
+  if (cap && (!seg_rec || !seg_sid || !seg_shift || !seg_first || !seg_last || !seg_hits || !seg_best)) return SHZ_E_INVALID;
+  uint64_t n = 0;
+  for (uint32_t r = 0; r < n_recs; ++r) {
+    bool open = false;
+    uint32_t o_sid = 0, o_first = 0, o_last = 0, o_hits = 0, o_best = 0;
+    int64_t o_shift = 0;
+    auto close = [&]() {
+      if (open && n < cap) {
+        seg_rec[n] = r;
+        seg_sid[n] = o_sid;
+        seg_shift[n] = o_shift;
+        seg_first[n] = o_first;
+        seg_last[n] = o_last;
+        seg_hits[n] = o_hits;
+        seg_best[n] = o_best;
+      }
+      n += open ? 1 : 0;
+      open = false;
+    };
+    const uint64_t nw = win_off[r + 1] - win_off[r];
+    for (uint64_t w = 0; w < nw; ++w) {
+      const uint64_t g = win_off[r] + w;
+      if (nres[g] < 1 || aligned[g * topn] < min_aligned) continue;   // no hit: changes nothing
+      const uint32_t s = sid[g * topn], a = aligned[g * topn];
+      const int64_t shift = (int64_t)delta[g * topn] - (int64_t)w * (int64_t)step_frames;   // song frame - recording frame
+      if (open && s == o_sid && shift == o_shift && w - o_last - 1 <= max_gap) {
+        o_last = (uint32_t)w;
+        ++o_hits;
+        o_best = std::max(o_best, a);
+        continue;
+      }
+      close();
+      open = true;
+      o_sid = s;
+      o_shift = shift;
+      o_first = o_last = (uint32_t)w;
+      o_hits = 1;
+      o_best = a;
+    }
+    close();
+  }
+  *count = n;
+  return n > cap ? SHZ_E_CAPACITY : SHZ_OK;
+}
