@@ -356,6 +356,9 @@ uint64_t shz_recognize_estimate(uint64_t frames, uint32_t fan_value);
 /* Test switch of shz_scan_batch: a group of windows handed to the match holds at most 3 windows, so that tests reach the
  * group borders with tiny inputs (results do not depend on the grouping). */
 #define SHZ_DEBUG_SCAN_SMALL_GROUPS 8u
+/* Test switch of shz_recognize_speeds: a slice of queries handed to the warp and the match holds at most 2 queries, so that
+ * tests reach the slice borders with tiny inputs (results do not depend on the slicing). */
+#define SHZ_DEBUG_SPEED_SMALL_SLICES 16u
 int32_t shz_set_debug(shz_ctx* ctx, uint32_t flags);
 int32_t shz_match_vt_redo(shz_ctx* ctx, uint64_t* count);
 /* A single query of at most 8,192 hashes handed over in host memory has its vote kernels queued before the number of its
@@ -600,6 +603,54 @@ int32_t shz_scan_timeline(const uint64_t* win_off, uint32_t n_recs, const uint32
                           uint32_t min_aligned, uint32_t max_gap, uint32_t* seg_rec, uint32_t* seg_sid, int64_t* seg_shift,
                           uint32_t* seg_first, uint32_t* seg_last, uint32_t* seg_hits, uint32_t* seg_best, uint64_t cap,
                           uint64_t* count);
+
+/* ---- speed-tolerant recognition (new; the reference's hash is an exact (f1, f2, dt) triple, recognizer.py:100-114, so audio
+ * played 1 % fast or slow no longer meets the table) ----------------------------------------------------------------------
+ * A query that plays s times as fast as the table's copy has its constellation peaks at frequency f s and time t / s.  The
+ * spectrogram is left alone: the integer coordinates of the query's peaks are mapped back to the table's domain for every
+ * factor of a ladder, and every variant is paired and hashed like generate_hashes (__init__.py:179-210).
+ * A factor is Q16: s16 = round(s 65536) in [32768, 131072] (0.5x .. 2x); above 65536 the query plays faster than the table's
+ * copy.  For a peak (f, t), in 64-bit integers:
+ *     t' = (t s16 + 32768) >> 16        f' = (2 65536 f + s16) / (2 s16)    (integer division: round-half-up of f 65536 / s16)
+ * peaks with f' > 2048 leave; the peaks of one (clip, speed) are ordered by (t', f', original index) -- what generate_hashes
+ * sees after its stable time sort -- and paired as shz_pair_hash pairs them: each with its next fan_value - 1 successors,
+ * 0 <= dt' <= 200, key32 = f1' << 20 | f2' << 8 | dt', t1 = t1'.  At s16 = 65536 the result is shz_pair_hash's, entry for
+ * entry.  Numpy twin: tests/speed_twin.py.
+ *
+ * shz_warp_pair_hash: peaks as for shz_pair_hash ((time asc, freq asc) per clip, t < 2^31; peak_off: n_clips + 1, HOST;
+ * peak_f / peak_t host, or device with SHZ_IN_DEVICE -- a host list that breaks the order is SHZ_E_INVALID, a device list is
+ * the caller's promise).  Query q owns the adjacent clips [query_clip0[q], query_clip0[q + 1]) as in shz_recognize_batch;
+ * query_clip0 = NULL: every clip is a query of its own (n_queries is not read).  OUTPUT ORDER: for query q, for speed v, for
+ * every clip c of q, the hashes of (c, v) in generation order -- (q, v) is one contiguous query of the match.  hash_off
+ * (HOST, n_clips n_speeds + 1 entries, may be NULL) is the CSR of those segments in that order, exact: the hashes are
+ * counted before they are written.  key32 / t1: host, or device with SHZ_OUT_DEVICE; more than cap hashes: SHZ_E_CAPACITY,
+ * *count = required, hash_off written, nothing else.  SHZ_E_INVALID before anything is launched: n_speeds of 0 or above 1024,
+ * a factor outside the range, fan_value outside [1, 64], a peak_off or query_clip0 that is not a CSR.  SHZ_E_UNSUPPORTED:
+ * peaks x speeds x (fan_value - 1) of 2^32 or more in one call. */
+int32_t shz_warp_pair_hash(shz_ctx* ctx, const uint16_t* peak_f, const uint32_t* peak_t, const uint64_t* peak_off,
+                           uint32_t n_clips, const uint32_t* query_clip0, uint32_t n_queries, const uint32_t* speed_q16,
+                           uint32_t n_speeds, uint32_t fan_value, uint32_t flags, uint32_t* key32, uint32_t* t1,
+                           uint64_t* hash_off, uint64_t cap, uint64_t* count);
+/* recognize() at an unknown speed: shz_peaks into buffers of the library, the warp above for every factor of speed_q16, and
+ * ONE match over n_queries x n_speeds queries ((q, v) = the union over q's channels of variant v); peaks and hashes never
+ * visit the host.  Clips, query_clip0, fs, amp_min, fan_value, topn as for shz_recognize_batch; flags: SHZ_PCM_DEVICE,
+ * SHZ_MATCH_FULL_SORT.  Per query the BEST variant is the one with the greatest rank-0 aligned count (0 without results);
+ * ties go to the factor nearest 65536, then to the lower index.  Outputs (host): out_best[n_queries] = its index into
+ * speed_q16; out_sid / out_delta / out_aligned / out_dedup [n_queries topn], out_nres, out_nhash (may be NULL) [n_queries]:
+ * the best variant's, shaped as shz_recognize_batch's -- out_delta is in the TABLE's frames; out_profile (may be NULL)
+ * [n_queries n_speeds]: the rank-0 aligned count of every variant.  The match's bias bound is the largest warped time,
+ * round((max_frames - 1) s_max).  Refused before anything is launched: what shz_recognize_batch refuses, n_speeds of 0 or
+ * above 1024 and a factor outside the range (SHZ_E_INVALID), a clip whose warped time could reach 2^20, the query offsets of
+ * the match (SHZ_E_UNSUPPORTED).  Queries x speeds go to the warp and the match in slices of whole queries whose hashes stay
+ * within the match's 2^28-pair budget and 1/8 of the workspace limit; results do not depend on the slicing
+ * (SHZ_DEBUG_SPEED_SMALL_SLICES).  ms_extract / ms_warp / ms_match (may be NULL): hipEvent times of the peak extraction, of
+ * the warp stages (with their one read-back a slice) and of the matches. */
+int32_t shz_recognize_speeds(shz_ctx* ctx, shz_table* table, const int16_t* pcm, const uint64_t* clip_off, uint32_t n_clips,
+                             const uint32_t* query_clip0, uint32_t n_queries, uint32_t fs, double amp_min, uint32_t fan_value,
+                             uint32_t topn, const uint32_t* speed_q16, uint32_t n_speeds, uint32_t flags, uint32_t* out_best,
+                             uint32_t* out_sid, int32_t* out_delta, uint32_t* out_aligned, uint32_t* out_dedup,
+                             uint32_t* out_nres, uint32_t* out_nhash, uint32_t* out_profile, float* ms_extract, float* ms_warp,
+                             float* ms_match);
 
 #ifdef __cplusplus
 }

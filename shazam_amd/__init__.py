@@ -349,3 +349,5 @@ from .stream import StreamFingerprinter, StreamRecognizer, fingerprint_stream  #
 from .resample import StreamResampler, resample_batch, resample_plan, resample_to_device  # noqa: E402,F401
 # long recordings (csrc/shz_scan.hip): every window of a recording matched in one call, and the timeline of its songs
 from .scan import scan, scan_windows  # noqa: E402,F401
+# queries played fast or slow (csrc/shz_speed.hip): the peaks warped for every factor of a ladder, all variants in one match
+from .speed import recognize_speeds, speed_ladder, warp_hashes  # noqa: E402,F401

@@ -14,6 +14,7 @@ OK, E_INVALID, E_HIP, E_CAPACITY, E_NOMEM, E_UNSUPPORTED, E_RCCL, E_STATE = 0, -
 PCM_DEVICE, OUT_DEVICE, IN_DEVICE, STFT_POWER, MATCH_FULL_SORT, RESERVE_GATHER, RESERVE_WAIT = 1, 2, 4, 8, 16, 32, 64
 # shz_set_debug test switches (include/shz.h); RUN_ROWS_MAX[_SMALL]: the most rows a run / a segment cut from runs holds
 DEBUG_VT_TINY_HEAVY, DEBUG_VT_PROBE1, DEBUG_RUN_LIMIT_SMALL, DEBUG_SCAN_SMALL_GROUPS = 1, 2, 4, 8
+DEBUG_SPEED_SMALL_SLICES = 16   # shz_recognize_speeds: at most 2 queries a slice
 RUN_ROWS_MAX, RUN_ROWS_MAX_SMALL = (1 << 32) - 4096, 65536
 NFFT, HOP, NBINS = 4096, 2048, 2049
 
@@ -141,6 +142,11 @@ SIGNATURES = {
                                    u64p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "shz_scan_timeline": (C.c_int32, [u64p, C.c_uint32, vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                       vp, vp, vp, vp, vp, vp, vp, C.c_uint64, u64p]),
+    "shz_warp_pair_hash": (C.c_int32, [vp, vp, vp, u64p, C.c_uint32, u32p, C.c_uint32, u32p, C.c_uint32, C.c_uint32, C.c_uint32,
+                                       vp, vp, u64p, C.c_uint64, u64p]),
+    "shz_recognize_speeds": (C.c_int32, [vp, vp, vp, u64p, C.c_uint32, u32p, C.c_uint32, C.c_uint32, C.c_double, C.c_uint32,
+                                         C.c_uint32, u32p, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp,
+                                         C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
 }
 
 
@@ -278,7 +284,8 @@ class Context:
 
     def set_debug(self, flags: int):
         """SHZ_DEBUG_* test switches (1: tiny hand-over list, 2: LDS probes give up after one round, 4: runs and segments cut
-        from runs hold at most RUN_ROWS_MAX_SMALL rows, 8: shz_scan_batch matches its windows in groups of at most 3)."""
+        from runs hold at most RUN_ROWS_MAX_SMALL rows, 8: shz_scan_batch matches its windows in groups of at most 3, 16: shz_recognize_speeds warps and
+        matches its queries in slices of at most 2)."""
         self.check(lib().shz_set_debug(self.h, int(flags)))
 
     def vt_redo_count(self) -> int:
@@ -599,6 +606,62 @@ class Context:
         self.check(call(res, cap_windows))
         n = int(cnt.value)
         return {k: v[:n] for k, v in res.items()}, wo, tuple(float(m.value) for m in ms)
+
+    def warp_pair_hash_raw(self, peak_f, peak_t, peak_off, speeds, query_clip0=None, fan_value=5, cap=0, device_in=False,
+                           out_key: DevBuf = None, out_t1: DevBuf = None):
+        """One shz_warp_pair_hash as it is: (rc, key32, t1, hash_off, count) without retrying.  peak_f / peak_t: host
+        arrays, or DevBufs with device_in.  With out_key / out_t1 DevBufs the hashes stay on the device and the returned
+        arrays are None."""
+        po = np.ascontiguousarray(peak_off, np.uint64)
+        sp = np.ascontiguousarray(speeds, np.uint32)
+        nc = len(po) - 1
+        qc = None if query_clip0 is None else np.ascontiguousarray(query_clip0, np.uint32)
+        if not device_in:
+            peak_f, peak_t = np.ascontiguousarray(peak_f, np.uint16), np.ascontiguousarray(peak_t, np.uint32)
+        ho, cnt = np.zeros(nc * len(sp) + 1, np.uint64), C.c_uint64()
+        flags = (IN_DEVICE if device_in else 0) | (OUT_DEVICE if out_key is not None else 0)
+        k = t1 = None
+        if out_key is None:
+            k, t1 = np.empty(max(int(cap), 1), np.uint32), np.empty(max(int(cap), 1), np.uint32)
+        rc = lib().shz_warp_pair_hash(self.h, ptr(peak_f), ptr(peak_t), po.ctypes.data_as(u64p), nc,
+                                      None if qc is None else qc.ctypes.data_as(u32p), 0 if qc is None else len(qc) - 1,
+                                      sp.ctypes.data_as(u32p), len(sp), int(fan_value), flags,
+                                      ptr(out_key if out_key is not None else k), ptr(out_t1 if out_key is not None else t1),
+                                      ho.ctypes.data_as(u64p), int(cap), C.byref(cnt))
+        n = int(cnt.value)
+        if k is not None:
+            k, t1 = k[:min(n, int(cap))], t1[:min(n, int(cap))]
+        return rc, k, t1, ho, n
+
+    def warp_pair_hash(self, peak_f, peak_t, peak_off, speeds, query_clip0=None, fan_value=5):
+        """shz_warp_pair_hash (two calls: count, then write): (key32, t1, hash_off) in the order query, speed, clip."""
+        rc, k, t1, ho, n = self.warp_pair_hash_raw(peak_f, peak_t, peak_off, speeds, query_clip0, fan_value, 0)
+        if rc == E_CAPACITY:
+            rc, k, t1, ho, n = self.warp_pair_hash_raw(peak_f, peak_t, peak_off, speeds, query_clip0, fan_value, n)
+        self.check(rc)
+        return k[:n], t1[:n], ho
+
+    def recognize_speeds(self, table: "Table", pcm, clip_off, query_clip0, speeds, fs=44100, amp_min=10.0, fan_value=5, topn=2,
+                         pcm_device=False, full_sort=False):
+        """shz_recognize_speeds: the peaks of the clips once, every factor of `speeds` (Q16) warped, hashed and matched on
+        the device.  Returns (res, ms): res as Table.match over the queries (the best variant's rows; no npairs) plus
+        best [nq] (index into speeds) and profile [nq, K] (rank-0 aligned count of every variant); ms = (extract, warp,
+        match) device times."""
+        co, nc = self._clip_off(clip_off)
+        qc = np.ascontiguousarray(query_clip0, np.uint32)
+        sp = np.ascontiguousarray(speeds, np.uint32)
+        nq = len(qc) - 1
+        res = _match_result(nq, topn)
+        del res["npairs"]
+        res["best"], res["profile"] = np.zeros(nq, np.uint32), np.zeros((nq, len(sp)), np.uint32)
+        ms = [C.c_float(), C.c_float(), C.c_float()]
+        self.check(lib().shz_recognize_speeds(self.h, table.h, ptr(pcm), co.ctypes.data_as(u64p), nc, qc.ctypes.data_as(u32p), nq,
+                                              int(fs), float(amp_min), int(fan_value), int(topn), sp.ctypes.data_as(u32p), len(sp),
+                                              (PCM_DEVICE if pcm_device else 0) | (MATCH_FULL_SORT if full_sort else 0),
+                                              ptr(res["best"]), ptr(res["sid"]), ptr(res["delta"]), ptr(res["aligned"]),
+                                              ptr(res["dedup"]), ptr(res["nres"]), ptr(res["nhash"]), ptr(res["profile"]),
+                                              *[C.byref(m) for m in ms]))
+        return res, tuple(float(m.value) for m in ms)
 
     def resample_raw(self, pcm, clip_off, L, M, T, taps, in_base=None, m_first=None, m_end=None, pcm_device=False,
                      out: DevBuf = None, cap=None):

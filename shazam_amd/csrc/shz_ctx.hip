@@ -8,7 +8,7 @@
 
 #include "shz_internal.h"
 
-extern "C" const char* shz_version(void) { return "shz 0.1 (gfx950)"; }
+extern "C" const char* shz_version(void) { return "shz 0.2 (gfx950)"; }
 
 int32_t shz_ws_reserve(shz_ctx* ctx, int slot, uint64_t bytes, void** out) {
   shz_buf& b = ctx->ws[slot];
@@ -369,6 +369,8 @@ extern "C" int32_t shz_ctx_destroy(shz_ctx* ctx) {
   for (hipEvent_t e : ctx->rq_ev)
     if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : ctx->sc_ev)
+    if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : ctx->sp_ev)
     if (e) (void)hipEventDestroy(e);
   if (ctx->tev_init)
     for (auto& e : ctx->tev) {

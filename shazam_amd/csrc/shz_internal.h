@@ -84,6 +84,13 @@ enum {
   SHZ_WS_SC_JOBS,    // shz_scan_batch: (window, channel) jobs | window jobs | hash_off of the clips
   SHZ_WS_SC_CTL,     // ... first entry | count | offset of every (window, channel), the total behind the offsets
   SHZ_WS_SC_KEY, SHZ_WS_SC_QO,   // ... the windows of one group: key32 and t1 - window start, window-major
+  SHZ_WS_SP_PF, SHZ_WS_SP_PT,    // shz_speed.hip: the peaks of the clips (the extraction's, or a host list staged)
+  SHZ_WS_SP_TAB,     // ... peak_off | speeds of the call
+  SHZ_WS_SP_Q,       // ... first item | first clip of every query of a pass
+  SHZ_WS_SP_A, SHZ_WS_SP_B,      // ... per (peak, speed) item: keep flags, then partner counts | their scans
+  SHZ_WS_SP_WF, SHZ_WS_SP_WT,    // ... the warped, compacted peaks in output order
+  SHZ_WS_SP_SEG,     // ... first kept peak of every (query, speed, clip) | hash_off | totals
+  SHZ_WS_SP_KEY, SHZ_WS_SP_T1,   // ... the hashes of a pass between the warp and the match
   SHZ_WS_COUNT
 };
 
@@ -113,6 +120,7 @@ struct shz_ctx {
   bool tev_init = false;
   hipEvent_t rq_ev[3] = {nullptr, nullptr, nullptr};   // shz_recognize_batch: start, extraction done, match done (created on first use)
   hipEvent_t sc_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // shz_scan_batch: start, extraction done, a group's gather begun / done, its match done (created on first use)
+  hipEvent_t sp_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // shz_recognize_speeds: start, peaks done, a slice's warp begun / done, its match done (created on first use)
   bool profiling = false;
   float kernel_ms[8] = {0};
   uint32_t kernel_launches[8] = {0};
