@@ -359,6 +359,9 @@ uint64_t shz_recognize_estimate(uint64_t frames, uint32_t fan_value);
 /* Test switch of shz_recognize_speeds: a slice of queries handed to the warp and the match holds at most 2 queries, so that
  * tests reach the slice borders with tiny inputs (results do not depend on the slicing). */
 #define SHZ_DEBUG_SPEED_SMALL_SLICES 16u
+/* Test switch of shz_scan_speeds: a slice holds at most 1 recording x 2 rungs and a group of windows handed to the match at
+ * most 3 windows, so that tests reach the slice, chunk and group borders with tiny inputs (results do not depend on them). */
+#define SHZ_DEBUG_SCAN_SPEED_SMALL_SLICES 32u
 int32_t shz_set_debug(shz_ctx* ctx, uint32_t flags);
 int32_t shz_match_vt_redo(shz_ctx* ctx, uint64_t* count);
 /* A single query of at most 8,192 hashes handed over in host memory has its vote kernels queued before the number of its
@@ -651,6 +654,64 @@ int32_t shz_recognize_speeds(shz_ctx* ctx, shz_table* table, const int16_t* pcm,
                              uint32_t* out_sid, int32_t* out_delta, uint32_t* out_aligned, uint32_t* out_dedup,
                              uint32_t* out_nres, uint32_t* out_nhash, uint32_t* out_profile, float* ms_extract, float* ms_warp,
                              float* ms_match);
+
+/* ---- scanning at an unknown speed (new; shz_scan_batch and shz_recognize_speeds joined: "which songs play in this hour of
+ * broadcast, and when?" where the station pitches its songs up or down) --------------------------------------------------
+ * shz_scan_speeds: the arguments of shz_scan_batch plus a ladder (speed_q16 / n_speeds, checked as shz_recognize_speeds
+ * checks them).  Every recording's peaks are extracted ONCE (shz_peaks), warped, re-ordered and paired for every rung as
+ * shz_warp_pair_hash does with the recording as the query, and the warped lists are cut into the windows on the device.
+ * WINDOW COUNT: in the recording's own frames, exactly shz_scan_window_count(F_r, window_frames, step_frames); win_off,
+ * cap_windows, *count and SHZ_E_CAPACITY as in shz_scan_batch (the total follows from the frame counts alone).
+ * WINDOW CONTENTS: with W_v(x) = (x s16 + 32768) >> 16 for rung v (64-bit; the warp's time map), window w starts at recording
+ * frame s = w step_frames; its query at rung v is the union, over the recording's channels, of the entries (key32, t1') of
+ * (recording, v, channel) with W_v(s) <= t1' < W_v(s + window_frames), and an entry's query offset is t1' - W_v(s).  At s16 =
+ * 65536 that is shz_scan_batch's window, entry for entry.  The EDGES note of shz_scan_batch holds here too.
+ * MATCH: every (window, rung) is one query of the match on device columns; its bias bound is ceil(window_frames s_max / 65536)
+ * - 1, which W_v(s + window_frames) - W_v(s) - 1 never exceeds at any rung or start (at 65536 alone: window_frames - 1).
+ * OUTPUTS per window (host, windows recording-major): out_best[n_wins] = the index of the best rung -- greatest rank-0
+ * aligned count (0 without results), ties to the factor nearest 65536, then to the lower index; out_sid / out_delta /
+ * out_aligned / out_dedup [n_wins topn], out_nres, out_nhash, out_npairs (the last two may be NULL) [n_wins]: the best rung's,
+ * shaped as shz_scan_batch's.  out_delta is in the TABLE's frames: the song frame that lies at the window's start.
+ * out_profile (may be NULL) [n_wins n_speeds]: the rank-0 aligned count of every rung.
+ * REFUSED before anything is launched: everything shz_scan_batch refuses; n_speeds of 0 or above 1024, a factor outside
+ * [32768, 131072], fan_value outside [1, 64] (SHZ_E_INVALID); ceil(window_frames s_max / 65536) >= 2^20, the query offsets of
+ * the match (SHZ_E_UNSUPPORTED).  A single (recording, rung) whose peaks x (fan_value - 1) reach 2^32, the warp's 32-bit
+ * scans, is SHZ_E_UNSUPPORTED too; the peaks are counted by the extraction, so this one comes after it and before any warp.
+ * SLICES: the work goes in slices of (whole recordings x a contiguous chunk of rungs) whose warped hashes stay within the
+ * match's 2^28-pair budget and 1/8 of the workspace limit (the ladder is cut only where one recording at all rungs is beyond
+ * that); inside a slice the windows go to the match in groups as in shz_scan_batch, a window with all its rungs never split;
+ * the best rung is folded over the chunks on the host.  Results do not depend on any of it
+ * (SHZ_DEBUG_SCAN_SPEED_SMALL_SLICES).  ms_extract / ms_warp / ms_window / ms_match (may be NULL): hipEvent times of the peak
+ * extraction, of the warp stages (with their one read-back a slice), of cutting the windows (bounds, scan, read-back,
+ * gathers) and of the matches. */
+int32_t shz_scan_speeds(shz_ctx* ctx, shz_table* t, const int16_t* pcm, const uint64_t* clip_off, uint32_t n_clips,
+                        const uint32_t* rec_clip0, uint32_t n_recs, uint32_t fs, double amp_min, uint32_t fan_value,
+                        uint32_t window_frames, uint32_t step_frames, uint32_t topn, const uint32_t* speed_q16, uint32_t n_speeds,
+                        uint32_t flags, uint64_t* win_off, uint32_t* out_best, uint32_t* out_sid, int32_t* out_delta,
+                        uint32_t* out_aligned, uint32_t* out_dedup, uint32_t* out_nres, uint32_t* out_nhash, uint64_t* out_npairs,
+                        uint32_t* out_profile, uint64_t cap_windows, uint64_t* count, float* ms_extract, float* ms_warp,
+                        float* ms_window, float* ms_match);
+/* The timeline of a speed-tolerant scan (no GPU, no ctx).  shz_scan_timeline's identity shift = delta - w step_frames is
+ * not constant when the recording plays faster or slower than the table's copy (at 1.03 the song advances 22 or 23 frames a
+ * 22-frame step), and neighbouring windows may choose neighbouring rungs, so continuity is judged between neighbouring hits.
+ * Inputs: win_off and out_sid / out_delta / out_aligned (stride topn, rank 0 is read) / out_nres / out_best of
+ * shz_scan_speeds, and its ladder (rung_tol compares INDICES: hand over a sorted ladder).  A window is a HIT iff nres >= 1
+ * and its rank-0 aligned >= min_aligned.  The windows of a recording are visited in order with one open segment, whose last
+ * hit is w1 with rung v1 and delta1: a hit w2 (rung v2, delta2) CONTINUES it iff the song id is the same, w2 - w1 - 1 <=
+ * max_gap, |v2 - v1| <= rung_tol and |delta2 - delta1 - W_v2((w2 - w1) step_frames)| <= shift_tol (W_v as above, 64-bit);
+ * any other hit closes it and opens a new one; a window without a hit changes nothing; the recording's end closes it.
+ * Per segment (recording-major, in order): recording, sid, first and last window, hit windows, largest aligned count,
+ * pos_first / pos_last (the deltas of its first and last hit: song frames at those windows' starts), and seg_rung = the
+ * index of the rung its hits chose most often (ties to the factor nearest 65536, then to the lower index).  Two-call idiom
+ * as shz_scan_timeline: more than cap segments: SHZ_E_CAPACITY, *count = their number, the first cap are written (cap = 0:
+ * the seg_* pointers may be NULL).  SHZ_E_INVALID: a ladder shz_scan_speeds would refuse, an out_best entry >= n_speeds,
+ * topn of 0, a win_off that decreases. */
+int32_t shz_scan_timeline_speeds(const uint64_t* win_off, uint32_t n_recs, const uint32_t* out_sid, const int32_t* out_delta,
+                                 const uint32_t* out_aligned, const uint32_t* out_nres, const uint32_t* out_best, uint32_t topn,
+                                 uint32_t step_frames, const uint32_t* speed_q16, uint32_t n_speeds, uint32_t min_aligned,
+                                 uint32_t max_gap, uint32_t rung_tol, uint32_t shift_tol, uint32_t* seg_rec, uint32_t* seg_sid,
+                                 uint32_t* seg_first, uint32_t* seg_last, uint32_t* seg_hits, uint32_t* seg_best,
+                                 int32_t* seg_pos_first, int32_t* seg_pos_last, uint32_t* seg_rung, uint64_t cap, uint64_t* count);
 
 #ifdef __cplusplus
 }

@@ -15,6 +15,7 @@ PCM_DEVICE, OUT_DEVICE, IN_DEVICE, STFT_POWER, MATCH_FULL_SORT, RESERVE_GATHER, 
 # shz_set_debug test switches (include/shz.h); RUN_ROWS_MAX[_SMALL]: the most rows a run / a segment cut from runs holds
 DEBUG_VT_TINY_HEAVY, DEBUG_VT_PROBE1, DEBUG_RUN_LIMIT_SMALL, DEBUG_SCAN_SMALL_GROUPS = 1, 2, 4, 8
 DEBUG_SPEED_SMALL_SLICES = 16   # shz_recognize_speeds: at most 2 queries a slice
+DEBUG_SCAN_SPEED_SMALL_SLICES = 32   # shz_scan_speeds: at most 1 recording x 2 rungs a slice, 3 windows a match group
 RUN_ROWS_MAX, RUN_ROWS_MAX_SMALL = (1 << 32) - 4096, 65536
 NFFT, HOP, NBINS = 4096, 2048, 2049
 
@@ -147,6 +148,13 @@ SIGNATURES = {
     "shz_recognize_speeds": (C.c_int32, [vp, vp, vp, u64p, C.c_uint32, u32p, C.c_uint32, C.c_uint32, C.c_double, C.c_uint32,
                                          C.c_uint32, u32p, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp,
                                          C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "shz_scan_speeds": (C.c_int32, [vp, vp, vp, u64p, C.c_uint32, u32p, C.c_uint32, C.c_uint32, C.c_double, C.c_uint32,
+                                    C.c_uint32, C.c_uint32, C.c_uint32, u32p, C.c_uint32, C.c_uint32, u64p, vp, vp, vp, vp, vp, vp,
+                                    vp, vp, vp, C.c_uint64, u64p, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                    C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "shz_scan_timeline_speeds": (C.c_int32, [u64p, C.c_uint32, vp, vp, vp, vp, vp, C.c_uint32, C.c_uint32, u32p, C.c_uint32,
+                                             C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                             C.c_uint64, u64p]),
 }
 
 
@@ -285,7 +293,8 @@ class Context:
     def set_debug(self, flags: int):
         """SHZ_DEBUG_* test switches (1: tiny hand-over list, 2: LDS probes give up after one round, 4: runs and segments cut
         from runs hold at most RUN_ROWS_MAX_SMALL rows, 8: shz_scan_batch matches its windows in groups of at most 3, 16: shz_recognize_speeds warps and
-        matches its queries in slices of at most 2)."""
+        matches its queries in slices of at most 2, 32: shz_scan_speeds works in slices of 1 recording x 2 rungs and matches
+        its windows in groups of at most 3)."""
         self.check(lib().shz_set_debug(self.h, int(flags)))
 
     def vt_redo_count(self) -> int:
@@ -607,6 +616,42 @@ class Context:
         n = int(cnt.value)
         return {k: v[:n] for k, v in res.items()}, wo, tuple(float(m.value) for m in ms)
 
+    def scan_speeds(self, table: "Table", pcm, clip_off, rec_clip0, window_frames, step_frames, speeds, fs=44100, amp_min=10.0,
+                    fan_value=5, topn=2, pcm_device=False, full_sort=False, cap_windows=None):
+        """shz_scan_speeds: the peaks of the clips once, warped for every factor of `speeds` (Q16), every window of every
+        recording matched at every rung on the device.  Returns (res, win_off, ms): res as scan_batch's (the best rung's
+        rows) plus best [n_windows] (index into speeds) and profile [n_windows, K] (rank-0 aligned count of every rung);
+        win_off the CSR of the windows over the recordings; ms = (extract, warp, window, match) device times."""
+        co, nc = self._clip_off(clip_off)
+        rc0 = np.ascontiguousarray(rec_clip0, np.uint32)
+        sp = np.ascontiguousarray(speeds, np.uint32)
+        nr = len(rc0) - 1
+        flags = (PCM_DEVICE if pcm_device else 0) | (MATCH_FULL_SORT if full_sort else 0)
+        wo, cnt = np.zeros(nr + 1, np.uint64), C.c_uint64()
+        ms = [C.c_float(), C.c_float(), C.c_float(), C.c_float()]
+
+        def call(res, cap):
+            return lib().shz_scan_speeds(self.h, table.h, ptr(pcm), co.ctypes.data_as(u64p), nc, rc0.ctypes.data_as(u32p), nr,
+                                         int(fs), float(amp_min), int(fan_value), int(window_frames), int(step_frames), int(topn),
+                                         sp.ctypes.data_as(u32p), len(sp), flags, wo.ctypes.data_as(u64p), ptr(res["best"]),
+                                         ptr(res["sid"]), ptr(res["delta"]), ptr(res["aligned"]), ptr(res["dedup"]),
+                                         ptr(res["nres"]), ptr(res["nhash"]), ptr(res["npairs"]), ptr(res["profile"]), int(cap),
+                                         C.byref(cnt), *[C.byref(m) for m in ms])
+
+        def room(n):
+            res = _match_result(n, topn)
+            res["best"], res["profile"] = np.zeros(n, np.uint32), np.zeros((n, len(sp)), np.uint32)
+            return res
+        if cap_windows is None:   # the two-call idiom: the first call launches nothing and names the total
+            rc = call(room(0), 0)
+            if rc != E_CAPACITY:
+                self.check(rc)
+            cap_windows = int(cnt.value)
+        res = room(int(cap_windows))
+        self.check(call(res, cap_windows))
+        n = int(cnt.value)
+        return {k: v[:n] for k, v in res.items()}, wo, tuple(float(m.value) for m in ms)
+
     def warp_pair_hash_raw(self, peak_f, peak_t, peak_off, speeds, query_clip0=None, fan_value=5, cap=0, device_in=False,
                            out_key: DevBuf = None, out_t1: DevBuf = None):
         """One shz_warp_pair_hash as it is: (rc, key32, t1, hash_off, count) without retrying.  peak_f / peak_t: host
@@ -774,6 +819,43 @@ def scan_timeline(win_off, sid, delta, aligned, nres, step_frames, min_aligned, 
         rc, seg, n = scan_timeline_raw(win_off, sid, delta, aligned, nres, step_frames, min_aligned, max_gap, n)
     if rc != OK:
         raise ShzError(rc, "shz_scan_timeline: bad arguments")
+    return seg
+
+
+SPEED_SEGMENT_FIELDS = (("rec", np.uint32), ("sid", np.uint32), ("first", np.uint32), ("last", np.uint32), ("hits", np.uint32),
+                        ("best", np.uint32), ("pos_first", np.int32), ("pos_last", np.int32), ("rung", np.uint32))
+
+
+def scan_timeline_speeds_raw(win_off, sid, delta, aligned, nres, best, step_frames, speeds, min_aligned, max_gap=1, rung_tol=1,
+                             shift_tol=2, cap=0):
+    """One shz_scan_timeline_speeds as it is (host only): (rc, segments, count) with room for `cap` segments."""
+    wo = np.ascontiguousarray(win_off, np.uint64)
+    sid, delta, aligned = (np.ascontiguousarray(a, d) for a, d in ((sid, np.uint32), (delta, np.int32), (aligned, np.uint32)))
+    nres, best, sp = (np.ascontiguousarray(a, np.uint32) for a in (nres, best, speeds))
+    nw = len(nres)
+    topn = 1 if sid.ndim == 1 else int(sid.shape[1])
+    assert sid.shape == delta.shape == aligned.shape and sid.size == nw * topn and len(best) == nw
+    assert int(wo[-1]) - int(wo[0]) <= nw
+    seg = {k: np.zeros(int(cap), d) for k, d in SPEED_SEGMENT_FIELDS}
+    cnt = C.c_uint64()
+    rc = lib().shz_scan_timeline_speeds(wo.ctypes.data_as(u64p), len(wo) - 1, ptr(sid), ptr(delta), ptr(aligned), ptr(nres),
+                                        ptr(best), topn, int(step_frames), sp.ctypes.data_as(u32p), len(sp), int(min_aligned),
+                                        int(max_gap), int(rung_tol), int(shift_tol),
+                                        *[ptr(seg[k]) if cap else None for k, _ in SPEED_SEGMENT_FIELDS], int(cap), C.byref(cnt))
+    return rc, seg, int(cnt.value)
+
+
+def scan_timeline_speeds(win_off, sid, delta, aligned, nres, best, step_frames, speeds, min_aligned, max_gap=1, rung_tol=1,
+                         shift_tol=2) -> dict:
+    """shz_scan_timeline_speeds (host only, two calls): the rank-0 answers of a speed-tolerant scan folded into segments by
+    local continuity -- arrays rec, sid, first / last (windows of the recording), hits, best (largest aligned count),
+    pos_first / pos_last (song frames at the first / last hit's start), rung (the index chosen most often)."""
+    args = (win_off, sid, delta, aligned, nres, best, step_frames, speeds, min_aligned, max_gap, rung_tol, shift_tol)
+    rc, seg, n = scan_timeline_speeds_raw(*args, 0)
+    if rc == E_CAPACITY:
+        rc, seg, n = scan_timeline_speeds_raw(*args, n)
+    if rc != OK:
+        raise ShzError(rc, "shz_scan_timeline_speeds: bad arguments")
     return seg
 
 

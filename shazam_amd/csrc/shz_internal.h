@@ -81,9 +81,10 @@ enum {
   SHZ_WS_VT5,        // sub-group of every expand chunk's first vote (expand by sort blocks)
   SHZ_WS_VT6,        // the bar of every query of a vote pass (vt_stream2_kernel)
   SHZ_WS_RQ_KEY, SHZ_WS_RQ_T1,   // hashes of shz_recognize_batch / shz_scan_batch between their extraction and their match (neither reserves them)
-  SHZ_WS_SC_JOBS,    // shz_scan_batch: (window, channel) jobs | window jobs | hash_off of the clips
-  SHZ_WS_SC_CTL,     // ... first entry | count | offset of every (window, channel), the total behind the offsets
-  SHZ_WS_SC_KEY, SHZ_WS_SC_QO,   // ... the windows of one group: key32 and t1 - window start, window-major
+  SHZ_WS_SC_JOBS,    // shz_scan_batch: (window, channel) jobs | window jobs | hash_off of the clips; shz_scan_speeds: the
+                     // descriptors of a slice's recordings
+  SHZ_WS_SC_CTL,     // ... first entry | count | offset of every (window, channel) / (window, rung, channel), the total behind the offsets
+  SHZ_WS_SC_KEY, SHZ_WS_SC_QO,   // ... the windows of one group: key32 and t1 - window start, window-major (rung-minor)
   SHZ_WS_SP_PF, SHZ_WS_SP_PT,    // shz_speed.hip: the peaks of the clips (the extraction's, or a host list staged)
   SHZ_WS_SP_TAB,     // ... peak_off | speeds of the call
   SHZ_WS_SP_Q,       // ... first item | first clip of every query of a pass
@@ -119,7 +120,7 @@ struct shz_ctx {
   hipEvent_t tev[16][2];
   bool tev_init = false;
   hipEvent_t rq_ev[3] = {nullptr, nullptr, nullptr};   // shz_recognize_batch: start, extraction done, match done (created on first use)
-  hipEvent_t sc_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // shz_scan_batch: start, extraction done, a group's gather begun / done, its match done (created on first use)
+  hipEvent_t sc_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // shz_scan_batch / shz_scan_speeds: start, extraction done, a stage begun / done, the next one done (created on first use)
   hipEvent_t sp_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // shz_recognize_speeds: start, peaks done, a slice's warp begun / done, its match done (created on first use)
   bool profiling = false;
   float kernel_ms[8] = {0};
@@ -231,6 +232,52 @@ int32_t shz_match_ready(shz_ctx* ctx, shz_table* t, uint32_t topn);
 int32_t shz_extract_owned(shz_ctx* ctx, const char* who, const int16_t* pcm, const uint64_t* clip_off, uint32_t n_clips,
                           uint32_t fs, double amp_min, uint32_t fan_value, uint32_t flags, uint64_t* hash_off,
                           const uint32_t** d_key, const uint32_t** d_t1);
+
+// ---- the speed warp's stages (shz_speed.hip), shared with the speed-tolerant scan (shz_scan.hip) ----------------------
+#define SP_S_MIN 32768u
+#define SP_S_ONE 65536u
+#define SP_S_MAX 131072u
+#define SP_MAX_SPEEDS 1024u
+struct sp_view {              // what the kernels of one pass read (device pointers)
+  const uint16_t* pf;         // peaks of all clips, (clip, t asc, f asc)
+  const uint32_t* pt;
+  const uint64_t* poff;       // n_clips + 1
+  const uint64_t* qbase;      // nq + 1: first item of every query of the pass (query q has peaks(q) x K items)
+  const uint32_t* clip0;      // nq + 1: first clip of every query of the pass
+  const uint32_t* speed;      // K
+  uint32_t nq, K, fan;
+  uint64_t n_items;
+};
+struct sp_pass {
+  sp_view V;
+  uint64_t n_seg;
+  uint32_t *a, *b;            // flags, then partner counts | places, then hash offsets
+  uint16_t* wf;
+  uint32_t *wt, *segstart;
+  unsigned long long *d_hoff, *d_tot;   // hash_off[n_seg + 1] | kept peaks, hashes
+};
+__host__ __device__ __forceinline__ uint32_t sp_warp_t(uint32_t t, uint32_t s16) {
+  const uint64_t x = ((uint64_t)t * s16 + 32768u) >> 16;
+  return x > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)x;   // (t < 2^31 is the caller's promise; this keeps the value defined)
+}
+// items of the queries [q0, q0 + nq) at K speeds (clip0: first clip of every query)
+uint64_t sp_items(const uint64_t* peak_off, const uint32_t* clip0, uint32_t q0, uint32_t nq, uint32_t K);
+// one warp pass over the queries [q0, q0 + nq) at the K factors d_speed[0 .. K): sp_count counts (hash_off: n_seg + 1 entries
+// on the host, relative to the pass, segments in the order query, speed, clip; P->d_hoff the same on the device; the stream
+// is idle on return), sp_write writes (key32, t1) of the pass to device columns of cap entries.  d_poff / d_speed: the call's
+// tables on the device (sp_upload_tables).  A pass without peaks launches nothing and leaves P's pointers unset
+int32_t sp_count(shz_ctx* ctx, const uint16_t* d_pf, const uint32_t* d_pt, const uint64_t* d_poff, const uint64_t* peak_off,
+                 const uint32_t* clip0, uint32_t q0, uint32_t nq, const uint32_t* d_speed, uint32_t K, uint32_t fan, sp_pass* P,
+                 uint64_t* hash_off);
+int32_t sp_write(shz_ctx* ctx, const sp_pass& P, uint32_t* d_key, uint32_t* d_t1, uint64_t cap);
+int32_t sp_check_ladder(shz_ctx* ctx, const char* who, const uint32_t* speed_q16, uint32_t n_speeds, uint32_t fan_value);
+int32_t sp_upload_tables(shz_ctx* ctx, const uint64_t* peak_off, uint32_t n_clips, const uint32_t* speed_q16, uint32_t K,
+                         const uint64_t** d_poff, const uint32_t** d_speed);
+uint32_t sp_best(const uint32_t* top1, const uint32_t* speed_q16, uint32_t K);
+// shz_peaks of the clips into SHZ_WS_SP_PF / SHZ_WS_SP_PT (frames: of all clips together; flags: SHZ_PCM_DEVICE)
+int32_t sp_peaks_owned(shz_ctx* ctx, const char* who, const int16_t* pcm, const uint64_t* clip_off, uint32_t n_clips,
+                       uint64_t frames, uint32_t fs, double amp_min, uint32_t flags, uint64_t* peak_off, const uint16_t** d_pf,
+                       const uint32_t** d_pt);
 
 // ---- RCCL helpers (shz_comm.hip) ----------------------------------------------------------
 int32_t shz_comm_info(shz_comm* c, int* rank, int* nranks);

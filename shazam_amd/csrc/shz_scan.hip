@@ -283,3 +283,393 @@ extern "C" int32_t shz_scan_timeline(const uint64_t* win_off, uint32_t n_recs, c
   *count = n;
   return n > cap ? SHZ_E_CAPACITY : SHZ_OK;
 }
+
+// ---- scanning at an unknown speed -------------------------------------------------------------------
+// The peaks of every recording are extracted once and warped for every rung of a ladder (shz_speed.hip); the warped hash
+// list of (recording, rung, channel) has non-decreasing t1', so the window that starts at recording frame s is, at rung v,
+// the range W_v(s) <= t1' < W_v(s + window_frames) of every channel's list, W_v(x) = (x s16 + 32768) >> 16 -- two
+// lower-bound searches again.  Nothing per window is built on the host: the kernels derive s and both bounds from one
+// descriptor per recording and the rung table.  Work goes in slices of (whole recordings x a contiguous chunk of rungs);
+// inside a slice the items are (window, rung, channel), window-major, so that (window, rung) is one contiguous query of
+// the match with its channels one behind the other.
+#define SS_SMALL_RUNGS 2u   // rungs of a slice under SHZ_DEBUG_SCAN_SPEED_SMALL_SLICES (and 1 recording, 3 windows a group)
+
+struct ss_rec {        // one recording of a slice; the entry behind the last one holds the slice's totals
+  uint64_t win0;       // its first window among the slice's windows
+  uint64_t item0;      // its first (window, rung, channel) item: the sum of windows x rungs x channels in front of it
+  uint64_t seg0;       // its first segment of the warp's CSR: (rung, channel) at seg0 + rung * nch + channel
+  uint32_t nch, pad;
+};
+
+__device__ __forceinline__ uint64_t ss_warp(uint64_t x, uint32_t s16) { return (x * s16 + 32768u) >> 16; }   // sp_warp_t, unclamped (x < 2^34)
+
+// per (window, rung, channel): where the window's hashes begin in the warped list of (rung, channel), and how many they are
+__global__ __launch_bounds__(SC_THREADS) void ss_bounds_kernel(const ss_rec* __restrict__ recs, uint32_t nr, uint64_t n_items,
+                                                               const uint32_t* __restrict__ speed, uint32_t kc,
+                                                               uint32_t window_frames, uint32_t step_frames,
+                                                               const unsigned long long* __restrict__ hoff,
+                                                               const uint32_t* __restrict__ t1, uint64_t* __restrict__ first,
+                                                               uint64_t* __restrict__ cnt) {
+  const uint64_t i = (uint64_t)blockIdx.x * SC_THREADS + threadIdx.x;
+  if (i >= n_items) return;
+  uint32_t lo = 0, hi = nr;   // the last recording whose first item is <= i (recordings without windows share a start)
+  while (lo + 1 < hi) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (recs[mid].item0 <= i) lo = mid; else hi = mid;
+  }
+  const ss_rec R = recs[lo];
+  const uint64_t rem = i - R.item0, qv = rem / R.nch, c = rem - qv * R.nch, w = qv / kc, v = qv - w * kc;
+  const uint32_t s16 = speed[v];
+  const uint64_t s = w * step_frames, e = R.seg0 + v * R.nch + c;
+  const uint64_t a = hoff[e], b = hoff[e + 1];
+  const uint64_t p = sc_lower_bound(t1, a, b, ss_warp(s, s16));
+  const uint64_t q = sc_lower_bound(t1, p, b, ss_warp(s + window_frames, s16));
+  first[i] = p;
+  cnt[i] = q - p;
+}
+
+// one workgroup per (window, rung) of the group [q0, q0 + gridDim.x) of the slice's queries: its channels' ranges, one
+// behind the other, to offs[item] - base of the group's columns (offs: exclusive scan of the counts, the total behind it)
+__global__ __launch_bounds__(SC_THREADS) void ss_gather_kernel(const ss_rec* __restrict__ recs, uint32_t nr, uint64_t q0,
+                                                               const uint32_t* __restrict__ speed, uint32_t kc, uint32_t step_frames,
+                                                               const uint64_t* __restrict__ first, const uint64_t* __restrict__ offs,
+                                                               uint64_t base, uint64_t cap, const uint32_t* __restrict__ key,
+                                                               const uint32_t* __restrict__ t1, uint32_t* __restrict__ out_key,
+                                                               uint32_t* __restrict__ out_qo) {
+  const uint64_t q = q0 + blockIdx.x;
+  uint32_t lo = 0, hi = nr;   // the last recording whose first query is <= q
+  while (lo + 1 < hi) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (recs[mid].win0 * kc <= q) lo = mid; else hi = mid;
+  }
+  const ss_rec R = recs[lo];
+  const uint64_t rem = q - R.win0 * kc, w = rem / kc, v = rem - w * kc;
+  const uint32_t t0 = (uint32_t)ss_warp(w * step_frames, speed[v]);   // (a window with entries starts below their t1' < 2^32)
+  for (uint32_t c = 0; c < R.nch; ++c) {
+    const uint64_t p = R.item0 + rem * R.nch + c;
+    const uint64_t src = first[p], dst = offs[p] - base, n = offs[p + 1] - offs[p];
+    if (dst + n > cap) return;   // (uniform; the host sizes the columns from the same offsets, so this never holds)
+    for (uint64_t i = threadIdx.x; i < n; i += SC_THREADS) {
+      out_key[dst + i] = key[src + i];
+      out_qo[dst + i] = t1[src + i] - t0;
+    }
+  }
+}
+
+extern "C" int32_t shz_scan_speeds(shz_ctx* ctx, shz_table* t, const int16_t* pcm, const uint64_t* clip_off, uint32_t n_clips,
+                                   const uint32_t* rec_clip0, uint32_t n_recs, uint32_t fs, double amp_min, uint32_t fan_value,
+                                   uint32_t window_frames, uint32_t step_frames, uint32_t topn, const uint32_t* speed_q16,
+                                   uint32_t n_speeds, uint32_t flags, uint64_t* win_off, uint32_t* out_best, uint32_t* out_sid,
+                                   int32_t* out_delta, uint32_t* out_aligned, uint32_t* out_dedup, uint32_t* out_nres,
+                                   uint32_t* out_nhash, uint64_t* out_npairs, uint32_t* out_profile, uint64_t cap_windows,
+                                   uint64_t* count, float* ms_extract, float* ms_warp, float* ms_window, float* ms_match) {
+  if (!ctx || !t) return SHZ_E_INVALID;
+  if (ms_extract) *ms_extract = 0.f;
+  if (ms_warp) *ms_warp = 0.f;
+  if (ms_window) *ms_window = 0.f;
+  if (ms_match) *ms_match = 0.f;
+  if (count) *count = 0;
+  // everything that can be refused is refused before the first launch
+  if (flags & ~(SHZ_PCM_DEVICE | SHZ_MATCH_FULL_SORT)) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_scan_speeds: flags may hold SHZ_PCM_DEVICE and SHZ_MATCH_FULL_SORT");
+  if (!win_off || !count) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_scan_speeds: win_off or count is NULL");
+  if (window_frames == 0 || window_frames >= (1u << 20))
+    SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_scan_speeds: window_frames must be in [1, 2^20) (query offsets), got %u", window_frames);
+  if (step_frames == 0) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_scan_speeds: step_frames must be at least 1");
+  SHZ_TRY(sp_check_ladder(ctx, "shz_scan_speeds", speed_q16, n_speeds, fan_value));
+  const uint32_t K = n_speeds, s_max = *std::max_element(speed_q16, speed_q16 + K);
+  // no window is longer at any rung: W_v(s + window) - W_v(s) <= ceil(window s16 / 65536)
+  const uint64_t len_max = ((uint64_t)window_frames * s_max + 65535) >> 16;
+  if (len_max >= (1ull << 20))
+    SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "shz_scan_speeds: a window of %u frames at factor %u / 65536 is %llu frames long; query offsets must be < 2^20",
+             window_frames, s_max, (unsigned long long)len_max);
+  win_off[0] = 0;
+  if (n_recs == 0) {
+    if (n_clips) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_scan_speeds: %u clips belong to no recording", n_clips);
+    return SHZ_OK;
+  }
+  if (!rec_clip0) SHZ_FAIL(ctx, SHZ_E_INVALID, "rec_clip0 is NULL");
+  if (rec_clip0[0] != 0 || rec_clip0[n_recs] != n_clips)
+    SHZ_FAIL(ctx, SHZ_E_INVALID, "rec_clip0 must start at 0 and end at n_clips = %u (it runs from %u to %u)", n_clips, rec_clip0[0],
+             rec_clip0[n_recs]);
+  for (uint32_t r = 0; r < n_recs; ++r)
+    if (rec_clip0[r + 1] < rec_clip0[r]) SHZ_FAIL(ctx, SHZ_E_INVALID, "rec_clip0 decreases at recording %u", r);
+  if (!clip_off) SHZ_FAIL(ctx, SHZ_E_INVALID, "clip_off is NULL");
+  for (uint32_t c = 0; c < n_clips; ++c)
+    if (clip_off[c + 1] < clip_off[c]) SHZ_FAIL(ctx, SHZ_E_INVALID, "clip_off decreases at clip %u", c);
+  if (fs == 0) SHZ_FAIL(ctx, SHZ_E_INVALID, "Fs must be > 0");
+  if (n_clips && !pcm && clip_off[n_clips] > clip_off[0]) SHZ_FAIL(ctx, SHZ_E_INVALID, "pcm is NULL");
+  SHZ_TRY(shz_match_ready(ctx, t, topn));
+  // the windows: their number follows from the frame counts alone, in the recording's own frames
+  uint64_t n_wins = 0, frames = 0;
+  for (uint32_t r = 0; r < n_recs; ++r) {
+    uint64_t f = 0;
+    for (uint32_t c = rec_clip0[r]; c < rec_clip0[r + 1]; ++c) {
+      const uint64_t fc = shz_frame_count_hop(clip_off[c + 1] - clip_off[c], ctx->hop);
+      f = std::max<uint64_t>(f, fc);
+      frames += fc;
+    }
+    n_wins += shz_scan_window_count(f, window_frames, step_frames);
+    win_off[r + 1] = n_wins;
+  }
+  *count = n_wins;
+  if (n_wins > cap_windows)
+    SHZ_FAIL(ctx, SHZ_E_CAPACITY, "shz_scan_speeds: %llu windows, room for %llu", (unsigned long long)n_wins, (unsigned long long)cap_windows);
+  if (n_wins == 0) return SHZ_OK;
+  if (!out_best || !out_sid || !out_delta || !out_aligned || !out_dedup || !out_nres) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_scan_speeds: NULL buffer");
+  SHZ_HIP(ctx, hipSetDevice(ctx->device));
+  const bool timed = ms_extract || ms_warp || ms_window || ms_match;
+  if (timed) {
+    for (hipEvent_t& e : ctx->sc_ev)
+      if (!e) SHZ_HIP(ctx, hipEventCreate(&e));
+    SHZ_HIP(ctx, hipEventRecord(ctx->sc_ev[0], ctx->stream));
+  }
+  // 1) the peaks of every clip, once, into the library's own buffers
+  std::vector<uint64_t> peak_off((size_t)n_clips + 1, 0);
+  const uint16_t* d_pf = nullptr;
+  const uint32_t* d_pt = nullptr;
+  SHZ_TRY(sp_peaks_owned(ctx, "shz_scan_speeds", pcm, clip_off, n_clips, frames, fs, amp_min, flags & SHZ_PCM_DEVICE, peak_off.data(),
+                         &d_pf, &d_pt));
+  if (timed) {
+    SHZ_HIP(ctx, hipEventRecord(ctx->sc_ev[1], ctx->stream));
+    SHZ_HIP(ctx, hipEventSynchronize(ctx->sc_ev[1]));
+    if (ms_extract) SHZ_HIP(ctx, hipEventElapsedTime(ms_extract, ctx->sc_ev[0], ctx->sc_ev[1]));
+  }
+  const uint64_t* d_poff;
+  const uint32_t* d_speed;
+  SHZ_TRY(sp_upload_tables(ctx, peak_off.data(), n_clips, speed_q16, K, &d_poff, &d_speed));
+  // 2) slices of whole recordings x a chunk of rungs: the entries a slice's warp can yield at most (every peak with all its
+  // partners, at every rung of the chunk) stay within the match's pair budget and 1/8 of the workspace limit.  The ladder
+  // is cut only where one recording at all rungs is beyond that; one (recording, rung) beyond it is a slice of its own
+  const bool small = (ctx->debug & SHZ_DEBUG_SCAN_SPEED_SMALL_SLICES) != 0;
+  const uint64_t per_item = std::max<uint32_t>(fan_value - 1, 1);
+  const uint64_t warp_entries = std::min<uint64_t>(std::max<uint64_t>(ctx->ws_limit / 64, 1), 1ull << 28);
+  const uint64_t group_entries = std::min<uint64_t>(std::max<uint64_t>(ctx->ws_limit / 64, 1), 1ull << 30);
+  const int64_t bias = (int64_t)len_max - 1;
+  auto dist = [&](uint32_t v) { return speed_q16[v] > SP_S_ONE ? speed_q16[v] - SP_S_ONE : SP_S_ONE - speed_q16[v]; };
+  std::vector<uint32_t> best_top1((size_t)n_wins, 0);
+  std::vector<uint32_t> v_sid, v_aligned, v_dedup, v_nres, v_nhash;
+  std::vector<int32_t> v_delta;
+  std::vector<uint64_t> v_npairs, ho, offs, win_item, query_off;
+  std::vector<ss_rec> hrec;
+  float warp_ms = 0.f, win_ms = 0.f, match_ms = 0.f;
+  for (uint32_t r0 = 0; r0 < n_recs;) {
+    uint32_t nr = 1, kc = K;
+    const uint64_t one = sp_items(peak_off.data(), rec_clip0, r0, 1, 1) * per_item;   // one rung of the first recording
+    if (one * K > warp_entries) kc = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(warp_entries / std::max<uint64_t>(one, 1), 1), K);
+    if (small) kc = std::min(kc, SS_SMALL_RUNGS);
+    if (kc == K && !small)
+      while (r0 + nr < n_recs && sp_items(peak_off.data(), rec_clip0, r0, nr + 1, K) * per_item <= warp_entries &&
+             (win_off[r0 + nr + 1] - win_off[r0]) * K <= (1ull << 24))
+        ++nr;
+    const uint64_t nws = win_off[r0 + nr] - win_off[r0];   // windows of the slice
+    if (nws == 0) {
+      r0 += nr;
+      continue;
+    }
+    for (uint32_t v0 = 0; v0 < K; v0 += kc) {
+      const uint32_t kcc = std::min(kc, K - v0);
+      // 2a) the warp of the slice: hashes of (recording, rung, channel), the exact CSR on both sides
+      if (timed) SHZ_HIP(ctx, hipEventRecord(ctx->sc_ev[2], ctx->stream));
+      const uint64_t n_seg = (uint64_t)(rec_clip0[r0 + nr] - rec_clip0[r0]) * kcc;
+      ho.assign((size_t)n_seg + 1, 0);
+      sp_pass P;
+      SHZ_TRY(sp_count(ctx, d_pf, d_pt, d_poff, peak_off.data(), rec_clip0, r0, nr, d_speed + v0, kcc, fan_value, &P, ho.data()));
+      const uint64_t total = ho[n_seg];
+      void *d_key, *d_t1;
+      SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SP_KEY, total * 4 + 64, &d_key));
+      SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SP_T1, total * 4 + 64, &d_t1));
+      if (total) SHZ_TRY(sp_write(ctx, P, (uint32_t*)d_key, (uint32_t*)d_t1, total));
+      if (timed) SHZ_HIP(ctx, hipEventRecord(ctx->sc_ev[3], ctx->stream));
+      // 2b) the windows of the slice: one descriptor a recording, bounds, scan, one read-back of the offsets
+      hrec.assign((size_t)nr + 1, ss_rec{0, 0, 0, 0, 0});
+      win_item.assign((size_t)nws + 1, 0);
+      uint64_t n_items = 0;
+      for (uint32_t r = 0; r < nr; ++r) {
+        const uint32_t c0 = rec_clip0[r0 + r], nch = rec_clip0[r0 + r + 1] - c0;
+        const uint64_t w0 = win_off[r0 + r] - win_off[r0], nw = win_off[r0 + r + 1] - win_off[r0 + r];
+        hrec[r] = ss_rec{w0, n_items, (uint64_t)(c0 - rec_clip0[r0]) * kcc, nch, 0};
+        for (uint64_t w = 0; w < nw; ++w) win_item[w0 + w] = n_items + w * kcc * nch;
+        n_items += nw * kcc * nch;
+      }
+      hrec[nr] = ss_rec{nws, n_items, n_seg, 0, 0};
+      win_item[nws] = n_items;
+      void *d_rec, *d_ctl;
+      SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SC_JOBS, ((uint64_t)nr + 1) * sizeof(ss_rec), &d_rec));
+      SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SC_CTL, (3 * n_items + 1) * 8, &d_ctl));
+      uint64_t *d_first = (uint64_t*)d_ctl, *d_cnt = d_first + n_items, *d_offs = d_cnt + n_items;   // d_offs[n_items] = the total
+      offs.assign((size_t)n_items + 1, 0);
+      if (total) {   // (without hashes every window is empty, and the pass has no CSR on the device)
+        SHZ_HIP(ctx, shz_memcpy(ctx, d_rec, hrec.data(), ((uint64_t)nr + 1) * sizeof(ss_rec), hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(ss_bounds_kernel, dim3((unsigned)((n_items + SC_THREADS - 1) / SC_THREADS)), dim3(SC_THREADS), 0, ctx->stream,
+                           (const ss_rec*)d_rec, nr, n_items, d_speed + v0, kcc, window_frames, step_frames,
+                           (const unsigned long long*)P.d_hoff, (const uint32_t*)d_t1, d_first, d_cnt);
+        SHZ_HIP(ctx, hipGetLastError());
+        SHZ_TRY(shz_scan_u64(ctx, d_cnt, d_offs, n_items, d_offs + n_items));
+        SHZ_HIP(ctx, shz_memcpy(ctx, offs.data(), d_offs, (n_items + 1) * 8, hipMemcpyDeviceToHost));
+      }
+      if (timed) SHZ_HIP(ctx, hipEventRecord(ctx->sc_ev[4], ctx->stream));
+      SHZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
+      if (timed) {
+        float a = 0.f, b = 0.f;
+        SHZ_HIP(ctx, hipEventElapsedTime(&a, ctx->sc_ev[2], ctx->sc_ev[3]));
+        SHZ_HIP(ctx, hipEventElapsedTime(&b, ctx->sc_ev[3], ctx->sc_ev[4]));
+        warp_ms += a;
+        win_ms += b;
+      }
+      // a hash lies in at most ceil(window / step) windows, +1 where the warp's rounding moves a border
+      const uint64_t rep = ((uint64_t)window_frames + step_frames - 1) / step_frames + 1;
+      if (offs[n_items] > total * rep)
+        SHZ_FAIL(ctx, SHZ_E_STATE, "shz_scan_speeds: %llu window entries from %llu hashes", (unsigned long long)offs[n_items],
+                 (unsigned long long)total);
+      auto win_at = [&](uint64_t w) { return offs[win_item[w]]; };
+      // 2c) group by group: gather the columns of (window, rung), match them where they lie.  A window's rungs stay together
+      const uint64_t max_wins = small ? SC_SMALL_GROUP : std::max<uint64_t>((1ull << 24) / kcc, 1);
+      const uint64_t nvq = nws * kcc;
+      v_sid.assign(nvq * topn, 0); v_aligned.assign(nvq * topn, 0); v_dedup.assign(nvq * topn, 0); v_delta.assign(nvq * topn, 0);
+      v_nres.assign(nvq, 0); v_nhash.assign(nvq, 0); v_npairs.assign(nvq, 0);
+      for (uint64_t g0 = 0; g0 < nws;) {
+        uint64_t g1 = g0 + 1;
+        while (g1 < nws && g1 - g0 < max_wins && win_at(g1 + 1) - win_at(g0) <= group_entries) ++g1;
+        const uint64_t base = win_at(g0), m = win_at(g1) - base, nq = (g1 - g0) * kcc;
+        void *d_gk, *d_gq;
+        SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SC_KEY, m * 4 + 64, &d_gk));
+        SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SC_QO, m * 4 + 64, &d_gq));
+        if (timed) SHZ_HIP(ctx, hipEventRecord(ctx->sc_ev[2], ctx->stream));
+        if (m) {
+          hipLaunchKernelGGL(ss_gather_kernel, dim3((unsigned)nq), dim3(SC_THREADS), 0, ctx->stream, (const ss_rec*)d_rec, nr, g0 * kcc,
+                             d_speed + v0, kcc, step_frames, (const uint64_t*)d_first, (const uint64_t*)d_offs, base, m,
+                             (const uint32_t*)d_key, (const uint32_t*)d_t1, (uint32_t*)d_gk, (uint32_t*)d_gq);
+          SHZ_HIP(ctx, hipGetLastError());
+        }
+        if (timed) SHZ_HIP(ctx, hipEventRecord(ctx->sc_ev[3], ctx->stream));
+        query_off.resize((size_t)nq + 1);
+        for (uint64_t w = g0; w < g1; ++w) {
+          const uint64_t nch = (win_item[w + 1] - win_item[w]) / kcc;
+          for (uint32_t v = 0; v < kcc; ++v) query_off[(size_t)((w - g0) * kcc + v)] = offs[win_item[w] + v * nch] - base;
+        }
+        query_off[nq] = m;
+        const uint64_t o = g0 * kcc;
+        SHZ_TRY(shz_match_device(ctx, t, (const uint32_t*)d_gk, (const uint32_t*)d_gq, query_off.data(), (uint32_t)nq, topn,
+                                 flags & SHZ_MATCH_FULL_SORT, bias, v_sid.data() + o * topn, v_delta.data() + o * topn,
+                                 v_aligned.data() + o * topn, v_dedup.data() + o * topn, v_nres.data() + o, v_nhash.data() + o,
+                                 v_npairs.data() + o));
+        if (timed) {
+          float a = 0.f, b = 0.f;
+          SHZ_HIP(ctx, hipEventRecord(ctx->sc_ev[4], ctx->stream));
+          SHZ_HIP(ctx, hipEventSynchronize(ctx->sc_ev[4]));
+          SHZ_HIP(ctx, hipEventElapsedTime(&a, ctx->sc_ev[2], ctx->sc_ev[3]));
+          SHZ_HIP(ctx, hipEventElapsedTime(&b, ctx->sc_ev[3], ctx->sc_ev[4]));
+          win_ms += a;
+          match_ms += b;
+        }
+        g0 = g1;
+      }
+      // 2d) the best rung of every window, folded over the chunks (sp_best's rule: rungs come in index order)
+      for (uint64_t w = 0; w < nws; ++w) {
+        const uint64_t gw = win_off[r0] + w;
+        for (uint32_t v = 0; v < kcc; ++v) {
+          const uint64_t src = w * kcc + v;
+          const uint32_t top1 = v_nres[src] ? v_aligned[src * topn] : 0u, gv = v0 + v;
+          if (out_profile) out_profile[gw * K + gv] = top1;
+          if (gv != 0 && !(top1 > best_top1[gw] || (top1 == best_top1[gw] && dist(gv) < dist(out_best[gw])))) continue;
+          best_top1[gw] = top1;
+          out_best[gw] = gv;
+          memcpy(out_sid + gw * topn, v_sid.data() + src * topn, (size_t)topn * 4);
+          memcpy(out_delta + gw * topn, v_delta.data() + src * topn, (size_t)topn * 4);
+          memcpy(out_aligned + gw * topn, v_aligned.data() + src * topn, (size_t)topn * 4);
+          memcpy(out_dedup + gw * topn, v_dedup.data() + src * topn, (size_t)topn * 4);
+          out_nres[gw] = v_nres[src];
+          if (out_nhash) out_nhash[gw] = v_nhash[src];
+          if (out_npairs) out_npairs[gw] = v_npairs[src];
+        }
+      }
+    }
+    r0 += nr;
+  }
+  if (ms_warp) *ms_warp = warp_ms;
+  if (ms_window) *ms_window = win_ms;
+  if (ms_match) *ms_match = match_ms;
+  return SHZ_OK;
+}
+
+// The per-window answers of a speed-tolerant scan folded into segments, on the host.  delta - w step is not constant when
+// the recording plays at another speed than the table's copy, so continuity is judged between neighbouring hits.
+extern "C" int32_t shz_scan_timeline_speeds(const uint64_t* win_off, uint32_t n_recs, const uint32_t* sid, const int32_t* delta,
+                                            const uint32_t* aligned, const uint32_t* nres, const uint32_t* best, uint32_t topn,
+                                            uint32_t step_frames, const uint32_t* speed_q16, uint32_t n_speeds,
+                                            uint32_t min_aligned, uint32_t max_gap, uint32_t rung_tol, uint32_t shift_tol,
+                                            uint32_t* seg_rec, uint32_t* seg_sid, uint32_t* seg_first, uint32_t* seg_last,
+                                            uint32_t* seg_hits, uint32_t* seg_best, int32_t* seg_pos_first, int32_t* seg_pos_last,
+                                            uint32_t* seg_rung, uint64_t cap, uint64_t* count) {
+  if (!count) return SHZ_E_INVALID;
+  *count = 0;
+  if (n_recs == 0) return SHZ_OK;
+  if (!win_off || topn == 0 || !speed_q16 || n_speeds == 0 || n_speeds > SP_MAX_SPEEDS) return SHZ_E_INVALID;
+  for (uint32_t v = 0; v < n_speeds; ++v)
+    if (speed_q16[v] < SP_S_MIN || speed_q16[v] > SP_S_MAX) return SHZ_E_INVALID;
+  for (uint32_t r = 0; r < n_recs; ++r)
+    if (win_off[r + 1] < win_off[r] || win_off[r + 1] - win_off[r] > 0xFFFFFFFFull) return SHZ_E_INVALID;
+  if (win_off[n_recs] > win_off[0] && (!sid || !delta || !aligned || !nres || !best)) return SHZ_E_INVALID;
+  if (cap && (!seg_rec || !seg_sid || !seg_first || !seg_last || !seg_hits || !seg_best || !seg_pos_first || !seg_pos_last || !seg_rung))
+    return SHZ_E_INVALID;
+  for (uint64_t g = win_off[0]; g < win_off[n_recs]; ++g)
+    if (best[g] >= n_speeds) return SHZ_E_INVALID;
+  std::vector<uint32_t> chosen(n_speeds, 0);   // how often the open segment's hits chose every rung
+  uint64_t n = 0;
+  for (uint32_t r = 0; r < n_recs; ++r) {
+    bool open = false;
+    uint32_t o_sid = 0, o_first = 0, o_last = 0, o_hits = 0, o_best = 0, o_rung = 0;
+    int64_t o_pos_first = 0, o_pos_last = 0;
+    auto close = [&]() {
+      if (open && n < cap) {
+        seg_rec[n] = r;
+        seg_sid[n] = o_sid;
+        seg_first[n] = o_first;
+        seg_last[n] = o_last;
+        seg_hits[n] = o_hits;
+        seg_best[n] = o_best;
+        seg_pos_first[n] = (int32_t)o_pos_first;
+        seg_pos_last[n] = (int32_t)o_pos_last;
+        seg_rung[n] = sp_best(chosen.data(), speed_q16, n_speeds);
+      }
+      n += open ? 1 : 0;
+      open = false;
+    };
+    const uint64_t nw = win_off[r + 1] - win_off[r];
+    for (uint64_t w = 0; w < nw; ++w) {
+      const uint64_t g = win_off[r] + w;
+      if (nres[g] < 1 || aligned[g * topn] < min_aligned) continue;   // no hit: changes nothing
+      const uint32_t s = sid[g * topn], a = aligned[g * topn], v = best[g];
+      const int64_t pos = delta[g * topn];
+      bool cont = open && s == o_sid && w - o_last - 1 <= max_gap && (v > o_rung ? v - o_rung : o_rung - v) <= rung_tol;
+      if (cont) {
+        // the song advances W_v((w - w_last) step) frames between the two windows' starts
+        const int64_t adv = (int64_t)((((w - o_last) * (uint64_t)step_frames) * speed_q16[v] + 32768u) >> 16);
+        const int64_t off = pos - o_pos_last - adv;
+        cont = (off < 0 ? -off : off) <= (int64_t)shift_tol;
+      }
+      if (cont) {
+        o_last = (uint32_t)w;
+        ++o_hits;
+        o_best = std::max(o_best, a);
+        o_pos_last = pos;
+        o_rung = v;
+        ++chosen[v];
+        continue;
+      }
+      close();
+      open = true;
+      o_sid = s;
+      o_first = o_last = (uint32_t)w;
+      o_hits = 1;
+      o_best = a;
+      o_pos_first = o_pos_last = pos;
+      o_rung = v;
+      std::fill(chosen.begin(), chosen.end(), 0u);
+      chosen[v] = 1;
+    }
+    close();
+  }
+  *count = n;
+  return n > cap ? SHZ_E_CAPACITY : SHZ_OK;
+}

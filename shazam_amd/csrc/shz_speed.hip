@@ -23,33 +23,15 @@
 #include "shz_internal.h"
 
 #define SP_THREADS 256
-#define SP_S_MIN 32768u
-#define SP_S_ONE 65536u
-#define SP_S_MAX 131072u
-#define SP_MAX_SPEEDS 1024u
 #define SP_F_MAX 2048u          // the last bin of the spectrogram (SHZ_NBINS - 1)
 #define SP_SMALL_SLICE 2u       // queries of a match slice under SHZ_DEBUG_SPEED_SMALL_SLICES
 
-struct sp_view {              // what the kernels of one pass read (device pointers)
-  const uint16_t* pf;         // peaks of all clips, (clip, t asc, f asc)
-  const uint32_t* pt;
-  const uint64_t* poff;       // n_clips + 1
-  const uint64_t* qbase;      // nq + 1: first item of every query of the pass (query q has peaks(q) x K items)
-  const uint32_t* clip0;      // nq + 1: first clip of every query of the pass
-  const uint32_t* speed;      // K
-  uint32_t nq, K, fan;
-  uint64_t n_items;
-};
 struct sp_item {
   uint32_t c, s16;
   uint64_t g, c_lo, c_hi;     // the peak, and the peaks of its clip
   uint64_t seg0, seg_n;       // first item of its (query, speed, clip), items of it
 };
 
-__host__ __device__ __forceinline__ uint32_t sp_warp_t(uint32_t t, uint32_t s16) {
-  const uint64_t x = ((uint64_t)t * s16 + 32768u) >> 16;
-  return x > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)x;   // (t < 2^31 is the caller's promise; this keeps the value defined)
-}
 __host__ __device__ __forceinline__ uint32_t sp_warp_f(uint32_t f, uint32_t s16) {
   if (f < 16384u) return ((f << 17) + s16) / (2u * s16);   // fits 32 bits: every bin of the spectrogram
   return (uint32_t)((((uint64_t)f << 17) + s16) / (2ull * s16));
@@ -212,25 +194,16 @@ __global__ __launch_bounds__(SP_THREADS) void sp_write_kernel(uint64_t n_items, 
   }
 }
 
-// ---- one warp pass over the queries [q0, q0 + nq): count (exact CSR on the host), then write
-struct sp_pass {
-  sp_view V;
-  uint64_t n_seg;
-  uint32_t *a, *b;            // flags, then partner counts | places, then hash offsets
-  uint16_t* wf;
-  uint32_t *wt, *segstart;
-  unsigned long long *d_hoff, *d_tot;   // hash_off[n_seg + 1] | kept peaks, hashes
-};
-
+// ---- one warp pass over the queries [q0, q0 + nq): count (exact CSR on the host), then write (sp_pass: shz_internal.h)
 static unsigned sp_blocks(uint64_t n) { return (unsigned)((n + SP_THREADS - 1) / SP_THREADS); }
 
 // items of the queries [q0, q0 + nq) at K speeds, and the entries they can yield at most
-static uint64_t sp_items(const uint64_t* peak_off, const uint32_t* clip0, uint32_t q0, uint32_t nq, uint32_t K) {
+uint64_t sp_items(const uint64_t* peak_off, const uint32_t* clip0, uint32_t q0, uint32_t nq, uint32_t K) {
   return (peak_off[clip0[q0 + nq]] - peak_off[clip0[q0]]) * K;
 }
 
 // hash_off: n_seg + 1 entries (host), relative to the pass.  d_poff / d_speed: the call's tables on the device.
-static int32_t sp_count(shz_ctx* ctx, const uint16_t* d_pf, const uint32_t* d_pt, const uint64_t* d_poff, const uint64_t* peak_off,
+int32_t sp_count(shz_ctx* ctx, const uint16_t* d_pf, const uint32_t* d_pt, const uint64_t* d_poff, const uint64_t* peak_off,
                         const uint32_t* clip0, uint32_t q0, uint32_t nq, const uint32_t* d_speed, uint32_t K, uint32_t fan,
                         sp_pass* P, uint64_t* hash_off) {
   const uint64_t n_items = sp_items(peak_off, clip0, q0, nq, K);
@@ -289,7 +262,7 @@ static int32_t sp_count(shz_ctx* ctx, const uint16_t* d_pf, const uint32_t* d_pt
   return SHZ_OK;
 }
 
-static int32_t sp_write(shz_ctx* ctx, const sp_pass& P, uint32_t* d_key, uint32_t* d_t1, uint64_t cap) {
+int32_t sp_write(shz_ctx* ctx, const sp_pass& P, uint32_t* d_key, uint32_t* d_t1, uint64_t cap) {
   if (P.V.n_items == 0) return SHZ_OK;
   hipLaunchKernelGGL(sp_write_kernel, dim3(sp_blocks(P.V.n_items)), dim3(SP_THREADS), 0, ctx->stream, P.V.n_items,
                      (const unsigned long long*)P.d_tot, (const uint32_t*)P.segstart, P.n_seg, (const uint16_t*)P.wf,
@@ -299,7 +272,7 @@ static int32_t sp_write(shz_ctx* ctx, const sp_pass& P, uint32_t* d_key, uint32_
 }
 
 // what both entry points refuse about a ladder and about the queries' clips, before anything is launched
-static int32_t sp_check_ladder(shz_ctx* ctx, const char* who, const uint32_t* speed_q16, uint32_t n_speeds, uint32_t fan_value) {
+int32_t sp_check_ladder(shz_ctx* ctx, const char* who, const uint32_t* speed_q16, uint32_t n_speeds, uint32_t fan_value) {
   if (n_speeds == 0 || n_speeds > SP_MAX_SPEEDS)
     SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: n_speeds must be in [1, %u], got %u", who, SP_MAX_SPEEDS, n_speeds);
   if (!speed_q16) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: speed_q16 is NULL", who);
@@ -321,7 +294,7 @@ static int32_t sp_check_queries(shz_ctx* ctx, const uint32_t* query_clip0, uint3
 }
 
 // peak_off | speeds on the device (one block of the call)
-static int32_t sp_upload_tables(shz_ctx* ctx, const uint64_t* peak_off, uint32_t n_clips, const uint32_t* speed_q16, uint32_t K,
+int32_t sp_upload_tables(shz_ctx* ctx, const uint64_t* peak_off, uint32_t n_clips, const uint32_t* speed_q16, uint32_t K,
                                 const uint64_t** d_poff, const uint32_t** d_speed) {
   const uint64_t po_bytes = ((uint64_t)n_clips + 1) * 8, bytes = po_bytes + (uint64_t)K * 4;
   std::vector<char> h(bytes);
@@ -410,12 +383,43 @@ extern "C" int32_t shz_warp_pair_hash(shz_ctx* ctx, const uint16_t* peak_f, cons
 }
 
 // index of the greatest top-1 aligned count; ties to the factor nearest 65536, then to the lower index
-static uint32_t sp_best(const uint32_t* top1, const uint32_t* speed_q16, uint32_t K) {
+uint32_t sp_best(const uint32_t* top1, const uint32_t* speed_q16, uint32_t K) {
   auto dist = [&](uint32_t v) { return speed_q16[v] > SP_S_ONE ? speed_q16[v] - SP_S_ONE : SP_S_ONE - speed_q16[v]; };
   uint32_t best = 0;
   for (uint32_t v = 1; v < K; ++v)
     if (top1[v] > top1[best] || (top1[v] == top1[best] && dist(v) < dist(best))) best = v;
   return best;
+}
+
+// shz_peaks of the clips into the slots SHZ_WS_SP_PF / SHZ_WS_SP_PT, sized from the frame counts and repeated with the room
+// the pass asked for: *d_pf / *d_pt are the lists, peak_off[n_clips + 1] (host) their CSR.  frames: of all clips together.
+// flags: SHZ_PCM_DEVICE.  No clips: nothing runs
+int32_t sp_peaks_owned(shz_ctx* ctx, const char* who, const int16_t* pcm, const uint64_t* clip_off, uint32_t n_clips,
+                       uint64_t frames, uint32_t fs, double amp_min, uint32_t flags, uint64_t* peak_off, const uint16_t** d_pf,
+                       const uint32_t** d_pt) {
+  void *pf = nullptr, *pt = nullptr;
+  if (n_clips) {
+    uint64_t pcap = frames * 16 + 4096;
+    const uint64_t have = std::min(ctx->ws[SHZ_WS_SP_PF].cap / 2, ctx->ws[SHZ_WS_SP_PT].cap / 4);
+    if (have > 64) pcap = std::max(pcap, have - 64);
+    for (int attempt = 0;; ++attempt) {
+      SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SP_PF, pcap * 2 + 64, &pf));
+      SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SP_PT, pcap * 4 + 64, &pt));
+      uint64_t cnt = 0;
+      const int32_t rc = shz_peaks(ctx, pcm, clip_off, n_clips, fs, amp_min, (flags & SHZ_PCM_DEVICE) | SHZ_OUT_DEVICE,
+                                   (uint16_t*)pf, (uint32_t*)pt, peak_off, pcap, &cnt);
+      if (rc == SHZ_E_CAPACITY && attempt < 2 && cnt > pcap) {
+        pcap = 2 * cnt + 4096;   // (twice: the per-clip fp64 splice parks a redone clip's entries behind the batch's)
+        continue;
+      }
+      if (rc == SHZ_E_CAPACITY) SHZ_FAIL(ctx, SHZ_E_STATE, "%s: the extraction needs %llu peaks after it was given %llu", who, (unsigned long long)cnt, (unsigned long long)pcap);
+      SHZ_TRY(rc);
+      break;
+    }
+  }
+  *d_pf = (const uint16_t*)pf;
+  *d_pt = (const uint32_t*)pt;
+  return SHZ_OK;
 }
 
 extern "C" int32_t shz_recognize_speeds(shz_ctx* ctx, shz_table* t, const int16_t* pcm, const uint64_t* clip_off, uint32_t n_clips,
@@ -464,26 +468,10 @@ extern "C" int32_t shz_recognize_speeds(shz_ctx* ctx, shz_table* t, const int16_
   }
   // 1) the peaks of every clip, once, into the library's own buffers
   std::vector<uint64_t> peak_off((size_t)n_clips + 1, 0);
-  void *d_pf = nullptr, *d_pt = nullptr;
-  if (n_clips) {
-    uint64_t pcap = frames * 16 + 4096;
-    const uint64_t have = std::min(ctx->ws[SHZ_WS_SP_PF].cap / 2, ctx->ws[SHZ_WS_SP_PT].cap / 4);
-    if (have > 64) pcap = std::max(pcap, have - 64);
-    for (int attempt = 0;; ++attempt) {
-      SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SP_PF, pcap * 2 + 64, &d_pf));
-      SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SP_PT, pcap * 4 + 64, &d_pt));
-      uint64_t cnt = 0;
-      const int32_t rc = shz_peaks(ctx, pcm, clip_off, n_clips, fs, amp_min, (flags & SHZ_PCM_DEVICE) | SHZ_OUT_DEVICE,
-                                   (uint16_t*)d_pf, (uint32_t*)d_pt, peak_off.data(), pcap, &cnt);
-      if (rc == SHZ_E_CAPACITY && attempt < 2 && cnt > pcap) {
-        pcap = 2 * cnt + 4096;   // (twice: the per-clip fp64 splice parks a redone clip's entries behind the batch's)
-        continue;
-      }
-      if (rc == SHZ_E_CAPACITY) SHZ_FAIL(ctx, SHZ_E_STATE, "shz_recognize_speeds: the extraction needs %llu peaks after it was given %llu", (unsigned long long)cnt, (unsigned long long)pcap);
-      SHZ_TRY(rc);
-      break;
-    }
-  }
+  const uint16_t* d_pf = nullptr;
+  const uint32_t* d_pt = nullptr;
+  SHZ_TRY(sp_peaks_owned(ctx, "shz_recognize_speeds", pcm, clip_off, n_clips, frames, fs, amp_min, flags & SHZ_PCM_DEVICE,
+                         peak_off.data(), &d_pf, &d_pt));
   if (timed) SHZ_HIP(ctx, hipEventRecord(ctx->sp_ev[1], ctx->stream));
   const uint64_t* d_poff;
   const uint32_t* d_speed;
@@ -508,7 +496,7 @@ extern "C" int32_t shz_recognize_speeds(shz_ctx* ctx, shz_table* t, const int16_
     const uint64_t n_seg = (uint64_t)(query_clip0[q0 + nq] - query_clip0[q0]) * K;
     ho.assign((size_t)n_seg + 1, 0);
     sp_pass P;
-    SHZ_TRY(sp_count(ctx, (const uint16_t*)d_pf, (const uint32_t*)d_pt, d_poff, peak_off.data(), query_clip0, q0, nq, d_speed, K,
+    SHZ_TRY(sp_count(ctx, d_pf, d_pt, d_poff, peak_off.data(), query_clip0, q0, nq, d_speed, K,
                      fan_value, &P, ho.data()));
     const uint64_t total = ho[n_seg];
     void *d_key, *d_t1;
