@@ -123,6 +123,18 @@ int32_t shz_sort_keys32(shz_ctx* ctx, const uint32_t* keys, uint64_t n, uint32_t
 int32_t shz_sort_keys32_seg(shz_ctx* ctx, const uint32_t* keys, const uint64_t* seg_off, uint32_t n_segs, uint32_t bit_lo,
                             uint32_t bit_hi, uint32_t* out);
 
+/* The device exclusive scans every stage computes its offsets with (tests / tools): out[i] = x[0] + ... + x[i-1], *total =
+ * the sum of all n, where x[i] is in[i] (SHZ_SCAN_U32: u32 in, u32 out; SHZ_SCAN_U64: u64 in, u64 out) or
+ * popcount(in[i]) (SHZ_SCAN_POPC64: u64 in, u32 out).  in / out / total are HOST arrays, out of n elements; total may be
+ * NULL (the device scan then gets no total pointer).  in_place != 0 runs the device scan with its output on its input
+ * (u32 and u64 only: SHZ_E_INVALID for popc64).  The 32-bit kinds form their sums in 32 bits: exact while the total is
+ * at most 2^32 - 1.  n = 0: *total = 0. */
+#define SHZ_SCAN_U32 0u
+#define SHZ_SCAN_POPC64 1u
+#define SHZ_SCAN_U64 2u
+int32_t shz_scan_host(shz_ctx* ctx, uint32_t kind, const void* in, void* out, uint64_t n, uint32_t in_place,
+                      uint64_t* total);
+
 /* Query preparation (bench / tests): exact sum of squares of each clip (device PCM, clip-major, equal
  * lengths) to HOST, and out = clip(rint(sig + scale[c] * noise)) on the device: the digital form of
  * get_noise_from_sound + sf.write (recognizer_test.py:426-435, 557); twin: oracle/synth.mix_query. */

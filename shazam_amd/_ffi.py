@@ -16,6 +16,7 @@ PCM_DEVICE, OUT_DEVICE, IN_DEVICE, STFT_POWER, MATCH_FULL_SORT, RESERVE_GATHER, 
 DEBUG_VT_TINY_HEAVY, DEBUG_VT_PROBE1, DEBUG_RUN_LIMIT_SMALL, DEBUG_SCAN_SMALL_GROUPS = 1, 2, 4, 8
 DEBUG_SPEED_SMALL_SLICES = 16   # shz_recognize_speeds: at most 2 queries a slice
 DEBUG_SCAN_SPEED_SMALL_SLICES = 32   # shz_scan_speeds: at most 1 recording x 2 rungs a slice, 3 windows a match group
+SCAN_U32, SCAN_POPC64, SCAN_U64 = 0, 1, 2   # shz_scan_host kinds
 RUN_ROWS_MAX, RUN_ROWS_MAX_SMALL = (1 << 32) - 4096, 65536
 NFFT, HOP, NBINS = 4096, 2048, 2049
 
@@ -53,6 +54,7 @@ SIGNATURES = {
     "shz_sort_pairs": (C.c_int32, [vp, vp, vp, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32]),
     "shz_sort_keys32": (C.c_int32, [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, vp]),
     "shz_sort_keys32_seg": (C.c_int32, [vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp]),
+    "shz_scan_host": (C.c_int32, [vp, C.c_uint32, vp, vp, C.c_uint64, C.c_uint32, u64p]),
     "shz_frame_count": (C.c_uint32, [C.c_uint64]),
     "shz_frame_count_hop": (C.c_uint32, [C.c_uint64, C.c_uint32]),
     "shz_set_overlap": (C.c_int32, [vp, C.c_uint32]),
@@ -370,6 +372,17 @@ class Context:
         self.check(lib().shz_sort_pairs(self.h, k.ctypes.data, v.ctypes.data if v is not None else None, vb, k.size,
                                         int(bit_lo), int(bit_hi)))
         return (k, v) if v is not None else k
+
+    def scan_prim(self, kind: int, values: np.ndarray, in_place: bool = False, want_total: bool = True):
+        """The device exclusive scan of shz_prims.hip as the stages call it: kind SCAN_U32 (uint32 -> uint32), SCAN_POPC64
+        (popcount of uint64 words -> uint32) or SCAN_U64 (uint64 -> uint64).  Returns (out, total); total is None without
+        want_total (the device scan then gets no total pointer).  in_place: the device output is the device input."""
+        x = np.ascontiguousarray(values, np.uint32 if kind == SCAN_U32 else np.uint64)
+        out = np.empty(len(x), np.uint64 if kind == SCAN_U64 else np.uint32)
+        tot = C.c_uint64(0xDEADBEEF)
+        self.check(lib().shz_scan_host(self.h, int(kind), ptr(x), ptr(out), len(x), 1 if in_place else 0,
+                                       C.byref(tot) if want_total else None))
+        return out, (int(tot.value) if want_total else None)
 
     def set_workspace_limit(self, nbytes):
         self.check(lib().shz_set_workspace_limit(self.h, int(nbytes)))

@@ -189,9 +189,13 @@ struct shz_prof_scope {
 };
 
 // ---- device primitives (shz_prims.hip) ------------------------------------------------
-// exclusive scan of n u32 values -> u32 (total written to d_total if non-null, as u64)
+// exclusive scan of n u32 values -> u32 (total written to d_total if non-null, as u64).  Contract: every sum is formed in
+// 32 bits (lanes, waves, block sums, the total before it is widened), so the caller keeps the grand total at or below
+// 2^32 - 1; up to there every prefix and the total are exact, above it they wrap.  d_out may be d_in (the sort's digit
+// tables); n = 0 writes *d_total = 0 and nothing else.
 int32_t shz_scan_u32(shz_ctx* ctx, const uint32_t* d_in, uint32_t* d_out, uint64_t n, uint64_t* d_total);
-// exclusive scan of popcount(mask[i]) for u64 words
+// exclusive scan of popcount(mask[i]) for u64 words -> u32; the same contract: the set bits of all n words together
+// number at most 2^32 - 1
 int32_t shz_scan_popc64(shz_ctx* ctx, const uint64_t* d_in, uint32_t* d_out, uint64_t n, uint64_t* d_total);
 // exclusive scan of n u64 values -> u64
 int32_t shz_scan_u64(shz_ctx* ctx, const uint64_t* d_in, uint64_t* d_out, uint64_t n, uint64_t* d_total);

@@ -1016,3 +1016,36 @@ extern "C" int32_t shz_sort_pairs(shz_ctx* ctx, uint64_t* keys, void* vals, uint
   SHZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return SHZ_OK;
 }
+
+extern "C" int32_t shz_scan_host(shz_ctx* ctx, uint32_t kind, const void* in, void* out, uint64_t n, uint32_t in_place,
+                                 uint64_t* total) {
+  if (!ctx) return SHZ_E_INVALID;
+  if (kind != SHZ_SCAN_U32 && kind != SHZ_SCAN_POPC64 && kind != SHZ_SCAN_U64)
+    SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_scan_host: unknown kind %u", kind);
+  if (in_place && kind == SHZ_SCAN_POPC64)
+    SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_scan_host: popc64 reads 8-byte words and writes 4-byte sums: not in place");
+  if (n && (!in || !out)) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_scan_host: NULL buffer");
+  if (n >> 40) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_scan_host: n must be < 2^40 (got %llu)", (unsigned long long)n);
+  SHZ_HIP(ctx, hipSetDevice(ctx->device));
+  const uint64_t ib = kind == SHZ_SCAN_U32 ? 4 : 8, ob = kind == SHZ_SCAN_U64 ? 8 : 4;
+  // the scan itself reserves SHZ_WS_SCAN_TMP only: the sort's slots are free here
+  void *d_in, *d_out, *d_tot = nullptr;
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SORT_A, n * ib, &d_in));
+  if (in_place) d_out = d_in;
+  else SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SORT_B, n * ob, &d_out));
+  if (total) SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SORT_C, 8, &d_tot));
+  SHZ_HIP(ctx, shz_memcpy(ctx, d_in, in, n * ib, hipMemcpyHostToDevice));
+  // what an earlier call left in the slots must not pass for a result: an element or a total the scan does not write reads 0xA5..
+  if (!in_place && n) SHZ_HIP(ctx, hipMemsetAsync(d_out, 0xA5, n * ob, ctx->stream));
+  if (total) SHZ_HIP(ctx, hipMemsetAsync(d_tot, 0xA5, 8, ctx->stream));
+  if (kind == SHZ_SCAN_U32)
+    SHZ_TRY(shz_scan_u32(ctx, (const uint32_t*)d_in, (uint32_t*)d_out, n, (uint64_t*)d_tot));
+  else if (kind == SHZ_SCAN_POPC64)
+    SHZ_TRY(shz_scan_popc64(ctx, (const uint64_t*)d_in, (uint32_t*)d_out, n, (uint64_t*)d_tot));
+  else
+    SHZ_TRY(shz_scan_u64(ctx, (const uint64_t*)d_in, (uint64_t*)d_out, n, (uint64_t*)d_tot));
+  SHZ_HIP(ctx, shz_memcpy(ctx, out, d_out, n * ob, hipMemcpyDeviceToHost));
+  if (total) SHZ_HIP(ctx, hipMemcpyAsync(total, d_tot, 8, hipMemcpyDeviceToHost, ctx->stream));
+  SHZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return SHZ_OK;
+}

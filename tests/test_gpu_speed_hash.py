@@ -2,7 +2,10 @@
 the CSR, in the order query, speed, clip -- on built peak sets: empty and one-peak clips, a tail with too few successors,
 frames that merge below unity with interleaving f', peaks that leave above the last bin, a gap that passes 200 frames only
 after the warp; every ladder edge and fan value; device lists equal host lists; the 65536 column is shz_pair_hash; a
-capacity that is too small names the exact count."""
+capacity that is too small names the exact count; single clips whose (peak, speed) item counts sit on the route edges of the
+device scan (shz_prims.hip: 2048 | 2049 items, 8192 | 8193 items) and inside its flat route."""
+import functools
+
 import numpy as np
 import pytest
 
@@ -140,3 +143,36 @@ def test_small_capacity_names_the_exact_count(ctx, packed):
     # the context is usable after the refusals
     k2, _, _ = ctx.warp_pair_hash(pf, pt, po, SPEEDS, None, 5)
     assert np.array_equal(k2, k)
+
+
+@functools.lru_cache(maxsize=None)
+def _long_clip(P):
+    """One clip of exactly P peaks in (t asc, f asc) order: 1 to 3 frames from one occupied frame to the next, 0 to 6 distinct
+    bins a frame, the last frame cut where the count reaches P."""
+    rng = np.random.default_rng(20240 + P)
+    f, t, fr = [], [], 0
+    while len(f) < P:
+        fr += int(rng.integers(1, 4))
+        n = int(rng.integers(0, 7))
+        f.extend(sorted(rng.choice(2049, n, replace=False).tolist()))
+        t.extend([fr] * n)
+    pf, pt = np.asarray(f[:P], np.uint16), np.asarray(t[:P], np.uint32)
+    for a in (pf, pt):
+        a.setflags(write=False)
+    return pf, pt, np.asarray([0, P], np.uint64)
+
+
+@pytest.mark.parametrize("fan", [2, 5])
+@pytest.mark.parametrize("ladder", [[40000], [65536], [40000, 65536, 70000]], ids=["below", "unity", "three"])
+@pytest.mark.parametrize("P", [2048, 2049, 8192, 8193])
+def test_item_counts_on_the_scan_route_edges(ctx, P, ladder, fan):
+    """sp_count scans P x len(ladder) items twice (keep flags, partner counts).  One rung: P items, on the edges between the
+    scan's single tile, its one-workgroup loop and its flat route; three rungs of 8192 / 8193 peaks: well inside the flat
+    route.  [40000] is below unity: frames merge and the peaks are re-ranked."""
+    pf, pt, po = _long_clip(P)
+    assert len(pf) == P and np.all(np.diff(pt.astype(np.int64) * 4096 + pf) > 0)
+    k, t1, ho = ctx.warp_pair_hash(pf, pt, po, ladder, None, fan)
+    ek, et, eho = T.warp_pair_batch(pf, pt, po, [0, 1], ladder, fan)
+    assert np.array_equal(ho, eho)
+    assert np.array_equal(k, ek) and np.array_equal(t1, et)
+    assert len(ho) == len(ladder) + 1 and len(k) >= P // 2
