@@ -167,6 +167,24 @@ uint32_t shz_frame_count(uint64_t n_samples);
 int32_t shz_stft_db(shz_ctx* ctx, const int16_t* pcm, const uint64_t* clip_off, uint32_t n_clips,
                     uint32_t fs, uint32_t flags, double* out_db, uint64_t cap_doubles, uint64_t* count);
 
+/* The rows the fast STFT kernel stages for fp32 peak picking (tests / tools): stft_psd_kernel launched as the extraction
+ * driver launches it (same clip tables, same grid and frame map) on a batch of HOST pcm, its rows copied to HOST memory
+ * without their padding: out = [frames][2049] of float (SHZ_STAGE_F32: the kernel of every extraction call) or of double
+ * (SHZ_STAGE_F64: the same arithmetic with the last conversion left out, which nothing else launches), frame-major, frames
+ * of all clips in clip order at the ctx's hop (shz_set_overlap).  A value is the power as specgram scales it, an exact
+ * zero staged as 1.0 (fp32: also a power that rounds to 0.0f).  The staging buffer is filled with 0xFF bytes first: a cell
+ * the kernel does not write reads as a NaN.  flags: SHZ_STAGE_PERSISTENT launches the persistent grid (each eighth of the
+ * frames walked by an eighth of the workgroups) whatever the frame count; without it the call takes chunks of 32 frames
+ * once there are more frames than the persistent grid has room for 32 each, as the single pipeline does.  *frames (may be
+ * NULL) = rows written.  One pass: SHZ_E_CAPACITY if the staged rows, the copied rows and the PCM exceed the workspace
+ * limit.  SHZ_E_INVALID before anything runs: NULL buffers with work to do, an unknown kind or flag bit, clip_off not
+ * non-decreasing, out_cap_rows below the frame count (*frames is set), more than 2^20 frames.  n_clips = 0: *frames = 0. */
+#define SHZ_STAGE_F32 0u
+#define SHZ_STAGE_F64 1u
+#define SHZ_STAGE_PERSISTENT 1u
+int32_t shz_stft_stage_host(shz_ctx* ctx, const int16_t* pcm, const uint64_t* clip_off, uint32_t n_clips, uint32_t fs,
+                            uint32_t kind, uint32_t flags, void* out, uint64_t out_cap_rows, uint64_t* frames);
+
 /* The log transform alone, on the HOST (no device, no ctx): out_db[i] = 10*log10(power[i]) where power != 0, else 0.0
  * (__init__.py:241), with the same correctly rounded logarithm the kernels use (csrc/shz_log10.h) -- the function
  * that decides ties in the peak test, exposed so that tests can pin it without a GPU. */
@@ -220,7 +238,7 @@ int32_t shz_numpy_tables(uint32_t nfft, double* window, double* twiddles, double
 /* The window of the fp64 path as the host's numpy forms it: window[4096] = np.hanning(4096), sumsq = (window ** 2).sum()
  * (mlab.window_hanning and the scaling of mlab._spectral_helper behind __init__.py:232-237).  The Python layer calls this for
  * every context it creates, so the window is numpy's by construction; without the call the libm form of shz_numpy_tables is
- * used (equal to numpy's on the hosts seen).  Affects the fp64 path only (ties, shz_stft_db), not the fp32 staging kernel. */
+ * used (equal to numpy's on the hosts seen).  The fast kernel behind the fp32 staging multiplies with the same table. */
 int32_t shz_set_numpy_window(shz_ctx* ctx, const double* window, double sumsq);
 /* How the host's numpy multiplies complex numbers (`np.conj(result) * result` in mlab._spectral_helper): fused = 1 (default):
  * real part fma(re, re, im * im) -- numpy's SIMD product on x86-64 with FMA3, the hosts of the fixtures; fused = 0:

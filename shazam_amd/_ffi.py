@@ -17,6 +17,7 @@ DEBUG_VT_TINY_HEAVY, DEBUG_VT_PROBE1, DEBUG_RUN_LIMIT_SMALL, DEBUG_SCAN_SMALL_GR
 DEBUG_SPEED_SMALL_SLICES = 16   # shz_recognize_speeds: at most 2 queries a slice
 DEBUG_SCAN_SPEED_SMALL_SLICES = 32   # shz_scan_speeds: at most 1 recording x 2 rungs a slice, 3 windows a match group
 SCAN_U32, SCAN_POPC64, SCAN_U64 = 0, 1, 2   # shz_scan_host kinds
+STAGE_F32, STAGE_F64, STAGE_PERSISTENT = 0, 1, 1   # shz_stft_stage_host kinds | flag
 RUN_ROWS_MAX, RUN_ROWS_MAX_SMALL = (1 << 32) - 4096, 65536
 NFFT, HOP, NBINS = 4096, 2048, 2049
 
@@ -63,6 +64,7 @@ SIGNATURES = {
     "shz_set_numpy_product": (C.c_int32, [vp, C.c_int32]),
     "shz_stft_db_any": (C.c_int32, [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_uint64, u64p]),
     "shz_stft_db": (C.c_int32, [vp, vp, u64p, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_uint64, u64p]),
+    "shz_stft_stage_host": (C.c_int32, [vp, vp, u64p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_uint64, u64p]),
     "shz_db_values": (C.c_int32, [vp, C.c_uint64, vp]),
     "shz_peaks": (C.c_int32, [vp, vp, u64p, C.c_uint32, C.c_uint32, C.c_double, C.c_uint32, vp, vp, u64p, C.c_uint64, u64p]),
     "shz_peaks_from_db": (C.c_int32, [vp, vp, C.c_uint32, C.c_uint32, C.c_double, vp, vp, C.c_uint64, u64p]),
@@ -497,6 +499,20 @@ class Context:
             res.append(out[pos:pos + f * NBINS].reshape(NBINS, f))
             pos += f * NBINS
         return res
+
+    def stft_stage(self, pcm, clip_off, fs=44100, kind=STAGE_F32, persistent=False) -> np.ndarray:
+        """The rows stft_psd_kernel stages, [frames of all clips][2049], float32 (STAGE_F32: what fp32 peak picking reads) or
+        float64 (STAGE_F64: the same arithmetic unrounded), launched as the extraction driver launches it; persistent: the
+        persistent grid whatever the frame count.  For tests and tools."""
+        x = np.ascontiguousarray(pcm, np.int16)
+        co, nc = self._clip_off(clip_off)
+        rows = sum(self.frames_of(int(co[i + 1] - co[i])) for i in range(nc))
+        out = np.empty((rows, NBINS), np.float64 if kind == STAGE_F64 else np.float32)
+        n = C.c_uint64()
+        self.check(lib().shz_stft_stage_host(self.h, ptr(x), co.ctypes.data_as(u64p), nc, int(fs), int(kind),
+                                             STAGE_PERSISTENT if persistent else 0, ptr(out), rows, C.byref(n)))
+        assert n.value == rows, (n.value, rows)
+        return out
 
     def set_numpy_product(self, fused: bool):
         """How the host's numpy forms conj(z) * z (see numpy_product_is_fused); set by __init__ from a probe."""

@@ -252,7 +252,9 @@ extern "C" int32_t shz_set_numpy_window(shz_ctx* ctx, const double* window, doub
   SHZ_HIP(ctx, hipSetDevice(ctx->device));
   SHZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
   SHZ_HIP(ctx, hipMemcpy(ctx->d_np_window, window, sizeof(double) * SHZ_NFFT, hipMemcpyHostToDevice));
+  SHZ_HIP(ctx, hipMemcpy(ctx->d_window, window, sizeof(double) * SHZ_NFFT, hipMemcpyHostToDevice));   // the fast kernel's copy
   ctx->np_sumsq = sumsq;
+  ctx->win_sumsq = sumsq;
   if (ctx->twin) return shz_set_numpy_window(ctx->twin, window, sumsq);
   return SHZ_OK;
 }
@@ -287,17 +289,12 @@ extern "C" int32_t shz_ctx_create(int32_t device_id, shz_ctx** out) {
     return SHZ_E_HIP;
   }
   ctx->ws_limit = ctx->prop.totalGlobalMem / 4;
-  // constant tables, computed in long double and rounded once
-  std::vector<double> win(SHZ_NFFT);
+  // constant tables.  The window of the fast STFT kernel is numpy's np.hanning(4096), the one the reference multiplies with
+  // (npw below; shz_set_numpy_window replaces both copies).  It used to be the correctly rounded Hann window (evaluated in
+  // long double): 2,254 of the 4,096 values differ from numpy's, by 2^-52 at most -- nothing against a frame's maximum,
+  // but 4e-11 of w[1] and 1e-13 of w[32], so a frame whose only samples sit in the window's first or last few dozen came
+  // out that far from the reference's spectrogram (tests/test_gpu_stft_stage.py: clips of 2, 3 and 33-37 samples).
   const long double pi = 3.14159265358979323846264338327950288L;
-  double sumsq = 0.0;
-  for (int i = 0; i < SHZ_NFFT; ++i) {
-    // np.hanning(M): 0.5 + 0.5*cos(pi*n/(M-1)), n = 1-M, 3-M, ...  (mlab.window_hanning)
-    long double nn = (long double)(1 - SHZ_NFFT + 2 * i);
-    win[i] = (double)(0.5L + 0.5L * cosl(pi * nn / (long double)(SHZ_NFFT - 1)));
-  }
-  for (int i = 0; i < SHZ_NFFT; ++i) sumsq += win[i] * win[i];
-  ctx->win_sumsq = sumsq;
   // twiddles of the 2048-point FFT (layout: stft_tables in shz_extract.hip): W^k for k <= 512 (the other octants by
   // symmetry), then W_64^(k t) for pass 2 ([t-1][k], k < 8) and W_512^(k t) for pass 3 ([t-1][k], k < 64), t = 1..7
   std::vector<double2> tw;
@@ -315,6 +312,8 @@ extern "C" int32_t shz_ctx_create(int32_t device_id, shz_ctx** out) {
   std::vector<double> npw(SHZ_NFFT);
   std::vector<double2> npc(SHZ_NFFT);
   shz_numpy_tables_host(SHZ_NFFT, npw.data(), npc.data(), &ctx->np_sumsq);
+  const std::vector<double>& win = npw;
+  ctx->win_sumsq = ctx->np_sumsq;
   {  // the twiddles in the order the passes read them (pocketfft's own per-pass tables: [c - 1][i] = comp[c l1 i]): copies,
      // no arithmetic -- neighbouring lanes then read neighbouring entries instead of 64 cache lines a load
     std::vector<double2> tw(SHZ_NFFT, double2{0.0, 0.0});

@@ -1428,7 +1428,8 @@ static stft_args make_stft_args(shz_ctx* ctx, const int16_t* d_pcm, const sub_de
   return a;
 }
 
-// fp32 staging: stft_psd_kernel<float>
+// fp32 staging: stft_psd_kernel<float>; T = double is the same arithmetic staged unrounded (shz_stft_stage_host only)
+template <typename T>
 static int32_t launch_stft(shz_ctx* ctx, const stft_args& a, bool persistent) {
   shz_prof_scope ps(ctx, 0);
   constexpr uint32_t WGS_PER_CU = 3, CHUNK_FRAMES = 32;   // resident workgroups per CU of the persistent grid (LDS allows 3)
@@ -1443,7 +1444,7 @@ static int32_t launch_stft(shz_ctx* ctx, const stft_args& a, bool persistent) {
     b.frames_per_wg = CHUNK_FRAMES;
     grid = (a.total_frames + CHUNK_FRAMES - 1) / CHUNK_FRAMES;
   }
-  hipLaunchKernelGGL(stft_psd_kernel<float>, dim3(grid), dim3(256), 0, ctx->stream, b);
+  hipLaunchKernelGGL(stft_psd_kernel<T>, dim3(grid), dim3(256), 0, ctx->stream, b);
   SHZ_HIP(ctx, hipGetLastError());
   return SHZ_OK;
 }
@@ -1644,6 +1645,71 @@ extern "C" int32_t shz_stft_db(shz_ctx* ctx, const int16_t* pcm, const uint64_t*
     out_pos += tr_pos;
   }
   return SHZ_OK;
+}
+
+// rows of `stride` values -> rows of SHZ_NBINS values (shz_stft_stage_host hands the staged rows out without their padding)
+template <typename T>
+__global__ __launch_bounds__(256) void unpad_rows_kernel(const T* __restrict__ in, uint32_t stride, uint32_t frames, T* __restrict__ out) {
+  const uint32_t g = blockIdx.x;
+  if (g >= frames) return;
+  for (uint32_t k = threadIdx.x; k < SHZ_NBINS; k += 256) out[(uint64_t)g * SHZ_NBINS + k] = in[(uint64_t)g * stride + k];
+}
+
+template <typename T>
+static int32_t stft_stage_rows(shz_ctx* ctx, const int16_t* pcm, const uint64_t* clip_off, uint32_t n_clips, uint32_t fs,
+                               bool persistent, uint32_t frames, T* out) {
+  constexpr uint32_t STRIDE = sizeof(T) == 8 ? DB_STRIDE : P32_STRIDE;
+  const uint64_t staged = (uint64_t)frames * STRIDE * sizeof(T), rows = (uint64_t)frames * SHZ_NBINS * sizeof(T);
+  const uint64_t need = staged + rows + (clip_off[n_clips] - clip_off[0]) * 2;
+  if (need > ctx->ws_limit)
+    SHZ_FAIL(ctx, SHZ_E_CAPACITY, "shz_stft_stage_host: %u frames need %llu bytes in one pass, the workspace limit is %llu", frames,
+             (unsigned long long)need, (unsigned long long)ctx->ws_limit);
+  const sub_batch sb{0, n_clips, frames};
+  std::vector<std::vector<uint64_t>> keep;
+  const int16_t* d_pcm;
+  uint64_t base;
+  SHZ_TRY(stage_pcm(ctx, pcm, clip_off, sb, 0, &d_pcm, &base));
+  sub_dev sd;
+  SHZ_TRY(upload_meta(ctx, clip_off, sb, base, MG_F32.n_slabs, 12 / MG_F32.nw, sd, keep));
+  void *d_pw, *d_rows;
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_DB, staged, &d_pw));
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_MISC3, rows, &d_rows));
+  // a cell the kernel does not write must not pass for a result: it reads as 0xFF bytes (a NaN of either type)
+  SHZ_HIP(ctx, hipMemsetAsync(d_pw, 0xFF, staged, ctx->stream));
+  SHZ_HIP(ctx, hipMemsetAsync(d_rows, 0xFF, rows, ctx->stream));
+  SHZ_TRY(launch_stft<T>(ctx, make_stft_args(ctx, d_pcm, sd, n_clips, frames, fs, d_pw), persistent));
+  hipLaunchKernelGGL(unpad_rows_kernel<T>, dim3(frames), dim3(256), 0, ctx->stream, (const T*)d_pw, STRIDE, frames, (T*)d_rows);
+  SHZ_HIP(ctx, hipGetLastError());
+  SHZ_HIP(ctx, shz_memcpy(ctx, out, d_rows, rows, hipMemcpyDeviceToHost));
+  SHZ_HIP(ctx, hipStreamSynchronize(ctx->stream));   // (`keep` lives until here)
+  return SHZ_OK;
+}
+
+extern "C" int32_t shz_stft_stage_host(shz_ctx* ctx, const int16_t* pcm, const uint64_t* clip_off, uint32_t n_clips, uint32_t fs,
+                                       uint32_t kind, uint32_t flags, void* out, uint64_t out_cap_rows, uint64_t* frames) {
+  if (!ctx) return SHZ_E_INVALID;
+  if (frames) *frames = 0;
+  if (kind != SHZ_STAGE_F32 && kind != SHZ_STAGE_F64) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_stft_stage_host: unknown kind %u", kind);
+  if (flags & ~SHZ_STAGE_PERSISTENT) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_stft_stage_host: unknown flag bits 0x%x", flags);
+  if (n_clips == 0) return SHZ_OK;
+  if (!clip_off) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_stft_stage_host: clip_off is NULL");
+  if (fs == 0) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_stft_stage_host: Fs must be > 0");
+  uint64_t total = 0;
+  for (uint32_t c = 0; c < n_clips; ++c) {
+    if (clip_off[c + 1] < clip_off[c]) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_stft_stage_host: clip_off must be non-decreasing (clip %u)", c);
+    total += frames_hop(clip_off[c + 1] - clip_off[c], ctx->hop);
+  }
+  if (total > (1u << 20))   // one sub-batch of the extraction driver holds at most as many (plan_sub_batches)
+    SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_stft_stage_host: %llu frames, at most 2^20 in one call", (unsigned long long)total);
+  if (frames) *frames = total;
+  if (!out) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_stft_stage_host: out is NULL");
+  if (!pcm && clip_off[n_clips] > clip_off[0]) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_stft_stage_host: pcm is NULL");
+  if (out_cap_rows < total)
+    SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_stft_stage_host: %llu rows, out holds %llu", (unsigned long long)total, (unsigned long long)out_cap_rows);
+  SHZ_HIP(ctx, hipSetDevice(ctx->device));
+  const bool persistent = (flags & SHZ_STAGE_PERSISTENT) != 0;
+  return kind == SHZ_STAGE_F64 ? stft_stage_rows<double>(ctx, pcm, clip_off, n_clips, fs, persistent, (uint32_t)total, (double*)out)
+                               : stft_stage_rows<float>(ctx, pcm, clip_off, n_clips, fs, persistent, (uint32_t)total, (float*)out);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1935,7 +2001,7 @@ static int32_t stage_sub_batch(shz_ctx* ctx, const xreq& rq, bool hashes, const 
   SHZ_TRY(upload_meta(ctx, rq.clip_off, sb, base, w->mg.n_slabs, xp.f32 ? 12 / w->mg.nw : 3, w->sd, keep));
   SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_DB, (uint64_t)sb.frames * pw_bytes_per_frame(xp.f32), &w->d_pw));
   w->sa = make_stft_args(ctx, d_pcm, w->sd, w->nc, sb.frames, rq.fs, w->d_pw);
-  if (xp.f32) SHZ_TRY(launch_stft(ctx, w->sa, xp.persistent_stft));
+  if (xp.f32) SHZ_TRY(launch_stft<float>(ctx, w->sa, xp.persistent_stft));
   else SHZ_TRY(launch_stft_np(ctx, w->sa));
   w->n_words = (uint64_t)sb.frames * w->mg.n_slabs * w->mg.nw;
   if (w->n_words >= (1ull << 32)) SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "too many mask words in one sub-batch");
