@@ -399,6 +399,22 @@ int32_t shz_match_vt_redo(shz_ctx* ctx, uint64_t* count);
  * calls queued them / took their results from them, since the context was created.  Same results either way;
  * SHZ_MATCH_NO_SPEC=1 in the environment turns the queueing off. */
 int32_t shz_match_spec_stats(shz_ctx* ctx, uint64_t* queued, uint64_t* used);
+/* The match as shz_recognize_batch, shz_recognize_speeds, shz_scan_batch, shz_scan_speeds and shz_listeners_push run it
+ * (tests / tools): on query columns that already lie on the device, with the bound of the query offsets those callers know
+ * without reading them.  key32 / q_off / query_off are HOST arrays as for shz_match_batch; the two columns are copied into
+ * device buffers the call allocates and frees, and the library's internal match on device columns runs on them unchanged.
+ * Outputs and refusals as shz_match_batch (flags: SHZ_MATCH_FULL_SORT only).  bias_bound: a promise that every q_off is
+ * <= bias_bound; below 0 or >= 2^32: no bound.  With a bound, ONE query of at most 8,192 hashes has its vote kernels queued
+ * ahead of the count (shz_match_spec_stats) on the layout the BOUND gives -- dbits = bits(largest table offset + bias_bound)
+ * -- where that layout fits the one-workgroup fold: 1 + sb + dbits <= 32, dbits <= 20, topn <= 8, bias_bound < 2^20, no
+ * SHZ_MATCH_FULL_SORT (and the table's last match does not promise this one more than 65,536 votes: hashes x its votes per
+ * hash).  Their results are the answer when the votes number at most 32,768 and no offset exceeded the bound;
+ * otherwise (and for a bound that does not hold) they are dropped and the call goes through the vote passes on the layout
+ * of the offsets themselves.  The same arrays for every bound. */
+int32_t shz_match_device_host(shz_ctx* ctx, shz_table* t, const uint32_t* key32, const uint32_t* q_off,
+                              const uint64_t* query_off, uint32_t n_queries, uint32_t topn, uint32_t flags, int64_t bias_bound,
+                              uint32_t* out_sid, int32_t* out_delta, uint32_t* out_aligned, uint32_t* out_dedup,
+                              uint32_t* out_nres, uint32_t* out_nhash, uint64_t* out_npairs);
 /* rows streamed / pairs voted by the last shz_match_batch (for HBM accounting) */
 int32_t shz_match_stats(shz_ctx* ctx, uint64_t* rows_scanned, uint64_t* pairs, uint64_t* distinct_keys);
 
@@ -564,6 +580,14 @@ int32_t shz_listeners_push(shz_listeners* L, const int16_t* pcm, const uint64_t*
 int32_t shz_listeners_reset(shz_listeners* L, const uint32_t* which, uint32_t n);
 /* listener l: hashes in its window, and the w0 of its last push (any pointer may be NULL) */
 int32_t shz_listeners_state(shz_listeners* L, uint32_t l, uint64_t* window_hashes, uint64_t* w0);
+/* The content of listener l's window (tests / tools): its entries in the order the device keeps them -- what the last push
+ * kept of the old window, then what it kept of the new hashes -- copied to the HOST arrays key32 / t1 (absolute frames) /
+ * q_off (t1 - w0 as the last push handed it to the match) of cap entries each; *n = their number (the window_hashes of
+ * shz_listeners_state).  More than cap: SHZ_E_CAPACITY with *n = the number needed, nothing copied.  The call waits for
+ * the ctx stream and changes no state.  q_off is meaningful only after a push: a listener that was reset has no entries,
+ * and before the first push there is nothing to read. */
+int32_t shz_listeners_window(shz_listeners* L, uint32_t l, uint32_t* key32, uint32_t* t1, uint32_t* q_off, uint64_t cap,
+                             uint64_t* n);
 /* No GPU, no ctx (like shz_stream_plan): the window of a listener whose channels have settled[0 .. channels) frames:
  * *horizon = their minimum H, *w0 = max(0, H - window_frames). */
 int32_t shz_listener_window(const uint64_t* settled, uint32_t channels, uint32_t window_frames, uint64_t* horizon, uint64_t* w0);

@@ -93,6 +93,8 @@ SIGNATURES = {
     "shz_table_song_rows": (C.c_int32, [vp, C.c_uint32, u64p]),
     "shz_match_batch": (C.c_int32, [vp, vp, vp, vp, u64p, C.c_uint32, C.c_uint32, C.c_uint32,
                                     vp, vp, vp, vp, vp, vp, vp]),
+    "shz_match_device_host": (C.c_int32, [vp, vp, vp, vp, u64p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int64,
+                                          vp, vp, vp, vp, vp, vp, vp]),
     "shz_recognize_batch": (C.c_int32, [vp, vp, vp, u64p, C.c_uint32, u32p, C.c_uint32, C.c_uint32, C.c_double, C.c_uint32,
                                         C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, C.POINTER(C.c_float),
                                         C.POINTER(C.c_float)]),
@@ -138,6 +140,7 @@ SIGNATURES = {
     "shz_listeners_push": (C.c_int32, [vp, vp, u64p, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp]),
     "shz_listeners_reset": (C.c_int32, [vp, vp, C.c_uint32]),
     "shz_listeners_state": (C.c_int32, [vp, C.c_uint32, u64p, u64p]),
+    "shz_listeners_window": (C.c_int32, [vp, C.c_uint32, vp, vp, vp, C.c_uint64, u64p]),
     "shz_listener_window": (C.c_int32, [u64p, C.c_uint32, C.c_uint32, u64p, u64p]),
     "shz_resample_i16": (C.c_int32, [vp, vp, u64p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.c_uint32,
                                      vp, u64p, C.c_uint64, u64p]),
@@ -1039,6 +1042,21 @@ class Table:
                                              ptr(res["nres"]), ptr(res["nhash"]), ptr(res["npairs"])))
         return res
 
+    def match_device(self, key32, q_off, query_off, topn=2, full_sort=False, bias_bound=-1):
+        """match() the way the fused calls and the listeners run it (shz_match_device_host): the two columns are put on the
+        device first and matched there, with the caller's bound of the query offsets (below 0 or >= 2^32: none).  For tests
+        and tools; same result arrays as match()."""
+        k = np.ascontiguousarray(key32, np.uint32)
+        o = np.ascontiguousarray(q_off, np.uint32)
+        qo = np.ascontiguousarray(query_off, np.uint64)
+        nq = len(qo) - 1
+        res = _match_result(nq, topn)
+        self.ctx.check(lib().shz_match_device_host(self.ctx.h, self.h, ptr(k), ptr(o), qo.ctypes.data_as(u64p), nq, topn,
+                                                   MATCH_FULL_SORT if full_sort else 0, int(bias_bound),
+                                                   ptr(res["sid"]), ptr(res["delta"]), ptr(res["aligned"]), ptr(res["dedup"]),
+                                                   ptr(res["nres"]), ptr(res["nhash"]), ptr(res["npairs"])))
+        return res
+
     def match_stats(self):
         a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
         self.ctx.check(lib().shz_match_stats(self.ctx.h, C.byref(a), C.byref(b), C.byref(c)))
@@ -1237,3 +1255,16 @@ class Listeners:
         a, b = C.c_uint64(), C.c_uint64()
         self.ctx.check(lib().shz_listeners_state(self.h, int(l), C.byref(a), C.byref(b)))
         return {"window_hashes": int(a.value), "w0": int(b.value)}
+
+    def window(self, l: int):
+        """(key32, t1, q_off) of listener l's window, in the order the device keeps them (shz_listeners_window); q_off is what
+        the last push handed to the match.  For tests and tools."""
+        n = C.c_uint64()
+        rc = lib().shz_listeners_window(self.h, int(l), None, None, None, 0, C.byref(n))
+        if rc != E_CAPACITY:
+            self.ctx.check(rc)
+        cnt = int(n.value)
+        k, t, q = (np.zeros(cnt, np.uint32) for _ in range(3))
+        if cnt:
+            self.ctx.check(lib().shz_listeners_window(self.h, int(l), ptr(k), ptr(t), ptr(q), cnt, C.byref(n)))
+        return k, t, q

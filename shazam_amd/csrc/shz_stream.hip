@@ -739,6 +739,31 @@ extern "C" int32_t shz_listeners_state(shz_listeners* L, uint32_t l, uint64_t* w
   return SHZ_OK;
 }
 
+// tests / tools: the entries of listener l's window as they lie in the current slot, with the query offsets the last push
+// wrote beside them.  Reads only.
+extern "C" int32_t shz_listeners_window(shz_listeners* L, uint32_t l, uint32_t* key32, uint32_t* t1, uint32_t* q_off, uint64_t cap,
+                                        uint64_t* n) {
+  SHZ_TRY(ls_check(L));
+  shz_ctx* ctx = L->ctx;
+  if (l >= L->n) SHZ_FAIL(ctx, SHZ_E_INVALID, "listener %u out of range (%u listeners)", l, L->n);
+  if (!n) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_listeners_window: n is NULL");
+  const uint64_t at = L->w_at[l], cnt = L->w_n[l];
+  *n = cnt;
+  if (cnt > cap) SHZ_FAIL(ctx, SHZ_E_CAPACITY, "output needs %llu entries, capacity %llu", (unsigned long long)cnt, (unsigned long long)cap);
+  if (cnt == 0) return SHZ_OK;
+  if (!key32 || !t1 || !q_off) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_listeners_window: NULL buffer");
+  SHZ_HIP(ctx, hipSetDevice(ctx->device));
+  SHZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  const shz_buf &wk = L->wk[L->cur], &wt = L->wt[L->cur];
+  if (!wk.p || !wt.p || !L->qo.p || (at + cnt) * 4 > std::min(std::min(wk.cap, wt.cap), L->qo.cap))
+    SHZ_FAIL(ctx, SHZ_E_STATE, "listeners: window [%llu, %llu) lies outside its slot", (unsigned long long)at, (unsigned long long)(at + cnt));
+  SHZ_HIP(ctx, shz_memcpy(ctx, key32, (const uint32_t*)wk.p + at, cnt * 4, hipMemcpyDeviceToHost));
+  SHZ_HIP(ctx, shz_memcpy(ctx, t1, (const uint32_t*)wt.p + at, cnt * 4, hipMemcpyDeviceToHost));
+  SHZ_HIP(ctx, shz_memcpy(ctx, q_off, (const uint32_t*)L->qo.p + at, cnt * 4, hipMemcpyDeviceToHost));
+  SHZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return SHZ_OK;
+}
+
 extern "C" int32_t shz_listener_window(const uint64_t* settled, uint32_t channels, uint32_t window_frames, uint64_t* horizon,
                                        uint64_t* w0) {
   if (!settled || channels == 0) return SHZ_E_INVALID;

@@ -2830,6 +2830,41 @@ int32_t shz_match_device(shz_ctx* ctx, shz_table* t, const uint32_t* d_key32, co
   return match_core(mc);
 }
 
+// tests / tools: shz_match_device on HOST columns -- copied into device buffers of this call's own (not the workspace, which
+// the match uses), handed to shz_match_device as its callers hand theirs, freed afterwards.  Nothing else is added: the
+// bound, the flags and the outputs go through as they are.
+extern "C" int32_t shz_match_device_host(shz_ctx* ctx, shz_table* t, const uint32_t* key32, const uint32_t* q_off,
+                                         const uint64_t* query_off, uint32_t n_queries, uint32_t topn, uint32_t flags,
+                                         int64_t bias_bound, uint32_t* out_sid, int32_t* out_delta, uint32_t* out_aligned,
+                                         uint32_t* out_dedup, uint32_t* out_nres, uint32_t* out_nhash, uint64_t* out_npairs) {
+  if (!ctx || !t) return SHZ_E_INVALID;
+  if (flags & ~SHZ_MATCH_FULL_SORT) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_match_device_host: flags may hold SHZ_MATCH_FULL_SORT");
+  if (n_queries && !query_off) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_match_device_host: query_off is NULL");
+  const uint64_t h1 = n_queries ? query_off[n_queries] : 0;
+  if (h1 && (!key32 || !q_off)) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_match_device_host: NULL column");
+  if (h1 >= (1ull << 32)) SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "shz_match_device_host: %llu hashes", (unsigned long long)h1);
+  SHZ_HIP(ctx, hipSetDevice(ctx->device));
+  void *d_key = nullptr, *d_qo = nullptr;
+  if (hipMalloc(&d_key, std::max<uint64_t>(h1, 1) * 4) != hipSuccess || hipMalloc(&d_qo, std::max<uint64_t>(h1, 1) * 4) != hipSuccess) {
+    (void)hipGetLastError();
+    if (d_key) (void)hipFree(d_key);
+    SHZ_FAIL(ctx, SHZ_E_NOMEM, "shz_match_device_host: hipMalloc(2 x %llu) failed", (unsigned long long)(h1 * 4));
+  }
+  int32_t rc = SHZ_OK;
+  if (h1 && (shz_memcpy(ctx, d_key, key32, h1 * 4, hipMemcpyHostToDevice) != hipSuccess ||
+             shz_memcpy(ctx, d_qo, q_off, h1 * 4, hipMemcpyHostToDevice) != hipSuccess)) {
+    ctx->err = "shz_match_device_host: copy of the columns failed";
+    rc = SHZ_E_HIP;
+  }
+  if (rc == SHZ_OK)
+    rc = shz_match_device(ctx, t, (const uint32_t*)d_key, (const uint32_t*)d_qo, query_off, n_queries, topn, flags, bias_bound,
+                          out_sid, out_delta, out_aligned, out_dedup, out_nres, out_nhash, out_npairs);
+  (void)hipStreamSynchronize(ctx->stream);   // (a refused call may have queued work that reads the columns)
+  (void)hipFree(d_key);
+  (void)hipFree(d_qo);
+  return rc;
+}
+
 // what match_core refuses before it launches anything, for callers that must know before they change state of their own
 int32_t shz_match_ready(shz_ctx* ctx, shz_table* t, uint32_t topn) {
   if (!ctx || !t) return SHZ_E_INVALID;

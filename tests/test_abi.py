@@ -30,6 +30,17 @@ def test_frame_count_needs_no_gpu():
     assert L.shz_version().startswith(b"shz")
 
 
+def test_tools_entries_refuse_null_handles_without_a_gpu():
+    """shz_match_device_host / shz_listeners_window (tests / tools): no context, no table, no listeners -> SHZ_E_INVALID
+    before anything touches a device"""
+    import ctypes as C
+    L = _ffi.lib()
+    n = C.c_uint64(7)
+    assert L.shz_match_device_host(None, None, None, None, None, 0, 2, 0, -1, None, None, None, None, None, None, None) == _ffi.E_INVALID
+    assert L.shz_listeners_window(None, 0, None, None, None, 0, C.byref(n)) == _ffi.E_INVALID
+    assert n.value == 7
+
+
 def test_registry_mirrors_reference():
     import pytest
     import shazam_amd as S
