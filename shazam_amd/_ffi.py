@@ -619,6 +619,20 @@ class Context:
                                              ptr(res["nres"]), ptr(res["nhash"]), ptr(res["npairs"]), C.byref(me), C.byref(mm)))
         return res, float(me.value), float(mm.value)
 
+    def _windows_with_room(self, call, room, cnt, cap_windows):
+        """The two-call capacity idiom of the scans.  call(res, cap) -> rc runs the library call on the arrays res = room(n)
+        with room for cap windows and leaves the total in cnt; without cap_windows the first call launches nothing and names
+        the total.  Returns the arrays, cut to the total."""
+        if cap_windows is None:
+            rc = call(room(0), 0)
+            if rc != E_CAPACITY:
+                self.check(rc)
+            cap_windows = int(cnt.value)
+        res = room(int(cap_windows))
+        self.check(call(res, cap_windows))
+        n = int(cnt.value)
+        return {k: v[:n] for k, v in res.items()}
+
     def scan_batch(self, table: "Table", pcm, clip_off, rec_clip0, window_frames, step_frames, fs=44100, amp_min=10.0,
                    fan_value=5, topn=2, pcm_device=False, full_sort=False, cap_windows=None):
         """shz_scan_batch: fingerprint the clips once and match every window of recording r = clips [rec_clip0[r],
@@ -638,15 +652,8 @@ class Context:
                                         flags, wo.ctypes.data_as(u64p), ptr(res["sid"]), ptr(res["delta"]), ptr(res["aligned"]),
                                         ptr(res["dedup"]), ptr(res["nres"]), ptr(res["nhash"]), ptr(res["npairs"]), int(cap),
                                         C.byref(cnt), *[C.byref(m) for m in ms])
-        if cap_windows is None:   # the two-call idiom: the first call launches nothing and names the total
-            rc = call(_match_result(0, topn), 0)
-            if rc != E_CAPACITY:
-                self.check(rc)
-            cap_windows = int(cnt.value)
-        res = _match_result(int(cap_windows), topn)
-        self.check(call(res, cap_windows))
-        n = int(cnt.value)
-        return {k: v[:n] for k, v in res.items()}, wo, tuple(float(m.value) for m in ms)
+        res = self._windows_with_room(call, lambda n: _match_result(n, topn), cnt, cap_windows)
+        return res, wo, tuple(float(m.value) for m in ms)
 
     def scan_speeds(self, table: "Table", pcm, clip_off, rec_clip0, window_frames, step_frames, speeds, fs=44100, amp_min=10.0,
                     fan_value=5, topn=2, pcm_device=False, full_sort=False, cap_windows=None):
@@ -674,15 +681,8 @@ class Context:
             res = _match_result(n, topn)
             res["best"], res["profile"] = np.zeros(n, np.uint32), np.zeros((n, len(sp)), np.uint32)
             return res
-        if cap_windows is None:   # the two-call idiom: the first call launches nothing and names the total
-            rc = call(room(0), 0)
-            if rc != E_CAPACITY:
-                self.check(rc)
-            cap_windows = int(cnt.value)
-        res = room(int(cap_windows))
-        self.check(call(res, cap_windows))
-        n = int(cnt.value)
-        return {k: v[:n] for k, v in res.items()}, wo, tuple(float(m.value) for m in ms)
+        res = self._windows_with_room(call, room, cnt, cap_windows)
+        return res, wo, tuple(float(m.value) for m in ms)
 
     def warp_pair_hash_raw(self, peak_f, peak_t, peak_off, speeds, query_clip0=None, fan_value=5, cap=0, device_in=False,
                            out_key: DevBuf = None, out_t1: DevBuf = None):

@@ -81,9 +81,9 @@ enum {
   SHZ_WS_VT5,        // sub-group of every expand chunk's first vote (expand by sort blocks)
   SHZ_WS_VT6,        // the bar of every query of a vote pass (vt_stream2_kernel)
   SHZ_WS_RQ_KEY, SHZ_WS_RQ_T1,   // hashes of shz_recognize_batch / shz_scan_batch between their extraction and their match (neither reserves them)
-  SHZ_WS_SC_JOBS,    // shz_scan_batch: (window, channel) jobs | window jobs | hash_off of the clips; shz_scan_speeds: the
-                     // descriptors of a slice's recordings
-  SHZ_WS_SC_CTL,     // ... first entry | count | offset of every (window, channel) / (window, rung, channel), the total behind the offsets
+  SHZ_WS_SC_JOBS,    // shz_scan.hip, the window stage of both scans: the descriptors of a slice's recordings (the plain scan: | hash_off
+                     // of the clips | its one rung behind them)
+  SHZ_WS_SC_CTL,     // ... first entry | count | offset of every (window, rung, channel), the total behind the offsets
   SHZ_WS_SC_KEY, SHZ_WS_SC_QO,   // ... the windows of one group: key32 and t1 - window start, window-major (rung-minor)
   SHZ_WS_SP_PF, SHZ_WS_SP_PT,    // shz_speed.hip: the peaks of the clips (the extraction's, or a host list staged)
   SHZ_WS_SP_TAB,     // ... peak_off | speeds of the call
@@ -120,7 +120,7 @@ struct shz_ctx {
   hipEvent_t tev[16][2];
   bool tev_init = false;
   hipEvent_t rq_ev[3] = {nullptr, nullptr, nullptr};   // shz_recognize_batch: start, extraction done, match done (created on first use)
-  hipEvent_t sc_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // shz_scan_batch / shz_scan_speeds: start, extraction done, a stage begun / done, the next one done (created on first use)
+  hipEvent_t sc_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // shz_scan_batch / shz_scan_speeds: start, extraction done (then: a warp begun / done); the window stage: a step begun / done, the match behind it done (created on first use)
   hipEvent_t sp_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // shz_recognize_speeds: start, peaks done, a slice's warp begun / done, its match done (created on first use)
   bool profiling = false;
   float kernel_ms[8] = {0};
@@ -228,6 +228,12 @@ int32_t shz_match_device(shz_ctx* ctx, shz_table* t, const uint32_t* d_key32, co
                          int32_t* out_delta, uint32_t* out_aligned, uint32_t* out_dedup, uint32_t* out_nres, uint32_t* out_nhash,
                          uint64_t* out_npairs);
 int32_t shz_match_ready(shz_ctx* ctx, shz_table* t, uint32_t topn);
+
+// ---- refusals the fused calls share (shz_recognize.hip) ------------------------------
+// clip0 (`name`): the CSR of the clips over n items (`what`) -- not NULL, from 0 to n_clips, never decreasing; clip_off: not
+// NULL, never decreasing.  SHZ_E_INVALID with a message otherwise
+int32_t shz_check_clip0(shz_ctx* ctx, const char* name, const char* what, const uint32_t* clip0, uint32_t n, uint32_t n_clips);
+int32_t shz_check_clip_off(shz_ctx* ctx, const uint64_t* clip_off, uint32_t n_clips);
 
 // ---- extraction into buffers the library owns (shz_recognize.hip) ------------------------------
 // shz_fingerprint_batch of the clips into the slots SHZ_WS_RQ_KEY / SHZ_WS_RQ_T1, sized from the frame counts

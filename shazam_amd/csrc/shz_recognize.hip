@@ -10,6 +10,23 @@
 
 #include "shz_internal.h"
 
+// What every fused call refuses about its clips before anything is launched.  clip0 (`name`, for the message) is the CSR of
+// the clips over the n items (`what`: queries, recordings): not NULL, starts at 0, ends at n_clips, never decreases
+int32_t shz_check_clip0(shz_ctx* ctx, const char* name, const char* what, const uint32_t* clip0, uint32_t n, uint32_t n_clips) {
+  if (!clip0) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s is NULL", name);
+  if (clip0[0] != 0 || clip0[n] != n_clips)
+    SHZ_FAIL(ctx, SHZ_E_INVALID, "%s must start at 0 and end at n_clips = %u (it runs from %u to %u)", name, n_clips, clip0[0], clip0[n]);
+  for (uint32_t i = 0; i < n; ++i)
+    if (clip0[i + 1] < clip0[i]) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s decreases at %s %u", name, what, i);
+  return SHZ_OK;
+}
+int32_t shz_check_clip_off(shz_ctx* ctx, const uint64_t* clip_off, uint32_t n_clips) {
+  if (!clip_off) SHZ_FAIL(ctx, SHZ_E_INVALID, "clip_off is NULL");
+  for (uint32_t c = 0; c < n_clips; ++c)
+    if (clip_off[c + 1] < clip_off[c]) SHZ_FAIL(ctx, SHZ_E_INVALID, "clip_off decreases at clip %u", c);
+  return SHZ_OK;
+}
+
 // The extraction half of the fused calls (shz_recognize_batch, shz_scan_batch): the hashes go to the slots SHZ_WS_RQ_KEY /
 // SHZ_WS_RQ_T1, sized from the frame counts (what the extraction pass itself estimates: 12 peaks a frame with all their
 // partners); the pass's SHZ_E_CAPACITY names the size that is enough
@@ -62,15 +79,8 @@ extern "C" int32_t shz_recognize_batch(shz_ctx* ctx, shz_table* t, const int16_t
     if (n_clips) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_recognize_batch: %u clips belong to no query", n_clips);
     return SHZ_OK;
   }
-  if (!query_clip0) SHZ_FAIL(ctx, SHZ_E_INVALID, "query_clip0 is NULL");
-  if (query_clip0[0] != 0 || query_clip0[n_queries] != n_clips)
-    SHZ_FAIL(ctx, SHZ_E_INVALID, "query_clip0 must start at 0 and end at n_clips = %u (it runs from %u to %u)", n_clips,
-             query_clip0[0], query_clip0[n_queries]);
-  for (uint32_t q = 0; q < n_queries; ++q)
-    if (query_clip0[q + 1] < query_clip0[q]) SHZ_FAIL(ctx, SHZ_E_INVALID, "query_clip0 decreases at query %u", q);
-  if (!clip_off) SHZ_FAIL(ctx, SHZ_E_INVALID, "clip_off is NULL");
-  for (uint32_t c = 0; c < n_clips; ++c)
-    if (clip_off[c + 1] < clip_off[c]) SHZ_FAIL(ctx, SHZ_E_INVALID, "clip_off decreases at clip %u", c);
+  SHZ_TRY(shz_check_clip0(ctx, "query_clip0", "query", query_clip0, n_queries, n_clips));
+  SHZ_TRY(shz_check_clip_off(ctx, clip_off, n_clips));
   if (fan_value < 1 || fan_value > 64) SHZ_FAIL(ctx, SHZ_E_INVALID, "fan_value must be in [1,64]");
   if (!out_sid || !out_delta || !out_aligned || !out_dedup || !out_nres) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_recognize_batch: NULL buffer");
   SHZ_TRY(shz_match_ready(ctx, t, topn));

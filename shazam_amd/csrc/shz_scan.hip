@@ -1,22 +1,33 @@
 // Scanning long recordings (the loop a monitor puts around recognize(), recognizer.py:357-392: record a stretch, fingerprint
 // every channel, union the hashes, match, align -- here for every overlapping stretch of a recording at once): each recording
 // is fingerprinted ONCE, its device-resident hash list is cut into overlapping time windows, and all windows are matched
-// together, recording-major.
+// together, recording-major; or its peaks are extracted once, warped for every rung of a speed ladder, and
+// every window is matched at every rung.
 //
-// Within a clip the hashes come out in generation order: peaks sorted by time, t1 the anchor's time (recognizer.py:100-114),
-// so t1 never decreases and the hashes of window [s, s + window_frames) are one contiguous range of every channel's list --
-// two lower-bound searches.  A window's query is the union over the recording's channels of (key32, t1 - s): what `offset`
-// means for a clip recorded from frame s, as the listeners have it.  The windows' columns are replicated ceil(window / step)
-// times, so they are written group by group into two slots and each group is matched where it lies.
+// Both scans share one window stage (sc_windows).  Within a clip the hashes come out in generation order: peaks sorted by
+// time, t1 the anchor's time (recognizer.py:100-114), so t1 never decreases, and neither does the warped t1' of one rung.
+// The window that starts at recording frame s is, at rung v, the range W_v(s) <= t1' < W_v(s + window_frames) of every
+// channel's list, W_v(x) = (x s16 + 32768) >> 16 -- two lower-bound searches.  A window's query at a rung is the union over
+// the recording's channels of (key32, t1' - W_v(s)): what `offset` means for a clip recorded from frame s, as the listeners
+// have it.  The plain scan is the unity case: one rung of factor 65536, W(x) = x, over the extraction's own hash lists.
+// Nothing per window is built on the host: the kernels derive s and both bounds from one descriptor per recording and the
+// rung table.  The items are (window, rung, channel), window-major, so that (window, rung) is one contiguous query of the
+// match with its channels one behind the other.  The windows' columns are replicated ceil(window / step) times, so they
+// are written group by group into two slots and each group is matched where it lies.
 #include <algorithm>
 
 #include "shz_internal.h"
 
 #define SC_THREADS 256
-#define SC_SMALL_GROUP 3u   // windows of a group under SHZ_DEBUG_SCAN_SMALL_GROUPS
+#define SC_SMALL_GROUP 3u   // windows of a group under SHZ_DEBUG_SCAN_SMALL_GROUPS / SHZ_DEBUG_SCAN_SPEED_SMALL_SLICES
+#define SS_SMALL_RUNGS 2u   // rungs of a slice under SHZ_DEBUG_SCAN_SPEED_SMALL_SLICES (and 1 recording a slice)
 
-struct sc_pair { uint32_t clip, s; };                 // one channel of one window: its clip, the window's first frame
-struct sc_win { uint64_t pair0; uint32_t nch, s; };   // one window: its first (window, channel) pair, its channels, its first frame
+struct sc_rec {        // one recording of a slice; the entry behind the last one holds the slice's totals
+  uint64_t win0;       // its first window among the slice's windows
+  uint64_t item0;      // its first (window, rung, channel) item: the sum of windows x rungs x channels in front of it
+  uint64_t seg0;       // its first segment of the hashes' CSR: (rung, channel) at seg0 + rung * nch + channel
+  uint32_t nch, pad;
+};
 
 extern "C" uint64_t shz_scan_window_count(uint64_t frames, uint32_t window_frames, uint32_t step_frames) {
   if (frames == 0 || window_frames == 0 || step_frames == 0) return 0;
@@ -33,38 +44,234 @@ __device__ __forceinline__ uint64_t sc_lower_bound(const uint32_t* __restrict__ 
   return a;
 }
 
-// per (window, channel): where the window's hashes begin in the channel's list, and how many they are
-__global__ __launch_bounds__(SC_THREADS) void scan_bounds_kernel(const sc_pair* __restrict__ pairs, uint64_t n_pairs,
-                                                                 const uint64_t* __restrict__ hash_off, const uint32_t* __restrict__ t1,
-                                                                 uint32_t window_frames, uint64_t* __restrict__ first,
-                                                                 uint64_t* __restrict__ cnt) {
-  const uint64_t p = (uint64_t)blockIdx.x * SC_THREADS + threadIdx.x;
-  if (p >= n_pairs) return;
-  const sc_pair j = pairs[p];
-  const uint64_t a = hash_off[j.clip], b = hash_off[j.clip + 1];
-  const uint64_t lo = sc_lower_bound(t1, a, b, j.s);
-  const uint64_t hi = sc_lower_bound(t1, lo, b, (uint64_t)j.s + window_frames);
-  first[p] = lo;
-  cnt[p] = hi - lo;
+// sp_warp_t, unclamped (x < 2^47: frame counts are far below); at s16 = 65536 it is x itself
+__device__ __forceinline__ uint64_t sc_warp(uint64_t x, uint32_t s16) { return (x * s16 + 32768u) >> 16; }
+
+// per (window, rung, channel): where the window's hashes begin in the list of (rung, channel), and how many they are
+__global__ __launch_bounds__(SC_THREADS) void sc_bounds_kernel(const sc_rec* __restrict__ recs, uint32_t nr, uint64_t n_items,
+                                                               const uint32_t* __restrict__ speed, uint32_t kc,
+                                                               uint32_t window_frames, uint32_t step_frames,
+                                                               const uint64_t* __restrict__ hoff, const uint32_t* __restrict__ t1,
+                                                               uint64_t* __restrict__ first, uint64_t* __restrict__ cnt) {
+  const uint64_t i = (uint64_t)blockIdx.x * SC_THREADS + threadIdx.x;
+  if (i >= n_items) return;
+  uint32_t lo = 0, hi = nr;   // the last recording whose first item is <= i (recordings without windows share a start)
+  while (lo + 1 < hi) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (recs[mid].item0 <= i) lo = mid; else hi = mid;
+  }
+  const sc_rec R = recs[lo];
+  const uint64_t rem = i - R.item0, qv = rem / R.nch, c = rem - qv * R.nch, w = qv / kc, v = qv - w * kc;
+  const uint32_t s16 = speed[v];
+  // (with step > window the last window may start behind the recording's end, above every t1: the searches compare in
+  // 64 bits, so it is empty whatever its start is, with no clamp to the 32 bits of t1)
+  const uint64_t s = w * step_frames, e = R.seg0 + v * R.nch + c;
+  const uint64_t a = hoff[e], b = hoff[e + 1];
+  const uint64_t p = sc_lower_bound(t1, a, b, sc_warp(s, s16));
+  const uint64_t q = sc_lower_bound(t1, p, b, sc_warp(s + window_frames, s16));
+  first[i] = p;
+  cnt[i] = q - p;
 }
 
-// one workgroup per window of the group [w0, w0 + gridDim.x): its channels' ranges, one behind the other, to
-// offs[pair] - base of the group's columns (offs: exclusive scan of the counts, the total behind it)
-__global__ __launch_bounds__(SC_THREADS) void scan_gather_kernel(const sc_win* __restrict__ wins, uint64_t w0,
-                                                                 const uint64_t* __restrict__ first, const uint64_t* __restrict__ offs,
-                                                                 uint64_t base, uint64_t cap, const uint32_t* __restrict__ key,
-                                                                 const uint32_t* __restrict__ t1, uint32_t* __restrict__ out_key,
-                                                                 uint32_t* __restrict__ out_qo) {
-  const sc_win w = wins[w0 + blockIdx.x];
-  for (uint32_t c = 0; c < w.nch; ++c) {
-    const uint64_t p = w.pair0 + c;
+// one workgroup per (window, rung) of the group [q0, q0 + gridDim.x) of the slice's queries: its channels' ranges, one
+// behind the other, to offs[item] - base of the group's columns (offs: exclusive scan of the counts, the total behind it)
+__global__ __launch_bounds__(SC_THREADS) void sc_gather_kernel(const sc_rec* __restrict__ recs, uint32_t nr, uint64_t q0,
+                                                               const uint32_t* __restrict__ speed, uint32_t kc, uint32_t step_frames,
+                                                               const uint64_t* __restrict__ first, const uint64_t* __restrict__ offs,
+                                                               uint64_t base, uint64_t cap, const uint32_t* __restrict__ key,
+                                                               const uint32_t* __restrict__ t1, uint32_t* __restrict__ out_key,
+                                                               uint32_t* __restrict__ out_qo) {
+  const uint64_t q = q0 + blockIdx.x;
+  uint32_t lo = 0, hi = nr;   // the last recording whose first query is <= q
+  while (lo + 1 < hi) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (recs[mid].win0 * kc <= q) lo = mid; else hi = mid;
+  }
+  const sc_rec R = recs[lo];
+  const uint64_t rem = q - R.win0 * kc, w = rem / kc, v = rem - w * kc;
+  const uint32_t t0 = (uint32_t)sc_warp(w * step_frames, speed[v]);   // (a window with entries starts below their t1' < 2^32)
+  for (uint32_t c = 0; c < R.nch; ++c) {
+    const uint64_t p = R.item0 + rem * R.nch + c;
     const uint64_t src = first[p], dst = offs[p] - base, n = offs[p + 1] - offs[p];
     if (dst + n > cap) return;   // (uniform; the host sizes the columns from the same offsets, so this never holds)
     for (uint64_t i = threadIdx.x; i < n; i += SC_THREADS) {
       out_key[dst + i] = key[src + i];
-      out_qo[dst + i] = t1[src + i] - w.s;
+      out_qo[dst + i] = t1[src + i] - t0;
     }
   }
+}
+
+// ---- what both scans refuse before the first launch ---------------------------------------------------------------------
+// In three parts, because the order of the refusals is part of the ABI and the speed scan's own (ladder, warped window
+// length; Fs, pcm) lie between them.
+static int32_t sc_check(shz_ctx* ctx, const char* who, uint32_t flags, const uint64_t* win_off, const uint64_t* count,
+                        uint32_t window_frames, uint32_t step_frames) {
+  if (flags & ~(SHZ_PCM_DEVICE | SHZ_MATCH_FULL_SORT)) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: flags may hold SHZ_PCM_DEVICE and SHZ_MATCH_FULL_SORT", who);
+  if (!win_off || !count) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: win_off or count is NULL", who);
+  if (window_frames == 0 || window_frames >= (1u << 20))
+    SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: window_frames must be in [1, 2^20) (query offsets), got %u", who, window_frames);
+  if (step_frames == 0) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: step_frames must be at least 1", who);
+  return SHZ_OK;
+}
+// the recordings' clips; without recordings there is nothing more to check, and the caller is done
+static int32_t sc_check_recs(shz_ctx* ctx, const char* who, const uint64_t* clip_off, uint32_t n_clips, const uint32_t* rec_clip0,
+                             uint32_t n_recs, uint64_t* win_off) {
+  win_off[0] = 0;
+  if (n_recs == 0) {
+    if (n_clips) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: %u clips belong to no recording", who, n_clips);
+    return SHZ_OK;
+  }
+  SHZ_TRY(shz_check_clip0(ctx, "rec_clip0", "recording", rec_clip0, n_recs, n_clips));
+  return shz_check_clip_off(ctx, clip_off, n_clips);
+}
+// the windows: their number follows from the frame counts alone, in the recording's own frames.  win_off and *count are
+// written whether or not the caller has room for them; *frames (if asked for): the frames of all clips together
+static int32_t sc_count_windows(shz_ctx* ctx, const char* who, const uint64_t* clip_off, const uint32_t* rec_clip0, uint32_t n_recs,
+                                uint32_t window_frames, uint32_t step_frames, uint64_t cap_windows, uint64_t* win_off,
+                                uint64_t* count, uint64_t* frames) {
+  uint64_t n_wins = 0, all = 0;
+  for (uint32_t r = 0; r < n_recs; ++r) {
+    uint64_t f = 0;
+    for (uint32_t c = rec_clip0[r]; c < rec_clip0[r + 1]; ++c) {
+      const uint64_t fc = shz_frame_count_hop(clip_off[c + 1] - clip_off[c], ctx->hop);
+      f = std::max<uint64_t>(f, fc);
+      all += fc;
+    }
+    n_wins += shz_scan_window_count(f, window_frames, step_frames);
+    win_off[r + 1] = n_wins;
+  }
+  *count = n_wins;
+  if (frames) *frames = all;
+  if (n_wins > cap_windows)
+    SHZ_FAIL(ctx, SHZ_E_CAPACITY, "%s: %llu windows, room for %llu", who, (unsigned long long)n_wins, (unsigned long long)cap_windows);
+  return SHZ_OK;
+}
+
+// ---- the window stage ---------------------------------------------------------------------------------------------------
+struct sc_slice {
+  const uint32_t* clip0;         // rec_clip0 and win_off of the call from the slice's first recording on: nr + 1 entries
+  const uint64_t* woff;          // (at least one of the nr recordings has a window)
+  uint32_t nr, kc;
+  const uint32_t* speed;         // the slice's kc rungs (Q16)
+  const uint64_t* hoff;          // CSR of the segments (recording, rung, channel) over key / t1, relative to them
+  bool tables_on_host;           // speed and hoff are on the host (they go up with the descriptors) / on the device
+  const uint32_t *d_key, *d_t1;  // the hashes (device), `total` of them
+  uint64_t total;
+  uint32_t window_frames, step_frames, topn, flags;   // flags: SHZ_MATCH_FULL_SORT
+  int64_t bias_bound;            // of the match: no query offset is above it
+  uint64_t rep;                  // the windows a hash can lie in at one rung (the sanity bound)
+  bool small_groups;             // SC_SMALL_GROUP windows a group (the callers' debug switches)
+  uint32_t *sid, *aligned, *dedup, *nres, *nhash;   // results, (window, rung)-major; nhash and npairs may be NULL
+  int32_t* delta;
+  uint64_t* npairs;
+};
+
+// Cuts the slice's hash lists into its windows and matches every (window, rung).  Device times are added to *win_ms and
+// *match_ms when `timed` (events sc_ev[2 .. 4]).  The stream is idle on return.
+static int32_t sc_windows(shz_ctx* ctx, shz_table* t, const char* who, const sc_slice& S, bool timed, float* win_ms, float* match_ms) {
+  if (timed) SHZ_HIP(ctx, hipEventRecord(ctx->sc_ev[2], ctx->stream));
+  const uint32_t nr = S.nr, kc = S.kc, topn = S.topn, *clip0 = S.clip0;
+  const uint64_t* woff = S.woff;
+  const uint64_t nws = woff[nr] - woff[0], n_seg = (uint64_t)(clip0[nr] - clip0[0]) * kc;
+  // 1) one descriptor a recording (behind them, if they come from the host: hoff | speed), and the first item of every window
+  const uint64_t rec_bytes = ((uint64_t)nr + 1) * sizeof(sc_rec), hoff_bytes = S.tables_on_host ? (n_seg + 1) * 8 : 0;
+  std::vector<char> block(rec_bytes + hoff_bytes + (S.tables_on_host ? (uint64_t)kc * 4 : 0));
+  sc_rec* hrec = (sc_rec*)block.data();
+  std::vector<uint64_t> win_item((size_t)nws + 1);
+  uint64_t n_items = 0;
+  for (uint32_t r = 0; r < nr; ++r) {
+    const uint32_t nch = clip0[r + 1] - clip0[r];
+    const uint64_t w0 = woff[r] - woff[0], nw = woff[r + 1] - woff[r];
+    hrec[r] = sc_rec{w0, n_items, (uint64_t)(clip0[r] - clip0[0]) * kc, nch, 0};
+    for (uint64_t w = 0; w < nw; ++w) win_item[w0 + w] = n_items + w * kc * nch;
+    n_items += nw * kc * nch;
+  }
+  hrec[nr] = sc_rec{nws, n_items, n_seg, 0, 0};
+  win_item[nws] = n_items;
+  void *d_rec, *d_ctl;
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SC_JOBS, block.size(), &d_rec));
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SC_CTL, (3 * n_items + 1) * 8, &d_ctl));
+  uint64_t *d_first = (uint64_t*)d_ctl, *d_cnt = d_first + n_items, *d_offs = d_cnt + n_items;   // d_offs[n_items] = the total
+  const uint64_t* d_hoff = S.hoff;
+  const uint32_t* d_speed = S.speed;
+  if (S.tables_on_host) {
+    memcpy(block.data() + rec_bytes, S.hoff, hoff_bytes);
+    memcpy(block.data() + rec_bytes + hoff_bytes, S.speed, (uint64_t)kc * 4);
+    d_hoff = (const uint64_t*)((char*)d_rec + rec_bytes);
+    d_speed = (const uint32_t*)((char*)d_rec + rec_bytes + hoff_bytes);
+  }
+  // 2) upload, 3) bounds, scan, one read-back: the offsets of every item
+  std::vector<uint64_t> offs((size_t)n_items + 1, 0);
+  if (S.total) {   // (without hashes every window is empty, and a warp pass has no CSR on the device)
+    SHZ_HIP(ctx, shz_memcpy(ctx, d_rec, block.data(), block.size(), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(sc_bounds_kernel, dim3((unsigned)((n_items + SC_THREADS - 1) / SC_THREADS)), dim3(SC_THREADS), 0, ctx->stream,
+                       (const sc_rec*)d_rec, nr, n_items, d_speed, kc, S.window_frames, S.step_frames, d_hoff, S.d_t1, d_first, d_cnt);
+    SHZ_HIP(ctx, hipGetLastError());
+    SHZ_TRY(shz_scan_u64(ctx, d_cnt, d_offs, n_items, d_offs + n_items));
+    SHZ_HIP(ctx, shz_memcpy(ctx, offs.data(), d_offs, (n_items + 1) * 8, hipMemcpyDeviceToHost));
+  }
+  if (timed) SHZ_HIP(ctx, hipEventRecord(ctx->sc_ev[3], ctx->stream));
+  SHZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (timed) {
+    float a = 0.f;
+    SHZ_HIP(ctx, hipEventElapsedTime(&a, ctx->sc_ev[2], ctx->sc_ev[3]));
+    *win_ms += a;
+  }
+  // 4) a hash lies in at most `rep` windows
+  if (offs[n_items] > S.total * S.rep)
+    SHZ_FAIL(ctx, SHZ_E_STATE, "%s: %llu window entries from %llu hashes", who, (unsigned long long)offs[n_items],
+             (unsigned long long)S.total);
+  auto win_at = [&](uint64_t w) { return offs[win_item[w]]; };
+  // 5) the groups.  A group's columns take at most 1/8 of the workspace limit (the match sizes its own sub-batches inside a
+  // group) and hold at most 2^24 queries; a window is never split and its rungs stay together, so one larger than that is
+  // a group of its own
+  const uint64_t max_entries = std::min<uint64_t>(std::max<uint64_t>(ctx->ws_limit / 64, 1), 1ull << 30);
+  const uint64_t max_wins = S.small_groups ? SC_SMALL_GROUP : std::max<uint64_t>((1ull << 24) / kc, 1);
+  std::vector<uint64_t> groups{0};   // first window of every group, nws behind them
+  uint64_t m_max = 0;
+  for (uint64_t g0 = 0; g0 < nws;) {
+    uint64_t g1 = g0 + 1;
+    while (g1 < nws && g1 - g0 < max_wins && win_at(g1 + 1) - win_at(g0) <= max_entries) ++g1;
+    m_max = std::max(m_max, win_at(g1) - win_at(g0));
+    groups.push_back(g1);
+    g0 = g1;
+  }
+  // 6) the columns of the largest group, 7) group by group: gather the columns of (window, rung), match them where they lie
+  void *d_gk, *d_gq;
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SC_KEY, m_max * 4 + 64, &d_gk));
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SC_QO, m_max * 4 + 64, &d_gq));
+  std::vector<uint64_t> query_off;
+  for (size_t g = 0; g + 1 < groups.size(); ++g) {
+    const uint64_t g0 = groups[g], g1 = groups[g + 1], base = win_at(g0), m = win_at(g1) - base, nq = (g1 - g0) * kc;
+    if (timed) SHZ_HIP(ctx, hipEventRecord(ctx->sc_ev[2], ctx->stream));
+    if (m) {
+      hipLaunchKernelGGL(sc_gather_kernel, dim3((unsigned)nq), dim3(SC_THREADS), 0, ctx->stream, (const sc_rec*)d_rec, nr, g0 * kc,
+                         d_speed, kc, S.step_frames, (const uint64_t*)d_first, (const uint64_t*)d_offs, base, m, S.d_key, S.d_t1,
+                         (uint32_t*)d_gk, (uint32_t*)d_gq);
+      SHZ_HIP(ctx, hipGetLastError());
+    }
+    if (timed) SHZ_HIP(ctx, hipEventRecord(ctx->sc_ev[3], ctx->stream));
+    query_off.resize((size_t)nq + 1);
+    for (uint64_t w = g0; w < g1; ++w) {
+      const uint64_t nch = (win_item[w + 1] - win_item[w]) / kc;
+      for (uint32_t v = 0; v < kc; ++v) query_off[(size_t)((w - g0) * kc + v)] = offs[win_item[w] + v * nch] - base;
+    }
+    query_off[nq] = m;
+    const uint64_t o = g0 * kc;
+    SHZ_TRY(shz_match_device(ctx, t, (const uint32_t*)d_gk, (const uint32_t*)d_gq, query_off.data(), (uint32_t)nq, topn, S.flags,
+                             S.bias_bound, S.sid + o * topn, S.delta + o * topn, S.aligned + o * topn, S.dedup + o * topn,
+                             S.nres + o, S.nhash ? S.nhash + o : nullptr, S.npairs ? S.npairs + o : nullptr));
+    if (timed) {
+      float a = 0.f, b = 0.f;
+      SHZ_HIP(ctx, hipEventRecord(ctx->sc_ev[4], ctx->stream));
+      SHZ_HIP(ctx, hipEventSynchronize(ctx->sc_ev[4]));
+      SHZ_HIP(ctx, hipEventElapsedTime(&a, ctx->sc_ev[2], ctx->sc_ev[3]));
+      SHZ_HIP(ctx, hipEventElapsedTime(&b, ctx->sc_ev[3], ctx->sc_ev[4]));
+      *win_ms += a;
+      *match_ms += b;
+    }
+  }
+  return SHZ_OK;
 }
 
 extern "C" int32_t shz_scan_batch(shz_ctx* ctx, shz_table* t, const int16_t* pcm, const uint64_t* clip_off, uint32_t n_clips,
@@ -73,48 +280,20 @@ extern "C" int32_t shz_scan_batch(shz_ctx* ctx, shz_table* t, const int16_t* pcm
                                   uint32_t* out_sid, int32_t* out_delta, uint32_t* out_aligned, uint32_t* out_dedup,
                                   uint32_t* out_nres, uint32_t* out_nhash, uint64_t* out_npairs, uint64_t cap_windows,
                                   uint64_t* count, float* ms_extract, float* ms_window, float* ms_match) {
+  const char* who = "shz_scan_batch";
   if (!ctx || !t) return SHZ_E_INVALID;
   if (ms_extract) *ms_extract = 0.f;
   if (ms_window) *ms_window = 0.f;
   if (ms_match) *ms_match = 0.f;
   if (count) *count = 0;
   // everything that can be refused is refused before the first launch
-  if (flags & ~(SHZ_PCM_DEVICE | SHZ_MATCH_FULL_SORT)) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_scan_batch: flags may hold SHZ_PCM_DEVICE and SHZ_MATCH_FULL_SORT");
-  if (!win_off || !count) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_scan_batch: win_off or count is NULL");
-  if (window_frames == 0 || window_frames >= (1u << 20))
-    SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_scan_batch: window_frames must be in [1, 2^20) (query offsets), got %u", window_frames);
-  if (step_frames == 0) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_scan_batch: step_frames must be at least 1");
+  SHZ_TRY(sc_check(ctx, who, flags, win_off, count, window_frames, step_frames));
   if (fan_value < 1 || fan_value > 64) SHZ_FAIL(ctx, SHZ_E_INVALID, "fan_value must be in [1,64]");
-  win_off[0] = 0;
-  if (n_recs == 0) {
-    if (n_clips) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_scan_batch: %u clips belong to no recording", n_clips);
-    return SHZ_OK;
-  }
-  if (!rec_clip0) SHZ_FAIL(ctx, SHZ_E_INVALID, "rec_clip0 is NULL");
-  if (rec_clip0[0] != 0 || rec_clip0[n_recs] != n_clips)
-    SHZ_FAIL(ctx, SHZ_E_INVALID, "rec_clip0 must start at 0 and end at n_clips = %u (it runs from %u to %u)", n_clips, rec_clip0[0],
-             rec_clip0[n_recs]);
-  for (uint32_t r = 0; r < n_recs; ++r)
-    if (rec_clip0[r + 1] < rec_clip0[r]) SHZ_FAIL(ctx, SHZ_E_INVALID, "rec_clip0 decreases at recording %u", r);
-  if (!clip_off) SHZ_FAIL(ctx, SHZ_E_INVALID, "clip_off is NULL");
-  for (uint32_t c = 0; c < n_clips; ++c)
-    if (clip_off[c + 1] < clip_off[c]) SHZ_FAIL(ctx, SHZ_E_INVALID, "clip_off decreases at clip %u", c);
+  SHZ_TRY(sc_check_recs(ctx, who, clip_off, n_clips, rec_clip0, n_recs, win_off));
+  if (n_recs == 0) return SHZ_OK;
   SHZ_TRY(shz_match_ready(ctx, t, topn));
-  // the windows: their number follows from the frame counts alone
-  uint64_t n_wins = 0, n_pairs = 0;
-  for (uint32_t r = 0; r < n_recs; ++r) {
-    uint64_t f = 0;
-    for (uint32_t c = rec_clip0[r]; c < rec_clip0[r + 1]; ++c)
-      f = std::max<uint64_t>(f, shz_frame_count_hop(clip_off[c + 1] - clip_off[c], ctx->hop));
-    const uint64_t w = shz_scan_window_count(f, window_frames, step_frames);
-    n_wins += w;
-    n_pairs += w * (rec_clip0[r + 1] - rec_clip0[r]);
-    win_off[r + 1] = n_wins;
-  }
-  *count = n_wins;
-  if (n_wins > cap_windows)
-    SHZ_FAIL(ctx, SHZ_E_CAPACITY, "shz_scan_batch: %llu windows, room for %llu", (unsigned long long)n_wins, (unsigned long long)cap_windows);
-  if (n_wins == 0) return SHZ_OK;
+  SHZ_TRY(sc_count_windows(ctx, who, clip_off, rec_clip0, n_recs, window_frames, step_frames, cap_windows, win_off, count, nullptr));
+  if (*count == 0) return SHZ_OK;
   if (!out_sid || !out_delta || !out_aligned || !out_dedup || !out_nres) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_scan_batch: NULL buffer");
   SHZ_HIP(ctx, hipSetDevice(ctx->device));
   const bool timed = ms_extract || ms_window || ms_match;
@@ -126,101 +305,19 @@ extern "C" int32_t shz_scan_batch(shz_ctx* ctx, shz_table* t, const int16_t* pcm
   // 1) every clip fingerprinted once, into the library's own buffers
   std::vector<uint64_t> hash_off((size_t)n_clips + 1, 0);
   const uint32_t *d_key = nullptr, *d_t1 = nullptr;
-  SHZ_TRY(shz_extract_owned(ctx, "shz_scan_batch", pcm, clip_off, n_clips, fs, amp_min, fan_value, flags & SHZ_PCM_DEVICE,
-                            hash_off.data(), &d_key, &d_t1));
+  SHZ_TRY(shz_extract_owned(ctx, who, pcm, clip_off, n_clips, fs, amp_min, fan_value, flags & SHZ_PCM_DEVICE, hash_off.data(), &d_key,
+                            &d_t1));
   if (timed) SHZ_HIP(ctx, hipEventRecord(ctx->sc_ev[1], ctx->stream));
-  // 2) the jobs: (window, channel) pairs | windows | hash_off, one block
-  const uint64_t pair_bytes = (n_pairs * sizeof(sc_pair) + 255) & ~255ull, win_bytes = (n_wins * sizeof(sc_win) + 255) & ~255ull;
-  const uint64_t job_bytes = pair_bytes + win_bytes + ((uint64_t)n_clips + 1) * 8;
-  std::vector<char> hjobs(job_bytes, 0);
-  sc_pair* hp = (sc_pair*)hjobs.data();
-  sc_win* hw = (sc_win*)(hjobs.data() + pair_bytes);
-  {
-    uint64_t p = 0, w = 0;
-    for (uint32_t r = 0; r < n_recs; ++r) {
-      const uint32_t c0 = rec_clip0[r], nch = rec_clip0[r + 1] - c0;
-      for (uint64_t i = 0; i < win_off[r + 1] - win_off[r]; ++i, ++w) {
-        // (with step > window the last window may start behind the recording's end: it is empty, and so is any start
-        // clamped to 2^32 - 1, which no t1 reaches)
-        const uint32_t s = (uint32_t)std::min<uint64_t>(i * step_frames, 0xFFFFFFFFull);
-        hw[w] = sc_win{p, nch, s};
-        for (uint32_t c = 0; c < nch; ++c) hp[p++] = sc_pair{c0 + c, s};
-      }
-    }
-  }
-  memcpy(hjobs.data() + pair_bytes + win_bytes, hash_off.data(), ((uint64_t)n_clips + 1) * 8);
-  void *d_jobs, *d_ctl;
-  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SC_JOBS, job_bytes, &d_jobs));
-  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SC_CTL, (3 * n_pairs + 1) * 8, &d_ctl));
-  const sc_pair* d_pairs = (const sc_pair*)d_jobs;
-  const sc_win* d_wins = (const sc_win*)((char*)d_jobs + pair_bytes);
-  const uint64_t* d_hoff = (const uint64_t*)((char*)d_jobs + pair_bytes + win_bytes);
-  uint64_t *d_first = (uint64_t*)d_ctl, *d_cnt = d_first + n_pairs, *d_offs = d_cnt + n_pairs;   // d_offs[n_pairs] = the total
-  SHZ_HIP(ctx, shz_memcpy(ctx, d_jobs, hjobs.data(), job_bytes, hipMemcpyHostToDevice));
-  // 3) bounds, 4) scan, 6) one read-back: the offsets of every pair (a recording with windows has a clip: n_pairs >= 1)
-  std::vector<uint64_t> offs((size_t)n_pairs + 1, 0);
-  hipLaunchKernelGGL(scan_bounds_kernel, dim3((unsigned)((n_pairs + SC_THREADS - 1) / SC_THREADS)), dim3(SC_THREADS), 0, ctx->stream,
-                     d_pairs, n_pairs, d_hoff, d_t1, window_frames, d_first, d_cnt);
-  SHZ_HIP(ctx, hipGetLastError());
-  SHZ_TRY(shz_scan_u64(ctx, d_cnt, d_offs, n_pairs, d_offs + n_pairs));
-  SHZ_HIP(ctx, shz_memcpy(ctx, offs.data(), d_offs, (n_pairs + 1) * 8, hipMemcpyDeviceToHost));
-  if (timed) SHZ_HIP(ctx, hipEventRecord(ctx->sc_ev[2], ctx->stream));
-  SHZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  // 2) the window stage at unity: all recordings, one rung of factor 65536 over the extraction's own CSR.  A hash lies in
+  // at most ceil(window / step) windows; no query offset reaches window_frames
+  const uint32_t one = SP_S_ONE;
   float win_ms = 0.f, match_ms = 0.f;
-  if (timed) {
-    if (ms_extract) SHZ_HIP(ctx, hipEventElapsedTime(ms_extract, ctx->sc_ev[0], ctx->sc_ev[1]));
-    SHZ_HIP(ctx, hipEventElapsedTime(&win_ms, ctx->sc_ev[1], ctx->sc_ev[2]));
-  }
-  // a hash lies in at most ceil(window / step) windows
-  const uint64_t total = offs[n_pairs], rep = ((uint64_t)window_frames + step_frames - 1) / step_frames;
-  if (total > hash_off[n_clips] * rep)
-    SHZ_FAIL(ctx, SHZ_E_STATE, "shz_scan_batch: %llu window entries from %llu hashes", (unsigned long long)total,
-             (unsigned long long)hash_off[n_clips]);
-  auto win_at = [&](uint64_t w) { return w < n_wins ? offs[hw[w].pair0] : total; };
-  // 5) + 7) group by group: gather the windows' columns, match them where they lie.  A group's columns take at most 1/8 of
-  // the workspace limit (the match sizes its own sub-batches inside a group); a window is never split, so one larger than
-  // that is a group of its own
-  const uint64_t max_entries = std::min<uint64_t>(std::max<uint64_t>(ctx->ws_limit / 64, 1), 1ull << 30);
-  const uint64_t max_wins = (ctx->debug & SHZ_DEBUG_SCAN_SMALL_GROUPS) ? SC_SMALL_GROUP : (1ull << 24);
-  std::vector<uint64_t> groups{0};   // first window of every group, n_wins behind them
-  uint64_t m_max = 0;
-  for (uint64_t g0 = 0; g0 < n_wins;) {
-    uint64_t g1 = g0 + 1;
-    while (g1 < n_wins && g1 - g0 < max_wins && win_at(g1 + 1) - win_at(g0) <= max_entries) ++g1;
-    m_max = std::max(m_max, win_at(g1) - win_at(g0));
-    groups.push_back(g1);
-    g0 = g1;
-  }
-  void *d_gk, *d_gq;
-  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SC_KEY, m_max * 4 + 64, &d_gk));
-  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SC_QO, m_max * 4 + 64, &d_gq));
-  std::vector<uint64_t> query_off;
-  for (size_t g = 0; g + 1 < groups.size(); ++g) {
-    const uint64_t g0 = groups[g], nq = groups[g + 1] - g0, base = win_at(g0), m = win_at(g0 + nq) - base;
-    if (timed) SHZ_HIP(ctx, hipEventRecord(ctx->sc_ev[2], ctx->stream));
-    if (m) {
-      hipLaunchKernelGGL(scan_gather_kernel, dim3((unsigned)nq), dim3(SC_THREADS), 0, ctx->stream, d_wins, g0, (const uint64_t*)d_first,
-                         (const uint64_t*)d_offs, base, m, d_key, d_t1, (uint32_t*)d_gk, (uint32_t*)d_gq);
-      SHZ_HIP(ctx, hipGetLastError());
-    }
-    if (timed) SHZ_HIP(ctx, hipEventRecord(ctx->sc_ev[3], ctx->stream));
-    query_off.resize((size_t)nq + 1);
-    for (uint64_t w = 0; w <= nq; ++w) query_off[w] = win_at(g0 + w) - base;
-    const uint64_t o = g0 * topn;
-    SHZ_TRY(shz_match_device(ctx, t, (const uint32_t*)d_gk, (const uint32_t*)d_gq, query_off.data(), (uint32_t)nq, topn,
-                             flags & SHZ_MATCH_FULL_SORT, (int64_t)window_frames - 1, out_sid + o, out_delta + o, out_aligned + o,
-                             out_dedup + o, out_nres + g0, out_nhash ? out_nhash + g0 : nullptr,
-                             out_npairs ? out_npairs + g0 : nullptr));
-    if (timed) {
-      float a = 0.f, b = 0.f;
-      SHZ_HIP(ctx, hipEventRecord(ctx->sc_ev[4], ctx->stream));
-      SHZ_HIP(ctx, hipEventSynchronize(ctx->sc_ev[4]));
-      SHZ_HIP(ctx, hipEventElapsedTime(&a, ctx->sc_ev[2], ctx->sc_ev[3]));
-      SHZ_HIP(ctx, hipEventElapsedTime(&b, ctx->sc_ev[3], ctx->sc_ev[4]));
-      win_ms += a;
-      match_ms += b;
-    }
-  }
+  sc_slice S{rec_clip0, win_off, n_recs, 1, &one, hash_off.data(), true, d_key, d_t1, hash_off[n_clips], window_frames, step_frames,
+             topn, flags & SHZ_MATCH_FULL_SORT, (int64_t)window_frames - 1, ((uint64_t)window_frames + step_frames - 1) / step_frames,
+             (ctx->debug & SHZ_DEBUG_SCAN_SMALL_GROUPS) != 0, out_sid, out_aligned, out_dedup, out_nres, out_nhash, out_delta,
+             out_npairs};
+  SHZ_TRY(sc_windows(ctx, t, who, S, timed, &win_ms, &match_ms));
+  if (ms_extract) SHZ_HIP(ctx, hipEventElapsedTime(ms_extract, ctx->sc_ev[0], ctx->sc_ev[1]));
   if (ms_window) *ms_window = win_ms;
   if (ms_match) *ms_match = match_ms;
   return SHZ_OK;
@@ -286,76 +383,8 @@ extern "C" int32_t shz_scan_timeline(const uint64_t* win_off, uint32_t n_recs, c
 
 // ---- scanning at an unknown speed -------------------------------------------------------------------
 // The peaks of every recording are extracted once and warped for every rung of a ladder (shz_speed.hip); the warped hash
-// list of (recording, rung, channel) has non-decreasing t1', so the window that starts at recording frame s is, at rung v,
-// the range W_v(s) <= t1' < W_v(s + window_frames) of every channel's list, W_v(x) = (x s16 + 32768) >> 16 -- two
-// lower-bound searches again.  Nothing per window is built on the host: the kernels derive s and both bounds from one
-// descriptor per recording and the rung table.  Work goes in slices of (whole recordings x a contiguous chunk of rungs);
-// inside a slice the items are (window, rung, channel), window-major, so that (window, rung) is one contiguous query of
-// the match with its channels one behind the other.
-#define SS_SMALL_RUNGS 2u   // rungs of a slice under SHZ_DEBUG_SCAN_SPEED_SMALL_SLICES (and 1 recording, 3 windows a group)
-
-struct ss_rec {        // one recording of a slice; the entry behind the last one holds the slice's totals
-  uint64_t win0;       // its first window among the slice's windows
-  uint64_t item0;      // its first (window, rung, channel) item: the sum of windows x rungs x channels in front of it
-  uint64_t seg0;       // its first segment of the warp's CSR: (rung, channel) at seg0 + rung * nch + channel
-  uint32_t nch, pad;
-};
-
-__device__ __forceinline__ uint64_t ss_warp(uint64_t x, uint32_t s16) { return (x * s16 + 32768u) >> 16; }   // sp_warp_t, unclamped (x < 2^34)
-
-// per (window, rung, channel): where the window's hashes begin in the warped list of (rung, channel), and how many they are
-__global__ __launch_bounds__(SC_THREADS) void ss_bounds_kernel(const ss_rec* __restrict__ recs, uint32_t nr, uint64_t n_items,
-                                                               const uint32_t* __restrict__ speed, uint32_t kc,
-                                                               uint32_t window_frames, uint32_t step_frames,
-                                                               const unsigned long long* __restrict__ hoff,
-                                                               const uint32_t* __restrict__ t1, uint64_t* __restrict__ first,
-                                                               uint64_t* __restrict__ cnt) {
-  const uint64_t i = (uint64_t)blockIdx.x * SC_THREADS + threadIdx.x;
-  if (i >= n_items) return;
-  uint32_t lo = 0, hi = nr;   // the last recording whose first item is <= i (recordings without windows share a start)
-  while (lo + 1 < hi) {
-    const uint32_t mid = (lo + hi) >> 1;
-    if (recs[mid].item0 <= i) lo = mid; else hi = mid;
-  }
-  const ss_rec R = recs[lo];
-  const uint64_t rem = i - R.item0, qv = rem / R.nch, c = rem - qv * R.nch, w = qv / kc, v = qv - w * kc;
-  const uint32_t s16 = speed[v];
-  const uint64_t s = w * step_frames, e = R.seg0 + v * R.nch + c;
-  const uint64_t a = hoff[e], b = hoff[e + 1];
-  const uint64_t p = sc_lower_bound(t1, a, b, ss_warp(s, s16));
-  const uint64_t q = sc_lower_bound(t1, p, b, ss_warp(s + window_frames, s16));
-  first[i] = p;
-  cnt[i] = q - p;
-}
-
-// one workgroup per (window, rung) of the group [q0, q0 + gridDim.x) of the slice's queries: its channels' ranges, one
-// behind the other, to offs[item] - base of the group's columns (offs: exclusive scan of the counts, the total behind it)
-__global__ __launch_bounds__(SC_THREADS) void ss_gather_kernel(const ss_rec* __restrict__ recs, uint32_t nr, uint64_t q0,
-                                                               const uint32_t* __restrict__ speed, uint32_t kc, uint32_t step_frames,
-                                                               const uint64_t* __restrict__ first, const uint64_t* __restrict__ offs,
-                                                               uint64_t base, uint64_t cap, const uint32_t* __restrict__ key,
-                                                               const uint32_t* __restrict__ t1, uint32_t* __restrict__ out_key,
-                                                               uint32_t* __restrict__ out_qo) {
-  const uint64_t q = q0 + blockIdx.x;
-  uint32_t lo = 0, hi = nr;   // the last recording whose first query is <= q
-  while (lo + 1 < hi) {
-    const uint32_t mid = (lo + hi) >> 1;
-    if (recs[mid].win0 * kc <= q) lo = mid; else hi = mid;
-  }
-  const ss_rec R = recs[lo];
-  const uint64_t rem = q - R.win0 * kc, w = rem / kc, v = rem - w * kc;
-  const uint32_t t0 = (uint32_t)ss_warp(w * step_frames, speed[v]);   // (a window with entries starts below their t1' < 2^32)
-  for (uint32_t c = 0; c < R.nch; ++c) {
-    const uint64_t p = R.item0 + rem * R.nch + c;
-    const uint64_t src = first[p], dst = offs[p] - base, n = offs[p + 1] - offs[p];
-    if (dst + n > cap) return;   // (uniform; the host sizes the columns from the same offsets, so this never holds)
-    for (uint64_t i = threadIdx.x; i < n; i += SC_THREADS) {
-      out_key[dst + i] = key[src + i];
-      out_qo[dst + i] = t1[src + i] - t0;
-    }
-  }
-}
-
+// list of (recording, rung, channel) has non-decreasing t1', so it goes through the window stage as it is.  Work goes in
+// slices of (whole recordings x a contiguous chunk of rungs): a warp pass and one call of the stage each.
 extern "C" int32_t shz_scan_speeds(shz_ctx* ctx, shz_table* t, const int16_t* pcm, const uint64_t* clip_off, uint32_t n_clips,
                                    const uint32_t* rec_clip0, uint32_t n_recs, uint32_t fs, double amp_min, uint32_t fan_value,
                                    uint32_t window_frames, uint32_t step_frames, uint32_t topn, const uint32_t* speed_q16,
@@ -363,6 +392,7 @@ extern "C" int32_t shz_scan_speeds(shz_ctx* ctx, shz_table* t, const int16_t* pc
                                    int32_t* out_delta, uint32_t* out_aligned, uint32_t* out_dedup, uint32_t* out_nres,
                                    uint32_t* out_nhash, uint64_t* out_npairs, uint32_t* out_profile, uint64_t cap_windows,
                                    uint64_t* count, float* ms_extract, float* ms_warp, float* ms_window, float* ms_match) {
+  const char* who = "shz_scan_speeds";
   if (!ctx || !t) return SHZ_E_INVALID;
   if (ms_extract) *ms_extract = 0.f;
   if (ms_warp) *ms_warp = 0.f;
@@ -370,50 +400,22 @@ extern "C" int32_t shz_scan_speeds(shz_ctx* ctx, shz_table* t, const int16_t* pc
   if (ms_match) *ms_match = 0.f;
   if (count) *count = 0;
   // everything that can be refused is refused before the first launch
-  if (flags & ~(SHZ_PCM_DEVICE | SHZ_MATCH_FULL_SORT)) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_scan_speeds: flags may hold SHZ_PCM_DEVICE and SHZ_MATCH_FULL_SORT");
-  if (!win_off || !count) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_scan_speeds: win_off or count is NULL");
-  if (window_frames == 0 || window_frames >= (1u << 20))
-    SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_scan_speeds: window_frames must be in [1, 2^20) (query offsets), got %u", window_frames);
-  if (step_frames == 0) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_scan_speeds: step_frames must be at least 1");
-  SHZ_TRY(sp_check_ladder(ctx, "shz_scan_speeds", speed_q16, n_speeds, fan_value));
+  SHZ_TRY(sc_check(ctx, who, flags, win_off, count, window_frames, step_frames));
+  SHZ_TRY(sp_check_ladder(ctx, who, speed_q16, n_speeds, fan_value));
   const uint32_t K = n_speeds, s_max = *std::max_element(speed_q16, speed_q16 + K);
   // no window is longer at any rung: W_v(s + window) - W_v(s) <= ceil(window s16 / 65536)
   const uint64_t len_max = ((uint64_t)window_frames * s_max + 65535) >> 16;
   if (len_max >= (1ull << 20))
     SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "shz_scan_speeds: a window of %u frames at factor %u / 65536 is %llu frames long; query offsets must be < 2^20",
              window_frames, s_max, (unsigned long long)len_max);
-  win_off[0] = 0;
-  if (n_recs == 0) {
-    if (n_clips) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_scan_speeds: %u clips belong to no recording", n_clips);
-    return SHZ_OK;
-  }
-  if (!rec_clip0) SHZ_FAIL(ctx, SHZ_E_INVALID, "rec_clip0 is NULL");
-  if (rec_clip0[0] != 0 || rec_clip0[n_recs] != n_clips)
-    SHZ_FAIL(ctx, SHZ_E_INVALID, "rec_clip0 must start at 0 and end at n_clips = %u (it runs from %u to %u)", n_clips, rec_clip0[0],
-             rec_clip0[n_recs]);
-  for (uint32_t r = 0; r < n_recs; ++r)
-    if (rec_clip0[r + 1] < rec_clip0[r]) SHZ_FAIL(ctx, SHZ_E_INVALID, "rec_clip0 decreases at recording %u", r);
-  if (!clip_off) SHZ_FAIL(ctx, SHZ_E_INVALID, "clip_off is NULL");
-  for (uint32_t c = 0; c < n_clips; ++c)
-    if (clip_off[c + 1] < clip_off[c]) SHZ_FAIL(ctx, SHZ_E_INVALID, "clip_off decreases at clip %u", c);
+  SHZ_TRY(sc_check_recs(ctx, who, clip_off, n_clips, rec_clip0, n_recs, win_off));
+  if (n_recs == 0) return SHZ_OK;
   if (fs == 0) SHZ_FAIL(ctx, SHZ_E_INVALID, "Fs must be > 0");
   if (n_clips && !pcm && clip_off[n_clips] > clip_off[0]) SHZ_FAIL(ctx, SHZ_E_INVALID, "pcm is NULL");
   SHZ_TRY(shz_match_ready(ctx, t, topn));
-  // the windows: their number follows from the frame counts alone, in the recording's own frames
-  uint64_t n_wins = 0, frames = 0;
-  for (uint32_t r = 0; r < n_recs; ++r) {
-    uint64_t f = 0;
-    for (uint32_t c = rec_clip0[r]; c < rec_clip0[r + 1]; ++c) {
-      const uint64_t fc = shz_frame_count_hop(clip_off[c + 1] - clip_off[c], ctx->hop);
-      f = std::max<uint64_t>(f, fc);
-      frames += fc;
-    }
-    n_wins += shz_scan_window_count(f, window_frames, step_frames);
-    win_off[r + 1] = n_wins;
-  }
-  *count = n_wins;
-  if (n_wins > cap_windows)
-    SHZ_FAIL(ctx, SHZ_E_CAPACITY, "shz_scan_speeds: %llu windows, room for %llu", (unsigned long long)n_wins, (unsigned long long)cap_windows);
+  uint64_t frames = 0;
+  SHZ_TRY(sc_count_windows(ctx, who, clip_off, rec_clip0, n_recs, window_frames, step_frames, cap_windows, win_off, count, &frames));
+  const uint64_t n_wins = *count;
   if (n_wins == 0) return SHZ_OK;
   if (!out_best || !out_sid || !out_delta || !out_aligned || !out_dedup || !out_nres) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_scan_speeds: NULL buffer");
   SHZ_HIP(ctx, hipSetDevice(ctx->device));
@@ -427,8 +429,7 @@ extern "C" int32_t shz_scan_speeds(shz_ctx* ctx, shz_table* t, const int16_t* pc
   std::vector<uint64_t> peak_off((size_t)n_clips + 1, 0);
   const uint16_t* d_pf = nullptr;
   const uint32_t* d_pt = nullptr;
-  SHZ_TRY(sp_peaks_owned(ctx, "shz_scan_speeds", pcm, clip_off, n_clips, frames, fs, amp_min, flags & SHZ_PCM_DEVICE, peak_off.data(),
-                         &d_pf, &d_pt));
+  SHZ_TRY(sp_peaks_owned(ctx, who, pcm, clip_off, n_clips, frames, fs, amp_min, flags & SHZ_PCM_DEVICE, peak_off.data(), &d_pf, &d_pt));
   if (timed) {
     SHZ_HIP(ctx, hipEventRecord(ctx->sc_ev[1], ctx->stream));
     SHZ_HIP(ctx, hipEventSynchronize(ctx->sc_ev[1]));
@@ -443,14 +444,11 @@ extern "C" int32_t shz_scan_speeds(shz_ctx* ctx, shz_table* t, const int16_t* pc
   const bool small = (ctx->debug & SHZ_DEBUG_SCAN_SPEED_SMALL_SLICES) != 0;
   const uint64_t per_item = std::max<uint32_t>(fan_value - 1, 1);
   const uint64_t warp_entries = std::min<uint64_t>(std::max<uint64_t>(ctx->ws_limit / 64, 1), 1ull << 28);
-  const uint64_t group_entries = std::min<uint64_t>(std::max<uint64_t>(ctx->ws_limit / 64, 1), 1ull << 30);
-  const int64_t bias = (int64_t)len_max - 1;
   auto dist = [&](uint32_t v) { return speed_q16[v] > SP_S_ONE ? speed_q16[v] - SP_S_ONE : SP_S_ONE - speed_q16[v]; };
   std::vector<uint32_t> best_top1((size_t)n_wins, 0);
   std::vector<uint32_t> v_sid, v_aligned, v_dedup, v_nres, v_nhash;
   std::vector<int32_t> v_delta;
-  std::vector<uint64_t> v_npairs, ho, offs, win_item, query_off;
-  std::vector<ss_rec> hrec;
+  std::vector<uint64_t> v_npairs, ho;
   float warp_ms = 0.f, win_ms = 0.f, match_ms = 0.f;
   for (uint32_t r0 = 0; r0 < n_recs;) {
     uint32_t nr = 1, kc = K;
@@ -468,8 +466,9 @@ extern "C" int32_t shz_scan_speeds(shz_ctx* ctx, shz_table* t, const int16_t* pc
     }
     for (uint32_t v0 = 0; v0 < K; v0 += kc) {
       const uint32_t kcc = std::min(kc, K - v0);
-      // 2a) the warp of the slice: hashes of (recording, rung, channel), the exact CSR on both sides
-      if (timed) SHZ_HIP(ctx, hipEventRecord(ctx->sc_ev[2], ctx->stream));
+      // 2a) the warp of the slice: hashes of (recording, rung, channel), the exact CSR on both sides (events 0 and 1 are
+      // free again: the window stage keeps to the others)
+      if (timed) SHZ_HIP(ctx, hipEventRecord(ctx->sc_ev[0], ctx->stream));
       const uint64_t n_seg = (uint64_t)(rec_clip0[r0 + nr] - rec_clip0[r0]) * kcc;
       ho.assign((size_t)n_seg + 1, 0);
       sp_pass P;
@@ -479,90 +478,21 @@ extern "C" int32_t shz_scan_speeds(shz_ctx* ctx, shz_table* t, const int16_t* pc
       SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SP_KEY, total * 4 + 64, &d_key));
       SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SP_T1, total * 4 + 64, &d_t1));
       if (total) SHZ_TRY(sp_write(ctx, P, (uint32_t*)d_key, (uint32_t*)d_t1, total));
-      if (timed) SHZ_HIP(ctx, hipEventRecord(ctx->sc_ev[3], ctx->stream));
-      // 2b) the windows of the slice: one descriptor a recording, bounds, scan, one read-back of the offsets
-      hrec.assign((size_t)nr + 1, ss_rec{0, 0, 0, 0, 0});
-      win_item.assign((size_t)nws + 1, 0);
-      uint64_t n_items = 0;
-      for (uint32_t r = 0; r < nr; ++r) {
-        const uint32_t c0 = rec_clip0[r0 + r], nch = rec_clip0[r0 + r + 1] - c0;
-        const uint64_t w0 = win_off[r0 + r] - win_off[r0], nw = win_off[r0 + r + 1] - win_off[r0 + r];
-        hrec[r] = ss_rec{w0, n_items, (uint64_t)(c0 - rec_clip0[r0]) * kcc, nch, 0};
-        for (uint64_t w = 0; w < nw; ++w) win_item[w0 + w] = n_items + w * kcc * nch;
-        n_items += nw * kcc * nch;
-      }
-      hrec[nr] = ss_rec{nws, n_items, n_seg, 0, 0};
-      win_item[nws] = n_items;
-      void *d_rec, *d_ctl;
-      SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SC_JOBS, ((uint64_t)nr + 1) * sizeof(ss_rec), &d_rec));
-      SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SC_CTL, (3 * n_items + 1) * 8, &d_ctl));
-      uint64_t *d_first = (uint64_t*)d_ctl, *d_cnt = d_first + n_items, *d_offs = d_cnt + n_items;   // d_offs[n_items] = the total
-      offs.assign((size_t)n_items + 1, 0);
-      if (total) {   // (without hashes every window is empty, and the pass has no CSR on the device)
-        SHZ_HIP(ctx, shz_memcpy(ctx, d_rec, hrec.data(), ((uint64_t)nr + 1) * sizeof(ss_rec), hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(ss_bounds_kernel, dim3((unsigned)((n_items + SC_THREADS - 1) / SC_THREADS)), dim3(SC_THREADS), 0, ctx->stream,
-                           (const ss_rec*)d_rec, nr, n_items, d_speed + v0, kcc, window_frames, step_frames,
-                           (const unsigned long long*)P.d_hoff, (const uint32_t*)d_t1, d_first, d_cnt);
-        SHZ_HIP(ctx, hipGetLastError());
-        SHZ_TRY(shz_scan_u64(ctx, d_cnt, d_offs, n_items, d_offs + n_items));
-        SHZ_HIP(ctx, shz_memcpy(ctx, offs.data(), d_offs, (n_items + 1) * 8, hipMemcpyDeviceToHost));
-      }
-      if (timed) SHZ_HIP(ctx, hipEventRecord(ctx->sc_ev[4], ctx->stream));
-      SHZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
-      if (timed) {
-        float a = 0.f, b = 0.f;
-        SHZ_HIP(ctx, hipEventElapsedTime(&a, ctx->sc_ev[2], ctx->sc_ev[3]));
-        SHZ_HIP(ctx, hipEventElapsedTime(&b, ctx->sc_ev[3], ctx->sc_ev[4]));
-        warp_ms += a;
-        win_ms += b;
-      }
-      // a hash lies in at most ceil(window / step) windows, +1 where the warp's rounding moves a border
-      const uint64_t rep = ((uint64_t)window_frames + step_frames - 1) / step_frames + 1;
-      if (offs[n_items] > total * rep)
-        SHZ_FAIL(ctx, SHZ_E_STATE, "shz_scan_speeds: %llu window entries from %llu hashes", (unsigned long long)offs[n_items],
-                 (unsigned long long)total);
-      auto win_at = [&](uint64_t w) { return offs[win_item[w]]; };
-      // 2c) group by group: gather the columns of (window, rung), match them where they lie.  A window's rungs stay together
-      const uint64_t max_wins = small ? SC_SMALL_GROUP : std::max<uint64_t>((1ull << 24) / kcc, 1);
+      if (timed) SHZ_HIP(ctx, hipEventRecord(ctx->sc_ev[1], ctx->stream));
+      // 2b) + 2c) the window stage on the warped lists.  A hash lies in at most ceil(window / step) windows, +1 where the
+      // warp's rounding moves a border; no query offset reaches len_max.  (A pass without hashes has no CSR on the device)
       const uint64_t nvq = nws * kcc;
       v_sid.assign(nvq * topn, 0); v_aligned.assign(nvq * topn, 0); v_dedup.assign(nvq * topn, 0); v_delta.assign(nvq * topn, 0);
       v_nres.assign(nvq, 0); v_nhash.assign(nvq, 0); v_npairs.assign(nvq, 0);
-      for (uint64_t g0 = 0; g0 < nws;) {
-        uint64_t g1 = g0 + 1;
-        while (g1 < nws && g1 - g0 < max_wins && win_at(g1 + 1) - win_at(g0) <= group_entries) ++g1;
-        const uint64_t base = win_at(g0), m = win_at(g1) - base, nq = (g1 - g0) * kcc;
-        void *d_gk, *d_gq;
-        SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SC_KEY, m * 4 + 64, &d_gk));
-        SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SC_QO, m * 4 + 64, &d_gq));
-        if (timed) SHZ_HIP(ctx, hipEventRecord(ctx->sc_ev[2], ctx->stream));
-        if (m) {
-          hipLaunchKernelGGL(ss_gather_kernel, dim3((unsigned)nq), dim3(SC_THREADS), 0, ctx->stream, (const ss_rec*)d_rec, nr, g0 * kcc,
-                             d_speed + v0, kcc, step_frames, (const uint64_t*)d_first, (const uint64_t*)d_offs, base, m,
-                             (const uint32_t*)d_key, (const uint32_t*)d_t1, (uint32_t*)d_gk, (uint32_t*)d_gq);
-          SHZ_HIP(ctx, hipGetLastError());
-        }
-        if (timed) SHZ_HIP(ctx, hipEventRecord(ctx->sc_ev[3], ctx->stream));
-        query_off.resize((size_t)nq + 1);
-        for (uint64_t w = g0; w < g1; ++w) {
-          const uint64_t nch = (win_item[w + 1] - win_item[w]) / kcc;
-          for (uint32_t v = 0; v < kcc; ++v) query_off[(size_t)((w - g0) * kcc + v)] = offs[win_item[w] + v * nch] - base;
-        }
-        query_off[nq] = m;
-        const uint64_t o = g0 * kcc;
-        SHZ_TRY(shz_match_device(ctx, t, (const uint32_t*)d_gk, (const uint32_t*)d_gq, query_off.data(), (uint32_t)nq, topn,
-                                 flags & SHZ_MATCH_FULL_SORT, bias, v_sid.data() + o * topn, v_delta.data() + o * topn,
-                                 v_aligned.data() + o * topn, v_dedup.data() + o * topn, v_nres.data() + o, v_nhash.data() + o,
-                                 v_npairs.data() + o));
-        if (timed) {
-          float a = 0.f, b = 0.f;
-          SHZ_HIP(ctx, hipEventRecord(ctx->sc_ev[4], ctx->stream));
-          SHZ_HIP(ctx, hipEventSynchronize(ctx->sc_ev[4]));
-          SHZ_HIP(ctx, hipEventElapsedTime(&a, ctx->sc_ev[2], ctx->sc_ev[3]));
-          SHZ_HIP(ctx, hipEventElapsedTime(&b, ctx->sc_ev[3], ctx->sc_ev[4]));
-          win_ms += a;
-          match_ms += b;
-        }
-        g0 = g1;
+      sc_slice S{rec_clip0 + r0, win_off + r0, nr, kcc, d_speed + v0, total ? (const uint64_t*)P.d_hoff : nullptr, false,
+                 (const uint32_t*)d_key, (const uint32_t*)d_t1, total, window_frames, step_frames, topn, flags & SHZ_MATCH_FULL_SORT,
+                 (int64_t)len_max - 1, ((uint64_t)window_frames + step_frames - 1) / step_frames + 1, small, v_sid.data(),
+                 v_aligned.data(), v_dedup.data(), v_nres.data(), v_nhash.data(), v_delta.data(), v_npairs.data()};
+      SHZ_TRY(sc_windows(ctx, t, who, S, timed, &win_ms, &match_ms));
+      if (timed) {
+        float a = 0.f;
+        SHZ_HIP(ctx, hipEventElapsedTime(&a, ctx->sc_ev[0], ctx->sc_ev[1]));
+        warp_ms += a;
       }
       // 2d) the best rung of every window, folded over the chunks (sp_best's rule: rungs come in index order)
       for (uint64_t w = 0; w < nws; ++w) {

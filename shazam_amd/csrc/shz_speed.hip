@@ -271,7 +271,7 @@ int32_t sp_write(shz_ctx* ctx, const sp_pass& P, uint32_t* d_key, uint32_t* d_t1
   return SHZ_OK;
 }
 
-// what both entry points refuse about a ladder and about the queries' clips, before anything is launched
+// what every entry point with a ladder refuses about it, before anything is launched
 int32_t sp_check_ladder(shz_ctx* ctx, const char* who, const uint32_t* speed_q16, uint32_t n_speeds, uint32_t fan_value) {
   if (n_speeds == 0 || n_speeds > SP_MAX_SPEEDS)
     SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: n_speeds must be in [1, %u], got %u", who, SP_MAX_SPEEDS, n_speeds);
@@ -281,15 +281,6 @@ int32_t sp_check_ladder(shz_ctx* ctx, const char* who, const uint32_t* speed_q16
       SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: speed %u is %u; factors are Q16 in [%u, %u] (0.5x .. 2x)", who, v, speed_q16[v], SP_S_MIN,
                SP_S_MAX);
   if (fan_value < 1 || fan_value > 64) SHZ_FAIL(ctx, SHZ_E_INVALID, "fan_value must be in [1,64]");
-  return SHZ_OK;
-}
-static int32_t sp_check_queries(shz_ctx* ctx, const uint32_t* query_clip0, uint32_t n_queries, uint32_t n_clips) {
-  if (!query_clip0) SHZ_FAIL(ctx, SHZ_E_INVALID, "query_clip0 is NULL");
-  if (query_clip0[0] != 0 || query_clip0[n_queries] != n_clips)
-    SHZ_FAIL(ctx, SHZ_E_INVALID, "query_clip0 must start at 0 and end at n_clips = %u (it runs from %u to %u)", n_clips,
-             query_clip0[0], query_clip0[n_queries]);
-  for (uint32_t q = 0; q < n_queries; ++q)
-    if (query_clip0[q + 1] < query_clip0[q]) SHZ_FAIL(ctx, SHZ_E_INVALID, "query_clip0 decreases at query %u", q);
   return SHZ_OK;
 }
 
@@ -328,7 +319,7 @@ extern "C" int32_t shz_warp_pair_hash(shz_ctx* ctx, const uint16_t* peak_f, cons
     query_clip0 = own.data();
     n_queries = n_clips;
   }
-  SHZ_TRY(sp_check_queries(ctx, query_clip0, n_queries, n_clips));
+  SHZ_TRY(shz_check_clip0(ctx, "query_clip0", "query", query_clip0, n_queries, n_clips));
   const uint64_t n = peak_off[n_clips] - peak_off[0];
   if (n && (!peak_f || !peak_t)) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_warp_pair_hash: NULL buffer");
   if (cap && (!key32 || !t1)) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_warp_pair_hash: NULL buffer");
@@ -439,10 +430,8 @@ extern "C" int32_t shz_recognize_speeds(shz_ctx* ctx, shz_table* t, const int16_
     if (n_clips) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_recognize_speeds: %u clips belong to no query", n_clips);
     return SHZ_OK;
   }
-  SHZ_TRY(sp_check_queries(ctx, query_clip0, n_queries, n_clips));
-  if (!clip_off) SHZ_FAIL(ctx, SHZ_E_INVALID, "clip_off is NULL");
-  for (uint32_t c = 0; c < n_clips; ++c)
-    if (clip_off[c + 1] < clip_off[c]) SHZ_FAIL(ctx, SHZ_E_INVALID, "clip_off decreases at clip %u", c);
+  SHZ_TRY(shz_check_clip0(ctx, "query_clip0", "query", query_clip0, n_queries, n_clips));
+  SHZ_TRY(shz_check_clip_off(ctx, clip_off, n_clips));
   if (fs == 0) SHZ_FAIL(ctx, SHZ_E_INVALID, "Fs must be > 0");
   if (n_clips && !pcm && clip_off[n_clips] > clip_off[0]) SHZ_FAIL(ctx, SHZ_E_INVALID, "pcm is NULL");
   if (!out_best || !out_sid || !out_delta || !out_aligned || !out_dedup || !out_nres) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_recognize_speeds: NULL buffer");

@@ -91,6 +91,23 @@ def scan_windows(recordings, db, Fs: int = 44100, window_seconds: float = 5, ste
     return res
 
 
+def _segment(db, w, seg, i):
+    """What a segment of either timeline says: the song, the span of its windows in the recording (the last window's end
+    clipped to the recording's), how many of them named the song and their best aligned count."""
+    from . import SONG_ID, SONG_NAME
+    r, first, last = int(seg["rec"][i]), int(seg["first"][i]), int(seg["last"][i])
+    hop, fs, sf, wf = w["hop"], w["fs"], w["step_frames"], w["window_frames"]
+    end_frame = min(last * sf + wf, int(w["frames"][r]))
+    return {
+        SONG_ID: int(seg["sid"][i]),
+        SONG_NAME: db.get_song_by_id(int(seg["sid"][i])).get(SONG_NAME, None).encode("utf8"),
+        "start_seconds": round(first * sf * hop / fs, 5),
+        "end_seconds": round(end_frame * hop / fs, 5),
+        "windows": int(seg["hits"][i]),
+        "hashes_aligned": int(seg["best"][i]),
+    }
+
+
 def scan(recordings, db, Fs: int = 44100, window_seconds: float = 5, step_seconds: float = 1, topn: int = TOPN,
          resample_to: int = None, min_aligned: int = 20, max_gap: int = 1, speeds=None, shift_tol: int = 2, rung_tol: int = 1):
     """The timeline of every recording: a list (per recording) of segments, each a dict with song_id, song_name,
@@ -107,50 +124,34 @@ def scan(recordings, db, Fs: int = 44100, window_seconds: float = 5, step_second
     rung its hits chose most often, as a float), "speed_fit" ((pos_last - pos_first) / ((last - first) * step_frames), None
     for a one-hit segment), "offset_seconds" / "offset_end_seconds" (the song position at the start of its first / last hit
     window, in the TABLE's seconds) and "pos_first" / "pos_last" (the same in the table's frames)."""
-    from . import OFFSET_SECS, SONG_ID, SONG_NAME
+    from . import OFFSET_SECS
     if speeds is not None:
         return _scan_speeds(recordings, db, Fs, window_seconds, step_seconds, topn, resample_to, min_aligned, max_gap, speeds,
                             shift_tol, rung_tol)
     w = scan_windows(recordings, db, Fs, window_seconds, step_seconds, topn, resample_to)
     seg = _ffi.scan_timeline(w["win_off"], w["sid"], w["delta"], w["aligned"], w["nres"], w["step_frames"], min_aligned, max_gap)
-    hop, fs, sf, wf = w["hop"], w["fs"], w["step_frames"], w["window_frames"]
     out = [[] for _ in range(len(w["frames"]))]
     for i in range(len(seg["rec"])):
-        r, first, last, shift = int(seg["rec"][i]), int(seg["first"][i]), int(seg["last"][i]), int(seg["shift"][i])
-        song = db.get_song_by_id(int(seg["sid"][i]))
-        end_frame = min(last * sf + wf, int(w["frames"][r]))
-        out[r].append({
-            SONG_ID: int(seg["sid"][i]),
-            SONG_NAME: song.get(SONG_NAME, None).encode("utf8"),
-            "start_seconds": round(first * sf * hop / fs, 5),
-            "end_seconds": round(end_frame * hop / fs, 5),
-            OFFSET_SECS: round(float(shift + first * sf) / DEFAULT_FS * hop, 5),
-            "shift": shift,
-            "windows": int(seg["hits"][i]),
-            "hashes_aligned": int(seg["best"][i]),
-        })
+        first, shift = int(seg["first"][i]), int(seg["shift"][i])
+        out[int(seg["rec"][i])].append(dict(
+            _segment(db, w, seg, i),
+            **{OFFSET_SECS: round(float(shift + first * w["step_frames"]) / DEFAULT_FS * w["hop"], 5), "shift": shift}))
     return out
 
 
 def _scan_speeds(recordings, db, Fs, window_seconds, step_seconds, topn, resample_to, min_aligned, max_gap, speeds, shift_tol,
                  rung_tol):
-    from . import OFFSET_SECS, SONG_ID, SONG_NAME
+    from . import OFFSET_SECS
     w = scan_windows(recordings, db, Fs, window_seconds, step_seconds, topn, resample_to, speeds=speeds)
     sp = w["speeds"]
     seg = _ffi.scan_timeline_speeds(w["win_off"], w["sid"], w["delta"], w["aligned"], w["nres"], w["best"], w["step_frames"], sp,
                                     min_aligned, max_gap, rung_tol, shift_tol)
-    hop, fs, sf, wf = w["hop"], w["fs"], w["step_frames"], w["window_frames"]
+    hop, sf = w["hop"], w["step_frames"]
     out = [[] for _ in range(len(w["frames"]))]
     for i in range(len(seg["rec"])):
-        r, first, last = int(seg["rec"][i]), int(seg["first"][i]), int(seg["last"][i])
+        first, last = int(seg["first"][i]), int(seg["last"][i])
         p0, p1 = int(seg["pos_first"][i]), int(seg["pos_last"][i])
-        song = db.get_song_by_id(int(seg["sid"][i]))
-        end_frame = min(last * sf + wf, int(w["frames"][r]))
-        out[r].append({
-            SONG_ID: int(seg["sid"][i]),
-            SONG_NAME: song.get(SONG_NAME, None).encode("utf8"),
-            "start_seconds": round(first * sf * hop / fs, 5),
-            "end_seconds": round(end_frame * hop / fs, 5),
+        out[int(seg["rec"][i])].append(dict(_segment(db, w, seg, i), **{
             OFFSET_SECS: round(float(p0) / DEFAULT_FS * hop, 5),
             "offset_end_seconds": round(float(p1) / DEFAULT_FS * hop, 5),
             "pos_first": p0,
@@ -159,7 +160,5 @@ def _scan_speeds(recordings, db, Fs, window_seconds, step_seconds, topn, resampl
             "last_window": last,
             "speed": float(sp[int(seg["rung"][i])]) / 65536.0,
             "speed_fit": (p1 - p0) / float((last - first) * sf) if last > first else None,
-            "windows": int(seg["hits"][i]),
-            "hashes_aligned": int(seg["best"][i]),
-        })
+        }))
     return out

@@ -220,6 +220,35 @@ def test_thirty_frames_window_one_and_step_above_window(S, ctx, db, songs):
     _check(S, db, [clip], 29, 1, what="two windows")
 
 
+def test_step_that_puts_a_window_beyond_every_t1(S, ctx, db, songs):
+    """Step 2^32 - 1: the second window starts above every t1.  Its start is not clamped to 32 bits anywhere; the device's
+    searches compare in 64 bits, so it is empty, and the first window is what it is at any step."""
+    clip = songs[3][2 * SR:2 * SR + 4096 + 29 * 2048]
+    near, _ = _check(S, db, [clip], 4, 1, what="window 4 step 1")
+    got, win_off = _check(S, db, [clip], 4, (1 << 32) - 1, what="step 2^32 - 1")
+    assert win_off.tolist() == [0, 2]
+    assert int(got["nhash"][1]) == 0 and int(got["nres"][1]) == 0
+    assert int(got["nhash"][0]) > 0
+    for name in ARRAYS:
+        assert np.array_equal(got[name][0], near[name][0]), name
+
+
+def test_recordings_without_windows_front_middle_and_end(S, ctx, db, songs):
+    """Recordings without windows share their start with the next one in the stage's descriptors: the search for "the last
+    recording whose first item is <= i" must step over them, one or two at a time, in front, in the middle and at the end."""
+    from shazam_amd import _ffi
+    a, b = songs[3][2 * SR:2 * SR + 4096 + 29 * 2048], songs[1][3 * SR:3 * SR + 4096 + 29 * 2048]
+    recs = [[], a, [], [], [b, b[:20000]], []]
+    for debug in (0, _ffi.DEBUG_SCAN_SMALL_GROUPS):
+        ctx.set_debug(debug)
+        try:
+            got, win_off = _check(S, db, recs, 4, 9, what=("empty recordings", debug))
+        finally:
+            ctx.set_debug(0)
+        assert win_off.tolist() == [0, 0, 4, 4, 4, 8, 8]
+        assert got["nhash"][:4].any() and got["nhash"][4:].any()
+
+
 def test_window_of_the_whole_recording_is_the_fused_call(S, ctx, db, mixed_batch):
     chans, pcm, off, first = _flatten(S, mixed_batch)
     frames = max(ctx.frames_of(len(c)) for c in chans)

@@ -223,6 +223,34 @@ def test_thirty_frames_window_one_and_step_above_window(S, ctx, db, songs):
     _check(S, d, [clip], 4, 9, THREE, what="step > window")
 
 
+def test_step_that_puts_a_window_beyond_every_t1(S, ctx, db, songs):
+    """Step 2^32 - 1: the second window starts above every t1' at every rung and is empty (test_gpu_scan.py has the reason)."""
+    d, _ = db
+    clip = songs[3][2 * SR:2 * SR + 4096 + 29 * 2048]
+    near, _ = _check(S, d, [clip], 4, 1, THREE, what="window 4 step 1")
+    got, win_off = _check(S, d, [clip], 4, (1 << 32) - 1, THREE, what="step 2^32 - 1")
+    assert win_off.tolist() == [0, 2]
+    assert int(got["nhash"][1]) == 0 and int(got["nres"][1]) == 0 and not got["profile"][1].any()
+    for name in ARRAYS + ("best", "profile"):
+        assert np.array_equal(got[name][0], near[name][0]), name
+
+
+def test_recordings_without_windows_front_middle_and_end(S, ctx, db, songs):
+    """The descriptor search steps over recordings without windows, here with slices of one recording too (test_gpu_scan.py)."""
+    from shazam_amd import _ffi
+    d, _ = db
+    a, b = songs[3][2 * SR:2 * SR + 4096 + 29 * 2048], songs[1][3 * SR:3 * SR + 4096 + 29 * 2048]
+    recs = [[], a, [], [], [b, b[:20000]], []]
+    for debug in (0, _ffi.DEBUG_SCAN_SPEED_SMALL_SLICES):
+        ctx.set_debug(debug)
+        try:
+            got, win_off = _check(S, d, recs, 4, 9, THREE, what=("empty recordings", debug))
+        finally:
+            ctx.set_debug(0)
+        assert win_off.tolist() == [0, 0, 4, 4, 4, 8, 8]
+        assert got["nhash"][:4].any() and got["nhash"][4:].any()
+
+
 # ---- slicing ----------------------------------------------------------------------------------------------------------
 def test_small_slices_and_device_pcm_give_the_same_arrays(S, ctx, db, recording, mixed_batch):
     from shazam_amd import _ffi
