@@ -216,10 +216,12 @@ __device__ __forceinline__ void dft8f_win(const int (&pw)[8], const double2 (&ww
 
 // PCM of frame `g` (sub-batch numbering) of clip `lo` as 8 packed sample pairs per thread
 // (lo16 = x[2n], hi16 = x[2n+1], n = j + 256 t)
-__device__ __forceinline__ void stft_load_frame(const stft_args& a, uint32_t lo, uint32_t g, int j, int (&pw)[8]) {
-  const uint64_t clen = a.clip_len[lo];
-  const uint64_t s_in_clip = (uint64_t)(g - a.clip_foff[lo]) * a.hop;
-  const int16_t* src = a.pcm + a.clip_soff[lo] + s_in_clip;
+// The clip's table entries are passed in: frame `g` of the clip whose frame 0 is `f0` (sub-batch numbering), whose `clen`
+// samples start at pcm[soff].  A caller that walks consecutive frames keeps them in scalar registers (stft_psd_kernel).
+__device__ __forceinline__ void stft_load_frame_at(const int16_t* pcm, uint64_t soff, uint64_t clen, uint32_t f0, uint32_t hop,
+                                                   uint32_t g, int j, int (&pw)[8]) {
+  const uint64_t s_in_clip = (uint64_t)(g - f0) * hop;
+  const int16_t* src = pcm + soff + s_in_clip;
   const uint64_t avail = clen > s_in_clip ? clen - s_in_clip : 0;  // samples readable from src
   if (avail >= SHZ_NFFT && (((uintptr_t)src) & 3) == 0) {
 #pragma unroll
@@ -242,6 +244,17 @@ __device__ __forceinline__ void stft_load_frame(const stft_args& a, uint32_t lo,
       pw[t] = (x0 & 0xFFFF) | (x1 << 16);
     }
   }
+}
+__device__ __forceinline__ void stft_load_frame(const stft_args& a, uint32_t lo, uint32_t g, int j, int (&pw)[8]) {
+  stft_load_frame_at(a.pcm, a.clip_soff[lo], a.clip_len[lo], a.clip_foff[lo], a.hop, g, j, pw);
+}
+
+// Load of a wave-uniform table entry through the scalar cache (s_load): the constant address space says what the compiler
+// cannot prove of a kernel that also stores -- that nothing in the launch writes the table.  Only for tables that are
+// complete before the launch (the scalar cache is invalidated when a kernel starts, not while it runs).
+template <typename T>
+__device__ __forceinline__ T ld_uniform(const T* p) {
+  return *(const __attribute__((address_space(4))) T*)p;
 }
 
 // One frame: windowed samples v[8] (complex point j + 256 t = samples 2n, 2n+1) -> power of the 2049 bins.
@@ -581,22 +594,33 @@ __global__ __launch_bounds__(256, STFT_OCC) void stft_psd_kernel(stft_args a) {
   // The loads of frame g + gridDim are issued BEFORE frame g's output stores: vmcnt retires in
   // order, so loads issued behind the stores would wait for the stores' HBM acknowledgements.
   int pw[8];
-  uint32_t clip = 0xFFFFFFFFu;  // clip of the frame loaded last: a workgroup's frames ascend, so the next one is near
+  // The clip of the frame loaded last, wave-uniform and in scalar registers: its index, its frames [c_f0, c_f1), its length
+  // and its first sample.  A workgroup's frames ascend, so a frame's clip is found by ONE scalar compare against c_f1; the
+  // tables are read (s_load, ld_uniform) only for the workgroup's first frame and where a frame crosses into a later clip,
+  // and no memory access stands in front of the PCM loads of any other frame.  (Read per frame -- as vector loads, each
+  // behind a vmcnt(0) that also waited for the previous frame's row stores -- they were three round trips in a chain at
+  // the head of every frame: DESIGN.md 3.1.)
+  uint32_t clip = 0, c_f0 = 0, c_f1 = 0;  // c_f1 = 0: no clip yet
+  uint64_t c_len = 0, c_soff = 0;
   auto issue_loads = [&](uint32_t g) {
-    uint32_t lo;
-    if (clip == 0xFFFFFFFFu) {  // first frame: uniform binary search over the frame offsets
-      lo = 0;
-      uint32_t hi = a.n_clips;
-      while (hi - lo > 1) {
-        uint32_t mid = (lo + hi) >> 1;
-        if (a.clip_foff[mid] <= g) lo = mid; else hi = mid;
+    if (g >= c_f1) {
+      uint32_t lo = clip;
+      if (c_f1 == 0) {  // first frame: uniform binary search over the frame offsets
+        uint32_t hi = a.n_clips;
+        while (hi - lo > 1) {
+          uint32_t mid = (lo + hi) >> 1;
+          if (ld_uniform(a.clip_foff + mid) <= g) lo = mid; else hi = mid;
+        }
+      } else {          // a later clip: walk on from the last one
+        while (lo + 1 < a.n_clips && ld_uniform(a.clip_foff + lo + 1) <= g) ++lo;
       }
-    } else {                    // later frames: walk on from the last clip (one or two scalar loads, not ten in a chain)
-      lo = clip;
-      while (lo + 1 < a.n_clips && a.clip_foff[lo + 1] <= g) ++lo;
+      clip = lo;
+      c_f0 = ld_uniform(a.clip_foff + lo);
+      c_f1 = ld_uniform(a.clip_foff + lo + 1);
+      c_len = ld_uniform(a.clip_len + lo);
+      c_soff = ld_uniform(a.clip_soff + lo);
     }
-    clip = lo;
-    stft_load_frame(a, lo, g, j, pw);
+    stft_load_frame_at(a.pcm, c_soff, c_len, c_f0, a.hop, g, j, pw);
   };
   // XCD-aware frame map: workgroups b, b+8, b+16, ... share an XCD (round-robin dispatch), so each
   // group of gridDim/8 workgroups walks ONE contiguous eighth of the frames and the 50 % overlap of
@@ -1294,6 +1318,8 @@ extern "C" uint32_t shz_frame_count(uint64_t n) {
 #define PK_SEG 252       // output frames per peak_pick workgroup (12 blocks of 21) when workgroups are scarce
 #define PK_SEG_LONG 672  // ... and when the batch is large: 32 blocks, a 30 s clip in one piece (no time halo)
 #define PK_SEG_SHORT 42  // ... and when a handful of workgroups is all there is: 2 blocks
+static_assert((uint64_t)(PK_SEG_LONG + 20) * P32_STRIDE * sizeof(float) < (1ull << 31),
+              "peak_pick32_kernel adds a row's distance from its segment's first row to a lane's 32-bit byte offset");
 
 static const mask_geom MG_F64 = {(SHZ_NBINS + PK_SW - 1) / PK_SW, 4, 63, PK_SW};
 // waves per peak_pick32 workgroup (slab = 61 nw - 17 bins).  Measured on 644,000 frames: 7 waves (5 slabs) 3.93 ms,

@@ -16,6 +16,8 @@
 // XF_FALLBACK (more undecided cells than the list holds) still sends the whole pass to fp64 staging.
 
 #define P32_PF 7  // frames per barrier group (3 groups = one van Herk block of 21)
+// predicate codes of the compare builtins that return the lane mask (__builtin_amdgcn_uicmp / sicmp / fcmpf)
+enum { P32_OGE = 3, P32_UGE = 35, P32_SGE = 39 };
 
 enum : uint32_t {
   XF_FALLBACK = 1u,   // fp32 staging cannot decide this input cheaply: rerun with fp64 staging
@@ -72,9 +74,13 @@ struct p32_args {
 // finds a lane whose centre is within one step of its window maximum -- one wave-row in eight -- can work out there and
 // then whether that lane is alone (second-largest row maximum of the window, 20 max) or has to be listed.
 // The mask buffer is zeroed by the host; only non-zero words are written.
-// The loads of the next group of P32_PF rows are in flight while a group is worked on.  Two groups ahead (14 rows in
-// flight per lane) was measured in round 4 on 644,000 frames: 2.13 ms -> 2.38 at 4 waves per SIMD (the 7 extra registers
-// spill) and 2.41 at 3 -- the kernel is bound by instruction issue, not by loads in flight.
+// The loads of the next group of P32_PF rows are in flight while a group is worked on: every group issues exactly P32_PF
+// loads, without a branch (a row past the segment's last is a re-read of the last, a column outside the spectrum a re-read
+// of column 0; the value is replaced by -inf where the group is CONSUMED), so the wait in front of a group's rows is
+// vmcnt(P32_PF), the loads just issued staying in flight.  (With each load behind its own `if (tn < hi)` the count was
+// unknown to the compiler and the wait was vmcnt(0) right behind the loads in two groups of three: DESIGN.md 3.2.)
+// Two groups ahead (14 rows in flight per lane) was measured in round 4 on 644,000 frames, with those vmcnt(0) waits:
+// 2.13 ms -> 2.38 at 4 waves per SIMD (the 7 extra registers spill) and 2.41 at 3.
 template <int NW, int OCC>
 __global__ __launch_bounds__(64 * NW, OCC) void peak_pick32_kernel(p32_args a) {
   constexpr int TH = 64 * NW, SW = 61 * NW - 17;
@@ -98,10 +104,11 @@ __global__ __launch_bounds__(64 * NW, OCC) void peak_pick32_kernel(p32_args a) {
   const bool loads = col >= 0 && col < SHZ_NBINS;
   const bool owns = lane < 61 && li >= 10 && li <= 61 * NW - 8;  // output column li (window = LDS columns li-10 .. li+10)
   const bool is_out = owns && col < SHZ_NBINS;
+  const uint64_t out_m = __builtin_amdgcn_ballot_w64(is_out);     // the wave's output lanes as a scalar mask
   const int lo = (int)sg.t0 - 10 > 0 ? (int)sg.t0 - 10 : 0;
   const int hi = (int)(sg.t1 + 10 < sg.nframes ? sg.t1 + 10 : sg.nframes);
   const int end = (int)sg.t1 + 10;  // last iteration decides frame t1-1
-  const uint32_t coff = loads ? (uint32_t)col : 0u;
+  const uint32_t boff = loads ? (uint32_t)col * 4u : 0u;         // byte offset in a row (a lane outside the spectrum: column 0)
   const float* base = a.A + (uint64_t)sg.gframe0 * P32_STRIDE;   // uniform; rows are added as uniform offsets
   const int o = owns ? li - 10 : 0;                              // other lanes read columns 0..17: valid, ignored
   const int wcol = lane < 61 ? li : TH + lane;                   // where this lane stores its row values
@@ -111,14 +118,20 @@ __global__ __launch_bounds__(64 * NW, OCC) void peak_pick32_kernel(p32_args a) {
   float R1 = NEG;
 #pragma unroll
   for (int u = 0; u < 21; ++u) { S1[u] = NEG; prev[u] = NEG; cur[u] = NEG; }
-  // (Round 4 tried to take the address arithmetic out of the rows -- one uniform row pointer advanced row by row, the rows'
-  // existence asked once per group, lanes outside the spectrum loading a clamped column and dropping the value -- 10 of the
-  // ~50 instructions of a row by the listing: 2.14 -> 2.22 ms on the same box.  The masked loads below stay.)
+  // row t of the segment's clip, clamped to the last row that exists (hi > lo >= 0): the segment's first row as the uniform
+  // base, and one 32-bit offset per lane = the lane's byte offset in a row + the row's distance from that base (a segment
+  // and its halo: at most PK_SEG_LONG + 20 rows of 8,256 bytes, asserted where the segments are cut).  The load is the
+  // scalar-base form, global_load_dword v, v_off, s[base]; a row costs min, subtract, multiply (scalar) and one 32-bit add
+  // (the compiler's own address was a 64-bit multiply-add per row and lane)
+  typedef __attribute__((address_space(1))) const char gchar;
+  typedef __attribute__((address_space(1))) const float gfloat;
+  gchar* const row0 = (gchar*)(base + (uint64_t)(uint32_t)lo * P32_STRIDE);
+  auto row_load = [&](int t) {
+    const uint32_t roff = (uint32_t)(min(t, hi - 1) - lo) * (uint32_t)(P32_STRIDE * sizeof(float));
+    return *(gfloat*)(row0 + (boff + roff));
+  };
 #pragma unroll
-  for (int p = 0; p < P32_PF; ++p) {
-    const int t = lo + p;
-    pre[p] = (loads && t < hi) ? (base + (uint64_t)t * P32_STRIDE)[coff] : NEG;
-  }
+  for (int p = 0; p < P32_PF; ++p) pre[p] = row_load(lo + p);
   for (int tb = lo; tb < end; tb += 21) {
     // which of the block's 21 centre frames tb - 10 + u lie inside the segment: one scalar word per block, one bit test per
     // row (the two compares and the mask logic per row were a third of the scalar instructions of this loop)
@@ -127,15 +140,17 @@ __global__ __launch_bounds__(64 * NW, OCC) void peak_pick32_kernel(p32_args a) {
 #pragma unroll
     for (int g3 = 0; g3 < 21 / P32_PF; ++g3) {
       float v[P32_PF], mx[P32_PF];
+      // the frames one group ahead: exactly P32_PF loads, no branch, nothing done with the values in this group
+      float nxt[P32_PF];
 #pragma unroll
-      for (int i = 0; i < P32_PF; ++i) v[i] = pre[i];
+      for (int i = 0; i < P32_PF; ++i) nxt[i] = row_load(tb + P32_PF * (g3 + 1) + i);
+      __builtin_amdgcn_sched_barrier(0);  // issued BEFORE the wait for this group's rows: that wait is then vmcnt(P32_PF)
+      // the group's rows as loaded one group ago; what does not exist (row past the segment, column outside the spectrum)
+      // becomes -inf here, where the value is first needed, by one select on a lane mask made of scalars
 #pragma unroll
       for (int i = 0; i < P32_PF; ++i) {
-        const int tn = tb + P32_PF * (g3 + 1) + i;  // the frame one group ahead: keeps P32_PF rows in flight
-        // every lane loads (a lane outside the spectrum: column 0, dropped by a select) behind ONE uniform test
-        float x = NEG;
-        if (tn < hi) x = (base + (uint64_t)tn * P32_STRIDE)[coff];
-        pre[i] = loads ? x : NEG;
+        v[i] = (loads && tb + P32_PF * g3 + i < hi) ? pre[i] : NEG;
+        pre[i] = nxt[i];
       }
       __syncthreads();  // every wave is done reading the previous group's rows
 #pragma unroll
@@ -173,8 +188,14 @@ __global__ __launch_bounds__(64 * NW, OCC) void peak_pick32_kernel(p32_args a) {
         const uint32_t q = (cw >> (3 * (kc % P32_PF))) & 7u;
         const int tc = t - 10;
         const bool in_seg = (seg_bits >> u) & 1u;
-        const bool hot = in_seg && is_out && q >= 1u && key_near(c1, t1, 1) && t1 >= a.p_lo;
-        if (__ballot(hot)) {  // wave-uniform: some lane's centre is within one step of its window maximum
+        // hot <=> in_seg && is_out && q >= 1 && key_near(c1, t1, 1) && t1 >= p_lo, kept as the lane MASK the compares
+        // deliver (a ballot of a bool made of several compares goes through a 0/1 register and a compare with zero)
+        const int kt1 = __float_as_int(t1);
+        const uint64_t hot = !in_seg ? 0ull
+                                     : out_m & __builtin_amdgcn_uicmp(q, 1u, P32_UGE) &
+                                           __builtin_amdgcn_sicmp(__float_as_int(c1), kt1 - 1, P32_SGE) &
+                                           __builtin_amdgcn_fcmpf(t1, a.p_lo, P32_OGE);
+        if (hot) {  // wave-uniform: some lane's centre is within one step of its window maximum
           float t2 = NEG;     // largest row maximum of the window's other rows
 #pragma unroll
           for (int k = 0; k < 21; ++k) {
@@ -184,9 +205,10 @@ __global__ __launch_bounds__(64 * NW, OCC) void peak_pick32_kernel(p32_args a) {
           }
           const bool exact = q >= 2u && c1 == t1;
           const bool uniq = q == 5u && !key_near(t2, t1, 2);
-          const bool pk = hot && exact && uniq && t1 > a.p_hi;
-          const bool und = hot && !pk;
-          const unsigned long long bal = __ballot(pk);
+          const bool hot_l = (hot >> lane) & 1ull;
+          const bool pk = hot_l && exact && uniq && t1 > a.p_hi;
+          const bool und = hot_l && !pk;
+          const unsigned long long bal = __builtin_amdgcn_ballot_w64(pk);
           if (bal && lane == 0) {
             a.mask[((uint64_t)(sg.gframe0 + tc) * a.n_slabs + slab) * NW + wave] = bal;
             atomicAdd(&a.frame_cnt[sg.gframe0 + tc], (uint32_t)__popcll(bal));
