@@ -709,6 +709,35 @@ int32_t shz_recognize_speeds(shz_ctx* ctx, shz_table* table, const int16_t* pcm,
                              uint32_t* out_nres, uint32_t* out_nhash, uint32_t* out_profile, float* ms_extract, float* ms_warp,
                              float* ms_match);
 
+/* ---- two warp factors (new): a time-stretch that keeps the pitch (a DJ deck with key-lock), a pitch shift that keeps the
+ * tempo, or both by different amounts move a query's peaks to (f p, t / a) with a tempo factor a and a pitch factor p of their
+ * own, which no rung of a speed ladder describes.  A WARP is a pair of Q16 factors (t16, f16), each in [32768, 131072]: the
+ * query runs t16 / 65536 times as fast and sounds f16 / 65536 times as high as the table's copy.  The maps are the ones
+ * above, each with its own factor:
+ *     t' = (t t16 + 32768) >> 16        f' = (2 65536 f + f16) / (2 f16)
+ * peaks with f' > 2048 leave, the kept peaks of one (clip, warp) are ordered by (t', f', original index) and paired as
+ * above.  Warp v is (tempo_q16[v], pitch_q16[v]); a speed s16 is the warp (s16, s16).  Numpy twin: tests/warp_twin.py.
+ *
+ * shz_warp_pair_hash_tf: the contract and the output order of shz_warp_pair_hash with "speed v" read as "warp v" (hash_off:
+ * n_clips n_warps + 1 entries).  SHZ_E_INVALID before anything is launched: n_warps of 0 or above 1024, a NULL table, a factor
+ * of either table outside the range (the message names the table and the index).  shz_warp_pair_hash(speed_q16) is this call
+ * with the one table given twice. */
+int32_t shz_warp_pair_hash_tf(shz_ctx* ctx, const uint16_t* peak_f, const uint32_t* peak_t, const uint64_t* peak_off,
+                              uint32_t n_clips, const uint32_t* query_clip0, uint32_t n_queries, const uint32_t* tempo_q16,
+                              const uint32_t* pitch_q16, uint32_t n_warps, uint32_t fan_value, uint32_t flags, uint32_t* key32,
+                              uint32_t* t1, uint64_t* hash_off, uint64_t cap, uint64_t* count);
+/* shz_recognize_speeds over warps: the same stages, outputs (out_best: index into the warps; out_profile [n_queries n_warps])
+ * and refusals.  The BEST variant is the one with the greatest rank-0 aligned count; ties go to the smaller
+ * |t16 - 65536| + |f16 - 65536|, then to the lower index (on a diagonal list: the rule of shz_recognize_speeds).  The bias
+ * bound of the match and the t' < 2^20 refusal use the largest t16.  shz_recognize_speeds(speed_q16) is this call with the one
+ * table given twice. */
+int32_t shz_recognize_warps(shz_ctx* ctx, shz_table* table, const int16_t* pcm, const uint64_t* clip_off, uint32_t n_clips,
+                            const uint32_t* query_clip0, uint32_t n_queries, uint32_t fs, double amp_min, uint32_t fan_value,
+                            uint32_t topn, const uint32_t* tempo_q16, const uint32_t* pitch_q16, uint32_t n_warps, uint32_t flags,
+                            uint32_t* out_best, uint32_t* out_sid, int32_t* out_delta, uint32_t* out_aligned, uint32_t* out_dedup,
+                            uint32_t* out_nres, uint32_t* out_nhash, uint32_t* out_profile, float* ms_extract, float* ms_warp,
+                            float* ms_match);
+
 /* ---- scanning at an unknown speed (new; shz_scan_batch and shz_recognize_speeds joined: "which songs play in this hour of
  * broadcast, and when?" where the station pitches its songs up or down) --------------------------------------------------
  * shz_scan_speeds: the arguments of shz_scan_batch plus a ladder (speed_q16 / n_speeds, checked as shz_recognize_speeds

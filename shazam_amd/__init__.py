@@ -350,4 +350,5 @@ from .resample import StreamResampler, resample_batch, resample_plan, resample_t
 # long recordings (csrc/shz_scan.hip): every window of a recording matched in one call, and the timeline of its songs
 from .scan import scan, scan_windows  # noqa: E402,F401
 # queries played fast or slow (csrc/shz_speed.hip): the peaks warped for every factor of a ladder, all variants in one match
-from .speed import recognize_speeds, speed_ladder, warp_hashes  # noqa: E402,F401
+from .speed import (pitch_ladder, recognize_speeds, recognize_warps, speed_ladder, tempo_ladder, warp_grid,  # noqa: E402,F401
+                    warp_hashes, warp_hashes_tf)

@@ -155,6 +155,11 @@ SIGNATURES = {
     "shz_recognize_speeds": (C.c_int32, [vp, vp, vp, u64p, C.c_uint32, u32p, C.c_uint32, C.c_uint32, C.c_double, C.c_uint32,
                                          C.c_uint32, u32p, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp,
                                          C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "shz_warp_pair_hash_tf": (C.c_int32, [vp, vp, vp, u64p, C.c_uint32, u32p, C.c_uint32, u32p, u32p, C.c_uint32, C.c_uint32,
+                                          C.c_uint32, vp, vp, u64p, C.c_uint64, u64p]),
+    "shz_recognize_warps": (C.c_int32, [vp, vp, vp, u64p, C.c_uint32, u32p, C.c_uint32, C.c_uint32, C.c_double, C.c_uint32,
+                                        C.c_uint32, u32p, u32p, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp,
+                                        C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "shz_scan_speeds": (C.c_int32, [vp, vp, vp, u64p, C.c_uint32, u32p, C.c_uint32, C.c_uint32, C.c_double, C.c_uint32,
                                     C.c_uint32, C.c_uint32, C.c_uint32, u32p, C.c_uint32, C.c_uint32, u64p, vp, vp, vp, vp, vp, vp,
                                     vp, vp, vp, C.c_uint64, u64p, C.POINTER(C.c_float), C.POINTER(C.c_float),
@@ -738,6 +743,65 @@ class Context:
                                               ptr(res["best"]), ptr(res["sid"]), ptr(res["delta"]), ptr(res["aligned"]),
                                               ptr(res["dedup"]), ptr(res["nres"]), ptr(res["nhash"]), ptr(res["profile"]),
                                               *[C.byref(m) for m in ms]))
+        return res, tuple(float(m.value) for m in ms)
+
+    def warp_pair_hash_tf_raw(self, peak_f, peak_t, peak_off, tempos, pitches, query_clip0=None, fan_value=5, cap=0,
+                              device_in=False, out_key: DevBuf = None, out_t1: DevBuf = None):
+        """One shz_warp_pair_hash_tf as it is: (rc, key32, t1, hash_off, count) without retrying; warp v is (tempos[v],
+        pitches[v]), Q16.  Buffers as for warp_pair_hash_raw."""
+        po = np.ascontiguousarray(peak_off, np.uint64)
+        tq, fq = np.ascontiguousarray(tempos, np.uint32), np.ascontiguousarray(pitches, np.uint32)
+        if tq.shape != fq.shape or tq.ndim != 1:
+            raise ValueError("tempos and pitches are two lists of one length: warp v is (tempos[v], pitches[v])")
+        nc = len(po) - 1
+        qc = None if query_clip0 is None else np.ascontiguousarray(query_clip0, np.uint32)
+        if not device_in:
+            peak_f, peak_t = np.ascontiguousarray(peak_f, np.uint16), np.ascontiguousarray(peak_t, np.uint32)
+        ho, cnt = np.zeros(nc * len(tq) + 1, np.uint64), C.c_uint64()
+        flags = (IN_DEVICE if device_in else 0) | (OUT_DEVICE if out_key is not None else 0)
+        k = t1 = None
+        if out_key is None:
+            k, t1 = np.empty(max(int(cap), 1), np.uint32), np.empty(max(int(cap), 1), np.uint32)
+        rc = lib().shz_warp_pair_hash_tf(self.h, ptr(peak_f), ptr(peak_t), po.ctypes.data_as(u64p), nc,
+                                         None if qc is None else qc.ctypes.data_as(u32p), 0 if qc is None else len(qc) - 1,
+                                         tq.ctypes.data_as(u32p), fq.ctypes.data_as(u32p), len(tq), int(fan_value), flags,
+                                         ptr(out_key if out_key is not None else k), ptr(out_t1 if out_key is not None else t1),
+                                         ho.ctypes.data_as(u64p), int(cap), C.byref(cnt))
+        n = int(cnt.value)
+        if k is not None:
+            k, t1 = k[:min(n, int(cap))], t1[:min(n, int(cap))]
+        return rc, k, t1, ho, n
+
+    def warp_pair_hash_tf(self, peak_f, peak_t, peak_off, tempos, pitches, query_clip0=None, fan_value=5):
+        """shz_warp_pair_hash_tf (two calls: count, then write): (key32, t1, hash_off) in the order query, warp, clip."""
+        rc, k, t1, ho, n = self.warp_pair_hash_tf_raw(peak_f, peak_t, peak_off, tempos, pitches, query_clip0, fan_value, 0)
+        if rc == E_CAPACITY:
+            rc, k, t1, ho, n = self.warp_pair_hash_tf_raw(peak_f, peak_t, peak_off, tempos, pitches, query_clip0, fan_value, n)
+        self.check(rc)
+        return k[:n], t1[:n], ho
+
+    def recognize_warps(self, table: "Table", pcm, clip_off, query_clip0, tempos, pitches, fs=44100, amp_min=10.0, fan_value=5,
+                        topn=2, pcm_device=False, full_sort=False):
+        """shz_recognize_warps: recognize_speeds with a time and a frequency factor of its own for every variant (warp v is
+        (tempos[v], pitches[v]), Q16).  Returns (res, ms) shaped as recognize_speeds': best [nq] indexes the warps, profile
+        is [nq, n_warps]."""
+        co, nc = self._clip_off(clip_off)
+        qc = np.ascontiguousarray(query_clip0, np.uint32)
+        tq, fq = np.ascontiguousarray(tempos, np.uint32), np.ascontiguousarray(pitches, np.uint32)
+        if tq.shape != fq.shape or tq.ndim != 1:
+            raise ValueError("tempos and pitches are two lists of one length: warp v is (tempos[v], pitches[v])")
+        nq = len(qc) - 1
+        res = _match_result(nq, topn)
+        del res["npairs"]
+        res["best"], res["profile"] = np.zeros(nq, np.uint32), np.zeros((nq, len(tq)), np.uint32)
+        ms = [C.c_float(), C.c_float(), C.c_float()]
+        self.check(lib().shz_recognize_warps(self.h, table.h, ptr(pcm), co.ctypes.data_as(u64p), nc, qc.ctypes.data_as(u32p), nq,
+                                             int(fs), float(amp_min), int(fan_value), int(topn), tq.ctypes.data_as(u32p),
+                                             fq.ctypes.data_as(u32p), len(tq),
+                                             (PCM_DEVICE if pcm_device else 0) | (MATCH_FULL_SORT if full_sort else 0),
+                                             ptr(res["best"]), ptr(res["sid"]), ptr(res["delta"]), ptr(res["aligned"]),
+                                             ptr(res["dedup"]), ptr(res["nres"]), ptr(res["nhash"]), ptr(res["profile"]),
+                                             *[C.byref(m) for m in ms]))
         return res, tuple(float(m.value) for m in ms)
 
     def resample_raw(self, pcm, clip_off, L, M, T, taps, in_base=None, m_first=None, m_end=None, pcm_device=False,

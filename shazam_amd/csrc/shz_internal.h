@@ -86,7 +86,7 @@ enum {
   SHZ_WS_SC_CTL,     // ... first entry | count | offset of every (window, rung, channel), the total behind the offsets
   SHZ_WS_SC_KEY, SHZ_WS_SC_QO,   // ... the windows of one group: key32 and t1 - window start, window-major (rung-minor)
   SHZ_WS_SP_PF, SHZ_WS_SP_PT,    // shz_speed.hip: the peaks of the clips (the extraction's, or a host list staged)
-  SHZ_WS_SP_TAB,     // ... peak_off | speeds of the call
+  SHZ_WS_SP_TAB,     // ... peak_off | time factors | frequency factors of the call
   SHZ_WS_SP_Q,       // ... first item | first clip of every query of a pass
   SHZ_WS_SP_A, SHZ_WS_SP_B,      // ... per (peak, speed) item: keep flags, then partner counts | their scans
   SHZ_WS_SP_WF, SHZ_WS_SP_WT,    // ... the warped, compacted peaks in output order
@@ -254,7 +254,8 @@ struct sp_view {              // what the kernels of one pass read (device point
   const uint64_t* poff;       // n_clips + 1
   const uint64_t* qbase;      // nq + 1: first item of every query of the pass (query q has peaks(q) x K items)
   const uint32_t* clip0;      // nq + 1: first clip of every query of the pass
-  const uint32_t* speed;      // K
+  const uint32_t* tempo;      // K: the time factor of every warp
+  const uint32_t* pitch;      // K: its frequency factor (the same table for a speed ladder)
   uint32_t nq, K, fan;
   uint64_t n_items;
 };
@@ -272,18 +273,25 @@ __host__ __device__ __forceinline__ uint32_t sp_warp_t(uint32_t t, uint32_t s16)
 }
 // items of the queries [q0, q0 + nq) at K speeds (clip0: first clip of every query)
 uint64_t sp_items(const uint64_t* peak_off, const uint32_t* clip0, uint32_t q0, uint32_t nq, uint32_t K);
-// one warp pass over the queries [q0, q0 + nq) at the K factors d_speed[0 .. K): sp_count counts (hash_off: n_seg + 1 entries
-// on the host, relative to the pass, segments in the order query, speed, clip; P->d_hoff the same on the device; the stream
-// is idle on return), sp_write writes (key32, t1) of the pass to device columns of cap entries.  d_poff / d_speed: the call's
-// tables on the device (sp_upload_tables).  A pass without peaks launches nothing and leaves P's pointers unset
+// one warp pass over the queries [q0, q0 + nq) at the K warps (d_tempo[v], d_pitch[v]), v in [0, K): sp_count counts
+// (hash_off: n_seg + 1 entries on the host, relative to the pass, segments in the order query, warp, clip; P->d_hoff the same
+// on the device; the stream is idle on return), sp_write writes (key32, t1) of the pass to device columns of cap entries.
+// d_poff / d_tempo / d_pitch: the call's tables on the device (sp_upload_tables; a speed ladder gives its one table twice).
+// A pass without peaks launches nothing and leaves P's pointers unset
 int32_t sp_count(shz_ctx* ctx, const uint16_t* d_pf, const uint32_t* d_pt, const uint64_t* d_poff, const uint64_t* peak_off,
-                 const uint32_t* clip0, uint32_t q0, uint32_t nq, const uint32_t* d_speed, uint32_t K, uint32_t fan, sp_pass* P,
-                 uint64_t* hash_off);
+                 const uint32_t* clip0, uint32_t q0, uint32_t nq, const uint32_t* d_tempo, const uint32_t* d_pitch, uint32_t K,
+                 uint32_t fan, sp_pass* P, uint64_t* hash_off);
 int32_t sp_write(shz_ctx* ctx, const sp_pass& P, uint32_t* d_key, uint32_t* d_t1, uint64_t cap);
-int32_t sp_check_ladder(shz_ctx* ctx, const char* who, const uint32_t* speed_q16, uint32_t n_speeds, uint32_t fan_value);
-int32_t sp_upload_tables(shz_ctx* ctx, const uint64_t* peak_off, uint32_t n_clips, const uint32_t* speed_q16, uint32_t K,
-                         const uint64_t** d_poff, const uint32_t** d_speed);
-uint32_t sp_best(const uint32_t* top1, const uint32_t* speed_q16, uint32_t K);
+// what every entry point with a ladder refuses about it.  n_name: the count's argument ("n_speeds"); t_name / f_name: what a
+// factor of either table is called ("speed", or "tempo" and "pitch"; the table's argument is <name>_q16).  pitch_q16 ==
+// tempo_q16 is one ladder: it is checked, and named, once
+int32_t sp_check_ladder(shz_ctx* ctx, const char* who, const char* n_name, const char* t_name, const uint32_t* tempo_q16,
+                        const char* f_name, const uint32_t* pitch_q16, uint32_t n, uint32_t fan_value);
+// peak_off | tempo | pitch on the device (one block of the call); pitch_q16 == tempo_q16: one table, *d_pitch = *d_tempo
+int32_t sp_upload_tables(shz_ctx* ctx, const uint64_t* peak_off, uint32_t n_clips, const uint32_t* tempo_q16,
+                         const uint32_t* pitch_q16, uint32_t K, const uint64_t** d_poff, const uint32_t** d_tempo,
+                         const uint32_t** d_pitch);
+uint32_t sp_best(const uint32_t* top1, const uint32_t* tempo_q16, const uint32_t* pitch_q16, uint32_t K);
 // shz_peaks of the clips into SHZ_WS_SP_PF / SHZ_WS_SP_PT (frames: of all clips together; flags: SHZ_PCM_DEVICE)
 int32_t sp_peaks_owned(shz_ctx* ctx, const char* who, const int16_t* pcm, const uint64_t* clip_off, uint32_t n_clips,
                        uint64_t frames, uint32_t fs, double amp_min, uint32_t flags, uint64_t* peak_off, const uint16_t** d_pf,

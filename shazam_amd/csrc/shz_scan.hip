@@ -401,7 +401,7 @@ extern "C" int32_t shz_scan_speeds(shz_ctx* ctx, shz_table* t, const int16_t* pc
   if (count) *count = 0;
   // everything that can be refused is refused before the first launch
   SHZ_TRY(sc_check(ctx, who, flags, win_off, count, window_frames, step_frames));
-  SHZ_TRY(sp_check_ladder(ctx, who, speed_q16, n_speeds, fan_value));
+  SHZ_TRY(sp_check_ladder(ctx, who, "n_speeds", "speed", speed_q16, "speed", speed_q16, n_speeds, fan_value));
   const uint32_t K = n_speeds, s_max = *std::max_element(speed_q16, speed_q16 + K);
   // no window is longer at any rung: W_v(s + window) - W_v(s) <= ceil(window s16 / 65536)
   const uint64_t len_max = ((uint64_t)window_frames * s_max + 65535) >> 16;
@@ -436,8 +436,8 @@ extern "C" int32_t shz_scan_speeds(shz_ctx* ctx, shz_table* t, const int16_t* pc
     if (ms_extract) SHZ_HIP(ctx, hipEventElapsedTime(ms_extract, ctx->sc_ev[0], ctx->sc_ev[1]));
   }
   const uint64_t* d_poff;
-  const uint32_t* d_speed;
-  SHZ_TRY(sp_upload_tables(ctx, peak_off.data(), n_clips, speed_q16, K, &d_poff, &d_speed));
+  const uint32_t *d_speed, *d_same;   // one ladder for time and frequency
+  SHZ_TRY(sp_upload_tables(ctx, peak_off.data(), n_clips, speed_q16, speed_q16, K, &d_poff, &d_speed, &d_same));
   // 2) slices of whole recordings x a chunk of rungs: the entries a slice's warp can yield at most (every peak with all its
   // partners, at every rung of the chunk) stay within the match's pair budget and 1/8 of the workspace limit.  The ladder
   // is cut only where one recording at all rungs is beyond that; one (recording, rung) beyond it is a slice of its own
@@ -472,7 +472,7 @@ extern "C" int32_t shz_scan_speeds(shz_ctx* ctx, shz_table* t, const int16_t* pc
       const uint64_t n_seg = (uint64_t)(rec_clip0[r0 + nr] - rec_clip0[r0]) * kcc;
       ho.assign((size_t)n_seg + 1, 0);
       sp_pass P;
-      SHZ_TRY(sp_count(ctx, d_pf, d_pt, d_poff, peak_off.data(), rec_clip0, r0, nr, d_speed + v0, kcc, fan_value, &P, ho.data()));
+      SHZ_TRY(sp_count(ctx, d_pf, d_pt, d_poff, peak_off.data(), rec_clip0, r0, nr, d_speed + v0, d_same + v0, kcc, fan_value, &P, ho.data()));
       const uint64_t total = ho[n_seg];
       void *d_key, *d_t1;
       SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SP_KEY, total * 4 + 64, &d_key));
@@ -560,7 +560,7 @@ extern "C" int32_t shz_scan_timeline_speeds(const uint64_t* win_off, uint32_t n_
         seg_best[n] = o_best;
         seg_pos_first[n] = (int32_t)o_pos_first;
         seg_pos_last[n] = (int32_t)o_pos_last;
-        seg_rung[n] = sp_best(chosen.data(), speed_q16, n_speeds);
+        seg_rung[n] = sp_best(chosen.data(), speed_q16, speed_q16, n_speeds);
       }
       n += open ? 1 : 0;
       open = false;

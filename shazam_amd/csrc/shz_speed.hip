@@ -10,6 +10,16 @@
 // time sort.  Both maps are monotone and the input is (t asc, f asc): for s >= 1 the order is the input's; for s < 1 at most
 // two neighbouring frames fall into one t', and a peak's place changes by a count over the neighbour frame.
 //
+// Two factors (numpy twin: tests/warp_twin.py): a time-stretch with the pitch kept, or a pitch shift with the
+// tempo kept, moves time and frequency by factors of their own.  A warp is a pair (t16, f16): t' is formed with t16, f' with
+// f16, and a speed is the pair (s16, s16).  The order argument per factor: f' is monotone in f at any f16, so inside one frame
+// the order (f', index) is the input's; t' is strictly monotone for t16 >= 65536, so there the whole order is the input's
+// whatever f16 is (f16 < 65536 spreads the bins and some leave, f16 > 65536 folds neighbouring bins into one f', and a tie
+// keeps the index order).  For t16 < 65536 frames t and t + 2 are still 2 t16 >= 65536 apart before the shift, so at most two
+// neighbouring frames share a t'; a peak then moves by the kept peaks of the OTHER frame that its f' passes, compared on f'
+// with "equal f': the earlier index first" -- ties across the two frames are what f16 > 65536 adds (bins 2k - 1 and 2k at
+// f16 = 131072), peaks of the neighbour frame that leave are what f16 < 65536 adds.  So the merge is switched by t16 alone.
+//
 // Work is laid out over (query, speed, clip, peak) items, so that a single short query with a ladder of a hundred factors
 // still fills waves, and so that the compacted peaks -- and the hashes behind them -- come out in the order the match
 // wants: for query q, for speed v, for every clip (channel) c of q.  (q, v) is then one contiguous query of the match.
@@ -27,7 +37,7 @@
 #define SP_SMALL_SLICE 2u       // queries of a match slice under SHZ_DEBUG_SPEED_SMALL_SLICES
 
 struct sp_item {
-  uint32_t c, s16;
+  uint32_t c, t16, f16;       // its clip, and the time and the frequency factor of its warp
   uint64_t g, c_lo, c_hi;     // the peak, and the peaks of its clip
   uint64_t seg0, seg_n;       // first item of its (query, speed, clip), items of it
 };
@@ -53,7 +63,8 @@ __device__ __forceinline__ bool sp_decode(const sp_view& V, uint64_t w, sp_item*
   uint32_t c = c0;
   while (c + 1 < c1 && V.poff[c + 1] <= g) ++c;   // (the channels of one query: one or two)
   it->c = c;
-  it->s16 = V.speed[v];
+  it->t16 = V.tempo[v];
+  it->f16 = V.pitch[v];
   it->g = g;
   it->c_lo = V.poff[c];
   it->c_hi = V.poff[c + 1];
@@ -66,7 +77,7 @@ __global__ __launch_bounds__(SP_THREADS) void sp_flag_kernel(sp_view V, uint32_t
   const uint64_t w = (uint64_t)blockIdx.x * SP_THREADS + threadIdx.x;
   if (w >= V.n_items) return;
   sp_item it;
-  flag[w] = sp_decode(V, w, &it) && sp_warp_f(V.pf[it.g], it.s16) <= SP_F_MAX ? 1u : 0u;
+  flag[w] = sp_decode(V, w, &it) && sp_warp_f(V.pf[it.g], it.f16) <= SP_F_MAX ? 1u : 0u;
 }
 
 // pos: exclusive scan of the flags; *d_kept: their sum.  The kept peaks of (q, v, c) are [pos[seg0], pos[seg0 + seg_n]).
@@ -77,31 +88,31 @@ __global__ __launch_bounds__(SP_THREADS) void sp_place_kernel(sp_view V, const u
   if (w >= V.n_items) return;
   sp_item it;
   if (!sp_decode(V, w, &it)) return;
-  const uint32_t s16 = it.s16, fi = sp_warp_f(V.pf[it.g], s16);
+  const uint32_t t16 = it.t16, f16 = it.f16, fi = sp_warp_f(V.pf[it.g], f16);
   if (fi > SP_F_MAX) return;
-  const uint32_t t = V.pt[it.g], ti = sp_warp_t(t, s16);
+  const uint32_t t = V.pt[it.g], ti = sp_warp_t(t, t16);
   const uint32_t base = pos[it.seg0];
   const uint64_t seg1 = it.seg0 + it.seg_n;
   const uint32_t end = seg1 < V.n_items ? pos[seg1] : (uint32_t)*d_kept;
   uint32_t rank = pos[w] - base;
-  if (s16 < SP_S_ONE) {
+  if (t16 < SP_S_ONE) {   // (the time factor alone decides whether frames merge; the comparisons below are on f' at any f16)
     // the frame in front of this peak's, if it falls into the same t': its kept peaks with a greater f' go behind this one
     uint64_t j = it.g;
     while (j > it.c_lo && V.pt[j - 1] == t) --j;
-    if (j > it.c_lo && sp_warp_t(V.pt[j - 1], s16) == ti) {
+    if (j > it.c_lo && sp_warp_t(V.pt[j - 1], t16) == ti) {
       const uint32_t tn = V.pt[j - 1];
       for (; j > it.c_lo && V.pt[j - 1] == tn; --j) {
-        const uint32_t fj = sp_warp_f(V.pf[j - 1], s16);
+        const uint32_t fj = sp_warp_f(V.pf[j - 1], f16);
         if (fj <= SP_F_MAX && fj > fi) --rank;
       }
     }
     // the frame behind it, likewise: its kept peaks with a smaller f' go in front (equal f': the earlier index first)
     j = it.g + 1;
     while (j < it.c_hi && V.pt[j] == t) ++j;
-    if (j < it.c_hi && sp_warp_t(V.pt[j], s16) == ti) {
+    if (j < it.c_hi && sp_warp_t(V.pt[j], t16) == ti) {
       const uint32_t tn = V.pt[j];
       for (; j < it.c_hi && V.pt[j] == tn; ++j)
-        if (sp_warp_f(V.pf[j], s16) < fi) ++rank;
+        if (sp_warp_f(V.pf[j], f16) < fi) ++rank;
     }
   }
   if (rank >= end - base) return;   // (peaks that are not in (t, f) order: nothing is written outside the segment)
@@ -202,15 +213,15 @@ uint64_t sp_items(const uint64_t* peak_off, const uint32_t* clip0, uint32_t q0, 
   return (peak_off[clip0[q0 + nq]] - peak_off[clip0[q0]]) * K;
 }
 
-// hash_off: n_seg + 1 entries (host), relative to the pass.  d_poff / d_speed: the call's tables on the device.
+// hash_off: n_seg + 1 entries (host), relative to the pass.  d_poff / d_tempo / d_pitch: the call's tables on the device.
 int32_t sp_count(shz_ctx* ctx, const uint16_t* d_pf, const uint32_t* d_pt, const uint64_t* d_poff, const uint64_t* peak_off,
-                        const uint32_t* clip0, uint32_t q0, uint32_t nq, const uint32_t* d_speed, uint32_t K, uint32_t fan,
-                        sp_pass* P, uint64_t* hash_off) {
+                        const uint32_t* clip0, uint32_t q0, uint32_t nq, const uint32_t* d_tempo, const uint32_t* d_pitch, uint32_t K,
+                        uint32_t fan, sp_pass* P, uint64_t* hash_off) {
   const uint64_t n_items = sp_items(peak_off, clip0, q0, nq, K);
   const uint64_t n_seg = (uint64_t)(clip0[q0 + nq] - clip0[q0]) * K;
   P->n_seg = n_seg;
   for (uint64_t e = 0; e <= n_seg; ++e) hash_off[e] = 0;
-  P->V = sp_view{d_pf, d_pt, d_poff, nullptr, nullptr, d_speed, nq, K, fan, n_items};
+  P->V = sp_view{d_pf, d_pt, d_poff, nullptr, nullptr, d_tempo, d_pitch, nq, K, fan, n_items};
   if (n_items == 0) return SHZ_OK;
   if (n_items * std::max<uint32_t>(fan - 1, 1) >= (1ull << 32))
     SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "speed warp: %llu (peak, speed) pairs at fan_value %u in one pass (32-bit offsets)",
@@ -271,45 +282,54 @@ int32_t sp_write(shz_ctx* ctx, const sp_pass& P, uint32_t* d_key, uint32_t* d_t1
   return SHZ_OK;
 }
 
-// what every entry point with a ladder refuses about it, before anything is launched
-int32_t sp_check_ladder(shz_ctx* ctx, const char* who, const uint32_t* speed_q16, uint32_t n_speeds, uint32_t fan_value) {
-  if (n_speeds == 0 || n_speeds > SP_MAX_SPEEDS)
-    SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: n_speeds must be in [1, %u], got %u", who, SP_MAX_SPEEDS, n_speeds);
-  if (!speed_q16) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: speed_q16 is NULL", who);
-  for (uint32_t v = 0; v < n_speeds; ++v)
-    if (speed_q16[v] < SP_S_MIN || speed_q16[v] > SP_S_MAX)
-      SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: speed %u is %u; factors are Q16 in [%u, %u] (0.5x .. 2x)", who, v, speed_q16[v], SP_S_MIN,
-               SP_S_MAX);
+// what every entry point with a ladder refuses about it, before anything is launched (names: shz_internal.h)
+int32_t sp_check_ladder(shz_ctx* ctx, const char* who, const char* n_name, const char* t_name, const uint32_t* tempo_q16,
+                        const char* f_name, const uint32_t* pitch_q16, uint32_t n, uint32_t fan_value) {
+  if (n == 0 || n > SP_MAX_SPEEDS) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: %s must be in [1, %u], got %u", who, n_name, SP_MAX_SPEEDS, n);
+  if (!tempo_q16) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: %s_q16 is NULL", who, t_name);
+  if (!pitch_q16) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: %s_q16 is NULL", who, f_name);
+  const uint32_t* tab[2] = {tempo_q16, pitch_q16};
+  const char* name[2] = {t_name, f_name};
+  for (int a = 0; a < (pitch_q16 == tempo_q16 ? 1 : 2); ++a)
+    for (uint32_t v = 0; v < n; ++v)
+      if (tab[a][v] < SP_S_MIN || tab[a][v] > SP_S_MAX)
+        SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: %s %u is %u; factors are Q16 in [%u, %u] (0.5x .. 2x)", who, name[a], v, tab[a][v], SP_S_MIN,
+                 SP_S_MAX);
   if (fan_value < 1 || fan_value > 64) SHZ_FAIL(ctx, SHZ_E_INVALID, "fan_value must be in [1,64]");
   return SHZ_OK;
 }
 
-// peak_off | speeds on the device (one block of the call)
-int32_t sp_upload_tables(shz_ctx* ctx, const uint64_t* peak_off, uint32_t n_clips, const uint32_t* speed_q16, uint32_t K,
-                                const uint64_t** d_poff, const uint32_t** d_speed) {
-  const uint64_t po_bytes = ((uint64_t)n_clips + 1) * 8, bytes = po_bytes + (uint64_t)K * 4;
+// peak_off | tempo | pitch on the device (one block of the call)
+int32_t sp_upload_tables(shz_ctx* ctx, const uint64_t* peak_off, uint32_t n_clips, const uint32_t* tempo_q16,
+                         const uint32_t* pitch_q16, uint32_t K, const uint64_t** d_poff, const uint32_t** d_tempo,
+                         const uint32_t** d_pitch) {
+  const bool one = pitch_q16 == tempo_q16;
+  const uint64_t po_bytes = ((uint64_t)n_clips + 1) * 8, tab_bytes = (uint64_t)K * 4, bytes = po_bytes + (one ? 1 : 2) * tab_bytes;
   std::vector<char> h(bytes);
   uint64_t* hp = (uint64_t*)h.data();
   for (uint32_t c = 0; c <= n_clips; ++c) hp[c] = peak_off[c] - peak_off[0];
-  memcpy(h.data() + po_bytes, speed_q16, (uint64_t)K * 4);
+  memcpy(h.data() + po_bytes, tempo_q16, tab_bytes);
+  if (!one) memcpy(h.data() + po_bytes + tab_bytes, pitch_q16, tab_bytes);
   void* d;
   SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SP_TAB, bytes, &d));
   SHZ_HIP(ctx, shz_memcpy(ctx, d, h.data(), bytes, hipMemcpyHostToDevice));
   *d_poff = (const uint64_t*)d;
-  *d_speed = (const uint32_t*)((char*)d + po_bytes);
+  *d_tempo = (const uint32_t*)((char*)d + po_bytes);
+  *d_pitch = one ? *d_tempo : (const uint32_t*)((char*)d + po_bytes + tab_bytes);
   return SHZ_OK;
 }
 
-extern "C" int32_t shz_warp_pair_hash(shz_ctx* ctx, const uint16_t* peak_f, const uint32_t* peak_t, const uint64_t* peak_off,
-                                      uint32_t n_clips, const uint32_t* query_clip0, uint32_t n_queries, const uint32_t* speed_q16,
-                                      uint32_t n_speeds, uint32_t fan_value, uint32_t flags, uint32_t* key32, uint32_t* t1,
-                                      uint64_t* hash_off, uint64_t cap, uint64_t* count) {
+extern "C" int32_t shz_warp_pair_hash_tf(shz_ctx* ctx, const uint16_t* peak_f, const uint32_t* peak_t, const uint64_t* peak_off,
+                                         uint32_t n_clips, const uint32_t* query_clip0, uint32_t n_queries,
+                                         const uint32_t* tempo_q16, const uint32_t* pitch_q16, uint32_t n_warps, uint32_t fan_value,
+                                         uint32_t flags, uint32_t* key32, uint32_t* t1, uint64_t* hash_off, uint64_t cap,
+                                         uint64_t* count) {
   if (!ctx) return SHZ_E_INVALID;
   if (count) *count = 0;
   // everything that can be refused is refused before the first launch
-  if (flags & ~(SHZ_IN_DEVICE | SHZ_OUT_DEVICE)) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_warp_pair_hash: flags may hold SHZ_IN_DEVICE and SHZ_OUT_DEVICE");
-  SHZ_TRY(sp_check_ladder(ctx, "shz_warp_pair_hash", speed_q16, n_speeds, fan_value));
-  if (!peak_off) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_warp_pair_hash: peak_off is NULL");
+  if (flags & ~(SHZ_IN_DEVICE | SHZ_OUT_DEVICE)) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_warp_pair_hash_tf: flags may hold SHZ_IN_DEVICE and SHZ_OUT_DEVICE");
+  SHZ_TRY(sp_check_ladder(ctx, "shz_warp_pair_hash_tf", "n_warps", "tempo", tempo_q16, "pitch", pitch_q16, n_warps, fan_value));
+  if (!peak_off) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_warp_pair_hash_tf: peak_off is NULL");
   for (uint32_t c = 0; c < n_clips; ++c)
     if (peak_off[c + 1] < peak_off[c]) SHZ_FAIL(ctx, SHZ_E_INVALID, "peak_off decreases at clip %u", c);
   std::vector<uint32_t> own;   // no queries given: every clip is a query of its own
@@ -321,17 +341,17 @@ extern "C" int32_t shz_warp_pair_hash(shz_ctx* ctx, const uint16_t* peak_f, cons
   }
   SHZ_TRY(shz_check_clip0(ctx, "query_clip0", "query", query_clip0, n_queries, n_clips));
   const uint64_t n = peak_off[n_clips] - peak_off[0];
-  if (n && (!peak_f || !peak_t)) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_warp_pair_hash: NULL buffer");
-  if (cap && (!key32 || !t1)) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_warp_pair_hash: NULL buffer");
+  if (n && (!peak_f || !peak_t)) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_warp_pair_hash_tf: NULL buffer");
+  if (cap && (!key32 || !t1)) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_warp_pair_hash_tf: NULL buffer");
   const bool in_dev = (flags & SHZ_IN_DEVICE) != 0, out_dev = (flags & SHZ_OUT_DEVICE) != 0;
   if (!in_dev)   // (device lists are the caller's promise, as for shz_pair_hash: time does not decrease inside a clip, t < 2^31)
     for (uint32_t c = 0; c < n_clips; ++c)
       for (uint64_t i = peak_off[c]; i < peak_off[c + 1]; ++i) {
-        if (peak_t[i] >= (1u << 31)) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_warp_pair_hash: peak %llu has t = %u; t must be < 2^31", (unsigned long long)i, peak_t[i]);
+        if (peak_t[i] >= (1u << 31)) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_warp_pair_hash_tf: peak %llu has t = %u; t must be < 2^31", (unsigned long long)i, peak_t[i]);
         if (i > peak_off[c] && peak_t[i] < peak_t[i - 1])
-          SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_warp_pair_hash: peaks must be in (time asc, freq asc) order; t decreases at peak %llu", (unsigned long long)i);
+          SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_warp_pair_hash_tf: peaks must be in (time asc, freq asc) order; t decreases at peak %llu", (unsigned long long)i);
       }
-  const uint64_t n_seg = (uint64_t)n_clips * n_speeds;
+  const uint64_t n_seg = (uint64_t)n_clips * n_warps;
   if (hash_off) memset(hash_off, 0, (n_seg + 1) * 8);
   if (n_clips == 0 || n == 0) return SHZ_OK;
   SHZ_HIP(ctx, hipSetDevice(ctx->device));
@@ -347,12 +367,12 @@ extern "C" int32_t shz_warp_pair_hash(shz_ctx* ctx, const uint16_t* peak_f, cons
     d_pt = (const uint32_t*)b;
   }
   const uint64_t* d_poff;
-  const uint32_t* d_speed;
-  SHZ_TRY(sp_upload_tables(ctx, peak_off, n_clips, speed_q16, n_speeds, &d_poff, &d_speed));
+  const uint32_t *d_tempo, *d_pitch;
+  SHZ_TRY(sp_upload_tables(ctx, peak_off, n_clips, tempo_q16, pitch_q16, n_warps, &d_poff, &d_tempo, &d_pitch));
   std::vector<uint64_t> rel((size_t)n_clips + 1), ho((size_t)n_seg + 1, 0);
   for (uint32_t c = 0; c <= n_clips; ++c) rel[c] = peak_off[c] - peak_off[0];
   sp_pass P;
-  SHZ_TRY(sp_count(ctx, d_pf, d_pt, d_poff, rel.data(), query_clip0, 0, n_queries, d_speed, n_speeds, fan_value, &P, ho.data()));
+  SHZ_TRY(sp_count(ctx, d_pf, d_pt, d_poff, rel.data(), query_clip0, 0, n_queries, d_tempo, d_pitch, n_warps, fan_value, &P, ho.data()));
   const uint64_t total = ho[n_seg];
   if (hash_off) memcpy(hash_off, ho.data(), (n_seg + 1) * 8);
   if (count) *count = total;
@@ -373,9 +393,23 @@ extern "C" int32_t shz_warp_pair_hash(shz_ctx* ctx, const uint16_t* peak_f, cons
   return SHZ_OK;
 }
 
-// index of the greatest top-1 aligned count; ties to the factor nearest 65536, then to the lower index
-uint32_t sp_best(const uint32_t* top1, const uint32_t* speed_q16, uint32_t K) {
-  auto dist = [&](uint32_t v) { return speed_q16[v] > SP_S_ONE ? speed_q16[v] - SP_S_ONE : SP_S_ONE - speed_q16[v]; };
+// the speed ladder: one table for time and frequency (its own names in what is refused about it)
+extern "C" int32_t shz_warp_pair_hash(shz_ctx* ctx, const uint16_t* peak_f, const uint32_t* peak_t, const uint64_t* peak_off,
+                                      uint32_t n_clips, const uint32_t* query_clip0, uint32_t n_queries, const uint32_t* speed_q16,
+                                      uint32_t n_speeds, uint32_t fan_value, uint32_t flags, uint32_t* key32, uint32_t* t1,
+                                      uint64_t* hash_off, uint64_t cap, uint64_t* count) {
+  if (!ctx) return SHZ_E_INVALID;
+  if (count) *count = 0;
+  SHZ_TRY(sp_check_ladder(ctx, "shz_warp_pair_hash", "n_speeds", "speed", speed_q16, "speed", speed_q16, n_speeds, fan_value));
+  return shz_warp_pair_hash_tf(ctx, peak_f, peak_t, peak_off, n_clips, query_clip0, n_queries, speed_q16, speed_q16, n_speeds,
+                               fan_value, flags, key32, t1, hash_off, cap, count);
+}
+
+// index of the greatest top-1 aligned count; ties to the smaller |t16 - 65536| + |f16 - 65536| (on a speed ladder: the factor
+// nearest 65536), then to the lower index
+uint32_t sp_best(const uint32_t* top1, const uint32_t* tempo_q16, const uint32_t* pitch_q16, uint32_t K) {
+  auto off = [](uint32_t s) { return s > SP_S_ONE ? s - SP_S_ONE : SP_S_ONE - s; };
+  auto dist = [&](uint32_t v) { return off(tempo_q16[v]) + off(pitch_q16[v]); };
   uint32_t best = 0;
   for (uint32_t v = 1; v < K; ++v)
     if (top1[v] > top1[best] || (top1[v] == top1[best] && dist(v) < dist(best))) best = v;
@@ -413,29 +447,29 @@ int32_t sp_peaks_owned(shz_ctx* ctx, const char* who, const int16_t* pcm, const 
   return SHZ_OK;
 }
 
-extern "C" int32_t shz_recognize_speeds(shz_ctx* ctx, shz_table* t, const int16_t* pcm, const uint64_t* clip_off, uint32_t n_clips,
-                                        const uint32_t* query_clip0, uint32_t n_queries, uint32_t fs, double amp_min,
-                                        uint32_t fan_value, uint32_t topn, const uint32_t* speed_q16, uint32_t n_speeds,
-                                        uint32_t flags, uint32_t* out_best, uint32_t* out_sid, int32_t* out_delta,
-                                        uint32_t* out_aligned, uint32_t* out_dedup, uint32_t* out_nres, uint32_t* out_nhash,
-                                        uint32_t* out_profile, float* ms_extract, float* ms_warp, float* ms_match) {
+extern "C" int32_t shz_recognize_warps(shz_ctx* ctx, shz_table* t, const int16_t* pcm, const uint64_t* clip_off, uint32_t n_clips,
+                                       const uint32_t* query_clip0, uint32_t n_queries, uint32_t fs, double amp_min,
+                                       uint32_t fan_value, uint32_t topn, const uint32_t* tempo_q16, const uint32_t* pitch_q16,
+                                       uint32_t n_warps, uint32_t flags, uint32_t* out_best, uint32_t* out_sid, int32_t* out_delta,
+                                       uint32_t* out_aligned, uint32_t* out_dedup, uint32_t* out_nres, uint32_t* out_nhash,
+                                       uint32_t* out_profile, float* ms_extract, float* ms_warp, float* ms_match) {
   if (!ctx || !t) return SHZ_E_INVALID;
   if (ms_extract) *ms_extract = 0.f;
   if (ms_warp) *ms_warp = 0.f;
   if (ms_match) *ms_match = 0.f;
   // everything that can be refused is refused before the first launch
-  if (flags & ~(SHZ_PCM_DEVICE | SHZ_MATCH_FULL_SORT)) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_recognize_speeds: flags may hold SHZ_PCM_DEVICE and SHZ_MATCH_FULL_SORT");
-  SHZ_TRY(sp_check_ladder(ctx, "shz_recognize_speeds", speed_q16, n_speeds, fan_value));
+  if (flags & ~(SHZ_PCM_DEVICE | SHZ_MATCH_FULL_SORT)) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_recognize_warps: flags may hold SHZ_PCM_DEVICE and SHZ_MATCH_FULL_SORT");
+  SHZ_TRY(sp_check_ladder(ctx, "shz_recognize_warps", "n_warps", "tempo", tempo_q16, "pitch", pitch_q16, n_warps, fan_value));
   if (n_queries == 0) {
-    if (n_clips) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_recognize_speeds: %u clips belong to no query", n_clips);
+    if (n_clips) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_recognize_warps: %u clips belong to no query", n_clips);
     return SHZ_OK;
   }
   SHZ_TRY(shz_check_clip0(ctx, "query_clip0", "query", query_clip0, n_queries, n_clips));
   SHZ_TRY(shz_check_clip_off(ctx, clip_off, n_clips));
   if (fs == 0) SHZ_FAIL(ctx, SHZ_E_INVALID, "Fs must be > 0");
   if (n_clips && !pcm && clip_off[n_clips] > clip_off[0]) SHZ_FAIL(ctx, SHZ_E_INVALID, "pcm is NULL");
-  if (!out_best || !out_sid || !out_delta || !out_aligned || !out_dedup || !out_nres) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_recognize_speeds: NULL buffer");
-  const uint32_t K = n_speeds, s_max = *std::max_element(speed_q16, speed_q16 + K);
+  if (!out_best || !out_sid || !out_delta || !out_aligned || !out_dedup || !out_nres) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_recognize_warps: NULL buffer");
+  const uint32_t K = n_warps, s_max = *std::max_element(tempo_q16, tempo_q16 + K);   // (time alone: the bias bound)
   uint64_t max_frames = 1, frames = 0;
   for (uint32_t c = 0; c < n_clips; ++c) {
     const uint64_t f = shz_frame_count_hop(clip_off[c + 1] - clip_off[c], ctx->hop);
@@ -445,7 +479,7 @@ extern "C" int32_t shz_recognize_speeds(shz_ctx* ctx, shz_table* t, const int16_
   // the largest warped time: round((max_frames - 1) s_max), the bias bound of the match
   const uint64_t t_max = ((max_frames - 1) * s_max + 32768) >> 16;
   if (t_max >= (1ull << 20))
-    SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "shz_recognize_speeds: a clip of %llu frames at factor %u / 65536 reaches t' = %llu; query offsets must be < 2^20",
+    SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "shz_recognize_warps: a clip of %llu frames at time factor %u / 65536 reaches t' = %llu; query offsets must be < 2^20",
              (unsigned long long)max_frames, s_max, (unsigned long long)t_max);
   SHZ_TRY(shz_match_ready(ctx, t, topn));
   SHZ_HIP(ctx, hipSetDevice(ctx->device));
@@ -459,12 +493,12 @@ extern "C" int32_t shz_recognize_speeds(shz_ctx* ctx, shz_table* t, const int16_
   std::vector<uint64_t> peak_off((size_t)n_clips + 1, 0);
   const uint16_t* d_pf = nullptr;
   const uint32_t* d_pt = nullptr;
-  SHZ_TRY(sp_peaks_owned(ctx, "shz_recognize_speeds", pcm, clip_off, n_clips, frames, fs, amp_min, flags & SHZ_PCM_DEVICE,
+  SHZ_TRY(sp_peaks_owned(ctx, "shz_recognize_warps", pcm, clip_off, n_clips, frames, fs, amp_min, flags & SHZ_PCM_DEVICE,
                          peak_off.data(), &d_pf, &d_pt));
   if (timed) SHZ_HIP(ctx, hipEventRecord(ctx->sp_ev[1], ctx->stream));
   const uint64_t* d_poff;
-  const uint32_t* d_speed;
-  SHZ_TRY(sp_upload_tables(ctx, peak_off.data(), n_clips, speed_q16, K, &d_poff, &d_speed));
+  const uint32_t *d_tempo, *d_pitch;
+  SHZ_TRY(sp_upload_tables(ctx, peak_off.data(), n_clips, tempo_q16, pitch_q16, K, &d_poff, &d_tempo, &d_pitch));
   // 2) slices of whole queries: the entries a slice can yield at most (every peak with all its partners, at every factor)
   // stay within the match's pair budget and 1/8 of the workspace limit.  A query is never split: one beyond that is a
   // slice of its own
@@ -485,7 +519,7 @@ extern "C" int32_t shz_recognize_speeds(shz_ctx* ctx, shz_table* t, const int16_
     const uint64_t n_seg = (uint64_t)(query_clip0[q0 + nq] - query_clip0[q0]) * K;
     ho.assign((size_t)n_seg + 1, 0);
     sp_pass P;
-    SHZ_TRY(sp_count(ctx, d_pf, d_pt, d_poff, peak_off.data(), query_clip0, q0, nq, d_speed, K,
+    SHZ_TRY(sp_count(ctx, d_pf, d_pt, d_poff, peak_off.data(), query_clip0, q0, nq, d_tempo, d_pitch, K,
                      fan_value, &P, ho.data()));
     const uint64_t total = ho[n_seg];
     void *d_key, *d_t1;
@@ -525,7 +559,7 @@ extern "C" int32_t shz_recognize_speeds(shz_ctx* ctx, shz_table* t, const int16_
     const uint64_t o = (uint64_t)q * K;
     for (uint32_t v = 0; v < K; ++v) top1[v] = v_nres[o + v] ? v_aligned[(o + v) * topn] : 0u;
     if (out_profile) memcpy(out_profile + o, top1.data(), (size_t)K * 4);
-    const uint32_t b = sp_best(top1.data(), speed_q16, K);
+    const uint32_t b = sp_best(top1.data(), tempo_q16, pitch_q16, K);
     const uint64_t src = (o + b) * topn, dst = (uint64_t)q * topn;
     out_best[q] = b;
     memcpy(out_sid + dst, v_sid.data() + src, (size_t)topn * 4);
@@ -536,4 +570,21 @@ extern "C" int32_t shz_recognize_speeds(shz_ctx* ctx, shz_table* t, const int16_
     if (out_nhash) out_nhash[q] = v_nhash[o + b];
   }
   return SHZ_OK;
+}
+
+// the speed ladder: one table for time and frequency (its own names in what is refused about it)
+extern "C" int32_t shz_recognize_speeds(shz_ctx* ctx, shz_table* t, const int16_t* pcm, const uint64_t* clip_off, uint32_t n_clips,
+                                        const uint32_t* query_clip0, uint32_t n_queries, uint32_t fs, double amp_min,
+                                        uint32_t fan_value, uint32_t topn, const uint32_t* speed_q16, uint32_t n_speeds,
+                                        uint32_t flags, uint32_t* out_best, uint32_t* out_sid, int32_t* out_delta,
+                                        uint32_t* out_aligned, uint32_t* out_dedup, uint32_t* out_nres, uint32_t* out_nhash,
+                                        uint32_t* out_profile, float* ms_extract, float* ms_warp, float* ms_match) {
+  if (!ctx || !t) return SHZ_E_INVALID;
+  if (ms_extract) *ms_extract = 0.f;
+  if (ms_warp) *ms_warp = 0.f;
+  if (ms_match) *ms_match = 0.f;
+  SHZ_TRY(sp_check_ladder(ctx, "shz_recognize_speeds", "n_speeds", "speed", speed_q16, "speed", speed_q16, n_speeds, fan_value));
+  return shz_recognize_warps(ctx, t, pcm, clip_off, n_clips, query_clip0, n_queries, fs, amp_min, fan_value, topn, speed_q16,
+                             speed_q16, n_speeds, flags, out_best, out_sid, out_delta, out_aligned, out_dedup, out_nres, out_nhash,
+                             out_profile, ms_extract, ms_warp, ms_match);
 }

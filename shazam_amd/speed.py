@@ -5,8 +5,14 @@ copy has already lost the match.  Here the query's constellation peaks are extra
 integer coordinates are mapped back to the table's domain (f' = round(f / s), t' = round(t s)), paired, hashed and matched
 on the device, and the factor with the most aligned hashes wins.  A variant costs no FFT.
 
+A speed is one factor for both axes.  A time-stretch that keeps the pitch (a deck with key-lock), a pitch shift that keeps
+the tempo, or both by different amounts are a WARP, a pair of Q16 factors (t16, f16): t' is formed with t16,
+f' with f16.  recognize_warps matches a list of pairs -- the product of a tempo ladder and a pitch ladder (search="grid"), or
+the pitch ladder at tempo 1 followed by the tempo ladder at every query's best pitch (search="separable", a heuristic).
+
 Limits: the hop is fixed, so a warped time is a rounded frame; a peak near the edge of its 21x21 neighbourhood may move when
-the audio is stretched; pitch-preserving time-stretch is NOT covered (it needs independent factors for f and t)."""
+the audio is stretched; the smearing a real phase-vocoder time-stretch adds is not modelled by the corpus the tolerances were
+measured on; the scan and the live listeners take speed ladders only, no warp pairs."""
 from __future__ import annotations
 
 from time import time
@@ -23,26 +29,71 @@ S_MIN, S_MAX = 32768, 131072
 DEFAULT_STEP_Q16 = 92
 
 
-def speed_ladder(lo: float = 0.95, hi: float = 1.05, step: float = None) -> np.ndarray:
-    """The factors tried for a query of unknown speed, as Q16 (uint32, sorted, no duplicates): 65536 + k * step for every k
-    that keeps the rung inside [lo, hi], and always 65536 itself.  step=None: the measured default, 92 / 65536 = 0.14 % --
-    twice the half-width (0.07 %) of the tolerance curve in DESIGN.md 3.7c, at which the aligned count of the right song
-    is half of what the true factor gives."""
-    st = DEFAULT_STEP_Q16 if step is None else int(round(float(step) * S_ONE))
+MAX_WARPS = 1024           # variants of one library call (SP_MAX_SPEEDS)
+# The two axes of a warp (scripts/warp_curves.py: oracle + tests/warp_twin.py, note corpus, 4 x 30 s in the
+# table, 10 s queries, 24 curves an axis).  Each step is twice the miss at which the mean aligned count of the right song
+# has fallen to half of its value at the true pair.
+#   pitch: half-width 0.06 % at any query length; step 0.12 % = round(0.0012 * 65536)
+#   tempo: half-width 2.1 % on 10 s queries; step 4.2 % = round(0.042 * 65536).  A wrong tempo lets the offset drift over the
+#          query, so the half-width scales inversely with the query's length (5.2 % at 5 s, 0.97 % at 20 s): queries much
+#          longer than 10 s want a proportionally finer tempo step
+DEFAULT_PITCH_STEP_Q16 = 79
+DEFAULT_TEMPO_STEP_Q16 = 2753
+
+
+def _ladder(name: str, lo: float, hi: float, st: int) -> np.ndarray:
     if st < 1:
         raise ValueError("step must be at least 1 / 65536")
     lo16, hi16 = int(np.ceil(float(lo) * S_ONE)), int(np.floor(float(hi) * S_ONE))
     if lo16 < S_MIN or hi16 > S_MAX or lo16 > hi16:
-        raise ValueError("speed_ladder: 0.5 <= lo <= hi <= 2.0")
+        raise ValueError(f"{name}: 0.5 <= lo <= hi <= 2.0")
     k_lo, k_hi = -((S_ONE - lo16) // st), (hi16 - S_ONE) // st      # ceil((lo16 - S_ONE) / st), floor((hi16 - S_ONE) / st)
     rungs = S_ONE + st * np.arange(k_lo, k_hi + 1, dtype=np.int64)
     return np.unique(np.concatenate([rungs, [S_ONE]])).astype(np.uint32)
 
 
-def _check_speeds(speeds) -> np.ndarray:
+def speed_ladder(lo: float = 0.95, hi: float = 1.05, step: float = None) -> np.ndarray:
+    """The factors tried for a query of unknown speed, as Q16 (uint32, sorted, no duplicates): 65536 + k * step for every k
+    that keeps the rung inside [lo, hi], and always 65536 itself.  step=None: the measured default, 92 / 65536 = 0.14 % --
+    twice the half-width (0.07 %) of the tolerance curve in DESIGN.md 3.7c, at which the aligned count of the right song
+    is half of what the true factor gives."""
+    return _ladder("speed_ladder", lo, hi, DEFAULT_STEP_Q16 if step is None else int(round(float(step) * S_ONE)))
+
+
+def tempo_ladder(lo: float = 0.95, hi: float = 1.05, step: float = None) -> np.ndarray:
+    """The time factors tried for a query of unknown tempo, Q16 like speed_ladder's rungs (sorted, always with 65536).
+    step=None: DEFAULT_TEMPO_STEP_Q16 / 65536, measured on 10 s queries."""
+    return _ladder("tempo_ladder", lo, hi, DEFAULT_TEMPO_STEP_Q16 if step is None else int(round(float(step) * S_ONE)))
+
+
+def pitch_ladder(lo: float = 0.95, hi: float = 1.05, step: float = None) -> np.ndarray:
+    """The frequency factors tried for a query of unknown pitch, Q16 like speed_ladder's rungs (sorted, always with 65536).
+    step=None: DEFAULT_PITCH_STEP_Q16 / 65536."""
+    return _ladder("pitch_ladder", lo, hi, DEFAULT_PITCH_STEP_Q16 if step is None else int(round(float(step) * S_ONE)))
+
+
+def warp_grid(tempos, pitches):
+    """(tempo_q16, pitch_q16) of every pair of the two ladders, tempo-major: pair i * len(pitches) + j is (tempos[i],
+    pitches[j]), so a row of the grid is one tempo at every pitch."""
+    t, f = _check_speeds(tempos, "tempos"), _check_speeds(pitches, "pitches")
+    return np.repeat(t, len(f)), np.tile(f, len(t))
+
+
+def warp_chunks(n_pairs: int, row: int = 1, limit: int = MAX_WARPS):
+    """[(a, b)]: the pair list [0, n_pairs) cut into library calls of at most `limit` pairs, each a whole number of rows of
+    `row` pairs (a grid's row: one tempo at every pitch; an explicit pair list: rows of 1)."""
+    if row < 1 or row > limit:
+        raise ValueError(f"a row of {row} pairs does not fit one call of at most {limit}: shorten the pitch ladder")
+    if n_pairs % row:
+        raise ValueError("the pair list is no whole number of rows")
+    per = (limit // row) * row
+    return [(a, min(a + per, n_pairs)) for a in range(0, n_pairs, per)]
+
+
+def _check_speeds(speeds, name: str = "speeds") -> np.ndarray:
     sp = np.ascontiguousarray(speeds)
-    if sp.dtype.kind not in "iu":
-        raise TypeError("speeds are Q16 integers (round(s * 65536)); see speed_ladder")
+    if sp.dtype.kind not in "iu" or sp.ndim != 1:
+        raise TypeError(f"{name} are Q16 integers (round(s * 65536)); see speed_ladder")
     return sp.astype(np.uint32)
 
 
@@ -53,6 +104,15 @@ def warp_hashes(peaks_f, peaks_t, peak_off, speeds, fan_value: int = 5, ctx=None
     segment c * n_speeds + v is clip c at speed v.  t1 is in the table's frames."""
     from . import get_context
     return (ctx or get_context()).warp_pair_hash(peaks_f, peaks_t, peak_off, _check_speeds(speeds), query_clip0, int(fan_value))
+
+
+def warp_hashes_tf(peaks_f, peaks_t, peak_off, tempos, pitches, fan_value: int = 5, ctx=None, query_clip0=None):
+    """warp_hashes with a time and a frequency factor of its own for every variant (shz_warp_pair_hash_tf): warp v is
+    (tempos[v], pitches[v]), Q16, two lists of one length (warp_grid makes them from two ladders).  Returns (key32, t1,
+    hash_off) in the order query, warp, clip."""
+    from . import get_context
+    return (ctx or get_context()).warp_pair_hash_tf(peaks_f, peaks_t, peak_off, _check_speeds(tempos, "tempos"),
+                                                    _check_speeds(pitches, "pitches"), query_clip0, int(fan_value))
 
 
 def recognize_speeds(queries, db, speeds=None, Fs: int = 44100, topn: int = 2, resample_to: int = None):
@@ -100,3 +160,147 @@ def recognize_speeds(queries, db, speeds=None, Fs: int = 44100, topn: int = 2, r
     return results, {"fingerprint_time": ms[0] * 1e-3, "warp_time": ms[1] * 1e-3, "query_time": ms[2] * 1e-3,
                      "align_time": align_time, "n_hashes": res["nhash"], "speeds": sp, "speed_best": res["best"],
                      "speed_profile": res["profile"]}
+
+
+def _warp_dist(t16, f16):
+    return np.abs(t16.astype(np.int64) - S_ONE) + np.abs(f16.astype(np.int64) - S_ONE)
+
+
+def merge_warp_chunks(parts, t16, f16):
+    """The results of one set of queries over consecutive chunks of a pair list (Context.recognize_warps' res, in the list's
+    order), as one call over the whole list would give them: per query the chunk whose best variant has the greatest
+    rank-0 aligned count, ties to the smaller |t16 - 65536| + |f16 - 65536|, then to the lower index; the profiles side by
+    side."""
+    if len(parts) == 1:
+        return parts[0]
+    profile = np.concatenate([p["profile"] for p in parts], axis=1)
+    starts = np.cumsum([0] + [p["profile"].shape[1] for p in parts])
+    dist = _warp_dist(t16, f16)
+    out = {k: v.copy() for k, v in parts[0].items()}
+    out["profile"] = profile
+    for q in range(len(out["best"])):
+        cand = [int(starts[i] + p["best"][q]) for i, p in enumerate(parts)]
+        g = min(cand, key=lambda v: (-int(profile[q, v]), int(dist[v]), v))
+        i = cand.index(g)
+        for k in out:
+            if k not in ("profile", "best"):
+                out[k][q] = parts[i][k][q]
+        out["best"][q] = g
+    return out
+
+
+def _match_pairs(ctx, table, chans, first, t16, f16, row, Fs, resample_to, kw):
+    """Context.recognize_warps of the queries (chans: every channel, first: the CSR of the queries over them) over the
+    whole pair list, in chunks of whole rows: (res, [ms_extract, ms_warp, ms_match] summed over the chunks)."""
+    from . import _as_pcm, resample_to_device
+    buf = None
+    if resample_to is not None and int(resample_to) != int(Fs):   # resampled on the device and handed on there
+        buf, off = resample_to_device(chans, int(Fs), int(resample_to), ctx)
+        pcm, fs, dev = buf, int(resample_to), True
+    else:
+        arrs = [_as_pcm(c) for c in chans]
+        off = np.zeros(len(arrs) + 1, np.uint64)
+        if arrs:
+            off[1:] = np.cumsum([len(a) for a in arrs])
+        pcm, fs, dev = (np.concatenate(arrs) if off[-1] else np.zeros(1, np.int16)), int(Fs), False
+    parts, ms = [], np.zeros(3)
+    try:
+        for a, b in warp_chunks(len(t16), row):
+            res, m = ctx.recognize_warps(table, pcm, off, first, t16[a:b], f16[a:b], fs=fs, pcm_device=dev, **kw)
+            parts.append(res)
+            ms += m
+    finally:
+        if buf is not None:
+            buf.free()
+    return merge_warp_chunks(parts, t16, f16), ms
+
+
+def recognize_warps(queries, db, tempos=None, pitches=None, warps=None, search: str = "grid", Fs: int = 44100, topn: int = 2,
+                    resample_to: int = None):
+    """recognize_speeds for queries whose tempo and pitch changed by factors of their own.  Returns (results_per_query,
+    timings) like recognize_speeds; every result dict carries "tempo" and "pitch" (the chosen factors as floats: the query
+    runs `tempo` times as fast and sounds `pitch` times as high as the table's copy), OFFSET / OFFSET_SECS are in the
+    TABLE's time.  The variants:
+      tempos / pitches   two Q16 ladders (tempo_ladder, pitch_ladder); None means [65536]
+      warps=(t16, f16)   an explicit pair list instead of the two ladders (TypeError with either of them)
+      search="grid"      every pair of the two ladders (warp_grid, tempo-major).  More than 1,024 pairs go to the library in
+                         chunks of whole rows and are merged by the best-variant rule
+      search="separable" two library calls: the pitch ladder at tempo 65536, then the tempo ladder at every query's best
+                         pitch rung (queries that share a rung go together).  The answer is the second stage's.
+                         len(tempos) + len(pitches) variants instead of their product.  A HEURISTIC: it relies on the
+                         pitch axis being found while the tempo is still wrong, which holds while the first stage's top
+                         answer is the right song -- measured up to a tempo
+                         deviation of 5 %, where the first stage still named the right song with 106 .. 160 votes against
+                         452 .. 584 at the true pair, and 59 .. 92 against 253 .. 347 at (1.03, 0.97) / (0.97, 1.03); beyond that, or against a table in
+                         which a wrong song collects more votes than the drifting right one, it can miss what the grid finds.
+    The chosen pair is the one with the greatest aligned count; ties go to the smaller |t16 - 65536| + |f16 - 65536|, then to
+    the lower index.  timings carries "warps" (the two Q16 arrays of the pairs matched), "warp_best" (index per query) and
+    "warp_profile" (the aligned count of the top answer of every pair): [n_pairs] / [n_queries, n_pairs] for the grid and
+    for a pair list; for the separable search the pairs differ per query, and the three are those of the second stage --
+    "warps" two [n_queries, len(tempos)] arrays, "warp_profile" of that shape -- with the first stage under "stage1"
+    ("warps", "warp_best", "warp_profile")."""
+    from . import DEFAULT_AMP_MIN, DEFAULT_FAN_VALUE, _result_dicts
+    if not hasattr(db.table, "h"):
+        raise NotImplementedError("fused recognition takes the unsharded table (shards=1)")
+    if search not in ("grid", "separable"):
+        raise ValueError('search is "grid" or "separable"')
+    if warps is not None:
+        if tempos is not None or pitches is not None:
+            raise TypeError("warps= is an explicit pair list: it excludes tempos= and pitches=")
+        if search != "grid":
+            raise TypeError('search="separable" takes the two ladders, not a pair list')
+        t16, f16 = _check_speeds(warps[0], "warps[0]"), _check_speeds(warps[1], "warps[1]")
+        if len(t16) != len(f16):
+            raise ValueError("warps=(t16, f16): two lists of one length")
+        row = 1
+    else:
+        tl = np.asarray([S_ONE], np.uint32) if tempos is None else _check_speeds(tempos, "tempos")
+        pl = np.asarray([S_ONE], np.uint32) if pitches is None else _check_speeds(pitches, "pitches")
+        t16, f16 = warp_grid(tl, pl)
+        row = max(len(pl), 1)
+    ctx = db.ctx
+    if getattr(ctx, "hop", HOP) != HOP:
+        ctx.set_overlap(NFFT - HOP)
+    db.finalize()
+    per_query = [[q] if (isinstance(q, np.ndarray) and q.ndim == 1) else list(q) for q in queries]
+    nq = len(per_query)
+
+    def csr(idx):
+        chans, first = [], [0]
+        for q in idx:
+            chans.extend(per_query[q])
+            first.append(len(chans))
+        return chans, np.asarray(first, np.uint32)
+
+    kw = dict(amp_min=float(DEFAULT_AMP_MIN), fan_value=DEFAULT_FAN_VALUE, topn=int(topn))
+    run = lambda idx, a, b, r: _match_pairs(ctx, db.table, *csr(idx), a, b, r, Fs, resample_to, kw)
+    extra = {}
+    if search == "grid":
+        res, ms = run(range(nq), t16, f16, row)
+        q_t16, q_f16 = t16[res["best"]], f16[res["best"]]
+        shown = (t16, f16)
+    else:
+        one = np.full(len(pl), S_ONE, np.uint32)
+        res1, ms = run(range(nq), one, pl, 1)
+        extra["stage1"] = {"warps": (one, pl), "warp_best": res1["best"], "warp_profile": res1["profile"]}
+        res = {k: np.zeros((nq,) + v.shape[1:], v.dtype) for k, v in res1.items() if k != "profile"}
+        res["profile"] = np.zeros((nq, len(tl)), np.uint32)
+        for rung in np.unique(res1["best"]).tolist() if nq else []:
+            idx = np.flatnonzero(res1["best"] == rung).tolist()
+            part, m = run(idx, tl, np.full(len(tl), pl[rung], np.uint32), 1)
+            ms = ms + m
+            for k in res:
+                res[k][idx] = part[k]
+        q_t16, q_f16 = tl[res["best"]], pl[res1["best"]]
+        shown = (np.tile(tl, (nq, 1)), np.repeat(q_f16[:, None], len(tl), axis=1))
+    t0 = time()
+    results = []
+    for q in range(nq):
+        dicts = _result_dicts(db, res, q, int(res["nhash"][q]))
+        for d in dicts:
+            d["tempo"], d["pitch"] = float(q_t16[q]) / S_ONE, float(q_f16[q]) / S_ONE
+        results.append(dicts)
+    align_time = time() - t0
+    return results, {"fingerprint_time": ms[0] * 1e-3, "warp_time": ms[1] * 1e-3, "query_time": ms[2] * 1e-3,
+                     "align_time": align_time, "n_hashes": res["nhash"], "warps": shown, "warp_best": res["best"],
+                     "warp_profile": res["profile"], **extra}
