@@ -331,6 +331,22 @@ int32_t shz_table_lookup(shz_table* t, const uint32_t* keys, uint64_t n_keys,
                          uint32_t* key32, uint32_t* sid, uint32_t* off, uint64_t cap, uint64_t* count);
 /* distinct (hash, offset) rows of one song = songs.total_hashes candidates (__init__.py:381) */
 int32_t shz_table_song_rows(shz_table* t, uint32_t sid, uint64_t* n_rows);
+/* SELECT hash, offset FROM fingerprints WHERE song_id IN (sids): the rows of the listed songs, gathered on the device (the
+ * reference has no such statement; its schema, mysql_database.py:34-58, would answer it).  Song sids[i] owns the rows
+ * [row_off[i], row_off[i + 1]) of key32 / off, in list order (the list need not be sorted); inside a song the rows are
+ * ordered by (key32, offset) ascending -- UNIQUE(song_id, offset, hash): no two are equal, the result is one fixed
+ * sequence.  Rows come from every frozen segment and the active one.  A listed id without rows -- one above the table's
+ * largest included -- owns an empty range.  sids, row_off (n_sids + 1 entries): host.  key32 / off: host arrays of cap rows,
+ * device arrays with SHZ_SONGS_DEVICE_OUT, or BOTH NULL: counts only -- row_off is filled, no row is copied (the batched
+ * shz_table_song_rows).  The song-id column is the only one read in full (twice, 4 bytes a row); keys and offsets are read
+ * where a row hits; scratch grows with the hits and the listed ids, not with the table's rows (4 bytes per 1,024 rows).
+ * SHZ_E_STATE: staged or unsealed rows (as shz_table_song_rows).  SHZ_E_INVALID, before anything is launched: NULL table,
+ * NULL row_off, exactly one of key32 / off NULL, a song id listed twice.  SHZ_E_CAPACITY: more than cap rows -- row_off is
+ * filled all the same, row_off[n_sids] is the room the call needs.  SHZ_E_UNSUPPORTED: 2^32 rows or more in one call.
+ * n_sids == 0: SHZ_OK, row_off[0] = 0. */
+#define SHZ_SONGS_DEVICE_OUT 128u /* shz_table_song_hashes: key32 / off are device memory */
+int32_t shz_table_song_hashes(shz_table* t, const uint32_t* sids, uint32_t n_sids, uint64_t* row_off, uint32_t* key32,
+                              uint32_t* off, uint64_t cap, uint32_t flags);
 
 /* ---- match + align (replaces return_matches/align_matches, recognizer.py:222-338) ------- */
 /* Queries are CSR: query q owns (key32, q_off) pairs [query_off[q], query_off[q+1]); duplicate
@@ -415,6 +431,25 @@ int32_t shz_match_device_host(shz_ctx* ctx, shz_table* t, const uint32_t* key32,
                               const uint64_t* query_off, uint32_t n_queries, uint32_t topn, uint32_t flags, int64_t bias_bound,
                               uint32_t* out_sid, int32_t* out_delta, uint32_t* out_aligned, uint32_t* out_dedup,
                               uint32_t* out_nres, uint32_t* out_nhash, uint64_t* out_npairs);
+/* Which of the table's own songs are the same recording: every listed song matched against the REST of the table in one
+ * call, without its audio.  shz_table_song_hashes gathers the songs' rows on the device (song sids[q] is query q, its
+ * offsets are the query offsets), the library's match on device columns runs on them with topn + 1 and the table's largest
+ * offset as the bound of the query offsets, and the song itself is taken out of its own list on the host.  That is exact:
+ * rows are unique per (hash, song, offset), so for one delta a query row pairs with at most one row of any song -- no song's
+ * aligned count exceeds the query's row count, which the song itself reaches at delta 0.  Among the topn + 1 results it is
+ * dropped and the exact top topn of the others remain; where it is missing (more than topn other songs tie with it and carry
+ * smaller ids) the first topn are that list already.  Outputs (host): the seven arrays of shz_match_batch for "every other
+ * song", same shapes and meaning ([n_sids * topn] / [n_sids], zero past out_nres), and out_rows[n_sids] (may be NULL), the
+ * songs' row counts.  out_nhash equals out_rows (a song's rows are distinct).  out_npairs is what the match counts: the
+ * song's pairs with its own rows are included.  out_dedup of a result is the rows of that song under the listed song's
+ * hashes, as for any query.
+ * topn in [1, 63] and flags SHZ_MATCH_FULL_SORT only, a song id listed twice: SHZ_E_INVALID.  The match's refusals pass
+ * through (SHZ_E_STATE for a table that is not finalized; offsets >= 2^31 in the table); a listed song holding an offset
+ * >= 2^20 is SHZ_E_UNSUPPORTED -- it is a query offset here -- and 2^32 gathered rows or more in one call likewise (list
+ * fewer songs a call).  One table on one GPU: a key-sharded table has no call like it. */
+int32_t shz_match_songs(shz_ctx* ctx, shz_table* t, const uint32_t* sids, uint32_t n_sids, uint32_t topn, uint32_t flags,
+                        uint64_t* out_rows, uint32_t* out_sid, int32_t* out_delta, uint32_t* out_aligned, uint32_t* out_dedup,
+                        uint32_t* out_nres, uint32_t* out_nhash, uint64_t* out_npairs);
 /* rows streamed / pairs voted by the last shz_match_batch (for HBM accounting) */
 int32_t shz_match_stats(shz_ctx* ctx, uint64_t* rows_scanned, uint64_t* pairs, uint64_t* distinct_keys);
 

@@ -12,6 +12,7 @@ LIB_PATH = os.environ.get("SHZ_LIB") or os.path.join(_HERE, "libshz.so")  # SHZ_
 
 OK, E_INVALID, E_HIP, E_CAPACITY, E_NOMEM, E_UNSUPPORTED, E_RCCL, E_STATE = 0, -1, -2, -3, -4, -5, -6, -7
 PCM_DEVICE, OUT_DEVICE, IN_DEVICE, STFT_POWER, MATCH_FULL_SORT, RESERVE_GATHER, RESERVE_WAIT = 1, 2, 4, 8, 16, 32, 64
+SONGS_DEVICE_OUT = 128   # shz_table_song_hashes: key32 / off are device memory
 # shz_set_debug test switches (include/shz.h); RUN_ROWS_MAX[_SMALL]: the most rows a run / a segment cut from runs holds
 DEBUG_VT_TINY_HEAVY, DEBUG_VT_PROBE1, DEBUG_RUN_LIMIT_SMALL, DEBUG_SCAN_SMALL_GROUPS = 1, 2, 4, 8
 DEBUG_SPEED_SMALL_SLICES = 16   # shz_recognize_speeds: at most 2 queries a slice
@@ -91,6 +92,8 @@ SIGNATURES = {
     "shz_table_export": (C.c_int32, [vp, vp, vp, vp, C.c_uint64, u64p]),
     "shz_table_lookup": (C.c_int32, [vp, vp, C.c_uint64, vp, vp, vp, C.c_uint64, u64p]),
     "shz_table_song_rows": (C.c_int32, [vp, C.c_uint32, u64p]),
+    "shz_table_song_hashes": (C.c_int32, [vp, vp, C.c_uint32, u64p, vp, vp, C.c_uint64, C.c_uint32]),
+    "shz_match_songs": (C.c_int32, [vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp]),
     "shz_match_batch": (C.c_int32, [vp, vp, vp, vp, u64p, C.c_uint32, C.c_uint32, C.c_uint32,
                                     vp, vp, vp, vp, vp, vp, vp]),
     "shz_match_device_host": (C.c_int32, [vp, vp, vp, vp, u64p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int64,
@@ -1051,6 +1054,32 @@ class Table:
         n = C.c_uint64()
         self.ctx.check(lib().shz_table_song_rows(self.h, int(sid), C.byref(n)))
         return n.value
+
+    def song_hashes(self, sids, counts_only=False):
+        """Rows of the listed songs (shz_table_song_hashes): (row_off, key32, off) -- song sids[i] owns the rows
+        [row_off[i], row_off[i + 1]), ordered by (key32, offset).  counts_only: row_off alone is filled (key32 / off come
+        back empty), no row is copied."""
+        a = np.ascontiguousarray(sids, np.uint32).reshape(-1)
+        ro = np.zeros(len(a) + 1, np.uint64)
+        empty = np.empty(0, np.uint32)
+        self.ctx.check(lib().shz_table_song_hashes(self.h, ptr(a), len(a), ro.ctypes.data_as(u64p), None, None, 0, 0))
+        n = int(ro[-1])
+        if counts_only or n == 0:
+            return ro, empty, empty.copy()
+        k, o = np.empty(n, np.uint32), np.empty(n, np.uint32)
+        self.ctx.check(lib().shz_table_song_hashes(self.h, ptr(a), len(a), ro.ctypes.data_as(u64p), ptr(k), ptr(o), n, 0))
+        return ro, k, o
+
+    def match_songs(self, sids, topn=5, full_sort=False):
+        """Every listed song matched against the rest of the table (shz_match_songs): the dict of match(), one query per
+        listed song with the song itself left out, plus "rows", the songs' row counts."""
+        a = np.ascontiguousarray(sids, np.uint32).reshape(-1)
+        res = _match_result(len(a), topn)
+        res["rows"] = np.zeros(len(a), np.uint64)
+        self.ctx.check(lib().shz_match_songs(self.ctx.h, self.h, ptr(a), len(a), topn, MATCH_FULL_SORT if full_sort else 0,
+                                             ptr(res["rows"]), ptr(res["sid"]), ptr(res["delta"]), ptr(res["aligned"]),
+                                             ptr(res["dedup"]), ptr(res["nres"]), ptr(res["nhash"]), ptr(res["npairs"])))
+        return res
 
     def finalize_runs(self, run_rows):
         """finalize() for staged rows that are consecutive blocks of run_rows[r] rows: every block is sorted on its own

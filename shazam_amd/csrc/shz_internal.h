@@ -92,6 +92,9 @@ enum {
   SHZ_WS_SP_WF, SHZ_WS_SP_WT,    // ... the warped, compacted peaks in output order
   SHZ_WS_SP_SEG,     // ... first kept peak of every (query, speed, clip) | hash_off | totals
   SHZ_WS_SP_KEY, SHZ_WS_SP_T1,   // ... the hashes of a pass between the warp and the match
+  SHZ_WS_CG_LIST,    // shz_catalog.hip: bitmap of the listed song ids | the list sorted | its slots | the list as given
+  SHZ_WS_CG_BLK,     // ... hits of every block of SG_ROWS rows, then their scan
+  SHZ_WS_CG_CNT,     // ... rows of every song id up to the largest listed | rows of every listed song | largest offset gathered
   SHZ_WS_COUNT
 };
 

@@ -178,6 +178,14 @@ class HipFingerprintDB:
         self.finalize()
         return self.table.match(key32, q_off, query_off, topn)
 
+    def find_duplicates(self, **kw):
+        """Duplicate, contained and overlapping tracks of this catalogue (shazam_amd/catalog.find_duplicates); one table
+        only: a key-sharded database has no song gather."""
+        if not hasattr(self.table, "h"):
+            raise NotImplementedError("find_duplicates takes the unsharded table (shards=1)")
+        from .catalog import find_duplicates
+        return find_duplicates(self, **kw)
+
     # ---- dump / load / export (checkpoint-resume of a long build; SURVEY 8f #2) ----------------------
     def save(self, path: str):
         """Write the table (sorted unique rows) and the songs dict to one .npz file."""
