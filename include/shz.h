@@ -623,6 +623,57 @@ int32_t shz_listeners_state(shz_listeners* L, uint32_t l, uint64_t* window_hashe
  * and before the first push there is nothing to read. */
 int32_t shz_listeners_window(shz_listeners* L, uint32_t l, uint32_t* key32, uint32_t* t1, uint32_t* q_off, uint64_t cap,
                              uint64_t* n);
+/* ---- listeners at a ladder: peak windows (new; a station that plays its songs a few percent fast is a live feed) ----------
+ * A warp acts on PEAKS (shz_warp_pair_hash_tf), so a window of hashes cannot be warped.  shz_listeners_create_peaks takes the
+ * arguments of shz_listeners_create and refuses what it refuses; the object it makes keeps, on the device and per channel, the
+ * settled peaks (f, t) of the channel's stream with t >= w0, in the stream's order (t ascending, f ascending).  w0 = max(0, H -
+ * window_frames), H the smallest settled horizon of the listener's channels (shz_listener_window).  No cut is made at H: a
+ * channel that runs ahead keeps its settled peaks.  The streams are exact, so channel c's window is the peaks of shz_peaks on
+ * the stream's whole signal with w0 <= t < H_c (after its end: every peak with t >= w0).
+ * The two kinds do not mix: shz_listeners_push and shz_listeners_window on a peak-window object, and shz_listeners_push_warps /
+ * _push_speeds / _peaks / _timing on a hash-window object, are SHZ_E_STATE and change nothing.  reset, destroy and state work
+ * on both; on a peak-window object shz_listeners_state reports as window_hashes the out_nhash of the last push's chosen
+ * variant (0 before any push and after a reset). */
+int32_t shz_listeners_create_peaks(shz_streams* s, shz_table* t, uint32_t n_listeners, uint32_t window_frames, shz_listeners** out);
+/* One shz_streams_push (pcm, chunk_off, end: per STREAM, as for shz_listeners_push), the newly settled peaks appended to the
+ * windows and the expired ones dropped on the device, then listener l at warp v = (tempo_q16[v], pitch_q16[v]) as one query:
+ * exactly the hashes shz_warp_pair_hash_tf yields for a query whose clips are l's channels, their peak lists the windows
+ * rebased to t - w0, at the streams' fan_value; query offsets are the warped t1'.  All n_listeners x n_warps queries go
+ * through the match, in slices of whole listeners cut as shz_recognize_warps cuts its queries (SHZ_DEBUG_SPEED_SMALL_SLICES:
+ * two listeners a slice); results do not depend on the slicing.  Outputs per listener as shz_recognize_warps' per query:
+ * out_best[n_listeners] the variant with the greatest rank-0 aligned count (ties: the smallest |t16 - 65536| + |f16 - 65536|,
+ * then the lower index), that variant's rows in out_sid / out_delta / out_aligned / out_dedup [n_listeners topn], out_nres,
+ * out_nhash (may be NULL), out_profile [n_listeners n_warps] (may be NULL), out_w0[n_listeners] (may be NULL).  out_delta is in
+ * the TABLE's frames: the song frame that lies at stream frame w0.  A listener without peaks in its window: nres = nhash = 0.
+ * An ended listener keeps its window and is matched again at this push's ladder: the ladder belongs to the push, not to the
+ * object, and a caller may narrow it once a station's speed is known.
+ * Refused before the streams are pushed, every stream and every window staying as it was: what shz_listeners_push refuses;
+ * n_warps of 0 or above 1024, a NULL table, a factor outside [32768, 131072] (SHZ_E_INVALID); flags other than SHZ_PCM_DEVICE |
+ * SHZ_MATCH_FULL_SORT; a largest warped time round((max_c H_c - w0 - 1) max tempo / 65536) >= 2^20 over the listeners, the
+ * query offsets of the match (SHZ_E_UNSUPPORTED; the horizons after the push follow from shz_stream_plan).
+ * NOT a bit-for-bit twin of shz_listeners_push at a ladder of {65536}: the hash windows hold the hashes the streams have
+ * emitted -- pending peaks have not paired yet, and a hash with t1 >= w0 stays whatever its partner -- while the peak
+ * windows pair the window's peaks among themselves.  The exact equivalence is with shz_warp_pair_hash_tf on the window's peaks
+ * (shz_listeners_peaks). */
+int32_t shz_listeners_push_warps(shz_listeners* L, const int16_t* pcm, const uint64_t* chunk_off, const uint32_t* end,
+                                 uint32_t topn, const uint32_t* tempo_q16, const uint32_t* pitch_q16, uint32_t n_warps,
+                                 uint32_t flags, uint32_t* out_best, uint32_t* out_sid, int32_t* out_delta, uint32_t* out_aligned,
+                                 uint32_t* out_dedup, uint32_t* out_nres, uint32_t* out_nhash, uint32_t* out_profile,
+                                 uint32_t* out_w0);
+/* shz_listeners_push_warps with the one table speed_q16 for time and frequency: a speed ladder (as shz_recognize_speeds is to
+ * shz_recognize_warps; what is refused about the ladder names n_speeds / speed) */
+int32_t shz_listeners_push_speeds(shz_listeners* L, const int16_t* pcm, const uint64_t* chunk_off, const uint32_t* end,
+                                  uint32_t topn, const uint32_t* speed_q16, uint32_t n_speeds, uint32_t flags, uint32_t* out_best,
+                                  uint32_t* out_sid, int32_t* out_delta, uint32_t* out_aligned, uint32_t* out_dedup,
+                                  uint32_t* out_nres, uint32_t* out_nhash, uint32_t* out_profile, uint32_t* out_w0);
+/* The window of channel `channel` of listener l (tests / tools): its peaks in the device's order, f and ABSOLUTE t, copied to
+ * the HOST arrays of cap entries each; *n = their number.  More than cap: SHZ_E_CAPACITY with *n = the number needed, nothing
+ * copied.  The call waits for the ctx stream and changes no state. */
+int32_t shz_listeners_peaks(shz_listeners* L, uint32_t l, uint32_t channel, uint16_t* f, uint32_t* t, uint64_t cap, uint64_t* n);
+/* Tools: ms (4 floats, may be NULL) = the hipEvent times of the last timed shz_listeners_push_warps -- the streams' push, the
+ * window kernels with their read-back, the warp, the match -- and pushes from now on are timed (enable != 0) or not.  Timing
+ * adds event waits to a push; it is off at creation. */
+int32_t shz_listeners_timing(shz_listeners* L, int32_t enable, float* ms);
 /* No GPU, no ctx (like shz_stream_plan): the window of a listener whose channels have settled[0 .. channels) frames:
  * *horizon = their minimum H, *w0 = max(0, H - window_frames). */
 int32_t shz_listener_window(const uint64_t* settled, uint32_t channels, uint32_t window_frames, uint64_t* horizon, uint64_t* w0);

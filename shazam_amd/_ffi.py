@@ -144,6 +144,13 @@ SIGNATURES = {
     "shz_listeners_reset": (C.c_int32, [vp, vp, C.c_uint32]),
     "shz_listeners_state": (C.c_int32, [vp, C.c_uint32, u64p, u64p]),
     "shz_listeners_window": (C.c_int32, [vp, C.c_uint32, vp, vp, vp, C.c_uint64, u64p]),
+    "shz_listeners_create_peaks": (C.c_int32, [vp, vp, C.c_uint32, C.c_uint32, C.POINTER(vp)]),
+    "shz_listeners_push_warps": (C.c_int32, [vp, vp, u64p, vp, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp,
+                                             vp, vp]),
+    "shz_listeners_push_speeds": (C.c_int32, [vp, vp, u64p, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp,
+                                              vp]),
+    "shz_listeners_peaks": (C.c_int32, [vp, C.c_uint32, C.c_uint32, vp, vp, C.c_uint64, u64p]),
+    "shz_listeners_timing": (C.c_int32, [vp, C.c_int32, vp]),
     "shz_listener_window": (C.c_int32, [u64p, C.c_uint32, C.c_uint32, u64p, u64p]),
     "shz_resample_i16": (C.c_int32, [vp, vp, u64p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.c_uint32,
                                      vp, u64p, C.c_uint64, u64p]),
@@ -1297,12 +1304,17 @@ def listener_window(settled, window_frames: int):
 
 class Listeners:
     """Device-resident listeners over a Streams object and a Table (shz_listeners_*): listener l = the adjacent streams
-    [l channels, (l + 1) channels); its window of settled hashes stays on the device between pushes."""
+    [l channels, (l + 1) channels); its window of settled hashes stays on the device between pushes.  peaks=True
+    (shz_listeners_create_peaks): the windows hold settled PEAKS per channel, and the pushes are push_warps / push_speeds --
+    every listener at every variant of a ladder; push / window are SHZ_E_STATE on it, as push_warps / push_speeds / peaks
+    are without it."""
 
-    def __init__(self, streams: Streams, table: Table, n_listeners: int, window_frames: int):
+    def __init__(self, streams: Streams, table: Table, n_listeners: int, window_frames: int, peaks: bool = False):
         self.ctx, self.streams, self.table, self.h, self.n = streams.ctx, streams, table, None, int(n_listeners)
+        self.peak_windows = bool(peaks)
         h = vp()
-        self.ctx.check(lib().shz_listeners_create(streams.h, table.h, self.n, int(window_frames), C.byref(h)))
+        create = lib().shz_listeners_create_peaks if peaks else lib().shz_listeners_create
+        self.ctx.check(create(streams.h, table.h, self.n, int(window_frames), C.byref(h)))
         self.h = h
 
     def close(self):
@@ -1361,3 +1373,68 @@ class Listeners:
         if cnt:
             self.ctx.check(lib().shz_listeners_window(self.h, int(l), ptr(k), ptr(t), ptr(q), cnt, C.byref(n)))
         return k, t, q
+
+    def _cat(self, chunks):
+        assert len(chunks) == self.streams.n
+        arrs = [np.zeros(0, np.int16) if c is None else np.ascontiguousarray(c, np.int16) for c in chunks]
+        off = np.zeros(self.streams.n + 1, np.uint64)
+        off[1:] = np.cumsum([len(a) for a in arrs])
+        return (np.concatenate(arrs) if off[-1] else np.zeros(1, np.int16)), off
+
+    def push_warps_raw(self, pcm, chunk_off, tempos, pitches=None, end=None, topn=2, pcm_device=False, full_sort=False):
+        """One shz_listeners_push_warps as it is (pitches=None: shz_listeners_push_speeds with the ladder `tempos`): (rc, res,
+        w0) with res as Context.recognize_warps' over the listeners -- the best variant's rows, best [n] and profile
+        [n, n_warps].  tempos / pitches: Q16."""
+        co = np.ascontiguousarray(chunk_off, np.uint64)
+        assert len(co) == self.streams.n + 1
+        ew = self.streams._end_bits(end)
+        tq = np.ascontiguousarray(tempos, np.uint32)
+        fq = None if pitches is None else np.ascontiguousarray(pitches, np.uint32)
+        if tq.ndim != 1 or (fq is not None and fq.shape != tq.shape):
+            raise ValueError("tempos and pitches are two lists of one length: warp v is (tempos[v], pitches[v])")
+        res, w0 = _match_result(self.n, topn), np.zeros(self.n, np.uint32)
+        del res["npairs"]
+        res["best"], res["profile"] = np.zeros(self.n, np.uint32), np.zeros((self.n, len(tq)), np.uint32)
+        flags = (PCM_DEVICE if pcm_device else 0) | (MATCH_FULL_SORT if full_sort else 0)
+        outs = [ptr(res[k]) for k in ("best", "sid", "delta", "aligned", "dedup", "nres", "nhash", "profile")] + [ptr(w0)]
+        if fq is None:
+            rc = lib().shz_listeners_push_speeds(self.h, ptr(pcm), co.ctypes.data_as(u64p), ptr(ew), int(topn), ptr(tq), len(tq),
+                                                 flags, *outs)
+        else:
+            rc = lib().shz_listeners_push_warps(self.h, ptr(pcm), co.ctypes.data_as(u64p), ptr(ew), int(topn), ptr(tq), ptr(fq),
+                                                len(tq), flags, *outs)
+        return rc, res, w0
+
+    def push_warps(self, chunks, tempo, pitch, end=None, topn=2):
+        """chunks / end as for push; warp v is (tempo[v], pitch[v]), Q16.  Returns (res, w0)."""
+        pcm, off = self._cat(chunks)
+        rc, res, w0 = self.push_warps_raw(pcm, off, tempo, pitch, end, topn)
+        self.ctx.check(rc)
+        return res, w0
+
+    def push_speeds(self, chunks, ladder, end=None, topn=2):
+        """push_warps at a speed ladder: the one Q16 table for time and frequency.  Returns (res, w0)."""
+        pcm, off = self._cat(chunks)
+        rc, res, w0 = self.push_warps_raw(pcm, off, ladder, None, end, topn)
+        self.ctx.check(rc)
+        return res, w0
+
+    def peaks(self, l: int, channel: int = 0):
+        """(f, t) of the peak window of channel `channel` of listener l, t in absolute frames of the stream, in the order the
+        device keeps them (shz_listeners_peaks).  For tests and tools."""
+        n = C.c_uint64()
+        rc = lib().shz_listeners_peaks(self.h, int(l), int(channel), None, None, 0, C.byref(n))
+        if rc != E_CAPACITY:
+            self.ctx.check(rc)
+        cnt = int(n.value)
+        f, t = np.zeros(cnt, np.uint16), np.zeros(cnt, np.uint32)
+        if cnt:
+            self.ctx.check(lib().shz_listeners_peaks(self.h, int(l), int(channel), ptr(f), ptr(t), cnt, C.byref(n)))
+        return f, t
+
+    def timing(self, enable: bool = True):
+        """(streams, window, warp, match) ms of the last timed push_warps / push_speeds; pushes from now on are timed or
+        not (shz_listeners_timing).  For tools."""
+        ms = (C.c_float * 4)()
+        self.ctx.check(lib().shz_listeners_timing(self.h, 1 if enable else 0, ms))
+        return tuple(float(x) for x in ms)

@@ -285,6 +285,16 @@ int32_t sp_count(shz_ctx* ctx, const uint16_t* d_pf, const uint32_t* d_pt, const
                  const uint32_t* clip0, uint32_t q0, uint32_t nq, const uint32_t* d_tempo, const uint32_t* d_pitch, uint32_t K,
                  uint32_t fan, sp_pass* P, uint64_t* hash_off);
 int32_t sp_write(shz_ctx* ctx, const sp_pass& P, uint32_t* d_key, uint32_t* d_t1, uint64_t cap);
+// steps 2-4 of shz_recognize_warps on peaks that lie on the device -- slices of whole queries (the 2^28-pair budget, 1/8 of the
+// workspace limit; SHZ_DEBUG_SPEED_SMALL_SLICES), sp_count / sp_write, shz_match_device on all (query, warp) pairs of a slice,
+// sp_best -- shared with the peak-window listeners (shz_stream.hip).  peak_off: host CSR from 0 over n_clips clips; t_max: the
+// largest warped time (the match's bias bound); flags: SHZ_MATCH_FULL_SORT; out_nhash / out_profile may be NULL; timed:
+// ms_warp / ms_match (may be NULL) get the two stages' hipEvent times
+int32_t sp_match_fold(shz_ctx* ctx, shz_table* t, const uint16_t* d_pf, const uint32_t* d_pt, const uint64_t* peak_off,
+                      uint32_t n_clips, const uint32_t* query_clip0, uint32_t n_queries, uint32_t fan_value, uint32_t topn,
+                      const uint32_t* tempo_q16, const uint32_t* pitch_q16, uint32_t K, uint32_t flags, uint64_t t_max,
+                      uint32_t* out_best, uint32_t* out_sid, int32_t* out_delta, uint32_t* out_aligned, uint32_t* out_dedup,
+                      uint32_t* out_nres, uint32_t* out_nhash, uint32_t* out_profile, bool timed, float* ms_warp, float* ms_match);
 // what every entry point with a ladder refuses about it.  n_name: the count's argument ("n_speeds"); t_name / f_name: what a
 // factor of either table is called ("speed", or "tempo" and "pitch"; the table's argument is <name>_q16).  pitch_q16 ==
 // tempo_q16 is one ladder: it is checked, and named, once

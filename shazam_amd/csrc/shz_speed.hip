@@ -447,6 +447,95 @@ int32_t sp_peaks_owned(shz_ctx* ctx, const char* who, const int16_t* pcm, const 
   return SHZ_OK;
 }
 
+// Steps 2-4 of a recognition at a ladder, for peaks that lie on the device (shz_recognize_warps after its extraction; the
+// peak-window listeners, shz_stream.hip): the K warps of every query warped, paired and hashed (sp_count / sp_write), all
+// (query, warp) pairs matched as queries of their own, the best variant of every query folded out (sp_best).  d_pf / d_pt:
+// the peaks of n_clips clips, peak_off their CSR from 0 (host); query q is the clips [query_clip0[q], query_clip0[q + 1]).
+// t_max: the largest warped time, the bias bound of the match.  flags: SHZ_MATCH_FULL_SORT.  out_nhash / out_profile may be
+// NULL.  timed: ms_warp / ms_match (may be NULL) get the hipEvent times of the two stages, summed over the slices
+int32_t sp_match_fold(shz_ctx* ctx, shz_table* t, const uint16_t* d_pf, const uint32_t* d_pt, const uint64_t* peak_off,
+                      uint32_t n_clips, const uint32_t* query_clip0, uint32_t n_queries, uint32_t fan_value, uint32_t topn,
+                      const uint32_t* tempo_q16, const uint32_t* pitch_q16, uint32_t K, uint32_t flags, uint64_t t_max,
+                      uint32_t* out_best, uint32_t* out_sid, int32_t* out_delta, uint32_t* out_aligned, uint32_t* out_dedup,
+                      uint32_t* out_nres, uint32_t* out_nhash, uint32_t* out_profile, bool timed, float* ms_warp, float* ms_match) {
+  if (timed)
+    for (hipEvent_t& e : ctx->sp_ev)
+      if (!e) SHZ_HIP(ctx, hipEventCreate(&e));
+  const uint64_t* d_poff;
+  const uint32_t *d_tempo, *d_pitch;
+  SHZ_TRY(sp_upload_tables(ctx, peak_off, n_clips, tempo_q16, pitch_q16, K, &d_poff, &d_tempo, &d_pitch));
+  // 2) slices of whole queries: the entries a slice can yield at most (every peak with all its partners, at every factor)
+  // stay within the match's pair budget and 1/8 of the workspace limit.  A query is never split: one beyond that is a
+  // slice of its own
+  const uint64_t per_item = std::max<uint32_t>(fan_value - 1, 1);
+  const uint64_t max_entries = std::min<uint64_t>(std::max<uint64_t>(ctx->ws_limit / 64, 1), 1ull << 28);
+  const uint32_t max_q = (ctx->debug & SHZ_DEBUG_SPEED_SMALL_SLICES) ? SP_SMALL_SLICE : (1u << 24) / K;
+  const uint64_t nv = (uint64_t)n_queries * K;
+  std::vector<uint32_t> v_sid(nv * topn), v_aligned(nv * topn), v_dedup(nv * topn), v_nres(nv), v_nhash(nv);
+  std::vector<int32_t> v_delta(nv * topn);
+  std::vector<uint64_t> ho, query_off;
+  float warp_ms = 0.f, match_ms = 0.f;
+  for (uint32_t q0 = 0; q0 < n_queries;) {
+    uint32_t nq = 1;
+    while (q0 + nq < n_queries && nq < max_q &&
+           sp_items(peak_off, query_clip0, q0, nq + 1, K) * per_item <= max_entries)
+      ++nq;
+    if (timed) SHZ_HIP(ctx, hipEventRecord(ctx->sp_ev[2], ctx->stream));
+    const uint64_t n_seg = (uint64_t)(query_clip0[q0 + nq] - query_clip0[q0]) * K;
+    ho.assign((size_t)n_seg + 1, 0);
+    sp_pass P;
+    SHZ_TRY(sp_count(ctx, d_pf, d_pt, d_poff, peak_off, query_clip0, q0, nq, d_tempo, d_pitch, K,
+                     fan_value, &P, ho.data()));
+    const uint64_t total = ho[n_seg];
+    void *d_key, *d_t1;
+    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SP_KEY, total * 4 + 64, &d_key));
+    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SP_T1, total * 4 + 64, &d_t1));
+    if (total) SHZ_TRY(sp_write(ctx, P, (uint32_t*)d_key, (uint32_t*)d_t1, total));
+    if (timed) SHZ_HIP(ctx, hipEventRecord(ctx->sp_ev[3], ctx->stream));
+    // 3) (query, speed) = one query of the match: the segments of its channels lie one behind the other
+    const uint64_t nvq = (uint64_t)nq * K;
+    query_off.resize((size_t)nvq + 1);
+    for (uint32_t q = 0; q < nq; ++q) {
+      const uint64_t e0 = (uint64_t)(query_clip0[q0 + q] - query_clip0[q0]) * K, nch = query_clip0[q0 + q + 1] - query_clip0[q0 + q];
+      for (uint32_t v = 0; v < K; ++v) query_off[(size_t)q * K + v] = ho[e0 + v * nch];
+    }
+    query_off[nvq] = total;
+    const uint64_t o = (uint64_t)q0 * K;
+    SHZ_TRY(shz_match_device(ctx, t, (const uint32_t*)d_key, (const uint32_t*)d_t1, query_off.data(), (uint32_t)nvq, topn,
+                             flags & SHZ_MATCH_FULL_SORT, (int64_t)t_max, v_sid.data() + o * topn, v_delta.data() + o * topn,
+                             v_aligned.data() + o * topn, v_dedup.data() + o * topn, v_nres.data() + o, v_nhash.data() + o, nullptr));
+    if (timed) {
+      float a = 0.f, b = 0.f;
+      SHZ_HIP(ctx, hipEventRecord(ctx->sp_ev[4], ctx->stream));
+      SHZ_HIP(ctx, hipEventSynchronize(ctx->sp_ev[4]));
+      SHZ_HIP(ctx, hipEventElapsedTime(&a, ctx->sp_ev[2], ctx->sp_ev[3]));
+      SHZ_HIP(ctx, hipEventElapsedTime(&b, ctx->sp_ev[3], ctx->sp_ev[4]));
+      warp_ms += a;
+      match_ms += b;
+    }
+    q0 += nq;
+  }
+  if (ms_warp) *ms_warp = warp_ms;
+  if (ms_match) *ms_match = match_ms;
+  // 4) the best variant of every query
+  std::vector<uint32_t> top1(K);
+  for (uint32_t q = 0; q < n_queries; ++q) {
+    const uint64_t o = (uint64_t)q * K;
+    for (uint32_t v = 0; v < K; ++v) top1[v] = v_nres[o + v] ? v_aligned[(o + v) * topn] : 0u;
+    if (out_profile) memcpy(out_profile + o, top1.data(), (size_t)K * 4);
+    const uint32_t b = sp_best(top1.data(), tempo_q16, pitch_q16, K);
+    const uint64_t src = (o + b) * topn, dst = (uint64_t)q * topn;
+    out_best[q] = b;
+    memcpy(out_sid + dst, v_sid.data() + src, (size_t)topn * 4);
+    memcpy(out_delta + dst, v_delta.data() + src, (size_t)topn * 4);
+    memcpy(out_aligned + dst, v_aligned.data() + src, (size_t)topn * 4);
+    memcpy(out_dedup + dst, v_dedup.data() + src, (size_t)topn * 4);
+    out_nres[q] = v_nres[o + b];
+    if (out_nhash) out_nhash[q] = v_nhash[o + b];
+  }
+  return SHZ_OK;
+}
+
 extern "C" int32_t shz_recognize_warps(shz_ctx* ctx, shz_table* t, const int16_t* pcm, const uint64_t* clip_off, uint32_t n_clips,
                                        const uint32_t* query_clip0, uint32_t n_queries, uint32_t fs, double amp_min,
                                        uint32_t fan_value, uint32_t topn, const uint32_t* tempo_q16, const uint32_t* pitch_q16,
@@ -496,79 +585,11 @@ extern "C" int32_t shz_recognize_warps(shz_ctx* ctx, shz_table* t, const int16_t
   SHZ_TRY(sp_peaks_owned(ctx, "shz_recognize_warps", pcm, clip_off, n_clips, frames, fs, amp_min, flags & SHZ_PCM_DEVICE,
                          peak_off.data(), &d_pf, &d_pt));
   if (timed) SHZ_HIP(ctx, hipEventRecord(ctx->sp_ev[1], ctx->stream));
-  const uint64_t* d_poff;
-  const uint32_t *d_tempo, *d_pitch;
-  SHZ_TRY(sp_upload_tables(ctx, peak_off.data(), n_clips, tempo_q16, pitch_q16, K, &d_poff, &d_tempo, &d_pitch));
-  // 2) slices of whole queries: the entries a slice can yield at most (every peak with all its partners, at every factor)
-  // stay within the match's pair budget and 1/8 of the workspace limit.  A query is never split: one beyond that is a
-  // slice of its own
-  const uint64_t per_item = std::max<uint32_t>(fan_value - 1, 1);
-  const uint64_t max_entries = std::min<uint64_t>(std::max<uint64_t>(ctx->ws_limit / 64, 1), 1ull << 28);
-  const uint32_t max_q = (ctx->debug & SHZ_DEBUG_SPEED_SMALL_SLICES) ? SP_SMALL_SLICE : (1u << 24) / K;
-  const uint64_t nv = (uint64_t)n_queries * K;
-  std::vector<uint32_t> v_sid(nv * topn), v_aligned(nv * topn), v_dedup(nv * topn), v_nres(nv), v_nhash(nv);
-  std::vector<int32_t> v_delta(nv * topn);
-  std::vector<uint64_t> ho, query_off;
-  float warp_ms = 0.f, match_ms = 0.f;
-  for (uint32_t q0 = 0; q0 < n_queries;) {
-    uint32_t nq = 1;
-    while (q0 + nq < n_queries && nq < max_q &&
-           sp_items(peak_off.data(), query_clip0, q0, nq + 1, K) * per_item <= max_entries)
-      ++nq;
-    if (timed) SHZ_HIP(ctx, hipEventRecord(ctx->sp_ev[2], ctx->stream));
-    const uint64_t n_seg = (uint64_t)(query_clip0[q0 + nq] - query_clip0[q0]) * K;
-    ho.assign((size_t)n_seg + 1, 0);
-    sp_pass P;
-    SHZ_TRY(sp_count(ctx, d_pf, d_pt, d_poff, peak_off.data(), query_clip0, q0, nq, d_tempo, d_pitch, K,
-                     fan_value, &P, ho.data()));
-    const uint64_t total = ho[n_seg];
-    void *d_key, *d_t1;
-    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SP_KEY, total * 4 + 64, &d_key));
-    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SP_T1, total * 4 + 64, &d_t1));
-    if (total) SHZ_TRY(sp_write(ctx, P, (uint32_t*)d_key, (uint32_t*)d_t1, total));
-    if (timed) SHZ_HIP(ctx, hipEventRecord(ctx->sp_ev[3], ctx->stream));
-    // 3) (query, speed) = one query of the match: the segments of its channels lie one behind the other
-    const uint64_t nvq = (uint64_t)nq * K;
-    query_off.resize((size_t)nvq + 1);
-    for (uint32_t q = 0; q < nq; ++q) {
-      const uint64_t e0 = (uint64_t)(query_clip0[q0 + q] - query_clip0[q0]) * K, nch = query_clip0[q0 + q + 1] - query_clip0[q0 + q];
-      for (uint32_t v = 0; v < K; ++v) query_off[(size_t)q * K + v] = ho[e0 + v * nch];
-    }
-    query_off[nvq] = total;
-    const uint64_t o = (uint64_t)q0 * K;
-    SHZ_TRY(shz_match_device(ctx, t, (const uint32_t*)d_key, (const uint32_t*)d_t1, query_off.data(), (uint32_t)nvq, topn,
-                             flags & SHZ_MATCH_FULL_SORT, (int64_t)t_max, v_sid.data() + o * topn, v_delta.data() + o * topn,
-                             v_aligned.data() + o * topn, v_dedup.data() + o * topn, v_nres.data() + o, v_nhash.data() + o, nullptr));
-    if (timed) {
-      float a = 0.f, b = 0.f;
-      SHZ_HIP(ctx, hipEventRecord(ctx->sp_ev[4], ctx->stream));
-      SHZ_HIP(ctx, hipEventSynchronize(ctx->sp_ev[4]));
-      SHZ_HIP(ctx, hipEventElapsedTime(&a, ctx->sp_ev[2], ctx->sp_ev[3]));
-      SHZ_HIP(ctx, hipEventElapsedTime(&b, ctx->sp_ev[3], ctx->sp_ev[4]));
-      warp_ms += a;
-      match_ms += b;
-    }
-    q0 += nq;
-  }
+  // 2-4) warped, hashed, matched in slices of whole queries; the best variant of every query
+  SHZ_TRY(sp_match_fold(ctx, t, d_pf, d_pt, peak_off.data(), n_clips, query_clip0, n_queries, fan_value, topn, tempo_q16, pitch_q16,
+                        K, flags & SHZ_MATCH_FULL_SORT, t_max, out_best, out_sid, out_delta, out_aligned, out_dedup, out_nres,
+                        out_nhash, out_profile, timed, ms_warp, ms_match));
   if (timed && ms_extract) SHZ_HIP(ctx, hipEventElapsedTime(ms_extract, ctx->sp_ev[0], ctx->sp_ev[1]));
-  if (ms_warp) *ms_warp = warp_ms;
-  if (ms_match) *ms_match = match_ms;
-  // 4) the best variant of every query
-  std::vector<uint32_t> top1(K);
-  for (uint32_t q = 0; q < n_queries; ++q) {
-    const uint64_t o = (uint64_t)q * K;
-    for (uint32_t v = 0; v < K; ++v) top1[v] = v_nres[o + v] ? v_aligned[(o + v) * topn] : 0u;
-    if (out_profile) memcpy(out_profile + o, top1.data(), (size_t)K * 4);
-    const uint32_t b = sp_best(top1.data(), tempo_q16, pitch_q16, K);
-    const uint64_t src = (o + b) * topn, dst = (uint64_t)q * topn;
-    out_best[q] = b;
-    memcpy(out_sid + dst, v_sid.data() + src, (size_t)topn * 4);
-    memcpy(out_delta + dst, v_delta.data() + src, (size_t)topn * 4);
-    memcpy(out_aligned + dst, v_aligned.data() + src, (size_t)topn * 4);
-    memcpy(out_dedup + dst, v_dedup.data() + src, (size_t)topn * 4);
-    out_nres[q] = v_nres[o + b];
-    if (out_nhash) out_nhash[q] = v_nhash[o + b];
-  }
   return SHZ_OK;
 }
 

@@ -48,11 +48,18 @@ struct st_job {
 };
 
 // per-job results the write kernel and the host read: [0] = total hashes (u64, by the scan); then h[J] u64, e[J] u32,
-// m[J] u32, kl[J] u32
+// m[J] u32, kl[J] u32, kh[J] u32
 struct st_ctl_view {
   unsigned long long* total;
   uint64_t* h;
-  uint32_t *e, *m, *kl;
+  uint32_t *e, *m, *kl, *kh;
+};
+
+// where the peaks that a push settled lie, per stream, for the peak-window listeners (internal: not on the ABI): pf / pt of
+// the object at [at, at + n), frames relative to w0.  Valid from a push that succeeded until the next call on the streams
+struct st_hand {
+  uint64_t at;
+  uint32_t n, w0;
 };
 
 struct shz_streams {
@@ -68,6 +75,7 @@ struct shz_streams {
   std::vector<uint8_t> ended, par_tail, par_pend;
   shz_buf win, pf, pt, pcm, jobs, poff, ctl, offs, ok, ot;   // grow-only device scratch of the object
   uint64_t peak_cap = 0;                   // peak list capacity the windows needed so far
+  std::vector<st_hand> hand;               // the last push's newly settled peaks (n = 0: none)
 };
 
 // ---- kernels -------------------------------------------------------------------------------------------------------
@@ -160,9 +168,9 @@ __global__ __launch_bounds__(ST_THREADS) void stream_count_kernel(const st_job* 
                                                                   const uint64_t* __restrict__ poff, st_ctl_view cv) {
   const uint32_t ji = blockIdx.x;
   const st_job j = jobs[ji];
-  __shared__ uint32_t s_kl, s_m, s_e, s_w[ST_THREADS / 64];
+  __shared__ uint32_t s_kl, s_kh, s_m, s_e, s_w[ST_THREADS / 64];
   if (!j.settle) {
-    if (threadIdx.x == 0) { cv.h[ji] = 0; cv.e[ji] = 0; cv.m[ji] = j.pend_n; cv.kl[ji] = 0; }
+    if (threadIdx.x == 0) { cv.h[ji] = 0; cv.e[ji] = 0; cv.m[ji] = j.pend_n; cv.kl[ji] = 0; cv.kh[ji] = 0; }
     return;
   }
   if (threadIdx.x == 0) {
@@ -191,6 +199,7 @@ __global__ __launch_bounds__(ST_THREADS) void stream_count_kernel(const st_job* 
       e = by_fan > by_dt ? by_fan : by_dt;
     }
     s_kl = kl;
+    s_kh = kh;
     s_m = m;
     s_e = e;
   }
@@ -209,6 +218,7 @@ __global__ __launch_bounds__(ST_THREADS) void stream_count_kernel(const st_job* 
     cv.e[ji] = e;
     cv.m[ji] = m;
     cv.kl[ji] = kl;
+    cv.kh[ji] = s_kh;
   }
 }
 
@@ -323,6 +333,7 @@ extern "C" int32_t shz_streams_create(shz_ctx* ctx, uint32_t n_streams, uint32_t
   s->ended.assign(n_streams, 0);
   s->par_tail.assign(n_streams, 0);
   s->par_pend.assign(n_streams, 0);
+  s->hand.assign(n_streams, st_hand{0, 0, 0});
   const uint64_t tb = 2ull * n_streams * s->tail_cap * 2, pb = 2ull * n_streams * ST_PEND;
   if (hipMalloc(&s->d_tail, tb) != hipSuccess || hipMalloc(&s->d_pend_f, pb * 2) != hipSuccess ||
       hipMalloc(&s->d_pend_t, pb * 4) != hipSuccess) {
@@ -388,6 +399,7 @@ extern "C" int32_t shz_streams_push(shz_streams* s, const int16_t* pcm, const ui
   if (count) *count = 0;
   if (!chunk_off || !hash_off || !count) SHZ_FAIL(ctx, SHZ_E_INVALID, "chunk_off, hash_off and count must not be NULL");
   const uint32_t n = s->n, hop = s->hop;
+  s->hand.assign(n, st_hand{0, 0, 0});
   for (uint32_t i = 0; i < n; ++i)
     if (chunk_off[i + 1] < chunk_off[i]) SHZ_FAIL(ctx, SHZ_E_INVALID, "chunk_off decreases at stream %u", i);
   const uint64_t in_total = chunk_off[n] - chunk_off[0];
@@ -509,13 +521,14 @@ extern "C" int32_t shz_streams_push(shz_streams* s, const int16_t* pcm, const ui
     if (j.settle) bound += ((uint64_t)j.pend_n + (j.win != ~0u ? poff[j.win + 1] - poff[j.win] : 0)) * (s->fan - 1);
   // 4) count, scan over the jobs, write
   const uint64_t c_h = 64, c_e = c_h + ((uint64_t)nj * 8 + 63) / 64 * 64, c_m = c_e + ((uint64_t)nj * 4 + 63) / 64 * 64,
-                 c_kl = c_m + ((uint64_t)nj * 4 + 63) / 64 * 64, c_bytes = c_kl + (uint64_t)nj * 4;
+                 c_kl = c_m + ((uint64_t)nj * 4 + 63) / 64 * 64, c_kh = c_kl + ((uint64_t)nj * 4 + 63) / 64 * 64,
+                 c_bytes = c_kh + (uint64_t)nj * 4;
   void *d_ctl, *d_offs;
   SHZ_TRY(st_reserve(ctx, s->ctl, c_bytes, &d_ctl));
   SHZ_TRY(st_reserve(ctx, s->offs, (uint64_t)nj * 8, &d_offs));
   char* cb = (char*)d_ctl;
   st_ctl_view cv{(unsigned long long*)cb, (uint64_t*)(cb + c_h), (uint32_t*)(cb + c_e), (uint32_t*)(cb + c_m),
-                 (uint32_t*)(cb + c_kl)};
+                 (uint32_t*)(cb + c_kl), (uint32_t*)(cb + c_kh)};
   const bool out_dev = (flags & SHZ_OUT_DEVICE) != 0;
   uint32_t *o_k = key32, *o_t = t1;
   uint64_t o_cap = cap;
@@ -536,10 +549,10 @@ extern "C" int32_t shz_streams_push(shz_streams* s, const int16_t* pcm, const ui
                      s->d_pend_f, s->d_pend_t, (const uint16_t*)d_pf, (const uint32_t*)d_pt, (const uint64_t*)d_poff, cv,
                      (const uint64_t*)d_offs, o_k, o_t, o_cap);
   SHZ_HIP(ctx, hipGetLastError());
-  // 5) one read-back: total, per-job hash counts, emitted prefixes and list lengths
+  // 5) one read-back: total, per-job hash counts, emitted prefixes, list lengths and settled ranges
   void* mailp;
-  SHZ_TRY(shz_mailbox(ctx, c_kl, &mailp));
-  SHZ_HIP(ctx, hipMemcpyAsync(mailp, d_ctl, c_kl, hipMemcpyDeviceToHost, ctx->stream));
+  SHZ_TRY(shz_mailbox(ctx, c_bytes, &mailp));
+  SHZ_HIP(ctx, hipMemcpyAsync(mailp, d_ctl, c_bytes, hipMemcpyDeviceToHost, ctx->stream));
   SHZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
   const char* mb = (const char*)mailp;
   const uint64_t total = *(const uint64_t*)mb;
@@ -549,7 +562,8 @@ extern "C" int32_t shz_streams_push(shz_streams* s, const int16_t* pcm, const ui
   if (total > cap)
     SHZ_FAIL(ctx, SHZ_E_CAPACITY, "output needs %llu entries, capacity %llu", (unsigned long long)total, (unsigned long long)cap);
   const uint64_t* hh = (const uint64_t*)(mb + c_h);
-  const uint32_t *ee = (const uint32_t*)(mb + c_e), *mm = (const uint32_t*)(mb + c_m);
+  const uint32_t *ee = (const uint32_t*)(mb + c_e), *mm = (const uint32_t*)(mb + c_m), *kkl = (const uint32_t*)(mb + c_kl),
+                 *kkh = (const uint32_t*)(mb + c_kh);
   std::vector<uint64_t> per(n, 0);
   for (uint32_t k = 0; k < nj; ++k) per[jobs[k].stream] = hh[k];
   if (!out_dev && total) {
@@ -569,6 +583,8 @@ extern "C" int32_t shz_streams_push(shz_streams* s, const int16_t* pcm, const ui
       s->pending[i] = mm[k] - ee[k];
       s->emitted[i] += hh[k];
       s->par_pend[i] ^= 1u;
+      if (j.win != ~0u && kkh[k] >= kkl[k] && poff[j.win] + kkh[k] <= poff[j.win + 1])
+        s->hand[i] = st_hand{poff[j.win] + kkl[k], kkh[k] - kkl[k], j.w0};
     }
     if (j.ending) s->ended[i] = 1;
   }
@@ -606,6 +622,14 @@ struct shz_listeners {
   shz_buf nk, nt;                  // the hashes of a push
   uint64_t new_cap = 0;            // entries nk / nt hold
   shz_buf qo, jobs, ctl;           // query offsets; ls_job per listener; total | counts | offsets
+  // peak windows (shz_listeners_create_peaks): per STREAM, the settled peaks with t >= w0 of its listener
+  bool peaks = false;
+  shz_buf pf[2], pt[2], pr;        // the two slots of (f, absolute t); the times t - w0 beside the current slot
+  std::vector<uint64_t> p_at;      // per stream: its window in the current slot
+  std::vector<uint32_t> p_n, last_nhash;   // ...; per listener: out_nhash of the last push's chosen variant
+  bool timed = false;              // shz_listeners_timing
+  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};   // push begun, streams done, windows done
+  float ms[4] = {0.f, 0.f, 0.f, 0.f};               // streams, window, warp, match of the last push
 };
 
 // entry i of a listener's old-then-new list and whether the window keeps it
@@ -679,8 +703,8 @@ __global__ __launch_bounds__(LS_THREADS) void listener_write_kernel(const ls_job
   }
 }
 
-extern "C" int32_t shz_listeners_create(shz_streams* s, shz_table* t, uint32_t n_listeners, uint32_t window_frames,
-                                        shz_listeners** out) {
+static int32_t ls_create(shz_streams* s, shz_table* t, uint32_t n_listeners, uint32_t window_frames, bool peaks,
+                         shz_listeners** out) {
   if (!s || !s->ctx || !out) return SHZ_E_INVALID;
   *out = nullptr;
   shz_ctx* ctx = s->ctx;
@@ -698,8 +722,22 @@ extern "C" int32_t shz_listeners_create(shz_streams* s, shz_table* t, uint32_t n
   L->w_at.assign(n_listeners, 0);
   L->w_n.assign(n_listeners, 0);
   L->w0.assign(n_listeners, 0);
+  L->peaks = peaks;
+  L->p_at.assign(s->n, 0);
+  L->p_n.assign(s->n, 0);
+  L->last_nhash.assign(n_listeners, 0);
   *out = L;
   return SHZ_OK;
+}
+
+extern "C" int32_t shz_listeners_create(shz_streams* s, shz_table* t, uint32_t n_listeners, uint32_t window_frames,
+                                        shz_listeners** out) {
+  return ls_create(s, t, n_listeners, window_frames, false, out);
+}
+
+extern "C" int32_t shz_listeners_create_peaks(shz_streams* s, shz_table* t, uint32_t n_listeners, uint32_t window_frames,
+                                              shz_listeners** out) {
+  return ls_create(s, t, n_listeners, window_frames, true, out);
 }
 
 extern "C" int32_t shz_listeners_destroy(shz_listeners* L) {
@@ -708,7 +746,11 @@ extern "C" int32_t shz_listeners_destroy(shz_listeners* L) {
     (void)hipSetDevice(L->ctx->device);
     (void)hipStreamSynchronize(L->ctx->stream);
   }
-  for (shz_buf* b : {&L->wk[0], &L->wk[1], &L->wt[0], &L->wt[1], &L->nk, &L->nt, &L->qo, &L->jobs, &L->ctl}) st_free(*b);
+  for (shz_buf* b : {&L->wk[0], &L->wk[1], &L->wt[0], &L->wt[1], &L->nk, &L->nt, &L->qo, &L->jobs, &L->ctl, &L->pf[0], &L->pf[1],
+                     &L->pt[0], &L->pt[1], &L->pr})
+    st_free(*b);
+  for (hipEvent_t e : L->ev)
+    if (e) (void)hipEventDestroy(e);
   delete L;
   return SHZ_OK;
 }
@@ -727,14 +769,17 @@ extern "C" int32_t shz_listeners_reset(shz_listeners* L, const uint32_t* which, 
   for (uint32_t i = 0; i < n; ++i)
     for (uint32_t c = 0; c < L->channels; ++c) streams.push_back(which[i] * L->channels + c);
   SHZ_TRY(shz_streams_reset(L->s, streams.data(), (uint32_t)streams.size()));
-  for (uint32_t i = 0; i < n; ++i) L->w_n[which[i]] = L->w0[which[i]] = 0;
+  for (uint32_t i = 0; i < n; ++i) {
+    L->w_n[which[i]] = L->w0[which[i]] = L->last_nhash[which[i]] = 0;
+    for (uint32_t c = 0; c < L->channels; ++c) L->p_n[(size_t)which[i] * L->channels + c] = 0;
+  }
   return SHZ_OK;
 }
 
 extern "C" int32_t shz_listeners_state(shz_listeners* L, uint32_t l, uint64_t* window_hashes, uint64_t* w0) {
   SHZ_TRY(ls_check(L));
   if (l >= L->n) SHZ_FAIL(L->ctx, SHZ_E_INVALID, "listener %u out of range (%u listeners)", l, L->n);
-  if (window_hashes) *window_hashes = L->w_n[l];
+  if (window_hashes) *window_hashes = L->peaks ? L->last_nhash[l] : L->w_n[l];
   if (w0) *w0 = L->w0[l];
   return SHZ_OK;
 }
@@ -747,6 +792,7 @@ extern "C" int32_t shz_listeners_window(shz_listeners* L, uint32_t l, uint32_t* 
   shz_ctx* ctx = L->ctx;
   if (l >= L->n) SHZ_FAIL(ctx, SHZ_E_INVALID, "listener %u out of range (%u listeners)", l, L->n);
   if (!n) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_listeners_window: n is NULL");
+  if (L->peaks) SHZ_FAIL(ctx, SHZ_E_STATE, "shz_listeners_window: the object keeps peak windows (shz_listeners_peaks)");
   const uint64_t at = L->w_at[l], cnt = L->w_n[l];
   *n = cnt;
   if (cnt > cap) SHZ_FAIL(ctx, SHZ_E_CAPACITY, "output needs %llu entries, capacity %llu", (unsigned long long)cnt, (unsigned long long)cap);
@@ -782,6 +828,7 @@ extern "C" int32_t shz_listeners_push(shz_listeners* L, const int16_t* pcm, cons
   shz_ctx* ctx = L->ctx;
   shz_streams* s = L->s;
   const uint32_t n = L->n, ch = L->channels;
+  if (L->peaks) SHZ_FAIL(ctx, SHZ_E_STATE, "shz_listeners_push: the object keeps peak windows (shz_listeners_push_warps)");
   // what the match would refuse is refused here, before any stream advances
   if (flags & ~(SHZ_PCM_DEVICE | SHZ_MATCH_FULL_SORT)) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_listeners_push: flags may hold SHZ_PCM_DEVICE and SHZ_MATCH_FULL_SORT");
   if (!out_sid || !out_delta || !out_aligned || !out_dedup || !out_nres) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_listeners_push: NULL buffer");
@@ -864,4 +911,287 @@ extern "C" int32_t shz_listeners_push(shz_listeners* L, const int16_t* pcm, cons
   return shz_match_device(ctx, L->t, (const uint32_t*)d_wk, (const uint32_t*)d_qo, query_off.data(), n, topn,
                           flags & SHZ_MATCH_FULL_SORT, (int64_t)bias, out_sid, out_delta, out_aligned, out_dedup, out_nres, out_nhash,
                           out_npairs);
+}
+
+// ---- listeners at a ladder: peak windows -----------------------------------------------------------------------------
+// A warp acts on peaks -- they move in integer coordinates, change order and pair anew (shz_speed.hip) -- so a window of
+// hashes cannot be warped.  A peak-window object keeps, per STREAM, the settled peaks (f, absolute t) with t >= w0 of its
+// listener, in the stream's order, in two packed slots as the hash windows are.  One push: the streams' push, which says where
+// every stream's newly settled peaks lie (st_hand); one small upload; peakwin_count_kernel, a scan over the streams,
+// peakwin_write_kernel -- kept old entries, then the new ones with their window clip's first frame added, compacted in order
+// into the OTHER slot, the times t - w0 beside them -- one read-back of the counts, which are the warp's peak_off; then every
+// (listener, warp) through sp_match_fold on the slot's f column and the rebased times.
+
+struct pk_job {
+  uint64_t old_at, new_at;   // first old entry in the current slot; first new entry in the streams' peak lists
+  uint32_t old_n, new_n;
+  uint32_t w0, add;          // the listener's window start; the first frame of the stream's window clip (new t + add is absolute)
+};
+
+// entry i of a stream's old-then-new list (absolute t) and whether the window keeps it
+__device__ __forceinline__ bool pk_entry(const pk_job& j, uint32_t i, const uint16_t* __restrict__ wf, const uint32_t* __restrict__ wt,
+                                         const uint16_t* __restrict__ nf, const uint32_t* __restrict__ nt, uint32_t* f, uint32_t* t) {
+  if (i >= j.old_n + j.new_n) return false;
+  if (i < j.old_n) {
+    *t = wt[j.old_at + i];
+    if (f) *f = wf[j.old_at + i];
+  } else {
+    *t = nt[j.new_at + (i - j.old_n)] + j.add;
+    if (f) *f = nf[j.new_at + (i - j.old_n)];
+  }
+  return *t >= j.w0;
+}
+
+// per stream: peaks its window keeps (one ballot per 64 entries, the waves' sums through LDS)
+__global__ __launch_bounds__(LS_THREADS) void peakwin_count_kernel(const pk_job* __restrict__ jobs, const uint32_t* __restrict__ wt,
+                                                                   const uint32_t* __restrict__ nt, uint64_t* __restrict__ cnt) {
+  const pk_job j = jobs[blockIdx.x];
+  const uint32_t n = j.old_n + j.new_n;
+  __shared__ uint32_t s_w[LS_THREADS / 64];
+  uint32_t c = 0;   // (the same in every lane of a wave)
+  for (uint32_t i0 = 0; i0 < n; i0 += LS_THREADS) {
+    uint32_t t;
+    const bool keep = pk_entry(j, i0 + threadIdx.x, nullptr, wt, nullptr, nt, nullptr, &t);
+    c += (uint32_t)__popcll(__ballot(keep));
+  }
+  if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = c;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t all = 0;
+    for (uint32_t i = 0; i < LS_THREADS / 64; ++i) all += s_w[i];
+    cnt[blockIdx.x] = all;
+  }
+}
+
+// per stream: the kept peaks, in order, at offs[stream] of the other slot, and their times relative to the window start
+__global__ __launch_bounds__(LS_THREADS) void peakwin_write_kernel(const pk_job* __restrict__ jobs, const uint16_t* __restrict__ wf,
+                                                                   const uint32_t* __restrict__ wt, const uint16_t* __restrict__ nf,
+                                                                   const uint32_t* __restrict__ nt, const uint64_t* __restrict__ offs,
+                                                                   const unsigned long long* __restrict__ total, uint64_t cap,
+                                                                   uint16_t* __restrict__ wf_out, uint32_t* __restrict__ wt_out,
+                                                                   uint32_t* __restrict__ rel) {
+  if (*total > cap) return;   // (uniform; the slots are sized by old_n + new_n of every stream, so this never holds)
+  const pk_job j = jobs[blockIdx.x];
+  const uint32_t n = j.old_n + j.new_n, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  __shared__ uint32_t s_w[2][LS_THREADS / 64];
+  uint64_t o = offs[blockIdx.x];
+  for (uint32_t i0 = 0, it = 0; i0 < n; i0 += LS_THREADS, ++it) {   // (n is the block's: every wave makes every round)
+    uint32_t f = 0, t = 0;
+    const bool keep = pk_entry(j, i0 + threadIdx.x, wf, wt, nf, nt, &f, &t);
+    const unsigned long long b = __ballot(keep);
+    const uint32_t pre = __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
+    uint32_t* sw = s_w[it & 1];   // (two rows: a wave may start the next round while another still reads this one's sums)
+    if (lane == 0) sw[w] = (uint32_t)__popcll(b);
+    __syncthreads();
+    uint32_t base = 0, all = 0;
+    for (uint32_t i = 0; i < LS_THREADS / 64; ++i) {
+      const uint32_t v = sw[i];
+      if (i < w) base += v;
+      all += v;
+    }
+    if (keep) {
+      const uint64_t p = o + base + pre;
+      wf_out[p] = (uint16_t)f;
+      wt_out[p] = t;
+      rel[p] = t - j.w0;
+    }
+    o += all;
+  }
+}
+
+extern "C" int32_t shz_listeners_timing(shz_listeners* L, int32_t enable, float* ms) {
+  SHZ_TRY(ls_check(L));
+  if (!L->peaks) SHZ_FAIL(L->ctx, SHZ_E_STATE, "shz_listeners_timing: the object keeps hash windows");
+  if (ms) memcpy(ms, L->ms, sizeof(L->ms));
+  L->timed = enable != 0;
+  return SHZ_OK;
+}
+
+extern "C" int32_t shz_listeners_peaks(shz_listeners* L, uint32_t l, uint32_t channel, uint16_t* f, uint32_t* t, uint64_t cap,
+                                       uint64_t* n) {
+  SHZ_TRY(ls_check(L));
+  shz_ctx* ctx = L->ctx;
+  if (!L->peaks) SHZ_FAIL(ctx, SHZ_E_STATE, "shz_listeners_peaks: the object keeps hash windows (shz_listeners_window)");
+  if (l >= L->n) SHZ_FAIL(ctx, SHZ_E_INVALID, "listener %u out of range (%u listeners)", l, L->n);
+  if (channel >= L->channels) SHZ_FAIL(ctx, SHZ_E_INVALID, "channel %u out of range (%u channels)", channel, L->channels);
+  if (!n) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_listeners_peaks: n is NULL");
+  const size_t i = (size_t)l * L->channels + channel;
+  const uint64_t at = L->p_at[i], cnt = L->p_n[i];
+  *n = cnt;
+  if (cnt > cap) SHZ_FAIL(ctx, SHZ_E_CAPACITY, "output needs %llu entries, capacity %llu", (unsigned long long)cnt, (unsigned long long)cap);
+  if (cnt == 0) return SHZ_OK;
+  if (!f || !t) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_listeners_peaks: NULL buffer");
+  SHZ_HIP(ctx, hipSetDevice(ctx->device));
+  SHZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  const shz_buf &pf = L->pf[L->cur], &pt = L->pt[L->cur];
+  if (!pf.p || !pt.p || (at + cnt) * 2 > pf.cap || (at + cnt) * 4 > pt.cap)
+    SHZ_FAIL(ctx, SHZ_E_STATE, "listeners: window [%llu, %llu) lies outside its slot", (unsigned long long)at, (unsigned long long)(at + cnt));
+  SHZ_HIP(ctx, shz_memcpy(ctx, f, (const uint16_t*)pf.p + at, cnt * 2, hipMemcpyDeviceToHost));
+  SHZ_HIP(ctx, shz_memcpy(ctx, t, (const uint32_t*)pt.p + at, cnt * 4, hipMemcpyDeviceToHost));
+  SHZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return SHZ_OK;
+}
+
+extern "C" int32_t shz_listeners_push_warps(shz_listeners* L, const int16_t* pcm, const uint64_t* chunk_off, const uint32_t* end,
+                                            uint32_t topn, const uint32_t* tempo_q16, const uint32_t* pitch_q16, uint32_t n_warps,
+                                            uint32_t flags, uint32_t* out_best, uint32_t* out_sid, int32_t* out_delta,
+                                            uint32_t* out_aligned, uint32_t* out_dedup, uint32_t* out_nres, uint32_t* out_nhash,
+                                            uint32_t* out_profile, uint32_t* out_w0) {
+  SHZ_TRY(ls_check(L));
+  shz_ctx* ctx = L->ctx;
+  shz_streams* s = L->s;
+  const uint32_t n = L->n, ch = L->channels, ns = s->n, K = n_warps;
+  if (!L->peaks) SHZ_FAIL(ctx, SHZ_E_STATE, "shz_listeners_push_warps: the object keeps hash windows (shz_listeners_push)");
+  // everything that can be refused is refused here, before any stream advances
+  if (flags & ~(SHZ_PCM_DEVICE | SHZ_MATCH_FULL_SORT)) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_listeners_push_warps: flags may hold SHZ_PCM_DEVICE and SHZ_MATCH_FULL_SORT");
+  SHZ_TRY(sp_check_ladder(ctx, "shz_listeners_push_warps", "n_warps", "tempo", tempo_q16, "pitch", pitch_q16, n_warps, s->fan));
+  if (!out_best || !out_sid || !out_delta || !out_aligned || !out_dedup || !out_nres) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_listeners_push_warps: NULL buffer");
+  SHZ_TRY(shz_match_ready(ctx, L->t, topn));
+  if (!chunk_off) SHZ_FAIL(ctx, SHZ_E_INVALID, "chunk_off must not be NULL");
+  for (uint32_t i = 0; i < ns; ++i)
+    if (chunk_off[i + 1] < chunk_off[i]) SHZ_FAIL(ctx, SHZ_E_INVALID, "chunk_off decreases at stream %u", i);
+  if (chunk_off[ns] > chunk_off[0] && !pcm) SHZ_FAIL(ctx, SHZ_E_INVALID, "pcm is NULL");
+  // the horizons after the push follow from the plan alone: w0 of every listener and the largest warped time
+  std::vector<uint64_t> h_after(ns);
+  for (uint32_t i = 0; i < ns; ++i) {
+    const uint64_t len = chunk_off[i + 1] - chunk_off[i];
+    const bool e = end && ((end[i >> 5] >> (i & 31)) & 1u);
+    h_after[i] = s->settled[i];
+    if (s->ended[i]) {
+      if (len || e) SHZ_FAIL(ctx, SHZ_E_STATE, "stream %u has ended; reset it before pushing to it again", i);
+      continue;
+    }
+    if (!len && !e) continue;
+    if (shz_stream_plan(s->samples[i], s->samples[i] + len, s->settled[i], s->hop, e ? 1 : 0, nullptr, nullptr, nullptr, &h_after[i]) != SHZ_OK)
+      SHZ_FAIL(ctx, SHZ_E_STATE, "stream %u: inconsistent state (samples %llu, settled %llu)", i, (unsigned long long)s->samples[i],
+               (unsigned long long)s->settled[i]);
+  }
+  const uint32_t s_max = *std::max_element(tempo_q16, tempo_q16 + K);   // (time alone: the bias bound)
+  std::vector<uint32_t> w0_new(n);
+  uint64_t t_max = 0;
+  for (uint32_t l = 0; l < n; ++l) {
+    uint64_t h, w0, top = 0;
+    SHZ_TRY(shz_listener_window(h_after.data() + (size_t)l * ch, ch, L->window_frames, &h, &w0));
+    for (uint32_t c = 0; c < ch; ++c) top = std::max(top, h_after[(size_t)l * ch + c]);
+    w0_new[l] = (uint32_t)w0;
+    // every settled t of a channel is below that channel's horizon
+    if (top > w0) t_max = std::max(t_max, ((top - w0 - 1) * s_max + 32768) >> 16);
+  }
+  if (t_max >= (1ull << 20))
+    SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "shz_listeners_push_warps: a window at time factor %u / 65536 reaches t' = %llu; query offsets must be < 2^20",
+             s_max, (unsigned long long)t_max);
+  SHZ_HIP(ctx, hipSetDevice(ctx->device));
+  const bool timed = L->timed;
+  if (timed) {
+    for (hipEvent_t& e : L->ev)
+      if (!e) SHZ_HIP(ctx, hipEventCreate(&e));
+    SHZ_HIP(ctx, hipEventRecord(L->ev[0], ctx->stream));
+  }
+  // 1) the streams' push; its hashes go to buffers of the object and are not used (the streams advance as they always do)
+  std::vector<uint64_t> hash_off((size_t)ns + 1, 0);
+  uint64_t count = 0;
+  void *d_nk, *d_nt;
+  if (L->new_cap == 0) L->new_cap = (uint64_t)ns * 256 + 4096;
+  for (int attempt = 0;; ++attempt) {
+    SHZ_TRY(st_reserve(ctx, L->nk, L->new_cap * 4 + 64, &d_nk));
+    SHZ_TRY(st_reserve(ctx, L->nt, L->new_cap * 4 + 64, &d_nt));
+    const int32_t rc = shz_streams_push(s, pcm, chunk_off, end, (flags & SHZ_PCM_DEVICE) | SHZ_OUT_DEVICE, (uint32_t*)d_nk,
+                                        (uint32_t*)d_nt, hash_off.data(), L->new_cap, &count);
+    if (rc == SHZ_E_CAPACITY && attempt < 2 && count > L->new_cap) {
+      L->new_cap = count + count / 4;
+      continue;
+    }
+    SHZ_TRY(rc);
+    break;
+  }
+  for (uint32_t i = 0; i < ns; ++i)
+    if (s->settled[i] != h_after[i])
+      SHZ_FAIL(ctx, SHZ_E_STATE, "listeners: stream %u settled %llu frames, its plan said %llu", i, (unsigned long long)s->settled[i],
+               (unsigned long long)h_after[i]);
+  if (timed) SHZ_HIP(ctx, hipEventRecord(L->ev[1], ctx->stream));
+  // 2) per stream: where its old and its newly settled peaks are; the slots hold at most all of them
+  void* mailp;
+  const uint64_t jb = ((uint64_t)ns * sizeof(pk_job) + 255) & ~255ull, rb = 64 + (uint64_t)ns * 8;
+  SHZ_TRY(shz_mailbox(ctx, jb + rb, &mailp));
+  pk_job* hj = (pk_job*)mailp;
+  uint64_t bound = 0;
+  for (uint32_t i = 0; i < ns; ++i) {
+    const st_hand& hd = s->hand[i];
+    hj[i] = pk_job{L->p_at[i], hd.at, L->p_n[i], hd.n, w0_new[i / ch], hd.w0};
+    bound += (uint64_t)L->p_n[i] + hd.n;
+  }
+  if (bound >= (1ull << 31)) SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "listeners: 2^31 peaks in the windows");
+  const uint32_t out = L->cur ^ 1u;
+  void *d_wf, *d_wt, *d_rel, *d_jobs, *d_ctl;
+  SHZ_TRY(st_reserve(ctx, L->pf[out], bound * 2 + 64, &d_wf));
+  SHZ_TRY(st_reserve(ctx, L->pt[out], bound * 4 + 64, &d_wt));
+  SHZ_TRY(st_reserve(ctx, L->pr, bound * 4 + 64, &d_rel));
+  SHZ_TRY(st_reserve(ctx, L->jobs, jb, &d_jobs));
+  SHZ_TRY(st_reserve(ctx, L->ctl, 64 + (uint64_t)ns * 16, &d_ctl));
+  const uint16_t* d_wf_in = (const uint16_t*)L->pf[L->cur].p;
+  const uint32_t* d_wt_in = (const uint32_t*)L->pt[L->cur].p;
+  unsigned long long* d_total = (unsigned long long*)d_ctl;
+  uint64_t *d_cnt = (uint64_t*)((char*)d_ctl + 64), *d_offs = d_cnt + ns;
+  SHZ_HIP(ctx, hipMemcpyAsync(d_jobs, hj, (uint64_t)ns * sizeof(pk_job), hipMemcpyHostToDevice, ctx->stream));
+  // 3) count, scan over the streams, compact into the other slot
+  hipLaunchKernelGGL(peakwin_count_kernel, dim3(ns), dim3(LS_THREADS), 0, ctx->stream, (const pk_job*)d_jobs, d_wt_in,
+                     (const uint32_t*)s->pt.p, d_cnt);
+  SHZ_HIP(ctx, hipGetLastError());
+  SHZ_TRY(shz_scan_u64(ctx, d_cnt, d_offs, ns, (uint64_t*)d_total));
+  hipLaunchKernelGGL(peakwin_write_kernel, dim3(ns), dim3(LS_THREADS), 0, ctx->stream, (const pk_job*)d_jobs, d_wf_in, d_wt_in,
+                     (const uint16_t*)s->pf.p, (const uint32_t*)s->pt.p, (const uint64_t*)d_offs, (const unsigned long long*)d_total,
+                     bound, (uint16_t*)d_wf, (uint32_t*)d_wt, (uint32_t*)d_rel);
+  SHZ_HIP(ctx, hipGetLastError());
+  // 4) one read-back: the counts are the warp's peak_off
+  char* hr = (char*)mailp + jb;
+  SHZ_HIP(ctx, hipMemcpyAsync(hr, d_ctl, rb, hipMemcpyDeviceToHost, ctx->stream));
+  if (timed) SHZ_HIP(ctx, hipEventRecord(L->ev[2], ctx->stream));
+  SHZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  const uint64_t total = *(const uint64_t*)hr;
+  const uint64_t* hc = (const uint64_t*)(hr + 64);
+  if (total > bound) SHZ_FAIL(ctx, SHZ_E_STATE, "listeners: %llu window peaks exceed their bound %llu", (unsigned long long)total, (unsigned long long)bound);
+  std::vector<uint64_t> peak_off((size_t)ns + 1, 0);
+  for (uint32_t i = 0; i < ns; ++i) peak_off[i + 1] = peak_off[i] + hc[i];
+  // the windows advance: the streams have
+  L->cur = out;
+  for (uint32_t i = 0; i < ns; ++i) {
+    L->p_at[i] = peak_off[i];
+    L->p_n[i] = (uint32_t)hc[i];
+  }
+  for (uint32_t l = 0; l < n; ++l) {
+    L->w0[l] = w0_new[l];
+    L->last_nhash[l] = 0;
+    if (out_w0) out_w0[l] = w0_new[l];
+  }
+  // 5) every (listener, warp) is one query: warped, hashed and matched as shz_recognize_warps does it
+  std::vector<uint32_t> clip0((size_t)n + 1), nhash(n, 0);
+  for (uint32_t l = 0; l <= n; ++l) clip0[l] = l * ch;
+  float ms_warp = 0.f, ms_match = 0.f;
+  SHZ_TRY(sp_match_fold(ctx, L->t, (const uint16_t*)d_wf, (const uint32_t*)d_rel, peak_off.data(), ns, clip0.data(), n, s->fan, topn,
+                        tempo_q16, pitch_q16, K, flags & SHZ_MATCH_FULL_SORT, t_max, out_best, out_sid, out_delta, out_aligned,
+                        out_dedup, out_nres, nhash.data(), out_profile, timed, &ms_warp, &ms_match));
+  for (uint32_t l = 0; l < n; ++l) {
+    L->last_nhash[l] = nhash[l];
+    if (out_nhash) out_nhash[l] = nhash[l];
+  }
+  if (timed) {
+    SHZ_HIP(ctx, hipEventElapsedTime(&L->ms[0], L->ev[0], L->ev[1]));
+    SHZ_HIP(ctx, hipEventElapsedTime(&L->ms[1], L->ev[1], L->ev[2]));
+    L->ms[2] = ms_warp;
+    L->ms[3] = ms_match;
+  }
+  return SHZ_OK;
+}
+
+// the speed ladder: one table for time and frequency (its own names in what is refused about it)
+extern "C" int32_t shz_listeners_push_speeds(shz_listeners* L, const int16_t* pcm, const uint64_t* chunk_off, const uint32_t* end,
+                                             uint32_t topn, const uint32_t* speed_q16, uint32_t n_speeds, uint32_t flags,
+                                             uint32_t* out_best, uint32_t* out_sid, int32_t* out_delta, uint32_t* out_aligned,
+                                             uint32_t* out_dedup, uint32_t* out_nres, uint32_t* out_nhash, uint32_t* out_profile,
+                                             uint32_t* out_w0) {
+  SHZ_TRY(ls_check(L));
+  if (!L->peaks) SHZ_FAIL(L->ctx, SHZ_E_STATE, "shz_listeners_push_speeds: the object keeps hash windows (shz_listeners_push)");
+  SHZ_TRY(sp_check_ladder(L->ctx, "shz_listeners_push_speeds", "n_speeds", "speed", speed_q16, "speed", speed_q16, n_speeds, L->s->fan));
+  return shz_listeners_push_warps(L, pcm, chunk_off, end, topn, speed_q16, speed_q16, n_speeds, flags, out_best, out_sid, out_delta,
+                                  out_aligned, out_dedup, out_nres, out_nhash, out_profile, out_w0);
 }

@@ -12,7 +12,7 @@ the pitch ladder at tempo 1 followed by the tempo ladder at every query's best p
 
 Limits: the hop is fixed, so a warped time is a rounded frame; a peak near the edge of its 21x21 neighbourhood may move when
 the audio is stretched; the smearing a real phase-vocoder time-stretch adds is not modelled by the corpus the tolerances were
-measured on; the scan and the live listeners take speed ladders only, no warp pairs."""
+measured on; the scan takes speed ladders only, no warp pairs (the device-resident listeners take both: stream.py)."""
 from __future__ import annotations
 
 from time import time

@@ -72,6 +72,32 @@ def _as_pcm(x):
     return conv(x)
 
 
+def _q16(a) -> np.ndarray:
+    """Q16 factors of a list given as Q16 integers or as floats"""
+    a = np.ascontiguousarray(a)
+    if a.ndim != 1 or a.dtype.kind not in "iuf":
+        raise TypeError("a ladder is a 1-D list of Q16 integers (round(s * 65536)) or of floats")
+    return (np.rint(a * 65536.0) if a.dtype.kind == "f" else a).astype(np.uint32)
+
+
+def _ladder_of(speeds, warps):
+    """("speed", s16, s16) or ("warp", t16, f16).  warps: a list of (tempo, pitch) pairs, or the tuple of two arrays
+    (tempos, pitches) that recognize_warps takes."""
+    if speeds is not None:
+        s = _q16(speeds)
+        return "speed", s, s
+    if isinstance(warps, tuple) and len(warps) == 2 and all(isinstance(x, np.ndarray) and x.ndim == 1 for x in warps):
+        t16, f16 = _q16(warps[0]), _q16(warps[1])   # (a tuple of two arrays: the two lists; anything else: pairs)
+    else:
+        w = np.asarray(warps)
+        if w.ndim != 2 or w.shape[1] != 2:
+            raise ValueError("warps is a list of (tempo, pitch) pairs, or the two lists (tempos, pitches)")
+        t16, f16 = _q16(np.ascontiguousarray(w[:, 0])), _q16(np.ascontiguousarray(w[:, 1]))
+    if len(t16) != len(f16):
+        raise ValueError("warps=(tempos, pitches): two lists of one length")
+    return "warp", t16, f16
+
+
 def fingerprint_stream(chunks, Fs: int = RATE, fan_value: int = 5, amp_min=10, ctx=None):
     """Generator: yields list[(hex20, t1)] per chunk of `chunks` (any iterable of 1-D int16 arrays); the stream ends with
     the last chunk.  The concatenation of what it yields equals fingerprint(np.concatenate(chunks))."""
@@ -102,10 +128,24 @@ class StreamRecognizer:
     smallest settled horizon of the listener's channels; window_frames = int(window_seconds * 44100 / hop).  Listeners
     with no hashes in the window get [].  device=True keeps the windows on the GPU (shz_listeners_*): one library call per
     push, no hash crosses the bus, same return value.  fs_in: the listeners' audio is at fs_in and the table at 44.1 kHz; the
-    chunks go through a StreamResampler first."""
+    chunks go through a StreamResampler first.
+
+    speeds= / warps= (device=True only): listeners whose audio may play fast or slow.  speeds is a ladder as recognize_speeds
+    takes it (Q16 integers, or floats), warps a list of (tempo, pitch) pairs or the two Q16 arrays as recognize_warps takes
+    them.  The windows then hold settled PEAKS (shz_listeners_create_peaks); every push warps, pairs and matches every
+    listener's window at every variant, and each result dict carries "speed", or "tempo" and "pitch", of the listener's
+    best variant; `offset` is in the TABLE's frames.  last_best / last_profile hold the arrays of the last push;
+    push(..., speeds=) / push(..., warps=) overrides the ladder for that push.  At a ladder of [65536] the results are those
+    of the window's peaks paired among themselves, not bit for bit the plain listener's."""
 
     def __init__(self, db, n_listeners: int, channels: int = 1, window_seconds: float = 5, topn: int = TOPN,
-                 fan_value: int = 5, amp_min=10, device: bool = False, fs_in: int = None):
+                 fan_value: int = 5, amp_min=10, device: bool = False, fs_in: int = None, speeds=None, warps=None):
+        if speeds is not None and warps is not None:
+            raise ValueError("speeds= and warps= exclude each other: a speed is the warp (s, s)")
+        if (speeds is not None or warps is not None) and not device:
+            raise ValueError("speeds= / warps= need device=True: the host recogniser keeps hashes, and a warp acts on peaks")
+        self.ladder = None if speeds is None and warps is None else _ladder_of(speeds, warps)
+        self.last_best = self.last_profile = None
         self.db, self.n, self.channels, self.topn = db, int(n_listeners), int(channels), int(topn)
         self.fp = StreamFingerprinter(self.n * self.channels, RATE, fan_value, amp_min, db.ctx, fs_in)
         self.window_frames = int(float(window_seconds) * RATE / self.fp.streams.hop)
@@ -115,7 +155,7 @@ class StreamRecognizer:
         if device:
             if not hasattr(db.table, "h"):
                 raise NotImplementedError("device-resident listeners take the unsharded table (shards=1)")
-            self.listeners = _ffi.Listeners(self.fp.streams, db.table, self.n, self.window_frames)
+            self.listeners = _ffi.Listeners(self.fp.streams, db.table, self.n, self.window_frames, peaks=self.ladder is not None)
 
     def _flat(self, per_listener):
         out = []
@@ -132,12 +172,20 @@ class StreamRecognizer:
         c = self.channels
         return min(self.fp.state(listener * c + j)["settled"] for j in range(c))
 
-    def push(self, chunks_per_listener, end=None):
+    def push(self, chunks_per_listener, end=None, speeds=None, warps=None):
         """chunks_per_listener[l]: list of `channels` 1-D int16 arrays (a bare array when channels == 1; None: nothing).
-        end: listeners whose channels all end after this chunk.  Returns [(results, w0)] per listener."""
+        end: listeners whose channels all end after this chunk.  Returns [(results, w0)] per listener.  speeds / warps:
+        this push's ladder, for a recogniser created with one."""
         assert len(chunks_per_listener) == self.n
+        if speeds is not None and warps is not None:
+            raise ValueError("speeds= and warps= exclude each other: a speed is the warp (s, s)")
+        if (speeds is not None or warps is not None) and self.ladder is None:
+            raise ValueError("a ladder for one push needs a recogniser created with speeds= or warps=")
         ends = None if end is None else [l * self.channels + j for l in (range(self.n) if end is True else end)
                                          for j in range(self.channels)]
+        if self.ladder is not None:
+            ladder = self.ladder if speeds is None and warps is None else _ladder_of(speeds, warps)
+            return self._push_ladder(self._flat(chunks_per_listener), ends, ladder)
         if self.listeners is not None:
             return self._push_device(self._flat(chunks_per_listener), ends)
         k, t1, ho = self.fp.push(self._flat(chunks_per_listener), ends)
@@ -173,8 +221,30 @@ class StreamRecognizer:
         nhash = res["nhash"].tolist()
         return [(_result_dicts(self.db, res, l, nhash[l]) if nhash[l] else [], int(w0[l])) for l in range(self.n)]
 
+    def _push_ladder(self, chunks, ends, ladder):
+        from . import _result_dicts
+        self.db.finalize()
+        kind, t16, f16 = ladder
+        pcm = self.fp._pcm(chunks, ends)
+        if kind == "speed":
+            res, w0 = self.listeners.push_speeds(pcm, t16, ends, self.topn)
+        else:
+            res, w0 = self.listeners.push_warps(pcm, t16, f16, ends, self.topn)
+        self.last_best, self.last_profile = res["best"], res["profile"]
+        nhash, out = res["nhash"].tolist(), []
+        for l in range(self.n):
+            dicts = _result_dicts(self.db, res, l, nhash[l]) if nhash[l] else []
+            b = int(res["best"][l])
+            for d in dicts:
+                if kind == "speed":
+                    d["speed"] = float(t16[b]) / 65536
+                else:
+                    d["tempo"], d["pitch"] = float(t16[b]) / 65536, float(f16[b]) / 65536
+            out.append((dicts, int(w0[l])))
+        return out
+
     def window_hashes(self, listener: int) -> int:
-        """Hashes in the listener's window after the last push."""
+        """Hashes in the listener's window after the last push (with a ladder: the hashes of its chosen variant)."""
         if self.listeners is not None:
             return self.listeners.state(listener)["window_hashes"]
         return len(self._k[listener])
