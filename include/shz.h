@@ -408,6 +408,9 @@ uint64_t shz_recognize_estimate(uint64_t frames, uint32_t fan_value);
 /* Test switch of shz_scan_speeds: a slice holds at most 1 recording x 2 rungs and a group of windows handed to the match at
  * most 3 windows, so that tests reach the slice, chunk and group borders with tiny inputs (results do not depend on them). */
 #define SHZ_DEBUG_SCAN_SPEED_SMALL_SLICES 32u
+/* Test switch of shz_match_songs_warps: a slice holds one song x at most 2 warps, so that tests reach the slice and chunk
+ * borders with tiny inputs (results do not depend on the slicing). */
+#define SHZ_DEBUG_CATALOG_SMALL_SLICES 64u
 int32_t shz_set_debug(shz_ctx* ctx, uint32_t flags);
 int32_t shz_match_vt_redo(shz_ctx* ctx, uint64_t* count);
 /* A single query of at most 8,192 hashes handed over in host memory has its vote kernels queued before the number of its
@@ -450,6 +453,65 @@ int32_t shz_match_device_host(shz_ctx* ctx, shz_table* t, const uint32_t* key32,
 int32_t shz_match_songs(shz_ctx* ctx, shz_table* t, const uint32_t* sids, uint32_t n_sids, uint32_t topn, uint32_t flags,
                         uint64_t* out_rows, uint32_t* out_sid, int32_t* out_delta, uint32_t* out_aligned, uint32_t* out_dedup,
                         uint32_t* out_nres, uint32_t* out_nhash, uint64_t* out_npairs);
+/* ---- sped-up and pitch-shifted copies inside the table (new): shz_match_songs finds a re-upload only while its audio is
+ * bit-identical; a copy pitched up 3 %, a 25/24 video transfer or a rip from a drifting deck shares no hash with its
+ * original.  The table holds no peaks, so the peak-level warp of shz_warp_pair_hash_tf cannot be applied to a stored song --
+ * but a row (key32 = f1 << 20 | f2 << 8 | dt, offset = t1) IS the two peaks (f1, t1) and (f2, t1 + dt).  The ROW WARP moves
+ * both with the maps of shz_warp_pair_hash_tf and forms the key again.  For a row (key32, off) and a warp (t16, f16), each
+ * factor Q16 in [32768, 131072], in 64-bit integers:
+ *     f1, f2, dt = key32 >> 20, (key32 >> 8) & 0xFFF, key32 & 0xFF
+ *     t1' = (off t16 + 32768) >> 16            t2' = ((off + dt) t16 + 32768) >> 16          dt' = t2' - t1'
+ *     f1' = (2 65536 f1 + f16) / (2 f16)       f2' likewise
+ *     kept iff f1' <= 2048 and f2' <= 2048 and dt' <= 200;   out = (f1' << 20 | f2' << 8 | dt',  t1')
+ * Elementwise: no sort, no fan_value, nothing is deduplicated (two rows may meet in one (key, t1'); the match collapses them
+ * and its out_nhash counts the distinct ones).  At (65536, 65536) the output is the input.  t1' is stored in 32 bits: offsets
+ * < 2^31, the table's own limit for matching, keep it exact at every factor.  Relation to the peak-level warp: for t16 >=
+ * 65536 and f16 >= 65536 the row warp of a song's hashes equals shz_warp_pair_hash_tf of its peaks entry for entry (the
+ * order of the peaks is the input's, no peak leaves, dt' >= dt keeps every pair's rank); below unity the peak-level warp
+ * pairs again after frames merge and peaks leave, and a few per cent of the entries differ.  Numpy twin:
+ * tests/rows_warp_twin.py.
+ *
+ * shz_warp_row_host (no GPU, no ctx): the map over n rows on the host -- the one inline function the kernels call.
+ * out_keep[i] = 1 where row i is kept; out_key32[i] / out_off[i] hold its image there and 0 elsewhere (nothing is compacted).
+ * SHZ_E_INVALID: a factor outside the range, a NULL array with n > 0.
+ *
+ * shz_warp_rows: the rows of n_songs songs -- song q owns [row_off[q], row_off[q + 1]), row_off: HOST, n_songs + 1 entries;
+ * key32 / off host, or device with SHZ_IN_DEVICE -- at every warp v = (tempo_q16[v], pitch_q16[v]).  OUTPUT ORDER: for song
+ * q, for warp v, the kept rows of q in their input order -- (q, v) is one contiguous query of the match.  out_row_off (HOST,
+ * n_songs n_warps + 1 entries in (q, v) order, may be NULL) is the CSR of those segments, exact: the rows are counted before
+ * they are written.  out_key32 / out_off: host, or device with SHZ_OUT_DEVICE; more than cap kept rows: SHZ_E_CAPACITY,
+ * *count = required, out_row_off written, nothing else (the two-call idiom of shz_warp_pair_hash).  The places come from a
+ * scan of block counts: no atomic decides where a row lands, and the output is repeatable.  SHZ_E_INVALID before anything is
+ * launched: n_warps of 0 or above 1024, a NULL table, a factor of either table outside the range, a row_off that decreases.
+ * SHZ_E_UNSUPPORTED: rows x n_warps of 2^32 or more in one call. */
+int32_t shz_warp_row_host(const uint32_t* key32, const uint32_t* off, uint64_t n, uint32_t t16, uint32_t f16,
+                          uint32_t* out_key32, uint32_t* out_off, uint8_t* out_keep);
+int32_t shz_warp_rows(shz_ctx* ctx, const uint32_t* key32, const uint32_t* off, const uint64_t* row_off, uint32_t n_songs,
+                      const uint32_t* tempo_q16, const uint32_t* pitch_q16, uint32_t n_warps, uint32_t flags,
+                      uint32_t* out_key32, uint32_t* out_off, uint64_t* out_row_off, uint64_t cap, uint64_t* count);
+/* shz_match_songs at a list of warps: the listed songs' rows are gathered as shz_match_songs gathers them (into columns the
+ * call owns), warped at every warp by the row warp above, and every (song q, warp v) is one query of the library's match on
+ * device columns, with topn + 1 and the bias bound (largest listed offset x largest t16 + 32768) >> 16; the song itself is
+ * taken out of each of its lists on the host -- dropping one element from the top topn + 1 leaves the exact top topn of the
+ * others at any warp.  Outputs (host), ALL variants, (q, v) at index q n_warps + v: out_sid / out_delta / out_aligned /
+ * out_dedup [n_sids n_warps topn], out_nres / out_nhash / out_npairs [n_sids n_warps] (the last two may be NULL), zero past
+ * out_nres; out_rows[n_sids] (may be NULL), the songs' unwarped row counts.  There is no best-of fold: an exact copy found at
+ * the identity must not hide a pitched copy of the same song found at another warp.  out_delta is the found song's frame
+ * under the listed song's WARPED frame 0.  out_nhash is the number of distinct warped rows of (q, v).  With the single warp
+ * (65536, 65536) the arrays equal shz_match_songs's.
+ * Refused: everything shz_match_songs refuses; n_warps of 0 or above 1024, a NULL table, a factor outside the range
+ * (SHZ_E_INVALID, before anything is launched); a listed offset whose image under the largest t16 reaches 2^20
+ * (SHZ_E_UNSUPPORTED; the message names the offset and the factor).
+ * SLICES: the work goes in slices of (whole songs x a contiguous chunk of warps) whose items -- rows x warps, 8 bytes each in
+ * the call's warped columns -- stay below 2^32, within 1/8 of the workspace limit and the match's 2^28-pair budget; the ladder
+ * is cut only where one song at all warps is beyond that.  The call's buffers are allocated once, for the largest slice.
+ * Results do not depend on the slicing (SHZ_DEBUG_CATALOG_SMALL_SLICES).  ms_gather / ms_warp / ms_match (may be NULL):
+ * hipEvent times of the gather, of the warp stages (with their one read-back a slice) and of the matches. */
+int32_t shz_match_songs_warps(shz_ctx* ctx, shz_table* t, const uint32_t* sids, uint32_t n_sids, uint32_t topn,
+                              const uint32_t* tempo_q16, const uint32_t* pitch_q16, uint32_t n_warps, uint32_t flags,
+                              uint64_t* out_rows, uint32_t* out_sid, int32_t* out_delta, uint32_t* out_aligned,
+                              uint32_t* out_dedup, uint32_t* out_nres, uint32_t* out_nhash, uint64_t* out_npairs,
+                              float* ms_gather, float* ms_warp, float* ms_match);
 /* rows streamed / pairs voted by the last shz_match_batch (for HBM accounting) */
 int32_t shz_match_stats(shz_ctx* ctx, uint64_t* rows_scanned, uint64_t* pairs, uint64_t* distinct_keys);
 

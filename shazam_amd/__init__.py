@@ -353,4 +353,4 @@ from .scan import scan, scan_windows  # noqa: E402,F401
 from .speed import (pitch_ladder, recognize_speeds, recognize_warps, speed_ladder, tempo_ladder, warp_grid,  # noqa: E402,F401
                     warp_hashes, warp_hashes_tf)
 # the catalogue against itself (csrc/shz_catalog.hip): the rows of listed songs as queries, duplicates and excerpts among them
-from .catalog import find_duplicates, fold_pairs, match_songs  # noqa: E402,F401
+from .catalog import find_duplicates, fold_pairs, fold_pairs_warps, match_songs  # noqa: E402,F401

@@ -17,6 +17,7 @@ SONGS_DEVICE_OUT = 128   # shz_table_song_hashes: key32 / off are device memory
 DEBUG_VT_TINY_HEAVY, DEBUG_VT_PROBE1, DEBUG_RUN_LIMIT_SMALL, DEBUG_SCAN_SMALL_GROUPS = 1, 2, 4, 8
 DEBUG_SPEED_SMALL_SLICES = 16   # shz_recognize_speeds: at most 2 queries a slice
 DEBUG_SCAN_SPEED_SMALL_SLICES = 32   # shz_scan_speeds: at most 1 recording x 2 rungs a slice, 3 windows a match group
+DEBUG_CATALOG_SMALL_SLICES = 64   # shz_match_songs_warps: one song x at most 2 warps a slice
 SCAN_U32, SCAN_POPC64, SCAN_U64 = 0, 1, 2   # shz_scan_host kinds
 STAGE_F32, STAGE_F64, STAGE_PERSISTENT = 0, 1, 1   # shz_stft_stage_host kinds | flag
 RUN_ROWS_MAX, RUN_ROWS_MAX_SMALL = (1 << 32) - 4096, 65536
@@ -94,6 +95,11 @@ SIGNATURES = {
     "shz_table_song_rows": (C.c_int32, [vp, C.c_uint32, u64p]),
     "shz_table_song_hashes": (C.c_int32, [vp, vp, C.c_uint32, u64p, vp, vp, C.c_uint64, C.c_uint32]),
     "shz_match_songs": (C.c_int32, [vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "shz_warp_row_host": (C.c_int32, [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp, vp]),
+    "shz_warp_rows": (C.c_int32, [vp, vp, vp, u64p, C.c_uint32, u32p, u32p, C.c_uint32, C.c_uint32, vp, vp, u64p, C.c_uint64,
+                                  u64p]),
+    "shz_match_songs_warps": (C.c_int32, [vp, vp, vp, C.c_uint32, C.c_uint32, u32p, u32p, C.c_uint32, C.c_uint32, vp, vp, vp, vp,
+                                          vp, vp, vp, vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "shz_match_batch": (C.c_int32, [vp, vp, vp, vp, u64p, C.c_uint32, C.c_uint32, C.c_uint32,
                                     vp, vp, vp, vp, vp, vp, vp]),
     "shz_match_device_host": (C.c_int32, [vp, vp, vp, vp, u64p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int64,
@@ -316,7 +322,7 @@ class Context:
         """SHZ_DEBUG_* test switches (1: tiny hand-over list, 2: LDS probes give up after one round, 4: runs and segments cut
         from runs hold at most RUN_ROWS_MAX_SMALL rows, 8: shz_scan_batch matches its windows in groups of at most 3, 16: shz_recognize_speeds warps and
         matches its queries in slices of at most 2, 32: shz_scan_speeds works in slices of 1 recording x 2 rungs and matches
-        its windows in groups of at most 3)."""
+        its windows in groups of at most 3, 64: shz_match_songs_warps works in slices of 1 song x 2 warps)."""
         self.check(lib().shz_set_debug(self.h, int(flags)))
 
     def vt_redo_count(self) -> int:
@@ -814,6 +820,40 @@ class Context:
                                              *[C.byref(m) for m in ms]))
         return res, tuple(float(m.value) for m in ms)
 
+    def warp_rows_raw(self, key32, off, row_off, tempos, pitches, cap=0, device_in=False, out_key: DevBuf = None,
+                      out_off: DevBuf = None):
+        """One shz_warp_rows as it is: (rc, key32, off, out_row_off, count) without retrying; warp v is (tempos[v],
+        pitches[v]), Q16.  key32 / off: host arrays, or DevBufs with device_in.  With out_key / out_off DevBufs the warped
+        rows stay on the device and the returned arrays are None."""
+        ro = np.ascontiguousarray(row_off, np.uint64)
+        tq, fq = np.ascontiguousarray(tempos, np.uint32), np.ascontiguousarray(pitches, np.uint32)
+        if tq.shape != fq.shape or tq.ndim != 1:
+            raise ValueError("tempos and pitches are two lists of one length: warp v is (tempos[v], pitches[v])")
+        ns = len(ro) - 1
+        if not device_in:
+            key32, off = np.ascontiguousarray(key32, np.uint32), np.ascontiguousarray(off, np.uint32)
+        oro, cnt = np.zeros(ns * len(tq) + 1, np.uint64), C.c_uint64()
+        flags = (IN_DEVICE if device_in else 0) | (OUT_DEVICE if out_key is not None else 0)
+        k = o = None
+        if out_key is None:
+            k, o = np.empty(max(int(cap), 1), np.uint32), np.empty(max(int(cap), 1), np.uint32)
+        rc = lib().shz_warp_rows(self.h, ptr(key32), ptr(off), ro.ctypes.data_as(u64p), ns, tq.ctypes.data_as(u32p),
+                                 fq.ctypes.data_as(u32p), len(tq), flags, ptr(out_key if out_key is not None else k),
+                                 ptr(out_off if out_key is not None else o), oro.ctypes.data_as(u64p), int(cap), C.byref(cnt))
+        n = int(cnt.value)
+        if k is not None:
+            k, o = k[:min(n, int(cap))], o[:min(n, int(cap))]
+        return rc, k, o, oro, n
+
+    def warp_rows(self, key32, off, row_off, tempos, pitches):
+        """shz_warp_rows (two calls: count, then write): the rows of every song at every warp, (key32, off, out_row_off) in
+        the order song, warp; out_row_off has n_songs * n_warps + 1 entries."""
+        rc, k, o, oro, n = self.warp_rows_raw(key32, off, row_off, tempos, pitches, 0)
+        if rc == E_CAPACITY:
+            rc, k, o, oro, n = self.warp_rows_raw(key32, off, row_off, tempos, pitches, n)
+        self.check(rc)
+        return k[:n], o[:n], oro
+
     def resample_raw(self, pcm, clip_off, L, M, T, taps, in_base=None, m_first=None, m_end=None, pcm_device=False,
                      out: DevBuf = None, cap=None):
         """One shz_resample_i16 as it is: (rc, out, out_off, count) without retrying.  taps: int32 [L, T] in Q30.  With `out`
@@ -885,6 +925,19 @@ def _match_result(nq: int, topn: int) -> dict:
         "sid": np.zeros((nq, topn), np.uint32), "delta": np.zeros((nq, topn), np.int32),
         "aligned": np.zeros((nq, topn), np.uint32), "dedup": np.zeros((nq, topn), np.uint32),
         "nres": np.zeros(nq, np.uint32), "nhash": np.zeros(nq, np.uint32), "npairs": np.zeros(nq, np.uint64)}
+
+
+def warp_row_host(key32, off, t16: int, f16: int):
+    """shz_warp_row_host (host only): the row warp's map over host arrays -- (key32', off', keep), elementwise; where
+    keep is False the two outputs are 0."""
+    k, o = np.ascontiguousarray(key32, np.uint32).reshape(-1), np.ascontiguousarray(off, np.uint32).reshape(-1)
+    if k.shape != o.shape:
+        raise ValueError("key32 and off are two columns of one length")
+    ok, oo, keep = np.zeros(len(k), np.uint32), np.zeros(len(k), np.uint32), np.zeros(len(k), np.uint8)
+    rc = lib().shz_warp_row_host(ptr(k), ptr(o), len(k), int(t16), int(f16), ptr(ok), ptr(oo), ptr(keep))
+    if rc != OK:
+        raise ShzError(rc, "shz_warp_row_host: factors are Q16 in [32768, 131072]")
+    return ok, oo, keep.astype(bool)
 
 
 def recognize_estimate(frames: int, fan_value: int = 5) -> int:
@@ -1086,6 +1139,27 @@ class Table:
         self.ctx.check(lib().shz_match_songs(self.ctx.h, self.h, ptr(a), len(a), topn, MATCH_FULL_SORT if full_sort else 0,
                                              ptr(res["rows"]), ptr(res["sid"]), ptr(res["delta"]), ptr(res["aligned"]),
                                              ptr(res["dedup"]), ptr(res["nres"]), ptr(res["nhash"]), ptr(res["npairs"])))
+        return res
+
+    def match_songs_warps(self, sids, tempos, pitches, topn=5, full_sort=False, timings=False):
+        """Every listed song at every warp (tempos[v], pitches[v]) matched against the rest of the table
+        (shz_match_songs_warps): the dict of match_songs with a warp axis -- sid, delta, aligned, dedup [n, n_warps, topn];
+        nres, nhash, npairs [n, n_warps]; rows [n].  timings: the dict also holds "ms" = (gather, warp, match) device times."""
+        a = np.ascontiguousarray(sids, np.uint32).reshape(-1)
+        tq, fq = np.ascontiguousarray(tempos, np.uint32), np.ascontiguousarray(pitches, np.uint32)
+        if tq.shape != fq.shape or tq.ndim != 1:
+            raise ValueError("tempos and pitches are two lists of one length: warp v is (tempos[v], pitches[v])")
+        n, K = len(a), len(tq)
+        res = {k: v.reshape((n, K) + v.shape[1:]) for k, v in _match_result(n * K, topn).items()}
+        res["rows"] = np.zeros(n, np.uint64)
+        ms = [C.c_float(), C.c_float(), C.c_float()]
+        self.ctx.check(lib().shz_match_songs_warps(self.ctx.h, self.h, ptr(a), n, topn, tq.ctypes.data_as(u32p),
+                                                   fq.ctypes.data_as(u32p), K, MATCH_FULL_SORT if full_sort else 0,
+                                                   ptr(res["rows"]), ptr(res["sid"]), ptr(res["delta"]), ptr(res["aligned"]),
+                                                   ptr(res["dedup"]), ptr(res["nres"]), ptr(res["nhash"]), ptr(res["npairs"]),
+                                                   *[C.byref(m) if timings else None for m in ms]))
+        if timings:
+            res["ms"] = tuple(float(m.value) for m in ms)
         return res
 
     def finalize_runs(self, run_rows):

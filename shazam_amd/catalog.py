@@ -9,7 +9,14 @@ batches and folds the answers of both directions into one record per pair of son
 
 A pair (a, b), a < b, is reported with delta = off_b - off_a (b's frame under a's frame 0), the aligned count, both row
 counts and both coverages aligned / rows.  "same": both songs are covered; "a_in_b" / "b_in_a": one is (an excerpt inside a
-longer track); "overlap": neither, but enough rows align.  The clusters of "same" are what delete_songs() wants."""
+longer track); "overlap": neither, but enough rows align.  The clusters of "same" are what delete_songs() wants.
+
+Altered copies: a re-upload pitched up 3 %, a 25/24 video transfer, a rip from a drifting deck shares no
+hash with its original.  With speeds= / tempos= / pitches= / warps= (the ladders of speed.py) every listed song's rows are
+warped on the device at every rung (shz_match_songs_warps: a row is two peaks, both are moved and the key is formed again)
+and matched; fold_pairs_warps keeps, per pair, the strongest observation over both sides and all rungs, and says which
+song's rows were warped by which factors.  Votes are counted in ONE delta bin: a rung that misses the true factor by m
+spreads a song of T frames over about T m bins, so long tracks want a finer ladder than short ones."""
 from __future__ import annotations
 
 import numpy as np
@@ -21,10 +28,23 @@ import numpy as np
 # fifth of the longer track should stay "a_in_b" / "b_in_a".  Not measured: re-encoded or noisy copies, tracks of minutes.
 MIN_ALIGNED = 200
 MIN_COVERAGE = 0.8
-BATCH_ROWS = 1 << 22     # rows of the listed songs handed to one shz_match_songs call
+BATCH_ROWS = 1 << 22     # rows of the listed songs handed to one shz_match_songs call (with a ladder: rows x warps)
+# Thresholds of the warped search, set between the two distributions scripts/catalog_speed_bench.py measured on an MI355X
+# (4,000 music-like 10 s songs of about 3,190 rows, 80 copies resampled to speeds within +-5 %, the default
+# ladder of 71 rungs, the best of every pair over ALL rungs and both sides): no unrelated pair aligned more than 54 rows or
+# covered more than 0.018 of its smaller song; a planted copy ON a rung aligned at least 415 rows (coverage >= 0.131 of either
+# song), one HALF A STEP (0.07 %) beside a rung at least 154 (coverage >= 0.046).  A warped copy is never covered like an exact
+# one (resampling moves peaks), so "same" here means 0.03 of both songs, not 0.8.  The CPU oracle's figures for the 3-rung
+# catalogue of tests/test_gpu_find_duplicates_warps.py agree: unrelated <= 22, planted >= 426, coverage >= 0.13 on the warped
+# side.  A ladder gives every unrelated pair n_warps chances and both counts grow with the track: not measured on tracks of
+# minutes, on ladders of hundreds of rungs, on codec or phase-vocoder output.
+MIN_ALIGNED_WARPED = 100
+MIN_COVERAGE_WARPED = 0.03
 
 PAIR_FIELDS = (("a", np.uint32), ("b", np.uint32), ("delta", np.int64), ("aligned", np.uint32), ("rows_a", np.uint64),
                ("rows_b", np.uint64), ("coverage_a", np.float64), ("coverage_b", np.float64), ("relation", "U7"))
+WARP_PAIR_FIELDS = PAIR_FIELDS + (("tempo_q16", np.uint32), ("pitch_q16", np.uint32), ("warped", "U1"), ("aligned_plain", np.uint32))
+S_ONE = 65536
 
 
 def _table_of(db_or_table):
@@ -38,13 +58,63 @@ def _table_of(db_or_table):
     return table, db
 
 
-def match_songs(db_or_table, sids, topn: int = 5, full_sort: bool = False) -> dict:
+def _ladder_of(speeds, tempos, pitches, warps):
+    """None without a ladder keyword, else (t16, f16, row): the pair list as speed.recognize_speeds / recognize_warps read
+    their arguments -- speeds= is the diagonal, tempos= with pitches= their product (warp_grid, tempo-major; a missing one
+    is [65536]), warps=(t16, f16) an explicit pair list; row: pairs of one grid row (library calls take whole rows)."""
+    from .speed import _check_speeds, warp_grid
+    if speeds is None and tempos is None and pitches is None and warps is None:
+        return None
+    if speeds is not None:
+        if tempos is not None or pitches is not None or warps is not None:
+            raise TypeError("speeds= is one factor for both axes: it excludes tempos=, pitches= and warps=")
+        sp = _check_speeds(speeds)
+        return sp, sp.copy(), 1
+    if warps is not None:
+        if tempos is not None or pitches is not None:
+            raise TypeError("warps= is an explicit pair list: it excludes tempos= and pitches=")
+        t16, f16 = _check_speeds(warps[0], "warps[0]"), _check_speeds(warps[1], "warps[1]")
+        if len(t16) != len(f16):
+            raise ValueError("warps=(t16, f16): two lists of one length")
+        return t16, f16, 1
+    tl = np.asarray([S_ONE], np.uint32) if tempos is None else _check_speeds(tempos, "tempos")
+    pl = np.asarray([S_ONE], np.uint32) if pitches is None else _check_speeds(pitches, "pitches")
+    return (*warp_grid(tl, pl), max(len(pl), 1))
+
+
+def _match_songs_warps(table, sids, t16, f16, row, topn, full_sort=False, timings=False):
+    """Table.match_songs_warps over the whole pair list: lists longer than one library call (1,024 warps) go in chunks of
+    whole rows and are put side by side along the warp axis.  timings: "ms" is summed over the chunks."""
+    from .speed import warp_chunks
+    parts = [table.match_songs_warps(sids, t16[a:b], f16[a:b], topn=topn, full_sort=full_sort, timings=timings)
+             for a, b in warp_chunks(len(t16), row)]
+    if not parts:
+        raise ValueError("the ladder is empty")
+    out = {f: np.concatenate([p[f] for p in parts], axis=1) for f in ("sid", "delta", "aligned", "dedup", "nres", "nhash", "npairs")}
+    out["rows"] = parts[0]["rows"]
+    if timings:
+        out["ms"] = tuple(np.sum([p["ms"] for p in parts], axis=0).tolist())
+    return out
+
+
+def match_songs(db_or_table, sids, topn: int = 5, full_sort: bool = False, speeds=None, tempos=None, pitches=None,
+                warps=None) -> dict:
     """Every listed song matched against the rest of the table in one library call (shz_match_songs): the arrays of
     Table.match with one query per listed song and the song itself left out (sid, delta, aligned, dedup [n, topn]; nres,
     nhash, npairs [n]), plus rows [n], the songs' row counts.  delta is the found song's frame under the listed song's
-    frame 0."""
+    frame 0.
+    With a ladder (speeds= / tempos= + pitches= / warps=, Q16 as in speed.py) every song's rows are warped at every pair
+    first (shz_match_songs_warps): the arrays gain a warp axis behind the song axis ([n, n_warps, topn] / [n, n_warps]),
+    "tempo_q16" / "pitch_q16" [n_warps] name the pairs, rows stay the unwarped counts, nhash is the distinct warped rows
+    and delta is the found song's frame under the listed song's WARPED frame 0."""
     table, _ = _table_of(db_or_table)
-    return table.match_songs(sids, topn=topn, full_sort=full_sort)
+    lad = _ladder_of(speeds, tempos, pitches, warps)
+    if lad is None:
+        return table.match_songs(sids, topn=topn, full_sort=full_sort)
+    t16, f16, row = lad
+    out = _match_songs_warps(table, sids, t16, f16, row, topn, full_sort)
+    out["tempo_q16"], out["pitch_q16"] = t16, f16
+    return out
 
 
 def _clusters(a: np.ndarray, b: np.ndarray) -> list:
@@ -121,18 +191,146 @@ def fold_pairs(sids, sid, delta, aligned, nres, song_ids, song_rows, min_aligned
     return {"pairs": pairs, "clusters": _clusters(pairs["a"][same], pairs["b"][same])}
 
 
-def find_duplicates(db_or_table, sids=None, topn: int = 5, min_aligned: int = MIN_ALIGNED, min_coverage: float = MIN_COVERAGE,
-                    batch_rows: int = BATCH_ROWS) -> dict:
+def _rows_lookup(song_ids, song_rows, who):
+    ids = np.asarray(song_ids, np.int64).reshape(-1)
+    rows = np.asarray(song_rows, np.uint64).reshape(-1)
+    by = np.argsort(ids, kind="stable")
+    ids, rows = ids[by], rows[by]
+
+    def rows_of(x):
+        at = np.searchsorted(ids, x)
+        if len(x) and (at.max(initial=0) >= len(ids) or not np.array_equal(ids[at], x)):
+            raise ValueError(f"{who}: a song without a row count")
+        return rows[at] if len(x) else np.zeros(0, np.uint64)
+
+    return rows_of
+
+
+def fold_pairs_warps(sids, tempo_q16, pitch_q16, sid, delta, aligned, nres, song_ids, song_rows,
+                     min_aligned=MIN_ALIGNED_WARPED, min_coverage=MIN_COVERAGE_WARPED) -> dict:
+    """The answers of match_songs at a ladder folded into one record per unordered pair of songs -- plain numpy, no GPU.
+
+    sids [n]: the listed songs; tempo_q16 / pitch_q16 [K]: the warps; sid / delta / aligned [n, K, topn], nres [n, K]: what
+    match_songs said about every (song, warp).  song_ids / song_rows: the plain row count of every song that occurs.
+    Returns {"pairs": structured array of WARP_PAIR_FIELDS ordered by (a, b), "clusters": list of id lists}.
+    Every (listed song, warp, rank) is an OBSERVATION of the pair it names.  Per pair a < b the kept observation is the one
+    with the greatest aligned count over both sides and all warps; ties go to the smaller |t16 - 65536| + |f16 - 65536|, then
+    to a's side, then to the lower warp index.  tempo_q16 / pitch_q16 are that observation's warp and warped says whose rows
+    it warped ("a" or "b": that song runs t16 / 65536 times as fast and sounds f16 / 65536 times as high as the other).
+    delta is as that side reported it -- the other song's frame under the warped song's WARPED frame 0 -- with the sign
+    turned when the side is b.  aligned_plain: the pair's greatest count at the warp (65536, 65536) if the ladder holds
+    it, else 0 -- what the plain find_duplicates would have seen.  Coverages are aligned / rows with the PLAIN row counts.
+    Pairs with aligned < min_aligned are dropped; relations and clusters as in fold_pairs."""
+    dt = np.dtype(list(WARP_PAIR_FIELDS))
+    sids = np.asarray(sids, np.int64).reshape(-1)
+    t16, f16 = np.asarray(tempo_q16, np.int64).reshape(-1), np.asarray(pitch_q16, np.int64).reshape(-1)
+    n, K = len(sids), len(t16)
+    if len(f16) != K:
+        raise ValueError("tempo_q16 and pitch_q16 are two lists of one length")
+    if n == 0 or K == 0:
+        return {"pairs": np.zeros(0, dt), "clusters": []}
+    sid = np.asarray(sid, np.int64).reshape(n, K, -1)
+    delta = np.asarray(delta, np.int64).reshape(n, K, -1)
+    aligned = np.asarray(aligned, np.int64).reshape(n, K, -1)
+    nres = np.asarray(nres, np.int64).reshape(n, K)
+    valid = np.arange(sid.shape[2])[None, None, :] < nres[:, :, None]
+    me = np.broadcast_to(sids[:, None, None], sid.shape)[valid]
+    v = np.broadcast_to(np.arange(K)[None, :, None], sid.shape)[valid]
+    other, d, al = sid[valid], delta[valid], aligned[valid]
+    keep = me != other
+    me, v, other, d, al = me[keep], v[keep], other[keep], d[keep], al[keep]
+    mine = me < other                               # the listed (warped) song is a: its side, delta as reported
+    a, b = np.where(mine, me, other), np.where(mine, other, me)
+    d = np.where(mine, d, -d)
+    dist = np.abs(t16 - S_ONE) + np.abs(f16 - S_ONE)
+    plain = np.where(dist[v] == 0, al, 0)
+    order = np.lexsort((v, ~mine, dist[v], -al, b, a))   # per (a, b): the kept observation first
+    a, b, d, al, v, mine, plain = a[order], b[order], d[order], al[order], v[order], mine[order], plain[order]
+    first = np.ones(len(a), bool)
+    first[1:] = (a[1:] != a[:-1]) | (b[1:] != b[:-1])
+    start = np.flatnonzero(first)
+    plain = np.maximum.reduceat(plain, start) if len(start) else plain[:0]
+    a, b, d, al, v, mine = a[first], b[first], d[first], al[first], v[first], mine[first]
+    ok = al >= min_aligned
+    a, b, d, al, v, mine, plain = a[ok], b[ok], d[ok], al[ok], v[ok], mine[ok], plain[ok]
+    rows_of = _rows_lookup(song_ids, song_rows, "fold_pairs_warps")
+    pairs = np.zeros(len(a), dt)
+    pairs["a"], pairs["b"], pairs["delta"], pairs["aligned"] = a, b, d, al
+    pairs["rows_a"], pairs["rows_b"] = rows_of(a), rows_of(b)
+    pairs["tempo_q16"], pairs["pitch_q16"] = t16[v], f16[v]
+    pairs["warped"] = np.where(mine, "a", "b")
+    pairs["aligned_plain"] = plain
+    with np.errstate(divide="ignore", invalid="ignore"):
+        pairs["coverage_a"] = al / pairs["rows_a"].astype(np.float64)
+        pairs["coverage_b"] = al / pairs["rows_b"].astype(np.float64)
+    ca, cb = pairs["coverage_a"] >= min_coverage, pairs["coverage_b"] >= min_coverage
+    pairs["relation"] = np.where(ca & cb, "same", np.where(ca, "a_in_b", np.where(cb, "b_in_a", "overlap")))
+    same = pairs["relation"] == "same"
+    return {"pairs": pairs, "clusters": _clusters(pairs["a"][same], pairs["b"][same])}
+
+
+def _batches(rows, live, budget):
+    """the live songs cut into the longest runs within the budget of rows, one song at least"""
+    parts, lo = [], 0
+    cum = np.cumsum(rows[live])
+    while lo < len(live):
+        base = cum[lo - 1] if lo else 0
+        hi = max(lo + 1, int(np.searchsorted(cum, base + int(budget), "right")))
+        parts.append(live[lo:hi])
+        lo = hi
+    return parts
+
+
+def _find_duplicates_warps(table, sids, lad, topn, min_aligned, min_coverage, batch_rows, timings=False):
+    from .speed import MAX_WARPS
+    t16, f16, row = lad
+    min_aligned = MIN_ALIGNED_WARPED if min_aligned is None else min_aligned
+    min_coverage = MIN_COVERAGE_WARPED if min_coverage is None else min_coverage
+    row_off, _, _ = table.song_hashes(sids, counts_only=True)
+    rows = np.diff(row_off.astype(np.int64))
+    live = np.flatnonzero(rows > 0)
+    per_call = max(1, min(len(t16), (MAX_WARPS // row) * row))      # warps of one library call
+    parts = _batches(rows, live, max(int(batch_rows) // per_call, 1))   # a batch: at most batch_rows rows x warps
+    res = [_match_songs_warps(table, sids[p], t16, f16, row, topn, timings=timings) for p in parts]
+    if not res:
+        out = fold_pairs_warps([], t16, f16, [], [], [], [], [], [], min_aligned, min_coverage)
+    else:
+        listed = np.concatenate([sids[p] for p in parts])
+        cat = {f: np.concatenate([r[f] for r in res]) for f in ("sid", "delta", "aligned", "nres", "rows")}
+        valid = np.arange(topn)[None, None, :] < cat["nres"][:, :, None].astype(np.int64)
+        found = np.setdiff1d(np.unique(cat["sid"][valid]), listed)
+        f_off, _, _ = table.song_hashes(found, counts_only=True)
+        out = fold_pairs_warps(listed, t16, f16, cat["sid"], cat["delta"], cat["aligned"], cat["nres"],
+                               np.concatenate([listed, found]), np.concatenate([cat["rows"], np.diff(f_off)]),
+                               min_aligned, min_coverage)
+    if timings:
+        out["ms"] = tuple(np.sum([r["ms"] for r in res], axis=0).tolist()) if res else (0.0, 0.0, 0.0)
+    return out
+
+
+def find_duplicates(db_or_table, sids=None, topn: int = 5, min_aligned: int = None, min_coverage: float = None,
+                    batch_rows: int = BATCH_ROWS, speeds=None, tempos=None, pitches=None, warps=None, timings: bool = False) -> dict:
     """Duplicate, contained and overlapping tracks among the listed songs (None: every song of the table) and the rest of
     the table.  The songs are walked in batches of at most batch_rows rows (one counts-only gather gives the row counts),
     each batch is one match_songs call, and fold_pairs makes one record per pair.  Returns its dict: "pairs" and
     "clusters" -- delete_songs(cluster[1:]) keeps the smallest id of every set of copies.  A pair is found when either
-    song lists the other among its topn strongest; raise topn for catalogues with many copies of one recording."""
+    song lists the other among its topn strongest; raise topn for catalogues with many copies of one recording.
+    min_aligned / min_coverage = None: MIN_ALIGNED / MIN_COVERAGE.
+    With a ladder (speeds= / tempos= + pitches= / warps=, as match_songs reads them) sped-up, slowed-down and pitch-shifted
+    copies are found too: every batch -- at most batch_rows rows x warps -- is matched at every pair, fold_pairs_warps makes
+    the records (WARP_PAIR_FIELDS: which song's rows were warped, by which factors, and the plain count), and the
+    thresholds default to MIN_ALIGNED_WARPED / MIN_COVERAGE_WARPED.  Put 65536 on the ladder (speed_ladder does) to keep
+    the exact copies in the same answer.  timings (ladder only): "ms" = (gather, warp, match) device times, summed."""
     table, _ = _table_of(db_or_table)
+    lad = _ladder_of(speeds, tempos, pitches, warps)
+    min_aligned = (MIN_ALIGNED if min_aligned is None else min_aligned) if lad is None else min_aligned
+    min_coverage = (MIN_COVERAGE if min_coverage is None else min_coverage) if lad is None else min_coverage
     if sids is None:
         from .shard import table_maxima
         sids = np.arange(1, table_maxima(table)[0] + 1, dtype=np.uint32) if table.rows()[0] else np.zeros(0, np.uint32)
     sids = np.ascontiguousarray(sids, np.uint32).reshape(-1)
+    if lad is not None:
+        return _find_duplicates_warps(table, sids, lad, topn, min_aligned, min_coverage, batch_rows, timings)
     row_off, _, _ = table.song_hashes(sids, counts_only=True)
     rows = np.diff(row_off.astype(np.int64))
     live = np.flatnonzero(rows > 0)                  # (songs without rows match nothing)

@@ -348,3 +348,424 @@ extern "C" int32_t shz_match_songs(shz_ctx* ctx, shz_table* t, const uint32_t* s
   }
   return SHZ_OK;
 }
+
+// ---- the row warp: sped-up and pitch-shifted copies inside the table -----------------------------------
+// The table holds no peaks, but a row IS two peaks: key32 = f1 << 20 | f2 << 8 | dt at offset t1 is (f1, t1) and (f2, t1 + dt).
+// Both are moved by the integer maps of shz_warp_pair_hash_tf (sp_warp_f, and the time map in 64 bits) and the key is formed
+// again; a row leaves where a frequency leaves the spectrogram or dt' passes 200.  Elementwise: no sort, no fan_value.
+//
+// Work is laid out over (song q, warp v, row r) items, song-major, then warp-major, then the song's rows (sp_decode's
+// layout): (q, v) is one contiguous query of the match, and a wave stays at one warp over consecutive rows.  The compaction
+// is sg_count_kernel / sg_write_kernel's: blocks of RW_ITEMS items, one wave a block; pass 1 ballots, writes one count per
+// block and adds the kept items to their (q, v) count (one add a wave where the wave lies inside one (q, v)); the block
+// counts are scanned; pass 2 repeats the map and writes at block base + rank inside the ballot.  No atomic decides a place.
+#define RW_ITEMS 512u   // items of a block
+#define RW_LOADS 8      // RW_ITEMS / 64
+#define RW_WAVES 4      // blocks (waves) of a workgroup
+#define RW_SMALL_WARPS 2u   // warps of a slice (of one song) under SHZ_DEBUG_CATALOG_SMALL_SLICES
+
+// THE map: row (key32, off) under the warp (t16, f16) -> kept?, and (*okey, *ooff) where kept (off t16 < 2^48 is the
+// caller's promise: t1' is stored in 32 bits).  The kernels and shz_warp_row_host both call it
+__host__ __device__ __forceinline__ bool rw_warp_row(uint32_t key32, uint32_t off, uint32_t t16, uint32_t f16, uint32_t* okey,
+                                                     uint32_t* ooff) {
+  const uint32_t f1 = key32 >> 20, f2 = (key32 >> 8) & 0xFFFu, dt = key32 & 0xFFu;
+  const uint64_t t1 = ((uint64_t)off * t16 + 32768u) >> 16, t2 = (((uint64_t)off + dt) * t16 + 32768u) >> 16;
+  const uint32_t g1 = sp_warp_f(f1, f16), g2 = sp_warp_f(f2, f16), d = (uint32_t)(t2 - t1);
+  *okey = (g1 << 20) | (g2 << 8) | d;
+  *ooff = (uint32_t)t1;
+  return g1 <= SP_F_MAX && g2 <= SP_F_MAX && d <= SHZ_MAX_DT;
+}
+
+struct rw_view {                   // what the kernels of one slice read (device pointers)
+  const uint32_t *key, *off;       // the rows of all songs of the call, song after song
+  const uint64_t* roff;            // CSR of the songs over them, from 0
+  const uint32_t *tempo, *pitch;   // the call's warps
+  uint32_t q0, nq, v0, K;          // the slice: songs [q0, q0 + nq) at the warps [v0, v0 + K)
+  uint64_t n_items;                // rows of those songs x K
+};
+struct rw_cursor {
+  uint32_t q, v, r, n;             // song and warp (of the slice), row of the song, rows of the song
+  uint64_t row0;                   // the song's first row
+};
+
+// item w < n_items -> its song (the last q whose first item is <= w: empty songs share a start), warp and row
+__device__ __forceinline__ void rw_seek(const rw_view& V, uint64_t w, rw_cursor* c) {
+  const uint64_t r00 = V.roff[V.q0];
+  uint32_t lo = 0, hi = V.nq;
+  while (lo + 1 < hi) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if ((V.roff[V.q0 + mid] - r00) * V.K <= w) lo = mid; else hi = mid;
+  }
+  const uint64_t r0 = V.roff[V.q0 + lo];
+  const uint32_t n = (uint32_t)(V.roff[V.q0 + lo + 1] - r0);   // (> 0: w lies inside the song's items)
+  const uint32_t rem = (uint32_t)(w - (r0 - r00) * V.K), v = rem / max(n, 1u);
+  c->q = lo;
+  c->v = min(v, V.K - 1);
+  c->r = min(rem - v * n, max(n, 1u) - 1);   // (the clamps hold for every consistent view; they keep any read inside the columns)
+  c->n = n;
+  c->row0 = r0;
+}
+
+// the RW_LOADS items of this lane in block blk: rows loaded, (q, v) kept as segment and warp; dead lanes: seg = ~0
+__device__ __forceinline__ void rw_load(const rw_view& V, uint64_t w0, uint32_t lane, uint32_t* k, uint32_t* o, uint32_t* seg,
+                                        uint32_t* vv) {
+  rw_cursor c{0, 0, 0, 0, 0};
+#pragma unroll
+  for (int j = 0; j < RW_LOADS; ++j) {
+    const uint64_t w = w0 + (uint64_t)j * 64 + lane;
+    seg[j] = 0xFFFFFFFFu;
+    k[j] = o[j] = vv[j] = 0;
+    if (w >= V.n_items) continue;
+    if (j == 0 || c.r + 64 >= c.n) rw_seek(V, w, &c);   // (64 items on: still inside this song's rows at this warp?)
+    else c.r += 64;
+    if (c.n == 0) continue;
+    k[j] = V.key[c.row0 + c.r];
+    o[j] = V.off[c.row0 + c.r];
+    seg[j] = c.q * V.K + c.v;
+    vv[j] = V.v0 + c.v;
+  }
+}
+
+// pass 1: kept items of every block, kept items of every (song, warp)
+__global__ __launch_bounds__(64 * RW_WAVES) void rw_count_kernel(rw_view V, uint32_t* __restrict__ blk_cnt,
+                                                                  uint32_t* __restrict__ seg_cnt) {
+  const uint32_t lane = threadIdx.x & 63;
+  const uint64_t blk = (uint64_t)blockIdx.x * RW_WAVES + (threadIdx.x >> 6);
+  const uint64_t w0 = blk * RW_ITEMS;
+  if (w0 >= V.n_items) return;   // uniform in the wave
+  uint32_t k[RW_LOADS], o[RW_LOADS], seg[RW_LOADS], vv[RW_LOADS];
+  rw_load(V, w0, lane, k, o, seg, vv);
+  uint32_t c = 0;
+#pragma unroll
+  for (int j = 0; j < RW_LOADS; ++j) {
+    const bool live = seg[j] != 0xFFFFFFFFu;
+    uint32_t a, b;
+    const bool keep = live && rw_warp_row(k[j], o[j], V.tempo[vv[j]], V.pitch[vv[j]], &a, &b);
+    const uint64_t m = __ballot(keep);
+    const uint32_t first = (uint32_t)__shfl((int)seg[j], 0, 64);   // (live lanes are a prefix of the wave)
+    if (__ballot(live && seg[j] != first) == 0) {   // the wave inside one (song, warp): one add
+      if (lane == 0 && m) atomicAdd(seg_cnt + first, (uint32_t)__popcll(m));
+    } else if (keep) {
+      atomicAdd(seg_cnt + seg[j], 1u);
+    }
+    c += (uint32_t)__popcll(m);
+  }
+  if (lane == 0) blk_cnt[blk] = c;
+}
+
+// pass 2: every kept item, in item order, at the place the scan of the block counts gives (no store at or beyond cap)
+__global__ __launch_bounds__(64 * RW_WAVES) void rw_write_kernel(rw_view V, const uint32_t* __restrict__ blk_pos,
+                                                                  uint32_t* __restrict__ out_key, uint32_t* __restrict__ out_off,
+                                                                  uint64_t cap) {
+  const uint32_t lane = threadIdx.x & 63;
+  const uint64_t blk = (uint64_t)blockIdx.x * RW_WAVES + (threadIdx.x >> 6);
+  const uint64_t w0 = blk * RW_ITEMS;
+  if (w0 >= V.n_items) return;   // uniform in the wave
+  uint32_t k[RW_LOADS], o[RW_LOADS], seg[RW_LOADS], vv[RW_LOADS];
+  rw_load(V, w0, lane, k, o, seg, vv);
+  uint64_t base = blk_pos[blk];
+#pragma unroll
+  for (int j = 0; j < RW_LOADS; ++j) {
+    uint32_t a, b;
+    const bool keep = seg[j] != 0xFFFFFFFFu && rw_warp_row(k[j], o[j], V.tempo[vv[j]], V.pitch[vv[j]], &a, &b);
+    const uint64_t m = __ballot(keep);
+    if (keep) {
+      const uint64_t pos = base + (uint64_t)__popcll(m & ((1ull << lane) - 1ull));
+      if (pos < cap) { out_key[pos] = a; out_off[pos] = b; }
+    }
+    base += (uint64_t)__popcll(m);
+  }
+}
+
+namespace {
+
+struct rw_tabs {
+  const uint64_t* d_roff = nullptr;
+  const uint32_t *d_tempo = nullptr, *d_pitch = nullptr;
+};
+struct rw_pass {
+  rw_view V;
+  uint64_t n_blk = 0;
+  uint32_t* d_blk = nullptr;
+};
+
+static inline uint64_t rw_blocks(uint64_t n) { return (n + RW_ITEMS - 1) / RW_ITEMS; }
+
+// CSR of the songs (from 0) | tempo | pitch on the device: one block of the call
+int32_t rw_upload(shz_ctx* ctx, const uint64_t* row_off, uint32_t n_songs, const uint32_t* tempo_q16, const uint32_t* pitch_q16,
+                  uint32_t K, rw_tabs* T) {
+  const uint64_t ro_bytes = ((uint64_t)n_songs + 1) * 8, tab_bytes = (uint64_t)K * 4, bytes = ro_bytes + 2 * tab_bytes;
+  std::vector<char> h(bytes);
+  uint64_t* hr = (uint64_t*)h.data();
+  for (uint32_t q = 0; q <= n_songs; ++q) hr[q] = row_off[q] - row_off[0];
+  memcpy(h.data() + ro_bytes, tempo_q16, tab_bytes);
+  memcpy(h.data() + ro_bytes + tab_bytes, pitch_q16, tab_bytes);
+  void* d;
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_RW_TAB, bytes, &d));
+  SHZ_HIP(ctx, shz_memcpy(ctx, d, h.data(), bytes, hipMemcpyHostToDevice));
+  T->d_roff = (const uint64_t*)d;
+  T->d_tempo = (const uint32_t*)((char*)d + ro_bytes);
+  T->d_pitch = T->d_tempo + K;
+  return SHZ_OK;
+}
+
+// pass 1 and the scan of one slice -- songs [q0, q0 + nq) at the warps [v0, v0 + kv) of rows that lie in d_key / d_off:
+// seg_off[nq kv + 1] (host) is the exact CSR of the (song, warp) segments, relative to the slice.  The stream is idle on
+// return.  A slice without rows launches nothing
+int32_t rw_count(shz_ctx* ctx, const rw_tabs& T, const uint32_t* d_key, const uint32_t* d_off, const uint64_t* row_off, uint32_t q0,
+                 uint32_t nq, uint32_t v0, uint32_t kv, rw_pass* P, uint64_t* seg_off) {
+  const uint64_t n_seg = (uint64_t)nq * kv, n_items = (row_off[q0 + nq] - row_off[q0]) * kv;
+  for (uint64_t e = 0; e <= n_seg; ++e) seg_off[e] = 0;
+  P->V = rw_view{d_key, d_off, T.d_roff, T.d_tempo, T.d_pitch, q0, nq, v0, kv, n_items};
+  P->n_blk = rw_blocks(n_items);
+  if (n_items == 0) return SHZ_OK;
+  void *d_blk, *d_cnt;
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_RW_BLK, P->n_blk * 4, &d_blk));
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_RW_CNT, n_seg * 4, &d_cnt));
+  P->d_blk = (uint32_t*)d_blk;
+  SHZ_HIP(ctx, hipMemsetAsync(d_cnt, 0, n_seg * 4, ctx->stream));
+  hipLaunchKernelGGL(rw_count_kernel, dim3((unsigned)((P->n_blk + RW_WAVES - 1) / RW_WAVES)), dim3(64 * RW_WAVES), 0, ctx->stream,
+                     P->V, P->d_blk, (uint32_t*)d_cnt);
+  SHZ_HIP(ctx, hipGetLastError());
+  SHZ_TRY(shz_scan_u32(ctx, P->d_blk, P->d_blk, P->n_blk, nullptr));
+  std::vector<uint32_t> cnt(n_seg);
+  SHZ_HIP(ctx, shz_memcpy(ctx, cnt.data(), d_cnt, n_seg * 4, hipMemcpyDeviceToHost));
+  SHZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  for (uint64_t e = 0; e < n_seg; ++e) seg_off[e + 1] = seg_off[e] + cnt[e];
+  return SHZ_OK;
+}
+
+int32_t rw_write(shz_ctx* ctx, const rw_pass& P, uint32_t* d_okey, uint32_t* d_ooff, uint64_t cap) {
+  if (P.V.n_items == 0) return SHZ_OK;
+  hipLaunchKernelGGL(rw_write_kernel, dim3((unsigned)((P.n_blk + RW_WAVES - 1) / RW_WAVES)), dim3(64 * RW_WAVES), 0, ctx->stream,
+                     P.V, (const uint32_t*)P.d_blk, d_okey, d_ooff, cap);
+  SHZ_HIP(ctx, hipGetLastError());
+  return SHZ_OK;
+}
+
+}  // namespace
+
+extern "C" int32_t shz_warp_row_host(const uint32_t* key32, const uint32_t* off, uint64_t n, uint32_t t16, uint32_t f16,
+                                     uint32_t* out_key32, uint32_t* out_off, uint8_t* out_keep) {
+  if (t16 < SP_S_MIN || t16 > SP_S_MAX || f16 < SP_S_MIN || f16 > SP_S_MAX) return SHZ_E_INVALID;
+  if (n && (!key32 || !off || !out_key32 || !out_off || !out_keep)) return SHZ_E_INVALID;
+  for (uint64_t i = 0; i < n; ++i) {
+    uint32_t a, b;
+    const bool keep = rw_warp_row(key32[i], off[i], t16, f16, &a, &b);
+    out_key32[i] = keep ? a : 0u;
+    out_off[i] = keep ? b : 0u;
+    out_keep[i] = keep ? 1 : 0;
+  }
+  return SHZ_OK;
+}
+
+extern "C" int32_t shz_warp_rows(shz_ctx* ctx, const uint32_t* key32, const uint32_t* off, const uint64_t* row_off, uint32_t n_songs,
+                                 const uint32_t* tempo_q16, const uint32_t* pitch_q16, uint32_t n_warps, uint32_t flags,
+                                 uint32_t* out_key32, uint32_t* out_off, uint64_t* out_row_off, uint64_t cap, uint64_t* count) {
+  if (!ctx) return SHZ_E_INVALID;
+  if (count) *count = 0;
+  // everything that can be refused is refused before the first launch
+  if (flags & ~(SHZ_IN_DEVICE | SHZ_OUT_DEVICE)) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_warp_rows: flags may hold SHZ_IN_DEVICE and SHZ_OUT_DEVICE");
+  SHZ_TRY(sp_check_ladder(ctx, "shz_warp_rows", "n_warps", "tempo", tempo_q16, "pitch", pitch_q16, n_warps, 1));
+  if (!row_off) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_warp_rows: row_off is NULL");
+  for (uint32_t q = 0; q < n_songs; ++q)
+    if (row_off[q + 1] < row_off[q]) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_warp_rows: row_off decreases at song %u", q);
+  const uint64_t n = row_off[n_songs] - row_off[0], n_seg = (uint64_t)n_songs * n_warps;
+  if (n && (!key32 || !off)) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_warp_rows: NULL buffer");
+  if (cap && (!out_key32 || !out_off)) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_warp_rows: NULL buffer");
+  if (n >= (1ull << 32) || n * n_warps >= (1ull << 32))
+    SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "shz_warp_rows: %llu rows x %u warps in one call (limit 2^32 - 1 items)", (unsigned long long)n, n_warps);
+  if (out_row_off) memset(out_row_off, 0, (n_seg + 1) * 8);
+  if (n == 0) return SHZ_OK;
+  SHZ_HIP(ctx, hipSetDevice(ctx->device));
+  sg_bufs own;
+  const uint32_t *d_key = key32 + row_off[0], *d_off = off + row_off[0];
+  if (!(flags & SHZ_IN_DEVICE)) {
+    uint32_t *a = (uint32_t*)own.get(n * 4), *b = (uint32_t*)own.get(n * 4);
+    if (!a || !b) SHZ_FAIL(ctx, SHZ_E_NOMEM, "shz_warp_rows: hipMalloc(2 x %llu) failed", (unsigned long long)(n * 4));
+    SHZ_HIP(ctx, shz_memcpy(ctx, a, d_key, n * 4, hipMemcpyHostToDevice));
+    SHZ_HIP(ctx, shz_memcpy(ctx, b, d_off, n * 4, hipMemcpyHostToDevice));
+    d_key = a;
+    d_off = b;
+  }
+  rw_tabs T;
+  SHZ_TRY(rw_upload(ctx, row_off, n_songs, tempo_q16, pitch_q16, n_warps, &T));
+  std::vector<uint64_t> rel((size_t)n_songs + 1), so((size_t)n_seg + 1, 0);
+  for (uint32_t q = 0; q <= n_songs; ++q) rel[q] = row_off[q] - row_off[0];
+  rw_pass P;
+  int32_t rc = rw_count(ctx, T, d_key, d_off, rel.data(), 0, n_songs, 0, n_warps, &P, so.data());
+  if (rc != SHZ_OK) { (void)hipStreamSynchronize(ctx->stream); return rc; }   // (queued work may read the staged columns)
+  const uint64_t total = so[n_seg];
+  if (out_row_off) memcpy(out_row_off, so.data(), (n_seg + 1) * 8);
+  if (count) *count = total;
+  if (total > cap) SHZ_FAIL(ctx, SHZ_E_CAPACITY, "shz_warp_rows: need %llu rows", (unsigned long long)total);
+  if (total == 0) return SHZ_OK;
+  uint32_t *d_ok = out_key32, *d_oo = out_off;
+  if (!(flags & SHZ_OUT_DEVICE)) {
+    d_ok = (uint32_t*)own.get(total * 4);
+    d_oo = (uint32_t*)own.get(total * 4);
+    if (!d_ok || !d_oo) SHZ_FAIL(ctx, SHZ_E_NOMEM, "shz_warp_rows: hipMalloc(2 x %llu) failed", (unsigned long long)(total * 4));
+  }
+  rc = rw_write(ctx, P, d_ok, d_oo, (flags & SHZ_OUT_DEVICE) ? cap : total);
+  if (rc == SHZ_OK && !(flags & SHZ_OUT_DEVICE)) {
+    if (shz_memcpy(ctx, out_key32, d_ok, total * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+        shz_memcpy(ctx, out_off, d_oo, total * 4, hipMemcpyDeviceToHost) != hipSuccess) {
+      ctx->err = "shz_warp_rows: copy of the warped rows failed";
+      rc = SHZ_E_HIP;
+    }
+  }
+  if (hipStreamSynchronize(ctx->stream) != hipSuccess && rc == SHZ_OK) { ctx->err = "shz_warp_rows: hipStreamSynchronize failed"; rc = SHZ_E_HIP; }
+  return rc;   // (the call's buffers are freed on return: the stream is idle)
+}
+
+namespace {
+struct rw_slice { uint32_t q0, nq, v0, kv; };
+}
+
+extern "C" int32_t shz_match_songs_warps(shz_ctx* ctx, shz_table* t, const uint32_t* sids, uint32_t n_sids, uint32_t topn,
+                                         const uint32_t* tempo_q16, const uint32_t* pitch_q16, uint32_t n_warps, uint32_t flags,
+                                         uint64_t* out_rows, uint32_t* out_sid, int32_t* out_delta, uint32_t* out_aligned,
+                                         uint32_t* out_dedup, uint32_t* out_nres, uint32_t* out_nhash, uint64_t* out_npairs,
+                                         float* ms_gather, float* ms_warp, float* ms_match) {
+  if (!ctx || !t) return SHZ_E_INVALID;
+  if (ms_gather) *ms_gather = 0.f;
+  if (ms_warp) *ms_warp = 0.f;
+  if (ms_match) *ms_match = 0.f;
+  if (t->ctx != ctx) SHZ_FAIL(ctx, SHZ_E_INVALID, "table belongs to another ctx");
+  if (topn < 1 || topn > 63) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_match_songs_warps: topn must be in [1,63]");
+  if (flags & ~SHZ_MATCH_FULL_SORT) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_match_songs_warps: flags may hold SHZ_MATCH_FULL_SORT");
+  SHZ_TRY(sp_check_ladder(ctx, "shz_match_songs_warps", "n_warps", "tempo", tempo_q16, "pitch", pitch_q16, n_warps, 1));
+  if (n_sids == 0) return SHZ_OK;
+  if (!out_sid || !out_delta || !out_aligned || !out_dedup || !out_nres) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_match_songs_warps: NULL buffer");
+  SHZ_TRY(shz_match_ready(ctx, t, topn + 1));
+  const uint32_t K = n_warps, w = topn + 1;
+  const uint32_t t16_max = *std::max_element(tempo_q16, tempo_q16 + K);   // (time alone: the bias bound)
+  const bool timed = ms_gather || ms_warp || ms_match;
+  if (timed) {
+    SHZ_HIP(ctx, hipSetDevice(ctx->device));
+    for (hipEvent_t& e : ctx->sp_ev)
+      if (!e) SHZ_HIP(ctx, hipEventCreate(&e));
+    SHZ_HIP(ctx, hipEventRecord(ctx->sp_ev[0], ctx->stream));
+  }
+  // 1) the rows of the listed songs into columns of this call (the match uses the workspace)
+  song_gather G;
+  std::vector<uint64_t> row_off((uint64_t)n_sids + 1);
+  SHZ_TRY(sg_prepare(t, "shz_match_songs_warps", sids, n_sids, row_off.data(), &G));
+  if (G.total >= (1ull << 32))
+    SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "shz_match_songs_warps: %llu rows in one call (limit 2^32 - 1); list fewer songs", (unsigned long long)G.total);
+  const uint64_t nv = (uint64_t)n_sids * K;
+  for (uint64_t i = 0; i < nv * topn; ++i) { out_sid[i] = 0; out_delta[i] = 0; out_aligned[i] = 0; out_dedup[i] = 0; }
+  for (uint64_t i = 0; i < nv; ++i) {
+    out_nres[i] = 0;
+    if (out_nhash) out_nhash[i] = 0;
+    if (out_npairs) out_npairs[i] = 0;
+  }
+  if (out_rows)
+    for (uint32_t q = 0; q < n_sids; ++q) out_rows[q] = row_off[q + 1] - row_off[q];
+  if (G.total == 0) return SHZ_OK;   // (no listed song has a row: nothing to look up, every count stays zero)
+  // 2) the slices, from the row counts alone: whole songs x a contiguous chunk of warps whose items (8 bytes each in the
+  // call's buffers) stay within 1/8 of the workspace limit and the match's 2^28-pair budget, and below 2^32; the ladder is
+  // cut only where one song at all warps is beyond that, and a song at one warp is never split
+  const uint64_t max_items = std::min<uint64_t>(std::max<uint64_t>(ctx->ws_limit / 64, 1), 1ull << 28);
+  const uint64_t max_seg = 1ull << 24;
+  const bool small = (ctx->debug & SHZ_DEBUG_CATALOG_SMALL_SLICES) != 0;
+  std::vector<rw_slice> plan;
+  uint64_t buf_items = 0;
+  for (uint32_t q0 = 0; q0 < n_sids;) {
+    const uint64_t r0 = row_off[q0 + 1] - row_off[q0];
+    if (small || r0 * K > max_items) {   // one song, its warps in chunks
+      const uint32_t kv = small ? RW_SMALL_WARPS : (uint32_t)std::max<uint64_t>(max_items / std::max<uint64_t>(r0, 1), 1);
+      for (uint32_t v0 = 0; v0 < K; v0 += kv) {
+        const uint32_t k = std::min(kv, K - v0);
+        plan.push_back({q0, 1, v0, k});
+        buf_items = std::max(buf_items, r0 * k);
+      }
+      ++q0;
+      continue;
+    }
+    uint32_t nq = 1;
+    while (q0 + nq < n_sids && (uint64_t)(nq + 1) * K <= max_seg && (row_off[q0 + nq + 1] - row_off[q0]) * K <= max_items) ++nq;
+    plan.push_back({q0, nq, 0, K});
+    buf_items = std::max(buf_items, (row_off[q0 + nq] - row_off[q0]) * K);
+    q0 += nq;
+  }
+  if (buf_items >= (1ull << 32))
+    SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "shz_match_songs_warps: a song of %llu rows (limit 2^32 - 1 warped rows a slice)", (unsigned long long)buf_items);
+  // the call's buffers, once: the gathered columns, the largest offset, the warped columns of the largest slice
+  sg_bufs own;
+  uint32_t *d_key = (uint32_t*)own.get(G.total * 4), *d_off = (uint32_t*)own.get(G.total * 4), *d_max = (uint32_t*)own.get(4);
+  uint32_t *d_wkey = (uint32_t*)own.get(buf_items * 4), *d_woff = (uint32_t*)own.get(buf_items * 4);
+  if (!d_key || !d_off || !d_max || !d_wkey || !d_woff)
+    SHZ_FAIL(ctx, SHZ_E_NOMEM, "shz_match_songs_warps: hipMalloc(2 x %llu + 2 x %llu) failed", (unsigned long long)(G.total * 4), (unsigned long long)(buf_items * 4));
+  uint32_t max_off = 0;
+  SHZ_HIP(ctx, hipMemsetAsync(d_max, 0, 4, ctx->stream));
+  SHZ_TRY(sg_fill(G, "shz_match_songs_warps", d_key, d_off, d_max));
+  SHZ_HIP(ctx, shz_memcpy(ctx, &max_off, d_max, 4, hipMemcpyDeviceToHost));
+  SHZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  // the largest warped offset: the bias bound of the match
+  const uint64_t t_max = ((uint64_t)max_off * t16_max + 32768) >> 16;
+  if (t_max >= (1ull << 20))
+    SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "shz_match_songs_warps: a listed song holds offset %u, which the time factor %u / 65536 takes to %llu; warped offsets are query offsets here and must be < 2^20",
+             max_off, t16_max, (unsigned long long)t_max);
+  if (timed) SHZ_HIP(ctx, hipEventRecord(ctx->sp_ev[1], ctx->stream));
+  rw_tabs T;
+  SHZ_TRY(rw_upload(ctx, row_off.data(), n_sids, tempo_q16, pitch_q16, K, &T));
+  // 3) warp and match, slice by slice: (song, warp) = one query of the match
+  std::vector<uint32_t> r_sid, r_aligned, r_dedup, r_nres, r_nhash;
+  std::vector<int32_t> r_delta;
+  std::vector<uint64_t> r_npairs, seg_off;
+  float warp_ms = 0.f, match_ms = 0.f;
+  int32_t rc = SHZ_OK;
+  for (const rw_slice& s : plan) {
+    const uint64_t n_seg = (uint64_t)s.nq * s.kv;
+    if (timed) SHZ_HIP(ctx, hipEventRecord(ctx->sp_ev[2], ctx->stream));
+    seg_off.assign((size_t)n_seg + 1, 0);
+    rw_pass P;
+    rc = rw_count(ctx, T, d_key, d_off, row_off.data(), s.q0, s.nq, s.v0, s.kv, &P, seg_off.data());
+    const uint64_t total = seg_off[n_seg];
+    if (rc == SHZ_OK && total) rc = rw_write(ctx, P, d_wkey, d_woff, buf_items);
+    if (rc != SHZ_OK) break;
+    if (timed) SHZ_HIP(ctx, hipEventRecord(ctx->sp_ev[3], ctx->stream));
+    r_sid.assign(n_seg * w, 0); r_aligned.assign(n_seg * w, 0); r_dedup.assign(n_seg * w, 0); r_delta.assign(n_seg * w, 0);
+    r_nres.assign(n_seg, 0); r_nhash.assign(n_seg, 0); r_npairs.assign(n_seg, 0);
+    if (total)
+      rc = shz_match_device(ctx, t, d_wkey, d_woff, seg_off.data(), (uint32_t)n_seg, w, flags, (int64_t)t_max, r_sid.data(),
+                            r_delta.data(), r_aligned.data(), r_dedup.data(), r_nres.data(), r_nhash.data(), r_npairs.data());
+    if (rc != SHZ_OK) break;
+    if (timed) {
+      float a = 0.f, b = 0.f;
+      SHZ_HIP(ctx, hipEventRecord(ctx->sp_ev[4], ctx->stream));
+      SHZ_HIP(ctx, hipEventSynchronize(ctx->sp_ev[4]));
+      SHZ_HIP(ctx, hipEventElapsedTime(&a, ctx->sp_ev[2], ctx->sp_ev[3]));
+      SHZ_HIP(ctx, hipEventElapsedTime(&b, ctx->sp_ev[3], ctx->sp_ev[4]));
+      warp_ms += a;
+      match_ms += b;
+    }
+    // 4) the song itself leaves the list of every one of its warps: what stays are the first topn of every other song
+    for (uint32_t q = 0; q < s.nq; ++q)
+      for (uint32_t v = 0; v < s.kv; ++v) {
+        const uint64_t e = (uint64_t)q * s.kv + v, qv = (uint64_t)(s.q0 + q) * K + s.v0 + v;
+        uint32_t k = 0;
+        for (uint32_t i = 0; i < std::min(r_nres[e], w) && k < topn; ++i) {
+          const uint64_t src = e * w + i, dst = qv * topn + k;
+          if (r_sid[src] == sids[s.q0 + q]) continue;
+          out_sid[dst] = r_sid[src];
+          out_delta[dst] = r_delta[src];
+          out_aligned[dst] = r_aligned[src];
+          out_dedup[dst] = r_dedup[src];
+          ++k;
+        }
+        out_nres[qv] = k;
+        if (out_nhash) out_nhash[qv] = r_nhash[e];
+        if (out_npairs) out_npairs[qv] = r_npairs[e];
+      }
+  }
+  (void)hipStreamSynchronize(ctx->stream);   // (a refused call may have queued work that reads the columns)
+  if (rc != SHZ_OK) return rc;
+  if (timed) {
+    if (ms_gather) SHZ_HIP(ctx, hipEventElapsedTime(ms_gather, ctx->sp_ev[0], ctx->sp_ev[1]));
+    if (ms_warp) *ms_warp = warp_ms;
+    if (ms_match) *ms_match = match_ms;
+  }
+  return SHZ_OK;
+}

@@ -95,6 +95,9 @@ enum {
   SHZ_WS_CG_LIST,    // shz_catalog.hip: bitmap of the listed song ids | the list sorted | its slots | the list as given
   SHZ_WS_CG_BLK,     // ... hits of every block of SG_ROWS rows, then their scan
   SHZ_WS_CG_CNT,     // ... rows of every song id up to the largest listed | rows of every listed song | largest offset gathered
+  SHZ_WS_RW_TAB,     // ... the row warp: CSR of the songs over their rows | time factors | frequency factors of the call
+  SHZ_WS_RW_BLK,     // ... kept items of every block of RW_ITEMS items of a slice, then their scan
+  SHZ_WS_RW_CNT,     // ... kept items of every (song, warp) of a slice
   SHZ_WS_COUNT
 };
 
@@ -124,7 +127,7 @@ struct shz_ctx {
   bool tev_init = false;
   hipEvent_t rq_ev[3] = {nullptr, nullptr, nullptr};   // shz_recognize_batch: start, extraction done, match done (created on first use)
   hipEvent_t sc_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // shz_scan_batch / shz_scan_speeds: start, extraction done (then: a warp begun / done); the window stage: a step begun / done, the match behind it done (created on first use)
-  hipEvent_t sp_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // shz_recognize_speeds: start, peaks done, a slice's warp begun / done, its match done (created on first use)
+  hipEvent_t sp_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // shz_recognize_speeds / shz_match_songs_warps: start, peaks (rows) done, a slice's warp begun / done, its match done (created on first use)
   bool profiling = false;
   float kernel_ms[8] = {0};
   uint32_t kernel_launches[8] = {0};
@@ -270,6 +273,11 @@ struct sp_pass {
   uint32_t *wt, *segstart;
   unsigned long long *d_hoff, *d_tot;   // hash_off[n_seg + 1] | kept peaks, hashes
 };
+#define SP_F_MAX 2048u          // the last bin of the spectrogram (SHZ_NBINS - 1)
+__host__ __device__ __forceinline__ uint32_t sp_warp_f(uint32_t f, uint32_t s16) {
+  if (f < 16384u) return ((f << 17) + s16) / (2u * s16);   // fits 32 bits: every bin of the spectrogram
+  return (uint32_t)((((uint64_t)f << 17) + s16) / (2ull * s16));
+}
 __host__ __device__ __forceinline__ uint32_t sp_warp_t(uint32_t t, uint32_t s16) {
   const uint64_t x = ((uint64_t)t * s16 + 32768u) >> 16;
   return x > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)x;   // (t < 2^31 is the caller's promise; this keeps the value defined)

@@ -33,7 +33,6 @@
 #include "shz_internal.h"
 
 #define SP_THREADS 256
-#define SP_F_MAX 2048u          // the last bin of the spectrogram (SHZ_NBINS - 1)
 #define SP_SMALL_SLICE 2u       // queries of a match slice under SHZ_DEBUG_SPEED_SMALL_SLICES
 
 struct sp_item {
@@ -41,11 +40,6 @@ struct sp_item {
   uint64_t g, c_lo, c_hi;     // the peak, and the peaks of its clip
   uint64_t seg0, seg_n;       // first item of its (query, speed, clip), items of it
 };
-
-__host__ __device__ __forceinline__ uint32_t sp_warp_f(uint32_t f, uint32_t s16) {
-  if (f < 16384u) return ((f << 17) + s16) / (2u * s16);   // fits 32 bits: every bin of the spectrogram
-  return (uint32_t)((((uint64_t)f << 17) + s16) / (2ull * s16));
-}
 
 // item w -> its query (the last q with qbase[q] <= w), speed, clip and peak.  Items of a query: speed-major, then its
 // clips' peaks one behind the other -- a wave stays at one speed over consecutive peaks

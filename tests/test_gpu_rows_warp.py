@@ -1,0 +1,115 @@
+"""GPU: shz_warp_rows -- the rows of songs warped at a list of (tempo, pitch) pairs and compacted in order -- against its
+numpy statement tests/rows_warp_twin.py, bit for bit, out_row_off included.
+
+The compaction works on blocks of 512 (song, warp, row) items, one wave a block, 64 items a ballot; items are song-major,
+then warp-major.  The row counts put (song, warp) borders on, one before and one behind the ballot and block borders, in one
+call, so that segments straddle blocks and ballots: songs of 0, 1, 63, 64, 65, 511, 512, 513, 1023, 1024 and 1025 rows, a song
+all of whose rows leave at the warps below unity (f >= 1025 at pitch 0.5), and a song of 3,000 rows that spans several
+blocks at one warp."""
+import numpy as np
+import pytest
+
+import rows_warp_twin as RT
+
+pytestmark = pytest.mark.gpu
+
+COUNTS = [0, 1, 63, 64, 65, 0, 511, 512, 513, 700, 1023, 1024, 1025, 3000, 2]
+LEAVES = 9                                                   # the song of 700 rows: every f1 >= 1025
+WARPS1 = ([32768], [32768])
+WARPS5 = ([32768, 131072, 65536, 67502, 63570], [32768, 131072, 65536, 60000, 70000])
+
+
+def make_rows(seed=5):
+    rng = np.random.default_rng(seed)
+    ro = np.concatenate([[0], np.cumsum(COUNTS)]).astype(np.uint64)
+    n = int(ro[-1])
+    f1, f2, dt = rng.integers(0, 2049, n), rng.integers(0, 2049, n), rng.integers(0, 201, n)
+    a, b = int(ro[LEAVES]), int(ro[LEAVES + 1])
+    f1[a:b] = rng.integers(1025, 2049, b - a)
+    key = ((f1 << 20) | (f2 << 8) | dt).astype(np.uint32)
+    off = rng.integers(0, 1 << 19, n).astype(np.uint32)
+    return key, off, ro
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    import shazam_amd as S
+    return S.get_context(0)
+
+
+@pytest.mark.parametrize("warps", (WARPS1, WARPS5), ids=("1warp", "5warps"))
+def test_host_columns_equal_the_twin(ctx, warps):
+    key, off, ro = make_rows()
+    wk, wo, wro = RT.warp_rows_batch(key, off, ro, *warps)
+    K = len(warps[0])
+    v_half = warps[1].index(32768)
+    assert wro[LEAVES * K + v_half + 1] == wro[LEAVES * K + v_half] and 0 < len(wk) < len(key) * K   # the plant leaves there
+    k, o, oro = ctx.warp_rows(key, off, ro, *warps)
+    assert np.array_equal(oro, wro)
+    assert k.dtype == np.uint32 and np.array_equal(k, wk) and np.array_equal(o, wo)
+    # a CSR that does not start at 0: the songs from the third on
+    k2, o2, oro2 = ctx.warp_rows(key, off, ro[2:], *warps)
+    assert np.array_equal(oro2, wro[2 * K:] - wro[2 * K]) and np.array_equal(k2, wk[int(wro[2 * K]):])
+    assert np.array_equal(o2, wo[int(wro[2 * K]):])
+
+
+def test_identity_returns_the_input(ctx):
+    key, off, ro = make_rows(6)
+    k, o, oro = ctx.warp_rows(key, off, ro, [65536], [65536])
+    assert np.array_equal(k, key) and np.array_equal(o, off) and np.array_equal(oro, ro)
+
+
+def test_device_columns_and_capacity(ctx):
+    from shazam_amd import _ffi
+    key, off, ro = make_rows(7)
+    wk, wo, wro = RT.warp_rows_batch(key, off, ro, *WARPS5)
+    n = len(wk)
+    # too little room: the exact count and the exact CSR, nothing else
+    rc, k, o, oro, cnt = ctx.warp_rows_raw(key, off, ro, *WARPS5, cap=n - 1)
+    assert rc == _ffi.E_CAPACITY and cnt == n and np.array_equal(oro, wro)
+    rc, k, o, oro, cnt = ctx.warp_rows_raw(key, off, ro, *WARPS5, cap=0)
+    assert rc == _ffi.E_CAPACITY and cnt == n and np.array_equal(oro, wro)
+    # exactly enough
+    rc, k, o, oro, cnt = ctx.warp_rows_raw(key, off, ro, *WARPS5, cap=n)
+    assert rc == _ffi.OK and cnt == n and np.array_equal(k, wk) and np.array_equal(o, wo)
+    # device in, device out
+    dk, do = _ffi.DevBuf(ctx, key.nbytes), _ffi.DevBuf(ctx, off.nbytes)
+    ok, oo = _ffi.DevBuf(ctx, n * 4), _ffi.DevBuf(ctx, n * 4)
+    try:
+        dk.upload(key)
+        do.upload(off)
+        rc, k, o, oro, cnt = ctx.warp_rows_raw(dk, do, ro, *WARPS5, cap=n, device_in=True, out_key=ok, out_off=oo)
+        assert rc == _ffi.OK and k is None and cnt == n and np.array_equal(oro, wro)
+        assert np.array_equal(ok.download(np.uint32, n), wk) and np.array_equal(oo.download(np.uint32, n), wo)
+        # device in, host out
+        rc, k, o, oro, cnt = ctx.warp_rows_raw(dk, do, ro, *WARPS5, cap=n, device_in=True)
+        assert rc == _ffi.OK and np.array_equal(k, wk) and np.array_equal(o, wo)
+    finally:
+        for b in (dk, do, ok, oo):
+            b.free()
+
+
+def test_refusals(ctx):
+    import shazam_amd as S
+    from shazam_amd import _ffi
+    key, off, ro = make_rows(8)
+
+    def refused(code, word, *a, **kw):
+        rc = ctx.warp_rows_raw(*a, **kw)[0]
+        assert rc == code
+        with pytest.raises(S.ShzError) as e:
+            ctx.check(rc)
+        assert word in str(e.value), str(e.value)
+
+    refused(_ffi.E_INVALID, "n_warps", key, off, ro, [], [])
+    refused(_ffi.E_INVALID, "n_warps", key, off, ro, [65536] * 1025, [65536] * 1025)
+    refused(_ffi.E_INVALID, "tempo 1", key, off, ro, [65536, 32767], [65536, 65536])
+    refused(_ffi.E_INVALID, "pitch 0", key, off, ro, [65536, 65536], [131073, 65536])
+    bad = ro.copy()
+    bad[4] = bad[3] - 1
+    refused(_ffi.E_INVALID, "row_off", key, off, bad, [65536], [65536])
+    # 2^22 rows x 1,024 warps = 2^32 items: refused from the CSR alone, before a row is read
+    refused(_ffi.E_UNSUPPORTED, "warps", key, off, np.array([0, 1 << 22], np.uint64), [65536] * 1024, [65536] * 1024)
+    # and the call still works afterwards
+    k, o, oro = ctx.warp_rows(key, off, ro, [65536], [65536])
+    assert np.array_equal(k, key)
