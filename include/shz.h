@@ -944,6 +944,55 @@ int32_t shz_scan_timeline_speeds(const uint64_t* win_off, uint32_t n_recs, const
                                  uint32_t* seg_first, uint32_t* seg_last, uint32_t* seg_hits, uint32_t* seg_best,
                                  int32_t* seg_pos_first, int32_t* seg_pos_last, uint32_t* seg_rung, uint64_t cap, uint64_t* count);
 
+/* ---- scanning at unknown tempo and pitch, per-window variant lists (new; shz_scan_speeds over warp pairs: DESIGN.md 3.7i) ----
+ * shz_scan_warps: the arguments of shz_scan_speeds with the ladder replaced by a warp list (tempo_q16 / pitch_q16 / n_warps,
+ * checked as shz_recognize_warps checks them: the message names the table and the index), an optional selection (sel_off /
+ * sel_warp, host) and an optional out_work[2].
+ * DENSE (both selection pointers NULL): the contract of shz_scan_speeds with "rung v" read as "warp v".  The hashes of
+ * (recording, warp, channel) are shz_warp_pair_hash_tf's.  Only the TIME factor enters a time: W_v(x) = (x t16 + 32768) >> 16
+ * gives the window borders and the query offsets, the bias bound of the match is ceil(window_frames t16_max / 65536) - 1, and
+ * ceil(window_frames t16_max / 65536) >= 2^20 is SHZ_E_UNSUPPORTED; pitch_q16 never enters a time.  The BEST variant of a
+ * window has the greatest rank-0 aligned count; ties go to the smaller |t16 - 65536| + |f16 - 65536|, then to the lower index.
+ * out_profile (may be NULL) is [n_wins n_warps].  shz_scan_speeds(speed_q16) is this call with the one table given twice and
+ * no selection.
+ * SELECTION: sel_off has n_wins + 1 entries over the windows, recording-major as in win_off (the caller knows n_wins from
+ * shz_scan_window_count), and sel_warp[sel_off[w] .. sel_off[w + 1]) are the warps window w tries, strictly ascending, each
+ * < n_warps.  Only the listed (window, warp) pairs become queries of the match.  out_profile is slot-aligned (sel_off[n_wins]
+ * entries), the best variant is chosen among the window's slots by the rule above, and a window with an empty list has nres
+ * 0, all arrays 0 and out_best = SHZ_SCAN_NO_WARP.  Warps that no window selects are dropped before slicing, and from there
+ * the call behaves as on the compacted list; if nothing is selected, nothing is extracted.  A full selection (every window
+ * lists 0 .. n_warps - 1) gives the dense call's arrays, entry for entry.  SHZ_E_INVALID before anything is launched: exactly
+ * one of the two pointers NULL, sel_off[0] != 0, a sel_off that decreases, a list that is not strictly ascending, an index
+ * >= n_warps.
+ * out_work (may be NULL): [0] = the warped hash entries written over the call (the sum of the slices' CSR totals), [1] = the
+ * window entries handed to the match (the sum of the window stage's totals): what a selection saves, as counts.
+ * SLICES as in shz_scan_speeds; a chunk of warps may cut through a window's list, and the best variant is folded over the
+ * chunks in index order.  Results do not depend on any of it (SHZ_DEBUG_SCAN_SPEED_SMALL_SLICES: 1 recording x 2 warps a
+ * slice, 3 windows a group). */
+#define SHZ_SCAN_NO_WARP 0xFFFFFFFFu
+int32_t shz_scan_warps(shz_ctx* ctx, shz_table* t, const int16_t* pcm, const uint64_t* clip_off, uint32_t n_clips,
+                       const uint32_t* rec_clip0, uint32_t n_recs, uint32_t fs, double amp_min, uint32_t fan_value,
+                       uint32_t window_frames, uint32_t step_frames, uint32_t topn, const uint32_t* tempo_q16,
+                       const uint32_t* pitch_q16, uint32_t n_warps, const uint64_t* sel_off, const uint32_t* sel_warp,
+                       uint32_t flags, uint64_t* win_off, uint32_t* out_best, uint32_t* out_sid, int32_t* out_delta,
+                       uint32_t* out_aligned, uint32_t* out_dedup, uint32_t* out_nres, uint32_t* out_nhash, uint64_t* out_npairs,
+                       uint32_t* out_profile, uint64_t* out_work, uint64_t cap_windows, uint64_t* count, float* ms_extract,
+                       float* ms_warp, float* ms_window, float* ms_match);
+/* The timeline of a scan over warps (no GPU, no ctx): shz_scan_timeline_speeds over a warp list that need not be sorted (any
+ * length >= 1, every factor in [32768, 131072]).  A hit w2 (warp (t2, f2), delta2) CONTINUES the open segment, whose last hit
+ * is w1 (warp (t1, f1), delta1), iff the song id is the same, w2 - w1 - 1 <= max_gap, |t2 - t1| <= tempo_tol_q16, |f2 - f1| <=
+ * pitch_tol_q16 and |delta2 - delta1 - W_t2((w2 - w1) step_frames)| <= shift_tol.  out_best is read for hits only, so
+ * SHZ_SCAN_NO_WARP on a window without results is fine (on a hit, an entry >= n_warps is SHZ_E_INVALID).  Per segment the
+ * arrays of the speed timeline, with seg_warp = the variant its hits chose most often (ties to the smaller
+ * |t16 - 65536| + |f16 - 65536|, then to the lower index).  Capacity: the same two-call idiom. */
+int32_t shz_scan_timeline_warps(const uint64_t* win_off, uint32_t n_recs, const uint32_t* out_sid, const int32_t* out_delta,
+                                const uint32_t* out_aligned, const uint32_t* out_nres, const uint32_t* out_best, uint32_t topn,
+                                uint32_t step_frames, const uint32_t* tempo_q16, const uint32_t* pitch_q16, uint32_t n_warps,
+                                uint32_t min_aligned, uint32_t max_gap, uint32_t tempo_tol_q16, uint32_t pitch_tol_q16,
+                                uint32_t shift_tol, uint32_t* seg_rec, uint32_t* seg_sid, uint32_t* seg_first, uint32_t* seg_last,
+                                uint32_t* seg_hits, uint32_t* seg_best, int32_t* seg_pos_first, int32_t* seg_pos_last,
+                                uint32_t* seg_warp, uint64_t cap, uint64_t* count);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,6 +18,7 @@ DEBUG_VT_TINY_HEAVY, DEBUG_VT_PROBE1, DEBUG_RUN_LIMIT_SMALL, DEBUG_SCAN_SMALL_GR
 DEBUG_SPEED_SMALL_SLICES = 16   # shz_recognize_speeds: at most 2 queries a slice
 DEBUG_SCAN_SPEED_SMALL_SLICES = 32   # shz_scan_speeds: at most 1 recording x 2 rungs a slice, 3 windows a match group
 DEBUG_CATALOG_SMALL_SLICES = 64   # shz_match_songs_warps: one song x at most 2 warps a slice
+SCAN_NO_WARP = 0xFFFFFFFF            # shz_scan_warps: out_best of a window that tried no variant
 SCAN_U32, SCAN_POPC64, SCAN_U64 = 0, 1, 2   # shz_scan_host kinds
 STAGE_F32, STAGE_F64, STAGE_PERSISTENT = 0, 1, 1   # shz_stft_stage_host kinds | flag
 RUN_ROWS_MAX, RUN_ROWS_MAX_SMALL = (1 << 32) - 4096, 65536
@@ -183,6 +184,13 @@ SIGNATURES = {
     "shz_scan_timeline_speeds": (C.c_int32, [u64p, C.c_uint32, vp, vp, vp, vp, vp, C.c_uint32, C.c_uint32, u32p, C.c_uint32,
                                              C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                              C.c_uint64, u64p]),
+    "shz_scan_warps": (C.c_int32, [vp, vp, vp, u64p, C.c_uint32, u32p, C.c_uint32, C.c_uint32, C.c_double, C.c_uint32,
+                                   C.c_uint32, C.c_uint32, C.c_uint32, u32p, u32p, C.c_uint32, u64p, u32p, C.c_uint32, u64p, vp, vp,
+                                   vp, vp, vp, vp, vp, vp, vp, u64p, C.c_uint64, u64p, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                   C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "shz_scan_timeline_warps": (C.c_int32, [u64p, C.c_uint32, vp, vp, vp, vp, vp, C.c_uint32, C.c_uint32, u32p, u32p, C.c_uint32,
+                                            C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp,
+                                            vp, vp, C.c_uint64, u64p]),
 }
 
 
@@ -705,6 +713,56 @@ class Context:
         res = self._windows_with_room(call, room, cnt, cap_windows)
         return res, wo, tuple(float(m.value) for m in ms)
 
+    def scan_warps(self, table: "Table", pcm, clip_off, rec_clip0, window_frames, step_frames, tempos, pitches, select=None,
+                   fs=44100, amp_min=10.0, fan_value=5, topn=2, pcm_device=False, full_sort=False, cap_windows=None):
+        """shz_scan_warps: scan_speeds with a time and a frequency factor of its own for every variant (warp v is (tempos[v],
+        pitches[v]), Q16).  select=(sel_off, sel_warp): window w tries the warps sel_warp[sel_off[w]:sel_off[w + 1]] only
+        (strictly ascending; the windows recording-major), and profile is slot-aligned ([sel_off[-1]]) instead of
+        [n_windows, n_warps]; a window with an empty list has best = SCAN_NO_WARP; a sel_off that has not one entry more
+        than there are windows is a ValueError.  Returns (res, win_off, ms) as scan_speeds, res with "work" = (warped hash
+        entries written, window entries handed to the match)."""
+        co, nc = self._clip_off(clip_off)
+        rc0 = np.ascontiguousarray(rec_clip0, np.uint32)
+        tq, fq = np.ascontiguousarray(tempos, np.uint32), np.ascontiguousarray(pitches, np.uint32)
+        if tq.shape != fq.shape or tq.ndim != 1:
+            raise ValueError("tempos and pitches are two lists of one length: warp v is (tempos[v], pitches[v])")
+        so = sw = None
+        if select is not None:
+            so, sw = np.ascontiguousarray(select[0], np.uint64), np.ascontiguousarray(select[1], np.uint32)
+            if len(so) < 1 or len(sw) < int(so.max(initial=0)):
+                raise ValueError("select=(sel_off, sel_warp): sel_off is a CSR over the windows into sel_warp")
+        nr = len(rc0) - 1
+        flags = (PCM_DEVICE if pcm_device else 0) | (MATCH_FULL_SORT if full_sort else 0)
+        wo, cnt, work = np.zeros(nr + 1, np.uint64), C.c_uint64(), np.zeros(2, np.uint64)
+        ms = [C.c_float(), C.c_float(), C.c_float(), C.c_float()]
+        prof = {}
+
+        def call(res, cap):
+            # without cap_windows the first call has counted the windows and launched nothing: a sel_off of another length
+            # is refused here, before the library reads it
+            if select is not None and cap and len(so) != int(cap) + 1:
+                raise ValueError(f"select: sel_off has {len(so)} entries for {int(cap)} windows")
+            return lib().shz_scan_warps(self.h, table.h, ptr(pcm), co.ctypes.data_as(u64p), nc, rc0.ctypes.data_as(u32p), nr,
+                                        int(fs), float(amp_min), int(fan_value), int(window_frames), int(step_frames), int(topn),
+                                        tq.ctypes.data_as(u32p), fq.ctypes.data_as(u32p), len(tq),
+                                        None if so is None else so.ctypes.data_as(u64p),
+                                        None if sw is None else sw.ctypes.data_as(u32p), flags, wo.ctypes.data_as(u64p),
+                                        ptr(res["best"]), ptr(res["sid"]), ptr(res["delta"]), ptr(res["aligned"]), ptr(res["dedup"]),
+                                        ptr(res["nres"]), ptr(res["nhash"]), ptr(res["npairs"]), ptr(prof["profile"]),
+                                        work.ctypes.data_as(u64p), int(cap), C.byref(cnt), *[C.byref(m) for m in ms])
+
+        def room(n):
+            res = _match_result(n, topn)
+            res["best"] = np.zeros(n, np.uint32)
+            prof["profile"] = np.zeros((n, len(tq)), np.uint32) if select is None else np.zeros(int(so[-1]) if n else 0, np.uint32)
+            return res
+        res = self._windows_with_room(call, room, cnt, cap_windows)
+        if select is not None and len(so) != int(cnt.value) + 1:      # (a cap_windows of the caller's above the total)
+            raise ValueError(f"select: sel_off has {len(so)} entries for {int(cnt.value)} windows")
+        res["profile"] = prof["profile"][:int(cnt.value)] if select is None else prof["profile"]
+        res["work"] = (int(work[0]), int(work[1]))
+        return res, wo, tuple(float(m.value) for m in ms)
+
     def warp_pair_hash_raw(self, peak_f, peak_t, peak_off, speeds, query_clip0=None, fan_value=5, cap=0, device_in=False,
                            out_key: DevBuf = None, out_t1: DevBuf = None):
         """One shz_warp_pair_hash as it is: (rc, key32, t1, hash_off, count) without retrying.  peak_f / peak_t: host
@@ -1015,6 +1073,43 @@ def scan_timeline_speeds(win_off, sid, delta, aligned, nres, best, step_frames, 
         rc, seg, n = scan_timeline_speeds_raw(*args, n)
     if rc != OK:
         raise ShzError(rc, "shz_scan_timeline_speeds: bad arguments")
+    return seg
+
+
+WARP_SEGMENT_FIELDS = SPEED_SEGMENT_FIELDS[:-1] + (("warp", np.uint32),)
+
+
+def scan_timeline_warps_raw(win_off, sid, delta, aligned, nres, best, step_frames, tempos, pitches, min_aligned, max_gap=1,
+                            tempo_tol=0, pitch_tol=0, shift_tol=2, cap=0):
+    """One shz_scan_timeline_warps as it is (host only): (rc, segments, count) with room for `cap` segments."""
+    wo = np.ascontiguousarray(win_off, np.uint64)
+    sid, delta, aligned = (np.ascontiguousarray(a, d) for a, d in ((sid, np.uint32), (delta, np.int32), (aligned, np.uint32)))
+    nres, best, tq, fq = (np.ascontiguousarray(a, np.uint32) for a in (nres, best, tempos, pitches))
+    nw = len(nres)
+    topn = 1 if sid.ndim == 1 else int(sid.shape[1])
+    assert sid.shape == delta.shape == aligned.shape and sid.size == nw * topn and len(best) == nw and len(tq) == len(fq)
+    assert int(wo[-1]) - int(wo[0]) <= nw
+    seg = {k: np.zeros(int(cap), d) for k, d in WARP_SEGMENT_FIELDS}
+    cnt = C.c_uint64()
+    rc = lib().shz_scan_timeline_warps(wo.ctypes.data_as(u64p), len(wo) - 1, ptr(sid), ptr(delta), ptr(aligned), ptr(nres),
+                                       ptr(best), topn, int(step_frames), tq.ctypes.data_as(u32p), fq.ctypes.data_as(u32p), len(tq),
+                                       int(min_aligned), int(max_gap), int(tempo_tol), int(pitch_tol), int(shift_tol),
+                                       *[ptr(seg[k]) if cap else None for k, _ in WARP_SEGMENT_FIELDS], int(cap), C.byref(cnt))
+    return rc, seg, int(cnt.value)
+
+
+def scan_timeline_warps(win_off, sid, delta, aligned, nres, best, step_frames, tempos, pitches, min_aligned, max_gap=1,
+                        tempo_tol=0, pitch_tol=0, shift_tol=2) -> dict:
+    """shz_scan_timeline_warps (host only, two calls): the rank-0 answers of a scan over warps folded into segments by local
+    continuity -- the arrays of scan_timeline_speeds with warp (the variant chosen most often) in place of rung.  tempo_tol /
+    pitch_tol: how far the factors of neighbouring hits may lie apart, Q16."""
+    args = (win_off, sid, delta, aligned, nres, best, step_frames, tempos, pitches, min_aligned, max_gap, tempo_tol, pitch_tol,
+            shift_tol)
+    rc, seg, n = scan_timeline_warps_raw(*args, 0)
+    if rc == E_CAPACITY:
+        rc, seg, n = scan_timeline_warps_raw(*args, n)
+    if rc != OK:
+        raise ShzError(rc, "shz_scan_timeline_warps: bad arguments")
     return seg
 
 

@@ -82,7 +82,8 @@ enum {
   SHZ_WS_VT6,        // the bar of every query of a vote pass (vt_stream2_kernel)
   SHZ_WS_RQ_KEY, SHZ_WS_RQ_T1,   // hashes of shz_recognize_batch / shz_scan_batch between their extraction and their match (neither reserves them)
   SHZ_WS_SC_JOBS,    // shz_scan.hip, the window stage of both scans: the descriptors of a slice's recordings (the plain scan: | hash_off
-                     // of the clips | its one rung behind them)
+                     // of the clips | its one rung behind them; a scan over warps with a selection: | the slot CSR over the slice's
+                     // windows | the rung of every slot)
   SHZ_WS_SC_CTL,     // ... first entry | count | offset of every (window, rung, channel), the total behind the offsets
   SHZ_WS_SC_KEY, SHZ_WS_SC_QO,   // ... the windows of one group: key32 and t1 - window start, window-major (rung-minor)
   SHZ_WS_SP_PF, SHZ_WS_SP_PT,    // shz_speed.hip: the peaks of the clips (the extraction's, or a host list staged)

@@ -13,7 +13,9 @@
 // Nothing per window is built on the host: the kernels derive s and both bounds from one descriptor per recording and the
 // rung table.  The items are (window, rung, channel), window-major, so that (window, rung) is one contiguous query of the
 // match with its channels one behind the other.  The windows' columns are replicated ceil(window / step) times, so they
-// are written group by group into two slots and each group is matched where it lies.
+// are written group by group into two slots and each group is matched where it lies.  A scan over warp pairs may hand the
+// stage a selection: every window tries a list of rungs of its own, a query is then a SLOT of that list, and
+// the items are (slot, channel).
 #include <algorithm>
 
 #include "shz_internal.h"
@@ -24,7 +26,8 @@
 
 struct sc_rec {        // one recording of a slice; the entry behind the last one holds the slice's totals
   uint64_t win0;       // its first window among the slice's windows
-  uint64_t item0;      // its first (window, rung, channel) item: the sum of windows x rungs x channels in front of it
+  uint64_t slot0;      // its first query (window, rung): win0 x rungs, or with a selection the slots in front of it
+  uint64_t item0;      // its first (window, rung, channel) item: the sum of queries x channels in front of it
   uint64_t seg0;       // its first segment of the hashes' CSR: (rung, channel) at seg0 + rung * nch + channel
   uint32_t nch, pad;
 };
@@ -47,25 +50,58 @@ __device__ __forceinline__ uint64_t sc_lower_bound(const uint32_t* __restrict__ 
 // sp_warp_t, unclamped (x < 2^47: frame counts are far below); at s16 = 65536 it is x itself
 __device__ __forceinline__ uint64_t sc_warp(uint64_t x, uint32_t s16) { return (x * s16 + 32768u) >> 16; }
 
-// per (window, rung, channel): where the window's hashes begin in the list of (rung, channel), and how many they are
+// Query q of recording r -> its window (counted inside the recording) and its rung.  Dense: every window has the slice's kc
+// rungs, so both follow from one division.  With a selection (slot_off != NULL) a query is a SLOT: slot_off is
+// the CSR of the slots over the slice's windows and slot_warp the rung of every slot, so the window is the last one of the
+// recording whose first slot is <= q -- windows with empty lists share a start with the window behind them, and the last
+// of such a run is the one that holds q, because q exists -- and the rung is read from the slot.
+__device__ __forceinline__ void sc_query(const sc_rec* __restrict__ recs, uint32_t r, const sc_rec& R, uint64_t q, uint32_t kc,
+                                         const uint64_t* __restrict__ slot_off, const uint32_t* __restrict__ slot_warp,
+                                         uint64_t* w, uint32_t* v) {
+  if (!slot_off) {   // (uniform: a kernel argument)
+    const uint64_t rem = q - R.slot0, ww = rem / kc;
+    *w = ww;
+    *v = (uint32_t)(rem - ww * kc);
+    return;
+  }
+  uint64_t lo = R.win0, hi = recs[r + 1].win0;   // (the recording has a slot, so it has a window: lo < hi)
+  while (lo + 1 < hi) {
+    const uint64_t mid = lo + ((hi - lo) >> 1);
+    if (slot_off[mid] <= q) lo = mid; else hi = mid;
+  }
+  *w = lo - R.win0;
+  *v = slot_warp[q];
+}
+
+// per (query, channel): where the window's hashes begin in the list of (rung, channel), and how many they are
 __global__ __launch_bounds__(SC_THREADS) void sc_bounds_kernel(const sc_rec* __restrict__ recs, uint32_t nr, uint64_t n_items,
                                                                const uint32_t* __restrict__ speed, uint32_t kc,
-                                                               uint32_t window_frames, uint32_t step_frames,
-                                                               const uint64_t* __restrict__ hoff, const uint32_t* __restrict__ t1,
-                                                               uint64_t* __restrict__ first, uint64_t* __restrict__ cnt) {
+                                                               const uint64_t* __restrict__ slot_off,
+                                                               const uint32_t* __restrict__ slot_warp, uint32_t window_frames,
+                                                               uint32_t step_frames, const uint64_t* __restrict__ hoff,
+                                                               const uint32_t* __restrict__ t1, uint64_t* __restrict__ first,
+                                                               uint64_t* __restrict__ cnt) {
   const uint64_t i = (uint64_t)blockIdx.x * SC_THREADS + threadIdx.x;
   if (i >= n_items) return;
-  uint32_t lo = 0, hi = nr;   // the last recording whose first item is <= i (recordings without windows share a start)
+  uint32_t lo = 0, hi = nr;   // the last recording whose first item is <= i (recordings without items share a start)
   while (lo + 1 < hi) {
     const uint32_t mid = (lo + hi) >> 1;
     if (recs[mid].item0 <= i) lo = mid; else hi = mid;
   }
   const sc_rec R = recs[lo];
-  const uint64_t rem = i - R.item0, qv = rem / R.nch, c = rem - qv * R.nch, w = qv / kc, v = qv - w * kc;
+  const uint64_t rem = i - R.item0, ql = rem / R.nch, c = rem - ql * R.nch;
+  uint64_t w;
+  uint32_t v;
+  sc_query(recs, lo, R, R.slot0 + ql, kc, slot_off, slot_warp, &w, &v);
+  if (v >= kc) {   // (the host checks every slot; a rung outside the slice's table would read outside the CSR)
+    first[i] = 0;
+    cnt[i] = 0;
+    return;
+  }
   const uint32_t s16 = speed[v];
   // (with step > window the last window may start behind the recording's end, above every t1: the searches compare in
   // 64 bits, so it is empty whatever its start is, with no clamp to the 32 bits of t1)
-  const uint64_t s = w * step_frames, e = R.seg0 + v * R.nch + c;
+  const uint64_t s = w * step_frames, e = R.seg0 + (uint64_t)v * R.nch + c;
   const uint64_t a = hoff[e], b = hoff[e + 1];
   const uint64_t p = sc_lower_bound(t1, a, b, sc_warp(s, s16));
   const uint64_t q = sc_lower_bound(t1, p, b, sc_warp(s + window_frames, s16));
@@ -73,25 +109,30 @@ __global__ __launch_bounds__(SC_THREADS) void sc_bounds_kernel(const sc_rec* __r
   cnt[i] = q - p;
 }
 
-// one workgroup per (window, rung) of the group [q0, q0 + gridDim.x) of the slice's queries: its channels' ranges, one
+// one workgroup per query (window, rung) of the group [q0, q0 + gridDim.x) of the slice's queries: its channels' ranges, one
 // behind the other, to offs[item] - base of the group's columns (offs: exclusive scan of the counts, the total behind it)
 __global__ __launch_bounds__(SC_THREADS) void sc_gather_kernel(const sc_rec* __restrict__ recs, uint32_t nr, uint64_t q0,
-                                                               const uint32_t* __restrict__ speed, uint32_t kc, uint32_t step_frames,
+                                                               const uint32_t* __restrict__ speed, uint32_t kc,
+                                                               const uint64_t* __restrict__ slot_off,
+                                                               const uint32_t* __restrict__ slot_warp, uint32_t step_frames,
                                                                const uint64_t* __restrict__ first, const uint64_t* __restrict__ offs,
                                                                uint64_t base, uint64_t cap, const uint32_t* __restrict__ key,
                                                                const uint32_t* __restrict__ t1, uint32_t* __restrict__ out_key,
                                                                uint32_t* __restrict__ out_qo) {
   const uint64_t q = q0 + blockIdx.x;
-  uint32_t lo = 0, hi = nr;   // the last recording whose first query is <= q
+  uint32_t lo = 0, hi = nr;   // the last recording whose first query is <= q (recordings without queries share a start)
   while (lo + 1 < hi) {
     const uint32_t mid = (lo + hi) >> 1;
-    if (recs[mid].win0 * kc <= q) lo = mid; else hi = mid;
+    if (recs[mid].slot0 <= q) lo = mid; else hi = mid;
   }
   const sc_rec R = recs[lo];
-  const uint64_t rem = q - R.win0 * kc, w = rem / kc, v = rem - w * kc;
+  uint64_t w;
+  uint32_t v;
+  sc_query(recs, lo, R, q, kc, slot_off, slot_warp, &w, &v);
+  if (v >= kc) return;   // (uniform; its items were counted as empty)
   const uint32_t t0 = (uint32_t)sc_warp(w * step_frames, speed[v]);   // (a window with entries starts below their t1' < 2^32)
   for (uint32_t c = 0; c < R.nch; ++c) {
-    const uint64_t p = R.item0 + rem * R.nch + c;
+    const uint64_t p = R.item0 + (q - R.slot0) * R.nch + c;
     const uint64_t src = first[p], dst = offs[p] - base, n = offs[p + 1] - offs[p];
     if (dst + n > cap) return;   // (uniform; the host sizes the columns from the same offsets, so this never holds)
     for (uint64_t i = threadIdx.x; i < n; i += SC_THREADS) {
@@ -152,7 +193,7 @@ struct sc_slice {
   const uint32_t* clip0;         // rec_clip0 and win_off of the call from the slice's first recording on: nr + 1 entries
   const uint64_t* woff;          // (at least one of the nr recordings has a window)
   uint32_t nr, kc;
-  const uint32_t* speed;         // the slice's kc rungs (Q16)
+  const uint32_t* speed;         // the slice's kc rungs (Q16): their time factors
   const uint64_t* hoff;          // CSR of the segments (recording, rung, channel) over key / t1, relative to them
   bool tables_on_host;           // speed and hoff are on the host (they go up with the descriptors) / on the device
   const uint32_t *d_key, *d_t1;  // the hashes (device), `total` of them
@@ -161,51 +202,77 @@ struct sc_slice {
   int64_t bias_bound;            // of the match: no query offset is above it
   uint64_t rep;                  // the windows a hash can lie in at one rung (the sanity bound)
   bool small_groups;             // SC_SMALL_GROUP windows a group (the callers' debug switches)
-  uint32_t *sid, *aligned, *dedup, *nres, *nhash;   // results, (window, rung)-major; nhash and npairs may be NULL
-  int32_t* delta;
+  uint32_t *sid, *aligned, *dedup, *nres, *nhash;   // results, query-major: (window, rung), or slot by slot; nhash and
+  int32_t* delta;                                   // npairs may be NULL
   uint64_t* npairs;
+  // a selection (host; NULL: every window at all kc rungs): slot_off = the CSR of the slots over the slice's windows from 0,
+  // slot_warp = the rung of every slot, < kc and ascending inside a window.  They go up with the descriptors
+  const uint64_t* slot_off;
+  const uint32_t* slot_warp;
+  uint64_t* entries;             // (may be NULL) the window entries handed to the match are added to it
 };
 
-// Cuts the slice's hash lists into its windows and matches every (window, rung).  Device times are added to *win_ms and
+// Cuts the slice's hash lists into its windows and matches every query.  Device times are added to *win_ms and
 // *match_ms when `timed` (events sc_ev[2 .. 4]).  The stream is idle on return.
 static int32_t sc_windows(shz_ctx* ctx, shz_table* t, const char* who, const sc_slice& S, bool timed, float* win_ms, float* match_ms) {
   if (timed) SHZ_HIP(ctx, hipEventRecord(ctx->sc_ev[2], ctx->stream));
   const uint32_t nr = S.nr, kc = S.kc, topn = S.topn, *clip0 = S.clip0;
   const uint64_t* woff = S.woff;
+  const bool sel = S.slot_off != nullptr;
   const uint64_t nws = woff[nr] - woff[0], n_seg = (uint64_t)(clip0[nr] - clip0[0]) * kc;
-  // 1) one descriptor a recording (behind them, if they come from the host: hoff | speed), and the first item of every window
+  auto slot_at = [&](uint64_t w) { return sel ? S.slot_off[w] : w * kc; };   // the first query of window w
+  const uint64_t n_slots = slot_at(nws);
+  // 1) one descriptor a recording (behind them, if they come from the host: hoff | speed; with a selection: the slot CSR),
+  // and the first item of every window
   const uint64_t rec_bytes = ((uint64_t)nr + 1) * sizeof(sc_rec), hoff_bytes = S.tables_on_host ? (n_seg + 1) * 8 : 0;
-  std::vector<char> block(rec_bytes + hoff_bytes + (S.tables_on_host ? (uint64_t)kc * 4 : 0));
+  const uint64_t soff_bytes = sel ? (nws + 1) * 8 : 0, speed_bytes = S.tables_on_host ? (uint64_t)kc * 4 : 0;
+  std::vector<char> block(rec_bytes + hoff_bytes + soff_bytes + speed_bytes + (sel ? n_slots * 4 : 0));
   sc_rec* hrec = (sc_rec*)block.data();
-  std::vector<uint64_t> win_item((size_t)nws + 1);
+  std::vector<uint64_t> win_item((size_t)nws + 1), win_nch((size_t)nws);
   uint64_t n_items = 0;
   for (uint32_t r = 0; r < nr; ++r) {
     const uint32_t nch = clip0[r + 1] - clip0[r];
     const uint64_t w0 = woff[r] - woff[0], nw = woff[r + 1] - woff[r];
-    hrec[r] = sc_rec{w0, n_items, (uint64_t)(clip0[r] - clip0[0]) * kc, nch, 0};
-    for (uint64_t w = 0; w < nw; ++w) win_item[w0 + w] = n_items + w * kc * nch;
-    n_items += nw * kc * nch;
+    hrec[r] = sc_rec{w0, slot_at(w0), n_items, (uint64_t)(clip0[r] - clip0[0]) * kc, nch, 0};
+    for (uint64_t w = 0; w < nw; ++w) {
+      win_item[w0 + w] = n_items + (slot_at(w0 + w) - slot_at(w0)) * nch;
+      win_nch[w0 + w] = nch;
+    }
+    n_items += (slot_at(w0 + nw) - slot_at(w0)) * nch;
   }
-  hrec[nr] = sc_rec{nws, n_items, n_seg, 0, 0};
+  hrec[nr] = sc_rec{nws, n_slots, n_items, n_seg, 0, 0};
   win_item[nws] = n_items;
+  if (n_items == 0) {   // (a selection that leaves the slice without a slot: nothing to cut, nothing to match)
+    SHZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return SHZ_OK;
+  }
   void *d_rec, *d_ctl;
   SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SC_JOBS, block.size(), &d_rec));
   SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SC_CTL, (3 * n_items + 1) * 8, &d_ctl));
   uint64_t *d_first = (uint64_t*)d_ctl, *d_cnt = d_first + n_items, *d_offs = d_cnt + n_items;   // d_offs[n_items] = the total
   const uint64_t* d_hoff = S.hoff;
   const uint32_t* d_speed = S.speed;
+  const uint64_t* d_soff = nullptr;
+  const uint32_t* d_swarp = nullptr;
   if (S.tables_on_host) {
     memcpy(block.data() + rec_bytes, S.hoff, hoff_bytes);
-    memcpy(block.data() + rec_bytes + hoff_bytes, S.speed, (uint64_t)kc * 4);
+    memcpy(block.data() + rec_bytes + hoff_bytes + soff_bytes, S.speed, speed_bytes);
     d_hoff = (const uint64_t*)((char*)d_rec + rec_bytes);
-    d_speed = (const uint32_t*)((char*)d_rec + rec_bytes + hoff_bytes);
+    d_speed = (const uint32_t*)((char*)d_rec + rec_bytes + hoff_bytes + soff_bytes);
+  }
+  if (sel) {   // (8-byte entries in front of 4-byte ones: every table keeps its alignment)
+    memcpy(block.data() + rec_bytes + hoff_bytes, S.slot_off, soff_bytes);
+    memcpy(block.data() + rec_bytes + hoff_bytes + soff_bytes + speed_bytes, S.slot_warp, n_slots * 4);
+    d_soff = (const uint64_t*)((char*)d_rec + rec_bytes + hoff_bytes);
+    d_swarp = (const uint32_t*)((char*)d_rec + rec_bytes + hoff_bytes + soff_bytes + speed_bytes);
   }
   // 2) upload, 3) bounds, scan, one read-back: the offsets of every item
   std::vector<uint64_t> offs((size_t)n_items + 1, 0);
   if (S.total) {   // (without hashes every window is empty, and a warp pass has no CSR on the device)
     SHZ_HIP(ctx, shz_memcpy(ctx, d_rec, block.data(), block.size(), hipMemcpyHostToDevice));
     hipLaunchKernelGGL(sc_bounds_kernel, dim3((unsigned)((n_items + SC_THREADS - 1) / SC_THREADS)), dim3(SC_THREADS), 0, ctx->stream,
-                       (const sc_rec*)d_rec, nr, n_items, d_speed, kc, S.window_frames, S.step_frames, d_hoff, S.d_t1, d_first, d_cnt);
+                       (const sc_rec*)d_rec, nr, n_items, d_speed, kc, d_soff, d_swarp, S.window_frames, S.step_frames, d_hoff, S.d_t1,
+                       d_first, d_cnt);
     SHZ_HIP(ctx, hipGetLastError());
     SHZ_TRY(shz_scan_u64(ctx, d_cnt, d_offs, n_items, d_offs + n_items));
     SHZ_HIP(ctx, shz_memcpy(ctx, offs.data(), d_offs, (n_items + 1) * 8, hipMemcpyDeviceToHost));
@@ -221,43 +288,44 @@ static int32_t sc_windows(shz_ctx* ctx, shz_table* t, const char* who, const sc_
   if (offs[n_items] > S.total * S.rep)
     SHZ_FAIL(ctx, SHZ_E_STATE, "%s: %llu window entries from %llu hashes", who, (unsigned long long)offs[n_items],
              (unsigned long long)S.total);
+  if (S.entries) *S.entries += offs[n_items];
   auto win_at = [&](uint64_t w) { return offs[win_item[w]]; };
   // 5) the groups.  A group's columns take at most 1/8 of the workspace limit (the match sizes its own sub-batches inside a
   // group) and hold at most 2^24 queries; a window is never split and its rungs stay together, so one larger than that is
   // a group of its own
   const uint64_t max_entries = std::min<uint64_t>(std::max<uint64_t>(ctx->ws_limit / 64, 1), 1ull << 30);
-  const uint64_t max_wins = S.small_groups ? SC_SMALL_GROUP : std::max<uint64_t>((1ull << 24) / kc, 1);
+  const uint64_t max_wins = S.small_groups ? SC_SMALL_GROUP : ~0ull;
   std::vector<uint64_t> groups{0};   // first window of every group, nws behind them
   uint64_t m_max = 0;
   for (uint64_t g0 = 0; g0 < nws;) {
     uint64_t g1 = g0 + 1;
-    while (g1 < nws && g1 - g0 < max_wins && win_at(g1 + 1) - win_at(g0) <= max_entries) ++g1;
+    while (g1 < nws && g1 - g0 < max_wins && slot_at(g1 + 1) - slot_at(g0) <= (1ull << 24) && win_at(g1 + 1) - win_at(g0) <= max_entries)
+      ++g1;
     m_max = std::max(m_max, win_at(g1) - win_at(g0));
     groups.push_back(g1);
     g0 = g1;
   }
-  // 6) the columns of the largest group, 7) group by group: gather the columns of (window, rung), match them where they lie
+  // 6) the columns of the largest group, 7) group by group: gather the columns of every query, match them where they lie
   void *d_gk, *d_gq;
   SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SC_KEY, m_max * 4 + 64, &d_gk));
   SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SC_QO, m_max * 4 + 64, &d_gq));
   std::vector<uint64_t> query_off;
   for (size_t g = 0; g + 1 < groups.size(); ++g) {
-    const uint64_t g0 = groups[g], g1 = groups[g + 1], base = win_at(g0), m = win_at(g1) - base, nq = (g1 - g0) * kc;
+    const uint64_t g0 = groups[g], g1 = groups[g + 1], base = win_at(g0), m = win_at(g1) - base, o = slot_at(g0), nq = slot_at(g1) - o;
+    if (nq == 0) continue;   // (windows without a slot)
     if (timed) SHZ_HIP(ctx, hipEventRecord(ctx->sc_ev[2], ctx->stream));
     if (m) {
-      hipLaunchKernelGGL(sc_gather_kernel, dim3((unsigned)nq), dim3(SC_THREADS), 0, ctx->stream, (const sc_rec*)d_rec, nr, g0 * kc,
-                         d_speed, kc, S.step_frames, (const uint64_t*)d_first, (const uint64_t*)d_offs, base, m, S.d_key, S.d_t1,
-                         (uint32_t*)d_gk, (uint32_t*)d_gq);
+      hipLaunchKernelGGL(sc_gather_kernel, dim3((unsigned)nq), dim3(SC_THREADS), 0, ctx->stream, (const sc_rec*)d_rec, nr, o, d_speed,
+                         kc, d_soff, d_swarp, S.step_frames, (const uint64_t*)d_first, (const uint64_t*)d_offs, base, m, S.d_key,
+                         S.d_t1, (uint32_t*)d_gk, (uint32_t*)d_gq);
       SHZ_HIP(ctx, hipGetLastError());
     }
     if (timed) SHZ_HIP(ctx, hipEventRecord(ctx->sc_ev[3], ctx->stream));
     query_off.resize((size_t)nq + 1);
-    for (uint64_t w = g0; w < g1; ++w) {
-      const uint64_t nch = (win_item[w + 1] - win_item[w]) / kc;
-      for (uint32_t v = 0; v < kc; ++v) query_off[(size_t)((w - g0) * kc + v)] = offs[win_item[w] + v * nch] - base;
-    }
+    for (uint64_t w = g0; w < g1; ++w)
+      for (uint64_t j = 0, nj = slot_at(w + 1) - slot_at(w); j < nj; ++j)
+        query_off[(size_t)(slot_at(w) - o + j)] = offs[win_item[w] + j * win_nch[w]] - base;
     query_off[nq] = m;
-    const uint64_t o = g0 * kc;
     SHZ_TRY(shz_match_device(ctx, t, (const uint32_t*)d_gk, (const uint32_t*)d_gq, query_off.data(), (uint32_t)nq, topn, S.flags,
                              S.bias_bound, S.sid + o * topn, S.delta + o * topn, S.aligned + o * topn, S.dedup + o * topn,
                              S.nres + o, S.nhash ? S.nhash + o : nullptr, S.npairs ? S.npairs + o : nullptr));
@@ -381,33 +449,47 @@ extern "C" int32_t shz_scan_timeline(const uint64_t* win_off, uint32_t n_recs, c
   return n > cap ? SHZ_E_CAPACITY : SHZ_OK;
 }
 
-// ---- scanning at an unknown speed -------------------------------------------------------------------
-// The peaks of every recording are extracted once and warped for every rung of a ladder (shz_speed.hip); the warped hash
-// list of (recording, rung, channel) has non-decreasing t1', so it goes through the window stage as it is.  Work goes in
-// slices of (whole recordings x a contiguous chunk of rungs): a warp pass and one call of the stage each.
-extern "C" int32_t shz_scan_speeds(shz_ctx* ctx, shz_table* t, const int16_t* pcm, const uint64_t* clip_off, uint32_t n_clips,
-                                   const uint32_t* rec_clip0, uint32_t n_recs, uint32_t fs, double amp_min, uint32_t fan_value,
-                                   uint32_t window_frames, uint32_t step_frames, uint32_t topn, const uint32_t* speed_q16,
-                                   uint32_t n_speeds, uint32_t flags, uint64_t* win_off, uint32_t* out_best, uint32_t* out_sid,
-                                   int32_t* out_delta, uint32_t* out_aligned, uint32_t* out_dedup, uint32_t* out_nres,
-                                   uint32_t* out_nhash, uint64_t* out_npairs, uint32_t* out_profile, uint64_t cap_windows,
-                                   uint64_t* count, float* ms_extract, float* ms_warp, float* ms_window, float* ms_match) {
-  const char* who = "shz_scan_speeds";
+// ---- scanning at an unknown speed, or at unknown tempo and pitch -------------------------------
+// The peaks of every recording are extracted once and warped for every variant of a list (shz_speed.hip); the warped hash
+// list of (recording, warp, channel) has non-decreasing t1', so it goes through the window stage as it is.  Work goes in
+// slices of (whole recordings x a contiguous chunk of warps): a warp pass and one call of the stage each.  Only the time
+// factor of a warp enters a time: the window borders, the query offsets and the bias bound.  With a selection every window
+// tries its own sub-list; warps that no window tries are dropped first, and a slice hands the stage the slots of its chunk.
+static uint32_t sc_warp_dist(uint32_t t16, uint32_t f16) {
+  auto off = [](uint32_t s) { return s > SP_S_ONE ? s - SP_S_ONE : SP_S_ONE - s; };
+  return off(t16) + off(f16);
+}
+
+// The one driver of both entry points.  who, n_name, t_name, f_name: the caller's own names for the call, the list's length
+// and its two tables in everything that is refused.
+static int32_t sc_scan_warps(shz_ctx* ctx, shz_table* t, const char* who, const char* n_name, const char* t_name, const char* f_name,
+                             const int16_t* pcm, const uint64_t* clip_off, uint32_t n_clips, const uint32_t* rec_clip0,
+                             uint32_t n_recs, uint32_t fs, double amp_min, uint32_t fan_value, uint32_t window_frames,
+                             uint32_t step_frames, uint32_t topn, const uint32_t* tempo_q16, const uint32_t* pitch_q16,
+                             uint32_t n_warps, const uint64_t* sel_off, const uint32_t* sel_warp, uint32_t flags, uint64_t* win_off,
+                             uint32_t* out_best, uint32_t* out_sid, int32_t* out_delta, uint32_t* out_aligned, uint32_t* out_dedup,
+                             uint32_t* out_nres, uint32_t* out_nhash, uint64_t* out_npairs, uint32_t* out_profile,
+                             uint64_t* out_work, uint64_t cap_windows, uint64_t* count, float* ms_extract, float* ms_warp,
+                             float* ms_window, float* ms_match) {
   if (!ctx || !t) return SHZ_E_INVALID;
   if (ms_extract) *ms_extract = 0.f;
   if (ms_warp) *ms_warp = 0.f;
   if (ms_window) *ms_window = 0.f;
   if (ms_match) *ms_match = 0.f;
   if (count) *count = 0;
+  if (out_work) out_work[0] = out_work[1] = 0;
   // everything that can be refused is refused before the first launch
   SHZ_TRY(sc_check(ctx, who, flags, win_off, count, window_frames, step_frames));
-  SHZ_TRY(sp_check_ladder(ctx, who, "n_speeds", "speed", speed_q16, "speed", speed_q16, n_speeds, fan_value));
-  const uint32_t K = n_speeds, s_max = *std::max_element(speed_q16, speed_q16 + K);
-  // no window is longer at any rung: W_v(s + window) - W_v(s) <= ceil(window s16 / 65536)
+  SHZ_TRY(sp_check_ladder(ctx, who, n_name, t_name, tempo_q16, f_name, pitch_q16, n_warps, fan_value));
+  if ((sel_off == nullptr) != (sel_warp == nullptr))
+    SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: sel_off and sel_warp go together; one of them is NULL", who);
+  const bool sel = sel_off != nullptr;
+  const uint32_t s_max = *std::max_element(tempo_q16, tempo_q16 + n_warps);   // (time alone: pitch_q16 never enters a time)
+  // no window is longer at any warp: W_v(s + window) - W_v(s) <= ceil(window t16 / 65536)
   const uint64_t len_max = ((uint64_t)window_frames * s_max + 65535) >> 16;
   if (len_max >= (1ull << 20))
-    SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "shz_scan_speeds: a window of %u frames at factor %u / 65536 is %llu frames long; query offsets must be < 2^20",
-             window_frames, s_max, (unsigned long long)len_max);
+    SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "%s: a window of %u frames at time factor %u / 65536 is %llu frames long; query offsets must be < 2^20",
+             who, window_frames, s_max, (unsigned long long)len_max);
   SHZ_TRY(sc_check_recs(ctx, who, clip_off, n_clips, rec_clip0, n_recs, win_off));
   if (n_recs == 0) return SHZ_OK;
   if (fs == 0) SHZ_FAIL(ctx, SHZ_E_INVALID, "Fs must be > 0");
@@ -417,7 +499,46 @@ extern "C" int32_t shz_scan_speeds(shz_ctx* ctx, shz_table* t, const int16_t* pc
   SHZ_TRY(sc_count_windows(ctx, who, clip_off, rec_clip0, n_recs, window_frames, step_frames, cap_windows, win_off, count, &frames));
   const uint64_t n_wins = *count;
   if (n_wins == 0) return SHZ_OK;
-  if (!out_best || !out_sid || !out_delta || !out_aligned || !out_dedup || !out_nres) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_scan_speeds: NULL buffer");
+  if (!out_best || !out_sid || !out_delta || !out_aligned || !out_dedup || !out_nres) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: NULL buffer", who);
+  // the selection: a CSR over the windows, every list strictly ascending and inside the warps.  used[v]: a window tries v
+  std::vector<uint32_t> c_t16, c_f16, c_of, c_index;   // the warps in use (compacted), their old indices, old -> new
+  if (sel) {
+    if (sel_off[0] != 0) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: sel_off[0] is %llu, not 0", who, (unsigned long long)sel_off[0]);
+    for (uint64_t w = 0; w < n_wins; ++w)
+      if (sel_off[w + 1] < sel_off[w]) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: sel_off decreases at window %llu", who, (unsigned long long)w);
+    std::vector<uint8_t> used(n_warps, 0);
+    for (uint64_t w = 0; w < n_wins; ++w)
+      for (uint64_t j = sel_off[w]; j < sel_off[w + 1]; ++j) {
+        if (sel_warp[j] >= n_warps)
+          SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: slot %llu of window %llu is warp %u of %u", who, (unsigned long long)(j - sel_off[w]),
+                   (unsigned long long)w, sel_warp[j], n_warps);
+        if (j > sel_off[w] && sel_warp[j] <= sel_warp[j - 1])
+          SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: the list of window %llu is not strictly ascending at slot %llu", who, (unsigned long long)w,
+                   (unsigned long long)(j - sel_off[w]));
+        used[sel_warp[j]] = 1;
+      }
+    c_index.assign(n_warps, 0);
+    for (uint32_t v = 0; v < n_warps; ++v)
+      if (used[v]) {
+        c_index[v] = (uint32_t)c_of.size();
+        c_of.push_back(v);
+        c_t16.push_back(tempo_q16[v]);
+        c_f16.push_back(pitch_q16[v]);
+      }
+    // windows without a slot keep this: no results, no variant
+    memset(out_sid, 0, n_wins * topn * 4); memset(out_delta, 0, n_wins * topn * 4); memset(out_aligned, 0, n_wins * topn * 4);
+    memset(out_dedup, 0, n_wins * topn * 4); memset(out_nres, 0, n_wins * 4);
+    if (out_nhash) memset(out_nhash, 0, n_wins * 4);
+    if (out_npairs) memset(out_npairs, 0, n_wins * 8);
+    if (out_profile) memset(out_profile, 0, sel_off[n_wins] * 4);
+    if (c_of.empty()) {   // nothing is selected: nothing is extracted
+      for (uint64_t w = 0; w < n_wins; ++w) out_best[w] = SHZ_SCAN_NO_WARP;
+      return SHZ_OK;
+    }
+  }
+  const uint32_t K = sel ? (uint32_t)c_of.size() : n_warps;   // from here on: the compacted list
+  const uint32_t* k_t16 = sel ? c_t16.data() : tempo_q16;
+  const uint32_t* k_f16 = sel ? c_f16.data() : (pitch_q16 == tempo_q16 ? k_t16 : pitch_q16);
   SHZ_HIP(ctx, hipSetDevice(ctx->device));
   const bool timed = ms_extract || ms_warp || ms_window || ms_match;
   if (timed) {
@@ -436,23 +557,24 @@ extern "C" int32_t shz_scan_speeds(shz_ctx* ctx, shz_table* t, const int16_t* pc
     if (ms_extract) SHZ_HIP(ctx, hipEventElapsedTime(ms_extract, ctx->sc_ev[0], ctx->sc_ev[1]));
   }
   const uint64_t* d_poff;
-  const uint32_t *d_speed, *d_same;   // one ladder for time and frequency
-  SHZ_TRY(sp_upload_tables(ctx, peak_off.data(), n_clips, speed_q16, speed_q16, K, &d_poff, &d_speed, &d_same));
-  // 2) slices of whole recordings x a chunk of rungs: the entries a slice's warp can yield at most (every peak with all its
-  // partners, at every rung of the chunk) stay within the match's pair budget and 1/8 of the workspace limit.  The ladder
-  // is cut only where one recording at all rungs is beyond that; one (recording, rung) beyond it is a slice of its own
+  const uint32_t *d_tempo, *d_pitch;   // (a speed ladder: one table for time and frequency)
+  SHZ_TRY(sp_upload_tables(ctx, peak_off.data(), n_clips, k_t16, k_f16, K, &d_poff, &d_tempo, &d_pitch));
+  // 2) slices of whole recordings x a chunk of warps: the entries a slice's warp can yield at most (every peak with all its
+  // partners, at every warp of the chunk) stay within the match's pair budget and 1/8 of the workspace limit.  The list
+  // is cut only where one recording at all warps is beyond that; one (recording, warp) beyond it is a slice of its own
   const bool small = (ctx->debug & SHZ_DEBUG_SCAN_SPEED_SMALL_SLICES) != 0;
   const uint64_t per_item = std::max<uint32_t>(fan_value - 1, 1);
   const uint64_t warp_entries = std::min<uint64_t>(std::max<uint64_t>(ctx->ws_limit / 64, 1), 1ull << 28);
-  auto dist = [&](uint32_t v) { return speed_q16[v] > SP_S_ONE ? speed_q16[v] - SP_S_ONE : SP_S_ONE - speed_q16[v]; };
   std::vector<uint32_t> best_top1((size_t)n_wins, 0);
-  std::vector<uint32_t> v_sid, v_aligned, v_dedup, v_nres, v_nhash;
+  for (uint64_t w = 0; w < n_wins; ++w) out_best[w] = SHZ_SCAN_NO_WARP;   // (no variant tried yet)
+  std::vector<uint32_t> v_sid, v_aligned, v_dedup, v_nres, v_nhash, s_warp;
   std::vector<int32_t> v_delta;
-  std::vector<uint64_t> v_npairs, ho;
+  std::vector<uint64_t> v_npairs, ho, s_off, s_first;
+  uint64_t work_hashes = 0, work_entries = 0;
   float warp_ms = 0.f, win_ms = 0.f, match_ms = 0.f;
   for (uint32_t r0 = 0; r0 < n_recs;) {
     uint32_t nr = 1, kc = K;
-    const uint64_t one = sp_items(peak_off.data(), rec_clip0, r0, 1, 1) * per_item;   // one rung of the first recording
+    const uint64_t one = sp_items(peak_off.data(), rec_clip0, r0, 1, 1) * per_item;   // one warp of the first recording
     if (one * K > warp_entries) kc = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(warp_entries / std::max<uint64_t>(one, 1), 1), K);
     if (small) kc = std::min(kc, SS_SMALL_RUNGS);
     if (kc == K && !small)
@@ -466,42 +588,64 @@ extern "C" int32_t shz_scan_speeds(shz_ctx* ctx, shz_table* t, const int16_t* pc
     }
     for (uint32_t v0 = 0; v0 < K; v0 += kc) {
       const uint32_t kcc = std::min(kc, K - v0);
-      // 2a) the warp of the slice: hashes of (recording, rung, channel), the exact CSR on both sides (events 0 and 1 are
+      // 2a) the warp of the slice: hashes of (recording, warp, channel), the exact CSR on both sides (events 0 and 1 are
       // free again: the window stage keeps to the others)
       if (timed) SHZ_HIP(ctx, hipEventRecord(ctx->sc_ev[0], ctx->stream));
       const uint64_t n_seg = (uint64_t)(rec_clip0[r0 + nr] - rec_clip0[r0]) * kcc;
       ho.assign((size_t)n_seg + 1, 0);
       sp_pass P;
-      SHZ_TRY(sp_count(ctx, d_pf, d_pt, d_poff, peak_off.data(), rec_clip0, r0, nr, d_speed + v0, d_same + v0, kcc, fan_value, &P, ho.data()));
+      SHZ_TRY(sp_count(ctx, d_pf, d_pt, d_poff, peak_off.data(), rec_clip0, r0, nr, d_tempo + v0, d_pitch + v0, kcc, fan_value, &P, ho.data()));
       const uint64_t total = ho[n_seg];
+      work_hashes += total;
       void *d_key, *d_t1;
       SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SP_KEY, total * 4 + 64, &d_key));
       SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SP_T1, total * 4 + 64, &d_t1));
       if (total) SHZ_TRY(sp_write(ctx, P, (uint32_t*)d_key, (uint32_t*)d_t1, total));
       if (timed) SHZ_HIP(ctx, hipEventRecord(ctx->sc_ev[1], ctx->stream));
+      // the slots of the chunk: the part [v0, v0 + kcc) of every window's list (ascending, so one range of it), as indices
+      // into the chunk.  s_first[w]: where that range begins in the call's sel_warp
+      uint64_t nvq = nws * kcc;
+      if (sel) {
+        s_off.assign((size_t)nws + 1, 0);
+        s_first.assign((size_t)nws, 0);
+        s_warp.clear();
+        for (uint64_t w = 0; w < nws; ++w) {
+          const uint64_t gw = win_off[r0] + w;
+          uint64_t j = sel_off[gw];
+          while (j < sel_off[gw + 1] && c_index[sel_warp[j]] < v0) ++j;
+          s_first[w] = j;
+          for (; j < sel_off[gw + 1] && c_index[sel_warp[j]] < v0 + kcc; ++j) s_warp.push_back(c_index[sel_warp[j]] - v0);
+          s_off[w + 1] = s_warp.size();
+        }
+        nvq = s_warp.size();
+      }
       // 2b) + 2c) the window stage on the warped lists.  A hash lies in at most ceil(window / step) windows, +1 where the
       // warp's rounding moves a border; no query offset reaches len_max.  (A pass without hashes has no CSR on the device)
-      const uint64_t nvq = nws * kcc;
       v_sid.assign(nvq * topn, 0); v_aligned.assign(nvq * topn, 0); v_dedup.assign(nvq * topn, 0); v_delta.assign(nvq * topn, 0);
       v_nres.assign(nvq, 0); v_nhash.assign(nvq, 0); v_npairs.assign(nvq, 0);
-      sc_slice S{rec_clip0 + r0, win_off + r0, nr, kcc, d_speed + v0, total ? (const uint64_t*)P.d_hoff : nullptr, false,
+      sc_slice S{rec_clip0 + r0, win_off + r0, nr, kcc, d_tempo + v0, total ? (const uint64_t*)P.d_hoff : nullptr, false,
                  (const uint32_t*)d_key, (const uint32_t*)d_t1, total, window_frames, step_frames, topn, flags & SHZ_MATCH_FULL_SORT,
                  (int64_t)len_max - 1, ((uint64_t)window_frames + step_frames - 1) / step_frames + 1, small, v_sid.data(),
-                 v_aligned.data(), v_dedup.data(), v_nres.data(), v_nhash.data(), v_delta.data(), v_npairs.data()};
+                 v_aligned.data(), v_dedup.data(), v_nres.data(), v_nhash.data(), v_delta.data(), v_npairs.data(),
+                 sel ? s_off.data() : nullptr, sel ? s_warp.data() : nullptr, &work_entries};
       SHZ_TRY(sc_windows(ctx, t, who, S, timed, &win_ms, &match_ms));
       if (timed) {
         float a = 0.f;
         SHZ_HIP(ctx, hipEventElapsedTime(&a, ctx->sc_ev[0], ctx->sc_ev[1]));
         warp_ms += a;
       }
-      // 2d) the best rung of every window, folded over the chunks (sp_best's rule: rungs come in index order)
+      // 2d) the best variant of every window, folded over the chunks (sp_best's rule: variants come in index order)
       for (uint64_t w = 0; w < nws; ++w) {
-        const uint64_t gw = win_off[r0] + w;
-        for (uint32_t v = 0; v < kcc; ++v) {
-          const uint64_t src = w * kcc + v;
-          const uint32_t top1 = v_nres[src] ? v_aligned[src * topn] : 0u, gv = v0 + v;
-          if (out_profile) out_profile[gw * K + gv] = top1;
-          if (gv != 0 && !(top1 > best_top1[gw] || (top1 == best_top1[gw] && dist(gv) < dist(out_best[gw])))) continue;
+        const uint64_t gw = win_off[r0] + w, q0 = sel ? s_off[w] : w * kcc, nq = sel ? s_off[w + 1] - s_off[w] : kcc;
+        for (uint64_t j = 0; j < nq; ++j) {
+          const uint64_t src = q0 + j;
+          const uint32_t cv = v0 + (sel ? s_warp[src] : (uint32_t)j), gv = sel ? c_of[cv] : cv;   // compacted / the caller's index
+          const uint32_t top1 = v_nres[src] ? v_aligned[src * topn] : 0u;
+          if (out_profile) out_profile[sel ? s_first[w] + j : gw * K + gv] = top1;
+          if (out_best[gw] != SHZ_SCAN_NO_WARP &&
+              !(top1 > best_top1[gw] || (top1 == best_top1[gw] && sc_warp_dist(tempo_q16[gv], pitch_q16[gv]) <
+                                                                      sc_warp_dist(tempo_q16[out_best[gw]], pitch_q16[out_best[gw]]))))
+            continue;
           best_top1[gw] = top1;
           out_best[gw] = gv;
           memcpy(out_sid + gw * topn, v_sid.data() + src * topn, (size_t)topn * 4);
@@ -516,10 +660,51 @@ extern "C" int32_t shz_scan_speeds(shz_ctx* ctx, shz_table* t, const int16_t* pc
     }
     r0 += nr;
   }
+  if (out_work) {
+    out_work[0] = work_hashes;
+    out_work[1] = work_entries;
+  }
   if (ms_warp) *ms_warp = warp_ms;
   if (ms_window) *ms_window = win_ms;
   if (ms_match) *ms_match = match_ms;
   return SHZ_OK;
+}
+
+extern "C" int32_t shz_scan_warps(shz_ctx* ctx, shz_table* t, const int16_t* pcm, const uint64_t* clip_off, uint32_t n_clips,
+                                  const uint32_t* rec_clip0, uint32_t n_recs, uint32_t fs, double amp_min, uint32_t fan_value,
+                                  uint32_t window_frames, uint32_t step_frames, uint32_t topn, const uint32_t* tempo_q16,
+                                  const uint32_t* pitch_q16, uint32_t n_warps, const uint64_t* sel_off, const uint32_t* sel_warp,
+                                  uint32_t flags, uint64_t* win_off, uint32_t* out_best, uint32_t* out_sid, int32_t* out_delta,
+                                  uint32_t* out_aligned, uint32_t* out_dedup, uint32_t* out_nres, uint32_t* out_nhash,
+                                  uint64_t* out_npairs, uint32_t* out_profile, uint64_t* out_work, uint64_t cap_windows,
+                                  uint64_t* count, float* ms_extract, float* ms_warp, float* ms_window, float* ms_match) {
+  return sc_scan_warps(ctx, t, "shz_scan_warps", "n_warps", "tempo", "pitch", pcm, clip_off, n_clips, rec_clip0, n_recs, fs, amp_min,
+                       fan_value, window_frames, step_frames, topn, tempo_q16, pitch_q16, n_warps, sel_off, sel_warp, flags, win_off,
+                       out_best, out_sid, out_delta, out_aligned, out_dedup, out_nres, out_nhash, out_npairs, out_profile, out_work,
+                       cap_windows, count, ms_extract, ms_warp, ms_window, ms_match);
+}
+
+// the speed ladder: one table for time and frequency, no selection (its own names in whatever is refused)
+extern "C" int32_t shz_scan_speeds(shz_ctx* ctx, shz_table* t, const int16_t* pcm, const uint64_t* clip_off, uint32_t n_clips,
+                                   const uint32_t* rec_clip0, uint32_t n_recs, uint32_t fs, double amp_min, uint32_t fan_value,
+                                   uint32_t window_frames, uint32_t step_frames, uint32_t topn, const uint32_t* speed_q16,
+                                   uint32_t n_speeds, uint32_t flags, uint64_t* win_off, uint32_t* out_best, uint32_t* out_sid,
+                                   int32_t* out_delta, uint32_t* out_aligned, uint32_t* out_dedup, uint32_t* out_nres,
+                                   uint32_t* out_nhash, uint64_t* out_npairs, uint32_t* out_profile, uint64_t cap_windows,
+                                   uint64_t* count, float* ms_extract, float* ms_warp, float* ms_window, float* ms_match) {
+  return sc_scan_warps(ctx, t, "shz_scan_speeds", "n_speeds", "speed", "speed", pcm, clip_off, n_clips, rec_clip0, n_recs, fs, amp_min,
+                       fan_value, window_frames, step_frames, topn, speed_q16, speed_q16, n_speeds, nullptr, nullptr, flags, win_off,
+                       out_best, out_sid, out_delta, out_aligned, out_dedup, out_nres, out_nhash, out_npairs, out_profile, nullptr,
+                       cap_windows, count, ms_extract, ms_warp, ms_window, ms_match);
+}
+
+// The song's advance between the starts of two hit windows `gap` windows apart, W_t16(gap step) = (gap step t16 + 32768) >> 16,
+// exact: gap and step are below 2^32 each and t16 at most 2^17, so the product needs 81 bits.  Positions are int32, so an
+// advance of 2^40 or more fails every shift_tol as the exact value would; the result is clamped there.
+static int64_t sc_advance(uint64_t gap, uint32_t step_frames, uint32_t t16) {
+  const unsigned __int128 adv = ((unsigned __int128)gap * step_frames * t16 + 32768u) >> 16;
+  const uint64_t top = 1ull << 40;
+  return (int64_t)(adv > top ? top : (uint64_t)adv);
 }
 
 // The per-window answers of a speed-tolerant scan folded into segments, on the host.  delta - w step is not constant when
@@ -574,7 +759,7 @@ extern "C" int32_t shz_scan_timeline_speeds(const uint64_t* win_off, uint32_t n_
       bool cont = open && s == o_sid && w - o_last - 1 <= max_gap && (v > o_rung ? v - o_rung : o_rung - v) <= rung_tol;
       if (cont) {
         // the song advances W_v((w - w_last) step) frames between the two windows' starts
-        const int64_t adv = (int64_t)((((w - o_last) * (uint64_t)step_frames) * speed_q16[v] + 32768u) >> 16);
+        const int64_t adv = sc_advance(w - o_last, step_frames, speed_q16[v]);
         const int64_t off = pos - o_pos_last - adv;
         cont = (off < 0 ? -off : off) <= (int64_t)shift_tol;
       }
@@ -595,6 +780,92 @@ extern "C" int32_t shz_scan_timeline_speeds(const uint64_t* win_off, uint32_t n_
       o_best = a;
       o_pos_first = o_pos_last = pos;
       o_rung = v;
+      std::fill(chosen.begin(), chosen.end(), 0u);
+      chosen[v] = 1;
+    }
+    close();
+  }
+  *count = n;
+  return n > cap ? SHZ_E_CAPACITY : SHZ_OK;
+}
+
+// The per-window answers of a scan over warps folded into segments, on the host: shz_scan_timeline_speeds with a tolerance for
+// each factor in place of the rung distance, so the list need not be sorted.  best is read for hits only.
+extern "C" int32_t shz_scan_timeline_warps(const uint64_t* win_off, uint32_t n_recs, const uint32_t* sid, const int32_t* delta,
+                                           const uint32_t* aligned, const uint32_t* nres, const uint32_t* best, uint32_t topn,
+                                           uint32_t step_frames, const uint32_t* tempo_q16, const uint32_t* pitch_q16,
+                                           uint32_t n_warps, uint32_t min_aligned, uint32_t max_gap, uint32_t tempo_tol_q16,
+                                           uint32_t pitch_tol_q16, uint32_t shift_tol, uint32_t* seg_rec, uint32_t* seg_sid,
+                                           uint32_t* seg_first, uint32_t* seg_last, uint32_t* seg_hits, uint32_t* seg_best,
+                                           int32_t* seg_pos_first, int32_t* seg_pos_last, uint32_t* seg_warp, uint64_t cap,
+                                           uint64_t* count) {
+  if (!count) return SHZ_E_INVALID;
+  *count = 0;
+  if (n_recs == 0) return SHZ_OK;
+  if (!win_off || topn == 0 || !tempo_q16 || !pitch_q16 || n_warps == 0) return SHZ_E_INVALID;
+  for (uint32_t v = 0; v < n_warps; ++v)
+    if (tempo_q16[v] < SP_S_MIN || tempo_q16[v] > SP_S_MAX || pitch_q16[v] < SP_S_MIN || pitch_q16[v] > SP_S_MAX) return SHZ_E_INVALID;
+  for (uint32_t r = 0; r < n_recs; ++r)
+    if (win_off[r + 1] < win_off[r] || win_off[r + 1] - win_off[r] > 0xFFFFFFFFull) return SHZ_E_INVALID;
+  if (win_off[n_recs] > win_off[0] && (!sid || !delta || !aligned || !nres || !best)) return SHZ_E_INVALID;
+  if (cap && (!seg_rec || !seg_sid || !seg_first || !seg_last || !seg_hits || !seg_best || !seg_pos_first || !seg_pos_last || !seg_warp))
+    return SHZ_E_INVALID;
+  auto hit = [&](uint64_t g) { return nres[g] >= 1 && aligned[g * topn] >= min_aligned; };
+  for (uint64_t g = win_off[0]; g < win_off[n_recs]; ++g)
+    if (hit(g) && best[g] >= n_warps) return SHZ_E_INVALID;
+  auto apart = [](uint32_t a, uint32_t b) { return a > b ? a - b : b - a; };
+  std::vector<uint32_t> chosen(n_warps, 0);   // how often the open segment's hits chose every variant
+  uint64_t n = 0;
+  for (uint32_t r = 0; r < n_recs; ++r) {
+    bool open = false;
+    uint32_t o_sid = 0, o_first = 0, o_last = 0, o_hits = 0, o_best = 0, o_v = 0;
+    int64_t o_pos_first = 0, o_pos_last = 0;
+    auto close = [&]() {
+      if (open && n < cap) {
+        seg_rec[n] = r;
+        seg_sid[n] = o_sid;
+        seg_first[n] = o_first;
+        seg_last[n] = o_last;
+        seg_hits[n] = o_hits;
+        seg_best[n] = o_best;
+        seg_pos_first[n] = (int32_t)o_pos_first;
+        seg_pos_last[n] = (int32_t)o_pos_last;
+        seg_warp[n] = sp_best(chosen.data(), tempo_q16, pitch_q16, n_warps);
+      }
+      n += open ? 1 : 0;
+      open = false;
+    };
+    const uint64_t nw = win_off[r + 1] - win_off[r];
+    for (uint64_t w = 0; w < nw; ++w) {
+      const uint64_t g = win_off[r] + w;
+      if (!hit(g)) continue;   // no hit: changes nothing
+      const uint32_t s = sid[g * topn], a = aligned[g * topn], v = best[g];
+      const int64_t pos = delta[g * topn];
+      bool cont = open && s == o_sid && w - o_last - 1 <= max_gap && apart(tempo_q16[v], tempo_q16[o_v]) <= tempo_tol_q16 &&
+                  apart(pitch_q16[v], pitch_q16[o_v]) <= pitch_tol_q16;
+      if (cont) {
+        // the song advances W_t16((w - w_last) step) frames between the two windows' starts
+        const int64_t adv = sc_advance(w - o_last, step_frames, tempo_q16[v]);
+        const int64_t off = pos - o_pos_last - adv;
+        cont = (off < 0 ? -off : off) <= (int64_t)shift_tol;
+      }
+      if (cont) {
+        o_last = (uint32_t)w;
+        ++o_hits;
+        o_best = std::max(o_best, a);
+        o_pos_last = pos;
+        o_v = v;
+        ++chosen[v];
+        continue;
+      }
+      close();
+      open = true;
+      o_sid = s;
+      o_first = o_last = (uint32_t)w;
+      o_hits = 1;
+      o_best = a;
+      o_pos_first = o_pos_last = pos;
+      o_v = v;
       std::fill(chosen.begin(), chosen.end(), 0u);
       chosen[v] = 1;
     }

@@ -7,7 +7,12 @@ into segments (shz_scan_timeline).
 
 A window's hashes are a SUBSET of the whole recording's hashes -- not what fingerprinting the cut audio would give: peaks
 near a cut see their neighbours beyond it, and a pair counts for the window its anchor lies in.  A recording must fit one
-extraction pass (2^20 frames, about 13.5 hours at the default hop); chaining longer files is the caller's."""
+extraction pass (2^20 frames, about 13.5 hours at the default hop); chaining longer files is the caller's.
+
+Recordings that play at another speed are scanned at a speed ladder (speeds=); recordings whose tempo and
+pitch moved by factors of their own at a list of warp pairs (tempos= / pitches= / warps=), every window at
+every pair (search="grid") or, far cheaper, every window at the pitch ladder and then at the tempo ladder beside its own best
+pitch (search="separable", a heuristic), which rests on the library's per-window variant lists."""
 from __future__ import annotations
 
 import numpy as np
@@ -41,8 +46,97 @@ def _ladder(speeds):
     return speed_ladder() if speeds is True else _check_speeds(speeds)
 
 
+# shift_tol of a scan over warps.  Between neighbouring hits of one piece |delta2 - delta1 - W(step)| was at
+# most 1 frame on the fixture of tests/test_gpu_scan_warps.py under the default ladders, and 3 frames where a piece's tempo
+# (1.08) lies between two rungs of the default tempo ladder (1.042, 1.084) and neighbouring windows choose either: a window
+# matched at a tempo that is off by d sees the song position of about its middle, off by d x window / 2 -- one rung (4.2 %)
+# over half a 108-frame window is 2.3 frames, plus the rounding.  The largest measured value plus one frame for the rounding
+# of the two deltas.
+WARP_SHIFT_TOL = 4
+
+
+def _rung(ladder) -> int:
+    """The largest gap between neighbouring distinct values of a Q16 list (0 for a single value)."""
+    u = np.unique(np.asarray(ladder, np.int64))
+    return int(np.diff(u).max()) if len(u) > 1 else 0
+
+
+def _warp_dist(t16, f16):
+    return np.abs(np.asarray(t16, np.int64) - 65536) + np.abs(np.asarray(f16, np.int64) - 65536)
+
+
+def _merge_dense(parts, t16, f16):
+    """Dense scan_warps results over consecutive chunks of a pair list as one call over the whole list gives them."""
+    from .speed import merge_warp_chunks
+    work = tuple(int(sum(p["work"][i] for p in parts)) for i in range(2))
+    out = merge_warp_chunks([{k: v for k, v in p.items() if k != "work"} for p in parts], t16, f16)
+    out["work"] = work
+    return out
+
+
+def _scan_warp_windows(run, tl, pl, t16, f16, row, search):
+    """The library calls of a scan over warps.  run(t16, f16, select) -> (res, win_off, ms) is Context.scan_warps on the
+    prepared audio.  Returns (res, win_off, ms); res["warps"] = (t16, f16) of the variants res["best"] indexes."""
+    from .speed import S_ONE, warp_chunks, warp_grid
+    ms = np.zeros(4)
+
+    def dense(a16, b16, r):
+        parts, wo = [], None
+        for a, b in warp_chunks(len(a16), r):
+            res, wo, m = run(a16[a:b], b16[a:b], None)
+            parts.append(res)
+            ms[:] += m
+        return _merge_dense(parts, a16, b16), wo
+    if search == "grid":
+        res, win_off = dense(t16, f16, row)
+        res["tried"], res["warps"] = np.ones(res["profile"].shape, bool), (t16, f16)
+        return res, win_off, ms
+    # separable: the pitch ladder at tempo 1, then per window the tempo ladder at its own best pitch
+    one = np.full(len(pl), S_ONE, np.uint32)
+    res, win_off = dense(one, pl, 1)
+    n_wins = len(res["best"])
+    res["stage1"] = {"best": res["best"].copy(), "profile": res["profile"], "work": res["work"]}
+    found = res["profile"][np.arange(n_wins), res["best"]] >= 1 if n_wins else np.zeros(0, bool)
+    rungs = np.unique(res["best"][found])                      # the distinct pitch rungs stage 1's windows chose
+    others = np.flatnonzero(tl != S_ONE)
+    g_t, g_f = warp_grid(tl, pl[rungs]) if len(rungs) else (np.zeros(0, np.uint32), np.zeros(0, np.uint32))
+    all_t, all_f = np.concatenate([one, g_t]), np.concatenate([pl, g_f])
+    profile = np.zeros((n_wins, len(all_t)), np.uint32)
+    tried = np.zeros((n_wins, len(all_t)), bool)
+    profile[:, :len(pl)], tried[:, :len(pl)] = res["profile"], True
+    work2 = (0, 0)
+    if len(rungs) and len(others):
+        col = np.searchsorted(rungs, res["best"])              # a window's column of the stage-2 grid
+        lists = [(others * len(rungs) + col[w]) if found[w] else np.zeros(0, np.int64) for w in range(n_wins)]
+        dist = _warp_dist(all_t, all_f)
+        top = profile[np.arange(n_wins), res["best"]].astype(np.int64)
+        for a, b in warp_chunks(len(g_t), len(rungs)):
+            part = [x[(x >= a) & (x < b)] - a for x in lists]
+            so = np.concatenate([[0], np.cumsum([len(x) for x in part])]).astype(np.uint64)
+            sw = np.concatenate(part).astype(np.uint32) if so[-1] else np.zeros(0, np.uint32)
+            r2, _, m = run(g_t[a:b], g_f[a:b], (so, sw))
+            ms[:] += m
+            work2 = (work2[0] + r2["work"][0], work2[1] + r2["work"][1])
+            for w in np.flatnonzero(np.diff(so.astype(np.int64)) > 0).tolist():
+                cols = len(pl) + a + sw[int(so[w]):int(so[w + 1])].astype(np.int64)
+                profile[w, cols], tried[w, cols] = r2["profile"][int(so[w]):int(so[w + 1])], True
+                g = len(pl) + a + int(r2["best"][w])
+                cur = int(res["best"][w])
+                p = int(profile[w, g])
+                if (-p, int(dist[g]), g) < (-int(top[w]), int(dist[cur]), cur):     # the best-variant rule over both stages
+                    top[w] = p
+                    res["best"][w] = g
+                    for k in ("sid", "delta", "aligned", "dedup", "nres", "nhash", "npairs"):
+                        res[k][w] = r2[k][w]
+    res["stage2"] = {"work": work2}
+    res["work"] = (res["work"][0] + work2[0], res["work"][1] + work2[1])
+    res["profile"], res["tried"], res["warps"] = profile, tried, (all_t, all_f)
+    return res, win_off, ms
+
+
 def scan_windows(recordings, db, Fs: int = 44100, window_seconds: float = 5, step_seconds: float = 1, topn: int = TOPN,
-                 resample_to: int = None, full_sort: bool = False, speeds=None):
+                 resample_to: int = None, full_sort: bool = False, speeds=None, tempos=None, pitches=None, warps=None,
+                 search: str = "grid"):
     """Every window of every recording matched in one library call.  recordings: 1-D int16 arrays, or lists of channels as in
     recognize_batch.  Returns a dict: the arrays of Table.match over all windows, recording-major (sid, delta, aligned, dedup
     [n_windows, topn]; nres, nhash, npairs [n_windows]), plus win_off (CSR of the windows over the recordings), frames (F_r
@@ -52,10 +146,28 @@ def scan_windows(recordings, db, Fs: int = 44100, window_seconds: float = 5, ste
     there.  speeds (a Q16 ladder, or True for speed_ladder()): every window is matched at every rung (shz_scan_speeds,
     DESIGN.md 3.7d); the arrays are the best rung's, `delta` is in the TABLE's frames, and the dict gains best (rung index
     per window), profile ([n_windows, K]), speed (the chosen factor per window, float), speeds (the ladder) and ms =
-    (extract, warp, window, match).  speeds=None: the plain scan, untouched."""
+    (extract, warp, window, match).  speeds=None: the plain scan, untouched.
+    tempos / pitches (two Q16 ladders), warps=(t16, f16) and search="grid" | "separable" mean what they mean in
+    recognize_warps and exclude speeds= (ValueError): every window is matched at warp pairs (shz_scan_warps, DESIGN.md
+    3.7i).  The dict then carries best (index per window into warps), warps (the two Q16 lists of the variants), profile
+    ([n_windows, len(warps[0])]: the rank-0 aligned count of every variant) and tried (which of them the window tried: all
+    for the grid), tempo / pitch (the chosen factors per window, float), work = (warped hash entries written, window entries
+    handed to the match) summed over the calls, and ms = (extract, warp, window, match).  search="grid": one dense call;
+    more than 1,024 pairs go in calls of whole tempo rows, merged by the best-variant rule.  search="separable", a
+    HEURISTIC as in recognize_warps: stage 1 scans every window at (65536, p) for every pitch; stage 2 is one call in which
+    every window that stage 1 gave a rank-0 count of at least 1 tries (a, its own best pitch) for every tempo a != 65536 and
+    the other windows try nothing; the answer is the best over everything a window tried, the variants are stage 1's
+    followed by the stage-2 grid (the tempos x the pitch rungs stage 1 chose), and stage1 / stage2 carry the stages' own
+    best / profile / work."""
     from . import DEFAULT_AMP_MIN, DEFAULT_FAN_VALUE, resample_to_device
     if not hasattr(db.table, "h"):
         raise NotImplementedError("scanning takes the unsharded table (shards=1)")
+    warped = tempos is not None or pitches is not None or warps is not None or search != "grid"
+    if warped and speeds is not None:
+        raise ValueError("speeds= is one factor for time and frequency: it excludes tempos=, pitches= and warps=")
+    if warped:
+        from .speed import _warp_list
+        tl, pl, t16, f16, row = _warp_list(tempos, pitches, warps, search)
     ctx = db.ctx
     topn = int(topn)
     db.finalize()
@@ -63,7 +175,12 @@ def scan_windows(recordings, db, Fs: int = 44100, window_seconds: float = 5, ste
     chans, first = _flatten(recordings)
     fs = int(Fs)
     kw = dict(amp_min=float(DEFAULT_AMP_MIN), fan_value=DEFAULT_FAN_VALUE, topn=topn, full_sort=full_sort)
-    if speeds is None:
+    if warped:
+        def run(table, pcm, off, first, wf, sf, **k):
+            call = lambda a16, b16, select: ctx.scan_warps(table, pcm, off, first, wf, sf, a16, b16, select, **k)   # noqa: E731
+            res, win_off, ms = _scan_warp_windows(call, tl, pl, t16, f16, row, search)
+            return res, win_off, tuple(float(m) for m in ms)
+    elif speeds is None:
         run = ctx.scan_batch
     else:
         sp = _ladder(speeds)
@@ -88,6 +205,9 @@ def scan_windows(recordings, db, Fs: int = 44100, window_seconds: float = 5, ste
     res.update(win_off=win_off, frames=frames, window_frames=wf, step_frames=sf, hop=hop, fs=fs, ms=ms)
     if speeds is not None:
         res.update(speeds=sp, speed=sp[res["best"]].astype(np.float64) / 65536.0)
+    if warped:
+        res.update(tempo=res["warps"][0][res["best"]].astype(np.float64) / 65536.0,
+                   pitch=res["warps"][1][res["best"]].astype(np.float64) / 65536.0)
     return res
 
 
@@ -109,7 +229,8 @@ def _segment(db, w, seg, i):
 
 
 def scan(recordings, db, Fs: int = 44100, window_seconds: float = 5, step_seconds: float = 1, topn: int = TOPN,
-         resample_to: int = None, min_aligned: int = 20, max_gap: int = 1, speeds=None, shift_tol: int = 2, rung_tol: int = 1):
+         resample_to: int = None, min_aligned: int = 20, max_gap: int = 1, speeds=None, shift_tol: int = None, rung_tol: int = 1,
+         tempos=None, pitches=None, warps=None, search: str = "grid", tempo_tol: int = None, pitch_tol: int = None):
     """The timeline of every recording: a list (per recording) of segments, each a dict with song_id, song_name,
     start_seconds / end_seconds (the span of the segment's windows in the recording, the last window's end clipped to the
     recording's), offset_seconds (the position in the song at the segment's start: align_matches' formula,
@@ -123,8 +244,22 @@ def scan(recordings, db, Fs: int = 44100, window_seconds: float = 5, step_second
     frames (shz_scan_timeline_speeds; there is no constant shift, so no "shift" key).  A segment then carries "speed" (the
     rung its hits chose most often, as a float), "speed_fit" ((pos_last - pos_first) / ((last - first) * step_frames), None
     for a one-hit segment), "offset_seconds" / "offset_end_seconds" (the song position at the start of its first / last hit
-    window, in the TABLE's seconds) and "pos_first" / "pos_last" (the same in the table's frames)."""
+    window, in the TABLE's seconds) and "pos_first" / "pos_last" (the same in the table's frames).  shift_tol=None: 2.
+    tempos / pitches / warps / search (as in scan_windows; ValueError together with speeds=): tempo and pitch may have moved
+    by factors of their own.  A segment is a run of hits of one song whose neighbours are at most max_gap windows apart, chose
+    tempo factors at most tempo_tol and pitch factors at most pitch_tol apart (Q16; None: one rung each, the largest gap
+    between neighbouring distinct values of the respective list of the variants) and whose song positions advance by the step
+    warped with the TEMPO factor within shift_tol frames (shz_scan_timeline_warps; None: WARP_SHIFT_TOL).  It carries what a
+    speed scan's segment carries, with "tempo" and "pitch" (the pair its hits chose most often, as floats) and "tempo_fit" in
+    place of "speed" and "speed_fit"."""
     from . import OFFSET_SECS
+    if tempos is not None or pitches is not None or warps is not None or search != "grid":
+        if speeds is not None:
+            raise ValueError("speeds= is one factor for time and frequency: it excludes tempos=, pitches= and warps=")
+        return _scan_warps(recordings, db, Fs, window_seconds, step_seconds, topn, resample_to, min_aligned, max_gap,
+                           dict(tempos=tempos, pitches=pitches, warps=warps, search=search), tempo_tol, pitch_tol,
+                           WARP_SHIFT_TOL if shift_tol is None else shift_tol)
+    shift_tol = 2 if shift_tol is None else shift_tol
     if speeds is not None:
         return _scan_speeds(recordings, db, Fs, window_seconds, step_seconds, topn, resample_to, min_aligned, max_gap, speeds,
                             shift_tol, rung_tol)
@@ -160,5 +295,33 @@ def _scan_speeds(recordings, db, Fs, window_seconds, step_seconds, topn, resampl
             "last_window": last,
             "speed": float(sp[int(seg["rung"][i])]) / 65536.0,
             "speed_fit": (p1 - p0) / float((last - first) * sf) if last > first else None,
+        }))
+    return out
+
+
+def _scan_warps(recordings, db, Fs, window_seconds, step_seconds, topn, resample_to, min_aligned, max_gap, variants, tempo_tol,
+                pitch_tol, shift_tol):
+    from . import OFFSET_SECS
+    w = scan_windows(recordings, db, Fs, window_seconds, step_seconds, topn, resample_to, **variants)
+    t16, f16 = w["warps"]
+    tempo_tol = _rung(t16) if tempo_tol is None else int(tempo_tol)
+    pitch_tol = _rung(f16) if pitch_tol is None else int(pitch_tol)
+    seg = _ffi.scan_timeline_warps(w["win_off"], w["sid"], w["delta"], w["aligned"], w["nres"], w["best"], w["step_frames"], t16, f16,
+                                   min_aligned, max_gap, tempo_tol, pitch_tol, shift_tol)
+    hop, sf = w["hop"], w["step_frames"]
+    out = [[] for _ in range(len(w["frames"]))]
+    for i in range(len(seg["rec"])):
+        first, last = int(seg["first"][i]), int(seg["last"][i])
+        p0, p1 = int(seg["pos_first"][i]), int(seg["pos_last"][i])
+        out[int(seg["rec"][i])].append(dict(_segment(db, w, seg, i), **{
+            OFFSET_SECS: round(float(p0) / DEFAULT_FS * hop, 5),
+            "offset_end_seconds": round(float(p1) / DEFAULT_FS * hop, 5),
+            "pos_first": p0,
+            "pos_last": p1,
+            "first_window": first,
+            "last_window": last,
+            "tempo": float(t16[int(seg["warp"][i])]) / 65536.0,
+            "pitch": float(f16[int(seg["warp"][i])]) / 65536.0,
+            "tempo_fit": (p1 - p0) / float((last - first) * sf) if last > first else None,
         }))
     return out

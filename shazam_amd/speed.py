@@ -12,7 +12,7 @@ the pitch ladder at tempo 1 followed by the tempo ladder at every query's best p
 
 Limits: the hop is fixed, so a warped time is a rounded frame; a peak near the edge of its 21x21 neighbourhood may move when
 the audio is stretched; the smearing a real phase-vocoder time-stretch adds is not modelled by the corpus the tolerances were
-measured on; the scan takes speed ladders only, no warp pairs (the device-resident listeners take both: stream.py)."""
+measured on.  The scan (scan.py) and the device-resident listeners (stream.py) take speed ladders and warp pairs alike."""
 from __future__ import annotations
 
 from time import time
@@ -215,6 +215,29 @@ def _match_pairs(ctx, table, chans, first, t16, f16, row, Fs, resample_to, kw):
     return merge_warp_chunks(parts, t16, f16), ms
 
 
+def _warp_list(tempos, pitches, warps, search):
+    """What recognize_warps and the scan make of tempos= / pitches= / warps= / search=: (tempo ladder, pitch ladder, t16, f16,
+    row) -- the pair list tempo-major and the pairs of one row of it (an explicit pair list: no ladders, rows of 1)."""
+    tl = pl = None
+    if search not in ("grid", "separable"):
+        raise ValueError('search is "grid" or "separable"')
+    if warps is not None:
+        if tempos is not None or pitches is not None:
+            raise TypeError("warps= is an explicit pair list: it excludes tempos= and pitches=")
+        if search != "grid":
+            raise TypeError('search="separable" takes the two ladders, not a pair list')
+        t16, f16 = _check_speeds(warps[0], "warps[0]"), _check_speeds(warps[1], "warps[1]")
+        if len(t16) != len(f16):
+            raise ValueError("warps=(t16, f16): two lists of one length")
+        row = 1
+    else:
+        tl = np.asarray([S_ONE], np.uint32) if tempos is None else _check_speeds(tempos, "tempos")
+        pl = np.asarray([S_ONE], np.uint32) if pitches is None else _check_speeds(pitches, "pitches")
+        t16, f16 = warp_grid(tl, pl)
+        row = max(len(pl), 1)
+    return tl, pl, t16, f16, row
+
+
 def recognize_warps(queries, db, tempos=None, pitches=None, warps=None, search: str = "grid", Fs: int = 44100, topn: int = 2,
                     resample_to: int = None):
     """recognize_speeds for queries whose tempo and pitch changed by factors of their own.  Returns (results_per_query,
@@ -242,22 +265,7 @@ def recognize_warps(queries, db, tempos=None, pitches=None, warps=None, search: 
     from . import DEFAULT_AMP_MIN, DEFAULT_FAN_VALUE, _result_dicts
     if not hasattr(db.table, "h"):
         raise NotImplementedError("fused recognition takes the unsharded table (shards=1)")
-    if search not in ("grid", "separable"):
-        raise ValueError('search is "grid" or "separable"')
-    if warps is not None:
-        if tempos is not None or pitches is not None:
-            raise TypeError("warps= is an explicit pair list: it excludes tempos= and pitches=")
-        if search != "grid":
-            raise TypeError('search="separable" takes the two ladders, not a pair list')
-        t16, f16 = _check_speeds(warps[0], "warps[0]"), _check_speeds(warps[1], "warps[1]")
-        if len(t16) != len(f16):
-            raise ValueError("warps=(t16, f16): two lists of one length")
-        row = 1
-    else:
-        tl = np.asarray([S_ONE], np.uint32) if tempos is None else _check_speeds(tempos, "tempos")
-        pl = np.asarray([S_ONE], np.uint32) if pitches is None else _check_speeds(pitches, "pitches")
-        t16, f16 = warp_grid(tl, pl)
-        row = max(len(pl), 1)
+    tl, pl, t16, f16, row = _warp_list(tempos, pitches, warps, search)
     ctx = db.ctx
     if getattr(ctx, "hop", HOP) != HOP:
         ctx.set_overlap(NFFT - HOP)
