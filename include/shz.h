@@ -411,7 +411,24 @@ uint64_t shz_recognize_estimate(uint64_t frames, uint32_t fan_value);
 /* Test switch of shz_match_songs_warps: a slice holds one song x at most 2 warps, so that tests reach the slice and chunk
  * borders with tiny inputs (results do not depend on the slicing). */
 #define SHZ_DEBUG_CATALOG_SMALL_SLICES 64u
+/* Test switch of the vote: the tolerant route (shz_set_vote_tolerance) is taken at tolerance 0 too, where it computes what
+ * the other routes compute, so that its kernels can be compared with theirs on the same inputs. */
+#define SHZ_DEBUG_VOTE_TOLERANT_ROUTE 128u
 int32_t shz_set_debug(shz_ctx* ctx, uint32_t flags);
+/* The vote's tolerance, a setting of the context that holds for its later calls (default 0).  With c[sid][d] the votes of a
+ * query per song and offset difference d = db_off - q_off, and S(sid, d) = the sum of c[sid][d .. d + bins]: a song's
+ * `aligned` is the largest S over the windows that start at an occupied d (the first one in ascending d where several reach
+ * it), its `delta` the bin inside that window with the largest count of its own (the smaller delta where bins tie); songs
+ * rank by aligned descending, then song id ascending.  dedup, nres, nhash, npairs do not depend on it, and bins = 0 is the
+ * plain vote of one bin (align_matches), bit for bit.  A window holds votes of its own (query, song) only.  Every call that
+ * votes inside the library follows it: shz_match_batch, shz_match_device_host, shz_recognize_batch, shz_recognize_speeds /
+ * _warps, shz_scan_batch / _speeds / _warps, shz_listeners_push*, shz_match_songs / _warps and shz_pairs_vote;
+ * shz_match_pairs, whose votes leave as they are, does not.  With bins > 0 the votes go one way: 8-byte votes in one pass
+ * over a sub-batch, the full sort, then a fold over runs of equal (query, song, delta) -- neither the vote tiles, the 4-byte
+ * votes nor the fold queued ahead of the count (shz_match_spec_stats) are taken.  bins > 31: SHZ_E_INVALID, the setting
+ * stays as it was.  A NULL ctx (or NULL bins): SHZ_E_INVALID. */
+int32_t shz_set_vote_tolerance(shz_ctx* ctx, uint32_t bins);
+int32_t shz_get_vote_tolerance(shz_ctx* ctx, uint32_t* bins);
 int32_t shz_match_vt_redo(shz_ctx* ctx, uint64_t* count);
 /* A single query of at most 8,192 hashes handed over in host memory has its vote kernels queued before the number of its
  * votes is known (they do nothing when it exceeds 32,768; the call then continues as for any other query): how many

@@ -19,7 +19,7 @@ from time import time
 import numpy as np
 
 from . import _ffi
-from ._ffi import HOP, NFFT, Context, ShzError, Table  # noqa: F401
+from ._ffi import HOP, NFFT, Context, ShzError, Table, takes_delta_tol  # noqa: F401
 
 # reference constants (__init__.py:41-51, recognizer.py:21-38,40-58,68)
 RATE = 44100
@@ -301,12 +301,14 @@ def _recognize_fused(queries, chans, owner, db, Fs, topn, resample_to=None):
                      "n_matches": res["npairs"], "n_hashes": res["nhash"]}
 
 
+@takes_delta_tol(lambda *a, **k: (k["db"] if "db" in k else a[1]).ctx)
 def recognize_batch(queries, db, Fs: int = RATE, topn: int = TOPN, fused: bool = False, resample_to: int = None):
     """Recognise flow (recognizer.py:377-392) for many queries at once.  Each query is a list of
     channels (1-D int16 arrays) or a single 1-D array.  Returns (results_per_query, timings).
     fused: fingerprint and match in ONE library call with the hashes staying on the device (shz_recognize_batch);
     same results, fingerprint_time / query_time are then the device times of the two halves.
-    resample_to: the queries are at Fs, the table at resample_to (see fingerprint_batch); either path."""
+    resample_to: the queries are at Fs, the table at resample_to (see fingerprint_batch); either path.
+    delta_tol= (keyword): the vote tolerance in offset bins for this call (Context.tolerance); None: the context's."""
     ctx = db.ctx
     chans, owner = [], []
     for qi, q in enumerate(queries):
@@ -333,13 +335,15 @@ def recognize_batch(queries, db, Fs: int = RATE, topn: int = TOPN, fused: bool =
                      "n_matches": res["npairs"], "n_hashes": res["nhash"]}
 
 
-def recognize(channels_or_samples, db=None, Fs: int = RATE, topn: int = TOPN, fused: bool = False, resample_to: int = None):
-    """recognizer.py:377-396: (final_results, fingerprint_time, query_time, align_time).  fused, resample_to: see recognize_batch."""
+def recognize(channels_or_samples, db=None, Fs: int = RATE, topn: int = TOPN, fused: bool = False, resample_to: int = None,
+              delta_tol: int = None):
+    """recognizer.py:377-396: (final_results, fingerprint_time, query_time, align_time).  fused, resample_to, delta_tol: see
+    recognize_batch."""
     if db is None:
         raise ValueError("recognize() needs the HipFingerprintDB holding the fingerprints")
     x = channels_or_samples
     q = [np.asarray(x)] if (not isinstance(x, (list, tuple)) or (len(x) and np.isscalar(x[0]))) else list(x)
-    results, tm = recognize_batch([q], db, Fs, topn, fused, resample_to)
+    results, tm = recognize_batch([q], db, Fs, topn, fused, resample_to, delta_tol=delta_tol)
     return results[0], tm["fingerprint_time"], tm["query_time"], tm["align_time"]
 
 

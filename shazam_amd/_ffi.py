@@ -2,7 +2,9 @@
 if the HIP library is missing or a call fails this module raises."""
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
+import functools
 import os
 
 import numpy as np
@@ -18,6 +20,7 @@ DEBUG_VT_TINY_HEAVY, DEBUG_VT_PROBE1, DEBUG_RUN_LIMIT_SMALL, DEBUG_SCAN_SMALL_GR
 DEBUG_SPEED_SMALL_SLICES = 16   # shz_recognize_speeds: at most 2 queries a slice
 DEBUG_SCAN_SPEED_SMALL_SLICES = 32   # shz_scan_speeds: at most 1 recording x 2 rungs a slice, 3 windows a match group
 DEBUG_CATALOG_SMALL_SLICES = 64   # shz_match_songs_warps: one song x at most 2 warps a slice
+DEBUG_VOTE_TOLERANT_ROUTE = 128   # the vote: the tolerant route at tolerance 0 too
 SCAN_NO_WARP = 0xFFFFFFFF            # shz_scan_warps: out_best of a window that tried no variant
 SCAN_U32, SCAN_POPC64, SCAN_U64 = 0, 1, 2   # shz_scan_host kinds
 STAGE_F32, STAGE_F64, STAGE_PERSISTENT = 0, 1, 1   # shz_stft_stage_host kinds | flag
@@ -75,6 +78,8 @@ SIGNATURES = {
     "shz_fingerprint_batch": (C.c_int32, [vp, vp, u64p, C.c_uint32, C.c_uint32, C.c_double, C.c_uint32, C.c_uint32,
                                           vp, vp, u64p, C.c_uint64, u64p]),
     "shz_set_stage_f64": (C.c_int32, [vp, C.c_int32]),
+    "shz_set_vote_tolerance": (C.c_int32, [vp, C.c_uint32]),
+    "shz_get_vote_tolerance": (C.c_int32, [vp, u32p]),
     "shz_upload_stats": (C.c_int32, [vp, u64p, u64p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "shz_extract_stats": (C.c_int32, [vp, u64p, u64p, u64p, u64p, u64p, u64p]),
     "shz_sha1_prefix": (C.c_int32, [vp, vp, C.c_uint64, C.c_uint32, vp]),
@@ -219,6 +224,20 @@ def numpy_product_is_fused() -> bool:
     return _NP_FUSED
 
 
+def takes_delta_tol(ctx_of):
+    """Decorator: the function gains the keyword delta_tol=None -- the vote tolerance in offset bins that holds while it runs
+    (Context.tolerance; None: the context stays as it is).  ctx_of(*args, **kw) finds the Context among its arguments."""
+    def deco(fn):
+        @functools.wraps(fn)
+        def run(*args, delta_tol=None, **kw):
+            if delta_tol is None:
+                return fn(*args, **kw)
+            with ctx_of(*args, **kw).tolerance(delta_tol):
+                return fn(*args, **kw)
+        return run
+    return deco
+
+
 class ShzError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"libshz error {code}: {msg}")
@@ -330,8 +349,36 @@ class Context:
         """SHZ_DEBUG_* test switches (1: tiny hand-over list, 2: LDS probes give up after one round, 4: runs and segments cut
         from runs hold at most RUN_ROWS_MAX_SMALL rows, 8: shz_scan_batch matches its windows in groups of at most 3, 16: shz_recognize_speeds warps and
         matches its queries in slices of at most 2, 32: shz_scan_speeds works in slices of 1 recording x 2 rungs and matches
-        its windows in groups of at most 3, 64: shz_match_songs_warps works in slices of 1 song x 2 warps)."""
+        its windows in groups of at most 3, 64: shz_match_songs_warps works in slices of 1 song x 2 warps, 128: the vote takes
+        the tolerant route at tolerance 0 too)."""
         self.check(lib().shz_set_debug(self.h, int(flags)))
+
+    def set_vote_tolerance(self, bins: int):
+        """Every later vote of this context sums a song's aligned count over bins + 1 neighbouring offset bins
+        (shz_set_vote_tolerance; 0: one bin, the default; more than 31: ShzError, the setting stays)."""
+        if not 0 <= int(bins) < 1 << 32:
+            raise ShzError(E_INVALID, f"vote tolerance {bins}")
+        self.check(lib().shz_set_vote_tolerance(self.h, int(bins)))
+
+    @property
+    def vote_tolerance(self) -> int:
+        n = C.c_uint32()
+        self.check(lib().shz_get_vote_tolerance(self.h, C.byref(n)))
+        return n.value
+
+    @contextlib.contextmanager
+    def tolerance(self, bins):
+        """with ctx.tolerance(bins): the vote tolerance inside the block, the previous one after it (also after an
+        exception).  bins None: the context stays as it is."""
+        if bins is None:
+            yield self
+            return
+        before = self.vote_tolerance
+        self.set_vote_tolerance(bins)
+        try:
+            yield self
+        finally:
+            self.set_vote_tolerance(before)
 
     def vt_redo_count(self) -> int:
         n = C.c_uint64()
@@ -1297,18 +1344,20 @@ class Table:
         self.ctx.check(lib().shz_table_allgather(self.h, comm.h, C.byref(b)))
         return b.value
 
-    def match(self, key32, q_off, query_off, topn=2, full_sort=False):
+    def match(self, key32, q_off, query_off, topn=2, full_sort=False, delta_tol=None):
         """Batched return_matches + align_matches.  Returns dict of arrays (see shz.h).  full_sort: the vote as one
-        sort of 8-byte votes + record chain (SHZ_MATCH_FULL_SORT), the form the faster vote paths are tested against."""
+        sort of 8-byte votes + record chain (SHZ_MATCH_FULL_SORT), the form the faster vote paths are tested against.
+        delta_tol: the vote tolerance of this call (Context.tolerance); None: the context's."""
         k = np.ascontiguousarray(key32, np.uint32)
         o = np.ascontiguousarray(q_off, np.uint32)
         qo = np.ascontiguousarray(query_off, np.uint64)
         nq = len(qo) - 1
         res = _match_result(nq, topn)
-        self.ctx.check(lib().shz_match_batch(self.ctx.h, self.h, ptr(k), ptr(o), qo.ctypes.data_as(u64p), nq, topn,
-                                             MATCH_FULL_SORT if full_sort else 0,
-                                             ptr(res["sid"]), ptr(res["delta"]), ptr(res["aligned"]), ptr(res["dedup"]),
-                                             ptr(res["nres"]), ptr(res["nhash"]), ptr(res["npairs"])))
+        with self.ctx.tolerance(delta_tol):
+            self.ctx.check(lib().shz_match_batch(self.ctx.h, self.h, ptr(k), ptr(o), qo.ctypes.data_as(u64p), nq, topn,
+                                                 MATCH_FULL_SORT if full_sort else 0,
+                                                 ptr(res["sid"]), ptr(res["delta"]), ptr(res["aligned"]), ptr(res["dedup"]),
+                                                 ptr(res["nres"]), ptr(res["nhash"]), ptr(res["npairs"])))
         return res
 
     def match_device(self, key32, q_off, query_off, topn=2, full_sort=False, bias_bound=-1):

@@ -21,6 +21,8 @@ from __future__ import annotations
 
 import numpy as np
 
+from ._ffi import takes_delta_tol
+
 # Detection thresholds, set between the two distributions scripts/catalog_bench.py measured on the music-like synthetic
 # corpus (10 s songs of about 3,180 rows): among 51,000 songs no unrelated pair aligned more than 59 rows or
 # covered more than 0.027 of its smaller song; no planted copy or excerpt aligned fewer than 1,474 rows or covered less than
@@ -97,6 +99,7 @@ def _match_songs_warps(table, sids, t16, f16, row, topn, full_sort=False, timing
     return out
 
 
+@takes_delta_tol(lambda *a, **k: (lambda x: x.ctx)(k["db_or_table"] if "db_or_table" in k else a[0]))
 def match_songs(db_or_table, sids, topn: int = 5, full_sort: bool = False, speeds=None, tempos=None, pitches=None,
                 warps=None) -> dict:
     """Every listed song matched against the rest of the table in one library call (shz_match_songs): the arrays of
@@ -106,7 +109,8 @@ def match_songs(db_or_table, sids, topn: int = 5, full_sort: bool = False, speed
     With a ladder (speeds= / tempos= + pitches= / warps=, Q16 as in speed.py) every song's rows are warped at every pair
     first (shz_match_songs_warps): the arrays gain a warp axis behind the song axis ([n, n_warps, topn] / [n, n_warps]),
     "tempo_q16" / "pitch_q16" [n_warps] name the pairs, rows stay the unwarped counts, nhash is the distinct warped rows
-    and delta is the found song's frame under the listed song's WARPED frame 0."""
+    and delta is the found song's frame under the listed song's WARPED frame 0.
+    delta_tol= (keyword): the vote tolerance in offset bins while the call runs (Context.tolerance); None: the context's."""
     table, _ = _table_of(db_or_table)
     lad = _ladder_of(speeds, tempos, pitches, warps)
     if lad is None:
@@ -308,6 +312,7 @@ def _find_duplicates_warps(table, sids, lad, topn, min_aligned, min_coverage, ba
     return out
 
 
+@takes_delta_tol(lambda *a, **k: (lambda x: x.ctx)(k["db_or_table"] if "db_or_table" in k else a[0]))
 def find_duplicates(db_or_table, sids=None, topn: int = 5, min_aligned: int = None, min_coverage: float = None,
                     batch_rows: int = BATCH_ROWS, speeds=None, tempos=None, pitches=None, warps=None, timings: bool = False) -> dict:
     """Duplicate, contained and overlapping tracks among the listed songs (None: every song of the table) and the rest of
@@ -320,7 +325,8 @@ def find_duplicates(db_or_table, sids=None, topn: int = 5, min_aligned: int = No
     copies are found too: every batch -- at most batch_rows rows x warps -- is matched at every pair, fold_pairs_warps makes
     the records (WARP_PAIR_FIELDS: which song's rows were warped, by which factors, and the plain count), and the
     thresholds default to MIN_ALIGNED_WARPED / MIN_COVERAGE_WARPED.  Put 65536 on the ladder (speed_ladder does) to keep
-    the exact copies in the same answer.  timings (ladder only): "ms" = (gather, warp, match) device times, summed."""
+    the exact copies in the same answer.  timings (ladder only): "ms" = (gather, warp, match) device times, summed.
+    delta_tol= (keyword): the vote tolerance in offset bins while the call runs (Context.tolerance); None: the context's."""
     table, _ = _table_of(db_or_table)
     lad = _ladder_of(speeds, tempos, pitches, warps)
     min_aligned = (MIN_ALIGNED if min_aligned is None else min_aligned) if lad is None else min_aligned

@@ -139,6 +139,7 @@ struct shz_ctx {
   uint64_t st_spec_queued = 0, st_spec_used = 0;   // single small queries whose votes were queued ahead of the count / whose results that gave
   uint64_t st_vt_redo = 0;      // sub-batches whose vote tiles flagged an overflow and were voted again by the full sort
   uint32_t debug = 0;           // SHZ_DEBUG_* (shz_set_debug): switches that force rare paths, for tests
+  uint32_t vote_tol = 0;        // shz_set_vote_tolerance: neighbouring offset bins a song's aligned count sums over (0 .. 31)
   // extraction stats: cells fp32 peak picking left undecided, of those decided on fp64 values, frames recomputed for
   // that, passes repeated with fp64 staging
   uint64_t st_und = 0, st_und_f64 = 0, st_und_ffts = 0, st_fallbacks = 0;

@@ -1068,6 +1068,138 @@ __global__ __launch_bounds__(256) void m_topn_final_kernel(const uint64_t* __res
   if (threadIdx.x == 0) out_nres[q] = found;
 }
 
+// ---- tolerant fold of the sorted votes (shz_set_vote_tolerance): a song's count is the sum over tol + 1 neighbouring
+// offset bins.  The votes are sorted by (query, sid, delta, flag), so a RUN -- the votes of one (query, sid, delta) -- is a
+// range of indices and a window of bins a range of runs: its sum is an index difference.
+//   mt_flag_kernel    per vote: run heads (scanned into run indices; R runs)
+//   mt_runs_kernel    per vote: first vote of every run, which runs open a (query, sid) group (scanned into record slots;
+//                     G groups), flag votes of every run
+//   mt_groups_kernel  per run:  the records of the groups start empty; first record of every query
+//   mt_window_kernel  per run:  the window that starts at the run -- at most tol + 1 runs of its own group ahead, no bin
+//                     beyond delta + tol or the delta field -- into its group's record: atomicMax of (sum << 32 | ~run), so
+//                     the first window in run order wins among equal sums; the flag votes are added up beside it.  A wave
+//                     joins the runs of one group before it goes to memory: a group of any size, spread over any number
+//                     of workgroups, costs its waves one atomic each.
+//   mt_record_kernel  per group: the winning window once more for its strongest bin (the first of equal ones: the smaller
+//                     delta), the record in the form m_reduce_kernel writes: g_pack = sum << 32 | ~sid, g_delta, g_dedup.
+// With tol = 0 a window is one run: the record is m_reduce_kernel's.  rfirst has R + 1 entries (rfirst[R] = P); counts
+// that the host does not know (R, G) are read on the device, the launches are sized by their bound P.
+__global__ void mt_flag_kernel(const uint64_t* __restrict__ v, uint64_t P, uint32_t* __restrict__ fl, uint32_t* __restrict__ gfl,
+                               uint32_t* __restrict__ rdd) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= P) return;
+  fl[i] = (i == 0 || (v[i] >> 1) != (v[i - 1] >> 1)) ? 1u : 0u;
+  gfl[i] = 0u;   // (per run, and R <= P: the scan over P entries ends in G)
+  rdd[i] = 0u;
+}
+
+__global__ __launch_bounds__(256) void mt_runs_kernel(const uint64_t* __restrict__ v, uint64_t P, int gshift,
+                                                      const uint32_t* __restrict__ fl, const uint32_t* __restrict__ ps,
+                                                      const unsigned long long* __restrict__ R_dev, uint32_t* __restrict__ rfirst,
+                                                      uint32_t* __restrict__ gfl, uint32_t* __restrict__ rdd) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  const bool in = i < P;
+  const uint64_t x = in ? v[i] : 0ull;
+  const bool head = in && fl[i] != 0u;
+  const uint32_t r = in ? (head ? ps[i] : ps[i] - 1u) : 0u;   // (vote 0 is a head: ps[i] >= 1 for every other vote)
+  if (head) {
+    rfirst[r] = (uint32_t)i;
+    gfl[r] = (i == 0 || (x >> gshift) != (v[i - 1] >> gshift)) ? 1u : 0u;
+  }
+  if (i == 0) rfirst[*R_dev] = (uint32_t)P;
+  // flag votes per run: the wave's lanes of one run are adjacent; the first of them adds their number up
+  const unsigned long long bits = __ballot(in && (x & 1ull)), heads = __ballot(head);
+  const uint32_t lane = threadIdx.x & 63u;
+  if (in && (head || lane == 0)) {
+    const unsigned long long above = lane == 63u ? 0ull : heads >> (lane + 1u);
+    const uint32_t span = above ? (uint32_t)__ffsll((long long)above) : 64u - lane;   // lanes [lane, lane + span)
+    const unsigned long long mask = (span == 64u ? ~0ull : (1ull << span) - 1ull) << lane;
+    const uint32_t c = (uint32_t)__popcll(bits & mask);
+    if (c) atomicAdd(&rdd[r], c);
+  }
+}
+
+__global__ void mt_groups_kernel(const uint64_t* __restrict__ v, const unsigned long long* __restrict__ R_dev, uint64_t bound,
+                                 int qshift, const uint32_t* __restrict__ rfirst, const uint32_t* __restrict__ gfl,
+                                 const uint32_t* __restrict__ gps, uint64_t* __restrict__ g_pack, uint32_t* __restrict__ g_dedup,
+                                 uint32_t* __restrict__ qstart) {
+  const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= bound || r >= *R_dev || !gfl[r]) return;
+  const uint32_t slot = gps[r], i = rfirst[r];
+  g_pack[slot] = 0ull;
+  g_dedup[slot] = 0u;
+  if (i == 0 || (v[i] >> qshift) != (v[i - 1] >> qshift)) qstart[v[i] >> qshift] = slot;   // first group of a query
+}
+
+// the window that starts at run r: sum of its votes; count and (biased) delta of its strongest bin
+__device__ __forceinline__ void mt_window(const uint64_t* __restrict__ v, const uint32_t* __restrict__ rfirst, uint64_t R,
+                                          uint64_t r, const m_bits& mb, uint32_t tol, uint32_t& sum, uint32_t& bestd) {
+  const int gshift = mb.dbits + 1;
+  const uint64_t dmask = (1ull << mb.dbits) - 1;
+  const uint32_t i0 = rfirst[r];
+  const uint64_t x0 = v[i0], grp = x0 >> gshift, d0 = (x0 >> 1) & dmask;
+  const uint64_t dend = min(d0 + tol, dmask);          // the window ends inside the delta field ...
+  const uint64_t kmax = min(r + tol + 1ull, R);        // ... and after tol + 1 runs at the most
+  uint32_t nxt = rfirst[r + 1];
+  uint32_t best = nxt - i0;
+  bestd = (uint32_t)d0;
+  uint64_t k = r + 1;
+  for (; k < kmax; ++k) {
+    const uint64_t x = v[nxt];                         // first vote of run k
+    const uint64_t d = (x >> 1) & dmask;
+    if ((x >> gshift) != grp || d > dend) break;       // ... and inside its (query, song) group
+    const uint32_t after = rfirst[k + 1], len = after - nxt;
+    if (len > best) { best = len; bestd = (uint32_t)d; }
+    nxt = after;
+  }
+  sum = nxt - i0;
+}
+
+__global__ __launch_bounds__(256) void mt_window_kernel(const uint64_t* __restrict__ v,
+                                                        const unsigned long long* __restrict__ R_dev, m_bits mb, uint32_t tol,
+                                                        const uint32_t* __restrict__ rfirst, const uint32_t* __restrict__ gfl,
+                                                        const uint32_t* __restrict__ gps, const uint32_t* __restrict__ rdd,
+                                                        unsigned long long* __restrict__ g_pack, uint32_t* __restrict__ g_dedup) {
+  const uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x, R = *R_dev;
+  const bool in = r < R;
+  uint32_t slot = 0xFFFFFFFFu, dd = 0;   // (slots number below P < 2^32 - 1)
+  unsigned long long best = 0;
+  if (in) {
+    uint32_t sum, bd;
+    mt_window(v, rfirst, R, r, mb, tol, sum, bd);
+    slot = gps[r] + gfl[r] - 1u;
+    best = ((unsigned long long)sum << 32) | (0xFFFFFFFFu - (uint32_t)r);
+    dd = rdd[r];
+  }
+  // the lanes of one group are adjacent: each ends up with what the lanes of its group from itself upwards hold
+  const uint32_t lane = threadIdx.x & 63u;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const unsigned long long ob = (unsigned long long)__shfl_down((long long)best, d, 64);
+    const uint32_t od = (uint32_t)__shfl_down((int)dd, d, 64), os = (uint32_t)__shfl_down((int)slot, d, 64);
+    if (lane + d < 64u && os == slot) { best = max(best, ob); dd += od; }
+  }
+  const uint32_t below = (uint32_t)__shfl_up((int)slot, 1, 64);
+  if (in && (lane == 0 || below != slot)) {
+    atomicMax(&g_pack[slot], best);
+    if (dd) atomicAdd(&g_dedup[slot], dd);
+  }
+}
+
+__global__ void mt_record_kernel(const uint64_t* __restrict__ v, const unsigned long long* __restrict__ R_dev, uint64_t bound,
+                                 m_bits mb, uint32_t tol, const uint32_t* __restrict__ rfirst, const uint32_t* __restrict__ gfl,
+                                 const uint32_t* __restrict__ gps, uint64_t* __restrict__ g_pack, uint32_t* __restrict__ g_delta) {
+  const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, R = *R_dev;
+  if (r >= bound || r >= R || !gfl[r]) return;
+  const uint32_t slot = gps[r];
+  const uint64_t w = g_pack[slot];
+  uint32_t sum, bd;
+  mt_window(v, rfirst, R, 0xFFFFFFFFu - (uint32_t)w, mb, tol, sum, bd);   // (sum == w >> 32)
+  const uint64_t sid = (v[rfirst[r]] >> (mb.dbits + 1)) & ((1ull << mb.sb) - 1);
+  g_pack[slot] = ((uint64_t)sum << 32) | (0xFFFFFFFFu - (uint32_t)sid);   // rank: count desc, then sid asc
+  g_delta[slot] = bd;
+}
+
 
 // ---------------------------------------------------------------------------------------------------------------
 // Vote tiles: the fold of 4-byte votes without sorting them all the way.
@@ -1928,6 +2060,30 @@ static res_block res_rows(res_block r, uint32_t qa, uint32_t topn) {
   return r;
 }
 
+// the records of a vote pass -> top-n per query, into the device rows r
+static int32_t vote_rank(shz_ctx* ctx, uint64_t P, uint32_t nq, m_bits mb, uint32_t topn, const uint32_t* qstart,
+                         const unsigned long long* d_G, const uint64_t* gh, const uint32_t* gd, const uint32_t* gdd,
+                         const res_block& r) {
+  // groups per query decide the shape: one workgroup per query, or C slices per query and a final ranking.  The bound
+  // votes / queries stands in for groups / queries (more slices than needed cost a few idle workgroups).
+  const uint32_t C = (uint32_t)std::min<uint64_t>(512, (P / nq + 16383) / 16384);
+  if (C <= 1) {
+    hipLaunchKernelGGL(m_topn_kernel, dim3(nq), dim3(256), 0, ctx->stream, qstart, d_G, mb, gh, gd, gdd, nq, topn, r.sid, r.delta,
+                       r.aligned, r.dedup, r.nres);
+  } else {
+    void *pp, *pr;
+    const uint64_t ncand = (uint64_t)C * topn;
+    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_M8, (uint64_t)nq * ncand * 8, &pp));
+    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_M9, (uint64_t)nq * ncand * 4, &pr));
+    hipLaunchKernelGGL(m_topn_partial_kernel, dim3(C, nq), dim3(256), 0, ctx->stream, qstart, d_G, nq, gh, topn, (uint64_t*)pp,
+                       (uint32_t*)pr);
+    hipLaunchKernelGGL(m_topn_final_kernel, dim3(nq), dim3(256), 0, ctx->stream, (const uint64_t*)pp, (const uint32_t*)pr,
+                       (uint32_t)ncand, mb, gd, gdd, nq, topn, r.sid, r.delta, r.aligned, r.dedup, r.nres);
+  }
+  SHZ_HIP(ctx, hipGetLastError());
+  return SHZ_OK;
+}
+
 // sorted votes -> one record per (query, song) group -> top-n per query, into the device rows r (zeroed by the caller)
 static int32_t vote_fold(shz_ctx* ctx, const uint64_t* vs, uint64_t P, uint32_t nq, m_bits mb, uint32_t topn, uint64_t* d_tot,
                          const res_block& r) {
@@ -1952,29 +2108,51 @@ static int32_t vote_fold(shz_ctx* ctx, const uint64_t* vs, uint64_t P, uint32_t 
                      (uint32_t*)gd, (uint32_t*)gdd, qstart, long_cnt, long_list);
   hipLaunchKernelGGL(m_reduce_long_kernel, dim3(std::min<uint32_t>(1024, nb)), dim3(256), 0, ctx->stream, vs, P, mb,
                      (const uint32_t*)long_cnt, (const uint2*)long_list, (uint64_t*)gh, (uint32_t*)gd, (uint32_t*)gdd);
-  // groups per query decide the shape: one workgroup per query, or C slices per query and a final ranking.  The bound
-  // votes / queries stands in for groups / queries (more slices than needed cost a few idle workgroups).
-  const uint32_t C = (uint32_t)std::min<uint64_t>(512, (P / nq + 16383) / 16384);
-  if (C <= 1) {
-    hipLaunchKernelGGL(m_topn_kernel, dim3(nq), dim3(256), 0, ctx->stream, (const uint32_t*)qstart, d_G, mb, (const uint64_t*)gh,
-                       (const uint32_t*)gd, (const uint32_t*)gdd, nq, topn, r.sid, r.delta, r.aligned, r.dedup, r.nres);
-  } else {
-    void *pp, *pr;
-    const uint64_t ncand = (uint64_t)C * topn;
-    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_M8, (uint64_t)nq * ncand * 8, &pp));
-    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_M9, (uint64_t)nq * ncand * 4, &pr));
-    hipLaunchKernelGGL(m_topn_partial_kernel, dim3(C, nq), dim3(256), 0, ctx->stream, (const uint32_t*)qstart, d_G, nq,
-                       (const uint64_t*)gh, topn, (uint64_t*)pp, (uint32_t*)pr);
-    hipLaunchKernelGGL(m_topn_final_kernel, dim3(nq), dim3(256), 0, ctx->stream, (const uint64_t*)pp, (const uint32_t*)pr,
-                       (uint32_t)ncand, mb, (const uint32_t*)gd, (const uint32_t*)gdd, nq, topn, r.sid, r.delta, r.aligned, r.dedup,
-                       r.nres);
-  }
-  SHZ_HIP(ctx, hipGetLastError());
-  return SHZ_OK;
+  return vote_rank(ctx, P, nq, mb, topn, qstart, d_G, (const uint64_t*)gh, (const uint32_t*)gd, (const uint32_t*)gdd, r);
 }
 
-// the full sort: sort the packed 8-byte votes, then vote_fold.  v0 holds the P votes, v1 is scratch of the same size.
-static int32_t vote_tail(shz_ctx* ctx, uint64_t* v0, uint64_t* v1, uint64_t P, uint32_t nq, m_bits mb, uint32_t topn,
+// ... with a tolerance (shz_set_vote_tolerance): the mt_* kernels in place of m_reduce_kernel / m_reduce_long_kernel, the same
+// records, the same ranking.  d_tot[0] = G as in vote_fold; d_tot[1] = R, the number of runs (both stay on the device).
+static int32_t vote_fold_tol(shz_ctx* ctx, const uint64_t* vs, uint64_t P, uint32_t nq, m_bits mb, uint32_t topn, uint32_t tol,
+                             uint64_t* d_tot, const res_block& r) {
+  void *a, *b, *gh, *gd, *gdd;
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_M1, (P * 3 + 1 + nq + 2) * 4, &a));   // fl | ps | rfirst (R + 1 <= P + 1) | qstart
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_M3, P * 3 * 4, &b));                  // gfl | gps | rdd (per run)
+  uint32_t *fl = (uint32_t*)a, *ps = fl + P, *rfirst = ps + P, *qstart = rfirst + P + 1;
+  uint32_t *gfl = (uint32_t*)b, *gps = gfl + P, *rdd = gps + P;
+  const unsigned long long *d_G = (const unsigned long long*)d_tot, *d_R = d_G + 1;
+  const int gshift = mb.dbits + 1, qshift = mb.sb + mb.dbits + 1;
+  const uint32_t nb = nblk(P);
+  hipLaunchKernelGGL(mt_flag_kernel, dim3(nb), dim3(256), 0, ctx->stream, vs, P, fl, gfl, rdd);
+  SHZ_HIP(ctx, hipGetLastError());
+  SHZ_TRY(shz_scan_u32(ctx, fl, ps, P, d_tot + 1));
+  hipLaunchKernelGGL(mt_runs_kernel, dim3(nb), dim3(256), 0, ctx->stream, vs, P, gshift, (const uint32_t*)fl, (const uint32_t*)ps,
+                     d_R, rfirst, gfl, rdd);
+  SHZ_HIP(ctx, hipGetLastError());
+  SHZ_TRY(shz_scan_u32(ctx, gfl, gps, P, d_tot));
+  hipLaunchKernelGGL(m_tail_init_kernel, dim3(nblk((uint64_t)nq + 1)), dim3(256), 0, ctx->stream, qstart, nq);
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_M2, P * 8, &gh));   // G <= P records, as in vote_fold
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_M5, P * 4, &gd));
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_M6, P * 4, &gdd));
+  hipLaunchKernelGGL(mt_groups_kernel, dim3(nb), dim3(256), 0, ctx->stream, vs, d_R, P, qshift, (const uint32_t*)rfirst,
+                     (const uint32_t*)gfl, (const uint32_t*)gps, (uint64_t*)gh, (uint32_t*)gdd, qstart);
+  hipLaunchKernelGGL(mt_window_kernel, dim3(nb), dim3(256), 0, ctx->stream, vs, d_R, mb, tol, (const uint32_t*)rfirst,
+                     (const uint32_t*)gfl, (const uint32_t*)gps, (const uint32_t*)rdd, (unsigned long long*)gh, (uint32_t*)gdd);
+  hipLaunchKernelGGL(mt_record_kernel, dim3(nb), dim3(256), 0, ctx->stream, vs, d_R, P, mb, tol, (const uint32_t*)rfirst,
+                     (const uint32_t*)gfl, (const uint32_t*)gps, (uint64_t*)gh, (uint32_t*)gd);
+  SHZ_HIP(ctx, hipGetLastError());
+  return vote_rank(ctx, P, nq, mb, topn, qstart, d_G, (const uint64_t*)gh, (const uint32_t*)gd, (const uint32_t*)gdd, r);
+}
+
+// the tolerance of this context's votes, or -1 for the plain fold of one bin (SHZ_DEBUG_VOTE_TOLERANT_ROUTE: the tolerant
+// fold at 0 bins too)
+static int vote_tol_of(const shz_ctx* ctx) {
+  return (ctx->vote_tol > 0 || (ctx->debug & SHZ_DEBUG_VOTE_TOLERANT_ROUTE)) ? (int)ctx->vote_tol : -1;
+}
+
+// the full sort: sort the packed 8-byte votes, then vote_fold (tol < 0) or vote_fold_tol.  v0 holds the P votes, v1 is
+// scratch of the same size.
+static int32_t vote_tail(shz_ctx* ctx, uint64_t* v0, uint64_t* v1, uint64_t P, uint32_t nq, m_bits mb, uint32_t topn, int tol,
                          uint64_t* d_tot, const res_block& r) {
   int sel = 0;
   // bit 0 (the first-offset flag) is only counted by the fold, never compared: it stays out of the sort
@@ -1986,6 +2164,7 @@ static int32_t vote_tail(shz_ctx* ctx, uint64_t* v0, uint64_t* v1, uint64_t P, u
   } else {
     SHZ_TRY(shz_sort_u64(ctx, v0, v1, nullptr, nullptr, 0, P, 1, mb.qb + mb.sb + mb.dbits + 1, &sel));
   }
+  if (tol >= 0) return vote_fold_tol(ctx, sel ? v1 : v0, P, nq, mb, topn, (uint32_t)tol, d_tot, r);
   return vote_fold(ctx, sel ? v1 : v0, P, nq, mb, topn, d_tot, r);
 }
 
@@ -2148,6 +2327,7 @@ enum vote_route {
   ROUTE_TILES,         // 4-byte votes through the vote tiles, expand and sort apart
   ROUTE_WIDEN,         // 4-byte votes (query bits inside), sorted and widened into the full sort's fold
   ROUTE_SORT64,        // 8-byte votes through the full sort, one pass over all queries
+  ROUTE_TOLERANT,      // shz_set_vote_tolerance: the same votes and sort, then the fold over neighbouring offset bins
 };
 struct vote_pass { uint32_t qa, qb; uint64_t v_lo, v_hi; };   // queries [qa, qb), their votes [v_lo, v_hi) of the sub-batch
 struct vote_plan {
@@ -2164,6 +2344,7 @@ struct vote_case {
   bool full_sort;          // SHZ_MATCH_FULL_SORT, or the tiles gave up on these queries: once more, through the full sort
   bool sink;               // the votes leave as they are (shz_match_pairs)
   bool queued_held;        // the fold queued ahead of the count ran on the right layout
+  int tol;                 // >= 0: the vote's tolerance in bins (vote_tol_of), every fold but the tolerant one is out
   vote_switches sw;
 };
 
@@ -2200,6 +2381,11 @@ static void vote_plan_make(const vote_case& c, vote_plan* plan) {
   if (c.queued_held) { plan->route = ROUTE_QUEUED; return; }
   if (c.P == 0) { plan->route = ROUTE_NONE; return; }
   if (c.sink) { plan->route = ROUTE_SINK; return; }
+  if (c.tol >= 0) {   // a sum over neighbouring bins needs the votes in order: one 8-byte pass, whatever their number
+    plan->passes.push_back(vote_pass{0, c.nq, 0, c.P});
+    plan->route = ROUTE_TOLERANT;
+    return;
+  }
   // expand -> sort -> groups -> top-n, in vote passes over ranges of queries.  4-BYTE votes when a pass's query
   // index, the song id and the biased delta fit 31 bits (1M songs x 10 s queries: 1 + 20 + 10): half the bytes
   // through expand and the sort passes, whose last pass widens to the 64-bit layout the fold reads.  Worth it only
@@ -2278,6 +2464,7 @@ struct match_sub {
   void* rb;                  // the result block ...
   uint64_t nres, rb_bytes;
   res_block r;               // ... and its views
+  int tol;                   // the ctx's vote tolerance for this visit (vote_tol_of)
   bool queued;               // one-workgroup fold queued ahead of the count ...
   uint32_t queued_bias;      // ... on this bias
   // counts (sub_read_counts)
@@ -2471,7 +2658,7 @@ static int32_t sub_queue_fold(const match_call& mc, match_sub& s) {
   // (vote32 == 1 would send P > MH_MAX votes through a 4-byte pass instead; the layout test with the bias still 0 is the
   // least it can need: it saves the walk over the offsets)
   const bool dev_in = (mc.flags & SHZ_IN_DEVICE) != 0;
-  if (mc.sink || (dev_in && !mc.has_bias_bound) || s.m > MH_MAX || sw.vote32 == 1 ||
+  if (mc.sink || s.tol >= 0 || (dev_in && !mc.has_bias_bound) || s.m > MH_MAX || sw.vote32 == 1 ||
       !one_wg_fits(s.nq, s.mb, mc.topn, s.full_sort, sw) ||
       (double)s.m * mc.t->votes_per_hash > 2.0 * VT_ONE_WG_MAX)   // (a table whose last query had far more votes: not worth queueing)
     return SHZ_OK;
@@ -2631,8 +2818,10 @@ static int32_t vote_run_pass(const match_call& mc, const match_sub& s, const vot
       SHZ_TRY(shz_sort_u32_widen(ctx, k32, k32 + b.pmax4, (uint64_t*)b.v1, pp, 1, mbp.qb + mbp.sb + mbp.dbits + 1, 0, nullptr));
       return vote_fold(ctx, (const uint64_t*)b.v1, pp, nqp, mbp, topn, d_G, r);
     case ROUTE_SORT64:
+    case ROUTE_TOLERANT:
       SHZ_TRY(expand_votes<uint64_t>(mc, s, tile_x, vp.v_lo, vp.v_hi, mbp, (int64_t)0, (uint64_t*)b.v0));
-      return vote_tail(ctx, (uint64_t*)b.v0, (uint64_t*)b.v1, pp, nqp, mbp, topn, d_G, r);
+      return vote_tail(ctx, (uint64_t*)b.v0, (uint64_t*)b.v1, pp, nqp, mbp, topn, plan.route == ROUTE_TOLERANT ? s.tol : -1, d_G,
+                       r);
     default:
       return SHZ_OK;   // (the routes without passes)
   }
@@ -2750,7 +2939,7 @@ static int32_t match_sub_run(match_call& mc, match_sub& s, sub_next* next) {
   // bound and no offset above it (else its kernels did nothing, or their results are overwritten, and the passes run as ever)
   const bool bias_held = (mc.flags & SHZ_IN_DEVICE) ? s.mb.bias <= s.queued_bias : s.mb.bias == s.queued_bias;
   vote_case c{s.nq, s.P, s.votes.data(), s.mb, mc.topn, s.full_sort, mc.sink != nullptr,
-              s.queued && s.P <= VT_ONE_WG_MAX && bias_held, vote_env()};
+              s.queued && s.P <= VT_ONE_WG_MAX && bias_held, s.tol, vote_env()};
   vote_plan plan;
   vote_plan_make(c, &plan);
   SHZ_TRY(sub_vote(mc, s, plan));
@@ -2794,6 +2983,7 @@ static int32_t match_core(match_call& mc) {
     if (s.m >= (1ull << 31)) SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "query %u has too many hashes", q0);
     s.redo = redo;
     s.full_sort = redo || (mc.flags & SHZ_MATCH_FULL_SORT);
+    s.tol = mc.sink ? -1 : vote_tol_of(ctx);
     s.mb = m_bits{bits_for(t->max_sid), 0, bits_for(s.nq - 1), 0};
     sub_next next;
     SHZ_TRY(match_sub_run(mc, s, &next));
@@ -2906,6 +3096,17 @@ extern "C" int32_t shz_match_pairs(shz_ctx* ctx, shz_table* t, const uint32_t* k
 extern "C" int32_t shz_set_debug(shz_ctx* ctx, uint32_t flags) {
   if (!ctx) return SHZ_E_INVALID;
   ctx->debug = flags;
+  return SHZ_OK;
+}
+extern "C" int32_t shz_set_vote_tolerance(shz_ctx* ctx, uint32_t bins) {
+  if (!ctx) return SHZ_E_INVALID;
+  if (bins > 31) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_set_vote_tolerance: %u bins (at most 31)", bins);
+  ctx->vote_tol = bins;
+  return SHZ_OK;
+}
+extern "C" int32_t shz_get_vote_tolerance(shz_ctx* ctx, uint32_t* bins) {
+  if (!ctx || !bins) return SHZ_E_INVALID;
+  *bins = ctx->vote_tol;
   return SHZ_OK;
 }
 extern "C" int32_t shz_match_vt_redo(shz_ctx* ctx, uint64_t* count) {
@@ -3077,11 +3278,12 @@ extern "C" int32_t shz_pairs_vote(shz_ctx* ctx, uint64_t* d_pairs, uint64_t n, u
   const res_block r{nullptr, (uint32_t*)r_sid, (int32_t*)r_delta, (uint32_t*)r_al, (uint32_t*)r_dd, (uint32_t*)r_n, nullptr,
                     nullptr};
   SHZ_TRY(pv_zero_results(ctx, r, n_queries, nres));
-  pv_tiles tiles;
-  SHZ_TRY(pairs_vote_tiles(ctx, d_pairs, (uint64_t*)v1, n, n_queries, mb, topn, r, &tiles));
+  const int tol = vote_tol_of(ctx);   // a tolerance: the full sort and the tolerant fold, as in the unsharded match
+  pv_tiles tiles = PV_NOT_TAKEN;
+  if (tol < 0) SHZ_TRY(pairs_vote_tiles(ctx, d_pairs, (uint64_t*)v1, n, n_queries, mb, topn, r, &tiles));
   if (tiles == PV_REDO) SHZ_TRY(pv_zero_results(ctx, r, n_queries, nres));
   // (the full sort orders any permutation of the votes: whatever the sort by query left in d_pairs / v1 is fine for it)
-  if (tiles != PV_DONE) SHZ_TRY(vote_tail(ctx, d_pairs, (uint64_t*)v1, n, n_queries, mb, topn, (uint64_t*)tot, r));
+  if (tiles != PV_DONE) SHZ_TRY(vote_tail(ctx, d_pairs, (uint64_t*)v1, n, n_queries, mb, topn, tol, (uint64_t*)tot, r));
   SHZ_HIP(ctx, shz_memcpy(ctx, out_sid, r_sid, nres * 4, hipMemcpyDeviceToHost));
   SHZ_HIP(ctx, shz_memcpy(ctx, out_delta, r_delta, nres * 4, hipMemcpyDeviceToHost));
   SHZ_HIP(ctx, shz_memcpy(ctx, out_aligned, r_al, nres * 4, hipMemcpyDeviceToHost));

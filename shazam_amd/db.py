@@ -174,9 +174,12 @@ class HipFingerprintDB:
         hexes = hex_of_keys(self.ctx, k)
         return [(h.upper(), int(a), int(b)) for h, a, b in zip(hexes, s.tolist(), o.tolist())]  # HEX() upper-cases
 
-    def match(self, key32, q_off, query_off, topn=2):
+    def match(self, key32, q_off, query_off, topn=2, delta_tol=None):
+        """Table.match / ShardedTable.match of the finalized table.  delta_tol: the vote tolerance of this call, None: the
+        context's."""
         self.finalize()
-        return self.table.match(key32, q_off, query_off, topn)
+        with self.ctx.tolerance(delta_tol):
+            return self.table.match(key32, q_off, query_off, topn)
 
     def find_duplicates(self, **kw):
         """Duplicate, contained and overlapping tracks of this catalogue (shazam_amd/catalog.find_duplicates); one table

@@ -18,7 +18,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import _ffi
-from ._ffi import HOP
+from ._ffi import HOP, takes_delta_tol
 
 TOPN = 2                 # recognizer.py:68, as the package has it
 DEFAULT_FS = 44100       # recognizer.py:21-38
@@ -134,6 +134,7 @@ def _scan_warp_windows(run, tl, pl, t16, f16, row, search):
     return res, win_off, ms
 
 
+@takes_delta_tol(lambda *a, **k: (k["db"] if "db" in k else a[1]).ctx)
 def scan_windows(recordings, db, Fs: int = 44100, window_seconds: float = 5, step_seconds: float = 1, topn: int = TOPN,
                  resample_to: int = None, full_sort: bool = False, speeds=None, tempos=None, pitches=None, warps=None,
                  search: str = "grid"):
@@ -158,7 +159,8 @@ def scan_windows(recordings, db, Fs: int = 44100, window_seconds: float = 5, ste
     every window that stage 1 gave a rank-0 count of at least 1 tries (a, its own best pitch) for every tempo a != 65536 and
     the other windows try nothing; the answer is the best over everything a window tried, the variants are stage 1's
     followed by the stage-2 grid (the tempos x the pitch rungs stage 1 chose), and stage1 / stage2 carry the stages' own
-    best / profile / work."""
+    best / profile / work.
+    delta_tol= (keyword): the vote tolerance in offset bins while the call runs (Context.tolerance); None: the context's."""
     from . import DEFAULT_AMP_MIN, DEFAULT_FAN_VALUE, resample_to_device
     if not hasattr(db.table, "h"):
         raise NotImplementedError("scanning takes the unsharded table (shards=1)")
@@ -228,6 +230,7 @@ def _segment(db, w, seg, i):
     }
 
 
+@takes_delta_tol(lambda *a, **k: (k["db"] if "db" in k else a[1]).ctx)
 def scan(recordings, db, Fs: int = 44100, window_seconds: float = 5, step_seconds: float = 1, topn: int = TOPN,
          resample_to: int = None, min_aligned: int = 20, max_gap: int = 1, speeds=None, shift_tol: int = None, rung_tol: int = 1,
          tempos=None, pitches=None, warps=None, search: str = "grid", tempo_tol: int = None, pitch_tol: int = None):
@@ -251,7 +254,8 @@ def scan(recordings, db, Fs: int = 44100, window_seconds: float = 5, step_second
     between neighbouring distinct values of the respective list of the variants) and whose song positions advance by the step
     warped with the TEMPO factor within shift_tol frames (shz_scan_timeline_warps; None: WARP_SHIFT_TOL).  It carries what a
     speed scan's segment carries, with "tempo" and "pitch" (the pair its hits chose most often, as floats) and "tempo_fit" in
-    place of "speed" and "speed_fit"."""
+    place of "speed" and "speed_fit".
+    delta_tol= (keyword): the vote tolerance in offset bins while the call runs (Context.tolerance); None: the context's."""
     from . import OFFSET_SECS
     if tempos is not None or pitches is not None or warps is not None or search != "grid":
         if speeds is not None:

@@ -204,9 +204,13 @@ class ShardedTable:
             self._pbuf.free()
         self._pbuf, self._pcap = self.ctx.alloc(cap * 8), cap
 
-    def match(self, key32, q_off, query_off, topn=2):
+    def match(self, key32, q_off, query_off, topn=2, delta_tol=None):
         """Same result dict as ``Table.match`` on the union of all shards.  Like ``Table.match``, queries whose votes do
-        not fit one 64-bit key together are matched in halves; a query with hashes that does not fit alone raises."""
+        not fit one 64-bit key together are matched in halves; a query with hashes that does not fit alone raises.
+        delta_tol: the vote tolerance of this call (the gathered votes are folded by it), None: the context's."""
+        if delta_tol is not None:
+            with self.ctx.tolerance(delta_tol):
+                return self.match(key32, q_off, query_off, topn)
         k = np.ascontiguousarray(key32, np.uint32)
         o = np.ascontiguousarray(q_off, np.uint32)
         qo = np.ascontiguousarray(query_off, np.uint64)

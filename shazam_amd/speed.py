@@ -19,7 +19,7 @@ from time import time
 
 import numpy as np
 
-from ._ffi import HOP, NFFT
+from ._ffi import HOP, NFFT, takes_delta_tol
 
 S_ONE = 65536              # the factor 1.0 in Q16
 S_MIN, S_MAX = 32768, 131072
@@ -115,12 +115,14 @@ def warp_hashes_tf(peaks_f, peaks_t, peak_off, tempos, pitches, fan_value: int =
                                                     _check_speeds(pitches, "pitches"), query_clip0, int(fan_value))
 
 
+@takes_delta_tol(lambda *a, **k: (k["db"] if "db" in k else a[1]).ctx)
 def recognize_speeds(queries, db, speeds=None, Fs: int = 44100, topn: int = 2, resample_to: int = None):
     """recognize_batch for queries of unknown speed.  Returns (results_per_query, timings) like recognize_batch; every
     result dict carries "speed" (the chosen factor as a float), OFFSET / OFFSET_SECS are in the TABLE's time, and timings
     carries "speeds" (the ladder, Q16), "speed_best" (index per query) and "speed_profile" ([n_queries, K]: the aligned count
     of the top answer of every factor).  speeds=None: speed_ladder().  The chosen factor is the one with the greatest
-    aligned count; ties go to the factor nearest 1.0, then to the lower index."""
+    aligned count; ties go to the factor nearest 1.0, then to the lower index.
+    delta_tol= (keyword): the vote tolerance in offset bins while the call runs (Context.tolerance); None: the context's."""
     from . import DEFAULT_AMP_MIN, DEFAULT_FAN_VALUE, _as_pcm, _result_dicts, resample_to_device
     if not hasattr(db.table, "h"):
         raise NotImplementedError("fused recognition takes the unsharded table (shards=1)")
@@ -238,6 +240,7 @@ def _warp_list(tempos, pitches, warps, search):
     return tl, pl, t16, f16, row
 
 
+@takes_delta_tol(lambda *a, **k: (k["db"] if "db" in k else a[1]).ctx)
 def recognize_warps(queries, db, tempos=None, pitches=None, warps=None, search: str = "grid", Fs: int = 44100, topn: int = 2,
                     resample_to: int = None):
     """recognize_speeds for queries whose tempo and pitch changed by factors of their own.  Returns (results_per_query,
@@ -261,7 +264,8 @@ def recognize_warps(queries, db, tempos=None, pitches=None, warps=None, search: 
     "warp_profile" (the aligned count of the top answer of every pair): [n_pairs] / [n_queries, n_pairs] for the grid and
     for a pair list; for the separable search the pairs differ per query, and the three are those of the second stage --
     "warps" two [n_queries, len(tempos)] arrays, "warp_profile" of that shape -- with the first stage under "stage1"
-    ("warps", "warp_best", "warp_profile")."""
+    ("warps", "warp_best", "warp_profile").
+    delta_tol= (keyword): the vote tolerance in offset bins while the call runs (Context.tolerance); None: the context's."""
     from . import DEFAULT_AMP_MIN, DEFAULT_FAN_VALUE, _result_dicts
     if not hasattr(db.table, "h"):
         raise NotImplementedError("fused recognition takes the unsharded table (shards=1)")

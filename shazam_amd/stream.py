@@ -136,16 +136,21 @@ class StreamRecognizer:
     listener's window at every variant, and each result dict carries "speed", or "tempo" and "pitch", of the listener's
     best variant; `offset` is in the TABLE's frames.  last_best / last_profile hold the arrays of the last push;
     push(..., speeds=) / push(..., warps=) overrides the ladder for that push.  At a ladder of [65536] the results are those
-    of the window's peaks paired among themselves, not bit for bit the plain listener's."""
+    of the window's peaks paired among themselves, not bit for bit the plain listener's.
+
+    delta_tol: the vote tolerance in offset bins of this recogniser's matches, held for its lifetime and set around every push
+    (Context.tolerance); None: whatever the context holds at the push."""
 
     def __init__(self, db, n_listeners: int, channels: int = 1, window_seconds: float = 5, topn: int = TOPN,
-                 fan_value: int = 5, amp_min=10, device: bool = False, fs_in: int = None, speeds=None, warps=None):
+                 fan_value: int = 5, amp_min=10, device: bool = False, fs_in: int = None, speeds=None, warps=None,
+                 delta_tol: int = None):
         if speeds is not None and warps is not None:
             raise ValueError("speeds= and warps= exclude each other: a speed is the warp (s, s)")
         if (speeds is not None or warps is not None) and not device:
             raise ValueError("speeds= / warps= need device=True: the host recogniser keeps hashes, and a warp acts on peaks")
         self.ladder = None if speeds is None and warps is None else _ladder_of(speeds, warps)
         self.last_best = self.last_profile = None
+        self.delta_tol = None if delta_tol is None else int(delta_tol)
         self.db, self.n, self.channels, self.topn = db, int(n_listeners), int(channels), int(topn)
         self.fp = StreamFingerprinter(self.n * self.channels, RATE, fan_value, amp_min, db.ctx, fs_in)
         self.window_frames = int(float(window_seconds) * RATE / self.fp.streams.hop)
@@ -176,6 +181,10 @@ class StreamRecognizer:
         """chunks_per_listener[l]: list of `channels` 1-D int16 arrays (a bare array when channels == 1; None: nothing).
         end: listeners whose channels all end after this chunk.  Returns [(results, w0)] per listener.  speeds / warps:
         this push's ladder, for a recogniser created with one."""
+        with self.db.ctx.tolerance(self.delta_tol):
+            return self._push(chunks_per_listener, end, speeds, warps)
+
+    def _push(self, chunks_per_listener, end, speeds, warps):
         assert len(chunks_per_listener) == self.n
         if speeds is not None and warps is not None:
             raise ValueError("speeds= and warps= exclude each other: a speed is the warp (s, s)")
