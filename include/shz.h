@@ -414,6 +414,10 @@ uint64_t shz_recognize_estimate(uint64_t frames, uint32_t fan_value);
 /* Test switch of the vote: the tolerant route (shz_set_vote_tolerance) is taken at tolerance 0 too, where it computes what
  * the other routes compute, so that its kernels can be compared with theirs on the same inputs. */
 #define SHZ_DEBUG_VOTE_TOLERANT_ROUTE 128u
+/* Test switch of shz_match_extents / shz_match_songs_extents: a tile of the extent kernel holds 64 pairs instead of 2,048,
+ * its LDS table 4 (element, segment) descriptors instead of 512, and a sub-batch 3 queries instead of 4,096, so that tests
+ * reach every border with tiny inputs (results do not depend on any of them). */
+#define SHZ_DEBUG_EXTENT_SMALL_TILES 256u
 int32_t shz_set_debug(shz_ctx* ctx, uint32_t flags);
 /* The vote's tolerance, a setting of the context that holds for its later calls (default 0).  With c[sid][d] the votes of a
  * query per song and offset difference d = db_off - q_off, and S(sid, d) = the sum of c[sid][d .. d + bins]: a song's
@@ -470,6 +474,41 @@ int32_t shz_match_device_host(shz_ctx* ctx, shz_table* t, const uint32_t* key32,
 int32_t shz_match_songs(shz_ctx* ctx, shz_table* t, const uint32_t* sids, uint32_t n_sids, uint32_t topn, uint32_t flags,
                         uint64_t* out_rows, uint32_t* out_sid, int32_t* out_delta, uint32_t* out_aligned, uint32_t* out_dedup,
                         uint32_t* out_nres, uint32_t* out_nhash, uint64_t* out_npairs);
+/* ---- match extents (new): WHERE in the query and in the song the aligned hashes lie.  A match answers (song, delta,
+ * aligned); delta says how the two timelines are shifted, not over which stretch the match holds.  This is a second pass
+ * over the same (query hash, table row) pairs for candidates the caller names -- usually the winners of a match.
+ * Definitions (tests/extent_twin.py is the same in Python): the table's rows (key, sid, off) and a query's hashes (key, q_off)
+ * are sets (duplicate hashes of a query collapse, as in the match); a PAIR is a (hash, row) of equal key with d = off - q_off
+ * (signed); it BELONGS to candidate (sid, d_lo, d_hi) when row.sid == sid and d_lo <= d <= d_hi, and to every candidate whose
+ * test it passes -- two candidates of a query may name one song with disjoint or overlapping ranges.  shift of a query = the
+ * smallest s >= 0 with (its largest q_off >> s) < 64, 0 for an empty query.  Per candidate: out_count = pairs that belong;
+ * out_q_first / out_q_last = the smallest / largest q_off among them; out_t_first / out_t_last = the smallest / largest off;
+ * out_hist[64] (may be NULL: not computed) = pairs that belong per bucket q_off >> shift.  All of them are 0 where count is 0.
+ * sum(hist) == count, and with d_lo == d_hi == the delta of a result of shz_match_batch at tolerance 0, count == its aligned.
+ * All arrays are HOST arrays: key32 / q_off / query_off as for shz_match_batch; the candidates [n_queries * ncand], slot c of
+ * query q at q * ncand + c, of which query q uses the first cand_n[q]; the outputs [n_queries * ncand] ([... * 64] for
+ * out_hist, [n_queries] for out_shift), zero at and past cand_n[q].  The outputs are written only by a call that returns
+ * SHZ_OK.  The vote tolerance of the context does not enter: the ranges are explicit.  Integer adds, minima and maxima only:
+ * exact and repeatable.
+ * Refused, before anything is launched: a NULL ctx, table or required array, ncand outside [1, 64], a cand_n[q] > ncand, a
+ * used candidate with d_lo > d_hi, a query_off that decreases (SHZ_E_INVALID); a table with staged or unsealed rows, or not
+ * finalized (SHZ_E_STATE, as the match); a query offset >= 2^20 or a table offset >= 2^31 (SHZ_E_UNSUPPORTED, as the match).
+ * n_queries == 0: SHZ_OK, nothing is written. */
+int32_t shz_match_extents(shz_ctx* ctx, shz_table* t, const uint32_t* key32, const uint32_t* q_off, const uint64_t* query_off,
+                          uint32_t n_queries, uint32_t ncand, const uint32_t* cand_sid, const int32_t* cand_dlo,
+                          const int32_t* cand_dhi, const uint32_t* cand_n, uint32_t* out_count, uint32_t* out_q_first,
+                          uint32_t* out_q_last, uint32_t* out_t_first, uint32_t* out_t_last, uint32_t* out_hist,
+                          uint32_t* out_shift);
+/* The catalogue form: the listed songs' rows are gathered on the device as shz_match_songs gathers them and are the queries
+ * (song sids[q] is query q, its offsets are the query offsets; no row crosses the bus).  Candidates and outputs as above with
+ * n_sids in place of n_queries.  A candidate may be the listed song itself: at d_lo = d_hi = 0 its count is the song's row
+ * count.  Refused as above, and: a song id listed twice (SHZ_E_INVALID, before anything is launched); 2^32 gathered rows or
+ * more in one call, a listed song holding an offset >= 2^20 -- it is a query offset here -- (SHZ_E_UNSUPPORTED; the latter is
+ * seen on the device, after the gather).  n_sids == 0: SHZ_OK. */
+int32_t shz_match_songs_extents(shz_ctx* ctx, shz_table* t, const uint32_t* sids, uint32_t n_sids, uint32_t ncand,
+                                const uint32_t* cand_sid, const int32_t* cand_dlo, const int32_t* cand_dhi, const uint32_t* cand_n,
+                                uint32_t* out_count, uint32_t* out_q_first, uint32_t* out_q_last, uint32_t* out_t_first,
+                                uint32_t* out_t_last, uint32_t* out_hist, uint32_t* out_shift);
 /* ---- sped-up and pitch-shifted copies inside the table (new): shz_match_songs finds a re-upload only while its audio is
  * bit-identical; a copy pitched up 3 %, a 25/24 video transfer or a rip from a drifting deck shares no hash with its
  * original.  The table holds no peaks, so the peak-level warp of shz_warp_pair_hash_tf cannot be applied to a stored song --

@@ -268,6 +268,26 @@ def _result_dicts(db, res, q, queried_hashes):
     return out
 
 
+def _frames_secs(frames: int) -> float:
+    return round(float(frames) / DEFAULT_FS * DEFAULT_WINDOW_SIZE * DEFAULT_OVERLAP_RATIO, 5)
+
+
+def _add_extents(db, results, key32, q_off, query_off, res):
+    """the extent keys of recognize_batch(extents=True), from one match_extents call on the results' (song, delta)"""
+    from .extent import extents_of
+    db.finalize()
+    if not hasattr(db.table, "h"):
+        raise NotImplementedError("extents take the unsharded table (shards=1)")
+    ext = extents_of(db.table, key32, q_off, query_off, res, tol=db.ctx.vote_tolerance)
+    for q, dicts in enumerate(results):
+        for n, d in enumerate(dicts):
+            qf, ql, tf, tl = (int(ext[f][q, n]) for f in ("q_first", "q_last", "t_first", "t_last"))
+            d.update({"query_first": qf, "query_last": ql, "song_first": tf, "song_last": tl,
+                      "query_start_secs": _frames_secs(qf), "query_end_secs": _frames_secs(ql + 1),
+                      "song_start_secs": _frames_secs(tf), "song_end_secs": _frames_secs(tl + 1),
+                      "extent_hist": ext["hist"][q, n].copy(), "extent_shift": int(ext["shift"][q])})
+
+
 def _recognize_fused(queries, chans, owner, db, Fs, topn, resample_to=None):
     """recognize_batch through shz_recognize_batch: one call, the hashes never leave the device."""
     if not hasattr(db.table, "h"):
@@ -302,13 +322,22 @@ def _recognize_fused(queries, chans, owner, db, Fs, topn, resample_to=None):
 
 
 @takes_delta_tol(lambda *a, **k: (k["db"] if "db" in k else a[1]).ctx)
-def recognize_batch(queries, db, Fs: int = RATE, topn: int = TOPN, fused: bool = False, resample_to: int = None):
+def recognize_batch(queries, db, Fs: int = RATE, topn: int = TOPN, fused: bool = False, resample_to: int = None,
+                    extents: bool = False):
     """Recognise flow (recognizer.py:377-392) for many queries at once.  Each query is a list of
     channels (1-D int16 arrays) or a single 1-D array.  Returns (results_per_query, timings).
     fused: fingerprint and match in ONE library call with the hashes staying on the device (shz_recognize_batch);
     same results, fingerprint_time / query_time are then the device times of the two halves.
     resample_to: the queries are at Fs, the table at resample_to (see fingerprint_batch); either path.
-    delta_tol= (keyword): the vote tolerance in offset bins for this call (Context.tolerance); None: the context's."""
+    delta_tol= (keyword): the vote tolerance in offset bins for this call (Context.tolerance); None: the context's.
+    extents: every result dict also says WHERE the match holds (extent.extents_of at the call's tolerance): "query_first" /
+    "query_last" / "song_first" / "song_last" (frames of the first and last aligned hash in the query and in the song),
+    "query_start_secs" / "query_end_secs" / "song_start_secs" / "song_end_secs" (frames converted as "offset_seconds"
+    converts, the end taken at last + 1), "extent_hist" (64 counts over the query's time) and "extent_shift" (bucket b of
+    it covers the query frames [b << shift, (b + 1) << shift)).  Not with fused: that call keeps its hashes inside the
+    library."""
+    if extents and fused:
+        raise ValueError("extents=True needs the query's hashes on the host: not with fused=True")
     ctx = db.ctx
     chans, owner = [], []
     for qi, q in enumerate(queries):
@@ -330,20 +359,22 @@ def recognize_batch(queries, db, Fs: int = RATE, topn: int = TOPN, fused: bool =
     query_time = time() - t0
     t0 = time()
     results = [_result_dicts(db, res, q, int(res["nhash"][q])) for q in range(nq)]
+    if extents:
+        _add_extents(db, results, k, t1, qoff, res)
     align_time = time() - t0
     return results, {"fingerprint_time": fingerprint_time, "query_time": query_time, "align_time": align_time,
                      "n_matches": res["npairs"], "n_hashes": res["nhash"]}
 
 
 def recognize(channels_or_samples, db=None, Fs: int = RATE, topn: int = TOPN, fused: bool = False, resample_to: int = None,
-              delta_tol: int = None):
-    """recognizer.py:377-396: (final_results, fingerprint_time, query_time, align_time).  fused, resample_to, delta_tol: see
-    recognize_batch."""
+              delta_tol: int = None, extents: bool = False):
+    """recognizer.py:377-396: (final_results, fingerprint_time, query_time, align_time).  fused, resample_to, delta_tol,
+    extents: see recognize_batch."""
     if db is None:
         raise ValueError("recognize() needs the HipFingerprintDB holding the fingerprints")
     x = channels_or_samples
     q = [np.asarray(x)] if (not isinstance(x, (list, tuple)) or (len(x) and np.isscalar(x[0]))) else list(x)
-    results, tm = recognize_batch([q], db, Fs, topn, fused, resample_to, delta_tol=delta_tol)
+    results, tm = recognize_batch([q], db, Fs, topn, fused, resample_to, extents, delta_tol=delta_tol)
     return results[0], tm["fingerprint_time"], tm["query_time"], tm["align_time"]
 
 

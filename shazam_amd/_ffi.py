@@ -21,6 +21,7 @@ DEBUG_SPEED_SMALL_SLICES = 16   # shz_recognize_speeds: at most 2 queries a slic
 DEBUG_SCAN_SPEED_SMALL_SLICES = 32   # shz_scan_speeds: at most 1 recording x 2 rungs a slice, 3 windows a match group
 DEBUG_CATALOG_SMALL_SLICES = 64   # shz_match_songs_warps: one song x at most 2 warps a slice
 DEBUG_VOTE_TOLERANT_ROUTE = 128   # the vote: the tolerant route at tolerance 0 too
+DEBUG_EXTENT_SMALL_TILES = 256   # shz_match_extents: tiles of 64 pairs, 4 descriptors in LDS, 3 queries a sub-batch
 SCAN_NO_WARP = 0xFFFFFFFF            # shz_scan_warps: out_best of a window that tried no variant
 SCAN_U32, SCAN_POPC64, SCAN_U64 = 0, 1, 2   # shz_scan_host kinds
 STAGE_F32, STAGE_F64, STAGE_PERSISTENT = 0, 1, 1   # shz_stft_stage_host kinds | flag
@@ -101,6 +102,8 @@ SIGNATURES = {
     "shz_table_song_rows": (C.c_int32, [vp, C.c_uint32, u64p]),
     "shz_table_song_hashes": (C.c_int32, [vp, vp, C.c_uint32, u64p, vp, vp, C.c_uint64, C.c_uint32]),
     "shz_match_songs": (C.c_int32, [vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "shz_match_extents": (C.c_int32, [vp, vp, vp, vp, u64p, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "shz_match_songs_extents": (C.c_int32, [vp, vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "shz_warp_row_host": (C.c_int32, [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp, vp]),
     "shz_warp_rows": (C.c_int32, [vp, vp, vp, u64p, C.c_uint32, u32p, u32p, C.c_uint32, C.c_uint32, vp, vp, u64p, C.c_uint64,
                                   u64p]),
@@ -350,7 +353,8 @@ class Context:
         from runs hold at most RUN_ROWS_MAX_SMALL rows, 8: shz_scan_batch matches its windows in groups of at most 3, 16: shz_recognize_speeds warps and
         matches its queries in slices of at most 2, 32: shz_scan_speeds works in slices of 1 recording x 2 rungs and matches
         its windows in groups of at most 3, 64: shz_match_songs_warps works in slices of 1 song x 2 warps, 128: the vote takes
-        the tolerant route at tolerance 0 too)."""
+        the tolerant route at tolerance 0 too, 256: the extent kernel works in tiles of 64 pairs with 4 descriptors in LDS and
+        sub-batches of 3 queries)."""
         self.check(lib().shz_set_debug(self.h, int(flags)))
 
     def set_vote_tolerance(self, bins: int):
@@ -1302,6 +1306,52 @@ class Table:
                                                    *[C.byref(m) if timings else None for m in ms]))
         if timings:
             res["ms"] = tuple(float(m.value) for m in ms)
+        return res
+
+    def _extent_args(self, n, cand_sid, d_lo, d_hi, cand_n, hist):
+        """the candidate arrays as [n, ncand] (a 1-d list is one slot a query) and the dict of zeroed outputs"""
+        cs = np.ascontiguousarray(cand_sid, np.uint32)
+        if cs.ndim == 1:
+            cs = cs.reshape(n, -1) if n else cs.reshape(0, 1)
+        lo = np.ascontiguousarray(d_lo, np.int32).reshape(cs.shape)
+        hi = np.ascontiguousarray(d_hi, np.int32).reshape(cs.shape)
+        if cs.ndim != 2 or cs.shape[0] != n:
+            raise ValueError(f"candidates are [n, ncand] arrays with n = {n}; got {cs.shape}")
+        ncand = cs.shape[1]
+        cn = (np.full(n, ncand, np.uint32) if cand_n is None else np.ascontiguousarray(cand_n, np.uint32).reshape(-1))
+        if len(cn) != n:
+            raise ValueError(f"cand_n has {len(cn)} entries for {n} queries")
+        res = {k: np.zeros((n, ncand), np.uint32) for k in ("count", "q_first", "q_last", "t_first", "t_last")}
+        res["hist"] = np.zeros((n, ncand, 64), np.uint32) if hist else None
+        res["shift"] = np.zeros(n, np.uint32)
+        return cs, lo, hi, cn, ncand, res
+
+    def match_extents(self, key32, q_off, query_off, cand_sid, d_lo, d_hi, cand_n=None, hist=True):
+        """Where the aligned hashes lie (shz_match_extents): per query and candidate (song cand_sid, offset differences d_lo ..
+        d_hi inclusive) the pairs that belong -- count, q_first / q_last (query frames), t_first / t_last (song frames) as
+        [n, ncand], hist [n, ncand, 64] (pairs per bucket q_off >> shift; None with hist false), shift [n].  Candidates are
+        [n, ncand] arrays, of which query q uses the first cand_n[q] (None: all); everything past them is zero."""
+        k = np.ascontiguousarray(key32, np.uint32)
+        o = np.ascontiguousarray(q_off, np.uint32)
+        qo = np.ascontiguousarray(query_off, np.uint64)
+        n = len(qo) - 1
+        cs, lo, hi, cn, ncand, res = self._extent_args(n, cand_sid, d_lo, d_hi, cand_n, hist)
+        self.ctx.check(lib().shz_match_extents(self.ctx.h, self.h, ptr(k), ptr(o), qo.ctypes.data_as(u64p), n, ncand, ptr(cs),
+                                               ptr(lo), ptr(hi), ptr(cn), ptr(res["count"]), ptr(res["q_first"]),
+                                               ptr(res["q_last"]), ptr(res["t_first"]), ptr(res["t_last"]), ptr(res["hist"]),
+                                               ptr(res["shift"])))
+        return res
+
+    def match_songs_extents(self, sids, cand_sid, d_lo, d_hi, cand_n=None, hist=True):
+        """match_extents with the listed songs' own rows as the queries (shz_match_songs_extents): the rows are gathered on the
+        device; q_first / q_last are offsets of the listed song, t_first / t_last of the candidate song."""
+        a = np.ascontiguousarray(sids, np.uint32).reshape(-1)
+        n = len(a)
+        cs, lo, hi, cn, ncand, res = self._extent_args(n, cand_sid, d_lo, d_hi, cand_n, hist)
+        self.ctx.check(lib().shz_match_songs_extents(self.ctx.h, self.h, ptr(a), n, ncand, ptr(cs), ptr(lo), ptr(hi), ptr(cn),
+                                                     ptr(res["count"]), ptr(res["q_first"]), ptr(res["q_last"]),
+                                                     ptr(res["t_first"]), ptr(res["t_last"]), ptr(res["hist"]),
+                                                     ptr(res["shift"])))
         return res
 
     def finalize_runs(self, run_rows):

@@ -45,6 +45,7 @@ MIN_COVERAGE_WARPED = 0.03
 
 PAIR_FIELDS = (("a", np.uint32), ("b", np.uint32), ("delta", np.int64), ("aligned", np.uint32), ("rows_a", np.uint64),
                ("rows_b", np.uint64), ("coverage_a", np.float64), ("coverage_b", np.float64), ("relation", "U7"))
+EXTENT_PAIR_FIELDS = PAIR_FIELDS + (("a_first", np.uint32), ("a_last", np.uint32), ("b_first", np.uint32), ("b_last", np.uint32))
 WARP_PAIR_FIELDS = PAIR_FIELDS + (("tempo_q16", np.uint32), ("pitch_q16", np.uint32), ("warped", "U1"), ("aligned_plain", np.uint32))
 S_ONE = 65536
 
@@ -285,6 +286,36 @@ def _batches(rows, live, budget):
     return parts
 
 
+def pair_extents(table, pairs, tol: int = 0, batch_rows: int = BATCH_ROWS) -> np.ndarray:
+    """The records of fold_pairs with the position of every pair in both songs (EXTENT_PAIR_FIELDS): a_first .. a_last are the
+    frames of song a, b_first .. b_last those of song b, between which the rows aligned at delta (+- tol) lie.  One
+    Table.match_songs_extents call per batch of a songs (at most batch_rows rows): the a songs are the queries, (b, delta -
+    tol, delta + tol) their candidates."""
+    out = np.zeros(len(pairs), np.dtype(list(EXTENT_PAIR_FIELDS)))
+    for f, _ in PAIR_FIELDS:
+        out[f] = pairs[f]
+    if len(pairs) == 0:
+        return out
+    a_ids, first, per = np.unique(pairs["a"], return_index=True, return_counts=True)   # (pairs are ordered by (a, b))
+    slot = np.arange(len(pairs)) - np.repeat(first, per)
+    row_off, _, _ = table.song_hashes(a_ids, counts_only=True)
+    rows = np.diff(row_off.astype(np.int64))
+    for part in _batches(rows, np.arange(len(a_ids)), batch_rows):
+        for c0 in range(0, int(per[part].max()), 64):        # (a song with more than 64 partners: 64 a call)
+            ncand = int(min(64, per[part].max() - c0))
+            cs, lo, hi = (np.zeros((len(part), ncand), t) for t in (np.uint32, np.int32, np.int32))
+            sel = np.flatnonzero(np.isin(pairs["a"], a_ids[part]) & (slot >= c0) & (slot < c0 + ncand))
+            at = np.searchsorted(a_ids[part], pairs["a"][sel])
+            cs[at, slot[sel] - c0] = pairs["b"][sel]
+            lo[at, slot[sel] - c0] = pairs["delta"][sel] - int(tol)
+            hi[at, slot[sel] - c0] = pairs["delta"][sel] + int(tol)
+            ext = table.match_songs_extents(a_ids[part], cs, lo, hi, cand_n=np.clip(per[part] - c0, 0, ncand).astype(np.uint32),
+                                            hist=False)
+            for f, g in (("a_first", "q_first"), ("a_last", "q_last"), ("b_first", "t_first"), ("b_last", "t_last")):
+                out[f][sel] = ext[g][at, slot[sel] - c0]
+    return out
+
+
 def _find_duplicates_warps(table, sids, lad, topn, min_aligned, min_coverage, batch_rows, timings=False):
     from .speed import MAX_WARPS
     t16, f16, row = lad
@@ -314,7 +345,8 @@ def _find_duplicates_warps(table, sids, lad, topn, min_aligned, min_coverage, ba
 
 @takes_delta_tol(lambda *a, **k: (lambda x: x.ctx)(k["db_or_table"] if "db_or_table" in k else a[0]))
 def find_duplicates(db_or_table, sids=None, topn: int = 5, min_aligned: int = None, min_coverage: float = None,
-                    batch_rows: int = BATCH_ROWS, speeds=None, tempos=None, pitches=None, warps=None, timings: bool = False) -> dict:
+                    batch_rows: int = BATCH_ROWS, speeds=None, tempos=None, pitches=None, warps=None, timings: bool = False,
+                    extents: bool = False) -> dict:
     """Duplicate, contained and overlapping tracks among the listed songs (None: every song of the table) and the rest of
     the table.  The songs are walked in batches of at most batch_rows rows (one counts-only gather gives the row counts),
     each batch is one match_songs call, and fold_pairs makes one record per pair.  Returns its dict: "pairs" and
@@ -326,9 +358,14 @@ def find_duplicates(db_or_table, sids=None, topn: int = 5, min_aligned: int = No
     the records (WARP_PAIR_FIELDS: which song's rows were warped, by which factors, and the plain count), and the
     thresholds default to MIN_ALIGNED_WARPED / MIN_COVERAGE_WARPED.  Put 65536 on the ladder (speed_ladder does) to keep
     the exact copies in the same answer.  timings (ladder only): "ms" = (gather, warp, match) device times, summed.
-    delta_tol= (keyword): the vote tolerance in offset bins while the call runs (Context.tolerance); None: the context's."""
+    delta_tol= (keyword): the vote tolerance in offset bins while the call runs (Context.tolerance); None: the context's.
+    extents: "pairs" gains a_first, a_last, b_first, b_last (EXTENT_PAIR_FIELDS; pair_extents): where in a and where in b the
+    aligned rows lie -- the position of an excerpt inside the longer track, the length of an overlap.  Not with a ladder:
+    warped rows have no extents yet."""
     table, _ = _table_of(db_or_table)
     lad = _ladder_of(speeds, tempos, pitches, warps)
+    if extents and lad is not None:
+        raise ValueError("extents=True does not take a ladder (speeds= / tempos= / pitches= / warps=)")
     min_aligned = (MIN_ALIGNED if min_aligned is None else min_aligned) if lad is None else min_aligned
     min_coverage = (MIN_COVERAGE if min_coverage is None else min_coverage) if lad is None else min_coverage
     if sids is None:
@@ -349,11 +386,17 @@ def find_duplicates(db_or_table, sids=None, topn: int = 5, min_aligned: int = No
         lo = hi
     res = [table.match_songs(sids[p], topn=topn) for p in parts]
     if not res:
-        return fold_pairs([], [], [], [], [], [], [], min_aligned, min_coverage)
+        out = fold_pairs([], [], [], [], [], [], [], min_aligned, min_coverage)
+        if extents:
+            out["pairs"] = pair_extents(table, out["pairs"])
+        return out
     listed = np.concatenate([sids[p] for p in parts])
     cat = {f: np.concatenate([r[f] for r in res]) for f in ("sid", "delta", "aligned", "nres", "rows")}
     valid = np.arange(topn)[None, :] < cat["nres"][:, None].astype(np.int64)
     found = np.setdiff1d(np.unique(cat["sid"][valid]), listed)      # songs outside the list: their rows by one more count
     f_off, _, _ = table.song_hashes(found, counts_only=True)
-    return fold_pairs(listed, cat["sid"], cat["delta"], cat["aligned"], cat["nres"], np.concatenate([listed, found]),
-                      np.concatenate([cat["rows"], np.diff(f_off)]), min_aligned, min_coverage)
+    out = fold_pairs(listed, cat["sid"], cat["delta"], cat["aligned"], cat["nres"], np.concatenate([listed, found]),
+                     np.concatenate([cat["rows"], np.diff(f_off)]), min_aligned, min_coverage)
+    if extents:
+        out["pairs"] = pair_extents(table, out["pairs"], tol=table.ctx.vote_tolerance, batch_rows=batch_rows)
+    return out

@@ -99,6 +99,12 @@ enum {
   SHZ_WS_RW_TAB,     // ... the row warp: CSR of the songs over their rows | time factors | frequency factors of the call
   SHZ_WS_RW_BLK,     // ... kept items of every block of RW_ITEMS items of a slice, then their scan
   SHZ_WS_RW_CNT,     // ... kept items of every (song, warp) of a slice
+  SHZ_WS_EX_SEGS,    // shz_extent.hip: the segment descriptors
+  SHZ_WS_EX_QOFF,    // ... the CSR of the queries over their hashes
+  SHZ_WS_EX_CAND,    // ... the candidates of the call: song ids | d_lo | d_hi | used slots of every query
+  SHZ_WS_EX_CTL,     // ... control block of a sub-batch | largest offset of every query | its shift
+  SHZ_WS_EX_OUT,     // ... count | q_first | q_last | t_first | t_last | histograms of every candidate
+  SHZ_WS_EX_LO, SHZ_WS_EX_ROWS, SHZ_WS_EX_PO,   // ... per (element, segment): first row, rows, pairs in front of it
   SHZ_WS_COUNT
 };
 

@@ -181,6 +181,13 @@ class HipFingerprintDB:
         with self.ctx.tolerance(delta_tol):
             return self.table.match(key32, q_off, query_off, topn)
 
+    def match_extents(self, key32, q_off, query_off, cand_sid, d_lo, d_hi, cand_n=None, hist=True):
+        """Table.match_extents of the finalized table: where the aligned hashes of the candidates lie; one table only."""
+        if not hasattr(self.table, "h"):
+            raise NotImplementedError("match_extents takes the unsharded table (shards=1)")
+        self.finalize()
+        return self.table.match_extents(key32, q_off, query_off, cand_sid, d_lo, d_hi, cand_n=cand_n, hist=hist)
+
     def find_duplicates(self, **kw):
         """Duplicate, contained and overlapping tracks of this catalogue (shazam_amd/catalog.find_duplicates); one table
         only: a key-sharded database has no song gather."""
