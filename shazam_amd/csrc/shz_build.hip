@@ -1049,9 +1049,10 @@ extern "C" int32_t shz_table_lookup(shz_table* t, const uint32_t* keys, uint64_t
 // BASELINE (1M songs = 20 bits, 3-minute tracks = 12 bits); other tables take the column path (finalize_active).
 //   * a run is sorted once, by the rank (or ingest batch) that made it, and never again;
 //   * N runs are merged in ONE pass ("every rank merges 8 sorted runs"): sampled splitters cut the value
-//     range into tiles of ~2,048 rows, a workgroup loads its tile's share of every run into LDS, ranks every element by
-//     binary searches in the other runs' shares, and writes the rows straight into the segment's three columns --
-//     8 bytes read and 12 written per row, no intermediate merged run, no pass per level of a merge tree;
+//     range into tiles of ~1,024 or ~2,048 rows, a workgroup loads its tile's share of every run into LDS, merges the
+//     shares pairwise along merge paths (log2 k rounds inside LDS: one binary search along a thread's diagonal, then a
+//     serial merge of the two heads), and writes the rows straight into the segment's three columns --
+//     8 bytes read and 12 written per row, no intermediate merged run, no pass per level of a merge tree in memory;
 //   * after shz_table_reserve the build performs no device allocation: the slab (columns), the run arena, the staging
 //     columns and the sort scratch exist before the first batch arrives (allocated on a helper thread beside it).
 
@@ -1424,7 +1425,7 @@ __global__ __launch_bounds__(KW_THREADS) void kw_tile_kernel(kw_runs R, const ui
   for (uint32_t stride = 1; stride < k; stride <<= 1) {
     uint64_t out[PER];
     uint32_t g = g0;
-    while (g < g1) {                                                    // one piece per region the thread's outputs touch (1, rarely 2)
+    while (g < g1) {                                                    // one piece per region the thread's outputs touch (1, rarely 2; 4 - 5 beside one huge run)
       uint32_t q = 0;
       while (q + 2 * stride < k && s_off[min(k, q + 2 * stride)] <= g) q += 2 * stride;
       const uint32_t a0 = min(s_off[q], total), mid = min(s_off[min(k, q + stride)], total), e = min(s_off[min(k, q + 2 * stride)], total);
@@ -1801,14 +1802,19 @@ static int32_t flush_runs(shz_table* t, bool final) {
     SHZ_HIP(ctx, hipStreamSynchronize(t->gx_stream));
     t->gx_stream = nullptr;
   }
-  if (t->runs.size() > KW_MAXK) SHZ_TRY(collapse_runs(t, KW_MAXK));
+  const uint64_t L = std::min<uint64_t>(t->seg_limit, run_rows_max(ctx));
+  // A merge takes KW_MAXK runs.  Under a segment limit below 8 kp2 rows (tests) it takes fewer: pieces are cut in whole
+  // tiles and a tile holds up to 3 max(kp2, L / 8) rows, so that a tile alone would outgrow the segment.  The smallest
+  // runs are merged first until the runs left let every tile stay below 3 L / 8 rows.
+  size_t keep = KW_MAXK;
+  while (keep > 1 && 8 * keep > L) keep >>= 1;
+  if (t->runs.size() > keep) SHZ_TRY(collapse_runs(t, keep));
   std::vector<const uint64_t*> ptr;
   for (const shz_run& r : t->runs) ptr.push_back(t->rbuf + r.off);
   const bool dedup = runs_may_share_rows(t->runs);
   uint32_t sid_lo = 0xFFFFFFFFu, sid_hi = 0;
   for (const shz_run& r : t->runs)
     if (r.n) { sid_lo = std::min(sid_lo, r.sid_lo); sid_hi = std::max(sid_hi, r.sid_hi); }
-  const uint64_t L = std::min<uint64_t>(t->seg_limit, run_rows_max(ctx));
   if (final) {
     SHZ_TRY(kway_merge(t, ptr, t->runs, dedup, L, 0xFFFFFFFFu, true, nullptr, 0, nullptr));
     t->runs.clear();

@@ -43,7 +43,7 @@ def _check_table(t, want):
 
 @pytest.mark.parametrize("ordered", [True, False])
 @pytest.mark.parametrize("n_runs, per, seg_rows", [(1, 5000, None), (3, 40000, None), (8, 9000, 20000), (5, 30000, 16000),
-                                                    (19, 3000, None), (2, 700, 256)])
+                                                    (19, 3000, None), (40, 1500, None), (2, 700, 256)])
 def test_sealed_runs_equal_numpy(env, ordered, n_runs, per, seg_rows):
     S, F, ctx = env
     rng = np.random.default_rng(n_runs * 1000 + per + int(ordered))
