@@ -864,6 +864,60 @@ int32_t shz_scan_timeline(const uint64_t* win_off, uint32_t n_recs, const uint32
                           uint32_t min_aligned, uint32_t max_gap, uint32_t* seg_rec, uint32_t* seg_sid, int64_t* seg_shift,
                           uint32_t* seg_first, uint32_t* seg_last, uint32_t* seg_hits, uint32_t* seg_best, uint64_t cap,
                           uint64_t* count);
+/* ---- scan extents (new): frame-accurate start and end of every segment.  A segment's span is only as fine as the windows:
+ * it starts at the start of its first hit window and ends at the end of its last one, and the music may begin or end
+ * anywhere inside them.  The scan holds every recording's hashes on the device and knows each segment's identity (sid,
+ * shift), so the extent pass of shz_match_extents can say where the aligned pairs of a segment really lie.
+ * ZONES (shz_scan_zones; no GPU, no ctx; tests/scan_extent_twin.py is the same in Python): with a = first and b = last window
+ * of a segment, W = window_frames, S = step_frames, M = margin_frames and F = frames[rec], every segment gets three half-open
+ * ranges [lo, hi) of recording frames, zone z of segment i at 3 i + z:
+ *   0 whole  [max(0, aS - M), min(F, bS + W + M))   all pairs of the play, its span in the song, a coarse histogram
+ *   1 head   [max(0, aS - M), min(F, aS + W))       where the play starts: 64 buckets over W + M frames whatever its length
+ *   2 tail   [bS,             min(F, bS + W + M))   where the play ends, likewise
+ * An interrupted song gives two segments of one identity (rec, sid, shift), whose margins must not reach into each other's
+ * windows: with L = the largest b_k S + W over EARLIER segments of the same identity, the lo of zones 0 and 1 is at least
+ * min(L, aS); with R = the smallest a_k S over LATER ones, the hi of zones 0 and 2 is at most max(R, bS + W).  Every bound is
+ * then clamped into [0, F]; a zone with lo >= hi after that (a window that starts behind the recording's end when S > W) is
+ * EMPTY and is written as hi = lo.  Positions are formed in 64 bits.
+ * Refused (SHZ_E_INVALID): window_frames or step_frames of 0, a NULL array (frames with n_recs > 0, the others with n_segs >
+ * 0), a frames[r] >= 2^32, a segment with first > last or rec >= n_recs, segments that are not in the order shz_scan_timeline
+ * emits (recordings ascending, inside a recording first > the last of the segment in front). */
+int32_t shz_scan_zones(const uint32_t* seg_rec, const uint32_t* seg_sid, const int64_t* seg_shift, const uint32_t* seg_first,
+                       const uint32_t* seg_last, uint64_t n_segs, const uint64_t* frames, uint32_t n_recs, uint32_t window_frames,
+                       uint32_t step_frames, uint32_t margin_frames, uint32_t* zone_lo, uint32_t* zone_hi);
+/* Everything in one call: the extraction (once), the window stage and the match of shz_scan_batch, shz_scan_timeline on the
+ * host inside the library (min_aligned, max_gap), the zones, and the extent pass on the zones' hashes, which are cut from the
+ * device-resident hash lists and never cross the bus.  The arguments up to `count` and ms_extract / ms_window / ms_match are
+ * shz_scan_batch's, and the window arrays and win_off are array for array what it writes; seg_* [cap_segs] and *seg_count
+ * are what shz_scan_timeline writes from them.
+ * The QUERY of a zone is the set, over the recording's channels, of (key32, t1 - lo) for the hashes with lo <= t1 < hi -- the
+ * cut of a window (EDGES above apply); its one CANDIDATE is (sid, shift + lo - d_tol, shift + lo + d_tol), because
+ * off - (t1 - lo) = (off - t1) + lo and off - t1 is the shift; its RESULT is what shz_match_extents defines for that query
+ * and candidate.  Zone outputs, [3 cap_segs] each, zone z of segment i at 3 i + z: zone_lo / zone_hi (the zone itself),
+ * zone_count, zone_q_first / zone_q_last (in RECORDING frames, + lo, where count > 0; 0 otherwise), zone_t_first /
+ * zone_t_last (song frames), zone_shift (of the zone's histogram: the smallest s with ((largest t1 - lo) >> s) < 64) and
+ * zone_hist [3 cap_segs x 64] (bucket (t1 - lo) >> shift; may be NULL: not computed).  With d_tol = 0 and the context's
+ * vote tolerance 0, zone 0's count of a one-window segment at margin 0 is that window's rank-0 aligned count, and zone 0's
+ * count of any segment is at least the segment's seg_best (every window's hash set is a subset of zone 0's).  ms_extent (may
+ * be NULL): hipEvent time of cutting the zones and of the extent pass.
+ * More segments than cap_segs: SHZ_E_CAPACITY, *seg_count = their number, the window arrays and the first cap_segs segments
+ * are written and NO zone output is: zone outputs only ever come from a call that returns SHZ_OK.  There are never more
+ * segments than windows.  No segment (or no window): SHZ_OK, *seg_count = 0, nothing is launched for zones.
+ * Refused before anything is launched, in this order behind shz_scan_batch's own refusals: d_tol > 31, margin_frames >= 2^20,
+ * a NULL seg_count or, with cap_segs > 0, a NULL segment or zone array (SHZ_E_INVALID); then the table as shz_match_extents
+ * refuses it (a table offset >= 2^31: SHZ_E_UNSUPPORTED).  Seen on the device, after the scan: a zone longer than 2^20 frames
+ * (a query offset of the extent pass; SHZ_E_UNSUPPORTED) -- a play of more than about 13 hours.  flags: shz_scan_batch's. */
+int32_t shz_scan_extents(shz_ctx* ctx, shz_table* t, const int16_t* pcm, const uint64_t* clip_off, uint32_t n_clips,
+                         const uint32_t* rec_clip0, uint32_t n_recs, uint32_t fs, double amp_min, uint32_t fan_value,
+                         uint32_t window_frames, uint32_t step_frames, uint32_t topn, uint32_t flags, uint32_t min_aligned,
+                         uint32_t max_gap, uint32_t margin_frames, uint32_t d_tol, uint64_t* win_off, uint32_t* out_sid,
+                         int32_t* out_delta, uint32_t* out_aligned, uint32_t* out_dedup, uint32_t* out_nres, uint32_t* out_nhash,
+                         uint64_t* out_npairs, uint64_t cap_windows, uint64_t* count, uint32_t* seg_rec, uint32_t* seg_sid,
+                         int64_t* seg_shift, uint32_t* seg_first, uint32_t* seg_last, uint32_t* seg_hits, uint32_t* seg_best,
+                         uint64_t cap_segs, uint64_t* seg_count, uint32_t* zone_lo, uint32_t* zone_hi, uint32_t* zone_count,
+                         uint32_t* zone_q_first, uint32_t* zone_q_last, uint32_t* zone_t_first, uint32_t* zone_t_last,
+                         uint32_t* zone_shift, uint32_t* zone_hist, float* ms_extract, float* ms_window, float* ms_match,
+                         float* ms_extent);
 
 /* ---- speed-tolerant recognition (new; the reference's hash is an exact (f1, f2, dt) triple, recognizer.py:100-114, so audio
  * played 1 % fast or slow no longer meets the table) ----------------------------------------------------------------------

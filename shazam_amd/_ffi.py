@@ -175,7 +175,13 @@ SIGNATURES = {
                                    u64p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "shz_scan_timeline": (C.c_int32, [u64p, C.c_uint32, vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                       vp, vp, vp, vp, vp, vp, vp, C.c_uint64, u64p]),
-    "shz_warp_pair_hash": (C.c_int32, [vp, vp, vp, u64p, C.c_uint32, u32p, C.c_uint32, u32p, C.c_uint32, C.c_uint32, C.c_uint32,
+    "shz_scan_zones": (C.c_int32, [vp, vp, vp, vp, vp, C.c_uint64, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp]),
+    "shz_scan_extents": (C.c_int32, [vp, vp, vp, u64p, C.c_uint32, u32p, C.c_uint32, C.c_uint32, C.c_double, C.c_uint32,
+                                     C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                     u64p, vp, vp, vp, vp, vp, vp, vp, C.c_uint64, u64p, vp, vp, vp, vp, vp, vp, vp, C.c_uint64, u64p,
+                                     vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                     C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "shz_warp_pair_hash":(C.c_int32, [vp, vp, vp, u64p, C.c_uint32, u32p, C.c_uint32, u32p, C.c_uint32, C.c_uint32, C.c_uint32,
                                        vp, vp, u64p, C.c_uint64, u64p]),
     "shz_recognize_speeds": (C.c_int32, [vp, vp, vp, u64p, C.c_uint32, u32p, C.c_uint32, C.c_uint32, C.c_double, C.c_uint32,
                                          C.c_uint32, u32p, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp,
@@ -735,6 +741,50 @@ class Context:
         res = self._windows_with_room(call, lambda n: _match_result(n, topn), cnt, cap_windows)
         return res, wo, tuple(float(m.value) for m in ms)
 
+    def scan_extents_raw(self, table: "Table", pcm, clip_off, rec_clip0, window_frames, step_frames, min_aligned, max_gap=1,
+                         margin_frames=0, d_tol=0, fs=44100, amp_min=10.0, fan_value=5, topn=2, pcm_device=False, full_sort=False,
+                         cap_windows=0, cap_segs=0, hist=True, fill=0, zones=True):
+        """One shz_scan_extents as it is, with room for cap_windows windows and cap_segs segments: (rc, res, seg, zone,
+        win_off, n_windows, n_segs, ms).  res as Table.match, seg as scan_timeline_raw's, zone = the arrays ZONE_FIELDS
+        [cap_segs, 3] and hist [cap_segs, 3, 64] (None with hist false); seg and zone arrays are filled with `fill` before the
+        call.  zones=False hands the library NULL zone arrays.  ms = (extract, window, match, extent)."""
+        co, nc = self._clip_off(clip_off)
+        rc0 = np.ascontiguousarray(rec_clip0, np.uint32)
+        nr = len(rc0) - 1
+        flags = (PCM_DEVICE if pcm_device else 0) | (MATCH_FULL_SORT if full_sort else 0)
+        wo, cnt, scnt = np.zeros(nr + 1, np.uint64), C.c_uint64(), C.c_uint64()
+        ms = [C.c_float(), C.c_float(), C.c_float(), C.c_float()]
+        res = _match_result(int(cap_windows), topn)
+        seg = {k: np.full(int(cap_segs), fill, d) for k, d in SEGMENT_FIELDS}
+        zone = {k: np.full((int(cap_segs), 3), fill, np.uint32) for k in ZONE_FIELDS}
+        zone["hist"] = np.full((int(cap_segs), 3, 64), fill, np.uint32) if hist else None
+        zp = [ptr(zone[k]) if zones else None for k in ZONE_FIELDS + ("hist",)]
+        rc = lib().shz_scan_extents(self.h, table.h, ptr(pcm), co.ctypes.data_as(u64p), nc, rc0.ctypes.data_as(u32p), nr, int(fs),
+                                    float(amp_min), int(fan_value), int(window_frames), int(step_frames), int(topn), flags,
+                                    int(min_aligned), int(max_gap), int(margin_frames), int(d_tol), wo.ctypes.data_as(u64p),
+                                    ptr(res["sid"]), ptr(res["delta"]), ptr(res["aligned"]), ptr(res["dedup"]), ptr(res["nres"]),
+                                    ptr(res["nhash"]), ptr(res["npairs"]), int(cap_windows), C.byref(cnt),
+                                    *[ptr(seg[k]) for k, _ in SEGMENT_FIELDS], int(cap_segs), C.byref(scnt), *zp,
+                                    *[C.byref(m) for m in ms])
+        return rc, res, seg, zone, wo, int(cnt.value), int(scnt.value), tuple(float(m.value) for m in ms)
+
+    def scan_extents(self, table: "Table", pcm, clip_off, rec_clip0, window_frames, step_frames, min_aligned, max_gap=1,
+                     margin_frames=0, d_tol=0, hist=True, **kw):
+        """shz_scan_extents: scan_batch, the timeline and the extent pass on every segment's three zones (whole, head, tail) in
+        one call, the recordings' hashes staying on the device.  Returns (res, win_off, seg, zone, ms): res / win_off as
+        scan_batch's, seg as scan_timeline's, zone = arrays lo, hi, count, q_first, q_last (recording frames), t_first, t_last
+        (song frames), shift [n_segs, 3] and hist [n_segs, 3, 64] (None with hist false), ms = (extract, window, match, extent).
+        Room: the window count follows from the frame counts (a first call that launches nothing), and there are never more
+        segments than windows, so one call with room for that many suffices."""
+        args = (table, pcm, clip_off, rec_clip0, window_frames, step_frames, min_aligned, max_gap, margin_frames, d_tol)
+        rc, _, _, _, _, n_wins, _, _ = self.scan_extents_raw(*args, hist=False, **kw)
+        if rc != E_CAPACITY:
+            self.check(rc)
+        rc, res, seg, zone, wo, n_wins, n_segs, ms = self.scan_extents_raw(*args, cap_windows=n_wins, cap_segs=n_wins, hist=hist, **kw)
+        self.check(rc)
+        return (res, wo, {k: v[:n_segs] for k, v in seg.items()},
+                {k: (None if v is None else v[:n_segs]) for k, v in zone.items()}, ms)
+
     def scan_speeds(self, table: "Table", pcm, clip_off, rec_clip0, window_frames, step_frames, speeds, fs=44100, amp_min=10.0,
                     fan_value=5, topn=2, pcm_device=False, full_sort=False, cap_windows=None):
         """shz_scan_speeds: the peaks of the clips once, warped for every factor of `speeds` (Q16), every window of every
@@ -1088,6 +1138,31 @@ def scan_timeline(win_off, sid, delta, aligned, nres, step_frames, min_aligned, 
     if rc != OK:
         raise ShzError(rc, "shz_scan_timeline: bad arguments")
     return seg
+
+
+ZONE_FIELDS = ("lo", "hi", "count", "q_first", "q_last", "t_first", "t_last", "shift")
+
+
+def scan_zones_raw(seg, frames, window_frames, step_frames, margin_frames):
+    """One shz_scan_zones as it is (host only): (rc, lo, hi), the zones [n_segs, 3] of the segments seg = the dict of
+    scan_timeline (rec, sid, shift, first, last are read)."""
+    a = {k: np.ascontiguousarray(seg[k], d) for k, d in SEGMENT_FIELDS[:5]}
+    n = len(a["rec"])
+    assert all(len(v) == n for v in a.values())
+    fr = np.ascontiguousarray(frames, np.uint64)
+    lo, hi = np.zeros((n, 3), np.uint32), np.zeros((n, 3), np.uint32)
+    rc = lib().shz_scan_zones(*[ptr(a[k]) for k, _ in SEGMENT_FIELDS[:5]], n, ptr(fr), len(fr), int(window_frames), int(step_frames),
+                              int(margin_frames), ptr(lo), ptr(hi))
+    return rc, lo, hi
+
+
+def scan_zones(seg, frames, window_frames, step_frames, margin_frames):
+    """shz_scan_zones (host only): the three zones [lo, hi) of recording frames of every segment -- whole, head, tail -- as
+    two arrays [n_segs, 3] (include/shz.h at shz_scan_zones)."""
+    rc, lo, hi = scan_zones_raw(seg, frames, window_frames, step_frames, margin_frames)
+    if rc != OK:
+        raise ShzError(rc, "shz_scan_zones: bad arguments")
+    return lo, hi
 
 
 SPEED_SEGMENT_FIELDS = (("rec", np.uint32), ("sid", np.uint32), ("first", np.uint32), ("last", np.uint32), ("hits", np.uint32),

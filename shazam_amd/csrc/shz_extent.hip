@@ -1,5 +1,6 @@
 // Match extents: WHERE in the query and in the song the aligned hashes of known winners lie.
-//   shz_match_extents / shz_match_songs_extents -> ex_device, on query columns that are on the device.
+//   shz_match_extents / shz_match_songs_extents -> ex_device, on query columns that are on the device; shz_scan_extents
+//   (shz_scan.hip) calls ex_device on the zones it cuts from a scan's own hash lists.
 //
 // A second, cheap pass over the (query hash, table row) pairs of the match.  The winners are known, so nothing is sorted by
 // song: the head composes (query, key32, q_off) elements, sorts them and drops duplicates (the set semantics of the match),
@@ -293,14 +294,6 @@ __global__ void ex_tail_kernel(const uint32_t* __restrict__ count, uint32_t* __r
 
 namespace {
 
-struct ex_args {   // what both entry points hand over (host arrays but the two query columns)
-  uint32_t n_queries, ncand;
-  const uint32_t* cand_sid;
-  const int32_t *cand_dlo, *cand_dhi;
-  const uint32_t* cand_n;
-  uint32_t *out_count, *out_q_first, *out_q_last, *out_t_first, *out_t_last, *out_hist, *out_shift;
-};
-
 struct own_bufs {   // device allocations of one call, freed when it ends
   std::vector<void*> p;
   ~own_bufs() {
@@ -314,7 +307,16 @@ struct own_bufs {   // device allocations of one call, freed when it ends
   }
 };
 
-// what both forms refuse about the table and the candidates before anything is launched (n > 0)
+}  // namespace
+
+// (ex_args, and the declarations of what follows: shz_internal.h -- the scan calls them on its own device columns)
+int32_t ex_table_limits(shz_ctx* ctx, shz_table* t, const char* who) {
+  if (t->max_off >= (1u << 31))
+    SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "%s: the table holds offset %u; offsets must be < 2^31", who, t->max_off);
+  return SHZ_OK;
+}
+
+// what every form refuses about the table and the candidates before anything is launched (n > 0)
 int32_t ex_check(shz_ctx* ctx, shz_table* t, const char* who, const ex_args& A) {
   if (!A.cand_sid || !A.cand_dlo || !A.cand_dhi || !A.cand_n) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: NULL candidate array", who);
   if (!A.out_count || !A.out_q_first || !A.out_q_last || !A.out_t_first || !A.out_t_last || !A.out_shift)
@@ -327,9 +329,7 @@ int32_t ex_check(shz_ctx* ctx, shz_table* t, const char* who, const ex_args& A) 
         SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: candidate %u of query %u has d_lo = %d above d_hi = %d", who, c, q, A.cand_dlo[i], A.cand_dhi[i]);
     }
   }
-  if (t->max_off >= (1u << 31))
-    SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "%s: the table holds offset %u; offsets must be < 2^31", who, t->max_off);
-  return SHZ_OK;
+  return ex_table_limits(ctx, t, who);
 }
 
 int32_t ex_state(shz_ctx* ctx, shz_table* t, const char* who, uint32_t ncand) {
@@ -340,9 +340,10 @@ int32_t ex_state(shz_ctx* ctx, shz_table* t, const char* who, uint32_t ncand) {
   return SHZ_OK;
 }
 
-// The one path of both entry points (and of whoever holds query columns on the device later: the scan, the listeners):
-// d_key32 / d_q_off are device columns, query_off (host) their CSR, never decreasing; the rest of A is checked (ex_check).
-// The outputs are written only when the whole call succeeded.
+// The one path of every entry point (the two below, and shz_scan_extents on the zones of a scan; whoever holds query columns
+// on the device later -- the listeners -- calls it the same way): d_key32 / d_q_off are device columns, query_off (host)
+// their CSR, never decreasing; the rest of A is checked (ex_check).  The outputs are written only when the whole call
+// succeeded.
 int32_t ex_device(shz_ctx* ctx, shz_table* t, const char* who, const uint32_t* d_key32, const uint32_t* d_q_off,
                   const uint64_t* query_off, const ex_args& A) {
   const uint32_t nq_all = A.n_queries, ncand = A.ncand;
@@ -443,8 +444,6 @@ int32_t ex_device(shz_ctx* ctx, shz_table* t, const char* who, const uint32_t* d
   memcpy(A.out_shift, hres.data() + cells * 5 + hist_words, (uint64_t)nq_all * 4);
   return SHZ_OK;
 }
-
-}  // namespace
 
 extern "C" int32_t shz_match_extents(shz_ctx* ctx, shz_table* t, const uint32_t* key32, const uint32_t* q_off,
                                      const uint64_t* query_off, uint32_t n_queries, uint32_t ncand, const uint32_t* cand_sid,

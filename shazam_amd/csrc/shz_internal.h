@@ -86,6 +86,8 @@ enum {
                      // windows | the rung of every slot)
   SHZ_WS_SC_CTL,     // ... first entry | count | offset of every (window, rung, channel), the total behind the offsets
   SHZ_WS_SC_KEY, SHZ_WS_SC_QO,   // ... the windows of one group: key32 and t1 - window start, window-major (rung-minor)
+                     // (shz_scan_extents' zone stage reuses the four SC slots once the window stage is done with them: zone
+                     // descriptors | hash_off; first | count | offset of every (zone, channel); key32 and t1 - lo of the zones)
   SHZ_WS_SP_PF, SHZ_WS_SP_PT,    // shz_speed.hip: the peaks of the clips (the extraction's, or a host list staged)
   SHZ_WS_SP_TAB,     // ... peak_off | time factors | frequency factors of the call
   SHZ_WS_SP_Q,       // ... first item | first clip of every query of a pass
@@ -242,6 +244,25 @@ int32_t shz_match_device(shz_ctx* ctx, shz_table* t, const uint32_t* d_key32, co
                          int32_t* out_delta, uint32_t* out_aligned, uint32_t* out_dedup, uint32_t* out_nres, uint32_t* out_nhash,
                          uint64_t* out_npairs);
 int32_t shz_match_ready(shz_ctx* ctx, shz_table* t, uint32_t topn);
+
+// ---- match extents on device columns the library owns (shz_extent.hip) ------------------------------
+struct ex_args {   // what every caller hands over (host arrays but the two query columns)
+  uint32_t n_queries, ncand;
+  const uint32_t* cand_sid;
+  const int32_t *cand_dlo, *cand_dhi;
+  const uint32_t* cand_n;
+  uint32_t *out_count, *out_q_first, *out_q_last, *out_t_first, *out_t_last, *out_hist, *out_shift;
+};
+// what every form refuses before anything is launched: the table's state (ex_state), its offsets (ex_table_limits: a part of
+// ex_check, for callers whose candidates do not exist yet when they must refuse), the candidates and outputs (ex_check; n > 0)
+int32_t ex_state(shz_ctx* ctx, shz_table* t, const char* who, uint32_t ncand);
+int32_t ex_table_limits(shz_ctx* ctx, shz_table* t, const char* who);
+int32_t ex_check(shz_ctx* ctx, shz_table* t, const char* who, const ex_args& A);
+// The one path of every entry point: d_key32 / d_q_off are device columns, query_off (host) their CSR, never decreasing; the
+// rest of A is checked (ex_check).  Workspace: the slots SHZ_WS_EX_*, SHZ_WS_SORT_A / _B and SHZ_WS_M1 / _M2 -- none of the
+// extraction's or the scan's.  The outputs are written only when the whole call succeeded; the stream is idle then.
+int32_t ex_device(shz_ctx* ctx, shz_table* t, const char* who, const uint32_t* d_key32, const uint32_t* d_q_off,
+                  const uint64_t* query_off, const ex_args& A);
 
 // ---- refusals the fused calls share (shz_recognize.hip) ------------------------------
 // clip0 (`name`): the CSR of the clips over n items (`what`) -- not NULL, from 0 to n_clips, never decreasing; clip_off: not

@@ -342,6 +342,76 @@ static int32_t sc_windows(shz_ctx* ctx, shz_table* t, const char* who, const sc_
   return SHZ_OK;
 }
 
+// ---- the plain scan: the body that shz_scan_batch and shz_scan_extents share, in its two halves -------------------------
+struct sc_plain {      // the arguments of shz_scan_batch
+  const int16_t* pcm;
+  const uint64_t* clip_off;
+  uint32_t n_clips;
+  const uint32_t* rec_clip0;
+  uint32_t n_recs, fs;
+  double amp_min;
+  uint32_t fan_value, window_frames, step_frames, topn, flags;
+  uint64_t* win_off;
+  uint32_t* out_sid;
+  int32_t* out_delta;
+  uint32_t *out_aligned, *out_dedup, *out_nres, *out_nhash;
+  uint64_t* out_npairs;
+  uint64_t cap_windows;
+  uint64_t* count;
+  float *ms_extract, *ms_window, *ms_match;
+};
+
+// everything the plain scan refuses, in its order, before the first launch.  *done: the call is over with SHZ_OK (no
+// recording, or no window) and nothing is to be launched
+static int32_t sc_plain_check(shz_ctx* ctx, shz_table* t, const char* who, const sc_plain& P, bool* done) {
+  *done = true;
+  if (P.ms_extract) *P.ms_extract = 0.f;
+  if (P.ms_window) *P.ms_window = 0.f;
+  if (P.ms_match) *P.ms_match = 0.f;
+  if (P.count) *P.count = 0;
+  SHZ_TRY(sc_check(ctx, who, P.flags, P.win_off, P.count, P.window_frames, P.step_frames));
+  if (P.fan_value < 1 || P.fan_value > 64) SHZ_FAIL(ctx, SHZ_E_INVALID, "fan_value must be in [1,64]");
+  SHZ_TRY(sc_check_recs(ctx, who, P.clip_off, P.n_clips, P.rec_clip0, P.n_recs, P.win_off));
+  if (P.n_recs == 0) return SHZ_OK;
+  SHZ_TRY(shz_match_ready(ctx, t, P.topn));
+  SHZ_TRY(sc_count_windows(ctx, who, P.clip_off, P.rec_clip0, P.n_recs, P.window_frames, P.step_frames, P.cap_windows, P.win_off,
+                           P.count, nullptr));
+  if (*P.count == 0) return SHZ_OK;
+  if (!P.out_sid || !P.out_delta || !P.out_aligned || !P.out_dedup || !P.out_nres) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: NULL buffer", who);
+  *done = false;
+  return SHZ_OK;
+}
+
+// extraction, window stage and match of a checked call.  hash_off (n_clips + 1, host) and *d_key / *d_t1 are the extraction's
+// columns: they lie in SHZ_WS_RQ_KEY / _T1, which neither the window stage nor the match reserves, so they are intact -- and the
+// stream idle (sc_windows) -- on return.  `timed` also when the caller times a stage of its own behind this
+static int32_t sc_plain_run(shz_ctx* ctx, shz_table* t, const char* who, const sc_plain& P, bool timed, uint64_t* hash_off,
+                            const uint32_t** d_key, const uint32_t** d_t1) {
+  SHZ_HIP(ctx, hipSetDevice(ctx->device));
+  if (timed) {
+    for (hipEvent_t& e : ctx->sc_ev)
+      if (!e) SHZ_HIP(ctx, hipEventCreate(&e));
+    SHZ_HIP(ctx, hipEventRecord(ctx->sc_ev[0], ctx->stream));
+  }
+  // 1) every clip fingerprinted once, into the library's own buffers
+  SHZ_TRY(shz_extract_owned(ctx, who, P.pcm, P.clip_off, P.n_clips, P.fs, P.amp_min, P.fan_value, P.flags & SHZ_PCM_DEVICE, hash_off,
+                            d_key, d_t1));
+  if (timed) SHZ_HIP(ctx, hipEventRecord(ctx->sc_ev[1], ctx->stream));
+  // 2) the window stage at unity: all recordings, one rung of factor 65536 over the extraction's own CSR.  A hash lies in
+  // at most ceil(window / step) windows; no query offset reaches window_frames
+  const uint32_t one = SP_S_ONE;
+  float win_ms = 0.f, match_ms = 0.f;
+  sc_slice S{P.rec_clip0, P.win_off, P.n_recs, 1, &one, hash_off, true, *d_key, *d_t1, hash_off[P.n_clips], P.window_frames,
+             P.step_frames, P.topn, P.flags & SHZ_MATCH_FULL_SORT, (int64_t)P.window_frames - 1,
+             ((uint64_t)P.window_frames + P.step_frames - 1) / P.step_frames, (ctx->debug & SHZ_DEBUG_SCAN_SMALL_GROUPS) != 0, P.out_sid,
+             P.out_aligned, P.out_dedup, P.out_nres, P.out_nhash, P.out_delta, P.out_npairs};
+  SHZ_TRY(sc_windows(ctx, t, who, S, timed, &win_ms, &match_ms));
+  if (P.ms_extract) SHZ_HIP(ctx, hipEventElapsedTime(P.ms_extract, ctx->sc_ev[0], ctx->sc_ev[1]));
+  if (P.ms_window) *P.ms_window = win_ms;
+  if (P.ms_match) *P.ms_match = match_ms;
+  return SHZ_OK;
+}
+
 extern "C" int32_t shz_scan_batch(shz_ctx* ctx, shz_table* t, const int16_t* pcm, const uint64_t* clip_off, uint32_t n_clips,
                                   const uint32_t* rec_clip0, uint32_t n_recs, uint32_t fs, double amp_min, uint32_t fan_value,
                                   uint32_t window_frames, uint32_t step_frames, uint32_t topn, uint32_t flags, uint64_t* win_off,
@@ -350,45 +420,16 @@ extern "C" int32_t shz_scan_batch(shz_ctx* ctx, shz_table* t, const int16_t* pcm
                                   uint64_t* count, float* ms_extract, float* ms_window, float* ms_match) {
   const char* who = "shz_scan_batch";
   if (!ctx || !t) return SHZ_E_INVALID;
-  if (ms_extract) *ms_extract = 0.f;
-  if (ms_window) *ms_window = 0.f;
-  if (ms_match) *ms_match = 0.f;
-  if (count) *count = 0;
+  const sc_plain P{pcm, clip_off, n_clips, rec_clip0, n_recs, fs, amp_min, fan_value, window_frames, step_frames, topn, flags, win_off,
+                   out_sid, out_delta, out_aligned, out_dedup, out_nres, out_nhash, out_npairs, cap_windows, count, ms_extract,
+                   ms_window, ms_match};
   // everything that can be refused is refused before the first launch
-  SHZ_TRY(sc_check(ctx, who, flags, win_off, count, window_frames, step_frames));
-  if (fan_value < 1 || fan_value > 64) SHZ_FAIL(ctx, SHZ_E_INVALID, "fan_value must be in [1,64]");
-  SHZ_TRY(sc_check_recs(ctx, who, clip_off, n_clips, rec_clip0, n_recs, win_off));
-  if (n_recs == 0) return SHZ_OK;
-  SHZ_TRY(shz_match_ready(ctx, t, topn));
-  SHZ_TRY(sc_count_windows(ctx, who, clip_off, rec_clip0, n_recs, window_frames, step_frames, cap_windows, win_off, count, nullptr));
-  if (*count == 0) return SHZ_OK;
-  if (!out_sid || !out_delta || !out_aligned || !out_dedup || !out_nres) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_scan_batch: NULL buffer");
-  SHZ_HIP(ctx, hipSetDevice(ctx->device));
-  const bool timed = ms_extract || ms_window || ms_match;
-  if (timed) {
-    for (hipEvent_t& e : ctx->sc_ev)
-      if (!e) SHZ_HIP(ctx, hipEventCreate(&e));
-    SHZ_HIP(ctx, hipEventRecord(ctx->sc_ev[0], ctx->stream));
-  }
-  // 1) every clip fingerprinted once, into the library's own buffers
+  bool done;
+  SHZ_TRY(sc_plain_check(ctx, t, who, P, &done));
+  if (done) return SHZ_OK;
   std::vector<uint64_t> hash_off((size_t)n_clips + 1, 0);
   const uint32_t *d_key = nullptr, *d_t1 = nullptr;
-  SHZ_TRY(shz_extract_owned(ctx, who, pcm, clip_off, n_clips, fs, amp_min, fan_value, flags & SHZ_PCM_DEVICE, hash_off.data(), &d_key,
-                            &d_t1));
-  if (timed) SHZ_HIP(ctx, hipEventRecord(ctx->sc_ev[1], ctx->stream));
-  // 2) the window stage at unity: all recordings, one rung of factor 65536 over the extraction's own CSR.  A hash lies in
-  // at most ceil(window / step) windows; no query offset reaches window_frames
-  const uint32_t one = SP_S_ONE;
-  float win_ms = 0.f, match_ms = 0.f;
-  sc_slice S{rec_clip0, win_off, n_recs, 1, &one, hash_off.data(), true, d_key, d_t1, hash_off[n_clips], window_frames, step_frames,
-             topn, flags & SHZ_MATCH_FULL_SORT, (int64_t)window_frames - 1, ((uint64_t)window_frames + step_frames - 1) / step_frames,
-             (ctx->debug & SHZ_DEBUG_SCAN_SMALL_GROUPS) != 0, out_sid, out_aligned, out_dedup, out_nres, out_nhash, out_delta,
-             out_npairs};
-  SHZ_TRY(sc_windows(ctx, t, who, S, timed, &win_ms, &match_ms));
-  if (ms_extract) SHZ_HIP(ctx, hipEventElapsedTime(ms_extract, ctx->sc_ev[0], ctx->sc_ev[1]));
-  if (ms_window) *ms_window = win_ms;
-  if (ms_match) *ms_match = match_ms;
-  return SHZ_OK;
+  return sc_plain_run(ctx, t, who, P, ms_extract || ms_window || ms_match, hash_off.data(), &d_key, &d_t1);
 }
 
 // The per-window answers of a scan folded into segments, on the host: "song X from window a to window b".
@@ -447,6 +488,264 @@ extern "C" int32_t shz_scan_timeline(const uint64_t* win_off, uint32_t n_recs, c
   }
   *count = n;
   return n > cap ? SHZ_E_CAPACITY : SHZ_OK;
+}
+
+// ---- scan extents: frame-accurate start and end of every segment --------------------------------------
+// Every segment of the timeline gets three ZONES of recording frames -- the whole play, its head and its tail, each with a
+// margin -- and every zone is one query of the extent pass (shz_extent.hip) with the segment's identity as its one candidate.
+// The zones' bounds, on the host: positions are formed in 64 bits and saturate far above every frame count (2^40), where
+// only the clamp to the recording's frames is left of them.
+extern "C" int32_t shz_scan_zones(const uint32_t* seg_rec, const uint32_t* seg_sid, const int64_t* seg_shift, const uint32_t* seg_first,
+                                  const uint32_t* seg_last, uint64_t n_segs, const uint64_t* frames, uint32_t n_recs,
+                                  uint32_t window_frames, uint32_t step_frames, uint32_t margin_frames, uint32_t* zone_lo,
+                                  uint32_t* zone_hi) {
+  if (window_frames == 0 || step_frames == 0) return SHZ_E_INVALID;
+  if (n_recs && !frames) return SHZ_E_INVALID;
+  for (uint32_t r = 0; r < n_recs; ++r)
+    if (frames[r] > 0xFFFFFFFFull) return SHZ_E_INVALID;
+  if (n_segs == 0) return SHZ_OK;
+  if (!seg_rec || !seg_sid || !seg_shift || !seg_first || !seg_last || !zone_lo || !zone_hi) return SHZ_E_INVALID;
+  for (uint64_t i = 0; i < n_segs; ++i) {
+    if (seg_rec[i] >= n_recs || seg_first[i] > seg_last[i]) return SHZ_E_INVALID;
+    if (i && (seg_rec[i] < seg_rec[i - 1] || (seg_rec[i] == seg_rec[i - 1] && seg_first[i] <= seg_last[i - 1]))) return SHZ_E_INVALID;
+  }
+  const uint64_t W = window_frames, M = margin_frames, top = 1ull << 40;
+  auto at = [&](uint32_t w) { return std::min<uint64_t>((uint64_t)w * step_frames, top); };
+  // the neighbours of the same identity inside a recording: windows ascend, so the nearest earlier one ends last and the
+  // nearest later one begins first.  prev[i] / next[i]: their indices, or n_segs
+  std::vector<uint64_t> prev((size_t)n_segs, n_segs), next((size_t)n_segs, n_segs);
+  for (uint64_t r0 = 0; r0 < n_segs;) {
+    uint64_t r1 = r0;
+    while (r1 < n_segs && seg_rec[r1] == seg_rec[r0]) ++r1;
+    std::vector<uint64_t> order;
+    for (uint64_t i = r0; i < r1; ++i) order.push_back(i);
+    std::stable_sort(order.begin(), order.end(), [&](uint64_t a, uint64_t b) {
+      return seg_sid[a] != seg_sid[b] ? seg_sid[a] < seg_sid[b] : seg_shift[a] < seg_shift[b];
+    });
+    for (size_t j = 1; j < order.size(); ++j) {
+      const uint64_t a = order[j - 1], b = order[j];
+      if (seg_sid[a] == seg_sid[b] && seg_shift[a] == seg_shift[b]) {
+        next[a] = b;
+        prev[b] = a;
+      }
+    }
+    r0 = r1;
+  }
+  for (uint64_t i = 0; i < n_segs; ++i) {
+    const uint64_t F = frames[seg_rec[i]], a = at(seg_first[i]), b = at(seg_last[i]);
+    uint64_t lo = a > M ? a - M : 0, hi = b + W + M;
+    if (prev[i] != n_segs) lo = std::max(lo, std::min(at(seg_last[prev[i]]) + W, a));
+    if (next[i] != n_segs) hi = std::min(hi, std::max(at(seg_first[next[i]]), b + W));
+    const uint64_t zl[3] = {lo, lo, b}, zh[3] = {hi, a + W, hi};
+    for (int z = 0; z < 3; ++z) {
+      const uint64_t l = std::min(zl[z], F), h = std::min(zh[z], F);
+      zone_lo[3 * i + z] = (uint32_t)l;
+      zone_hi[3 * i + z] = (uint32_t)std::max(l, h);
+    }
+  }
+  return SHZ_OK;
+}
+
+struct sc_zone {       // one zone of the zone stage; the entry behind the last one holds the total
+  uint64_t item0;      // its first (zone, channel) item: the channels of the zones in front of it
+  uint64_t clip0;      // the first clip of its recording: channel c is segment clip0 + c of the hashes' CSR
+  uint32_t lo, hi;     // recording frames [lo, hi)
+  uint32_t nch, pad;
+};
+
+// per (zone, channel): where the zone's hashes begin in the channel's list, and how many they are.  Zones have arbitrary
+// (recording, lo, hi): nothing here is derived from a window number.  (64-bit compares, as sc_bounds_kernel)
+__global__ __launch_bounds__(SC_THREADS) void sc_zone_bounds_kernel(const sc_zone* __restrict__ zones, uint32_t nz, uint64_t n_items,
+                                                                    const uint64_t* __restrict__ hoff, const uint32_t* __restrict__ t1,
+                                                                    uint64_t* __restrict__ first, uint64_t* __restrict__ cnt) {
+  const uint64_t i = (uint64_t)blockIdx.x * SC_THREADS + threadIdx.x;
+  if (i >= n_items) return;
+  uint32_t l = 0, h = nz;   // the last zone whose first item is <= i (every zone has a channel: its recording has a window)
+  while (l + 1 < h) {
+    const uint32_t mid = l + ((h - l) >> 1);
+    if (zones[mid].item0 <= i) l = mid; else h = mid;
+  }
+  const sc_zone Z = zones[l];
+  const uint64_t c = i - Z.item0;
+  if (c >= Z.nch) {   // (never: the host builds item0 from nch)
+    first[i] = 0;
+    cnt[i] = 0;
+    return;
+  }
+  const uint64_t a = hoff[Z.clip0 + c], b = hoff[Z.clip0 + c + 1];
+  const uint64_t p = sc_lower_bound(t1, a, b, Z.lo);
+  const uint64_t q = Z.hi > Z.lo ? sc_lower_bound(t1, p, b, Z.hi) : p;
+  first[i] = p;
+  cnt[i] = q - p;
+}
+
+// one workgroup per zone: its channels' ranges, one behind the other, to offs[item] of the columns (offs: exclusive scan of
+// the counts, the total behind it): key32 and t1 - lo
+__global__ __launch_bounds__(SC_THREADS) void sc_zone_gather_kernel(const sc_zone* __restrict__ zones, const uint64_t* __restrict__ first,
+                                                                    const uint64_t* __restrict__ offs, uint64_t cap,
+                                                                    const uint32_t* __restrict__ key, const uint32_t* __restrict__ t1,
+                                                                    uint32_t* __restrict__ out_key, uint32_t* __restrict__ out_qo) {
+  const sc_zone Z = zones[blockIdx.x];
+  for (uint32_t c = 0; c < Z.nch; ++c) {
+    const uint64_t p = Z.item0 + c;
+    const uint64_t src = first[p], dst = offs[p], n = offs[p + 1] - offs[p];
+    if (dst + n > cap) return;   // (uniform; the host sizes the columns from the same offsets, so this never holds)
+    for (uint64_t i = threadIdx.x; i < n; i += SC_THREADS) {
+      out_key[dst + i] = key[src + i];
+      out_qo[dst + i] = t1[src + i] - Z.lo;
+    }
+  }
+}
+
+// The zone stage: cuts the extraction's hash lists (d_key / d_t1, CSR hash_off over the clips, all of them alive in
+// SHZ_WS_RQ_KEY / _T1) into the nz zones and leaves their columns on the device, query_off (nz + 1, host) their CSR.  It
+// runs behind sc_windows, which returns with the stream idle and is done with its workspace: the slots SHZ_WS_SC_JOBS,
+// _CTL, _KEY and _QO are REUSED here (descriptors | hash_off; first | count | offsets; the two columns) instead of adding
+// slots that would only ever be live when those are dead.  The extent pass behind it reserves none of them.  The stream is
+// idle on return.
+static int32_t sc_zone_stage(shz_ctx* ctx, const char* who, const uint32_t* rec_clip0, uint32_t n_clips, const uint64_t* hash_off,
+                             const uint32_t* d_key, const uint32_t* d_t1, const uint32_t* seg_rec, uint64_t n_segs,
+                             const uint32_t* zone_lo, const uint32_t* zone_hi, uint64_t* query_off, const uint32_t** d_zk,
+                             const uint32_t** d_zq) {
+  const uint64_t nz = 3 * n_segs, total = hash_off[n_clips];
+  const uint64_t zone_bytes = (nz + 1) * sizeof(sc_zone), hoff_bytes = ((uint64_t)n_clips + 1) * 8;
+  std::vector<char> block(zone_bytes + hoff_bytes);
+  sc_zone* hz = (sc_zone*)block.data();
+  uint64_t n_items = 0;
+  for (uint64_t z = 0; z < nz; ++z) {
+    const uint32_t r = seg_rec[z / 3], nch = rec_clip0[r + 1] - rec_clip0[r];
+    hz[z] = sc_zone{n_items, rec_clip0[r], zone_lo[z], zone_hi[z], nch, 0};
+    n_items += nch;
+  }
+  hz[nz] = sc_zone{n_items, n_clips, 0, 0, 0, 0};
+  memcpy(block.data() + zone_bytes, hash_off, hoff_bytes);
+  void *d_blk, *d_ctl, *d_k, *d_q;
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SC_JOBS, block.size(), &d_blk));
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SC_CTL, (3 * n_items + 1) * 8, &d_ctl));
+  uint64_t *d_first = (uint64_t*)d_ctl, *d_cnt = d_first + n_items, *d_offs = d_cnt + n_items;   // d_offs[n_items] = the total
+  std::vector<uint64_t> offs((size_t)n_items + 1, 0);
+  if (total && n_items) {   // (without hashes every zone is empty)
+    SHZ_HIP(ctx, shz_memcpy(ctx, d_blk, block.data(), block.size(), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(sc_zone_bounds_kernel, dim3((unsigned)((n_items + SC_THREADS - 1) / SC_THREADS)), dim3(SC_THREADS), 0, ctx->stream,
+                       (const sc_zone*)d_blk, (uint32_t)nz, n_items, (const uint64_t*)((char*)d_blk + zone_bytes), d_t1, d_first, d_cnt);
+    SHZ_HIP(ctx, hipGetLastError());
+    SHZ_TRY(shz_scan_u64(ctx, d_cnt, d_offs, n_items, d_offs + n_items));
+    SHZ_HIP(ctx, shz_memcpy(ctx, offs.data(), d_offs, (n_items + 1) * 8, hipMemcpyDeviceToHost));
+    SHZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  const uint64_t m = offs[n_items];
+  if (m > total * nz)   // a hash lies at most once in a zone
+    SHZ_FAIL(ctx, SHZ_E_STATE, "%s: %llu zone entries from %llu hashes in %llu zones", who, (unsigned long long)m,
+             (unsigned long long)total, (unsigned long long)nz);
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SC_KEY, m * 4 + 64, &d_k));
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SC_QO, m * 4 + 64, &d_q));
+  if (m) {
+    hipLaunchKernelGGL(sc_zone_gather_kernel, dim3((unsigned)nz), dim3(SC_THREADS), 0, ctx->stream, (const sc_zone*)d_blk,
+                       (const uint64_t*)d_first, (const uint64_t*)d_offs, m, d_key, d_t1, (uint32_t*)d_k, (uint32_t*)d_q);
+    SHZ_HIP(ctx, hipGetLastError());
+    SHZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  for (uint64_t z = 0; z <= nz; ++z) query_off[z] = offs[hz[z].item0];
+  *d_zk = (const uint32_t*)d_k;
+  *d_zq = (const uint32_t*)d_q;
+  return SHZ_OK;
+}
+
+extern "C" int32_t shz_scan_extents(shz_ctx* ctx, shz_table* t, const int16_t* pcm, const uint64_t* clip_off, uint32_t n_clips,
+                                    const uint32_t* rec_clip0, uint32_t n_recs, uint32_t fs, double amp_min, uint32_t fan_value,
+                                    uint32_t window_frames, uint32_t step_frames, uint32_t topn, uint32_t flags, uint32_t min_aligned,
+                                    uint32_t max_gap, uint32_t margin_frames, uint32_t d_tol, uint64_t* win_off, uint32_t* out_sid,
+                                    int32_t* out_delta, uint32_t* out_aligned, uint32_t* out_dedup, uint32_t* out_nres,
+                                    uint32_t* out_nhash, uint64_t* out_npairs, uint64_t cap_windows, uint64_t* count,
+                                    uint32_t* seg_rec, uint32_t* seg_sid, int64_t* seg_shift, uint32_t* seg_first, uint32_t* seg_last,
+                                    uint32_t* seg_hits, uint32_t* seg_best, uint64_t cap_segs, uint64_t* seg_count, uint32_t* zone_lo,
+                                    uint32_t* zone_hi, uint32_t* zone_count, uint32_t* zone_q_first, uint32_t* zone_q_last,
+                                    uint32_t* zone_t_first, uint32_t* zone_t_last, uint32_t* zone_shift, uint32_t* zone_hist,
+                                    float* ms_extract, float* ms_window, float* ms_match, float* ms_extent) {
+  const char* who = "shz_scan_extents";
+  if (!ctx || !t) return SHZ_E_INVALID;
+  if (ms_extent) *ms_extent = 0.f;
+  if (seg_count) *seg_count = 0;
+  const sc_plain P{pcm, clip_off, n_clips, rec_clip0, n_recs, fs, amp_min, fan_value, window_frames, step_frames, topn, flags, win_off,
+                   out_sid, out_delta, out_aligned, out_dedup, out_nres, out_nhash, out_npairs, cap_windows, count, ms_extract,
+                   ms_window, ms_match};
+  // everything that can be refused is refused before the first launch: the plain scan's refusals, then this call's own
+  bool done;
+  SHZ_TRY(sc_plain_check(ctx, t, who, P, &done));
+  if (d_tol > 31) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: d_tol must be in [0, 31], got %u", who, d_tol);
+  if (margin_frames >= (1u << 20)) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: margin_frames must be below 2^20, got %u", who, margin_frames);
+  if (!seg_count) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: seg_count is NULL", who);
+  if (cap_segs && (!seg_rec || !seg_sid || !seg_shift || !seg_first || !seg_last || !seg_hits || !seg_best))
+    SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: NULL segment array", who);
+  if (cap_segs && (!zone_lo || !zone_hi || !zone_count || !zone_q_first || !zone_q_last || !zone_t_first || !zone_t_last || !zone_shift))
+    SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: NULL zone array", who);
+  if (done) return SHZ_OK;   // no recording, or no window: no segment
+  SHZ_TRY(ex_state(ctx, t, who, 1));
+  SHZ_TRY(ex_table_limits(ctx, t, who));
+  // 1) + 2) the plain scan; the extraction's columns stay where they are
+  const bool timed = ms_extract || ms_window || ms_match || ms_extent;
+  std::vector<uint64_t> hash_off((size_t)n_clips + 1, 0);
+  const uint32_t *d_key = nullptr, *d_t1 = nullptr;
+  SHZ_TRY(sc_plain_run(ctx, t, who, P, timed, hash_off.data(), &d_key, &d_t1));
+  // 3) the timeline, on the host
+  const int32_t rc = shz_scan_timeline(win_off, n_recs, out_sid, out_delta, out_aligned, out_nres, topn, step_frames, min_aligned, max_gap,
+                                       seg_rec, seg_sid, seg_shift, seg_first, seg_last, seg_hits, seg_best, cap_segs, seg_count);
+  const uint64_t n_segs = *seg_count;
+  if (rc == SHZ_E_CAPACITY)
+    SHZ_FAIL(ctx, SHZ_E_CAPACITY, "%s: %llu segments, room for %llu", who, (unsigned long long)n_segs, (unsigned long long)cap_segs);
+  if (rc != SHZ_OK) SHZ_FAIL(ctx, rc, "%s: the timeline refused the scan's own arrays", who);
+  if (n_segs == 0) return SHZ_OK;
+  if (3 * n_segs >= (1ull << 31)) SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "%s: %llu segments in one call", who, (unsigned long long)n_segs);
+  // 4) the zones and their candidates, on the host
+  const uint64_t nz = 3 * n_segs;
+  std::vector<uint64_t> frames((size_t)n_recs, 0);
+  for (uint32_t r = 0; r < n_recs; ++r)
+    for (uint32_t c = rec_clip0[r]; c < rec_clip0[r + 1]; ++c)
+      frames[r] = std::max<uint64_t>(frames[r], shz_frame_count_hop(clip_off[c + 1] - clip_off[c], ctx->hop));
+  std::vector<uint32_t> z_lo((size_t)nz), z_hi((size_t)nz), c_sid((size_t)nz), c_n((size_t)nz);
+  std::vector<int32_t> c_dlo((size_t)nz), c_dhi((size_t)nz);
+  if (shz_scan_zones(seg_rec, seg_sid, seg_shift, seg_first, seg_last, n_segs, frames.data(), n_recs, window_frames, step_frames,
+                     margin_frames, z_lo.data(), z_hi.data()) != SHZ_OK)
+    SHZ_FAIL(ctx, SHZ_E_STATE, "%s: the zones refused the timeline's own segments", who);
+  for (uint64_t z = 0; z < nz; ++z) {
+    // off - (t1 - lo) = (off - t1) + lo, and off - t1 is the shift.  Every difference of a table offset < 2^31 and a query
+    // offset < 2^20 fits 32 bits: a range that does not meet them holds no pair, the others lose nothing at the clamp
+    const int64_t d = seg_shift[z / 3] + (int64_t)z_lo[z], lo = d - (int64_t)d_tol, hi = d + (int64_t)d_tol;
+    const bool none = lo > INT32_MAX || hi < INT32_MIN;
+    c_sid[z] = seg_sid[z / 3];
+    c_dlo[z] = none ? 0 : (int32_t)std::max<int64_t>(lo, INT32_MIN);
+    c_dhi[z] = none ? 0 : (int32_t)std::min<int64_t>(hi, INT32_MAX);
+    c_n[z] = none ? 0u : 1u;
+  }
+  // 5) the zone stage, 6) the extent pass on its columns.  (events 2 and 3 are free again: the window stage is over)
+  if (timed) SHZ_HIP(ctx, hipEventRecord(ctx->sc_ev[2], ctx->stream));
+  std::vector<uint64_t> query_off((size_t)nz + 1, 0);
+  const uint32_t *d_zk = nullptr, *d_zq = nullptr;
+  SHZ_TRY(sc_zone_stage(ctx, who, rec_clip0, n_clips, hash_off.data(), d_key, d_t1, seg_rec, n_segs, z_lo.data(), z_hi.data(),
+                        query_off.data(), &d_zk, &d_zq));
+  const ex_args A{(uint32_t)nz, 1, c_sid.data(), c_dlo.data(), c_dhi.data(), c_n.data(), zone_count, zone_q_first, zone_q_last,
+                  zone_t_first, zone_t_last, zone_hist, zone_shift};
+  SHZ_TRY(ex_check(ctx, t, who, A));
+  const int32_t rx = ex_device(ctx, t, who, d_zk, d_zq, query_off.data(), A);
+  if (rx != SHZ_OK) {
+    (void)hipStreamSynchronize(ctx->stream);   // (a refused pass may have queued work that reads the columns)
+    return rx;
+  }
+  if (timed) {
+    SHZ_HIP(ctx, hipEventRecord(ctx->sc_ev[3], ctx->stream));
+    SHZ_HIP(ctx, hipEventSynchronize(ctx->sc_ev[3]));
+    if (ms_extent) SHZ_HIP(ctx, hipEventElapsedTime(ms_extent, ctx->sc_ev[2], ctx->sc_ev[3]));
+  }
+  // the pass has written its outputs: the zones beside them, query frames -> recording frames
+  for (uint64_t z = 0; z < nz; ++z) {
+    zone_lo[z] = z_lo[z];
+    zone_hi[z] = z_hi[z];
+    if (zone_count[z]) {
+      zone_q_first[z] += z_lo[z];
+      zone_q_last[z] += z_lo[z];
+    }
+  }
+  return SHZ_OK;
 }
 
 // ---- scanning at an unknown speed, or at unknown tempo and pitch -------------------------------

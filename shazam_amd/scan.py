@@ -137,7 +137,7 @@ def _scan_warp_windows(run, tl, pl, t16, f16, row, search):
 @takes_delta_tol(lambda *a, **k: (k["db"] if "db" in k else a[1]).ctx)
 def scan_windows(recordings, db, Fs: int = 44100, window_seconds: float = 5, step_seconds: float = 1, topn: int = TOPN,
                  resample_to: int = None, full_sort: bool = False, speeds=None, tempos=None, pitches=None, warps=None,
-                 search: str = "grid"):
+                 search: str = "grid", _extents: dict = None):
     """Every window of every recording matched in one library call.  recordings: 1-D int16 arrays, or lists of channels as in
     recognize_batch.  Returns a dict: the arrays of Table.match over all windows, recording-major (sid, delta, aligned, dedup
     [n_windows, topn]; nres, nhash, npairs [n_windows]), plus win_off (CSR of the windows over the recordings), frames (F_r
@@ -182,6 +182,17 @@ def scan_windows(recordings, db, Fs: int = 44100, window_seconds: float = 5, ste
             call = lambda a16, b16, select: ctx.scan_warps(table, pcm, off, first, wf, sf, a16, b16, select, **k)   # noqa: E731
             res, win_off, ms = _scan_warp_windows(call, tl, pl, t16, f16, row, search)
             return res, win_off, tuple(float(m) for m in ms)
+    elif _extents is not None:   # scan(extents=True): the timeline and the extent pass inside the same library call
+        if speeds is not None:
+            raise ValueError("extents=True takes the plain scan: not with speeds=")
+
+        def run(table, pcm, off, first, wf, sf, fs, **k):
+            ms_ = _extents["margin_seconds"]
+            margin = wf if ms_ is None else max(0, int(round(float(ms_) * fs / hop)))
+            res, win_off, seg, zone, ms = ctx.scan_extents(table, pcm, off, first, wf, sf, _extents["min_aligned"], _extents["max_gap"],
+                                                           margin, ctx.vote_tolerance, fs=fs, **k)
+            res.update(segments=seg, zones=zone, margin_frames=margin)
+            return res, win_off, ms
     elif speeds is None:
         run = ctx.scan_batch
     else:
@@ -233,7 +244,8 @@ def _segment(db, w, seg, i):
 @takes_delta_tol(lambda *a, **k: (k["db"] if "db" in k else a[1]).ctx)
 def scan(recordings, db, Fs: int = 44100, window_seconds: float = 5, step_seconds: float = 1, topn: int = TOPN,
          resample_to: int = None, min_aligned: int = 20, max_gap: int = 1, speeds=None, shift_tol: int = None, rung_tol: int = 1,
-         tempos=None, pitches=None, warps=None, search: str = "grid", tempo_tol: int = None, pitch_tol: int = None):
+         tempos=None, pitches=None, warps=None, search: str = "grid", tempo_tol: int = None, pitch_tol: int = None,
+         extents: bool = False, margin_seconds: float = None):
     """The timeline of every recording: a list (per recording) of segments, each a dict with song_id, song_name,
     start_seconds / end_seconds (the span of the segment's windows in the recording, the last window's end clipped to the
     recording's), offset_seconds (the position in the song at the segment's start: align_matches' formula,
@@ -255,8 +267,23 @@ def scan(recordings, db, Fs: int = 44100, window_seconds: float = 5, step_second
     warped with the TEMPO factor within shift_tol frames (shz_scan_timeline_warps; None: WARP_SHIFT_TOL).  It carries what a
     speed scan's segment carries, with "tempo" and "pitch" (the pair its hits chose most often, as floats) and "tempo_fit" in
     place of "speed" and "speed_fit".
-    delta_tol= (keyword): the vote tolerance in offset bins while the call runs (Context.tolerance); None: the context's."""
+    delta_tol= (keyword): the vote tolerance in offset bins while the call runs (Context.tolerance); None: the context's.
+    extents=True (the plain scan only: ValueError with speeds=, tempos=, pitches=, warps= or another search;
+    NotImplementedError on a sharded table): start_seconds / end_seconds are only as fine as the windows, so every segment also
+    says where its aligned hashes really lie (shz_scan_extents, DESIGN.md 3.7l: the extent pass on three zones of the
+    recording -- the whole play, its head and its tail, each widened by margin_seconds; None: one window -- at the call's
+    tolerance, inside the same library call).  Every key above keeps its value; a segment gains play_start_seconds /
+    play_end_seconds (the first / last bucket of the head / tail zone's histogram that holds extent.DENSE_MIN_COUNT pairs,
+    the end clipped to the zone's; without such a bucket the zone's first / last pair; without a pair start_seconds /
+    end_seconds), play_first_frame / play_last_frame (the first pair of the head zone, the last of the tail zone, in recording
+    frames; None without a pair), song_start_seconds / song_end_seconds (the span of the whole play's pairs in the song,
+    converted as offset_seconds; None without a pair), pairs (their number), extent_hist / extent_shift / extent_lo (their
+    histogram over the whole-play zone, which starts at recording frame extent_lo)."""
     from . import OFFSET_SECS
+    if extents:
+        if speeds is not None or tempos is not None or pitches is not None or warps is not None or search != "grid":
+            raise ValueError("extents=True takes the plain scan: warped extents are not implemented (DESIGN.md 8)")
+        return _scan_extents(recordings, db, Fs, window_seconds, step_seconds, topn, resample_to, min_aligned, max_gap, margin_seconds)
     if tempos is not None or pitches is not None or warps is not None or search != "grid":
         if speeds is not None:
             raise ValueError("speeds= is one factor for time and frequency: it excludes tempos=, pitches= and warps=")
@@ -275,6 +302,39 @@ def scan(recordings, db, Fs: int = 44100, window_seconds: float = 5, step_second
         out[int(seg["rec"][i])].append(dict(
             _segment(db, w, seg, i),
             **{OFFSET_SECS: round(float(shift + first * w["step_frames"]) / DEFAULT_FS * w["hop"], 5), "shift": shift}))
+    return out
+
+
+def _scan_extents(recordings, db, Fs, window_seconds, step_seconds, topn, resample_to, min_aligned, max_gap, margin_seconds):
+    from . import OFFSET_SECS
+    from .extent import dense_span
+    w = scan_windows(recordings, db, Fs, window_seconds, step_seconds, topn, resample_to,
+                     _extents=dict(min_aligned=int(min_aligned), max_gap=int(max_gap), margin_seconds=margin_seconds))
+    seg, zone = w["segments"], w["zones"]
+    hop, fs = w["hop"], w["fs"]
+    secs = lambda frame: round(frame * hop / fs, 5)                              # noqa: E731  (as _segment converts)
+    song_secs = lambda frame: round(float(frame) / DEFAULT_FS * hop, 5)          # noqa: E731  (as offset_seconds converts)
+    out = [[] for _ in range(len(w["frames"]))]
+    for i in range(len(seg["rec"])):
+        first, shift = int(seg["first"][i]), int(seg["shift"][i])
+        d = dict(_segment(db, w, seg, i),
+                 **{OFFSET_SECS: round(float(shift + first * w["step_frames"]) / DEFAULT_FS * hop, 5), "shift": shift})
+        z = {k: [int(x) for x in zone[k][i]] for k in _ffi.ZONE_FIELDS}          # [whole, head, tail] of every field
+        d["play_start_seconds"], d["play_end_seconds"] = d["start_seconds"], d["end_seconds"]
+        d["play_first_frame"] = d["play_last_frame"] = None
+        if z["count"][1]:
+            span = dense_span(zone["hist"][i, 1], z["shift"][1])
+            d["play_start_seconds"] = secs(z["q_first"][1] if span is None else z["lo"][1] + span[0])
+            d["play_first_frame"] = z["q_first"][1]
+        if z["count"][2]:
+            span = dense_span(zone["hist"][i, 2], z["shift"][2])
+            d["play_end_seconds"] = secs(z["q_last"][2] + 1 if span is None else min(z["lo"][2] + span[1], z["hi"][2]))
+            d["play_last_frame"] = z["q_last"][2]
+        some = z["count"][0] > 0
+        d.update(song_start_seconds=song_secs(z["t_first"][0]) if some else None,
+                 song_end_seconds=song_secs(z["t_last"][0] + 1) if some else None,
+                 pairs=z["count"][0], extent_hist=zone["hist"][i, 0].copy(), extent_shift=z["shift"][0], extent_lo=z["lo"][0])
+        out[int(seg["rec"][i])].append(d)
     return out
 
 
