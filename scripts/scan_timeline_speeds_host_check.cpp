@@ -1,5 +1,5 @@
-// Stand-alone host check of the scan's host-only functions (no GPU is touched): shz_scan_window_count, shz_scan_timeline and
-// shz_scan_timeline_speeds on hand-built arrays, meant to be built with the host sanitizers and run on a CPU machine:
+// Stand-alone host check of the scan's host-only functions (no GPU is touched): shz_scan_window_count, shz_scan_timeline,
+// shz_scan_timeline_speeds and shz_scan_timeline_warps on hand-built arrays, meant to be built with the host sanitizers and run on a CPU machine:
 //   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -fPIC -ffp-contract=off -Xarch_host -fsanitize=address,undefined \
 //         -Xarch_host -fno-omit-frame-pointer -c shazam_amd/csrc/shz_scan.hip -o shz_scan.san.o      (shz_speed.hip likewise)
 //   clang++ -std=c++17 -O1 -g -fsanitize=address,undefined -c scripts/scan_timeline_speeds_host_check.cpp -o main.o
@@ -75,6 +75,46 @@ int main() {
                                 2, s3.rec.data(), s3.sid.data(), s3.first.data(), s3.last.data(), s3.hits.data(), s3.best.data(),
                                 s3.p0.data(), s3.p1.data(), s3.rung.data(), 8, &count);
   EXPECT(rc == SHZ_OK && count >= 3 && s3.rec[0] == 0 && s3.rec[1] == 2);
+  // the warps' timeline with the diagonal ladder as both tables: neighbouring rungs (92 apart) are in tolerance, so the same two
+  // segments come out
+  for (uint64_t cap = 0; cap <= 3; ++cap) {
+    segs s(cap);
+    rc = shz_scan_timeline_warps(win_off, 1, sid.data(), delta.data(), aligned.data(), nres.data(), best.data(), topn, 22, ladder, ladder,
+                                 9, 40, 1, 92, 92, 2, s.rec.data(), s.sid.data(), s.first.data(), s.last.data(), s.hits.data(),
+                                 s.best.data(), s.p0.data(), s.p1.data(), s.rung.data(), cap, &count);
+    EXPECT(count == 2 && rc == (cap < 2 ? SHZ_E_CAPACITY : SHZ_OK));
+    if (cap >= 1) EXPECT(s.sid[0] == 2 && s.first[0] == 0 && s.last[0] == 9 && s.hits[0] == 10 && s.p0[0] == -23 && s.p1[0] == 181 && s.rung[0] == 7);
+    if (cap >= 2) EXPECT(s.sid[1] == 4 && s.first[1] == 10 && s.last[1] == 19 && s.p0[1] == -58 && s.p1[1] == 134 && s.rung[1] == 1);
+  }
+  // one rung apart is 92: at a tolerance of 91 every change of rung opens a segment
+  {
+    segs s(n);
+    rc = shz_scan_timeline_warps(win_off, 1, sid.data(), delta.data(), aligned.data(), nres.data(), best.data(), topn, 22, ladder, ladder,
+                                 9, 40, 1, 91, 92, 2, s.rec.data(), s.sid.data(), s.first.data(), s.last.data(), s.hits.data(),
+                                 s.best.data(), s.p0.data(), s.p1.data(), s.rung.data(), n, &count);
+    EXPECT(rc == SHZ_OK && count == 11 && s.hits[0] == 10 && s.hits[1] == 1 && s.rung[1] == 0 && s.rung[2] == 1);
+  }
+  // SHZ_SCAN_NO_WARP on a window that is no hit: the warps' timeline reads best for hits only and bridges the gap, the speeds'
+  // checks every window
+  {
+    std::vector<uint32_t> nres1(nres), best1(best);
+    nres1[5] = 0;
+    best1[5] = SHZ_SCAN_NO_WARP;
+    segs s(2);
+    rc = shz_scan_timeline_warps(win_off, 1, sid.data(), delta.data(), aligned.data(), nres1.data(), best1.data(), topn, 22, ladder,
+                                 ladder, 9, 40, 1, 92, 92, 2, s.rec.data(), s.sid.data(), s.first.data(), s.last.data(), s.hits.data(),
+                                 s.best.data(), s.p0.data(), s.p1.data(), s.rung.data(), 2, &count);
+    EXPECT(rc == SHZ_OK && count == 2 && s.first[0] == 0 && s.last[0] == 9 && s.hits[0] == 9 && s.rung[0] == 7 && s.hits[1] == 10);
+    rc = shz_scan_timeline_speeds(win_off, 1, sid.data(), delta.data(), aligned.data(), nres1.data(), best1.data(), topn, 22, ladder, 9,
+                                  40, 1, 1, 2, s.rec.data(), s.sid.data(), s.first.data(), s.last.data(), s.hits.data(), s.best.data(),
+                                  s.p0.data(), s.p1.data(), s.rung.data(), 2, &count);
+    EXPECT(rc == SHZ_E_INVALID);
+    nres1[5] = 1;   // a hit: now the entry is refused
+    rc = shz_scan_timeline_warps(win_off, 1, sid.data(), delta.data(), aligned.data(), nres1.data(), best1.data(), topn, 22, ladder,
+                                 ladder, 9, 40, 1, 92, 92, 2, s.rec.data(), s.sid.data(), s.first.data(), s.last.data(), s.hits.data(),
+                                 s.best.data(), s.p0.data(), s.p1.data(), s.rung.data(), 2, &count);
+    EXPECT(rc == SHZ_E_INVALID);
+  }
   // the plain timeline and the window count on the same arrays
   std::vector<uint32_t> a(n), b(n), c(n), d(n), e(n);
   std::vector<int64_t> sh(n);

@@ -1113,31 +1113,51 @@ SEGMENT_FIELDS = (("rec", np.uint32), ("sid", np.uint32), ("shift", np.int64), (
                   ("hits", np.uint32), ("best", np.uint32))
 
 
-def scan_timeline_raw(win_off, sid, delta, aligned, nres, step_frames, min_aligned, max_gap=1, cap=0):
-    """One shz_scan_timeline as it is (host only): (rc, segments, count) with room for `cap` segments."""
+def _timeline_raw(fn, fields, win_off, sid, delta, aligned, nres, step_frames, min_aligned, max_gap, cap, best=None, tables=(),
+                  tols=()):
+    """One call of a timeline fold as it is (host only): (rc, segments, count) with room for `cap` segments.  best, tables and
+    tols are what the variants' folds take beside the plain one's arguments."""
     wo = np.ascontiguousarray(win_off, np.uint64)
     sid, delta, aligned = (np.ascontiguousarray(a, d) for a, d in ((sid, np.uint32), (delta, np.int32), (aligned, np.uint32)))
     nres = np.ascontiguousarray(nres, np.uint32)
+    tabs = [np.ascontiguousarray(t, np.uint32) for t in tables]
     nw = len(nres)
     topn = 1 if sid.ndim == 1 else int(sid.shape[1])
     assert sid.shape == delta.shape == aligned.shape and sid.size == nw * topn and int(wo[-1]) - int(wo[0]) <= nw
-    seg = {k: np.zeros(int(cap), d) for k, d in SEGMENT_FIELDS}
+    assert all(len(t) == len(tabs[0]) for t in tabs)
+    variant, ladder = [], []
+    if best is not None:
+        best = np.ascontiguousarray(best, np.uint32)
+        assert len(best) == nw
+        variant, ladder = [ptr(best)], [t.ctypes.data_as(u32p) for t in tabs] + [len(tabs[0])]
+    seg = {k: np.zeros(int(cap), d) for k, d in fields}
     cnt = C.c_uint64()
-    rc = lib().shz_scan_timeline(wo.ctypes.data_as(u64p), len(wo) - 1, ptr(sid), ptr(delta), ptr(aligned), ptr(nres), topn,
-                                 int(step_frames), int(min_aligned), int(max_gap),
-                                 *[ptr(seg[k]) if cap else None for k, _ in SEGMENT_FIELDS], int(cap), C.byref(cnt))
+    rc = fn(wo.ctypes.data_as(u64p), len(wo) - 1, ptr(sid), ptr(delta), ptr(aligned), ptr(nres), *variant, topn, int(step_frames),
+            *ladder, int(min_aligned), int(max_gap), *[int(x) for x in tols], *[ptr(seg[k]) if cap else None for k, _ in fields],
+            int(cap), C.byref(cnt))
     return rc, seg, int(cnt.value)
+
+
+def _timeline(raw, name, *args) -> dict:
+    """The two calls of a timeline fold: one for the count, one with that much room."""
+    rc, seg, n = raw(*args, 0)
+    if rc == E_CAPACITY:
+        rc, seg, n = raw(*args, n)
+    if rc != OK:
+        raise ShzError(rc, name + ": bad arguments")
+    return seg
+
+
+def scan_timeline_raw(win_off, sid, delta, aligned, nres, step_frames, min_aligned, max_gap=1, cap=0):
+    """One shz_scan_timeline as it is (host only): (rc, segments, count) with room for `cap` segments."""
+    return _timeline_raw(lib().shz_scan_timeline, SEGMENT_FIELDS, win_off, sid, delta, aligned, nres, step_frames, min_aligned,
+                         max_gap, cap)
 
 
 def scan_timeline(win_off, sid, delta, aligned, nres, step_frames, min_aligned, max_gap=1) -> dict:
     """shz_scan_timeline (host only, two calls): the rank-0 answers of a scan folded into segments -- arrays rec, sid, shift
     (song frame - recording frame), first / last (windows of the recording), hits, best (largest aligned count)."""
-    rc, seg, n = scan_timeline_raw(win_off, sid, delta, aligned, nres, step_frames, min_aligned, max_gap, 0)
-    if rc == E_CAPACITY:
-        rc, seg, n = scan_timeline_raw(win_off, sid, delta, aligned, nres, step_frames, min_aligned, max_gap, n)
-    if rc != OK:
-        raise ShzError(rc, "shz_scan_timeline: bad arguments")
-    return seg
+    return _timeline(scan_timeline_raw, "shz_scan_timeline", win_off, sid, delta, aligned, nres, step_frames, min_aligned, max_gap)
 
 
 ZONE_FIELDS = ("lo", "hi", "count", "q_first", "q_last", "t_first", "t_last", "shift")
@@ -1172,20 +1192,8 @@ SPEED_SEGMENT_FIELDS = (("rec", np.uint32), ("sid", np.uint32), ("first", np.uin
 def scan_timeline_speeds_raw(win_off, sid, delta, aligned, nres, best, step_frames, speeds, min_aligned, max_gap=1, rung_tol=1,
                              shift_tol=2, cap=0):
     """One shz_scan_timeline_speeds as it is (host only): (rc, segments, count) with room for `cap` segments."""
-    wo = np.ascontiguousarray(win_off, np.uint64)
-    sid, delta, aligned = (np.ascontiguousarray(a, d) for a, d in ((sid, np.uint32), (delta, np.int32), (aligned, np.uint32)))
-    nres, best, sp = (np.ascontiguousarray(a, np.uint32) for a in (nres, best, speeds))
-    nw = len(nres)
-    topn = 1 if sid.ndim == 1 else int(sid.shape[1])
-    assert sid.shape == delta.shape == aligned.shape and sid.size == nw * topn and len(best) == nw
-    assert int(wo[-1]) - int(wo[0]) <= nw
-    seg = {k: np.zeros(int(cap), d) for k, d in SPEED_SEGMENT_FIELDS}
-    cnt = C.c_uint64()
-    rc = lib().shz_scan_timeline_speeds(wo.ctypes.data_as(u64p), len(wo) - 1, ptr(sid), ptr(delta), ptr(aligned), ptr(nres),
-                                        ptr(best), topn, int(step_frames), sp.ctypes.data_as(u32p), len(sp), int(min_aligned),
-                                        int(max_gap), int(rung_tol), int(shift_tol),
-                                        *[ptr(seg[k]) if cap else None for k, _ in SPEED_SEGMENT_FIELDS], int(cap), C.byref(cnt))
-    return rc, seg, int(cnt.value)
+    return _timeline_raw(lib().shz_scan_timeline_speeds, SPEED_SEGMENT_FIELDS, win_off, sid, delta, aligned, nres, step_frames,
+                         min_aligned, max_gap, cap, best, (speeds,), (rung_tol, shift_tol))
 
 
 def scan_timeline_speeds(win_off, sid, delta, aligned, nres, best, step_frames, speeds, min_aligned, max_gap=1, rung_tol=1,
@@ -1193,13 +1201,8 @@ def scan_timeline_speeds(win_off, sid, delta, aligned, nres, best, step_frames, 
     """shz_scan_timeline_speeds (host only, two calls): the rank-0 answers of a speed-tolerant scan folded into segments by
     local continuity -- arrays rec, sid, first / last (windows of the recording), hits, best (largest aligned count),
     pos_first / pos_last (song frames at the first / last hit's start), rung (the index chosen most often)."""
-    args = (win_off, sid, delta, aligned, nres, best, step_frames, speeds, min_aligned, max_gap, rung_tol, shift_tol)
-    rc, seg, n = scan_timeline_speeds_raw(*args, 0)
-    if rc == E_CAPACITY:
-        rc, seg, n = scan_timeline_speeds_raw(*args, n)
-    if rc != OK:
-        raise ShzError(rc, "shz_scan_timeline_speeds: bad arguments")
-    return seg
+    return _timeline(scan_timeline_speeds_raw, "shz_scan_timeline_speeds", win_off, sid, delta, aligned, nres, best, step_frames,
+                     speeds, min_aligned, max_gap, rung_tol, shift_tol)
 
 
 WARP_SEGMENT_FIELDS = SPEED_SEGMENT_FIELDS[:-1] + (("warp", np.uint32),)
@@ -1208,20 +1211,8 @@ WARP_SEGMENT_FIELDS = SPEED_SEGMENT_FIELDS[:-1] + (("warp", np.uint32),)
 def scan_timeline_warps_raw(win_off, sid, delta, aligned, nres, best, step_frames, tempos, pitches, min_aligned, max_gap=1,
                             tempo_tol=0, pitch_tol=0, shift_tol=2, cap=0):
     """One shz_scan_timeline_warps as it is (host only): (rc, segments, count) with room for `cap` segments."""
-    wo = np.ascontiguousarray(win_off, np.uint64)
-    sid, delta, aligned = (np.ascontiguousarray(a, d) for a, d in ((sid, np.uint32), (delta, np.int32), (aligned, np.uint32)))
-    nres, best, tq, fq = (np.ascontiguousarray(a, np.uint32) for a in (nres, best, tempos, pitches))
-    nw = len(nres)
-    topn = 1 if sid.ndim == 1 else int(sid.shape[1])
-    assert sid.shape == delta.shape == aligned.shape and sid.size == nw * topn and len(best) == nw and len(tq) == len(fq)
-    assert int(wo[-1]) - int(wo[0]) <= nw
-    seg = {k: np.zeros(int(cap), d) for k, d in WARP_SEGMENT_FIELDS}
-    cnt = C.c_uint64()
-    rc = lib().shz_scan_timeline_warps(wo.ctypes.data_as(u64p), len(wo) - 1, ptr(sid), ptr(delta), ptr(aligned), ptr(nres),
-                                       ptr(best), topn, int(step_frames), tq.ctypes.data_as(u32p), fq.ctypes.data_as(u32p), len(tq),
-                                       int(min_aligned), int(max_gap), int(tempo_tol), int(pitch_tol), int(shift_tol),
-                                       *[ptr(seg[k]) if cap else None for k, _ in WARP_SEGMENT_FIELDS], int(cap), C.byref(cnt))
-    return rc, seg, int(cnt.value)
+    return _timeline_raw(lib().shz_scan_timeline_warps, WARP_SEGMENT_FIELDS, win_off, sid, delta, aligned, nres, step_frames,
+                         min_aligned, max_gap, cap, best, (tempos, pitches), (tempo_tol, pitch_tol, shift_tol))
 
 
 def scan_timeline_warps(win_off, sid, delta, aligned, nres, best, step_frames, tempos, pitches, min_aligned, max_gap=1,
@@ -1229,14 +1220,8 @@ def scan_timeline_warps(win_off, sid, delta, aligned, nres, best, step_frames, t
     """shz_scan_timeline_warps (host only, two calls): the rank-0 answers of a scan over warps folded into segments by local
     continuity -- the arrays of scan_timeline_speeds with warp (the variant chosen most often) in place of rung.  tempo_tol /
     pitch_tol: how far the factors of neighbouring hits may lie apart, Q16."""
-    args = (win_off, sid, delta, aligned, nres, best, step_frames, tempos, pitches, min_aligned, max_gap, tempo_tol, pitch_tol,
-            shift_tol)
-    rc, seg, n = scan_timeline_warps_raw(*args, 0)
-    if rc == E_CAPACITY:
-        rc, seg, n = scan_timeline_warps_raw(*args, n)
-    if rc != OK:
-        raise ShzError(rc, "shz_scan_timeline_warps: bad arguments")
-    return seg
+    return _timeline(scan_timeline_warps_raw, "shz_scan_timeline_warps", win_off, sid, delta, aligned, nres, best, step_frames,
+                     tempos, pitches, min_aligned, max_gap, tempo_tol, pitch_tol, shift_tol)
 
 
 class Table:

@@ -432,7 +432,92 @@ extern "C" int32_t shz_scan_batch(shz_ctx* ctx, shz_table* t, const int16_t* pcm
   return sc_plain_run(ctx, t, who, P, ms_extract || ms_window || ms_match, hash_off.data(), &d_key, &d_t1);
 }
 
-// The per-window answers of a scan folded into segments, on the host: "song X from window a to window b".
+// ---- the timeline fold: the per-window answers of a scan folded into segments, on the host --------------------------------
+// "Song X from window a to window b": a hit is a window whose best answer has min_aligned aligned hashes; a hit extends the
+// open segment of its recording if it names the same song, lies at most max_gap windows behind the segment's last hit and the
+// entry point's rule says it follows; any other hit closes the segment and opens one.  Segments beyond cap are counted and not
+// written.  The three timelines differ in the rule alone:
+//   follows(g, w, gap, delta)   does the hit at window w of its recording (g of all), gap windows after the last, continue?
+//   take(g, w, delta, first)    the hit is the segment's (first: it opens one)
+//   write(n)                    the rule's own outputs of the open segment, as segment n
+static inline bool sc_hit(const uint32_t* aligned, const uint32_t* nres, uint32_t topn, uint32_t min_aligned, uint64_t g) {
+  return nres[g] >= 1 && aligned[g * topn] >= min_aligned;
+}
+
+// win_off is a CSR whose recordings hold at most 2^32-1 windows each
+static bool sc_win_off_ok(const uint64_t* win_off, uint32_t n_recs) {
+  for (uint32_t r = 0; r < n_recs; ++r)
+    if (win_off[r + 1] < win_off[r] || win_off[r + 1] - win_off[r] > 0xFFFFFFFFull) return false;
+  return true;
+}
+
+static bool sc_factors_ok(const uint32_t* q16, uint32_t n) {
+  for (uint32_t v = 0; v < n; ++v)
+    if (q16[v] < SP_S_MIN || q16[v] > SP_S_MAX) return false;
+  return true;
+}
+
+template <class Rule>
+static int32_t sc_fold(const uint64_t* win_off, uint32_t n_recs, const uint32_t* sid, const int32_t* delta, const uint32_t* aligned,
+                       const uint32_t* nres, uint32_t topn, uint32_t min_aligned, uint32_t max_gap, uint32_t* seg_rec,
+                       uint32_t* seg_sid, uint32_t* seg_first, uint32_t* seg_last, uint32_t* seg_hits, uint32_t* seg_best, uint64_t cap,
+                       uint64_t* count, Rule& rule) {
+  uint64_t n = 0;
+  for (uint32_t r = 0; r < n_recs; ++r) {
+    bool open = false;
+    uint32_t o_sid = 0, o_first = 0, o_last = 0, o_hits = 0, o_best = 0;
+    auto close = [&]() {
+      if (open && n < cap) {
+        seg_rec[n] = r;
+        seg_sid[n] = o_sid;
+        seg_first[n] = o_first;
+        seg_last[n] = o_last;
+        seg_hits[n] = o_hits;
+        seg_best[n] = o_best;
+        rule.write(n);
+      }
+      n += open ? 1 : 0;
+      open = false;
+    };
+    const uint64_t nw = win_off[r + 1] - win_off[r];
+    for (uint64_t w = 0; w < nw; ++w) {
+      const uint64_t g = win_off[r] + w;
+      if (!sc_hit(aligned, nres, topn, min_aligned, g)) continue;   // no hit: changes nothing
+      const uint32_t s = sid[g * topn], a = aligned[g * topn];
+      const int64_t d = delta[g * topn];
+      const bool cont = open && s == o_sid && w - o_last - 1 <= max_gap && rule.follows(g, w, w - o_last, d);
+      if (!cont) {
+        close();
+        open = true;
+        o_sid = s;
+        o_first = (uint32_t)w;
+        o_hits = 0;
+        o_best = a;
+      }
+      o_last = (uint32_t)w;
+      ++o_hits;
+      o_best = std::max(o_best, a);
+      rule.take(g, w, d, !cont);
+    }
+    close();
+  }
+  *count = n;
+  return n > cap ? SHZ_E_CAPACITY : SHZ_OK;
+}
+
+// plain: the shift, song frame - recording frame, is the segment's
+struct sc_rule_shift {
+  uint32_t step_frames;
+  int64_t* seg_shift;
+  int64_t o_shift = 0;
+  int64_t shift(uint64_t w, int64_t d) const { return d - (int64_t)w * (int64_t)step_frames; }
+  bool follows(uint64_t, uint64_t w, uint64_t, int64_t d) const { return shift(w, d) == o_shift; }
+  void take(uint64_t, uint64_t w, int64_t d, bool first) {
+    if (first) o_shift = shift(w, d);
+  }
+  void write(uint64_t n) const { seg_shift[n] = o_shift; }
+};
+
 extern "C" int32_t shz_scan_timeline(const uint64_t* win_off, uint32_t n_recs, const uint32_t* sid, const int32_t* delta,
                                      const uint32_t* aligned, const uint32_t* nres, uint32_t topn, uint32_t step_frames,
                                      uint32_t min_aligned, uint32_t max_gap, uint32_t* seg_rec, uint32_t* seg_sid, int64_t* seg_shift,
@@ -442,52 +527,12 @@ extern "C" int32_t shz_scan_timeline(const uint64_t* win_off, uint32_t n_recs, c
   *count = 0;
   if (n_recs == 0) return SHZ_OK;
   if (!win_off || topn == 0) return SHZ_E_INVALID;
-  for (uint32_t r = 0; r < n_recs; ++r)
-    if (win_off[r + 1] < win_off[r] || win_off[r + 1] - win_off[r] > 0xFFFFFFFFull) return SHZ_E_INVALID;
+  if (!sc_win_off_ok(win_off, n_recs)) return SHZ_E_INVALID;
   if (win_off[n_recs] > win_off[0] && (!sid || !delta || !aligned || !nres)) return SHZ_E_INVALID;
   if (cap && (!seg_rec || !seg_sid || !seg_shift || !seg_first || !seg_last || !seg_hits || !seg_best)) return SHZ_E_INVALID;
-  uint64_t n = 0;
-  for (uint32_t r = 0; r < n_recs; ++r) {
-    bool open = false;
-    uint32_t o_sid = 0, o_first = 0, o_last = 0, o_hits = 0, o_best = 0;
-    int64_t o_shift = 0;
-    auto close = [&]() {
-      if (open && n < cap) {
-        seg_rec[n] = r;
-        seg_sid[n] = o_sid;
-        seg_shift[n] = o_shift;
-        seg_first[n] = o_first;
-        seg_last[n] = o_last;
-        seg_hits[n] = o_hits;
-        seg_best[n] = o_best;
-      }
-      n += open ? 1 : 0;
-      open = false;
-    };
-    const uint64_t nw = win_off[r + 1] - win_off[r];
-    for (uint64_t w = 0; w < nw; ++w) {
-      const uint64_t g = win_off[r] + w;
-      if (nres[g] < 1 || aligned[g * topn] < min_aligned) continue;   // no hit: changes nothing
-      const uint32_t s = sid[g * topn], a = aligned[g * topn];
-      const int64_t shift = (int64_t)delta[g * topn] - (int64_t)w * (int64_t)step_frames;   // song frame - recording frame
-      if (open && s == o_sid && shift == o_shift && w - o_last - 1 <= max_gap) {
-        o_last = (uint32_t)w;
-        ++o_hits;
-        o_best = std::max(o_best, a);
-        continue;
-      }
-      close();
-      open = true;
-      o_sid = s;
-      o_shift = shift;
-      o_first = o_last = (uint32_t)w;
-      o_hits = 1;
-      o_best = a;
-    }
-    close();
-  }
-  *count = n;
-  return n > cap ? SHZ_E_CAPACITY : SHZ_OK;
+  sc_rule_shift rule{step_frames, seg_shift};
+  return sc_fold(win_off, n_recs, sid, delta, aligned, nres, topn, min_aligned, max_gap, seg_rec, seg_sid, seg_first, seg_last,
+                 seg_hits, seg_best, cap, count, rule);
 }
 
 // ---- scan extents: frame-accurate start and end of every segment --------------------------------------
@@ -1006,8 +1051,44 @@ static int64_t sc_advance(uint64_t gap, uint32_t step_frames, uint32_t t16) {
   return (int64_t)(adv > top ? top : (uint64_t)adv);
 }
 
-// The per-window answers of a speed-tolerant scan folded into segments, on the host.  delta - w step is not constant when
-// the recording plays at another speed than the table's copy, so continuity is judged between neighbouring hits.
+// A scan over variants: delta - w step is not constant when the recording plays at another tempo than the table's copy, so
+// continuity is judged between neighbouring hits -- their variants at most rung_tol list places and tempo_tol / pitch_tol in the
+// factors apart (~0u: that distance does not count), and the song's position advanced by what the hit's time factor says, within
+// shift_tol.  The segment reports its first and last position and the variant most of its hits chose (sp_best on the histogram).
+struct sc_rule_variant {
+  const uint32_t *best, *tempo_q16, *pitch_q16;
+  uint32_t n_variants, step_frames, rung_tol, tempo_tol, pitch_tol, shift_tol;
+  int32_t *seg_pos_first, *seg_pos_last;
+  uint32_t* seg_variant;
+  std::vector<uint32_t> chosen;   // how often the open segment's hits chose every variant
+  uint32_t o_v = 0;
+  int64_t o_pos_first = 0, o_pos_last = 0;
+  static uint32_t apart(uint32_t a, uint32_t b) { return a > b ? a - b : b - a; }
+  bool follows(uint64_t g, uint64_t, uint64_t gap, int64_t pos) const {
+    const uint32_t v = best[g];
+    if (apart(v, o_v) > rung_tol || apart(tempo_q16[v], tempo_q16[o_v]) > tempo_tol || apart(pitch_q16[v], pitch_q16[o_v]) > pitch_tol)
+      return false;
+    // the song advances W_t16(gap step) frames between the two windows' starts
+    const int64_t off = pos - o_pos_last - sc_advance(gap, step_frames, tempo_q16[v]);
+    return (off < 0 ? -off : off) <= (int64_t)shift_tol;
+  }
+  void take(uint64_t g, uint64_t, int64_t pos, bool first) {
+    if (first) {
+      o_pos_first = pos;
+      std::fill(chosen.begin(), chosen.end(), 0u);
+    }
+    o_pos_last = pos;
+    o_v = best[g];
+    ++chosen[o_v];
+  }
+  void write(uint64_t n) const {
+    seg_pos_first[n] = (int32_t)o_pos_first;
+    seg_pos_last[n] = (int32_t)o_pos_last;
+    seg_variant[n] = sp_best(chosen.data(), tempo_q16, pitch_q16, n_variants);
+  }
+};
+
+// The timeline of a speed-tolerant scan: one sorted ladder, neighbouring hits at most rung_tol rungs apart.
 extern "C" int32_t shz_scan_timeline_speeds(const uint64_t* win_off, uint32_t n_recs, const uint32_t* sid, const int32_t* delta,
                                             const uint32_t* aligned, const uint32_t* nres, const uint32_t* best, uint32_t topn,
                                             uint32_t step_frames, const uint32_t* speed_q16, uint32_t n_speeds,
@@ -1019,77 +1100,21 @@ extern "C" int32_t shz_scan_timeline_speeds(const uint64_t* win_off, uint32_t n_
   *count = 0;
   if (n_recs == 0) return SHZ_OK;
   if (!win_off || topn == 0 || !speed_q16 || n_speeds == 0 || n_speeds > SP_MAX_SPEEDS) return SHZ_E_INVALID;
-  for (uint32_t v = 0; v < n_speeds; ++v)
-    if (speed_q16[v] < SP_S_MIN || speed_q16[v] > SP_S_MAX) return SHZ_E_INVALID;
-  for (uint32_t r = 0; r < n_recs; ++r)
-    if (win_off[r + 1] < win_off[r] || win_off[r + 1] - win_off[r] > 0xFFFFFFFFull) return SHZ_E_INVALID;
+  if (!sc_factors_ok(speed_q16, n_speeds)) return SHZ_E_INVALID;
+  if (!sc_win_off_ok(win_off, n_recs)) return SHZ_E_INVALID;
   if (win_off[n_recs] > win_off[0] && (!sid || !delta || !aligned || !nres || !best)) return SHZ_E_INVALID;
   if (cap && (!seg_rec || !seg_sid || !seg_first || !seg_last || !seg_hits || !seg_best || !seg_pos_first || !seg_pos_last || !seg_rung))
     return SHZ_E_INVALID;
   for (uint64_t g = win_off[0]; g < win_off[n_recs]; ++g)
     if (best[g] >= n_speeds) return SHZ_E_INVALID;
-  std::vector<uint32_t> chosen(n_speeds, 0);   // how often the open segment's hits chose every rung
-  uint64_t n = 0;
-  for (uint32_t r = 0; r < n_recs; ++r) {
-    bool open = false;
-    uint32_t o_sid = 0, o_first = 0, o_last = 0, o_hits = 0, o_best = 0, o_rung = 0;
-    int64_t o_pos_first = 0, o_pos_last = 0;
-    auto close = [&]() {
-      if (open && n < cap) {
-        seg_rec[n] = r;
-        seg_sid[n] = o_sid;
-        seg_first[n] = o_first;
-        seg_last[n] = o_last;
-        seg_hits[n] = o_hits;
-        seg_best[n] = o_best;
-        seg_pos_first[n] = (int32_t)o_pos_first;
-        seg_pos_last[n] = (int32_t)o_pos_last;
-        seg_rung[n] = sp_best(chosen.data(), speed_q16, speed_q16, n_speeds);
-      }
-      n += open ? 1 : 0;
-      open = false;
-    };
-    const uint64_t nw = win_off[r + 1] - win_off[r];
-    for (uint64_t w = 0; w < nw; ++w) {
-      const uint64_t g = win_off[r] + w;
-      if (nres[g] < 1 || aligned[g * topn] < min_aligned) continue;   // no hit: changes nothing
-      const uint32_t s = sid[g * topn], a = aligned[g * topn], v = best[g];
-      const int64_t pos = delta[g * topn];
-      bool cont = open && s == o_sid && w - o_last - 1 <= max_gap && (v > o_rung ? v - o_rung : o_rung - v) <= rung_tol;
-      if (cont) {
-        // the song advances W_v((w - w_last) step) frames between the two windows' starts
-        const int64_t adv = sc_advance(w - o_last, step_frames, speed_q16[v]);
-        const int64_t off = pos - o_pos_last - adv;
-        cont = (off < 0 ? -off : off) <= (int64_t)shift_tol;
-      }
-      if (cont) {
-        o_last = (uint32_t)w;
-        ++o_hits;
-        o_best = std::max(o_best, a);
-        o_pos_last = pos;
-        o_rung = v;
-        ++chosen[v];
-        continue;
-      }
-      close();
-      open = true;
-      o_sid = s;
-      o_first = o_last = (uint32_t)w;
-      o_hits = 1;
-      o_best = a;
-      o_pos_first = o_pos_last = pos;
-      o_rung = v;
-      std::fill(chosen.begin(), chosen.end(), 0u);
-      chosen[v] = 1;
-    }
-    close();
-  }
-  *count = n;
-  return n > cap ? SHZ_E_CAPACITY : SHZ_OK;
+  sc_rule_variant rule{best, speed_q16, speed_q16, n_speeds, step_frames, rung_tol, ~0u, ~0u, shift_tol, seg_pos_first, seg_pos_last,
+                       seg_rung, std::vector<uint32_t>(n_speeds, 0)};
+  return sc_fold(win_off, n_recs, sid, delta, aligned, nres, topn, min_aligned, max_gap, seg_rec, seg_sid, seg_first, seg_last,
+                 seg_hits, seg_best, cap, count, rule);
 }
 
-// The per-window answers of a scan over warps folded into segments, on the host: shz_scan_timeline_speeds with a tolerance for
-// each factor in place of the rung distance, so the list need not be sorted.  best is read for hits only.
+// The timeline of a scan over warps: a tolerance for each factor in place of the rung distance, so the list need not be sorted
+// (and may be longer than one call's ladder).  best is read for hits only.
 extern "C" int32_t shz_scan_timeline_warps(const uint64_t* win_off, uint32_t n_recs, const uint32_t* sid, const int32_t* delta,
                                            const uint32_t* aligned, const uint32_t* nres, const uint32_t* best, uint32_t topn,
                                            uint32_t step_frames, const uint32_t* tempo_q16, const uint32_t* pitch_q16,
@@ -1102,74 +1127,15 @@ extern "C" int32_t shz_scan_timeline_warps(const uint64_t* win_off, uint32_t n_r
   *count = 0;
   if (n_recs == 0) return SHZ_OK;
   if (!win_off || topn == 0 || !tempo_q16 || !pitch_q16 || n_warps == 0) return SHZ_E_INVALID;
-  for (uint32_t v = 0; v < n_warps; ++v)
-    if (tempo_q16[v] < SP_S_MIN || tempo_q16[v] > SP_S_MAX || pitch_q16[v] < SP_S_MIN || pitch_q16[v] > SP_S_MAX) return SHZ_E_INVALID;
-  for (uint32_t r = 0; r < n_recs; ++r)
-    if (win_off[r + 1] < win_off[r] || win_off[r + 1] - win_off[r] > 0xFFFFFFFFull) return SHZ_E_INVALID;
+  if (!sc_factors_ok(tempo_q16, n_warps) || !sc_factors_ok(pitch_q16, n_warps)) return SHZ_E_INVALID;
+  if (!sc_win_off_ok(win_off, n_recs)) return SHZ_E_INVALID;
   if (win_off[n_recs] > win_off[0] && (!sid || !delta || !aligned || !nres || !best)) return SHZ_E_INVALID;
   if (cap && (!seg_rec || !seg_sid || !seg_first || !seg_last || !seg_hits || !seg_best || !seg_pos_first || !seg_pos_last || !seg_warp))
     return SHZ_E_INVALID;
-  auto hit = [&](uint64_t g) { return nres[g] >= 1 && aligned[g * topn] >= min_aligned; };
   for (uint64_t g = win_off[0]; g < win_off[n_recs]; ++g)
-    if (hit(g) && best[g] >= n_warps) return SHZ_E_INVALID;
-  auto apart = [](uint32_t a, uint32_t b) { return a > b ? a - b : b - a; };
-  std::vector<uint32_t> chosen(n_warps, 0);   // how often the open segment's hits chose every variant
-  uint64_t n = 0;
-  for (uint32_t r = 0; r < n_recs; ++r) {
-    bool open = false;
-    uint32_t o_sid = 0, o_first = 0, o_last = 0, o_hits = 0, o_best = 0, o_v = 0;
-    int64_t o_pos_first = 0, o_pos_last = 0;
-    auto close = [&]() {
-      if (open && n < cap) {
-        seg_rec[n] = r;
-        seg_sid[n] = o_sid;
-        seg_first[n] = o_first;
-        seg_last[n] = o_last;
-        seg_hits[n] = o_hits;
-        seg_best[n] = o_best;
-        seg_pos_first[n] = (int32_t)o_pos_first;
-        seg_pos_last[n] = (int32_t)o_pos_last;
-        seg_warp[n] = sp_best(chosen.data(), tempo_q16, pitch_q16, n_warps);
-      }
-      n += open ? 1 : 0;
-      open = false;
-    };
-    const uint64_t nw = win_off[r + 1] - win_off[r];
-    for (uint64_t w = 0; w < nw; ++w) {
-      const uint64_t g = win_off[r] + w;
-      if (!hit(g)) continue;   // no hit: changes nothing
-      const uint32_t s = sid[g * topn], a = aligned[g * topn], v = best[g];
-      const int64_t pos = delta[g * topn];
-      bool cont = open && s == o_sid && w - o_last - 1 <= max_gap && apart(tempo_q16[v], tempo_q16[o_v]) <= tempo_tol_q16 &&
-                  apart(pitch_q16[v], pitch_q16[o_v]) <= pitch_tol_q16;
-      if (cont) {
-        // the song advances W_t16((w - w_last) step) frames between the two windows' starts
-        const int64_t adv = sc_advance(w - o_last, step_frames, tempo_q16[v]);
-        const int64_t off = pos - o_pos_last - adv;
-        cont = (off < 0 ? -off : off) <= (int64_t)shift_tol;
-      }
-      if (cont) {
-        o_last = (uint32_t)w;
-        ++o_hits;
-        o_best = std::max(o_best, a);
-        o_pos_last = pos;
-        o_v = v;
-        ++chosen[v];
-        continue;
-      }
-      close();
-      open = true;
-      o_sid = s;
-      o_first = o_last = (uint32_t)w;
-      o_hits = 1;
-      o_best = a;
-      o_pos_first = o_pos_last = pos;
-      o_v = v;
-      std::fill(chosen.begin(), chosen.end(), 0u);
-      chosen[v] = 1;
-    }
-    close();
-  }
-  *count = n;
-  return n > cap ? SHZ_E_CAPACITY : SHZ_OK;
+    if (sc_hit(aligned, nres, topn, min_aligned, g) && best[g] >= n_warps) return SHZ_E_INVALID;
+  sc_rule_variant rule{best, tempo_q16, pitch_q16, n_warps, step_frames, ~0u, tempo_tol_q16, pitch_tol_q16, shift_tol, seg_pos_first,
+                       seg_pos_last, seg_warp, std::vector<uint32_t>(n_warps, 0)};
+  return sc_fold(win_off, n_recs, sid, delta, aligned, nres, topn, min_aligned, max_gap, seg_rec, seg_sid, seg_first, seg_last,
+                 seg_hits, seg_best, cap, count, rule);
 }

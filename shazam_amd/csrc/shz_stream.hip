@@ -596,18 +596,19 @@ extern "C" int32_t shz_streams_push(shz_streams* s, const int16_t* pcm, const ui
 // sliding window: the hashes with t1 >= w0 = max(0, H - window_frames), H the smallest settled horizon of its channels,
 // query offsets t1 - w0.  The windows live on the device as two packed slots of (key32, absolute t1) columns, listener l's
 // entries at [w_at[l], w_at[l] + w_n[l]) of the current slot.  One push: the streams' push with device output, one small
-// upload (per listener: where its old and its new entries are, and w0), listener_count_kernel, a scan over the listeners,
-// listener_write_kernel -- kept old entries, then kept new ones, compacted in order into the OTHER slot, and in the same
+// upload (per listener: where its old and its new entries are, and w0), window_count_kernel, a scan over the listeners,
+// window_write_kernel -- kept old entries, then kept new ones, compacted in order into the OTHER slot, and in the same
 // pass the query offsets t1 - w0 beside them (the query's key column is the new window's) -- one read-back of the counts,
 // which are the match's query_off, and the match on device input.  The slots flip once the counts are back, so a push that
 // fails before leaves every window as it was.
 
 #define LS_THREADS 256
 
-struct ls_job {
-  uint64_t old_at, new_at;   // first old entry in the current window slot; first new entry in the push's hashes
+// One job of the window stage, which hash windows (one job per listener) and peak windows (one per stream) share.
+struct win_job {
+  uint64_t old_at, new_at;   // first old entry in the current slot; first new entry in the push's lists
   uint32_t old_n, new_n;
-  uint32_t w0, pad;
+  uint32_t w0, add;          // the window start; what makes a new t absolute (peaks: the first frame of the stream's window clip)
 };
 
 struct shz_listeners {
@@ -621,7 +622,7 @@ struct shz_listeners {
   std::vector<uint32_t> w_n, w0;
   shz_buf nk, nt;                  // the hashes of a push
   uint64_t new_cap = 0;            // entries nk / nt hold
-  shz_buf qo, jobs, ctl;           // query offsets; ls_job per listener; total | counts | offsets
+  shz_buf qo, jobs, ctl;           // query offsets; the window stage's jobs; total | counts | offsets
   // peak windows (shz_listeners_create_peaks): per STREAM, the settled peaks with t >= w0 of its listener
   bool peaks = false;
   shz_buf pf[2], pt[2], pr;        // the two slots of (f, absolute t); the times t - w0 beside the current slot
@@ -632,30 +633,31 @@ struct shz_listeners {
   float ms[4] = {0.f, 0.f, 0.f, 0.f};               // streams, window, warp, match of the last push
 };
 
-// entry i of a listener's old-then-new list and whether the window keeps it
-__device__ __forceinline__ bool ls_entry(const ls_job& j, uint32_t i, const uint32_t* __restrict__ wk, const uint32_t* __restrict__ wt,
-                                         const uint32_t* __restrict__ nk, const uint32_t* __restrict__ nt, uint32_t* k, uint32_t* t) {
+// entry i of a job's old-then-new list (payload, absolute t) and whether the window keeps it
+template <class P>
+__device__ __forceinline__ bool win_entry(const win_job& j, uint32_t i, const P* __restrict__ wp, const uint32_t* __restrict__ wt,
+                                          const P* __restrict__ np, const uint32_t* __restrict__ nt, P* p, uint32_t* t) {
   if (i >= j.old_n + j.new_n) return false;
   if (i < j.old_n) {
     *t = wt[j.old_at + i];
-    if (k) *k = wk[j.old_at + i];
+    if (p) *p = wp[j.old_at + i];
   } else {
-    *t = nt[j.new_at + (i - j.old_n)];
-    if (k) *k = nk[j.new_at + (i - j.old_n)];
+    *t = nt[j.new_at + (i - j.old_n)] + j.add;
+    if (p) *p = np[j.new_at + (i - j.old_n)];
   }
   return *t >= j.w0;
 }
 
-// per listener: entries its window keeps (one ballot per 64 entries, the waves' sums through LDS)
-__global__ __launch_bounds__(LS_THREADS) void listener_count_kernel(const ls_job* __restrict__ jobs, const uint32_t* __restrict__ wt,
-                                                                    const uint32_t* __restrict__ nt, uint64_t* __restrict__ cnt) {
-  const ls_job j = jobs[blockIdx.x];
+// per job: entries its window keeps (one ballot per 64 entries, the waves' sums through LDS)
+__global__ __launch_bounds__(LS_THREADS) void window_count_kernel(const win_job* __restrict__ jobs, const uint32_t* __restrict__ wt,
+                                                                  const uint32_t* __restrict__ nt, uint64_t* __restrict__ cnt) {
+  const win_job j = jobs[blockIdx.x];
   const uint32_t n = j.old_n + j.new_n;
   __shared__ uint32_t s_w[LS_THREADS / 64];
   uint32_t c = 0;   // (the same in every lane of a wave)
   for (uint32_t i0 = 0; i0 < n; i0 += LS_THREADS) {
     uint32_t t;
-    const bool keep = ls_entry(j, i0 + threadIdx.x, nullptr, wt, nullptr, nt, nullptr, &t);
+    const bool keep = win_entry<uint32_t>(j, i0 + threadIdx.x, nullptr, wt, nullptr, nt, nullptr, &t);
     c += (uint32_t)__popcll(__ballot(keep));
   }
   if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = c;
@@ -667,21 +669,23 @@ __global__ __launch_bounds__(LS_THREADS) void listener_count_kernel(const ls_job
   }
 }
 
-// per listener: the kept entries, in order, at offs[listener] of the other window slot, and their query offsets
-__global__ __launch_bounds__(LS_THREADS) void listener_write_kernel(const ls_job* __restrict__ jobs, const uint32_t* __restrict__ wk,
-                                                                    const uint32_t* __restrict__ wt, const uint32_t* __restrict__ nk,
-                                                                    const uint32_t* __restrict__ nt, const uint64_t* __restrict__ offs,
-                                                                    const unsigned long long* __restrict__ total, uint64_t cap,
-                                                                    uint32_t* __restrict__ wk_out, uint32_t* __restrict__ wt_out,
-                                                                    uint32_t* __restrict__ qo) {
+// per job: the kept entries, in order, at offs[job] of the other slot, and their times relative to the window start
+template <class P>
+__global__ __launch_bounds__(LS_THREADS) void window_write_kernel(const win_job* __restrict__ jobs, const P* __restrict__ wp,
+                                                                  const uint32_t* __restrict__ wt, const P* __restrict__ np,
+                                                                  const uint32_t* __restrict__ nt, const uint64_t* __restrict__ offs,
+                                                                  const unsigned long long* __restrict__ total, uint64_t cap,
+                                                                  P* __restrict__ wp_out, uint32_t* __restrict__ wt_out,
+                                                                  uint32_t* __restrict__ rel) {
   if (*total > cap) return;   // (uniform; the host sizes the slots by a bound, so this never holds: it keeps a wrong bound harmless)
-  const ls_job j = jobs[blockIdx.x];
+  const win_job j = jobs[blockIdx.x];
   const uint32_t n = j.old_n + j.new_n, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   __shared__ uint32_t s_w[2][LS_THREADS / 64];
   uint64_t o = offs[blockIdx.x];
-  for (uint32_t i0 = 0, it = 0; i0 < n; i0 += LS_THREADS, ++it) {
-    uint32_t k = 0, t = 0;
-    const bool keep = ls_entry(j, i0 + threadIdx.x, wk, wt, nk, nt, &k, &t);
+  for (uint32_t i0 = 0, it = 0; i0 < n; i0 += LS_THREADS, ++it) {   // (n is the block's: every wave makes every round)
+    P v = 0;
+    uint32_t t = 0;
+    const bool keep = win_entry<P>(j, i0 + threadIdx.x, wp, wt, np, nt, &v, &t);
     const unsigned long long b = __ballot(keep);
     const uint32_t pre = __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
     uint32_t* sw = s_w[it & 1];   // (two rows: a wave may start the next round while another still reads this one's sums)
@@ -689,15 +693,15 @@ __global__ __launch_bounds__(LS_THREADS) void listener_write_kernel(const ls_job
     __syncthreads();
     uint32_t base = 0, all = 0;
     for (uint32_t i = 0; i < LS_THREADS / 64; ++i) {
-      const uint32_t v = sw[i];
-      if (i < w) base += v;
-      all += v;
+      const uint32_t x = sw[i];
+      if (i < w) base += x;
+      all += x;
     }
     if (keep) {
-      const uint64_t p = o + base + pre;
-      wk_out[p] = k;
-      wt_out[p] = t;
-      qo[p] = t - j.w0;
+      const uint64_t q = o + base + pre;
+      wp_out[q] = v;
+      wt_out[q] = t;
+      rel[q] = t - j.w0;
     }
     o += all;
   }
@@ -820,6 +824,71 @@ extern "C" int32_t shz_listener_window(const uint64_t* settled, uint32_t channel
   return SHZ_OK;
 }
 
+// The streams' push of a listeners' push: hashes to the object's own device buffers (L->nk / L->nt).  Its SHZ_E_CAPACITY changes
+// no stream and names the room, so the buffers grow and the push is made again.
+static int32_t ls_streams_push(shz_listeners* L, const int16_t* pcm, const uint64_t* chunk_off, const uint32_t* end, uint32_t flags,
+                               uint64_t* hash_off) {
+  shz_ctx* ctx = L->ctx;
+  uint64_t count = 0;
+  void *d_nk, *d_nt;
+  if (L->new_cap == 0) L->new_cap = (uint64_t)L->s->n * 256 + 4096;
+  for (int attempt = 0;; ++attempt) {
+    SHZ_TRY(st_reserve(ctx, L->nk, L->new_cap * 4 + 64, &d_nk));
+    SHZ_TRY(st_reserve(ctx, L->nt, L->new_cap * 4 + 64, &d_nt));
+    const int32_t rc = shz_streams_push(L->s, pcm, chunk_off, end, (flags & SHZ_PCM_DEVICE) | SHZ_OUT_DEVICE, (uint32_t*)d_nk,
+                                        (uint32_t*)d_nt, hash_off, L->new_cap, &count);
+    if (rc == SHZ_E_CAPACITY && attempt < 2 && count > L->new_cap) {
+      L->new_cap = count + count / 4;
+      continue;
+    }
+    return rc;
+  }
+}
+
+// The window stage's mailbox: nj jobs for the host to fill | total (64 bytes) and the nj counts read back.
+static inline uint64_t win_jobs_bytes(uint32_t nj) { return ((uint64_t)nj * sizeof(win_job) + 255) & ~255ull; }
+
+static int32_t win_mailbox(shz_ctx* ctx, uint32_t nj, win_job** hj) {
+  void* mailp;
+  SHZ_TRY(shz_mailbox(ctx, win_jobs_bytes(nj) + 64 + (uint64_t)nj * 8, &mailp));
+  *hj = (win_job*)mailp;
+  return SHZ_OK;
+}
+
+// The window stage on the nj jobs in the mailbox: one upload, count, a scan over the jobs, the kept old-then-new entries
+// compacted in order into the output slot (sized by the caller for `bound` entries) with t - w0 beside them, and one read-back
+// of the counts; csr is their CSR from 0.  Commits nothing: the caller flips the slots once this has returned SHZ_OK.
+template <class P>
+static int32_t win_compact(shz_listeners* L, uint32_t nj, const win_job* hj, uint64_t bound, const char* what, const P* wp_in,
+                           const uint32_t* wt_in, const P* np, const uint32_t* nt, P* wp_out, uint32_t* wt_out, uint32_t* rel,
+                           hipEvent_t queued, std::vector<uint64_t>& csr) {
+  shz_ctx* ctx = L->ctx;
+  void *d_jobs, *d_ctl;
+  const uint64_t jb = win_jobs_bytes(nj), rb = 64 + (uint64_t)nj * 8;
+  SHZ_TRY(st_reserve(ctx, L->jobs, jb, &d_jobs));
+  SHZ_TRY(st_reserve(ctx, L->ctl, 64 + (uint64_t)nj * 16, &d_ctl));
+  unsigned long long* d_total = (unsigned long long*)d_ctl;
+  uint64_t *d_cnt = (uint64_t*)((char*)d_ctl + 64), *d_offs = d_cnt + nj;
+  SHZ_HIP(ctx, hipMemcpyAsync(d_jobs, hj, (uint64_t)nj * sizeof(win_job), hipMemcpyHostToDevice, ctx->stream));
+  hipLaunchKernelGGL(window_count_kernel, dim3(nj), dim3(LS_THREADS), 0, ctx->stream, (const win_job*)d_jobs, wt_in, nt, d_cnt);
+  SHZ_HIP(ctx, hipGetLastError());
+  SHZ_TRY(shz_scan_u64(ctx, d_cnt, d_offs, nj, (uint64_t*)d_total));
+  hipLaunchKernelGGL(window_write_kernel<P>, dim3(nj), dim3(LS_THREADS), 0, ctx->stream, (const win_job*)d_jobs, wp_in, wt_in, np, nt,
+                     (const uint64_t*)d_offs, (const unsigned long long*)d_total, bound, wp_out, wt_out, rel);
+  SHZ_HIP(ctx, hipGetLastError());
+  char* hr = (char*)hj + jb;
+  SHZ_HIP(ctx, hipMemcpyAsync(hr, d_ctl, rb, hipMemcpyDeviceToHost, ctx->stream));
+  if (queued) SHZ_HIP(ctx, hipEventRecord(queued, ctx->stream));
+  SHZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  const uint64_t total = *(const uint64_t*)hr;
+  const uint64_t* hc = (const uint64_t*)(hr + 64);
+  if (total > bound)
+    SHZ_FAIL(ctx, SHZ_E_STATE, "listeners: %llu window %s exceed their bound %llu", (unsigned long long)total, what, (unsigned long long)bound);
+  csr.assign((size_t)nj + 1, 0);
+  for (uint32_t k = 0; k < nj; ++k) csr[k + 1] = csr[k] + hc[k];
+  return SHZ_OK;
+}
+
 extern "C" int32_t shz_listeners_push(shz_listeners* L, const int16_t* pcm, const uint64_t* chunk_off, const uint32_t* end,
                                       uint32_t topn, uint32_t flags, uint32_t* out_sid, int32_t* out_delta, uint32_t* out_aligned,
                                       uint32_t* out_dedup, uint32_t* out_nres, uint32_t* out_nhash, uint64_t* out_npairs,
@@ -834,28 +903,12 @@ extern "C" int32_t shz_listeners_push(shz_listeners* L, const int16_t* pcm, cons
   if (!out_sid || !out_delta || !out_aligned || !out_dedup || !out_nres) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_listeners_push: NULL buffer");
   SHZ_TRY(shz_match_ready(ctx, L->t, topn));
   SHZ_HIP(ctx, hipSetDevice(ctx->device));
-  // 1) the streams' push, hashes to the object's own device buffers; its SHZ_E_CAPACITY changes no stream and names the room
+  // 1) the streams' push, hashes to the object's own device buffers
   std::vector<uint64_t> hash_off((size_t)s->n + 1, 0);
-  uint64_t count = 0;
-  void *d_nk, *d_nt;
-  if (L->new_cap == 0) L->new_cap = (uint64_t)s->n * 256 + 4096;
-  for (int attempt = 0;; ++attempt) {
-    SHZ_TRY(st_reserve(ctx, L->nk, L->new_cap * 4 + 64, &d_nk));
-    SHZ_TRY(st_reserve(ctx, L->nt, L->new_cap * 4 + 64, &d_nt));
-    const int32_t rc = shz_streams_push(s, pcm, chunk_off, end, (flags & SHZ_PCM_DEVICE) | SHZ_OUT_DEVICE, (uint32_t*)d_nk,
-                                        (uint32_t*)d_nt, hash_off.data(), L->new_cap, &count);
-    if (rc == SHZ_E_CAPACITY && attempt < 2 && count > L->new_cap) {
-      L->new_cap = count + count / 4;
-      continue;
-    }
-    SHZ_TRY(rc);
-    break;
-  }
+  SHZ_TRY(ls_streams_push(L, pcm, chunk_off, end, flags, hash_off.data()));
   // 2) w0 of every listener from the horizons, where its entries are, and a bound of what the windows can hold
-  void* mailp;
-  const uint64_t jb = ((uint64_t)n * sizeof(ls_job) + 255) & ~255ull, rb = 64 + (uint64_t)n * 8;
-  SHZ_TRY(shz_mailbox(ctx, jb + rb, &mailp));
-  ls_job* hj = (ls_job*)mailp;
+  win_job* hj;
+  SHZ_TRY(win_mailbox(ctx, n, &hj));
   uint64_t bound = 0, bias = 0;
   std::vector<uint32_t> w0_new(n);
   for (uint32_t l = 0; l < n; ++l) {
@@ -863,47 +916,28 @@ extern "C" int32_t shz_listeners_push(shz_listeners* L, const int16_t* pcm, cons
     SHZ_TRY(shz_listener_window(s->settled.data() + (size_t)l * ch, ch, L->window_frames, &h, &w0));
     for (uint32_t c = 0; c < ch; ++c) top = std::max(top, s->settled[(size_t)l * ch + c]);
     const uint64_t a = hash_off[(size_t)l * ch], b = hash_off[(size_t)(l + 1) * ch];
-    hj[l] = ls_job{L->w_at[l], a, L->w_n[l], (uint32_t)(b - a), (uint32_t)w0, 0u};
+    hj[l] = win_job{L->w_at[l], a, L->w_n[l], (uint32_t)(b - a), (uint32_t)w0, 0u};
     w0_new[l] = (uint32_t)w0;
     bound += (uint64_t)L->w_n[l] + (b - a);
     if ((uint64_t)L->w_n[l] + (b - a) >= (1ull << 31)) SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "listener %u: 2^31 hashes in its window", l);
     // every t1 of a channel is below that channel's horizon: the largest query offset of the push is below this
     if (top > w0) bias = std::max(bias, top - w0 - 1);
   }
+  // 3) count, scan over the listeners, compact into the other slot; 4) one read-back: the counts are the match's query_off
   const uint32_t out = L->cur ^ 1u;
-  void *d_wk, *d_wt, *d_qo, *d_jobs, *d_ctl;
+  void *d_wk, *d_wt, *d_qo;
   SHZ_TRY(st_reserve(ctx, L->wk[out], bound * 4 + 64, &d_wk));
   SHZ_TRY(st_reserve(ctx, L->wt[out], bound * 4 + 64, &d_wt));
   SHZ_TRY(st_reserve(ctx, L->qo, bound * 4 + 64, &d_qo));
-  SHZ_TRY(st_reserve(ctx, L->jobs, jb, &d_jobs));
-  SHZ_TRY(st_reserve(ctx, L->ctl, 64 + (uint64_t)n * 16, &d_ctl));
-  const uint32_t *d_wk_in = (const uint32_t*)L->wk[L->cur].p, *d_wt_in = (const uint32_t*)L->wt[L->cur].p;
-  unsigned long long* d_total = (unsigned long long*)d_ctl;
-  uint64_t *d_cnt = (uint64_t*)((char*)d_ctl + 64), *d_offs = d_cnt + n;
-  SHZ_HIP(ctx, hipMemcpyAsync(d_jobs, hj, (uint64_t)n * sizeof(ls_job), hipMemcpyHostToDevice, ctx->stream));
-  // 3) count, scan over the listeners, compact into the other slot
-  hipLaunchKernelGGL(listener_count_kernel, dim3(n), dim3(LS_THREADS), 0, ctx->stream, (const ls_job*)d_jobs, d_wt_in,
-                     (const uint32_t*)d_nt, d_cnt);
-  SHZ_HIP(ctx, hipGetLastError());
-  SHZ_TRY(shz_scan_u64(ctx, d_cnt, d_offs, n, (uint64_t*)d_total));
-  hipLaunchKernelGGL(listener_write_kernel, dim3(n), dim3(LS_THREADS), 0, ctx->stream, (const ls_job*)d_jobs, d_wk_in, d_wt_in,
-                     (const uint32_t*)d_nk, (const uint32_t*)d_nt, (const uint64_t*)d_offs, (const unsigned long long*)d_total, bound,
-                     (uint32_t*)d_wk, (uint32_t*)d_wt, (uint32_t*)d_qo);
-  SHZ_HIP(ctx, hipGetLastError());
-  // 4) one read-back: the counts are the match's query_off
-  char* hr = (char*)mailp + jb;
-  SHZ_HIP(ctx, hipMemcpyAsync(hr, d_ctl, rb, hipMemcpyDeviceToHost, ctx->stream));
-  SHZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  const uint64_t total = *(const uint64_t*)hr;
-  const uint64_t* hc = (const uint64_t*)(hr + 64);
-  if (total > bound) SHZ_FAIL(ctx, SHZ_E_STATE, "listeners: %llu window entries exceed their bound %llu", (unsigned long long)total, (unsigned long long)bound);
-  std::vector<uint64_t> query_off((size_t)n + 1, 0);
-  for (uint32_t l = 0; l < n; ++l) query_off[l + 1] = query_off[l] + hc[l];
+  std::vector<uint64_t> query_off;
+  SHZ_TRY(win_compact<uint32_t>(L, n, hj, bound, "entries", (const uint32_t*)L->wk[L->cur].p, (const uint32_t*)L->wt[L->cur].p,
+                                (const uint32_t*)L->nk.p, (const uint32_t*)L->nt.p, (uint32_t*)d_wk, (uint32_t*)d_wt, (uint32_t*)d_qo,
+                                nullptr, query_off));
   // the windows advance: the streams have
   L->cur = out;
   for (uint32_t l = 0; l < n; ++l) {
     L->w_at[l] = query_off[l];
-    L->w_n[l] = (uint32_t)hc[l];
+    L->w_n[l] = (uint32_t)(query_off[l + 1] - query_off[l]);
     L->w0[l] = w0_new[l];
     if (out_w0) out_w0[l] = w0_new[l];
   }
@@ -917,87 +951,10 @@ extern "C" int32_t shz_listeners_push(shz_listeners* L, const int16_t* pcm, cons
 // A warp acts on peaks -- they move in integer coordinates, change order and pair anew (shz_speed.hip) -- so a window of
 // hashes cannot be warped.  A peak-window object keeps, per STREAM, the settled peaks (f, absolute t) with t >= w0 of its
 // listener, in the stream's order, in two packed slots as the hash windows are.  One push: the streams' push, which says where
-// every stream's newly settled peaks lie (st_hand); one small upload; peakwin_count_kernel, a scan over the streams,
-// peakwin_write_kernel -- kept old entries, then the new ones with their window clip's first frame added, compacted in order
+// every stream's newly settled peaks lie (st_hand); one small upload; the same window_count_kernel, a scan over the streams,
+// window_write_kernel -- kept old entries, then the new ones with their window clip's first frame added, compacted in order
 // into the OTHER slot, the times t - w0 beside them -- one read-back of the counts, which are the warp's peak_off; then every
 // (listener, warp) through sp_match_fold on the slot's f column and the rebased times.
-
-struct pk_job {
-  uint64_t old_at, new_at;   // first old entry in the current slot; first new entry in the streams' peak lists
-  uint32_t old_n, new_n;
-  uint32_t w0, add;          // the listener's window start; the first frame of the stream's window clip (new t + add is absolute)
-};
-
-// entry i of a stream's old-then-new list (absolute t) and whether the window keeps it
-__device__ __forceinline__ bool pk_entry(const pk_job& j, uint32_t i, const uint16_t* __restrict__ wf, const uint32_t* __restrict__ wt,
-                                         const uint16_t* __restrict__ nf, const uint32_t* __restrict__ nt, uint32_t* f, uint32_t* t) {
-  if (i >= j.old_n + j.new_n) return false;
-  if (i < j.old_n) {
-    *t = wt[j.old_at + i];
-    if (f) *f = wf[j.old_at + i];
-  } else {
-    *t = nt[j.new_at + (i - j.old_n)] + j.add;
-    if (f) *f = nf[j.new_at + (i - j.old_n)];
-  }
-  return *t >= j.w0;
-}
-
-// per stream: peaks its window keeps (one ballot per 64 entries, the waves' sums through LDS)
-__global__ __launch_bounds__(LS_THREADS) void peakwin_count_kernel(const pk_job* __restrict__ jobs, const uint32_t* __restrict__ wt,
-                                                                   const uint32_t* __restrict__ nt, uint64_t* __restrict__ cnt) {
-  const pk_job j = jobs[blockIdx.x];
-  const uint32_t n = j.old_n + j.new_n;
-  __shared__ uint32_t s_w[LS_THREADS / 64];
-  uint32_t c = 0;   // (the same in every lane of a wave)
-  for (uint32_t i0 = 0; i0 < n; i0 += LS_THREADS) {
-    uint32_t t;
-    const bool keep = pk_entry(j, i0 + threadIdx.x, nullptr, wt, nullptr, nt, nullptr, &t);
-    c += (uint32_t)__popcll(__ballot(keep));
-  }
-  if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t all = 0;
-    for (uint32_t i = 0; i < LS_THREADS / 64; ++i) all += s_w[i];
-    cnt[blockIdx.x] = all;
-  }
-}
-
-// per stream: the kept peaks, in order, at offs[stream] of the other slot, and their times relative to the window start
-__global__ __launch_bounds__(LS_THREADS) void peakwin_write_kernel(const pk_job* __restrict__ jobs, const uint16_t* __restrict__ wf,
-                                                                   const uint32_t* __restrict__ wt, const uint16_t* __restrict__ nf,
-                                                                   const uint32_t* __restrict__ nt, const uint64_t* __restrict__ offs,
-                                                                   const unsigned long long* __restrict__ total, uint64_t cap,
-                                                                   uint16_t* __restrict__ wf_out, uint32_t* __restrict__ wt_out,
-                                                                   uint32_t* __restrict__ rel) {
-  if (*total > cap) return;   // (uniform; the slots are sized by old_n + new_n of every stream, so this never holds)
-  const pk_job j = jobs[blockIdx.x];
-  const uint32_t n = j.old_n + j.new_n, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  __shared__ uint32_t s_w[2][LS_THREADS / 64];
-  uint64_t o = offs[blockIdx.x];
-  for (uint32_t i0 = 0, it = 0; i0 < n; i0 += LS_THREADS, ++it) {   // (n is the block's: every wave makes every round)
-    uint32_t f = 0, t = 0;
-    const bool keep = pk_entry(j, i0 + threadIdx.x, wf, wt, nf, nt, &f, &t);
-    const unsigned long long b = __ballot(keep);
-    const uint32_t pre = __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
-    uint32_t* sw = s_w[it & 1];   // (two rows: a wave may start the next round while another still reads this one's sums)
-    if (lane == 0) sw[w] = (uint32_t)__popcll(b);
-    __syncthreads();
-    uint32_t base = 0, all = 0;
-    for (uint32_t i = 0; i < LS_THREADS / 64; ++i) {
-      const uint32_t v = sw[i];
-      if (i < w) base += v;
-      all += v;
-    }
-    if (keep) {
-      const uint64_t p = o + base + pre;
-      wf_out[p] = (uint16_t)f;
-      wt_out[p] = t;
-      rel[p] = t - j.w0;
-    }
-    o += all;
-  }
-}
 
 extern "C" int32_t shz_listeners_timing(shz_listeners* L, int32_t enable, float* ms) {
   SHZ_TRY(ls_check(L));
@@ -1089,74 +1046,37 @@ extern "C" int32_t shz_listeners_push_warps(shz_listeners* L, const int16_t* pcm
   }
   // 1) the streams' push; its hashes go to buffers of the object and are not used (the streams advance as they always do)
   std::vector<uint64_t> hash_off((size_t)ns + 1, 0);
-  uint64_t count = 0;
-  void *d_nk, *d_nt;
-  if (L->new_cap == 0) L->new_cap = (uint64_t)ns * 256 + 4096;
-  for (int attempt = 0;; ++attempt) {
-    SHZ_TRY(st_reserve(ctx, L->nk, L->new_cap * 4 + 64, &d_nk));
-    SHZ_TRY(st_reserve(ctx, L->nt, L->new_cap * 4 + 64, &d_nt));
-    const int32_t rc = shz_streams_push(s, pcm, chunk_off, end, (flags & SHZ_PCM_DEVICE) | SHZ_OUT_DEVICE, (uint32_t*)d_nk,
-                                        (uint32_t*)d_nt, hash_off.data(), L->new_cap, &count);
-    if (rc == SHZ_E_CAPACITY && attempt < 2 && count > L->new_cap) {
-      L->new_cap = count + count / 4;
-      continue;
-    }
-    SHZ_TRY(rc);
-    break;
-  }
+  SHZ_TRY(ls_streams_push(L, pcm, chunk_off, end, flags, hash_off.data()));
   for (uint32_t i = 0; i < ns; ++i)
     if (s->settled[i] != h_after[i])
       SHZ_FAIL(ctx, SHZ_E_STATE, "listeners: stream %u settled %llu frames, its plan said %llu", i, (unsigned long long)s->settled[i],
                (unsigned long long)h_after[i]);
   if (timed) SHZ_HIP(ctx, hipEventRecord(L->ev[1], ctx->stream));
   // 2) per stream: where its old and its newly settled peaks are; the slots hold at most all of them
-  void* mailp;
-  const uint64_t jb = ((uint64_t)ns * sizeof(pk_job) + 255) & ~255ull, rb = 64 + (uint64_t)ns * 8;
-  SHZ_TRY(shz_mailbox(ctx, jb + rb, &mailp));
-  pk_job* hj = (pk_job*)mailp;
+  win_job* hj;
+  SHZ_TRY(win_mailbox(ctx, ns, &hj));
   uint64_t bound = 0;
   for (uint32_t i = 0; i < ns; ++i) {
     const st_hand& hd = s->hand[i];
-    hj[i] = pk_job{L->p_at[i], hd.at, L->p_n[i], hd.n, w0_new[i / ch], hd.w0};
+    hj[i] = win_job{L->p_at[i], hd.at, L->p_n[i], hd.n, w0_new[i / ch], hd.w0};
     bound += (uint64_t)L->p_n[i] + hd.n;
   }
   if (bound >= (1ull << 31)) SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "listeners: 2^31 peaks in the windows");
+  // 3) count, scan over the streams, compact into the other slot; 4) one read-back: the counts are the warp's peak_off
   const uint32_t out = L->cur ^ 1u;
-  void *d_wf, *d_wt, *d_rel, *d_jobs, *d_ctl;
+  void *d_wf, *d_wt, *d_rel;
   SHZ_TRY(st_reserve(ctx, L->pf[out], bound * 2 + 64, &d_wf));
   SHZ_TRY(st_reserve(ctx, L->pt[out], bound * 4 + 64, &d_wt));
   SHZ_TRY(st_reserve(ctx, L->pr, bound * 4 + 64, &d_rel));
-  SHZ_TRY(st_reserve(ctx, L->jobs, jb, &d_jobs));
-  SHZ_TRY(st_reserve(ctx, L->ctl, 64 + (uint64_t)ns * 16, &d_ctl));
-  const uint16_t* d_wf_in = (const uint16_t*)L->pf[L->cur].p;
-  const uint32_t* d_wt_in = (const uint32_t*)L->pt[L->cur].p;
-  unsigned long long* d_total = (unsigned long long*)d_ctl;
-  uint64_t *d_cnt = (uint64_t*)((char*)d_ctl + 64), *d_offs = d_cnt + ns;
-  SHZ_HIP(ctx, hipMemcpyAsync(d_jobs, hj, (uint64_t)ns * sizeof(pk_job), hipMemcpyHostToDevice, ctx->stream));
-  // 3) count, scan over the streams, compact into the other slot
-  hipLaunchKernelGGL(peakwin_count_kernel, dim3(ns), dim3(LS_THREADS), 0, ctx->stream, (const pk_job*)d_jobs, d_wt_in,
-                     (const uint32_t*)s->pt.p, d_cnt);
-  SHZ_HIP(ctx, hipGetLastError());
-  SHZ_TRY(shz_scan_u64(ctx, d_cnt, d_offs, ns, (uint64_t*)d_total));
-  hipLaunchKernelGGL(peakwin_write_kernel, dim3(ns), dim3(LS_THREADS), 0, ctx->stream, (const pk_job*)d_jobs, d_wf_in, d_wt_in,
-                     (const uint16_t*)s->pf.p, (const uint32_t*)s->pt.p, (const uint64_t*)d_offs, (const unsigned long long*)d_total,
-                     bound, (uint16_t*)d_wf, (uint32_t*)d_wt, (uint32_t*)d_rel);
-  SHZ_HIP(ctx, hipGetLastError());
-  // 4) one read-back: the counts are the warp's peak_off
-  char* hr = (char*)mailp + jb;
-  SHZ_HIP(ctx, hipMemcpyAsync(hr, d_ctl, rb, hipMemcpyDeviceToHost, ctx->stream));
-  if (timed) SHZ_HIP(ctx, hipEventRecord(L->ev[2], ctx->stream));
-  SHZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  const uint64_t total = *(const uint64_t*)hr;
-  const uint64_t* hc = (const uint64_t*)(hr + 64);
-  if (total > bound) SHZ_FAIL(ctx, SHZ_E_STATE, "listeners: %llu window peaks exceed their bound %llu", (unsigned long long)total, (unsigned long long)bound);
-  std::vector<uint64_t> peak_off((size_t)ns + 1, 0);
-  for (uint32_t i = 0; i < ns; ++i) peak_off[i + 1] = peak_off[i] + hc[i];
+  std::vector<uint64_t> peak_off;
+  SHZ_TRY(win_compact<uint16_t>(L, ns, hj, bound, "peaks", (const uint16_t*)L->pf[L->cur].p, (const uint32_t*)L->pt[L->cur].p,
+                                (const uint16_t*)s->pf.p, (const uint32_t*)s->pt.p, (uint16_t*)d_wf, (uint32_t*)d_wt, (uint32_t*)d_rel,
+                                timed ? L->ev[2] : nullptr, peak_off));
   // the windows advance: the streams have
   L->cur = out;
   for (uint32_t i = 0; i < ns; ++i) {
     L->p_at[i] = peak_off[i];
-    L->p_n[i] = (uint32_t)hc[i];
+    L->p_n[i] = (uint32_t)(peak_off[i + 1] - peak_off[i]);
   }
   for (uint32_t l = 0; l < n; ++l) {
     L->w0[l] = w0_new[l];

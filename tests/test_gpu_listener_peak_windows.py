@@ -1,4 +1,4 @@
-"""GPU: the CONTENT of the listeners' peak windows (peakwin_count_kernel / peakwin_write_kernel in csrc/shz_stream.hip), read
+"""GPU: the CONTENT of the listeners' peak windows (window_count_kernel / window_write_kernel in csrc/shz_stream.hip), read
 back through Listeners.peaks after every push and compared entry for entry and in order with the numpy twin
 (tests/listen_speed_twin.py): the oracle's peaks of every channel's whole signal with w0 <= t < H_c.  The match cannot show
 a compaction that duplicates one peak and drops another, or misplaces peaks at a wave or round border.

@@ -1,4 +1,4 @@
-"""GPU: the CONTENT of the device-resident listeners' windows (listener_count_kernel / listener_write_kernel in
+"""GPU: the CONTENT of the device-resident listeners' windows (window_count_kernel / window_write_kernel in
 csrc/shz_stream.hip), read back through the tests / tools entry shz_listeners_window after every push and compared element
 by element and in order with the numpy recogniser's own window (StreamRecognizer(device=False)._k / ._t): key, t1, and the
 query offset t1 - w0 the push handed to the match.  The match results cannot show a compaction that duplicates one entry
