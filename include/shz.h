@@ -499,6 +499,22 @@ int32_t shz_match_extents(shz_ctx* ctx, shz_table* t, const uint32_t* key32, con
                           const int32_t* cand_dhi, const uint32_t* cand_n, uint32_t* out_count, uint32_t* out_q_first,
                           uint32_t* out_q_last, uint32_t* out_t_first, uint32_t* out_t_last, uint32_t* out_hist,
                           uint32_t* out_shift);
+/* shz_match_extents with the MOMENTS of every candidate's pairs (new; tests/fit_twin.py is the same in Python): the arguments
+ * and the contract above, and four more outputs, HOST arrays of [n_queries * ncand], all required.  For candidate (sid, d_lo,
+ * d_hi) and every pair that belongs to it let q = q_off and u = d - d_lo, so 0 <= u <= d_hi - d_lo:
+ *     out_sum_q = sum q    out_sum_u = sum u    out_sum_qq = sum q^2    out_sum_qu = sum q u      (unsigned 64 bits, modulo 2^64)
+ * all 0 where count is 0 and at and past cand_n[q].  They are what a least-squares line d = slope q + intercept through the
+ * pairs needs (shazam_amd/extent.py: line_fit): a query that runs at another tempo than the rung it was warped with lets d
+ * drift along q, and the slope says by how much.  Integer adds only: exact and repeatable.  The seven other outputs equal
+ * shz_match_extents' on the same inputs.  A used candidate with d_hi - d_lo >= 4096 is refused (SHZ_E_UNSUPPORTED, before
+ * anything is launched): below that q u < 2^32, so sum_q, sum_u and sum_qu cannot wrap, and sum_qq wraps only from 2^24 pairs
+ * on.  A NULL sum array: SHZ_E_INVALID. */
+int32_t shz_match_extents_fit(shz_ctx* ctx, shz_table* t, const uint32_t* key32, const uint32_t* q_off, const uint64_t* query_off,
+                              uint32_t n_queries, uint32_t ncand, const uint32_t* cand_sid, const int32_t* cand_dlo,
+                              const int32_t* cand_dhi, const uint32_t* cand_n, uint32_t* out_count, uint32_t* out_q_first,
+                              uint32_t* out_q_last, uint32_t* out_t_first, uint32_t* out_t_last, uint32_t* out_hist,
+                              uint32_t* out_shift, uint64_t* out_sum_q, uint64_t* out_sum_u, uint64_t* out_sum_qq,
+                              uint64_t* out_sum_qu);
 /* The catalogue form: the listed songs' rows are gathered on the device as shz_match_songs gathers them and are the queries
  * (song sids[q] is query q, its offsets are the query offsets; no row crosses the bus).  Candidates and outputs as above with
  * n_sids in place of n_queries.  A candidate may be the listed song itself: at d_lo = d_hi = 0 its count is the song's row
@@ -995,6 +1011,43 @@ int32_t shz_recognize_warps(shz_ctx* ctx, shz_table* table, const int16_t* pcm, 
                             uint32_t* out_best, uint32_t* out_sid, int32_t* out_delta, uint32_t* out_aligned, uint32_t* out_dedup,
                             uint32_t* out_nres, uint32_t* out_nhash, uint32_t* out_profile, float* ms_extract, float* ms_warp,
                             float* ms_match);
+/* shz_recognize_warps with the extent pass of shz_match_extents_fit on every query's results (new).  The warped hashes of a
+ * query exist on the device only, so the pass runs inside the call: on every slice of queries, between its match and the
+ * next slice's warp.  The arguments of shz_recognize_warps, then drift_bins and the extent outputs (host).  The recognition
+ * outputs equal shz_recognize_warps' on the same inputs, entry for entry.  The QUERY of the extent pass for query q is the hash
+ * list of its BEST variant -- the union over its channels, as the match saw it --, and candidate n < out_nres[q] is
+ * (out_sid[q, n], out_delta[q, n] - w, out_delta[q, n] + w) with w = the context's vote tolerance + drift_bins; ncand = topn.
+ * out_count / out_q_first / out_q_last / out_t_first / out_t_last / out_sum_q / out_sum_u / out_sum_qq / out_sum_qu
+ * [n_queries topn], out_hist [n_queries topn 64] (may be NULL), out_shift [n_queries]: as shz_match_extents_fit defines them,
+ * zero at and past out_nres[q].  out_q_first / out_q_last, the histogram and the shift are in WARPED frames, the table's
+ * domain, as out_delta is; the sums' q likewise, and u = d - (out_delta - w).  At tolerance 0 and drift_bins 0, out_count ==
+ * out_aligned.  A query whose true tempo a differs from its best rung's lets d = off - t' drift along t' with slope
+ * a / rung - 1: drift_bins widens the candidates so that the drifting pairs belong, and the sums give the slope.
+ * Refused before anything is launched: what shz_recognize_warps refuses; what shz_match_extents refuses about the table; a
+ * NULL extent array other than out_hist, topn > 64 (SHZ_E_INVALID); 2 w + 1 > 4096 (SHZ_E_UNSUPPORTED).  The outputs are
+ * written only by a call that returns SHZ_OK.  Results depend neither on the slicing nor on the extent pass's tiling
+ * (SHZ_DEBUG_SPEED_SMALL_SLICES, SHZ_DEBUG_EXTENT_SMALL_TILES).  ms_extent (may be NULL): the hipEvent time of the extent
+ * stages, the packing of the best variants' hashes included. */
+int32_t shz_recognize_warps_extents(shz_ctx* ctx, shz_table* table, const int16_t* pcm, const uint64_t* clip_off, uint32_t n_clips,
+                                    const uint32_t* query_clip0, uint32_t n_queries, uint32_t fs, double amp_min,
+                                    uint32_t fan_value, uint32_t topn, const uint32_t* tempo_q16, const uint32_t* pitch_q16,
+                                    uint32_t n_warps, uint32_t flags, uint32_t* out_best, uint32_t* out_sid, int32_t* out_delta,
+                                    uint32_t* out_aligned, uint32_t* out_dedup, uint32_t* out_nres, uint32_t* out_nhash,
+                                    uint32_t* out_profile, float* ms_extract, float* ms_warp, float* ms_match, uint32_t drift_bins,
+                                    uint32_t* out_count, uint32_t* out_q_first, uint32_t* out_q_last, uint32_t* out_t_first,
+                                    uint32_t* out_t_last, uint64_t* out_sum_q, uint64_t* out_sum_u, uint64_t* out_sum_qq,
+                                    uint64_t* out_sum_qu, uint32_t* out_hist, uint32_t* out_shift, float* ms_extent);
+/* shz_recognize_warps_extents with the one table speed_q16 for time and frequency (as shz_recognize_speeds is to
+ * shz_recognize_warps; what is refused about the ladder names n_speeds / speed) */
+int32_t shz_recognize_speeds_extents(shz_ctx* ctx, shz_table* table, const int16_t* pcm, const uint64_t* clip_off, uint32_t n_clips,
+                                     const uint32_t* query_clip0, uint32_t n_queries, uint32_t fs, double amp_min,
+                                     uint32_t fan_value, uint32_t topn, const uint32_t* speed_q16, uint32_t n_speeds,
+                                     uint32_t flags, uint32_t* out_best, uint32_t* out_sid, int32_t* out_delta,
+                                     uint32_t* out_aligned, uint32_t* out_dedup, uint32_t* out_nres, uint32_t* out_nhash,
+                                     uint32_t* out_profile, float* ms_extract, float* ms_warp, float* ms_match, uint32_t drift_bins,
+                                     uint32_t* out_count, uint32_t* out_q_first, uint32_t* out_q_last, uint32_t* out_t_first,
+                                     uint32_t* out_t_last, uint64_t* out_sum_q, uint64_t* out_sum_u, uint64_t* out_sum_qq,
+                                     uint64_t* out_sum_qu, uint32_t* out_hist, uint32_t* out_shift, float* ms_extent);
 
 /* ---- scanning at an unknown speed (new; shz_scan_batch and shz_recognize_speeds joined: "which songs play in this hour of
  * broadcast, and when?" where the station pitches its songs up or down) --------------------------------------------------

@@ -103,6 +103,8 @@ SIGNATURES = {
     "shz_table_song_hashes": (C.c_int32, [vp, vp, C.c_uint32, u64p, vp, vp, C.c_uint64, C.c_uint32]),
     "shz_match_songs": (C.c_int32, [vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp]),
     "shz_match_extents": (C.c_int32, [vp, vp, vp, vp, u64p, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "shz_match_extents_fit": (C.c_int32, [vp, vp, vp, vp, u64p, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                          vp, vp, vp, vp]),
     "shz_match_songs_extents": (C.c_int32, [vp, vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "shz_warp_row_host": (C.c_int32, [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp, vp]),
     "shz_warp_rows": (C.c_int32, [vp, vp, vp, u64p, C.c_uint32, u32p, u32p, C.c_uint32, C.c_uint32, vp, vp, u64p, C.c_uint64,
@@ -186,11 +188,19 @@ SIGNATURES = {
     "shz_recognize_speeds": (C.c_int32, [vp, vp, vp, u64p, C.c_uint32, u32p, C.c_uint32, C.c_uint32, C.c_double, C.c_uint32,
                                          C.c_uint32, u32p, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp,
                                          C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "shz_recognize_speeds_extents": (C.c_int32, [vp, vp, vp, u64p, C.c_uint32, u32p, C.c_uint32, C.c_uint32, C.c_double, C.c_uint32,
+                                                 C.c_uint32, u32p, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp,
+                                                 C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint32,
+                                                 vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(C.c_float)]),
     "shz_warp_pair_hash_tf": (C.c_int32, [vp, vp, vp, u64p, C.c_uint32, u32p, C.c_uint32, u32p, u32p, C.c_uint32, C.c_uint32,
                                           C.c_uint32, vp, vp, u64p, C.c_uint64, u64p]),
     "shz_recognize_warps": (C.c_int32, [vp, vp, vp, u64p, C.c_uint32, u32p, C.c_uint32, C.c_uint32, C.c_double, C.c_uint32,
                                         C.c_uint32, u32p, u32p, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp,
                                         C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "shz_recognize_warps_extents": (C.c_int32, [vp, vp, vp, u64p, C.c_uint32, u32p, C.c_uint32, C.c_uint32, C.c_double, C.c_uint32,
+                                                C.c_uint32, u32p, u32p, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp,
+                                                C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint32,
+                                                vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(C.c_float)]),
     "shz_scan_speeds": (C.c_int32, [vp, vp, vp, u64p, C.c_uint32, u32p, C.c_uint32, C.c_uint32, C.c_double, C.c_uint32,
                                     C.c_uint32, C.c_uint32, C.c_uint32, u32p, C.c_uint32, C.c_uint32, u64p, vp, vp, vp, vp, vp, vp,
                                     vp, vp, vp, C.c_uint64, u64p, C.POINTER(C.c_float), C.POINTER(C.c_float),
@@ -899,11 +909,15 @@ class Context:
         return k[:n], t1[:n], ho
 
     def recognize_speeds(self, table: "Table", pcm, clip_off, query_clip0, speeds, fs=44100, amp_min=10.0, fan_value=5, topn=2,
-                         pcm_device=False, full_sort=False):
+                         pcm_device=False, full_sort=False, extents=False, drift_bins=0):
         """shz_recognize_speeds: the peaks of the clips once, every factor of `speeds` (Q16) warped, hashed and matched on
         the device.  Returns (res, ms): res as Table.match over the queries (the best variant's rows; no npairs) plus
         best [nq] (index into speeds) and profile [nq, K] (rank-0 aligned count of every variant); ms = (extract, warp,
-        match) device times."""
+        match) device times.  extents / drift_bins: as recognize_warps' (shz_recognize_speeds_extents)."""
+        if extents:
+            sp = np.ascontiguousarray(speeds, np.uint32)
+            return self._recognize_extents("shz_recognize_speeds_extents", table, pcm, clip_off, query_clip0, [sp], fs, amp_min,
+                                           fan_value, topn, pcm_device, full_sort, drift_bins)
         co, nc = self._clip_off(clip_off)
         qc = np.ascontiguousarray(query_clip0, np.uint32)
         sp = np.ascontiguousarray(speeds, np.uint32)
@@ -955,16 +969,49 @@ class Context:
         self.check(rc)
         return k[:n], t1[:n], ho
 
+    def _recognize_extents(self, symbol, table, pcm, clip_off, query_clip0, ladders, fs, amp_min, fan_value, topn, pcm_device,
+                           full_sort, drift_bins):
+        """shz_recognize_warps_extents (ladders = [tempos, pitches]) / shz_recognize_speeds_extents (ladders = [speeds]): (res,
+        ms) with the extent arrays in res and ms = (extract, warp, match, extent)"""
+        co, nc = self._clip_off(clip_off)
+        qc = np.ascontiguousarray(query_clip0, np.uint32)
+        nq, K = len(qc) - 1, len(ladders[0])
+        res = _match_result(nq, topn)
+        del res["npairs"]
+        res["best"], res["profile"] = np.zeros(nq, np.uint32), np.zeros((nq, K), np.uint32)
+        ext32, ext64 = ("count", "q_first", "q_last", "t_first", "t_last"), ("sum_q", "sum_u", "sum_qq", "sum_qu")
+        res.update({k: np.zeros((nq, topn), np.uint32) for k in ext32})
+        res.update({k: np.zeros((nq, topn), np.uint64) for k in ext64})
+        res["hist"], res["shift"] = np.zeros((nq, topn, 64), np.uint32), np.zeros(nq, np.uint32)
+        ms = [C.c_float(), C.c_float(), C.c_float(), C.c_float()]
+        self.check(getattr(lib(), symbol)(self.h, table.h, ptr(pcm), co.ctypes.data_as(u64p), nc, qc.ctypes.data_as(u32p), nq,
+                                          int(fs), float(amp_min), int(fan_value), int(topn),
+                                          *[a.ctypes.data_as(u32p) for a in ladders], K,
+                                          (PCM_DEVICE if pcm_device else 0) | (MATCH_FULL_SORT if full_sort else 0),
+                                          ptr(res["best"]), ptr(res["sid"]), ptr(res["delta"]), ptr(res["aligned"]),
+                                          ptr(res["dedup"]), ptr(res["nres"]), ptr(res["nhash"]), ptr(res["profile"]),
+                                          *[C.byref(m) for m in ms[:3]], int(drift_bins), *[ptr(res[k]) for k in ext32 + ext64],
+                                          ptr(res["hist"]), ptr(res["shift"]), C.byref(ms[3])))
+        return res, tuple(float(m.value) for m in ms)
+
     def recognize_warps(self, table: "Table", pcm, clip_off, query_clip0, tempos, pitches, fs=44100, amp_min=10.0, fan_value=5,
-                        topn=2, pcm_device=False, full_sort=False):
+                        topn=2, pcm_device=False, full_sort=False, extents=False, drift_bins=0):
         """shz_recognize_warps: recognize_speeds with a time and a frequency factor of its own for every variant (warp v is
         (tempos[v], pitches[v]), Q16).  Returns (res, ms) shaped as recognize_speeds': best [nq] indexes the warps, profile
-        is [nq, n_warps]."""
+        is [nq, n_warps].
+        extents (shz_recognize_warps_extents): the extent pass on the best variant's hashes, candidate n of query q being
+        (sid[q, n], delta[q, n] - w, delta[q, n] + w) with w = the vote tolerance + drift_bins.  res gains count, q_first,
+        q_last, t_first, t_last [nq, topn] (q_* in WARPED frames, as delta), the moments sum_q, sum_u, sum_qq, sum_qu
+        [nq, topn] (uint64; extent.line_fit), hist [nq, topn, 64] and shift [nq]; ms gains a fourth entry, the extent
+        stage."""
         co, nc = self._clip_off(clip_off)
         qc = np.ascontiguousarray(query_clip0, np.uint32)
         tq, fq = np.ascontiguousarray(tempos, np.uint32), np.ascontiguousarray(pitches, np.uint32)
         if tq.shape != fq.shape or tq.ndim != 1:
             raise ValueError("tempos and pitches are two lists of one length: warp v is (tempos[v], pitches[v])")
+        if extents:
+            return self._recognize_extents("shz_recognize_warps_extents", table, pcm, clip_off, query_clip0, [tq, fq], fs, amp_min,
+                                           fan_value, topn, pcm_device, full_sort, drift_bins)
         nq = len(qc) - 1
         res = _match_result(nq, topn)
         del res["npairs"]
@@ -1386,16 +1433,26 @@ class Table:
         res["shift"] = np.zeros(n, np.uint32)
         return cs, lo, hi, cn, ncand, res
 
-    def match_extents(self, key32, q_off, query_off, cand_sid, d_lo, d_hi, cand_n=None, hist=True):
+    def match_extents(self, key32, q_off, query_off, cand_sid, d_lo, d_hi, cand_n=None, hist=True, fit=False):
         """Where the aligned hashes lie (shz_match_extents): per query and candidate (song cand_sid, offset differences d_lo ..
         d_hi inclusive) the pairs that belong -- count, q_first / q_last (query frames), t_first / t_last (song frames) as
         [n, ncand], hist [n, ncand, 64] (pairs per bucket q_off >> shift; None with hist false), shift [n].  Candidates are
-        [n, ncand] arrays, of which query q uses the first cand_n[q] (None: all); everything past them is zero."""
+        [n, ncand] arrays, of which query q uses the first cand_n[q] (None: all); everything past them is zero.
+        fit (shz_match_extents_fit): the moments of every candidate's pairs too -- sum_q, sum_u, sum_qq, sum_qu [n, ncand]
+        (uint64, modulo 2^64) with q = q_off and u = (off - q_off) - d_lo; a used candidate must span less than 4,096 bins."""
         k = np.ascontiguousarray(key32, np.uint32)
         o = np.ascontiguousarray(q_off, np.uint32)
         qo = np.ascontiguousarray(query_off, np.uint64)
         n = len(qo) - 1
         cs, lo, hi, cn, ncand, res = self._extent_args(n, cand_sid, d_lo, d_hi, cand_n, hist)
+        if fit:
+            sums = {f: np.zeros((n, ncand), np.uint64) for f in ("sum_q", "sum_u", "sum_qq", "sum_qu")}
+            self.ctx.check(lib().shz_match_extents_fit(self.ctx.h, self.h, ptr(k), ptr(o), qo.ctypes.data_as(u64p), n, ncand, ptr(cs),
+                                                       ptr(lo), ptr(hi), ptr(cn), ptr(res["count"]), ptr(res["q_first"]),
+                                                       ptr(res["q_last"]), ptr(res["t_first"]), ptr(res["t_last"]),
+                                                       ptr(res["hist"]), ptr(res["shift"]), *[ptr(a) for a in sums.values()]))
+            res.update(sums)
+            return res
         self.ctx.check(lib().shz_match_extents(self.ctx.h, self.h, ptr(k), ptr(o), qo.ctypes.data_as(u64p), n, ncand, ptr(cs),
                                                ptr(lo), ptr(hi), ptr(cn), ptr(res["count"]), ptr(res["q_first"]),
                                                ptr(res["q_last"]), ptr(res["t_first"]), ptr(res["t_last"]), ptr(res["hist"]),

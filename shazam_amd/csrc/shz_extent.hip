@@ -13,6 +13,12 @@
 // touches.  Almost every pair misses: load, compare, nothing.  A hit is accumulated with integer atomicAdd / atomicMin /
 // atomicMax alone -- in LDS for those queries, flushed once per (chunk, candidate touched) -- so no order changes a result.
 // The rows of a key are streamed: nothing here relies on their order inside the key.
+//
+// The moments of a candidate's pairs (shz_match_extents_fit, and the extent stage of
+// shz_recognize_warps_extents): with q = q_off and u = d - d_lo of every pair that belongs, sum q, sum u, sum q^2 and sum q u
+// in unsigned 64 bits, accumulated where the count is -- four 64-bit LDS adds a hit into one 32-byte cell of the candidate
+// (an LDS atomic costs what a store costs at either width, experiments/lds_ops/README.md), flushed with the count; 64-bit
+// global adds for the other queries.  The kernel is a template: without the moments it is the code it was.
 #include "shz_table_int.h"
 
 #define EX_QOFF_BITS 20
@@ -134,6 +140,7 @@ struct ex_cands {                 // the call's candidates and outputs on the de
   uint32_t *count, *q_first, *q_last, *t_first, *t_last;
   uint32_t* hist;                 // [n_queries * ncand * 64], or NULL
   uint32_t ncand;
+  unsigned long long* fit;        // [n_queries * ncand][4]: sum q, sum u, sum q^2, sum q u of every candidate, or NULL
 };
 
 // one hit of candidate cell (query * ncand + slot), straight to global memory
@@ -144,9 +151,17 @@ __device__ __forceinline__ void ex_hit_global(const ex_cands& C, uint64_t cell, 
   atomicMin(C.t_first + cell, off);
   atomicMax(C.t_last + cell, off);
 }
+// the four moments of one hit, q = q_off and u = d - d_lo < EX_FIT_MAX_WIDTH (so q u < 2^32), added to a cell's four words
+__device__ __forceinline__ void ex_hit_fit(unsigned long long* __restrict__ f, uint32_t qo, uint32_t u) {
+  atomicAdd(f + 0, (unsigned long long)qo);
+  atomicAdd(f + 1, (unsigned long long)u);
+  atomicAdd(f + 2, (unsigned long long)qo * qo);
+  atomicAdd(f + 3, (unsigned long long)qo * u);
+}
 
 // tile = pairs [blockIdx.x * tile, ... + tile) of the sub-batch's P; po[x] = pairs in front of x = (element, segment), nx + 1
-// entries at least (po[nx] = P); q0 = the sub-batch's first query in the call
+// entries at least (po[nx] = P); q0 = the sub-batch's first query in the call.  FIT: the moments too (C.fit is not NULL)
+template <bool FIT>
 __global__ __launch_bounds__(256) void ex_pairs_kernel(const uint64_t* __restrict__ E, const uint64_t* __restrict__ po,
                                                         const uint32_t* __restrict__ g_lo, uint32_t nx, uint32_t nseg,
                                                         const shz_seg_dev* __restrict__ segs, uint64_t P, uint32_t tile,
@@ -161,6 +176,7 @@ __global__ __launch_bounds__(256) void ex_pairs_kernel(const uint64_t* __restric
       s_tmin[EX_QC * EX_MAX_CAND], s_tmax[EX_QC * EX_MAX_CAND];
   __shared__ uint32_t s_cn[EX_QC], s_shift[EX_QC];
   __shared__ uint32_t s_x[2];
+  __shared__ unsigned long long s_fit[FIT ? EX_QC * EX_MAX_CAND * 4 : 1];   // 8 KB: a candidate's four sums side by side
 #ifdef EX_DIRECT_ATOMICS
   const bool lds_acc = false;
 #else
@@ -198,6 +214,8 @@ __global__ __launch_bounds__(256) void ex_pairs_kernel(const uint64_t* __restric
         s_cnt[i] = 0; s_qmin[i] = 0xFFFFFFFFu; s_qmaxv[i] = 0; s_tmin[i] = 0xFFFFFFFFu; s_tmax[i] = 0;
       }
       if (tid < EX_QC) s_cn[tid] = 0;
+      if (FIT)
+        for (uint32_t i = tid; i < EX_QC * EX_MAX_CAND * 4; i += 256) s_fit[i] = 0;
     }
     __syncthreads();
     if (lds_acc) {
@@ -247,6 +265,7 @@ __global__ __launch_bounds__(256) void ex_pairs_kernel(const uint64_t* __restric
             atomicMax(s_qmaxv + k, qo);
             atomicMin(s_tmin + k, off);
             atomicMax(s_tmax + k, off);
+            if (FIT) ex_hit_fit(s_fit + 4 * k, qo, (uint32_t)(d - (int64_t)s_clo[k]));
             if (C.hist) atomicAdd(C.hist + ((((uint64_t)q0 + q) * ncand + c) << 6) + (qo >> s_shift[j]), 1u);
           }
         }
@@ -257,6 +276,7 @@ __global__ __launch_bounds__(256) void ex_pairs_kernel(const uint64_t* __restric
           const uint64_t cell = gq * ncand + c;
           if (C.sid[cell] == sid && d >= (int64_t)C.dlo[cell] && d <= (int64_t)C.dhi[cell]) {
             ex_hit_global(C, cell, qo, off);
+            if (FIT) ex_hit_fit(C.fit + 4 * cell, qo, (uint32_t)(d - (int64_t)C.dlo[cell]));
             if (C.hist) atomicAdd(C.hist + (cell << 6) + (qo >> ex_shift_of(C.qmax[gq])), 1u);
           }
         }
@@ -273,6 +293,8 @@ __global__ __launch_bounds__(256) void ex_pairs_kernel(const uint64_t* __restric
         atomicMax(C.q_last + cell, s_qmaxv[i]);
         atomicMin(C.t_first + cell, s_tmin[i]);
         atomicMax(C.t_last + cell, s_tmax[i]);
+        if (FIT)
+          for (uint32_t k = 0; k < 4; ++k) atomicAdd(C.fit + 4 * cell + k, s_fit[4 * i + k]);
       }
       __syncthreads();
     }
@@ -321,12 +343,17 @@ int32_t ex_check(shz_ctx* ctx, shz_table* t, const char* who, const ex_args& A) 
   if (!A.cand_sid || !A.cand_dlo || !A.cand_dhi || !A.cand_n) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: NULL candidate array", who);
   if (!A.out_count || !A.out_q_first || !A.out_q_last || !A.out_t_first || !A.out_t_last || !A.out_shift)
     SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: NULL output array", who);
+  const int nfit = !!A.out_sum_q + !!A.out_sum_u + !!A.out_sum_qq + !!A.out_sum_qu;
+  if (nfit != 0 && nfit != 4) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: NULL sum array (all four, or none)", who);
   for (uint32_t q = 0; q < A.n_queries; ++q) {
     if (A.cand_n[q] > A.ncand) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: cand_n[%u] = %u is above ncand = %u", who, q, A.cand_n[q], A.ncand);
     for (uint32_t c = 0; c < A.cand_n[q]; ++c) {
       const uint64_t i = (uint64_t)q * A.ncand + c;
       if (A.cand_dlo[i] > A.cand_dhi[i])
         SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: candidate %u of query %u has d_lo = %d above d_hi = %d", who, c, q, A.cand_dlo[i], A.cand_dhi[i]);
+      if (nfit && (int64_t)A.cand_dhi[i] - A.cand_dlo[i] >= EX_FIT_MAX_WIDTH)
+        SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "%s: candidate %u of query %u spans d_lo = %d .. d_hi = %d; with the sums d_hi - d_lo must be < %d",
+                 who, c, q, A.cand_dlo[i], A.cand_dhi[i], EX_FIT_MAX_WIDTH);
     }
   }
   return ex_table_limits(ctx, t, who);
@@ -362,7 +389,9 @@ int32_t ex_device(shz_ctx* ctx, shz_table* t, const char* who, const uint32_t* d
   SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_EX_CAND, cells * 12 + (uint64_t)nq_all * 4, &d_cand));
   SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_EX_CTL, 256 + (uint64_t)nq_all * 8, &d_ctl));   // exctl | qmax | shift
   const uint64_t hist_words = A.out_hist ? cells * EX_HIST : 0;
-  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_EX_OUT, (cells * 5 + hist_words) * 4, &d_out));
+  const bool fit = A.out_sum_q != nullptr;
+  const uint64_t fit_at = ((cells * 5 + hist_words) * 4 + 7) & ~7ull, out_bytes = fit_at + (fit ? cells * 32 : 0);   // ... | the sums
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_EX_OUT, out_bytes, &d_out));
   SHZ_HIP(ctx, shz_memcpy(ctx, d_segs, hsegs.data(), sizeof(shz_seg_dev) * nseg, hipMemcpyHostToDevice));
   SHZ_HIP(ctx, shz_memcpy(ctx, d_qoff, query_off, ((uint64_t)nq_all + 1) * 8, hipMemcpyHostToDevice));
   uint32_t* dc = (uint32_t*)d_cand;
@@ -375,8 +404,9 @@ int32_t ex_device(shz_ctx* ctx, shz_table* t, const char* who, const uint32_t* d
   uint32_t* d_shift = d_qmax + nq_all;
   uint32_t* o = (uint32_t*)d_out;
   ex_cands C{dc, (const int32_t*)(dc + cells), (const int32_t*)(dc + 2 * cells), dc + 3 * cells, d_qmax,
-             o, o + cells, o + 2 * cells, o + 3 * cells, o + 4 * cells, A.out_hist ? o + 5 * cells : nullptr, ncand};
-  SHZ_HIP(ctx, hipMemsetAsync(d_out, 0, (cells * 5 + hist_words) * 4, ctx->stream));
+             o, o + cells, o + 2 * cells, o + 3 * cells, o + 4 * cells, A.out_hist ? o + 5 * cells : nullptr, ncand,
+             fit ? (unsigned long long*)((char*)d_out + fit_at) : nullptr};
+  SHZ_HIP(ctx, hipMemsetAsync(d_out, 0, out_bytes, ctx->stream));
   SHZ_HIP(ctx, hipMemsetAsync(d_qmax, 0, (uint64_t)nq_all * 4, ctx->stream));
   hipLaunchKernelGGL(ex_init_kernel, dim3(nblk(cells)), dim3(256), 0, ctx->stream, C.q_first, C.t_first, cells);
   SHZ_HIP(ctx, hipGetLastError());
@@ -423,9 +453,9 @@ int32_t ex_device(shz_ctx* ctx, shz_table* t, const char* who, const uint32_t* d
     const uint64_t ntiles = (h.P + tile - 1) / tile;
     if (ntiles >= (1ull << 31)) SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "%s: %llu pairs in one sub-batch", who, h.P);
     if (ntiles) {
-      hipLaunchKernelGGL(ex_pairs_kernel, dim3((unsigned)ntiles), dim3(256), 0, ctx->stream, (const uint64_t*)E, (const uint64_t*)po,
-                         (const uint32_t*)lo, (uint32_t)(h.mu * nseg), nseg, (const shz_seg_dev*)d_segs, (uint64_t)h.P, tile, sub_cap,
-                         q0, C);
+      hipLaunchKernelGGL(fit ? ex_pairs_kernel<true> : ex_pairs_kernel<false>, dim3((unsigned)ntiles), dim3(256), 0, ctx->stream,
+                         (const uint64_t*)E, (const uint64_t*)po, (const uint32_t*)lo, (uint32_t)(h.mu * nseg), nseg,
+                         (const shz_seg_dev*)d_segs, (uint64_t)h.P, tile, sub_cap, q0, C);
       SHZ_HIP(ctx, hipGetLastError());
     }
     q0 += nq;
@@ -437,30 +467,33 @@ int32_t ex_device(shz_ctx* ctx, shz_table* t, const char* who, const uint32_t* d
   std::vector<uint32_t> hres(cells * 5 + hist_words + nq_all);
   SHZ_HIP(ctx, shz_memcpy(ctx, hres.data(), d_out, (cells * 5 + hist_words) * 4, hipMemcpyDeviceToHost));
   SHZ_HIP(ctx, shz_memcpy(ctx, hres.data() + cells * 5 + hist_words, d_shift, (uint64_t)nq_all * 4, hipMemcpyDeviceToHost));
+  std::vector<uint64_t> hfit(fit ? cells * 4 : 0);
+  if (fit && cells) SHZ_HIP(ctx, shz_memcpy(ctx, hfit.data(), C.fit, cells * 32, hipMemcpyDeviceToHost));
   SHZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
   uint32_t* outs[5] = {A.out_count, A.out_q_first, A.out_q_last, A.out_t_first, A.out_t_last};
   for (int k = 0; k < 5; ++k) memcpy(outs[k], hres.data() + cells * k, cells * 4);
   if (A.out_hist) memcpy(A.out_hist, hres.data() + cells * 5, hist_words * 4);
   memcpy(A.out_shift, hres.data() + cells * 5 + hist_words, (uint64_t)nq_all * 4);
+  for (uint64_t i = 0; fit && i < cells; ++i) {
+    A.out_sum_q[i] = hfit[4 * i];
+    A.out_sum_u[i] = hfit[4 * i + 1];
+    A.out_sum_qq[i] = hfit[4 * i + 2];
+    A.out_sum_qu[i] = hfit[4 * i + 3];
+  }
   return SHZ_OK;
 }
 
-extern "C" int32_t shz_match_extents(shz_ctx* ctx, shz_table* t, const uint32_t* key32, const uint32_t* q_off,
-                                     const uint64_t* query_off, uint32_t n_queries, uint32_t ncand, const uint32_t* cand_sid,
-                                     const int32_t* cand_dlo, const int32_t* cand_dhi, const uint32_t* cand_n, uint32_t* out_count,
-                                     uint32_t* out_q_first, uint32_t* out_q_last, uint32_t* out_t_first, uint32_t* out_t_last,
-                                     uint32_t* out_hist, uint32_t* out_shift) {
-  if (!ctx || !t) return SHZ_E_INVALID;
-  const char* who = "shz_match_extents";
-  SHZ_TRY(ex_state(ctx, t, who, ncand));
+// the host-array form, with the sums (shz_match_extents_fit) or without: A holds everything but the queries
+static int32_t ex_host(shz_ctx* ctx, shz_table* t, const char* who, const uint32_t* key32, const uint32_t* q_off,
+                       const uint64_t* query_off, const ex_args& A) {
+  const uint32_t n_queries = A.n_queries;
+  SHZ_TRY(ex_state(ctx, t, who, A.ncand));
   if (n_queries == 0) return SHZ_OK;
   if (!query_off) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: query_off is NULL", who);
   for (uint32_t q = 0; q < n_queries; ++q)
     if (query_off[q + 1] < query_off[q]) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: query_off decreases at query %u", who, q);
   const uint64_t h0 = query_off[0], h1 = query_off[n_queries];
   if (h1 > h0 && (!key32 || !q_off)) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: NULL column", who);
-  const ex_args A{n_queries, ncand, cand_sid, cand_dlo, cand_dhi, cand_n, out_count, out_q_first, out_q_last, out_t_first,
-                  out_t_last, out_hist, out_shift};
   SHZ_TRY(ex_check(ctx, t, who, A));
   for (uint64_t i = h0; i < h1; ++i)
     if (q_off[i] >> EX_QOFF_BITS) SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "%s: query offset %u; offsets must be < 2^20", who, q_off[i]);
@@ -478,6 +511,35 @@ extern "C" int32_t shz_match_extents(shz_ctx* ctx, shz_table* t, const uint32_t*
   const int32_t rc = ex_device(ctx, t, who, (const uint32_t*)d_key, (const uint32_t*)d_qo, rel.data(), A);
   if (rc != SHZ_OK) (void)hipStreamSynchronize(ctx->stream);
   return rc;
+}
+
+extern "C" int32_t shz_match_extents(shz_ctx* ctx, shz_table* t, const uint32_t* key32, const uint32_t* q_off,
+                                     const uint64_t* query_off, uint32_t n_queries, uint32_t ncand, const uint32_t* cand_sid,
+                                     const int32_t* cand_dlo, const int32_t* cand_dhi, const uint32_t* cand_n, uint32_t* out_count,
+                                     uint32_t* out_q_first, uint32_t* out_q_last, uint32_t* out_t_first, uint32_t* out_t_last,
+                                     uint32_t* out_hist, uint32_t* out_shift) {
+  if (!ctx || !t) return SHZ_E_INVALID;
+  const ex_args A{n_queries, ncand, cand_sid, cand_dlo, cand_dhi, cand_n, out_count, out_q_first, out_q_last, out_t_first,
+                  out_t_last, out_hist, out_shift};
+  return ex_host(ctx, t, "shz_match_extents", key32, q_off, query_off, A);
+}
+
+extern "C" int32_t shz_match_extents_fit(shz_ctx* ctx, shz_table* t, const uint32_t* key32, const uint32_t* q_off,
+                                         const uint64_t* query_off, uint32_t n_queries, uint32_t ncand, const uint32_t* cand_sid,
+                                         const int32_t* cand_dlo, const int32_t* cand_dhi, const uint32_t* cand_n,
+                                         uint32_t* out_count, uint32_t* out_q_first, uint32_t* out_q_last, uint32_t* out_t_first,
+                                         uint32_t* out_t_last, uint32_t* out_hist, uint32_t* out_shift, uint64_t* out_sum_q,
+                                         uint64_t* out_sum_u, uint64_t* out_sum_qq, uint64_t* out_sum_qu) {
+  if (!ctx || !t) return SHZ_E_INVALID;
+  if (n_queries && (!out_sum_q || !out_sum_u || !out_sum_qq || !out_sum_qu))
+    SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_match_extents_fit: NULL sum array");
+  ex_args A{n_queries, ncand, cand_sid, cand_dlo, cand_dhi, cand_n, out_count, out_q_first, out_q_last, out_t_first,
+            out_t_last, out_hist, out_shift};
+  A.out_sum_q = out_sum_q;
+  A.out_sum_u = out_sum_u;
+  A.out_sum_qq = out_sum_qq;
+  A.out_sum_qu = out_sum_qu;
+  return ex_host(ctx, t, "shz_match_extents_fit", key32, q_off, query_off, A);
 }
 
 extern "C" int32_t shz_match_songs_extents(shz_ctx* ctx, shz_table* t, const uint32_t* sids, uint32_t n_sids, uint32_t ncand,

@@ -107,6 +107,9 @@ enum {
   SHZ_WS_EX_CTL,     // ... control block of a sub-batch | largest offset of every query | its shift
   SHZ_WS_EX_OUT,     // ... count | q_first | q_last | t_first | t_last | histograms of every candidate
   SHZ_WS_EX_LO, SHZ_WS_EX_ROWS, SHZ_WS_EX_PO,   // ... per (element, segment): first row, rows, pairs in front of it
+  SHZ_WS_SP_XTAB,    // shz_speed.hip, the extent stage of shz_recognize_warps_extents: first hash of every query's best variant in the
+                     // slice's columns | the CSR of the packed queries
+  SHZ_WS_SP_XKEY, SHZ_WS_SP_XT1,   // ... the hashes of the best variants of a slice, packed one query behind the other
   SHZ_WS_COUNT
 };
 
@@ -136,7 +139,7 @@ struct shz_ctx {
   bool tev_init = false;
   hipEvent_t rq_ev[3] = {nullptr, nullptr, nullptr};   // shz_recognize_batch: start, extraction done, match done (created on first use)
   hipEvent_t sc_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // shz_scan_batch / shz_scan_speeds: start, extraction done (then: a warp begun / done); the window stage: a step begun / done, the match behind it done (created on first use)
-  hipEvent_t sp_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // shz_recognize_speeds / shz_match_songs_warps: start, peaks (rows) done, a slice's warp begun / done, its match done (created on first use)
+  hipEvent_t sp_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // shz_recognize_speeds / shz_match_songs_warps: start, peaks (rows) done, a slice's warp begun / done, its match done, its extent pass done (created on first use)
   bool profiling = false;
   float kernel_ms[8] = {0};
   uint32_t kernel_launches[8] = {0};
@@ -252,9 +255,13 @@ struct ex_args {   // what every caller hands over (host arrays but the two quer
   const int32_t *cand_dlo, *cand_dhi;
   const uint32_t* cand_n;
   uint32_t *out_count, *out_q_first, *out_q_last, *out_t_first, *out_t_last, *out_hist, *out_shift;
+  // the moments of every candidate's pairs, [n_queries * ncand] each: all four NULL (not computed) or none
+  uint64_t *out_sum_q = nullptr, *out_sum_u = nullptr, *out_sum_qq = nullptr, *out_sum_qu = nullptr;
 };
+#define EX_FIT_MAX_WIDTH 4096   // with the moments, d_hi - d_lo stays below it: q u < 2^32 and no sum but sum_qq can wrap
 // what every form refuses before anything is launched: the table's state (ex_state), its offsets (ex_table_limits: a part of
-// ex_check, for callers whose candidates do not exist yet when they must refuse), the candidates and outputs (ex_check; n > 0)
+// ex_check, for callers whose candidates do not exist yet when they must refuse), the candidates and outputs (ex_check; n > 0;
+// with the moments asked for: all four arrays, and every used candidate narrower than EX_FIT_MAX_WIDTH)
 int32_t ex_state(shz_ctx* ctx, shz_table* t, const char* who, uint32_t ncand);
 int32_t ex_table_limits(shz_ctx* ctx, shz_table* t, const char* who);
 int32_t ex_check(shz_ctx* ctx, shz_table* t, const char* who, const ex_args& A);
@@ -327,11 +334,23 @@ int32_t sp_write(shz_ctx* ctx, const sp_pass& P, uint32_t* d_key, uint32_t* d_t1
 // sp_best -- shared with the peak-window listeners (shz_stream.hip).  peak_off: host CSR from 0 over n_clips clips; t_max: the
 // largest warped time (the match's bias bound); flags: SHZ_MATCH_FULL_SORT; out_nhash / out_profile may be NULL; timed:
 // ms_warp / ms_match (may be NULL) get the two stages' hipEvent times
+// X (may be NULL: no extent stage): the extent pass of every slice on the hashes of its queries' best variants, which exist
+// on the device only until the next slice is warped -- candidate n < nres of query q is (sid, delta - w, delta + w); the
+// outputs [n_queries * topn] ([... * 64] for hist, which may be NULL; [n_queries] for shift) are written when the whole call
+// succeeded; ms_extent (may be NULL) gets the stage's hipEvent time with `timed`
+struct sp_extent {
+  uint32_t w;
+  uint32_t *count, *q_first, *q_last, *t_first, *t_last;
+  uint64_t *sum_q, *sum_u, *sum_qq, *sum_qu;
+  uint32_t *hist, *shift;
+  float* ms_extent;
+};
 int32_t sp_match_fold(shz_ctx* ctx, shz_table* t, const uint16_t* d_pf, const uint32_t* d_pt, const uint64_t* peak_off,
                       uint32_t n_clips, const uint32_t* query_clip0, uint32_t n_queries, uint32_t fan_value, uint32_t topn,
                       const uint32_t* tempo_q16, const uint32_t* pitch_q16, uint32_t K, uint32_t flags, uint64_t t_max,
                       uint32_t* out_best, uint32_t* out_sid, int32_t* out_delta, uint32_t* out_aligned, uint32_t* out_dedup,
-                      uint32_t* out_nres, uint32_t* out_nhash, uint32_t* out_profile, bool timed, float* ms_warp, float* ms_match);
+                      uint32_t* out_nres, uint32_t* out_nhash, uint32_t* out_profile, bool timed, float* ms_warp, float* ms_match,
+                      const sp_extent* X = nullptr);
 // what every entry point with a ladder refuses about it.  n_name: the count's argument ("n_speeds"); t_name / f_name: what a
 // factor of either table is called ("speed", or "tempo" and "pitch"; the table's argument is <name>_q16).  pitch_q16 ==
 // tempo_q16 is one ladder: it is checked, and named, once

@@ -441,17 +441,87 @@ int32_t sp_peaks_owned(shz_ctx* ctx, const char* who, const int16_t* pcm, const 
   return SHZ_OK;
 }
 
+// the hashes of every query's best variant, packed: entry i of the packed columns belongs to the last query q with
+// dst_off[q] <= i (empty queries share a start) and is entry src_off[q] + (i - dst_off[q]) of the slice's columns
+__global__ __launch_bounds__(SP_THREADS) void sp_gather_kernel(const uint32_t* __restrict__ key32, const uint32_t* __restrict__ t1,
+                                                                const uint64_t* __restrict__ src_off /* nq */,
+                                                                const uint64_t* __restrict__ dst_off /* nq + 1 */, uint32_t nq,
+                                                                uint32_t* __restrict__ out_key, uint32_t* __restrict__ out_t1) {
+  const uint64_t i = (uint64_t)blockIdx.x * SP_THREADS + threadIdx.x;
+  if (i >= dst_off[nq]) return;
+  uint32_t lo = 0, hi = nq;
+  while (lo + 1 < hi) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (dst_off[mid] <= i) lo = mid; else hi = mid;
+  }
+  const uint64_t src = src_off[lo] + (i - dst_off[lo]);
+  out_key[i] = key32[src];
+  out_t1[i] = t1[src];
+}
+
+// The extent stage of one slice, between its match and the next slice's warp: the queries [q0, q0 + nq) of
+// the call, whose variants' hashes lie in d_key / d_t1 under query_off (nq * K + 1 entries) and whose match results are v_*
+// (of the whole call, variant-major per query).  The best variant of every query is chosen as step 4 chooses it; its hashes
+// are packed into SHZ_WS_SP_XKEY / _XT1 and go through ex_device, which uses the slots SHZ_WS_EX_*, SORT_A / _B and M1 / _M2:
+// none of them holds anything the later slices need (the peaks and the call's tables are in SHZ_WS_SP_PF / _PT / _TAB).
+// The outputs go to the rows [q0, q0 + nq) of R, the call's own block
+static int32_t sp_extent_slice(shz_ctx* ctx, shz_table* t, const uint32_t* d_key, const uint32_t* d_t1, const uint64_t* query_off,
+                               uint32_t q0, uint32_t nq, uint32_t K, uint32_t topn, const uint32_t* tempo_q16,
+                               const uint32_t* pitch_q16, const uint32_t* v_sid, const int32_t* v_delta, const uint32_t* v_aligned,
+                               const uint32_t* v_nres, uint32_t w, const sp_extent& R) {
+  std::vector<uint64_t> tab((size_t)2 * nq + 1);   // src_off [nq] | dst_off [nq + 1]
+  std::vector<uint32_t> c_sid((size_t)nq * topn, 0), c_n(nq), top1(K);
+  std::vector<int32_t> c_dlo((size_t)nq * topn, 0), c_dhi((size_t)nq * topn, 0);
+  uint64_t* dst = tab.data() + nq;
+  dst[0] = 0;
+  for (uint32_t q = 0; q < nq; ++q) {
+    const uint64_t o = (uint64_t)(q0 + q) * K;
+    for (uint32_t v = 0; v < K; ++v) top1[v] = v_nres[o + v] ? v_aligned[(o + v) * topn] : 0u;
+    const uint32_t b = sp_best(top1.data(), tempo_q16, pitch_q16, K);
+    tab[q] = query_off[(size_t)q * K + b];
+    dst[q + 1] = dst[q] + (query_off[(size_t)q * K + b + 1] - tab[q]);
+    c_n[q] = std::min(v_nres[o + b], topn);
+    for (uint32_t n = 0; n < c_n[q]; ++n) {
+      const int64_t d = v_delta[(o + b) * topn + n];
+      c_sid[(size_t)q * topn + n] = v_sid[(o + b) * topn + n];
+      c_dlo[(size_t)q * topn + n] = (int32_t)std::max<int64_t>(d - w, INT32_MIN);
+      c_dhi[(size_t)q * topn + n] = (int32_t)std::min<int64_t>(d + w, INT32_MAX);
+    }
+  }
+  const uint64_t total = dst[nq];
+  void *d_tab, *xk, *xt;
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SP_XTAB, tab.size() * 8, &d_tab));
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SP_XKEY, total * 4 + 64, &xk));
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SP_XT1, total * 4 + 64, &xt));
+  if (total) {
+    SHZ_HIP(ctx, shz_memcpy(ctx, d_tab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(sp_gather_kernel, dim3(sp_blocks(total)), dim3(SP_THREADS), 0, ctx->stream, d_key, d_t1,
+                       (const uint64_t*)d_tab, (const uint64_t*)d_tab + nq, nq, (uint32_t*)xk, (uint32_t*)xt);
+    SHZ_HIP(ctx, hipGetLastError());
+  }
+  const uint64_t c0 = (uint64_t)q0 * topn;
+  ex_args A{nq, topn, c_sid.data(), c_dlo.data(), c_dhi.data(), c_n.data(), R.count + c0, R.q_first + c0, R.q_last + c0,
+            R.t_first + c0, R.t_last + c0, R.hist ? R.hist + c0 * 64 : nullptr, R.shift + q0};
+  A.out_sum_q = R.sum_q + c0;
+  A.out_sum_u = R.sum_u + c0;
+  A.out_sum_qq = R.sum_qq + c0;
+  A.out_sum_qu = R.sum_qu + c0;
+  return ex_device(ctx, t, "shz_recognize_warps_extents", (const uint32_t*)xk, (const uint32_t*)xt, dst, A);
+}
+
 // Steps 2-4 of a recognition at a ladder, for peaks that lie on the device (shz_recognize_warps after its extraction; the
 // peak-window listeners, shz_stream.hip): the K warps of every query warped, paired and hashed (sp_count / sp_write), all
 // (query, warp) pairs matched as queries of their own, the best variant of every query folded out (sp_best).  d_pf / d_pt:
 // the peaks of n_clips clips, peak_off their CSR from 0 (host); query q is the clips [query_clip0[q], query_clip0[q + 1]).
 // t_max: the largest warped time, the bias bound of the match.  flags: SHZ_MATCH_FULL_SORT.  out_nhash / out_profile may be
-// NULL.  timed: ms_warp / ms_match (may be NULL) get the hipEvent times of the two stages, summed over the slices
+// NULL.  timed: ms_warp / ms_match (may be NULL) get the hipEvent times of the two stages, summed over the slices.  X: the
+// extent stage (shz_internal.h), run on every slice while its hashes are there
 int32_t sp_match_fold(shz_ctx* ctx, shz_table* t, const uint16_t* d_pf, const uint32_t* d_pt, const uint64_t* peak_off,
                       uint32_t n_clips, const uint32_t* query_clip0, uint32_t n_queries, uint32_t fan_value, uint32_t topn,
                       const uint32_t* tempo_q16, const uint32_t* pitch_q16, uint32_t K, uint32_t flags, uint64_t t_max,
                       uint32_t* out_best, uint32_t* out_sid, int32_t* out_delta, uint32_t* out_aligned, uint32_t* out_dedup,
-                      uint32_t* out_nres, uint32_t* out_nhash, uint32_t* out_profile, bool timed, float* ms_warp, float* ms_match) {
+                      uint32_t* out_nres, uint32_t* out_nhash, uint32_t* out_profile, bool timed, float* ms_warp, float* ms_match,
+                      const sp_extent* X) {
   if (timed)
     for (hipEvent_t& e : ctx->sp_ev)
       if (!e) SHZ_HIP(ctx, hipEventCreate(&e));
@@ -468,7 +538,18 @@ int32_t sp_match_fold(shz_ctx* ctx, shz_table* t, const uint16_t* d_pf, const ui
   std::vector<uint32_t> v_sid(nv * topn), v_aligned(nv * topn), v_dedup(nv * topn), v_nres(nv), v_nhash(nv);
   std::vector<int32_t> v_delta(nv * topn);
   std::vector<uint64_t> ho, query_off;
-  float warp_ms = 0.f, match_ms = 0.f;
+  float warp_ms = 0.f, match_ms = 0.f, extent_ms = 0.f;
+  // the extent stage's results, in a block of this call: the caller's arrays are written when every slice is through
+  const uint64_t xc = X ? (uint64_t)n_queries * topn : 0;
+  std::vector<uint32_t> x32(xc * 5 + (X && X->hist ? xc * 64 : 0) + (X ? n_queries : 0));
+  std::vector<uint64_t> x64(xc * 4);
+  sp_extent R{};
+  if (X) {
+    uint32_t* p = x32.data();
+    uint64_t* s = x64.data();
+    R = sp_extent{X->w, p, p + xc, p + 2 * xc, p + 3 * xc, p + 4 * xc, s, s + xc, s + 2 * xc, s + 3 * xc,
+                  X->hist ? p + 5 * xc : nullptr, p + 5 * xc + (X->hist ? xc * 64 : 0), nullptr};
+  }
   for (uint32_t q0 = 0; q0 < n_queries;) {
     uint32_t nq = 1;
     while (q0 + nq < n_queries && nq < max_q &&
@@ -507,10 +588,32 @@ int32_t sp_match_fold(shz_ctx* ctx, shz_table* t, const uint16_t* d_pf, const ui
       warp_ms += a;
       match_ms += b;
     }
+    if (X) {   // (the match's results of the slice are on the host, its hashes still on the device)
+      SHZ_TRY(sp_extent_slice(ctx, t, (const uint32_t*)d_key, (const uint32_t*)d_t1, query_off.data(), q0, nq, K, topn, tempo_q16,
+                              pitch_q16, v_sid.data(), v_delta.data(), v_aligned.data(), v_nres.data(), X->w, R));
+      if (timed) {
+        float c = 0.f;
+        SHZ_HIP(ctx, hipEventRecord(ctx->sp_ev[5], ctx->stream));
+        SHZ_HIP(ctx, hipEventSynchronize(ctx->sp_ev[5]));
+        SHZ_HIP(ctx, hipEventElapsedTime(&c, ctx->sp_ev[4], ctx->sp_ev[5]));
+        extent_ms += c;
+      }
+    }
     q0 += nq;
   }
   if (ms_warp) *ms_warp = warp_ms;
   if (ms_match) *ms_match = match_ms;
+  if (X) {
+    if (X->ms_extent) *X->ms_extent = extent_ms;
+    uint32_t* o32[5] = {X->count, X->q_first, X->q_last, X->t_first, X->t_last};
+    const uint32_t* r32[5] = {R.count, R.q_first, R.q_last, R.t_first, R.t_last};
+    uint64_t* o64[4] = {X->sum_q, X->sum_u, X->sum_qq, X->sum_qu};
+    const uint64_t* r64[4] = {R.sum_q, R.sum_u, R.sum_qq, R.sum_qu};
+    for (int k = 0; k < 5; ++k) memcpy(o32[k], r32[k], xc * 4);
+    for (int k = 0; k < 4; ++k) memcpy(o64[k], r64[k], xc * 8);
+    if (X->hist) memcpy(X->hist, R.hist, xc * 64 * 4);
+    memcpy(X->shift, R.shift, (size_t)n_queries * 4);
+  }
   // 4) the best variant of every query
   std::vector<uint32_t> top1(K);
   for (uint32_t q = 0; q < n_queries; ++q) {
@@ -530,16 +633,17 @@ int32_t sp_match_fold(shz_ctx* ctx, shz_table* t, const uint16_t* d_pf, const ui
   return SHZ_OK;
 }
 
-extern "C" int32_t shz_recognize_warps(shz_ctx* ctx, shz_table* t, const int16_t* pcm, const uint64_t* clip_off, uint32_t n_clips,
-                                       const uint32_t* query_clip0, uint32_t n_queries, uint32_t fs, double amp_min,
-                                       uint32_t fan_value, uint32_t topn, const uint32_t* tempo_q16, const uint32_t* pitch_q16,
-                                       uint32_t n_warps, uint32_t flags, uint32_t* out_best, uint32_t* out_sid, int32_t* out_delta,
-                                       uint32_t* out_aligned, uint32_t* out_dedup, uint32_t* out_nres, uint32_t* out_nhash,
-                                       uint32_t* out_profile, float* ms_extract, float* ms_warp, float* ms_match) {
-  if (!ctx || !t) return SHZ_E_INVALID;
+// shz_recognize_warps, and with X shz_recognize_warps_extents: one driver, the extent stage optional
+static int32_t sp_recognize(shz_ctx* ctx, shz_table* t, const int16_t* pcm, const uint64_t* clip_off, uint32_t n_clips,
+                            const uint32_t* query_clip0, uint32_t n_queries, uint32_t fs, double amp_min, uint32_t fan_value,
+                            uint32_t topn, const uint32_t* tempo_q16, const uint32_t* pitch_q16, uint32_t n_warps, uint32_t flags,
+                            uint32_t* out_best, uint32_t* out_sid, int32_t* out_delta, uint32_t* out_aligned, uint32_t* out_dedup,
+                            uint32_t* out_nres, uint32_t* out_nhash, uint32_t* out_profile, float* ms_extract, float* ms_warp,
+                            float* ms_match, const sp_extent* X) {
   if (ms_extract) *ms_extract = 0.f;
   if (ms_warp) *ms_warp = 0.f;
   if (ms_match) *ms_match = 0.f;
+  if (X && X->ms_extent) *X->ms_extent = 0.f;
   // everything that can be refused is refused before the first launch
   if (flags & ~(SHZ_PCM_DEVICE | SHZ_MATCH_FULL_SORT)) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_recognize_warps: flags may hold SHZ_PCM_DEVICE and SHZ_MATCH_FULL_SORT");
   SHZ_TRY(sp_check_ladder(ctx, "shz_recognize_warps", "n_warps", "tempo", tempo_q16, "pitch", pitch_q16, n_warps, fan_value));
@@ -552,6 +656,18 @@ extern "C" int32_t shz_recognize_warps(shz_ctx* ctx, shz_table* t, const int16_t
   if (fs == 0) SHZ_FAIL(ctx, SHZ_E_INVALID, "Fs must be > 0");
   if (n_clips && !pcm && clip_off[n_clips] > clip_off[0]) SHZ_FAIL(ctx, SHZ_E_INVALID, "pcm is NULL");
   if (!out_best || !out_sid || !out_delta || !out_aligned || !out_dedup || !out_nres) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_recognize_warps: NULL buffer");
+  if (X) {
+    const char* who = "shz_recognize_warps_extents";
+    if (!X->count || !X->q_first || !X->q_last || !X->t_first || !X->t_last || !X->sum_q || !X->sum_u || !X->sum_qq || !X->sum_qu ||
+        !X->shift)
+      SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: NULL extent array", who);
+    if (topn > 64) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: topn must be in [1,64], one candidate a result", who);
+    if (2ull * X->w + 1 > EX_FIT_MAX_WIDTH)
+      SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "%s: vote tolerance + drift_bins = %u; a candidate's 2 w + 1 bins must be <= %d", who, X->w,
+               EX_FIT_MAX_WIDTH);
+    SHZ_TRY(ex_state(ctx, t, who, topn));
+    SHZ_TRY(ex_table_limits(ctx, t, who));
+  }
   const uint32_t K = n_warps, s_max = *std::max_element(tempo_q16, tempo_q16 + K);   // (time alone: the bias bound)
   uint64_t max_frames = 1, frames = 0;
   for (uint32_t c = 0; c < n_clips; ++c) {
@@ -566,7 +682,7 @@ extern "C" int32_t shz_recognize_warps(shz_ctx* ctx, shz_table* t, const int16_t
              (unsigned long long)max_frames, s_max, (unsigned long long)t_max);
   SHZ_TRY(shz_match_ready(ctx, t, topn));
   SHZ_HIP(ctx, hipSetDevice(ctx->device));
-  const bool timed = ms_extract || ms_warp || ms_match;
+  const bool timed = ms_extract || ms_warp || ms_match || (X && X->ms_extent);
   if (timed) {
     for (hipEvent_t& e : ctx->sp_ev)
       if (!e) SHZ_HIP(ctx, hipEventCreate(&e));
@@ -582,9 +698,38 @@ extern "C" int32_t shz_recognize_warps(shz_ctx* ctx, shz_table* t, const int16_t
   // 2-4) warped, hashed, matched in slices of whole queries; the best variant of every query
   SHZ_TRY(sp_match_fold(ctx, t, d_pf, d_pt, peak_off.data(), n_clips, query_clip0, n_queries, fan_value, topn, tempo_q16, pitch_q16,
                         K, flags & SHZ_MATCH_FULL_SORT, t_max, out_best, out_sid, out_delta, out_aligned, out_dedup, out_nres,
-                        out_nhash, out_profile, timed, ms_warp, ms_match));
+                        out_nhash, out_profile, timed, ms_warp, ms_match, X));
   if (timed && ms_extract) SHZ_HIP(ctx, hipEventElapsedTime(ms_extract, ctx->sp_ev[0], ctx->sp_ev[1]));
   return SHZ_OK;
+}
+
+extern "C" int32_t shz_recognize_warps(shz_ctx* ctx, shz_table* t, const int16_t* pcm, const uint64_t* clip_off, uint32_t n_clips,
+                                       const uint32_t* query_clip0, uint32_t n_queries, uint32_t fs, double amp_min,
+                                       uint32_t fan_value, uint32_t topn, const uint32_t* tempo_q16, const uint32_t* pitch_q16,
+                                       uint32_t n_warps, uint32_t flags, uint32_t* out_best, uint32_t* out_sid, int32_t* out_delta,
+                                       uint32_t* out_aligned, uint32_t* out_dedup, uint32_t* out_nres, uint32_t* out_nhash,
+                                       uint32_t* out_profile, float* ms_extract, float* ms_warp, float* ms_match) {
+  if (!ctx || !t) return SHZ_E_INVALID;
+  return sp_recognize(ctx, t, pcm, clip_off, n_clips, query_clip0, n_queries, fs, amp_min, fan_value, topn, tempo_q16, pitch_q16,
+                      n_warps, flags, out_best, out_sid, out_delta, out_aligned, out_dedup, out_nres, out_nhash, out_profile,
+                      ms_extract, ms_warp, ms_match, nullptr);
+}
+
+extern "C" int32_t shz_recognize_warps_extents(
+    shz_ctx* ctx, shz_table* t, const int16_t* pcm, const uint64_t* clip_off, uint32_t n_clips, const uint32_t* query_clip0,
+    uint32_t n_queries, uint32_t fs, double amp_min, uint32_t fan_value, uint32_t topn, const uint32_t* tempo_q16,
+    const uint32_t* pitch_q16, uint32_t n_warps, uint32_t flags, uint32_t* out_best, uint32_t* out_sid, int32_t* out_delta,
+    uint32_t* out_aligned, uint32_t* out_dedup, uint32_t* out_nres, uint32_t* out_nhash, uint32_t* out_profile, float* ms_extract,
+    float* ms_warp, float* ms_match, uint32_t drift_bins, uint32_t* out_count, uint32_t* out_q_first, uint32_t* out_q_last,
+    uint32_t* out_t_first, uint32_t* out_t_last, uint64_t* out_sum_q, uint64_t* out_sum_u, uint64_t* out_sum_qq,
+    uint64_t* out_sum_qu, uint32_t* out_hist, uint32_t* out_shift, float* ms_extent) {
+  if (!ctx || !t) return SHZ_E_INVALID;
+  const uint64_t w = (uint64_t)ctx->vote_tol + drift_bins;
+  const sp_extent X{(uint32_t)std::min<uint64_t>(w, 0xFFFFFFFFull), out_count, out_q_first, out_q_last, out_t_first, out_t_last,
+                    out_sum_q, out_sum_u, out_sum_qq, out_sum_qu, out_hist, out_shift, ms_extent};
+  return sp_recognize(ctx, t, pcm, clip_off, n_clips, query_clip0, n_queries, fs, amp_min, fan_value, topn, tempo_q16, pitch_q16,
+                      n_warps, flags, out_best, out_sid, out_delta, out_aligned, out_dedup, out_nres, out_nhash, out_profile,
+                      ms_extract, ms_warp, ms_match, &X);
 }
 
 // the speed ladder: one table for time and frequency (its own names in what is refused about it)
@@ -602,4 +747,25 @@ extern "C" int32_t shz_recognize_speeds(shz_ctx* ctx, shz_table* t, const int16_
   return shz_recognize_warps(ctx, t, pcm, clip_off, n_clips, query_clip0, n_queries, fs, amp_min, fan_value, topn, speed_q16,
                              speed_q16, n_speeds, flags, out_best, out_sid, out_delta, out_aligned, out_dedup, out_nres, out_nhash,
                              out_profile, ms_extract, ms_warp, ms_match);
+}
+
+extern "C" int32_t shz_recognize_speeds_extents(
+    shz_ctx* ctx, shz_table* t, const int16_t* pcm, const uint64_t* clip_off, uint32_t n_clips, const uint32_t* query_clip0,
+    uint32_t n_queries, uint32_t fs, double amp_min, uint32_t fan_value, uint32_t topn, const uint32_t* speed_q16, uint32_t n_speeds,
+    uint32_t flags, uint32_t* out_best, uint32_t* out_sid, int32_t* out_delta, uint32_t* out_aligned, uint32_t* out_dedup,
+    uint32_t* out_nres, uint32_t* out_nhash, uint32_t* out_profile, float* ms_extract, float* ms_warp, float* ms_match,
+    uint32_t drift_bins, uint32_t* out_count, uint32_t* out_q_first, uint32_t* out_q_last, uint32_t* out_t_first,
+    uint32_t* out_t_last, uint64_t* out_sum_q, uint64_t* out_sum_u, uint64_t* out_sum_qq, uint64_t* out_sum_qu, uint32_t* out_hist,
+    uint32_t* out_shift, float* ms_extent) {
+  if (!ctx || !t) return SHZ_E_INVALID;
+  if (ms_extract) *ms_extract = 0.f;
+  if (ms_warp) *ms_warp = 0.f;
+  if (ms_match) *ms_match = 0.f;
+  if (ms_extent) *ms_extent = 0.f;
+  SHZ_TRY(sp_check_ladder(ctx, "shz_recognize_speeds_extents", "n_speeds", "speed", speed_q16, "speed", speed_q16, n_speeds, fan_value));
+  return shz_recognize_warps_extents(ctx, t, pcm, clip_off, n_clips, query_clip0, n_queries, fs, amp_min, fan_value, topn, speed_q16,
+                                     speed_q16, n_speeds, flags, out_best, out_sid, out_delta, out_aligned, out_dedup, out_nres,
+                                     out_nhash, out_profile, ms_extract, ms_warp, ms_match, drift_bins, out_count, out_q_first,
+                                     out_q_last, out_t_first, out_t_last, out_sum_q, out_sum_u, out_sum_qq, out_sum_qu, out_hist,
+                                     out_shift, ms_extent);
 }

@@ -115,14 +115,66 @@ def warp_hashes_tf(peaks_f, peaks_t, peak_off, tempos, pitches, fan_value: int =
                                                     _check_speeds(pitches, "pitches"), query_clip0, int(fan_value))
 
 
+def default_drift_bins(ctx, clip_samples, tempos, tol: int = 0) -> int:
+    """drift_bins=None of recognize_speeds / recognize_warps: ceil(t_max * h / 65536), clamped so that a candidate's
+    2 (tol + drift) + 1 bins stay within the 4,096 the moments allow.  t_max: the call's largest warped frame as the library
+    computes it, round((max_frames - 1) * largest tempo rung); h: half the largest gap between neighbouring DISTINCT tempo
+    rungs (Q16), 0 for one rung.  Derivation: a query of true tempo a warped at rung r puts its aligned pairs on the line
+    d = t' (a / r - 1) + c (extent.tempo_of).  The best rung is the nearest one, so |a - r| <= h / 65536, and over the warped
+    frames 0 .. t_max the line moves by at most t_max h / 65536 bins.  The match's delta is one bin ON that line, so the
+    range delta +- that many bins holds all of it."""
+    rungs = np.unique(np.asarray(tempos, np.int64))
+    if len(rungs) < 2 or len(clip_samples) == 0:
+        return 0
+    gap = int(np.max(np.diff(rungs)))                                 # 2 h
+    t_max = ((max(max(ctx.frames_of(int(n)) for n in clip_samples), 1) - 1) * int(rungs[-1]) + 32768) >> 16
+    drift = -((-t_max * gap) // (2 * S_ONE))
+    return max(0, min(drift, (4096 - 1) // 2 - int(tol)))
+
+
+def _drift_of(ctx, chans, Fs, resample_to, tempos, drift_bins):
+    """drift_bins of a call over the channels `chans`: the caller's, or default_drift_bins at the lengths the library sees"""
+    if drift_bins is not None:
+        return int(drift_bins)
+    n = [len(c) for c in chans]
+    if resample_to is not None and int(resample_to) != int(Fs):
+        from .resample import out_len, resample_plan
+        L, M = resample_plan(int(Fs), int(resample_to))[:2]
+        n = [out_len(x, L, M) for x in n]
+    return default_drift_bins(ctx, n, tempos, ctx.vote_tolerance)
+
+
+def _add_warp_extents(results, res, q_t16, w: int):
+    """the extent keys of recognize_speeds / recognize_warps(extents=True) from Context.recognize_warps' extent arrays; q_t16:
+    the time factor of every query's best variant; w: vote tolerance + drift_bins, the half-width of every candidate"""
+    from . import _frames_secs
+    from .extent import line_fit, own_frames, tempo_of
+    for q, dicts in enumerate(results):
+        t16 = int(q_t16[q])
+        for n, d in enumerate(dicts):
+            wf, wl, tf, tl = (int(res[f][q, n]) for f in ("q_first", "q_last", "t_first", "t_last"))
+            qf, ql = own_frames(wf, wl, t16)
+            fit = {"count": int(res["count"][q, n]), **{k: int(res[k][q, n]) for k in ("sum_q", "sum_u", "sum_qq", "sum_qu")},
+                   "d_lo": int(res["delta"][q, n]) - int(w)}
+            line = line_fit(**fit)
+            d.update({"query_first": qf, "query_last": ql, "song_first": tf, "song_last": tl,
+                      "query_start_secs": _frames_secs(qf), "query_end_secs": _frames_secs(ql + 1),
+                      "song_start_secs": _frames_secs(tf), "song_end_secs": _frames_secs(tl + 1),
+                      "extent_hist": res["hist"][q, n].copy(), "extent_shift": int(res["shift"][q]),
+                      "warped_first": wf, "warped_last": wl, "fit": fit,
+                      "tempo_fit": None if line is None else float(tempo_of(t16, line[0]))})
+
+
 @takes_delta_tol(lambda *a, **k: (k["db"] if "db" in k else a[1]).ctx)
-def recognize_speeds(queries, db, speeds=None, Fs: int = 44100, topn: int = 2, resample_to: int = None):
+def recognize_speeds(queries, db, speeds=None, Fs: int = 44100, topn: int = 2, resample_to: int = None, extents: bool = False,
+                     drift_bins: int = None):
     """recognize_batch for queries of unknown speed.  Returns (results_per_query, timings) like recognize_batch; every
     result dict carries "speed" (the chosen factor as a float), OFFSET / OFFSET_SECS are in the TABLE's time, and timings
     carries "speeds" (the ladder, Q16), "speed_best" (index per query) and "speed_profile" ([n_queries, K]: the aligned count
     of the top answer of every factor).  speeds=None: speed_ladder().  The chosen factor is the one with the greatest
     aligned count; ties go to the factor nearest 1.0, then to the lower index.
-    delta_tol= (keyword): the vote tolerance in offset bins while the call runs (Context.tolerance); None: the context's."""
+    delta_tol= (keyword): the vote tolerance in offset bins while the call runs (Context.tolerance); None: the context's.
+    extents / drift_bins: as recognize_warps' -- the chosen speed is the rung of both axes, "tempo_fit" the fitted TIME factor."""
     from . import DEFAULT_AMP_MIN, DEFAULT_FAN_VALUE, _as_pcm, _result_dicts, resample_to_device
     if not hasattr(db.table, "h"):
         raise NotImplementedError("fused recognition takes the unsharded table (shards=1)")
@@ -138,6 +190,8 @@ def recognize_speeds(queries, db, speeds=None, Fs: int = 44100, topn: int = 2, r
         first.append(len(chans))
     first = np.asarray(first, np.uint32)
     kw = dict(amp_min=float(DEFAULT_AMP_MIN), fan_value=DEFAULT_FAN_VALUE, topn=int(topn))
+    if extents:
+        kw.update(extents=True, drift_bins=_drift_of(ctx, chans, Fs, resample_to, sp, drift_bins))
     if resample_to is not None and int(resample_to) != int(Fs):   # resampled on the device and handed on there
         buf, off = resample_to_device(chans, int(Fs), int(resample_to), ctx)
         try:
@@ -158,10 +212,14 @@ def recognize_speeds(queries, db, speeds=None, Fs: int = 44100, topn: int = 2, r
         for d in dicts:
             d["speed"] = float(sp[int(res["best"][q])]) / S_ONE
         results.append(dicts)
+    extra = {}
+    if extents:
+        _add_warp_extents(results, res, sp[res["best"]], ctx.vote_tolerance + kw["drift_bins"])
+        extra = {"extent_time": ms[3] * 1e-3, "drift_bins": kw["drift_bins"]}
     align_time = time() - t0
     return results, {"fingerprint_time": ms[0] * 1e-3, "warp_time": ms[1] * 1e-3, "query_time": ms[2] * 1e-3,
                      "align_time": align_time, "n_hashes": res["nhash"], "speeds": sp, "speed_best": res["best"],
-                     "speed_profile": res["profile"]}
+                     "speed_profile": res["profile"], **extra}
 
 
 def _warp_dist(t16, f16):
@@ -191,9 +249,11 @@ def merge_warp_chunks(parts, t16, f16):
     return out
 
 
-def _match_pairs(ctx, table, chans, first, t16, f16, row, Fs, resample_to, kw):
+def _match_pairs(ctx, table, chans, first, t16, f16, row, Fs, resample_to, kw, drift=None):
     """Context.recognize_warps of the queries (chans: every channel, first: the CSR of the queries over them) over the
-    whole pair list, in chunks of whole rows: (res, [ms_extract, ms_warp, ms_match] summed over the chunks)."""
+    whole pair list, in chunks of whole rows: (res, [ms_extract, ms_warp, ms_match, ms_extent] summed over the chunks).
+    drift: None for no extents, else drift_bins (the same in every chunk: merge_warp_chunks then copies the extent arrays of
+    the winning chunk like any other per-query key)."""
     from . import _as_pcm, resample_to_device
     buf = None
     if resample_to is not None and int(resample_to) != int(Fs):   # resampled on the device and handed on there
@@ -205,12 +265,13 @@ def _match_pairs(ctx, table, chans, first, t16, f16, row, Fs, resample_to, kw):
         if arrs:
             off[1:] = np.cumsum([len(a) for a in arrs])
         pcm, fs, dev = (np.concatenate(arrs) if off[-1] else np.zeros(1, np.int16)), int(Fs), False
-    parts, ms = [], np.zeros(3)
+    parts, ms = [], np.zeros(4)
+    xkw = {} if drift is None else dict(extents=True, drift_bins=int(drift))
     try:
         for a, b in warp_chunks(len(t16), row):
-            res, m = ctx.recognize_warps(table, pcm, off, first, t16[a:b], f16[a:b], fs=fs, pcm_device=dev, **kw)
+            res, m = ctx.recognize_warps(table, pcm, off, first, t16[a:b], f16[a:b], fs=fs, pcm_device=dev, **kw, **xkw)
             parts.append(res)
-            ms += m
+            ms[:len(m)] += m
     finally:
         if buf is not None:
             buf.free()
@@ -242,7 +303,7 @@ def _warp_list(tempos, pitches, warps, search):
 
 @takes_delta_tol(lambda *a, **k: (k["db"] if "db" in k else a[1]).ctx)
 def recognize_warps(queries, db, tempos=None, pitches=None, warps=None, search: str = "grid", Fs: int = 44100, topn: int = 2,
-                    resample_to: int = None):
+                    resample_to: int = None, extents: bool = False, drift_bins: int = None):
     """recognize_speeds for queries whose tempo and pitch changed by factors of their own.  Returns (results_per_query,
     timings) like recognize_speeds; every result dict carries "tempo" and "pitch" (the chosen factors as floats: the query
     runs `tempo` times as fast and sounds `pitch` times as high as the table's copy), OFFSET / OFFSET_SECS are in the
@@ -265,7 +326,21 @@ def recognize_warps(queries, db, tempos=None, pitches=None, warps=None, search: 
     for a pair list; for the separable search the pairs differ per query, and the three are those of the second stage --
     "warps" two [n_queries, len(tempos)] arrays, "warp_profile" of that shape -- with the first stage under "stage1"
     ("warps", "warp_best", "warp_profile").
-    delta_tol= (keyword): the vote tolerance in offset bins while the call runs (Context.tolerance); None: the context's."""
+    delta_tol= (keyword): the vote tolerance in offset bins while the call runs (Context.tolerance); None: the context's.
+    extents: every result dict also says WHERE the match holds and what tempo its pairs fit (shz_recognize_warps_extents,
+    DESIGN.md 3.7m): the keys of recognize_batch(extents=True) -- "query_first" / "query_last" and the "query_*_secs" in the
+    QUERY's own frames (extent.own_frames at the chosen time factor), "song_*", "extent_hist", "extent_shift" as the extent
+    pass delivers them (the histogram over WARPED frames) --, "warped_first" / "warped_last" (the table's domain), "fit" (the
+    pairs' count and moments sum_q, sum_u, sum_qq, sum_qu as Python ints, and d_lo) and "tempo_fit" (extent.tempo_of of
+    extent.line_fit on them, a float; None where there is no line).  The candidate of a result is delta +- (the vote
+    tolerance + drift_bins).  drift_bins=None: default_drift_bins of the call's tempo rungs -- the true tempo lies within half
+    a step of the best rung, and the range must hold the drift that leaves (derivation there).  The separable search reports
+    the second stage's extents.  The fit is an unweighted least-squares line: chance pairs inside the range pull it.
+    Measured on an MI355X (scripts/fit_bench.py, profiles/fit_bench.json): note corpus, 8 songs of 30 s, 48
+    queries of 10 s at true tempos 0.97 .. 1.03 against the default tempo ladder -- |tempo_fit - true| 0.00063 at the median,
+    0.0021 at the worst, where |rung - true| is 0.012 and 0.022; every query had a fit; the extent stage took 0.37 ms beside a
+    match of 0.61 ms.  Synthetic notes and a small table: not measured on real time-stretched audio.
+    timings gains "extent_time" and "drift_bins"."""
     from . import DEFAULT_AMP_MIN, DEFAULT_FAN_VALUE, _result_dicts
     if not hasattr(db.table, "h"):
         raise NotImplementedError("fused recognition takes the unsharded table (shards=1)")
@@ -285,24 +360,31 @@ def recognize_warps(queries, db, tempos=None, pitches=None, warps=None, search: 
         return chans, np.asarray(first, np.uint32)
 
     kw = dict(amp_min=float(DEFAULT_AMP_MIN), fan_value=DEFAULT_FAN_VALUE, topn=int(topn))
-    run = lambda idx, a, b, r: _match_pairs(ctx, db.table, *csr(idx), a, b, r, Fs, resample_to, kw)
+    drift = None
+    if extents:   # (from the whole call's clips and tempo rungs, whatever chunk or stage a library call holds)
+        drift = _drift_of(ctx, [c for cs in per_query for c in cs], Fs, resample_to, t16 if search == "grid" else tl, drift_bins)
+    run = lambda idx, a, b, r, x=None: _match_pairs(ctx, db.table, *csr(idx), a, b, r, Fs, resample_to, kw, x)
     extra = {}
     if search == "grid":
-        res, ms = run(range(nq), t16, f16, row)
+        res, ms = run(range(nq), t16, f16, row, drift)
         q_t16, q_f16 = t16[res["best"]], f16[res["best"]]
         shown = (t16, f16)
     else:
         one = np.full(len(pl), S_ONE, np.uint32)
         res1, ms = run(range(nq), one, pl, 1)
         extra["stage1"] = {"warps": (one, pl), "warp_best": res1["best"], "warp_profile": res1["profile"]}
-        res = {k: np.zeros((nq,) + v.shape[1:], v.dtype) for k, v in res1.items() if k != "profile"}
-        res["profile"] = np.zeros((nq, len(tl)), np.uint32)
+        res = None
         for rung in np.unique(res1["best"]).tolist() if nq else []:
             idx = np.flatnonzero(res1["best"] == rung).tolist()
-            part, m = run(idx, tl, np.full(len(tl), pl[rung], np.uint32), 1)
+            part, m = run(idx, tl, np.full(len(tl), pl[rung], np.uint32), 1, drift)
             ms = ms + m
+            if res is None:
+                res = {k: np.zeros((nq,) + v.shape[1:], v.dtype) for k, v in part.items()}
             for k in res:
                 res[k][idx] = part[k]
+        if res is None:
+            res = {k: np.zeros((nq,) + v.shape[1:], v.dtype) for k, v in res1.items() if k != "profile"}
+            res["profile"] = np.zeros((nq, len(tl)), np.uint32)
         q_t16, q_f16 = tl[res["best"]], pl[res1["best"]]
         shown = (np.tile(tl, (nq, 1)), np.repeat(q_f16[:, None], len(tl), axis=1))
     t0 = time()
@@ -312,6 +394,9 @@ def recognize_warps(queries, db, tempos=None, pitches=None, warps=None, search: 
         for d in dicts:
             d["tempo"], d["pitch"] = float(q_t16[q]) / S_ONE, float(q_f16[q]) / S_ONE
         results.append(dicts)
+    if extents:
+        _add_warp_extents(results, res, q_t16, ctx.vote_tolerance + drift)
+        extra.update({"extent_time": ms[3] * 1e-3, "drift_bins": drift})
     align_time = time() - t0
     return results, {"fingerprint_time": ms[0] * 1e-3, "warp_time": ms[1] * 1e-3, "query_time": ms[2] * 1e-3,
                      "align_time": align_time, "n_hashes": res["nhash"], "warps": shown, "warp_best": res["best"],
