@@ -1156,6 +1156,78 @@ int32_t shz_scan_timeline_warps(const uint64_t* win_off, uint32_t n_recs, const 
                                 uint32_t* seg_hits, uint32_t* seg_best, int32_t* seg_pos_first, int32_t* seg_pos_last,
                                 uint32_t* seg_warp, uint64_t cap, uint64_t* count);
 
+/* ---- warped scan extents (new): frame-accurate play bounds and a tempo fit for every segment of a speed-,
+ * tempo- or pitch-tolerant scan.  shz_scan_extents serves the plain scan, whose segments have one constant shift.  A segment of
+ * shz_scan_timeline_speeds / _warps has none: the recording plays at a tempo of its own, the rung its windows chose is only
+ * near it, and the offset difference DRIFTS over the play.  So every segment brings its own pair (t16, f16) -- Q16 VALUES, not
+ * indices, which serves ladders, pair lists, chunked grids and the separable search alike (a speed is t16 == f16) --, its zones
+ * are cut from hash lists warped at that pair, and the candidate of a zone is widened by drift_bins and comes back with the
+ * four moments of shz_match_extents_fit, from which the host fits the tempo the play really runs at.
+ * For segment i: recording r, song sid, first / last window a, b, p_a = seg_pos_first, p_b = seg_pos_last (the song frames at
+ * the starts of those windows, as the warped timelines emit them), W = window_frames, S = step_frames, M = margin_frames and
+ * W(x) = (x t16 + 32768) >> 16 in 64 bits.
+ * ZONES (shz_scan_play_zones; no GPU, no ctx; tests/scan_play_twin.py is the same in Python): zone_lo / zone_hi, in the
+ * recording's OWN frames, are exactly what shz_scan_zones gives for these segments with every seg_shift 0 -- a warped play has
+ * no constant shift, so the identity that keeps margins out of each other's windows is (rec, sid).  Zone z of segment i sits at
+ * 3 i + z: whole, head, tail.  zone_wlo / zone_whi are their warped borders W(lo), W(hi) (64 bits: F < 2^32 at factor 2).
+ * A zone's QUERY is the union, over the recording's channels, of the entries (key32, t1') of shz_warp_pair_hash_tf's list for
+ * (channel, (t16, f16)) with W(lo) <= t1' < W(hi), at query offset t1' - W(lo): the window contents of shz_scan_warps with
+ * arbitrary borders (EDGES at shz_scan_batch apply).  This is the definition; the twin computes it from the full warped list
+ * of the whole channel.
+ * A zone's one CANDIDATE, in 64-bit signed arithmetic, with c_a = p_a - W(a S) + W(lo), c_b = p_b - W(b S) + W(lo) and
+ * w = the vote tolerance + drift_bins:
+ *   0 whole  (sid, min(c_a, c_b) - w, max(c_a, c_b) + w)     the drift line runs from one end to the other
+ *   1 head   (sid, c_a - w, c_a + w)
+ *   2 tail   (sid, c_b - w, c_b + w)
+ * A range that lies wholly outside int32 is NO candidate (cand_n = 0, d_lo = d_hi = 0); the others are clamped to int32, which
+ * loses no pair (shz_scan_extents' argument).  (a S and b S saturate at 2^40 like shz_scan_zones' positions; such a range lies
+ * below int32 whatever the rest is.)
+ * shz_scan_play_zones writes zone_lo, zone_hi, zone_wlo, zone_whi, zone_d_lo, zone_d_hi and cand_n, [3 n_segs] each, and only
+ * when it returns SHZ_OK.  n_segs = 0: SHZ_OK.  Refused, in this order: what shz_scan_zones refuses (SHZ_E_INVALID); a NULL
+ * array with n_segs > 0 (SHZ_E_INVALID); a seg_t16 outside [32768, 131072] (SHZ_E_INVALID); a zone with W(hi) - W(lo) >= 2^20
+ * (a query offset of the extent pass; SHZ_E_UNSUPPORTED); a used candidate with d_hi - d_lo >= 4096 (the moments;
+ * SHZ_E_UNSUPPORTED).  With t16 = 65536, p_a = shift + a S, p_b = shift + b S and w = d_tol, and no song with segments at two
+ * shifts in one recording, zones and candidates are shz_scan_zones' and shz_scan_extents'. */
+int32_t shz_scan_play_zones(const uint32_t* seg_rec, const uint32_t* seg_sid, const uint32_t* seg_first, const uint32_t* seg_last,
+                            const int32_t* seg_pos_first, const int32_t* seg_pos_last, const uint32_t* seg_t16, uint64_t n_segs,
+                            const uint64_t* frames, uint32_t n_recs, uint32_t window_frames, uint32_t step_frames,
+                            uint32_t margin_frames, uint32_t w, uint32_t* zone_lo, uint32_t* zone_hi, uint64_t* zone_wlo,
+                            uint64_t* zone_whi, int32_t* zone_d_lo, int32_t* zone_d_hi, uint32_t* cand_n);
+/* The device stage, for the segments a caller folded from any warped scan of the same audio.  pcm .. step_frames and flags
+ * (SHZ_PCM_DEVICE) are shz_scan_warps'; seg_* [n_segs] are the caller's segments in the timeline's order, each with its pair.
+ * Stages: (a) the peaks of every clip, once; (b) one JOB per (segment, channel): the channel's peaks whose warped time lies in
+ * [W(lo0), W(hi0) - 1 + 200] ([lo0, hi0) = zone 0; 200 = the largest dt of a hash), found by two warped-time binary searches
+ * on the device -- whole t' groups, and every partner of every anchor below W(hi0), so the job's hashes with t1' < W(hi0) are
+ * the full list's, entry for entry; (c) the warp stage of shz_warp_pair_hash_tf on the jobs, every item taking its factors and
+ * its peak range from its job; (d) the three zones of every segment cut from its jobs' hash lists at W(lo), W(hi); (e) the
+ * extent pass with the moments, one candidate a zone.  Only the plays are warped, each at its own pair -- about one recording's
+ * peaks, where warping whole recordings at every pair in use costs (pairs in use) x the recording.  Warped hashes never leave
+ * the device.  The unsharded table only.
+ * Outputs, [3 n_segs] each, zone z of segment i at 3 i + z: zone_lo / zone_hi / zone_d_lo / zone_d_hi (shz_scan_play_zones'),
+ * zone_count, zone_q_first / zone_q_last (in WARPED recording frames: offset + W(lo), where count > 0; 0 otherwise),
+ * zone_t_first / zone_t_last (song frames), zone_shift, zone_hist [x 64, bucket (t1' - W(lo)) >> shift; may be NULL] and
+ * zone_sum_q / _u / _qq / _qu: the RESULT of shz_match_extents_fit for the zone's query and candidate (q = the query offset,
+ * u = d - zone_d_lo).  out_work (may be NULL): [0] peak items warped, [1] hash entries written, [2] zone entries handed to the
+ * extent pass.  ms_extract / ms_warp (jobs and warp) / ms_extent (cut and extent pass): hipEvent times, may be NULL.  Every
+ * output is written only by a call that returns SHZ_OK.  n_segs = 0: SHZ_OK, nothing is launched, nothing is written.  Results
+ * depend neither on the extent pass's tiling nor on anything else (SHZ_DEBUG_EXTENT_SMALL_TILES).
+ * Refused before anything is launched, in this order: flags beyond SHZ_PCM_DEVICE, window_frames outside [1, 2^20),
+ * step_frames of 0, fan_value outside [1, 64], margin_frames >= 2^20 (SHZ_E_INVALID); [n_segs = 0 returns here]; 3 n_segs >=
+ * 2^31 (SHZ_E_UNSUPPORTED); no recording, rec_clip0 / clip_off as shz_scan_warps refuses them, Fs of 0, a NULL pcm, a NULL
+ * segment or zone array, a seg_f16 outside [32768, 131072] (SHZ_E_INVALID); the table as shz_match_extents refuses it; then
+ * what shz_scan_play_zones refuses, with w = the context's vote tolerance + drift_bins; a warped border >= 2^32
+ * (SHZ_E_UNSUPPORTED).  Seen on the device: 2^32 or more (peak item, partner) pairs in the one pass (SHZ_E_UNSUPPORTED). */
+int32_t shz_scan_plays(shz_ctx* ctx, shz_table* t, const int16_t* pcm, const uint64_t* clip_off, uint32_t n_clips,
+                       const uint32_t* rec_clip0, uint32_t n_recs, uint32_t fs, double amp_min, uint32_t fan_value,
+                       uint32_t window_frames, uint32_t step_frames, uint32_t flags, const uint32_t* seg_rec,
+                       const uint32_t* seg_sid, const uint32_t* seg_first, const uint32_t* seg_last, const int32_t* seg_pos_first,
+                       const int32_t* seg_pos_last, const uint32_t* seg_t16, const uint32_t* seg_f16, uint64_t n_segs,
+                       uint32_t margin_frames, uint32_t drift_bins, uint32_t* zone_lo, uint32_t* zone_hi, int32_t* zone_d_lo,
+                       int32_t* zone_d_hi, uint32_t* zone_count, uint32_t* zone_q_first, uint32_t* zone_q_last,
+                       uint32_t* zone_t_first, uint32_t* zone_t_last, uint32_t* zone_shift, uint32_t* zone_hist,
+                       uint64_t* zone_sum_q, uint64_t* zone_sum_u, uint64_t* zone_sum_qq, uint64_t* zone_sum_qu,
+                       uint64_t* out_work, float* ms_extract, float* ms_warp, float* ms_extent);
+
 #ifdef __cplusplus
 }
 #endif

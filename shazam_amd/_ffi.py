@@ -215,6 +215,12 @@ SIGNATURES = {
     "shz_scan_timeline_warps": (C.c_int32, [u64p, C.c_uint32, vp, vp, vp, vp, vp, C.c_uint32, C.c_uint32, u32p, u32p, C.c_uint32,
                                             C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp,
                                             vp, vp, C.c_uint64, u64p]),
+    "shz_scan_play_zones": (C.c_int32, [vp, vp, vp, vp, vp, vp, vp, C.c_uint64, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                        C.c_uint32, vp, vp, vp, vp, vp, vp, vp]),
+    "shz_scan_plays": (C.c_int32, [vp, vp, vp, u64p, C.c_uint32, u32p, C.c_uint32, C.c_uint32, C.c_double, C.c_uint32, C.c_uint32,
+                                   C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32,
+                                   vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(C.c_float),
+                                   C.POINTER(C.c_float), C.POINTER(C.c_float)]),
 }
 
 
@@ -874,6 +880,40 @@ class Context:
         res["work"] = (int(work[0]), int(work[1]))
         return res, wo, tuple(float(m.value) for m in ms)
 
+    def scan_plays_raw(self, table: "Table", pcm, clip_off, rec_clip0, window_frames, step_frames, seg, margin_frames=0,
+                       drift_bins=0, fs=44100, amp_min=10.0, fan_value=5, pcm_device=False, hist=True, fill=0, work=True):
+        """One shz_scan_plays as it is: (rc, zone, work, ms).  seg = the arrays PLAY_SEGMENT_FIELDS of the caller's segments
+        (a warped timeline's, each with its own Q16 pair t16 / f16).  zone = the arrays PLAY_ZONE_FIELDS [n_segs, 3] and hist
+        [n_segs, 3, 64] (None with hist false), filled with `fill` before the call; work = (peak items warped, hash entries
+        written, zone entries handed to the extent pass); ms = (extract, warp, extent)."""
+        co, nc = self._clip_off(clip_off)
+        rc0 = np.ascontiguousarray(rec_clip0, np.uint32)
+        a = _play_segments(seg)
+        n = len(a["rec"])
+        zone = {k: np.full((n, 3), fill, d) for k, d in PLAY_ZONE_FIELDS}
+        zone["hist"] = np.full((n, 3, 64), fill, np.uint32) if hist else None
+        wk = np.full(3, fill, np.uint64)
+        ms = [C.c_float(), C.c_float(), C.c_float()]
+        rc = lib().shz_scan_plays(self.h, table.h, ptr(pcm), co.ctypes.data_as(u64p), nc, rc0.ctypes.data_as(u32p), len(rc0) - 1,
+                                  int(fs), float(amp_min), int(fan_value), int(window_frames), int(step_frames),
+                                  PCM_DEVICE if pcm_device else 0, *[ptr(a[k]) for k, _ in PLAY_SEGMENT_FIELDS], n,
+                                  int(margin_frames), int(drift_bins), *[ptr(zone[k]) for k, _ in PLAY_ZONE_FIELDS[:10]],
+                                  ptr(zone["hist"]), *[ptr(zone[k]) for k, _ in PLAY_ZONE_FIELDS[10:]],
+                                  ptr(wk) if work else None, *[C.byref(m) for m in ms])
+        return rc, zone, tuple(int(x) for x in wk), tuple(float(m.value) for m in ms)
+
+    def scan_plays(self, table: "Table", pcm, clip_off, rec_clip0, window_frames, step_frames, seg, margin_frames=0, drift_bins=0,
+                   **kw):
+        """shz_scan_plays: the extent pass with the moments on the three zones (whole, head, tail) of every
+        segment of a warped scan, each cut from hash lists warped at the segment's own pair, which never leave the device.
+        Returns (zone, work, ms): zone = arrays lo, hi (own recording frames), d_lo, d_hi (the candidate), count, q_first,
+        q_last (WARPED recording frames), t_first, t_last (song frames), shift, sum_q, sum_u, sum_qq, sum_qu [n_segs, 3] and
+        hist [n_segs, 3, 64]; work and ms as scan_plays_raw."""
+        rc, zone, work, ms = self.scan_plays_raw(table, pcm, clip_off, rec_clip0, window_frames, step_frames, seg, margin_frames,
+                                                 drift_bins, **kw)
+        self.check(rc)
+        return zone, work, ms
+
     def warp_pair_hash_raw(self, peak_f, peak_t, peak_off, speeds, query_clip0=None, fan_value=5, cap=0, device_in=False,
                            out_key: DevBuf = None, out_t1: DevBuf = None):
         """One shz_warp_pair_hash as it is: (rc, key32, t1, hash_off, count) without retrying.  peak_f / peak_t: host
@@ -1230,6 +1270,47 @@ def scan_zones(seg, frames, window_frames, step_frames, margin_frames):
     if rc != OK:
         raise ShzError(rc, "shz_scan_zones: bad arguments")
     return lo, hi
+
+
+# the segments shz_scan_play_zones / shz_scan_plays read (a warped timeline's, each with its own Q16 pair), and their zone outputs
+PLAY_SEGMENT_FIELDS = (("rec", np.uint32), ("sid", np.uint32), ("first", np.uint32), ("last", np.uint32), ("pos_first", np.int32),
+                       ("pos_last", np.int32), ("t16", np.uint32), ("f16", np.uint32))
+PLAY_ZONE_FIELDS = (("lo", np.uint32), ("hi", np.uint32), ("d_lo", np.int32), ("d_hi", np.int32), ("count", np.uint32),
+                    ("q_first", np.uint32), ("q_last", np.uint32), ("t_first", np.uint32), ("t_last", np.uint32),
+                    ("shift", np.uint32), ("sum_q", np.uint64), ("sum_u", np.uint64), ("sum_qq", np.uint64), ("sum_qu", np.uint64))
+
+
+def _play_segments(seg) -> dict:
+    a = {k: np.ascontiguousarray(seg[k], d).reshape(-1) for k, d in PLAY_SEGMENT_FIELDS if k in seg}
+    if "f16" not in a:
+        a["f16"] = a["t16"]
+    assert all(len(v) == len(a["rec"]) for v in a.values())
+    return a
+
+
+def scan_play_zones_raw(seg, frames, window_frames, step_frames, margin_frames, w, fill=0):
+    """One shz_scan_play_zones as it is (host only): (rc, zones) for the segments seg (rec, sid, first, last, pos_first, pos_last,
+    t16 are read); zones = arrays lo, hi (uint32), wlo, whi (uint64), d_lo, d_hi (int32), cand_n (uint32), [n_segs, 3] each,
+    filled with `fill` before the call."""
+    a = _play_segments(seg)
+    n = len(a["rec"])
+    fr = np.ascontiguousarray(frames, np.uint64)
+    z = {k: np.full((n, 3), fill, d) for k, d in (("lo", np.uint32), ("hi", np.uint32), ("wlo", np.uint64), ("whi", np.uint64),
+                                                   ("d_lo", np.int32), ("d_hi", np.int32), ("cand_n", np.uint32))}
+    rc = lib().shz_scan_play_zones(*[ptr(a[k]) for k, _ in PLAY_SEGMENT_FIELDS[:7]], n, ptr(fr), len(fr), int(window_frames),
+                                   int(step_frames), int(margin_frames), int(w), *[ptr(v) for v in z.values()])
+    return rc, z
+
+
+def scan_play_zones(seg, frames, window_frames, step_frames, margin_frames, w):
+    """shz_scan_play_zones (host only): the three zones of every segment of a warped scan -- lo / hi in the
+    recording's own frames, wlo / whi warped with the segment's time factor -- and the one widened candidate of every zone
+    (d_lo, d_hi; cand_n 0 where it lies outside int32), w = the vote tolerance + drift_bins."""
+    rc, z = scan_play_zones_raw(seg, frames, window_frames, step_frames, margin_frames, w)
+    if rc != OK:
+        raise ShzError(rc, "shz_scan_play_zones: bad segments or factors (INVALID), or a zone of 2^20 warped frames / a candidate "
+                           "of 4,096 bins or more (UNSUPPORTED)")
+    return z
 
 
 SPEED_SEGMENT_FIELDS = (("rec", np.uint32), ("sid", np.uint32), ("first", np.uint32), ("last", np.uint32), ("hits", np.uint32),

@@ -87,10 +87,12 @@ enum {
   SHZ_WS_SC_CTL,     // ... first entry | count | offset of every (window, rung, channel), the total behind the offsets
   SHZ_WS_SC_KEY, SHZ_WS_SC_QO,   // ... the windows of one group: key32 and t1 - window start, window-major (rung-minor)
                      // (shz_scan_extents' zone stage reuses the four SC slots once the window stage is done with them: zone
-                     // descriptors | hash_off; first | count | offset of every (zone, channel); key32 and t1 - lo of the zones)
+                     // descriptors | hash_off; first | count | offset of every (zone, channel); key32 and t1 - lo of the zones;
+                     // shz_scan_plays, which has no window stage, uses them the same way over the CSR of its jobs)
   SHZ_WS_SP_PF, SHZ_WS_SP_PT,    // shz_speed.hip: the peaks of the clips (the extraction's, or a host list staged)
   SHZ_WS_SP_TAB,     // ... peak_off | time factors | frequency factors of the call
-  SHZ_WS_SP_Q,       // ... first item | first clip of every query of a pass
+  SHZ_WS_SP_Q,       // ... first item | first clip of every query of a pass (the job form, shz_scan_plays: the job descriptors | the
+                     // items of every job | their scan)
   SHZ_WS_SP_A, SHZ_WS_SP_B,      // ... per (peak, speed) item: keep flags, then partner counts | their scans
   SHZ_WS_SP_WF, SHZ_WS_SP_WT,    // ... the warped, compacted peaks in output order
   SHZ_WS_SP_SEG,     // ... first kept peak of every (query, speed, clip) | hash_off | totals
@@ -290,6 +292,11 @@ int32_t shz_extract_owned(shz_ctx* ctx, const char* who, const int16_t* pcm, con
 #define SP_S_ONE 65536u
 #define SP_S_MAX 131072u
 #define SP_MAX_SPEEDS 1024u
+struct sp_job {               // one job of the job form (sp_count_jobs): a range of one clip's peaks at a pair of its own
+  uint64_t c_lo, c_hi;        // its peaks [c_lo, c_hi) in the peak lists (host: all peaks of its clip; narrowed on the device)
+  uint64_t w_lo, w_end;       // the warped times it keeps: w_lo <= W(t) <= w_end
+  uint32_t t16, f16;          // its time and its frequency factor (Q16)
+};
 struct sp_view {              // what the kernels of one pass read (device pointers)
   const uint16_t* pf;         // peaks of all clips, (clip, t asc, f asc)
   const uint32_t* pt;
@@ -300,6 +307,8 @@ struct sp_view {              // what the kernels of one pass read (device point
   const uint32_t* pitch;      // K: its frequency factor (the same table for a speed ladder)
   uint32_t nq, K, fan;
   uint64_t n_items;
+  const sp_job* jobs = nullptr;   // the job form: nq jobs, qbase their first items, segment e of the CSR is job e; poff, clip0,
+                                  // tempo and pitch are not read
 };
 struct sp_pass {
   sp_view V;
@@ -329,6 +338,9 @@ int32_t sp_count(shz_ctx* ctx, const uint16_t* d_pf, const uint32_t* d_pt, const
                  const uint32_t* clip0, uint32_t q0, uint32_t nq, const uint32_t* d_tempo, const uint32_t* d_pitch, uint32_t K,
                  uint32_t fan, sp_pass* P, uint64_t* hash_off);
 int32_t sp_write(shz_ctx* ctx, const sp_pass& P, uint32_t* d_key, uint32_t* d_t1, uint64_t cap);
+// the same pass over a list of jobs (shz_scan_plays): hash_off has n_jobs + 1 entries, *n_items = the peak items warped
+int32_t sp_count_jobs(shz_ctx* ctx, const uint16_t* d_pf, const uint32_t* d_pt, const sp_job* jobs, uint32_t n_jobs, uint32_t fan,
+                      sp_pass* P, uint64_t* hash_off, uint64_t* n_items);
 // steps 2-4 of shz_recognize_warps on peaks that lie on the device -- slices of whole queries (the 2^28-pair budget, 1/8 of the
 // workspace limit; SHZ_DEBUG_SPEED_SMALL_SLICES), sp_count / sp_write, shz_match_device on all (query, warp) pairs of a slice,
 // sp_best -- shared with the peak-window listeners (shz_stream.hip).  peak_off: host CSR from 0 over n_clips clips; t_max: the

@@ -593,8 +593,9 @@ extern "C" int32_t shz_scan_zones(const uint32_t* seg_rec, const uint32_t* seg_s
 
 struct sc_zone {       // one zone of the zone stage; the entry behind the last one holds the total
   uint64_t item0;      // its first (zone, channel) item: the channels of the zones in front of it
-  uint64_t clip0;      // the first clip of its recording: channel c is segment clip0 + c of the hashes' CSR
-  uint32_t lo, hi;     // recording frames [lo, hi)
+  uint64_t seg0;       // channel c is segment seg0 + c of the hashes' CSR: the first clip of its recording (shz_scan_extents),
+                       // the first job of its segment (shz_scan_plays)
+  uint32_t lo, hi;     // frames [lo, hi) of the lists' t1: recording frames, or warped recording frames
   uint32_t nch, pad;
 };
 
@@ -605,7 +606,7 @@ __global__ __launch_bounds__(SC_THREADS) void sc_zone_bounds_kernel(const sc_zon
                                                                     uint64_t* __restrict__ first, uint64_t* __restrict__ cnt) {
   const uint64_t i = (uint64_t)blockIdx.x * SC_THREADS + threadIdx.x;
   if (i >= n_items) return;
-  uint32_t l = 0, h = nz;   // the last zone whose first item is <= i (every zone has a channel: its recording has a window)
+  uint32_t l = 0, h = nz;   // the last zone whose first item is <= i (zones without a channel share a start with the next)
   while (l + 1 < h) {
     const uint32_t mid = l + ((h - l) >> 1);
     if (zones[mid].item0 <= i) l = mid; else h = mid;
@@ -617,7 +618,7 @@ __global__ __launch_bounds__(SC_THREADS) void sc_zone_bounds_kernel(const sc_zon
     cnt[i] = 0;
     return;
   }
-  const uint64_t a = hoff[Z.clip0 + c], b = hoff[Z.clip0 + c + 1];
+  const uint64_t a = hoff[Z.seg0 + c], b = hoff[Z.seg0 + c + 1];
   const uint64_t p = sc_lower_bound(t1, a, b, Z.lo);
   const uint64_t q = Z.hi > Z.lo ? sc_lower_bound(t1, p, b, Z.hi) : p;
   first[i] = p;
@@ -642,27 +643,29 @@ __global__ __launch_bounds__(SC_THREADS) void sc_zone_gather_kernel(const sc_zon
   }
 }
 
-// The zone stage: cuts the extraction's hash lists (d_key / d_t1, CSR hash_off over the clips, all of them alive in
-// SHZ_WS_RQ_KEY / _T1) into the nz zones and leaves their columns on the device, query_off (nz + 1, host) their CSR.  It
-// runs behind sc_windows, which returns with the stream idle and is done with its workspace: the slots SHZ_WS_SC_JOBS,
-// _CTL, _KEY and _QO are REUSED here (descriptors | hash_off; first | count | offsets; the two columns) instead of adding
-// slots that would only ever be live when those are dead.  The extent pass behind it reserves none of them.  The stream is
-// idle on return.
-static int32_t sc_zone_stage(shz_ctx* ctx, const char* who, const uint32_t* rec_clip0, uint32_t n_clips, const uint64_t* hash_off,
-                             const uint32_t* d_key, const uint32_t* d_t1, const uint32_t* seg_rec, uint64_t n_segs,
+// The zone stage: cuts device-resident hash lists (d_key / d_t1, t1 never decreasing inside a list; hash_off, host, their CSR
+// over n_csr lists) into the three zones of n_segs segments and leaves the zones' columns on the device, query_off (3 n_segs
+// + 1, host) their CSR.  Zone z of segment i is [zone_lo[3 i + z], zone_hi[3 i + z]) of the lists seg_csr0[i] .. + seg_nch[i],
+// one behind the other.  shz_scan_extents hands it the extraction's lists (alive in SHZ_WS_RQ_KEY / _T1; a segment's lists
+// are its recording's clips, the borders recording frames); shz_scan_plays the warped lists of its jobs (SHZ_WS_SP_KEY / _T1;
+// a segment's lists are its jobs, the borders warped).  It runs behind sc_windows, which returns with the stream idle and is
+// done with its workspace, or in a call without a window stage: the slots SHZ_WS_SC_JOBS, _CTL, _KEY and _QO are REUSED here
+// (descriptors | hash_off; first | count | offsets; the two columns) instead of adding slots that would only ever be live
+// when those are dead.  The extent pass behind it reserves none of them.  The stream is idle on return.
+static int32_t sc_zone_stage(shz_ctx* ctx, const char* who, const uint64_t* seg_csr0, const uint32_t* seg_nch, uint64_t n_segs,
+                             uint64_t n_csr, const uint64_t* hash_off, const uint32_t* d_key, const uint32_t* d_t1,
                              const uint32_t* zone_lo, const uint32_t* zone_hi, uint64_t* query_off, const uint32_t** d_zk,
                              const uint32_t** d_zq) {
-  const uint64_t nz = 3 * n_segs, total = hash_off[n_clips];
-  const uint64_t zone_bytes = (nz + 1) * sizeof(sc_zone), hoff_bytes = ((uint64_t)n_clips + 1) * 8;
+  const uint64_t nz = 3 * n_segs, total = hash_off[n_csr];
+  const uint64_t zone_bytes = (nz + 1) * sizeof(sc_zone), hoff_bytes = (n_csr + 1) * 8;
   std::vector<char> block(zone_bytes + hoff_bytes);
   sc_zone* hz = (sc_zone*)block.data();
   uint64_t n_items = 0;
   for (uint64_t z = 0; z < nz; ++z) {
-    const uint32_t r = seg_rec[z / 3], nch = rec_clip0[r + 1] - rec_clip0[r];
-    hz[z] = sc_zone{n_items, rec_clip0[r], zone_lo[z], zone_hi[z], nch, 0};
-    n_items += nch;
+    hz[z] = sc_zone{n_items, seg_csr0[z / 3], zone_lo[z], zone_hi[z], seg_nch[z / 3], 0};
+    n_items += seg_nch[z / 3];
   }
-  hz[nz] = sc_zone{n_items, n_clips, 0, 0, 0, 0};
+  hz[nz] = sc_zone{n_items, n_csr, 0, 0, 0, 0};
   memcpy(block.data() + zone_bytes, hash_off, hoff_bytes);
   void *d_blk, *d_ctl, *d_k, *d_q;
   SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SC_JOBS, block.size(), &d_blk));
@@ -766,8 +769,14 @@ extern "C" int32_t shz_scan_extents(shz_ctx* ctx, shz_table* t, const int16_t* p
   if (timed) SHZ_HIP(ctx, hipEventRecord(ctx->sc_ev[2], ctx->stream));
   std::vector<uint64_t> query_off((size_t)nz + 1, 0);
   const uint32_t *d_zk = nullptr, *d_zq = nullptr;
-  SHZ_TRY(sc_zone_stage(ctx, who, rec_clip0, n_clips, hash_off.data(), d_key, d_t1, seg_rec, n_segs, z_lo.data(), z_hi.data(),
-                        query_off.data(), &d_zk, &d_zq));
+  std::vector<uint64_t> seg_csr0((size_t)n_segs);   // a segment's lists: the clips of its recording
+  std::vector<uint32_t> seg_nch((size_t)n_segs);
+  for (uint64_t i = 0; i < n_segs; ++i) {
+    seg_csr0[i] = rec_clip0[seg_rec[i]];
+    seg_nch[i] = rec_clip0[seg_rec[i] + 1] - rec_clip0[seg_rec[i]];
+  }
+  SHZ_TRY(sc_zone_stage(ctx, who, seg_csr0.data(), seg_nch.data(), n_segs, n_clips, hash_off.data(), d_key, d_t1, z_lo.data(),
+                        z_hi.data(), query_off.data(), &d_zk, &d_zq));
   const ex_args A{(uint32_t)nz, 1, c_sid.data(), c_dlo.data(), c_dhi.data(), c_n.data(), zone_count, zone_q_first, zone_q_last,
                   zone_t_first, zone_t_last, zone_hist, zone_shift};
   SHZ_TRY(ex_check(ctx, t, who, A));
@@ -1138,4 +1147,236 @@ extern "C" int32_t shz_scan_timeline_warps(const uint64_t* win_off, uint32_t n_r
                        seg_pos_last, seg_warp, std::vector<uint32_t>(n_warps, 0)};
   return sc_fold(win_off, n_recs, sid, delta, aligned, nres, topn, min_aligned, max_gap, seg_rec, seg_sid, seg_first, seg_last,
                  seg_hits, seg_best, cap, count, rule);
+}
+
+// ---- warped scan extents: frame-accurate play bounds and a tempo fit for the segments of a warped scan ----
+// A segment of shz_scan_timeline_speeds / _warps has no constant shift, so its zones are clamped by (rec, sid) alone --
+// shz_scan_zones with every shift 0 -- and every zone gets a WIDENED candidate: the drift line of a play that really runs
+// at a tempo beside its rung leaves the rung's own offset bin by (true / rung - 1) frames per warped frame.  With W(x) =
+// (x t16 + 32768) >> 16, p_a / p_b the song frames at the starts of the first / last window (a S, b S) and the zone's warped
+// start W(lo), the offset difference off - (t1' - W(lo)) is c_a = p_a - W(a S) + W(lo) at the first window and c_b = p_b -
+// W(b S) + W(lo) at the last one.  Positions are formed in 64 bits; a S saturates at 2^40 as shz_scan_zones' do, where c is
+// below every int32 whatever the rest is.
+extern "C" int32_t shz_scan_play_zones(const uint32_t* seg_rec, const uint32_t* seg_sid, const uint32_t* seg_first,
+                                       const uint32_t* seg_last, const int32_t* seg_pos_first, const int32_t* seg_pos_last,
+                                       const uint32_t* seg_t16, uint64_t n_segs, const uint64_t* frames, uint32_t n_recs,
+                                       uint32_t window_frames, uint32_t step_frames, uint32_t margin_frames, uint32_t w,
+                                       uint32_t* zone_lo, uint32_t* zone_hi, uint64_t* zone_wlo, uint64_t* zone_whi,
+                                       int32_t* zone_d_lo, int32_t* zone_d_hi, uint32_t* cand_n) {
+  const uint64_t nz = 3 * n_segs;
+  std::vector<int64_t> shift((size_t)n_segs, 0);
+  std::vector<uint32_t> lo((size_t)nz), hi((size_t)nz), cn((size_t)nz);
+  // 1) the own-frame zones, and everything shz_scan_zones refuses
+  const int32_t rc = shz_scan_zones(seg_rec, seg_sid, shift.data(), seg_first, seg_last, n_segs, frames, n_recs, window_frames,
+                                    step_frames, margin_frames, lo.data(), hi.data());
+  if (rc != SHZ_OK) return rc;
+  if (n_segs == 0) return SHZ_OK;
+  if (!seg_pos_first || !seg_pos_last || !seg_t16 || !zone_lo || !zone_hi || !zone_wlo || !zone_whi || !zone_d_lo || !zone_d_hi || !cand_n)
+    return SHZ_E_INVALID;
+  // 2) the factors, 3) the warped zones and their lengths, 4) the candidates and their widths
+  for (uint64_t i = 0; i < n_segs; ++i)
+    if (seg_t16[i] < SP_S_MIN || seg_t16[i] > SP_S_MAX) return SHZ_E_INVALID;
+  auto warp = [](uint64_t x, uint32_t t16) { return (x * t16 + 32768u) >> 16; };   // (x <= 2^40, t16 <= 2^17)
+  std::vector<uint64_t> wlo((size_t)nz), whi((size_t)nz);
+  for (uint64_t z = 0; z < nz; ++z) {
+    wlo[z] = warp(lo[z], seg_t16[z / 3]);
+    whi[z] = warp(hi[z], seg_t16[z / 3]);
+    if (whi[z] - wlo[z] >= (1ull << 20)) return SHZ_E_UNSUPPORTED;   // (a query offset of the extent pass)
+  }
+  std::vector<int32_t> dlo((size_t)nz), dhi((size_t)nz);
+  const uint64_t top = 1ull << 40;
+  for (uint64_t i = 0; i < n_segs; ++i) {
+    const uint32_t t16 = seg_t16[i];
+    const int64_t wa = (int64_t)warp(std::min<uint64_t>((uint64_t)seg_first[i] * step_frames, top), t16);
+    const int64_t wb = (int64_t)warp(std::min<uint64_t>((uint64_t)seg_last[i] * step_frames, top), t16);
+    for (int z = 0; z < 3; ++z) {
+      const uint64_t k = 3 * i + z;
+      const int64_t c_a = (int64_t)seg_pos_first[i] - wa + (int64_t)wlo[k], c_b = (int64_t)seg_pos_last[i] - wb + (int64_t)wlo[k];
+      // whole: the drift line runs from one end to the other; head: where it starts; tail: where it ends
+      const int64_t c_lo = z == 0 ? std::min(c_a, c_b) : (z == 1 ? c_a : c_b), c_hi = z == 0 ? std::max(c_a, c_b) : c_lo;
+      const int64_t l = c_lo - (int64_t)w, h = c_hi + (int64_t)w;
+      // (as shz_scan_extents: a range that does not meet the differences a table offset < 2^31 and a query offset < 2^20
+      // can have holds no pair; the others lose nothing at the clamp)
+      const bool none = l > INT32_MAX || h < INT32_MIN;
+      dlo[k] = none ? 0 : (int32_t)std::max<int64_t>(l, INT32_MIN);
+      dhi[k] = none ? 0 : (int32_t)std::min<int64_t>(h, INT32_MAX);
+      cn[k] = none ? 0u : 1u;
+      if (!none && (int64_t)dhi[k] - dlo[k] >= EX_FIT_MAX_WIDTH) return SHZ_E_UNSUPPORTED;   // (the moments: q u < 2^32)
+    }
+  }
+  for (uint64_t z = 0; z < nz; ++z) {
+    zone_lo[z] = lo[z];
+    zone_hi[z] = hi[z];
+    zone_wlo[z] = wlo[z];
+    zone_whi[z] = whi[z];
+    zone_d_lo[z] = dlo[z];
+    zone_d_hi[z] = dhi[z];
+    cand_n[z] = cn[z];
+  }
+  return SHZ_OK;
+}
+
+// The device stage.  Why a job's hashes are the full list's: a job is (segment, channel) and keeps the channel's peaks whose
+// WARPED time lies in [W(lo0), W(hi0) - 1 + SHZ_MAX_DT], zone 0 being [lo0, hi0).  (1) Choosing by warped time keeps whole t'
+// groups: every peak that shares a t' with a kept one is kept, so sp_place's merge of neighbouring frames (t16 < 65536) sees
+// the peaks it sees on the whole channel, and the kept peaks stand in the order they have in the full warped list.  (2) An
+// anchor with t1' < W(hi0) pairs with the next fan - 1 peaks of that order whose dt' <= SHZ_MAX_DT: all of them have t' <=
+// W(hi0) - 1 + SHZ_MAX_DT and are kept, and a peak that is missing behind the range would have failed dt' <= SHZ_MAX_DT.  So
+// the job's hashes with W(lo0) <= t1' < W(hi0) are the full list's, entry for entry, and the three zones -- which lie inside
+// zone 0 -- are cut from them; anchors in the tail behind W(hi0) have lost partners and are never cut.
+// tests/scan_play_twin.py cuts the full list; its equality with this call is the proof in practice.
+// Workspace: the peaks in SHZ_WS_SP_PF / _PT, the job table in SHZ_WS_SP_Q, the pass in SHZ_WS_SP_A .. _SEG, the warped hashes
+// in SHZ_WS_SP_KEY / _T1 -- all as the warped scan uses them; the zone stage REUSES SHZ_WS_SC_JOBS / _CTL / _KEY / _QO, whose
+// owner (the window stage) does not run in this call; the extent pass keeps to its own.  No slot is added.
+extern "C" int32_t shz_scan_plays(shz_ctx* ctx, shz_table* t, const int16_t* pcm, const uint64_t* clip_off, uint32_t n_clips,
+                                  const uint32_t* rec_clip0, uint32_t n_recs, uint32_t fs, double amp_min, uint32_t fan_value,
+                                  uint32_t window_frames, uint32_t step_frames, uint32_t flags, const uint32_t* seg_rec,
+                                  const uint32_t* seg_sid, const uint32_t* seg_first, const uint32_t* seg_last,
+                                  const int32_t* seg_pos_first, const int32_t* seg_pos_last, const uint32_t* seg_t16,
+                                  const uint32_t* seg_f16, uint64_t n_segs, uint32_t margin_frames, uint32_t drift_bins,
+                                  uint32_t* zone_lo, uint32_t* zone_hi, int32_t* zone_d_lo, int32_t* zone_d_hi, uint32_t* zone_count,
+                                  uint32_t* zone_q_first, uint32_t* zone_q_last, uint32_t* zone_t_first, uint32_t* zone_t_last,
+                                  uint32_t* zone_shift, uint32_t* zone_hist, uint64_t* zone_sum_q, uint64_t* zone_sum_u,
+                                  uint64_t* zone_sum_qq, uint64_t* zone_sum_qu, uint64_t* out_work, float* ms_extract,
+                                  float* ms_warp, float* ms_extent) {
+  const char* who = "shz_scan_plays";
+  if (!ctx || !t) return SHZ_E_INVALID;
+  // everything that can be refused is refused before the first launch, in this order
+  if (flags & ~SHZ_PCM_DEVICE) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: flags may hold SHZ_PCM_DEVICE", who);
+  if (window_frames == 0 || window_frames >= (1u << 20))
+    SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: window_frames must be in [1, 2^20) (query offsets), got %u", who, window_frames);
+  if (step_frames == 0) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: step_frames must be at least 1", who);
+  if (fan_value < 1 || fan_value > 64) SHZ_FAIL(ctx, SHZ_E_INVALID, "fan_value must be in [1,64]");
+  if (margin_frames >= (1u << 20)) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: margin_frames must be below 2^20, got %u", who, margin_frames);
+  if (n_segs == 0) return SHZ_OK;   // no segment: nothing is launched, nothing is written
+  if (3 * n_segs >= (1ull << 31)) SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "%s: %llu segments in one call", who, (unsigned long long)n_segs);
+  if (n_recs == 0) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: %llu segments and no recording", who, (unsigned long long)n_segs);
+  SHZ_TRY(shz_check_clip0(ctx, "rec_clip0", "recording", rec_clip0, n_recs, n_clips));
+  SHZ_TRY(shz_check_clip_off(ctx, clip_off, n_clips));
+  if (fs == 0) SHZ_FAIL(ctx, SHZ_E_INVALID, "Fs must be > 0");
+  if (n_clips && !pcm && clip_off[n_clips] > clip_off[0]) SHZ_FAIL(ctx, SHZ_E_INVALID, "pcm is NULL");
+  if (!seg_rec || !seg_sid || !seg_first || !seg_last || !seg_pos_first || !seg_pos_last || !seg_t16 || !seg_f16)
+    SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: NULL segment array", who);
+  if (!zone_lo || !zone_hi || !zone_d_lo || !zone_d_hi || !zone_count || !zone_q_first || !zone_q_last || !zone_t_first ||
+      !zone_t_last || !zone_shift || !zone_sum_q || !zone_sum_u || !zone_sum_qq || !zone_sum_qu)
+    SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: NULL zone array", who);
+  for (uint64_t i = 0; i < n_segs; ++i)
+    if (seg_f16[i] < SP_S_MIN || seg_f16[i] > SP_S_MAX)
+      SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: pitch factor of segment %llu is %u; factors are Q16 in [%u, %u] (0.5x .. 2x)", who,
+               (unsigned long long)i, seg_f16[i], SP_S_MIN, SP_S_MAX);
+  SHZ_TRY(ex_state(ctx, t, who, 1));
+  SHZ_TRY(ex_table_limits(ctx, t, who));
+  // the zones and their candidates, on the host: shz_scan_play_zones, and what it refuses
+  const uint64_t nz = 3 * n_segs;
+  std::vector<uint64_t> frames((size_t)n_recs, 0);
+  uint64_t all_frames = 0;
+  for (uint32_t r = 0; r < n_recs; ++r)
+    for (uint32_t c = rec_clip0[r]; c < rec_clip0[r + 1]; ++c) {
+      const uint64_t fc = shz_frame_count_hop(clip_off[c + 1] - clip_off[c], ctx->hop);
+      frames[r] = std::max<uint64_t>(frames[r], fc);
+      all_frames += fc;
+    }
+  const uint32_t w = (uint32_t)std::min<uint64_t>((uint64_t)ctx->vote_tol + drift_bins, 0xFFFFFFFFull);
+  std::vector<uint32_t> z_lo((size_t)nz), z_hi((size_t)nz), c_sid((size_t)nz), c_n((size_t)nz), w_lo((size_t)nz), w_hi((size_t)nz);
+  std::vector<uint64_t> z_wlo((size_t)nz), z_whi((size_t)nz);
+  std::vector<int32_t> c_dlo((size_t)nz), c_dhi((size_t)nz);
+  const int32_t rz = shz_scan_play_zones(seg_rec, seg_sid, seg_first, seg_last, seg_pos_first, seg_pos_last, seg_t16, n_segs,
+                                         frames.data(), n_recs, window_frames, step_frames, margin_frames, w, z_lo.data(), z_hi.data(),
+                                         z_wlo.data(), z_whi.data(), c_dlo.data(), c_dhi.data(), c_n.data());
+  if (rz == SHZ_E_INVALID)
+    SHZ_FAIL(ctx, rz, "%s: segments must be a timeline's (recordings ascending and below n_recs, first <= last, windows ascending "
+             "inside a recording), time factors Q16 in [%u, %u]", who, SP_S_MIN, SP_S_MAX);
+  if (rz == SHZ_E_UNSUPPORTED)
+    SHZ_FAIL(ctx, rz, "%s: a warped zone of 2^20 frames or more (query offsets), or a candidate %u bins or more wide at "
+             "tolerance %u + drift_bins %u (the sums)", who, EX_FIT_MAX_WIDTH, ctx->vote_tol, drift_bins);
+  SHZ_TRY(rz);
+  for (uint64_t z = 0; z < nz; ++z) {
+    if (z_whi[z] > 0xFFFFFFFFull) SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "%s: a warped frame beyond 2^32", who);
+    w_lo[z] = (uint32_t)z_wlo[z];
+    w_hi[z] = (uint32_t)z_whi[z];
+    c_sid[z] = seg_sid[z / 3];
+  }
+  ex_args A{(uint32_t)nz, 1, c_sid.data(), c_dlo.data(), c_dhi.data(), c_n.data(), zone_count, zone_q_first, zone_q_last,
+            zone_t_first, zone_t_last, zone_hist, zone_shift};
+  A.out_sum_q = zone_sum_q;
+  A.out_sum_u = zone_sum_u;
+  A.out_sum_qq = zone_sum_qq;
+  A.out_sum_qu = zone_sum_qu;
+  SHZ_TRY(ex_check(ctx, t, who, A));
+  SHZ_HIP(ctx, hipSetDevice(ctx->device));
+  const bool timed = ms_extract || ms_warp || ms_extent;
+  if (timed) {
+    for (hipEvent_t& e : ctx->sc_ev)
+      if (!e) SHZ_HIP(ctx, hipEventCreate(&e));
+    SHZ_HIP(ctx, hipEventRecord(ctx->sc_ev[0], ctx->stream));
+  }
+  // a) the peaks of every clip, once
+  std::vector<uint64_t> peak_off((size_t)n_clips + 1, 0);
+  const uint16_t* d_pf = nullptr;
+  const uint32_t* d_pt = nullptr;
+  SHZ_TRY(sp_peaks_owned(ctx, who, pcm, clip_off, n_clips, all_frames, fs, amp_min, flags & SHZ_PCM_DEVICE, peak_off.data(), &d_pf, &d_pt));
+  if (timed) SHZ_HIP(ctx, hipEventRecord(ctx->sc_ev[1], ctx->stream));
+  // b) one job per (segment, channel), covering zone 0 and SHZ_MAX_DT warped frames behind it
+  std::vector<sp_job> jobs;
+  std::vector<uint64_t> seg_job0((size_t)n_segs);
+  std::vector<uint32_t> seg_nch((size_t)n_segs);
+  for (uint64_t i = 0; i < n_segs; ++i) {
+    const uint32_t c0 = rec_clip0[seg_rec[i]], c1 = rec_clip0[seg_rec[i] + 1];
+    seg_job0[i] = jobs.size();
+    seg_nch[i] = c1 - c0;
+    for (uint32_t c = c0; c < c1; ++c)
+      jobs.push_back(sp_job{peak_off[c] - peak_off[0], peak_off[c + 1] - peak_off[0], z_wlo[3 * i], z_whi[3 * i] + SHZ_MAX_DT - 1,
+                            seg_t16[i], seg_f16[i]});
+  }
+  const uint64_t n_jobs = jobs.size();
+  if (n_jobs >= (1ull << 31)) SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "%s: %llu (segment, channel) jobs in one call", who, (unsigned long long)n_jobs);
+  // c) the warp on the jobs: the exact CSR on both sides, the hashes stay on the device
+  std::vector<uint64_t> ho((size_t)n_jobs + 1, 0);
+  uint64_t n_items = 0, total = 0;
+  void *d_key = nullptr, *d_t1 = nullptr;
+  if (n_jobs) {
+    sp_pass P;
+    SHZ_TRY(sp_count_jobs(ctx, d_pf, d_pt, jobs.data(), (uint32_t)n_jobs, fan_value, &P, ho.data(), &n_items));
+    total = ho[n_jobs];
+    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SP_KEY, total * 4 + 64, &d_key));
+    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SP_T1, total * 4 + 64, &d_t1));
+    if (total) SHZ_TRY(sp_write(ctx, P, (uint32_t*)d_key, (uint32_t*)d_t1, total));
+  }
+  if (timed) SHZ_HIP(ctx, hipEventRecord(ctx->sc_ev[2], ctx->stream));
+  // d) the cut: the zone stage over the jobs' CSR with the warped borders, e) the extent pass with the moments
+  std::vector<uint64_t> query_off((size_t)nz + 1, 0);
+  const uint32_t *d_zk = nullptr, *d_zq = nullptr;
+  SHZ_TRY(sc_zone_stage(ctx, who, seg_job0.data(), seg_nch.data(), n_segs, n_jobs, ho.data(), (const uint32_t*)d_key,
+                        (const uint32_t*)d_t1, w_lo.data(), w_hi.data(), query_off.data(), &d_zk, &d_zq));
+  const int32_t rx = ex_device(ctx, t, who, d_zk, d_zq, query_off.data(), A);
+  if (rx != SHZ_OK) {
+    (void)hipStreamSynchronize(ctx->stream);   // (a refused pass may have queued work that reads the columns)
+    return rx;
+  }
+  float ms[3] = {0.f, 0.f, 0.f};
+  if (timed) {
+    SHZ_HIP(ctx, hipEventRecord(ctx->sc_ev[3], ctx->stream));
+    SHZ_HIP(ctx, hipEventSynchronize(ctx->sc_ev[3]));
+    for (int k = 0; k < 3; ++k) SHZ_HIP(ctx, hipEventElapsedTime(&ms[k], ctx->sc_ev[k], ctx->sc_ev[k + 1]));
+  }
+  // the pass has written its outputs: the zones and candidates beside them, query frames -> warped recording frames
+  for (uint64_t z = 0; z < nz; ++z) {
+    zone_lo[z] = z_lo[z];
+    zone_hi[z] = z_hi[z];
+    zone_d_lo[z] = c_dlo[z];
+    zone_d_hi[z] = c_dhi[z];
+    if (zone_count[z]) {
+      zone_q_first[z] += w_lo[z];
+      zone_q_last[z] += w_lo[z];
+    }
+  }
+  if (out_work) {
+    out_work[0] = n_items;
+    out_work[1] = total;
+    out_work[2] = query_off[nz];
+  }
+  if (ms_extract) *ms_extract = ms[0];
+  if (ms_warp) *ms_warp = ms[1];
+  if (ms_extent) *ms_extent = ms[2];
+  return SHZ_OK;
 }

@@ -28,6 +28,8 @@
 //     sp_seg   : first kept peak of every (q, v, c)
 //     sp_count : partners of every kept peak         scan -> offsets;  sp_hoff: the exact CSR, read back once
 //     sp_write : (key32, t1) as pair_write_kernel forms them
+// The JOB form runs the same kernels over a list of jobs (clip, a range of its peaks, a pair of its own) in place
+// of the product: the segments of a warped scan each play at their own pair, and only their frames need warping.
 #include <algorithm>
 
 #include "shz_internal.h"
@@ -48,6 +50,19 @@ __device__ __forceinline__ bool sp_decode(const sp_view& V, uint64_t w, sp_item*
   while (lo + 1 < hi) {
     const uint32_t mid = (lo + hi) >> 1;
     if (V.qbase[mid] <= w) lo = mid; else hi = mid;
+  }
+  if (V.jobs) {   // (uniform: a kernel argument) the job form: nq jobs, qbase their first items.  Empty jobs share a base with
+    // the job behind them, and the last of such a run is the one that holds w, because w exists
+    const sp_job J = V.jobs[lo];
+    it->c = lo;
+    it->t16 = J.t16;
+    it->f16 = J.f16;
+    it->g = J.c_lo + (w - V.qbase[lo]);
+    it->c_lo = J.c_lo;
+    it->c_hi = J.c_hi;
+    it->seg0 = V.qbase[lo];
+    it->seg_n = J.c_hi - J.c_lo;
+    return it->g < J.c_hi;
   }
   const uint32_t c0 = V.clip0[lo], c1 = V.clip0[lo + 1];
   const uint64_t p0 = V.poff[c0], nqp = V.poff[c1] - p0;
@@ -121,7 +136,9 @@ __global__ __launch_bounds__(SP_THREADS) void sp_seg_kernel(sp_view V, uint64_t 
   const uint64_t e = (uint64_t)blockIdx.x * SP_THREADS + threadIdx.x;
   if (e > n_seg) return;
   uint64_t item0 = V.n_items;
-  if (e < n_seg) {
+  if (e < n_seg && V.jobs) {   // the job form: segment e is job e (an empty one starts where the next begins)
+    item0 = V.qbase[e];
+  } else if (e < n_seg) {
     const uint32_t cb = V.clip0[0];
     uint32_t lo = 0, hi = V.nq;   // the last query whose first segment is <= e
     while (lo + 1 < hi) {
@@ -207,39 +224,28 @@ uint64_t sp_items(const uint64_t* peak_off, const uint32_t* clip0, uint32_t q0, 
   return (peak_off[clip0[q0 + nq]] - peak_off[clip0[q0]]) * K;
 }
 
-// hash_off: n_seg + 1 entries (host), relative to the pass.  d_poff / d_tempo / d_pitch: the call's tables on the device.
-int32_t sp_count(shz_ctx* ctx, const uint16_t* d_pf, const uint32_t* d_pt, const uint64_t* d_poff, const uint64_t* peak_off,
-                        const uint32_t* clip0, uint32_t q0, uint32_t nq, const uint32_t* d_tempo, const uint32_t* d_pitch, uint32_t K,
-                        uint32_t fan, sp_pass* P, uint64_t* hash_off) {
-  const uint64_t n_items = sp_items(peak_off, clip0, q0, nq, K);
-  const uint64_t n_seg = (uint64_t)(clip0[q0 + nq] - clip0[q0]) * K;
-  P->n_seg = n_seg;
-  for (uint64_t e = 0; e <= n_seg; ++e) hash_off[e] = 0;
-  P->V = sp_view{d_pf, d_pt, d_poff, nullptr, nullptr, d_tempo, d_pitch, nq, K, fan, n_items};
-  if (n_items == 0) return SHZ_OK;
+// what a pass can hold: the places and the hash offsets of its items are 32 bits wide
+static int32_t sp_fits(shz_ctx* ctx, uint64_t n_items, uint32_t fan) {
   if (n_items * std::max<uint32_t>(fan - 1, 1) >= (1ull << 32))
     SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "speed warp: %llu (peak, speed) pairs at fan_value %u in one pass (32-bit offsets)",
              (unsigned long long)n_items, fan);
-  // the pass's own tables: qbase | clip0
-  const uint64_t qb_bytes = ((uint64_t)nq + 1) * 8, tab_bytes = qb_bytes + ((uint64_t)nq + 1) * 4;
-  void *hm, *d_q, *a, *b, *wf, *wt, *sg;
-  SHZ_TRY(shz_mailbox(ctx, tab_bytes, &hm));
-  uint64_t* hq = (uint64_t*)hm;
-  uint32_t* hc = (uint32_t*)((char*)hm + qb_bytes);
-  for (uint32_t q = 0; q <= nq; ++q) {
-    hq[q] = (peak_off[clip0[q0 + q]] - peak_off[clip0[q0]]) * K;
-    hc[q] = clip0[q0 + q];
-  }
+  return SHZ_OK;
+}
+
+// The stages of a pass whose view is complete (P->V with its tables on the device, n_items > 0; P->n_seg): flag -> scan ->
+// place -> segment starts -> count -> scan -> the exact CSR, read back once into hash_off.  Both forms run it: the product
+// form (sp_count) and the job form (sp_count_jobs) differ in what an item decodes to (sp_decode, sp_seg_kernel) and in
+// nothing else.  The stream is idle on return
+static int32_t sp_run(shz_ctx* ctx, sp_pass* P, uint64_t* hash_off) {
+  const uint64_t n_items = P->V.n_items, n_seg = P->n_seg;
+  const uint32_t fan = P->V.fan;
+  void *a, *b, *wf, *wt, *sg;
   const uint64_t seg_bytes = ((n_seg + 1) * 4 + 255) & ~255ull;
-  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SP_Q, tab_bytes, &d_q));
   SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SP_A, n_items * 4, &a));
   SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SP_B, n_items * 4, &b));
   SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SP_WF, n_items * 2, &wf));
   SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SP_WT, n_items * 4, &wt));
   SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SP_SEG, seg_bytes + (n_seg + 1) * 8 + 64, &sg));
-  SHZ_HIP(ctx, hipMemcpyAsync(d_q, hm, tab_bytes, hipMemcpyHostToDevice, ctx->stream));
-  P->V.qbase = (const uint64_t*)d_q;
-  P->V.clip0 = (const uint32_t*)((char*)d_q + qb_bytes);
   P->a = (uint32_t*)a;
   P->b = (uint32_t*)b;
   P->wf = (uint16_t*)wf;
@@ -265,6 +271,84 @@ int32_t sp_count(shz_ctx* ctx, const uint16_t* d_pf, const uint32_t* d_pt, const
   SHZ_HIP(ctx, shz_memcpy(ctx, hash_off, P->d_hoff, (n_seg + 1) * 8, hipMemcpyDeviceToHost));
   SHZ_HIP(ctx, hipStreamSynchronize(st));
   return SHZ_OK;
+}
+
+// hash_off: n_seg + 1 entries (host), relative to the pass.  d_poff / d_tempo / d_pitch: the call's tables on the device.
+int32_t sp_count(shz_ctx* ctx, const uint16_t* d_pf, const uint32_t* d_pt, const uint64_t* d_poff, const uint64_t* peak_off,
+                        const uint32_t* clip0, uint32_t q0, uint32_t nq, const uint32_t* d_tempo, const uint32_t* d_pitch, uint32_t K,
+                        uint32_t fan, sp_pass* P, uint64_t* hash_off) {
+  const uint64_t n_items = sp_items(peak_off, clip0, q0, nq, K);
+  const uint64_t n_seg = (uint64_t)(clip0[q0 + nq] - clip0[q0]) * K;
+  P->n_seg = n_seg;
+  for (uint64_t e = 0; e <= n_seg; ++e) hash_off[e] = 0;
+  P->V = sp_view{d_pf, d_pt, d_poff, nullptr, nullptr, d_tempo, d_pitch, nq, K, fan, n_items};
+  if (n_items == 0) return SHZ_OK;
+  SHZ_TRY(sp_fits(ctx, n_items, fan));
+  // the pass's own tables: qbase | clip0
+  const uint64_t qb_bytes = ((uint64_t)nq + 1) * 8, tab_bytes = qb_bytes + ((uint64_t)nq + 1) * 4;
+  void *hm, *d_q;
+  SHZ_TRY(shz_mailbox(ctx, tab_bytes, &hm));
+  uint64_t* hq = (uint64_t*)hm;
+  uint32_t* hc = (uint32_t*)((char*)hm + qb_bytes);
+  for (uint32_t q = 0; q <= nq; ++q) {
+    hq[q] = (peak_off[clip0[q0 + q]] - peak_off[clip0[q0]]) * K;
+    hc[q] = clip0[q0 + q];
+  }
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SP_Q, tab_bytes, &d_q));
+  SHZ_HIP(ctx, hipMemcpyAsync(d_q, hm, tab_bytes, hipMemcpyHostToDevice, ctx->stream));
+  P->V.qbase = (const uint64_t*)d_q;
+  P->V.clip0 = (const uint32_t*)((char*)d_q + qb_bytes);
+  return sp_run(ctx, P, hash_off);
+}
+
+// ---- the job form: the warp stage on a list of jobs (clip, a range of its peaks, its own pair) -------------
+// first peak of [a, b) whose warped time is >= v (peak times do not decrease inside a clip, and neither does W)
+__device__ __forceinline__ uint64_t sp_lower_bound_w(const uint32_t* __restrict__ pt, uint64_t a, uint64_t b, uint32_t t16, uint64_t v) {
+  while (a < b) {
+    const uint64_t mid = a + ((b - a) >> 1);
+    if ((((uint64_t)pt[mid] * t16 + 32768u) >> 16) < v) a = mid + 1; else b = mid;
+  }
+  return a;
+}
+
+// job j comes in with all peaks of its clip and leaves with those whose warped time lies in [w_lo, w_end]; cnt[j]: how many
+__global__ __launch_bounds__(SP_THREADS) void sp_job_range_kernel(const uint32_t* __restrict__ pt, sp_job* __restrict__ jobs,
+                                                                   uint32_t n_jobs, uint64_t* __restrict__ cnt) {
+  const uint64_t j = (uint64_t)blockIdx.x * SP_THREADS + threadIdx.x;
+  if (j >= n_jobs) return;
+  const sp_job J = jobs[j];
+  const uint64_t a = sp_lower_bound_w(pt, J.c_lo, J.c_hi, J.t16, J.w_lo);
+  const uint64_t b = sp_lower_bound_w(pt, a, J.c_hi, J.t16, J.w_end + 1);
+  jobs[j].c_lo = a;
+  jobs[j].c_hi = b;
+  cnt[j] = b - a;
+}
+
+// The warp stage on jobs: every item takes its factors, its peak range and its segment from its job (sp_decode), segment e
+// of the CSR is job e.  jobs (host, n_jobs >= 1): c_lo / c_hi = the peaks of the job's clip in d_pt.  Two warped-time binary
+// searches per job narrow them on the device, shz_scan_u64 gives the jobs' first items and one read-back their number
+// (*n_items); then the stages of every pass (sp_run).  The job table lies in SHZ_WS_SP_Q, where the product form keeps its
+// own: descriptors | items of every job | their scan.  hash_off: n_jobs + 1 entries (host).  No items: nothing is warped
+// and P's pointers stay unset, as in sp_count
+int32_t sp_count_jobs(shz_ctx* ctx, const uint16_t* d_pf, const uint32_t* d_pt, const sp_job* jobs, uint32_t n_jobs, uint32_t fan,
+                      sp_pass* P, uint64_t* hash_off, uint64_t* n_items) {
+  const uint64_t job_bytes = (uint64_t)n_jobs * sizeof(sp_job);
+  void* d_q;
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SP_Q, job_bytes + (2 * (uint64_t)n_jobs + 1) * 8, &d_q));
+  sp_job* d_jobs = (sp_job*)d_q;
+  uint64_t *d_cnt = (uint64_t*)((char*)d_q + job_bytes), *d_base = d_cnt + n_jobs;   // d_base[n_jobs] = the items of all jobs
+  SHZ_HIP(ctx, shz_memcpy(ctx, d_jobs, jobs, job_bytes, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(sp_job_range_kernel, dim3(sp_blocks(n_jobs)), dim3(SP_THREADS), 0, ctx->stream, d_pt, d_jobs, n_jobs, d_cnt);
+  SHZ_HIP(ctx, hipGetLastError());
+  SHZ_TRY(shz_scan_u64(ctx, d_cnt, d_base, n_jobs, d_base + n_jobs));
+  SHZ_HIP(ctx, shz_memcpy(ctx, n_items, d_base + n_jobs, 8, hipMemcpyDeviceToHost));
+  SHZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  P->n_seg = n_jobs;
+  for (uint64_t e = 0; e <= n_jobs; ++e) hash_off[e] = 0;
+  P->V = sp_view{d_pf, d_pt, nullptr, d_base, nullptr, nullptr, nullptr, n_jobs, 1, fan, *n_items, d_jobs};
+  if (*n_items == 0) return SHZ_OK;
+  SHZ_TRY(sp_fits(ctx, *n_items, fan));
+  return sp_run(ctx, P, hash_off);
 }
 
 int32_t sp_write(shz_ctx* ctx, const sp_pass& P, uint32_t* d_key, uint32_t* d_t1, uint64_t cap) {

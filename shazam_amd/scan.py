@@ -137,7 +137,7 @@ def _scan_warp_windows(run, tl, pl, t16, f16, row, search):
 @takes_delta_tol(lambda *a, **k: (k["db"] if "db" in k else a[1]).ctx)
 def scan_windows(recordings, db, Fs: int = 44100, window_seconds: float = 5, step_seconds: float = 1, topn: int = TOPN,
                  resample_to: int = None, full_sort: bool = False, speeds=None, tempos=None, pitches=None, warps=None,
-                 search: str = "grid", _extents: dict = None):
+                 search: str = "grid", _extents: dict = None, _fit: dict = None):
     """Every window of every recording matched in one library call.  recordings: 1-D int16 arrays, or lists of channels as in
     recognize_batch.  Returns a dict: the arrays of Table.match over all windows, recording-major (sid, delta, aligned, dedup
     [n_windows, topn]; nres, nhash, npairs [n_windows]), plus win_off (CSR of the windows over the recordings), frames (F_r
@@ -160,7 +160,9 @@ def scan_windows(recordings, db, Fs: int = 44100, window_seconds: float = 5, ste
     the other windows try nothing; the answer is the best over everything a window tried, the variants are stage 1's
     followed by the stage-2 grid (the tempos x the pitch rungs stage 1 chose), and stage1 / stage2 carry the stages' own
     best / profile / work.
-    delta_tol= (keyword): the vote tolerance in offset bins while the call runs (Context.tolerance); None: the context's."""
+    delta_tol= (keyword): the vote tolerance in offset bins while the call runs (Context.tolerance); None: the context's.
+    _fit (scan(extents="fit")): the plays stage of a warped scan runs behind the scan on the same prepared audio -- with
+    resample_to= the same device buffer, before it is freed -- and the dict gains "plays" (_play_stage)."""
     from . import DEFAULT_AMP_MIN, DEFAULT_FAN_VALUE, resample_to_device
     if not hasattr(db.table, "h"):
         raise NotImplementedError("scanning takes the unsharded table (shards=1)")
@@ -204,6 +206,8 @@ def scan_windows(recordings, db, Fs: int = 44100, window_seconds: float = 5, ste
         buf, off = resample_to_device(chans, int(Fs), fs, ctx)
         try:
             res, win_off, ms = run(db.table, buf, off, first, wf, sf, fs=fs, pcm_device=True, **kw)
+            if _fit is not None:
+                res["plays"] = _play_stage(ctx, db.table, buf, off, first, wf, sf, fs, hop, res, win_off, _fit, True)
         finally:
             buf.free()
     else:
@@ -213,6 +217,8 @@ def scan_windows(recordings, db, Fs: int = 44100, window_seconds: float = 5, ste
             off[1:] = np.cumsum([len(c) for c in chans])
         pcm = np.concatenate(chans) if off[-1] else np.zeros(1, np.int16)
         res, win_off, ms = run(db.table, pcm, off, first, wf, sf, fs=fs, **kw)
+        if _fit is not None:
+            res["plays"] = _play_stage(ctx, db.table, pcm, off, first, wf, sf, fs, hop, res, win_off, _fit, False)
     frames = np.array([max((ctx.frames_of(int(off[c + 1] - off[c])) for c in range(int(first[r]), int(first[r + 1]))), default=0)
                        for r in range(len(first) - 1)], np.int64)
     res.update(win_off=win_off, frames=frames, window_frames=wf, step_frames=sf, hop=hop, fs=fs, ms=ms)
@@ -222,6 +228,64 @@ def scan_windows(recordings, db, Fs: int = 44100, window_seconds: float = 5, ste
         res.update(tempo=res["warps"][0][res["best"]].astype(np.float64) / 65536.0,
                    pitch=res["warps"][1][res["best"]].astype(np.float64) / 65536.0)
     return res
+
+
+def default_drift_bins(window_frames: int, margin_frames: int, time_factors, tol: int) -> int:
+    """drift_bins=None of scan(extents="fit"): ceil(L h / 65536), L = ceil((window + margin) t_max / 65536) the largest warped
+    edge-zone length and h the largest gap between neighbouring distinct time factors of the variants (0 for one factor) -- a
+    segment's hits may sit a rung from its majority rung, and a play one rung off drifts by h / 65536 bins per warped frame.
+    Clamped so that the candidate of an edge zone, 2 (tol + drift_bins) + 1 bins, stays within the 4,096 of the moments."""
+    t_max = int(np.max(np.asarray(time_factors, np.int64)))
+    L = -(-(int(window_frames) + int(margin_frames)) * t_max // 65536)
+    return max(0, min(-(-L * _rung(time_factors) // 65536), (4096 - 1) // 2 - int(tol)))
+
+
+def _play_stage(ctx, table, pcm, off, first, wf, sf, fs, hop, res, win_off, fit, pcm_device):
+    """The plays stage of scan(extents="fit"): the timeline of the scan just run (fit["timeline"](res, win_off, step) ->
+    (segments, t16, f16): the fold and every segment's own Q16 pair), then ONE Context.scan_plays on the same audio."""
+    from . import DEFAULT_AMP_MIN, DEFAULT_FAN_VALUE
+    seg, t16, f16 = fit["timeline"](res, win_off, sf)
+    margin = wf if fit["margin_seconds"] is None else max(0, int(round(float(fit["margin_seconds"]) * fs / hop)))
+    drift = fit["drift_bins"]
+    if drift is None:
+        drift = default_drift_bins(wf, margin, fit["time_factors"](res), ctx.vote_tolerance)
+    zone, work, ms = ctx.scan_plays(table, pcm, off, first, wf, sf, dict(seg, t16=t16, f16=f16), margin, int(drift), fs=fs,
+                                    amp_min=float(DEFAULT_AMP_MIN), fan_value=DEFAULT_FAN_VALUE, pcm_device=pcm_device)
+    return dict(segments=seg, t16=t16, f16=f16, zones=zone, work=work, ms=ms, margin_frames=margin, drift_bins=int(drift))
+
+
+def _play_keys(w, i, tempo_key):
+    """What extents="fit" adds to segment i.  Zone results are in WARPED recording frames; extent.own_frames
+    maps them back with the segment's own time factor, and the result is clipped to the zone."""
+    from .extent import dense_span, line_fit, own_frames, tempo_of
+    p = w["plays"]
+    zone, t16 = p["zones"], int(p["t16"][i])
+    hop, fs = w["hop"], w["fs"]
+    z = {k: [int(x) for x in zone[k][i]] for k, _ in _ffi.PLAY_ZONE_FIELDS}       # [whole, head, tail] of every field
+    wlo = [(lo * t16 + 32768) >> 16 for lo in z["lo"]]
+    whi = [(hi * t16 + 32768) >> 16 for hi in z["hi"]]
+    secs = lambda frame: round(frame * hop / fs, 5)                              # noqa: E731  (as _segment converts)
+    song_secs = lambda frame: round(float(frame) / DEFAULT_FS * hop, 5)          # noqa: E731  (as offset_seconds converts)
+    clip = lambda f, k: min(max(f, z["lo"][k]), z["hi"][k])                      # noqa: E731
+    d = {"play_first_frame": None, "play_last_frame": None}
+    if z["count"][1]:
+        span = dense_span(zone["hist"][i, 1], z["shift"][1])
+        start = z["q_first"][1] if span is None else wlo[1] + span[0]             # the first warped frame of the play
+        d["play_start_seconds"] = secs(clip(own_frames(start, start, t16)[0], 1))
+        d["play_first_frame"] = own_frames(z["q_first"][1], z["q_first"][1], t16)[0]
+    if z["count"][2]:
+        span = dense_span(zone["hist"][i, 2], z["shift"][2])
+        last = z["q_last"][2] if span is None else min(wlo[2] + span[1], whi[2]) - 1   # its last warped frame
+        d["play_end_seconds"] = secs(clip(own_frames(last, last, t16)[1] + 1, 2))
+        d["play_last_frame"] = own_frames(z["q_last"][2], z["q_last"][2], t16)[1]
+    some = z["count"][0] > 0
+    fit = {k: z[k][0] for k in ("count", "sum_q", "sum_u", "sum_qq", "sum_qu", "d_lo")}
+    line = line_fit(**fit)
+    d.update(song_start_seconds=song_secs(z["t_first"][0]) if some else None,
+             song_end_seconds=song_secs(z["t_last"][0] + 1) if some else None,
+             pairs=z["count"][0], extent_hist=zone["hist"][i, 0].copy(), extent_shift=z["shift"][0], extent_lo=z["lo"][0], fit=fit)
+    d[tempo_key] = None if line is None else float(tempo_of(t16, line[0]))
+    return d
 
 
 def _segment(db, w, seg, i):
@@ -245,7 +309,7 @@ def _segment(db, w, seg, i):
 def scan(recordings, db, Fs: int = 44100, window_seconds: float = 5, step_seconds: float = 1, topn: int = TOPN,
          resample_to: int = None, min_aligned: int = 20, max_gap: int = 1, speeds=None, shift_tol: int = None, rung_tol: int = 1,
          tempos=None, pitches=None, warps=None, search: str = "grid", tempo_tol: int = None, pitch_tol: int = None,
-         extents: bool = False, margin_seconds: float = None):
+         extents=False, margin_seconds: float = None, drift_bins: int = None):
     """The timeline of every recording: a list (per recording) of segments, each a dict with song_id, song_name,
     start_seconds / end_seconds (the span of the segment's windows in the recording, the last window's end clipped to the
     recording's), offset_seconds (the position in the song at the segment's start: align_matches' formula,
@@ -278,22 +342,43 @@ def scan(recordings, db, Fs: int = 44100, window_seconds: float = 5, step_second
     end_seconds), play_first_frame / play_last_frame (the first pair of the head zone, the last of the tail zone, in recording
     frames; None without a pair), song_start_seconds / song_end_seconds (the span of the whole play's pairs in the song,
     converted as offset_seconds; None without a pair), pairs (their number), extent_hist / extent_shift / extent_lo (their
-    histogram over the whole-play zone, which starts at recording frame extent_lo)."""
+    histogram over the whole-play zone, which starts at recording frame extent_lo).
+    extents="fit" (with speeds=, or with tempos= / pitches= / warps= and either search; ValueError without a ladder: use
+    extents=True; NotImplementedError on a sharded table): the same refinement for a warped scan, and the tempo the play
+    really runs at (shz_scan_plays).  The scan and its timeline run exactly as without it; then ONE library
+    call on the same prepared audio warps the frames of every play at the play's own pair, cuts the three zones and runs the
+    extent pass with the moments, the candidate of every zone widened by drift_bins offset bins (None:
+    default_drift_bins) beside the call's tolerance.  Every key above keeps its value; a segment gains play_start_seconds /
+    play_end_seconds (dense_span on the head / tail zone's histogram, which counts WARPED frames; the frame goes through
+    extent.own_frames with the segment's time factor and is clipped to the zone; the fallbacks of extents=True),
+    play_first_frame / play_last_frame (own recording frames), song_start_seconds / song_end_seconds, pairs (of the whole
+    play), extent_hist / extent_shift / extent_lo (bucket b of the whole-play zone holds the warped frames W(extent_lo) + [b <<
+    shift, (b + 1) << shift), W with the segment's time factor), fit (count, the four sums and d_lo of the whole play:
+    extent.line_fit's arguments) and play_tempo (extent.tempo_of on the fitted slope, as a float; None without a fit) -- under
+    speeds= the key is play_speed."""
     from . import OFFSET_SECS
-    if extents:
-        if speeds is not None or tempos is not None or pitches is not None or warps is not None or search != "grid":
-            raise ValueError("extents=True takes the plain scan: warped extents are not implemented (DESIGN.md 8)")
+    ladder = speeds is not None or tempos is not None or pitches is not None or warps is not None or search != "grid"
+    fit = None
+    if isinstance(extents, str):
+        if extents != "fit":
+            raise ValueError('extents is False, True or "fit"')
+        if not ladder:
+            raise ValueError('extents="fit" refines a warped scan (speeds=, tempos=, pitches=, warps=): use extents=True')
+        fit = dict(margin_seconds=margin_seconds, drift_bins=drift_bins)
+    elif extents:
+        if ladder:
+            raise ValueError('extents=True takes the plain scan: a warped scan takes extents="fit" (DESIGN.md 3.7n)')
         return _scan_extents(recordings, db, Fs, window_seconds, step_seconds, topn, resample_to, min_aligned, max_gap, margin_seconds)
     if tempos is not None or pitches is not None or warps is not None or search != "grid":
         if speeds is not None:
             raise ValueError("speeds= is one factor for time and frequency: it excludes tempos=, pitches= and warps=")
         return _scan_warps(recordings, db, Fs, window_seconds, step_seconds, topn, resample_to, min_aligned, max_gap,
                            dict(tempos=tempos, pitches=pitches, warps=warps, search=search), tempo_tol, pitch_tol,
-                           WARP_SHIFT_TOL if shift_tol is None else shift_tol)
+                           WARP_SHIFT_TOL if shift_tol is None else shift_tol, fit)
     shift_tol = 2 if shift_tol is None else shift_tol
     if speeds is not None:
         return _scan_speeds(recordings, db, Fs, window_seconds, step_seconds, topn, resample_to, min_aligned, max_gap, speeds,
-                            shift_tol, rung_tol)
+                            shift_tol, rung_tol, fit)
     w = scan_windows(recordings, db, Fs, window_seconds, step_seconds, topn, resample_to)
     seg = _ffi.scan_timeline(w["win_off"], w["sid"], w["delta"], w["aligned"], w["nres"], w["step_frames"], min_aligned, max_gap)
     out = [[] for _ in range(len(w["frames"]))]
@@ -339,12 +424,20 @@ def _scan_extents(recordings, db, Fs, window_seconds, step_seconds, topn, resamp
 
 
 def _scan_speeds(recordings, db, Fs, window_seconds, step_seconds, topn, resample_to, min_aligned, max_gap, speeds, shift_tol,
-                 rung_tol):
+                 rung_tol, fit=None):
     from . import OFFSET_SECS
-    w = scan_windows(recordings, db, Fs, window_seconds, step_seconds, topn, resample_to, speeds=speeds)
-    sp = w["speeds"]
-    seg = _ffi.scan_timeline_speeds(w["win_off"], w["sid"], w["delta"], w["aligned"], w["nres"], w["best"], w["step_frames"], sp,
-                                    min_aligned, max_gap, rung_tol, shift_tol)
+    sp = _ladder(speeds)
+
+    def timeline(res, win_off, sf):
+        return _ffi.scan_timeline_speeds(win_off, res["sid"], res["delta"], res["aligned"], res["nres"], res["best"], sf, sp,
+                                         min_aligned, max_gap, rung_tol, shift_tol)
+    if fit is not None:
+        def fold(res, win_off, sf):
+            seg = timeline(res, win_off, sf)
+            return seg, sp[seg["rung"]], sp[seg["rung"]]
+        fit = dict(fit, timeline=fold, time_factors=lambda res: sp)
+    w = scan_windows(recordings, db, Fs, window_seconds, step_seconds, topn, resample_to, speeds=speeds, _fit=fit)
+    seg = w["plays"]["segments"] if fit is not None else timeline(w, w["win_off"], w["step_frames"])
     hop, sf = w["hop"], w["step_frames"]
     out = [[] for _ in range(len(w["frames"]))]
     for i in range(len(seg["rec"])):
@@ -360,18 +453,29 @@ def _scan_speeds(recordings, db, Fs, window_seconds, step_seconds, topn, resampl
             "speed": float(sp[int(seg["rung"][i])]) / 65536.0,
             "speed_fit": (p1 - p0) / float((last - first) * sf) if last > first else None,
         }))
+        if fit is not None:
+            d = out[int(seg["rec"][i])][-1]
+            d.update(dict(play_start_seconds=d["start_seconds"], play_end_seconds=d["end_seconds"]), **_play_keys(w, i, "play_speed"))
     return out
 
 
 def _scan_warps(recordings, db, Fs, window_seconds, step_seconds, topn, resample_to, min_aligned, max_gap, variants, tempo_tol,
-                pitch_tol, shift_tol):
+                pitch_tol, shift_tol, fit=None):
     from . import OFFSET_SECS
-    w = scan_windows(recordings, db, Fs, window_seconds, step_seconds, topn, resample_to, **variants)
+
+    def timeline(res, win_off, sf):
+        t16, f16 = res["warps"]
+        return _ffi.scan_timeline_warps(win_off, res["sid"], res["delta"], res["aligned"], res["nres"], res["best"], sf, t16, f16,
+                                        min_aligned, max_gap, _rung(t16) if tempo_tol is None else int(tempo_tol),
+                                        _rung(f16) if pitch_tol is None else int(pitch_tol), shift_tol)
+    if fit is not None:
+        def fold(res, win_off, sf):
+            seg = timeline(res, win_off, sf)
+            return seg, res["warps"][0][seg["warp"]], res["warps"][1][seg["warp"]]
+        fit = dict(fit, timeline=fold, time_factors=lambda res: res["warps"][0])
+    w = scan_windows(recordings, db, Fs, window_seconds, step_seconds, topn, resample_to, _fit=fit, **variants)
     t16, f16 = w["warps"]
-    tempo_tol = _rung(t16) if tempo_tol is None else int(tempo_tol)
-    pitch_tol = _rung(f16) if pitch_tol is None else int(pitch_tol)
-    seg = _ffi.scan_timeline_warps(w["win_off"], w["sid"], w["delta"], w["aligned"], w["nres"], w["best"], w["step_frames"], t16, f16,
-                                   min_aligned, max_gap, tempo_tol, pitch_tol, shift_tol)
+    seg = w["plays"]["segments"] if fit is not None else timeline(w, w["win_off"], w["step_frames"])
     hop, sf = w["hop"], w["step_frames"]
     out = [[] for _ in range(len(w["frames"]))]
     for i in range(len(seg["rec"])):
@@ -388,4 +492,7 @@ def _scan_warps(recordings, db, Fs, window_seconds, step_seconds, topn, resample
             "pitch": float(f16[int(seg["warp"][i])]) / 65536.0,
             "tempo_fit": (p1 - p0) / float((last - first) * sf) if last > first else None,
         }))
+        if fit is not None:
+            d = out[int(seg["rec"][i])][-1]
+            d.update(dict(play_start_seconds=d["start_seconds"], play_end_seconds=d["end_seconds"]), **_play_keys(w, i, "play_tempo"))
     return out
