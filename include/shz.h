@@ -409,7 +409,8 @@ uint64_t shz_recognize_estimate(uint64_t frames, uint32_t fan_value);
  * most 3 windows, so that tests reach the slice, chunk and group borders with tiny inputs (results do not depend on them). */
 #define SHZ_DEBUG_SCAN_SPEED_SMALL_SLICES 32u
 /* Test switch of shz_match_songs_warps: a slice holds one song x at most 2 warps, so that tests reach the slice and chunk
- * borders with tiny inputs (results do not depend on the slicing). */
+ * borders with tiny inputs (results do not depend on the slicing); of shz_match_songs_warps_extents: a slice holds at most 2
+ * jobs. */
 #define SHZ_DEBUG_CATALOG_SMALL_SLICES 64u
 /* Test switch of the vote: the tolerant route (shz_set_vote_tolerance) is taken at tolerance 0 too, where it computes what
  * the other routes compute, so that its kernels can be compared with theirs on the same inputs. */
@@ -584,6 +585,42 @@ int32_t shz_match_songs_warps(shz_ctx* ctx, shz_table* t, const uint32_t* sids, 
                               uint64_t* out_rows, uint32_t* out_sid, int32_t* out_delta, uint32_t* out_aligned,
                               uint32_t* out_dedup, uint32_t* out_nres, uint32_t* out_nhash, uint64_t* out_npairs,
                               float* ms_gather, float* ms_warp, float* ms_match);
+/* WHERE an altered copy overlaps its original, and at what tempo (new): the extent pass of shz_match_extents_fit on songs of
+ * the table warped by the row warp, one JOB a query.  Job j is (job_sid[j], job_t16[j], job_f16[j]) -- usually a pair
+ * shz_match_songs_warps found, at the warp it was found at; one song may stand in several jobs at different warps.  The
+ * query of job j is the set { row warp of (key32, off) under (job_t16[j], job_f16[j]), kept } over the rows of song
+ * job_sid[j]; the outputs are exactly those of shz_match_extents_fit on those queries and the given candidates (candidates
+ * and outputs [n_jobs * ncand], [n_jobs * ncand * 64] for out_hist, which may be NULL, [n_jobs] for out_shift; the four sums
+ * are required).  out_q_first / out_q_last are WARPED frames of the listed song (shazam_amd/extent.py: own_frames takes them
+ * back to its own), out_t_first / out_t_last frames of the candidate song.  out_kept[n_jobs] (may be NULL): the kept warped
+ * rows of every job BEFORE the set collapses rows that meet in one (key, t1'); out_count counts the set.  A song without
+ * rows, or a job whose rows all leave under its warp, is an empty query: its outputs are zero.  With every job at (65536,
+ * 65536) on distinct songs the seven extent arrays equal shz_match_songs_extents' and the sums shz_match_extents_fit's on
+ * the songs' gathered rows.  Numpy twin: tests/rows_fit_twin.py.
+ * Every distinct song is gathered ONCE, on the device, as shz_match_songs gathers it (no row crosses the bus); the JOB FORM
+ * of the row warp lays the work out over (job, row of its song) items, job-major, counts the kept rows per block and per
+ * job, scans, and writes job after job, the kept rows of a job in input order: a job is one contiguous query and the CSR
+ * over the jobs is exact (no atomic decides where a row lands).
+ * Refused before anything is launched: what shz_match_songs_extents and shz_match_extents_fit refuse (the table's state, ncand
+ * outside [1, 64], a cand_n above ncand, d_lo > d_hi, a NULL array: SHZ_E_INVALID / SHZ_E_STATE; a used candidate of 4,096
+ * bins or more, a table offset >= 2^31: SHZ_E_UNSUPPORTED); a factor outside [32768, 131072], a NULL job array with n_jobs
+ * > 0 (SHZ_E_INVALID).  Refused after the gather: a listed offset whose image under its job's t16 reaches 2^20 -- it is a
+ * query offset here -- (SHZ_E_UNSUPPORTED; the message names the offset and the factor); 2^32 gathered rows or more, or 2^32
+ * items (rows over all jobs) or more in one call (SHZ_E_UNSUPPORTED).  n_jobs == 0: SHZ_OK, nothing is written.  The outputs
+ * are written only by a call that returns SHZ_OK.
+ * SLICES: the jobs go in slices of whole jobs whose items -- 8 bytes each in the call's warped columns -- stay within 1/8 of
+ * the workspace limit, each slice through the extent pass (which cuts its queries into sub-batches of its own); the call's
+ * buffers are allocated once, for the largest slice.  Under SHZ_DEBUG_CATALOG_SMALL_SLICES a slice holds at most 2 jobs;
+ * SHZ_DEBUG_EXTENT_SMALL_TILES acts as in shz_match_extents.  Results do not depend on the slicing.  ms_gather / ms_warp /
+ * ms_extent (may be NULL): hipEvent times of the gather, of the warp stages (with their one read-back a slice) and of the
+ * extent passes. */
+int32_t shz_match_songs_warps_extents(shz_ctx* ctx, shz_table* t, const uint32_t* job_sid, const uint32_t* job_t16,
+                                      const uint32_t* job_f16, uint32_t n_jobs, uint32_t ncand, const uint32_t* cand_sid,
+                                      const int32_t* cand_dlo, const int32_t* cand_dhi, const uint32_t* cand_n,
+                                      uint32_t* out_count, uint32_t* out_q_first, uint32_t* out_q_last, uint32_t* out_t_first,
+                                      uint32_t* out_t_last, uint32_t* out_hist, uint32_t* out_shift, uint64_t* out_sum_q,
+                                      uint64_t* out_sum_u, uint64_t* out_sum_qq, uint64_t* out_sum_qu, uint64_t* out_kept,
+                                      float* ms_gather, float* ms_warp, float* ms_extent);
 /* rows streamed / pairs voted by the last shz_match_batch (for HBM accounting) */
 int32_t shz_match_stats(shz_ctx* ctx, uint64_t* rows_scanned, uint64_t* pairs, uint64_t* distinct_keys);
 

@@ -111,6 +111,9 @@ SIGNATURES = {
                                   u64p]),
     "shz_match_songs_warps": (C.c_int32, [vp, vp, vp, C.c_uint32, C.c_uint32, u32p, u32p, C.c_uint32, C.c_uint32, vp, vp, vp, vp,
                                           vp, vp, vp, vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "shz_match_songs_warps_extents": (C.c_int32, [vp, vp, u32p, u32p, u32p, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp,
+                                                  vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                                  C.POINTER(C.c_float)]),
     "shz_match_batch": (C.c_int32, [vp, vp, vp, vp, u64p, C.c_uint32, C.c_uint32, C.c_uint32,
                                     vp, vp, vp, vp, vp, vp, vp]),
     "shz_match_device_host": (C.c_int32, [vp, vp, vp, vp, u64p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int64,
@@ -1550,6 +1553,33 @@ class Table:
                                                      ptr(res["count"]), ptr(res["q_first"]), ptr(res["q_last"]),
                                                      ptr(res["t_first"]), ptr(res["t_last"]), ptr(res["hist"]),
                                                      ptr(res["shift"])))
+        return res
+
+    def match_songs_warps_extents(self, job_sid, tempos, pitches, cand_sid, d_lo, d_hi, cand_n=None, hist=False, timings=False):
+        """match_extents(..., fit=True) with songs of the table, warped on the device, as the queries
+        (shz_match_songs_warps_extents): job j is song job_sid[j] under the row warp (tempos[j], pitches[j]) (Q16); one song
+        may stand in several jobs.  Returns the dict of match_extents(..., fit=True) over the jobs -- q_first / q_last are
+        WARPED frames of the listed song (extent.own_frames takes them back), t_first / t_last frames of the candidate song --
+        plus "kept" [n], the kept warped rows of every job before rows that meet in one (key, t1') collapse.  timings: the
+        dict also holds "ms" = (gather, warp, extent) device times."""
+        a = np.ascontiguousarray(job_sid, np.uint32).reshape(-1)
+        tq, fq = np.ascontiguousarray(tempos, np.uint32).reshape(-1), np.ascontiguousarray(pitches, np.uint32).reshape(-1)
+        n = len(a)
+        if len(tq) != n or len(fq) != n:
+            raise ValueError("job_sid, tempos and pitches are three lists of one length: job j is (job_sid[j], tempos[j], pitches[j])")
+        cs, lo, hi, cn, ncand, res = self._extent_args(n, cand_sid, d_lo, d_hi, cand_n, hist)
+        sums = {f: np.zeros((n, ncand), np.uint64) for f in ("sum_q", "sum_u", "sum_qq", "sum_qu")}
+        kept = np.zeros(n, np.uint64)
+        ms = [C.c_float(), C.c_float(), C.c_float()]
+        self.ctx.check(lib().shz_match_songs_warps_extents(
+            self.ctx.h, self.h, a.ctypes.data_as(u32p), tq.ctypes.data_as(u32p), fq.ctypes.data_as(u32p), n, ncand, ptr(cs), ptr(lo),
+            ptr(hi), ptr(cn), ptr(res["count"]), ptr(res["q_first"]), ptr(res["q_last"]), ptr(res["t_first"]), ptr(res["t_last"]),
+            ptr(res["hist"]), ptr(res["shift"]), *[ptr(s) for s in sums.values()], ptr(kept),
+            *[C.byref(m) if timings else None for m in ms]))
+        res.update(sums)
+        res["kept"] = kept
+        if timings:
+            res["ms"] = tuple(float(m.value) for m in ms)
         return res
 
     def finalize_runs(self, run_rows):

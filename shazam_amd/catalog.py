@@ -16,7 +16,12 @@ hash with its original.  With speeds= / tempos= / pitches= / warps= (the ladders
 warped on the device at every rung (shz_match_songs_warps: a row is two peaks, both are moved and the key is formed again)
 and matched; fold_pairs_warps keeps, per pair, the strongest observation over both sides and all rungs, and says which
 song's rows were warped by which factors.  Votes are counted in ONE delta bin: a rung that misses the true factor by m
-spreads a song of T frames over about T m bins, so long tracks want a finer ladder than short ones."""
+spreads a song of T frames over about T m bins, so long tracks want a finer ladder than short ones.
+
+Where an altered copy overlaps its original: with extents="fit" the found pairs go through one more library
+call (shz_match_songs_warps_extents: every pair's warped song is a JOB at the one warp the pair was found at, its candidate
+the other song around the pair's delta), and pair_extents_warps turns the result into the span in both songs' own frames,
+the rows aligned there and tempo_fit, the factor the copy really runs at between the rungs."""
 from __future__ import annotations
 
 import numpy as np
@@ -47,6 +52,9 @@ PAIR_FIELDS = (("a", np.uint32), ("b", np.uint32), ("delta", np.int64), ("aligne
                ("rows_b", np.uint64), ("coverage_a", np.float64), ("coverage_b", np.float64), ("relation", "U7"))
 EXTENT_PAIR_FIELDS = PAIR_FIELDS + (("a_first", np.uint32), ("a_last", np.uint32), ("b_first", np.uint32), ("b_last", np.uint32))
 WARP_PAIR_FIELDS = PAIR_FIELDS + (("tempo_q16", np.uint32), ("pitch_q16", np.uint32), ("warped", "U1"), ("aligned_plain", np.uint32))
+WARP_EXTENT_PAIR_FIELDS = WARP_PAIR_FIELDS + (("a_first", np.uint32), ("a_last", np.uint32), ("b_first", np.uint32), ("b_last", np.uint32),
+                                              ("count", np.uint32), ("warped_first", np.uint32), ("warped_last", np.uint32),
+                                              ("tempo_fit", np.float64), ("drift_bins", np.uint32))
 S_ONE = 65536
 
 
@@ -316,7 +324,94 @@ def pair_extents(table, pairs, tol: int = 0, batch_rows: int = BATCH_ROWS) -> np
     return out
 
 
-def _find_duplicates_warps(table, sids, lad, topn, min_aligned, min_coverage, batch_rows, timings=False):
+def warp_drift_bins(max_off: int, tempo_q16, tol: int = 0) -> int:
+    """drift_bins=None of pair_extents_warps: speed.default_drift_bins' formula, ceil(t_max h / 65536), with t_max = the image
+    of the table's largest offset max_off under the largest tempo rung among tempo_q16 and h = half the largest gap between
+    neighbouring DISTINCT rungs among tempo_q16 (0 for one rung), clamped so that a candidate's 2 (tol + drift) + 1 bins stay
+    within the 4,096 the moments allow.  Derivation as there: a copy of true tempo a found at rung r puts its aligned rows on
+    the line d = t' (a / r - 1) + c; the found rung is the nearest, |a - r| <= h / 65536, and over the warped frames 0 ..
+    t_max the line moves by at most t_max h / 65536 bins; the pair's delta is one bin ON that line."""
+    rungs = np.unique(np.asarray(tempo_q16, np.int64))
+    if len(rungs) < 2:
+        return 0
+    gap = int(np.max(np.diff(rungs)))                                 # 2 h
+    t_max = (int(max_off) * int(rungs[-1]) + 32768) >> 16
+    drift = -((-t_max * gap) // (2 * S_ONE))
+    return max(0, min(drift, (4096 - 1) // 2 - int(tol)))
+
+
+def _pair_extents_warps(table, pairs, tol, drift_bins, batch_rows, timings=False):
+    """pair_extents_warps, and the (gather, warp, extent) device times of its library calls, summed (zeros without timings)"""
+    from .extent import line_fit, own_frames, tempo_of
+    out = np.zeros(len(pairs), np.dtype(list(WARP_EXTENT_PAIR_FIELDS)))
+    for f, _ in WARP_PAIR_FIELDS:
+        out[f] = pairs[f]
+    out["tempo_fit"] = np.nan
+    ms = np.zeros(3)
+    if len(pairs) == 0:
+        return out, tuple(ms.tolist())
+    tol = int(tol)
+    if drift_bins is None:
+        from .shard import table_maxima
+        drift_bins = warp_drift_bins(table_maxima(table)[1], pairs["tempo_q16"], tol)
+    drift_bins = int(drift_bins)
+    if tol < 0 or drift_bins < 0:
+        raise ValueError("tol and drift_bins must be >= 0")
+    out["drift_bins"] = drift_bins
+    side_a = pairs["warped"] == "a"
+    warped = np.where(side_a, pairs["a"], pairs["b"]).astype(np.uint32)      # the job's song: its rows are warped
+    other = np.where(side_a, pairs["b"], pairs["a"]).astype(np.uint32)       # the job's one candidate
+    d = np.where(side_a, pairs["delta"], -pairs["delta"]).astype(np.int64)   # (fold_pairs_warps turned b's sign: turned back)
+    w = tol + drift_bins
+    ids, inv = np.unique(warped, return_inverse=True)
+    row_off, _, _ = table.song_hashes(ids, counts_only=True)
+    rows = np.diff(np.asarray(row_off).astype(np.int64))[inv]                # rows of every job
+    for part in _batches(rows, np.arange(len(pairs)), batch_rows):
+        ext = table.match_songs_warps_extents(warped[part], pairs["tempo_q16"][part], pairs["pitch_q16"][part], other[part],
+                                              (d[part] - w).astype(np.int32), (d[part] + w).astype(np.int32), hist=False,
+                                              timings=timings)
+        if timings:
+            ms += np.asarray(ext["ms"])
+        for i, p in enumerate(part):
+            n = int(ext["count"][i, 0])
+            out["count"][p] = n
+            if n == 0:
+                continue
+            t16, qf, ql = int(pairs["tempo_q16"][p]), int(ext["q_first"][i, 0]), int(ext["q_last"][i, 0])
+            own = own_frames(qf, ql, t16)
+            there = (int(ext["t_first"][i, 0]), int(ext["t_last"][i, 0]))
+            mine, theirs = (("a_first", "a_last"), ("b_first", "b_last")) if side_a[p] else (("b_first", "b_last"), ("a_first", "a_last"))
+            out[mine[0]][p], out[mine[1]][p] = own
+            out[theirs[0]][p], out[theirs[1]][p] = there
+            out["warped_first"][p], out["warped_last"][p] = qf, ql
+            fit = line_fit(n, ext["sum_q"][i, 0], ext["sum_u"][i, 0], ext["sum_qq"][i, 0], ext["sum_qu"][i, 0], int(d[p]) - w)
+            if fit is not None:
+                out["tempo_fit"][p] = float(tempo_of(t16, fit[0]))
+    return out, tuple(ms.tolist())
+
+
+def pair_extents_warps(table, pairs, tol: int = 0, drift_bins: int = None, batch_rows: int = BATCH_ROWS) -> np.ndarray:
+    """The records of fold_pairs_warps with the position of every pair in both songs and a tempo fit (WARP_EXTENT_PAIR_FIELDS;
+    DESIGN.md 3.7o).  One JOB per pair -- the pair's warped song at its (tempo_q16, pitch_q16) -- with one candidate, the other
+    song at d +- (tol + drift_bins), d = delta where warped == "a" and -delta where warped == "b" (fold_pairs_warps turned that
+    side's sign); the jobs go to Table.match_songs_warps_extents in batches of at most batch_rows rows (one job at least).
+    a_first .. a_last / b_first .. b_last: the frames of song a / b between which the aligned rows lie -- the warped song's
+    are its OWN frames (extent.own_frames of warped_first .. warped_last, its warped frames), the other song's are the
+    candidate's t_first .. t_last.  count: the aligned pairs in the range.  tempo_fit = extent.tempo_of(tempo_q16, slope of
+    extent.line_fit): the warped song runs tempo_fit times as fast as the other -- what tempo_q16 / 65536 says, refined; NaN
+    where line_fit gives None.  All of them are 0 (NaN) where count is 0.  The fit pays on a coarse tempo axis and on long
+    tracks; scripts/catalog_fit_bench.py measured that on 10 s tracks under the default fine ladder the rung is nearer the
+    truth than the fit.
+    drift_bins=None: warp_drift_bins(the table's largest offset, pairs["tempo_q16"], tol), derived, not tuned.  The table's
+    largest offset is an upper bound of every song's length, so the range is wide enough for every pair and wider than a
+    short track needs (chance pairs inside the range pull the line): a catalogue mixing short and long tracks may want an
+    explicit drift_bins.  Only the rungs the pairs were found at are known here: pairs found at ONE rung give no gap and
+    drift_bins 0, pairs found at rungs that are not neighbours a gap larger than the ladder's.  find_duplicates, which has
+    the ladder, derives the value from the ladder's rungs and hands it over."""
+    return _pair_extents_warps(table, pairs, tol, drift_bins, batch_rows)[0]
+
+
+def _find_duplicates_warps(table, sids, lad, topn, min_aligned, min_coverage, batch_rows, timings=False, fit=None):
     from .speed import MAX_WARPS
     t16, f16, row = lad
     min_aligned = MIN_ALIGNED_WARPED if min_aligned is None else min_aligned
@@ -340,13 +435,21 @@ def _find_duplicates_warps(table, sids, lad, topn, min_aligned, min_coverage, ba
                                min_aligned, min_coverage)
     if timings:
         out["ms"] = tuple(np.sum([r["ms"] for r in res], axis=0).tolist()) if res else (0.0, 0.0, 0.0)
+    if fit is not None:   # (tol, drift_bins): the extent stage on the found pairs
+        tol, drift = fit
+        if drift is None and len(out["pairs"]):   # the LADDER's rungs are known here: the pairs' rungs are a subset, their gaps no smaller
+            from .shard import table_maxima
+            drift = warp_drift_bins(table_maxima(table)[1], t16, tol)
+        out["pairs"], ms = _pair_extents_warps(table, out["pairs"], tol, drift, batch_rows, timings)
+        if timings:
+            out["ms"] = out["ms"] + (float(sum(ms)),)
     return out
 
 
 @takes_delta_tol(lambda *a, **k: (lambda x: x.ctx)(k["db_or_table"] if "db_or_table" in k else a[0]))
 def find_duplicates(db_or_table, sids=None, topn: int = 5, min_aligned: int = None, min_coverage: float = None,
                     batch_rows: int = BATCH_ROWS, speeds=None, tempos=None, pitches=None, warps=None, timings: bool = False,
-                    extents: bool = False) -> dict:
+                    extents=False, drift_bins: int = None) -> dict:
     """Duplicate, contained and overlapping tracks among the listed songs (None: every song of the table) and the rest of
     the table.  The songs are walked in batches of at most batch_rows rows (one counts-only gather gives the row counts),
     each batch is one match_songs call, and fold_pairs makes one record per pair.  Returns its dict: "pairs" and
@@ -360,12 +463,29 @@ def find_duplicates(db_or_table, sids=None, topn: int = 5, min_aligned: int = No
     the exact copies in the same answer.  timings (ladder only): "ms" = (gather, warp, match) device times, summed.
     delta_tol= (keyword): the vote tolerance in offset bins while the call runs (Context.tolerance); None: the context's.
     extents: "pairs" gains a_first, a_last, b_first, b_last (EXTENT_PAIR_FIELDS; pair_extents): where in a and where in b the
-    aligned rows lie -- the position of an excerpt inside the longer track, the length of an overlap.  Not with a ladder:
-    warped rows have no extents yet."""
+    aligned rows lie -- the position of an excerpt inside the longer track, the length of an overlap.  extents=True does not
+    take a ladder.
+    extents="fit" (ladder only; the spelling of scan()): the search as above, then pair_extents_warps on the found pairs with
+    tol = the vote tolerance of the call -- "pairs" has WARP_EXTENT_PAIR_FIELDS: where in a and in b an altered copy and its
+    original overlap (each in its song's own frames), how many rows align there, and tempo_fit, the tempo the copy really runs
+    at between the rungs.  drift_bins: bins each side of a pair's delta the extent pass looks at, beside the tolerance; None:
+    warp_drift_bins(the table's largest offset, the LADDER's tempo rungs, tol) -- the formula of pair_extents_warps with the
+    rungs the search really had, whose gaps are no larger than those among the rungs the pairs were found at (on the note
+    corpus of tests/test_gpu_find_duplicates_fit.py the two plants are found at the outer rungs of three: 15 bins from the
+    ladder, 29 from the pairs alone, and at 29 six chance pairs move an excerpt's start by 12 frames).  "clusters" and every column of
+    WARP_PAIR_FIELDS are what the call without extents gives; with timings "ms" gains a fourth entry, the device time of the
+    extent stage (its gather, warp and extent passes together)."""
     table, _ = _table_of(db_or_table)
     lad = _ladder_of(speeds, tempos, pitches, warps)
-    if extents and lad is not None:
-        raise ValueError("extents=True does not take a ladder (speeds= / tempos= / pitches= / warps=)")
+    fit = isinstance(extents, str)
+    if fit and extents != "fit":
+        raise ValueError(f'extents is False, True or "fit"; got {extents!r}')
+    if fit and lad is None:
+        raise ValueError('extents="fit" takes a ladder (speeds= / tempos= / pitches= / warps=); without one use extents=True')
+    if extents and not fit and lad is not None:
+        raise ValueError('extents=True does not take a ladder (speeds= / tempos= / pitches= / warps=); with one use extents="fit"')
+    if drift_bins is not None and not fit:
+        raise ValueError('drift_bins belongs to extents="fit"')
     min_aligned = (MIN_ALIGNED if min_aligned is None else min_aligned) if lad is None else min_aligned
     min_coverage = (MIN_COVERAGE if min_coverage is None else min_coverage) if lad is None else min_coverage
     if sids is None:
@@ -373,7 +493,8 @@ def find_duplicates(db_or_table, sids=None, topn: int = 5, min_aligned: int = No
         sids = np.arange(1, table_maxima(table)[0] + 1, dtype=np.uint32) if table.rows()[0] else np.zeros(0, np.uint32)
     sids = np.ascontiguousarray(sids, np.uint32).reshape(-1)
     if lad is not None:
-        return _find_duplicates_warps(table, sids, lad, topn, min_aligned, min_coverage, batch_rows, timings)
+        return _find_duplicates_warps(table, sids, lad, topn, min_aligned, min_coverage, batch_rows, timings,
+                                      (table.ctx.vote_tolerance, drift_bins) if fit else None)
     row_off, _, _ = table.song_hashes(sids, counts_only=True)
     rows = np.diff(row_off.astype(np.int64))
     live = np.flatnonzero(rows > 0)                  # (songs without rows match nothing)

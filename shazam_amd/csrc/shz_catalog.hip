@@ -769,3 +769,358 @@ extern "C" int32_t shz_match_songs_warps(shz_ctx* ctx, shz_table* t, const uint3
   }
   return SHZ_OK;
 }
+
+// ---- the job form of the row warp: where an altered copy overlaps its original, and at what tempo ---------
+// The product form above warps every listed song at every warp.  The refinement of found pairs needs a JOB LIST: job j is one
+// song (an index into the call's gathered songs) at the one warp (t16, f16) its pair was found at, and a song may stand in
+// several jobs.  Work is laid out over (job j, row r) items, job-major, then the rows of the job's song in gathered order: a
+// job is one contiguous query of the extent pass, and a wave stays at one warp over consecutive rows wherever it lies inside
+// one job.  The two passes are the product form's: blocks of RW_ITEMS items, one wave a block; pass 1 ballots, writes one
+// count per block and adds the kept items to their job's count (one add a wave where the wave lies inside one job); the block
+// counts are scanned; pass 2 repeats the map and writes at block base + rank inside the ballot.  No atomic decides a place.
+// The view stands beside rw_view: the product kernels read what they read before.
+#define RWJ_SMALL_JOBS 2u   // jobs of a slice under SHZ_DEBUG_CATALOG_SMALL_SLICES
+struct rwj_view {                      // what the kernels of one slice of jobs read (device pointers)
+  const uint32_t *key, *off;           // the rows of the call's distinct songs, song after song
+  const uint64_t* roff;                // CSR of those songs over them, from 0
+  const uint32_t *song, *t16, *f16;    // the slice's jobs: song (index into roff), time factor, frequency factor
+  const uint64_t* base;                // nj + 1: first item of every job of the slice (item w of the slice is base[0] + w)
+  uint32_t nj;
+  uint64_t n_items;                    // base[nj] - base[0]
+};
+struct rwj_cursor {
+  uint32_t j, r, n;                    // job (of the slice), row of its song, rows of its song
+  uint64_t row0;                       // the song's first row
+};
+
+// item w < n_items -> its job (the last j whose first item is <= w: empty jobs share a start) and row
+__device__ __forceinline__ void rwj_seek(const rwj_view& V, uint64_t w, rwj_cursor* c) {
+  const uint64_t b0 = V.base[0];
+  uint32_t lo = 0, hi = V.nj;
+  while (lo + 1 < hi) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (V.base[mid] - b0 <= w) lo = mid; else hi = mid;
+  }
+  const uint32_t s = V.song[lo];
+  const uint64_t r0 = V.roff[s];
+  const uint32_t n = (uint32_t)(V.roff[s + 1] - r0);   // (> 0: w lies inside the job's items)
+  const uint64_t rem = w - (V.base[lo] - b0);
+  c->j = lo;
+  c->r = (uint32_t)min(rem, (uint64_t)(max(n, 1u) - 1));   // (the clamp holds for every consistent view; it keeps any read inside the columns)
+  c->n = n;
+  c->row0 = r0;
+}
+
+// the RW_LOADS items of this lane in the block at w0: rows loaded, the job kept as segment; dead lanes: seg = ~0
+__device__ __forceinline__ void rwj_load(const rwj_view& V, uint64_t w0, uint32_t lane, uint32_t* k, uint32_t* o, uint32_t* seg) {
+  rwj_cursor c{0, 0, 0, 0};
+#pragma unroll
+  for (int j = 0; j < RW_LOADS; ++j) {
+    const uint64_t w = w0 + (uint64_t)j * 64 + lane;
+    seg[j] = 0xFFFFFFFFu;
+    k[j] = o[j] = 0;
+    if (w >= V.n_items) continue;
+    if (j == 0 || c.r + 64 >= c.n) rwj_seek(V, w, &c);   // (64 items on: still inside this job's rows?)
+    else c.r += 64;
+    if (c.n == 0) continue;
+    k[j] = V.key[c.row0 + c.r];
+    o[j] = V.off[c.row0 + c.r];
+    seg[j] = c.j;
+  }
+}
+
+// pass 1: kept items of every block, kept items of every job
+__global__ __launch_bounds__(64 * RW_WAVES) void rwj_count_kernel(rwj_view V, uint32_t* __restrict__ blk_cnt,
+                                                                   uint32_t* __restrict__ job_cnt) {
+  const uint32_t lane = threadIdx.x & 63;
+  const uint64_t blk = (uint64_t)blockIdx.x * RW_WAVES + (threadIdx.x >> 6);
+  const uint64_t w0 = blk * RW_ITEMS;
+  if (w0 >= V.n_items) return;   // uniform in the wave
+  uint32_t k[RW_LOADS], o[RW_LOADS], seg[RW_LOADS];
+  rwj_load(V, w0, lane, k, o, seg);
+  uint32_t c = 0;
+#pragma unroll
+  for (int j = 0; j < RW_LOADS; ++j) {
+    const bool live = seg[j] != 0xFFFFFFFFu;
+    const uint32_t e = live ? seg[j] : 0u;   // (a dead lane reads job 0's factors and keeps nothing)
+    uint32_t a, b;
+    const bool keep = rw_warp_row(k[j], o[j], V.t16[e], V.f16[e], &a, &b) && live;
+    const uint64_t m = __ballot(keep);
+    const uint32_t first = (uint32_t)__shfl((int)seg[j], 0, 64);   // (live lanes are a prefix of the wave)
+    if (__ballot(live && seg[j] != first) == 0) {   // the wave inside one job: one add
+      if (lane == 0 && m) atomicAdd(job_cnt + first, (uint32_t)__popcll(m));
+    } else if (keep) {
+      atomicAdd(job_cnt + seg[j], 1u);
+    }
+    c += (uint32_t)__popcll(m);
+  }
+  if (lane == 0) blk_cnt[blk] = c;
+}
+
+// pass 2: every kept item, in item order, at the place the scan of the block counts gives (no store at or beyond cap)
+__global__ __launch_bounds__(64 * RW_WAVES) void rwj_write_kernel(rwj_view V, const uint32_t* __restrict__ blk_pos,
+                                                                   uint32_t* __restrict__ out_key, uint32_t* __restrict__ out_off,
+                                                                   uint64_t cap) {
+  const uint32_t lane = threadIdx.x & 63;
+  const uint64_t blk = (uint64_t)blockIdx.x * RW_WAVES + (threadIdx.x >> 6);
+  const uint64_t w0 = blk * RW_ITEMS;
+  if (w0 >= V.n_items) return;   // uniform in the wave
+  uint32_t k[RW_LOADS], o[RW_LOADS], seg[RW_LOADS];
+  rwj_load(V, w0, lane, k, o, seg);
+  uint64_t base = blk_pos[blk];
+#pragma unroll
+  for (int j = 0; j < RW_LOADS; ++j) {
+    const bool live = seg[j] != 0xFFFFFFFFu;
+    const uint32_t e = live ? seg[j] : 0u;
+    uint32_t a, b;
+    const bool keep = rw_warp_row(k[j], o[j], V.t16[e], V.f16[e], &a, &b) && live;
+    const uint64_t m = __ballot(keep);
+    if (keep) {
+      const uint64_t pos = base + (uint64_t)__popcll(m & ((1ull << lane) - 1ull));
+      if (pos < cap) { out_key[pos] = a; out_off[pos] = b; }
+    }
+    base += (uint64_t)__popcll(m);
+  }
+}
+
+// the largest offset of every gathered song (song_max zeroed; a song without rows keeps 0): one atomicMax a wave where the
+// wave lies inside one song, whose result no order changes
+__global__ __launch_bounds__(256) void rwj_song_max_kernel(const uint32_t* __restrict__ off, const uint64_t* __restrict__ roff,
+                                                            uint32_t n_songs, uint64_t total, uint32_t* __restrict__ song_max) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  const bool live = i < total;
+  uint32_t lo = 0, hi = n_songs;   // the last song whose first row is <= i (empty songs share a start)
+  while (live && lo + 1 < hi) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (roff[mid] <= i) lo = mid; else hi = mid;
+  }
+  uint32_t o = live ? off[i] : 0u;
+  const uint32_t first = (uint32_t)__shfl((int)lo, 0, 64);   // (live lanes are a prefix of the wave)
+  if (__ballot(live && lo != first) == 0) {
+    for (int d = 32; d >= 1; d >>= 1) o = max(o, (uint32_t)__shfl_xor((int)o, d, 64));
+    if ((threadIdx.x & 63) == 0 && o) atomicMax(song_max + first, o);
+  } else if (live && o) {
+    atomicMax(song_max + lo, o);
+  }
+}
+
+namespace {
+
+struct rwj_tabs {                      // the call's tables on the device (one block): roff | base | song | t16 | f16
+  const uint64_t *d_roff = nullptr, *d_base = nullptr;
+  const uint32_t *d_song = nullptr, *d_t16 = nullptr, *d_f16 = nullptr;
+};
+struct rwj_pass {
+  rwj_view V;
+  uint64_t n_blk = 0;
+  uint32_t* d_blk = nullptr;
+};
+
+// roff[n_songs + 1] (from 0), base[n_jobs + 1], and the three job columns, uploaded once a call
+int32_t rwj_upload(shz_ctx* ctx, const uint64_t* row_off, uint32_t n_songs, const uint64_t* base, const uint32_t* song,
+                   const uint32_t* t16, const uint32_t* f16, uint32_t n_jobs, rwj_tabs* T) {
+  const uint64_t ro_bytes = ((uint64_t)n_songs + 1) * 8, ba_bytes = ((uint64_t)n_jobs + 1) * 8, col = (uint64_t)n_jobs * 4;
+  const uint64_t bytes = ro_bytes + ba_bytes + 3 * col;
+  std::vector<char> h(bytes);
+  memcpy(h.data(), row_off, ro_bytes);
+  memcpy(h.data() + ro_bytes, base, ba_bytes);
+  memcpy(h.data() + ro_bytes + ba_bytes, song, col);
+  memcpy(h.data() + ro_bytes + ba_bytes + col, t16, col);
+  memcpy(h.data() + ro_bytes + ba_bytes + 2 * col, f16, col);
+  void* d;
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_RW_TAB, bytes, &d));
+  SHZ_HIP(ctx, shz_memcpy(ctx, d, h.data(), bytes, hipMemcpyHostToDevice));
+  T->d_roff = (const uint64_t*)d;
+  T->d_base = (const uint64_t*)((char*)d + ro_bytes);
+  T->d_song = (const uint32_t*)((char*)d + ro_bytes + ba_bytes);
+  T->d_t16 = T->d_song + n_jobs;
+  T->d_f16 = T->d_t16 + n_jobs;
+  return SHZ_OK;
+}
+
+// pass 1 and the scan of one slice, the jobs [j0, j0 + nj) of n_items items: job_off[nj + 1] (host) is the exact CSR of the
+// jobs' kept rows, relative to the slice.  The stream is idle on return.  A slice without items launches nothing
+int32_t rwj_count(shz_ctx* ctx, const rwj_tabs& T, const uint32_t* d_key, const uint32_t* d_off, uint32_t j0, uint32_t nj,
+                  uint64_t n_items, rwj_pass* P, uint64_t* job_off) {
+  for (uint32_t e = 0; e <= nj; ++e) job_off[e] = 0;
+  P->V = rwj_view{d_key, d_off, T.d_roff, T.d_song + j0, T.d_t16 + j0, T.d_f16 + j0, T.d_base + j0, nj, n_items};
+  P->n_blk = rw_blocks(n_items);
+  if (n_items == 0) return SHZ_OK;
+  void *d_blk, *d_cnt;
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_RW_BLK, P->n_blk * 4, &d_blk));
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_RW_CNT, (uint64_t)nj * 4, &d_cnt));
+  P->d_blk = (uint32_t*)d_blk;
+  SHZ_HIP(ctx, hipMemsetAsync(d_cnt, 0, (uint64_t)nj * 4, ctx->stream));
+  hipLaunchKernelGGL(rwj_count_kernel, dim3((unsigned)((P->n_blk + RW_WAVES - 1) / RW_WAVES)), dim3(64 * RW_WAVES), 0, ctx->stream,
+                     P->V, P->d_blk, (uint32_t*)d_cnt);
+  SHZ_HIP(ctx, hipGetLastError());
+  SHZ_TRY(shz_scan_u32(ctx, P->d_blk, P->d_blk, P->n_blk, nullptr));
+  std::vector<uint32_t> cnt(nj);
+  SHZ_HIP(ctx, shz_memcpy(ctx, cnt.data(), d_cnt, (uint64_t)nj * 4, hipMemcpyDeviceToHost));
+  SHZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  for (uint32_t e = 0; e < nj; ++e) job_off[e + 1] = job_off[e] + cnt[e];
+  return SHZ_OK;
+}
+
+int32_t rwj_write(shz_ctx* ctx, const rwj_pass& P, uint32_t* d_okey, uint32_t* d_ooff, uint64_t cap) {
+  if (P.V.n_items == 0) return SHZ_OK;
+  hipLaunchKernelGGL(rwj_write_kernel, dim3((unsigned)((P.n_blk + RW_WAVES - 1) / RW_WAVES)), dim3(64 * RW_WAVES), 0, ctx->stream,
+                     P.V, (const uint32_t*)P.d_blk, d_okey, d_ooff, cap);
+  SHZ_HIP(ctx, hipGetLastError());
+  return SHZ_OK;
+}
+
+struct rwj_slice { uint32_t j0, nj; };
+
+}  // namespace
+
+extern "C" int32_t shz_match_songs_warps_extents(shz_ctx* ctx, shz_table* t, const uint32_t* job_sid, const uint32_t* job_t16,
+                                                 const uint32_t* job_f16, uint32_t n_jobs, uint32_t ncand, const uint32_t* cand_sid,
+                                                 const int32_t* cand_dlo, const int32_t* cand_dhi, const uint32_t* cand_n,
+                                                 uint32_t* out_count, uint32_t* out_q_first, uint32_t* out_q_last,
+                                                 uint32_t* out_t_first, uint32_t* out_t_last, uint32_t* out_hist, uint32_t* out_shift,
+                                                 uint64_t* out_sum_q, uint64_t* out_sum_u, uint64_t* out_sum_qq, uint64_t* out_sum_qu,
+                                                 uint64_t* out_kept, float* ms_gather, float* ms_warp, float* ms_extent) {
+  if (!ctx || !t) return SHZ_E_INVALID;
+  const char* who = "shz_match_songs_warps_extents";
+  // everything that can be refused from the arguments is refused before the first launch
+  SHZ_TRY(ex_state(ctx, t, who, ncand));
+  if (n_jobs == 0) return SHZ_OK;
+  if (!job_sid || !job_t16 || !job_f16) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: NULL job array", who);
+  for (uint32_t j = 0; j < n_jobs; ++j)
+    if (job_t16[j] < SP_S_MIN || job_t16[j] > SP_S_MAX || job_f16[j] < SP_S_MIN || job_f16[j] > SP_S_MAX)
+      SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: job %u has the factors (%u, %u); factors are Q16 in [%u, %u] (0.5x .. 2x)", who, j, job_t16[j],
+               job_f16[j], SP_S_MIN, SP_S_MAX);
+  if (!out_sum_q || !out_sum_u || !out_sum_qq || !out_sum_qu) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: NULL sum array", who);
+  ex_args A{n_jobs, ncand, cand_sid, cand_dlo, cand_dhi, cand_n, out_count, out_q_first, out_q_last, out_t_first, out_t_last,
+            out_hist, out_shift};
+  A.out_sum_q = out_sum_q;
+  A.out_sum_u = out_sum_u;
+  A.out_sum_qq = out_sum_qq;
+  A.out_sum_qu = out_sum_qu;
+  SHZ_TRY(ex_check(ctx, t, who, A));
+  const bool timed = ms_gather || ms_warp || ms_extent;
+  if (timed) {
+    SHZ_HIP(ctx, hipSetDevice(ctx->device));
+    for (hipEvent_t& e : ctx->sp_ev)
+      if (!e) SHZ_HIP(ctx, hipEventCreate(&e));
+    SHZ_HIP(ctx, hipEventRecord(ctx->sp_ev[0], ctx->stream));
+  }
+  // 1) the distinct songs of the jobs, ascending, each gathered once; job j reads song slot[j] of them
+  std::vector<uint32_t> usid(job_sid, job_sid + n_jobs), slot(n_jobs);
+  std::sort(usid.begin(), usid.end());
+  usid.erase(std::unique(usid.begin(), usid.end()), usid.end());
+  const uint32_t n_songs = (uint32_t)usid.size();
+  for (uint32_t j = 0; j < n_jobs; ++j) slot[j] = (uint32_t)(std::lower_bound(usid.begin(), usid.end(), job_sid[j]) - usid.begin());
+  song_gather G;
+  std::vector<uint64_t> row_off((size_t)n_songs + 1);
+  SHZ_TRY(sg_prepare(t, who, usid.data(), n_songs, row_off.data(), &G));
+  if (G.total >= (1ull << 32))
+    SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "%s: %llu rows in one call (limit 2^32 - 1); list fewer songs", who, (unsigned long long)G.total);
+  std::vector<uint64_t> base((size_t)n_jobs + 1, 0);   // first item of every job
+  for (uint32_t j = 0; j < n_jobs; ++j) base[j + 1] = base[j] + (row_off[slot[j] + 1] - row_off[slot[j]]);
+  if (base[n_jobs] >= (1ull << 32))
+    SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "%s: %llu rows over all jobs in one call (limit 2^32 - 1 items); list fewer jobs", who,
+             (unsigned long long)base[n_jobs]);
+  // the results of all slices collect here: the caller's arrays are written when the whole call succeeded
+  const uint64_t cells = (uint64_t)n_jobs * ncand;
+  std::vector<uint32_t> r_u32(cells * 5 + (out_hist ? cells * 64 : 0) + n_jobs, 0u);
+  std::vector<uint64_t> r_u64(cells * 4 + n_jobs, 0ull);
+  uint32_t *r_hist = out_hist ? r_u32.data() + cells * 5 : nullptr, *r_shift = r_u32.data() + r_u32.size() - n_jobs;
+  uint64_t* r_kept = r_u64.data() + cells * 4;
+  float gather_ms = 0.f, warp_ms = 0.f, extent_ms = 0.f;
+  int32_t rc = SHZ_OK;
+  if (G.total) {   // (no job's song has a row: every query is empty, every output zero)
+    // 2) the slices, from the row counts alone: whole jobs whose items (8 bytes each in the call's warped columns) stay
+    // within 1/8 of the workspace limit; a job is never split
+    const uint64_t max_items = std::max<uint64_t>(ctx->ws_limit / 64, 1);
+    const uint32_t max_jobs = (ctx->debug & SHZ_DEBUG_CATALOG_SMALL_SLICES) ? RWJ_SMALL_JOBS : (1u << 24);
+    std::vector<rwj_slice> plan;
+    uint64_t buf_items = 0;
+    for (uint32_t j0 = 0; j0 < n_jobs;) {
+      uint32_t nj = 1;
+      while (j0 + nj < n_jobs && nj < max_jobs && base[j0 + nj + 1] - base[j0] <= max_items) ++nj;
+      plan.push_back({j0, nj});
+      buf_items = std::max(buf_items, base[j0 + nj] - base[j0]);
+      j0 += nj;
+    }
+    // the call's buffers, once: the gathered columns, the songs' largest offsets, the warped columns of the largest slice
+    sg_bufs own;
+    uint32_t *d_key = (uint32_t*)own.get(G.total * 4), *d_off = (uint32_t*)own.get(G.total * 4);
+    uint32_t* d_smax = (uint32_t*)own.get((uint64_t)n_songs * 4);
+    uint32_t *d_wkey = (uint32_t*)own.get(buf_items * 4), *d_woff = (uint32_t*)own.get(buf_items * 4);
+    if (!d_key || !d_off || !d_smax || !d_wkey || !d_woff)
+      SHZ_FAIL(ctx, SHZ_E_NOMEM, "%s: hipMalloc(2 x %llu + 2 x %llu) failed", who, (unsigned long long)(G.total * 4), (unsigned long long)(buf_items * 4));
+    SHZ_TRY(sg_fill(G, who, d_key, d_off, nullptr));
+    rwj_tabs T;
+    SHZ_TRY(rwj_upload(ctx, row_off.data(), n_songs, base.data(), slot.data(), job_t16, job_f16, n_jobs, &T));
+    // a warped offset is a query offset of the extent pass: every job's largest must stay below 2^20
+    std::vector<uint32_t> smax(n_songs);
+    SHZ_HIP(ctx, hipMemsetAsync(d_smax, 0, (uint64_t)n_songs * 4, ctx->stream));
+    hipLaunchKernelGGL(rwj_song_max_kernel, dim3(nblk(G.total)), dim3(256), 0, ctx->stream, (const uint32_t*)d_off, T.d_roff, n_songs,
+                       G.total, d_smax);
+    SHZ_HIP(ctx, hipGetLastError());
+    const hipError_t e_copy = shz_memcpy(ctx, smax.data(), d_smax, (uint64_t)n_songs * 4, hipMemcpyDeviceToHost);
+    const hipError_t e_sync = hipStreamSynchronize(ctx->stream);   // (the call's buffers are freed on return: the stream is idle)
+    if (e_copy != hipSuccess || e_sync != hipSuccess) SHZ_FAIL(ctx, SHZ_E_HIP, "%s: reading the songs' largest offsets failed", who);
+    for (uint32_t j = 0; j < n_jobs; ++j) {
+      const uint64_t img = ((uint64_t)smax[slot[j]] * job_t16[j] + 32768) >> 16;
+      if (img >= (1ull << 20))
+        SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "%s: song %u of job %u holds offset %u, which the time factor %u / 65536 takes to %llu; warped offsets are query offsets here and must be < 2^20",
+                 who, job_sid[j], j, smax[slot[j]], job_t16[j], (unsigned long long)img);
+    }
+    if (timed) SHZ_HIP(ctx, hipEventRecord(ctx->sp_ev[1], ctx->stream));
+    // 3) warp and extent pass, slice by slice: job = one query
+    std::vector<uint64_t> job_off;
+    bool ev_failed = false;
+    for (const rwj_slice& s : plan) {
+      if (timed && hipEventRecord(ctx->sp_ev[2], ctx->stream) != hipSuccess) { ev_failed = true; break; }
+      job_off.assign((size_t)s.nj + 1, 0);
+      rwj_pass P;
+      rc = rwj_count(ctx, T, d_key, d_off, s.j0, s.nj, base[s.j0 + s.nj] - base[s.j0], &P, job_off.data());
+      const uint64_t total = job_off[s.nj];
+      if (rc == SHZ_OK && total) rc = rwj_write(ctx, P, d_wkey, d_woff, buf_items);
+      if (rc != SHZ_OK) break;
+      for (uint32_t e = 0; e < s.nj; ++e) r_kept[s.j0 + e] = job_off[e + 1] - job_off[e];
+      if (timed && hipEventRecord(ctx->sp_ev[3], ctx->stream) != hipSuccess) { ev_failed = true; break; }
+      if (total) {   // (a slice whose rows all left: its queries are empty, its outputs stay zero)
+        const uint64_t c0 = (uint64_t)s.j0 * ncand;
+        ex_args S{s.nj, ncand, cand_sid + c0, cand_dlo + c0, cand_dhi + c0, cand_n + s.j0, r_u32.data() + c0,
+                  r_u32.data() + cells + c0, r_u32.data() + 2 * cells + c0, r_u32.data() + 3 * cells + c0,
+                  r_u32.data() + 4 * cells + c0, r_hist ? r_hist + c0 * 64 : nullptr, r_shift + s.j0};
+        S.out_sum_q = r_u64.data() + c0;
+        S.out_sum_u = r_u64.data() + cells + c0;
+        S.out_sum_qq = r_u64.data() + 2 * cells + c0;
+        S.out_sum_qu = r_u64.data() + 3 * cells + c0;
+        rc = ex_device(ctx, t, who, d_wkey, d_woff, job_off.data(), S);
+        if (rc != SHZ_OK) break;
+      }
+      if (timed) {
+        float a = 0.f, b = 0.f;
+        if (hipEventRecord(ctx->sp_ev[5], ctx->stream) != hipSuccess || hipEventSynchronize(ctx->sp_ev[5]) != hipSuccess ||
+            hipEventElapsedTime(&a, ctx->sp_ev[2], ctx->sp_ev[3]) != hipSuccess ||
+            hipEventElapsedTime(&b, ctx->sp_ev[3], ctx->sp_ev[5]) != hipSuccess) {
+          ev_failed = true;
+          break;
+        }
+        warp_ms += a;
+        extent_ms += b;
+      }
+    }
+    (void)hipStreamSynchronize(ctx->stream);   // (a refused call may have queued work that reads the columns)
+    if (ev_failed) SHZ_FAIL(ctx, SHZ_E_HIP, "%s: timing a slice failed", who);
+    if (rc != SHZ_OK) return rc;
+    if (timed) SHZ_HIP(ctx, hipEventElapsedTime(&gather_ms, ctx->sp_ev[0], ctx->sp_ev[1]));
+  }
+  uint32_t* outs[5] = {out_count, out_q_first, out_q_last, out_t_first, out_t_last};
+  for (int k = 0; k < 5; ++k) memcpy(outs[k], r_u32.data() + cells * k, cells * 4);
+  if (out_hist) memcpy(out_hist, r_hist, cells * 64 * 4);
+  memcpy(out_shift, r_shift, (uint64_t)n_jobs * 4);
+  uint64_t* sums[4] = {out_sum_q, out_sum_u, out_sum_qq, out_sum_qu};
+  for (int k = 0; k < 4; ++k) memcpy(sums[k], r_u64.data() + cells * k, cells * 8);
+  if (out_kept) memcpy(out_kept, r_kept, (uint64_t)n_jobs * 8);
+  if (ms_gather) *ms_gather = gather_ms;
+  if (ms_warp) *ms_warp = warp_ms;
+  if (ms_extent) *ms_extent = extent_ms;
+  return SHZ_OK;
+}

@@ -100,7 +100,8 @@ enum {
   SHZ_WS_CG_LIST,    // shz_catalog.hip: bitmap of the listed song ids | the list sorted | its slots | the list as given
   SHZ_WS_CG_BLK,     // ... hits of every block of SG_ROWS rows, then their scan
   SHZ_WS_CG_CNT,     // ... rows of every song id up to the largest listed | rows of every listed song | largest offset gathered
-  SHZ_WS_RW_TAB,     // ... the row warp: CSR of the songs over their rows | time factors | frequency factors of the call
+  SHZ_WS_RW_TAB,     // ... the row warp: CSR of the songs over their rows | time factors | frequency factors of the call (the job
+                     // form: CSR of the songs | first item of every job | the jobs' songs | their time | their frequency factors)
   SHZ_WS_RW_BLK,     // ... kept items of every block of RW_ITEMS items of a slice, then their scan
   SHZ_WS_RW_CNT,     // ... kept items of every (song, warp) of a slice
   SHZ_WS_EX_SEGS,    // shz_extent.hip: the segment descriptors
@@ -141,7 +142,7 @@ struct shz_ctx {
   bool tev_init = false;
   hipEvent_t rq_ev[3] = {nullptr, nullptr, nullptr};   // shz_recognize_batch: start, extraction done, match done (created on first use)
   hipEvent_t sc_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // shz_scan_batch / shz_scan_speeds: start, extraction done (then: a warp begun / done); the window stage: a step begun / done, the match behind it done (created on first use)
-  hipEvent_t sp_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // shz_recognize_speeds / shz_match_songs_warps: start, peaks (rows) done, a slice's warp begun / done, its match done, its extent pass done (created on first use)
+  hipEvent_t sp_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // shz_recognize_speeds / shz_match_songs_warps / _warps_extents: start, peaks (rows) done, a slice's warp begun / done, its match done, its extent pass done (created on first use)
   bool profiling = false;
   float kernel_ms[8] = {0};
   uint32_t kernel_launches[8] = {0};
