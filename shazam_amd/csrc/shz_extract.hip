@@ -8,7 +8,7 @@
 // Data layout in HBM (per sub-batch):
 //   pcm      int16, clips concatenated                                        (input)
 //   pw       f64 [frame][DB_STRIDE=2056] POWER (0 stored as 1.0), all clips' frames  (stage buffer)
-//   mask     u64 [frame][n_slabs][4]  one bit per (frame, bin): peak          (stage buffer)
+//   mask     u64 [frame][n_slabs][nw] one bit per (frame, bin): peak          (stage buffer)
 //   peak_f/t u16/u32 in (clip, t asc, f asc) order                             (stage buffer)
 //   key32/t1 u32 in the reference's generation order                           (output)
 #include <type_traits>
@@ -1125,7 +1125,7 @@ __global__ void xctl_advance_kernel(xctl* c, uint32_t cap_peaks, bool hashes) {
 // (__init__.py:155,194-195: peaks ordered by time, then frequency, per clip) -- and does the rest on the list it wrote.
 // Same results as the separate kernels, bit for bit (tests/test_gpu_extract.py runs both on the same inputs).
 #define XT_THREADS 1024
-#define XT_MAX_WORDS (XT_THREADS * 160)   // 4,096 frames of 40 mask words
+#define XT_MAX_WORDS (XT_THREADS * 188)   // 4,096 frames of 47 mask words (fp32 staging: MG_F32)
 #define XT_MAX_PEAKS 65536
 
 __device__ __forceinline__ uint32_t xt_block_scan(uint32_t v, uint32_t* total, uint32_t* tmp) {   // exclusive, 1024 threads
@@ -1322,14 +1322,17 @@ static_assert((uint64_t)(PK_SEG_LONG + 20) * P32_STRIDE * sizeof(float) < (1ull 
               "peak_pick32_kernel adds a row's distance from its segment's first row to a lane's 32-bit byte offset");
 
 static const mask_geom MG_F64 = {(SHZ_NBINS + PK_SW - 1) / PK_SW, 4, 63, PK_SW};
-// waves per peak_pick32 workgroup (slab = 61 nw - 17 bins).  Measured on 644,000 frames: 7 waves (5 slabs) 3.93 ms,
-// 6: 4.47, 4 (10 slabs): 2.65, 3: 2.56, 2 (20 slabs of 105 bins, 19 % halo): 2.05, 1: 2.22 -- small workgroups win
-// although they re-read more halo: the two barriers per 7 frames cost more than the columns.
-// Waves per SIMD: 4 (128 VGPRs): 2.12 ms vs 2.49 at 3.
-#define P32_NW 2
+// peak_pick32: one wave per workgroup, a slab = the wave's P32_OW = 44 output bins (47 slabs, one mask word each; the
+// wave reads 64 columns for them).  P32_OCC is the least occupancy asked for (4 waves per SIMD = 128 VGPRs); the kernel
+// uses 78.  (The geometry sweep of the earlier LDS-shared kernel, 1 to 7 waves a workgroup, is in DESIGN.md 3.2.)
+#define P32_NW 1
 #define P32_OCC 4
-#define P32_SW (61 * P32_NW - 17)
-static const mask_geom MG_F32 = {(SHZ_NBINS + P32_SW - 1) / P32_SW, P32_NW, 61, P32_SW};
+#define P32_SW P32_OW
+static const mask_geom MG_F32 = {(SHZ_NBINS + P32_SW - 1) / P32_SW, P32_NW, P32_OW, P32_SW};
+// The segment rule of upload_meta was tuned with 20 slabs of two waves, 6 workgroups a CU; it decides how a batch is
+// cut, not what is computed, and stays as it was
+#define P32_RULE_SLABS 20
+#define P32_RULE_WG_PER_CU 6
 
 struct sub_batch {
   uint32_t c0, c1;        // clips [c0, c1)
@@ -1696,7 +1699,7 @@ static int32_t stft_stage_rows(shz_ctx* ctx, const int16_t* pcm, const uint64_t*
   uint64_t base;
   SHZ_TRY(stage_pcm(ctx, pcm, clip_off, sb, 0, &d_pcm, &base));
   sub_dev sd;
-  SHZ_TRY(upload_meta(ctx, clip_off, sb, base, MG_F32.n_slabs, 12 / MG_F32.nw, sd, keep));
+  SHZ_TRY(upload_meta(ctx, clip_off, sb, base, P32_RULE_SLABS, P32_RULE_WG_PER_CU, sd, keep));
   void *d_pw, *d_rows;
   SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_DB, staged, &d_pw));
   SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_MISC3, rows, &d_rows));
@@ -2024,7 +2027,7 @@ static int32_t stage_sub_batch(shz_ctx* ctx, const xreq& rq, bool hashes, const 
   const int16_t* d_pcm;
   uint64_t base;
   SHZ_TRY(stage_pcm(ctx, rq.pcm, rq.clip_off, sb, rq.flags, &d_pcm, &base));
-  SHZ_TRY(upload_meta(ctx, rq.clip_off, sb, base, w->mg.n_slabs, xp.f32 ? 12 / w->mg.nw : 3, w->sd, keep));
+  SHZ_TRY(upload_meta(ctx, rq.clip_off, sb, base, xp.f32 ? P32_RULE_SLABS : w->mg.n_slabs, xp.f32 ? P32_RULE_WG_PER_CU : 3, w->sd, keep));
   SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_DB, (uint64_t)sb.frames * pw_bytes_per_frame(xp.f32), &w->d_pw));
   w->sa = make_stft_args(ctx, d_pcm, w->sd, w->nc, sb.frames, rq.fs, w->d_pw);
   if (xp.f32) SHZ_TRY(launch_stft<float>(ctx, w->sa, xp.persistent_stft));

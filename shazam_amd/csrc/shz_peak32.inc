@@ -15,7 +15,8 @@
 // (peak_pick_kernel<true>) and splices their entries into the batch's; every other clip of the batch is settled here.
 // XF_FALLBACK (more undecided cells than the list holds) still sends the whole pass to fp64 staging.
 
-#define P32_PF 7  // frames per barrier group (3 groups = one van Herk block of 21)
+#define P32_BH 7   // rows of a time block = rows of a load group; divides the segment lengths 42, 252 and 672
+#define P32_OW 44  // output columns of a wave: its 64 columns less the 10 halo columns on either side
 // predicate codes of the compare builtins that return the lane mask (__builtin_amdgcn_uicmp / sicmp / fcmpf)
 enum { P32_OGE = 3, P32_UGE = 35, P32_SGE = 39 };
 
@@ -47,9 +48,6 @@ struct mask_geom {
 };
 
 __device__ __forceinline__ bool key_near(float p, float m, int d) { return __float_as_int(p) >= __float_as_int(m) - d; }
-__device__ __forceinline__ float f_wave_shl1(float v) {  // value of lane + 1 (lane 63: unspecified)
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x130 /* wave_shl:1 */, 0xF, 0xF, false));
-}
 
 struct p32_args {
   const float* A;            // [frame][P32_STRIDE]
@@ -63,32 +61,40 @@ struct p32_args {
   uint32_t* frame_cnt;       // peaks per frame (zeroed by the host): what the scan in front of peak_expand needs
 };
 
-// Workgroup = NW waves = (clip segment, slab of SW = 61 NW - 17 bins); wave w, lane l holds slab column 61 w + l
-// (lanes 61..63 repeat lanes 0..2 of the next wave, so pair and quad maxima come from DPP wave shifts).
-// Frequency direction through LDS: rows of pair maxima r2[i] = max(x[i], x[i+1]) and quad maxima r4[i] = max(x[i..i+3]);
-// the 20 neighbours of column c in its row are r4[c-10], r4[c-6], r2[c-2] | r2[c+1], r4[c+3], r4[c+7]: six 4-byte reads
-// give the row maximum WITHOUT the centre (mx), and e = key(centre) - key(mx) classifies the centre in its row:
-// e >= 3 alone at the top, e >= 0 holds the maximum, e >= -1 within one step of it (3 bits per row, packed).
-// Time direction: van Herk / Gil-Werman on blocks of 21 frames (prefix maximum R1 of the current block, suffix maxima S1
-// of the previous one: 2 max per frame); the row maxima of both blocks stay in registers (cur, prev), so a wave that
-// finds a lane whose centre is within one step of its window maximum -- one wave-row in eight -- can work out there and
-// then whether that lane is alone (second-largest row maximum of the window, 20 max) or has to be listed.
+// Block rule of non-maximum suppression (Neubeck and Van Gool 2006): the 21x21 window of a cell contains every cell at most
+// 10 rows and 10 columns away, so a cell that is not within two key steps of the maximum of ANY set of such cells is neither
+// a peak nor listed (both need key(cell) >= key(window maximum) - 2, see `hot` below).  Only the few cells that pass such a
+// test get the window test; the others cost a select and a maximum.
+// Workgroup = one wave = (clip segment, slab of P32_OW = 44 bins); lane l holds slab column l - 10, lanes 10..53 are the
+// output columns.  Waves share nothing: no LDS memory, no barrier; the 20 halo columns are re-read (through L2).
+// Blocks: P32_BH = 7 rows (the load group; divides 42, 252, 672, and blocks start at the segment's first frame) by a
+// SLIDING 21 columns centred on the lane, not an aligned 8 or 16: the window of a cell in rows 7k..7k+6 holds those 7 rows
+// of its 21 columns whole, and so does it hold block k-1 for the block's rows 0..3 and block k+1 for rows 3..6.  So
+//   bm = the lane's column maximum over a block (3 max3), hm = the maximum of bm over lanes l-10..l+10 (once per block:
+//   doubling, 7 lane permutes + 5 max), and a cell of block k goes on only if its key >= key(max(hm[k], hm[k-+1])) - 2:
+// one compare per stored row, taken as a lane mask, a wave-uniform branch.  That is a test against 14 x 21 = 294 cells; about
+// one row in seven has a lane that passes (0.85 rows a block on noise), where aligned 7 x 8 blocks would pass eight cells
+// per seven rows.
+// A row that goes on is decided once block k+2 is complete (its window reaches row 7k+16), from the rows of blocks
+// k-2..k+2, which stay in registers (5 x 7; the five blocks rotate through five unrolled phases, so nothing is moved):
+// mx = the row maximum without the centre (20 neighbouring lanes), co = the lane's column maximum over the window's other
+// 20 rows (10 max3), t2 = the maximum of co over the 21 lanes = the largest of the other rows' maxima, t1 = max(mx, centre,
+// t2) = the window maximum; then the tests of the rule above, as before: alone at the top by more than 2 steps and > p_hi:
+// mask bit and frame_cnt; within a step of the maximum and >= p_lo but not alone: undecided list.
+// Lane permutes are ds_bpermute_b32: they use the LDS crossbar but no LDS memory, and only once per block and per row
+// that goes on, never per row.
 // The mask buffer is zeroed by the host; only non-zero words are written.
-// The loads of the next group of P32_PF rows are in flight while a group is worked on: every group issues exactly P32_PF
-// loads, without a branch (a row past the segment's last is a re-read of the last, a column outside the spectrum a re-read
-// of column 0; the value is replaced by -inf where the group is CONSUMED), so the wait in front of a group's rows is
-// vmcnt(P32_PF), the loads just issued staying in flight.  (With each load behind its own `if (tn < hi)` the count was
-// unknown to the compiler and the wait was vmcnt(0) right behind the loads in two groups of three: DESIGN.md 3.2.)
-// Two groups ahead (14 rows in flight per lane) was measured in round 4 on 644,000 frames, with those vmcnt(0) waits:
-// 2.13 ms -> 2.38 at 4 waves per SIMD (the 7 extra registers spill) and 2.41 at 3.
+// The loads of the next group of P32_BH rows are in flight while a group is worked on: every group issues exactly P32_BH
+// loads, without a branch (a row outside the segment and its halo is a re-read of the nearest row inside, a column outside
+// the spectrum a re-read of column 0; the value is replaced by -inf where the group is CONSUMED), so the wait in front of a
+// group's rows is vmcnt(P32_BH), the loads just issued staying in flight.  (With each load behind its own `if (tn < hi)`
+// the count was unknown to the compiler and the wait was vmcnt(0) right behind the loads: DESIGN.md 3.2.)
+template <int PH> struct p32_phase { static constexpr int value = PH; };
+
 template <int NW, int OCC>
 __global__ __launch_bounds__(64 * NW, OCC) void peak_pick32_kernel(p32_args a) {
-  constexpr int TH = 64 * NW, SW = 61 * NW - 17;
-  // lanes 61..63 of a wave hold no column of their own (their pair / quad maxima are the next wave's): they store into a
-  // dump column behind the row instead of being masked off row by row
-  constexpr int TW = TH + 64;
-  __shared__ float r2[P32_PF][TW];
-  __shared__ float r4[P32_PF][TW];
+  static_assert(NW == 1, "waves share nothing: one wave per workgroup, one mask word per slab");
+  constexpr int BH = P32_BH, SW = P32_OW;
   // XCD-aware work map (a speed choice only): workgroups b, b+8, b+16, ... share an XCD and its L2 (round-robin
   // dispatch), so the n_slabs slabs of one segment are given to consecutive workgroups of ONE XCD: the 20 halo columns
   // neighbouring slabs share are then read from HBM once, not once per XCD.
@@ -97,28 +103,43 @@ __global__ __launch_bounds__(64 * NW, OCC) void peak_pick32_kernel(p32_args a) {
   const uint32_t slab = (b >> 3) % a.n_slabs;
   if ((b >> 3) / a.n_slabs >= per_xcd || seg_i >= a.n_segs) return;   // uniform: before any barrier
   const peak_seg sg = a.segs[seg_i];
-  const int j = threadIdx.x, lane = j & 63, wave = j >> 6;
+  const int lane = threadIdx.x;
   const float NEG = -__builtin_inff();
-  const int li = 61 * wave + lane;                               // LDS column = bin - (slab*SW - 10)
-  const int col = (int)slab * SW - 10 + li;
+  const int col = (int)slab * SW - 10 + lane;
   const bool loads = col >= 0 && col < SHZ_NBINS;
-  const bool owns = lane < 61 && li >= 10 && li <= 61 * NW - 8;  // output column li (window = LDS columns li-10 .. li+10)
-  const bool is_out = owns && col < SHZ_NBINS;
+  const bool is_out = lane >= 10 && lane < 10 + SW && col < SHZ_NBINS;  // window = lanes lane-10 .. lane+10
   const uint64_t out_m = __builtin_amdgcn_ballot_w64(is_out);     // the wave's output lanes as a scalar mask
-  const int lo = (int)sg.t0 - 10 > 0 ? (int)sg.t0 - 10 : 0;
+  const int t0 = (int)sg.t0, t1 = (int)sg.t1;
+  const int lo = t0 - 10 > 0 ? t0 - 10 : 0;
   const int hi = (int)(sg.t1 + 10 < sg.nframes ? sg.t1 + 10 : sg.nframes);
-  const int end = (int)sg.t1 + 10;  // last iteration decides frame t1-1
   const uint32_t boff = loads ? (uint32_t)col * 4u : 0u;         // byte offset in a row (a lane outside the spectrum: column 0)
   const float* base = a.A + (uint64_t)sg.gframe0 * P32_STRIDE;   // uniform; rows are added as uniform offsets
-  const int o = owns ? li - 10 : 0;                              // other lanes read columns 0..17: valid, ignored
-  const int wcol = lane < 61 ? li : TH + lane;                   // where this lane stores its row values
+  // the value of lane + d (mod 64) by ds_bpermute_b32: the byte address of the source lane's register
+  auto lane_at = [&](int d) { return ((lane + d) & 63) << 2; };
+  const int a1 = lane_at(1), a2 = lane_at(2), a4 = lane_at(4), a6 = lane_at(6), a8 = lane_at(8), a9 = lane_at(9),
+            a10 = lane_at(10), am2 = lane_at(-2), am10 = lane_at(-10);
+  auto from = [](int addr, float v) { return __int_as_float(__builtin_amdgcn_ds_bpermute(addr, __float_as_int(v))); };
+  // maximum over lanes l-10 .. l+10 (true for lanes 10..53, whose 21 lanes exist): x[l-10..l+5], x[l+6..l+9], x[l+10]
+  auto max21 = [&](float x) {
+    const float w2 = fmaxf(x, from(a1, x)), w4 = fmaxf(w2, from(a2, w2)), w8 = fmaxf(w4, from(a4, w4));
+    const float w16 = fmaxf(w8, from(a8, w8));
+    return fmaxf(fmaxf(from(am10, w16), from(a6, w4)), from(a10, x));
+  };
+  // the same without lane l itself: x[l-10..l-3], x[l-2..l-1] | x[l+1..l+8], x[l+9..l+10]
+  auto max20 = [&](float x) {
+    const float w2 = fmaxf(x, from(a1, x)), w4 = fmaxf(w2, from(a2, w2)), w8 = fmaxf(w4, from(a4, w4));
+    return fmaxf(fmaxf(from(am10, w8), from(am2, w2)), fmaxf(from(a1, w8), from(a9, w2)));
+  };
 
-  float S1[21], cur[21], prev[21], pre[P32_PF];
-  uint32_t qc[3] = {0, 0, 0}, qp[3] = {0, 0, 0};  // 3-bit row classes of the current / previous block, 7 rows per word
-  float R1 = NEG;
+  // R[b]: the rows of a block; five blocks rotate through the five slots.  hm[b]: see the header
+  float R[5][BH], hm[5], pre[BH];
 #pragma unroll
-  for (int u = 0; u < 21; ++u) { S1[u] = NEG; prev[u] = NEG; cur[u] = NEG; }
-  // row t of the segment's clip, clamped to the last row that exists (hi > lo >= 0): the segment's first row as the uniform
+  for (int b5 = 0; b5 < 5; ++b5) {
+    hm[b5] = NEG;
+#pragma unroll
+    for (int i = 0; i < BH; ++i) R[b5][i] = NEG;
+  }
+  // row t of the segment's clip, clamped to the rows the segment reads (hi > lo >= 0): the segment's first row as the uniform
   // base, and one 32-bit offset per lane = the lane's byte offset in a row + the row's distance from that base (a segment
   // and its halo: at most PK_SEG_LONG + 20 rows of 8,256 bytes, asserted where the segments are cut).  The load is the
   // scalar-base form, global_load_dword v, v_off, s[base]; a row costs min, subtract, multiply (scalar) and one 32-bit add
@@ -127,107 +148,97 @@ __global__ __launch_bounds__(64 * NW, OCC) void peak_pick32_kernel(p32_args a) {
   typedef __attribute__((address_space(1))) const float gfloat;
   gchar* const row0 = (gchar*)(base + (uint64_t)(uint32_t)lo * P32_STRIDE);
   auto row_load = [&](int t) {
-    const uint32_t roff = (uint32_t)(min(t, hi - 1) - lo) * (uint32_t)(P32_STRIDE * sizeof(float));
+    const uint32_t roff = (uint32_t)(min(max(t, lo), hi - 1) - lo) * (uint32_t)(P32_STRIDE * sizeof(float));
     return *(gfloat*)(row0 + (boff + roff));
   };
+  // Blocks are counted from the segment's first frame: block k = rows t0 + 7k .. t0 + 7k + 6, k = -2 (its rows t0-10..t0-8
+  // are the first a window reaches) .. n_blk + 1.  Step s consumes block s - 2 and decides the rows of block s - 4.
+  const int n_blk = (t1 - t0 + BH - 1) / BH, n_steps = n_blk + 4;
 #pragma unroll
-  for (int p = 0; p < P32_PF; ++p) pre[p] = row_load(lo + p);
-  for (int tb = lo; tb < end; tb += 21) {
-    // which of the block's 21 centre frames tb - 10 + u lie inside the segment: one scalar word per block, one bit test per
-    // row (the two compares and the mask logic per row were a third of the scalar instructions of this loop)
-    const int c_lo = max((int)sg.t0 - (tb - 10), 0), c_hi = min((int)sg.t1 - (tb - 10), 21);
-    const uint32_t seg_bits = c_hi > c_lo ? ((1u << (c_hi - c_lo)) - 1u) << c_lo : 0u;
+  for (int p = 0; p < BH; ++p) pre[p] = row_load(t0 - 2 * BH + p);
+
+  // one step; PH = s mod 5 at compile time, so that block s - d lives in slot (PH - d) mod 5 and no row is ever moved
+  auto step = [&](auto ph, const int s) {
+    constexpr int PH = decltype(ph)::value;
+    constexpr int S0 = PH, S1 = (PH + 4) % 5, S2 = (PH + 3) % 5, S3 = (PH + 2) % 5, S4 = (PH + 1) % 5;  // blocks s, s-1, .. s-4
+    const int tb = t0 + (s - 2) * BH;   // first row of the block consumed
+    // the rows one group ahead: exactly BH loads, no branch, nothing done with the values in this step
+    float nxt[BH];
 #pragma unroll
-    for (int g3 = 0; g3 < 21 / P32_PF; ++g3) {
-      float v[P32_PF], mx[P32_PF];
-      // the frames one group ahead: exactly P32_PF loads, no branch, nothing done with the values in this group
-      float nxt[P32_PF];
+    for (int i = 0; i < BH; ++i) nxt[i] = row_load(tb + BH + i);
+    __builtin_amdgcn_sched_barrier(0);  // issued BEFORE the wait for this block's rows: that wait is then vmcnt(BH)
+    // the block's rows as loaded one step ago; what the segment does not read (row outside [lo, hi), column outside the
+    // spectrum) becomes -inf here, where the value is first needed, by one select on a lane mask made of scalars.
+    // Which rows exist: one scalar word per block, one bit test per row
+    const int v_lo = max(lo - tb, 0), v_hi = min(hi - tb, BH);
+    const uint32_t row_bits = v_hi > v_lo ? ((1u << (v_hi - v_lo)) - 1u) << v_lo : 0u;
 #pragma unroll
-      for (int i = 0; i < P32_PF; ++i) nxt[i] = row_load(tb + P32_PF * (g3 + 1) + i);
-      __builtin_amdgcn_sched_barrier(0);  // issued BEFORE the wait for this group's rows: that wait is then vmcnt(P32_PF)
-      // the group's rows as loaded one group ago; what does not exist (row past the segment, column outside the spectrum)
-      // becomes -inf here, where the value is first needed, by one select on a lane mask made of scalars
+    for (int i = 0; i < BH; ++i) {
+      R[S0][i] = (loads && ((row_bits >> i) & 1u)) ? pre[i] : NEG;
+      pre[i] = nxt[i];
+    }
+    const float bm = fmaxf(fmaxf(fmaxf(R[S0][0], R[S0][1]), fmaxf(R[S0][2], R[S0][3])),
+                           fmaxf(fmaxf(R[S0][4], R[S0][5]), R[S0][6]));
+    static_assert(BH == 7, "the block maximum and the thresholds below are written for 7 rows");
+    hm[S0] = max21(bm);
+    if (s < 4) return;   // uniform
+    // block k = s - 4 in slot S2, k-1 in S3 (whole inside the window of rows 0..3), k+1 in S1 (rows 3..6)
+    const int tk = t0 + (s - 4) * BH;
+    const uint32_t seg_bits = (1u << min(t1 - tk, BH)) - 1u;   // rows of the block inside the segment (t1 > tk: s < n_steps)
+    const int k_lo = __float_as_int(fmaxf(hm[S2], hm[S3])) - 2, k_hi = __float_as_int(fmaxf(hm[S2], hm[S1])) - 2;
+    const int k_mid = max(k_lo, k_hi);
 #pragma unroll
-      for (int i = 0; i < P32_PF; ++i) {
-        v[i] = (loads && tb + P32_PF * g3 + i < hi) ? pre[i] : NEG;
-        pre[i] = nxt[i];
+    for (int i = 0; i < BH; ++i) {
+      const float c = R[S2][i];
+      const uint64_t cand = !((seg_bits >> i) & 1u)
+                                ? 0ull
+                                : out_m & __builtin_amdgcn_sicmp(__float_as_int(c), i < 3 ? k_lo : i > 3 ? k_hi : k_mid, P32_SGE);
+      if (!cand) continue;   // wave-uniform: no lane of this row is within two steps of its 14 x 21 cells' maximum
+      const int tc = tk + i;
+      // the centre in its row: e >= 5 alone at the top, >= 2 holds the row maximum, >= 1 within one step of it
+      const float mx = max20(c), c1 = fmaxf(mx, c);
+      int e = __float_as_int(c) - __float_as_int(mx) + 2;
+      const uint32_t q = (uint32_t)min(max(e, 0), 5);
+      // the lane's column over the window's other rows tc-10 .. tc+10: rows i+d of block k, which are row (i+d) mod 7 of a
+      // neighbouring block where i+d leaves 0..6
+      float co = NEG;
+#pragma unroll
+      for (int d = -10; d <= 10; ++d) {
+        if (d == 0) continue;
+        const int r = i + d + 2 * BH, bq = r / BH, br = r % BH;   // bq: 0 = block k-2 .. 4 = block k+2
+        co = fmaxf(co, bq == 0 ? R[S4][br] : bq == 1 ? R[S3][br] : bq == 2 ? R[S2][br] : bq == 3 ? R[S1][br] : R[S0][br]);
       }
-      __syncthreads();  // every wave is done reading the previous group's rows
-#pragma unroll
-      for (int i = 0; i < P32_PF; ++i) {
-        const float p2 = fmaxf(v[i], f_wave_shl1(v[i]));                 // columns li, li+1     (valid: lane < 63)
-        const float p4 = fmaxf(p2, f_wave_shl1(f_wave_shl1(p2)));        // columns li .. li+3   (valid: lane < 61)
-        r2[i][wcol] = p2; r4[i][wcol] = p4;
-      }
-      __syncthreads();
-#pragma unroll
-      for (int i = 0; i < P32_PF; ++i) {
-        const float l = fmaxf(fmaxf(r4[i][o], r4[i][o + 4]), r2[i][o + 8]);
-        const float r = fmaxf(fmaxf(r4[i][o + 13], r4[i][o + 17]), r2[i][o + 11]);
-        mx[i] = fmaxf(l, r);
-      }
-      uint32_t qw = 0;
-      // time direction (registers only)
-#pragma unroll
-      for (int i = 0; i < P32_PF; ++i) {
-        const int u = P32_PF * g3 + i;
-        const int t = tb + u;
-        const float m = fmaxf(mx[i], v[i]);
-        int e = __float_as_int(v[i]) - __float_as_int(mx[i]) + 2;   // >= 5 alone, >= 2 holds the row maximum, >= 1 near it
-        e = min(max(e, 0), 5);
-        qw |= (uint32_t)e << (3 * i);
-        if (i == P32_PF - 1) qc[g3] = qw;
-        R1 = (u == 0) ? m : fmaxf(R1, m);
-        cur[u] = m;
-        const float t1 = (u < 20) ? fmaxf(S1[(u + 1) % 21], R1) : R1;
-        // centre frame t - 10: position u-10 of the current block or u+11 of the previous one
-        const int kc = (u + 11) % 21;
-        const float c1 = (u >= 10) ? cur[kc] : prev[kc];
-        // class word of the centre row (the current group's word is still being assembled in qw)
-        const uint32_t cw = (u >= 10) ? ((kc / P32_PF == g3) ? qw : qc[kc / P32_PF]) : qp[kc / P32_PF];
-        const uint32_t q = (cw >> (3 * (kc % P32_PF))) & 7u;
-        const int tc = t - 10;
-        const bool in_seg = (seg_bits >> u) & 1u;
-        // hot <=> in_seg && is_out && q >= 1 && key_near(c1, t1, 1) && t1 >= p_lo, kept as the lane MASK the compares
-        // deliver (a ballot of a bool made of several compares goes through a 0/1 register and a compare with zero)
-        const int kt1 = __float_as_int(t1);
-        const uint64_t hot = !in_seg ? 0ull
-                                     : out_m & __builtin_amdgcn_uicmp(q, 1u, P32_UGE) &
-                                           __builtin_amdgcn_sicmp(__float_as_int(c1), kt1 - 1, P32_SGE) &
-                                           __builtin_amdgcn_fcmpf(t1, a.p_lo, P32_OGE);
-        if (hot) {  // wave-uniform: some lane's centre is within one step of its window maximum
-          float t2 = NEG;     // largest row maximum of the window's other rows
-#pragma unroll
-          for (int k = 0; k < 21; ++k) {
-            if (k == kc) continue;
-            const bool in_cur = k <= u;  // window rows: cur[0..u] and prev[u+1..20]
-            t2 = fmaxf(t2, in_cur ? cur[k] : prev[k]);
-          }
-          const bool exact = q >= 2u && c1 == t1;
-          const bool uniq = q == 5u && !key_near(t2, t1, 2);
-          const bool hot_l = (hot >> lane) & 1ull;
-          const bool pk = hot_l && exact && uniq && t1 > a.p_hi;
-          const bool und = hot_l && !pk;
-          const unsigned long long bal = __builtin_amdgcn_ballot_w64(pk);
-          if (bal && lane == 0) {
-            a.mask[((uint64_t)(sg.gframe0 + tc) * a.n_slabs + slab) * NW + wave] = bal;
-            atomicAdd(&a.frame_cnt[sg.gframe0 + tc], (uint32_t)__popcll(bal));
-          }
-          if (und) {
-            const uint32_t idx = atomicAdd(&a.ctl->und_count, 1u);
-            if (idx < a.und_cap) a.und_list[idx] = ((uint64_t)(sg.gframe0 + tc) << 12) | (uint32_t)col;
-          }
+      const float t2 = max21(co);          // largest row maximum of the window's other rows
+      const float w1 = fmaxf(c1, t2);      // the window's maximum
+      // hot <=> in_seg && is_out && q >= 1 && key_near(c1, w1, 1) && w1 >= p_lo, kept as the lane MASK the compares
+      // deliver (a ballot of a bool made of several compares goes through a 0/1 register and a compare with zero)
+      const uint64_t hot = out_m & __builtin_amdgcn_uicmp(q, 1u, P32_UGE) &
+                           __builtin_amdgcn_sicmp(__float_as_int(c1), __float_as_int(w1) - 1, P32_SGE) &
+                           __builtin_amdgcn_fcmpf(w1, a.p_lo, P32_OGE);
+      if (hot) {  // wave-uniform: some lane's centre is within one step of its window maximum
+        const bool exact = q >= 2u && c1 == w1;
+        const bool uniq = q == 5u && !key_near(t2, w1, 2);
+        const bool hot_l = (hot >> lane) & 1ull;
+        const bool pk = hot_l && exact && uniq && w1 > a.p_hi;
+        const bool und = hot_l && !pk;
+        const unsigned long long bal = __builtin_amdgcn_ballot_w64(pk);
+        if (bal && lane == 0) {
+          a.mask[(uint64_t)(sg.gframe0 + tc) * a.n_slabs + slab] = bal;
+          atomicAdd(&a.frame_cnt[sg.gframe0 + tc], (uint32_t)__popcll(bal));
         }
-        if (u == 20) {  // block complete: it becomes the previous one; suffix maxima
-          qp[0] = qc[0]; qp[1] = qc[1]; qp[2] = qc[2];
-#pragma unroll
-          for (int k = 0; k < 21; ++k) prev[k] = cur[k];
-          S1[20] = cur[20];
-#pragma unroll
-          for (int k = 19; k >= 0; --k) S1[k] = fmaxf(cur[k], S1[k + 1]);
+        if (und) {
+          const uint32_t idx = atomicAdd(&a.ctl->und_count, 1u);
+          if (idx < a.und_cap) a.und_list[idx] = ((uint64_t)(sg.gframe0 + tc) << 12) | (uint32_t)col;
         }
       }
     }
+  };
+  for (int s = 0; s < n_steps; s += 5) {
+    step(p32_phase<0>{}, s);
+    if (s + 1 < n_steps) step(p32_phase<1>{}, s + 1);
+    if (s + 2 < n_steps) step(p32_phase<2>{}, s + 2);
+    if (s + 3 < n_steps) step(p32_phase<3>{}, s + 3);
+    if (s + 4 < n_steps) step(p32_phase<4>{}, s + 4);
   }
 }
 
@@ -380,7 +391,8 @@ __global__ __launch_bounds__(256, 2) void peak_verify_kernel(verify_args a) {
       if (pk) {
         const uint32_t slab = (uint32_t)bin / a.mg.sw;
         const uint32_t lic = (uint32_t)bin - slab * a.mg.sw + 10;
-        const uint32_t wv = lic / a.mg.lane_stride, ln = lic % a.mg.lane_stride;
+        // the wave that OWNS the column (a wave's lanes reach past lane_stride where the next wave or slab takes over)
+        const uint32_t wv = min(lic / a.mg.lane_stride, a.mg.nw - 1u), ln = lic - wv * a.mg.lane_stride;
         const unsigned long long was = atomicOr((unsigned long long*)&a.mask[((uint64_t)g * a.mg.n_slabs + slab) * a.mg.nw + wv], 1ull << ln);
         if (!((was >> ln) & 1ull)) atomicAdd(&a.frame_cnt[g], 1u);
       }
