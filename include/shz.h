@@ -419,6 +419,10 @@ uint64_t shz_recognize_estimate(uint64_t frames, uint32_t fan_value);
  * its LDS table 4 (element, segment) descriptors instead of 512, and a sub-batch 3 queries instead of 4,096, so that tests
  * reach every border with tiny inputs (results do not depend on any of them). */
 #define SHZ_DEBUG_EXTENT_SMALL_TILES 256u
+/* Test switch of shz_repeats_batch / shz_repeats_hashes: a slice holds one recording, an expand tile 64 pairs instead of
+ * 2,048 and a block of the flag, count and cell kernels 64 elements instead of 256, so that tests reach every border with
+ * tiny inputs (results do not depend on any of them). */
+#define SHZ_DEBUG_REPEAT_SMALL_SLICES 512u
 int32_t shz_set_debug(shz_ctx* ctx, uint32_t flags);
 /* The vote's tolerance, a setting of the context that holds for its later calls (default 0).  With c[sid][d] the votes of a
  * query per song and offset difference d = db_off - q_off, and S(sid, d) = the sum of c[sid][d .. d + bins]: a song's
@@ -1264,6 +1268,69 @@ int32_t shz_scan_plays(shz_ctx* ctx, shz_table* t, const int16_t* pcm, const uin
                        uint32_t* zone_t_first, uint32_t* zone_t_last, uint32_t* zone_shift, uint32_t* zone_hist,
                        uint64_t* zone_sum_q, uint64_t* zone_sum_u, uint64_t* zone_sum_qq, uint64_t* zone_sum_qu,
                        uint64_t* out_work, float* ms_extract, float* ms_warp, float* ms_extent);
+
+/* ---- repeated content inside a recording (new; no table, no catalogue) -------------------------------------------------
+ * "Which stretches of this recording air more than once?" -- adverts, jingles, idents, a song nobody has inserted yet.  Two
+ * hashes of one recording with the same key at times t_i < t_j vote for the lag t_j - t_i; a stretch that airs twice piles
+ * its votes on one lag over a contiguous stretch of t_i (tests/repeat_twin.py is the definition in Python).
+ * All quantities are integers, in frames at the ctx's hop.
+ * HASHES: recording r owns the adjacent clips (its channels) [rec_clip0[r], rec_clip0[r + 1]), as in shz_scan_batch; H_r is
+ * the SET of (key32, t1) over its channels.  rec_hashes[r] = |H_r|.
+ * PAIRS: per key of H_r with the distinct times t_0 < ... < t_(m-1): m > max_run is a stop hash -- no pairs, 1 to
+ * rec_skipped_keys[r], m to rec_skipped_rows[r]; otherwise every i < j with min_lag <= t_j - t_i <= max_lag is the pair
+ * (lag = t_j - t_i, t = t_i).  Pairs never cross recordings.  rec_pairs[r] = their number.
+ * CELLS: (r, lag, block = t >> cell_shift) with pairs (count), first (min t) and last (max t).  Returned: the cells with
+ * pairs >= min_cell_pairs in the order (r, lag, block) ascending -- cell_lag / _block / _pairs / _first / _last [cap_cells] --
+ * and cell_off[n_recs + 1], their CSR over the recordings.  More than cap_cells: SHZ_E_CAPACITY, *count = the cells needed;
+ * cell_off and the four rec_* arrays are filled all the same, and the first cap_cells cells written.
+ * The device chain, all integer: compose rec << 52 | key32 << 20 | t1; sort on the significant bits, unique; runs (one key
+ * of one recording); partners of every element by two binary searches inside its run; a 64-bit scan; pair keys rec << 40 |
+ * lag << 20 | t written by output tile; sort on the bits from cell_shift up; cell heads, exact min / max, compaction.
+ * Recordings go through the pair stage in slices of consecutive whole recordings whose two pair buffers fit 1/8 of the
+ * workspace limit (shz_set_workspace_limit); the results do not depend on the slicing (SHZ_DEBUG_REPEAT_SMALL_SLICES).  A
+ * single recording whose pairs do not fit is SHZ_E_UNSUPPORTED: the message names it, its pairs and the two knobs, min_lag
+ * and max_run.  More than 4,096 recordings in one call, or 2^32 hashes or more: SHZ_E_UNSUPPORTED.
+ * Refused before anything is launched, nothing written (SHZ_E_INVALID): a NULL ctx, count, cell_off or rec_* array, a NULL
+ * cell array with cap_cells > 0, a NULL column with hashes; clips without a recording, rec_clip0 / hash_off / clip_off that
+ * do not start at 0, decrease or do not end at n_clips; unknown flag bits; max_lag < min_lag; max_lag >= 2^20; max_run
+ * outside [2, 1024]; cell_shift > 19; min_cell_pairs of 0; (shz_repeats_hashes) a t1 >= 2^20; (shz_repeats_batch) fan_value
+ * outside [1, 64].  n_recs = 0 or no hashes: SHZ_OK, no cells, cell_off all 0.
+ * shz_repeats_hashes: key32 / t1 are HOST columns, hash_off[n_clips + 1] their CSR over the clips; they are copied into
+ * device buffers the call allocates and frees (tests / tools, as shz_match_device_host).  flags: 0.
+ * shz_repeats_batch: the clips are fingerprinted into the library's own buffers (as shz_scan_batch: pcm host, or device with
+ * SHZ_PCM_DEVICE) and the chain reads them there -- no hash crosses the bus.  ms_extract / ms_pairs / ms_cells (may be NULL):
+ * hipEvent intervals of the extraction, of compose .. expand and of the cell stage.  They are intervals on the stream, not
+ * kernel time alone: the host read-backs inside a stage (the unique count and the recordings' numbers in ms_pairs; per
+ * slice the cell count, the kept count and the copy of the cells in ms_cells) and their synchronisations lie inside them.
+ * They are written (0 first) only once nothing more can be refused before a launch. */
+int32_t shz_repeats_hashes(shz_ctx* ctx, const uint32_t* key32, const uint32_t* t1, const uint64_t* hash_off, uint32_t n_clips,
+                           const uint32_t* rec_clip0, uint32_t n_recs, uint32_t min_lag, uint32_t max_lag, uint32_t max_run,
+                           uint32_t cell_shift, uint32_t min_cell_pairs, uint32_t flags, uint64_t* cell_off, uint32_t* cell_lag,
+                           uint32_t* cell_block, uint32_t* cell_pairs, uint32_t* cell_first, uint32_t* cell_last,
+                           uint32_t* rec_hashes, uint32_t* rec_skipped_keys, uint64_t* rec_pairs, uint64_t* rec_skipped_rows,
+                           uint64_t cap_cells, uint64_t* count);
+int32_t shz_repeats_batch(shz_ctx* ctx, const int16_t* pcm, const uint64_t* clip_off, uint32_t n_clips, const uint32_t* rec_clip0,
+                          uint32_t n_recs, uint32_t fs, double amp_min, uint32_t fan_value, uint32_t min_lag, uint32_t max_lag,
+                          uint32_t max_run, uint32_t cell_shift, uint32_t min_cell_pairs, uint32_t flags, uint64_t* cell_off,
+                          uint32_t* cell_lag, uint32_t* cell_block, uint32_t* cell_pairs, uint32_t* cell_first,
+                          uint32_t* cell_last, uint32_t* rec_hashes, uint32_t* rec_skipped_keys, uint64_t* rec_pairs,
+                          uint64_t* rec_skipped_rows, uint64_t cap_cells, uint64_t* count, float* ms_extract, float* ms_pairs,
+                          float* ms_cells);
+/* The fold (no GPU, no ctx): the returned cells of every recording joined into repeats.  Two cells of one recording are
+ * LINKED iff |lag - lag'| <= lag_tol and |block - block'| <= max_gap + 1; a repeat is a connected component of that relation
+ * whose summed pairs reach min_pairs.  Per repeat: rec; lag = the lag holding the most pairs of the component (the smaller
+ * on a tie); lag_lo / lag_hi; first (min) and last (max) over its cells; pairs (64 bits); cells.  The audio of [first, last]
+ * airs again at [first + lag, last + lag].  Order: (rec, first, lag, smallest cell index of the component) ascending.  Each
+ * cell looks its neighbours up in the sorted list (union-find over cell indices): no pass over all pairs of cells.  Two-call
+ * idiom as shz_scan_timeline: more than cap repeats: SHZ_E_CAPACITY, *count = their number, the first cap are written (cap =
+ * 0: the rep_* pointers may be NULL).  SHZ_E_INVALID: a NULL count, cell_off (which must start at 0 and not decrease) or, with
+ * cells, a NULL cell array; a NULL rep_* array with cap > 0; cells of a recording that are not in strictly ascending (lag,
+ * block) order; a cell whose first > last. */
+int32_t shz_repeats_fold(const uint64_t* cell_off, uint32_t n_recs, const uint32_t* cell_lag, const uint32_t* cell_block,
+                         const uint32_t* cell_pairs, const uint32_t* cell_first, const uint32_t* cell_last, uint32_t lag_tol,
+                         uint32_t max_gap, uint64_t min_pairs, uint32_t* rep_rec, uint32_t* rep_lag, uint32_t* rep_lag_lo,
+                         uint32_t* rep_lag_hi, uint32_t* rep_first, uint32_t* rep_last, uint64_t* rep_pairs, uint32_t* rep_cells,
+                         uint64_t cap, uint64_t* count);
 
 #ifdef __cplusplus
 }

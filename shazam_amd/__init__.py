@@ -389,3 +389,5 @@ from .speed import (pitch_ladder, recognize_speeds, recognize_warps, speed_ladde
                     warp_hashes, warp_hashes_tf)
 # the catalogue against itself (csrc/shz_catalog.hip): the rows of listed songs as queries, duplicates and excerpts among them
 from .catalog import find_duplicates, fold_pairs, fold_pairs_warps, match_songs  # noqa: E402,F401
+# repeated content inside recordings, no catalogue (csrc/shz_repeat.hip): the lag histogram of a recording against itself
+from .repeats import find_repeats, find_repeats_hashes, occurrences  # noqa: E402,F401

@@ -22,6 +22,7 @@ DEBUG_SCAN_SPEED_SMALL_SLICES = 32   # shz_scan_speeds: at most 1 recording x 2 
 DEBUG_CATALOG_SMALL_SLICES = 64   # shz_match_songs_warps: one song x at most 2 warps a slice
 DEBUG_VOTE_TOLERANT_ROUTE = 128   # the vote: the tolerant route at tolerance 0 too
 DEBUG_EXTENT_SMALL_TILES = 256   # shz_match_extents: tiles of 64 pairs, 4 descriptors in LDS, 3 queries a sub-batch
+DEBUG_REPEAT_SMALL_SLICES = 512  # shz_repeats_*: one recording a slice, expand tiles of 64 pairs, blocks of 64 elements
 SCAN_NO_WARP = 0xFFFFFFFF            # shz_scan_warps: out_best of a window that tried no variant
 SCAN_U32, SCAN_POPC64, SCAN_U64 = 0, 1, 2   # shz_scan_host kinds
 STAGE_F32, STAGE_F64, STAGE_PERSISTENT = 0, 1, 1   # shz_stft_stage_host kinds | flag
@@ -224,6 +225,13 @@ SIGNATURES = {
                                    C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32,
                                    vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(C.c_float),
                                    C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "shz_repeats_hashes": (C.c_int32, [vp, vp, vp, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                       C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint64, u64p]),
+    "shz_repeats_batch": (C.c_int32, [vp, vp, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.c_double, C.c_uint32, C.c_uint32,
+                                      C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                      vp, C.c_uint64, u64p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "shz_repeats_fold": (C.c_int32, [vp, C.c_uint32, vp, vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint64, vp, vp, vp, vp, vp, vp,
+                                     vp, vp, C.c_uint64, u64p]),
 }
 
 
@@ -379,7 +387,8 @@ class Context:
         matches its queries in slices of at most 2, 32: shz_scan_speeds works in slices of 1 recording x 2 rungs and matches
         its windows in groups of at most 3, 64: shz_match_songs_warps works in slices of 1 song x 2 warps, 128: the vote takes
         the tolerant route at tolerance 0 too, 256: the extent kernel works in tiles of 64 pairs with 4 descriptors in LDS and
-        sub-batches of 3 queries)."""
+        sub-batches of 3 queries, 512: shz_repeats_* works in slices of one recording, expand tiles of 64 pairs and blocks of
+        64 elements)."""
         self.check(lib().shz_set_debug(self.h, int(flags)))
 
     def set_vote_tolerance(self, bins: int):
@@ -759,6 +768,95 @@ class Context:
                                         C.byref(cnt), *[C.byref(m) for m in ms])
         res = self._windows_with_room(call, lambda n: _match_result(n, topn), cnt, cap_windows)
         return res, wo, tuple(float(m.value) for m in ms)
+
+    # ---- repeated content inside recordings (shz_repeat.hip) -----------------------------------------------------------
+    def _repeats_call(self, fn, nr, cap_cells, fill):
+        """The outputs of shz_repeats_hashes / shz_repeats_batch and their capacity idiom.  fn(out, cap, cnt) -> rc.  cap_cells
+        None: a first call with no room names the count, a second one has it; a number: that one call as it is.  fill: what
+        the arrays hold beforehand (tests).  Returns (rc, out, count): out = cell_off, the CELL_FIELDS arrays (cut to the cells
+        written), rec_hashes, rec_skipped_keys, rec_pairs, rec_skipped_rows."""
+        cnt = C.c_uint64(fill)
+
+        def room(cap):
+            out = {k: np.full(int(cap), fill, np.uint32) for k in CELL_FIELDS}
+            out.update(cell_off=np.full(nr + 1, fill, np.uint64), rec_hashes=np.full(nr, fill, np.uint32),
+                       rec_skipped_keys=np.full(nr, fill, np.uint32), rec_pairs=np.full(nr, fill, np.uint64),
+                       rec_skipped_rows=np.full(nr, fill, np.uint64))
+            return out
+        if cap_cells is None:
+            out = room(0)
+            rc = fn(out, 0, cnt)
+            if rc == E_CAPACITY:
+                out = room(int(cnt.value))
+                rc = fn(out, int(cnt.value), cnt)
+            self.check(rc)
+        else:
+            out = room(cap_cells)
+            rc = fn(out, int(cap_cells), cnt)
+        n = int(cnt.value)
+        if rc in (OK, E_CAPACITY):
+            for k in CELL_FIELDS:
+                out[k] = out[k][:min(n, len(out[k]))]
+        return rc, out, n
+
+    @staticmethod
+    def _repeat_outs(out, cap):
+        cells = [ptr(out[k]) if cap else None for k in CELL_FIELDS]
+        return [ptr(out["cell_off"]), *cells, ptr(out["rec_hashes"]), ptr(out["rec_skipped_keys"]), ptr(out["rec_pairs"]),
+                ptr(out["rec_skipped_rows"])]
+
+    def repeats_hashes_raw(self, key32, t1, hash_off, rec_clip0, min_lag, max_lag, max_run=64, cell_shift=5, min_cell_pairs=8,
+                           flags=0, cap_cells=None, fill=0):
+        """One shz_repeats_hashes as it is on HOST columns: (rc, out, count) -- see _repeats_call."""
+        k = np.ascontiguousarray(key32, np.uint32)
+        t = np.ascontiguousarray(t1, np.uint32)
+        ho = np.ascontiguousarray(hash_off, np.uint64)
+        rc0 = np.ascontiguousarray(rec_clip0, np.uint32)
+        nc, nr = len(ho) - 1, len(rc0) - 1
+
+        def fn(out, cap, cnt):
+            return lib().shz_repeats_hashes(self.h, ptr(k), ptr(t), ptr(ho), nc, ptr(rc0), nr, int(min_lag), int(max_lag),
+                                            int(max_run), int(cell_shift), int(min_cell_pairs), int(flags),
+                                            *self._repeat_outs(out, cap), int(cap), C.byref(cnt))
+        return self._repeats_call(fn, nr, cap_cells, fill)
+
+    def repeats_hashes(self, key32, t1, hash_off, rec_clip0, min_lag, max_lag, max_run=64, cell_shift=5, min_cell_pairs=8):
+        """shz_repeats_hashes (two calls): the repeat cells of recordings given as fingerprints -- host columns key32 / t1,
+        hash_off their CSR over the clips, recording r = the clips [rec_clip0[r], rec_clip0[r + 1]).  Returns a dict: cell_off
+        (CSR of the cells over the recordings), lag, block, pairs, first, last per cell, and rec_hashes, rec_pairs,
+        rec_skipped_keys, rec_skipped_rows per recording."""
+        _, out, _ = self.repeats_hashes_raw(key32, t1, hash_off, rec_clip0, min_lag, max_lag, max_run, cell_shift, min_cell_pairs)
+        return out
+
+    def repeats_batch_raw(self, pcm, clip_off, rec_clip0, min_lag, max_lag, max_run=64, cell_shift=5, min_cell_pairs=8, fs=44100,
+                          amp_min=10.0, fan_value=5, pcm_device=False, cap_cells=None, fill=0):
+        """One shz_repeats_batch as it is: (rc, out, count, ms) -- out as _repeats_call, ms = (extract, pairs, cells) device
+        times of the last call."""
+        co, nc = self._clip_off(clip_off)
+        rc0 = np.ascontiguousarray(rec_clip0, np.uint32)
+        nr = len(rc0) - 1
+        ms = [C.c_float(float(np.float32(fill))) for _ in range(3)]
+
+        def fn(out, cap, cnt):
+            return lib().shz_repeats_batch(self.h, ptr(pcm), ptr(co), nc, ptr(rc0), nr, int(fs), float(amp_min), int(fan_value),
+                                           int(min_lag), int(max_lag), int(max_run), int(cell_shift), int(min_cell_pairs),
+                                           PCM_DEVICE if pcm_device else 0, *self._repeat_outs(out, cap), int(cap), C.byref(cnt),
+                                           *[C.byref(m) for m in ms])
+        rc, out, n = self._repeats_call(fn, nr, cap_cells, fill)
+        return rc, out, n, tuple(float(m.value) for m in ms)
+
+    def repeats_batch(self, pcm, clip_off, rec_clip0, min_lag, max_lag, max_run=64, cell_shift=5, min_cell_pairs=8, fs=44100,
+                      amp_min=10.0, fan_value=5, pcm_device=False, cap_cells=None):
+        """shz_repeats_batch: fingerprint the clips and find the repeat cells of recording r = clips [rec_clip0[r],
+        rec_clip0[r + 1]) in one call, the hashes staying on the device.  cap_cells: the room of the first call (None: a call
+        for the count, then one with that room -- the audio is fingerprinted twice; a number large enough: one call).  Returns
+        (out, ms): out as repeats_hashes, ms = (extract, pairs, cells) device times."""
+        args = (pcm, clip_off, rec_clip0, min_lag, max_lag, max_run, cell_shift, min_cell_pairs, fs, amp_min, fan_value, pcm_device)
+        rc, out, n, ms = self.repeats_batch_raw(*args, cap_cells)      # (cap_cells None: both calls, checked)
+        if rc == E_CAPACITY:
+            rc, out, n, ms = self.repeats_batch_raw(*args, n)
+        self.check(rc)
+        return out, ms
 
     def scan_extents_raw(self, table: "Table", pcm, clip_off, rec_clip0, window_frames, step_frames, min_aligned, max_gap=1,
                          margin_frames=0, d_tol=0, fs=44100, amp_min=10.0, fan_value=5, topn=2, pcm_device=False, full_sort=False,
@@ -1248,6 +1346,36 @@ def scan_timeline(win_off, sid, delta, aligned, nres, step_frames, min_aligned, 
     """shz_scan_timeline (host only, two calls): the rank-0 answers of a scan folded into segments -- arrays rec, sid, shift
     (song frame - recording frame), first / last (windows of the recording), hits, best (largest aligned count)."""
     return _timeline(scan_timeline_raw, "shz_scan_timeline", win_off, sid, delta, aligned, nres, step_frames, min_aligned, max_gap)
+
+
+CELL_FIELDS = ("lag", "block", "pairs", "first", "last")
+REPEAT_FIELDS = (("rec", np.uint32), ("lag", np.uint32), ("lag_lo", np.uint32), ("lag_hi", np.uint32), ("first", np.uint32),
+                 ("last", np.uint32), ("pairs", np.uint64), ("cells", np.uint32))
+
+
+def repeats_fold_raw(cell_off, lag, block, pairs, first, last, lag_tol=1, max_gap=1, min_pairs=100, cap=0, fill=0):
+    """One shz_repeats_fold as it is (host only): (rc, repeats, count) with room for `cap` repeats (arrays REPEAT_FIELDS)."""
+    co = np.ascontiguousarray(cell_off, np.uint64)
+    cols = [np.ascontiguousarray(a, np.uint32) for a in (lag, block, pairs, first, last)]
+    assert all(len(a) >= int(co[-1]) for a in cols) if len(co) else True
+    rep = {k: np.full(int(cap), fill, d) for k, d in REPEAT_FIELDS}
+    cnt = C.c_uint64(fill)
+    rc = lib().shz_repeats_fold(ptr(co), len(co) - 1, *[ptr(a) for a in cols], int(lag_tol), int(max_gap), int(min_pairs),
+                                *[ptr(rep[k]) if cap else None for k, _ in REPEAT_FIELDS], int(cap), C.byref(cnt))
+    return rc, rep, int(cnt.value)
+
+
+def repeats_fold(cell_off, lag, block, pairs, first, last, lag_tol=1, max_gap=1, min_pairs=100) -> dict:
+    """shz_repeats_fold (host only, two calls): the repeat cells of shz_repeats_* joined into repeats -- arrays rec, lag (the
+    lag holding the most pairs), lag_lo, lag_hi, first, last (frames: [first, last] airs again at [first + lag, last + lag]),
+    pairs, cells; ordered by (rec, first, lag)."""
+    args = (cell_off, lag, block, pairs, first, last, lag_tol, max_gap, min_pairs)
+    rc, rep, n = repeats_fold_raw(*args, 0)
+    if rc == E_CAPACITY:
+        rc, rep, n = repeats_fold_raw(*args, n)
+    if rc != OK:
+        raise ShzError(rc, "shz_repeats_fold: bad arguments")
+    return rep
 
 
 ZONE_FIELDS = ("lo", "hi", "count", "q_first", "q_last", "t_first", "t_last", "shift")

@@ -371,6 +371,8 @@ extern "C" int32_t shz_ctx_destroy(shz_ctx* ctx) {
     if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : ctx->sp_ev)
     if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : ctx->rp_ev)
+    if (e) (void)hipEventDestroy(e);
   if (ctx->tev_init)
     for (auto& e : ctx->tev) {
       (void)hipEventDestroy(e[0]);

@@ -113,6 +113,14 @@ enum {
   SHZ_WS_SP_XTAB,    // shz_speed.hip, the extent stage of shz_recognize_warps_extents: first hash of every query's best variant in the
                      // slice's columns | the CSR of the packed queries
   SHZ_WS_SP_XKEY, SHZ_WS_SP_XT1,   // ... the hashes of the best variants of a slice, packed one query behind the other
+  SHZ_WS_RP_REC,     // shz_repeat.hip: totals | first hash, first unique element, pairs in front and skip counters of every recording
+  SHZ_WS_RP_U,       // ... the unique composed hashes rec << 52 | key32 << 20 | t1, sorted
+  SHZ_WS_RP_FLAG, SHZ_WS_RP_SCAN,   // ... head flags and their scan: of the sorted hashes, of the runs, of a slice's sorted pairs
+  SHZ_WS_RP_RUN,     // ... first element of every run (one key of one recording), the element count behind the last
+  SHZ_WS_RP_LO,      // ... first partner of every element
+  SHZ_WS_RP_CNT, SHZ_WS_RP_POFF,    // ... partners of every element | pairs in front of it, the total behind the last
+  SHZ_WS_RP_CELL,    // ... a slice's cells: first pair | first | last | keep flag | place among the kept
+  SHZ_WS_RP_OUT,     // ... a slice's kept cells: rec | lag | block | pairs | first | last
   SHZ_WS_COUNT
 };
 
@@ -143,6 +151,7 @@ struct shz_ctx {
   hipEvent_t rq_ev[3] = {nullptr, nullptr, nullptr};   // shz_recognize_batch: start, extraction done, match done (created on first use)
   hipEvent_t sc_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // shz_scan_batch / shz_scan_speeds: start, extraction done (then: a warp begun / done); the window stage: a step begun / done, the match behind it done (created on first use)
   hipEvent_t sp_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // shz_recognize_speeds / shz_match_songs_warps / _warps_extents: start, peaks (rows) done, a slice's warp begun / done, its match done, its extent pass done (created on first use)
+  hipEvent_t rp_ev[3] = {nullptr, nullptr, nullptr};   // shz_repeats_batch / _hashes: a stage begun, the pairs done, the cells done (created on first use)
   bool profiling = false;
   float kernel_ms[8] = {0};
   uint32_t kernel_launches[8] = {0};

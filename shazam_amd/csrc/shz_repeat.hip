@@ -1,0 +1,723 @@
+// Repeated content inside a recording, without a table: the self-join of a recording's hashes as a lag
+// histogram.  Two hashes of one recording with the same key at times t_i < t_j vote for the lag t_j - t_i; a stretch of audio
+// that airs twice piles its votes on one lag over a contiguous stretch of t_i.  The chain is integer from end to end:
+//
+//   compose   rec << 52 | key32 << 20 | t1 of every hash (the recording by binary search in the CSR)
+//   unique    shz_sort_u64 on the significant bits, head flags, scan, compaction             -> rec_hashes
+//   runs      one key of one recording: head flags on key >> 20, scan, first element of every run
+//   count     partners of element i: two binary searches for t_i + min_lag, t_i + max_lag in (i, run end); runs longer than
+//             max_run count 0 and feed the skip counters; shz_scan_u64                         -> rec_pairs
+//   expand    by OUTPUT tile: a workgroup owns consecutive pair positions and finds their owner elements in the scanned
+//             counts, so the stores are coalesced whatever the run lengths: rec_in_slice << 40 | lag << 20 | t_i
+//   cells     shz_sort_u64 on the bits from cell_shift up (the low bits of t ride along), head flags, scan; pairs = run length,
+//             first / last = a wave-segmented min / max and one atomicMin / atomicMax per (wave, cell); the cells with
+//             min_cell_pairs pairs compacted and copied out
+//
+// expand and cells run per slice of whole recordings whose two pair buffers fit 1/8 of the workspace limit.  Workspace: the
+// slots SHZ_WS_RP_*, SHZ_WS_SORT_* and SHZ_WS_SCAN_TMP -- none of the extraction's, so shz_repeats_batch reads the hashes
+// where shz_extract_owned left them.  shz_repeats_fold (host) joins the returned cells into repeats.
+#include <algorithm>
+#include <numeric>
+
+#include "shz_internal.h"
+
+#define RP_THREADS 256
+#define RP_SMALL 64u            // threads of a block and pairs of an expand tile under SHZ_DEBUG_REPEAT_SMALL_SLICES
+#define RP_TILE 2048u           // pairs of an expand tile
+#define RP_MAX_RECS 4096u       // recordings of a call: 12 bits above key32 << 20 | t1, and above lag << 20 | t
+#define RP_T_BITS 20
+#define RP_T_MASK 0xFFFFFu
+
+struct rp_params {
+  uint32_t min_lag, max_lag, max_run, cell_shift, min_cell_pairs;
+};
+struct rp_out {
+  uint64_t* cell_off;
+  uint32_t *cell_lag, *cell_block, *cell_pairs, *cell_first, *cell_last, *rec_hashes, *rec_skipped_keys;
+  uint64_t *rec_pairs, *rec_skipped_rows, cap_cells, *count;
+};
+
+static inline unsigned rp_grid(uint64_t n, uint32_t bs) { return (unsigned)((n + bs - 1) / bs); }
+static inline int rp_bits(uint32_t v) {   // bits that hold the values 0 .. v
+  int b = 0;
+  while (v >> b) ++b;
+  return b;
+}
+
+// ---- kernels ------------------------------------------------------------------------------------------------------------
+// rec_off[n_recs + 1]: first hash of every recording; entry i belongs to the last r with rec_off[r] <= i
+__global__ __launch_bounds__(RP_THREADS) void rp_compose_kernel(const uint32_t* __restrict__ key32, const uint32_t* __restrict__ t1,
+                                                                const uint64_t* __restrict__ rec_off, uint32_t n_recs, uint64_t n,
+                                                                uint64_t* __restrict__ out) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  uint32_t lo = 0, hi = n_recs;
+  while (hi - lo > 1) {
+    const uint32_t mid = lo + ((hi - lo) >> 1);
+    if (rec_off[mid] <= i) lo = mid; else hi = mid;
+  }
+  out[i] = ((uint64_t)lo << 52) | ((uint64_t)key32[i] << RP_T_BITS) | (t1[i] & RP_T_MASK);
+}
+
+// flag[i] = keys[i] >> shift differs from its left neighbour's (element 0: set)
+__global__ __launch_bounds__(RP_THREADS) void rp_head_kernel(const uint64_t* __restrict__ keys, uint64_t n, int shift,
+                                                             uint32_t* __restrict__ flag) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  flag[i] = (i == 0 || (keys[i] >> shift) != (keys[i - 1] >> shift)) ? 1u : 0u;
+}
+
+__global__ __launch_bounds__(RP_THREADS) void rp_compact_kernel(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ flag,
+                                                                const uint32_t* __restrict__ pos, uint64_t n,
+                                                                uint64_t* __restrict__ out) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  if (flag[i]) out[pos[i]] = keys[i];
+}
+
+// rec_start[r] = first unique element of recording r, r = 0 .. n_recs (the last: n)
+__global__ __launch_bounds__(RP_THREADS) void rp_rec_start_kernel(const uint64_t* __restrict__ U, uint32_t n, uint32_t n_recs,
+                                                                  uint32_t* __restrict__ rec_start) {
+  const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r > n_recs) return;
+  uint32_t lo = 0, hi = n;   // first element with U >> 52 >= r
+  if (r == n_recs) lo = n;
+  while (lo < hi) {
+    const uint32_t mid = lo + ((hi - lo) >> 1);
+    if ((uint32_t)(U[mid] >> 52) < r) lo = mid + 1; else hi = mid;
+  }
+  rec_start[r] = lo;
+}
+
+// run_start[id] at the heads; the entry behind the last run (tot[1] runs) = n
+__global__ __launch_bounds__(RP_THREADS) void rp_run_start_kernel(const uint32_t* __restrict__ head, const uint32_t* __restrict__ pos,
+                                                                  uint32_t n, const uint64_t* __restrict__ n_runs,
+                                                                  uint32_t* __restrict__ run_start) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  if (head[i]) run_start[pos[i]] = i;
+  if (i == 0) run_start[*n_runs] = n;
+}
+
+// partners of element i in its run: the elements j in (i, run end) with min_lag <= t_j - t_i <= max_lag -- the times of a run
+// ascend strictly -- as [lo[i], lo[i] + cnt[i]).  Runs longer than max_run: 0, and their heads count the skipped key and rows
+__global__ __launch_bounds__(RP_THREADS) void rp_count_kernel(const uint64_t* __restrict__ U, const uint32_t* __restrict__ head,
+                                                              const uint32_t* __restrict__ pos, const uint32_t* __restrict__ run_start,
+                                                              uint32_t n, rp_params P, uint64_t* __restrict__ cnt,
+                                                              uint32_t* __restrict__ lo_out, uint32_t* __restrict__ skip_keys,
+                                                              unsigned long long* __restrict__ skip_rows) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t h = head[i], id = pos[i] + h - 1;
+  const uint32_t b = run_start[id], e = run_start[id + 1];
+  const uint64_t key = U[i];
+  if (e - b > P.max_run) {
+    cnt[i] = 0;
+    lo_out[i] = 0;
+    if (h) {
+      const uint32_t r = (uint32_t)(key >> 52);
+      atomicAdd(&skip_keys[r], 1u);
+      atomicAdd(&skip_rows[r], (unsigned long long)(e - b));
+    }
+    return;
+  }
+  const uint32_t t = (uint32_t)key & RP_T_MASK, t_lo = t + P.min_lag, t_hi = t + P.max_lag;   // < 2^21
+  uint32_t l = i + 1, r = e;   // first j with t_j >= t_lo
+  while (l < r) {
+    const uint32_t mid = l + ((r - l) >> 1);
+    if (((uint32_t)U[mid] & RP_T_MASK) < t_lo) l = mid + 1; else r = mid;
+  }
+  const uint32_t first = l;
+  r = e;                       // first j with t_j > t_hi
+  while (l < r) {
+    const uint32_t mid = l + ((r - l) >> 1);
+    if (((uint32_t)U[mid] & RP_T_MASK) <= t_hi) l = mid + 1; else r = mid;
+  }
+  cnt[i] = l - first;
+  lo_out[i] = first;
+}
+
+// rec_po[r] = pairs in front of recording r, r = 0 .. n_recs
+__global__ __launch_bounds__(RP_THREADS) void rp_rec_pairs_kernel(const uint64_t* __restrict__ poff, const uint32_t* __restrict__ rec_start,
+                                                                  uint32_t n_recs, uint64_t* __restrict__ rec_po) {
+  const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r <= n_recs) rec_po[r] = poff[rec_start[r]];
+}
+
+// The pairs [P0, P0 + np) of the elements [e0, e1) go to out[0 .. np): block b owns the positions [b tile, (b + 1) tile).
+// Pair g belongs to the last element x with poff[x] <= g (elements without partners share their successor's poff and are
+// never that one); it is x's partner number g - poff[x].  The block finds the owners of its first and last pair, every lane
+// searches between them
+__global__ __launch_bounds__(RP_THREADS) void rp_expand_kernel(const uint64_t* __restrict__ U, const uint64_t* __restrict__ poff,
+                                                               const uint32_t* __restrict__ lo, uint32_t e0, uint32_t e1, uint64_t P0,
+                                                               uint64_t np, uint32_t tile, uint32_t r0, uint64_t* __restrict__ out) {
+  const uint64_t base = (uint64_t)blockIdx.x * tile;
+  if (base >= np) return;
+  const uint64_t end = min(base + tile, np);
+  uint32_t xA, xB;
+  {
+    const uint64_t gA = P0 + base, gB = P0 + end - 1;
+    uint32_t l = e0, h = e1;
+    while (h - l > 1) {
+      const uint32_t mid = l + ((h - l) >> 1);
+      if (poff[mid] <= gA) l = mid; else h = mid;
+    }
+    xA = l;
+    h = e1;
+    while (h - l > 1) {
+      const uint32_t mid = l + ((h - l) >> 1);
+      if (poff[mid] <= gB) l = mid; else h = mid;
+    }
+    xB = l;
+  }
+  for (uint64_t p = base + threadIdx.x; p < end; p += blockDim.x) {
+    const uint64_t g = P0 + p;
+    uint32_t l = xA, h = xB + 1;
+    while (h - l > 1) {
+      const uint32_t mid = l + ((h - l) >> 1);
+      if (poff[mid] <= g) l = mid; else h = mid;
+    }
+    const uint64_t key = U[l];
+    const uint32_t j = lo[l] + (uint32_t)(g - poff[l]);
+    const uint32_t ti = (uint32_t)key & RP_T_MASK, tj = (uint32_t)U[j] & RP_T_MASK;
+    out[p] = ((uint64_t)((uint32_t)(key >> 52) - r0) << 40) | ((uint64_t)(tj - ti) << RP_T_BITS) | ti;
+  }
+}
+
+__global__ __launch_bounds__(RP_THREADS) void rp_cell_init_kernel(uint32_t nc, uint32_t np, uint32_t* __restrict__ head_pos,
+                                                                  uint32_t* __restrict__ first, uint32_t* __restrict__ last) {
+  const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c < nc) {
+    first[c] = 0xFFFFFFFFu;
+    last[c] = 0u;
+  }
+  if (c == nc) head_pos[nc] = np;
+}
+
+// Pair i of the sorted slice lies in cell pos[i] + head[i] - 1; the heads write head_pos.  first / last: the lanes of a wave
+// that share a cell are neighbours, so a segmented scan over the wave leaves the cell's min / max of the wave in its last lane
+// there, which hands them to the cell record -- integers, the same whatever the order
+__global__ __launch_bounds__(RP_THREADS) void rp_cell_reduce_kernel(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ head,
+                                                                    const uint32_t* __restrict__ pos, uint32_t np,
+                                                                    uint32_t* __restrict__ head_pos, uint32_t* __restrict__ first,
+                                                                    uint32_t* __restrict__ last) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  const int lane = threadIdx.x & 63;
+  const bool live = i < np;
+  uint32_t id = 0xFFFFFFFFu, mn = 0xFFFFFFFFu, mx = 0u;
+  if (live) {
+    const uint32_t h = head[i];
+    id = pos[i] + h - 1;
+    mn = mx = (uint32_t)keys[i] & RP_T_MASK;
+    if (h) head_pos[id] = i;
+  }
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const uint32_t oid = __shfl_up(id, d, 64), omn = __shfl_up(mn, d, 64), omx = __shfl_up(mx, d, 64);
+    if (lane >= d && oid == id) {
+      mn = min(mn, omn);
+      mx = max(mx, omx);
+    }
+  }
+  const uint32_t nid = __shfl_down(id, 1, 64);
+  if (live && (lane == 63 || nid != id)) {
+    atomicMin(&first[id], mn);
+    atomicMax(&last[id], mx);
+  }
+}
+
+__global__ __launch_bounds__(RP_THREADS) void rp_keep_kernel(const uint32_t* __restrict__ head_pos, uint32_t nc, uint32_t min_pairs,
+                                                             uint32_t* __restrict__ keep) {
+  const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c < nc) keep[c] = (head_pos[c + 1] - head_pos[c]) >= min_pairs ? 1u : 0u;
+}
+
+// the kept cells in their order: out = rec | lag | block | pairs | first | last, nk entries each
+__global__ __launch_bounds__(RP_THREADS) void rp_cell_out_kernel(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ head_pos,
+                                                                 const uint32_t* __restrict__ first, const uint32_t* __restrict__ last,
+                                                                 const uint32_t* __restrict__ keep, const uint32_t* __restrict__ place,
+                                                                 uint32_t nc, uint32_t nk, uint32_t r0, uint32_t cell_shift,
+                                                                 uint32_t* __restrict__ out) {
+  const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= nc || !keep[c]) return;
+  const uint32_t o = place[c], hp = head_pos[c];
+  if (o >= nk) return;
+  const uint64_t key = keys[hp];
+  out[o] = (uint32_t)(key >> 40) + r0;
+  out[(uint64_t)nk + o] = (uint32_t)(key >> RP_T_BITS) & RP_T_MASK;
+  out[2ull * nk + o] = ((uint32_t)key & RP_T_MASK) >> cell_shift;
+  out[3ull * nk + o] = head_pos[c + 1] - hp;
+  out[4ull * nk + o] = first[c];
+  out[5ull * nk + o] = last[c];
+}
+
+// ---- what both entry points refuse before anything is launched ------------------------------------------------------------
+static int32_t rp_check(shz_ctx* ctx, const char* who, const rp_params& P, const rp_out& O) {
+  if (!O.count || !O.cell_off || !O.rec_hashes || !O.rec_skipped_keys || !O.rec_pairs || !O.rec_skipped_rows)
+    SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: count, cell_off or a rec_* array is NULL", who);
+  if (O.cap_cells && (!O.cell_lag || !O.cell_block || !O.cell_pairs || !O.cell_first || !O.cell_last))
+    SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: NULL cell array with room for %llu cells", who, (unsigned long long)O.cap_cells);
+  if (P.max_lag < P.min_lag) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: max_lag %u is below min_lag %u", who, P.max_lag, P.min_lag);
+  if (P.max_lag >= (1u << RP_T_BITS)) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: max_lag must be below 2^20, got %u", who, P.max_lag);
+  if (P.max_run < 2 || P.max_run > 1024) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: max_run must be in [2, 1024], got %u", who, P.max_run);
+  if (P.cell_shift > 19) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: cell_shift must be at most 19, got %u", who, P.cell_shift);
+  if (P.min_cell_pairs == 0) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: min_cell_pairs must be at least 1", who);
+  return SHZ_OK;
+}
+// the recordings' clips (no recording: no clips either, and the caller is done -- what it writes then: rp_empty)
+static int32_t rp_check_recs(shz_ctx* ctx, const char* who, uint32_t n_clips, const uint32_t* rec_clip0, uint32_t n_recs) {
+  if (n_recs == 0) {
+    if (n_clips) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: %u clips belong to no recording", who, n_clips);
+    return SHZ_OK;
+  }
+  if (n_recs > RP_MAX_RECS) SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "%s: %u recordings in one call, at most %u", who, n_recs, RP_MAX_RECS);
+  return shz_check_clip0(ctx, "rec_clip0", "recording", rec_clip0, n_recs, n_clips);
+}
+static void rp_empty(const rp_out& O, uint32_t n_recs) {
+  *O.count = 0;
+  for (uint32_t r = 0; r <= n_recs; ++r) O.cell_off[r] = 0;
+  for (uint32_t r = 0; r < n_recs; ++r) {
+    O.rec_hashes[r] = O.rec_skipped_keys[r] = 0;
+    O.rec_pairs[r] = O.rec_skipped_rows[r] = 0;
+  }
+}
+
+// ---- the core on device columns -------------------------------------------------------------------------------------------
+// d_key32 / d_t1: device columns of hash_off[n_clips] < 2^32 entries with t1 < 2^20, hash_off (host) their CSR over the clips;
+// everything else is checked (rp_check, rp_check_recs; n_recs >= 1).  The outputs are written when the call ends with SHZ_OK
+// or SHZ_E_CAPACITY; the stream is idle then.  ms_pairs / ms_cells (may be NULL) get the stages' hipEvent times
+static int32_t rp_core(shz_ctx* ctx, const char* who, const uint32_t* d_key32, const uint32_t* d_t1, const uint64_t* hash_off,
+                       const uint32_t* rec_clip0, uint32_t n_recs, const rp_params& P, const rp_out& O, float* ms_pairs,
+                       float* ms_cells) {
+  const uint64_t N = hash_off[rec_clip0[n_recs]];
+  if (N == 0) {
+    rp_empty(O, n_recs);
+    return SHZ_OK;
+  }
+  const bool small = (ctx->debug & SHZ_DEBUG_REPEAT_SMALL_SLICES) != 0, timed = ms_pairs || ms_cells;
+  const uint32_t bs = small ? RP_SMALL : RP_THREADS, tile = small ? RP_SMALL : RP_TILE;
+  hipStream_t st = ctx->stream;
+  float pairs_ms = 0.f, cells_ms = 0.f;
+  if (timed) {
+    for (hipEvent_t& e : ctx->rp_ev)
+      if (!e) SHZ_HIP(ctx, hipEventCreate(&e));
+    SHZ_HIP(ctx, hipEventRecord(ctx->rp_ev[0], st));
+  }
+  // the recordings' block: tot[4] (unique elements, runs, a slice's cells, its kept cells) | rec_off | rec_po | skip_rows (u64)
+  // | rec_start | skip_keys (u32).  rec_off goes up, the rest comes back in one copy
+  const uint64_t nr1 = (uint64_t)n_recs + 1;
+  const uint64_t o_off = 4, o_po = o_off + nr1, o_rows = o_po + nr1, n64 = o_rows + n_recs;
+  const uint64_t rec_bytes = n64 * 8 + (nr1 + n_recs) * 4;
+  std::vector<uint64_t> hrec((size_t)((rec_bytes + 7) / 8), 0);
+  for (uint32_t r = 0; r <= n_recs; ++r) hrec[o_off + r] = hash_off[rec_clip0[r]];
+  void* d_rec;
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_RP_REC, hrec.size() * 8, &d_rec));
+  uint64_t* d64 = (uint64_t*)d_rec;
+  uint64_t *d_tot = d64, *d_rec_off = d64 + o_off, *d_rec_po = d64 + o_po, *d_skip_rows = d64 + o_rows;
+  uint32_t *d_rec_start = (uint32_t*)(d64 + n64), *d_skip_keys = d_rec_start + nr1;
+  SHZ_HIP(ctx, shz_memcpy(ctx, d_rec, hrec.data(), hrec.size() * 8, hipMemcpyHostToDevice));
+  // 1) compose, 2) sort + unique
+  void *ka, *kb, *d_flag, *d_scan, *d_u;
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SORT_A, N * 8, &ka));
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SORT_B, N * 8, &kb));
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_RP_FLAG, N * 4, &d_flag));
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_RP_SCAN, N * 4, &d_scan));
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_RP_U, N * 8, &d_u));
+  hipLaunchKernelGGL(rp_compose_kernel, dim3(rp_grid(N, bs)), dim3(bs), 0, st, d_key32, d_t1, (const uint64_t*)d_rec_off, n_recs, N,
+                     (uint64_t*)ka);
+  SHZ_HIP(ctx, hipGetLastError());
+  int sel = 0;
+  SHZ_TRY(shz_sort_u64(ctx, (uint64_t*)ka, (uint64_t*)kb, nullptr, nullptr, 0, N, 0, 52 + rp_bits(n_recs - 1), &sel));
+  const uint64_t* sorted = (const uint64_t*)(sel ? kb : ka);
+  hipLaunchKernelGGL(rp_head_kernel, dim3(rp_grid(N, bs)), dim3(bs), 0, st, sorted, N, 0, (uint32_t*)d_flag);
+  SHZ_HIP(ctx, hipGetLastError());
+  SHZ_TRY(shz_scan_u32(ctx, (const uint32_t*)d_flag, (uint32_t*)d_scan, N, d_tot));
+  hipLaunchKernelGGL(rp_compact_kernel, dim3(rp_grid(N, bs)), dim3(bs), 0, st, sorted, (const uint32_t*)d_flag, (const uint32_t*)d_scan,
+                     N, (uint64_t*)d_u);
+  SHZ_HIP(ctx, hipGetLastError());
+  uint64_t nu64 = 0;
+  SHZ_HIP(ctx, shz_memcpy(ctx, &nu64, d_tot, 8, hipMemcpyDeviceToHost));
+  SHZ_HIP(ctx, hipStreamSynchronize(st));
+  if (nu64 == 0 || nu64 > N) SHZ_FAIL(ctx, SHZ_E_STATE, "%s: %llu unique hashes of %llu", who, (unsigned long long)nu64, (unsigned long long)N);
+  const uint32_t nu = (uint32_t)nu64;
+  const uint64_t* U = (const uint64_t*)d_u;
+  // 3) runs, 4) count, scan, the recordings' numbers
+  void *d_run, *d_lo, *d_cnt, *d_poff;
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_RP_RUN, ((uint64_t)nu + 1) * 4, &d_run));
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_RP_LO, (uint64_t)nu * 4, &d_lo));
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_RP_CNT, (uint64_t)nu * 8, &d_cnt));
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_RP_POFF, ((uint64_t)nu + 1) * 8, &d_poff));
+  hipLaunchKernelGGL(rp_rec_start_kernel, dim3(rp_grid(nr1, bs)), dim3(bs), 0, st, U, nu, n_recs, d_rec_start);
+  hipLaunchKernelGGL(rp_head_kernel, dim3(rp_grid(nu, bs)), dim3(bs), 0, st, U, (uint64_t)nu, RP_T_BITS, (uint32_t*)d_flag);
+  SHZ_HIP(ctx, hipGetLastError());
+  SHZ_TRY(shz_scan_u32(ctx, (const uint32_t*)d_flag, (uint32_t*)d_scan, nu, d_tot + 1));
+  hipLaunchKernelGGL(rp_run_start_kernel, dim3(rp_grid(nu, bs)), dim3(bs), 0, st, (const uint32_t*)d_flag, (const uint32_t*)d_scan, nu,
+                     (const uint64_t*)(d_tot + 1), (uint32_t*)d_run);
+  hipLaunchKernelGGL(rp_count_kernel, dim3(rp_grid(nu, bs)), dim3(bs), 0, st, U, (const uint32_t*)d_flag, (const uint32_t*)d_scan,
+                     (const uint32_t*)d_run, nu, P, (uint64_t*)d_cnt, (uint32_t*)d_lo, d_skip_keys, (unsigned long long*)d_skip_rows);
+  SHZ_HIP(ctx, hipGetLastError());
+  uint64_t* poff = (uint64_t*)d_poff;
+  SHZ_TRY(shz_scan_u64(ctx, (const uint64_t*)d_cnt, poff, nu, poff + nu));
+  hipLaunchKernelGGL(rp_rec_pairs_kernel, dim3(rp_grid(nr1, bs)), dim3(bs), 0, st, (const uint64_t*)poff, (const uint32_t*)d_rec_start,
+                     n_recs, d_rec_po);
+  SHZ_HIP(ctx, hipGetLastError());
+  SHZ_HIP(ctx, shz_memcpy(ctx, hrec.data(), d_rec, hrec.size() * 8, hipMemcpyDeviceToHost));
+  if (timed) SHZ_HIP(ctx, hipEventRecord(ctx->rp_ev[1], st));
+  SHZ_HIP(ctx, hipStreamSynchronize(st));
+  if (timed) {
+    float a = 0.f;
+    SHZ_HIP(ctx, hipEventElapsedTime(&a, ctx->rp_ev[0], ctx->rp_ev[1]));
+    pairs_ms += a;
+  }
+  const uint64_t *rec_po = hrec.data() + o_po, *skip_rows = hrec.data() + o_rows;
+  const uint32_t *rec_start = (const uint32_t*)(hrec.data() + n64), *skip_keys = rec_start + nr1;
+  if (rec_start[0] != 0 || rec_start[n_recs] != nu || rec_po[0] != 0)
+    SHZ_FAIL(ctx, SHZ_E_STATE, "%s: the recordings' borders do not span the %u unique hashes", who, nu);
+  for (uint32_t r = 0; r < n_recs; ++r)
+    if (rec_start[r + 1] < rec_start[r] || rec_po[r + 1] < rec_po[r])
+      SHZ_FAIL(ctx, SHZ_E_STATE, "%s: the borders of recording %u decrease", who, r);
+  // 5) the slices: consecutive whole recordings whose two pair buffers fit 1/8 of the workspace limit
+  const uint64_t max_pairs = std::min<uint64_t>(std::max<uint64_t>(ctx->ws_limit / 8 / 16, 1), 1ull << 31);
+  for (uint32_t r = 0; r < n_recs; ++r)
+    if (rec_po[r + 1] - rec_po[r] > max_pairs)
+      SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED,
+               "%s: recording %u has %llu pairs, a slice holds %llu (workspace limit): raise min_lag (%u) or lower max_run (%u)", who, r,
+               (unsigned long long)(rec_po[r + 1] - rec_po[r]), (unsigned long long)max_pairs, P.min_lag, P.max_run);
+  std::vector<uint32_t> slices{0};
+  uint64_t np_max = 0;
+  for (uint32_t r0 = 0; r0 < n_recs;) {
+    uint32_t r1 = r0 + 1;
+    while (!small && r1 < n_recs && rec_po[r1 + 1] - rec_po[r0] <= max_pairs) ++r1;
+    np_max = std::max(np_max, rec_po[r1] - rec_po[r0]);
+    slices.push_back(r1);
+    r0 = r1;
+  }
+  // 6) slice by slice: expand, sort, cells
+  std::vector<uint32_t> c_lag, c_block, c_pairs, c_first, c_last, blockbuf;
+  std::vector<uint64_t> cell_off((size_t)nr1, 0);
+  uint64_t n_cells_all = 0;
+  if (np_max) {
+    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SORT_A, np_max * 8, &ka));
+    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SORT_B, np_max * 8, &kb));
+    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_RP_FLAG, np_max * 4, &d_flag));
+    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_RP_SCAN, np_max * 4, &d_scan));
+  }
+  for (size_t s = 0; s + 1 < slices.size(); ++s) {
+    const uint32_t r0 = slices[s], r1 = slices[s + 1], e0 = rec_start[r0], e1 = rec_start[r1];
+    const uint64_t P0 = rec_po[r0], np64 = rec_po[r1] - P0;
+    if (np64 == 0) continue;
+    const uint32_t np = (uint32_t)np64;   // (<= 2^31)
+    if (timed) SHZ_HIP(ctx, hipEventRecord(ctx->rp_ev[0], st));
+    hipLaunchKernelGGL(rp_expand_kernel, dim3(rp_grid(np, tile)), dim3(bs), 0, st, U, (const uint64_t*)poff, (const uint32_t*)d_lo, e0, e1,
+                       P0, np64, tile, r0, (uint64_t*)ka);
+    SHZ_HIP(ctx, hipGetLastError());
+    if (timed) SHZ_HIP(ctx, hipEventRecord(ctx->rp_ev[1], st));
+    SHZ_TRY(shz_sort_u64(ctx, (uint64_t*)ka, (uint64_t*)kb, nullptr, nullptr, 0, np, (int)P.cell_shift, 40 + rp_bits(r1 - r0 - 1), &sel));
+    const uint64_t* pk = (const uint64_t*)(sel ? kb : ka);
+    hipLaunchKernelGGL(rp_head_kernel, dim3(rp_grid(np, bs)), dim3(bs), 0, st, pk, (uint64_t)np, (int)P.cell_shift, (uint32_t*)d_flag);
+    SHZ_HIP(ctx, hipGetLastError());
+    SHZ_TRY(shz_scan_u32(ctx, (const uint32_t*)d_flag, (uint32_t*)d_scan, np, d_tot + 2));
+    uint64_t nc64 = 0;
+    SHZ_HIP(ctx, shz_memcpy(ctx, &nc64, d_tot + 2, 8, hipMemcpyDeviceToHost));
+    SHZ_HIP(ctx, hipStreamSynchronize(st));
+    if (nc64 == 0 || nc64 > np) SHZ_FAIL(ctx, SHZ_E_STATE, "%s: %llu cells of %u pairs", who, (unsigned long long)nc64, np);
+    const uint32_t nc = (uint32_t)nc64;
+    void* d_cell;
+    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_RP_CELL, (5ull * nc + 2) * 4, &d_cell));
+    uint32_t *head_pos = (uint32_t*)d_cell, *cfirst = head_pos + nc + 1, *clast = cfirst + nc, *keep = clast + nc, *place = keep + nc;
+    hipLaunchKernelGGL(rp_cell_init_kernel, dim3(rp_grid((uint64_t)nc + 1, bs)), dim3(bs), 0, st, nc, np, head_pos, cfirst, clast);
+    hipLaunchKernelGGL(rp_cell_reduce_kernel, dim3(rp_grid(np, bs)), dim3(bs), 0, st, pk, (const uint32_t*)d_flag, (const uint32_t*)d_scan,
+                       np, head_pos, cfirst, clast);
+    hipLaunchKernelGGL(rp_keep_kernel, dim3(rp_grid(nc, bs)), dim3(bs), 0, st, (const uint32_t*)head_pos, nc, P.min_cell_pairs, keep);
+    SHZ_HIP(ctx, hipGetLastError());
+    SHZ_TRY(shz_scan_u32(ctx, (const uint32_t*)keep, place, nc, d_tot + 3));
+    uint64_t nk64 = 0;
+    SHZ_HIP(ctx, shz_memcpy(ctx, &nk64, d_tot + 3, 8, hipMemcpyDeviceToHost));
+    SHZ_HIP(ctx, hipStreamSynchronize(st));
+    if (nk64 > nc) SHZ_FAIL(ctx, SHZ_E_STATE, "%s: %llu kept cells of %u", who, (unsigned long long)nk64, nc);
+    const uint32_t nk = (uint32_t)nk64;
+    if (nk) {
+      void* d_out;
+      SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_RP_OUT, 6ull * nk * 4, &d_out));
+      hipLaunchKernelGGL(rp_cell_out_kernel, dim3(rp_grid(nc, bs)), dim3(bs), 0, st, pk, (const uint32_t*)head_pos, (const uint32_t*)cfirst,
+                         (const uint32_t*)clast, (const uint32_t*)keep, (const uint32_t*)place, nc, nk, r0, P.cell_shift, (uint32_t*)d_out);
+      SHZ_HIP(ctx, hipGetLastError());
+      blockbuf.resize(6 * (size_t)nk);
+      SHZ_HIP(ctx, shz_memcpy(ctx, blockbuf.data(), d_out, 6ull * nk * 4, hipMemcpyDeviceToHost));
+    }
+    if (timed) SHZ_HIP(ctx, hipEventRecord(ctx->rp_ev[2], st));
+    SHZ_HIP(ctx, hipStreamSynchronize(st));
+    if (timed) {
+      float a = 0.f, b = 0.f;
+      SHZ_HIP(ctx, hipEventElapsedTime(&a, ctx->rp_ev[0], ctx->rp_ev[1]));
+      SHZ_HIP(ctx, hipEventElapsedTime(&b, ctx->rp_ev[1], ctx->rp_ev[2]));
+      pairs_ms += a;
+      cells_ms += b;
+    }
+    for (uint32_t k = 0; k < nk; ++k) {
+      const uint32_t r = blockbuf[k];
+      if (r < r0 || r >= r1) SHZ_FAIL(ctx, SHZ_E_STATE, "%s: a cell of recording %u in the slice [%u, %u)", who, r, r0, r1);
+      ++cell_off[r + 1];
+      if (n_cells_all + k < O.cap_cells) {   // (what has no room is counted only)
+        c_lag.push_back(blockbuf[(size_t)nk + k]);
+        c_block.push_back(blockbuf[2 * (size_t)nk + k]);
+        c_pairs.push_back(blockbuf[3 * (size_t)nk + k]);
+        c_first.push_back(blockbuf[4 * (size_t)nk + k]);
+        c_last.push_back(blockbuf[5 * (size_t)nk + k]);
+      }
+    }
+    n_cells_all += nk;
+  }
+  // 7) the outputs
+  for (uint32_t r = 0; r < n_recs; ++r) {
+    cell_off[r + 1] += cell_off[r];
+    O.rec_hashes[r] = rec_start[r + 1] - rec_start[r];
+    O.rec_pairs[r] = rec_po[r + 1] - rec_po[r];
+    O.rec_skipped_keys[r] = skip_keys[r];
+    O.rec_skipped_rows[r] = skip_rows[r];
+  }
+  memcpy(O.cell_off, cell_off.data(), nr1 * 8);
+  *O.count = n_cells_all;
+  const size_t nw = c_lag.size();
+  if (nw) {
+    memcpy(O.cell_lag, c_lag.data(), nw * 4);
+    memcpy(O.cell_block, c_block.data(), nw * 4);
+    memcpy(O.cell_pairs, c_pairs.data(), nw * 4);
+    memcpy(O.cell_first, c_first.data(), nw * 4);
+    memcpy(O.cell_last, c_last.data(), nw * 4);
+  }
+  if (ms_pairs) *ms_pairs = pairs_ms;
+  if (ms_cells) *ms_cells = cells_ms;
+  if (n_cells_all > O.cap_cells)
+    SHZ_FAIL(ctx, SHZ_E_CAPACITY, "%s: %llu cells, room for %llu", who, (unsigned long long)n_cells_all, (unsigned long long)O.cap_cells);
+  return SHZ_OK;
+}
+
+// ---- the entry points -------------------------------------------------------------------------------------------------------
+extern "C" int32_t shz_repeats_hashes(shz_ctx* ctx, const uint32_t* key32, const uint32_t* t1, const uint64_t* hash_off, uint32_t n_clips,
+                                      const uint32_t* rec_clip0, uint32_t n_recs, uint32_t min_lag, uint32_t max_lag, uint32_t max_run,
+                                      uint32_t cell_shift, uint32_t min_cell_pairs, uint32_t flags, uint64_t* cell_off, uint32_t* cell_lag,
+                                      uint32_t* cell_block, uint32_t* cell_pairs, uint32_t* cell_first, uint32_t* cell_last,
+                                      uint32_t* rec_hashes, uint32_t* rec_skipped_keys, uint64_t* rec_pairs, uint64_t* rec_skipped_rows,
+                                      uint64_t cap_cells, uint64_t* count) {
+  const char* who = "shz_repeats_hashes";
+  if (!ctx) return SHZ_E_INVALID;
+  const rp_params P{min_lag, max_lag, max_run, cell_shift, min_cell_pairs};
+  const rp_out O{cell_off, cell_lag, cell_block, cell_pairs, cell_first, cell_last, rec_hashes, rec_skipped_keys, rec_pairs,
+                 rec_skipped_rows, cap_cells, count};
+  // everything that can be refused is refused before the first launch
+  if (flags) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: flags must be 0", who);
+  SHZ_TRY(rp_check(ctx, who, P, O));
+  SHZ_TRY(rp_check_recs(ctx, who, n_clips, rec_clip0, n_recs));
+  if (!hash_off) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: hash_off is NULL", who);
+  if (hash_off[0] != 0) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: hash_off must start at 0 (it starts at %llu)", who, (unsigned long long)hash_off[0]);
+  for (uint32_t c = 0; c < n_clips; ++c)
+    if (hash_off[c + 1] < hash_off[c]) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: hash_off decreases at clip %u", who, c);
+  const uint64_t N = hash_off[n_clips];
+  if (N && (!key32 || !t1)) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: NULL column", who);
+  if (N >= (1ull << 32)) SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "%s: %llu hashes", who, (unsigned long long)N);
+  for (uint64_t i = 0; i < N; ++i)
+    if (t1[i] >> RP_T_BITS) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: t1[%llu] = %u, times must be below 2^20", who, (unsigned long long)i, t1[i]);
+  if (n_recs == 0 || N == 0) {
+    rp_empty(O, n_recs);
+    return SHZ_OK;
+  }
+  SHZ_HIP(ctx, hipSetDevice(ctx->device));
+  void *d_key = nullptr, *d_t1 = nullptr;
+  if (hipMalloc(&d_key, N * 4) != hipSuccess || hipMalloc(&d_t1, N * 4) != hipSuccess) {
+    (void)hipGetLastError();
+    if (d_key) (void)hipFree(d_key);
+    SHZ_FAIL(ctx, SHZ_E_NOMEM, "%s: hipMalloc(2 x %llu) failed", who, (unsigned long long)(N * 4));
+  }
+  int32_t rc = SHZ_OK;
+  if (shz_memcpy(ctx, d_key, key32, N * 4, hipMemcpyHostToDevice) != hipSuccess ||
+      shz_memcpy(ctx, d_t1, t1, N * 4, hipMemcpyHostToDevice) != hipSuccess) {
+    ctx->err = "shz_repeats_hashes: copy of the columns failed";
+    rc = SHZ_E_HIP;
+  }
+  if (rc == SHZ_OK)
+    rc = rp_core(ctx, who, (const uint32_t*)d_key, (const uint32_t*)d_t1, hash_off, rec_clip0, n_recs, P, O, nullptr, nullptr);
+  (void)hipStreamSynchronize(ctx->stream);   // (a refused call may have queued work that reads the columns)
+  (void)hipFree(d_key);
+  (void)hipFree(d_t1);
+  return rc;
+}
+
+extern "C" int32_t shz_repeats_batch(shz_ctx* ctx, const int16_t* pcm, const uint64_t* clip_off, uint32_t n_clips,
+                                     const uint32_t* rec_clip0, uint32_t n_recs, uint32_t fs, double amp_min, uint32_t fan_value,
+                                     uint32_t min_lag, uint32_t max_lag, uint32_t max_run, uint32_t cell_shift, uint32_t min_cell_pairs,
+                                     uint32_t flags, uint64_t* cell_off, uint32_t* cell_lag, uint32_t* cell_block, uint32_t* cell_pairs,
+                                     uint32_t* cell_first, uint32_t* cell_last, uint32_t* rec_hashes, uint32_t* rec_skipped_keys,
+                                     uint64_t* rec_pairs, uint64_t* rec_skipped_rows, uint64_t cap_cells, uint64_t* count,
+                                     float* ms_extract, float* ms_pairs, float* ms_cells) {
+  const char* who = "shz_repeats_batch";
+  if (!ctx) return SHZ_E_INVALID;
+  const rp_params P{min_lag, max_lag, max_run, cell_shift, min_cell_pairs};
+  const rp_out O{cell_off, cell_lag, cell_block, cell_pairs, cell_first, cell_last, rec_hashes, rec_skipped_keys, rec_pairs,
+                 rec_skipped_rows, cap_cells, count};
+  if (flags & ~SHZ_PCM_DEVICE) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: flags may hold SHZ_PCM_DEVICE", who);
+  SHZ_TRY(rp_check(ctx, who, P, O));
+  if (fan_value < 1 || fan_value > 64) SHZ_FAIL(ctx, SHZ_E_INVALID, "fan_value must be in [1,64]");
+  SHZ_TRY(rp_check_recs(ctx, who, n_clips, rec_clip0, n_recs));
+  if (n_recs) SHZ_TRY(shz_check_clip_off(ctx, clip_off, n_clips));
+  // (nothing is refused behind this line without a launch: the first write)
+  if (ms_extract) *ms_extract = 0.f;
+  if (ms_pairs) *ms_pairs = 0.f;
+  if (ms_cells) *ms_cells = 0.f;
+  if (n_recs == 0) {
+    rp_empty(O, 0);
+    return SHZ_OK;
+  }
+  SHZ_HIP(ctx, hipSetDevice(ctx->device));
+  const bool timed = ms_extract || ms_pairs || ms_cells;
+  if (timed) {
+    for (hipEvent_t& e : ctx->rp_ev)
+      if (!e) SHZ_HIP(ctx, hipEventCreate(&e));
+    SHZ_HIP(ctx, hipEventRecord(ctx->rp_ev[0], ctx->stream));
+  }
+  std::vector<uint64_t> hash_off((size_t)n_clips + 1, 0);
+  const uint32_t *d_key = nullptr, *d_t1 = nullptr;
+  SHZ_TRY(shz_extract_owned(ctx, who, pcm, clip_off, n_clips, fs, amp_min, fan_value, flags & SHZ_PCM_DEVICE, hash_off.data(), &d_key,
+                            &d_t1));
+  if (timed) {
+    SHZ_HIP(ctx, hipEventRecord(ctx->rp_ev[1], ctx->stream));
+    SHZ_HIP(ctx, hipEventSynchronize(ctx->rp_ev[1]));
+    if (ms_extract) SHZ_HIP(ctx, hipEventElapsedTime(ms_extract, ctx->rp_ev[0], ctx->rp_ev[1]));
+  }
+  if (hash_off[n_clips] >= (1ull << 32)) SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "%s: %llu hashes", who, (unsigned long long)hash_off[n_clips]);
+  float dummy_a = 0.f, dummy_b = 0.f;
+  return rp_core(ctx, who, d_key, d_t1, hash_off.data(), rec_clip0, n_recs, P, O, timed ? (ms_pairs ? ms_pairs : &dummy_a) : nullptr,
+                 timed ? (ms_cells ? ms_cells : &dummy_b) : nullptr);
+}
+
+// ---- the fold: cells -> repeats, on the host ----------------------------------------------------------------------------------
+// Union-find over cell indices, the smaller index the root.  A cell looks only at the cells in front of it: in every row of
+// lags [lag - lag_tol, lag] the blocks [block - max_gap - 1, block + max_gap + 1], found by binary search in the sorted list --
+// a row without such a cell costs one search, and every other step is a neighbour
+namespace {
+struct rp_find {
+  std::vector<uint64_t> up;
+  explicit rp_find(uint64_t n) : up((size_t)n) { std::iota(up.begin(), up.end(), 0ull); }
+  uint64_t root(uint64_t x) {
+    while (up[x] != x) {
+      up[x] = up[up[x]];
+      x = up[x];
+    }
+    return x;
+  }
+  void join(uint64_t a, uint64_t b) {
+    a = root(a);
+    b = root(b);
+    if (a < b) up[b] = a; else up[a] = b;
+  }
+};
+struct rp_comp {
+  uint64_t pairs = 0, cur_sum = 0, best_sum = 0, root = 0;
+  uint32_t first = 0xFFFFFFFFu, last = 0, lag_lo = 0, lag_hi = 0, cur_lag = 0, best_lag = 0, cells = 0;
+};
+}   // namespace
+
+extern "C" int32_t shz_repeats_fold(const uint64_t* cell_off, uint32_t n_recs, const uint32_t* cell_lag, const uint32_t* cell_block,
+                                    const uint32_t* cell_pairs, const uint32_t* cell_first, const uint32_t* cell_last, uint32_t lag_tol,
+                                    uint32_t max_gap, uint64_t min_pairs, uint32_t* rep_rec, uint32_t* rep_lag, uint32_t* rep_lag_lo,
+                                    uint32_t* rep_lag_hi, uint32_t* rep_first, uint32_t* rep_last, uint64_t* rep_pairs,
+                                    uint32_t* rep_cells, uint64_t cap, uint64_t* count) {
+  if (!count || !cell_off || cell_off[0] != 0) return SHZ_E_INVALID;
+  for (uint32_t r = 0; r < n_recs; ++r)
+    if (cell_off[r + 1] < cell_off[r]) return SHZ_E_INVALID;
+  const uint64_t n = cell_off[n_recs];
+  if (n && (!cell_lag || !cell_block || !cell_pairs || !cell_first || !cell_last)) return SHZ_E_INVALID;
+  if (cap && (!rep_rec || !rep_lag || !rep_lag_lo || !rep_lag_hi || !rep_first || !rep_last || !rep_pairs || !rep_cells))
+    return SHZ_E_INVALID;
+  auto before = [&](uint64_t i, uint64_t lag, uint64_t block) {   // cell i < (lag, block)
+    return cell_lag[i] < lag || (cell_lag[i] == lag && cell_block[i] < block);
+  };
+  for (uint32_t r = 0; r < n_recs; ++r)
+    for (uint64_t i = cell_off[r]; i < cell_off[r + 1]; ++i) {
+      if (i > cell_off[r] && !before(i - 1, cell_lag[i], cell_block[i])) return SHZ_E_INVALID;
+      if (cell_first[i] > cell_last[i]) return SHZ_E_INVALID;
+    }
+  rp_find uf(n);
+  const uint64_t reach = (uint64_t)max_gap + 1;
+  for (uint32_t r = 0; r < n_recs; ++r) {
+    const uint64_t c0 = cell_off[r];
+    for (uint64_t i = c0; i < cell_off[r + 1]; ++i) {
+      const uint64_t lag = cell_lag[i], block = cell_block[i];
+      const uint64_t lag_lo = lag > lag_tol ? lag - lag_tol : 0, b_lo = block > reach ? block - reach : 0, b_hi = block + reach;
+      uint64_t row = lag_lo;
+      while (row <= lag) {
+        uint64_t p = c0, hi = i;   // first cell in [c0, i) at or behind (row, b_lo)
+        while (p < hi) {
+          const uint64_t mid = p + ((hi - p) >> 1);
+          if (before(mid, row, b_lo)) p = mid + 1; else hi = mid;
+        }
+        if (p >= i) break;
+        if (cell_lag[p] != row) {   // the row holds no such cell: on to the row p lies in (ahead, as the list is sorted)
+          row = cell_lag[p];
+          continue;
+        }
+        for (uint64_t q = p; q < i && cell_lag[q] == row && cell_block[q] <= b_hi; ++q) uf.join(q, i);
+        ++row;
+      }
+    }
+  }
+  // the components in the order of their smallest cell: sums, spans, the lag with the most pairs (cells arrive lag-ascending,
+  // so a component's cells of one lag arrive together)
+  std::vector<rp_comp> comps;
+  std::vector<uint64_t> comp_of((size_t)n, ~0ull);
+  std::vector<uint32_t> comp_rec;
+  auto close_lag = [](rp_comp& c) {
+    if (c.cur_sum > c.best_sum) {
+      c.best_sum = c.cur_sum;
+      c.best_lag = c.cur_lag;
+    }
+  };
+  for (uint32_t r = 0; r < n_recs; ++r)
+    for (uint64_t i = cell_off[r]; i < cell_off[r + 1]; ++i) {
+      const uint64_t root = uf.root(i);
+      if (root == i) {
+        comp_of[i] = comps.size();
+        comps.emplace_back();
+        comps.back().root = i;
+        comps.back().lag_lo = comps.back().cur_lag = comps.back().best_lag = cell_lag[i];
+        comp_rec.push_back(r);
+      }
+      rp_comp& c = comps[comp_of[root]];
+      if (cell_lag[i] != c.cur_lag) {
+        close_lag(c);
+        c.cur_lag = cell_lag[i];
+        c.cur_sum = 0;
+      }
+      c.cur_sum += cell_pairs[i];
+      c.pairs += cell_pairs[i];
+      c.first = std::min(c.first, cell_first[i]);
+      c.last = std::max(c.last, cell_last[i]);
+      c.lag_hi = cell_lag[i];
+      ++c.cells;
+    }
+  std::vector<uint64_t> keep;
+  for (uint64_t k = 0; k < comps.size(); ++k) {
+    close_lag(comps[k]);
+    if (comps[k].pairs >= min_pairs) keep.push_back(k);
+  }
+  std::sort(keep.begin(), keep.end(), [&](uint64_t a, uint64_t b) {
+    const rp_comp &x = comps[a], &y = comps[b];
+    if (comp_rec[a] != comp_rec[b]) return comp_rec[a] < comp_rec[b];
+    if (x.first != y.first) return x.first < y.first;
+    if (x.best_lag != y.best_lag) return x.best_lag < y.best_lag;
+    return x.root < y.root;
+  });
+  *count = keep.size();
+  for (uint64_t k = 0; k < keep.size() && k < cap; ++k) {
+    const rp_comp& c = comps[keep[k]];
+    rep_rec[k] = comp_rec[keep[k]];
+    rep_lag[k] = c.best_lag;
+    rep_lag_lo[k] = c.lag_lo;
+    rep_lag_hi[k] = c.lag_hi;
+    rep_first[k] = c.first;
+    rep_last[k] = c.last;
+    rep_pairs[k] = c.pairs;
+    rep_cells[k] = c.cells;
+  }
+  return keep.size() > cap ? SHZ_E_CAPACITY : SHZ_OK;
+}
