@@ -419,7 +419,7 @@ uint64_t shz_recognize_estimate(uint64_t frames, uint32_t fan_value);
  * its LDS table 4 (element, segment) descriptors instead of 512, and a sub-batch 3 queries instead of 4,096, so that tests
  * reach every border with tiny inputs (results do not depend on any of them). */
 #define SHZ_DEBUG_EXTENT_SMALL_TILES 256u
-/* Test switch of shz_repeats_batch / shz_repeats_hashes: a slice holds one recording, an expand tile 64 pairs instead of
+/* Test switch of shz_repeats_* and shz_shared_*: a slice holds one recording (one job), an expand tile 64 pairs instead of
  * 2,048 and a block of the flag, count and cell kernels 64 elements instead of 256, so that tests reach every border with
  * tiny inputs (results do not depend on any of them). */
 #define SHZ_DEBUG_REPEAT_SMALL_SLICES 512u
@@ -1331,6 +1331,57 @@ int32_t shz_repeats_fold(const uint64_t* cell_off, uint32_t n_recs, const uint32
                          uint32_t max_gap, uint64_t min_pairs, uint32_t* rep_rec, uint32_t* rep_lag, uint32_t* rep_lag_lo,
                          uint32_t* rep_lag_hi, uint32_t* rep_first, uint32_t* rep_last, uint64_t* rep_pairs, uint32_t* rep_cells,
                          uint64_t cap, uint64_t* count);
+
+/* ---- content shared between recordings (new; no table, no catalogue) -----------------------------------------------------
+ * "Which stretches of recording a also air in recording b?" -- station A against station B, Monday's adverts against
+ * Tuesday's, one unlabelled tape against another, the night half of a day against its day half.  The join of
+ * shz_repeats_* between TWO recordings with a SIGNED lag, driven by a list of jobs (tests/shared_twin.py
+ * is the definition in Python).  All quantities are integers, in frames at the ctx's hop.
+ * HASHES: recordings, clips and H_r as in shz_repeats_*.  rec_hashes[r] = |H_r|.
+ * JOBS: job j = (job_a[j], job_b[j]), two different recordings < n_recs.  A recording may be named by any number of jobs,
+ * (a, b) and (b, a) may both be listed, and a job listed twice is answered twice.
+ * PAIRS: per job and key present in H_a and H_b, with m_a distinct times in a and m_b in b: m_a > max_run or m_b > max_run
+ * is a stop hash -- no pairs, 1 to job_skipped_keys[j], m_a + m_b to job_skipped_rows[j]; otherwise every (t_a, t_b) with
+ * lag_lo <= t_b - t_a <= lag_hi is the pair (lag = t_b - t_a, t = t_a).  job_pairs[j] = their number.
+ * CELLS: (j, lag, block = t_a >> cell_shift) with pairs, first (min t_a) and last (max t_a).  Returned: the cells with
+ * pairs >= min_cell_pairs in the order (j, lag, block) ascending, and cell_off[n_jobs + 1], their CSR over the JOBS.
+ * cell_lag is BIASED: lag + SHZ_SHARED_LAG_BIAS, so that the arrays of a call feed shz_repeats_fold as they are, the jobs
+ * standing in for its recordings (its order check and its |lag - lag'| <= lag_tol do not see the bias; the caller takes
+ * the bias off rep_lag / rep_lag_lo / rep_lag_hi).  The audio of [first, last] in a airs in b at [first + lag, last + lag].
+ * More than cap_cells: SHZ_E_CAPACITY, *count = the cells needed; cell_off, rec_hashes and the three job_* arrays are filled
+ * all the same, and the first cap_cells cells written.
+ * The device chain, all integer: the elements, runs and recording borders of shz_repeats_*; one ITEM per (job, unique
+ * element of a); per item the run of its key in b by a lower and an upper bound, and its partners there by two more
+ * searches for t_a + lag_lo and t_a + lag_hi (signed, cut to [0, 2^20 - 1]); a 64-bit scan; pair keys job << 41 | (lag +
+ * 2^20) << 20 | t_a written by output tile; from there the cell stage of shz_repeats_* on a lag field of 21 bits.  Jobs go
+ * through the pair stage in slices of consecutive whole jobs whose two pair buffers fit 1/8 of the workspace limit; the
+ * results do not depend on the slicing (SHZ_DEBUG_REPEAT_SMALL_SLICES: one job a slice).  A single job whose pairs do not
+ * fit is SHZ_E_UNSUPPORTED: the message names it, its recordings, its pairs, the lag window and max_run.  Also
+ * SHZ_E_UNSUPPORTED: more than 4,096 recordings or 4,096 jobs in one call, 2^32 hashes or more, 2^32 items or more.
+ * Refused before anything is launched, nothing written (SHZ_E_INVALID): what shz_repeats_* refuses (with job_* in the place
+ * of its rec_* arrays), and: a NULL job_a / job_b with n_jobs > 0; a job with a == b or a recording >= n_recs; a lag
+ * window outside [-(2^20 - 1), 2^20 - 1]; lag_hi < lag_lo.  n_jobs = 0 or no hashes: SHZ_OK, no cells, cell_off all 0;
+ * rec_hashes is filled all the same.
+ * shz_shared_hashes: HOST columns, as shz_repeats_hashes (tests / tools).  flags: 0.
+ * shz_shared_batch: the clips are fingerprinted into the library's own buffers, as shz_repeats_batch (flags:
+ * SHZ_PCM_DEVICE) -- every recording once, whatever the number of jobs that name it, and no hash crosses the bus.
+ * ms_extract / ms_pairs / ms_cells as there: stream intervals with the host read-backs of their stage inside them (ms_pairs:
+ * the unique count, the recordings' borders, the jobs' numbers). */
+#define SHZ_SHARED_LAG_BIAS 1048576u
+int32_t shz_shared_hashes(shz_ctx* ctx, const uint32_t* key32, const uint32_t* t1, const uint64_t* hash_off, uint32_t n_clips,
+                          const uint32_t* rec_clip0, uint32_t n_recs, const uint32_t* job_a, const uint32_t* job_b,
+                          uint32_t n_jobs, int32_t lag_lo, int32_t lag_hi, uint32_t max_run, uint32_t cell_shift,
+                          uint32_t min_cell_pairs, uint32_t flags, uint64_t* cell_off, uint32_t* cell_lag, uint32_t* cell_block,
+                          uint32_t* cell_pairs, uint32_t* cell_first, uint32_t* cell_last, uint32_t* rec_hashes,
+                          uint64_t* job_pairs, uint32_t* job_skipped_keys, uint64_t* job_skipped_rows, uint64_t cap_cells,
+                          uint64_t* count);
+int32_t shz_shared_batch(shz_ctx* ctx, const int16_t* pcm, const uint64_t* clip_off, uint32_t n_clips, const uint32_t* rec_clip0,
+                         uint32_t n_recs, uint32_t fs, double amp_min, uint32_t fan_value, const uint32_t* job_a,
+                         const uint32_t* job_b, uint32_t n_jobs, int32_t lag_lo, int32_t lag_hi, uint32_t max_run,
+                         uint32_t cell_shift, uint32_t min_cell_pairs, uint32_t flags, uint64_t* cell_off, uint32_t* cell_lag,
+                         uint32_t* cell_block, uint32_t* cell_pairs, uint32_t* cell_first, uint32_t* cell_last,
+                         uint32_t* rec_hashes, uint64_t* job_pairs, uint32_t* job_skipped_keys, uint64_t* job_skipped_rows,
+                         uint64_t cap_cells, uint64_t* count, float* ms_extract, float* ms_pairs, float* ms_cells);
 
 #ifdef __cplusplus
 }

@@ -391,3 +391,5 @@ from .speed import (pitch_ladder, recognize_speeds, recognize_warps, speed_ladde
 from .catalog import find_duplicates, fold_pairs, fold_pairs_warps, match_songs  # noqa: E402,F401
 # repeated content inside recordings, no catalogue (csrc/shz_repeat.hip): the lag histogram of a recording against itself
 from .repeats import find_repeats, find_repeats_hashes, occurrences  # noqa: E402,F401
+# content shared between recordings, no catalogue (csrc/shz_repeat.hip, the job form): a signed lag histogram per pair of recordings
+from .shared import find_shared, find_shared_hashes, shared_occurrences  # noqa: E402,F401

@@ -22,7 +22,8 @@ DEBUG_SCAN_SPEED_SMALL_SLICES = 32   # shz_scan_speeds: at most 1 recording x 2 
 DEBUG_CATALOG_SMALL_SLICES = 64   # shz_match_songs_warps: one song x at most 2 warps a slice
 DEBUG_VOTE_TOLERANT_ROUTE = 128   # the vote: the tolerant route at tolerance 0 too
 DEBUG_EXTENT_SMALL_TILES = 256   # shz_match_extents: tiles of 64 pairs, 4 descriptors in LDS, 3 queries a sub-batch
-DEBUG_REPEAT_SMALL_SLICES = 512  # shz_repeats_*: one recording a slice, expand tiles of 64 pairs, blocks of 64 elements
+DEBUG_REPEAT_SMALL_SLICES = 512  # shz_repeats_* / shz_shared_*: one recording (job) a slice, expand tiles of 64 pairs, blocks of 64 elements
+SHARED_LAG_BIAS = 1 << 20        # shz_shared_*: cell_lag = lag + SHARED_LAG_BIAS (SHZ_SHARED_LAG_BIAS)
 SCAN_NO_WARP = 0xFFFFFFFF            # shz_scan_warps: out_best of a window that tried no variant
 SCAN_U32, SCAN_POPC64, SCAN_U64 = 0, 1, 2   # shz_scan_host kinds
 STAGE_F32, STAGE_F64, STAGE_PERSISTENT = 0, 1, 1   # shz_stft_stage_host kinds | flag
@@ -232,6 +233,11 @@ SIGNATURES = {
                                       vp, C.c_uint64, u64p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "shz_repeats_fold": (C.c_int32, [vp, C.c_uint32, vp, vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint64, vp, vp, vp, vp, vp, vp,
                                      vp, vp, C.c_uint64, u64p]),
+    "shz_shared_hashes": (C.c_int32, [vp, vp, vp, vp, C.c_uint32, vp, C.c_uint32, vp, vp, C.c_uint32, C.c_int32, C.c_int32, C.c_uint32,
+                                      C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint64, u64p]),
+    "shz_shared_batch": (C.c_int32, [vp, vp, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.c_double, C.c_uint32, vp, vp, C.c_uint32,
+                                     C.c_int32, C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp,
+                                     vp, vp, C.c_uint64, u64p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
 }
 
 
@@ -775,14 +781,17 @@ class Context:
         None: a first call with no room names the count, a second one has it; a number: that one call as it is.  fill: what
         the arrays hold beforehand (tests).  Returns (rc, out, count): out = cell_off, the CELL_FIELDS arrays (cut to the cells
         written), rec_hashes, rec_skipped_keys, rec_pairs, rec_skipped_rows."""
-        cnt = C.c_uint64(fill)
-
         def room(cap):
             out = {k: np.full(int(cap), fill, np.uint32) for k in CELL_FIELDS}
             out.update(cell_off=np.full(nr + 1, fill, np.uint64), rec_hashes=np.full(nr, fill, np.uint32),
                        rec_skipped_keys=np.full(nr, fill, np.uint32), rec_pairs=np.full(nr, fill, np.uint64),
                        rec_skipped_rows=np.full(nr, fill, np.uint64))
             return out
+        return self._cells_call(fn, room, cap_cells, fill)
+
+    def _cells_call(self, fn, room, cap_cells, fill):
+        """The capacity idiom of the calls that return cells: room(cap) -> the output arrays with room for cap cells."""
+        cnt = C.c_uint64(fill)
         if cap_cells is None:
             out = room(0)
             rc = fn(out, 0, cnt)
@@ -855,6 +864,86 @@ class Context:
         rc, out, n, ms = self.repeats_batch_raw(*args, cap_cells)      # (cap_cells None: both calls, checked)
         if rc == E_CAPACITY:
             rc, out, n, ms = self.repeats_batch_raw(*args, n)
+        self.check(rc)
+        return out, ms
+
+    # ---- content shared between recordings (shz_repeat.hip: the job form of the join) ------------------------------------
+    def _shared_call(self, fn, nr, nj, cap_cells, fill):
+        """The outputs of shz_shared_hashes / shz_shared_batch and their capacity idiom, as _repeats_call.  Returns (rc, out,
+        count): out = cell_off (over the JOBS), the CELL_FIELDS arrays (lag BIASED by SHARED_LAG_BIAS, as the library returns
+        it), rec_hashes, job_pairs, job_skipped_keys, job_skipped_rows."""
+        def room(cap):
+            out = {k: np.full(int(cap), fill, np.uint32) for k in CELL_FIELDS}
+            out.update(cell_off=np.full(nj + 1, fill, np.uint64), rec_hashes=np.full(nr, fill, np.uint32),
+                       job_pairs=np.full(nj, fill, np.uint64), job_skipped_keys=np.full(nj, fill, np.uint32),
+                       job_skipped_rows=np.full(nj, fill, np.uint64))
+            return out
+        return self._cells_call(fn, room, cap_cells, fill)
+
+    @staticmethod
+    def _shared_outs(out, cap):
+        cells = [ptr(out[k]) if cap else None for k in CELL_FIELDS]
+        return [ptr(out["cell_off"]), *cells, ptr(out["rec_hashes"]), ptr(out["job_pairs"]), ptr(out["job_skipped_keys"]),
+                ptr(out["job_skipped_rows"])]
+
+    @staticmethod
+    def _jobs(jobs):
+        """(a, b) pairs -> the two uint32 columns of the ABI"""
+        j = np.asarray(list(jobs), np.uint32).reshape(-1, 2)
+        return np.ascontiguousarray(j[:, 0]), np.ascontiguousarray(j[:, 1])
+
+    def shared_hashes_raw(self, key32, t1, hash_off, rec_clip0, jobs, lag_lo, lag_hi, max_run=64, cell_shift=5, min_cell_pairs=8,
+                          flags=0, cap_cells=None, fill=0):
+        """One shz_shared_hashes as it is on HOST columns: (rc, out, count) -- see _shared_call.  jobs: (a, b) pairs."""
+        k = np.ascontiguousarray(key32, np.uint32)
+        t = np.ascontiguousarray(t1, np.uint32)
+        ho = np.ascontiguousarray(hash_off, np.uint64)
+        rc0 = np.ascontiguousarray(rec_clip0, np.uint32)
+        ja, jb = self._jobs(jobs)
+        nc, nr, nj = len(ho) - 1, len(rc0) - 1, len(ja)
+
+        def fn(out, cap, cnt):
+            return lib().shz_shared_hashes(self.h, ptr(k), ptr(t), ptr(ho), nc, ptr(rc0), nr, ptr(ja), ptr(jb), nj, int(lag_lo),
+                                           int(lag_hi), int(max_run), int(cell_shift), int(min_cell_pairs), int(flags),
+                                           *self._shared_outs(out, cap), int(cap), C.byref(cnt))
+        return self._shared_call(fn, nr, nj, cap_cells, fill)
+
+    def shared_hashes(self, key32, t1, hash_off, rec_clip0, jobs, lag_lo, lag_hi, max_run=64, cell_shift=5, min_cell_pairs=8):
+        """shz_shared_hashes (two calls): the cells of content shared between recordings given as fingerprints -- host columns
+        key32 / t1, hash_off their CSR over the clips, recording r = the clips [rec_clip0[r], rec_clip0[r + 1]), jobs a list of
+        (a, b): what of recording a also airs in recording b, at a lag t_b - t_a in [lag_lo, lag_hi] (signed frames).  Returns
+        a dict: cell_off (CSR of the cells over the jobs), lag (BIASED: lag + SHARED_LAG_BIAS, the form repeats_fold takes),
+        block, pairs, first, last per cell, rec_hashes per recording, job_pairs, job_skipped_keys, job_skipped_rows per job."""
+        _, out, _ = self.shared_hashes_raw(key32, t1, hash_off, rec_clip0, jobs, lag_lo, lag_hi, max_run, cell_shift, min_cell_pairs)
+        return out
+
+    def shared_batch_raw(self, pcm, clip_off, rec_clip0, jobs, lag_lo, lag_hi, max_run=64, cell_shift=5, min_cell_pairs=8, fs=44100,
+                         amp_min=10.0, fan_value=5, pcm_device=False, cap_cells=None, fill=0):
+        """One shz_shared_batch as it is: (rc, out, count, ms) -- out as _shared_call, ms = (extract, pairs, cells) device times
+        of the last call."""
+        co, nc = self._clip_off(clip_off)
+        rc0 = np.ascontiguousarray(rec_clip0, np.uint32)
+        ja, jb = self._jobs(jobs)
+        nr, nj = len(rc0) - 1, len(ja)
+        ms = [C.c_float(float(np.float32(fill))) for _ in range(3)]
+
+        def fn(out, cap, cnt):
+            return lib().shz_shared_batch(self.h, ptr(pcm), ptr(co), nc, ptr(rc0), nr, int(fs), float(amp_min), int(fan_value),
+                                          ptr(ja), ptr(jb), nj, int(lag_lo), int(lag_hi), int(max_run), int(cell_shift),
+                                          int(min_cell_pairs), PCM_DEVICE if pcm_device else 0, *self._shared_outs(out, cap), int(cap),
+                                          C.byref(cnt), *[C.byref(m) for m in ms])
+        rc, out, n = self._shared_call(fn, nr, nj, cap_cells, fill)
+        return rc, out, n, tuple(float(m.value) for m in ms)
+
+    def shared_batch(self, pcm, clip_off, rec_clip0, jobs, lag_lo, lag_hi, max_run=64, cell_shift=5, min_cell_pairs=8, fs=44100,
+                     amp_min=10.0, fan_value=5, pcm_device=False, cap_cells=None):
+        """shz_shared_batch: fingerprint the clips -- every recording once, however many jobs name it -- and find the cells of
+        every job (a, b) in one call, the hashes staying on the device.  cap_cells as repeats_batch.  Returns (out, ms): out as
+        shared_hashes, ms = (extract, pairs, cells) device times."""
+        args = (pcm, clip_off, rec_clip0, jobs, lag_lo, lag_hi, max_run, cell_shift, min_cell_pairs, fs, amp_min, fan_value, pcm_device)
+        rc, out, n, ms = self.shared_batch_raw(*args, cap_cells)       # (cap_cells None: both calls, checked)
+        if rc == E_CAPACITY:
+            rc, out, n, ms = self.shared_batch_raw(*args, n)
         self.check(rc)
         return out, ms
 

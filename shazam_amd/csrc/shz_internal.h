@@ -121,6 +121,8 @@ enum {
   SHZ_WS_RP_CNT, SHZ_WS_RP_POFF,    // ... partners of every element | pairs in front of it, the total behind the last
   SHZ_WS_RP_CELL,    // ... a slice's cells: first pair | first | last | keep flag | place among the kept
   SHZ_WS_RP_OUT,     // ... a slice's kept cells: rec | lag | block | pairs | first | last
+  SHZ_WS_SH_EL,      // ... the join between two recordings (shz_shared_*; it uses the RP slots with items in the place of elements and
+                     // jobs in the place of recordings): the element of every item
   SHZ_WS_COUNT
 };
 
@@ -151,7 +153,7 @@ struct shz_ctx {
   hipEvent_t rq_ev[3] = {nullptr, nullptr, nullptr};   // shz_recognize_batch: start, extraction done, match done (created on first use)
   hipEvent_t sc_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // shz_scan_batch / shz_scan_speeds: start, extraction done (then: a warp begun / done); the window stage: a step begun / done, the match behind it done (created on first use)
   hipEvent_t sp_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // shz_recognize_speeds / shz_match_songs_warps / _warps_extents: start, peaks (rows) done, a slice's warp begun / done, its match done, its extent pass done (created on first use)
-  hipEvent_t rp_ev[3] = {nullptr, nullptr, nullptr};   // shz_repeats_batch / _hashes: a stage begun, the pairs done, the cells done (created on first use)
+  hipEvent_t rp_ev[3] = {nullptr, nullptr, nullptr};   // shz_repeats_* / shz_shared_*: a stage begun, the pairs done, the cells done (created on first use)
   bool profiling = false;
   float kernel_ms[8] = {0};
   uint32_t kernel_launches[8] = {0};

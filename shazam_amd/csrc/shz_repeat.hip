@@ -16,6 +16,11 @@
 // expand and cells run per slice of whole recordings whose two pair buffers fit 1/8 of the workspace limit.  Workspace: the
 // slots SHZ_WS_RP_*, SHZ_WS_SORT_* and SHZ_WS_SCAN_TMP -- none of the extraction's, so shz_repeats_batch reads the hashes
 // where shz_extract_owned left them.  shz_repeats_fold (host) joins the returned cells into repeats.
+//
+// Content shared between TWO recordings (shz_shared_*) is the same join over a list of jobs (a, b) with a
+// signed lag: the elements and runs of all recordings once (rp_elements), one item per (job, element of a), the partners of an
+// item in b's run of its key (sh_count_kernel), pairs job << 41 | (lag + 2^20) << 20 | t_a by output tile (sh_expand_kernel),
+// and from there the cell stage above with a lag field of 21 bits (rp_cells).
 #include <algorithm>
 #include <numeric>
 
@@ -232,19 +237,20 @@ __global__ __launch_bounds__(RP_THREADS) void rp_keep_kernel(const uint32_t* __r
   if (c < nc) keep[c] = (head_pos[c + 1] - head_pos[c]) >= min_pairs ? 1u : 0u;
 }
 
-// the kept cells in their order: out = rec | lag | block | pairs | first | last, nk entries each
+// the kept cells in their order: out = rec | lag | block | pairs | first | last, nk entries each.  lag_bits: the width of the
+// lag field above the 20 bits of t (20: the self-join's lag; 21: the biased signed lag of the join between two recordings)
 __global__ __launch_bounds__(RP_THREADS) void rp_cell_out_kernel(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ head_pos,
                                                                  const uint32_t* __restrict__ first, const uint32_t* __restrict__ last,
                                                                  const uint32_t* __restrict__ keep, const uint32_t* __restrict__ place,
                                                                  uint32_t nc, uint32_t nk, uint32_t r0, uint32_t cell_shift,
-                                                                 uint32_t* __restrict__ out) {
+                                                                 int lag_bits, uint32_t* __restrict__ out) {
   const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= nc || !keep[c]) return;
   const uint32_t o = place[c], hp = head_pos[c];
   if (o >= nk) return;
   const uint64_t key = keys[hp];
-  out[o] = (uint32_t)(key >> 40) + r0;
-  out[(uint64_t)nk + o] = (uint32_t)(key >> RP_T_BITS) & RP_T_MASK;
+  out[o] = (uint32_t)(key >> (RP_T_BITS + lag_bits)) + r0;
+  out[(uint64_t)nk + o] = (uint32_t)(key >> RP_T_BITS) & ((1u << lag_bits) - 1u);
   out[2ull * nk + o] = ((uint32_t)key & RP_T_MASK) >> cell_shift;
   out[3ull * nk + o] = head_pos[c + 1] - hp;
   out[4ull * nk + o] = first[c];
@@ -252,6 +258,12 @@ __global__ __launch_bounds__(RP_THREADS) void rp_cell_out_kernel(const uint64_t*
 }
 
 // ---- what both entry points refuse before anything is launched ------------------------------------------------------------
+static int32_t rp_check_knobs(shz_ctx* ctx, const char* who, uint32_t max_run, uint32_t cell_shift, uint32_t min_cell_pairs) {
+  if (max_run < 2 || max_run > 1024) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: max_run must be in [2, 1024], got %u", who, max_run);
+  if (cell_shift > 19) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: cell_shift must be at most 19, got %u", who, cell_shift);
+  if (min_cell_pairs == 0) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: min_cell_pairs must be at least 1", who);
+  return SHZ_OK;
+}
 static int32_t rp_check(shz_ctx* ctx, const char* who, const rp_params& P, const rp_out& O) {
   if (!O.count || !O.cell_off || !O.rec_hashes || !O.rec_skipped_keys || !O.rec_pairs || !O.rec_skipped_rows)
     SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: count, cell_off or a rec_* array is NULL", who);
@@ -259,11 +271,44 @@ static int32_t rp_check(shz_ctx* ctx, const char* who, const rp_params& P, const
     SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: NULL cell array with room for %llu cells", who, (unsigned long long)O.cap_cells);
   if (P.max_lag < P.min_lag) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: max_lag %u is below min_lag %u", who, P.max_lag, P.min_lag);
   if (P.max_lag >= (1u << RP_T_BITS)) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: max_lag must be below 2^20, got %u", who, P.max_lag);
-  if (P.max_run < 2 || P.max_run > 1024) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: max_run must be in [2, 1024], got %u", who, P.max_run);
-  if (P.cell_shift > 19) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: cell_shift must be at most 19, got %u", who, P.cell_shift);
-  if (P.min_cell_pairs == 0) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: min_cell_pairs must be at least 1", who);
+  return rp_check_knobs(ctx, who, P.max_run, P.cell_shift, P.min_cell_pairs);
+}
+// host columns: hash_off[n_clips + 1] from 0 and never decreasing, the columns there, fewer than 2^32 hashes, every t1 < 2^20
+static int32_t rp_check_columns(shz_ctx* ctx, const char* who, const uint32_t* key32, const uint32_t* t1, const uint64_t* hash_off,
+                                uint32_t n_clips) {
+  if (!hash_off) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: hash_off is NULL", who);
+  if (hash_off[0] != 0) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: hash_off must start at 0 (it starts at %llu)", who, (unsigned long long)hash_off[0]);
+  for (uint32_t c = 0; c < n_clips; ++c)
+    if (hash_off[c + 1] < hash_off[c]) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: hash_off decreases at clip %u", who, c);
+  const uint64_t N = hash_off[n_clips];
+  if (N && (!key32 || !t1)) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: NULL column", who);
+  if (N >= (1ull << 32)) SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "%s: %llu hashes", who, (unsigned long long)N);
+  for (uint64_t i = 0; i < N; ++i)
+    if (t1[i] >> RP_T_BITS) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: t1[%llu] = %u, times must be below 2^20", who, (unsigned long long)i, t1[i]);
   return SHZ_OK;
 }
+// device copies of N >= 1 host hashes for the length of a call (tests / tools)
+struct rp_columns {
+  shz_ctx* ctx;
+  void *key = nullptr, *t1 = nullptr;
+  explicit rp_columns(shz_ctx* c) : ctx(c) {}
+  int32_t upload(const char* who, const uint32_t* key32, const uint32_t* t1_, uint64_t N) {
+    SHZ_HIP(ctx, hipSetDevice(ctx->device));
+    if (hipMalloc(&key, N * 4) != hipSuccess || hipMalloc(&t1, N * 4) != hipSuccess) {
+      (void)hipGetLastError();
+      SHZ_FAIL(ctx, SHZ_E_NOMEM, "%s: hipMalloc(2 x %llu) failed", who, (unsigned long long)(N * 4));
+    }
+    if (shz_memcpy(ctx, key, key32, N * 4, hipMemcpyHostToDevice) != hipSuccess ||
+        shz_memcpy(ctx, t1, t1_, N * 4, hipMemcpyHostToDevice) != hipSuccess)
+      SHZ_FAIL(ctx, SHZ_E_HIP, "%s: copy of the columns failed", who);
+    return SHZ_OK;
+  }
+  ~rp_columns() {
+    if (key || t1) (void)hipStreamSynchronize(ctx->stream);   // (a refused call may have queued work that reads the columns)
+    if (key) (void)hipFree(key);
+    if (t1) (void)hipFree(t1);
+  }
+};
 // the recordings' clips (no recording: no clips either, and the caller is done -- what it writes then: rp_empty)
 static int32_t rp_check_recs(shz_ctx* ctx, const char* who, uint32_t n_clips, const uint32_t* rec_clip0, uint32_t n_recs) {
   if (n_recs == 0) {
@@ -281,6 +326,182 @@ static void rp_empty(const rp_out& O, uint32_t n_recs) {
     O.rec_pairs[r] = O.rec_skipped_rows[r] = 0;
   }
 }
+
+// ---- the stages both joins share --------------------------------------------------------------------------------------------
+struct rp_elems {
+  const uint64_t* U;                        // the unique composed hashes, sorted
+  uint32_t nu;
+  const uint32_t *head, *pos, *run_start;   // run heads and their scan (SHZ_WS_RP_FLAG / _SCAN), first element of every run
+};
+// compose, sort + unique, the recordings' borders, the runs of the N >= 1 hashes.  d_rec_off[n_recs + 1]: first hash of every
+// recording; d_tot[0] / d_tot[1] get the unique elements / the runs, d_rec_start[n_recs + 1] the borders in U.  One host
+// read-back (the unique count); the stream is busy with the runs on return
+static int32_t rp_elements(shz_ctx* ctx, const char* who, const uint32_t* d_key32, const uint32_t* d_t1, uint64_t N, uint32_t n_recs,
+                           const uint64_t* d_rec_off, uint64_t* d_tot, uint32_t* d_rec_start, uint32_t bs, rp_elems* E) {
+  hipStream_t st = ctx->stream;
+  void *ka, *kb, *d_flag, *d_scan, *d_u, *d_run;
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SORT_A, N * 8, &ka));
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SORT_B, N * 8, &kb));
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_RP_FLAG, N * 4, &d_flag));
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_RP_SCAN, N * 4, &d_scan));
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_RP_U, N * 8, &d_u));
+  hipLaunchKernelGGL(rp_compose_kernel, dim3(rp_grid(N, bs)), dim3(bs), 0, st, d_key32, d_t1, d_rec_off, n_recs, N, (uint64_t*)ka);
+  SHZ_HIP(ctx, hipGetLastError());
+  int sel = 0;
+  SHZ_TRY(shz_sort_u64(ctx, (uint64_t*)ka, (uint64_t*)kb, nullptr, nullptr, 0, N, 0, 52 + rp_bits(n_recs - 1), &sel));
+  const uint64_t* sorted = (const uint64_t*)(sel ? kb : ka);
+  hipLaunchKernelGGL(rp_head_kernel, dim3(rp_grid(N, bs)), dim3(bs), 0, st, sorted, N, 0, (uint32_t*)d_flag);
+  SHZ_HIP(ctx, hipGetLastError());
+  SHZ_TRY(shz_scan_u32(ctx, (const uint32_t*)d_flag, (uint32_t*)d_scan, N, d_tot));
+  hipLaunchKernelGGL(rp_compact_kernel, dim3(rp_grid(N, bs)), dim3(bs), 0, st, sorted, (const uint32_t*)d_flag, (const uint32_t*)d_scan,
+                     N, (uint64_t*)d_u);
+  SHZ_HIP(ctx, hipGetLastError());
+  uint64_t nu64 = 0;
+  SHZ_HIP(ctx, shz_memcpy(ctx, &nu64, d_tot, 8, hipMemcpyDeviceToHost));
+  SHZ_HIP(ctx, hipStreamSynchronize(st));
+  if (nu64 == 0 || nu64 > N) SHZ_FAIL(ctx, SHZ_E_STATE, "%s: %llu unique hashes of %llu", who, (unsigned long long)nu64, (unsigned long long)N);
+  const uint32_t nu = (uint32_t)nu64;
+  const uint64_t* U = (const uint64_t*)d_u;
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_RP_RUN, ((uint64_t)nu + 1) * 4, &d_run));
+  hipLaunchKernelGGL(rp_rec_start_kernel, dim3(rp_grid((uint64_t)n_recs + 1, bs)), dim3(bs), 0, st, U, nu, n_recs, d_rec_start);
+  hipLaunchKernelGGL(rp_head_kernel, dim3(rp_grid(nu, bs)), dim3(bs), 0, st, U, (uint64_t)nu, RP_T_BITS, (uint32_t*)d_flag);
+  SHZ_HIP(ctx, hipGetLastError());
+  SHZ_TRY(shz_scan_u32(ctx, (const uint32_t*)d_flag, (uint32_t*)d_scan, nu, d_tot + 1));
+  hipLaunchKernelGGL(rp_run_start_kernel, dim3(rp_grid(nu, bs)), dim3(bs), 0, st, (const uint32_t*)d_flag, (const uint32_t*)d_scan, nu,
+                     (const uint64_t*)(d_tot + 1), (uint32_t*)d_run);
+  SHZ_HIP(ctx, hipGetLastError());
+  *E = rp_elems{U, nu, (const uint32_t*)d_flag, (const uint32_t*)d_scan, (const uint32_t*)d_run};
+  return SHZ_OK;
+}
+
+// the slices: consecutive whole owners (recordings, jobs) whose pairs po[o + 1] - po[o] together stay within max_pairs, none
+// larger than that alone; one owner a slice under SHZ_DEBUG_REPEAT_SMALL_SLICES.  Returns the slices' borders
+static std::vector<uint32_t> rp_cut_slices(const uint64_t* po, uint32_t n, uint64_t max_pairs, bool small, uint64_t* np_max) {
+  std::vector<uint32_t> slices{0};
+  *np_max = 0;
+  for (uint32_t r0 = 0; r0 < n;) {
+    uint32_t r1 = r0 + 1;
+    while (!small && r1 < n && po[r1 + 1] - po[r0] <= max_pairs) ++r1;
+    *np_max = std::max(*np_max, po[r1] - po[r0]);
+    slices.push_back(r1);
+    r0 = r1;
+  }
+  return slices;
+}
+
+// The cell stage of a slice and the cells of the call.  A slice's np pair keys owner_in_slice << (20 + lag_bits) | lag << 20 | t
+// lie in ka (the expand, queued behind rp_ev[0], wrote them); slice() sorts them on the bits from cell_shift up, reduces the
+// cells and gathers the kept ones on the host, copy_out() hands them to the caller
+struct rp_cells {
+  shz_ctx* ctx;
+  const char *who, *what;   // the entry point, and what owns cells ("recording", "job"), for messages
+  uint32_t n_owners, bs;
+  uint64_t cap;
+  bool timed;
+  uint64_t *ka = nullptr, *kb = nullptr;
+  uint32_t *flag = nullptr, *scan = nullptr;
+  std::vector<uint32_t> c_lag, c_block, c_pairs, c_first, c_last, blockbuf;
+  std::vector<uint64_t> cell_off;
+  uint64_t n_cells_all = 0;
+  rp_cells(shz_ctx* c, const char* who_, const char* what_, uint32_t n, uint64_t cap_, uint32_t bs_, bool timed_)
+      : ctx(c), who(who_), what(what_), n_owners(n), bs(bs_), cap(cap_), timed(timed_), cell_off((size_t)n + 1, 0) {}
+  int32_t reserve(uint64_t np_max) {
+    if (np_max == 0) return SHZ_OK;
+    void* p;
+    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SORT_A, np_max * 8, &p));
+    ka = (uint64_t*)p;
+    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SORT_B, np_max * 8, &p));
+    kb = (uint64_t*)p;
+    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_RP_FLAG, np_max * 4, &p));
+    flag = (uint32_t*)p;
+    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_RP_SCAN, np_max * 4, &p));
+    scan = (uint32_t*)p;
+    return SHZ_OK;
+  }
+  // d_tot[2] / d_tot[3]: the slice's cells / kept cells.  The owners [r0, r1) are in the slice.  The times of the expand and of
+  // the cell stage are added to *ms_expand / *ms_cells when timed
+  int32_t slice(uint64_t* d_tot, uint32_t np, uint32_t cell_shift, uint32_t min_cell_pairs, int lag_bits, uint32_t r0, uint32_t r1,
+                float* ms_expand, float* ms_cells) {
+    hipStream_t st = ctx->stream;
+    if (timed) SHZ_HIP(ctx, hipEventRecord(ctx->rp_ev[1], st));
+    int sel = 0;
+    SHZ_TRY(shz_sort_u64(ctx, ka, kb, nullptr, nullptr, 0, np, (int)cell_shift, RP_T_BITS + lag_bits + rp_bits(r1 - r0 - 1), &sel));
+    const uint64_t* pk = sel ? kb : ka;
+    hipLaunchKernelGGL(rp_head_kernel, dim3(rp_grid(np, bs)), dim3(bs), 0, st, pk, (uint64_t)np, (int)cell_shift, flag);
+    SHZ_HIP(ctx, hipGetLastError());
+    SHZ_TRY(shz_scan_u32(ctx, (const uint32_t*)flag, scan, np, d_tot + 2));
+    uint64_t nc64 = 0;
+    SHZ_HIP(ctx, shz_memcpy(ctx, &nc64, d_tot + 2, 8, hipMemcpyDeviceToHost));
+    SHZ_HIP(ctx, hipStreamSynchronize(st));
+    if (nc64 == 0 || nc64 > np) SHZ_FAIL(ctx, SHZ_E_STATE, "%s: %llu cells of %u pairs", who, (unsigned long long)nc64, np);
+    const uint32_t nc = (uint32_t)nc64;
+    void* d_cell;
+    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_RP_CELL, (5ull * nc + 2) * 4, &d_cell));
+    uint32_t *head_pos = (uint32_t*)d_cell, *cfirst = head_pos + nc + 1, *clast = cfirst + nc, *keep = clast + nc, *place = keep + nc;
+    hipLaunchKernelGGL(rp_cell_init_kernel, dim3(rp_grid((uint64_t)nc + 1, bs)), dim3(bs), 0, st, nc, np, head_pos, cfirst, clast);
+    hipLaunchKernelGGL(rp_cell_reduce_kernel, dim3(rp_grid(np, bs)), dim3(bs), 0, st, pk, (const uint32_t*)flag, (const uint32_t*)scan, np,
+                       head_pos, cfirst, clast);
+    hipLaunchKernelGGL(rp_keep_kernel, dim3(rp_grid(nc, bs)), dim3(bs), 0, st, (const uint32_t*)head_pos, nc, min_cell_pairs, keep);
+    SHZ_HIP(ctx, hipGetLastError());
+    SHZ_TRY(shz_scan_u32(ctx, (const uint32_t*)keep, place, nc, d_tot + 3));
+    uint64_t nk64 = 0;
+    SHZ_HIP(ctx, shz_memcpy(ctx, &nk64, d_tot + 3, 8, hipMemcpyDeviceToHost));
+    SHZ_HIP(ctx, hipStreamSynchronize(st));
+    if (nk64 > nc) SHZ_FAIL(ctx, SHZ_E_STATE, "%s: %llu kept cells of %u", who, (unsigned long long)nk64, nc);
+    const uint32_t nk = (uint32_t)nk64;
+    if (nk) {
+      void* d_out;
+      SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_RP_OUT, 6ull * nk * 4, &d_out));
+      hipLaunchKernelGGL(rp_cell_out_kernel, dim3(rp_grid(nc, bs)), dim3(bs), 0, st, pk, (const uint32_t*)head_pos, (const uint32_t*)cfirst,
+                         (const uint32_t*)clast, (const uint32_t*)keep, (const uint32_t*)place, nc, nk, r0, cell_shift, lag_bits,
+                         (uint32_t*)d_out);
+      SHZ_HIP(ctx, hipGetLastError());
+      blockbuf.resize(6 * (size_t)nk);
+      SHZ_HIP(ctx, shz_memcpy(ctx, blockbuf.data(), d_out, 6ull * nk * 4, hipMemcpyDeviceToHost));
+    }
+    if (timed) SHZ_HIP(ctx, hipEventRecord(ctx->rp_ev[2], st));
+    SHZ_HIP(ctx, hipStreamSynchronize(st));
+    if (timed) {
+      float a = 0.f, b = 0.f;
+      SHZ_HIP(ctx, hipEventElapsedTime(&a, ctx->rp_ev[0], ctx->rp_ev[1]));
+      SHZ_HIP(ctx, hipEventElapsedTime(&b, ctx->rp_ev[1], ctx->rp_ev[2]));
+      *ms_expand += a;
+      *ms_cells += b;
+    }
+    for (uint32_t k = 0; k < nk; ++k) {
+      const uint32_t r = blockbuf[k];
+      if (r < r0 || r >= r1) SHZ_FAIL(ctx, SHZ_E_STATE, "%s: a cell of %s %u in the slice [%u, %u)", who, what, r, r0, r1);
+      ++cell_off[r + 1];
+      if (n_cells_all + k < cap) {   // (what has no room is counted only)
+        c_lag.push_back(blockbuf[(size_t)nk + k]);
+        c_block.push_back(blockbuf[2 * (size_t)nk + k]);
+        c_pairs.push_back(blockbuf[3 * (size_t)nk + k]);
+        c_first.push_back(blockbuf[4 * (size_t)nk + k]);
+        c_last.push_back(blockbuf[5 * (size_t)nk + k]);
+      }
+    }
+    n_cells_all += nk;
+    return SHZ_OK;
+  }
+  // cell_off[n_owners + 1], *count and the cells there is room for; SHZ_E_CAPACITY when there are more
+  int32_t copy_out(uint64_t* o_off, uint32_t* o_lag, uint32_t* o_block, uint32_t* o_pairs, uint32_t* o_first, uint32_t* o_last,
+                   uint64_t* count) {
+    for (uint32_t r = 0; r < n_owners; ++r) cell_off[r + 1] += cell_off[r];
+    memcpy(o_off, cell_off.data(), ((size_t)n_owners + 1) * 8);
+    *count = n_cells_all;
+    const size_t nw = c_lag.size();
+    if (nw) {
+      memcpy(o_lag, c_lag.data(), nw * 4);
+      memcpy(o_block, c_block.data(), nw * 4);
+      memcpy(o_pairs, c_pairs.data(), nw * 4);
+      memcpy(o_first, c_first.data(), nw * 4);
+      memcpy(o_last, c_last.data(), nw * 4);
+    }
+    if (n_cells_all > cap)
+      SHZ_FAIL(ctx, SHZ_E_CAPACITY, "%s: %llu cells, room for %llu", who, (unsigned long long)n_cells_all, (unsigned long long)cap);
+    return SHZ_OK;
+  }
+};
 
 // ---- the core on device columns -------------------------------------------------------------------------------------------
 // d_key32 / d_t1: device columns of hash_off[n_clips] < 2^32 entries with t1 < 2^20, hash_off (host) their CSR over the clips;
@@ -316,45 +537,18 @@ static int32_t rp_core(shz_ctx* ctx, const char* who, const uint32_t* d_key32, c
   uint64_t *d_tot = d64, *d_rec_off = d64 + o_off, *d_rec_po = d64 + o_po, *d_skip_rows = d64 + o_rows;
   uint32_t *d_rec_start = (uint32_t*)(d64 + n64), *d_skip_keys = d_rec_start + nr1;
   SHZ_HIP(ctx, shz_memcpy(ctx, d_rec, hrec.data(), hrec.size() * 8, hipMemcpyHostToDevice));
-  // 1) compose, 2) sort + unique
-  void *ka, *kb, *d_flag, *d_scan, *d_u;
-  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SORT_A, N * 8, &ka));
-  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SORT_B, N * 8, &kb));
-  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_RP_FLAG, N * 4, &d_flag));
-  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_RP_SCAN, N * 4, &d_scan));
-  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_RP_U, N * 8, &d_u));
-  hipLaunchKernelGGL(rp_compose_kernel, dim3(rp_grid(N, bs)), dim3(bs), 0, st, d_key32, d_t1, (const uint64_t*)d_rec_off, n_recs, N,
-                     (uint64_t*)ka);
-  SHZ_HIP(ctx, hipGetLastError());
-  int sel = 0;
-  SHZ_TRY(shz_sort_u64(ctx, (uint64_t*)ka, (uint64_t*)kb, nullptr, nullptr, 0, N, 0, 52 + rp_bits(n_recs - 1), &sel));
-  const uint64_t* sorted = (const uint64_t*)(sel ? kb : ka);
-  hipLaunchKernelGGL(rp_head_kernel, dim3(rp_grid(N, bs)), dim3(bs), 0, st, sorted, N, 0, (uint32_t*)d_flag);
-  SHZ_HIP(ctx, hipGetLastError());
-  SHZ_TRY(shz_scan_u32(ctx, (const uint32_t*)d_flag, (uint32_t*)d_scan, N, d_tot));
-  hipLaunchKernelGGL(rp_compact_kernel, dim3(rp_grid(N, bs)), dim3(bs), 0, st, sorted, (const uint32_t*)d_flag, (const uint32_t*)d_scan,
-                     N, (uint64_t*)d_u);
-  SHZ_HIP(ctx, hipGetLastError());
-  uint64_t nu64 = 0;
-  SHZ_HIP(ctx, shz_memcpy(ctx, &nu64, d_tot, 8, hipMemcpyDeviceToHost));
-  SHZ_HIP(ctx, hipStreamSynchronize(st));
-  if (nu64 == 0 || nu64 > N) SHZ_FAIL(ctx, SHZ_E_STATE, "%s: %llu unique hashes of %llu", who, (unsigned long long)nu64, (unsigned long long)N);
-  const uint32_t nu = (uint32_t)nu64;
-  const uint64_t* U = (const uint64_t*)d_u;
-  // 3) runs, 4) count, scan, the recordings' numbers
-  void *d_run, *d_lo, *d_cnt, *d_poff;
-  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_RP_RUN, ((uint64_t)nu + 1) * 4, &d_run));
+  // 1) compose, 2) sort + unique, 3) runs
+  rp_elems E;
+  SHZ_TRY(rp_elements(ctx, who, d_key32, d_t1, N, n_recs, d_rec_off, d_tot, d_rec_start, bs, &E));
+  const uint32_t nu = E.nu;
+  const uint64_t* U = E.U;
+  // 4) count, scan, the recordings' numbers
+  void *d_lo, *d_cnt, *d_poff;
   SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_RP_LO, (uint64_t)nu * 4, &d_lo));
   SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_RP_CNT, (uint64_t)nu * 8, &d_cnt));
   SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_RP_POFF, ((uint64_t)nu + 1) * 8, &d_poff));
-  hipLaunchKernelGGL(rp_rec_start_kernel, dim3(rp_grid(nr1, bs)), dim3(bs), 0, st, U, nu, n_recs, d_rec_start);
-  hipLaunchKernelGGL(rp_head_kernel, dim3(rp_grid(nu, bs)), dim3(bs), 0, st, U, (uint64_t)nu, RP_T_BITS, (uint32_t*)d_flag);
-  SHZ_HIP(ctx, hipGetLastError());
-  SHZ_TRY(shz_scan_u32(ctx, (const uint32_t*)d_flag, (uint32_t*)d_scan, nu, d_tot + 1));
-  hipLaunchKernelGGL(rp_run_start_kernel, dim3(rp_grid(nu, bs)), dim3(bs), 0, st, (const uint32_t*)d_flag, (const uint32_t*)d_scan, nu,
-                     (const uint64_t*)(d_tot + 1), (uint32_t*)d_run);
-  hipLaunchKernelGGL(rp_count_kernel, dim3(rp_grid(nu, bs)), dim3(bs), 0, st, U, (const uint32_t*)d_flag, (const uint32_t*)d_scan,
-                     (const uint32_t*)d_run, nu, P, (uint64_t*)d_cnt, (uint32_t*)d_lo, d_skip_keys, (unsigned long long*)d_skip_rows);
+  hipLaunchKernelGGL(rp_count_kernel, dim3(rp_grid(nu, bs)), dim3(bs), 0, st, U, E.head, E.pos, E.run_start, nu, P, (uint64_t*)d_cnt,
+                     (uint32_t*)d_lo, d_skip_keys, (unsigned long long*)d_skip_rows);
   SHZ_HIP(ctx, hipGetLastError());
   uint64_t* poff = (uint64_t*)d_poff;
   SHZ_TRY(shz_scan_u64(ctx, (const uint64_t*)d_cnt, poff, nu, poff + nu));
@@ -383,25 +577,11 @@ static int32_t rp_core(shz_ctx* ctx, const char* who, const uint32_t* d_key32, c
       SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED,
                "%s: recording %u has %llu pairs, a slice holds %llu (workspace limit): raise min_lag (%u) or lower max_run (%u)", who, r,
                (unsigned long long)(rec_po[r + 1] - rec_po[r]), (unsigned long long)max_pairs, P.min_lag, P.max_run);
-  std::vector<uint32_t> slices{0};
   uint64_t np_max = 0;
-  for (uint32_t r0 = 0; r0 < n_recs;) {
-    uint32_t r1 = r0 + 1;
-    while (!small && r1 < n_recs && rec_po[r1 + 1] - rec_po[r0] <= max_pairs) ++r1;
-    np_max = std::max(np_max, rec_po[r1] - rec_po[r0]);
-    slices.push_back(r1);
-    r0 = r1;
-  }
+  const std::vector<uint32_t> slices = rp_cut_slices(rec_po, n_recs, max_pairs, small, &np_max);
   // 6) slice by slice: expand, sort, cells
-  std::vector<uint32_t> c_lag, c_block, c_pairs, c_first, c_last, blockbuf;
-  std::vector<uint64_t> cell_off((size_t)nr1, 0);
-  uint64_t n_cells_all = 0;
-  if (np_max) {
-    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SORT_A, np_max * 8, &ka));
-    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SORT_B, np_max * 8, &kb));
-    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_RP_FLAG, np_max * 4, &d_flag));
-    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_RP_SCAN, np_max * 4, &d_scan));
-  }
+  rp_cells C(ctx, who, "recording", n_recs, O.cap_cells, bs, timed);
+  SHZ_TRY(C.reserve(np_max));
   for (size_t s = 0; s + 1 < slices.size(); ++s) {
     const uint32_t r0 = slices[s], r1 = slices[s + 1], e0 = rec_start[r0], e1 = rec_start[r1];
     const uint64_t P0 = rec_po[r0], np64 = rec_po[r1] - P0;
@@ -409,87 +589,54 @@ static int32_t rp_core(shz_ctx* ctx, const char* who, const uint32_t* d_key32, c
     const uint32_t np = (uint32_t)np64;   // (<= 2^31)
     if (timed) SHZ_HIP(ctx, hipEventRecord(ctx->rp_ev[0], st));
     hipLaunchKernelGGL(rp_expand_kernel, dim3(rp_grid(np, tile)), dim3(bs), 0, st, U, (const uint64_t*)poff, (const uint32_t*)d_lo, e0, e1,
-                       P0, np64, tile, r0, (uint64_t*)ka);
+                       P0, np64, tile, r0, C.ka);
     SHZ_HIP(ctx, hipGetLastError());
-    if (timed) SHZ_HIP(ctx, hipEventRecord(ctx->rp_ev[1], st));
-    SHZ_TRY(shz_sort_u64(ctx, (uint64_t*)ka, (uint64_t*)kb, nullptr, nullptr, 0, np, (int)P.cell_shift, 40 + rp_bits(r1 - r0 - 1), &sel));
-    const uint64_t* pk = (const uint64_t*)(sel ? kb : ka);
-    hipLaunchKernelGGL(rp_head_kernel, dim3(rp_grid(np, bs)), dim3(bs), 0, st, pk, (uint64_t)np, (int)P.cell_shift, (uint32_t*)d_flag);
-    SHZ_HIP(ctx, hipGetLastError());
-    SHZ_TRY(shz_scan_u32(ctx, (const uint32_t*)d_flag, (uint32_t*)d_scan, np, d_tot + 2));
-    uint64_t nc64 = 0;
-    SHZ_HIP(ctx, shz_memcpy(ctx, &nc64, d_tot + 2, 8, hipMemcpyDeviceToHost));
-    SHZ_HIP(ctx, hipStreamSynchronize(st));
-    if (nc64 == 0 || nc64 > np) SHZ_FAIL(ctx, SHZ_E_STATE, "%s: %llu cells of %u pairs", who, (unsigned long long)nc64, np);
-    const uint32_t nc = (uint32_t)nc64;
-    void* d_cell;
-    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_RP_CELL, (5ull * nc + 2) * 4, &d_cell));
-    uint32_t *head_pos = (uint32_t*)d_cell, *cfirst = head_pos + nc + 1, *clast = cfirst + nc, *keep = clast + nc, *place = keep + nc;
-    hipLaunchKernelGGL(rp_cell_init_kernel, dim3(rp_grid((uint64_t)nc + 1, bs)), dim3(bs), 0, st, nc, np, head_pos, cfirst, clast);
-    hipLaunchKernelGGL(rp_cell_reduce_kernel, dim3(rp_grid(np, bs)), dim3(bs), 0, st, pk, (const uint32_t*)d_flag, (const uint32_t*)d_scan,
-                       np, head_pos, cfirst, clast);
-    hipLaunchKernelGGL(rp_keep_kernel, dim3(rp_grid(nc, bs)), dim3(bs), 0, st, (const uint32_t*)head_pos, nc, P.min_cell_pairs, keep);
-    SHZ_HIP(ctx, hipGetLastError());
-    SHZ_TRY(shz_scan_u32(ctx, (const uint32_t*)keep, place, nc, d_tot + 3));
-    uint64_t nk64 = 0;
-    SHZ_HIP(ctx, shz_memcpy(ctx, &nk64, d_tot + 3, 8, hipMemcpyDeviceToHost));
-    SHZ_HIP(ctx, hipStreamSynchronize(st));
-    if (nk64 > nc) SHZ_FAIL(ctx, SHZ_E_STATE, "%s: %llu kept cells of %u", who, (unsigned long long)nk64, nc);
-    const uint32_t nk = (uint32_t)nk64;
-    if (nk) {
-      void* d_out;
-      SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_RP_OUT, 6ull * nk * 4, &d_out));
-      hipLaunchKernelGGL(rp_cell_out_kernel, dim3(rp_grid(nc, bs)), dim3(bs), 0, st, pk, (const uint32_t*)head_pos, (const uint32_t*)cfirst,
-                         (const uint32_t*)clast, (const uint32_t*)keep, (const uint32_t*)place, nc, nk, r0, P.cell_shift, (uint32_t*)d_out);
-      SHZ_HIP(ctx, hipGetLastError());
-      blockbuf.resize(6 * (size_t)nk);
-      SHZ_HIP(ctx, shz_memcpy(ctx, blockbuf.data(), d_out, 6ull * nk * 4, hipMemcpyDeviceToHost));
-    }
-    if (timed) SHZ_HIP(ctx, hipEventRecord(ctx->rp_ev[2], st));
-    SHZ_HIP(ctx, hipStreamSynchronize(st));
-    if (timed) {
-      float a = 0.f, b = 0.f;
-      SHZ_HIP(ctx, hipEventElapsedTime(&a, ctx->rp_ev[0], ctx->rp_ev[1]));
-      SHZ_HIP(ctx, hipEventElapsedTime(&b, ctx->rp_ev[1], ctx->rp_ev[2]));
-      pairs_ms += a;
-      cells_ms += b;
-    }
-    for (uint32_t k = 0; k < nk; ++k) {
-      const uint32_t r = blockbuf[k];
-      if (r < r0 || r >= r1) SHZ_FAIL(ctx, SHZ_E_STATE, "%s: a cell of recording %u in the slice [%u, %u)", who, r, r0, r1);
-      ++cell_off[r + 1];
-      if (n_cells_all + k < O.cap_cells) {   // (what has no room is counted only)
-        c_lag.push_back(blockbuf[(size_t)nk + k]);
-        c_block.push_back(blockbuf[2 * (size_t)nk + k]);
-        c_pairs.push_back(blockbuf[3 * (size_t)nk + k]);
-        c_first.push_back(blockbuf[4 * (size_t)nk + k]);
-        c_last.push_back(blockbuf[5 * (size_t)nk + k]);
-      }
-    }
-    n_cells_all += nk;
+    SHZ_TRY(C.slice(d_tot, np, P.cell_shift, P.min_cell_pairs, RP_T_BITS, r0, r1, &pairs_ms, &cells_ms));
   }
   // 7) the outputs
   for (uint32_t r = 0; r < n_recs; ++r) {
-    cell_off[r + 1] += cell_off[r];
     O.rec_hashes[r] = rec_start[r + 1] - rec_start[r];
     O.rec_pairs[r] = rec_po[r + 1] - rec_po[r];
     O.rec_skipped_keys[r] = skip_keys[r];
     O.rec_skipped_rows[r] = skip_rows[r];
   }
-  memcpy(O.cell_off, cell_off.data(), nr1 * 8);
-  *O.count = n_cells_all;
-  const size_t nw = c_lag.size();
-  if (nw) {
-    memcpy(O.cell_lag, c_lag.data(), nw * 4);
-    memcpy(O.cell_block, c_block.data(), nw * 4);
-    memcpy(O.cell_pairs, c_pairs.data(), nw * 4);
-    memcpy(O.cell_first, c_first.data(), nw * 4);
-    memcpy(O.cell_last, c_last.data(), nw * 4);
-  }
   if (ms_pairs) *ms_pairs = pairs_ms;
   if (ms_cells) *ms_cells = cells_ms;
-  if (n_cells_all > O.cap_cells)
-    SHZ_FAIL(ctx, SHZ_E_CAPACITY, "%s: %llu cells, room for %llu", who, (unsigned long long)n_cells_all, (unsigned long long)O.cap_cells);
+  return C.copy_out(O.cell_off, O.cell_lag, O.cell_block, O.cell_pairs, O.cell_first, O.cell_last, O.count);
+}
+
+// ---- the extraction of the fused calls ----------------------------------------------------------------------------------------
+// the three times of a fused call (each may be NULL), zeroed: the first write of the call.  A call that times anything hands
+// the cores a place for both of their times
+struct rp_times {
+  float *extract, *p, *c, spare[2] = {0.f, 0.f};
+  bool timed;
+  rp_times(float* ms_extract, float* ms_pairs, float* ms_cells)
+      : extract(ms_extract), p(ms_pairs), c(ms_cells), timed(ms_extract || ms_pairs || ms_cells) {
+    if (extract) *extract = 0.f;
+    if (p) *p = 0.f;
+    if (c) *c = 0.f;
+  }
+  float* pairs() { return timed ? (p ? p : &spare[0]) : nullptr; }
+  float* cells() { return timed ? (c ? c : &spare[1]) : nullptr; }
+};
+// the clips fingerprinted into the library's own columns (shz_extract_owned), timed; fewer than 2^32 hashes
+static int32_t rp_extract(shz_ctx* ctx, const char* who, const int16_t* pcm, const uint64_t* clip_off, uint32_t n_clips, uint32_t fs,
+                          double amp_min, uint32_t fan_value, uint32_t flags, rp_times& T, uint64_t* hash_off, const uint32_t** d_key,
+                          const uint32_t** d_t1) {
+  SHZ_HIP(ctx, hipSetDevice(ctx->device));
+  if (T.timed) {
+    for (hipEvent_t& e : ctx->rp_ev)
+      if (!e) SHZ_HIP(ctx, hipEventCreate(&e));
+    SHZ_HIP(ctx, hipEventRecord(ctx->rp_ev[0], ctx->stream));
+  }
+  SHZ_TRY(shz_extract_owned(ctx, who, pcm, clip_off, n_clips, fs, amp_min, fan_value, flags & SHZ_PCM_DEVICE, hash_off, d_key, d_t1));
+  if (T.timed) {
+    SHZ_HIP(ctx, hipEventRecord(ctx->rp_ev[1], ctx->stream));
+    SHZ_HIP(ctx, hipEventSynchronize(ctx->rp_ev[1]));
+    if (T.extract) SHZ_HIP(ctx, hipEventElapsedTime(T.extract, ctx->rp_ev[0], ctx->rp_ev[1]));
+  }
+  if (hash_off[n_clips] >= (1ull << 32)) SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "%s: %llu hashes", who, (unsigned long long)hash_off[n_clips]);
   return SHZ_OK;
 }
 
@@ -509,38 +656,15 @@ extern "C" int32_t shz_repeats_hashes(shz_ctx* ctx, const uint32_t* key32, const
   if (flags) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: flags must be 0", who);
   SHZ_TRY(rp_check(ctx, who, P, O));
   SHZ_TRY(rp_check_recs(ctx, who, n_clips, rec_clip0, n_recs));
-  if (!hash_off) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: hash_off is NULL", who);
-  if (hash_off[0] != 0) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: hash_off must start at 0 (it starts at %llu)", who, (unsigned long long)hash_off[0]);
-  for (uint32_t c = 0; c < n_clips; ++c)
-    if (hash_off[c + 1] < hash_off[c]) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: hash_off decreases at clip %u", who, c);
+  SHZ_TRY(rp_check_columns(ctx, who, key32, t1, hash_off, n_clips));
   const uint64_t N = hash_off[n_clips];
-  if (N && (!key32 || !t1)) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: NULL column", who);
-  if (N >= (1ull << 32)) SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "%s: %llu hashes", who, (unsigned long long)N);
-  for (uint64_t i = 0; i < N; ++i)
-    if (t1[i] >> RP_T_BITS) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: t1[%llu] = %u, times must be below 2^20", who, (unsigned long long)i, t1[i]);
   if (n_recs == 0 || N == 0) {
     rp_empty(O, n_recs);
     return SHZ_OK;
   }
-  SHZ_HIP(ctx, hipSetDevice(ctx->device));
-  void *d_key = nullptr, *d_t1 = nullptr;
-  if (hipMalloc(&d_key, N * 4) != hipSuccess || hipMalloc(&d_t1, N * 4) != hipSuccess) {
-    (void)hipGetLastError();
-    if (d_key) (void)hipFree(d_key);
-    SHZ_FAIL(ctx, SHZ_E_NOMEM, "%s: hipMalloc(2 x %llu) failed", who, (unsigned long long)(N * 4));
-  }
-  int32_t rc = SHZ_OK;
-  if (shz_memcpy(ctx, d_key, key32, N * 4, hipMemcpyHostToDevice) != hipSuccess ||
-      shz_memcpy(ctx, d_t1, t1, N * 4, hipMemcpyHostToDevice) != hipSuccess) {
-    ctx->err = "shz_repeats_hashes: copy of the columns failed";
-    rc = SHZ_E_HIP;
-  }
-  if (rc == SHZ_OK)
-    rc = rp_core(ctx, who, (const uint32_t*)d_key, (const uint32_t*)d_t1, hash_off, rec_clip0, n_recs, P, O, nullptr, nullptr);
-  (void)hipStreamSynchronize(ctx->stream);   // (a refused call may have queued work that reads the columns)
-  (void)hipFree(d_key);
-  (void)hipFree(d_t1);
-  return rc;
+  rp_columns C(ctx);
+  SHZ_TRY(C.upload(who, key32, t1, N));
+  return rp_core(ctx, who, (const uint32_t*)C.key, (const uint32_t*)C.t1, hash_off, rec_clip0, n_recs, P, O, nullptr, nullptr);
 }
 
 extern "C" int32_t shz_repeats_batch(shz_ctx* ctx, const int16_t* pcm, const uint64_t* clip_off, uint32_t n_clips,
@@ -561,33 +685,373 @@ extern "C" int32_t shz_repeats_batch(shz_ctx* ctx, const int16_t* pcm, const uin
   SHZ_TRY(rp_check_recs(ctx, who, n_clips, rec_clip0, n_recs));
   if (n_recs) SHZ_TRY(shz_check_clip_off(ctx, clip_off, n_clips));
   // (nothing is refused behind this line without a launch: the first write)
-  if (ms_extract) *ms_extract = 0.f;
-  if (ms_pairs) *ms_pairs = 0.f;
-  if (ms_cells) *ms_cells = 0.f;
+  rp_times T(ms_extract, ms_pairs, ms_cells);
   if (n_recs == 0) {
     rp_empty(O, 0);
     return SHZ_OK;
   }
-  SHZ_HIP(ctx, hipSetDevice(ctx->device));
-  const bool timed = ms_extract || ms_pairs || ms_cells;
+  std::vector<uint64_t> hash_off((size_t)n_clips + 1, 0);
+  const uint32_t *d_key = nullptr, *d_t1 = nullptr;
+  SHZ_TRY(rp_extract(ctx, who, pcm, clip_off, n_clips, fs, amp_min, fan_value, flags, T, hash_off.data(), &d_key, &d_t1));
+  return rp_core(ctx, who, d_key, d_t1, hash_off.data(), rec_clip0, n_recs, P, O, T.pairs(), T.cells());
+}
+
+// ---- content shared between two recordings: the join over a list of jobs (a, b) -----------------------------
+// The elements, the runs and the recordings' borders are the self-join's (rp_elements).  Job j owns one ITEM per unique element
+// of its recording a; an item's partners are the elements of b with its key and lag_lo <= t_b - t_a <= lag_hi, a range of b's
+// run of that key.  Pair key: job_in_slice << 41 | (lag + 2^20) << 20 | t_a; from there on the cell stage is the self-join's
+// with a lag field of 21 bits, and the lag leaves the library biased by SHZ_SHARED_LAG_BIAS
+#define SH_MAX_JOBS 4096u
+#define SH_LAG_BITS 21
+
+struct sh_params {
+  int32_t lag_lo, lag_hi;
+  uint32_t max_run, cell_shift, min_cell_pairs;
+};
+struct sh_out {
+  uint64_t* cell_off;
+  uint32_t *cell_lag, *cell_block, *cell_pairs, *cell_first, *cell_last, *rec_hashes, *job_skipped_keys;
+  uint64_t *job_pairs, *job_skipped_rows, cap_cells, *count;
+};
+
+// Item i belongs to the last job j with item_off[j] <= i (jobs without items share their successor's offset and are never that
+// one) and is element el = rec_start[a] + i - item_off[j].  b's run of the key: the elements x of [rec_start[b], rec_start[b + 1])
+// with U[x] >> 20 == b << 32 | key32, by a lower and an upper bound.  A key that b lacks counts 0; one with more than max_run
+// times in a or in b is a stop hash: 0, and a's run head counts the key and the rows of both runs; otherwise the partners are
+// the entries of b's run with t in [t_a + lag_lo, t_a + lag_hi] cut to [0, 2^20 - 1] -- the times of a run ascend strictly --
+// as [lo[i], lo[i] + cnt[i])
+__global__ __launch_bounds__(RP_THREADS) void sh_count_kernel(const uint64_t* __restrict__ U, const uint32_t* __restrict__ head,
+                                                              const uint32_t* __restrict__ pos, const uint32_t* __restrict__ run_start,
+                                                              const uint32_t* __restrict__ rec_start, const uint32_t* __restrict__ item_off,
+                                                              const uint32_t* __restrict__ job_a, const uint32_t* __restrict__ job_b,
+                                                              uint32_t n_jobs, uint32_t n_items, sh_params P, uint64_t* __restrict__ cnt,
+                                                              uint32_t* __restrict__ lo_out, uint32_t* __restrict__ el_out,
+                                                              uint32_t* __restrict__ skip_keys, unsigned long long* __restrict__ skip_rows) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_items) return;
+  uint32_t j = 0, jh = n_jobs;
+  while (jh - j > 1) {
+    const uint32_t mid = j + ((jh - j) >> 1);
+    if (item_off[mid] <= i) j = mid; else jh = mid;
+  }
+  const uint32_t b = job_b[j], el = rec_start[job_a[j]] + (i - item_off[j]);
+  const uint64_t key = U[el];
+  const uint64_t want = ((uint64_t)b << 32) | (uint32_t)(key >> RP_T_BITS);
+  const uint32_t b1 = rec_start[b + 1];
+  uint32_t l = rec_start[b], r = b1;   // first x of b with U[x] >> 20 >= want
+  while (l < r) {
+    const uint32_t mid = l + ((r - l) >> 1);
+    if ((U[mid] >> RP_T_BITS) < want) l = mid + 1; else r = mid;
+  }
+  const uint32_t rb = l;
+  r = b1;                              // first x with U[x] >> 20 > want
+  while (l < r) {
+    const uint32_t mid = l + ((r - l) >> 1);
+    if ((U[mid] >> RP_T_BITS) <= want) l = mid + 1; else r = mid;
+  }
+  const uint32_t re = l, m_b = re - rb;
+  uint32_t first = 0, n = 0;
+  if (m_b) {
+    const uint32_t h = head[el], id = pos[el] + h - 1, m_a = run_start[id + 1] - run_start[id];
+    if (m_a > P.max_run || m_b > P.max_run) {
+      if (h) {
+        atomicAdd(&skip_keys[j], 1u);
+        atomicAdd(&skip_rows[j], (unsigned long long)m_a + m_b);
+      }
+    } else {
+      const int32_t t = (int32_t)((uint32_t)key & RP_T_MASK);
+      int32_t t_lo = t + P.lag_lo, t_hi = t + P.lag_hi;   // (|lag| < 2^20: no overflow)
+      if (t_hi >= 0 && t_lo <= (int32_t)RP_T_MASK) {
+        t_lo = max(t_lo, 0);
+        t_hi = min(t_hi, (int32_t)RP_T_MASK);
+        l = rb, r = re;                // first x with t_x >= t_lo
+        while (l < r) {
+          const uint32_t mid = l + ((r - l) >> 1);
+          if (((uint32_t)U[mid] & RP_T_MASK) < (uint32_t)t_lo) l = mid + 1; else r = mid;
+        }
+        first = l;
+        r = re;                        // first x with t_x > t_hi
+        while (l < r) {
+          const uint32_t mid = l + ((r - l) >> 1);
+          if (((uint32_t)U[mid] & RP_T_MASK) <= (uint32_t)t_hi) l = mid + 1; else r = mid;
+        }
+        n = l - first;
+      }
+    }
+  }
+  cnt[i] = n;
+  lo_out[i] = first;
+  el_out[i] = el;
+}
+
+// rp_expand_kernel over items: the pairs [P0, P0 + np) of the items [x0, x1), which are those of the jobs [j0, j1), go to
+// out[0 .. np).  The block finds the owner items of its first and last pair and their jobs; every lane searches its pair's owner
+// between the two items and the owner's job between the two jobs
+__global__ __launch_bounds__(RP_THREADS) void sh_expand_kernel(const uint64_t* __restrict__ U, const uint64_t* __restrict__ poff,
+                                                               const uint32_t* __restrict__ lo, const uint32_t* __restrict__ el,
+                                                               const uint32_t* __restrict__ item_off, uint32_t x0, uint32_t x1,
+                                                               uint64_t P0, uint64_t np, uint32_t tile, uint32_t j0, uint32_t j1,
+                                                               uint64_t* __restrict__ out) {
+  const uint64_t base = (uint64_t)blockIdx.x * tile;
+  if (base >= np) return;
+  const uint64_t end = min(base + tile, np);
+  uint32_t xA, xB, jA, jB;
+  {
+    const uint64_t gA = P0 + base, gB = P0 + end - 1;
+    uint32_t l = x0, h = x1;
+    while (h - l > 1) {
+      const uint32_t mid = l + ((h - l) >> 1);
+      if (poff[mid] <= gA) l = mid; else h = mid;
+    }
+    xA = l;
+    h = x1;
+    while (h - l > 1) {
+      const uint32_t mid = l + ((h - l) >> 1);
+      if (poff[mid] <= gB) l = mid; else h = mid;
+    }
+    xB = l;
+    l = j0, h = j1;
+    while (h - l > 1) {
+      const uint32_t mid = l + ((h - l) >> 1);
+      if (item_off[mid] <= xA) l = mid; else h = mid;
+    }
+    jA = l;
+    h = j1;
+    while (h - l > 1) {
+      const uint32_t mid = l + ((h - l) >> 1);
+      if (item_off[mid] <= xB) l = mid; else h = mid;
+    }
+    jB = l;
+  }
+  for (uint64_t p = base + threadIdx.x; p < end; p += blockDim.x) {
+    const uint64_t g = P0 + p;
+    uint32_t l = xA, h = xB + 1;
+    while (h - l > 1) {
+      const uint32_t mid = l + ((h - l) >> 1);
+      if (poff[mid] <= g) l = mid; else h = mid;
+    }
+    uint32_t j = jA, jh = jB + 1;
+    while (jh - j > 1) {
+      const uint32_t mid = j + ((jh - j) >> 1);
+      if (item_off[mid] <= l) j = mid; else jh = mid;
+    }
+    const uint32_t ta = (uint32_t)U[el[l]] & RP_T_MASK, tb = (uint32_t)U[lo[l] + (uint32_t)(g - poff[l])] & RP_T_MASK;
+    out[p] = ((uint64_t)(j - j0) << (RP_T_BITS + SH_LAG_BITS)) | ((uint64_t)(tb + SHZ_SHARED_LAG_BIAS - ta) << RP_T_BITS) | ta;
+  }
+}
+
+static int32_t sh_check(shz_ctx* ctx, const char* who, const sh_params& P, const sh_out& O, const uint32_t* job_a, const uint32_t* job_b,
+                        uint32_t n_jobs, uint32_t n_recs) {
+  if (!O.count || !O.cell_off || !O.rec_hashes || !O.job_pairs || !O.job_skipped_keys || !O.job_skipped_rows)
+    SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: count, cell_off, rec_hashes or a job_* array is NULL", who);
+  if (O.cap_cells && (!O.cell_lag || !O.cell_block || !O.cell_pairs || !O.cell_first || !O.cell_last))
+    SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: NULL cell array with room for %llu cells", who, (unsigned long long)O.cap_cells);
+  const int32_t most = (int32_t)RP_T_MASK;
+  if (P.lag_lo < -most || P.lag_hi > most)
+    SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: the lag window [%d, %d] must lie in [-(2^20 - 1), 2^20 - 1]", who, P.lag_lo, P.lag_hi);
+  if (P.lag_hi < P.lag_lo) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: lag_hi %d is below lag_lo %d", who, P.lag_hi, P.lag_lo);
+  SHZ_TRY(rp_check_knobs(ctx, who, P.max_run, P.cell_shift, P.min_cell_pairs));
+  if (n_jobs > SH_MAX_JOBS) SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "%s: %u jobs in one call, at most %u", who, n_jobs, SH_MAX_JOBS);
+  if (n_jobs && (!job_a || !job_b)) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: NULL job list with %u jobs", who, n_jobs);
+  for (uint32_t j = 0; j < n_jobs; ++j) {
+    if (job_a[j] >= n_recs || job_b[j] >= n_recs)
+      SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: job %u names the recordings %u and %u of %u", who, j, job_a[j], job_b[j], n_recs);
+    if (job_a[j] == job_b[j])
+      SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: job %u joins recording %u with itself (that is shz_repeats_*)", who, j, job_a[j]);
+  }
+  return SHZ_OK;
+}
+static void sh_empty(const sh_out& O, uint32_t n_recs, uint32_t n_jobs) {
+  *O.count = 0;
+  for (uint32_t j = 0; j <= n_jobs; ++j) O.cell_off[j] = 0;
+  for (uint32_t r = 0; r < n_recs; ++r) O.rec_hashes[r] = 0;
+  for (uint32_t j = 0; j < n_jobs; ++j) {
+    O.job_skipped_keys[j] = 0;
+    O.job_pairs[j] = O.job_skipped_rows[j] = 0;
+  }
+}
+
+// The core on device columns, as rp_core: everything is checked (sh_check, rp_check_recs), the outputs are written when the call
+// ends with SHZ_OK or SHZ_E_CAPACITY
+static int32_t sh_core(shz_ctx* ctx, const char* who, const uint32_t* d_key32, const uint32_t* d_t1, const uint64_t* hash_off,
+                       const uint32_t* rec_clip0, uint32_t n_recs, const uint32_t* job_a, const uint32_t* job_b, uint32_t n_jobs,
+                       const sh_params& P, const sh_out& O, float* ms_pairs, float* ms_cells) {
+  const uint64_t N = n_recs ? hash_off[rec_clip0[n_recs]] : 0;
+  if (N == 0) {
+    sh_empty(O, n_recs, n_jobs);
+    return SHZ_OK;
+  }
+  const bool small = (ctx->debug & SHZ_DEBUG_REPEAT_SMALL_SLICES) != 0, timed = ms_pairs || ms_cells;
+  const uint32_t bs = small ? RP_SMALL : RP_THREADS, tile = small ? RP_SMALL : RP_TILE;
+  hipStream_t st = ctx->stream;
+  float pairs_ms = 0.f, cells_ms = 0.f;
   if (timed) {
     for (hipEvent_t& e : ctx->rp_ev)
       if (!e) SHZ_HIP(ctx, hipEventCreate(&e));
-    SHZ_HIP(ctx, hipEventRecord(ctx->rp_ev[0], ctx->stream));
+    SHZ_HIP(ctx, hipEventRecord(ctx->rp_ev[0], st));
+  }
+  // the block of the recordings and jobs: tot[4] | rec_off | job_po | skip_rows (u64) | rec_start | item_off | job_a | job_b |
+  // skip_keys (u32).  rec_off and the jobs go up, item_off follows once the borders are known, the rest comes back in one copy
+  const uint64_t nr1 = (uint64_t)n_recs + 1, nj1 = (uint64_t)n_jobs + 1;
+  const uint64_t o_off = 4, o_po = o_off + nr1, o_rows = o_po + nj1, n64 = o_rows + n_jobs;
+  const uint64_t blk_bytes = n64 * 8 + (nr1 + nj1 + 3ull * n_jobs) * 4;
+  std::vector<uint64_t> hblk((size_t)((blk_bytes + 7) / 8), 0);
+  uint32_t *h_rec_start = (uint32_t*)(hblk.data() + n64), *h_item_off = h_rec_start + nr1, *h_job_a = h_item_off + nj1,
+           *h_job_b = h_job_a + n_jobs, *h_skip_keys = h_job_b + n_jobs;
+  for (uint32_t r = 0; r <= n_recs; ++r) hblk[o_off + r] = hash_off[rec_clip0[r]];
+  for (uint32_t j = 0; j < n_jobs; ++j) {
+    h_job_a[j] = job_a[j];
+    h_job_b[j] = job_b[j];
+  }
+  void* d_blk;
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_RP_REC, hblk.size() * 8, &d_blk));
+  uint64_t* d64 = (uint64_t*)d_blk;
+  uint64_t *d_tot = d64, *d_rec_off = d64 + o_off, *d_job_po = d64 + o_po, *d_skip_rows = d64 + o_rows;
+  uint32_t *d_rec_start = (uint32_t*)(d64 + n64), *d_item_off = d_rec_start + nr1, *d_job_a = d_item_off + nj1, *d_job_b = d_job_a + n_jobs,
+           *d_skip_keys = d_job_b + n_jobs;
+  SHZ_HIP(ctx, shz_memcpy(ctx, d_blk, hblk.data(), hblk.size() * 8, hipMemcpyHostToDevice));
+  // 1) .. 3) the elements, as the self-join's
+  rp_elems E;
+  SHZ_TRY(rp_elements(ctx, who, d_key32, d_t1, N, n_recs, d_rec_off, d_tot, d_rec_start, bs, &E));
+  const uint32_t nu = E.nu;
+  // 4) the items: the borders come back (the count kernel's grid needs their total on the host anyway), item_off goes up
+  SHZ_HIP(ctx, shz_memcpy(ctx, h_rec_start, d_rec_start, nr1 * 4, hipMemcpyDeviceToHost));
+  SHZ_HIP(ctx, hipStreamSynchronize(st));
+  if (h_rec_start[0] != 0 || h_rec_start[n_recs] != nu)
+    SHZ_FAIL(ctx, SHZ_E_STATE, "%s: the recordings' borders do not span the %u unique hashes", who, nu);
+  for (uint32_t r = 0; r < n_recs; ++r)
+    if (h_rec_start[r + 1] < h_rec_start[r]) SHZ_FAIL(ctx, SHZ_E_STATE, "%s: the borders of recording %u decrease", who, r);
+  std::vector<uint32_t> rec_start(h_rec_start, h_rec_start + nr1), item_off((size_t)nj1, 0);
+  uint64_t ni64 = 0;
+  for (uint32_t j = 0; j < n_jobs; ++j) {
+    ni64 += rec_start[job_a[j] + 1] - rec_start[job_a[j]];
+    if (ni64 >> 32)
+      SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "%s: the jobs up to %u have %llu items (unique hashes of their first recordings), a call holds 2^32 - 1",
+               who, j, (unsigned long long)ni64);
+    item_off[j + 1] = (uint32_t)ni64;
+  }
+  const uint32_t ni = (uint32_t)ni64;
+  // 5) count, scan, the jobs' numbers
+  void *d_lo = nullptr, *d_el = nullptr, *d_cnt, *d_poff = nullptr;
+  if (ni) {
+    memcpy(h_item_off, item_off.data(), nj1 * 4);
+    SHZ_HIP(ctx, shz_memcpy(ctx, d_item_off, h_item_off, nj1 * 4, hipMemcpyHostToDevice));
+    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_RP_LO, (uint64_t)ni * 4, &d_lo));
+    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SH_EL, (uint64_t)ni * 4, &d_el));
+    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_RP_CNT, (uint64_t)ni * 8, &d_cnt));
+    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_RP_POFF, ((uint64_t)ni + 1) * 8, &d_poff));
+    hipLaunchKernelGGL(sh_count_kernel, dim3(rp_grid(ni, bs)), dim3(bs), 0, st, E.U, E.head, E.pos, E.run_start, (const uint32_t*)d_rec_start,
+                       (const uint32_t*)d_item_off, (const uint32_t*)d_job_a, (const uint32_t*)d_job_b, n_jobs, ni, P, (uint64_t*)d_cnt,
+                       (uint32_t*)d_lo, (uint32_t*)d_el, d_skip_keys, (unsigned long long*)d_skip_rows);
+    SHZ_HIP(ctx, hipGetLastError());
+    SHZ_TRY(shz_scan_u64(ctx, (const uint64_t*)d_cnt, (uint64_t*)d_poff, ni, (uint64_t*)d_poff + ni));
+    hipLaunchKernelGGL(rp_rec_pairs_kernel, dim3(rp_grid(nj1, bs)), dim3(bs), 0, st, (const uint64_t*)d_poff, (const uint32_t*)d_item_off,
+                       n_jobs, d_job_po);
+    SHZ_HIP(ctx, hipGetLastError());
+    SHZ_HIP(ctx, shz_memcpy(ctx, hblk.data(), d_blk, hblk.size() * 8, hipMemcpyDeviceToHost));
+  }
+  if (timed) SHZ_HIP(ctx, hipEventRecord(ctx->rp_ev[1], st));
+  SHZ_HIP(ctx, hipStreamSynchronize(st));
+  if (timed) {
+    float a = 0.f;
+    SHZ_HIP(ctx, hipEventElapsedTime(&a, ctx->rp_ev[0], ctx->rp_ev[1]));
+    pairs_ms += a;
+  }
+  const uint64_t *job_po = hblk.data() + o_po, *skip_rows = hblk.data() + o_rows;
+  if (job_po[0] != 0) SHZ_FAIL(ctx, SHZ_E_STATE, "%s: %llu pairs in front of the first job", who, (unsigned long long)job_po[0]);
+  for (uint32_t j = 0; j < n_jobs; ++j)
+    if (job_po[j + 1] < job_po[j]) SHZ_FAIL(ctx, SHZ_E_STATE, "%s: the pairs in front of job %u decrease", who, j);
+  // 6) the slices: consecutive whole jobs whose two pair buffers fit 1/8 of the workspace limit
+  const uint64_t max_pairs = std::min<uint64_t>(std::max<uint64_t>(ctx->ws_limit / 8 / 16, 1), 1ull << 31);
+  for (uint32_t j = 0; j < n_jobs; ++j)
+    if (job_po[j + 1] - job_po[j] > max_pairs)
+      SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED,
+               "%s: job %u (recordings %u and %u) has %llu pairs, a slice holds %llu (workspace limit): narrow the lag window [%d, %d] or "
+               "lower max_run (%u)",
+               who, j, job_a[j], job_b[j], (unsigned long long)(job_po[j + 1] - job_po[j]), (unsigned long long)max_pairs, P.lag_lo,
+               P.lag_hi, P.max_run);
+  uint64_t np_max = 0;
+  const std::vector<uint32_t> slices = rp_cut_slices(job_po, n_jobs, max_pairs, small, &np_max);
+  // 7) slice by slice: expand, then the self-join's cell stage on a lag field of 21 bits
+  rp_cells C(ctx, who, "job", n_jobs, O.cap_cells, bs, timed);
+  SHZ_TRY(C.reserve(np_max));
+  for (size_t s = 0; s + 1 < slices.size(); ++s) {
+    const uint32_t j0 = slices[s], j1 = slices[s + 1];
+    const uint64_t P0 = job_po[j0], np64 = job_po[j1] - P0;
+    if (np64 == 0) continue;
+    const uint32_t np = (uint32_t)np64;   // (<= 2^31)
+    if (timed) SHZ_HIP(ctx, hipEventRecord(ctx->rp_ev[0], st));
+    hipLaunchKernelGGL(sh_expand_kernel, dim3(rp_grid(np, tile)), dim3(bs), 0, st, E.U, (const uint64_t*)d_poff, (const uint32_t*)d_lo,
+                       (const uint32_t*)d_el, (const uint32_t*)d_item_off, item_off[j0], item_off[j1], P0, np64, tile, j0, j1, C.ka);
+    SHZ_HIP(ctx, hipGetLastError());
+    SHZ_TRY(C.slice(d_tot, np, P.cell_shift, P.min_cell_pairs, SH_LAG_BITS, j0, j1, &pairs_ms, &cells_ms));
+  }
+  // 8) the outputs
+  for (uint32_t r = 0; r < n_recs; ++r) O.rec_hashes[r] = rec_start[r + 1] - rec_start[r];
+  for (uint32_t j = 0; j < n_jobs; ++j) {
+    O.job_pairs[j] = job_po[j + 1] - job_po[j];
+    O.job_skipped_keys[j] = h_skip_keys[j];
+    O.job_skipped_rows[j] = skip_rows[j];
+  }
+  if (ms_pairs) *ms_pairs = pairs_ms;
+  if (ms_cells) *ms_cells = cells_ms;
+  return C.copy_out(O.cell_off, O.cell_lag, O.cell_block, O.cell_pairs, O.cell_first, O.cell_last, O.count);
+}
+
+extern "C" int32_t shz_shared_hashes(shz_ctx* ctx, const uint32_t* key32, const uint32_t* t1, const uint64_t* hash_off, uint32_t n_clips,
+                                     const uint32_t* rec_clip0, uint32_t n_recs, const uint32_t* job_a, const uint32_t* job_b,
+                                     uint32_t n_jobs, int32_t lag_lo, int32_t lag_hi, uint32_t max_run, uint32_t cell_shift,
+                                     uint32_t min_cell_pairs, uint32_t flags, uint64_t* cell_off, uint32_t* cell_lag, uint32_t* cell_block,
+                                     uint32_t* cell_pairs, uint32_t* cell_first, uint32_t* cell_last, uint32_t* rec_hashes,
+                                     uint64_t* job_pairs, uint32_t* job_skipped_keys, uint64_t* job_skipped_rows, uint64_t cap_cells,
+                                     uint64_t* count) {
+  const char* who = "shz_shared_hashes";
+  if (!ctx) return SHZ_E_INVALID;
+  const sh_params P{lag_lo, lag_hi, max_run, cell_shift, min_cell_pairs};
+  const sh_out O{cell_off, cell_lag, cell_block, cell_pairs, cell_first, cell_last, rec_hashes, job_skipped_keys, job_pairs,
+                 job_skipped_rows, cap_cells, count};
+  if (flags) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: flags must be 0", who);
+  SHZ_TRY(sh_check(ctx, who, P, O, job_a, job_b, n_jobs, n_recs));
+  SHZ_TRY(rp_check_recs(ctx, who, n_clips, rec_clip0, n_recs));
+  SHZ_TRY(rp_check_columns(ctx, who, key32, t1, hash_off, n_clips));
+  const uint64_t N = hash_off[n_clips];
+  if (n_recs == 0 || N == 0) {
+    sh_empty(O, n_recs, n_jobs);
+    return SHZ_OK;
+  }
+  rp_columns C(ctx);
+  SHZ_TRY(C.upload(who, key32, t1, N));
+  return sh_core(ctx, who, (const uint32_t*)C.key, (const uint32_t*)C.t1, hash_off, rec_clip0, n_recs, job_a, job_b, n_jobs, P, O, nullptr,
+                 nullptr);
+}
+
+extern "C" int32_t shz_shared_batch(shz_ctx* ctx, const int16_t* pcm, const uint64_t* clip_off, uint32_t n_clips, const uint32_t* rec_clip0,
+                                    uint32_t n_recs, uint32_t fs, double amp_min, uint32_t fan_value, const uint32_t* job_a,
+                                    const uint32_t* job_b, uint32_t n_jobs, int32_t lag_lo, int32_t lag_hi, uint32_t max_run,
+                                    uint32_t cell_shift, uint32_t min_cell_pairs, uint32_t flags, uint64_t* cell_off, uint32_t* cell_lag,
+                                    uint32_t* cell_block, uint32_t* cell_pairs, uint32_t* cell_first, uint32_t* cell_last,
+                                    uint32_t* rec_hashes, uint64_t* job_pairs, uint32_t* job_skipped_keys, uint64_t* job_skipped_rows,
+                                    uint64_t cap_cells, uint64_t* count, float* ms_extract, float* ms_pairs, float* ms_cells) {
+  const char* who = "shz_shared_batch";
+  if (!ctx) return SHZ_E_INVALID;
+  const sh_params P{lag_lo, lag_hi, max_run, cell_shift, min_cell_pairs};
+  const sh_out O{cell_off, cell_lag, cell_block, cell_pairs, cell_first, cell_last, rec_hashes, job_skipped_keys, job_pairs,
+                 job_skipped_rows, cap_cells, count};
+  if (flags & ~SHZ_PCM_DEVICE) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: flags may hold SHZ_PCM_DEVICE", who);
+  SHZ_TRY(sh_check(ctx, who, P, O, job_a, job_b, n_jobs, n_recs));
+  if (fan_value < 1 || fan_value > 64) SHZ_FAIL(ctx, SHZ_E_INVALID, "fan_value must be in [1,64]");
+  SHZ_TRY(rp_check_recs(ctx, who, n_clips, rec_clip0, n_recs));
+  if (n_recs) SHZ_TRY(shz_check_clip_off(ctx, clip_off, n_clips));
+  // (nothing is refused behind this line without a launch: the first write)
+  rp_times T(ms_extract, ms_pairs, ms_cells);
+  if (n_recs == 0) {
+    sh_empty(O, 0, 0);   // (without recordings sh_check let no job through)
+    return SHZ_OK;
   }
   std::vector<uint64_t> hash_off((size_t)n_clips + 1, 0);
   const uint32_t *d_key = nullptr, *d_t1 = nullptr;
-  SHZ_TRY(shz_extract_owned(ctx, who, pcm, clip_off, n_clips, fs, amp_min, fan_value, flags & SHZ_PCM_DEVICE, hash_off.data(), &d_key,
-                            &d_t1));
-  if (timed) {
-    SHZ_HIP(ctx, hipEventRecord(ctx->rp_ev[1], ctx->stream));
-    SHZ_HIP(ctx, hipEventSynchronize(ctx->rp_ev[1]));
-    if (ms_extract) SHZ_HIP(ctx, hipEventElapsedTime(ms_extract, ctx->rp_ev[0], ctx->rp_ev[1]));
-  }
-  if (hash_off[n_clips] >= (1ull << 32)) SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "%s: %llu hashes", who, (unsigned long long)hash_off[n_clips]);
-  float dummy_a = 0.f, dummy_b = 0.f;
-  return rp_core(ctx, who, d_key, d_t1, hash_off.data(), rec_clip0, n_recs, P, O, timed ? (ms_pairs ? ms_pairs : &dummy_a) : nullptr,
-                 timed ? (ms_cells ? ms_cells : &dummy_b) : nullptr);
+  SHZ_TRY(rp_extract(ctx, who, pcm, clip_off, n_clips, fs, amp_min, fan_value, flags, T, hash_off.data(), &d_key, &d_t1));
+  return sh_core(ctx, who, d_key, d_t1, hash_off.data(), rec_clip0, n_recs, job_a, job_b, n_jobs, P, O, T.pairs(), T.cells());
 }
 
 // ---- the fold: cells -> repeats, on the host ----------------------------------------------------------------------------------
