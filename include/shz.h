@@ -1383,6 +1383,59 @@ int32_t shz_shared_batch(shz_ctx* ctx, const int16_t* pcm, const uint64_t* clip_
                          uint32_t* rec_hashes, uint64_t* job_pairs, uint32_t* job_skipped_keys, uint64_t* job_skipped_rows,
                          uint64_t cap_cells, uint64_t* count, float* ms_extract, float* ms_pairs, float* ms_cells);
 
+/* ---- ALTERED content shared between recordings (new): the join at a table of warps ------------------------------------------
+ * Station B pitches a song up 3 % that station A plays straight; the night re-run of a show comes off a drifting deck; a 25/24
+ * video transfer of a tape is compared with the tape.  No catalogue row stands behind either side, and one per cent of speed
+ * already empties the plain join (an exact (f1, f2, dt) key).  So the join runs at a table of warps (DESIGN.md 3.7r;
+ * tests/shared_warp_twin.py is the definition in Python).  All quantities are integers, in frames at the ctx's hop.
+ * WARPS: (tempo_q16[v], pitch_q16[v]), v < n_warps, as shz_warp_pair_hash_tf takes them.
+ * HASHES: H_r as in shz_shared_*, formed from r's PEAKS: the entries of one clip are the pairs of its peak list.  H_{r,v}: the
+ * same over the peak lists warped by warp v -- exactly the maps, the dropped peaks and the order of shz_warp_pair_hash_tf.  At
+ * (65536, 65536) H_{r,v} = H_r.  rec_hashes[r] = |H_r|.
+ * JOBS: job j = (job_a[j], job_b[j], job_v[j], job_lag_lo[j], job_lag_hi[j]): what of recording a, played tempo / 65536 times as
+ * fast and sounding pitch / 65536 times as high as b's copy, airs in b.  a == b is allowed -- the warped repeat inside one
+ * recording; the caller keeps the trivial lags out with the window.  Every job has a window of its own.
+ * PAIRS, stop hashes, CELLS, their order, the bias of cell_lag and the capacity idiom: those of shz_shared_*, with H_{a,v} in
+ * the place of H_a, H_b plain and the job's window.  t is a's WARPED time t'_a, lag = t_b - t'_a, block = t'_a >> cell_shift.
+ * job_hashes[j] = |H_{a,v}|.
+ * The chain, all on the ctx's stream: the peaks of every clip once; ONE warp pass in the job form over every
+ * clip at (65536, 65536) and the clips of every distinct (a, v) some job names -- ten jobs that name one (a, v) warp it once
+ * --, whole peak ranges; the columns go to the join of shz_shared_* as VIRTUAL recordings, r for the plain ones and n_recs + k
+ * for the k-th distinct (a, v), with (virtual(a, v), b) as its job; the count kernel reads the window of its job.  No hash
+ * leaves the device.  The warp pass is not sliced.
+ * Refused before anything is launched, nothing written (SHZ_E_INVALID): what shz_shared_* refuses except a == b; what
+ * shz_warp_pair_hash_tf refuses about the table (n_warps in [1, 1024], factors in [32768, 131072]); a job_v >= n_warps; a NULL
+ * job array with n_jobs > 0; a window of a job outside [-(2^20 - 1), 2^20 - 1] or with lag_hi < lag_lo (the message names the
+ * job).  SHZ_E_UNSUPPORTED, before any launch where it depends on the inputs alone: more than 4,096 jobs; n_recs + distinct (a,
+ * v) above 4,096 (a warped recording is a recording of the join); a clip of a whose largest warped time ((frames - 1) t16 +
+ * 32768) >> 16 reaches 2^20 (shz_shared_warps_peaks: its last peak's time in the place of frames - 1); 2^32 or more (peak,
+ * warp) items times (fan_value - 1), hashes or join items; a job that alone exceeds a slice.  n_jobs = 0 or no peaks: SHZ_OK,
+ * no cells, rec_hashes filled.
+ * shz_shared_warps_peaks: HOST peak lists (tests / tools), peak_off[n_clips + 1] from 0; the library copies them into device
+ * buffers it allocates and frees.  Also SHZ_E_INVALID: a t >= 2^20, an f > 2048, peaks of a clip not in (t asc, f asc) order.
+ * flags: 0.
+ * shz_shared_warps_batch: PCM (flags: SHZ_PCM_DEVICE).  ms_extract / ms_warp / ms_pairs / ms_cells (each may be NULL): stream
+ * intervals with the host read-backs of their stage inside them (ms_warp: the job ranges and the CSR of the pass; the others
+ * as shz_shared_batch). */
+int32_t shz_shared_warps_peaks(shz_ctx* ctx, const uint16_t* peak_f, const uint32_t* peak_t, const uint64_t* peak_off,
+                               uint32_t n_clips, const uint32_t* rec_clip0, uint32_t n_recs, uint32_t fan_value,
+                               const uint32_t* tempo_q16, const uint32_t* pitch_q16, uint32_t n_warps, const uint32_t* job_a,
+                               const uint32_t* job_b, const uint32_t* job_v, const int32_t* job_lag_lo, const int32_t* job_lag_hi,
+                               uint32_t n_jobs, uint32_t max_run, uint32_t cell_shift, uint32_t min_cell_pairs, uint32_t flags,
+                               uint64_t* cell_off, uint32_t* cell_lag, uint32_t* cell_block, uint32_t* cell_pairs,
+                               uint32_t* cell_first, uint32_t* cell_last, uint32_t* rec_hashes, uint32_t* job_hashes,
+                               uint64_t* job_pairs, uint32_t* job_skipped_keys, uint64_t* job_skipped_rows, uint64_t cap_cells,
+                               uint64_t* count);
+int32_t shz_shared_warps_batch(shz_ctx* ctx, const int16_t* pcm, const uint64_t* clip_off, uint32_t n_clips,
+                               const uint32_t* rec_clip0, uint32_t n_recs, uint32_t fs, double amp_min, uint32_t fan_value,
+                               const uint32_t* tempo_q16, const uint32_t* pitch_q16, uint32_t n_warps, const uint32_t* job_a,
+                               const uint32_t* job_b, const uint32_t* job_v, const int32_t* job_lag_lo, const int32_t* job_lag_hi,
+                               uint32_t n_jobs, uint32_t max_run, uint32_t cell_shift, uint32_t min_cell_pairs, uint32_t flags,
+                               uint64_t* cell_off, uint32_t* cell_lag, uint32_t* cell_block, uint32_t* cell_pairs,
+                               uint32_t* cell_first, uint32_t* cell_last, uint32_t* rec_hashes, uint32_t* job_hashes,
+                               uint64_t* job_pairs, uint32_t* job_skipped_keys, uint64_t* job_skipped_rows, uint64_t cap_cells,
+                               uint64_t* count, float* ms_extract, float* ms_warp, float* ms_pairs, float* ms_cells);
+
 #ifdef __cplusplus
 }
 #endif

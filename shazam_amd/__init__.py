@@ -392,4 +392,4 @@ from .catalog import find_duplicates, fold_pairs, fold_pairs_warps, match_songs 
 # repeated content inside recordings, no catalogue (csrc/shz_repeat.hip): the lag histogram of a recording against itself
 from .repeats import find_repeats, find_repeats_hashes, occurrences  # noqa: E402,F401
 # content shared between recordings, no catalogue (csrc/shz_repeat.hip, the job form): a signed lag histogram per pair of recordings
-from .shared import find_shared, find_shared_hashes, shared_occurrences  # noqa: E402,F401
+from .shared import cells_fit, find_shared, find_shared_hashes, find_shared_peaks, shared_occurrences  # noqa: E402,F401

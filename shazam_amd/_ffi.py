@@ -238,6 +238,13 @@ SIGNATURES = {
     "shz_shared_batch": (C.c_int32, [vp, vp, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.c_double, C.c_uint32, vp, vp, C.c_uint32,
                                      C.c_int32, C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp,
                                      vp, vp, C.c_uint64, u64p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "shz_shared_warps_peaks": (C.c_int32, [vp, vp, vp, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, vp, vp, C.c_uint32, vp, vp, vp, vp, vp,
+                                           C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp,
+                                           vp, vp, vp, C.c_uint64, u64p]),
+    "shz_shared_warps_batch": (C.c_int32, [vp, vp, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.c_double, C.c_uint32, vp, vp, C.c_uint32,
+                                           vp, vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp,
+                                           vp, vp, vp, vp, vp, vp, vp, C.c_uint64, u64p, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                           C.POINTER(C.c_float), C.POINTER(C.c_float)]),
 }
 
 
@@ -944,6 +951,91 @@ class Context:
         rc, out, n, ms = self.shared_batch_raw(*args, cap_cells)       # (cap_cells None: both calls, checked)
         if rc == E_CAPACITY:
             rc, out, n, ms = self.shared_batch_raw(*args, n)
+        self.check(rc)
+        return out, ms
+
+    # ---- altered content shared between recordings (shz_repeat.hip: the join at a table of warps) ------------------------
+    def _shared_warps_call(self, fn, nr, nj, cap_cells, fill):
+        """_shared_call with job_hashes beside the job_* arrays"""
+        def room(cap):
+            out = {k: np.full(int(cap), fill, np.uint32) for k in CELL_FIELDS}
+            out.update(cell_off=np.full(nj + 1, fill, np.uint64), rec_hashes=np.full(nr, fill, np.uint32),
+                       job_hashes=np.full(nj, fill, np.uint32), job_pairs=np.full(nj, fill, np.uint64),
+                       job_skipped_keys=np.full(nj, fill, np.uint32), job_skipped_rows=np.full(nj, fill, np.uint64))
+            return out
+        return self._cells_call(fn, room, cap_cells, fill)
+
+    @staticmethod
+    def _shared_warps_outs(out, cap):
+        cells = [ptr(out[k]) if cap else None for k in CELL_FIELDS]
+        return [ptr(out["cell_off"]), *cells, ptr(out["rec_hashes"]), ptr(out["job_hashes"]), ptr(out["job_pairs"]),
+                ptr(out["job_skipped_keys"]), ptr(out["job_skipped_rows"])]
+
+    @staticmethod
+    def _warp_jobs(jobs, tempos, pitches):
+        """jobs (a, b, v, lag_lo, lag_hi) -> the five columns of the ABI; the warp table as two uint32 columns"""
+        j = np.asarray(list(jobs), np.int64).reshape(-1, 5)
+        cols = [np.ascontiguousarray(j[:, c], np.uint32) for c in range(3)] + [np.ascontiguousarray(j[:, c], np.int32) for c in (3, 4)]
+        tq, fq = np.ascontiguousarray(tempos, np.uint32), np.ascontiguousarray(pitches, np.uint32)
+        if tq.shape != fq.shape or tq.ndim != 1:
+            raise ValueError("tempos and pitches are two lists of one length: warp v is (tempos[v], pitches[v])")
+        return cols, tq, fq
+
+    def shared_warps_peaks_raw(self, peak_f, peak_t, peak_off, rec_clip0, tempos, pitches, jobs, max_run=64, cell_shift=5,
+                               min_cell_pairs=8, fan_value=5, flags=0, cap_cells=None, fill=0):
+        """One shz_shared_warps_peaks as it is on HOST peak lists: (rc, out, count) -- out as _shared_call plus job_hashes.
+        jobs: (a, b, v, lag_lo, lag_hi) tuples; warp v is (tempos[v], pitches[v]), Q16."""
+        pf, pt = np.ascontiguousarray(peak_f, np.uint16), np.ascontiguousarray(peak_t, np.uint32)
+        po = np.ascontiguousarray(peak_off, np.uint64)
+        rc0 = np.ascontiguousarray(rec_clip0, np.uint32)
+        cols, tq, fq = self._warp_jobs(jobs, tempos, pitches)
+        nc, nr, nj = len(po) - 1, len(rc0) - 1, len(cols[0])
+
+        def fn(out, cap, cnt):
+            return lib().shz_shared_warps_peaks(self.h, ptr(pf), ptr(pt), ptr(po), nc, ptr(rc0), nr, int(fan_value), ptr(tq), ptr(fq),
+                                                len(tq), *[ptr(c) for c in cols], nj, int(max_run), int(cell_shift),
+                                                int(min_cell_pairs), int(flags), *self._shared_warps_outs(out, cap), int(cap),
+                                                C.byref(cnt))
+        return self._shared_warps_call(fn, nr, nj, cap_cells, fill)
+
+    def shared_warps_peaks(self, peak_f, peak_t, peak_off, rec_clip0, tempos, pitches, jobs, max_run=64, cell_shift=5,
+                           min_cell_pairs=8, fan_value=5):
+        """shz_shared_warps_peaks (two calls): the cells of altered content shared between recordings given as peak lists --
+        host columns peak_f / peak_t in (t asc, f asc) order per clip, peak_off their CSR over the clips, recording r = the
+        clips [rec_clip0[r], rec_clip0[r + 1]); jobs a list of (a, b, v, lag_lo, lag_hi): what of recording a, warped by
+        (tempos[v], pitches[v]) (Q16), airs in b at a lag t_b - t'_a in the job's window.  Returns shared_hashes' dict (first,
+        last, block in a's WARPED frames) plus job_hashes."""
+        _, out, _ = self.shared_warps_peaks_raw(peak_f, peak_t, peak_off, rec_clip0, tempos, pitches, jobs, max_run, cell_shift,
+                                                min_cell_pairs, fan_value)
+        return out
+
+    def shared_warps_batch_raw(self, pcm, clip_off, rec_clip0, tempos, pitches, jobs, max_run=64, cell_shift=5, min_cell_pairs=8,
+                               fs=44100, amp_min=10.0, fan_value=5, pcm_device=False, cap_cells=None, fill=0):
+        """One shz_shared_warps_batch as it is: (rc, out, count, ms) -- ms = (extract, warp, pairs, cells) device times of the
+        last call."""
+        co, nc = self._clip_off(clip_off)
+        rc0 = np.ascontiguousarray(rec_clip0, np.uint32)
+        cols, tq, fq = self._warp_jobs(jobs, tempos, pitches)
+        nr, nj = len(rc0) - 1, len(cols[0])
+        ms = [C.c_float(float(np.float32(fill))) for _ in range(4)]
+
+        def fn(out, cap, cnt):
+            return lib().shz_shared_warps_batch(self.h, ptr(pcm), ptr(co), nc, ptr(rc0), nr, int(fs), float(amp_min), int(fan_value),
+                                                ptr(tq), ptr(fq), len(tq), *[ptr(c) for c in cols], nj, int(max_run), int(cell_shift),
+                                                int(min_cell_pairs), PCM_DEVICE if pcm_device else 0,
+                                                *self._shared_warps_outs(out, cap), int(cap), C.byref(cnt), *[C.byref(m) for m in ms])
+        rc, out, n = self._shared_warps_call(fn, nr, nj, cap_cells, fill)
+        return rc, out, n, tuple(float(m.value) for m in ms)
+
+    def shared_warps_batch(self, pcm, clip_off, rec_clip0, tempos, pitches, jobs, max_run=64, cell_shift=5, min_cell_pairs=8,
+                           fs=44100, amp_min=10.0, fan_value=5, pcm_device=False, cap_cells=None):
+        """shz_shared_warps_batch: the peaks of every clip once, one warp pass over every distinct (recording, warp) the jobs
+        name, and the cells of every job in one call, the hashes staying on the device.  cap_cells as repeats_batch.  Returns
+        (out, ms): out as shared_warps_peaks, ms = (extract, warp, pairs, cells) device times."""
+        args = (pcm, clip_off, rec_clip0, tempos, pitches, jobs, max_run, cell_shift, min_cell_pairs, fs, amp_min, fan_value, pcm_device)
+        rc, out, n, ms = self.shared_warps_batch_raw(*args, cap_cells)  # (cap_cells None: both calls, checked)
+        if rc == E_CAPACITY:
+            rc, out, n, ms = self.shared_warps_batch_raw(*args, n)
         self.check(rc)
         return out, ms
 

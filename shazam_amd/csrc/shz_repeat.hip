@@ -21,6 +21,10 @@
 // signed lag: the elements and runs of all recordings once (rp_elements), one item per (job, element of a), the partners of an
 // item in b's run of its key (sh_count_kernel), pairs job << 41 | (lag + 2^20) << 20 | t_a by output tile (sh_expand_kernel),
 // and from there the cell stage above with a lag field of 21 bits (rp_cells).
+//
+// ALTERED shared content (shz_shared_warps_*) is that join at a table of warps: one warp pass in the job form
+// (shz_speed.hip) over every clip as it is and over the clips of every distinct (recording, warp) the jobs name, its columns
+// handed to sh_core as virtual recordings, and a lag window per job in sh_count_kernel.
 #include <algorithm>
 #include <numeric>
 
@@ -719,11 +723,13 @@ struct sh_out {
 // with U[x] >> 20 == b << 32 | key32, by a lower and an upper bound.  A key that b lacks counts 0; one with more than max_run
 // times in a or in b is a stop hash: 0, and a's run head counts the key and the rows of both runs; otherwise the partners are
 // the entries of b's run with t in [t_a + lag_lo, t_a + lag_hi] cut to [0, 2^20 - 1] -- the times of a run ascend strictly --
-// as [lo[i], lo[i] + cnt[i])
+// as [lo[i], lo[i] + cnt[i]).  job_lo / job_hi (both or neither; NULL: the call's window P.lag_lo .. P.lag_hi): a window per job,
+// read once the item knows its job -- the lanes of a wave may hold jobs with different windows, nothing is uniform here
 __global__ __launch_bounds__(RP_THREADS) void sh_count_kernel(const uint64_t* __restrict__ U, const uint32_t* __restrict__ head,
                                                               const uint32_t* __restrict__ pos, const uint32_t* __restrict__ run_start,
                                                               const uint32_t* __restrict__ rec_start, const uint32_t* __restrict__ item_off,
                                                               const uint32_t* __restrict__ job_a, const uint32_t* __restrict__ job_b,
+                                                              const int32_t* __restrict__ job_lo, const int32_t* __restrict__ job_hi,
                                                               uint32_t n_jobs, uint32_t n_items, sh_params P, uint64_t* __restrict__ cnt,
                                                               uint32_t* __restrict__ lo_out, uint32_t* __restrict__ el_out,
                                                               uint32_t* __restrict__ skip_keys, unsigned long long* __restrict__ skip_rows) {
@@ -760,7 +766,7 @@ __global__ __launch_bounds__(RP_THREADS) void sh_count_kernel(const uint64_t* __
       }
     } else {
       const int32_t t = (int32_t)((uint32_t)key & RP_T_MASK);
-      int32_t t_lo = t + P.lag_lo, t_hi = t + P.lag_hi;   // (|lag| < 2^20: no overflow)
+      int32_t t_lo = t + (job_lo ? job_lo[j] : P.lag_lo), t_hi = t + (job_hi ? job_hi[j] : P.lag_hi);   // (|lag| < 2^20: no overflow)
       if (t_hi >= 0 && t_lo <= (int32_t)RP_T_MASK) {
         t_lo = max(t_lo, 0);
         t_hi = min(t_hi, (int32_t)RP_T_MASK);
@@ -872,10 +878,12 @@ static void sh_empty(const sh_out& O, uint32_t n_recs, uint32_t n_jobs) {
 }
 
 // The core on device columns, as rp_core: everything is checked (sh_check, rp_check_recs), the outputs are written when the call
-// ends with SHZ_OK or SHZ_E_CAPACITY
+// ends with SHZ_OK or SHZ_E_CAPACITY.  job_lag_lo / job_lag_hi (host, both or neither; NULL: P's window for every job): the
+// window of every job, checked by the caller
 static int32_t sh_core(shz_ctx* ctx, const char* who, const uint32_t* d_key32, const uint32_t* d_t1, const uint64_t* hash_off,
                        const uint32_t* rec_clip0, uint32_t n_recs, const uint32_t* job_a, const uint32_t* job_b, uint32_t n_jobs,
-                       const sh_params& P, const sh_out& O, float* ms_pairs, float* ms_cells) {
+                       const sh_params& P, const sh_out& O, float* ms_pairs, float* ms_cells, const int32_t* job_lag_lo = nullptr,
+                       const int32_t* job_lag_hi = nullptr) {
   const uint64_t N = n_recs ? hash_off[rec_clip0[n_recs]] : 0;
   if (N == 0) {
     sh_empty(O, n_recs, n_jobs);
@@ -891,10 +899,12 @@ static int32_t sh_core(shz_ctx* ctx, const char* who, const uint32_t* d_key32, c
     SHZ_HIP(ctx, hipEventRecord(ctx->rp_ev[0], st));
   }
   // the block of the recordings and jobs: tot[4] | rec_off | job_po | skip_rows (u64) | rec_start | item_off | job_a | job_b |
-  // skip_keys (u32).  rec_off and the jobs go up, item_off follows once the borders are known, the rest comes back in one copy
+  // skip_keys (u32) | with a window per job: lag_lo | lag_hi (i32).  rec_off and the jobs go up, item_off follows once the borders
+  // are known, the rest comes back in one copy
+  const bool windows = job_lag_lo && job_lag_hi;
   const uint64_t nr1 = (uint64_t)n_recs + 1, nj1 = (uint64_t)n_jobs + 1;
   const uint64_t o_off = 4, o_po = o_off + nr1, o_rows = o_po + nj1, n64 = o_rows + n_jobs;
-  const uint64_t blk_bytes = n64 * 8 + (nr1 + nj1 + 3ull * n_jobs) * 4;
+  const uint64_t blk_bytes = n64 * 8 + (nr1 + nj1 + (windows ? 5ull : 3ull) * n_jobs) * 4;
   std::vector<uint64_t> hblk((size_t)((blk_bytes + 7) / 8), 0);
   uint32_t *h_rec_start = (uint32_t*)(hblk.data() + n64), *h_item_off = h_rec_start + nr1, *h_job_a = h_item_off + nj1,
            *h_job_b = h_job_a + n_jobs, *h_skip_keys = h_job_b + n_jobs;
@@ -903,12 +913,17 @@ static int32_t sh_core(shz_ctx* ctx, const char* who, const uint32_t* d_key32, c
     h_job_a[j] = job_a[j];
     h_job_b[j] = job_b[j];
   }
+  if (windows) {
+    memcpy(h_skip_keys + n_jobs, job_lag_lo, (size_t)n_jobs * 4);
+    memcpy(h_skip_keys + 2 * (size_t)n_jobs, job_lag_hi, (size_t)n_jobs * 4);
+  }
   void* d_blk;
   SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_RP_REC, hblk.size() * 8, &d_blk));
   uint64_t* d64 = (uint64_t*)d_blk;
   uint64_t *d_tot = d64, *d_rec_off = d64 + o_off, *d_job_po = d64 + o_po, *d_skip_rows = d64 + o_rows;
   uint32_t *d_rec_start = (uint32_t*)(d64 + n64), *d_item_off = d_rec_start + nr1, *d_job_a = d_item_off + nj1, *d_job_b = d_job_a + n_jobs,
            *d_skip_keys = d_job_b + n_jobs;
+  const int32_t *d_job_lo = windows ? (const int32_t*)(d_skip_keys + n_jobs) : nullptr, *d_job_hi = windows ? d_job_lo + n_jobs : nullptr;
   SHZ_HIP(ctx, shz_memcpy(ctx, d_blk, hblk.data(), hblk.size() * 8, hipMemcpyHostToDevice));
   // 1) .. 3) the elements, as the self-join's
   rp_elems E;
@@ -941,7 +956,8 @@ static int32_t sh_core(shz_ctx* ctx, const char* who, const uint32_t* d_key32, c
     SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_RP_CNT, (uint64_t)ni * 8, &d_cnt));
     SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_RP_POFF, ((uint64_t)ni + 1) * 8, &d_poff));
     hipLaunchKernelGGL(sh_count_kernel, dim3(rp_grid(ni, bs)), dim3(bs), 0, st, E.U, E.head, E.pos, E.run_start, (const uint32_t*)d_rec_start,
-                       (const uint32_t*)d_item_off, (const uint32_t*)d_job_a, (const uint32_t*)d_job_b, n_jobs, ni, P, (uint64_t*)d_cnt,
+                       (const uint32_t*)d_item_off, (const uint32_t*)d_job_a, (const uint32_t*)d_job_b, d_job_lo, d_job_hi, n_jobs, ni, P,
+                       (uint64_t*)d_cnt,
                        (uint32_t*)d_lo, (uint32_t*)d_el, d_skip_keys, (unsigned long long*)d_skip_rows);
     SHZ_HIP(ctx, hipGetLastError());
     SHZ_TRY(shz_scan_u64(ctx, (const uint64_t*)d_cnt, (uint64_t*)d_poff, ni, (uint64_t*)d_poff + ni));
@@ -968,8 +984,8 @@ static int32_t sh_core(shz_ctx* ctx, const char* who, const uint32_t* d_key32, c
       SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED,
                "%s: job %u (recordings %u and %u) has %llu pairs, a slice holds %llu (workspace limit): narrow the lag window [%d, %d] or "
                "lower max_run (%u)",
-               who, j, job_a[j], job_b[j], (unsigned long long)(job_po[j + 1] - job_po[j]), (unsigned long long)max_pairs, P.lag_lo,
-               P.lag_hi, P.max_run);
+               who, j, job_a[j], job_b[j], (unsigned long long)(job_po[j + 1] - job_po[j]), (unsigned long long)max_pairs,
+               windows ? job_lag_lo[j] : P.lag_lo, windows ? job_lag_hi[j] : P.lag_hi, P.max_run);
   uint64_t np_max = 0;
   const std::vector<uint32_t> slices = rp_cut_slices(job_po, n_jobs, max_pairs, small, &np_max);
   // 7) slice by slice: expand, then the self-join's cell stage on a lag field of 21 bits
@@ -1052,6 +1068,296 @@ extern "C" int32_t shz_shared_batch(shz_ctx* ctx, const int16_t* pcm, const uint
   const uint32_t *d_key = nullptr, *d_t1 = nullptr;
   SHZ_TRY(rp_extract(ctx, who, pcm, clip_off, n_clips, fs, amp_min, fan_value, flags, T, hash_off.data(), &d_key, &d_t1));
   return sh_core(ctx, who, d_key, d_t1, hash_off.data(), rec_clip0, n_recs, job_a, job_b, n_jobs, P, O, T.pairs(), T.cells());
+}
+
+// ---- ALTERED content shared between recordings: the join at a table of warps -----------------------------------
+// Job j = (a, b, v, lag_lo, lag_hi): what of recording a, played tempo[v] / 65536 times as fast and sounding pitch[v] / 65536 times
+// as high as b's copy, airs in b.  Nothing of the join is new: ONE warp pass in the job form (sp_count_jobs / sp_write, DESIGN.md
+// 3.7n) pairs and hashes every clip at (65536, 65536) and the clips of every distinct (a, v) at its warp, whole peak ranges; its
+// CSR over the warp jobs is the CSR of VIRTUAL clips, the plain recordings own the first n_clips of them and the k-th distinct
+// (a, v) owns the next run as virtual recording n_recs + k; sh_core joins (virtual(a, v), b) with the window of its job.  The
+// warped columns lie in SHZ_WS_SP_KEY / _T1, which no stage of the join touches.
+#define SW_W_END (1ull << 40)   // above every warped time: a warp job keeps all peaks of its clip
+
+struct sw_jobs {                // the job list of a call and the table it points into (host)
+  const uint32_t *a, *b, *v;
+  const int32_t *lo, *hi;
+  uint32_t n;
+  const uint32_t *tempo, *pitch;
+  uint32_t n_warps;
+};
+struct sw_plan {
+  std::vector<uint32_t> va_rec, va_warp;   // the distinct (a, v) in the order of their first job
+  std::vector<uint32_t> job_virt;          // the virtual recording n_recs + k of every job
+};
+
+// what both entry points refuse about the outputs, the knobs, the table and the jobs: SHZ_E_INVALID first, then the limits that
+// depend on the counts alone.  P's window is not read
+static int32_t sw_check(shz_ctx* ctx, const char* who, const sh_params& P, const sh_out& O, const uint32_t* job_hashes, const sw_jobs& J,
+                        uint32_t n_recs, uint32_t fan_value) {
+  if (!O.count || !O.cell_off || !O.rec_hashes || !O.job_pairs || !O.job_skipped_keys || !O.job_skipped_rows || !job_hashes)
+    SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: count, cell_off, rec_hashes or a job_* array is NULL", who);
+  if (O.cap_cells && (!O.cell_lag || !O.cell_block || !O.cell_pairs || !O.cell_first || !O.cell_last))
+    SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: NULL cell array with room for %llu cells", who, (unsigned long long)O.cap_cells);
+  SHZ_TRY(rp_check_knobs(ctx, who, P.max_run, P.cell_shift, P.min_cell_pairs));
+  SHZ_TRY(sp_check_ladder(ctx, who, "n_warps", "tempo", J.tempo, "pitch", J.pitch, J.n_warps, fan_value));
+  if (J.n && (!J.a || !J.b || !J.v || !J.lo || !J.hi)) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: NULL job array with %u jobs", who, J.n);
+  const int32_t most = (int32_t)RP_T_MASK;
+  for (uint32_t j = 0; j < J.n && j < SH_MAX_JOBS; ++j) {
+    if (J.a[j] >= n_recs || J.b[j] >= n_recs)
+      SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: job %u names the recordings %u and %u of %u", who, j, J.a[j], J.b[j], n_recs);
+    if (J.v[j] >= J.n_warps) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: job %u names warp %u of %u", who, j, J.v[j], J.n_warps);
+    if (J.lo[j] < -most || J.hi[j] > most)
+      SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: the lag window [%d, %d] of job %u must lie in [-(2^20 - 1), 2^20 - 1]", who, J.lo[j], J.hi[j], j);
+    if (J.hi[j] < J.lo[j]) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: job %u: lag_hi %d is below lag_lo %d", who, j, J.hi[j], J.lo[j]);
+  }
+  if (J.n > SH_MAX_JOBS) SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "%s: %u jobs in one call, at most %u", who, J.n, SH_MAX_JOBS);
+  return SHZ_OK;
+}
+
+// the distinct (a, v) of the jobs; more than 4,096 virtual recordings: SHZ_E_UNSUPPORTED
+static int32_t sw_plan_jobs(shz_ctx* ctx, const char* who, const sw_jobs& J, uint32_t n_recs, sw_plan* L) {
+  std::vector<std::pair<uint64_t, uint32_t>> idx;   // a << 32 | v, sorted, beside its k
+  L->job_virt.resize(J.n);
+  for (uint32_t j = 0; j < J.n; ++j) {
+    const uint64_t key = ((uint64_t)J.a[j] << 32) | J.v[j];
+    auto it = std::lower_bound(idx.begin(), idx.end(), std::make_pair(key, 0u));
+    if (it == idx.end() || it->first != key) {
+      it = idx.insert(it, std::make_pair(key, (uint32_t)L->va_rec.size()));
+      L->va_rec.push_back(J.a[j]);
+      L->va_warp.push_back(J.v[j]);
+    }
+    L->job_virt[j] = n_recs + it->second;
+  }
+  if ((uint64_t)n_recs + L->va_rec.size() > RP_MAX_RECS)
+    SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED,
+             "%s: %u recordings and %llu distinct (recording, warp) pairs in one call, at most %u together (a warped recording "
+             "is a recording of the join)", who, n_recs, (unsigned long long)L->va_rec.size(), RP_MAX_RECS);
+  return SHZ_OK;
+}
+
+// last[c]: the largest frame a peak of clip c can have.  The clips of every distinct (a, v) must stay below 2^20 after the warp
+static int32_t sw_check_times(shz_ctx* ctx, const char* who, const uint64_t* last, const uint8_t* has, const uint32_t* rec_clip0,
+                              const sw_jobs& J, const sw_plan& L) {
+  for (size_t k = 0; k < L.va_rec.size(); ++k) {
+    const uint32_t a = L.va_rec[k], t16 = J.tempo[L.va_warp[k]];
+    for (uint32_t c = rec_clip0[a]; c < rec_clip0[a + 1]; ++c) {
+      if (!has[c]) continue;
+      const uint64_t w = (last[c] * t16 + 32768u) >> 16;
+      if (w >> RP_T_BITS)
+        SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "%s: frame %llu of clip %u (recording %u) lies at %llu at tempo %u / 65536 (warp %u); warped "
+                 "times must be below 2^20", who, (unsigned long long)last[c], c, a, (unsigned long long)w, t16, L.va_warp[k]);
+    }
+  }
+  return SHZ_OK;
+}
+
+static void sw_empty(const sh_out& O, uint32_t* job_hashes, uint32_t n_recs, uint32_t n_jobs) {
+  sh_empty(O, n_recs, n_jobs);
+  for (uint32_t j = 0; j < n_jobs; ++j) job_hashes[j] = 0;
+}
+
+// The core on device peak lists (d_pf / d_pt, peak_off their host CSR from 0 over the clips, at least one peak): everything is
+// checked.  ms_warp (may be NULL) gets the warp pass's stream interval (rp_ev[0] .. rp_ev[1], the read-backs of the job ranges and
+// of the CSR inside it)
+static int32_t sw_core(shz_ctx* ctx, const char* who, const uint16_t* d_pf, const uint32_t* d_pt, const uint64_t* peak_off, uint32_t n_clips,
+                       const uint32_t* rec_clip0, uint32_t n_recs, uint32_t fan_value, const sw_jobs& J, const sw_plan& L, const sh_params& P,
+                       const sh_out& O, uint32_t* job_hashes, float* ms_warp, float* ms_pairs, float* ms_cells) {
+  hipStream_t st = ctx->stream;
+  const uint32_t n_virt = n_recs + (uint32_t)L.va_rec.size();
+  uint64_t n_warped = peak_off[n_clips];   // the (peak, warp) items of the pass, known before it runs
+  for (size_t k = 0; k < L.va_rec.size(); ++k) n_warped += peak_off[rec_clip0[L.va_rec[k] + 1]] - peak_off[rec_clip0[L.va_rec[k]]];
+  if (n_warped * std::max<uint32_t>(fan_value - 1, 1) >= (1ull << 32))
+    SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "%s: %llu (peak, warp) items at fan_value %u in the one warp pass (32-bit offsets): fewer jobs a call",
+             who, (unsigned long long)n_warped, fan_value);
+  // 1) the warp jobs = the virtual clips, and the virtual recordings over them
+  std::vector<sp_job> wj;
+  std::vector<uint32_t> vrec((size_t)n_virt + 1);
+  for (uint32_t c = 0; c < n_clips; ++c) wj.push_back(sp_job{peak_off[c], peak_off[c + 1], 0, SW_W_END, SP_S_ONE, SP_S_ONE});
+  for (uint32_t r = 0; r <= n_recs; ++r) vrec[r] = rec_clip0[r];
+  for (size_t k = 0; k < L.va_rec.size(); ++k) {
+    const uint32_t a = L.va_rec[k], v = L.va_warp[k];
+    for (uint32_t c = rec_clip0[a]; c < rec_clip0[a + 1]; ++c)
+      wj.push_back(sp_job{peak_off[c], peak_off[c + 1], 0, SW_W_END, J.tempo[v], J.pitch[v]});
+    vrec[n_recs + k + 1] = (uint32_t)wj.size();
+  }
+  if (wj.size() >> 31) SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "%s: %llu warped clips in one call", who, (unsigned long long)wj.size());
+  const uint32_t n_wj = (uint32_t)wj.size();
+  // 2) one warp pass over all of them; the hashes stay on the device
+  if (ms_warp) SHZ_HIP(ctx, hipEventRecord(ctx->rp_ev[0], st));
+  std::vector<uint64_t> ho((size_t)n_wj + 1, 0);
+  uint64_t n_items = 0;
+  sp_pass W;
+  SHZ_TRY(sp_count_jobs(ctx, d_pf, d_pt, wj.data(), n_wj, fan_value, &W, ho.data(), &n_items));
+  const uint64_t total = ho[n_wj];
+  if (total >> 32) SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "%s: %llu hashes of %u plain and warped clips, a call holds 2^32 - 1", who,
+                            (unsigned long long)total, n_wj);
+  void *d_key = nullptr, *d_t1 = nullptr;
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SP_KEY, total * 4 + 64, &d_key));
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SP_T1, total * 4 + 64, &d_t1));
+  if (total) SHZ_TRY(sp_write(ctx, W, (uint32_t*)d_key, (uint32_t*)d_t1, total));
+  if (ms_warp) {
+    SHZ_HIP(ctx, hipEventRecord(ctx->rp_ev[1], st));
+    SHZ_HIP(ctx, hipEventSynchronize(ctx->rp_ev[1]));
+    SHZ_HIP(ctx, hipEventElapsedTime(ms_warp, ctx->rp_ev[0], ctx->rp_ev[1]));
+  }
+  // 3) the join of (virtual(a, v), b) at the window of every job
+  std::vector<uint32_t> virt_hashes((size_t)n_virt, 0);
+  sh_out V = O;
+  V.rec_hashes = virt_hashes.data();
+  const int32_t rc = sh_core(ctx, who, (const uint32_t*)d_key, (const uint32_t*)d_t1, ho.data(), vrec.data(), n_virt, L.job_virt.data(), J.b,
+                             J.n, P, V, ms_pairs, ms_cells, J.lo, J.hi);
+  if (rc != SHZ_OK && rc != SHZ_E_CAPACITY) {
+    (void)hipStreamSynchronize(st);   // (a refused join may have queued work that reads the columns)
+    return rc;
+  }
+  for (uint32_t r = 0; r < n_recs; ++r) O.rec_hashes[r] = virt_hashes[r];
+  for (uint32_t j = 0; j < J.n; ++j) job_hashes[j] = virt_hashes[L.job_virt[j]];
+  return rc;
+}
+
+// device copies of N >= 1 host peaks for the length of a call (tests / tools)
+struct sw_peaks {
+  shz_ctx* ctx;
+  void *f = nullptr, *t = nullptr;
+  explicit sw_peaks(shz_ctx* c) : ctx(c) {}
+  int32_t upload(const char* who, const uint16_t* peak_f, const uint32_t* peak_t, uint64_t N) {
+    SHZ_HIP(ctx, hipSetDevice(ctx->device));
+    if (hipMalloc(&f, N * 2 + 64) != hipSuccess || hipMalloc(&t, N * 4 + 64) != hipSuccess) {
+      (void)hipGetLastError();
+      SHZ_FAIL(ctx, SHZ_E_NOMEM, "%s: hipMalloc(%llu + %llu) failed", who, (unsigned long long)(N * 2), (unsigned long long)(N * 4));
+    }
+    if (shz_memcpy(ctx, f, peak_f, N * 2, hipMemcpyHostToDevice) != hipSuccess ||
+        shz_memcpy(ctx, t, peak_t, N * 4, hipMemcpyHostToDevice) != hipSuccess)
+      SHZ_FAIL(ctx, SHZ_E_HIP, "%s: copy of the peaks failed", who);
+    return SHZ_OK;
+  }
+  ~sw_peaks() {
+    if (f || t) (void)hipStreamSynchronize(ctx->stream);
+    if (f) (void)hipFree(f);
+    if (t) (void)hipFree(t);
+  }
+};
+
+extern "C" int32_t shz_shared_warps_peaks(shz_ctx* ctx, const uint16_t* peak_f, const uint32_t* peak_t, const uint64_t* peak_off,
+                                          uint32_t n_clips, const uint32_t* rec_clip0, uint32_t n_recs, uint32_t fan_value,
+                                          const uint32_t* tempo_q16, const uint32_t* pitch_q16, uint32_t n_warps, const uint32_t* job_a,
+                                          const uint32_t* job_b, const uint32_t* job_v, const int32_t* job_lag_lo,
+                                          const int32_t* job_lag_hi, uint32_t n_jobs, uint32_t max_run, uint32_t cell_shift,
+                                          uint32_t min_cell_pairs, uint32_t flags, uint64_t* cell_off, uint32_t* cell_lag,
+                                          uint32_t* cell_block, uint32_t* cell_pairs, uint32_t* cell_first, uint32_t* cell_last,
+                                          uint32_t* rec_hashes, uint32_t* job_hashes, uint64_t* job_pairs, uint32_t* job_skipped_keys,
+                                          uint64_t* job_skipped_rows, uint64_t cap_cells, uint64_t* count) {
+  const char* who = "shz_shared_warps_peaks";
+  if (!ctx) return SHZ_E_INVALID;
+  const sh_params P{0, 0, max_run, cell_shift, min_cell_pairs};
+  const sh_out O{cell_off, cell_lag, cell_block, cell_pairs, cell_first, cell_last, rec_hashes, job_skipped_keys, job_pairs,
+                 job_skipped_rows, cap_cells, count};
+  const sw_jobs J{job_a, job_b, job_v, job_lag_lo, job_lag_hi, n_jobs, tempo_q16, pitch_q16, n_warps};
+  // everything that can be refused is refused before the first launch
+  if (flags) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: flags must be 0", who);
+  SHZ_TRY(sw_check(ctx, who, P, O, job_hashes, J, n_recs, fan_value));
+  SHZ_TRY(rp_check_recs(ctx, who, n_clips, rec_clip0, n_recs));
+  if (!peak_off) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: peak_off is NULL", who);
+  if (peak_off[0] != 0) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: peak_off must start at 0 (it starts at %llu)", who, (unsigned long long)peak_off[0]);
+  for (uint32_t c = 0; c < n_clips; ++c)
+    if (peak_off[c + 1] < peak_off[c]) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: peak_off decreases at clip %u", who, c);
+  const uint64_t N = peak_off[n_clips];
+  if (N && (!peak_f || !peak_t)) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: NULL peak list", who);
+  std::vector<uint64_t> last((size_t)n_clips, 0);
+  std::vector<uint8_t> has((size_t)n_clips, 0);
+  for (uint32_t c = 0; c < n_clips; ++c)
+    for (uint64_t i = peak_off[c]; i < peak_off[c + 1]; ++i) {
+      if (peak_t[i] >> RP_T_BITS)
+        SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: peak %llu has t = %u, times must be below 2^20", who, (unsigned long long)i, peak_t[i]);
+      if (peak_f[i] > SP_F_MAX)
+        SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: peak %llu has f = %u, the spectrogram ends at bin %u", who, (unsigned long long)i, peak_f[i], SP_F_MAX);
+      if (i > peak_off[c] && (peak_t[i] < peak_t[i - 1] || (peak_t[i] == peak_t[i - 1] && peak_f[i] < peak_f[i - 1])))
+        SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: peaks must be in (time asc, freq asc) order inside a clip; peak %llu breaks it", who,
+                 (unsigned long long)i);
+      last[c] = peak_t[i];
+      has[c] = 1;
+    }
+  sw_plan L;
+  SHZ_TRY(sw_plan_jobs(ctx, who, J, n_recs, &L));
+  if (n_recs) SHZ_TRY(sw_check_times(ctx, who, last.data(), has.data(), rec_clip0, J, L));
+  if (n_recs == 0 || N == 0) {
+    sw_empty(O, job_hashes, n_recs, n_jobs);
+    return SHZ_OK;
+  }
+  sw_peaks C(ctx);
+  SHZ_TRY(C.upload(who, peak_f, peak_t, N));
+  return sw_core(ctx, who, (const uint16_t*)C.f, (const uint32_t*)C.t, peak_off, n_clips, rec_clip0, n_recs, fan_value, J, L, P, O, job_hashes,
+                 nullptr, nullptr, nullptr);
+}
+
+extern "C" int32_t shz_shared_warps_batch(shz_ctx* ctx, const int16_t* pcm, const uint64_t* clip_off, uint32_t n_clips,
+                                          const uint32_t* rec_clip0, uint32_t n_recs, uint32_t fs, double amp_min, uint32_t fan_value,
+                                          const uint32_t* tempo_q16, const uint32_t* pitch_q16, uint32_t n_warps, const uint32_t* job_a,
+                                          const uint32_t* job_b, const uint32_t* job_v, const int32_t* job_lag_lo,
+                                          const int32_t* job_lag_hi, uint32_t n_jobs, uint32_t max_run, uint32_t cell_shift,
+                                          uint32_t min_cell_pairs, uint32_t flags, uint64_t* cell_off, uint32_t* cell_lag,
+                                          uint32_t* cell_block, uint32_t* cell_pairs, uint32_t* cell_first, uint32_t* cell_last,
+                                          uint32_t* rec_hashes, uint32_t* job_hashes, uint64_t* job_pairs, uint32_t* job_skipped_keys,
+                                          uint64_t* job_skipped_rows, uint64_t cap_cells, uint64_t* count, float* ms_extract,
+                                          float* ms_warp, float* ms_pairs, float* ms_cells) {
+  const char* who = "shz_shared_warps_batch";
+  if (!ctx) return SHZ_E_INVALID;
+  const sh_params P{0, 0, max_run, cell_shift, min_cell_pairs};
+  const sh_out O{cell_off, cell_lag, cell_block, cell_pairs, cell_first, cell_last, rec_hashes, job_skipped_keys, job_pairs,
+                 job_skipped_rows, cap_cells, count};
+  const sw_jobs J{job_a, job_b, job_v, job_lag_lo, job_lag_hi, n_jobs, tempo_q16, pitch_q16, n_warps};
+  if (flags & ~SHZ_PCM_DEVICE) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: flags may hold SHZ_PCM_DEVICE", who);
+  SHZ_TRY(sw_check(ctx, who, P, O, job_hashes, J, n_recs, fan_value));
+  SHZ_TRY(rp_check_recs(ctx, who, n_clips, rec_clip0, n_recs));
+  if (n_recs) SHZ_TRY(shz_check_clip_off(ctx, clip_off, n_clips));
+  sw_plan L;
+  SHZ_TRY(sw_plan_jobs(ctx, who, J, n_recs, &L));
+  // the frames of every clip bound its peaks' times: the plain side as it is, the warped side at its tempo
+  std::vector<uint64_t> last((size_t)n_clips, 0);
+  std::vector<uint8_t> has((size_t)n_clips, 1);
+  uint64_t all_frames = 0;
+  for (uint32_t c = 0; n_recs && c < n_clips; ++c) {
+    const uint64_t fc = shz_frame_count_hop(clip_off[c + 1] - clip_off[c], ctx->hop);
+    all_frames += fc;
+    last[c] = fc ? fc - 1 : 0;
+    if (last[c] >> RP_T_BITS)
+      SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "%s: clip %u has %llu frames, times must be below 2^20", who, c, (unsigned long long)fc);
+  }
+  if (n_recs) SHZ_TRY(sw_check_times(ctx, who, last.data(), has.data(), rec_clip0, J, L));
+  // (nothing is refused behind this line without a launch: the first write)
+  rp_times T(ms_extract, ms_pairs, ms_cells);
+  if (ms_warp) *ms_warp = 0.f;
+  if (n_recs == 0) {
+    sw_empty(O, job_hashes, 0, 0);   // (without recordings sw_check let no job through)
+    return SHZ_OK;
+  }
+  SHZ_HIP(ctx, hipSetDevice(ctx->device));
+  const bool timed = T.timed || ms_warp;
+  float spare = 0.f;
+  if (timed) {
+    for (hipEvent_t& e : ctx->rp_ev)
+      if (!e) SHZ_HIP(ctx, hipEventCreate(&e));
+    SHZ_HIP(ctx, hipEventRecord(ctx->rp_ev[0], ctx->stream));
+  }
+  std::vector<uint64_t> peak_off((size_t)n_clips + 1, 0);
+  const uint16_t* d_pf = nullptr;
+  const uint32_t* d_pt = nullptr;
+  SHZ_TRY(sp_peaks_owned(ctx, who, pcm, clip_off, n_clips, all_frames, fs, amp_min, flags & SHZ_PCM_DEVICE, peak_off.data(), &d_pf, &d_pt));
+  if (timed) {
+    SHZ_HIP(ctx, hipEventRecord(ctx->rp_ev[1], ctx->stream));
+    SHZ_HIP(ctx, hipEventSynchronize(ctx->rp_ev[1]));
+    if (T.extract) SHZ_HIP(ctx, hipEventElapsedTime(T.extract, ctx->rp_ev[0], ctx->rp_ev[1]));
+  }
+  for (uint32_t c = n_clips; c > 0; --c) peak_off[c] -= peak_off[0];
+  peak_off[0] = 0;
+  if (peak_off[n_clips] == 0) {
+    sw_empty(O, job_hashes, n_recs, n_jobs);
+    return SHZ_OK;
+  }
+  return sw_core(ctx, who, d_pf, d_pt, peak_off.data(), n_clips, rec_clip0, n_recs, fan_value, J, L, P, O, job_hashes,
+                 timed ? (ms_warp ? ms_warp : &spare) : nullptr, timed ? (T.pairs() ? T.pairs() : &spare) : nullptr,
+                 timed ? (T.cells() ? T.cells() : &spare) : nullptr);
 }
 
 // ---- the fold: cells -> repeats, on the host ----------------------------------------------------------------------------------
