@@ -41,6 +41,7 @@ extern "C" {
 #define SHZ_STFT_POWER 8u    /* shz_stft_db: write the PSD itself, not 10*log10 */
 #define SHZ_RESERVE_GATHER 32u /* shz_table_reserve: size the run arena for an all-gathered build (every rank's rows) */
 #define SHZ_RESERVE_WAIT 64u   /* shz_table_reserve: return when the allocations exist (setup outside a timed region) */
+#define SHZ_SCAN_KEEP_MASK 128u /* shz_scan_extents: out_nres holds, on entry, a keep mask of the windows (see there) */
 #define SHZ_MATCH_FULL_SORT 16u /* shz_match_batch: 8-byte votes, full radix sort and record chain (the reference form of
                                   the vote: what the 4-byte votes and the vote tiles must reproduce) */
 
@@ -423,6 +424,10 @@ uint64_t shz_recognize_estimate(uint64_t frames, uint32_t fan_value);
  * 2,048 and a block of the flag, count and cell kernels 64 elements instead of 256, so that tests reach every border with
  * tiny inputs (results do not depend on any of them). */
 #define SHZ_DEBUG_REPEAT_SMALL_SLICES 512u
+/* Test switch of the vote floor (shz_set_vote_floor): a match sub-batch holds at most 3 queries and the histogram kernels'
+ * LDS table 2 queries instead of 32, so that tests reach the sub-batch border, the table's border and the direct global
+ * adds with tiny inputs (results do not depend on the switch). */
+#define SHZ_DEBUG_FLOOR_SMALL 1024u
 int32_t shz_set_debug(shz_ctx* ctx, uint32_t flags);
 /* The vote's tolerance, a setting of the context that holds for its later calls (default 0).  With c[sid][d] the votes of a
  * query per song and offset difference d = db_off - q_off, and S(sid, d) = the sum of c[sid][d .. d + bins]: a song's
@@ -438,6 +443,32 @@ int32_t shz_set_debug(shz_ctx* ctx, uint32_t flags);
  * stays as it was.  A NULL ctx (or NULL bins): SHZ_E_INVALID. */
 int32_t shz_set_vote_tolerance(shz_ctx* ctx, uint32_t bins);
 int32_t shz_get_vote_tolerance(shz_ctx* ctx, uint32_t* bins);
+/* The vote floor, a setting of the context that holds for its later calls (default off): how far chance reaches for a query.
+ * With c(s, d) the votes of a query per song s and offset difference d, and a count c >= 1 put into one of 32 buckets --
+ * c - 1 for c <= 16 (buckets 0 .. 15 are the exact counts 1 .. 16), else min(31, floor(log2 c) + 12) (bucket 16: 17 .. 31,
+ * bucket 17: 32 .. 63, ..., bucket 31: everything from 2^19 up; shz_vote_bucket) -- every query handed to a vote records one
+ * ROW of two exact histograms, 32 + 32 uint32_t:
+ *   bin_hist[b]   the bins (s, d) with c(s, d) >= 1 whose count falls into bucket b -- single bins, whatever the tolerance;
+ *   song_hist[b]  the songs with any vote whose best count falls into bucket b: the value the vote reports as `aligned` for
+ *                 that song (the largest c(s, d); under shz_set_vote_tolerance the best window sum).
+ * A query without hashes or without a match records two zero rows.  sum(song_hist) = the songs with a vote; with topn at
+ * least that, the bucketed `aligned` column is song_hist; where every bin count is <= 16, sum((b + 1) bin_hist[b]) = npairs.
+ * While it is on, the votes go one way, as under a tolerance: 8-byte votes in one pass over a sub-batch, the full sort, the
+ * fold over runs at the tolerance in force, and two histogram kernels over the runs and the fold's records; the rows come
+ * back with the result block (no extra round trip).  Every result array is what it is with the setting off.  Rows are kept
+ * in host memory owned by the context, in the order the queries were handed to the vote (every call listed at
+ * shz_set_vote_tolerance; a caller that skips the vote because nothing is to be looked up records zero rows, so the rows of
+ * a call line up with its result arrays; shz_match_pairs records nothing, shz_pairs_vote records the rows of its votes; a
+ * refused call records nothing).  A ROW COSTS 256 BYTES OF HOST MEMORY UNTIL IT IS TAKEN: take them call by call.
+ * shz_set_vote_floor(on = 0) drops the rows not yet taken.  shz_vote_floor_rows: the rows recorded since the last take.
+ * shz_vote_floor_take copies them, in order, into song_hist / bin_hist ([cap][32] each) and clears the store, *n = their
+ * number; with more rows than cap it returns SHZ_E_CAPACITY with *n = the number needed, copies nothing and clears nothing.
+ * shz_vote_bucket: the bucket of a count (no GPU, no ctx; count 0 or a NULL bucket: SHZ_E_INVALID). */
+int32_t shz_set_vote_floor(shz_ctx* ctx, uint32_t on);
+int32_t shz_get_vote_floor(shz_ctx* ctx, uint32_t* on);
+int32_t shz_vote_floor_rows(shz_ctx* ctx, uint64_t* n);
+int32_t shz_vote_floor_take(shz_ctx* ctx, uint32_t* song_hist, uint32_t* bin_hist, uint64_t cap, uint64_t* n);
+int32_t shz_vote_bucket(uint32_t count, uint32_t* bucket);
 int32_t shz_match_vt_redo(shz_ctx* ctx, uint64_t* count);
 /* A single query of at most 8,192 hashes handed over in host memory has its vote kernels queued before the number of its
  * votes is known (they do nothing when it exceeds 32,768; the call then continues as for any other query): how many
@@ -963,7 +994,11 @@ int32_t shz_scan_zones(const uint32_t* seg_rec, const uint32_t* seg_sid, const i
  * Refused before anything is launched, in this order behind shz_scan_batch's own refusals: d_tol > 31, margin_frames >= 2^20,
  * a NULL seg_count or, with cap_segs > 0, a NULL segment or zone array (SHZ_E_INVALID); then the table as shz_match_extents
  * refuses it (a table offset >= 2^31: SHZ_E_UNSUPPORTED).  Seen on the device, after the scan: a zone longer than 2^20 frames
- * (a query offset of the extent pass; SHZ_E_UNSUPPORTED) -- a play of more than about 13 hours.  flags: shz_scan_batch's. */
+ * (a query offset of the extent pass; SHZ_E_UNSUPPORTED) -- a play of more than about 13 hours.  flags: shz_scan_batch's, and
+ * SHZ_SCAN_KEEP_MASK: out_nres[w] holds ON ENTRY a keep mask of the cap_windows windows (recording-major, as a scan of the
+ * same arguments orders them) -- a window whose entry is 0 has its out_nres cleared behind the scan and before the timeline,
+ * so it is no hit of any segment; its other outputs stay what the scan wrote.  It is how a caller that judged the windows of
+ * an earlier scan by a rule of its own (scan(min_score=)) gets the timeline and the zones of the rest. */
 int32_t shz_scan_extents(shz_ctx* ctx, shz_table* t, const int16_t* pcm, const uint64_t* clip_off, uint32_t n_clips,
                          const uint32_t* rec_clip0, uint32_t n_recs, uint32_t fs, double amp_min, uint32_t fan_value,
                          uint32_t window_frames, uint32_t step_frames, uint32_t topn, uint32_t flags, uint32_t min_aligned,

@@ -288,7 +288,15 @@ def _add_extents(db, results, key32, q_off, query_off, res):
                       "extent_hist": ext["hist"][q, n].copy(), "extent_shift": int(ext["shift"][q])})
 
 
-def _recognize_fused(queries, chans, owner, db, Fs, topn, resample_to=None):
+def _add_floor(results, res):
+    """the "floor" entry of recognize_batch(floor=True): on the first result dict of every query that has one"""
+    from .floor import floor_entry
+    for q, dicts in enumerate(results):
+        if dicts:
+            dicts[0]["floor"] = floor_entry(res["song_hist"][q], res["bin_hist"][q], int(res["aligned"][q, 0]))
+
+
+def _recognize_fused(queries, chans, owner, db, Fs, topn, resample_to=None, floor=False):
     """recognize_batch through shz_recognize_batch: one call, the hashes never leave the device."""
     if not hasattr(db.table, "h"):
         raise NotImplementedError("fused recognition takes the unsharded table (shards=1)")
@@ -298,12 +306,21 @@ def _recognize_fused(queries, chans, owner, db, Fs, topn, resample_to=None):
     db.finalize()
     nq = len(queries)
     first = np.searchsorted(np.asarray(owner, np.int64), np.arange(nq + 1)).astype(np.uint32)
+
+    def call(*a, **kw):     # floor: the rows the one call records, taken before the setting goes back
+        with ctx.floor(floor):
+            res, ms_extract, ms_match = ctx.recognize_batch(*a, **kw)
+            if floor:
+                res["song_hist"], res["bin_hist"] = ctx.take_floor()
+                if len(res["song_hist"]) != nq:
+                    raise RuntimeError(f"vote floor: {len(res['song_hist'])} rows recorded for {nq} queries")
+        return res, ms_extract, ms_match
+
     if resample_to is not None and int(resample_to) != int(Fs):   # resampled on the device and handed on there
         buf, off = resample_to_device(chans, int(Fs), int(resample_to), ctx)
         try:
-            res, ms_extract, ms_match = ctx.recognize_batch(db.table, buf, off, first, fs=int(resample_to),
-                                                            amp_min=float(DEFAULT_AMP_MIN), fan_value=DEFAULT_FAN_VALUE,
-                                                            topn=int(topn), pcm_device=True)
+            res, ms_extract, ms_match = call(db.table, buf, off, first, fs=int(resample_to), amp_min=float(DEFAULT_AMP_MIN),
+                                             fan_value=DEFAULT_FAN_VALUE, topn=int(topn), pcm_device=True)
         finally:
             buf.free()
     else:
@@ -312,10 +329,12 @@ def _recognize_fused(queries, chans, owner, db, Fs, topn, resample_to=None):
         if arrs:
             off[1:] = np.cumsum([len(a) for a in arrs])
         pcm = np.concatenate(arrs) if off[-1] else np.zeros(1, np.int16)
-        res, ms_extract, ms_match = ctx.recognize_batch(db.table, pcm, off, first, fs=int(Fs), amp_min=float(DEFAULT_AMP_MIN),
-                                                        fan_value=DEFAULT_FAN_VALUE, topn=int(topn))
+        res, ms_extract, ms_match = call(db.table, pcm, off, first, fs=int(Fs), amp_min=float(DEFAULT_AMP_MIN),
+                                         fan_value=DEFAULT_FAN_VALUE, topn=int(topn))
     t0 = time()
     results = [_result_dicts(db, res, q, int(res["nhash"][q])) for q in range(nq)]
+    if floor:
+        _add_floor(results, res)
     align_time = time() - t0
     return results, {"fingerprint_time": ms_extract * 1e-3, "query_time": ms_match * 1e-3, "align_time": align_time,
                      "n_matches": res["npairs"], "n_hashes": res["nhash"]}
@@ -323,7 +342,7 @@ def _recognize_fused(queries, chans, owner, db, Fs, topn, resample_to=None):
 
 @takes_delta_tol(lambda *a, **k: (k["db"] if "db" in k else a[1]).ctx)
 def recognize_batch(queries, db, Fs: int = RATE, topn: int = TOPN, fused: bool = False, resample_to: int = None,
-                    extents: bool = False):
+                    extents: bool = False, floor: bool = False):
     """Recognise flow (recognizer.py:377-392) for many queries at once.  Each query is a list of
     channels (1-D int16 arrays) or a single 1-D array.  Returns (results_per_query, timings).
     fused: fingerprint and match in ONE library call with the hashes staying on the device (shz_recognize_batch);
@@ -335,7 +354,11 @@ def recognize_batch(queries, db, Fs: int = RATE, topn: int = TOPN, fused: bool =
     "query_start_secs" / "query_end_secs" / "song_start_secs" / "song_end_secs" (frames converted as "offset_seconds"
     converts, the end taken at last + 1), "extent_hist" (64 counts over the query's time) and "extent_shift" (bucket b of
     it covers the query frames [b << shift, (b + 1) << shift)).  Not with fused: that call keeps its hashes inside the
-    library."""
+    library.
+    floor: the first result dict of every query gains "floor": {"song_hist", "bin_hist"} -- the query's two vote-floor
+    histograms ([32] uint32, Context.floor) -- and {"expected_above", "score"} -- what shazam_amd.floor.expected_above / score
+    make of song_hist and the query's best aligned count (a heuristic; None where nothing can be fitted).  The other entries
+    do not change; either path, with resample_to and delta_tol."""
     if extents and fused:
         raise ValueError("extents=True needs the query's hashes on the host: not with fused=True")
     ctx = db.ctx
@@ -345,7 +368,7 @@ def recognize_batch(queries, db, Fs: int = RATE, topn: int = TOPN, fused: bool =
         chans.extend(cs)
         owner.extend([qi] * len(cs))
     if fused:
-        return _recognize_fused(queries, chans, owner, db, Fs, topn, resample_to)
+        return _recognize_fused(queries, chans, owner, db, Fs, topn, resample_to, floor)
     t0 = time()
     k, t1, ho = fingerprint_batch(chans, Fs, ctx=ctx, resample_to=resample_to)
     fingerprint_time = time() - t0
@@ -355,10 +378,12 @@ def recognize_batch(queries, db, Fs: int = RATE, topn: int = TOPN, fused: bool =
     first = np.searchsorted(owner, np.arange(nq + 1))
     qoff = ho[first]
     t0 = time()
-    res = db.match(k, t1, qoff, topn)
+    res = db.match(k, t1, qoff, topn, floor=floor)
     query_time = time() - t0
     t0 = time()
     results = [_result_dicts(db, res, q, int(res["nhash"][q])) for q in range(nq)]
+    if floor:
+        _add_floor(results, res)
     if extents:
         _add_extents(db, results, k, t1, qoff, res)
     align_time = time() - t0
@@ -367,14 +392,14 @@ def recognize_batch(queries, db, Fs: int = RATE, topn: int = TOPN, fused: bool =
 
 
 def recognize(channels_or_samples, db=None, Fs: int = RATE, topn: int = TOPN, fused: bool = False, resample_to: int = None,
-              delta_tol: int = None, extents: bool = False):
+              delta_tol: int = None, extents: bool = False, floor: bool = False):
     """recognizer.py:377-396: (final_results, fingerprint_time, query_time, align_time).  fused, resample_to, delta_tol,
-    extents: see recognize_batch."""
+    extents, floor: see recognize_batch."""
     if db is None:
         raise ValueError("recognize() needs the HipFingerprintDB holding the fingerprints")
     x = channels_or_samples
     q = [np.asarray(x)] if (not isinstance(x, (list, tuple)) or (len(x) and np.isscalar(x[0]))) else list(x)
-    results, tm = recognize_batch([q], db, Fs, topn, fused, resample_to, extents, delta_tol=delta_tol)
+    results, tm = recognize_batch([q], db, Fs, topn, fused, resample_to, extents, floor, delta_tol=delta_tol)
     return results[0], tm["fingerprint_time"], tm["query_time"], tm["align_time"]
 
 

@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get("SHZ_LIB") or os.path.join(_HERE, "libshz.so")  # SHZ_
 
 OK, E_INVALID, E_HIP, E_CAPACITY, E_NOMEM, E_UNSUPPORTED, E_RCCL, E_STATE = 0, -1, -2, -3, -4, -5, -6, -7
 PCM_DEVICE, OUT_DEVICE, IN_DEVICE, STFT_POWER, MATCH_FULL_SORT, RESERVE_GATHER, RESERVE_WAIT = 1, 2, 4, 8, 16, 32, 64
+SCAN_KEEP_MASK = 128   # shz_scan_extents: out_nres holds a keep mask of the windows on entry
 SONGS_DEVICE_OUT = 128   # shz_table_song_hashes: key32 / off are device memory
 # shz_set_debug test switches (include/shz.h); RUN_ROWS_MAX[_SMALL]: the most rows a run / a segment cut from runs holds
 DEBUG_VT_TINY_HEAVY, DEBUG_VT_PROBE1, DEBUG_RUN_LIMIT_SMALL, DEBUG_SCAN_SMALL_GROUPS = 1, 2, 4, 8
@@ -23,6 +24,7 @@ DEBUG_CATALOG_SMALL_SLICES = 64   # shz_match_songs_warps: one song x at most 2 
 DEBUG_VOTE_TOLERANT_ROUTE = 128   # the vote: the tolerant route at tolerance 0 too
 DEBUG_EXTENT_SMALL_TILES = 256   # shz_match_extents: tiles of 64 pairs, 4 descriptors in LDS, 3 queries a sub-batch
 DEBUG_REPEAT_SMALL_SLICES = 512  # shz_repeats_* / shz_shared_*: one recording (job) a slice, expand tiles of 64 pairs, blocks of 64 elements
+DEBUG_FLOOR_SMALL = 1024         # the vote floor: at most 3 queries a match sub-batch, 2 queries in the histogram kernels' LDS table
 SHARED_LAG_BIAS = 1 << 20        # shz_shared_*: cell_lag = lag + SHARED_LAG_BIAS (SHZ_SHARED_LAG_BIAS)
 SCAN_NO_WARP = 0xFFFFFFFF            # shz_scan_warps: out_best of a window that tried no variant
 SCAN_U32, SCAN_POPC64, SCAN_U64 = 0, 1, 2   # shz_scan_host kinds
@@ -83,6 +85,11 @@ SIGNATURES = {
     "shz_set_stage_f64": (C.c_int32, [vp, C.c_int32]),
     "shz_set_vote_tolerance": (C.c_int32, [vp, C.c_uint32]),
     "shz_get_vote_tolerance": (C.c_int32, [vp, u32p]),
+    "shz_set_vote_floor": (C.c_int32, [vp, C.c_uint32]),
+    "shz_get_vote_floor": (C.c_int32, [vp, u32p]),
+    "shz_vote_floor_rows": (C.c_int32, [vp, u64p]),
+    "shz_vote_floor_take": (C.c_int32, [vp, vp, vp, C.c_uint64, u64p]),
+    "shz_vote_bucket": (C.c_int32, [C.c_uint32, u32p]),
     "shz_upload_stats": (C.c_int32, [vp, u64p, u64p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "shz_extract_stats": (C.c_int32, [vp, u64p, u64p, u64p, u64p, u64p, u64p]),
     "shz_sha1_prefix": (C.c_int32, [vp, vp, C.c_uint64, C.c_uint32, vp]),
@@ -401,7 +408,8 @@ class Context:
         its windows in groups of at most 3, 64: shz_match_songs_warps works in slices of 1 song x 2 warps, 128: the vote takes
         the tolerant route at tolerance 0 too, 256: the extent kernel works in tiles of 64 pairs with 4 descriptors in LDS and
         sub-batches of 3 queries, 512: shz_repeats_* works in slices of one recording, expand tiles of 64 pairs and blocks of
-        64 elements)."""
+        64 elements, 1024: with the vote floor on, match sub-batches of at most 3 queries and histogram kernels with 2
+        queries in LDS)."""
         self.check(lib().shz_set_debug(self.h, int(flags)))
 
     def set_vote_tolerance(self, bins: int):
@@ -430,6 +438,53 @@ class Context:
             yield self
         finally:
             self.set_vote_tolerance(before)
+
+    # ---- the vote floor (shz_set_vote_floor) ----------------------------------------------
+    def set_vote_floor(self, on: bool):
+        """Every later vote of this context records, per query, a row of two histograms: how many songs reached which best
+        count and how many single bins reached which count (32 buckets, shazam_amd.floor.bucket_of).  A row costs 256 bytes
+        of host memory until it is taken (take_floor); switching off drops the rows not taken."""
+        self.check(lib().shz_set_vote_floor(self.h, 1 if on else 0))
+
+    @property
+    def vote_floor(self) -> bool:
+        n = C.c_uint32()
+        self.check(lib().shz_get_vote_floor(self.h, C.byref(n)))
+        return bool(n.value)
+
+    def floor_rows(self) -> int:
+        """Rows recorded since the last take_floor()."""
+        n = C.c_uint64()
+        self.check(lib().shz_vote_floor_rows(self.h, C.byref(n)))
+        return n.value
+
+    def take_floor(self):
+        """(song_hist, bin_hist), [n, 32] uint32 each: the rows recorded since the last take, in the order the queries were
+        handed to the vote; the store is empty afterwards."""
+        n = self.floor_rows()
+        sh, bh = np.zeros((n, 32), np.uint32), np.zeros((n, 32), np.uint32)
+        got = C.c_uint64()
+        self.check(lib().shz_vote_floor_take(self.h, ptr(sh) if n else None, ptr(bh) if n else None, n, C.byref(got)))
+        return sh, bh
+
+    @contextlib.contextmanager
+    def floor(self, on=True):
+        """with ctx.floor(): the vote floor on inside the block; the previous state after it, and no rows left over from the
+        block (also after an exception).  on False / None: the context stays as it is.  Where the floor was on already, the
+        rows recorded before the block and not yet taken are dropped too (the store is one list: a call that asks for its own
+        rows takes it whole) -- take_floor() first if they matter.  The same holds for floor=True on match(), recognize*() and
+        scan_windows(), which run inside this block."""
+        if not on:
+            yield self
+            return
+        before = self.vote_floor
+        self.set_vote_floor(True)
+        try:
+            yield self
+        finally:
+            self.set_vote_floor(False)      # drops the leftovers
+            if before:
+                self.set_vote_floor(True)
 
     def vt_redo_count(self) -> int:
         n = C.c_uint64()
@@ -1041,11 +1096,12 @@ class Context:
 
     def scan_extents_raw(self, table: "Table", pcm, clip_off, rec_clip0, window_frames, step_frames, min_aligned, max_gap=1,
                          margin_frames=0, d_tol=0, fs=44100, amp_min=10.0, fan_value=5, topn=2, pcm_device=False, full_sort=False,
-                         cap_windows=0, cap_segs=0, hist=True, fill=0, zones=True):
+                         cap_windows=0, cap_segs=0, hist=True, fill=0, zones=True, keep=None):
         """One shz_scan_extents as it is, with room for cap_windows windows and cap_segs segments: (rc, res, seg, zone,
         win_off, n_windows, n_segs, ms).  res as Table.match, seg as scan_timeline_raw's, zone = the arrays ZONE_FIELDS
         [cap_segs, 3] and hist [cap_segs, 3, 64] (None with hist false); seg and zone arrays are filled with `fill` before the
-        call.  zones=False hands the library NULL zone arrays.  ms = (extract, window, match, extent)."""
+        call.  zones=False hands the library NULL zone arrays.  ms = (extract, window, match, extent).  keep ([cap_windows], bool):
+        SHZ_SCAN_KEEP_MASK -- the windows with a false entry are cleared before the timeline."""
         co, nc = self._clip_off(clip_off)
         rc0 = np.ascontiguousarray(rec_clip0, np.uint32)
         nr = len(rc0) - 1
@@ -1053,6 +1109,11 @@ class Context:
         wo, cnt, scnt = np.zeros(nr + 1, np.uint64), C.c_uint64(), C.c_uint64()
         ms = [C.c_float(), C.c_float(), C.c_float(), C.c_float()]
         res = _match_result(int(cap_windows), topn)
+        if keep is not None and int(cap_windows):
+            if len(keep) != int(cap_windows):
+                raise ValueError(f"keep has {len(keep)} entries for {int(cap_windows)} windows")
+            res["nres"][:] = np.asarray(keep, bool)
+            flags |= SCAN_KEEP_MASK
         seg = {k: np.full(int(cap_segs), fill, d) for k, d in SEGMENT_FIELDS}
         zone = {k: np.full((int(cap_segs), 3), fill, np.uint32) for k in ZONE_FIELDS}
         zone["hist"] = np.full((int(cap_segs), 3, 64), fill, np.uint32) if hist else None
@@ -1067,18 +1128,19 @@ class Context:
         return rc, res, seg, zone, wo, int(cnt.value), int(scnt.value), tuple(float(m.value) for m in ms)
 
     def scan_extents(self, table: "Table", pcm, clip_off, rec_clip0, window_frames, step_frames, min_aligned, max_gap=1,
-                     margin_frames=0, d_tol=0, hist=True, **kw):
+                     margin_frames=0, d_tol=0, hist=True, keep=None, **kw):
         """shz_scan_extents: scan_batch, the timeline and the extent pass on every segment's three zones (whole, head, tail) in
         one call, the recordings' hashes staying on the device.  Returns (res, win_off, seg, zone, ms): res / win_off as
         scan_batch's, seg as scan_timeline's, zone = arrays lo, hi, count, q_first, q_last (recording frames), t_first, t_last
         (song frames), shift [n_segs, 3] and hist [n_segs, 3, 64] (None with hist false), ms = (extract, window, match, extent).
         Room: the window count follows from the frame counts (a first call that launches nothing), and there are never more
-        segments than windows, so one call with room for that many suffices."""
+        segments than windows, so one call with room for that many suffices.  keep: see scan_extents_raw."""
         args = (table, pcm, clip_off, rec_clip0, window_frames, step_frames, min_aligned, max_gap, margin_frames, d_tol)
         rc, _, _, _, _, n_wins, _, _ = self.scan_extents_raw(*args, hist=False, **kw)
         if rc != E_CAPACITY:
             self.check(rc)
-        rc, res, seg, zone, wo, n_wins, n_segs, ms = self.scan_extents_raw(*args, cap_windows=n_wins, cap_segs=n_wins, hist=hist, **kw)
+        rc, res, seg, zone, wo, n_wins, n_segs, ms = self.scan_extents_raw(*args, cap_windows=n_wins, cap_segs=n_wins, hist=hist,
+                                                                           keep=keep, **kw)
         self.check(rc)
         return (res, wo, {k: v[:n_segs] for k, v in seg.items()},
                 {k: (None if v is None else v[:n_segs]) for k, v in zone.items()}, ms)
@@ -1664,6 +1726,15 @@ def scan_timeline_warps(win_off, sid, delta, aligned, nres, best, step_frames, t
                      tempos, pitches, min_aligned, max_gap, tempo_tol, pitch_tol, shift_tol)
 
 
+def _floor_into(ctx, res, before, n):
+    """The n rows a call recorded, those behind the `before` rows that were in the store, into res as song_hist / bin_hist
+    (the store is taken whole: Context.floor() drops what is left over anyway)."""
+    sh, bh = ctx.take_floor()
+    if len(sh) - before != n:
+        raise ShzError(E_STATE, f"vote floor: {len(sh) - before} rows recorded for {n} queries")
+    res["song_hist"], res["bin_hist"] = sh[before:], bh[before:]
+
+
 class Table:
     """HBM-resident fingerprints table: rows (key32, song_id, offset)."""
 
@@ -1931,35 +2002,44 @@ class Table:
         self.ctx.check(lib().shz_table_allgather(self.h, comm.h, C.byref(b)))
         return b.value
 
-    def match(self, key32, q_off, query_off, topn=2, full_sort=False, delta_tol=None):
+    def match(self, key32, q_off, query_off, topn=2, full_sort=False, delta_tol=None, floor=False):
         """Batched return_matches + align_matches.  Returns dict of arrays (see shz.h).  full_sort: the vote as one
         sort of 8-byte votes + record chain (SHZ_MATCH_FULL_SORT), the form the faster vote paths are tested against.
-        delta_tol: the vote tolerance of this call (Context.tolerance); None: the context's."""
+        delta_tol: the vote tolerance of this call (Context.tolerance); None: the context's.  floor: the result gains
+        song_hist and bin_hist, [n_queries, 32] uint32 (Context.floor, shazam_amd.floor); the other arrays do not change.  Rows
+        that a context with the floor switched on by hand had recorded before are dropped (Context.floor)."""
         k = np.ascontiguousarray(key32, np.uint32)
         o = np.ascontiguousarray(q_off, np.uint32)
         qo = np.ascontiguousarray(query_off, np.uint64)
         nq = len(qo) - 1
         res = _match_result(nq, topn)
-        with self.ctx.tolerance(delta_tol):
+        with self.ctx.tolerance(delta_tol), self.ctx.floor(floor):
+            before = self.ctx.floor_rows() if floor else 0
             self.ctx.check(lib().shz_match_batch(self.ctx.h, self.h, ptr(k), ptr(o), qo.ctypes.data_as(u64p), nq, topn,
                                                  MATCH_FULL_SORT if full_sort else 0,
                                                  ptr(res["sid"]), ptr(res["delta"]), ptr(res["aligned"]), ptr(res["dedup"]),
                                                  ptr(res["nres"]), ptr(res["nhash"]), ptr(res["npairs"])))
+            if floor:
+                _floor_into(self.ctx, res, before, nq)
         return res
 
-    def match_device(self, key32, q_off, query_off, topn=2, full_sort=False, bias_bound=-1):
+    def match_device(self, key32, q_off, query_off, topn=2, full_sort=False, bias_bound=-1, floor=False):
         """match() the way the fused calls and the listeners run it (shz_match_device_host): the two columns are put on the
         device first and matched there, with the caller's bound of the query offsets (below 0 or >= 2^32: none).  For tests
-        and tools; same result arrays as match()."""
+        and tools; same result arrays as match() (floor: as there)."""
         k = np.ascontiguousarray(key32, np.uint32)
         o = np.ascontiguousarray(q_off, np.uint32)
         qo = np.ascontiguousarray(query_off, np.uint64)
         nq = len(qo) - 1
         res = _match_result(nq, topn)
-        self.ctx.check(lib().shz_match_device_host(self.ctx.h, self.h, ptr(k), ptr(o), qo.ctypes.data_as(u64p), nq, topn,
-                                                   MATCH_FULL_SORT if full_sort else 0, int(bias_bound),
-                                                   ptr(res["sid"]), ptr(res["delta"]), ptr(res["aligned"]), ptr(res["dedup"]),
-                                                   ptr(res["nres"]), ptr(res["nhash"]), ptr(res["npairs"])))
+        with self.ctx.floor(floor):
+            before = self.ctx.floor_rows() if floor else 0
+            self.ctx.check(lib().shz_match_device_host(self.ctx.h, self.h, ptr(k), ptr(o), qo.ctypes.data_as(u64p), nq, topn,
+                                                       MATCH_FULL_SORT if full_sort else 0, int(bias_bound),
+                                                       ptr(res["sid"]), ptr(res["delta"]), ptr(res["aligned"]), ptr(res["dedup"]),
+                                                       ptr(res["nres"]), ptr(res["nhash"]), ptr(res["npairs"])))
+            if floor:
+                _floor_into(self.ctx, res, before, nq)
         return res
 
     def match_stats(self):

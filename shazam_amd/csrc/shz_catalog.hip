@@ -323,6 +323,8 @@ extern "C" int32_t shz_match_songs(shz_ctx* ctx, shz_table* t, const uint32_t* s
   if (G.total)   // (no listed song has a row: nothing to look up, every count stays zero)
     rc = shz_match_device(ctx, t, d_key, d_off, row_off.data(), n_sids, w, flags, (int64_t)t->max_off, r_sid.data(),
                           r_delta.data(), r_aligned.data(), r_dedup.data(), r_nres.data(), r_nhash.data(), r_npairs.data());
+  else
+    shz_floor_zero_rows(ctx, n_sids);   // (the vote floor's rows line up with the result arrays)
   (void)hipStreamSynchronize(ctx->stream);   // (a refused call may have queued work that reads the columns)
   if (rc != SHZ_OK) return rc;
   // the song itself leaves its own list: what stays are the first topn of every other song (see shz.h)
@@ -662,7 +664,10 @@ extern "C" int32_t shz_match_songs_warps(shz_ctx* ctx, shz_table* t, const uint3
   }
   if (out_rows)
     for (uint32_t q = 0; q < n_sids; ++q) out_rows[q] = row_off[q + 1] - row_off[q];
-  if (G.total == 0) return SHZ_OK;   // (no listed song has a row: nothing to look up, every count stays zero)
+  if (G.total == 0) {   // (no listed song has a row: nothing to look up, every count stays zero -- and every floor row)
+    shz_floor_zero_rows(ctx, nv);
+    return SHZ_OK;
+  }
   // 2) the slices, from the row counts alone: whole songs x a contiguous chunk of warps whose items (8 bytes each in the
   // call's buffers) stay within 1/8 of the workspace limit and the match's 2^28-pair budget, and below 2^32; the ladder is
   // cut only where one song at all warps is beyond that, and a song at one warp is never split
@@ -731,6 +736,8 @@ extern "C" int32_t shz_match_songs_warps(shz_ctx* ctx, shz_table* t, const uint3
     if (total)
       rc = shz_match_device(ctx, t, d_wkey, d_woff, seg_off.data(), (uint32_t)n_seg, w, flags, (int64_t)t_max, r_sid.data(),
                             r_delta.data(), r_aligned.data(), r_dedup.data(), r_nres.data(), r_nhash.data(), r_npairs.data());
+    else
+      shz_floor_zero_rows(ctx, n_seg);   // (a slice without a warped row: the vote floor's rows line up with the result arrays)
     if (rc != SHZ_OK) break;
     if (timed) {
       float a = 0.f, b = 0.f;

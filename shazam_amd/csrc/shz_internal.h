@@ -165,6 +165,8 @@ struct shz_ctx {
   uint64_t st_vt_redo = 0;      // sub-batches whose vote tiles flagged an overflow and were voted again by the full sort
   uint32_t debug = 0;           // SHZ_DEBUG_* (shz_set_debug): switches that force rare paths, for tests
   uint32_t vote_tol = 0;        // shz_set_vote_tolerance: neighbouring offset bins a song's aligned count sums over (0 .. 31)
+  uint32_t vote_floor = 0;      // shz_set_vote_floor: every query handed to the match records a row of two histograms
+  std::vector<uint32_t> floor_rows;   // ... the rows not yet taken, in query order: song_hist[32] | bin_hist[32] each (256 bytes)
   // extraction stats: cells fp32 peak picking left undecided, of those decided on fp64 values, frames recomputed for
   // that, passes repeated with fp64 staging
   uint64_t st_und = 0, st_und_f64 = 0, st_und_ffts = 0, st_fallbacks = 0;
@@ -261,6 +263,9 @@ int32_t shz_match_device(shz_ctx* ctx, shz_table* t, const uint32_t* d_key32, co
                          int32_t* out_delta, uint32_t* out_aligned, uint32_t* out_dedup, uint32_t* out_nres, uint32_t* out_nhash,
                          uint64_t* out_npairs);
 int32_t shz_match_ready(shz_ctx* ctx, shz_table* t, uint32_t topn);
+// the vote floor (shz_set_vote_floor): n zero rows, for a caller that skips the match because nothing is to be looked up (its
+// rows must line up with its result arrays).  Nothing while the floor is off
+void shz_floor_zero_rows(shz_ctx* ctx, uint64_t n);
 
 // ---- match extents on device columns the library owns (shz_extent.hip) ------------------------------
 struct ex_args {   // what every caller hands over (host arrays but the two query columns)

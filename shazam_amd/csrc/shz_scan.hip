@@ -714,6 +714,12 @@ extern "C" int32_t shz_scan_extents(shz_ctx* ctx, shz_table* t, const int16_t* p
   if (!ctx || !t) return SHZ_E_INVALID;
   if (ms_extent) *ms_extent = 0.f;
   if (seg_count) *seg_count = 0;
+  // SHZ_SCAN_KEEP_MASK: the caller's keep mask arrives in out_nres, which the scan overwrites -- a copy of this call's own
+  std::vector<uint8_t> keep;
+  if ((flags & SHZ_SCAN_KEEP_MASK) && out_nres)
+    for (uint64_t w = 0; w < cap_windows; ++w) keep.push_back(out_nres[w] != 0);
+  const bool masked = (flags & SHZ_SCAN_KEEP_MASK) != 0;
+  flags &= ~SHZ_SCAN_KEEP_MASK;
   const sc_plain P{pcm, clip_off, n_clips, rec_clip0, n_recs, fs, amp_min, fan_value, window_frames, step_frames, topn, flags, win_off,
                    out_sid, out_delta, out_aligned, out_dedup, out_nres, out_nhash, out_npairs, cap_windows, count, ms_extract,
                    ms_window, ms_match};
@@ -735,6 +741,9 @@ extern "C" int32_t shz_scan_extents(shz_ctx* ctx, shz_table* t, const int16_t* p
   std::vector<uint64_t> hash_off((size_t)n_clips + 1, 0);
   const uint32_t *d_key = nullptr, *d_t1 = nullptr;
   SHZ_TRY(sc_plain_run(ctx, t, who, P, timed, hash_off.data(), &d_key, &d_t1));
+  if (masked)   // (the windows were counted: *count <= cap_windows = the mask's length)
+    for (uint64_t w = 0; w < *count && w < keep.size(); ++w)
+      if (!keep[w]) out_nres[w] = 0;
   // 3) the timeline, on the host
   const int32_t rc = shz_scan_timeline(win_off, n_recs, out_sid, out_delta, out_aligned, out_nres, topn, step_frames, min_aligned, max_gap,
                                        seg_rec, seg_sid, seg_shift, seg_first, seg_last, seg_hits, seg_best, cap_segs, seg_count);

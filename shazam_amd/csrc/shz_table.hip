@@ -1200,6 +1200,60 @@ __global__ void mt_record_kernel(const uint64_t* __restrict__ v, const unsigned 
   g_delta[slot] = bd;
 }
 
+// ---- the vote floor (shz_set_vote_floor): per query, how many single bins and how many songs reached which count -- the
+// evidence the top-n throws away.  A count c >= 1 falls into one of FH_BUCKETS buckets: c - 1 up to 16 (exact counts), then
+// by powers of two, floor(log2 c) + 12 (17..31 -> 16, 32..63 -> 17, ...), everything from 2^19 up into the last one.  The
+// kernel and shz_vote_bucket share the function.
+#define FH_BUCKETS 32
+#define FH_ROW (2 * FH_BUCKETS)   // the row of a query: song_hist[FH_BUCKETS] | bin_hist[FH_BUCKETS]
+#define FH_LDS_Q 32               // queries of a workgroup's span that its LDS table holds (SHZ_DEBUG_FLOOR_SMALL: 2)
+#define FH_SMALL_Q 3              // queries of a match sub-batch under SHZ_DEBUG_FLOOR_SMALL
+__host__ __device__ __forceinline__ uint32_t vote_bucket(uint32_t c) {   // c >= 1
+  if (c <= 16u) return c - 1u;
+  const uint32_t b = (31u - (uint32_t)__builtin_clz(c)) + 12u;
+  return b < (uint32_t)FH_BUCKETS - 1u ? b : (uint32_t)FH_BUCKETS - 1u;
+}
+
+// Both histogram stages run behind the tolerant fold's records, over its RUNS (rfirst, R: a run is the votes of one (query,
+// song, delta), its length a difference of two first indices -- no thread walks a run of 40,000 votes):
+//   fh_hist_kernel<false>  every run: the bucket of its length            -> bin_hist  (single bins, whatever the tolerance)
+//   fh_hist_kernel<true>   every run that opens a (query, song) group: the bucket of the group's record, the count the
+//                          fold reports as `aligned` for that song        -> song_hist
+// The votes are sorted by query, so the 256 runs of a workgroup span a contiguous range of queries that starts at the query
+// of its first run: the first lq <= FH_LDS_Q queries of the span are counted in an LDS table and flushed with one global add
+// per non-zero cell, the queries behind them (a span that does not fit) go to global memory one add a run.  Integer adds:
+// exact, and independent of the order.  hist: the rows of the pass's first query (zeroed by the caller).
+template <bool SONGS>
+__global__ __launch_bounds__(256) void fh_hist_kernel(const uint64_t* __restrict__ v, const unsigned long long* __restrict__ R_dev,
+                                                      int qshift, const uint32_t* __restrict__ rfirst,
+                                                      const uint32_t* __restrict__ gfl, const uint32_t* __restrict__ gps,
+                                                      const uint64_t* __restrict__ g_pack, uint32_t lq, uint32_t nq,
+                                                      uint32_t* __restrict__ hist) {
+  __shared__ uint32_t tab[FH_LDS_Q * FH_BUCKETS];
+  const uint64_t R = *R_dev, r0 = (uint64_t)blockIdx.x * 256;
+  if (r0 >= R) return;   // uniform
+  const uint32_t col = SONGS ? 0u : (uint32_t)FH_BUCKETS;
+  for (uint32_t i = threadIdx.x; i < lq * FH_BUCKETS; i += 256) tab[i] = 0u;
+  const uint32_t q0 = qshift < 64 ? (uint32_t)(v[rfirst[r0]] >> qshift) : 0u;
+  __syncthreads();
+  const uint64_t r = r0 + threadIdx.x;
+  if (r < R && (!SONGS || gfl[r] != 0u)) {
+    const uint32_t i = rfirst[r];
+    const uint32_t q = qshift < 64 ? (uint32_t)(v[i] >> qshift) : 0u;
+    const uint32_t c = SONGS ? (uint32_t)(g_pack[gps[r]] >> 32) : rfirst[r + 1] - i;
+    if (c != 0u && q < nq) {   // (always: a run has a vote, a vote's query is one of the pass)
+      const uint32_t b = vote_bucket(c);
+      if (q - q0 < lq) atomicAdd(&tab[(q - q0) * FH_BUCKETS + b], 1u);
+      else atomicAdd(&hist[(uint64_t)q * FH_ROW + col + b], 1u);
+    }
+  }
+  __syncthreads();
+  for (uint32_t i = threadIdx.x; i < lq * FH_BUCKETS; i += 256) {
+    const uint32_t n = tab[i];
+    if (n) atomicAdd(&hist[(uint64_t)(q0 + i / FH_BUCKETS) * FH_ROW + col + (i % FH_BUCKETS)], n);
+  }
+}
+
 
 // ---------------------------------------------------------------------------------------------------------------
 // Vote tiles: the fold of 4-byte votes without sorting them all the way.
@@ -2045,6 +2099,7 @@ struct res_block {
   int32_t* delta;
   uint32_t *aligned, *dedup, *nres, *nhash;
   uint32_t* vt_err;   // set by a vote-tile kernel whose LDS table or range list overflowed: the votes go through the full sort again
+  uint32_t* hist = nullptr;   // the vote floor's rows [nq][FH_ROW] behind the block (shz_set_vote_floor), NULL while it is off
 };
 static uint64_t res_block_bytes(uint32_t nq, uint64_t nres) { return (uint64_t)nq * 8 + nres * 16 + (uint64_t)nq * 8 + 8; }
 static res_block res_block_at(void* base, uint32_t nq, uint64_t nres) {
@@ -2057,6 +2112,7 @@ static res_block res_rows(res_block r, uint32_t qa, uint32_t topn) {
   const uint64_t o = (uint64_t)qa * topn;
   r.sid += o; r.delta += o; r.aligned += o; r.dedup += o;
   r.nres += qa;
+  if (r.hist) r.hist += (uint64_t)qa * FH_ROW;
   return r;
 }
 
@@ -2140,14 +2196,22 @@ static int32_t vote_fold_tol(shz_ctx* ctx, const uint64_t* vs, uint64_t P, uint3
                      (const uint32_t*)gfl, (const uint32_t*)gps, (const uint32_t*)rdd, (unsigned long long*)gh, (uint32_t*)gdd);
   hipLaunchKernelGGL(mt_record_kernel, dim3(nb), dim3(256), 0, ctx->stream, vs, d_R, P, mb, tol, (const uint32_t*)rfirst,
                      (const uint32_t*)gfl, (const uint32_t*)gps, (uint64_t*)gh, (uint32_t*)gd);
+  if (r.hist) {   // the vote floor: the runs' lengths and the groups' records, before the ranking throws them away
+    const uint32_t lq = (ctx->debug & SHZ_DEBUG_FLOOR_SMALL) ? 2u : (uint32_t)FH_LDS_Q;
+    hipLaunchKernelGGL(fh_hist_kernel<false>, dim3(nb), dim3(256), 0, ctx->stream, vs, d_R, qshift, (const uint32_t*)rfirst,
+                       (const uint32_t*)gfl, (const uint32_t*)gps, (const uint64_t*)gh, lq, nq, r.hist);
+    hipLaunchKernelGGL(fh_hist_kernel<true>, dim3(nb), dim3(256), 0, ctx->stream, vs, d_R, qshift, (const uint32_t*)rfirst,
+                       (const uint32_t*)gfl, (const uint32_t*)gps, (const uint64_t*)gh, lq, nq, r.hist);
+  }
   SHZ_HIP(ctx, hipGetLastError());
   return vote_rank(ctx, P, nq, mb, topn, qstart, d_G, (const uint64_t*)gh, (const uint32_t*)gd, (const uint32_t*)gdd, r);
 }
 
 // the tolerance of this context's votes, or -1 for the plain fold of one bin (SHZ_DEBUG_VOTE_TOLERANT_ROUTE: the tolerant
-// fold at 0 bins too)
+// fold at 0 bins too; the vote floor: its histograms are taken from the tolerant fold's runs and records, at the tolerance
+// in force -- at 0 bins that fold computes the plain fold's results)
 static int vote_tol_of(const shz_ctx* ctx) {
-  return (ctx->vote_tol > 0 || (ctx->debug & SHZ_DEBUG_VOTE_TOLERANT_ROUTE)) ? (int)ctx->vote_tol : -1;
+  return (ctx->vote_tol > 0 || ctx->vote_floor || (ctx->debug & SHZ_DEBUG_VOTE_TOLERANT_ROUTE)) ? (int)ctx->vote_tol : -1;
 }
 
 // the full sort: sort the packed 8-byte votes, then vote_fold (tol < 0) or vote_fold_tol.  v0 holds the P votes, v1 is
@@ -2381,7 +2445,9 @@ static void vote_plan_make(const vote_case& c, vote_plan* plan) {
   if (c.queued_held) { plan->route = ROUTE_QUEUED; return; }
   if (c.P == 0) { plan->route = ROUTE_NONE; return; }
   if (c.sink) { plan->route = ROUTE_SINK; return; }
-  if (c.tol >= 0) {   // a sum over neighbouring bins needs the votes in order: one 8-byte pass, whatever their number
+  // a sum over neighbouring bins needs the votes in order: one 8-byte pass, whatever their number.  The vote floor goes this
+  // way too, at the tolerance in force (vote_tol_of): its histograms are taken from the sorted runs and the fold's records
+  if (c.tol >= 0) {
     plan->passes.push_back(vote_pass{0, c.nq, 0, c.P});
     plan->route = ROUTE_TOLERANT;
     return;
@@ -2441,6 +2507,10 @@ struct match_call {
   bool has_bias_bound;          // the caller knows a bound of the query offsets without looking at them ...
   uint32_t bias_bound;          // ... every q_off <= bias_bound: the queued fold may take it for its bias
   bool pack_small;              // segment descriptors | query offsets | control block travel as one pinned copy
+  // the vote floor (shz_set_vote_floor; never with a sink): the rows of the queries committed so far, FH_ROW words each, in
+  // query order -- handed to the context's store when the whole call succeeded
+  bool floor;
+  std::vector<uint32_t> floor_rows;
 };
 enum sub_next {
   SUB_GO,          // on to the next stage
@@ -2633,9 +2703,11 @@ static int32_t sub_head(match_call& mc, match_sub& s, sub_next* next) {
     SHZ_TRY(head_sorted(mc, s, c0, c1));
   }
   s.nres = (uint64_t)nq * (mc.sink ? 0 : mc.topn);
-  s.rb_bytes = res_block_bytes(nq, s.nres);
+  // (the vote floor's rows lie behind the block: zeroed by the probe with it, read back with it)
+  s.rb_bytes = res_block_bytes(nq, s.nres) + (mc.floor ? (uint64_t)nq * FH_ROW * 4 : 0);
   SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_PEAK_F, s.rb_bytes + 64, &s.rb));
   s.r = res_block_at(s.rb, nq, s.nres);
+  if (mc.floor) s.r.hist = (uint32_t*)((char*)s.rb + res_block_bytes(nq, s.nres));
   hipLaunchKernelGGL(m_probe_kernel, dim3(nblk(s.nx_bound)), dim3(256), 0, ctx->stream, (const uint64_t*)s.E,
                      (const uint32_t*)s.gs, &s.d_ctl->ng, s.nx_bound, mc.d_segs, mc.nseg, s.glo, (uint64_t*)gpairs,
                      (unsigned long long*)s.d_ctl + 16, (uint32_t*)s.rb, (uint32_t)((s.rb_bytes + 3) / 4));
@@ -2870,7 +2942,8 @@ static int32_t sub_vote(const match_call& mc, const match_sub& s, const vote_pla
 }
 
 // no hash of the queries is looked up here (none given, or all of them another shard's): zero counters, no results
-static void sub_commit_empty(const match_call& mc, const match_sub& s) {
+static void sub_commit_empty(match_call& mc, const match_sub& s) {
+  if (mc.floor) mc.floor_rows.resize(mc.floor_rows.size() + (size_t)s.nq * FH_ROW, 0u);   // zero rows
   for (uint32_t q = s.q0; q < s.q0 + s.nq; ++q) {
     if (mc.out_nres) mc.out_nres[q] = 0;
     if (mc.out_nhash) mc.out_nhash[q] = 0;
@@ -2880,7 +2953,7 @@ static void sub_commit_empty(const match_call& mc, const match_sub& s) {
 
 // the result block back (with the counts already, where the queued fold held) and out to the caller -- unless the LDS fold
 // flagged an overflow: then nothing is committed and the queries go round again
-static int32_t sub_commit(const match_call& mc, const match_sub& s, vote_route route, sub_next* next) {
+static int32_t sub_commit(match_call& mc, const match_sub& s, vote_route route, sub_next* next) {
   shz_ctx* ctx = mc.ctx;
   const uint32_t q0 = s.q0, nq = s.nq;
   void* hb;
@@ -2921,6 +2994,10 @@ static int32_t sub_commit(const match_call& mc, const match_sub& s, vote_route r
     memcpy(mc.out_aligned + o0, h.aligned, s.nres * 4);
     memcpy(mc.out_dedup + o0, h.dedup, s.nres * 4);
     memcpy(mc.out_nres + q0, h.nres, (uint64_t)nq * 4);
+  }
+  if (mc.floor) {   // (a sub-batch that goes round again never gets here: its queries record once)
+    const uint32_t* rows = (const uint32_t*)((const char*)hb + res_block_bytes(nq, s.nres));
+    mc.floor_rows.insert(mc.floor_rows.end(), rows, rows + (size_t)nq * FH_ROW);
   }
   *next = SUB_DONE;
   return SHZ_OK;
@@ -2974,6 +3051,9 @@ static int32_t match_core(match_call& mc) {
   // a shard's compose marks hashes it does not own with the query index nq (sorted behind all queries): nq << 52 must
   // not wrap, so its sub-batches stay below MAX_Q_SUB
   uint32_t step = std::min<uint32_t>(mc.n_queries, (mc.sink && mc.sink->nshards > 1) ? MAX_Q_SUB - 1 : MAX_Q_SUB);
+  mc.floor = ctx->vote_floor && !mc.sink;   // (shz_match_pairs votes nothing: its votes' rows are shz_pairs_vote's)
+  mc.floor_rows.clear();
+  if (mc.floor && (ctx->debug & SHZ_DEBUG_FLOOR_SMALL)) step = std::min<uint32_t>(step, FH_SMALL_Q);
   bool redo = false;
   for (uint32_t q0 = 0; q0 < mc.n_queries;) {
     match_sub s{};
@@ -2994,6 +3074,7 @@ static int32_t match_core(match_call& mc) {
       default: redo = false; q0 += s.nq; break;   // SUB_DONE
     }
   }
+  if (mc.floor) ctx->floor_rows.insert(ctx->floor_rows.end(), mc.floor_rows.begin(), mc.floor_rows.end());
   return SHZ_OK;
 }
 
@@ -3108,6 +3189,43 @@ extern "C" int32_t shz_get_vote_tolerance(shz_ctx* ctx, uint32_t* bins) {
   if (!ctx || !bins) return SHZ_E_INVALID;
   *bins = ctx->vote_tol;
   return SHZ_OK;
+}
+extern "C" int32_t shz_set_vote_floor(shz_ctx* ctx, uint32_t on) {
+  if (!ctx) return SHZ_E_INVALID;
+  ctx->vote_floor = on ? 1u : 0u;
+  if (!on) std::vector<uint32_t>().swap(ctx->floor_rows);   // off: the rows not taken are dropped
+  return SHZ_OK;
+}
+extern "C" int32_t shz_get_vote_floor(shz_ctx* ctx, uint32_t* on) {
+  if (!ctx || !on) return SHZ_E_INVALID;
+  *on = ctx->vote_floor;
+  return SHZ_OK;
+}
+extern "C" int32_t shz_vote_floor_rows(shz_ctx* ctx, uint64_t* n) {
+  if (!ctx || !n) return SHZ_E_INVALID;
+  *n = ctx->floor_rows.size() / FH_ROW;
+  return SHZ_OK;
+}
+extern "C" int32_t shz_vote_floor_take(shz_ctx* ctx, uint32_t* song_hist, uint32_t* bin_hist, uint64_t cap, uint64_t* n) {
+  if (!ctx || !n) return SHZ_E_INVALID;
+  const uint64_t rows = ctx->floor_rows.size() / FH_ROW;
+  *n = rows;
+  if (rows > cap) SHZ_FAIL(ctx, SHZ_E_CAPACITY, "shz_vote_floor_take: %llu rows, capacity %llu", (unsigned long long)rows, (unsigned long long)cap);
+  if (rows && (!song_hist || !bin_hist)) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_vote_floor_take: NULL buffer");
+  for (uint64_t q = 0; q < rows; ++q) {
+    memcpy(song_hist + q * FH_BUCKETS, ctx->floor_rows.data() + q * FH_ROW, FH_BUCKETS * 4);
+    memcpy(bin_hist + q * FH_BUCKETS, ctx->floor_rows.data() + q * FH_ROW + FH_BUCKETS, FH_BUCKETS * 4);
+  }
+  ctx->floor_rows.clear();
+  return SHZ_OK;
+}
+extern "C" int32_t shz_vote_bucket(uint32_t count, uint32_t* bucket) {
+  if (!bucket || count == 0) return SHZ_E_INVALID;
+  *bucket = vote_bucket(count);
+  return SHZ_OK;
+}
+void shz_floor_zero_rows(shz_ctx* ctx, uint64_t n) {
+  if (ctx->vote_floor) ctx->floor_rows.resize(ctx->floor_rows.size() + n * FH_ROW, 0u);
 }
 extern "C" int32_t shz_match_vt_redo(shz_ctx* ctx, uint64_t* count) {
   if (!ctx || !count) return SHZ_E_INVALID;
@@ -3263,7 +3381,7 @@ extern "C" int32_t shz_pairs_vote(shz_ctx* ctx, uint64_t* d_pairs, uint64_t n, u
   const uint64_t nres = (uint64_t)n_queries * topn;
   memset(out_sid, 0, nres * 4); memset(out_delta, 0, nres * 4); memset(out_aligned, 0, nres * 4);
   memset(out_dedup, 0, nres * 4); memset(out_nres, 0, (uint64_t)n_queries * 4);
-  if (n == 0) return SHZ_OK;
+  if (n == 0) { shz_floor_zero_rows(ctx, n_queries); return SHZ_OK; }
   if (!d_pairs) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_pairs_vote: NULL votes");
   if ((uintptr_t)d_pairs & 15) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_pairs_vote: the vote buffer must be 16-byte aligned");
   SHZ_HIP(ctx, hipSetDevice(ctx->device));
@@ -3275,10 +3393,18 @@ extern "C" int32_t shz_pairs_vote(shz_ctx* ctx, uint64_t* d_pairs, uint64_t n, u
   SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_PEAK_CLIP, nres * 4, &r_al));
   SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_MISC1, nres * 4, &r_dd));
   SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_MISC2, (uint64_t)n_queries * 4, &r_n));
-  const res_block r{nullptr, (uint32_t*)r_sid, (int32_t*)r_delta, (uint32_t*)r_al, (uint32_t*)r_dd, (uint32_t*)r_n, nullptr,
-                    nullptr};
+  const res_block r_plain{nullptr, (uint32_t*)r_sid, (int32_t*)r_delta, (uint32_t*)r_al, (uint32_t*)r_dd, (uint32_t*)r_n, nullptr,
+                          nullptr};
+  res_block r = r_plain;
+  const uint64_t floor_bytes = (uint64_t)n_queries * FH_ROW * 4;
+  if (ctx->vote_floor) {   // the vote floor: the rows of the gathered votes, as match_core records its own
+    void* fh;
+    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_MISC3, floor_bytes, &fh));
+    SHZ_HIP(ctx, hipMemsetAsync(fh, 0, floor_bytes, ctx->stream));
+    r.hist = (uint32_t*)fh;
+  }
   SHZ_TRY(pv_zero_results(ctx, r, n_queries, nres));
-  const int tol = vote_tol_of(ctx);   // a tolerance: the full sort and the tolerant fold, as in the unsharded match
+  const int tol = vote_tol_of(ctx);   // a tolerance (or the vote floor): the full sort and the tolerant fold, as in the unsharded match
   pv_tiles tiles = PV_NOT_TAKEN;
   if (tol < 0) SHZ_TRY(pairs_vote_tiles(ctx, d_pairs, (uint64_t*)v1, n, n_queries, mb, topn, r, &tiles));
   if (tiles == PV_REDO) SHZ_TRY(pv_zero_results(ctx, r, n_queries, nres));
@@ -3289,6 +3415,12 @@ extern "C" int32_t shz_pairs_vote(shz_ctx* ctx, uint64_t* d_pairs, uint64_t n, u
   SHZ_HIP(ctx, shz_memcpy(ctx, out_aligned, r_al, nres * 4, hipMemcpyDeviceToHost));
   SHZ_HIP(ctx, shz_memcpy(ctx, out_dedup, r_dd, nres * 4, hipMemcpyDeviceToHost));
   SHZ_HIP(ctx, shz_memcpy(ctx, out_nres, r_n, (uint64_t)n_queries * 4, hipMemcpyDeviceToHost));
+  std::vector<uint32_t> rows;
+  if (r.hist) {
+    rows.resize((size_t)n_queries * FH_ROW);
+    SHZ_HIP(ctx, shz_memcpy(ctx, rows.data(), r.hist, floor_bytes, hipMemcpyDeviceToHost));
+  }
   SHZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  ctx->floor_rows.insert(ctx->floor_rows.end(), rows.begin(), rows.end());
   return SHZ_OK;
 }

@@ -174,12 +174,12 @@ class HipFingerprintDB:
         hexes = hex_of_keys(self.ctx, k)
         return [(h.upper(), int(a), int(b)) for h, a, b in zip(hexes, s.tolist(), o.tolist())]  # HEX() upper-cases
 
-    def match(self, key32, q_off, query_off, topn=2, delta_tol=None):
+    def match(self, key32, q_off, query_off, topn=2, delta_tol=None, floor=False):
         """Table.match / ShardedTable.match of the finalized table.  delta_tol: the vote tolerance of this call, None: the
-        context's."""
+        context's.  floor: the result gains song_hist / bin_hist (Table.match)."""
         self.finalize()
         with self.ctx.tolerance(delta_tol):
-            return self.table.match(key32, q_off, query_off, topn)
+            return self.table.match(key32, q_off, query_off, topn, floor=floor)
 
     def match_extents(self, key32, q_off, query_off, cand_sid, d_lo, d_hi, cand_n=None, hist=True):
         """Table.match_extents of the finalized table: where the aligned hashes of the candidates lie; one table only."""

@@ -137,7 +137,7 @@ def _scan_warp_windows(run, tl, pl, t16, f16, row, search):
 @takes_delta_tol(lambda *a, **k: (k["db"] if "db" in k else a[1]).ctx)
 def scan_windows(recordings, db, Fs: int = 44100, window_seconds: float = 5, step_seconds: float = 1, topn: int = TOPN,
                  resample_to: int = None, full_sort: bool = False, speeds=None, tempos=None, pitches=None, warps=None,
-                 search: str = "grid", _extents: dict = None, _fit: dict = None):
+                 search: str = "grid", floor: bool = False, _extents: dict = None, _fit: dict = None):
     """Every window of every recording matched in one library call.  recordings: 1-D int16 arrays, or lists of channels as in
     recognize_batch.  Returns a dict: the arrays of Table.match over all windows, recording-major (sid, delta, aligned, dedup
     [n_windows, topn]; nres, nhash, npairs [n_windows]), plus win_off (CSR of the windows over the recordings), frames (F_r
@@ -161,6 +161,9 @@ def scan_windows(recordings, db, Fs: int = 44100, window_seconds: float = 5, ste
     followed by the stage-2 grid (the tempos x the pitch rungs stage 1 chose), and stage1 / stage2 carry the stages' own
     best / profile / work.
     delta_tol= (keyword): the vote tolerance in offset bins while the call runs (Context.tolerance); None: the context's.
+    floor (the plain scan only: ValueError with speeds=, tempos=, pitches=, warps= or another search): the dict gains song_hist
+    and bin_hist, [n_windows, 32] uint32, recording-major -- the two vote-floor histograms of every window (Context.floor,
+    shazam_amd.floor); the other arrays do not change.
     _fit (scan(extents="fit")): the plays stage of a warped scan runs behind the scan on the same prepared audio -- with
     resample_to= the same device buffer, before it is freed -- and the dict gains "plays" (_play_stage)."""
     from . import DEFAULT_AMP_MIN, DEFAULT_FAN_VALUE, resample_to_device
@@ -169,6 +172,10 @@ def scan_windows(recordings, db, Fs: int = 44100, window_seconds: float = 5, ste
     warped = tempos is not None or pitches is not None or warps is not None or search != "grid"
     if warped and speeds is not None:
         raise ValueError("speeds= is one factor for time and frequency: it excludes tempos=, pitches= and warps=")
+    if floor and (warped or speeds is not None):
+        raise ValueError("floor=True takes the plain scan: not with speeds=, tempos=, pitches=, warps= or another search")
+    if floor and _extents is not None:
+        raise ValueError("floor=True takes the plain scan: not inside the extent call")
     if warped:
         from .speed import _warp_list
         tl, pl, t16, f16, row = _warp_list(tempos, pitches, warps, search)
@@ -192,8 +199,16 @@ def scan_windows(recordings, db, Fs: int = 44100, window_seconds: float = 5, ste
             ms_ = _extents["margin_seconds"]
             margin = wf if ms_ is None else max(0, int(round(float(ms_) * fs / hop)))
             res, win_off, seg, zone, ms = ctx.scan_extents(table, pcm, off, first, wf, sf, _extents["min_aligned"], _extents["max_gap"],
-                                                           margin, ctx.vote_tolerance, fs=fs, **k)
+                                                           margin, ctx.vote_tolerance, fs=fs, keep=_extents.get("keep"), **k)
             res.update(segments=seg, zones=zone, margin_frames=margin)
+            return res, win_off, ms
+    elif floor:       # the rows the call records, one per window in the order of the result arrays
+        def run(*a, **k):
+            with ctx.floor():
+                res, win_off, ms = ctx.scan_batch(*a, **k)
+                res["song_hist"], res["bin_hist"] = ctx.take_floor()
+            if len(res["song_hist"]) != len(res["nres"]):
+                raise RuntimeError(f"vote floor: {len(res['song_hist'])} rows recorded for {len(res['nres'])} windows")
             return res, win_off, ms
     elif speeds is None:
         run = ctx.scan_batch
@@ -309,7 +324,7 @@ def _segment(db, w, seg, i):
 def scan(recordings, db, Fs: int = 44100, window_seconds: float = 5, step_seconds: float = 1, topn: int = TOPN,
          resample_to: int = None, min_aligned: int = 20, max_gap: int = 1, speeds=None, shift_tol: int = None, rung_tol: int = 1,
          tempos=None, pitches=None, warps=None, search: str = "grid", tempo_tol: int = None, pitch_tol: int = None,
-         extents=False, margin_seconds: float = None, drift_bins: int = None):
+         extents=False, margin_seconds: float = None, drift_bins: int = None, min_score: float = None):
     """The timeline of every recording: a list (per recording) of segments, each a dict with song_id, song_name,
     start_seconds / end_seconds (the span of the segment's windows in the recording, the last window's end clipped to the
     recording's), offset_seconds (the position in the song at the segment's start: align_matches' formula,
@@ -355,8 +370,18 @@ def scan(recordings, db, Fs: int = 44100, window_seconds: float = 5, step_second
     play), extent_hist / extent_shift / extent_lo (bucket b of the whole-play zone holds the warped frames W(extent_lo) + [b <<
     shift, (b + 1) << shift), W with the segment's time factor), fit (count, the four sums and d_lo of the whole play:
     extent.line_fit's arguments) and play_tempo (extent.tempo_of on the fitted slope, as a float; None without a fit) -- under
-    speeds= the key is play_speed."""
+    speeds= the key is play_speed.
+    min_score (the plain scan, with or without extents=True; ValueError with a ladder): a window counts only if its best
+    candidate ALSO scores at least min_score -- shazam_amd.floor.score of its aligned count against the window's own song
+    histogram (scan_windows(floor=True)), a heuristic measured on synthetic audio only.  A window whose
+    score is None (nothing to compare against) counts: min_aligned alone decides there.  The windows below it have their
+    nres cleared before the timeline.  With extents=True, whose timeline is folded inside the library call, the windows are
+    scanned once with the floor on and the extent call then runs with a keep mask of them (SHZ_SCAN_KEEP_MASK): two scans.
+    None, the default: no such test, the call as it always was."""
     from . import OFFSET_SECS
+    if min_score is not None:
+        if speeds is not None or tempos is not None or pitches is not None or warps is not None or search != "grid":
+            raise ValueError("min_score takes the plain scan: not with speeds=, tempos=, pitches=, warps= or another search")
     ladder = speeds is not None or tempos is not None or pitches is not None or warps is not None or search != "grid"
     fit = None
     if isinstance(extents, str):
@@ -368,7 +393,8 @@ def scan(recordings, db, Fs: int = 44100, window_seconds: float = 5, step_second
     elif extents:
         if ladder:
             raise ValueError('extents=True takes the plain scan: a warped scan takes extents="fit" (DESIGN.md 3.7n)')
-        return _scan_extents(recordings, db, Fs, window_seconds, step_seconds, topn, resample_to, min_aligned, max_gap, margin_seconds)
+        return _scan_extents(recordings, db, Fs, window_seconds, step_seconds, topn, resample_to, min_aligned, max_gap, margin_seconds,
+                             min_score)
     if tempos is not None or pitches is not None or warps is not None or search != "grid":
         if speeds is not None:
             raise ValueError("speeds= is one factor for time and frequency: it excludes tempos=, pitches= and warps=")
@@ -379,8 +405,12 @@ def scan(recordings, db, Fs: int = 44100, window_seconds: float = 5, step_second
     if speeds is not None:
         return _scan_speeds(recordings, db, Fs, window_seconds, step_seconds, topn, resample_to, min_aligned, max_gap, speeds,
                             shift_tol, rung_tol, fit)
-    w = scan_windows(recordings, db, Fs, window_seconds, step_seconds, topn, resample_to)
-    seg = _ffi.scan_timeline(w["win_off"], w["sid"], w["delta"], w["aligned"], w["nres"], w["step_frames"], min_aligned, max_gap)
+    w = scan_windows(recordings, db, Fs, window_seconds, step_seconds, topn, resample_to, floor=min_score is not None)
+    nres = w["nres"]
+    if min_score is not None:      # windows below the score are cleared before the timeline, which stays as it is
+        from .floor import keep_windows
+        nres = keep_windows(nres, w["aligned"], w["song_hist"], float(min_score))
+    seg = _ffi.scan_timeline(w["win_off"], w["sid"], w["delta"], w["aligned"], nres, w["step_frames"], min_aligned, max_gap)
     out = [[] for _ in range(len(w["frames"]))]
     for i in range(len(seg["rec"])):
         first, shift = int(seg["first"][i]), int(seg["shift"][i])
@@ -390,11 +420,17 @@ def scan(recordings, db, Fs: int = 44100, window_seconds: float = 5, step_second
     return out
 
 
-def _scan_extents(recordings, db, Fs, window_seconds, step_seconds, topn, resample_to, min_aligned, max_gap, margin_seconds):
+def _scan_extents(recordings, db, Fs, window_seconds, step_seconds, topn, resample_to, min_aligned, max_gap, margin_seconds,
+                  min_score=None):
     from . import OFFSET_SECS
     from .extent import dense_span
+    keep = None
+    if min_score is not None:      # the windows judged on a scan with the floor on; the extent call keeps the rest
+        from .floor import keep_windows
+        f = scan_windows(recordings, db, Fs, window_seconds, step_seconds, topn, resample_to, floor=True)
+        keep = (keep_windows(f["nres"], f["aligned"], f["song_hist"], float(min_score)) > 0) | (f["nres"] == 0)
     w = scan_windows(recordings, db, Fs, window_seconds, step_seconds, topn, resample_to,
-                     _extents=dict(min_aligned=int(min_aligned), max_gap=int(max_gap), margin_seconds=margin_seconds))
+                     _extents=dict(min_aligned=int(min_aligned), max_gap=int(max_gap), margin_seconds=margin_seconds, keep=keep))
     seg, zone = w["segments"], w["zones"]
     hop, fs = w["hop"], w["fs"]
     secs = lambda frame: round(frame * hop / fs, 5)                              # noqa: E731  (as _segment converts)

@@ -204,12 +204,16 @@ class ShardedTable:
             self._pbuf.free()
         self._pbuf, self._pcap = self.ctx.alloc(cap * 8), cap
 
-    def match(self, key32, q_off, query_off, topn=2, delta_tol=None):
+    def match(self, key32, q_off, query_off, topn=2, delta_tol=None, floor=False):
         """Same result dict as ``Table.match`` on the union of all shards.  Like ``Table.match``, queries whose votes do
         not fit one 64-bit key together are matched in halves; a query with hashes that does not fit alone raises.
-        delta_tol: the vote tolerance of this call (the gathered votes are folded by it), None: the context's."""
-        if delta_tol is not None:
-            with self.ctx.tolerance(delta_tol):
+        delta_tol: the vote tolerance of this call (the gathered votes are folded by it), None: the context's.
+        floor: the result gains song_hist / bin_hist as ``Table.match``'s does -- the histograms of the gathered votes
+        (shz_pairs_vote records them; with a communicator every rank gets them), equal to the unsharded table's.
+        With the floor on (this argument, or Context.set_vote_floor by hand) the call takes the context's row store whole: rows
+        recorded before it and not yet taken are dropped (Context.floor)."""
+        if delta_tol is not None or floor:
+            with self.ctx.tolerance(delta_tol), self.ctx.floor(floor):
                 return self.match(key32, q_off, query_off, topn)
         k = np.ascontiguousarray(key32, np.uint32)
         o = np.ascontiguousarray(q_off, np.uint32)
@@ -222,6 +226,9 @@ class ShardedTable:
         res = {"sid": np.zeros((nq, topn), np.uint32), "delta": np.zeros((nq, topn), np.int32),
                "aligned": np.zeros((nq, topn), np.uint32), "dedup": np.zeros((nq, topn), np.uint32),
                "nres": np.zeros(nq, np.uint32), "nhash": np.zeros(nq, np.uint32), "npairs": np.zeros(nq, np.uint64)}
+        if self.ctx.vote_floor:                         # (queries without hashes are never voted: their rows stay zero)
+            res["song_hist"], res["bin_hist"] = np.zeros((nq, 32), np.uint32), np.zeros((nq, 32), np.uint32)
+            self.ctx.take_floor()                       # the rows of this call only
         self.last_votes = 0
         todo = [(0, nq)] if nq else []
         while todo:                                     # ranges of queries, in order (with a communicator: SPMD)
@@ -265,6 +272,8 @@ class ShardedTable:
             self.last_votes += total
             # nhash / npairs: this rank's share; their sum over the ranks is the unsharded table's value
         res["nhash"], res["npairs"] = nhash, npairs
+        if ctx.vote_floor:
+            res["song_hist"], res["bin_hist"] = ctx.take_floor()
         return res
 
     # -- the rest of Table's surface (shards on this GPU only) ------------------------------------
