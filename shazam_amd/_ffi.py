@@ -837,59 +837,79 @@ class Context:
         res = self._windows_with_room(call, lambda n: _match_result(n, topn), cnt, cap_windows)
         return res, wo, tuple(float(m.value) for m in ms)
 
-    # ---- repeated content inside recordings (shz_repeat.hip) -----------------------------------------------------------
-    def _repeats_call(self, fn, nr, cap_cells, fill):
-        """The outputs of shz_repeats_hashes / shz_repeats_batch and their capacity idiom.  fn(out, cap, cnt) -> rc.  cap_cells
-        None: a first call with no room names the count, a second one has it; a number: that one call as it is.  fill: what
-        the arrays hold beforehand (tests).  Returns (rc, out, count): out = cell_off, the CELL_FIELDS arrays (cut to the cells
-        written), rec_hashes, rec_skipped_keys, rec_pairs, rec_skipped_rows."""
-        def room(cap):
-            out = {k: np.full(int(cap), fill, np.uint32) for k in CELL_FIELDS}
-            out.update(cell_off=np.full(nr + 1, fill, np.uint64), rec_hashes=np.full(nr, fill, np.uint32),
-                       rec_skipped_keys=np.full(nr, fill, np.uint32), rec_pairs=np.full(nr, fill, np.uint64),
-                       rec_skipped_rows=np.full(nr, fill, np.uint64))
-            return out
-        return self._cells_call(fn, room, cap_cells, fill)
+    # ---- the calls that return cells (shz_repeat.hip): repeats inside recordings, content shared between recordings, and that
+    # at a table of warps.  Per family: what owns the cells (cell_off runs over it), and the arrays behind the cell arrays in
+    # the order of the ABI -- name, dtype, what they run over
+    _CELL_CALLS = {
+        "repeats": ("rec", (("rec_hashes", np.uint32, "rec"), ("rec_skipped_keys", np.uint32, "rec"), ("rec_pairs", np.uint64, "rec"),
+                            ("rec_skipped_rows", np.uint64, "rec"))),
+        "shared": ("job", (("rec_hashes", np.uint32, "rec"), ("job_pairs", np.uint64, "job"), ("job_skipped_keys", np.uint32, "job"),
+                           ("job_skipped_rows", np.uint64, "job"))),
+        "shared_warps": ("job", (("rec_hashes", np.uint32, "rec"), ("job_hashes", np.uint32, "job"), ("job_pairs", np.uint64, "job"),
+                                 ("job_skipped_keys", np.uint32, "job"), ("job_skipped_rows", np.uint64, "job"))),
+    }
 
-    def _cells_call(self, fn, room, cap_cells, fill):
-        """The capacity idiom of the calls that return cells: room(cap) -> the output arrays with room for cap cells."""
+    def _cells_call(self, family, fn, nr, nj, cap_cells, fill, n_ms=0):
+        """One call that returns cells and its capacity idiom.  fn(outs, tail) -> rc makes the library call: outs are the output
+        arrays and the room as the ABI orders them, tail the count and the n_ms times behind them.  cap_cells None: a first call
+        with no room names the count, a second one has it, checked; a number: that one call as it is.  fill: what the arrays
+        hold beforehand (tests).  Returns (rc, out, count), and with n_ms (rc, out, count, ms): out = the CELL_FIELDS arrays (cut
+        to the cells written; lag BIASED by SHARED_LAG_BIAS in the shared families, as the library returns it), cell_off over
+        the family's owners, and the family's arrays per recording and per job; ms = the device times of the last call."""
+        owner, arrays = self._CELL_CALLS[family]
+        size = {"rec": nr, "job": nj}
         cnt = C.c_uint64(fill)
+        ms = [C.c_float(float(np.float32(fill))) for _ in range(n_ms)]
+
+        def call(cap):
+            out = {k: np.full(int(cap), fill, np.uint32) for k in CELL_FIELDS}
+            out["cell_off"] = np.full(size[owner] + 1, fill, np.uint64)
+            out.update((name, np.full(size[over], fill, dtype)) for name, dtype, over in arrays)
+            outs = [ptr(out["cell_off"]), *[ptr(out[k]) if cap else None for k in CELL_FIELDS], *[ptr(out[a[0]]) for a in arrays], int(cap)]
+            return fn(outs, [C.byref(cnt), *[C.byref(m) for m in ms]]), out
         if cap_cells is None:
-            out = room(0)
-            rc = fn(out, 0, cnt)
+            rc, out = call(0)
             if rc == E_CAPACITY:
-                out = room(int(cnt.value))
-                rc = fn(out, int(cnt.value), cnt)
+                rc, out = call(int(cnt.value))
             self.check(rc)
         else:
-            out = room(cap_cells)
-            rc = fn(out, int(cap_cells), cnt)
+            rc, out = call(cap_cells)
         n = int(cnt.value)
         if rc in (OK, E_CAPACITY):
             for k in CELL_FIELDS:
                 out[k] = out[k][:min(n, len(out[k]))]
-        return rc, out, n
+        return (rc, out, n, tuple(float(m.value) for m in ms)) if n_ms else (rc, out, n)
+
+    def _cells_with_room(self, raw, args, cap_cells):
+        """A fused *_raw call with the room of the first call given: repeated once with the count it named, checked -> (out, ms)"""
+        rc, out, n, ms = raw(*args, cap_cells)                         # (cap_cells None: both calls, checked)
+        if rc == E_CAPACITY:
+            rc, out, n, ms = raw(*args, n)
+        self.check(rc)
+        return out, ms
 
     @staticmethod
-    def _repeat_outs(out, cap):
-        cells = [ptr(out[k]) if cap else None for k in CELL_FIELDS]
-        return [ptr(out["cell_off"]), *cells, ptr(out["rec_hashes"]), ptr(out["rec_skipped_keys"]), ptr(out["rec_pairs"]),
-                ptr(out["rec_skipped_rows"])]
+    def _host_columns(a, dtype_a, b, off, rec_clip0):
+        """Two host columns, their CSR over the clips and the recordings' CSR as the ABI takes them; n_clips, n_recs"""
+        off, rc0 = np.ascontiguousarray(off, np.uint64), np.ascontiguousarray(rec_clip0, np.uint32)
+        return np.ascontiguousarray(a, dtype_a), np.ascontiguousarray(b, np.uint32), off, rc0, len(off) - 1, len(rc0) - 1
 
+    def _pcm_clips(self, clip_off, rec_clip0):
+        """clip_off and the recordings' CSR as the ABI takes them; n_clips, n_recs"""
+        co, nc = self._clip_off(clip_off)
+        rc0 = np.ascontiguousarray(rec_clip0, np.uint32)
+        return co, rc0, nc, len(rc0) - 1
+
+    # ---- repeated content inside recordings ------------------------------------------------------------------------------
     def repeats_hashes_raw(self, key32, t1, hash_off, rec_clip0, min_lag, max_lag, max_run=64, cell_shift=5, min_cell_pairs=8,
                            flags=0, cap_cells=None, fill=0):
-        """One shz_repeats_hashes as it is on HOST columns: (rc, out, count) -- see _repeats_call."""
-        k = np.ascontiguousarray(key32, np.uint32)
-        t = np.ascontiguousarray(t1, np.uint32)
-        ho = np.ascontiguousarray(hash_off, np.uint64)
-        rc0 = np.ascontiguousarray(rec_clip0, np.uint32)
-        nc, nr = len(ho) - 1, len(rc0) - 1
+        """One shz_repeats_hashes as it is on HOST columns: (rc, out, count) -- see _cells_call."""
+        k, t, ho, rc0, nc, nr = self._host_columns(key32, np.uint32, t1, hash_off, rec_clip0)
 
-        def fn(out, cap, cnt):
+        def fn(outs, tail):
             return lib().shz_repeats_hashes(self.h, ptr(k), ptr(t), ptr(ho), nc, ptr(rc0), nr, int(min_lag), int(max_lag),
-                                            int(max_run), int(cell_shift), int(min_cell_pairs), int(flags),
-                                            *self._repeat_outs(out, cap), int(cap), C.byref(cnt))
-        return self._repeats_call(fn, nr, cap_cells, fill)
+                                            int(max_run), int(cell_shift), int(min_cell_pairs), int(flags), *outs, *tail)
+        return self._cells_call("repeats", fn, nr, 0, cap_cells, fill)
 
     def repeats_hashes(self, key32, t1, hash_off, rec_clip0, min_lag, max_lag, max_run=64, cell_shift=5, min_cell_pairs=8):
         """shz_repeats_hashes (two calls): the repeat cells of recordings given as fingerprints -- host columns key32 / t1,
@@ -901,20 +921,15 @@ class Context:
 
     def repeats_batch_raw(self, pcm, clip_off, rec_clip0, min_lag, max_lag, max_run=64, cell_shift=5, min_cell_pairs=8, fs=44100,
                           amp_min=10.0, fan_value=5, pcm_device=False, cap_cells=None, fill=0):
-        """One shz_repeats_batch as it is: (rc, out, count, ms) -- out as _repeats_call, ms = (extract, pairs, cells) device
+        """One shz_repeats_batch as it is: (rc, out, count, ms) -- out as _cells_call, ms = (extract, pairs, cells) device
         times of the last call."""
-        co, nc = self._clip_off(clip_off)
-        rc0 = np.ascontiguousarray(rec_clip0, np.uint32)
-        nr = len(rc0) - 1
-        ms = [C.c_float(float(np.float32(fill))) for _ in range(3)]
+        co, rc0, nc, nr = self._pcm_clips(clip_off, rec_clip0)
 
-        def fn(out, cap, cnt):
+        def fn(outs, tail):
             return lib().shz_repeats_batch(self.h, ptr(pcm), ptr(co), nc, ptr(rc0), nr, int(fs), float(amp_min), int(fan_value),
                                            int(min_lag), int(max_lag), int(max_run), int(cell_shift), int(min_cell_pairs),
-                                           PCM_DEVICE if pcm_device else 0, *self._repeat_outs(out, cap), int(cap), C.byref(cnt),
-                                           *[C.byref(m) for m in ms])
-        rc, out, n = self._repeats_call(fn, nr, cap_cells, fill)
-        return rc, out, n, tuple(float(m.value) for m in ms)
+                                           PCM_DEVICE if pcm_device else 0, *outs, *tail)
+        return self._cells_call("repeats", fn, nr, 0, cap_cells, fill, n_ms=3)
 
     def repeats_batch(self, pcm, clip_off, rec_clip0, min_lag, max_lag, max_run=64, cell_shift=5, min_cell_pairs=8, fs=44100,
                       amp_min=10.0, fan_value=5, pcm_device=False, cap_cells=None):
@@ -923,31 +938,9 @@ class Context:
         for the count, then one with that room -- the audio is fingerprinted twice; a number large enough: one call).  Returns
         (out, ms): out as repeats_hashes, ms = (extract, pairs, cells) device times."""
         args = (pcm, clip_off, rec_clip0, min_lag, max_lag, max_run, cell_shift, min_cell_pairs, fs, amp_min, fan_value, pcm_device)
-        rc, out, n, ms = self.repeats_batch_raw(*args, cap_cells)      # (cap_cells None: both calls, checked)
-        if rc == E_CAPACITY:
-            rc, out, n, ms = self.repeats_batch_raw(*args, n)
-        self.check(rc)
-        return out, ms
+        return self._cells_with_room(self.repeats_batch_raw, args, cap_cells)
 
-    # ---- content shared between recordings (shz_repeat.hip: the job form of the join) ------------------------------------
-    def _shared_call(self, fn, nr, nj, cap_cells, fill):
-        """The outputs of shz_shared_hashes / shz_shared_batch and their capacity idiom, as _repeats_call.  Returns (rc, out,
-        count): out = cell_off (over the JOBS), the CELL_FIELDS arrays (lag BIASED by SHARED_LAG_BIAS, as the library returns
-        it), rec_hashes, job_pairs, job_skipped_keys, job_skipped_rows."""
-        def room(cap):
-            out = {k: np.full(int(cap), fill, np.uint32) for k in CELL_FIELDS}
-            out.update(cell_off=np.full(nj + 1, fill, np.uint64), rec_hashes=np.full(nr, fill, np.uint32),
-                       job_pairs=np.full(nj, fill, np.uint64), job_skipped_keys=np.full(nj, fill, np.uint32),
-                       job_skipped_rows=np.full(nj, fill, np.uint64))
-            return out
-        return self._cells_call(fn, room, cap_cells, fill)
-
-    @staticmethod
-    def _shared_outs(out, cap):
-        cells = [ptr(out[k]) if cap else None for k in CELL_FIELDS]
-        return [ptr(out["cell_off"]), *cells, ptr(out["rec_hashes"]), ptr(out["job_pairs"]), ptr(out["job_skipped_keys"]),
-                ptr(out["job_skipped_rows"])]
-
+    # ---- content shared between recordings (the job form of the join) ----------------------------------------------------
     @staticmethod
     def _jobs(jobs):
         """(a, b) pairs -> the two uint32 columns of the ABI"""
@@ -956,19 +949,14 @@ class Context:
 
     def shared_hashes_raw(self, key32, t1, hash_off, rec_clip0, jobs, lag_lo, lag_hi, max_run=64, cell_shift=5, min_cell_pairs=8,
                           flags=0, cap_cells=None, fill=0):
-        """One shz_shared_hashes as it is on HOST columns: (rc, out, count) -- see _shared_call.  jobs: (a, b) pairs."""
-        k = np.ascontiguousarray(key32, np.uint32)
-        t = np.ascontiguousarray(t1, np.uint32)
-        ho = np.ascontiguousarray(hash_off, np.uint64)
-        rc0 = np.ascontiguousarray(rec_clip0, np.uint32)
+        """One shz_shared_hashes as it is on HOST columns: (rc, out, count) -- see _cells_call.  jobs: (a, b) pairs."""
+        k, t, ho, rc0, nc, nr = self._host_columns(key32, np.uint32, t1, hash_off, rec_clip0)
         ja, jb = self._jobs(jobs)
-        nc, nr, nj = len(ho) - 1, len(rc0) - 1, len(ja)
 
-        def fn(out, cap, cnt):
-            return lib().shz_shared_hashes(self.h, ptr(k), ptr(t), ptr(ho), nc, ptr(rc0), nr, ptr(ja), ptr(jb), nj, int(lag_lo),
-                                           int(lag_hi), int(max_run), int(cell_shift), int(min_cell_pairs), int(flags),
-                                           *self._shared_outs(out, cap), int(cap), C.byref(cnt))
-        return self._shared_call(fn, nr, nj, cap_cells, fill)
+        def fn(outs, tail):
+            return lib().shz_shared_hashes(self.h, ptr(k), ptr(t), ptr(ho), nc, ptr(rc0), nr, ptr(ja), ptr(jb), len(ja), int(lag_lo),
+                                           int(lag_hi), int(max_run), int(cell_shift), int(min_cell_pairs), int(flags), *outs, *tail)
+        return self._cells_call("shared", fn, nr, len(ja), cap_cells, fill)
 
     def shared_hashes(self, key32, t1, hash_off, rec_clip0, jobs, lag_lo, lag_hi, max_run=64, cell_shift=5, min_cell_pairs=8):
         """shz_shared_hashes (two calls): the cells of content shared between recordings given as fingerprints -- host columns
@@ -981,21 +969,16 @@ class Context:
 
     def shared_batch_raw(self, pcm, clip_off, rec_clip0, jobs, lag_lo, lag_hi, max_run=64, cell_shift=5, min_cell_pairs=8, fs=44100,
                          amp_min=10.0, fan_value=5, pcm_device=False, cap_cells=None, fill=0):
-        """One shz_shared_batch as it is: (rc, out, count, ms) -- out as _shared_call, ms = (extract, pairs, cells) device times
+        """One shz_shared_batch as it is: (rc, out, count, ms) -- out as _cells_call, ms = (extract, pairs, cells) device times
         of the last call."""
-        co, nc = self._clip_off(clip_off)
-        rc0 = np.ascontiguousarray(rec_clip0, np.uint32)
+        co, rc0, nc, nr = self._pcm_clips(clip_off, rec_clip0)
         ja, jb = self._jobs(jobs)
-        nr, nj = len(rc0) - 1, len(ja)
-        ms = [C.c_float(float(np.float32(fill))) for _ in range(3)]
 
-        def fn(out, cap, cnt):
+        def fn(outs, tail):
             return lib().shz_shared_batch(self.h, ptr(pcm), ptr(co), nc, ptr(rc0), nr, int(fs), float(amp_min), int(fan_value),
-                                          ptr(ja), ptr(jb), nj, int(lag_lo), int(lag_hi), int(max_run), int(cell_shift),
-                                          int(min_cell_pairs), PCM_DEVICE if pcm_device else 0, *self._shared_outs(out, cap), int(cap),
-                                          C.byref(cnt), *[C.byref(m) for m in ms])
-        rc, out, n = self._shared_call(fn, nr, nj, cap_cells, fill)
-        return rc, out, n, tuple(float(m.value) for m in ms)
+                                          ptr(ja), ptr(jb), len(ja), int(lag_lo), int(lag_hi), int(max_run), int(cell_shift),
+                                          int(min_cell_pairs), PCM_DEVICE if pcm_device else 0, *outs, *tail)
+        return self._cells_call("shared", fn, nr, len(ja), cap_cells, fill, n_ms=3)
 
     def shared_batch(self, pcm, clip_off, rec_clip0, jobs, lag_lo, lag_hi, max_run=64, cell_shift=5, min_cell_pairs=8, fs=44100,
                      amp_min=10.0, fan_value=5, pcm_device=False, cap_cells=None):
@@ -1003,29 +986,9 @@ class Context:
         every job (a, b) in one call, the hashes staying on the device.  cap_cells as repeats_batch.  Returns (out, ms): out as
         shared_hashes, ms = (extract, pairs, cells) device times."""
         args = (pcm, clip_off, rec_clip0, jobs, lag_lo, lag_hi, max_run, cell_shift, min_cell_pairs, fs, amp_min, fan_value, pcm_device)
-        rc, out, n, ms = self.shared_batch_raw(*args, cap_cells)       # (cap_cells None: both calls, checked)
-        if rc == E_CAPACITY:
-            rc, out, n, ms = self.shared_batch_raw(*args, n)
-        self.check(rc)
-        return out, ms
+        return self._cells_with_room(self.shared_batch_raw, args, cap_cells)
 
-    # ---- altered content shared between recordings (shz_repeat.hip: the join at a table of warps) ------------------------
-    def _shared_warps_call(self, fn, nr, nj, cap_cells, fill):
-        """_shared_call with job_hashes beside the job_* arrays"""
-        def room(cap):
-            out = {k: np.full(int(cap), fill, np.uint32) for k in CELL_FIELDS}
-            out.update(cell_off=np.full(nj + 1, fill, np.uint64), rec_hashes=np.full(nr, fill, np.uint32),
-                       job_hashes=np.full(nj, fill, np.uint32), job_pairs=np.full(nj, fill, np.uint64),
-                       job_skipped_keys=np.full(nj, fill, np.uint32), job_skipped_rows=np.full(nj, fill, np.uint64))
-            return out
-        return self._cells_call(fn, room, cap_cells, fill)
-
-    @staticmethod
-    def _shared_warps_outs(out, cap):
-        cells = [ptr(out[k]) if cap else None for k in CELL_FIELDS]
-        return [ptr(out["cell_off"]), *cells, ptr(out["rec_hashes"]), ptr(out["job_hashes"]), ptr(out["job_pairs"]),
-                ptr(out["job_skipped_keys"]), ptr(out["job_skipped_rows"])]
-
+    # ---- altered content shared between recordings (the join at a table of warps) ----------------------------------------
     @staticmethod
     def _warp_jobs(jobs, tempos, pitches):
         """jobs (a, b, v, lag_lo, lag_hi) -> the five columns of the ABI; the warp table as two uint32 columns"""
@@ -1038,20 +1001,17 @@ class Context:
 
     def shared_warps_peaks_raw(self, peak_f, peak_t, peak_off, rec_clip0, tempos, pitches, jobs, max_run=64, cell_shift=5,
                                min_cell_pairs=8, fan_value=5, flags=0, cap_cells=None, fill=0):
-        """One shz_shared_warps_peaks as it is on HOST peak lists: (rc, out, count) -- out as _shared_call plus job_hashes.
+        """One shz_shared_warps_peaks as it is on HOST peak lists: (rc, out, count) -- out as _cells_call, job_hashes among it.
         jobs: (a, b, v, lag_lo, lag_hi) tuples; warp v is (tempos[v], pitches[v]), Q16."""
-        pf, pt = np.ascontiguousarray(peak_f, np.uint16), np.ascontiguousarray(peak_t, np.uint32)
-        po = np.ascontiguousarray(peak_off, np.uint64)
-        rc0 = np.ascontiguousarray(rec_clip0, np.uint32)
+        pf, pt, po, rc0, nc, nr = self._host_columns(peak_f, np.uint16, peak_t, peak_off, rec_clip0)
         cols, tq, fq = self._warp_jobs(jobs, tempos, pitches)
-        nc, nr, nj = len(po) - 1, len(rc0) - 1, len(cols[0])
+        nj = len(cols[0])
 
-        def fn(out, cap, cnt):
+        def fn(outs, tail):
             return lib().shz_shared_warps_peaks(self.h, ptr(pf), ptr(pt), ptr(po), nc, ptr(rc0), nr, int(fan_value), ptr(tq), ptr(fq),
                                                 len(tq), *[ptr(c) for c in cols], nj, int(max_run), int(cell_shift),
-                                                int(min_cell_pairs), int(flags), *self._shared_warps_outs(out, cap), int(cap),
-                                                C.byref(cnt))
-        return self._shared_warps_call(fn, nr, nj, cap_cells, fill)
+                                                int(min_cell_pairs), int(flags), *outs, *tail)
+        return self._cells_call("shared_warps", fn, nr, nj, cap_cells, fill)
 
     def shared_warps_peaks(self, peak_f, peak_t, peak_off, rec_clip0, tempos, pitches, jobs, max_run=64, cell_shift=5,
                            min_cell_pairs=8, fan_value=5):
@@ -1068,19 +1028,15 @@ class Context:
                                fs=44100, amp_min=10.0, fan_value=5, pcm_device=False, cap_cells=None, fill=0):
         """One shz_shared_warps_batch as it is: (rc, out, count, ms) -- ms = (extract, warp, pairs, cells) device times of the
         last call."""
-        co, nc = self._clip_off(clip_off)
-        rc0 = np.ascontiguousarray(rec_clip0, np.uint32)
+        co, rc0, nc, nr = self._pcm_clips(clip_off, rec_clip0)
         cols, tq, fq = self._warp_jobs(jobs, tempos, pitches)
-        nr, nj = len(rc0) - 1, len(cols[0])
-        ms = [C.c_float(float(np.float32(fill))) for _ in range(4)]
+        nj = len(cols[0])
 
-        def fn(out, cap, cnt):
+        def fn(outs, tail):
             return lib().shz_shared_warps_batch(self.h, ptr(pcm), ptr(co), nc, ptr(rc0), nr, int(fs), float(amp_min), int(fan_value),
                                                 ptr(tq), ptr(fq), len(tq), *[ptr(c) for c in cols], nj, int(max_run), int(cell_shift),
-                                                int(min_cell_pairs), PCM_DEVICE if pcm_device else 0,
-                                                *self._shared_warps_outs(out, cap), int(cap), C.byref(cnt), *[C.byref(m) for m in ms])
-        rc, out, n = self._shared_warps_call(fn, nr, nj, cap_cells, fill)
-        return rc, out, n, tuple(float(m.value) for m in ms)
+                                                int(min_cell_pairs), PCM_DEVICE if pcm_device else 0, *outs, *tail)
+        return self._cells_call("shared_warps", fn, nr, nj, cap_cells, fill, n_ms=4)
 
     def shared_warps_batch(self, pcm, clip_off, rec_clip0, tempos, pitches, jobs, max_run=64, cell_shift=5, min_cell_pairs=8,
                            fs=44100, amp_min=10.0, fan_value=5, pcm_device=False, cap_cells=None):
@@ -1088,11 +1044,7 @@ class Context:
         name, and the cells of every job in one call, the hashes staying on the device.  cap_cells as repeats_batch.  Returns
         (out, ms): out as shared_warps_peaks, ms = (extract, warp, pairs, cells) device times."""
         args = (pcm, clip_off, rec_clip0, tempos, pitches, jobs, max_run, cell_shift, min_cell_pairs, fs, amp_min, fan_value, pcm_device)
-        rc, out, n, ms = self.shared_warps_batch_raw(*args, cap_cells)  # (cap_cells None: both calls, checked)
-        if rc == E_CAPACITY:
-            rc, out, n, ms = self.shared_warps_batch_raw(*args, n)
-        self.check(rc)
-        return out, ms
+        return self._cells_with_room(self.shared_warps_batch_raw, args, cap_cells)
 
     def scan_extents_raw(self, table: "Table", pcm, clip_off, rec_clip0, window_frames, step_frames, min_aligned, max_gap=1,
                          margin_frames=0, d_tol=0, fs=44100, amp_min=10.0, fan_value=5, topn=2, pcm_device=False, full_sort=False,

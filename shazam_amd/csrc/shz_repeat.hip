@@ -22,6 +22,11 @@
 // item in b's run of its key (sh_count_kernel), pairs job << 41 | (lag + 2^20) << 20 | t_a by output tile (sh_expand_kernel),
 // and from there the cell stage above with a lag field of 21 bits (rp_cells).
 //
+// On the host both joins (rp_core, sh_core) are the same list of stages around their own count and expand launches: the header
+// block of the call (rp_header), the elements (rp_elements), the owners' pairs (rp_owner_pairs: scan, pairs in front of every
+// recording or job, the one read-back) and the slices with the cells and the outputs (rp_slices, rp_cells), all timed on one
+// clock (rp_clock).  The searches of the kernels are rp_last_le and rp_bound.
+//
 // ALTERED shared content (shz_shared_warps_*) is that join at a table of warps: one warp pass in the job form
 // (shz_speed.hip) over every clip as it is and over the clips of every distinct (recording, warp) the jobs name, its columns
 // handed to sh_core as virtual recordings, and a lag window per job in sh_count_kernel.
@@ -40,10 +45,12 @@
 struct rp_params {
   uint32_t min_lag, max_lag, max_run, cell_shift, min_cell_pairs;
 };
+// the outputs of every call of the family.  The OWNERS of pairs and cells are the recordings (shz_repeats_*) or the jobs
+// (shz_shared_*): cell_off and the owner_* arrays run over them, rec_hashes over the recordings
 struct rp_out {
   uint64_t* cell_off;
-  uint32_t *cell_lag, *cell_block, *cell_pairs, *cell_first, *cell_last, *rec_hashes, *rec_skipped_keys;
-  uint64_t *rec_pairs, *rec_skipped_rows, cap_cells, *count;
+  uint32_t *cell_lag, *cell_block, *cell_pairs, *cell_first, *cell_last, *rec_hashes, *owner_skipped_keys;
+  uint64_t *owner_pairs, *owner_skipped_rows, cap_cells, *count;
 };
 
 static inline unsigned rp_grid(uint64_t n, uint32_t bs) { return (unsigned)((n + bs - 1) / bs); }
@@ -54,17 +61,31 @@ static inline int rp_bits(uint32_t v) {   // bits that hold the values 0 .. v
 }
 
 // ---- kernels ------------------------------------------------------------------------------------------------------------
+// the last index i of [l, h) with a[i] <= v, in an ascending a with a[l] <= v (l when h - l < 2)
+template <class T>
+__device__ __forceinline__ uint32_t rp_last_le(const T* __restrict__ a, uint32_t l, uint32_t h, T v) {
+  while (h - l > 1) {
+    const uint32_t mid = l + ((h - l) >> 1);
+    if (a[mid] <= v) l = mid; else h = mid;
+  }
+  return l;
+}
+// the first index i of [l, r) with key(i) >= v -- past: with key(i) > v -- where key ascends over [l, r); r when there is none
+template <bool past, class V, class K>
+__device__ __forceinline__ uint32_t rp_bound(uint32_t l, uint32_t r, V v, K key) {
+  while (l < r) {
+    const uint32_t mid = l + ((r - l) >> 1);
+    if (past ? key(mid) <= v : key(mid) < v) l = mid + 1; else r = mid;
+  }
+  return l;
+}
 // rec_off[n_recs + 1]: first hash of every recording; entry i belongs to the last r with rec_off[r] <= i
 __global__ __launch_bounds__(RP_THREADS) void rp_compose_kernel(const uint32_t* __restrict__ key32, const uint32_t* __restrict__ t1,
                                                                 const uint64_t* __restrict__ rec_off, uint32_t n_recs, uint64_t n,
                                                                 uint64_t* __restrict__ out) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  uint32_t lo = 0, hi = n_recs;
-  while (hi - lo > 1) {
-    const uint32_t mid = lo + ((hi - lo) >> 1);
-    if (rec_off[mid] <= i) lo = mid; else hi = mid;
-  }
+  const uint32_t lo = rp_last_le(rec_off, 0u, n_recs, i);
   out[i] = ((uint64_t)lo << 52) | ((uint64_t)key32[i] << RP_T_BITS) | (t1[i] & RP_T_MASK);
 }
 
@@ -89,13 +110,7 @@ __global__ __launch_bounds__(RP_THREADS) void rp_rec_start_kernel(const uint64_t
                                                                   uint32_t* __restrict__ rec_start) {
   const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
   if (r > n_recs) return;
-  uint32_t lo = 0, hi = n;   // first element with U >> 52 >= r
-  if (r == n_recs) lo = n;
-  while (lo < hi) {
-    const uint32_t mid = lo + ((hi - lo) >> 1);
-    if ((uint32_t)(U[mid] >> 52) < r) lo = mid + 1; else hi = mid;
-  }
-  rec_start[r] = lo;
+  rec_start[r] = rp_bound<false>(r == n_recs ? n : 0u, n, r, [&](uint32_t x) { return (uint32_t)(U[x] >> 52); });
 }
 
 // run_start[id] at the heads; the entry behind the last run (tot[1] runs) = n
@@ -131,18 +146,9 @@ __global__ __launch_bounds__(RP_THREADS) void rp_count_kernel(const uint64_t* __
     return;
   }
   const uint32_t t = (uint32_t)key & RP_T_MASK, t_lo = t + P.min_lag, t_hi = t + P.max_lag;   // < 2^21
-  uint32_t l = i + 1, r = e;   // first j with t_j >= t_lo
-  while (l < r) {
-    const uint32_t mid = l + ((r - l) >> 1);
-    if (((uint32_t)U[mid] & RP_T_MASK) < t_lo) l = mid + 1; else r = mid;
-  }
-  const uint32_t first = l;
-  r = e;                       // first j with t_j > t_hi
-  while (l < r) {
-    const uint32_t mid = l + ((r - l) >> 1);
-    if (((uint32_t)U[mid] & RP_T_MASK) <= t_hi) l = mid + 1; else r = mid;
-  }
-  cnt[i] = l - first;
+  const auto t_of = [&](uint32_t x) { return (uint32_t)U[x] & RP_T_MASK; };
+  const uint32_t first = rp_bound<false>(i + 1, e, t_lo, t_of);   // first j with t_j >= t_lo
+  cnt[i] = rp_bound<true>(first, e, t_hi, t_of) - first;          // behind it: first j with t_j > t_hi
   lo_out[i] = first;
 }
 
@@ -157,35 +163,31 @@ __global__ __launch_bounds__(RP_THREADS) void rp_rec_pairs_kernel(const uint64_t
 // Pair g belongs to the last element x with poff[x] <= g (elements without partners share their successor's poff and are
 // never that one); it is x's partner number g - poff[x].  The block finds the owners of its first and last pair, every lane
 // searches between them
+struct rp_tile {
+  uint64_t base, end;   // the block's positions
+  uint32_t xA, xB;      // the owners of its first and last pair
+};
+__device__ __forceinline__ bool rp_tile_of(const uint64_t* __restrict__ poff, uint32_t e0, uint32_t e1, uint64_t P0, uint64_t np,
+                                           uint32_t tile, rp_tile* T) {
+  T->base = (uint64_t)blockIdx.x * tile;
+  if (T->base >= np) return false;
+  T->end = min(T->base + tile, np);
+  T->xA = rp_last_le(poff, e0, e1, P0 + T->base);
+  T->xB = rp_last_le(poff, T->xA, e1, P0 + T->end - 1);
+  return true;
+}
+// the owner of the block's pair g
+__device__ __forceinline__ uint32_t rp_tile_owner(const uint64_t* __restrict__ poff, const rp_tile& T, uint64_t g) {
+  return rp_last_le(poff, T.xA, T.xB + 1, g);
+}
 __global__ __launch_bounds__(RP_THREADS) void rp_expand_kernel(const uint64_t* __restrict__ U, const uint64_t* __restrict__ poff,
                                                                const uint32_t* __restrict__ lo, uint32_t e0, uint32_t e1, uint64_t P0,
                                                                uint64_t np, uint32_t tile, uint32_t r0, uint64_t* __restrict__ out) {
-  const uint64_t base = (uint64_t)blockIdx.x * tile;
-  if (base >= np) return;
-  const uint64_t end = min(base + tile, np);
-  uint32_t xA, xB;
-  {
-    const uint64_t gA = P0 + base, gB = P0 + end - 1;
-    uint32_t l = e0, h = e1;
-    while (h - l > 1) {
-      const uint32_t mid = l + ((h - l) >> 1);
-      if (poff[mid] <= gA) l = mid; else h = mid;
-    }
-    xA = l;
-    h = e1;
-    while (h - l > 1) {
-      const uint32_t mid = l + ((h - l) >> 1);
-      if (poff[mid] <= gB) l = mid; else h = mid;
-    }
-    xB = l;
-  }
-  for (uint64_t p = base + threadIdx.x; p < end; p += blockDim.x) {
+  rp_tile T;
+  if (!rp_tile_of(poff, e0, e1, P0, np, tile, &T)) return;
+  for (uint64_t p = T.base + threadIdx.x; p < T.end; p += blockDim.x) {
     const uint64_t g = P0 + p;
-    uint32_t l = xA, h = xB + 1;
-    while (h - l > 1) {
-      const uint32_t mid = l + ((h - l) >> 1);
-      if (poff[mid] <= g) l = mid; else h = mid;
-    }
+    const uint32_t l = rp_tile_owner(poff, T, g);
     const uint64_t key = U[l];
     const uint32_t j = lo[l] + (uint32_t)(g - poff[l]);
     const uint32_t ti = (uint32_t)key & RP_T_MASK, tj = (uint32_t)U[j] & RP_T_MASK;
@@ -261,56 +263,70 @@ __global__ __launch_bounds__(RP_THREADS) void rp_cell_out_kernel(const uint64_t*
   out[5ull * nk + o] = last[c];
 }
 
-// ---- what both entry points refuse before anything is launched ------------------------------------------------------------
+// ---- what the entry points refuse before anything is launched --------------------------------------------------------------
 static int32_t rp_check_knobs(shz_ctx* ctx, const char* who, uint32_t max_run, uint32_t cell_shift, uint32_t min_cell_pairs) {
   if (max_run < 2 || max_run > 1024) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: max_run must be in [2, 1024], got %u", who, max_run);
   if (cell_shift > 19) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: cell_shift must be at most 19, got %u", who, cell_shift);
   if (min_cell_pairs == 0) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: min_cell_pairs must be at least 1", who);
   return SHZ_OK;
 }
-static int32_t rp_check(shz_ctx* ctx, const char* who, const rp_params& P, const rp_out& O) {
-  if (!O.count || !O.cell_off || !O.rec_hashes || !O.rec_skipped_keys || !O.rec_pairs || !O.rec_skipped_rows)
-    SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: count, cell_off or a rec_* array is NULL", who);
+// the output arrays: `needed` names the ones a call cannot do without ("count, cell_off or a rec_* array"); more_ok: what the
+// caller has of them beside rp_out
+static int32_t rp_check_out(shz_ctx* ctx, const char* who, const rp_out& O, const char* needed, bool more_ok = true) {
+  if (!O.count || !O.cell_off || !O.rec_hashes || !O.owner_skipped_keys || !O.owner_pairs || !O.owner_skipped_rows || !more_ok)
+    SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: %s is NULL", who, needed);
   if (O.cap_cells && (!O.cell_lag || !O.cell_block || !O.cell_pairs || !O.cell_first || !O.cell_last))
     SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: NULL cell array with room for %llu cells", who, (unsigned long long)O.cap_cells);
+  return SHZ_OK;
+}
+static int32_t rp_check(shz_ctx* ctx, const char* who, const rp_params& P, const rp_out& O) {
+  SHZ_TRY(rp_check_out(ctx, who, O, "count, cell_off or a rec_* array"));
   if (P.max_lag < P.min_lag) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: max_lag %u is below min_lag %u", who, P.max_lag, P.min_lag);
   if (P.max_lag >= (1u << RP_T_BITS)) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: max_lag must be below 2^20, got %u", who, P.max_lag);
   return rp_check_knobs(ctx, who, P.max_run, P.cell_shift, P.min_cell_pairs);
 }
-// host columns: hash_off[n_clips + 1] from 0 and never decreasing, the columns there, fewer than 2^32 hashes, every t1 < 2^20
+// a host CSR over the clips: off[n_clips + 1] (`name`) from 0 and never decreasing, and with entries the columns there
+// (have_columns; `columns`: what they are called)
+static int32_t rp_check_csr(shz_ctx* ctx, const char* who, const char* name, const uint64_t* off, uint32_t n_clips, bool have_columns,
+                            const char* columns) {
+  if (!off) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: %s is NULL", who, name);
+  if (off[0] != 0) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: %s must start at 0 (it starts at %llu)", who, name, (unsigned long long)off[0]);
+  for (uint32_t c = 0; c < n_clips; ++c)
+    if (off[c + 1] < off[c]) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: %s decreases at clip %u", who, name, c);
+  if (off[n_clips] && !have_columns) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: NULL %s", who, columns);
+  return SHZ_OK;
+}
+// host columns: hash_off a CSR over the clips, fewer than 2^32 hashes, every t1 < 2^20
 static int32_t rp_check_columns(shz_ctx* ctx, const char* who, const uint32_t* key32, const uint32_t* t1, const uint64_t* hash_off,
                                 uint32_t n_clips) {
-  if (!hash_off) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: hash_off is NULL", who);
-  if (hash_off[0] != 0) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: hash_off must start at 0 (it starts at %llu)", who, (unsigned long long)hash_off[0]);
-  for (uint32_t c = 0; c < n_clips; ++c)
-    if (hash_off[c + 1] < hash_off[c]) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: hash_off decreases at clip %u", who, c);
+  SHZ_TRY(rp_check_csr(ctx, who, "hash_off", hash_off, n_clips, key32 && t1, "column"));
   const uint64_t N = hash_off[n_clips];
-  if (N && (!key32 || !t1)) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: NULL column", who);
   if (N >= (1ull << 32)) SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "%s: %llu hashes", who, (unsigned long long)N);
   for (uint64_t i = 0; i < N; ++i)
     if (t1[i] >> RP_T_BITS) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: t1[%llu] = %u, times must be below 2^20", who, (unsigned long long)i, t1[i]);
   return SHZ_OK;
 }
-// device copies of N >= 1 host hashes for the length of a call (tests / tools)
-struct rp_columns {
+// device copies of two host columns of N >= 1 entries (`what`: "columns", "peaks") for the length of a call (tests / tools);
+// pad: bytes of room behind each
+struct rp_upload {
   shz_ctx* ctx;
-  void *key = nullptr, *t1 = nullptr;
-  explicit rp_columns(shz_ctx* c) : ctx(c) {}
-  int32_t upload(const char* who, const uint32_t* key32, const uint32_t* t1_, uint64_t N) {
+  void *a = nullptr, *b = nullptr;
+  explicit rp_upload(shz_ctx* c) : ctx(c) {}
+  int32_t upload(const char* who, const char* what, const void* ha, uint64_t bytes_a, const void* hb, uint64_t bytes_b, uint64_t pad) {
     SHZ_HIP(ctx, hipSetDevice(ctx->device));
-    if (hipMalloc(&key, N * 4) != hipSuccess || hipMalloc(&t1, N * 4) != hipSuccess) {
+    if (hipMalloc(&a, bytes_a + pad) != hipSuccess || hipMalloc(&b, bytes_b + pad) != hipSuccess) {
       (void)hipGetLastError();
-      SHZ_FAIL(ctx, SHZ_E_NOMEM, "%s: hipMalloc(2 x %llu) failed", who, (unsigned long long)(N * 4));
+      SHZ_FAIL(ctx, SHZ_E_NOMEM, "%s: hipMalloc(%llu + %llu) failed", who, (unsigned long long)bytes_a, (unsigned long long)bytes_b);
     }
-    if (shz_memcpy(ctx, key, key32, N * 4, hipMemcpyHostToDevice) != hipSuccess ||
-        shz_memcpy(ctx, t1, t1_, N * 4, hipMemcpyHostToDevice) != hipSuccess)
-      SHZ_FAIL(ctx, SHZ_E_HIP, "%s: copy of the columns failed", who);
+    if (shz_memcpy(ctx, a, ha, bytes_a, hipMemcpyHostToDevice) != hipSuccess ||
+        shz_memcpy(ctx, b, hb, bytes_b, hipMemcpyHostToDevice) != hipSuccess)
+      SHZ_FAIL(ctx, SHZ_E_HIP, "%s: copy of the %s failed", who, what);
     return SHZ_OK;
   }
-  ~rp_columns() {
-    if (key || t1) (void)hipStreamSynchronize(ctx->stream);   // (a refused call may have queued work that reads the columns)
-    if (key) (void)hipFree(key);
-    if (t1) (void)hipFree(t1);
+  ~rp_upload() {
+    if (a || b) (void)hipStreamSynchronize(ctx->stream);   // (a refused call may have queued work that reads the columns)
+    if (a) (void)hipFree(a);
+    if (b) (void)hipFree(b);
   }
 };
 // the recordings' clips (no recording: no clips either, and the caller is done -- what it writes then: rp_empty)
@@ -322,26 +338,164 @@ static int32_t rp_check_recs(shz_ctx* ctx, const char* who, uint32_t n_clips, co
   if (n_recs > RP_MAX_RECS) SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "%s: %u recordings in one call, at most %u", who, n_recs, RP_MAX_RECS);
   return shz_check_clip0(ctx, "rec_clip0", "recording", rec_clip0, n_recs, n_clips);
 }
-static void rp_empty(const rp_out& O, uint32_t n_recs) {
+// what a call without hashes returns
+static void rp_empty(const rp_out& O, uint32_t n_recs, uint32_t n_owners) {
   *O.count = 0;
-  for (uint32_t r = 0; r <= n_recs; ++r) O.cell_off[r] = 0;
-  for (uint32_t r = 0; r < n_recs; ++r) {
-    O.rec_hashes[r] = O.rec_skipped_keys[r] = 0;
-    O.rec_pairs[r] = O.rec_skipped_rows[r] = 0;
+  for (uint32_t o = 0; o <= n_owners; ++o) O.cell_off[o] = 0;
+  for (uint32_t r = 0; r < n_recs; ++r) O.rec_hashes[r] = 0;
+  for (uint32_t o = 0; o < n_owners; ++o) {
+    O.owner_skipped_keys[o] = 0;
+    O.owner_pairs[o] = O.owner_skipped_rows[o] = 0;
   }
 }
 
 // ---- the stages both joins share --------------------------------------------------------------------------------------------
+// The clock of a call.  It owns ctx->rp_ev (created on first use): start() marks the stream, split(into) marks it again -- the
+// interval since the mark before belongs to *into -- and lap(into) is a split that waits for its mark and adds every interval
+// since start() to its place.  into may be NULL: that interval is dropped.  A clock that is off does none of this, waiting included
+struct rp_clock {
+  shz_ctx* ctx;
+  bool on;
+  int n = 0;   // marks behind start(): rp_ev[1 .. n]
+  float* into[2] = {nullptr, nullptr};
+  rp_clock(shz_ctx* c, bool on_) : ctx(c), on(on_) {}
+  int32_t start() {
+    if (!on) return SHZ_OK;
+    for (hipEvent_t& e : ctx->rp_ev)
+      if (!e) SHZ_HIP(ctx, hipEventCreate(&e));
+    n = 0;
+    SHZ_HIP(ctx, hipEventRecord(ctx->rp_ev[0], ctx->stream));
+    return SHZ_OK;
+  }
+  int32_t split(float* a) {
+    if (!on) return SHZ_OK;
+    if (n >= 2) SHZ_FAIL(ctx, SHZ_E_STATE, "rp_clock: three marks behind one start");
+    into[n++] = a;
+    SHZ_HIP(ctx, hipEventRecord(ctx->rp_ev[n], ctx->stream));
+    return SHZ_OK;
+  }
+  int32_t lap(float* a) {
+    if (!on) return SHZ_OK;
+    SHZ_TRY(split(a));
+    SHZ_HIP(ctx, hipEventSynchronize(ctx->rp_ev[n]));
+    for (int k = 0; k < n; ++k) {
+      float ms = 0.f;
+      SHZ_HIP(ctx, hipEventElapsedTime(&ms, ctx->rp_ev[k], ctx->rp_ev[k + 1]));
+      if (into[k]) *into[k] += ms;
+    }
+    n = 0;
+    return SHZ_OK;
+  }
+};
+// the times a fused call returns (each may be NULL), zeroed: the first write of the call.  A call that is asked for any of them
+// times every stage: at(p) is p's place, or the one spare float for a time nobody reads
+struct rp_times {
+  float *extract, *warp, *pairs, *cells, spare = 0.f;
+  bool on;
+  rp_times(float* e, float* w, float* p, float* c) : extract(e), warp(w), pairs(p), cells(c), on(e || w || p || c) {
+    for (float* m : {e, w, p, c})
+      if (m) *m = 0.f;
+  }
+  float* at(float* p) { return on ? (p ? p : &spare) : nullptr; }
+};
+// what the stages of one join share: the name for messages, the launch shapes (SHZ_DEBUG_REPEAT_SMALL_SLICES), the clock and the
+// join's two times.  The join is timed when either time is asked for
+struct rp_call {
+  shz_ctx* ctx;
+  const char* who;
+  bool small;
+  uint32_t bs, tile;
+  rp_clock K;
+  float *ms_pairs, *ms_cells, pairs_ms = 0.f, cells_ms = 0.f;   // where the times go at the end (may be NULL) | as they add up
+  rp_call(shz_ctx* c, const char* w, float* ms_pairs_, float* ms_cells_)
+      : ctx(c), who(w), small((c->debug & SHZ_DEBUG_REPEAT_SMALL_SLICES) != 0), bs(small ? RP_SMALL : RP_THREADS),
+        tile(small ? RP_SMALL : RP_TILE), K(c, ms_pairs_ || ms_cells_), ms_pairs(ms_pairs_), ms_cells(ms_cells_) {}
+};
+
+// The header block of a join in SHZ_WS_RP_REC, laid out once: a field is a byte offset that holds for the host copy (h) and the
+// device copy (d) alike.  The u64 fields come first, then the u32 ones, then what the caller adds before place() (u32, i32).
+// The owners (recordings, jobs) own the pairs:
+//   u64   tot[4]       unique elements, runs, a slice's cells, its kept cells
+//         rec_off      first hash of every recording, n_recs + 1 (goes up)
+//         owner_po     pairs in front of every owner, n_owners + 1
+//         skip_rows    rows of the runs skipped, per owner
+//   u32   rec_start    first unique element of every recording, n_recs + 1
+//         skip_keys    keys skipped, per owner
+// One upload and one read-back per join (up / down); a single field may travel on its own
+template <class T>
+struct rp_field {
+  uint64_t at;
+};
+struct rp_header {
+  shz_ctx* ctx;
+  uint32_t n_recs, n_owners;
+  uint64_t bytes = 0;
+  std::vector<uint64_t> host;
+  char* dev = nullptr;
+  rp_field<uint64_t> tot, rec_off, owner_po, skip_rows;
+  rp_field<uint32_t> rec_start, skip_keys;
+  template <class T>
+  rp_field<T> add(uint64_t n) {
+    const rp_field<T> f{bytes};
+    bytes += n * sizeof(T);
+    return f;
+  }
+  rp_header(shz_ctx* c, uint32_t n_recs_, uint32_t n_owners_) : ctx(c), n_recs(n_recs_), n_owners(n_owners_) {
+    tot = add<uint64_t>(4);
+    rec_off = add<uint64_t>((uint64_t)n_recs + 1);
+    owner_po = add<uint64_t>((uint64_t)n_owners + 1);
+    skip_rows = add<uint64_t>(n_owners);
+    rec_start = add<uint32_t>((uint64_t)n_recs + 1);
+    skip_keys = add<uint32_t>(n_owners);
+  }
+  template <class T>
+  T* h(rp_field<T> f) { return (T*)((char*)host.data() + f.at); }
+  template <class T>
+  T* d(rp_field<T> f) { return (T*)(dev + f.at); }
+  // the host copy, zero but for rec_off, and the room on the device
+  int32_t place(const uint64_t* hash_off, const uint32_t* rec_clip0) {
+    host.assign((size_t)((bytes + 7) / 8), 0);
+    for (uint32_t r = 0; r <= n_recs; ++r) h(rec_off)[r] = hash_off[rec_clip0[r]];
+    void* p;
+    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_RP_REC, host.size() * 8, &p));
+    dev = (char*)p;
+    return SHZ_OK;
+  }
+  int32_t up() {
+    SHZ_HIP(ctx, shz_memcpy(ctx, dev, host.data(), host.size() * 8, hipMemcpyHostToDevice));
+    return SHZ_OK;
+  }
+  int32_t down() {
+    SHZ_HIP(ctx, shz_memcpy(ctx, host.data(), dev, host.size() * 8, hipMemcpyDeviceToHost));
+    return SHZ_OK;
+  }
+  template <class T>
+  int32_t up(rp_field<T> f, uint64_t n) {
+    SHZ_HIP(ctx, shz_memcpy(ctx, d(f), h(f), n * sizeof(T), hipMemcpyHostToDevice));
+    return SHZ_OK;
+  }
+  template <class T>
+  int32_t down(rp_field<T> f, uint64_t n) {
+    SHZ_HIP(ctx, shz_memcpy(ctx, h(f), d(f), n * sizeof(T), hipMemcpyDeviceToHost));
+    return SHZ_OK;
+  }
+};
+
 struct rp_elems {
   const uint64_t* U;                        // the unique composed hashes, sorted
   uint32_t nu;
   const uint32_t *head, *pos, *run_start;   // run heads and their scan (SHZ_WS_RP_FLAG / _SCAN), first element of every run
 };
-// compose, sort + unique, the recordings' borders, the runs of the N >= 1 hashes.  d_rec_off[n_recs + 1]: first hash of every
-// recording; d_tot[0] / d_tot[1] get the unique elements / the runs, d_rec_start[n_recs + 1] the borders in U.  One host
-// read-back (the unique count); the stream is busy with the runs on return
-static int32_t rp_elements(shz_ctx* ctx, const char* who, const uint32_t* d_key32, const uint32_t* d_t1, uint64_t N, uint32_t n_recs,
-                           const uint64_t* d_rec_off, uint64_t* d_tot, uint32_t* d_rec_start, uint32_t bs, rp_elems* E) {
+// compose, sort + unique, the recordings' borders, the runs of the N >= 1 hashes.  The header (uploaded) holds rec_off; its
+// tot[0] / tot[1] get the unique elements / the runs, its rec_start the borders in U.  One host read-back (the unique count);
+// the stream is busy with the runs on return
+static int32_t rp_elements(rp_call& X, const uint32_t* d_key32, const uint32_t* d_t1, uint64_t N, rp_header& H, rp_elems* E) {
+  shz_ctx* ctx = X.ctx;
+  const char* who = X.who;
+  const uint32_t bs = X.bs, n_recs = H.n_recs;
+  const uint64_t* d_rec_off = H.d(H.rec_off);
+  uint64_t* d_tot = H.d(H.tot);
+  uint32_t* d_rec_start = H.d(H.rec_start);
   hipStream_t st = ctx->stream;
   void *ka, *kb, *d_flag, *d_scan, *d_u, *d_run;
   SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SORT_A, N * 8, &ka));
@@ -394,21 +548,21 @@ static std::vector<uint32_t> rp_cut_slices(const uint64_t* po, uint32_t n, uint6
 }
 
 // The cell stage of a slice and the cells of the call.  A slice's np pair keys owner_in_slice << (20 + lag_bits) | lag << 20 | t
-// lie in ka (the expand, queued behind rp_ev[0], wrote them); slice() sorts them on the bits from cell_shift up, reduces the
-// cells and gathers the kept ones on the host, copy_out() hands them to the caller
+// lie in ka (the expand, queued behind the clock's start(), wrote them); slice() sorts them on the bits from cell_shift up,
+// reduces the cells and gathers the kept ones on the host, copy_out() hands them to the caller
 struct rp_cells {
+  rp_call& X;
   shz_ctx* ctx;
   const char *who, *what;   // the entry point, and what owns cells ("recording", "job"), for messages
   uint32_t n_owners, bs;
   uint64_t cap;
-  bool timed;
   uint64_t *ka = nullptr, *kb = nullptr;
   uint32_t *flag = nullptr, *scan = nullptr;
   std::vector<uint32_t> c_lag, c_block, c_pairs, c_first, c_last, blockbuf;
   std::vector<uint64_t> cell_off;
   uint64_t n_cells_all = 0;
-  rp_cells(shz_ctx* c, const char* who_, const char* what_, uint32_t n, uint64_t cap_, uint32_t bs_, bool timed_)
-      : ctx(c), who(who_), what(what_), n_owners(n), bs(bs_), cap(cap_), timed(timed_), cell_off((size_t)n + 1, 0) {}
+  rp_cells(rp_call& x, const char* what_, uint32_t n, uint64_t cap_)
+      : X(x), ctx(x.ctx), who(x.who), what(what_), n_owners(n), bs(x.bs), cap(cap_), cell_off((size_t)n + 1, 0) {}
   int32_t reserve(uint64_t np_max) {
     if (np_max == 0) return SHZ_OK;
     void* p;
@@ -422,12 +576,11 @@ struct rp_cells {
     scan = (uint32_t*)p;
     return SHZ_OK;
   }
-  // d_tot[2] / d_tot[3]: the slice's cells / kept cells.  The owners [r0, r1) are in the slice.  The times of the expand and of
-  // the cell stage are added to *ms_expand / *ms_cells when timed
-  int32_t slice(uint64_t* d_tot, uint32_t np, uint32_t cell_shift, uint32_t min_cell_pairs, int lag_bits, uint32_t r0, uint32_t r1,
-                float* ms_expand, float* ms_cells) {
+  // d_tot[2] / d_tot[3]: the slice's cells / kept cells.  The owners [r0, r1) are in the slice.  The time of the expand goes to
+  // the join's pairs, that of the cell stage to its cells
+  int32_t slice(uint64_t* d_tot, uint32_t np, uint32_t cell_shift, uint32_t min_cell_pairs, int lag_bits, uint32_t r0, uint32_t r1) {
     hipStream_t st = ctx->stream;
-    if (timed) SHZ_HIP(ctx, hipEventRecord(ctx->rp_ev[1], st));
+    SHZ_TRY(X.K.split(&X.pairs_ms));
     int sel = 0;
     SHZ_TRY(shz_sort_u64(ctx, ka, kb, nullptr, nullptr, 0, np, (int)cell_shift, RP_T_BITS + lag_bits + rp_bits(r1 - r0 - 1), &sel));
     const uint64_t* pk = sel ? kb : ka;
@@ -463,15 +616,8 @@ struct rp_cells {
       blockbuf.resize(6 * (size_t)nk);
       SHZ_HIP(ctx, shz_memcpy(ctx, blockbuf.data(), d_out, 6ull * nk * 4, hipMemcpyDeviceToHost));
     }
-    if (timed) SHZ_HIP(ctx, hipEventRecord(ctx->rp_ev[2], st));
+    SHZ_TRY(X.K.lap(&X.cells_ms));
     SHZ_HIP(ctx, hipStreamSynchronize(st));
-    if (timed) {
-      float a = 0.f, b = 0.f;
-      SHZ_HIP(ctx, hipEventElapsedTime(&a, ctx->rp_ev[0], ctx->rp_ev[1]));
-      SHZ_HIP(ctx, hipEventElapsedTime(&b, ctx->rp_ev[1], ctx->rp_ev[2]));
-      *ms_expand += a;
-      *ms_cells += b;
-    }
     for (uint32_t k = 0; k < nk; ++k) {
       const uint32_t r = blockbuf[k];
       if (r < r0 || r >= r1) SHZ_FAIL(ctx, SHZ_E_STATE, "%s: a cell of %s %u in the slice [%u, %u)", who, what, r, r0, r1);
@@ -488,24 +634,111 @@ struct rp_cells {
     return SHZ_OK;
   }
   // cell_off[n_owners + 1], *count and the cells there is room for; SHZ_E_CAPACITY when there are more
-  int32_t copy_out(uint64_t* o_off, uint32_t* o_lag, uint32_t* o_block, uint32_t* o_pairs, uint32_t* o_first, uint32_t* o_last,
-                   uint64_t* count) {
+  int32_t copy_out(const rp_out& O) {
     for (uint32_t r = 0; r < n_owners; ++r) cell_off[r + 1] += cell_off[r];
-    memcpy(o_off, cell_off.data(), ((size_t)n_owners + 1) * 8);
-    *count = n_cells_all;
+    memcpy(O.cell_off, cell_off.data(), ((size_t)n_owners + 1) * 8);
+    *O.count = n_cells_all;
     const size_t nw = c_lag.size();
     if (nw) {
-      memcpy(o_lag, c_lag.data(), nw * 4);
-      memcpy(o_block, c_block.data(), nw * 4);
-      memcpy(o_pairs, c_pairs.data(), nw * 4);
-      memcpy(o_first, c_first.data(), nw * 4);
-      memcpy(o_last, c_last.data(), nw * 4);
+      memcpy(O.cell_lag, c_lag.data(), nw * 4);
+      memcpy(O.cell_block, c_block.data(), nw * 4);
+      memcpy(O.cell_pairs, c_pairs.data(), nw * 4);
+      memcpy(O.cell_first, c_first.data(), nw * 4);
+      memcpy(O.cell_last, c_last.data(), nw * 4);
     }
     if (n_cells_all > cap)
       SHZ_FAIL(ctx, SHZ_E_CAPACITY, "%s: %llu cells, room for %llu", who, (unsigned long long)n_cells_all, (unsigned long long)cap);
     return SHZ_OK;
   }
 };
+
+// the recordings' borders in U as they came back: they span the nu unique hashes and never decrease
+static int32_t rp_check_borders(rp_call& X, const uint32_t* rec_start, uint32_t n_recs, uint32_t nu) {
+  if (rec_start[0] != 0 || rec_start[n_recs] != nu)
+    SHZ_FAIL(X.ctx, SHZ_E_STATE, "%s: the recordings' borders do not span the %u unique hashes", X.who, nu);
+  for (uint32_t r = 0; r < n_recs; ++r)
+    if (rec_start[r + 1] < rec_start[r]) SHZ_FAIL(X.ctx, SHZ_E_STATE, "%s: the borders of recording %u decrease", X.who, r);
+  return SHZ_OK;
+}
+
+// what a count kernel writes about the n things it counts for (elements, items): the partners of i are lo[i] .. lo[i] + cnt[i];
+// poff[n + 1]: the scan of cnt.  Slots SHZ_WS_RP_LO / _CNT / _POFF
+struct rp_counts {
+  uint32_t* lo = nullptr;
+  uint64_t *cnt = nullptr, *poff = nullptr;
+  int32_t reserve(shz_ctx* ctx, uint64_t n) {
+    void* p;
+    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_RP_LO, n * 4, &p));
+    lo = (uint32_t*)p;
+    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_RP_CNT, n * 8, &p));
+    cnt = (uint64_t*)p;
+    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_RP_POFF, (n + 1) * 8, &p));
+    poff = (uint64_t*)p;
+    return SHZ_OK;
+  }
+};
+// The owners' pairs.  The count kernel is queued; d_first[n_owners + 1] (device): the first of the n counted things of every
+// owner.  Scan, the pairs in front of every owner, the header back in one copy; the interval since the clock's start() is the
+// join's pairs time, and the stream is idle on return.  Nothing counted: nothing runs and no owner has pairs.  The offsets must
+// start at 0 and never decrease
+static int32_t rp_owner_pairs(rp_call& X, rp_header& H, const char* noun, const rp_counts& C, uint32_t n, const uint32_t* d_first) {
+  shz_ctx* ctx = X.ctx;
+  hipStream_t st = ctx->stream;
+  if (n) {
+    SHZ_TRY(shz_scan_u64(ctx, (const uint64_t*)C.cnt, C.poff, n, C.poff + n));
+    hipLaunchKernelGGL(rp_rec_pairs_kernel, dim3(rp_grid((uint64_t)H.n_owners + 1, X.bs)), dim3(X.bs), 0, st, (const uint64_t*)C.poff,
+                       d_first, H.n_owners, H.d(H.owner_po));
+    SHZ_HIP(ctx, hipGetLastError());
+    SHZ_TRY(H.down());
+  }
+  SHZ_TRY(X.K.lap(&X.pairs_ms));
+  SHZ_HIP(ctx, hipStreamSynchronize(st));
+  const uint64_t* po = H.h(H.owner_po);
+  if (po[0] != 0) SHZ_FAIL(ctx, SHZ_E_STATE, "%s: %llu pairs in front of the first %s", X.who, (unsigned long long)po[0], noun);
+  for (uint32_t o = 0; o < H.n_owners; ++o)
+    if (po[o + 1] < po[o]) SHZ_FAIL(ctx, SHZ_E_STATE, "%s: the pairs in front of %s %u decrease", X.who, noun, o);
+  return SHZ_OK;
+}
+
+// The slices, the cells and the outputs of a join whose header is back.  Slices: consecutive whole owners whose two pair buffers
+// fit 1/8 of the workspace limit.  refuse(o, pairs, max_pairs) words the refusal of an owner that has more pairs than a slice
+// holds -- it names the knobs of its join -- and expand(o0, o1, P0, np, out) queues the one launch that writes the np pairs of the
+// owners [o0, o1), which begin at pair P0, to out; the cell stage works on a lag field of lag_bits.  Then, and only then, the
+// outputs are written: rec_hashes from the borders, the owners' numbers, the join's times, and the cells there is room for
+template <class Refuse, class Expand>
+static int32_t rp_slices(rp_call& X, rp_header& H, const char* noun, uint32_t cell_shift, uint32_t min_cell_pairs, int lag_bits,
+                         const rp_out& O, Refuse refuse, Expand expand) {
+  shz_ctx* ctx = X.ctx;
+  const uint32_t n = H.n_owners;
+  const uint64_t* po = H.h(H.owner_po);
+  const uint64_t max_pairs = std::min<uint64_t>(std::max<uint64_t>(ctx->ws_limit / 8 / 16, 1), 1ull << 31);
+  for (uint32_t o = 0; o < n; ++o)
+    if (po[o + 1] - po[o] > max_pairs) return refuse(o, po[o + 1] - po[o], max_pairs);
+  uint64_t np_max = 0;
+  const std::vector<uint32_t> slices = rp_cut_slices(po, n, max_pairs, X.small, &np_max);
+  rp_cells C(X, noun, n, O.cap_cells);
+  SHZ_TRY(C.reserve(np_max));
+  for (size_t s = 0; s + 1 < slices.size(); ++s) {
+    const uint32_t o0 = slices[s], o1 = slices[s + 1];
+    const uint64_t P0 = po[o0], np64 = po[o1] - P0;
+    if (np64 == 0) continue;
+    SHZ_TRY(X.K.start());
+    expand(o0, o1, P0, np64, C.ka);
+    SHZ_HIP(ctx, hipGetLastError());
+    SHZ_TRY(C.slice(H.d(H.tot), (uint32_t)np64 /* <= 2^31 */, cell_shift, min_cell_pairs, lag_bits, o0, o1));
+  }
+  const uint32_t *rec_start = H.h(H.rec_start), *skip_keys = H.h(H.skip_keys);
+  const uint64_t* skip_rows = H.h(H.skip_rows);
+  for (uint32_t r = 0; r < H.n_recs; ++r) O.rec_hashes[r] = rec_start[r + 1] - rec_start[r];
+  for (uint32_t o = 0; o < n; ++o) {
+    O.owner_pairs[o] = po[o + 1] - po[o];
+    O.owner_skipped_keys[o] = skip_keys[o];
+    O.owner_skipped_rows[o] = skip_rows[o];
+  }
+  if (X.ms_pairs) *X.ms_pairs = X.pairs_ms;
+  if (X.ms_cells) *X.ms_cells = X.cells_ms;
+  return C.copy_out(O);
+}
 
 // ---- the core on device columns -------------------------------------------------------------------------------------------
 // d_key32 / d_t1: device columns of hash_off[n_clips] < 2^32 entries with t1 < 2^20, hash_off (host) their CSR over the clips;
@@ -516,130 +749,58 @@ static int32_t rp_core(shz_ctx* ctx, const char* who, const uint32_t* d_key32, c
                        float* ms_cells) {
   const uint64_t N = hash_off[rec_clip0[n_recs]];
   if (N == 0) {
-    rp_empty(O, n_recs);
+    rp_empty(O, n_recs, n_recs);
     return SHZ_OK;
   }
-  const bool small = (ctx->debug & SHZ_DEBUG_REPEAT_SMALL_SLICES) != 0, timed = ms_pairs || ms_cells;
-  const uint32_t bs = small ? RP_SMALL : RP_THREADS, tile = small ? RP_SMALL : RP_TILE;
   hipStream_t st = ctx->stream;
-  float pairs_ms = 0.f, cells_ms = 0.f;
-  if (timed) {
-    for (hipEvent_t& e : ctx->rp_ev)
-      if (!e) SHZ_HIP(ctx, hipEventCreate(&e));
-    SHZ_HIP(ctx, hipEventRecord(ctx->rp_ev[0], st));
-  }
-  // the recordings' block: tot[4] (unique elements, runs, a slice's cells, its kept cells) | rec_off | rec_po | skip_rows (u64)
-  // | rec_start | skip_keys (u32).  rec_off goes up, the rest comes back in one copy
-  const uint64_t nr1 = (uint64_t)n_recs + 1;
-  const uint64_t o_off = 4, o_po = o_off + nr1, o_rows = o_po + nr1, n64 = o_rows + n_recs;
-  const uint64_t rec_bytes = n64 * 8 + (nr1 + n_recs) * 4;
-  std::vector<uint64_t> hrec((size_t)((rec_bytes + 7) / 8), 0);
-  for (uint32_t r = 0; r <= n_recs; ++r) hrec[o_off + r] = hash_off[rec_clip0[r]];
-  void* d_rec;
-  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_RP_REC, hrec.size() * 8, &d_rec));
-  uint64_t* d64 = (uint64_t*)d_rec;
-  uint64_t *d_tot = d64, *d_rec_off = d64 + o_off, *d_rec_po = d64 + o_po, *d_skip_rows = d64 + o_rows;
-  uint32_t *d_rec_start = (uint32_t*)(d64 + n64), *d_skip_keys = d_rec_start + nr1;
-  SHZ_HIP(ctx, shz_memcpy(ctx, d_rec, hrec.data(), hrec.size() * 8, hipMemcpyHostToDevice));
+  rp_call X(ctx, who, ms_pairs, ms_cells);
+  SHZ_TRY(X.K.start());
+  // the header: the recordings own the pairs.  rec_off goes up, the rest comes back in one copy
+  rp_header H(ctx, n_recs, n_recs);
+  SHZ_TRY(H.place(hash_off, rec_clip0));
+  SHZ_TRY(H.up());
   // 1) compose, 2) sort + unique, 3) runs
   rp_elems E;
-  SHZ_TRY(rp_elements(ctx, who, d_key32, d_t1, N, n_recs, d_rec_off, d_tot, d_rec_start, bs, &E));
-  const uint32_t nu = E.nu;
-  const uint64_t* U = E.U;
+  SHZ_TRY(rp_elements(X, d_key32, d_t1, N, H, &E));
   // 4) count, scan, the recordings' numbers
-  void *d_lo, *d_cnt, *d_poff;
-  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_RP_LO, (uint64_t)nu * 4, &d_lo));
-  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_RP_CNT, (uint64_t)nu * 8, &d_cnt));
-  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_RP_POFF, ((uint64_t)nu + 1) * 8, &d_poff));
-  hipLaunchKernelGGL(rp_count_kernel, dim3(rp_grid(nu, bs)), dim3(bs), 0, st, U, E.head, E.pos, E.run_start, nu, P, (uint64_t*)d_cnt,
-                     (uint32_t*)d_lo, d_skip_keys, (unsigned long long*)d_skip_rows);
+  rp_counts C;
+  SHZ_TRY(C.reserve(ctx, E.nu));
+  hipLaunchKernelGGL(rp_count_kernel, dim3(rp_grid(E.nu, X.bs)), dim3(X.bs), 0, st, E.U, E.head, E.pos, E.run_start, E.nu, P, C.cnt, C.lo,
+                     H.d(H.skip_keys), (unsigned long long*)H.d(H.skip_rows));
   SHZ_HIP(ctx, hipGetLastError());
-  uint64_t* poff = (uint64_t*)d_poff;
-  SHZ_TRY(shz_scan_u64(ctx, (const uint64_t*)d_cnt, poff, nu, poff + nu));
-  hipLaunchKernelGGL(rp_rec_pairs_kernel, dim3(rp_grid(nr1, bs)), dim3(bs), 0, st, (const uint64_t*)poff, (const uint32_t*)d_rec_start,
-                     n_recs, d_rec_po);
-  SHZ_HIP(ctx, hipGetLastError());
-  SHZ_HIP(ctx, shz_memcpy(ctx, hrec.data(), d_rec, hrec.size() * 8, hipMemcpyDeviceToHost));
-  if (timed) SHZ_HIP(ctx, hipEventRecord(ctx->rp_ev[1], st));
-  SHZ_HIP(ctx, hipStreamSynchronize(st));
-  if (timed) {
-    float a = 0.f;
-    SHZ_HIP(ctx, hipEventElapsedTime(&a, ctx->rp_ev[0], ctx->rp_ev[1]));
-    pairs_ms += a;
-  }
-  const uint64_t *rec_po = hrec.data() + o_po, *skip_rows = hrec.data() + o_rows;
-  const uint32_t *rec_start = (const uint32_t*)(hrec.data() + n64), *skip_keys = rec_start + nr1;
-  if (rec_start[0] != 0 || rec_start[n_recs] != nu || rec_po[0] != 0)
-    SHZ_FAIL(ctx, SHZ_E_STATE, "%s: the recordings' borders do not span the %u unique hashes", who, nu);
-  for (uint32_t r = 0; r < n_recs; ++r)
-    if (rec_start[r + 1] < rec_start[r] || rec_po[r + 1] < rec_po[r])
-      SHZ_FAIL(ctx, SHZ_E_STATE, "%s: the borders of recording %u decrease", who, r);
-  // 5) the slices: consecutive whole recordings whose two pair buffers fit 1/8 of the workspace limit
-  const uint64_t max_pairs = std::min<uint64_t>(std::max<uint64_t>(ctx->ws_limit / 8 / 16, 1), 1ull << 31);
-  for (uint32_t r = 0; r < n_recs; ++r)
-    if (rec_po[r + 1] - rec_po[r] > max_pairs)
-      SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED,
-               "%s: recording %u has %llu pairs, a slice holds %llu (workspace limit): raise min_lag (%u) or lower max_run (%u)", who, r,
-               (unsigned long long)(rec_po[r + 1] - rec_po[r]), (unsigned long long)max_pairs, P.min_lag, P.max_run);
-  uint64_t np_max = 0;
-  const std::vector<uint32_t> slices = rp_cut_slices(rec_po, n_recs, max_pairs, small, &np_max);
-  // 6) slice by slice: expand, sort, cells
-  rp_cells C(ctx, who, "recording", n_recs, O.cap_cells, bs, timed);
-  SHZ_TRY(C.reserve(np_max));
-  for (size_t s = 0; s + 1 < slices.size(); ++s) {
-    const uint32_t r0 = slices[s], r1 = slices[s + 1], e0 = rec_start[r0], e1 = rec_start[r1];
-    const uint64_t P0 = rec_po[r0], np64 = rec_po[r1] - P0;
-    if (np64 == 0) continue;
-    const uint32_t np = (uint32_t)np64;   // (<= 2^31)
-    if (timed) SHZ_HIP(ctx, hipEventRecord(ctx->rp_ev[0], st));
-    hipLaunchKernelGGL(rp_expand_kernel, dim3(rp_grid(np, tile)), dim3(bs), 0, st, U, (const uint64_t*)poff, (const uint32_t*)d_lo, e0, e1,
-                       P0, np64, tile, r0, C.ka);
-    SHZ_HIP(ctx, hipGetLastError());
-    SHZ_TRY(C.slice(d_tot, np, P.cell_shift, P.min_cell_pairs, RP_T_BITS, r0, r1, &pairs_ms, &cells_ms));
-  }
-  // 7) the outputs
-  for (uint32_t r = 0; r < n_recs; ++r) {
-    O.rec_hashes[r] = rec_start[r + 1] - rec_start[r];
-    O.rec_pairs[r] = rec_po[r + 1] - rec_po[r];
-    O.rec_skipped_keys[r] = skip_keys[r];
-    O.rec_skipped_rows[r] = skip_rows[r];
-  }
-  if (ms_pairs) *ms_pairs = pairs_ms;
-  if (ms_cells) *ms_cells = cells_ms;
-  return C.copy_out(O.cell_off, O.cell_lag, O.cell_block, O.cell_pairs, O.cell_first, O.cell_last, O.count);
+  SHZ_TRY(rp_owner_pairs(X, H, "recording", C, E.nu, H.d(H.rec_start)));
+  const uint32_t* rec_start = H.h(H.rec_start);
+  SHZ_TRY(rp_check_borders(X, rec_start, n_recs, E.nu));
+  // 5) slice by slice: expand, sort, cells; 6) the outputs
+  auto refuse = [&](uint32_t r, uint64_t pairs, uint64_t max_pairs) -> int32_t {
+    SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED,
+             "%s: recording %u has %llu pairs, a slice holds %llu (workspace limit): raise min_lag (%u) or lower max_run (%u)", who, r,
+             (unsigned long long)pairs, (unsigned long long)max_pairs, P.min_lag, P.max_run);
+  };
+  auto expand = [&](uint32_t r0, uint32_t r1, uint64_t P0, uint64_t np, uint64_t* out) {
+    hipLaunchKernelGGL(rp_expand_kernel, dim3(rp_grid(np, X.tile)), dim3(X.bs), 0, st, E.U, (const uint64_t*)C.poff, (const uint32_t*)C.lo,
+                       rec_start[r0], rec_start[r1], P0, np, X.tile, r0, out);
+  };
+  return rp_slices(X, H, "recording", P.cell_shift, P.min_cell_pairs, RP_T_BITS, O, refuse, expand);
 }
 
 // ---- the extraction of the fused calls ----------------------------------------------------------------------------------------
-// the three times of a fused call (each may be NULL), zeroed: the first write of the call.  A call that times anything hands
-// the cores a place for both of their times
-struct rp_times {
-  float *extract, *p, *c, spare[2] = {0.f, 0.f};
-  bool timed;
-  rp_times(float* ms_extract, float* ms_pairs, float* ms_cells)
-      : extract(ms_extract), p(ms_pairs), c(ms_cells), timed(ms_extract || ms_pairs || ms_cells) {
-    if (extract) *extract = 0.f;
-    if (p) *p = 0.f;
-    if (c) *c = 0.f;
-  }
-  float* pairs() { return timed ? (p ? p : &spare[0]) : nullptr; }
-  float* cells() { return timed ? (c ? c : &spare[1]) : nullptr; }
-};
+// extract() -- shz_extract_owned, sp_peaks_owned -- on the clock of the call: its stream interval is the call's extraction time
+template <class F>
+static int32_t rp_timed_extract(shz_ctx* ctx, rp_times& T, F extract) {
+  SHZ_HIP(ctx, hipSetDevice(ctx->device));
+  rp_clock K(ctx, T.on);
+  SHZ_TRY(K.start());
+  SHZ_TRY(extract());
+  return K.lap(T.extract);
+}
 // the clips fingerprinted into the library's own columns (shz_extract_owned), timed; fewer than 2^32 hashes
 static int32_t rp_extract(shz_ctx* ctx, const char* who, const int16_t* pcm, const uint64_t* clip_off, uint32_t n_clips, uint32_t fs,
                           double amp_min, uint32_t fan_value, uint32_t flags, rp_times& T, uint64_t* hash_off, const uint32_t** d_key,
                           const uint32_t** d_t1) {
-  SHZ_HIP(ctx, hipSetDevice(ctx->device));
-  if (T.timed) {
-    for (hipEvent_t& e : ctx->rp_ev)
-      if (!e) SHZ_HIP(ctx, hipEventCreate(&e));
-    SHZ_HIP(ctx, hipEventRecord(ctx->rp_ev[0], ctx->stream));
-  }
-  SHZ_TRY(shz_extract_owned(ctx, who, pcm, clip_off, n_clips, fs, amp_min, fan_value, flags & SHZ_PCM_DEVICE, hash_off, d_key, d_t1));
-  if (T.timed) {
-    SHZ_HIP(ctx, hipEventRecord(ctx->rp_ev[1], ctx->stream));
-    SHZ_HIP(ctx, hipEventSynchronize(ctx->rp_ev[1]));
-    if (T.extract) SHZ_HIP(ctx, hipEventElapsedTime(T.extract, ctx->rp_ev[0], ctx->rp_ev[1]));
-  }
+  SHZ_TRY(rp_timed_extract(ctx, T, [&] {
+    return shz_extract_owned(ctx, who, pcm, clip_off, n_clips, fs, amp_min, fan_value, flags & SHZ_PCM_DEVICE, hash_off, d_key, d_t1);
+  }));
   if (hash_off[n_clips] >= (1ull << 32)) SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "%s: %llu hashes", who, (unsigned long long)hash_off[n_clips]);
   return SHZ_OK;
 }
@@ -663,12 +824,12 @@ extern "C" int32_t shz_repeats_hashes(shz_ctx* ctx, const uint32_t* key32, const
   SHZ_TRY(rp_check_columns(ctx, who, key32, t1, hash_off, n_clips));
   const uint64_t N = hash_off[n_clips];
   if (n_recs == 0 || N == 0) {
-    rp_empty(O, n_recs);
+    rp_empty(O, n_recs, n_recs);
     return SHZ_OK;
   }
-  rp_columns C(ctx);
-  SHZ_TRY(C.upload(who, key32, t1, N));
-  return rp_core(ctx, who, (const uint32_t*)C.key, (const uint32_t*)C.t1, hash_off, rec_clip0, n_recs, P, O, nullptr, nullptr);
+  rp_upload C(ctx);
+  SHZ_TRY(C.upload(who, "columns", key32, N * 4, t1, N * 4, 0));
+  return rp_core(ctx, who, (const uint32_t*)C.a, (const uint32_t*)C.b, hash_off, rec_clip0, n_recs, P, O, nullptr, nullptr);
 }
 
 extern "C" int32_t shz_repeats_batch(shz_ctx* ctx, const int16_t* pcm, const uint64_t* clip_off, uint32_t n_clips,
@@ -689,15 +850,15 @@ extern "C" int32_t shz_repeats_batch(shz_ctx* ctx, const int16_t* pcm, const uin
   SHZ_TRY(rp_check_recs(ctx, who, n_clips, rec_clip0, n_recs));
   if (n_recs) SHZ_TRY(shz_check_clip_off(ctx, clip_off, n_clips));
   // (nothing is refused behind this line without a launch: the first write)
-  rp_times T(ms_extract, ms_pairs, ms_cells);
+  rp_times T(ms_extract, nullptr, ms_pairs, ms_cells);
   if (n_recs == 0) {
-    rp_empty(O, 0);
+    rp_empty(O, 0, 0);
     return SHZ_OK;
   }
   std::vector<uint64_t> hash_off((size_t)n_clips + 1, 0);
   const uint32_t *d_key = nullptr, *d_t1 = nullptr;
   SHZ_TRY(rp_extract(ctx, who, pcm, clip_off, n_clips, fs, amp_min, fan_value, flags, T, hash_off.data(), &d_key, &d_t1));
-  return rp_core(ctx, who, d_key, d_t1, hash_off.data(), rec_clip0, n_recs, P, O, T.pairs(), T.cells());
+  return rp_core(ctx, who, d_key, d_t1, hash_off.data(), rec_clip0, n_recs, P, O, T.at(T.pairs), T.at(T.cells));
 }
 
 // ---- content shared between two recordings: the join over a list of jobs (a, b) -----------------------------
@@ -711,11 +872,6 @@ extern "C" int32_t shz_repeats_batch(shz_ctx* ctx, const int16_t* pcm, const uin
 struct sh_params {
   int32_t lag_lo, lag_hi;
   uint32_t max_run, cell_shift, min_cell_pairs;
-};
-struct sh_out {
-  uint64_t* cell_off;
-  uint32_t *cell_lag, *cell_block, *cell_pairs, *cell_first, *cell_last, *rec_hashes, *job_skipped_keys;
-  uint64_t *job_pairs, *job_skipped_rows, cap_cells, *count;
 };
 
 // Item i belongs to the last job j with item_off[j] <= i (jobs without items share their successor's offset and are never that
@@ -735,27 +891,14 @@ __global__ __launch_bounds__(RP_THREADS) void sh_count_kernel(const uint64_t* __
                                                               uint32_t* __restrict__ skip_keys, unsigned long long* __restrict__ skip_rows) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n_items) return;
-  uint32_t j = 0, jh = n_jobs;
-  while (jh - j > 1) {
-    const uint32_t mid = j + ((jh - j) >> 1);
-    if (item_off[mid] <= i) j = mid; else jh = mid;
-  }
+  const uint32_t j = rp_last_le(item_off, 0u, n_jobs, i);
   const uint32_t b = job_b[j], el = rec_start[job_a[j]] + (i - item_off[j]);
   const uint64_t key = U[el];
   const uint64_t want = ((uint64_t)b << 32) | (uint32_t)(key >> RP_T_BITS);
   const uint32_t b1 = rec_start[b + 1];
-  uint32_t l = rec_start[b], r = b1;   // first x of b with U[x] >> 20 >= want
-  while (l < r) {
-    const uint32_t mid = l + ((r - l) >> 1);
-    if ((U[mid] >> RP_T_BITS) < want) l = mid + 1; else r = mid;
-  }
-  const uint32_t rb = l;
-  r = b1;                              // first x with U[x] >> 20 > want
-  while (l < r) {
-    const uint32_t mid = l + ((r - l) >> 1);
-    if ((U[mid] >> RP_T_BITS) <= want) l = mid + 1; else r = mid;
-  }
-  const uint32_t re = l, m_b = re - rb;
+  const auto key_of = [&](uint32_t x) { return U[x] >> RP_T_BITS; };
+  const uint32_t rb = rp_bound<false>(rec_start[b], b1, want, key_of);   // first x of b with U[x] >> 20 >= want
+  const uint32_t re = rp_bound<true>(rb, b1, want, key_of), m_b = re - rb;   // behind it: first x with U[x] >> 20 > want
   uint32_t first = 0, n = 0;
   if (m_b) {
     const uint32_t h = head[el], id = pos[el] + h - 1, m_a = run_start[id + 1] - run_start[id];
@@ -770,18 +913,9 @@ __global__ __launch_bounds__(RP_THREADS) void sh_count_kernel(const uint64_t* __
       if (t_hi >= 0 && t_lo <= (int32_t)RP_T_MASK) {
         t_lo = max(t_lo, 0);
         t_hi = min(t_hi, (int32_t)RP_T_MASK);
-        l = rb, r = re;                // first x with t_x >= t_lo
-        while (l < r) {
-          const uint32_t mid = l + ((r - l) >> 1);
-          if (((uint32_t)U[mid] & RP_T_MASK) < (uint32_t)t_lo) l = mid + 1; else r = mid;
-        }
-        first = l;
-        r = re;                        // first x with t_x > t_hi
-        while (l < r) {
-          const uint32_t mid = l + ((r - l) >> 1);
-          if (((uint32_t)U[mid] & RP_T_MASK) <= (uint32_t)t_hi) l = mid + 1; else r = mid;
-        }
-        n = l - first;
+        const auto t_of = [&](uint32_t x) { return (uint32_t)U[x] & RP_T_MASK; };
+        first = rp_bound<false>(rb, re, (uint32_t)t_lo, t_of);        // first x with t_x >= t_lo
+        n = rp_bound<true>(first, re, (uint32_t)t_hi, t_of) - first;   // behind it: first x with t_x > t_hi
       }
     }
   }
@@ -798,60 +932,27 @@ __global__ __launch_bounds__(RP_THREADS) void sh_expand_kernel(const uint64_t* _
                                                                const uint32_t* __restrict__ item_off, uint32_t x0, uint32_t x1,
                                                                uint64_t P0, uint64_t np, uint32_t tile, uint32_t j0, uint32_t j1,
                                                                uint64_t* __restrict__ out) {
-  const uint64_t base = (uint64_t)blockIdx.x * tile;
-  if (base >= np) return;
-  const uint64_t end = min(base + tile, np);
-  uint32_t xA, xB, jA, jB;
-  {
-    const uint64_t gA = P0 + base, gB = P0 + end - 1;
-    uint32_t l = x0, h = x1;
-    while (h - l > 1) {
-      const uint32_t mid = l + ((h - l) >> 1);
-      if (poff[mid] <= gA) l = mid; else h = mid;
-    }
-    xA = l;
-    h = x1;
-    while (h - l > 1) {
-      const uint32_t mid = l + ((h - l) >> 1);
-      if (poff[mid] <= gB) l = mid; else h = mid;
-    }
-    xB = l;
-    l = j0, h = j1;
-    while (h - l > 1) {
-      const uint32_t mid = l + ((h - l) >> 1);
-      if (item_off[mid] <= xA) l = mid; else h = mid;
-    }
-    jA = l;
-    h = j1;
-    while (h - l > 1) {
-      const uint32_t mid = l + ((h - l) >> 1);
-      if (item_off[mid] <= xB) l = mid; else h = mid;
-    }
-    jB = l;
-  }
-  for (uint64_t p = base + threadIdx.x; p < end; p += blockDim.x) {
+  rp_tile T;
+  if (!rp_tile_of(poff, x0, x1, P0, np, tile, &T)) return;
+  const uint32_t jA = rp_last_le(item_off, j0, j1, T.xA), jB = rp_last_le(item_off, jA, j1, T.xB);
+  for (uint64_t p = T.base + threadIdx.x; p < T.end; p += blockDim.x) {
     const uint64_t g = P0 + p;
-    uint32_t l = xA, h = xB + 1;
-    while (h - l > 1) {
-      const uint32_t mid = l + ((h - l) >> 1);
-      if (poff[mid] <= g) l = mid; else h = mid;
-    }
-    uint32_t j = jA, jh = jB + 1;
-    while (jh - j > 1) {
-      const uint32_t mid = j + ((jh - j) >> 1);
-      if (item_off[mid] <= l) j = mid; else jh = mid;
-    }
+    const uint32_t l = rp_tile_owner(poff, T, g), j = rp_last_le(item_off, jA, jB + 1, l);
     const uint32_t ta = (uint32_t)U[el[l]] & RP_T_MASK, tb = (uint32_t)U[lo[l] + (uint32_t)(g - poff[l])] & RP_T_MASK;
     out[p] = ((uint64_t)(j - j0) << (RP_T_BITS + SH_LAG_BITS)) | ((uint64_t)(tb + SHZ_SHARED_LAG_BIAS - ta) << RP_T_BITS) | ta;
   }
 }
 
-static int32_t sh_check(shz_ctx* ctx, const char* who, const sh_params& P, const sh_out& O, const uint32_t* job_a, const uint32_t* job_b,
+// job j names two recordings of the call
+static int32_t sh_check_names(shz_ctx* ctx, const char* who, uint32_t j, uint32_t a, uint32_t b, uint32_t n_recs) {
+  if (a >= n_recs || b >= n_recs) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: job %u names the recordings %u and %u of %u", who, j, a, b, n_recs);
+  return SHZ_OK;
+}
+// what the plain calls refuse about the outputs, the one window, the knobs and the jobs: the job count before the jobs.  (The
+// warped calls look at their jobs first, word the window per job and let a recording meet itself: sw_check)
+static int32_t sh_check(shz_ctx* ctx, const char* who, const sh_params& P, const rp_out& O, const uint32_t* job_a, const uint32_t* job_b,
                         uint32_t n_jobs, uint32_t n_recs) {
-  if (!O.count || !O.cell_off || !O.rec_hashes || !O.job_pairs || !O.job_skipped_keys || !O.job_skipped_rows)
-    SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: count, cell_off, rec_hashes or a job_* array is NULL", who);
-  if (O.cap_cells && (!O.cell_lag || !O.cell_block || !O.cell_pairs || !O.cell_first || !O.cell_last))
-    SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: NULL cell array with room for %llu cells", who, (unsigned long long)O.cap_cells);
+  SHZ_TRY(rp_check_out(ctx, who, O, "count, cell_off, rec_hashes or a job_* array"));
   const int32_t most = (int32_t)RP_T_MASK;
   if (P.lag_lo < -most || P.lag_hi > most)
     SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: the lag window [%d, %d] must lie in [-(2^20 - 1), 2^20 - 1]", who, P.lag_lo, P.lag_hi);
@@ -860,21 +961,11 @@ static int32_t sh_check(shz_ctx* ctx, const char* who, const sh_params& P, const
   if (n_jobs > SH_MAX_JOBS) SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "%s: %u jobs in one call, at most %u", who, n_jobs, SH_MAX_JOBS);
   if (n_jobs && (!job_a || !job_b)) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: NULL job list with %u jobs", who, n_jobs);
   for (uint32_t j = 0; j < n_jobs; ++j) {
-    if (job_a[j] >= n_recs || job_b[j] >= n_recs)
-      SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: job %u names the recordings %u and %u of %u", who, j, job_a[j], job_b[j], n_recs);
+    SHZ_TRY(sh_check_names(ctx, who, j, job_a[j], job_b[j], n_recs));
     if (job_a[j] == job_b[j])
       SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: job %u joins recording %u with itself (that is shz_repeats_*)", who, j, job_a[j]);
   }
   return SHZ_OK;
-}
-static void sh_empty(const sh_out& O, uint32_t n_recs, uint32_t n_jobs) {
-  *O.count = 0;
-  for (uint32_t j = 0; j <= n_jobs; ++j) O.cell_off[j] = 0;
-  for (uint32_t r = 0; r < n_recs; ++r) O.rec_hashes[r] = 0;
-  for (uint32_t j = 0; j < n_jobs; ++j) {
-    O.job_skipped_keys[j] = 0;
-    O.job_pairs[j] = O.job_skipped_rows[j] = 0;
-  }
 }
 
 // The core on device columns, as rp_core: everything is checked (sh_check, rp_check_recs), the outputs are written when the call
@@ -882,61 +973,40 @@ static void sh_empty(const sh_out& O, uint32_t n_recs, uint32_t n_jobs) {
 // window of every job, checked by the caller
 static int32_t sh_core(shz_ctx* ctx, const char* who, const uint32_t* d_key32, const uint32_t* d_t1, const uint64_t* hash_off,
                        const uint32_t* rec_clip0, uint32_t n_recs, const uint32_t* job_a, const uint32_t* job_b, uint32_t n_jobs,
-                       const sh_params& P, const sh_out& O, float* ms_pairs, float* ms_cells, const int32_t* job_lag_lo = nullptr,
+                       const sh_params& P, const rp_out& O, float* ms_pairs, float* ms_cells, const int32_t* job_lag_lo = nullptr,
                        const int32_t* job_lag_hi = nullptr) {
   const uint64_t N = n_recs ? hash_off[rec_clip0[n_recs]] : 0;
   if (N == 0) {
-    sh_empty(O, n_recs, n_jobs);
+    rp_empty(O, n_recs, n_jobs);
     return SHZ_OK;
   }
-  const bool small = (ctx->debug & SHZ_DEBUG_REPEAT_SMALL_SLICES) != 0, timed = ms_pairs || ms_cells;
-  const uint32_t bs = small ? RP_SMALL : RP_THREADS, tile = small ? RP_SMALL : RP_TILE;
   hipStream_t st = ctx->stream;
-  float pairs_ms = 0.f, cells_ms = 0.f;
-  if (timed) {
-    for (hipEvent_t& e : ctx->rp_ev)
-      if (!e) SHZ_HIP(ctx, hipEventCreate(&e));
-    SHZ_HIP(ctx, hipEventRecord(ctx->rp_ev[0], st));
-  }
-  // the block of the recordings and jobs: tot[4] | rec_off | job_po | skip_rows (u64) | rec_start | item_off | job_a | job_b |
-  // skip_keys (u32) | with a window per job: lag_lo | lag_hi (i32).  rec_off and the jobs go up, item_off follows once the borders
-  // are known, the rest comes back in one copy
+  rp_call X(ctx, who, ms_pairs, ms_cells);
+  SHZ_TRY(X.K.start());
+  // the header: the jobs own the pairs, and behind its fields lie item_off | job_a | job_b (u32) | with a window per job: lag_lo |
+  // lag_hi (i32).  rec_off and the jobs go up, item_off follows once the borders are known, the rest comes back in one copy
   const bool windows = job_lag_lo && job_lag_hi;
-  const uint64_t nr1 = (uint64_t)n_recs + 1, nj1 = (uint64_t)n_jobs + 1;
-  const uint64_t o_off = 4, o_po = o_off + nr1, o_rows = o_po + nj1, n64 = o_rows + n_jobs;
-  const uint64_t blk_bytes = n64 * 8 + (nr1 + nj1 + (windows ? 5ull : 3ull) * n_jobs) * 4;
-  std::vector<uint64_t> hblk((size_t)((blk_bytes + 7) / 8), 0);
-  uint32_t *h_rec_start = (uint32_t*)(hblk.data() + n64), *h_item_off = h_rec_start + nr1, *h_job_a = h_item_off + nj1,
-           *h_job_b = h_job_a + n_jobs, *h_skip_keys = h_job_b + n_jobs;
-  for (uint32_t r = 0; r <= n_recs; ++r) hblk[o_off + r] = hash_off[rec_clip0[r]];
-  for (uint32_t j = 0; j < n_jobs; ++j) {
-    h_job_a[j] = job_a[j];
-    h_job_b[j] = job_b[j];
-  }
+  const uint64_t nj1 = (uint64_t)n_jobs + 1;
+  rp_header H(ctx, n_recs, n_jobs);
+  const rp_field<uint32_t> f_item = H.add<uint32_t>(nj1), f_a = H.add<uint32_t>(n_jobs), f_b = H.add<uint32_t>(n_jobs);
+  const rp_field<int32_t> f_lo = H.add<int32_t>(windows ? n_jobs : 0), f_hi = H.add<int32_t>(windows ? n_jobs : 0);
+  SHZ_TRY(H.place(hash_off, rec_clip0));
+  std::copy_n(job_a, n_jobs, H.h(f_a));
+  std::copy_n(job_b, n_jobs, H.h(f_b));
   if (windows) {
-    memcpy(h_skip_keys + n_jobs, job_lag_lo, (size_t)n_jobs * 4);
-    memcpy(h_skip_keys + 2 * (size_t)n_jobs, job_lag_hi, (size_t)n_jobs * 4);
+    std::copy_n(job_lag_lo, n_jobs, H.h(f_lo));
+    std::copy_n(job_lag_hi, n_jobs, H.h(f_hi));
   }
-  void* d_blk;
-  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_RP_REC, hblk.size() * 8, &d_blk));
-  uint64_t* d64 = (uint64_t*)d_blk;
-  uint64_t *d_tot = d64, *d_rec_off = d64 + o_off, *d_job_po = d64 + o_po, *d_skip_rows = d64 + o_rows;
-  uint32_t *d_rec_start = (uint32_t*)(d64 + n64), *d_item_off = d_rec_start + nr1, *d_job_a = d_item_off + nj1, *d_job_b = d_job_a + n_jobs,
-           *d_skip_keys = d_job_b + n_jobs;
-  const int32_t *d_job_lo = windows ? (const int32_t*)(d_skip_keys + n_jobs) : nullptr, *d_job_hi = windows ? d_job_lo + n_jobs : nullptr;
-  SHZ_HIP(ctx, shz_memcpy(ctx, d_blk, hblk.data(), hblk.size() * 8, hipMemcpyHostToDevice));
+  SHZ_TRY(H.up());
   // 1) .. 3) the elements, as the self-join's
   rp_elems E;
-  SHZ_TRY(rp_elements(ctx, who, d_key32, d_t1, N, n_recs, d_rec_off, d_tot, d_rec_start, bs, &E));
-  const uint32_t nu = E.nu;
+  SHZ_TRY(rp_elements(X, d_key32, d_t1, N, H, &E));
   // 4) the items: the borders come back (the count kernel's grid needs their total on the host anyway), item_off goes up
-  SHZ_HIP(ctx, shz_memcpy(ctx, h_rec_start, d_rec_start, nr1 * 4, hipMemcpyDeviceToHost));
+  SHZ_TRY(H.down(H.rec_start, (uint64_t)n_recs + 1));
   SHZ_HIP(ctx, hipStreamSynchronize(st));
-  if (h_rec_start[0] != 0 || h_rec_start[n_recs] != nu)
-    SHZ_FAIL(ctx, SHZ_E_STATE, "%s: the recordings' borders do not span the %u unique hashes", who, nu);
-  for (uint32_t r = 0; r < n_recs; ++r)
-    if (h_rec_start[r + 1] < h_rec_start[r]) SHZ_FAIL(ctx, SHZ_E_STATE, "%s: the borders of recording %u decrease", who, r);
-  std::vector<uint32_t> rec_start(h_rec_start, h_rec_start + nr1), item_off((size_t)nj1, 0);
+  const uint32_t* rec_start = H.h(H.rec_start);
+  SHZ_TRY(rp_check_borders(X, rec_start, n_recs, E.nu));
+  uint32_t* item_off = H.h(f_item);
   uint64_t ni64 = 0;
   for (uint32_t j = 0; j < n_jobs; ++j) {
     ni64 += rec_start[job_a[j] + 1] - rec_start[job_a[j]];
@@ -947,71 +1017,32 @@ static int32_t sh_core(shz_ctx* ctx, const char* who, const uint32_t* d_key32, c
   }
   const uint32_t ni = (uint32_t)ni64;
   // 5) count, scan, the jobs' numbers
-  void *d_lo = nullptr, *d_el = nullptr, *d_cnt, *d_poff = nullptr;
+  rp_counts C;
+  void* d_el = nullptr;
   if (ni) {
-    memcpy(h_item_off, item_off.data(), nj1 * 4);
-    SHZ_HIP(ctx, shz_memcpy(ctx, d_item_off, h_item_off, nj1 * 4, hipMemcpyHostToDevice));
-    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_RP_LO, (uint64_t)ni * 4, &d_lo));
+    SHZ_TRY(H.up(f_item, nj1));
+    SHZ_TRY(C.reserve(ctx, ni));
     SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SH_EL, (uint64_t)ni * 4, &d_el));
-    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_RP_CNT, (uint64_t)ni * 8, &d_cnt));
-    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_RP_POFF, ((uint64_t)ni + 1) * 8, &d_poff));
-    hipLaunchKernelGGL(sh_count_kernel, dim3(rp_grid(ni, bs)), dim3(bs), 0, st, E.U, E.head, E.pos, E.run_start, (const uint32_t*)d_rec_start,
-                       (const uint32_t*)d_item_off, (const uint32_t*)d_job_a, (const uint32_t*)d_job_b, d_job_lo, d_job_hi, n_jobs, ni, P,
-                       (uint64_t*)d_cnt,
-                       (uint32_t*)d_lo, (uint32_t*)d_el, d_skip_keys, (unsigned long long*)d_skip_rows);
+    hipLaunchKernelGGL(sh_count_kernel, dim3(rp_grid(ni, X.bs)), dim3(X.bs), 0, st, E.U, E.head, E.pos, E.run_start,
+                       (const uint32_t*)H.d(H.rec_start), (const uint32_t*)H.d(f_item), (const uint32_t*)H.d(f_a), (const uint32_t*)H.d(f_b),
+                       windows ? (const int32_t*)H.d(f_lo) : nullptr, windows ? (const int32_t*)H.d(f_hi) : nullptr, n_jobs, ni, P, C.cnt,
+                       C.lo, (uint32_t*)d_el, H.d(H.skip_keys), (unsigned long long*)H.d(H.skip_rows));
     SHZ_HIP(ctx, hipGetLastError());
-    SHZ_TRY(shz_scan_u64(ctx, (const uint64_t*)d_cnt, (uint64_t*)d_poff, ni, (uint64_t*)d_poff + ni));
-    hipLaunchKernelGGL(rp_rec_pairs_kernel, dim3(rp_grid(nj1, bs)), dim3(bs), 0, st, (const uint64_t*)d_poff, (const uint32_t*)d_item_off,
-                       n_jobs, d_job_po);
-    SHZ_HIP(ctx, hipGetLastError());
-    SHZ_HIP(ctx, shz_memcpy(ctx, hblk.data(), d_blk, hblk.size() * 8, hipMemcpyDeviceToHost));
   }
-  if (timed) SHZ_HIP(ctx, hipEventRecord(ctx->rp_ev[1], st));
-  SHZ_HIP(ctx, hipStreamSynchronize(st));
-  if (timed) {
-    float a = 0.f;
-    SHZ_HIP(ctx, hipEventElapsedTime(&a, ctx->rp_ev[0], ctx->rp_ev[1]));
-    pairs_ms += a;
-  }
-  const uint64_t *job_po = hblk.data() + o_po, *skip_rows = hblk.data() + o_rows;
-  if (job_po[0] != 0) SHZ_FAIL(ctx, SHZ_E_STATE, "%s: %llu pairs in front of the first job", who, (unsigned long long)job_po[0]);
-  for (uint32_t j = 0; j < n_jobs; ++j)
-    if (job_po[j + 1] < job_po[j]) SHZ_FAIL(ctx, SHZ_E_STATE, "%s: the pairs in front of job %u decrease", who, j);
-  // 6) the slices: consecutive whole jobs whose two pair buffers fit 1/8 of the workspace limit
-  const uint64_t max_pairs = std::min<uint64_t>(std::max<uint64_t>(ctx->ws_limit / 8 / 16, 1), 1ull << 31);
-  for (uint32_t j = 0; j < n_jobs; ++j)
-    if (job_po[j + 1] - job_po[j] > max_pairs)
-      SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED,
-               "%s: job %u (recordings %u and %u) has %llu pairs, a slice holds %llu (workspace limit): narrow the lag window [%d, %d] or "
-               "lower max_run (%u)",
-               who, j, job_a[j], job_b[j], (unsigned long long)(job_po[j + 1] - job_po[j]), (unsigned long long)max_pairs,
-               windows ? job_lag_lo[j] : P.lag_lo, windows ? job_lag_hi[j] : P.lag_hi, P.max_run);
-  uint64_t np_max = 0;
-  const std::vector<uint32_t> slices = rp_cut_slices(job_po, n_jobs, max_pairs, small, &np_max);
-  // 7) slice by slice: expand, then the self-join's cell stage on a lag field of 21 bits
-  rp_cells C(ctx, who, "job", n_jobs, O.cap_cells, bs, timed);
-  SHZ_TRY(C.reserve(np_max));
-  for (size_t s = 0; s + 1 < slices.size(); ++s) {
-    const uint32_t j0 = slices[s], j1 = slices[s + 1];
-    const uint64_t P0 = job_po[j0], np64 = job_po[j1] - P0;
-    if (np64 == 0) continue;
-    const uint32_t np = (uint32_t)np64;   // (<= 2^31)
-    if (timed) SHZ_HIP(ctx, hipEventRecord(ctx->rp_ev[0], st));
-    hipLaunchKernelGGL(sh_expand_kernel, dim3(rp_grid(np, tile)), dim3(bs), 0, st, E.U, (const uint64_t*)d_poff, (const uint32_t*)d_lo,
-                       (const uint32_t*)d_el, (const uint32_t*)d_item_off, item_off[j0], item_off[j1], P0, np64, tile, j0, j1, C.ka);
-    SHZ_HIP(ctx, hipGetLastError());
-    SHZ_TRY(C.slice(d_tot, np, P.cell_shift, P.min_cell_pairs, SH_LAG_BITS, j0, j1, &pairs_ms, &cells_ms));
-  }
-  // 8) the outputs
-  for (uint32_t r = 0; r < n_recs; ++r) O.rec_hashes[r] = rec_start[r + 1] - rec_start[r];
-  for (uint32_t j = 0; j < n_jobs; ++j) {
-    O.job_pairs[j] = job_po[j + 1] - job_po[j];
-    O.job_skipped_keys[j] = h_skip_keys[j];
-    O.job_skipped_rows[j] = skip_rows[j];
-  }
-  if (ms_pairs) *ms_pairs = pairs_ms;
-  if (ms_cells) *ms_cells = cells_ms;
-  return C.copy_out(O.cell_off, O.cell_lag, O.cell_block, O.cell_pairs, O.cell_first, O.cell_last, O.count);
+  SHZ_TRY(rp_owner_pairs(X, H, "job", C, ni, H.d(f_item)));
+  // 6) slice by slice: expand, then the self-join's cell stage on a lag field of 21 bits; 7) the outputs
+  auto refuse = [&](uint32_t j, uint64_t pairs, uint64_t max_pairs) -> int32_t {
+    SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED,
+             "%s: job %u (recordings %u and %u) has %llu pairs, a slice holds %llu (workspace limit): narrow the lag window [%d, %d] or "
+             "lower max_run (%u)",
+             who, j, job_a[j], job_b[j], (unsigned long long)pairs, (unsigned long long)max_pairs, windows ? job_lag_lo[j] : P.lag_lo,
+             windows ? job_lag_hi[j] : P.lag_hi, P.max_run);
+  };
+  auto expand = [&](uint32_t j0, uint32_t j1, uint64_t P0, uint64_t np, uint64_t* out) {
+    hipLaunchKernelGGL(sh_expand_kernel, dim3(rp_grid(np, X.tile)), dim3(X.bs), 0, st, E.U, (const uint64_t*)C.poff, (const uint32_t*)C.lo,
+                       (const uint32_t*)d_el, (const uint32_t*)H.d(f_item), item_off[j0], item_off[j1], P0, np, X.tile, j0, j1, out);
+  };
+  return rp_slices(X, H, "job", P.cell_shift, P.min_cell_pairs, SH_LAG_BITS, O, refuse, expand);
 }
 
 extern "C" int32_t shz_shared_hashes(shz_ctx* ctx, const uint32_t* key32, const uint32_t* t1, const uint64_t* hash_off, uint32_t n_clips,
@@ -1024,7 +1055,7 @@ extern "C" int32_t shz_shared_hashes(shz_ctx* ctx, const uint32_t* key32, const 
   const char* who = "shz_shared_hashes";
   if (!ctx) return SHZ_E_INVALID;
   const sh_params P{lag_lo, lag_hi, max_run, cell_shift, min_cell_pairs};
-  const sh_out O{cell_off, cell_lag, cell_block, cell_pairs, cell_first, cell_last, rec_hashes, job_skipped_keys, job_pairs,
+  const rp_out O{cell_off, cell_lag, cell_block, cell_pairs, cell_first, cell_last, rec_hashes, job_skipped_keys, job_pairs,
                  job_skipped_rows, cap_cells, count};
   if (flags) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: flags must be 0", who);
   SHZ_TRY(sh_check(ctx, who, P, O, job_a, job_b, n_jobs, n_recs));
@@ -1032,12 +1063,12 @@ extern "C" int32_t shz_shared_hashes(shz_ctx* ctx, const uint32_t* key32, const 
   SHZ_TRY(rp_check_columns(ctx, who, key32, t1, hash_off, n_clips));
   const uint64_t N = hash_off[n_clips];
   if (n_recs == 0 || N == 0) {
-    sh_empty(O, n_recs, n_jobs);
+    rp_empty(O, n_recs, n_jobs);
     return SHZ_OK;
   }
-  rp_columns C(ctx);
-  SHZ_TRY(C.upload(who, key32, t1, N));
-  return sh_core(ctx, who, (const uint32_t*)C.key, (const uint32_t*)C.t1, hash_off, rec_clip0, n_recs, job_a, job_b, n_jobs, P, O, nullptr,
+  rp_upload C(ctx);
+  SHZ_TRY(C.upload(who, "columns", key32, N * 4, t1, N * 4, 0));
+  return sh_core(ctx, who, (const uint32_t*)C.a, (const uint32_t*)C.b, hash_off, rec_clip0, n_recs, job_a, job_b, n_jobs, P, O, nullptr,
                  nullptr);
 }
 
@@ -1051,7 +1082,7 @@ extern "C" int32_t shz_shared_batch(shz_ctx* ctx, const int16_t* pcm, const uint
   const char* who = "shz_shared_batch";
   if (!ctx) return SHZ_E_INVALID;
   const sh_params P{lag_lo, lag_hi, max_run, cell_shift, min_cell_pairs};
-  const sh_out O{cell_off, cell_lag, cell_block, cell_pairs, cell_first, cell_last, rec_hashes, job_skipped_keys, job_pairs,
+  const rp_out O{cell_off, cell_lag, cell_block, cell_pairs, cell_first, cell_last, rec_hashes, job_skipped_keys, job_pairs,
                  job_skipped_rows, cap_cells, count};
   if (flags & ~SHZ_PCM_DEVICE) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: flags may hold SHZ_PCM_DEVICE", who);
   SHZ_TRY(sh_check(ctx, who, P, O, job_a, job_b, n_jobs, n_recs));
@@ -1059,15 +1090,15 @@ extern "C" int32_t shz_shared_batch(shz_ctx* ctx, const int16_t* pcm, const uint
   SHZ_TRY(rp_check_recs(ctx, who, n_clips, rec_clip0, n_recs));
   if (n_recs) SHZ_TRY(shz_check_clip_off(ctx, clip_off, n_clips));
   // (nothing is refused behind this line without a launch: the first write)
-  rp_times T(ms_extract, ms_pairs, ms_cells);
+  rp_times T(ms_extract, nullptr, ms_pairs, ms_cells);
   if (n_recs == 0) {
-    sh_empty(O, 0, 0);   // (without recordings sh_check let no job through)
+    rp_empty(O, 0, 0);   // (without recordings sh_check let no job through)
     return SHZ_OK;
   }
   std::vector<uint64_t> hash_off((size_t)n_clips + 1, 0);
   const uint32_t *d_key = nullptr, *d_t1 = nullptr;
   SHZ_TRY(rp_extract(ctx, who, pcm, clip_off, n_clips, fs, amp_min, fan_value, flags, T, hash_off.data(), &d_key, &d_t1));
-  return sh_core(ctx, who, d_key, d_t1, hash_off.data(), rec_clip0, n_recs, job_a, job_b, n_jobs, P, O, T.pairs(), T.cells());
+  return sh_core(ctx, who, d_key, d_t1, hash_off.data(), rec_clip0, n_recs, job_a, job_b, n_jobs, P, O, T.at(T.pairs), T.at(T.cells));
 }
 
 // ---- ALTERED content shared between recordings: the join at a table of warps -----------------------------------
@@ -1093,19 +1124,15 @@ struct sw_plan {
 
 // what both entry points refuse about the outputs, the knobs, the table and the jobs: SHZ_E_INVALID first, then the limits that
 // depend on the counts alone.  P's window is not read
-static int32_t sw_check(shz_ctx* ctx, const char* who, const sh_params& P, const sh_out& O, const uint32_t* job_hashes, const sw_jobs& J,
+static int32_t sw_check(shz_ctx* ctx, const char* who, const sh_params& P, const rp_out& O, const uint32_t* job_hashes, const sw_jobs& J,
                         uint32_t n_recs, uint32_t fan_value) {
-  if (!O.count || !O.cell_off || !O.rec_hashes || !O.job_pairs || !O.job_skipped_keys || !O.job_skipped_rows || !job_hashes)
-    SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: count, cell_off, rec_hashes or a job_* array is NULL", who);
-  if (O.cap_cells && (!O.cell_lag || !O.cell_block || !O.cell_pairs || !O.cell_first || !O.cell_last))
-    SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: NULL cell array with room for %llu cells", who, (unsigned long long)O.cap_cells);
+  SHZ_TRY(rp_check_out(ctx, who, O, "count, cell_off, rec_hashes or a job_* array", job_hashes != nullptr));
   SHZ_TRY(rp_check_knobs(ctx, who, P.max_run, P.cell_shift, P.min_cell_pairs));
   SHZ_TRY(sp_check_ladder(ctx, who, "n_warps", "tempo", J.tempo, "pitch", J.pitch, J.n_warps, fan_value));
   if (J.n && (!J.a || !J.b || !J.v || !J.lo || !J.hi)) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: NULL job array with %u jobs", who, J.n);
   const int32_t most = (int32_t)RP_T_MASK;
   for (uint32_t j = 0; j < J.n && j < SH_MAX_JOBS; ++j) {
-    if (J.a[j] >= n_recs || J.b[j] >= n_recs)
-      SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: job %u names the recordings %u and %u of %u", who, j, J.a[j], J.b[j], n_recs);
+    SHZ_TRY(sh_check_names(ctx, who, j, J.a[j], J.b[j], n_recs));
     if (J.v[j] >= J.n_warps) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: job %u names warp %u of %u", who, j, J.v[j], J.n_warps);
     if (J.lo[j] < -most || J.hi[j] > most)
       SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: the lag window [%d, %d] of job %u must lie in [-(2^20 - 1), 2^20 - 1]", who, J.lo[j], J.hi[j], j);
@@ -1152,17 +1179,17 @@ static int32_t sw_check_times(shz_ctx* ctx, const char* who, const uint64_t* las
   return SHZ_OK;
 }
 
-static void sw_empty(const sh_out& O, uint32_t* job_hashes, uint32_t n_recs, uint32_t n_jobs) {
-  sh_empty(O, n_recs, n_jobs);
+static void sw_empty(const rp_out& O, uint32_t* job_hashes, uint32_t n_recs, uint32_t n_jobs) {
+  rp_empty(O, n_recs, n_jobs);
   for (uint32_t j = 0; j < n_jobs; ++j) job_hashes[j] = 0;
 }
 
 // The core on device peak lists (d_pf / d_pt, peak_off their host CSR from 0 over the clips, at least one peak): everything is
-// checked.  ms_warp (may be NULL) gets the warp pass's stream interval (rp_ev[0] .. rp_ev[1], the read-backs of the job ranges and
+// checked.  ms_warp (may be NULL) gets the warp pass's stream interval (a lap of the clock, the read-backs of the job ranges and
 // of the CSR inside it)
 static int32_t sw_core(shz_ctx* ctx, const char* who, const uint16_t* d_pf, const uint32_t* d_pt, const uint64_t* peak_off, uint32_t n_clips,
                        const uint32_t* rec_clip0, uint32_t n_recs, uint32_t fan_value, const sw_jobs& J, const sw_plan& L, const sh_params& P,
-                       const sh_out& O, uint32_t* job_hashes, float* ms_warp, float* ms_pairs, float* ms_cells) {
+                       const rp_out& O, uint32_t* job_hashes, float* ms_warp, float* ms_pairs, float* ms_cells) {
   hipStream_t st = ctx->stream;
   const uint32_t n_virt = n_recs + (uint32_t)L.va_rec.size();
   uint64_t n_warped = peak_off[n_clips];   // the (peak, warp) items of the pass, known before it runs
@@ -1184,7 +1211,8 @@ static int32_t sw_core(shz_ctx* ctx, const char* who, const uint16_t* d_pf, cons
   if (wj.size() >> 31) SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "%s: %llu warped clips in one call", who, (unsigned long long)wj.size());
   const uint32_t n_wj = (uint32_t)wj.size();
   // 2) one warp pass over all of them; the hashes stay on the device
-  if (ms_warp) SHZ_HIP(ctx, hipEventRecord(ctx->rp_ev[0], st));
+  rp_clock K(ctx, ms_warp != nullptr);
+  SHZ_TRY(K.start());
   std::vector<uint64_t> ho((size_t)n_wj + 1, 0);
   uint64_t n_items = 0;
   sp_pass W;
@@ -1196,14 +1224,10 @@ static int32_t sw_core(shz_ctx* ctx, const char* who, const uint16_t* d_pf, cons
   SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SP_KEY, total * 4 + 64, &d_key));
   SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_SP_T1, total * 4 + 64, &d_t1));
   if (total) SHZ_TRY(sp_write(ctx, W, (uint32_t*)d_key, (uint32_t*)d_t1, total));
-  if (ms_warp) {
-    SHZ_HIP(ctx, hipEventRecord(ctx->rp_ev[1], st));
-    SHZ_HIP(ctx, hipEventSynchronize(ctx->rp_ev[1]));
-    SHZ_HIP(ctx, hipEventElapsedTime(ms_warp, ctx->rp_ev[0], ctx->rp_ev[1]));
-  }
+  SHZ_TRY(K.lap(ms_warp));
   // 3) the join of (virtual(a, v), b) at the window of every job
   std::vector<uint32_t> virt_hashes((size_t)n_virt, 0);
-  sh_out V = O;
+  rp_out V = O;
   V.rec_hashes = virt_hashes.data();
   const int32_t rc = sh_core(ctx, who, (const uint32_t*)d_key, (const uint32_t*)d_t1, ho.data(), vrec.data(), n_virt, L.job_virt.data(), J.b,
                              J.n, P, V, ms_pairs, ms_cells, J.lo, J.hi);
@@ -1215,29 +1239,6 @@ static int32_t sw_core(shz_ctx* ctx, const char* who, const uint16_t* d_pf, cons
   for (uint32_t j = 0; j < J.n; ++j) job_hashes[j] = virt_hashes[L.job_virt[j]];
   return rc;
 }
-
-// device copies of N >= 1 host peaks for the length of a call (tests / tools)
-struct sw_peaks {
-  shz_ctx* ctx;
-  void *f = nullptr, *t = nullptr;
-  explicit sw_peaks(shz_ctx* c) : ctx(c) {}
-  int32_t upload(const char* who, const uint16_t* peak_f, const uint32_t* peak_t, uint64_t N) {
-    SHZ_HIP(ctx, hipSetDevice(ctx->device));
-    if (hipMalloc(&f, N * 2 + 64) != hipSuccess || hipMalloc(&t, N * 4 + 64) != hipSuccess) {
-      (void)hipGetLastError();
-      SHZ_FAIL(ctx, SHZ_E_NOMEM, "%s: hipMalloc(%llu + %llu) failed", who, (unsigned long long)(N * 2), (unsigned long long)(N * 4));
-    }
-    if (shz_memcpy(ctx, f, peak_f, N * 2, hipMemcpyHostToDevice) != hipSuccess ||
-        shz_memcpy(ctx, t, peak_t, N * 4, hipMemcpyHostToDevice) != hipSuccess)
-      SHZ_FAIL(ctx, SHZ_E_HIP, "%s: copy of the peaks failed", who);
-    return SHZ_OK;
-  }
-  ~sw_peaks() {
-    if (f || t) (void)hipStreamSynchronize(ctx->stream);
-    if (f) (void)hipFree(f);
-    if (t) (void)hipFree(t);
-  }
-};
 
 extern "C" int32_t shz_shared_warps_peaks(shz_ctx* ctx, const uint16_t* peak_f, const uint32_t* peak_t, const uint64_t* peak_off,
                                           uint32_t n_clips, const uint32_t* rec_clip0, uint32_t n_recs, uint32_t fan_value,
@@ -1251,19 +1252,15 @@ extern "C" int32_t shz_shared_warps_peaks(shz_ctx* ctx, const uint16_t* peak_f, 
   const char* who = "shz_shared_warps_peaks";
   if (!ctx) return SHZ_E_INVALID;
   const sh_params P{0, 0, max_run, cell_shift, min_cell_pairs};
-  const sh_out O{cell_off, cell_lag, cell_block, cell_pairs, cell_first, cell_last, rec_hashes, job_skipped_keys, job_pairs,
+  const rp_out O{cell_off, cell_lag, cell_block, cell_pairs, cell_first, cell_last, rec_hashes, job_skipped_keys, job_pairs,
                  job_skipped_rows, cap_cells, count};
   const sw_jobs J{job_a, job_b, job_v, job_lag_lo, job_lag_hi, n_jobs, tempo_q16, pitch_q16, n_warps};
   // everything that can be refused is refused before the first launch
   if (flags) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: flags must be 0", who);
   SHZ_TRY(sw_check(ctx, who, P, O, job_hashes, J, n_recs, fan_value));
   SHZ_TRY(rp_check_recs(ctx, who, n_clips, rec_clip0, n_recs));
-  if (!peak_off) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: peak_off is NULL", who);
-  if (peak_off[0] != 0) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: peak_off must start at 0 (it starts at %llu)", who, (unsigned long long)peak_off[0]);
-  for (uint32_t c = 0; c < n_clips; ++c)
-    if (peak_off[c + 1] < peak_off[c]) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: peak_off decreases at clip %u", who, c);
+  SHZ_TRY(rp_check_csr(ctx, who, "peak_off", peak_off, n_clips, peak_f && peak_t, "peak list"));
   const uint64_t N = peak_off[n_clips];
-  if (N && (!peak_f || !peak_t)) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: NULL peak list", who);
   std::vector<uint64_t> last((size_t)n_clips, 0);
   std::vector<uint8_t> has((size_t)n_clips, 0);
   for (uint32_t c = 0; c < n_clips; ++c)
@@ -1285,9 +1282,9 @@ extern "C" int32_t shz_shared_warps_peaks(shz_ctx* ctx, const uint16_t* peak_f, 
     sw_empty(O, job_hashes, n_recs, n_jobs);
     return SHZ_OK;
   }
-  sw_peaks C(ctx);
-  SHZ_TRY(C.upload(who, peak_f, peak_t, N));
-  return sw_core(ctx, who, (const uint16_t*)C.f, (const uint32_t*)C.t, peak_off, n_clips, rec_clip0, n_recs, fan_value, J, L, P, O, job_hashes,
+  rp_upload C(ctx);
+  SHZ_TRY(C.upload(who, "peaks", peak_f, N * 2, peak_t, N * 4, 64));
+  return sw_core(ctx, who, (const uint16_t*)C.a, (const uint32_t*)C.b, peak_off, n_clips, rec_clip0, n_recs, fan_value, J, L, P, O, job_hashes,
                  nullptr, nullptr, nullptr);
 }
 
@@ -1304,7 +1301,7 @@ extern "C" int32_t shz_shared_warps_batch(shz_ctx* ctx, const int16_t* pcm, cons
   const char* who = "shz_shared_warps_batch";
   if (!ctx) return SHZ_E_INVALID;
   const sh_params P{0, 0, max_run, cell_shift, min_cell_pairs};
-  const sh_out O{cell_off, cell_lag, cell_block, cell_pairs, cell_first, cell_last, rec_hashes, job_skipped_keys, job_pairs,
+  const rp_out O{cell_off, cell_lag, cell_block, cell_pairs, cell_first, cell_last, rec_hashes, job_skipped_keys, job_pairs,
                  job_skipped_rows, cap_cells, count};
   const sw_jobs J{job_a, job_b, job_v, job_lag_lo, job_lag_hi, n_jobs, tempo_q16, pitch_q16, n_warps};
   if (flags & ~SHZ_PCM_DEVICE) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: flags may hold SHZ_PCM_DEVICE", who);
@@ -1326,29 +1323,17 @@ extern "C" int32_t shz_shared_warps_batch(shz_ctx* ctx, const int16_t* pcm, cons
   }
   if (n_recs) SHZ_TRY(sw_check_times(ctx, who, last.data(), has.data(), rec_clip0, J, L));
   // (nothing is refused behind this line without a launch: the first write)
-  rp_times T(ms_extract, ms_pairs, ms_cells);
-  if (ms_warp) *ms_warp = 0.f;
+  rp_times T(ms_extract, ms_warp, ms_pairs, ms_cells);
   if (n_recs == 0) {
     sw_empty(O, job_hashes, 0, 0);   // (without recordings sw_check let no job through)
     return SHZ_OK;
   }
-  SHZ_HIP(ctx, hipSetDevice(ctx->device));
-  const bool timed = T.timed || ms_warp;
-  float spare = 0.f;
-  if (timed) {
-    for (hipEvent_t& e : ctx->rp_ev)
-      if (!e) SHZ_HIP(ctx, hipEventCreate(&e));
-    SHZ_HIP(ctx, hipEventRecord(ctx->rp_ev[0], ctx->stream));
-  }
   std::vector<uint64_t> peak_off((size_t)n_clips + 1, 0);
   const uint16_t* d_pf = nullptr;
   const uint32_t* d_pt = nullptr;
-  SHZ_TRY(sp_peaks_owned(ctx, who, pcm, clip_off, n_clips, all_frames, fs, amp_min, flags & SHZ_PCM_DEVICE, peak_off.data(), &d_pf, &d_pt));
-  if (timed) {
-    SHZ_HIP(ctx, hipEventRecord(ctx->rp_ev[1], ctx->stream));
-    SHZ_HIP(ctx, hipEventSynchronize(ctx->rp_ev[1]));
-    if (T.extract) SHZ_HIP(ctx, hipEventElapsedTime(T.extract, ctx->rp_ev[0], ctx->rp_ev[1]));
-  }
+  SHZ_TRY(rp_timed_extract(ctx, T, [&] {
+    return sp_peaks_owned(ctx, who, pcm, clip_off, n_clips, all_frames, fs, amp_min, flags & SHZ_PCM_DEVICE, peak_off.data(), &d_pf, &d_pt);
+  }));
   for (uint32_t c = n_clips; c > 0; --c) peak_off[c] -= peak_off[0];
   peak_off[0] = 0;
   if (peak_off[n_clips] == 0) {
@@ -1356,8 +1341,7 @@ extern "C" int32_t shz_shared_warps_batch(shz_ctx* ctx, const int16_t* pcm, cons
     return SHZ_OK;
   }
   return sw_core(ctx, who, d_pf, d_pt, peak_off.data(), n_clips, rec_clip0, n_recs, fan_value, J, L, P, O, job_hashes,
-                 timed ? (ms_warp ? ms_warp : &spare) : nullptr, timed ? (T.pairs() ? T.pairs() : &spare) : nullptr,
-                 timed ? (T.cells() ? T.cells() : &spare) : nullptr);
+                 T.at(T.warp), T.at(T.pairs), T.at(T.cells));
 }
 
 // ---- the fold: cells -> repeats, on the host ----------------------------------------------------------------------------------

@@ -128,20 +128,11 @@ def find_repeats_hashes(key32, t1, hash_off, rec_clip0=None, Fs: int = 44100, mi
     return out
 
 
-def occurrences(repeats) -> list:
-    """The airings behind a list of repeats (host only).  Every repeat names two intervals of its recording, [first, last] and
-    [first + lag, last + lag]; two intervals of one recording are the same airing when they overlap by at least half of the
-    shorter one.  Airings joined by a repeat form a group, so an ident aired three times comes back as ONE group of three
-    intervals instead of three pairwise repeats.  repeats: find_repeats' dicts (rec, first, last, lag are read).  Returns a
-    list of dicts, ordered by recording and first airing: recording, intervals (the airings' (first, last) frames, each the
-    hull of the intervals merged into it, ascending) and repeats (indices into the list given)."""
-    items = []
-    for n, p in enumerate(repeats):
-        r, f, l, g = int(p["rec"]), int(p["first"]), int(p["last"]), int(p["lag"])
-        items.append((r, f, l))
-        items.append((r, f + g, l + g))
-    up = list(range(len(items)))                    # union-find over the intervals: the same airing
-
+def _airing_groups(items) -> list:
+    """The grouping behind occurrences() and shared.shared_occurrences().  items[2 n] and items[2 n + 1] are the two intervals
+    (recording, start, end) that link n -- a repeat, a shared stretch -- names.  Two intervals of one recording are the same
+    airing when they overlap by at least half of the shorter one; airings joined by a link form a group.  Returns, in no
+    order, per group (airings, links): the airings' hulls [recording, start, end] and the set of the links in it."""
     def root(u, x):
         while u[x] != x:
             u[x] = u[u[x]]
@@ -152,6 +143,7 @@ def occurrences(repeats) -> list:
         a, b = root(u, a), root(u, b)
         if a != b:
             u[max(a, b)] = min(a, b)
+    up = list(range(len(items)))                    # union-find over the intervals: the same airing
     order = sorted(range(len(items)), key=lambda k: items[k])
     for x, a in enumerate(order):                   # intervals of one recording by start: only those that begin inside a can overlap it
         ra, sa, ea = items[a]
@@ -162,17 +154,31 @@ def occurrences(repeats) -> list:
             over = min(ea, eb) - sb + 1
             if 2 * over >= min(ea - sa + 1, eb - sb + 1):
                 join(up, a, b)
-    grp = [root(up, k) for k in range(len(items))]  # and over the airings: joined by a repeat
-    gup = list(range(len(items)))
-    for n in range(len(repeats)):
-        join(gup, grp[2 * n], grp[2 * n + 1])
+    air = [root(up, k) for k in range(len(items))]
+    gup = list(range(len(items)))                   # and over the airings: joined by a link
+    for n in range(len(items) // 2):
+        join(gup, air[2 * n], air[2 * n + 1])
     groups = {}
     for k, (r, s, e) in enumerate(items):
-        g = groups.setdefault((r, root(gup, grp[k])), {"airs": {}, "repeats": set()})
-        air = g["airs"].setdefault(grp[k], [s, e])
-        air[0], air[1] = min(air[0], s), max(air[1], e)
-        g["repeats"].add(k // 2)
-    out = [{"recording": r, "intervals": sorted((s, e) for s, e in g["airs"].values()), "repeats": sorted(g["repeats"])}
-           for (r, _), g in groups.items()]
+        airs, links = groups.setdefault(root(gup, air[k]), ({}, set()))
+        hull = airs.setdefault(air[k], [r, s, e])
+        hull[1], hull[2] = min(hull[1], s), max(hull[2], e)
+        links.add(k // 2)
+    return [(list(airs.values()), links) for airs, links in groups.values()]
+
+
+def occurrences(repeats) -> list:
+    """The airings behind a list of repeats (host only).  Every repeat names two intervals of its recording, [first, last] and
+    [first + lag, last + lag]; two intervals of one recording are the same airing when they overlap by at least half of the
+    shorter one.  Airings joined by a repeat form a group, so an ident aired three times comes back as ONE group of three
+    intervals instead of three pairwise repeats.  repeats: find_repeats' dicts (rec, first, last, lag are read).  Returns a
+    list of dicts, ordered by recording and first airing: recording, intervals (the airings' (first, last) frames, each the
+    hull of the intervals merged into it, ascending) and repeats (indices into the list given)."""
+    items = []
+    for p in repeats:
+        r, f, l, g = int(p["rec"]), int(p["first"]), int(p["last"]), int(p["lag"])
+        items += [(r, f, l), (r, f + g, l + g)]
+    out = [{"recording": airs[0][0], "intervals": sorted((s, e) for _, s, e in airs), "repeats": sorted(links)}
+           for airs, links in _airing_groups(items)]               # (a group lies in one recording: nothing here links two)
     out.sort(key=lambda g: (g["recording"], g["intervals"][0]))
     return out

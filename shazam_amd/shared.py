@@ -19,7 +19,7 @@ from __future__ import annotations
 import numpy as np
 
 from ._ffi import HOP, SHARED_LAG_BIAS
-from .repeats import FIRST_ROOM, MAX_LAG, _fold
+from .repeats import FIRST_ROOM, MAX_LAG, _airing_groups, _fold
 
 MAX_JOBS = 4096          # jobs of one library call (shz_shared_*): more are split
 MAX_RECS = 4096          # recordings of one library call: a call carries only those its jobs name
@@ -438,52 +438,18 @@ def shared_occurrences(shared, repeats=()) -> list:
     the intervals merged into it), shared and repeats (indices into the lists given).
     A stretch found at a ladder (find_shared(speeds= / tempos= / pitches= / warps=)) names its intervals itself: (rec_a, a_first,
     a_last), a's OWN frames, and (rec_b, b_first, b_last) -- its first / last are warped frames, which are no place in a."""
-    items, link = [], []                            # the intervals | per stretch or repeat: ("shared" / "repeats", index)
-    for n, p in enumerate(shared):
+    items = []                                      # two intervals per stretch, then two per repeat
+    for p in shared:
         f, l, g = int(p["first"]), int(p["last"]), int(p["lag"])
         if "a_first" in p:
             items += [(int(p["rec_a"]), int(p["a_first"]), int(p["a_last"])), (int(p["rec_b"]), int(p["b_first"]), int(p["b_last"]))]
         else:
             items += [(int(p["rec_a"]), f, l), (int(p["rec_b"]), f + g, l + g)]
-        link.append(("shared", n))
-    for n, p in enumerate(repeats):
+    ns = len(items) // 2
+    for p in repeats:
         r, f, l, g = int(p["rec"]), int(p["first"]), int(p["last"]), int(p["lag"])
         items += [(r, f, l), (r, f + g, l + g)]
-        link.append(("repeats", n))
-    up = list(range(len(items)))                    # union-find over the intervals: the same airing
-
-    def root(u, x):
-        while u[x] != x:
-            u[x] = u[u[x]]
-            x = u[x]
-        return x
-
-    def join(u, a, b):
-        a, b = root(u, a), root(u, b)
-        if a != b:
-            u[max(a, b)] = min(a, b)
-    order = sorted(range(len(items)), key=lambda k: items[k])
-    for x, a in enumerate(order):                   # intervals of one recording by start: only those that begin inside a can overlap it
-        ra, sa, ea = items[a]
-        for b in order[x + 1:]:
-            rb, sb, eb = items[b]
-            if rb != ra or sb > ea:
-                break
-            over = min(ea, eb) - sb + 1
-            if 2 * over >= min(ea - sa + 1, eb - sb + 1):
-                join(up, a, b)
-    air = [root(up, k) for k in range(len(items))]
-    gup = list(range(len(items)))                   # and over the airings: joined by a stretch or a repeat
-    for n in range(len(link)):
-        join(gup, air[2 * n], air[2 * n + 1])
-    groups = {}
-    for k, (r, s, e) in enumerate(items):
-        g = groups.setdefault(root(gup, air[k]), {"airs": {}, "shared": set(), "repeats": set()})
-        hull = g["airs"].setdefault(air[k], [r, s, e])
-        hull[1], hull[2] = min(hull[1], s), max(hull[2], e)
-        kind, n = link[k // 2]
-        g[kind].add(n)
-    out = [{"airings": sorted(tuple(h) for h in g["airs"].values()), "shared": sorted(g["shared"]), "repeats": sorted(g["repeats"])}
-           for g in groups.values()]
+    out = [{"airings": sorted(tuple(h) for h in airs), "shared": sorted(n for n in links if n < ns),
+            "repeats": sorted(n - ns for n in links if n >= ns)} for airs, links in _airing_groups(items)]
     out.sort(key=lambda g: g["airings"][0])
     return out
