@@ -286,6 +286,60 @@ extern "C" int32_t shz_table_song_hashes(shz_table* t, const uint32_t* sids, uin
   return SHZ_OK;
 }
 
+namespace {
+
+// The rows of the listed songs as columns that belong to the call (`own`; the match that follows uses the workspace):
+// row_off[n_sids + 1] on the host, *d_key / *d_off of G->total rows (NULL where no listed song has a row) and, where max_off
+// is given, the largest offset among them.  The stream is idle on return.
+int32_t sg_columns(shz_table* t, const char* who, const uint32_t* sids, uint32_t n_sids, uint64_t* row_off, song_gather* G,
+                   sg_bufs* own, uint32_t** d_key, uint32_t** d_off, uint32_t* max_off) {
+  shz_ctx* ctx = t->ctx;
+  *d_key = *d_off = nullptr;
+  if (max_off) *max_off = 0;
+  SHZ_TRY(sg_prepare(t, who, sids, n_sids, row_off, G));
+  if (G->total >= (1ull << 32))
+    SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "%s: %llu rows in one call (limit 2^32 - 1); list fewer songs", who, (unsigned long long)G->total);
+  if (G->total == 0) return SHZ_OK;
+  *d_key = (uint32_t*)own->get(G->total * 4);
+  *d_off = (uint32_t*)own->get(G->total * 4);
+  uint32_t* d_max = max_off ? (uint32_t*)own->get(4) : nullptr;
+  if (!*d_key || !*d_off || (max_off && !d_max)) SHZ_FAIL(ctx, SHZ_E_NOMEM, "%s: hipMalloc(2 x %llu) failed", who, (unsigned long long)(G->total * 4));
+  if (d_max) SHZ_HIP(ctx, hipMemsetAsync(d_max, 0, 4, ctx->stream));
+  SHZ_TRY(sg_fill(*G, who, *d_key, *d_off, d_max));
+  if (d_max) {
+    SHZ_HIP(ctx, shz_memcpy(ctx, max_off, d_max, 4, hipMemcpyDeviceToHost));
+    SHZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  return SHZ_OK;
+}
+
+// The song itself leaves its own list (see shz.h).  r_*: the top w = topn + 1 of n queries, query i being a form of the song
+// sids[i / per]; out_*: the first topn of every OTHER song, the rest of a row zeroed, and their number
+void sg_drop_self(const uint32_t* sids, uint32_t per, uint64_t n, uint32_t topn, const uint32_t* r_sid, const int32_t* r_delta,
+                  const uint32_t* r_aligned, const uint32_t* r_dedup, const uint32_t* r_nres, uint32_t* out_sid, int32_t* out_delta,
+                  uint32_t* out_aligned, uint32_t* out_dedup, uint32_t* out_nres) {
+  const uint32_t w = topn + 1;
+  for (uint64_t q = 0; q < n; ++q) {
+    uint32_t k = 0;
+    for (uint32_t i = 0; i < std::min(r_nres[q], w) && k < topn; ++i) {
+      const uint64_t src = q * w + i, dst = q * topn + k;
+      if (r_sid[src] == sids[q / per]) continue;
+      out_sid[dst] = r_sid[src];
+      out_delta[dst] = r_delta[src];
+      out_aligned[dst] = r_aligned[src];
+      out_dedup[dst] = r_dedup[src];
+      ++k;
+    }
+    out_nres[q] = k;
+    for (; k < topn; ++k) {
+      const uint64_t dst = q * topn + k;
+      out_sid[dst] = 0; out_delta[dst] = 0; out_aligned[dst] = 0; out_dedup[dst] = 0;
+    }
+  }
+}
+
+}  // namespace
+
 extern "C" int32_t shz_match_songs(shz_ctx* ctx, shz_table* t, const uint32_t* sids, uint32_t n_sids, uint32_t topn, uint32_t flags,
                                    uint64_t* out_rows, uint32_t* out_sid, int32_t* out_delta, uint32_t* out_aligned,
                                    uint32_t* out_dedup, uint32_t* out_nres, uint32_t* out_nhash, uint64_t* out_npairs) {
@@ -297,21 +351,10 @@ extern "C" int32_t shz_match_songs(shz_ctx* ctx, shz_table* t, const uint32_t* s
   if (!out_sid || !out_delta || !out_aligned || !out_dedup || !out_nres) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_match_songs: NULL buffer");
   SHZ_TRY(shz_match_ready(ctx, t, topn + 1));
   song_gather G;
-  std::vector<uint64_t> row_off((uint64_t)n_sids + 1);
-  SHZ_TRY(sg_prepare(t, "shz_match_songs", sids, n_sids, row_off.data(), &G));
-  if (G.total >= (1ull << 32))
-    SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "shz_match_songs: %llu rows in one call (limit 2^32 - 1); list fewer songs", (unsigned long long)G.total);
-  // the query columns belong to this call: the match uses the workspace
   sg_bufs own;
-  uint32_t *d_key = (uint32_t*)own.get(G.total * 4), *d_off = (uint32_t*)own.get(G.total * 4), *d_max = (uint32_t*)own.get(4);
-  if (!d_key || !d_off || !d_max) SHZ_FAIL(ctx, SHZ_E_NOMEM, "shz_match_songs: hipMalloc(2 x %llu) failed", (unsigned long long)(G.total * 4));
-  uint32_t max_off = 0;
-  if (G.total) {
-    SHZ_HIP(ctx, hipMemsetAsync(d_max, 0, 4, ctx->stream));
-    SHZ_TRY(sg_fill(G, "shz_match_songs", d_key, d_off, d_max));
-    SHZ_HIP(ctx, shz_memcpy(ctx, &max_off, d_max, 4, hipMemcpyDeviceToHost));
-    SHZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  }
+  std::vector<uint64_t> row_off((uint64_t)n_sids + 1);
+  uint32_t *d_key, *d_off, max_off;
+  SHZ_TRY(sg_columns(t, "shz_match_songs", sids, n_sids, row_off.data(), &G, &own, &d_key, &d_off, &max_off));
   if (max_off >= (1u << 20))
     SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "shz_match_songs: a listed song holds offset %u; its offsets are query offsets here and must be < 2^20", max_off);
   const uint32_t w = topn + 1;
@@ -327,23 +370,9 @@ extern "C" int32_t shz_match_songs(shz_ctx* ctx, shz_table* t, const uint32_t* s
     shz_floor_zero_rows(ctx, n_sids);   // (the vote floor's rows line up with the result arrays)
   (void)hipStreamSynchronize(ctx->stream);   // (a refused call may have queued work that reads the columns)
   if (rc != SHZ_OK) return rc;
-  // the song itself leaves its own list: what stays are the first topn of every other song (see shz.h)
+  sg_drop_self(sids, 1, n_sids, topn, r_sid.data(), r_delta.data(), r_aligned.data(), r_dedup.data(), r_nres.data(), out_sid,
+               out_delta, out_aligned, out_dedup, out_nres);
   for (uint32_t q = 0; q < n_sids; ++q) {
-    uint32_t k = 0;
-    for (uint32_t i = 0; i < std::min(r_nres[q], w) && k < topn; ++i) {
-      const uint64_t src = (uint64_t)q * w + i, dst = (uint64_t)q * topn + k;
-      if (r_sid[src] == sids[q]) continue;
-      out_sid[dst] = r_sid[src];
-      out_delta[dst] = r_delta[src];
-      out_aligned[dst] = r_aligned[src];
-      out_dedup[dst] = r_dedup[src];
-      ++k;
-    }
-    out_nres[q] = k;
-    for (; k < topn; ++k) {
-      const uint64_t dst = (uint64_t)q * topn + k;
-      out_sid[dst] = 0; out_delta[dst] = 0; out_aligned[dst] = 0; out_dedup[dst] = 0;
-    }
     if (out_rows) out_rows[q] = row_off[q + 1] - row_off[q];
     if (out_nhash) out_nhash[q] = r_nhash[q];
     if (out_npairs) out_npairs[q] = r_npairs[q];
@@ -351,20 +380,27 @@ extern "C" int32_t shz_match_songs(shz_ctx* ctx, shz_table* t, const uint32_t* s
   return SHZ_OK;
 }
 
-// ---- the row warp: sped-up and pitch-shifted copies inside the table -----------------------------------
+// ---- the row warp: sped-up and pitch-shifted copies inside the table -----------------------------
 // The table holds no peaks, but a row IS two peaks: key32 = f1 << 20 | f2 << 8 | dt at offset t1 is (f1, t1) and (f2, t1 + dt).
 // Both are moved by the integer maps of shz_warp_pair_hash_tf (sp_warp_f, and the time map in 64 bits) and the key is formed
 // again; a row leaves where a frequency leaves the spectrogram or dt' passes 200.  Elementwise: no sort, no fan_value.
 //
-// Work is laid out over (song q, warp v, row r) items, song-major, then warp-major, then the song's rows (sp_decode's
-// layout): (q, v) is one contiguous query of the match, and a wave stays at one warp over consecutive rows.  The compaction
-// is sg_count_kernel / sg_write_kernel's: blocks of RW_ITEMS items, one wave a block; pass 1 ballots, writes one count per
-// block and adds the kept items to their (q, v) count (one add a wave where the wave lies inside one (q, v)); the block
-// counts are scanned; pass 2 repeats the map and writes at block base + rank inside the ballot.  No atomic decides a place.
+// Work is laid out over items, and a LAYOUT says which row of which song an item is, which segment of the output it counts
+// into and which factor pair warps it.  There are two:
+//   product (3.7h)  every listed song at every warp: (song q, warp v, row r) items, song-major, then warp-major, then the
+//                   song's rows (sp_decode's layout); segment q K + v is one contiguous query of the match;
+//   jobs (3.7o)     a list of (song, t16, f16) in which a song may stand several times: (job j, row r) items, job-major, then
+//                   the rows of the job's song; segment j is one contiguous query of the extent pass.
+// In both a wave stays at one warp over consecutive rows wherever it lies inside one segment.  The compaction is
+// sg_count_kernel / sg_write_kernel's and exists once, as templates on the layout: blocks of RW_ITEMS items, one wave a
+// block; pass 1 ballots, writes one count per block and adds the kept items to their segment's count (one add a wave where
+// the wave lies inside one segment); the block counts are scanned; pass 2 repeats the map and writes at block base + rank
+// inside the ballot.  No atomic decides a place.
 #define RW_ITEMS 512u   // items of a block
 #define RW_LOADS 8      // RW_ITEMS / 64
 #define RW_WAVES 4      // blocks (waves) of a workgroup
 #define RW_SMALL_WARPS 2u   // warps of a slice (of one song) under SHZ_DEBUG_CATALOG_SMALL_SLICES
+#define RW_SMALL_JOBS 2u    // jobs of a slice under SHZ_DEBUG_CATALOG_SMALL_SLICES
 
 // THE map: row (key32, off) under the warp (t16, f16) -> kept?, and (*okey, *ooff) where kept (off t16 < 2^48 is the
 // caller's promise: t1' is stored in 32 bits).  The kernels and shz_warp_row_host both call it
@@ -378,74 +414,106 @@ __host__ __device__ __forceinline__ bool rw_warp_row(uint32_t key32, uint32_t of
   return g1 <= SP_F_MAX && g2 <= SP_F_MAX && d <= SHZ_MAX_DT;
 }
 
-struct rw_view {                   // what the kernels of one slice read (device pointers)
-  const uint32_t *key, *off;       // the rows of all songs of the call, song after song
-  const uint64_t* roff;            // CSR of the songs over them, from 0
-  const uint32_t *tempo, *pitch;   // the call's warps
-  uint32_t q0, nq, v0, K;          // the slice: songs [q0, q0 + nq) at the warps [v0, v0 + K)
-  uint64_t n_items;                // rows of those songs x K
-};
-struct rw_cursor {
-  uint32_t q, v, r, n;             // song and warp (of the slice), row of the song, rows of the song
+struct rw_cursor {                 // where an item lies
+  uint32_t seg, fac;               // the segment it counts into, the index of its factor pair
+  uint32_t r, n;                   // row of the song, rows of the song
   uint64_t row0;                   // the song's first row
 };
 
-// item w < n_items -> its song (the last q whose first item is <= w: empty songs share a start), warp and row
-__device__ __forceinline__ void rw_seek(const rw_view& V, uint64_t w, rw_cursor* c) {
-  const uint64_t r00 = V.roff[V.q0];
-  uint32_t lo = 0, hi = V.nq;
-  while (lo + 1 < hi) {
-    const uint32_t mid = (lo + hi) >> 1;
-    if ((V.roff[V.q0 + mid] - r00) * V.K <= w) lo = mid; else hi = mid;
+struct rw_product {                // the slice: songs [q0, q0 + nq) at the warps [v0, v0 + K)
+  const uint64_t* roff;            // CSR of the call's songs over the rows, from 0
+  uint32_t q0, nq, v0, K;
+  // item w -> its song (the last q whose first item is <= w: empty songs share a start), warp and row
+  __device__ __forceinline__ void seek(uint64_t w, rw_cursor* c) const {
+    const uint64_t r00 = roff[q0];
+    uint32_t lo = 0, hi = nq;
+    while (lo + 1 < hi) {
+      const uint32_t mid = (lo + hi) >> 1;
+      if ((roff[q0 + mid] - r00) * K <= w) lo = mid; else hi = mid;
+    }
+    const uint64_t r0 = roff[q0 + lo];
+    const uint32_t n = (uint32_t)(roff[q0 + lo + 1] - r0);   // (> 0: w lies inside the song's items)
+    const uint32_t rem = (uint32_t)(w - (r0 - r00) * K), v = rem / max(n, 1u), vc = min(v, K - 1);
+    c->seg = lo * K + vc;
+    c->fac = v0 + vc;
+    c->r = min(rem - v * n, max(n, 1u) - 1);   // (the clamps hold for every consistent view; they keep any read inside the columns)
+    c->n = n;
+    c->row0 = r0;
   }
-  const uint64_t r0 = V.roff[V.q0 + lo];
-  const uint32_t n = (uint32_t)(V.roff[V.q0 + lo + 1] - r0);   // (> 0: w lies inside the song's items)
-  const uint32_t rem = (uint32_t)(w - (r0 - r00) * V.K), v = rem / max(n, 1u);
-  c->q = lo;
-  c->v = min(v, V.K - 1);
-  c->r = min(rem - v * n, max(n, 1u) - 1);   // (the clamps hold for every consistent view; they keep any read inside the columns)
-  c->n = n;
-  c->row0 = r0;
-}
+};
 
-// the RW_LOADS items of this lane in block blk: rows loaded, (q, v) kept as segment and warp; dead lanes: seg = ~0
-__device__ __forceinline__ void rw_load(const rw_view& V, uint64_t w0, uint32_t lane, uint32_t* k, uint32_t* o, uint32_t* seg,
-                                        uint32_t* vv) {
+struct rw_jobs {                   // the slice: nj jobs, each one song at one warp
+  const uint64_t* roff;            // CSR of the call's distinct songs over the rows, from 0
+  const uint32_t* song;            // the job's song (index into roff)
+  const uint64_t* base;            // nj + 1: first item of every job (item w of the slice is base[0] + w)
+  uint32_t nj;
+  // item w -> its job (the last j whose first item is <= w: empty jobs share a start) and row
+  __device__ __forceinline__ void seek(uint64_t w, rw_cursor* c) const {
+    const uint64_t b0 = base[0];
+    uint32_t lo = 0, hi = nj;
+    while (lo + 1 < hi) {
+      const uint32_t mid = (lo + hi) >> 1;
+      if (base[mid] - b0 <= w) lo = mid; else hi = mid;
+    }
+    const uint32_t s = song[lo];
+    const uint64_t r0 = roff[s];
+    const uint32_t n = (uint32_t)(roff[s + 1] - r0);   // (> 0: w lies inside the job's items)
+    const uint64_t rem = w - (base[lo] - b0);
+    c->seg = c->fac = lo;
+    c->r = (uint32_t)min(rem, (uint64_t)(max(n, 1u) - 1));   // (the clamp holds for every consistent view; it keeps any read inside the columns)
+    c->n = n;
+    c->row0 = r0;
+  }
+};
+
+template <class L>
+struct rw_view {                   // what the kernels of one slice read (device pointers)
+  const uint32_t *key, *off;       // the rows of all songs of the call, song after song
+  const uint32_t *t16, *f16;       // the factor pairs a cursor's fac indexes: the call's warps, or the slice's jobs
+  uint64_t n_items;
+  L lay;
+};
+
+// the RW_LOADS items of this lane in the block at w0: rows loaded, segment and factor index kept; dead lanes: seg = ~0, fac = 0
+template <class L>
+__device__ __forceinline__ void rw_load(const rw_view<L>& V, uint64_t w0, uint32_t lane, uint32_t* k, uint32_t* o, uint32_t* seg,
+                                        uint32_t* fac) {
   rw_cursor c{0, 0, 0, 0, 0};
 #pragma unroll
   for (int j = 0; j < RW_LOADS; ++j) {
     const uint64_t w = w0 + (uint64_t)j * 64 + lane;
     seg[j] = 0xFFFFFFFFu;
-    k[j] = o[j] = vv[j] = 0;
+    k[j] = o[j] = fac[j] = 0;
     if (w >= V.n_items) continue;
-    if (j == 0 || c.r + 64 >= c.n) rw_seek(V, w, &c);   // (64 items on: still inside this song's rows at this warp?)
+    if (j == 0 || c.r + 64 >= c.n) V.lay.seek(w, &c);   // (64 items on: still inside this segment's rows?)
     else c.r += 64;
     if (c.n == 0) continue;
     k[j] = V.key[c.row0 + c.r];
     o[j] = V.off[c.row0 + c.r];
-    seg[j] = c.q * V.K + c.v;
-    vv[j] = V.v0 + c.v;
+    seg[j] = c.seg;
+    fac[j] = c.fac;
   }
 }
 
-// pass 1: kept items of every block, kept items of every (song, warp)
-__global__ __launch_bounds__(64 * RW_WAVES) void rw_count_kernel(rw_view V, uint32_t* __restrict__ blk_cnt,
+// pass 1: kept items of every block, kept items of every segment
+template <class L>
+__global__ __launch_bounds__(64 * RW_WAVES) void rw_count_kernel(rw_view<L> V, uint32_t* __restrict__ blk_cnt,
                                                                   uint32_t* __restrict__ seg_cnt) {
   const uint32_t lane = threadIdx.x & 63;
   const uint64_t blk = (uint64_t)blockIdx.x * RW_WAVES + (threadIdx.x >> 6);
   const uint64_t w0 = blk * RW_ITEMS;
   if (w0 >= V.n_items) return;   // uniform in the wave
-  uint32_t k[RW_LOADS], o[RW_LOADS], seg[RW_LOADS], vv[RW_LOADS];
-  rw_load(V, w0, lane, k, o, seg, vv);
+  uint32_t k[RW_LOADS], o[RW_LOADS], seg[RW_LOADS], fac[RW_LOADS];
+  rw_load(V, w0, lane, k, o, seg, fac);
   uint32_t c = 0;
 #pragma unroll
   for (int j = 0; j < RW_LOADS; ++j) {
-    const bool live = seg[j] != 0xFFFFFFFFu;
+    const bool live = seg[j] != 0xFFFFFFFFu;   // (a dead lane maps nothing; its factor index 0 lies inside the arrays)
     uint32_t a, b;
-    const bool keep = live && rw_warp_row(k[j], o[j], V.tempo[vv[j]], V.pitch[vv[j]], &a, &b);
+    const bool keep = live && rw_warp_row(k[j], o[j], V.t16[fac[j]], V.f16[fac[j]], &a, &b);
     const uint64_t m = __ballot(keep);
     const uint32_t first = (uint32_t)__shfl((int)seg[j], 0, 64);   // (live lanes are a prefix of the wave)
-    if (__ballot(live && seg[j] != first) == 0) {   // the wave inside one (song, warp): one add
+    if (__ballot(live && seg[j] != first) == 0) {   // the wave inside one segment: one add
       if (lane == 0 && m) atomicAdd(seg_cnt + first, (uint32_t)__popcll(m));
     } else if (keep) {
       atomicAdd(seg_cnt + seg[j], 1u);
@@ -456,20 +524,21 @@ __global__ __launch_bounds__(64 * RW_WAVES) void rw_count_kernel(rw_view V, uint
 }
 
 // pass 2: every kept item, in item order, at the place the scan of the block counts gives (no store at or beyond cap)
-__global__ __launch_bounds__(64 * RW_WAVES) void rw_write_kernel(rw_view V, const uint32_t* __restrict__ blk_pos,
+template <class L>
+__global__ __launch_bounds__(64 * RW_WAVES) void rw_write_kernel(rw_view<L> V, const uint32_t* __restrict__ blk_pos,
                                                                   uint32_t* __restrict__ out_key, uint32_t* __restrict__ out_off,
                                                                   uint64_t cap) {
   const uint32_t lane = threadIdx.x & 63;
   const uint64_t blk = (uint64_t)blockIdx.x * RW_WAVES + (threadIdx.x >> 6);
   const uint64_t w0 = blk * RW_ITEMS;
   if (w0 >= V.n_items) return;   // uniform in the wave
-  uint32_t k[RW_LOADS], o[RW_LOADS], seg[RW_LOADS], vv[RW_LOADS];
-  rw_load(V, w0, lane, k, o, seg, vv);
+  uint32_t k[RW_LOADS], o[RW_LOADS], seg[RW_LOADS], fac[RW_LOADS];
+  rw_load(V, w0, lane, k, o, seg, fac);
   uint64_t base = blk_pos[blk];
 #pragma unroll
   for (int j = 0; j < RW_LOADS; ++j) {
     uint32_t a, b;
-    const bool keep = seg[j] != 0xFFFFFFFFu && rw_warp_row(k[j], o[j], V.tempo[vv[j]], V.pitch[vv[j]], &a, &b);
+    const bool keep = seg[j] != 0xFFFFFFFFu && rw_warp_row(k[j], o[j], V.t16[fac[j]], V.f16[fac[j]], &a, &b);
     const uint64_t m = __ballot(keep);
     if (keep) {
       const uint64_t pos = base + (uint64_t)__popcll(m & ((1ull << lane) - 1ull));
@@ -479,57 +548,83 @@ __global__ __launch_bounds__(64 * RW_WAVES) void rw_write_kernel(rw_view V, cons
   }
 }
 
+// the largest offset of every gathered song (song_max zeroed; a song without rows keeps 0): one atomicMax a wave where the
+// wave lies inside one song, whose result no order changes
+__global__ __launch_bounds__(256) void rw_song_max_kernel(const uint32_t* __restrict__ off, const uint64_t* __restrict__ roff,
+                                                           uint32_t n_songs, uint64_t total, uint32_t* __restrict__ song_max) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  const bool live = i < total;
+  uint32_t lo = 0, hi = n_songs;   // the last song whose first row is <= i (empty songs share a start)
+  while (live && lo + 1 < hi) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (roff[mid] <= i) lo = mid; else hi = mid;
+  }
+  uint32_t o = live ? off[i] : 0u;
+  const uint32_t first = (uint32_t)__shfl((int)lo, 0, 64);   // (live lanes are a prefix of the wave)
+  if (__ballot(live && lo != first) == 0) {
+    for (int d = 32; d >= 1; d >>= 1) o = max(o, (uint32_t)__shfl_xor((int)o, d, 64));
+    if ((threadIdx.x & 63) == 0 && o) atomicMax(song_max + first, o);
+  } else if (live && o) {
+    atomicMax(song_max + lo, o);
+  }
+}
+
 namespace {
 
-struct rw_tabs {
-  const uint64_t* d_roff = nullptr;
-  const uint32_t *d_tempo = nullptr, *d_pitch = nullptr;
+struct rw_tabs {                   // the call's tables on the device (one block); base and song in the job form only
+  const uint64_t *d_roff = nullptr, *d_base = nullptr;
+  const uint32_t *d_t16 = nullptr, *d_f16 = nullptr, *d_song = nullptr;
 };
-struct rw_pass {
-  rw_view V;
-  uint64_t n_blk = 0;
-  uint32_t* d_blk = nullptr;
+template <class L>
+struct rw_slice {                  // one slice of a call: its view and the number of its segments
+  rw_view<L> V;
+  uint64_t n_seg;
 };
 
 static inline uint64_t rw_blocks(uint64_t n) { return (n + RW_ITEMS - 1) / RW_ITEMS; }
+static inline dim3 rw_grid(uint64_t n_items) { return dim3((unsigned)((rw_blocks(n_items) + RW_WAVES - 1) / RW_WAVES)); }
 
-// CSR of the songs (from 0) | tempo | pitch on the device: one block of the call
-int32_t rw_upload(shz_ctx* ctx, const uint64_t* row_off, uint32_t n_songs, const uint32_t* tempo_q16, const uint32_t* pitch_q16,
-                  uint32_t K, rw_tabs* T) {
-  const uint64_t ro_bytes = ((uint64_t)n_songs + 1) * 8, tab_bytes = (uint64_t)K * 4, bytes = ro_bytes + 2 * tab_bytes;
+// roff[n_songs + 1] (from 0) | base[n_fac + 1] | t16[n_fac] | f16[n_fac] | song[n_fac], uploaded once a call; base and song
+// may both be NULL (the product form: the factors are the call's warps)
+int32_t rw_upload(shz_ctx* ctx, const uint64_t* row_off, uint32_t n_songs, const uint32_t* t16, const uint32_t* f16, uint32_t n_fac,
+                  const uint64_t* base, const uint32_t* song, rw_tabs* T) {
+  const uint64_t ro_bytes = ((uint64_t)n_songs + 1) * 8, ba_bytes = base ? ((uint64_t)n_fac + 1) * 8 : 0, col = (uint64_t)n_fac * 4;
+  const uint64_t bytes = ro_bytes + ba_bytes + (song ? 3 : 2) * col;
   std::vector<char> h(bytes);
   uint64_t* hr = (uint64_t*)h.data();
   for (uint32_t q = 0; q <= n_songs; ++q) hr[q] = row_off[q] - row_off[0];
-  memcpy(h.data() + ro_bytes, tempo_q16, tab_bytes);
-  memcpy(h.data() + ro_bytes + tab_bytes, pitch_q16, tab_bytes);
+  if (base) memcpy(h.data() + ro_bytes, base, ba_bytes);
+  memcpy(h.data() + ro_bytes + ba_bytes, t16, col);
+  memcpy(h.data() + ro_bytes + ba_bytes + col, f16, col);
+  if (song) memcpy(h.data() + ro_bytes + ba_bytes + 2 * col, song, col);
   void* d;
   SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_RW_TAB, bytes, &d));
   SHZ_HIP(ctx, shz_memcpy(ctx, d, h.data(), bytes, hipMemcpyHostToDevice));
   T->d_roff = (const uint64_t*)d;
-  T->d_tempo = (const uint32_t*)((char*)d + ro_bytes);
-  T->d_pitch = T->d_tempo + K;
+  T->d_base = (const uint64_t*)((char*)d + ro_bytes);
+  T->d_t16 = (const uint32_t*)((char*)d + ro_bytes + ba_bytes);
+  T->d_f16 = T->d_t16 + n_fac;
+  T->d_song = T->d_f16 + n_fac;
   return SHZ_OK;
 }
 
-// pass 1 and the scan of one slice -- songs [q0, q0 + nq) at the warps [v0, v0 + kv) of rows that lie in d_key / d_off:
-// seg_off[nq kv + 1] (host) is the exact CSR of the (song, warp) segments, relative to the slice.  The stream is idle on
-// return.  A slice without rows launches nothing
-int32_t rw_count(shz_ctx* ctx, const rw_tabs& T, const uint32_t* d_key, const uint32_t* d_off, const uint64_t* row_off, uint32_t q0,
-                 uint32_t nq, uint32_t v0, uint32_t kv, rw_pass* P, uint64_t* seg_off) {
-  const uint64_t n_seg = (uint64_t)nq * kv, n_items = (row_off[q0 + nq] - row_off[q0]) * kv;
+// pass 1 and the scan of one slice: seg_off[n_seg + 1] (host) is the exact CSR of the segments' kept rows, relative to the
+// slice, and *d_blk the scanned block counts that pass 2 reads.  The stream is idle on return.  A slice without items
+// launches nothing
+template <class L>
+int32_t rw_count(shz_ctx* ctx, const rw_view<L>& V, uint64_t n_seg, uint32_t** d_blk, uint64_t* seg_off) {
   for (uint64_t e = 0; e <= n_seg; ++e) seg_off[e] = 0;
-  P->V = rw_view{d_key, d_off, T.d_roff, T.d_tempo, T.d_pitch, q0, nq, v0, kv, n_items};
-  P->n_blk = rw_blocks(n_items);
-  if (n_items == 0) return SHZ_OK;
-  void *d_blk, *d_cnt;
-  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_RW_BLK, P->n_blk * 4, &d_blk));
+  *d_blk = nullptr;
+  if (V.n_items == 0) return SHZ_OK;
+  const uint64_t n_blk = rw_blocks(V.n_items);
+  void *blk, *d_cnt;
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_RW_BLK, n_blk * 4, &blk));
   SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_RW_CNT, n_seg * 4, &d_cnt));
-  P->d_blk = (uint32_t*)d_blk;
+  *d_blk = (uint32_t*)blk;
   SHZ_HIP(ctx, hipMemsetAsync(d_cnt, 0, n_seg * 4, ctx->stream));
-  hipLaunchKernelGGL(rw_count_kernel, dim3((unsigned)((P->n_blk + RW_WAVES - 1) / RW_WAVES)), dim3(64 * RW_WAVES), 0, ctx->stream,
-                     P->V, P->d_blk, (uint32_t*)d_cnt);
+  hipLaunchKernelGGL(rw_count_kernel<L>, rw_grid(V.n_items), dim3(64 * RW_WAVES), 0, ctx->stream, V, *d_blk, (uint32_t*)d_cnt);
   SHZ_HIP(ctx, hipGetLastError());
-  SHZ_TRY(shz_scan_u32(ctx, P->d_blk, P->d_blk, P->n_blk, nullptr));
+  SHZ_TRY(shz_scan_u32(ctx, *d_blk, *d_blk, n_blk, nullptr));
   std::vector<uint32_t> cnt(n_seg);
   SHZ_HIP(ctx, shz_memcpy(ctx, cnt.data(), d_cnt, n_seg * 4, hipMemcpyDeviceToHost));
   SHZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -537,12 +632,60 @@ int32_t rw_count(shz_ctx* ctx, const rw_tabs& T, const uint32_t* d_key, const ui
   return SHZ_OK;
 }
 
-int32_t rw_write(shz_ctx* ctx, const rw_pass& P, uint32_t* d_okey, uint32_t* d_ooff, uint64_t cap) {
-  if (P.V.n_items == 0) return SHZ_OK;
-  hipLaunchKernelGGL(rw_write_kernel, dim3((unsigned)((P.n_blk + RW_WAVES - 1) / RW_WAVES)), dim3(64 * RW_WAVES), 0, ctx->stream,
-                     P.V, (const uint32_t*)P.d_blk, d_okey, d_ooff, cap);
+// pass 2 of the slice rw_count counted (d_blk: its block counts, scanned), queued on the stream
+template <class L>
+int32_t rw_write(shz_ctx* ctx, const rw_view<L>& V, const uint32_t* d_blk, uint32_t* d_okey, uint32_t* d_ooff, uint64_t cap) {
+  if (V.n_items == 0) return SHZ_OK;
+  hipLaunchKernelGGL(rw_write_kernel<L>, rw_grid(V.n_items), dim3(64 * RW_WAVES), 0, ctx->stream, V, d_blk, d_okey, d_ooff, cap);
   SHZ_HIP(ctx, hipGetLastError());
   return SHZ_OK;
+}
+
+// a timed call begins: the ctx's events exist (created on first use) and slot 0 holds the start
+int32_t rw_clock_start(shz_ctx* ctx) {
+  SHZ_HIP(ctx, hipSetDevice(ctx->device));
+  for (hipEvent_t& e : ctx->sp_ev)
+    if (!e) SHZ_HIP(ctx, hipEventCreate(&e));
+  SHZ_HIP(ctx, hipEventRecord(ctx->sp_ev[0], ctx->stream));
+  return SHZ_OK;
+}
+
+// Warp and stage, slice by slice.  Per slice: both passes into d_wkey / d_woff (room for buf_items rows), then
+// stage(i, seg_off) on the warped columns and the CSR of the slice's segments over them (seg_off[n_seg] rows; the stage is
+// called for a slice whose rows all left too).  Where timed, *warp_ms and *stage_ms gain the slice's two hipEvent intervals
+// (slots 2, 3, 4 of sp_ev: neither shz_match_device nor ex_device records an event).
+// Nothing returns from inside the loop: a failed pass, stage or event call ends it, and the stream is synchronised before
+// the error leaves -- work that a refused call queued may read the columns, which the caller frees next.
+template <class L, class Stage>
+int32_t rw_run_slices(shz_ctx* ctx, const char* who, const std::vector<rw_slice<L>>& slices, uint32_t* d_wkey, uint32_t* d_woff,
+                      uint64_t buf_items, bool timed, Stage stage, float* warp_ms, float* stage_ms) {
+  hipEvent_t* ev = ctx->sp_ev;
+  const auto mark = [&](int i) { return !timed || hipEventRecord(ev[i], ctx->stream) == hipSuccess; };
+  std::vector<uint64_t> seg_off;
+  int32_t rc = SHZ_OK;
+  bool ev_ok = true;
+  for (size_t i = 0; i < slices.size(); ++i) {
+    const rw_slice<L>& s = slices[i];
+    if (!(ev_ok = mark(2))) break;
+    seg_off.assign((size_t)s.n_seg + 1, 0);
+    uint32_t* d_blk = nullptr;
+    rc = rw_count(ctx, s.V, s.n_seg, &d_blk, seg_off.data());
+    if (rc == SHZ_OK && seg_off[s.n_seg]) rc = rw_write(ctx, s.V, d_blk, d_wkey, d_woff, buf_items);
+    if (rc != SHZ_OK || !(ev_ok = mark(3))) break;
+    rc = stage(i, seg_off.data());
+    if (rc != SHZ_OK) break;
+    if (timed) {
+      float a = 0.f, b = 0.f;
+      ev_ok = mark(4) && hipEventSynchronize(ev[4]) == hipSuccess && hipEventElapsedTime(&a, ev[2], ev[3]) == hipSuccess &&
+              hipEventElapsedTime(&b, ev[3], ev[4]) == hipSuccess;
+      if (!ev_ok) break;
+      *warp_ms += a;
+      *stage_ms += b;
+    }
+  }
+  (void)hipStreamSynchronize(ctx->stream);
+  if (!ev_ok) SHZ_FAIL(ctx, SHZ_E_HIP, "%s: timing a slice failed", who);
+  return rc;
 }
 
 }  // namespace
@@ -591,11 +734,11 @@ extern "C" int32_t shz_warp_rows(shz_ctx* ctx, const uint32_t* key32, const uint
     d_off = b;
   }
   rw_tabs T;
-  SHZ_TRY(rw_upload(ctx, row_off, n_songs, tempo_q16, pitch_q16, n_warps, &T));
-  std::vector<uint64_t> rel((size_t)n_songs + 1), so((size_t)n_seg + 1, 0);
-  for (uint32_t q = 0; q <= n_songs; ++q) rel[q] = row_off[q] - row_off[0];
-  rw_pass P;
-  int32_t rc = rw_count(ctx, T, d_key, d_off, rel.data(), 0, n_songs, 0, n_warps, &P, so.data());
+  SHZ_TRY(rw_upload(ctx, row_off, n_songs, tempo_q16, pitch_q16, n_warps, nullptr, nullptr, &T));
+  const rw_view<rw_product> V{d_key, d_off, T.d_t16, T.d_f16, n * n_warps, {T.d_roff, 0, n_songs, 0, n_warps}};
+  std::vector<uint64_t> so((size_t)n_seg + 1, 0);
+  uint32_t* d_blk = nullptr;
+  int32_t rc = rw_count(ctx, V, n_seg, &d_blk, so.data());
   if (rc != SHZ_OK) { (void)hipStreamSynchronize(ctx->stream); return rc; }   // (queued work may read the staged columns)
   const uint64_t total = so[n_seg];
   if (out_row_off) memcpy(out_row_off, so.data(), (n_seg + 1) * 8);
@@ -608,7 +751,7 @@ extern "C" int32_t shz_warp_rows(shz_ctx* ctx, const uint32_t* key32, const uint
     d_oo = (uint32_t*)own.get(total * 4);
     if (!d_ok || !d_oo) SHZ_FAIL(ctx, SHZ_E_NOMEM, "shz_warp_rows: hipMalloc(2 x %llu) failed", (unsigned long long)(total * 4));
   }
-  rc = rw_write(ctx, P, d_ok, d_oo, (flags & SHZ_OUT_DEVICE) ? cap : total);
+  rc = rw_write(ctx, V, d_blk, d_ok, d_oo, (flags & SHZ_OUT_DEVICE) ? cap : total);
   if (rc == SHZ_OK && !(flags & SHZ_OUT_DEVICE)) {
     if (shz_memcpy(ctx, out_key32, d_ok, total * 4, hipMemcpyDeviceToHost) != hipSuccess ||
         shz_memcpy(ctx, out_off, d_oo, total * 4, hipMemcpyDeviceToHost) != hipSuccess) {
@@ -620,41 +763,33 @@ extern "C" int32_t shz_warp_rows(shz_ctx* ctx, const uint32_t* key32, const uint
   return rc;   // (the call's buffers are freed on return: the stream is idle)
 }
 
-namespace {
-struct rw_slice { uint32_t q0, nq, v0, kv; };
-}
-
 extern "C" int32_t shz_match_songs_warps(shz_ctx* ctx, shz_table* t, const uint32_t* sids, uint32_t n_sids, uint32_t topn,
                                          const uint32_t* tempo_q16, const uint32_t* pitch_q16, uint32_t n_warps, uint32_t flags,
                                          uint64_t* out_rows, uint32_t* out_sid, int32_t* out_delta, uint32_t* out_aligned,
                                          uint32_t* out_dedup, uint32_t* out_nres, uint32_t* out_nhash, uint64_t* out_npairs,
                                          float* ms_gather, float* ms_warp, float* ms_match) {
   if (!ctx || !t) return SHZ_E_INVALID;
+  const char* who = "shz_match_songs_warps";
   if (ms_gather) *ms_gather = 0.f;
   if (ms_warp) *ms_warp = 0.f;
   if (ms_match) *ms_match = 0.f;
   if (t->ctx != ctx) SHZ_FAIL(ctx, SHZ_E_INVALID, "table belongs to another ctx");
   if (topn < 1 || topn > 63) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_match_songs_warps: topn must be in [1,63]");
   if (flags & ~SHZ_MATCH_FULL_SORT) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_match_songs_warps: flags may hold SHZ_MATCH_FULL_SORT");
-  SHZ_TRY(sp_check_ladder(ctx, "shz_match_songs_warps", "n_warps", "tempo", tempo_q16, "pitch", pitch_q16, n_warps, 1));
+  SHZ_TRY(sp_check_ladder(ctx, who, "n_warps", "tempo", tempo_q16, "pitch", pitch_q16, n_warps, 1));
   if (n_sids == 0) return SHZ_OK;
   if (!out_sid || !out_delta || !out_aligned || !out_dedup || !out_nres) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_match_songs_warps: NULL buffer");
   SHZ_TRY(shz_match_ready(ctx, t, topn + 1));
   const uint32_t K = n_warps, w = topn + 1;
   const uint32_t t16_max = *std::max_element(tempo_q16, tempo_q16 + K);   // (time alone: the bias bound)
   const bool timed = ms_gather || ms_warp || ms_match;
-  if (timed) {
-    SHZ_HIP(ctx, hipSetDevice(ctx->device));
-    for (hipEvent_t& e : ctx->sp_ev)
-      if (!e) SHZ_HIP(ctx, hipEventCreate(&e));
-    SHZ_HIP(ctx, hipEventRecord(ctx->sp_ev[0], ctx->stream));
-  }
-  // 1) the rows of the listed songs into columns of this call (the match uses the workspace)
+  if (timed) SHZ_TRY(rw_clock_start(ctx));
+  // 1) the rows of the listed songs into columns of this call
   song_gather G;
+  sg_bufs own;
   std::vector<uint64_t> row_off((uint64_t)n_sids + 1);
-  SHZ_TRY(sg_prepare(t, "shz_match_songs_warps", sids, n_sids, row_off.data(), &G));
-  if (G.total >= (1ull << 32))
-    SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "shz_match_songs_warps: %llu rows in one call (limit 2^32 - 1); list fewer songs", (unsigned long long)G.total);
+  uint32_t *d_key, *d_off, max_off;
+  SHZ_TRY(sg_columns(t, who, sids, n_sids, row_off.data(), &G, &own, &d_key, &d_off, &max_off));
   const uint64_t nv = (uint64_t)n_sids * K;
   for (uint64_t i = 0; i < nv * topn; ++i) { out_sid[i] = 0; out_delta[i] = 0; out_aligned[i] = 0; out_dedup[i] = 0; }
   for (uint64_t i = 0; i < nv; ++i) {
@@ -668,107 +803,69 @@ extern "C" int32_t shz_match_songs_warps(shz_ctx* ctx, shz_table* t, const uint3
     shz_floor_zero_rows(ctx, nv);
     return SHZ_OK;
   }
-  // 2) the slices, from the row counts alone: whole songs x a contiguous chunk of warps whose items (8 bytes each in the
-  // call's buffers) stay within 1/8 of the workspace limit and the match's 2^28-pair budget, and below 2^32; the ladder is
-  // cut only where one song at all warps is beyond that, and a song at one warp is never split
-  const uint64_t max_items = std::min<uint64_t>(std::max<uint64_t>(ctx->ws_limit / 64, 1), 1ull << 28);
-  const uint64_t max_seg = 1ull << 24;
-  const bool small = (ctx->debug & SHZ_DEBUG_CATALOG_SMALL_SLICES) != 0;
-  std::vector<rw_slice> plan;
-  uint64_t buf_items = 0;
-  for (uint32_t q0 = 0; q0 < n_sids;) {
-    const uint64_t r0 = row_off[q0 + 1] - row_off[q0];
-    if (small || r0 * K > max_items) {   // one song, its warps in chunks
-      const uint32_t kv = small ? RW_SMALL_WARPS : (uint32_t)std::max<uint64_t>(max_items / std::max<uint64_t>(r0, 1), 1);
-      for (uint32_t v0 = 0; v0 < K; v0 += kv) {
-        const uint32_t k = std::min(kv, K - v0);
-        plan.push_back({q0, 1, v0, k});
-        buf_items = std::max(buf_items, r0 * k);
-      }
-      ++q0;
-      continue;
-    }
-    uint32_t nq = 1;
-    while (q0 + nq < n_sids && (uint64_t)(nq + 1) * K <= max_seg && (row_off[q0 + nq + 1] - row_off[q0]) * K <= max_items) ++nq;
-    plan.push_back({q0, nq, 0, K});
-    buf_items = std::max(buf_items, (row_off[q0 + nq] - row_off[q0]) * K);
-    q0 += nq;
-  }
-  if (buf_items >= (1ull << 32))
-    SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "shz_match_songs_warps: a song of %llu rows (limit 2^32 - 1 warped rows a slice)", (unsigned long long)buf_items);
-  // the call's buffers, once: the gathered columns, the largest offset, the warped columns of the largest slice
-  sg_bufs own;
-  uint32_t *d_key = (uint32_t*)own.get(G.total * 4), *d_off = (uint32_t*)own.get(G.total * 4), *d_max = (uint32_t*)own.get(4);
-  uint32_t *d_wkey = (uint32_t*)own.get(buf_items * 4), *d_woff = (uint32_t*)own.get(buf_items * 4);
-  if (!d_key || !d_off || !d_max || !d_wkey || !d_woff)
-    SHZ_FAIL(ctx, SHZ_E_NOMEM, "shz_match_songs_warps: hipMalloc(2 x %llu + 2 x %llu) failed", (unsigned long long)(G.total * 4), (unsigned long long)(buf_items * 4));
-  uint32_t max_off = 0;
-  SHZ_HIP(ctx, hipMemsetAsync(d_max, 0, 4, ctx->stream));
-  SHZ_TRY(sg_fill(G, "shz_match_songs_warps", d_key, d_off, d_max));
-  SHZ_HIP(ctx, shz_memcpy(ctx, &max_off, d_max, 4, hipMemcpyDeviceToHost));
-  SHZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
   // the largest warped offset: the bias bound of the match
   const uint64_t t_max = ((uint64_t)max_off * t16_max + 32768) >> 16;
   if (t_max >= (1ull << 20))
     SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "shz_match_songs_warps: a listed song holds offset %u, which the time factor %u / 65536 takes to %llu; warped offsets are query offsets here and must be < 2^20",
              max_off, t16_max, (unsigned long long)t_max);
-  if (timed) SHZ_HIP(ctx, hipEventRecord(ctx->sp_ev[1], ctx->stream));
   rw_tabs T;
-  SHZ_TRY(rw_upload(ctx, row_off.data(), n_sids, tempo_q16, pitch_q16, K, &T));
-  // 3) warp and match, slice by slice: (song, warp) = one query of the match
-  std::vector<uint32_t> r_sid, r_aligned, r_dedup, r_nres, r_nhash;
-  std::vector<int32_t> r_delta;
-  std::vector<uint64_t> r_npairs, seg_off;
-  float warp_ms = 0.f, match_ms = 0.f;
-  int32_t rc = SHZ_OK;
-  for (const rw_slice& s : plan) {
-    const uint64_t n_seg = (uint64_t)s.nq * s.kv;
-    if (timed) SHZ_HIP(ctx, hipEventRecord(ctx->sp_ev[2], ctx->stream));
-    seg_off.assign((size_t)n_seg + 1, 0);
-    rw_pass P;
-    rc = rw_count(ctx, T, d_key, d_off, row_off.data(), s.q0, s.nq, s.v0, s.kv, &P, seg_off.data());
-    const uint64_t total = seg_off[n_seg];
-    if (rc == SHZ_OK && total) rc = rw_write(ctx, P, d_wkey, d_woff, buf_items);
-    if (rc != SHZ_OK) break;
-    if (timed) SHZ_HIP(ctx, hipEventRecord(ctx->sp_ev[3], ctx->stream));
-    r_sid.assign(n_seg * w, 0); r_aligned.assign(n_seg * w, 0); r_dedup.assign(n_seg * w, 0); r_delta.assign(n_seg * w, 0);
-    r_nres.assign(n_seg, 0); r_nhash.assign(n_seg, 0); r_npairs.assign(n_seg, 0);
-    if (total)
-      rc = shz_match_device(ctx, t, d_wkey, d_woff, seg_off.data(), (uint32_t)n_seg, w, flags, (int64_t)t_max, r_sid.data(),
-                            r_delta.data(), r_aligned.data(), r_dedup.data(), r_nres.data(), r_nhash.data(), r_npairs.data());
-    else
-      shz_floor_zero_rows(ctx, n_seg);   // (a slice without a warped row: the vote floor's rows line up with the result arrays)
-    if (rc != SHZ_OK) break;
-    if (timed) {
-      float a = 0.f, b = 0.f;
-      SHZ_HIP(ctx, hipEventRecord(ctx->sp_ev[4], ctx->stream));
-      SHZ_HIP(ctx, hipEventSynchronize(ctx->sp_ev[4]));
-      SHZ_HIP(ctx, hipEventElapsedTime(&a, ctx->sp_ev[2], ctx->sp_ev[3]));
-      SHZ_HIP(ctx, hipEventElapsedTime(&b, ctx->sp_ev[3], ctx->sp_ev[4]));
-      warp_ms += a;
-      match_ms += b;
+  SHZ_TRY(rw_upload(ctx, row_off.data(), n_sids, tempo_q16, pitch_q16, K, nullptr, nullptr, &T));
+  // 2) the slices, from the row counts alone: whole songs x a contiguous chunk of warps whose items (8 bytes each in the
+  // call's buffers) stay within 1/8 of the workspace limit and the match's 2^28-pair budget, and below 2^32; the ladder is
+  // cut only where one song at all warps is beyond that, and a song at one warp is never split.  Either way the segments of
+  // a slice are the queries q0 K + v0 onwards of the call, one after the other
+  const uint64_t max_items = std::min<uint64_t>(std::max<uint64_t>(ctx->ws_limit / 64, 1), 1ull << 28);
+  const uint64_t max_seg = 1ull << 24;
+  const bool small = (ctx->debug & SHZ_DEBUG_CATALOG_SMALL_SLICES) != 0;
+  std::vector<rw_slice<rw_product>> plan;
+  uint64_t buf_items = 0;
+  const auto slice = [&](uint32_t q0, uint32_t nq, uint32_t v0, uint32_t kv) {
+    const uint64_t n_items = (row_off[q0 + nq] - row_off[q0]) * kv;
+    plan.push_back({{d_key, d_off, T.d_t16, T.d_f16, n_items, {T.d_roff, q0, nq, v0, kv}}, (uint64_t)nq * kv});
+    buf_items = std::max(buf_items, n_items);
+  };
+  for (uint32_t q0 = 0; q0 < n_sids;) {
+    const uint64_t r0 = row_off[q0 + 1] - row_off[q0];
+    if (small || r0 * K > max_items) {   // one song, its warps in chunks
+      const uint32_t kv = small ? RW_SMALL_WARPS : (uint32_t)std::max<uint64_t>(max_items / std::max<uint64_t>(r0, 1), 1);
+      for (uint32_t v0 = 0; v0 < K; v0 += kv) slice(q0, 1, v0, std::min(kv, K - v0));
+      ++q0;
+      continue;
     }
-    // 4) the song itself leaves the list of every one of its warps: what stays are the first topn of every other song
-    for (uint32_t q = 0; q < s.nq; ++q)
-      for (uint32_t v = 0; v < s.kv; ++v) {
-        const uint64_t e = (uint64_t)q * s.kv + v, qv = (uint64_t)(s.q0 + q) * K + s.v0 + v;
-        uint32_t k = 0;
-        for (uint32_t i = 0; i < std::min(r_nres[e], w) && k < topn; ++i) {
-          const uint64_t src = e * w + i, dst = qv * topn + k;
-          if (r_sid[src] == sids[s.q0 + q]) continue;
-          out_sid[dst] = r_sid[src];
-          out_delta[dst] = r_delta[src];
-          out_aligned[dst] = r_aligned[src];
-          out_dedup[dst] = r_dedup[src];
-          ++k;
-        }
-        out_nres[qv] = k;
-        if (out_nhash) out_nhash[qv] = r_nhash[e];
-        if (out_npairs) out_npairs[qv] = r_npairs[e];
-      }
+    uint32_t nq = 1;
+    while (q0 + nq < n_sids && (uint64_t)(nq + 1) * K <= max_seg && (row_off[q0 + nq + 1] - row_off[q0]) * K <= max_items) ++nq;
+    slice(q0, nq, 0, K);
+    q0 += nq;
   }
-  (void)hipStreamSynchronize(ctx->stream);   // (a refused call may have queued work that reads the columns)
-  if (rc != SHZ_OK) return rc;
+  if (buf_items >= (1ull << 32))
+    SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "shz_match_songs_warps: a song of %llu rows (limit 2^32 - 1 warped rows a slice)", (unsigned long long)buf_items);
+  // the warped columns of the largest slice, once
+  uint32_t *d_wkey = (uint32_t*)own.get(buf_items * 4), *d_woff = (uint32_t*)own.get(buf_items * 4);
+  if (!d_wkey || !d_woff)
+    SHZ_FAIL(ctx, SHZ_E_NOMEM, "shz_match_songs_warps: hipMalloc(2 x %llu + 2 x %llu) failed", (unsigned long long)(G.total * 4), (unsigned long long)(buf_items * 4));
+  if (timed) SHZ_HIP(ctx, hipEventRecord(ctx->sp_ev[1], ctx->stream));
+  // 3) warp and match, slice by slice: (song, warp) = one query of the match, its top w at its place among the call's
+  std::vector<uint32_t> r_sid(nv * w), r_aligned(nv * w), r_dedup(nv * w), r_nres(nv), r_nhash(nv);
+  std::vector<int32_t> r_delta(nv * w);
+  std::vector<uint64_t> r_npairs(nv);
+  float warp_ms = 0.f, match_ms = 0.f;
+  const auto match = [&](size_t i, const uint64_t* seg_off) -> int32_t {
+    const rw_slice<rw_product>& s = plan[i];
+    const uint64_t e0 = (uint64_t)s.V.lay.q0 * K + s.V.lay.v0;
+    if (!seg_off[s.n_seg]) {   // (a slice without a warped row: the vote floor's rows line up with the result arrays)
+      shz_floor_zero_rows(ctx, s.n_seg);
+      return SHZ_OK;
+    }
+    return shz_match_device(ctx, t, d_wkey, d_woff, seg_off, (uint32_t)s.n_seg, w, flags, (int64_t)t_max, r_sid.data() + e0 * w,
+                            r_delta.data() + e0 * w, r_aligned.data() + e0 * w, r_dedup.data() + e0 * w, r_nres.data() + e0,
+                            r_nhash.data() + e0, r_npairs.data() + e0);
+  };
+  SHZ_TRY(rw_run_slices(ctx, who, plan, d_wkey, d_woff, buf_items, timed, match, &warp_ms, &match_ms));
+  // 4) the song itself leaves the list of every one of its warps
+  sg_drop_self(sids, K, nv, topn, r_sid.data(), r_delta.data(), r_aligned.data(), r_dedup.data(), r_nres.data(), out_sid, out_delta,
+               out_aligned, out_dedup, out_nres);
+  if (out_nhash) memcpy(out_nhash, r_nhash.data(), nv * 4);
+  if (out_npairs) memcpy(out_npairs, r_npairs.data(), nv * 8);
   if (timed) {
     if (ms_gather) SHZ_HIP(ctx, hipEventElapsedTime(ms_gather, ctx->sp_ev[0], ctx->sp_ev[1]));
     if (ms_warp) *ms_warp = warp_ms;
@@ -777,210 +874,9 @@ extern "C" int32_t shz_match_songs_warps(shz_ctx* ctx, shz_table* t, const uint3
   return SHZ_OK;
 }
 
-// ---- the job form of the row warp: where an altered copy overlaps its original, and at what tempo ---------
-// The product form above warps every listed song at every warp.  The refinement of found pairs needs a JOB LIST: job j is one
-// song (an index into the call's gathered songs) at the one warp (t16, f16) its pair was found at, and a song may stand in
-// several jobs.  Work is laid out over (job j, row r) items, job-major, then the rows of the job's song in gathered order: a
-// job is one contiguous query of the extent pass, and a wave stays at one warp over consecutive rows wherever it lies inside
-// one job.  The two passes are the product form's: blocks of RW_ITEMS items, one wave a block; pass 1 ballots, writes one
-// count per block and adds the kept items to their job's count (one add a wave where the wave lies inside one job); the block
-// counts are scanned; pass 2 repeats the map and writes at block base + rank inside the ballot.  No atomic decides a place.
-// The view stands beside rw_view: the product kernels read what they read before.
-#define RWJ_SMALL_JOBS 2u   // jobs of a slice under SHZ_DEBUG_CATALOG_SMALL_SLICES
-struct rwj_view {                      // what the kernels of one slice of jobs read (device pointers)
-  const uint32_t *key, *off;           // the rows of the call's distinct songs, song after song
-  const uint64_t* roff;                // CSR of those songs over them, from 0
-  const uint32_t *song, *t16, *f16;    // the slice's jobs: song (index into roff), time factor, frequency factor
-  const uint64_t* base;                // nj + 1: first item of every job of the slice (item w of the slice is base[0] + w)
-  uint32_t nj;
-  uint64_t n_items;                    // base[nj] - base[0]
-};
-struct rwj_cursor {
-  uint32_t j, r, n;                    // job (of the slice), row of its song, rows of its song
-  uint64_t row0;                       // the song's first row
-};
-
-// item w < n_items -> its job (the last j whose first item is <= w: empty jobs share a start) and row
-__device__ __forceinline__ void rwj_seek(const rwj_view& V, uint64_t w, rwj_cursor* c) {
-  const uint64_t b0 = V.base[0];
-  uint32_t lo = 0, hi = V.nj;
-  while (lo + 1 < hi) {
-    const uint32_t mid = (lo + hi) >> 1;
-    if (V.base[mid] - b0 <= w) lo = mid; else hi = mid;
-  }
-  const uint32_t s = V.song[lo];
-  const uint64_t r0 = V.roff[s];
-  const uint32_t n = (uint32_t)(V.roff[s + 1] - r0);   // (> 0: w lies inside the job's items)
-  const uint64_t rem = w - (V.base[lo] - b0);
-  c->j = lo;
-  c->r = (uint32_t)min(rem, (uint64_t)(max(n, 1u) - 1));   // (the clamp holds for every consistent view; it keeps any read inside the columns)
-  c->n = n;
-  c->row0 = r0;
-}
-
-// the RW_LOADS items of this lane in the block at w0: rows loaded, the job kept as segment; dead lanes: seg = ~0
-__device__ __forceinline__ void rwj_load(const rwj_view& V, uint64_t w0, uint32_t lane, uint32_t* k, uint32_t* o, uint32_t* seg) {
-  rwj_cursor c{0, 0, 0, 0};
-#pragma unroll
-  for (int j = 0; j < RW_LOADS; ++j) {
-    const uint64_t w = w0 + (uint64_t)j * 64 + lane;
-    seg[j] = 0xFFFFFFFFu;
-    k[j] = o[j] = 0;
-    if (w >= V.n_items) continue;
-    if (j == 0 || c.r + 64 >= c.n) rwj_seek(V, w, &c);   // (64 items on: still inside this job's rows?)
-    else c.r += 64;
-    if (c.n == 0) continue;
-    k[j] = V.key[c.row0 + c.r];
-    o[j] = V.off[c.row0 + c.r];
-    seg[j] = c.j;
-  }
-}
-
-// pass 1: kept items of every block, kept items of every job
-__global__ __launch_bounds__(64 * RW_WAVES) void rwj_count_kernel(rwj_view V, uint32_t* __restrict__ blk_cnt,
-                                                                   uint32_t* __restrict__ job_cnt) {
-  const uint32_t lane = threadIdx.x & 63;
-  const uint64_t blk = (uint64_t)blockIdx.x * RW_WAVES + (threadIdx.x >> 6);
-  const uint64_t w0 = blk * RW_ITEMS;
-  if (w0 >= V.n_items) return;   // uniform in the wave
-  uint32_t k[RW_LOADS], o[RW_LOADS], seg[RW_LOADS];
-  rwj_load(V, w0, lane, k, o, seg);
-  uint32_t c = 0;
-#pragma unroll
-  for (int j = 0; j < RW_LOADS; ++j) {
-    const bool live = seg[j] != 0xFFFFFFFFu;
-    const uint32_t e = live ? seg[j] : 0u;   // (a dead lane reads job 0's factors and keeps nothing)
-    uint32_t a, b;
-    const bool keep = rw_warp_row(k[j], o[j], V.t16[e], V.f16[e], &a, &b) && live;
-    const uint64_t m = __ballot(keep);
-    const uint32_t first = (uint32_t)__shfl((int)seg[j], 0, 64);   // (live lanes are a prefix of the wave)
-    if (__ballot(live && seg[j] != first) == 0) {   // the wave inside one job: one add
-      if (lane == 0 && m) atomicAdd(job_cnt + first, (uint32_t)__popcll(m));
-    } else if (keep) {
-      atomicAdd(job_cnt + seg[j], 1u);
-    }
-    c += (uint32_t)__popcll(m);
-  }
-  if (lane == 0) blk_cnt[blk] = c;
-}
-
-// pass 2: every kept item, in item order, at the place the scan of the block counts gives (no store at or beyond cap)
-__global__ __launch_bounds__(64 * RW_WAVES) void rwj_write_kernel(rwj_view V, const uint32_t* __restrict__ blk_pos,
-                                                                   uint32_t* __restrict__ out_key, uint32_t* __restrict__ out_off,
-                                                                   uint64_t cap) {
-  const uint32_t lane = threadIdx.x & 63;
-  const uint64_t blk = (uint64_t)blockIdx.x * RW_WAVES + (threadIdx.x >> 6);
-  const uint64_t w0 = blk * RW_ITEMS;
-  if (w0 >= V.n_items) return;   // uniform in the wave
-  uint32_t k[RW_LOADS], o[RW_LOADS], seg[RW_LOADS];
-  rwj_load(V, w0, lane, k, o, seg);
-  uint64_t base = blk_pos[blk];
-#pragma unroll
-  for (int j = 0; j < RW_LOADS; ++j) {
-    const bool live = seg[j] != 0xFFFFFFFFu;
-    const uint32_t e = live ? seg[j] : 0u;
-    uint32_t a, b;
-    const bool keep = rw_warp_row(k[j], o[j], V.t16[e], V.f16[e], &a, &b) && live;
-    const uint64_t m = __ballot(keep);
-    if (keep) {
-      const uint64_t pos = base + (uint64_t)__popcll(m & ((1ull << lane) - 1ull));
-      if (pos < cap) { out_key[pos] = a; out_off[pos] = b; }
-    }
-    base += (uint64_t)__popcll(m);
-  }
-}
-
-// the largest offset of every gathered song (song_max zeroed; a song without rows keeps 0): one atomicMax a wave where the
-// wave lies inside one song, whose result no order changes
-__global__ __launch_bounds__(256) void rwj_song_max_kernel(const uint32_t* __restrict__ off, const uint64_t* __restrict__ roff,
-                                                            uint32_t n_songs, uint64_t total, uint32_t* __restrict__ song_max) {
-  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-  const bool live = i < total;
-  uint32_t lo = 0, hi = n_songs;   // the last song whose first row is <= i (empty songs share a start)
-  while (live && lo + 1 < hi) {
-    const uint32_t mid = (lo + hi) >> 1;
-    if (roff[mid] <= i) lo = mid; else hi = mid;
-  }
-  uint32_t o = live ? off[i] : 0u;
-  const uint32_t first = (uint32_t)__shfl((int)lo, 0, 64);   // (live lanes are a prefix of the wave)
-  if (__ballot(live && lo != first) == 0) {
-    for (int d = 32; d >= 1; d >>= 1) o = max(o, (uint32_t)__shfl_xor((int)o, d, 64));
-    if ((threadIdx.x & 63) == 0 && o) atomicMax(song_max + first, o);
-  } else if (live && o) {
-    atomicMax(song_max + lo, o);
-  }
-}
-
-namespace {
-
-struct rwj_tabs {                      // the call's tables on the device (one block): roff | base | song | t16 | f16
-  const uint64_t *d_roff = nullptr, *d_base = nullptr;
-  const uint32_t *d_song = nullptr, *d_t16 = nullptr, *d_f16 = nullptr;
-};
-struct rwj_pass {
-  rwj_view V;
-  uint64_t n_blk = 0;
-  uint32_t* d_blk = nullptr;
-};
-
-// roff[n_songs + 1] (from 0), base[n_jobs + 1], and the three job columns, uploaded once a call
-int32_t rwj_upload(shz_ctx* ctx, const uint64_t* row_off, uint32_t n_songs, const uint64_t* base, const uint32_t* song,
-                   const uint32_t* t16, const uint32_t* f16, uint32_t n_jobs, rwj_tabs* T) {
-  const uint64_t ro_bytes = ((uint64_t)n_songs + 1) * 8, ba_bytes = ((uint64_t)n_jobs + 1) * 8, col = (uint64_t)n_jobs * 4;
-  const uint64_t bytes = ro_bytes + ba_bytes + 3 * col;
-  std::vector<char> h(bytes);
-  memcpy(h.data(), row_off, ro_bytes);
-  memcpy(h.data() + ro_bytes, base, ba_bytes);
-  memcpy(h.data() + ro_bytes + ba_bytes, song, col);
-  memcpy(h.data() + ro_bytes + ba_bytes + col, t16, col);
-  memcpy(h.data() + ro_bytes + ba_bytes + 2 * col, f16, col);
-  void* d;
-  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_RW_TAB, bytes, &d));
-  SHZ_HIP(ctx, shz_memcpy(ctx, d, h.data(), bytes, hipMemcpyHostToDevice));
-  T->d_roff = (const uint64_t*)d;
-  T->d_base = (const uint64_t*)((char*)d + ro_bytes);
-  T->d_song = (const uint32_t*)((char*)d + ro_bytes + ba_bytes);
-  T->d_t16 = T->d_song + n_jobs;
-  T->d_f16 = T->d_t16 + n_jobs;
-  return SHZ_OK;
-}
-
-// pass 1 and the scan of one slice, the jobs [j0, j0 + nj) of n_items items: job_off[nj + 1] (host) is the exact CSR of the
-// jobs' kept rows, relative to the slice.  The stream is idle on return.  A slice without items launches nothing
-int32_t rwj_count(shz_ctx* ctx, const rwj_tabs& T, const uint32_t* d_key, const uint32_t* d_off, uint32_t j0, uint32_t nj,
-                  uint64_t n_items, rwj_pass* P, uint64_t* job_off) {
-  for (uint32_t e = 0; e <= nj; ++e) job_off[e] = 0;
-  P->V = rwj_view{d_key, d_off, T.d_roff, T.d_song + j0, T.d_t16 + j0, T.d_f16 + j0, T.d_base + j0, nj, n_items};
-  P->n_blk = rw_blocks(n_items);
-  if (n_items == 0) return SHZ_OK;
-  void *d_blk, *d_cnt;
-  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_RW_BLK, P->n_blk * 4, &d_blk));
-  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_RW_CNT, (uint64_t)nj * 4, &d_cnt));
-  P->d_blk = (uint32_t*)d_blk;
-  SHZ_HIP(ctx, hipMemsetAsync(d_cnt, 0, (uint64_t)nj * 4, ctx->stream));
-  hipLaunchKernelGGL(rwj_count_kernel, dim3((unsigned)((P->n_blk + RW_WAVES - 1) / RW_WAVES)), dim3(64 * RW_WAVES), 0, ctx->stream,
-                     P->V, P->d_blk, (uint32_t*)d_cnt);
-  SHZ_HIP(ctx, hipGetLastError());
-  SHZ_TRY(shz_scan_u32(ctx, P->d_blk, P->d_blk, P->n_blk, nullptr));
-  std::vector<uint32_t> cnt(nj);
-  SHZ_HIP(ctx, shz_memcpy(ctx, cnt.data(), d_cnt, (uint64_t)nj * 4, hipMemcpyDeviceToHost));
-  SHZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  for (uint32_t e = 0; e < nj; ++e) job_off[e + 1] = job_off[e] + cnt[e];
-  return SHZ_OK;
-}
-
-int32_t rwj_write(shz_ctx* ctx, const rwj_pass& P, uint32_t* d_okey, uint32_t* d_ooff, uint64_t cap) {
-  if (P.V.n_items == 0) return SHZ_OK;
-  hipLaunchKernelGGL(rwj_write_kernel, dim3((unsigned)((P.n_blk + RW_WAVES - 1) / RW_WAVES)), dim3(64 * RW_WAVES), 0, ctx->stream,
-                     P.V, (const uint32_t*)P.d_blk, d_okey, d_ooff, cap);
-  SHZ_HIP(ctx, hipGetLastError());
-  return SHZ_OK;
-}
-
-struct rwj_slice { uint32_t j0, nj; };
-
-}  // namespace
-
+// ---- the job form: where an altered copy overlaps its original, and at what tempo ------------------------
+// The refinement of found pairs has a JOB LIST: job j is one song at the one warp (t16, f16) its pair was found at, and a song
+// may stand in several jobs.  The row warp is the one above, under the rw_jobs layout.
 extern "C" int32_t shz_match_songs_warps_extents(shz_ctx* ctx, shz_table* t, const uint32_t* job_sid, const uint32_t* job_t16,
                                                  const uint32_t* job_f16, uint32_t n_jobs, uint32_t ncand, const uint32_t* cand_sid,
                                                  const int32_t* cand_dlo, const int32_t* cand_dhi, const uint32_t* cand_n,
@@ -1007,12 +903,7 @@ extern "C" int32_t shz_match_songs_warps_extents(shz_ctx* ctx, shz_table* t, con
   A.out_sum_qu = out_sum_qu;
   SHZ_TRY(ex_check(ctx, t, who, A));
   const bool timed = ms_gather || ms_warp || ms_extent;
-  if (timed) {
-    SHZ_HIP(ctx, hipSetDevice(ctx->device));
-    for (hipEvent_t& e : ctx->sp_ev)
-      if (!e) SHZ_HIP(ctx, hipEventCreate(&e));
-    SHZ_HIP(ctx, hipEventRecord(ctx->sp_ev[0], ctx->stream));
-  }
+  if (timed) SHZ_TRY(rw_clock_start(ctx));
   // 1) the distinct songs of the jobs, ascending, each gathered once; job j reads song slot[j] of them
   std::vector<uint32_t> usid(job_sid, job_sid + n_jobs), slot(n_jobs);
   std::sort(usid.begin(), usid.end());
@@ -1020,10 +911,10 @@ extern "C" int32_t shz_match_songs_warps_extents(shz_ctx* ctx, shz_table* t, con
   const uint32_t n_songs = (uint32_t)usid.size();
   for (uint32_t j = 0; j < n_jobs; ++j) slot[j] = (uint32_t)(std::lower_bound(usid.begin(), usid.end(), job_sid[j]) - usid.begin());
   song_gather G;
+  sg_bufs own;
   std::vector<uint64_t> row_off((size_t)n_songs + 1);
-  SHZ_TRY(sg_prepare(t, who, usid.data(), n_songs, row_off.data(), &G));
-  if (G.total >= (1ull << 32))
-    SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "%s: %llu rows in one call (limit 2^32 - 1); list fewer songs", who, (unsigned long long)G.total);
+  uint32_t *d_key, *d_off;
+  SHZ_TRY(sg_columns(t, who, usid.data(), n_songs, row_off.data(), &G, &own, &d_key, &d_off, nullptr));
   std::vector<uint64_t> base((size_t)n_jobs + 1, 0);   // first item of every job
   for (uint32_t j = 0; j < n_jobs; ++j) base[j + 1] = base[j] + (row_off[slot[j] + 1] - row_off[slot[j]]);
   if (base[n_jobs] >= (1ull << 32))
@@ -1036,35 +927,34 @@ extern "C" int32_t shz_match_songs_warps_extents(shz_ctx* ctx, shz_table* t, con
   uint32_t *r_hist = out_hist ? r_u32.data() + cells * 5 : nullptr, *r_shift = r_u32.data() + r_u32.size() - n_jobs;
   uint64_t* r_kept = r_u64.data() + cells * 4;
   float gather_ms = 0.f, warp_ms = 0.f, extent_ms = 0.f;
-  int32_t rc = SHZ_OK;
   if (G.total) {   // (no job's song has a row: every query is empty, every output zero)
+    rw_tabs T;
+    SHZ_TRY(rw_upload(ctx, row_off.data(), n_songs, job_t16, job_f16, n_jobs, base.data(), slot.data(), &T));
     // 2) the slices, from the row counts alone: whole jobs whose items (8 bytes each in the call's warped columns) stay
     // within 1/8 of the workspace limit; a job is never split
     const uint64_t max_items = std::max<uint64_t>(ctx->ws_limit / 64, 1);
-    const uint32_t max_jobs = (ctx->debug & SHZ_DEBUG_CATALOG_SMALL_SLICES) ? RWJ_SMALL_JOBS : (1u << 24);
-    std::vector<rwj_slice> plan;
+    const uint32_t max_jobs = (ctx->debug & SHZ_DEBUG_CATALOG_SMALL_SLICES) ? RW_SMALL_JOBS : (1u << 24);
+    std::vector<rw_slice<rw_jobs>> plan;
+    std::vector<uint32_t> first;   // the first job of every slice
     uint64_t buf_items = 0;
     for (uint32_t j0 = 0; j0 < n_jobs;) {
       uint32_t nj = 1;
       while (j0 + nj < n_jobs && nj < max_jobs && base[j0 + nj + 1] - base[j0] <= max_items) ++nj;
-      plan.push_back({j0, nj});
-      buf_items = std::max(buf_items, base[j0 + nj] - base[j0]);
+      const uint64_t n_items = base[j0 + nj] - base[j0];
+      plan.push_back({{d_key, d_off, T.d_t16 + j0, T.d_f16 + j0, n_items, {T.d_roff, T.d_song + j0, T.d_base + j0, nj}}, nj});
+      first.push_back(j0);
+      buf_items = std::max(buf_items, n_items);
       j0 += nj;
     }
-    // the call's buffers, once: the gathered columns, the songs' largest offsets, the warped columns of the largest slice
-    sg_bufs own;
-    uint32_t *d_key = (uint32_t*)own.get(G.total * 4), *d_off = (uint32_t*)own.get(G.total * 4);
+    // the songs' largest offsets and the warped columns of the largest slice, once
     uint32_t* d_smax = (uint32_t*)own.get((uint64_t)n_songs * 4);
     uint32_t *d_wkey = (uint32_t*)own.get(buf_items * 4), *d_woff = (uint32_t*)own.get(buf_items * 4);
-    if (!d_key || !d_off || !d_smax || !d_wkey || !d_woff)
+    if (!d_smax || !d_wkey || !d_woff)
       SHZ_FAIL(ctx, SHZ_E_NOMEM, "%s: hipMalloc(2 x %llu + 2 x %llu) failed", who, (unsigned long long)(G.total * 4), (unsigned long long)(buf_items * 4));
-    SHZ_TRY(sg_fill(G, who, d_key, d_off, nullptr));
-    rwj_tabs T;
-    SHZ_TRY(rwj_upload(ctx, row_off.data(), n_songs, base.data(), slot.data(), job_t16, job_f16, n_jobs, &T));
     // a warped offset is a query offset of the extent pass: every job's largest must stay below 2^20
     std::vector<uint32_t> smax(n_songs);
     SHZ_HIP(ctx, hipMemsetAsync(d_smax, 0, (uint64_t)n_songs * 4, ctx->stream));
-    hipLaunchKernelGGL(rwj_song_max_kernel, dim3(nblk(G.total)), dim3(256), 0, ctx->stream, (const uint32_t*)d_off, T.d_roff, n_songs,
+    hipLaunchKernelGGL(rw_song_max_kernel, dim3(nblk(G.total)), dim3(256), 0, ctx->stream, (const uint32_t*)d_off, T.d_roff, n_songs,
                        G.total, d_smax);
     SHZ_HIP(ctx, hipGetLastError());
     const hipError_t e_copy = shz_memcpy(ctx, smax.data(), d_smax, (uint64_t)n_songs * 4, hipMemcpyDeviceToHost);
@@ -1078,45 +968,21 @@ extern "C" int32_t shz_match_songs_warps_extents(shz_ctx* ctx, shz_table* t, con
     }
     if (timed) SHZ_HIP(ctx, hipEventRecord(ctx->sp_ev[1], ctx->stream));
     // 3) warp and extent pass, slice by slice: job = one query
-    std::vector<uint64_t> job_off;
-    bool ev_failed = false;
-    for (const rwj_slice& s : plan) {
-      if (timed && hipEventRecord(ctx->sp_ev[2], ctx->stream) != hipSuccess) { ev_failed = true; break; }
-      job_off.assign((size_t)s.nj + 1, 0);
-      rwj_pass P;
-      rc = rwj_count(ctx, T, d_key, d_off, s.j0, s.nj, base[s.j0 + s.nj] - base[s.j0], &P, job_off.data());
-      const uint64_t total = job_off[s.nj];
-      if (rc == SHZ_OK && total) rc = rwj_write(ctx, P, d_wkey, d_woff, buf_items);
-      if (rc != SHZ_OK) break;
-      for (uint32_t e = 0; e < s.nj; ++e) r_kept[s.j0 + e] = job_off[e + 1] - job_off[e];
-      if (timed && hipEventRecord(ctx->sp_ev[3], ctx->stream) != hipSuccess) { ev_failed = true; break; }
-      if (total) {   // (a slice whose rows all left: its queries are empty, its outputs stay zero)
-        const uint64_t c0 = (uint64_t)s.j0 * ncand;
-        ex_args S{s.nj, ncand, cand_sid + c0, cand_dlo + c0, cand_dhi + c0, cand_n + s.j0, r_u32.data() + c0,
-                  r_u32.data() + cells + c0, r_u32.data() + 2 * cells + c0, r_u32.data() + 3 * cells + c0,
-                  r_u32.data() + 4 * cells + c0, r_hist ? r_hist + c0 * 64 : nullptr, r_shift + s.j0};
-        S.out_sum_q = r_u64.data() + c0;
-        S.out_sum_u = r_u64.data() + cells + c0;
-        S.out_sum_qq = r_u64.data() + 2 * cells + c0;
-        S.out_sum_qu = r_u64.data() + 3 * cells + c0;
-        rc = ex_device(ctx, t, who, d_wkey, d_woff, job_off.data(), S);
-        if (rc != SHZ_OK) break;
-      }
-      if (timed) {
-        float a = 0.f, b = 0.f;
-        if (hipEventRecord(ctx->sp_ev[5], ctx->stream) != hipSuccess || hipEventSynchronize(ctx->sp_ev[5]) != hipSuccess ||
-            hipEventElapsedTime(&a, ctx->sp_ev[2], ctx->sp_ev[3]) != hipSuccess ||
-            hipEventElapsedTime(&b, ctx->sp_ev[3], ctx->sp_ev[5]) != hipSuccess) {
-          ev_failed = true;
-          break;
-        }
-        warp_ms += a;
-        extent_ms += b;
-      }
-    }
-    (void)hipStreamSynchronize(ctx->stream);   // (a refused call may have queued work that reads the columns)
-    if (ev_failed) SHZ_FAIL(ctx, SHZ_E_HIP, "%s: timing a slice failed", who);
-    if (rc != SHZ_OK) return rc;
+    const auto extent = [&](size_t i, const uint64_t* job_off) -> int32_t {
+      const uint32_t j0 = first[i], nj = (uint32_t)plan[i].n_seg;
+      for (uint32_t e = 0; e < nj; ++e) r_kept[j0 + e] = job_off[e + 1] - job_off[e];
+      if (!job_off[nj]) return SHZ_OK;   // (a slice whose rows all left: its queries are empty, its outputs stay zero)
+      const uint64_t c0 = (uint64_t)j0 * ncand;
+      ex_args S{nj, ncand, cand_sid + c0, cand_dlo + c0, cand_dhi + c0, cand_n + j0, r_u32.data() + c0,
+                r_u32.data() + cells + c0, r_u32.data() + 2 * cells + c0, r_u32.data() + 3 * cells + c0,
+                r_u32.data() + 4 * cells + c0, r_hist ? r_hist + c0 * 64 : nullptr, r_shift + j0};
+      S.out_sum_q = r_u64.data() + c0;
+      S.out_sum_u = r_u64.data() + cells + c0;
+      S.out_sum_qq = r_u64.data() + 2 * cells + c0;
+      S.out_sum_qu = r_u64.data() + 3 * cells + c0;
+      return ex_device(ctx, t, who, d_wkey, d_woff, job_off, S);
+    };
+    SHZ_TRY(rw_run_slices(ctx, who, plan, d_wkey, d_woff, buf_items, timed, extent, &warp_ms, &extent_ms));
     if (timed) SHZ_HIP(ctx, hipEventElapsedTime(&gather_ms, ctx->sp_ev[0], ctx->sp_ev[1]));
   }
   uint32_t* outs[5] = {out_count, out_q_first, out_q_last, out_t_first, out_t_last};

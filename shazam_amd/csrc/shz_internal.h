@@ -152,7 +152,7 @@ struct shz_ctx {
   bool tev_init = false;
   hipEvent_t rq_ev[3] = {nullptr, nullptr, nullptr};   // shz_recognize_batch: start, extraction done, match done (created on first use)
   hipEvent_t sc_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // shz_scan_batch / shz_scan_speeds: start, extraction done (then: a warp begun / done); the window stage: a step begun / done, the match behind it done (created on first use)
-  hipEvent_t sp_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // shz_recognize_speeds / shz_match_songs_warps / _warps_extents: start, peaks (rows) done, a slice's warp begun / done, its match done, its extent pass done (created on first use)
+  hipEvent_t sp_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // shz_recognize_speeds / shz_match_songs_warps / _warps_extents: start, peaks (rows) done, a slice's warp begun / done, the stage after it done (the match; in the catalogue's job form the extent pass), shz_recognize_speeds' extent pass done (created on first use)
   hipEvent_t rp_ev[3] = {nullptr, nullptr, nullptr};   // shz_repeats_* / shz_shared_*: a stage begun, the pairs done, the cells done (created on first use)
   bool profiling = false;
   float kernel_ms[8] = {0};

@@ -89,6 +89,42 @@ def test_device_columns_and_capacity(ctx):
             b.free()
 
 
+def test_the_job_form_keeps_what_the_product_form_keeps():
+    """The two layouts share one kernel pair.  With jobs = every (song, warp) of a product call in product order, out_kept of
+    shz_match_songs_warps_extents is the per-segment count of shz_warp_rows' out_row_off on the same songs' exported rows:
+    the 15 COUNTS as a table (an id without rows is a song of 0 rows), 3 warps (offsets < 2^19 stay below 2^20 at 1.03), one
+    dummy candidate; whole and in slices of 2 jobs."""
+    import shazam_amd as S
+    from shazam_amd import _ffi
+    ctx = S.get_context(0)
+    key, off, ro = make_rows(9)
+    tempos, pitches = [32768, 65536, 67502], [32768, 65536, 60000]
+    sids = np.arange(1, len(COUNTS) + 1, dtype=np.uint32)
+    t = S.Table(ctx)
+    try:
+        for q, s in enumerate(sids):
+            if COUNTS[q]:
+                t.insert(key[int(ro[q]):int(ro[q + 1])], int(s), off[int(ro[q]):int(ro[q + 1])])
+        t.finalize()
+        sro, sk, so = t.song_hashes(sids)
+        assert np.diff(sro.astype(np.int64)).tolist() == COUNTS
+        _, _, oro = ctx.warp_rows(sk, so, sro, tempos, pitches)
+        want = np.diff(oro.astype(np.int64))
+        K, n = len(tempos), len(sids) * len(tempos)
+        assert want[LEAVES * K] == 0 and want[LEAVES * K + 1] == COUNTS[LEAVES] and 0 < want.sum() < K * sum(COUNTS)
+        cand = np.ones((n, 1), np.uint32)
+        for flag in (0, _ffi.DEBUG_CATALOG_SMALL_SLICES):
+            ctx.set_debug(flag)
+            try:
+                got = t.match_songs_warps_extents(np.repeat(sids, K), np.tile(tempos, len(sids)), np.tile(pitches, len(sids)), cand,
+                                                  np.zeros((n, 1), np.int32), np.zeros((n, 1), np.int32))
+            finally:
+                ctx.set_debug(0)
+            assert np.array_equal(np.asarray(got["kept"], np.int64), want), flag
+    finally:
+        t.close()
+
+
 def test_refusals(ctx):
     import shazam_amd as S
     from shazam_amd import _ffi
