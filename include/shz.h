@@ -312,13 +312,17 @@ int32_t shz_table_set_run_rows(shz_table* t, uint64_t rows);
 /* A table is a list of sorted segments (each one radix sort, < 2^32 rows; one cut from sealed runs holds at most
  * min(rows, 2^32 - 4096)) that every probe visits; rows beyond `rows` per segment open a new one at finalize.  Default 2^31; smaller values only for tests.
  * UNIQUE(song_id, offset, hash) + INSERT IGNORE (mysql_database.py:54-55, 62-68) hold across segments: staged rows
- * that already sit in a frozen segment are dropped at finalize, duplicates inside the batch by the sort. */
+ * that already sit in a frozen segment are dropped at finalize, duplicates inside the batch by the sort.  The value may
+ * change between calls: an active segment that already holds more rows is frozen as it is by the next batch that does not fit. */
 int32_t shz_table_set_segment_rows(shz_table* t, uint64_t rows);
 /* ON DELETE CASCADE of fingerprints when songs are deleted (mysql_database.py:57-58; DELETE_UNFINGERPRINTED :132-134,
  * the reference's crash recovery at __init__.py:424): every row of the listed song ids leaves the table (all segments
- * and the staged rows), the order of the rest is kept.  sids: host array. */
+ * and the staged rows), the order of the rest is kept.  sids: host array of any 32-bit ids, listed or not in the table
+ * (scratch: 4 bytes per listed id, whatever its value).  Sealed runs become segments first.  A finalized table whose last
+ * rows leave stays finalized: it answers, with nothing, without another shz_table_finalize. */
 int32_t shz_table_delete_songs(shz_table* t, const uint32_t* sids, uint64_t n_sids, uint64_t* rows_deleted);
-/* DROP TABLE fingerprints: no rows, no segments; allocations of the active segment are kept for the rows to come. */
+/* DROP TABLE fingerprints: no rows, no segments; allocations of the active segment are kept for the rows to come.  A
+ * finalized table stays finalized (empty); one that never was still refuses queries (SHZ_E_STATE). */
 int32_t shz_table_clear(shz_table* t);
 int32_t shz_table_rows(shz_table* t, uint64_t* n_rows, uint64_t* n_staged);
 /* number of sorted segments the finalized rows live in (every query hash is looked up in each of them) */

@@ -514,12 +514,18 @@ static int32_t finalize_active(shz_table* t, const uint32_t* skey, const uint32_
 
 // ---- rows leaving the table: ON DELETE CASCADE of a song's fingerprints (mysql_database.py:57-58), and INSERT IGNORE
 // against rows that already sit in a frozen segment (UNIQUE(song_id, offset, hash), :54-55, 62-68) ----
-__global__ void tbl_sid_keep_kernel(const uint32_t* __restrict__ sid, uint64_t n, const uint32_t* __restrict__ bitmap,
-                                    uint32_t nbits, uint32_t* __restrict__ flag) {
+// flag = 0 for the rows of the listed songs: ids[] is sorted and distinct, searched per row -- nothing is sized by an id's value
+__global__ void tbl_sid_keep_kernel(const uint32_t* __restrict__ sid, uint64_t n, const uint32_t* __restrict__ ids,
+                                    uint32_t n_ids, uint32_t* __restrict__ flag) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const uint32_t s = sid[i];
-  flag[i] = (s < nbits && ((bitmap[s >> 5] >> (s & 31)) & 1u)) ? 0u : 1u;
+  uint32_t lo = 0, hi = n_ids;   // first entry >= s
+  while (lo < hi) {
+    const uint32_t mid = lo + ((hi - lo) >> 1);
+    if (ids[mid] < s) lo = mid + 1; else hi = mid;
+  }
+  flag[i] = (lo < n_ids && ids[lo] == s) ? 0u : 1u;
 }
 __global__ void tbl_gather_u32_kernel(const uint32_t* __restrict__ in, const uint32_t* __restrict__ flag,
                                       const uint32_t* __restrict__ pos, uint64_t n, uint32_t* __restrict__ out) {
@@ -601,6 +607,18 @@ static int32_t rebuild_buckets(shz_ctx* ctx, uint32_t* key, uint64_t n, uint32_t
   return SHZ_OK;
 }
 
+// A table without segments answers queries through one empty bucket: what finalize leaves when no row came, and what a
+// finalized table keeps when its last rows are deleted or cleared (freeze_active took the bucket array along).
+static int32_t empty_table_bucket(shz_table* t) {
+  shz_ctx* ctx = t->ctx;
+  if (t->bucket || t->n || !t->done.empty()) return SHZ_OK;
+  SHZ_HIP(ctx, hipMalloc(&t->bucket, 2 * 4));
+  SHZ_HIP(ctx, hipMemsetAsync(t->bucket, 0, 8, ctx->stream));
+  t->nbuckets = 1;
+  t->bcap = 2;
+  return SHZ_OK;
+}
+
 extern "C" int32_t shz_table_delete_songs(shz_table* t, const uint32_t* sids, uint64_t n_sids, uint64_t* rows_deleted) {
   if (!t) return SHZ_E_INVALID;
   shz_ctx* ctx = t->ctx;
@@ -610,21 +628,23 @@ extern "C" int32_t shz_table_delete_songs(shz_table* t, const uint32_t* sids, ui
   if (!sids) SHZ_FAIL(ctx, SHZ_E_INVALID, "sids is NULL");
   SHZ_HIP(ctx, hipSetDevice(ctx->device));
   if (!t->runs.empty()) SHZ_TRY(flush_runs(t, true));   // sealed runs become segments first: rows leave segments and staged rows
-  uint32_t mx = 0;
-  for (uint64_t i = 0; i < n_sids; ++i) mx = std::max(mx, sids[i]);
-  const uint32_t nbits = mx + 1;
-  std::vector<uint32_t> bm(((uint64_t)nbits + 31) / 32, 0u);
-  for (uint64_t i = 0; i < n_sids; ++i) bm[sids[i] >> 5] |= 1u << (sids[i] & 31);
-  void* d_bm;
-  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_M2, bm.size() * 4, &d_bm));
-  SHZ_HIP(ctx, shz_memcpy(ctx, d_bm, bm.data(), bm.size() * 4, hipMemcpyHostToDevice));
+  // the listed ids as a sorted list (a bitmap up to the largest id wrapped to no bits at id 2^32 - 1, and took id / 8 bytes)
+  std::vector<uint32_t> ids(sids, sids + n_sids);
+  std::sort(ids.begin(), ids.end());
+  ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
+  if (ids.size() >= (1ull << 32)) SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "delete_songs: every song id is listed; use shz_table_clear");
+  const uint32_t n_ids = (uint32_t)ids.size();
+  const bool answered = t->bucket || !t->done.empty();   // the table was finalized: it keeps answering when its last row leaves
+  void* d_ids;
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_M2, ids.size() * 4, &d_ids));
+  SHZ_HIP(ctx, shz_memcpy(ctx, d_ids, ids.data(), ids.size() * 4, hipMemcpyHostToDevice));
   SHZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
   uint64_t gone = 0;
   auto purge = [&](uint32_t* key, uint32_t* sid, uint32_t* off, uint64_t n, uint64_t* kept) -> int32_t {
     void* fl;
     SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_M0, std::max<uint64_t>(n, 1) * 4, &fl));
     hipLaunchKernelGGL(tbl_sid_keep_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream,
-                       (const uint32_t*)sid, n, (const uint32_t*)d_bm, nbits, (uint32_t*)fl);
+                       (const uint32_t*)sid, n, (const uint32_t*)d_ids, n_ids, (uint32_t*)fl);
     SHZ_HIP(ctx, hipGetLastError());
     return compact_cols(ctx, key, sid, off, n, (const uint32_t*)fl, kept);
   };
@@ -660,6 +680,7 @@ extern "C" int32_t shz_table_delete_songs(shz_table* t, const uint32_t* sids, ui
     t->ns = kept;
   }
   if (rows_deleted) *rows_deleted = gone;
+  if (answered) SHZ_TRY(empty_table_bucket(t));   // every segment may be gone: still a finalized table, of no rows
   return SHZ_OK;
 }
 
@@ -669,6 +690,7 @@ extern "C" int32_t shz_table_clear(shz_table* t) {
   SHZ_HIP(ctx, hipSetDevice(ctx->device));
   SHZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
   if (t->gx_stream) SHZ_HIP(ctx, hipStreamSynchronize(t->gx_stream));
+  const bool answered = t->bucket || !t->done.empty();   // a finalized table stays one: empty, and it answers
   for (shz_seg& g : t->done) {
     free_cols(g.slab, g.key, g.sid, g.off);
     if (g.bucket) (void)hipFree(g.bucket);
@@ -689,6 +711,7 @@ extern "C" int32_t shz_table_clear(shz_table* t) {
   t->ns = 0;
   t->max_sid = t->max_off = 0;
   t->broken = false;
+  if (answered) SHZ_TRY(empty_table_bucket(t));
   return SHZ_OK;
 }
 
@@ -743,12 +766,7 @@ extern "C" int32_t shz_table_finalize(shz_table* t) {
     SHZ_TRY(seal_staged(t, nullptr, 0, &packed));
     if (packed) {
       SHZ_TRY(flush_runs(t, true));
-      if (!t->bucket && t->n == 0 && t->done.empty()) {  // every row was a duplicate of nothing: still an empty table
-        SHZ_HIP(ctx, hipMalloc(&t->bucket, 2 * 4));
-        SHZ_HIP(ctx, hipMemsetAsync(t->bucket, 0, 8, ctx->stream));
-        t->nbuckets = 1;
-      }
-      return SHZ_OK;
+      return empty_table_bucket(t);   // no row came out of the runs: still an empty table
     }
     if (!t->runs.empty()) SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "song ids and offsets outgrew 32 bits while sealed runs were waiting");
   }
@@ -761,7 +779,8 @@ extern "C" int32_t shz_table_finalize(shz_table* t) {
     // batch fell below it (1.13e9-row batches against 2^31 left every segment half empty: 11 segments for 1.15e10 rows
     // instead of 6 -- and every query hash is looked up in every segment).
     const uint32_t S = 64;
-    const uint32_t m = (uint32_t)std::min<uint64_t>(S - 1, (t->seg_limit - t->n) * S / t->ns);
+    const uint64_t room = t->seg_limit > t->n ? t->seg_limit - t->n : 0;   // (the limit may have been lowered below the rows held)
+    const uint32_t m = (uint32_t)std::min<uint64_t>(S - 1, room * S / t->ns);
     if (m >= S / 16) {
       SHZ_TRY(drop_staged_duplicates_of_frozen(t, st_lo, st_hi));
       if (t->ns) {
@@ -810,14 +829,7 @@ extern "C" int32_t shz_table_finalize(shz_table* t) {
     freeze_active(t);   // what is still staged starts new segment(s)
   }
   SHZ_TRY(drop_staged_duplicates_of_frozen(t, st_lo, st_hi));    // UNIQUE(song_id, offset, hash) across segments
-  if (t->ns == 0) {
-    if (!t->bucket && t->n == 0 && t->done.empty()) {  // empty table: one empty bucket
-      SHZ_HIP(ctx, hipMalloc(&t->bucket, 2 * 4));
-      SHZ_HIP(ctx, hipMemsetAsync(t->bucket, 0, 8, ctx->stream));
-      t->nbuckets = 1;
-    }
-    return SHZ_OK;
-  }
+  if (t->ns == 0) return empty_table_bucket(t);   // (an empty table: one empty bucket)
   // staged rows go into the active segment if they fit; otherwise the active segment is frozen and the
   // staged rows are cut into slices BY KEY (all copies of a row land in the same slice, so duplicates
   // inside one batch are still removed), one new segment per slice
