@@ -432,6 +432,10 @@ uint64_t shz_recognize_estimate(uint64_t frames, uint32_t fan_value);
  * LDS table 2 queries instead of 32, so that tests reach the sub-batch border, the table's border and the direct global
  * adds with tiny inputs (results do not depend on the switch). */
 #define SHZ_DEBUG_FLOOR_SMALL 1024u
+/* Test switch of the song filter (shz_set_song_filter): with a filter set, a block of the two filter kernels holds 64 votes
+ * instead of 2,048 and a match sub-batch at most 3 queries, so that tests reach the block, wave and sub-batch borders with
+ * tiny inputs (results do not depend on the switch). */
+#define SHZ_DEBUG_FILTER_SMALL 2048u
 int32_t shz_set_debug(shz_ctx* ctx, uint32_t flags);
 /* The vote's tolerance, a setting of the context that holds for its later calls (default 0).  With c[sid][d] the votes of a
  * query per song and offset difference d = db_off - q_off, and S(sid, d) = the sum of c[sid][d .. d + bins]: a song's
@@ -473,6 +477,38 @@ int32_t shz_get_vote_floor(shz_ctx* ctx, uint32_t* on);
 int32_t shz_vote_floor_rows(shz_ctx* ctx, uint64_t* n);
 int32_t shz_vote_floor_take(shz_ctx* ctx, uint32_t* song_hist, uint32_t* bin_hist, uint64_t cap, uint64_t* n);
 int32_t shz_vote_bucket(uint32_t count, uint32_t* bucket);
+/* The song filter, a setting of the context that holds for its later calls (default: none): match within a set of songs.  A
+ * FILTERED MATCH ON A TABLE GIVES THE ARRAYS THAT THE PLAIN MATCH GIVES ON A TABLE HOLDING ONLY THE ALLOWED SONGS' ROWS.
+ * n_sets sets of song ids as a CSR: set s owns sids[set_off[s] .. set_off[s + 1]); ids in any order, repeats allowed; an
+ * empty set is legal (it allows nothing; with SHZ_FILTER_EXCLUDE it denies nothing).  n_sets = 0 clears the filter (sids,
+ * set_off and flags are not looked at).  Query q keeps the votes of song s iff bit(set(q), s) != exclude, where
+ * bit(set, s) = s is listed in the set and exclude = flags & SHZ_FILTER_EXCLUDE.  set(q) is set_of_query[q] in
+ * shz_match_batch_sets (and shz_match_device_host_sets) and set 0 EVERYWHERE ELSE: shz_match_batch, shz_match_device_host
+ * and every call that matches inside the library (shz_recognize_batch, shz_recognize_speeds / _warps, shz_scan_batch /
+ * _speeds / _warps, shz_listeners_push*, shz_match_songs / _warps), whose queries are windows, variants and listed songs the
+ * caller never sees.  While a filter is set: out_npairs counts the KEPT pairs; out_nhash is the query's alone, as ever;
+ * out_dedup keeps its meaning (a row belongs to one song); with the vote floor on, both histograms are those of the kept
+ * votes; shz_match_stats keeps counting the probed pairs.  shz_match_pairs and shz_pairs_vote (the sharded match) return
+ * SHZ_E_UNSUPPORTED while a filter is set: nothing ignores it silently.  With no filter set nothing changes.
+ * The library builds one bitmap per set on the host, words = largest listed id / 32 + 1 for all sets (a song id beyond the
+ * bitmap counts as not listed), and keeps them in a device block the context owns until the filter is cleared, replaced or
+ * the context destroyed; the filter belongs to no table.  The votes then go one way, as under a tolerance: 8-byte votes in
+ * one pass over a sub-batch; between the expand and the sort a stable compaction drops the barred votes (a count kernel, a
+ * scan of the block counts, a write kernel) and the kept total is read back -- one more small round trip a vote pass; then
+ * the full sort and the fold over runs at the tolerance in force.
+ * Refused, the previous setting staying in force: a NULL ctx, a NULL set_off, a NULL sids with ids listed, set_off[0] != 0,
+ * a set_off that decreases, flag bits other than SHZ_FILTER_EXCLUDE (SHZ_E_INVALID); bitmaps of more than 2^31 bytes
+ * together (SHZ_E_UNSUPPORTED); no memory for them (SHZ_E_NOMEM).
+ * shz_get_song_filter: the sets, the flags and the ids listed over all sets as given (each pointer may be NULL).
+ * shz_match_batch_sets: shz_match_batch with the set of every query; SHZ_E_STATE with no filter set, SHZ_E_INVALID for a
+ * NULL set_of_query or an entry >= n_sets, both before anything is launched. */
+#define SHZ_FILTER_EXCLUDE 1u
+int32_t shz_set_song_filter(shz_ctx* ctx, const uint32_t* sids, const uint64_t* set_off, uint32_t n_sets, uint32_t flags);
+int32_t shz_get_song_filter(shz_ctx* ctx, uint32_t* n_sets, uint32_t* flags, uint64_t* n_ids);
+int32_t shz_match_batch_sets(shz_ctx* ctx, shz_table* t, const uint32_t* key32, const uint32_t* q_off,
+                             const uint64_t* query_off, uint32_t n_queries, uint32_t topn, uint32_t flags,
+                             uint32_t* out_sid, int32_t* out_delta, uint32_t* out_aligned, uint32_t* out_dedup,
+                             uint32_t* out_nres, uint32_t* out_nhash, uint64_t* out_npairs, const uint32_t* set_of_query);
 int32_t shz_match_vt_redo(shz_ctx* ctx, uint64_t* count);
 /* A single query of at most 8,192 hashes handed over in host memory has its vote kernels queued before the number of its
  * votes is known (they do nothing when it exceeds 32,768; the call then continues as for any other query): how many
@@ -495,6 +531,12 @@ int32_t shz_match_device_host(shz_ctx* ctx, shz_table* t, const uint32_t* key32,
                               const uint64_t* query_off, uint32_t n_queries, uint32_t topn, uint32_t flags, int64_t bias_bound,
                               uint32_t* out_sid, int32_t* out_delta, uint32_t* out_aligned, uint32_t* out_dedup,
                               uint32_t* out_nres, uint32_t* out_nhash, uint64_t* out_npairs);
+/* ... with the set of every query under a song filter, as shz_match_batch_sets takes and refuses it (tests / tools). */
+int32_t shz_match_device_host_sets(shz_ctx* ctx, shz_table* t, const uint32_t* key32, const uint32_t* q_off,
+                                   const uint64_t* query_off, uint32_t n_queries, uint32_t topn, uint32_t flags,
+                                   int64_t bias_bound, uint32_t* out_sid, int32_t* out_delta, uint32_t* out_aligned,
+                                   uint32_t* out_dedup, uint32_t* out_nres, uint32_t* out_nhash, uint64_t* out_npairs,
+                                   const uint32_t* set_of_query);
 /* Which of the table's own songs are the same recording: every listed song matched against the REST of the table in one
  * call, without its audio.  shz_table_song_hashes gathers the songs' rows on the device (song sids[q] is query q, its
  * offsets are the query offsets), the library's match on device columns runs on them with topn + 1 and the table's largest

@@ -19,7 +19,7 @@ from time import time
 import numpy as np
 
 from . import _ffi
-from ._ffi import HOP, NFFT, Context, ShzError, Table, takes_delta_tol  # noqa: F401
+from ._ffi import HOP, NFFT, Context, ShzError, Table, takes_delta_tol, takes_song_filter  # noqa: F401
 
 # reference constants (__init__.py:41-51, recognizer.py:21-38,40-58,68)
 RATE = 44100
@@ -340,6 +340,7 @@ def _recognize_fused(queries, chans, owner, db, Fs, topn, resample_to=None, floo
                      "n_matches": res["npairs"], "n_hashes": res["nhash"]}
 
 
+@takes_song_filter(lambda *a, **k: (k["db"] if "db" in k else a[1]).ctx)
 @takes_delta_tol(lambda *a, **k: (k["db"] if "db" in k else a[1]).ctx)
 def recognize_batch(queries, db, Fs: int = RATE, topn: int = TOPN, fused: bool = False, resample_to: int = None,
                     extents: bool = False, floor: bool = False):
@@ -358,7 +359,10 @@ def recognize_batch(queries, db, Fs: int = RATE, topn: int = TOPN, fused: bool =
     floor: the first result dict of every query gains "floor": {"song_hist", "bin_hist"} -- the query's two vote-floor
     histograms ([32] uint32, Context.floor) -- and {"expected_above", "score"} -- what shazam_amd.floor.expected_above / score
     make of song_hist and the query's best aligned count (a heuristic; None where nothing can be fitted).  The other entries
-    do not change; either path, with resample_to and delta_tol."""
+    do not change; either path, with resample_to and delta_tol.
+    songs= / exclude= (keywords, song ids): the queries are matched within / without these songs (Context.songs,
+    Table.match(songs=)): the results of the same call on a database holding only the allowed songs, "n_matches" counting
+    the kept pairs; either path; the unsharded table only (a sharded database: NotImplementedError)."""
     if extents and fused:
         raise ValueError("extents=True needs the query's hashes on the host: not with fused=True")
     ctx = db.ctx
@@ -392,14 +396,15 @@ def recognize_batch(queries, db, Fs: int = RATE, topn: int = TOPN, fused: bool =
 
 
 def recognize(channels_or_samples, db=None, Fs: int = RATE, topn: int = TOPN, fused: bool = False, resample_to: int = None,
-              delta_tol: int = None, extents: bool = False, floor: bool = False):
+              delta_tol: int = None, extents: bool = False, floor: bool = False, songs=None, exclude=None):
     """recognizer.py:377-396: (final_results, fingerprint_time, query_time, align_time).  fused, resample_to, delta_tol,
-    extents, floor: see recognize_batch."""
+    extents, floor, songs, exclude: see recognize_batch."""
     if db is None:
         raise ValueError("recognize() needs the HipFingerprintDB holding the fingerprints")
     x = channels_or_samples
     q = [np.asarray(x)] if (not isinstance(x, (list, tuple)) or (len(x) and np.isscalar(x[0]))) else list(x)
-    results, tm = recognize_batch([q], db, Fs, topn, fused, resample_to, extents, floor, delta_tol=delta_tol)
+    results, tm = recognize_batch([q], db, Fs, topn, fused, resample_to, extents, floor, delta_tol=delta_tol, songs=songs,
+                                  exclude=exclude)
     return results[0], tm["fingerprint_time"], tm["query_time"], tm["align_time"]
 
 

@@ -25,6 +25,8 @@ DEBUG_VOTE_TOLERANT_ROUTE = 128   # the vote: the tolerant route at tolerance 0 
 DEBUG_EXTENT_SMALL_TILES = 256   # shz_match_extents: tiles of 64 pairs, 4 descriptors in LDS, 3 queries a sub-batch
 DEBUG_REPEAT_SMALL_SLICES = 512  # shz_repeats_* / shz_shared_*: one recording (job) a slice, expand tiles of 64 pairs, blocks of 64 elements
 DEBUG_FLOOR_SMALL = 1024         # the vote floor: at most 3 queries a match sub-batch, 2 queries in the histogram kernels' LDS table
+DEBUG_FILTER_SMALL = 2048        # the song filter: filter kernels' blocks of 64 votes, at most 3 queries a match sub-batch
+FILTER_EXCLUDE = 1               # shz_set_song_filter: the listed songs are barred (SHZ_FILTER_EXCLUDE)
 SHARED_LAG_BIAS = 1 << 20        # shz_shared_*: cell_lag = lag + SHARED_LAG_BIAS (SHZ_SHARED_LAG_BIAS)
 SCAN_NO_WARP = 0xFFFFFFFF            # shz_scan_warps: out_best of a window that tried no variant
 SCAN_U32, SCAN_POPC64, SCAN_U64 = 0, 1, 2   # shz_scan_host kinds
@@ -87,6 +89,11 @@ SIGNATURES = {
     "shz_get_vote_tolerance": (C.c_int32, [vp, u32p]),
     "shz_set_vote_floor": (C.c_int32, [vp, C.c_uint32]),
     "shz_get_vote_floor": (C.c_int32, [vp, u32p]),
+    "shz_set_song_filter": (C.c_int32, [vp, vp, vp, C.c_uint32, C.c_uint32]),
+    "shz_get_song_filter": (C.c_int32, [vp, u32p, u32p, u64p]),
+    "shz_match_batch_sets": (C.c_int32, [vp, vp, vp, vp, u64p, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "shz_match_device_host_sets": (C.c_int32, [vp, vp, vp, vp, u64p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int64, vp, vp, vp, vp,
+                                               vp, vp, vp, vp]),
     "shz_vote_floor_rows": (C.c_int32, [vp, u64p]),
     "shz_vote_floor_take": (C.c_int32, [vp, vp, vp, C.c_uint64, u64p]),
     "shz_vote_bucket": (C.c_int32, [C.c_uint32, u32p]),
@@ -294,6 +301,41 @@ def takes_delta_tol(ctx_of):
     return deco
 
 
+def _song_ids(a):
+    """any iterable of song ids -> a contiguous uint32 array"""
+    v = np.asarray(a if isinstance(a, np.ndarray) else sorted(a) if isinstance(a, (set, frozenset)) else list(a))
+    if v.size and (v.min() < 0 or v.max() >= 1 << 32):
+        raise ValueError("song ids must fit 32 bits")
+    return np.ascontiguousarray(v.reshape(-1), np.uint32)
+
+
+def _song_sets(sets):
+    """one iterable of ids, or a list of iterables -> a list of uint32 arrays (a sequence whose entries are all iterable is
+    a list of sets; an empty one is ONE empty set)"""
+    if isinstance(sets, np.ndarray) and sets.ndim <= 1:
+        return [_song_ids(sets)]
+    sets = list(sets)
+    if sets and all(hasattr(a, "__iter__") for a in sets):
+        return [_song_ids(a) for a in sets]
+    return [_song_ids(sets)]
+
+
+def takes_song_filter(ctx_of):
+    """Decorator: the function gains the keywords songs=None and exclude=None -- song ids the call matches within / without
+    (Context.songs: the song filter while it runs, the previous one afterwards; both None: the context stays as it is; both
+    given: ValueError).  The library-internal queries of the call (windows, variants) all use the one set.  ctx_of(*args,
+    **kw) finds the Context among its arguments."""
+    def deco(fn):
+        @functools.wraps(fn)
+        def run(*args, songs=None, exclude=None, **kw):
+            if songs is None and exclude is None:
+                return fn(*args, **kw)
+            with ctx_of(*args, **kw).songs(only=songs, exclude=exclude):
+                return fn(*args, **kw)
+        return run
+    return deco
+
+
 class ShzError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"libshz error {code}: {msg}")
@@ -409,7 +451,8 @@ class Context:
         the tolerant route at tolerance 0 too, 256: the extent kernel works in tiles of 64 pairs with 4 descriptors in LDS and
         sub-batches of 3 queries, 512: shz_repeats_* works in slices of one recording, expand tiles of 64 pairs and blocks of
         64 elements, 1024: with the vote floor on, match sub-batches of at most 3 queries and histogram kernels with 2
-        queries in LDS)."""
+        queries in LDS, 2048: with a song filter set, filter kernels whose blocks hold 64 votes and match sub-batches of at
+        most 3 queries)."""
         self.check(lib().shz_set_debug(self.h, int(flags)))
 
     def set_vote_tolerance(self, bins: int):
@@ -485,6 +528,63 @@ class Context:
             self.set_vote_floor(False)      # drops the leftovers
             if before:
                 self.set_vote_floor(True)
+
+    # ---- the song filter (shz_set_song_filter) ---------------------------------------------
+    def set_song_filter(self, sets, exclude=False):
+        """Every later match of this context votes within a set of songs (shz_set_song_filter): the result arrays are those
+        of the plain match on a table holding only the allowed songs' rows.  sets: one iterable of song ids, or a list of
+        iterables (several sets: Table.match(song_sets=, set_of=) says which query uses which; every other call uses set
+        0).  exclude: the listed songs are the barred ones.  An empty set allows nothing (exclude: bars nothing).  Ids in
+        any order, repeats allowed.  The unsharded table only.  A refused call leaves the previous filter in force."""
+        lists = _song_sets(sets)
+        off = np.zeros(len(lists) + 1, np.uint64)
+        off[1:] = np.cumsum([len(a) for a in lists], dtype=np.uint64)
+        ids = np.ascontiguousarray(np.concatenate(lists) if lists else np.zeros(0, np.uint32), np.uint32)
+        self.check(lib().shz_set_song_filter(self.h, ptr(ids), ptr(off), len(lists), FILTER_EXCLUDE if exclude else 0))
+        self._song_filter = (lists, bool(exclude)) if lists else None
+
+    def clear_song_filter(self):
+        """No song filter (the default): every song of the table is matched."""
+        self.check(lib().shz_set_song_filter(self.h, None, None, 0, 0))
+        self._song_filter = None
+
+    @property
+    def song_filter(self):
+        """None, or {"n_sets", "exclude", "n_ids"} of the filter in force (shz_get_song_filter)."""
+        n, f, ids = C.c_uint32(), C.c_uint32(), C.c_uint64()
+        self.check(lib().shz_get_song_filter(self.h, C.byref(n), C.byref(f), C.byref(ids)))
+        if n.value == 0:
+            return None
+        return {"n_sets": n.value, "exclude": bool(f.value & FILTER_EXCLUDE), "n_ids": ids.value}
+
+    @contextlib.contextmanager
+    def songs(self, only=None, exclude=None, sets=None):
+        """with ctx.songs(only=ids) / ctx.songs(exclude=ids) / ctx.songs(sets=[ids, ...]): the song filter inside the block,
+        the previous one after it (also after an exception; the wrapper keeps the lists it last sent).  With sets=,
+        exclude=True makes every set a list of barred songs.  All three None: the context stays as it is.  only= together
+        with an exclude= list, or with sets=: ValueError."""
+        deny_list = exclude is not None and not isinstance(exclude, (bool, np.bool_))
+        if only is not None and (deny_list or sets is not None):
+            raise ValueError("songs(): only= goes without exclude= and without sets=")
+        if sets is not None and deny_list:
+            raise ValueError("songs(): with sets=, exclude is True or False")
+        if only is None and sets is None and not deny_list:
+            yield self
+            return
+        before = getattr(self, "_song_filter", None)
+        if sets is not None:
+            self.set_song_filter([_song_ids(a) for a in sets], exclude=bool(exclude))
+        elif only is not None:
+            self.set_song_filter([_song_ids(only)])
+        else:
+            self.set_song_filter([_song_ids(exclude)], exclude=True)
+        try:
+            yield self
+        finally:
+            if before is None:
+                self.clear_song_filter()
+            else:
+                self.set_song_filter(before[0], exclude=before[1])
 
     def vt_redo_count(self) -> int:
         n = C.c_uint64()
@@ -1954,42 +2054,69 @@ class Table:
         self.ctx.check(lib().shz_table_allgather(self.h, comm.h, C.byref(b)))
         return b.value
 
-    def match(self, key32, q_off, query_off, topn=2, full_sort=False, delta_tol=None, floor=False):
+    def _filter_of(self, nq, songs, exclude, song_sets, set_of):
+        """the arguments of Context.songs() for a match call, and the uint32 map of its queries (None: set 0)"""
+        if (song_sets is None) != (set_of is None):
+            raise ValueError("song_sets= and set_of= go together")
+        if song_sets is not None and (songs is not None or (exclude is not None and not isinstance(exclude, bool))):
+            raise ValueError("song_sets= goes without songs= and without an exclude= list (exclude=True bars the listed songs)")
+        if song_sets is None:
+            return dict(only=songs, exclude=exclude), None
+        m = np.ascontiguousarray(set_of, np.uint32).reshape(-1)
+        if len(m) != nq:
+            raise ValueError(f"set_of has {len(m)} entries for {nq} queries")
+        return dict(sets=list(song_sets), exclude=bool(exclude)), m
+
+    def match(self, key32, q_off, query_off, topn=2, full_sort=False, delta_tol=None, floor=False, songs=None, exclude=None,
+              song_sets=None, set_of=None):
         """Batched return_matches + align_matches.  Returns dict of arrays (see shz.h).  full_sort: the vote as one
         sort of 8-byte votes + record chain (SHZ_MATCH_FULL_SORT), the form the faster vote paths are tested against.
         delta_tol: the vote tolerance of this call (Context.tolerance); None: the context's.  floor: the result gains
         song_hist and bin_hist, [n_queries, 32] uint32 (Context.floor, shazam_amd.floor); the other arrays do not change.  Rows
-        that a context with the floor switched on by hand had recorded before are dropped (Context.floor)."""
+        that a context with the floor switched on by hand had recorded before are dropped (Context.floor).
+        songs= / exclude= (song ids): the match within / without these songs, one set for all queries (Context.songs; the
+        arrays of a plain match on a table of the allowed songs' rows only; npairs counts the kept pairs).  song_sets= (a
+        list of id lists) with set_of= (a set index per query): per-query sets (shz_match_batch_sets); exclude=True bars
+        the listed songs.  The context's own filter is back in force afterwards."""
         k = np.ascontiguousarray(key32, np.uint32)
         o = np.ascontiguousarray(q_off, np.uint32)
         qo = np.ascontiguousarray(query_off, np.uint64)
         nq = len(qo) - 1
         res = _match_result(nq, topn)
-        with self.ctx.tolerance(delta_tol), self.ctx.floor(floor):
+        filt, smap = self._filter_of(nq, songs, exclude, song_sets, set_of)
+        with self.ctx.tolerance(delta_tol), self.ctx.floor(floor), self.ctx.songs(**filt):
             before = self.ctx.floor_rows() if floor else 0
-            self.ctx.check(lib().shz_match_batch(self.ctx.h, self.h, ptr(k), ptr(o), qo.ctypes.data_as(u64p), nq, topn,
-                                                 MATCH_FULL_SORT if full_sort else 0,
-                                                 ptr(res["sid"]), ptr(res["delta"]), ptr(res["aligned"]), ptr(res["dedup"]),
-                                                 ptr(res["nres"]), ptr(res["nhash"]), ptr(res["npairs"])))
+            args = (self.ctx.h, self.h, ptr(k), ptr(o), qo.ctypes.data_as(u64p), nq, topn, MATCH_FULL_SORT if full_sort else 0,
+                    ptr(res["sid"]), ptr(res["delta"]), ptr(res["aligned"]), ptr(res["dedup"]), ptr(res["nres"]), ptr(res["nhash"]),
+                    ptr(res["npairs"]))
+            if smap is None:
+                self.ctx.check(lib().shz_match_batch(*args))
+            else:
+                self.ctx.check(lib().shz_match_batch_sets(*args, ptr(smap)))
             if floor:
                 _floor_into(self.ctx, res, before, nq)
         return res
 
-    def match_device(self, key32, q_off, query_off, topn=2, full_sort=False, bias_bound=-1, floor=False):
+    def match_device(self, key32, q_off, query_off, topn=2, full_sort=False, bias_bound=-1, floor=False, songs=None, exclude=None,
+                     song_sets=None, set_of=None, delta_tol=None):
         """match() the way the fused calls and the listeners run it (shz_match_device_host): the two columns are put on the
         device first and matched there, with the caller's bound of the query offsets (below 0 or >= 2^32: none).  For tests
-        and tools; same result arrays as match() (floor: as there)."""
+        and tools; same result arrays as match() (floor, songs, exclude, song_sets, set_of, delta_tol: as there)."""
         k = np.ascontiguousarray(key32, np.uint32)
         o = np.ascontiguousarray(q_off, np.uint32)
         qo = np.ascontiguousarray(query_off, np.uint64)
         nq = len(qo) - 1
         res = _match_result(nq, topn)
-        with self.ctx.floor(floor):
+        filt, smap = self._filter_of(nq, songs, exclude, song_sets, set_of)
+        with self.ctx.tolerance(delta_tol), self.ctx.floor(floor), self.ctx.songs(**filt):
             before = self.ctx.floor_rows() if floor else 0
-            self.ctx.check(lib().shz_match_device_host(self.ctx.h, self.h, ptr(k), ptr(o), qo.ctypes.data_as(u64p), nq, topn,
-                                                       MATCH_FULL_SORT if full_sort else 0, int(bias_bound),
-                                                       ptr(res["sid"]), ptr(res["delta"]), ptr(res["aligned"]), ptr(res["dedup"]),
-                                                       ptr(res["nres"]), ptr(res["nhash"]), ptr(res["npairs"])))
+            args = (self.ctx.h, self.h, ptr(k), ptr(o), qo.ctypes.data_as(u64p), nq, topn, MATCH_FULL_SORT if full_sort else 0,
+                    int(bias_bound), ptr(res["sid"]), ptr(res["delta"]), ptr(res["aligned"]), ptr(res["dedup"]), ptr(res["nres"]),
+                    ptr(res["nhash"]), ptr(res["npairs"]))
+            if smap is None:
+                self.ctx.check(lib().shz_match_device_host(*args))
+            else:
+                self.ctx.check(lib().shz_match_device_host_sets(*args, ptr(smap)))
             if floor:
                 _floor_into(self.ctx, res, before, nq)
         return res

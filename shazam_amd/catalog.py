@@ -119,7 +119,9 @@ def match_songs(db_or_table, sids, topn: int = 5, full_sort: bool = False, speed
     first (shz_match_songs_warps): the arrays gain a warp axis behind the song axis ([n, n_warps, topn] / [n, n_warps]),
     "tempo_q16" / "pitch_q16" [n_warps] name the pairs, rows stay the unwarped counts, nhash is the distinct warped rows
     and delta is the found song's frame under the listed song's WARPED frame 0.
-    delta_tol= (keyword): the vote tolerance in offset bins while the call runs (Context.tolerance); None: the context's."""
+    delta_tol= (keyword): the vote tolerance in offset bins while the call runs (Context.tolerance); None: the context's.
+    A song filter is taken from the context: run the call inside `with ctx.songs(only=...)` / `ctx.songs(exclude=...)` to match
+    within / without a set of songs (every variant, every listed song uses the one set)."""
     table, _ = _table_of(db_or_table)
     lad = _ladder_of(speeds, tempos, pitches, warps)
     if lad is None:
@@ -462,6 +464,8 @@ def find_duplicates(db_or_table, sids=None, topn: int = 5, min_aligned: int = No
     thresholds default to MIN_ALIGNED_WARPED / MIN_COVERAGE_WARPED.  Put 65536 on the ladder (speed_ladder does) to keep
     the exact copies in the same answer.  timings (ladder only): "ms" = (gather, warp, match) device times, summed.
     delta_tol= (keyword): the vote tolerance in offset bins while the call runs (Context.tolerance); None: the context's.
+    A song filter is taken from the context: run the call inside `with ctx.songs(only=...)` / `ctx.songs(exclude=...)` to match
+    within / without a set of songs (every variant, every listed song uses the one set).
     extents: "pairs" gains a_first, a_last, b_first, b_last (EXTENT_PAIR_FIELDS; pair_extents): where in a and where in b the
     aligned rows lie -- the position of an excerpt inside the longer track, the length of an overlap.  extents=True does not
     take a ladder.

@@ -358,6 +358,7 @@ extern "C" int32_t shz_ctx_destroy(shz_ctx* ctx) {
   if (ctx->d_np_comp) (void)hipFree(ctx->d_np_comp);
   if (ctx->d_twiddle) (void)hipFree(ctx->d_twiddle);
   if (ctx->d_sine_lut) (void)hipFree(ctx->d_sine_lut);
+  if (ctx->d_filter) (void)hipFree(ctx->d_filter);   // shz_set_song_filter
   if (ctx->twin) { (void)shz_ctx_destroy(ctx->twin); ctx->twin = nullptr; }
   if (ctx->ev_twin) (void)hipEventDestroy(ctx->ev_twin);
   if (ctx->mail) (void)hipHostFree(ctx->mail);

@@ -123,6 +123,8 @@ enum {
   SHZ_WS_RP_OUT,     // ... a slice's kept cells: rec | lag | block | pairs | first | last
   SHZ_WS_SH_EL,      // ... the join between two recordings (shz_shared_*; it uses the RP slots with items in the place of elements and
                      // jobs in the place of recordings): the element of every item
+  SHZ_WS_FS_BLK,     // shz_table.hip, the song filter (shz_set_song_filter): kept total | kept votes of every block | their scan
+  SHZ_WS_FS_MAP,     // ... the set of every query of the sub-batch (shz_match_batch_sets)
   SHZ_WS_COUNT
 };
 
@@ -167,6 +169,11 @@ struct shz_ctx {
   uint32_t vote_tol = 0;        // shz_set_vote_tolerance: neighbouring offset bins a song's aligned count sums over (0 .. 31)
   uint32_t vote_floor = 0;      // shz_set_vote_floor: every query handed to the match records a row of two histograms
   std::vector<uint32_t> floor_rows;   // ... the rows not yet taken, in query order: song_hist[32] | bin_hist[32] each (256 bytes)
+  // shz_set_song_filter: one bitmap of filter_words words per set, set-major, in a device block of the context's own (not a
+  // workspace slot: it outlives every call); NULL and filter_sets == 0 while no filter is set
+  uint32_t* d_filter = nullptr;
+  uint32_t filter_sets = 0, filter_words = 0, filter_flags = 0;
+  uint64_t filter_ids = 0;      // ids listed over all sets, as given (shz_get_song_filter)
   // extraction stats: cells fp32 peak picking left undecided, of those decided on fp64 values, frames recomputed for
   // that, passes repeated with fp64 staging
   uint64_t st_und = 0, st_und_f64 = 0, st_und_ffts = 0, st_fallbacks = 0;
@@ -261,7 +268,7 @@ int32_t shz_sort_u32_widen(shz_ctx* ctx, uint32_t* k0, uint32_t* k1, uint64_t* o
 int32_t shz_match_device(shz_ctx* ctx, shz_table* t, const uint32_t* d_key32, const uint32_t* d_q_off, const uint64_t* query_off,
                          uint32_t n_queries, uint32_t topn, uint32_t flags, int64_t bias_bound, uint32_t* out_sid,
                          int32_t* out_delta, uint32_t* out_aligned, uint32_t* out_dedup, uint32_t* out_nres, uint32_t* out_nhash,
-                         uint64_t* out_npairs);
+                         uint64_t* out_npairs, const uint32_t* set_of_query = nullptr);   // (host; NULL: set 0 of a song filter)
 int32_t shz_match_ready(shz_ctx* ctx, shz_table* t, uint32_t topn);
 // the vote floor (shz_set_vote_floor): n zero rows, for a caller that skips the match because nothing is to be looked up (its
 // rows must line up with its result arrays).  Nothing while the floor is off

@@ -2207,11 +2207,138 @@ static int32_t vote_fold_tol(shz_ctx* ctx, const uint64_t* vs, uint64_t P, uint3
   return vote_rank(ctx, P, nq, mb, topn, qstart, d_G, (const uint64_t*)gh, (const uint32_t*)gd, (const uint32_t*)gdd, r);
 }
 
+// ---- the song filter (shz_set_song_filter): between the expand and the sort of the one 8-byte pass, the votes of the songs
+// outside their query's set are dropped by a stable compaction -- kept votes of every block (fs_count_kernel), their scan,
+// the kept votes in order (fs_write_kernel).  A block holds FS_BLOCK votes, a wave a quarter of them in FS_ROUNDS rounds of
+// 64 lanes x 2 votes (one 16-byte load a lane); ranks inside a round come from two 64-bit ballots, the waves' bases from LDS.
+// A vote costs its 8 bytes read twice and one bitmap word (L2: 128 KB a set at 1M songs), a kept vote 8 bytes written.
+#define FS_BLOCK 2048u
+#define FS_SMALL_BLOCK 64u   // SHZ_DEBUG_FILTER_SMALL
+#define FS_SMALL_Q 3u        // queries of a match sub-batch under SHZ_DEBUG_FILTER_SMALL
+#define FS_ROUNDS 4          // = FS_BLOCK / 4 waves / 128 votes
+struct fs_view {
+  const uint64_t* v;         // the P expanded votes, query-major (16-byte aligned)
+  uint64_t P;
+  const uint32_t* bm;        // [n_sets][words] bitmaps
+  const uint32_t* set_of;    // the set of every query of the sub-batch, NULL: set 0
+  uint32_t words, exclude, nq, bv;   // bv: votes of a block
+  int sshift, qshift;        // dbits + 1; sb + dbits + 1
+  uint64_t smask;            // mask(sb)
+};
+// does the vote stay?  *q = its query (a query index the layout cannot hold keeps nothing and counts nowhere)
+__device__ __forceinline__ bool fs_keep(const fs_view& F, uint64_t v, uint32_t* q) {
+  const uint32_t qq = (uint32_t)(v >> F.qshift);
+  *q = qq;
+  if (qq >= F.nq) return false;
+  const uint32_t sid = (uint32_t)((v >> F.sshift) & F.smask), w = sid >> 5;
+  uint32_t bit = 0;   // an id beyond the bitmap is not listed
+  if (w < F.words) bit = (F.bm[(uint64_t)(F.set_of ? F.set_of[qq] : 0u) * F.words + w] >> (sid & 31)) & 1u;
+  return bit != F.exclude;
+}
+// round r of a wave: lane l holds the votes i, i + 1 with i = w0 + 128 r + 2 l, dead beyond `end`
+__device__ __forceinline__ void fs_load(const fs_view& F, uint64_t i, uint64_t end, uint64_t* a, uint64_t* b, bool* la, bool* lb) {
+  *la = i < end;
+  *lb = i + 1 < end;
+  *a = *b = 0;
+  if (*lb) {
+    const ulonglong2 x = *(const ulonglong2*)(F.v + i);
+    *a = x.x;
+    *b = x.y;
+  } else if (*la) {
+    *a = F.v[i];
+  }
+}
+// the kept votes of a round that spans several queries: one add per query present
+__device__ __forceinline__ void fs_add_runs(uint32_t q, bool keep, uint32_t lane, unsigned long long* __restrict__ npairs) {
+  uint64_t todo = __ballot(keep);
+  while (todo) {
+    const int l = __ffsll((unsigned long long)todo) - 1;
+    const uint32_t qq = (uint32_t)__shfl((int)q, l, 64);
+    const uint64_t m = __ballot(keep && q == qq);
+    if ((int)lane == l) atomicAdd(npairs + qq, (unsigned long long)__popcll(m));
+    todo &= ~m;
+  }
+}
+__global__ __launch_bounds__(256) void fs_count_kernel(fs_view F, uint32_t* __restrict__ blk_cnt,
+                                                       unsigned long long* __restrict__ npairs /*zeroed*/) {
+  __shared__ uint32_t s_w[4];
+  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wc = F.bv >> 2;
+  const uint64_t w0 = (uint64_t)blockIdx.x * F.bv + (uint64_t)wave * wc;
+  const uint64_t end = w0 + wc < F.P ? w0 + wc : F.P;
+  uint32_t c = 0, acc_q = 0, acc_n = 0;   // acc: kept votes of the run of query acc_q not yet added (uniform in the wave)
+#pragma unroll
+  for (int r = 0; r < FS_ROUNDS; ++r) {
+    uint64_t a, b;
+    bool la, lb;
+    uint32_t qa = 0, qb = 0;
+    fs_load(F, w0 + 128ull * r + 2ull * lane, end, &a, &b, &la, &lb);
+    const bool ka = la && fs_keep(F, a, &qa), kb = lb && fs_keep(F, b, &qb);
+    const uint64_t ma = __ballot(ka), mb = __ballot(kb);
+    const uint32_t n = (uint32_t)(__popcll(ma) + __popcll(mb));
+    if (n) {   // uniform
+      const uint32_t qf = ma ? (uint32_t)__shfl((int)qa, __ffsll((unsigned long long)ma) - 1, 64)
+                             : (uint32_t)__shfl((int)qb, __ffsll((unsigned long long)mb) - 1, 64);
+      if ((__ballot(ka && qa != qf) | __ballot(kb && qb != qf)) == 0) {   // one query: the run goes on
+        if (qf != acc_q) {
+          if (lane == 0 && acc_n) atomicAdd(npairs + acc_q, (unsigned long long)acc_n);
+          acc_q = qf;
+          acc_n = 0;
+        }
+        acc_n += n;
+      } else {
+        if (lane == 0 && acc_n) atomicAdd(npairs + acc_q, (unsigned long long)acc_n);
+        acc_n = 0;
+        fs_add_runs(qa, ka, lane, npairs);
+        fs_add_runs(qb, kb, lane, npairs);
+      }
+    }
+    c += n;
+  }
+  if (lane == 0 && acc_n) atomicAdd(npairs + acc_q, (unsigned long long)acc_n);
+  if (lane == 0) s_w[wave] = c;
+  __syncthreads();
+  if (threadIdx.x == 0) blk_cnt[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+}
+__global__ __launch_bounds__(256) void fs_write_kernel(fs_view F, const uint32_t* __restrict__ blk_pos, uint64_t* __restrict__ out) {
+  __shared__ uint32_t s_w[4];
+  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wc = F.bv >> 2;
+  const uint64_t w0 = (uint64_t)blockIdx.x * F.bv + (uint64_t)wave * wc;
+  const uint64_t end = w0 + wc < F.P ? w0 + wc : F.P;
+  const uint64_t below = (1ull << lane) - 1ull;
+  uint64_t a[FS_ROUNDS], b[FS_ROUNDS];
+  uint32_t keep = 0, c = 0;   // keep: bit 2 r = the round's first vote stays, bit 2 r + 1 = its second
+#pragma unroll
+  for (int r = 0; r < FS_ROUNDS; ++r) {
+    bool la, lb;
+    uint32_t q = 0;
+    fs_load(F, w0 + 128ull * r + 2ull * lane, end, &a[r], &b[r], &la, &lb);
+    const bool ka = la && fs_keep(F, a[r], &q), kb = lb && fs_keep(F, b[r], &q);
+    keep |= (ka ? 1u : 0u) << (2 * r) | (kb ? 2u : 0u) << (2 * r);
+    c += (uint32_t)(__popcll(__ballot(ka)) + __popcll(__ballot(kb)));
+  }
+  if (lane == 0) s_w[wave] = c;
+  __syncthreads();
+  uint64_t base = blk_pos[blockIdx.x];
+  for (uint32_t w = 0; w < wave; ++w) base += s_w[w];
+#pragma unroll
+  for (int r = 0; r < FS_ROUNDS; ++r) {
+    const bool ka = (keep >> (2 * r)) & 1u, kb = (keep >> (2 * r + 1)) & 1u;
+    const uint64_t ma = __ballot(ka), mb = __ballot(kb);
+    const uint64_t pos = base + (uint64_t)(__popcll(ma & below) + __popcll(mb & below));   // lane order, a before b
+    if (ka && pos < F.P) out[pos] = a[r];
+    if (kb && pos + (ka ? 1u : 0u) < F.P) out[pos + (ka ? 1u : 0u)] = b[r];
+    base += (uint64_t)(__popcll(ma) + __popcll(mb));
+  }
+}
+
 // the tolerance of this context's votes, or -1 for the plain fold of one bin (SHZ_DEBUG_VOTE_TOLERANT_ROUTE: the tolerant
 // fold at 0 bins too; the vote floor: its histograms are taken from the tolerant fold's runs and records, at the tolerance
-// in force -- at 0 bins that fold computes the plain fold's results)
+// in force -- at 0 bins that fold computes the plain fold's results; a song filter, shz_set_song_filter: the one 8-byte pass
+// is where its compaction sits)
 static int vote_tol_of(const shz_ctx* ctx) {
-  return (ctx->vote_tol > 0 || ctx->vote_floor || (ctx->debug & SHZ_DEBUG_VOTE_TOLERANT_ROUTE)) ? (int)ctx->vote_tol : -1;
+  return (ctx->vote_tol > 0 || ctx->vote_floor || ctx->filter_sets || (ctx->debug & SHZ_DEBUG_VOTE_TOLERANT_ROUTE))
+             ? (int)ctx->vote_tol
+             : -1;
 }
 
 // the full sort: sort the packed 8-byte votes, then vote_fold (tol < 0) or vote_fold_tol.  v0 holds the P votes, v1 is
@@ -2511,6 +2638,10 @@ struct match_call {
   // query order -- handed to the context's store when the whole call succeeded
   bool floor;
   std::vector<uint32_t> floor_rows;
+  // the song filter (shz_set_song_filter; refused with a sink): on for this call, and the set of every query (host,
+  // shz_match_batch_sets), NULL: set 0
+  bool filter = false;
+  const uint32_t* set_of = nullptr;
 };
 enum sub_next {
   SUB_GO,          // on to the next stage
@@ -2540,6 +2671,7 @@ struct match_sub {
   // counts (sub_read_counts)
   void* mail;                // control block | votes per query | result block of a queued fold
   uint64_t mu, P, nx, rows_total;
+  uint64_t kept;             // the votes that were folded: P, or what the song filter left of them
   uint32_t ng;
   std::vector<uint64_t> votes;   // per query
   double tr[4];              // SHZ_TRACE_MATCH: start, head queued, counts back, votes queued
@@ -2800,7 +2932,7 @@ static int32_t sub_read_counts(const match_call& mc, match_sub& s, sub_next* nex
   }
   s.ng = (uint32_t)h.ng;
   s.nx = (uint64_t)s.ng * mc.nseg;   // sub-groups: (query, key) group x segment
-  s.P = h.P;
+  s.P = s.kept = h.P;
   s.rows_total = 0;
   for (int i = 0; i < M_ROW_STRIPES; ++i) s.rows_total += ((const uint64_t*)mail)[16 + i];
   ctx->m_votes_per_hash = mc.t->votes_per_hash = (double)s.P / (double)s.mu;
@@ -2842,8 +2974,43 @@ static int32_t vote_to_sink(const match_call& mc, const match_sub& s) {
 // the vote buffers of the passes of a plan: v0 | (4-byte votes: a second buffer at v0 + pmax4 entries), v1
 struct vote_bufs { void *v0, *v1; uint64_t pmax4; };
 
+// the song filter on the pp expanded votes in v_in (the one 8-byte pass: all queries of the sub-batch, query index from 0):
+// the kept votes, in order, into v_out; the kept pairs of every query into the sub-batch's npairs words; *kept = their
+// total, read back -- the second small round trip of this route (the sort and the fold are sized by it)
+static int32_t vote_filter(const match_call& mc, const match_sub& s, const uint64_t* v_in, uint64_t* v_out, uint64_t pp,
+                           uint64_t* kept) {
+  shz_ctx* ctx = mc.ctx;
+  const uint32_t bv = (ctx->debug & SHZ_DEBUG_FILTER_SMALL) ? FS_SMALL_BLOCK : FS_BLOCK;
+  const uint64_t nb = (pp + bv - 1) / bv;
+  void *blk, *mail;
+  SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_FS_BLK, 8 + nb * 8, &blk));
+  uint64_t* d_kept = (uint64_t*)blk;
+  uint32_t *cnt = (uint32_t*)(d_kept + 1), *pos = cnt + nb;
+  const uint32_t* d_map = nullptr;
+  if (mc.set_of) {
+    void* p;
+    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_FS_MAP, (uint64_t)s.nq * 4, &p));
+    SHZ_HIP(ctx, shz_memcpy(ctx, p, mc.set_of + s.q0, (uint64_t)s.nq * 4, hipMemcpyHostToDevice));
+    d_map = (const uint32_t*)p;
+  }
+  const fs_view F{v_in, pp, ctx->d_filter, d_map, ctx->filter_words, (ctx->filter_flags & SHZ_FILTER_EXCLUDE) ? 1u : 0u, s.nq, bv,
+                  s.mb.dbits + 1, s.mb.sb + s.mb.dbits + 1, (1ull << s.mb.sb) - 1ull};
+  SHZ_HIP(ctx, hipMemsetAsync(s.r.npairs, 0, (uint64_t)s.nq * 8, ctx->stream));
+  hipLaunchKernelGGL(fs_count_kernel, dim3((uint32_t)nb), dim3(256), 0, ctx->stream, F, cnt, (unsigned long long*)s.r.npairs);
+  SHZ_HIP(ctx, hipGetLastError());
+  SHZ_TRY(shz_scan_u32(ctx, cnt, pos, nb, d_kept));
+  hipLaunchKernelGGL(fs_write_kernel, dim3((uint32_t)nb), dim3(256), 0, ctx->stream, F, (const uint32_t*)pos, v_out);
+  SHZ_HIP(ctx, hipGetLastError());
+  SHZ_TRY(shz_mailbox(ctx, 8, &mail));
+  SHZ_HIP(ctx, hipMemcpyAsync(mail, d_kept, 8, hipMemcpyDeviceToHost, ctx->stream));
+  SHZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  *kept = *(const uint64_t*)mail;
+  if (*kept > pp) SHZ_FAIL(ctx, SHZ_E_HIP, "song filter: %llu of %llu votes kept", (unsigned long long)*kept, (unsigned long long)pp);
+  return SHZ_OK;
+}
+
 // one pass of the plan: expand its votes, then sort / fold / rank as the route says, into the rows of its first query
-static int32_t vote_run_pass(const match_call& mc, const match_sub& s, const vote_plan& plan, const vote_pass& vp,
+static int32_t vote_run_pass(const match_call& mc, match_sub& s, const vote_plan& plan, const vote_pass& vp,
                              const uint32_t* tile_x, const vote_bufs& b) {
   shz_ctx* ctx = mc.ctx;
   const uint32_t topn = mc.topn, nqp = vp.qb - vp.qa;
@@ -2892,6 +3059,11 @@ static int32_t vote_run_pass(const match_call& mc, const match_sub& s, const vot
     case ROUTE_SORT64:
     case ROUTE_TOLERANT:
       SHZ_TRY(expand_votes<uint64_t>(mc, s, tile_x, vp.v_lo, vp.v_hi, mbp, (int64_t)0, (uint64_t*)b.v0));
+      if (mc.filter) {   // (always ROUTE_TOLERANT, vote_tol_of: the one pass over the sub-batch)
+        SHZ_TRY(vote_filter(mc, s, (const uint64_t*)b.v0, (uint64_t*)b.v1, pp, &s.kept));
+        if (s.kept == 0) return SHZ_OK;   // the probe zeroed the result rows, and a floor row stays zero
+        return vote_tail(ctx, (uint64_t*)b.v1, (uint64_t*)b.v0, s.kept, nqp, mbp, topn, s.tol, d_G, r);
+      }
       return vote_tail(ctx, (uint64_t*)b.v0, (uint64_t*)b.v1, pp, nqp, mbp, topn, plan.route == ROUTE_TOLERANT ? s.tol : -1, d_G,
                        r);
     default:
@@ -2900,7 +3072,7 @@ static int32_t vote_run_pass(const match_call& mc, const match_sub& s, const vot
 }
 
 // the votes of a sub-batch, by the plan's route: vote buffers, the expand tiles' starts for all passes, then pass by pass
-static int32_t sub_vote(const match_call& mc, const match_sub& s, const vote_plan& plan) {
+static int32_t sub_vote(const match_call& mc, match_sub& s, const vote_plan& plan) {
   shz_ctx* ctx = mc.ctx;
   if (plan.route == ROUTE_SINK) return vote_to_sink(mc, s);
   const std::vector<vote_pass>& passes = plan.passes;
@@ -2981,7 +3153,7 @@ static int32_t sub_commit(match_call& mc, const match_sub& s, vote_route route, 
   ctx->st_pairs += s.P;
   ctx->st_keys += s.ng;
   if (nq == 1) {
-    if (mc.out_npairs) mc.out_npairs[q0] = s.P;
+    if (mc.out_npairs) mc.out_npairs[q0] = s.kept;   // (P but under a song filter)
     if (mc.out_nhash) mc.out_nhash[q0] = (uint32_t)s.mu;
   } else {
     if (mc.out_npairs) memcpy(mc.out_npairs + q0, h.npairs, (uint64_t)nq * 8);
@@ -3054,6 +3226,8 @@ static int32_t match_core(match_call& mc) {
   mc.floor = ctx->vote_floor && !mc.sink;   // (shz_match_pairs votes nothing: its votes' rows are shz_pairs_vote's)
   mc.floor_rows.clear();
   if (mc.floor && (ctx->debug & SHZ_DEBUG_FLOOR_SMALL)) step = std::min<uint32_t>(step, FH_SMALL_Q);
+  mc.filter = ctx->filter_sets != 0 && !mc.sink;   // (shz_match_pairs refuses a filter before it gets here)
+  if (mc.filter && (ctx->debug & SHZ_DEBUG_FILTER_SMALL)) step = std::min<uint32_t>(step, FS_SMALL_Q);
   bool redo = false;
   for (uint32_t q0 = 0; q0 < mc.n_queries;) {
     match_sub s{};
@@ -3087,27 +3261,51 @@ extern "C" int32_t shz_match_batch(shz_ctx* ctx, shz_table* t, const uint32_t* k
   return match_core(mc);
 }
 
+// what shz_match_batch_sets / shz_match_device_host_sets refuse before anything is launched
+static int32_t match_sets_check(shz_ctx* ctx, const char* who, uint32_t n_queries, const uint32_t* set_of_query) {
+  if (!ctx->filter_sets) SHZ_FAIL(ctx, SHZ_E_STATE, "%s: no song filter is set (shz_set_song_filter)", who);
+  if (n_queries && !set_of_query) SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: set_of_query is NULL", who);
+  for (uint32_t q = 0; q < n_queries; ++q)
+    if (set_of_query[q] >= ctx->filter_sets)
+      SHZ_FAIL(ctx, SHZ_E_INVALID, "%s: query %u asks for set %u of %u", who, q, set_of_query[q], ctx->filter_sets);
+  return SHZ_OK;
+}
+
+extern "C" int32_t shz_match_batch_sets(shz_ctx* ctx, shz_table* t, const uint32_t* key32, const uint32_t* q_off,
+                                        const uint64_t* query_off, uint32_t n_queries, uint32_t topn, uint32_t flags,
+                                        uint32_t* out_sid, int32_t* out_delta, uint32_t* out_aligned, uint32_t* out_dedup,
+                                        uint32_t* out_nres, uint32_t* out_nhash, uint64_t* out_npairs,
+                                        const uint32_t* set_of_query) {
+  if (!ctx || !t) return SHZ_E_INVALID;
+  SHZ_TRY(match_sets_check(ctx, "shz_match_batch_sets", n_queries, set_of_query));
+  match_call mc{ctx, t, key32, q_off, query_off, n_queries, topn, flags, out_sid, out_delta, out_aligned, out_dedup,
+                out_nres, out_nhash, out_npairs, nullptr};
+  mc.set_of = set_of_query;
+  return match_core(mc);
+}
+
 // match_core on query columns that are already on the device and belong to the library (the fused recognise call, the
 // listeners): query_off is the host's; bias_bound >= every q_off, or < 0 where the caller knows none
 int32_t shz_match_device(shz_ctx* ctx, shz_table* t, const uint32_t* d_key32, const uint32_t* d_q_off, const uint64_t* query_off,
                          uint32_t n_queries, uint32_t topn, uint32_t flags, int64_t bias_bound, uint32_t* out_sid,
                          int32_t* out_delta, uint32_t* out_aligned, uint32_t* out_dedup, uint32_t* out_nres, uint32_t* out_nhash,
-                         uint64_t* out_npairs) {
+                         uint64_t* out_npairs, const uint32_t* set_of_query) {
   match_call mc{ctx, t, d_key32, d_q_off, query_off, n_queries, topn, (flags & SHZ_MATCH_FULL_SORT) | SHZ_IN_DEVICE, out_sid,
                 out_delta, out_aligned, out_dedup, out_nres, out_nhash, out_npairs, nullptr};
   mc.has_bias_bound = bias_bound >= 0 && bias_bound < (int64_t)1 << 32;
   mc.bias_bound = mc.has_bias_bound ? (uint32_t)bias_bound : 0u;
   mc.pack_small = true;
+  mc.set_of = set_of_query;   // (host; NULL from every caller inside the library: set 0)
   return match_core(mc);
 }
 
 // tests / tools: shz_match_device on HOST columns -- copied into device buffers of this call's own (not the workspace, which
 // the match uses), handed to shz_match_device as its callers hand theirs, freed afterwards.  Nothing else is added: the
 // bound, the flags and the outputs go through as they are.
-extern "C" int32_t shz_match_device_host(shz_ctx* ctx, shz_table* t, const uint32_t* key32, const uint32_t* q_off,
-                                         const uint64_t* query_off, uint32_t n_queries, uint32_t topn, uint32_t flags,
-                                         int64_t bias_bound, uint32_t* out_sid, int32_t* out_delta, uint32_t* out_aligned,
-                                         uint32_t* out_dedup, uint32_t* out_nres, uint32_t* out_nhash, uint64_t* out_npairs) {
+static int32_t match_device_host(shz_ctx* ctx, shz_table* t, const uint32_t* key32, const uint32_t* q_off,
+                                 const uint64_t* query_off, uint32_t n_queries, uint32_t topn, uint32_t flags, int64_t bias_bound,
+                                 uint32_t* out_sid, int32_t* out_delta, uint32_t* out_aligned, uint32_t* out_dedup,
+                                 uint32_t* out_nres, uint32_t* out_nhash, uint64_t* out_npairs, const uint32_t* set_of_query) {
   if (!ctx || !t) return SHZ_E_INVALID;
   if (flags & ~SHZ_MATCH_FULL_SORT) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_match_device_host: flags may hold SHZ_MATCH_FULL_SORT");
   if (n_queries && !query_off) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_match_device_host: query_off is NULL");
@@ -3129,11 +3327,29 @@ extern "C" int32_t shz_match_device_host(shz_ctx* ctx, shz_table* t, const uint3
   }
   if (rc == SHZ_OK)
     rc = shz_match_device(ctx, t, (const uint32_t*)d_key, (const uint32_t*)d_qo, query_off, n_queries, topn, flags, bias_bound,
-                          out_sid, out_delta, out_aligned, out_dedup, out_nres, out_nhash, out_npairs);
+                          out_sid, out_delta, out_aligned, out_dedup, out_nres, out_nhash, out_npairs, set_of_query);
   (void)hipStreamSynchronize(ctx->stream);   // (a refused call may have queued work that reads the columns)
   (void)hipFree(d_key);
   (void)hipFree(d_qo);
   return rc;
+}
+extern "C" int32_t shz_match_device_host(shz_ctx* ctx, shz_table* t, const uint32_t* key32, const uint32_t* q_off,
+                                         const uint64_t* query_off, uint32_t n_queries, uint32_t topn, uint32_t flags,
+                                         int64_t bias_bound, uint32_t* out_sid, int32_t* out_delta, uint32_t* out_aligned,
+                                         uint32_t* out_dedup, uint32_t* out_nres, uint32_t* out_nhash, uint64_t* out_npairs) {
+  return match_device_host(ctx, t, key32, q_off, query_off, n_queries, topn, flags, bias_bound, out_sid, out_delta, out_aligned,
+                           out_dedup, out_nres, out_nhash, out_npairs, nullptr);
+}
+// ... with the set of every query, as shz_match_batch_sets takes it (and refuses it)
+extern "C" int32_t shz_match_device_host_sets(shz_ctx* ctx, shz_table* t, const uint32_t* key32, const uint32_t* q_off,
+                                              const uint64_t* query_off, uint32_t n_queries, uint32_t topn, uint32_t flags,
+                                              int64_t bias_bound, uint32_t* out_sid, int32_t* out_delta, uint32_t* out_aligned,
+                                              uint32_t* out_dedup, uint32_t* out_nres, uint32_t* out_nhash, uint64_t* out_npairs,
+                                              const uint32_t* set_of_query) {
+  if (!ctx || !t) return SHZ_E_INVALID;
+  SHZ_TRY(match_sets_check(ctx, "shz_match_device_host_sets", n_queries, set_of_query));
+  return match_device_host(ctx, t, key32, q_off, query_off, n_queries, topn, flags, bias_bound, out_sid, out_delta, out_aligned,
+                           out_dedup, out_nres, out_nhash, out_npairs, set_of_query);
 }
 
 // what match_core refuses before it launches anything, for callers that must know before they change state of their own
@@ -3160,6 +3376,7 @@ extern "C" int32_t shz_match_pairs(shz_ctx* ctx, shz_table* t, const uint32_t* k
                                    uint64_t* d_pairs, uint64_t cap, uint64_t* count, uint32_t* out_nhash,
                                    uint64_t* out_npairs) {
   if (!ctx || !count) return SHZ_E_INVALID;
+  if (ctx->filter_sets) SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "shz_match_pairs: a song filter is set (shz_set_song_filter): the sharded match does not apply it");
   if (cap && !d_pairs) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_match_pairs: NULL buffer");
   if (nshards == 0 || shard >= nshards) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_match_pairs: shard %u of %u", shard, nshards);
   if (sid_bits < 1 || delta_bits < 1 || delta_bits > 32 ||
@@ -3194,6 +3411,65 @@ extern "C" int32_t shz_set_vote_floor(shz_ctx* ctx, uint32_t on) {
   if (!ctx) return SHZ_E_INVALID;
   ctx->vote_floor = on ? 1u : 0u;
   if (!on) std::vector<uint32_t>().swap(ctx->floor_rows);   // off: the rows not taken are dropped
+  return SHZ_OK;
+}
+// the song filter: one bitmap per set, built on the host, in a device block of the context's own.  Every refusal leaves the
+// previous setting in force: the new block replaces the old one only when it is complete
+extern "C" int32_t shz_set_song_filter(shz_ctx* ctx, const uint32_t* sids, const uint64_t* set_off, uint32_t n_sets, uint32_t flags) {
+  if (!ctx) return SHZ_E_INVALID;
+  if (flags & ~SHZ_FILTER_EXCLUDE) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_set_song_filter: flags may hold SHZ_FILTER_EXCLUDE");
+  uint64_t n_ids = 0, words = 0;
+  if (n_sets) {
+    if (!set_off) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_set_song_filter: set_off is NULL");
+    if (set_off[0] != 0) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_set_song_filter: set_off[0] is %llu, not 0", (unsigned long long)set_off[0]);
+    for (uint32_t i = 0; i < n_sets; ++i)
+      if (set_off[i + 1] < set_off[i]) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_set_song_filter: set_off decreases at set %u", i);
+    n_ids = set_off[n_sets];
+    if (n_ids && !sids) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_set_song_filter: sids is NULL");
+    uint32_t top = 0;
+    for (uint64_t i = 0; i < n_ids; ++i) top = std::max(top, sids[i]);
+    words = n_ids ? (uint64_t)top / 32 + 1 : 0;
+    if (words * n_sets * 4 > (1ull << 31))
+      SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "shz_set_song_filter: %u bitmaps of %llu words exceed 2^31 bytes", n_sets, (unsigned long long)words);
+  }
+  SHZ_HIP(ctx, hipSetDevice(ctx->device));
+  void* d_new = nullptr;
+  if (n_sets) {
+    std::vector<uint32_t> bm;
+    try {
+      bm.assign(std::max<uint64_t>(words * n_sets, 1), 0u);
+    } catch (const std::bad_alloc&) {
+      SHZ_FAIL(ctx, SHZ_E_NOMEM, "shz_set_song_filter: no host memory for %llu bitmap words", (unsigned long long)(words * n_sets));
+    }
+    for (uint32_t s = 0; s < n_sets; ++s)
+      for (uint64_t i = set_off[s]; i < set_off[s + 1]; ++i) bm[(uint64_t)s * words + sids[i] / 32] |= 1u << (sids[i] & 31);
+    if (hipMalloc(&d_new, bm.size() * 4) != hipSuccess) {
+      (void)hipGetLastError();
+      SHZ_FAIL(ctx, SHZ_E_NOMEM, "shz_set_song_filter: hipMalloc(%llu) failed", (unsigned long long)(bm.size() * 4));
+    }
+    if (shz_memcpy(ctx, d_new, bm.data(), bm.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
+        hipStreamSynchronize(ctx->stream) != hipSuccess) {
+      (void)hipGetLastError();
+      (void)hipFree(d_new);
+      SHZ_FAIL(ctx, SHZ_E_HIP, "shz_set_song_filter: upload of the bitmaps failed");
+    }
+  }
+  if (ctx->d_filter) {
+    (void)hipStreamSynchronize(ctx->stream);   // (nothing queued reads the old block any more)
+    (void)hipFree(ctx->d_filter);
+  }
+  ctx->d_filter = (uint32_t*)d_new;
+  ctx->filter_sets = n_sets;
+  ctx->filter_words = (uint32_t)words;
+  ctx->filter_flags = n_sets ? flags : 0u;
+  ctx->filter_ids = n_ids;
+  return SHZ_OK;
+}
+extern "C" int32_t shz_get_song_filter(shz_ctx* ctx, uint32_t* n_sets, uint32_t* flags, uint64_t* n_ids) {
+  if (!ctx) return SHZ_E_INVALID;
+  if (n_sets) *n_sets = ctx->filter_sets;
+  if (flags) *flags = ctx->filter_flags;
+  if (n_ids) *n_ids = ctx->filter_ids;
   return SHZ_OK;
 }
 extern "C" int32_t shz_get_vote_floor(shz_ctx* ctx, uint32_t* on) {
@@ -3371,6 +3647,7 @@ extern "C" int32_t shz_pairs_vote(shz_ctx* ctx, uint64_t* d_pairs, uint64_t n, u
                                   uint32_t delta_bits, uint32_t bias, uint32_t topn, uint32_t* out_sid, int32_t* out_delta,
                                   uint32_t* out_aligned, uint32_t* out_dedup, uint32_t* out_nres) {
   if (!ctx) return SHZ_E_INVALID;
+  if (ctx->filter_sets) SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "shz_pairs_vote: a song filter is set (shz_set_song_filter): the sharded match does not apply it");
   if (n_queries == 0) return SHZ_OK;
   if (!out_sid || !out_delta || !out_aligned || !out_dedup || !out_nres) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_pairs_vote: NULL output");
   if (topn < 1 || topn > 64) SHZ_FAIL(ctx, SHZ_E_INVALID, "topn must be in [1,64]");

@@ -174,12 +174,17 @@ class HipFingerprintDB:
         hexes = hex_of_keys(self.ctx, k)
         return [(h.upper(), int(a), int(b)) for h, a, b in zip(hexes, s.tolist(), o.tolist())]  # HEX() upper-cases
 
-    def match(self, key32, q_off, query_off, topn=2, delta_tol=None, floor=False):
+    def match(self, key32, q_off, query_off, topn=2, delta_tol=None, floor=False, songs=None, exclude=None, song_sets=None,
+              set_of=None):
         """Table.match / ShardedTable.match of the finalized table.  delta_tol: the vote tolerance of this call, None: the
-        context's.  floor: the result gains song_hist / bin_hist (Table.match)."""
+        context's.  floor: the result gains song_hist / bin_hist (Table.match).  songs / exclude / song_sets / set_of: the
+        match within a set of songs (Table.match); the unsharded table only (a sharded database: NotImplementedError)."""
         self.finalize()
+        filt = {k: v for k, v in (("songs", songs), ("exclude", exclude), ("song_sets", song_sets), ("set_of", set_of)) if v is not None}
+        if filt and not hasattr(self.table, "h"):
+            raise NotImplementedError("songs= / exclude= / song_sets= take the unsharded table (shards=1)")
         with self.ctx.tolerance(delta_tol):
-            return self.table.match(key32, q_off, query_off, topn, floor=floor)
+            return self.table.match(key32, q_off, query_off, topn, floor=floor, **filt)
 
     def match_extents(self, key32, q_off, query_off, cand_sid, d_lo, d_hi, cand_n=None, hist=True):
         """Table.match_extents of the finalized table: where the aligned hashes of the candidates lie; one table only."""

@@ -211,7 +211,11 @@ class ShardedTable:
         floor: the result gains song_hist / bin_hist as ``Table.match``'s does -- the histograms of the gathered votes
         (shz_pairs_vote records them; with a communicator every rank gets them), equal to the unsharded table's.
         With the floor on (this argument, or Context.set_vote_floor by hand) the call takes the context's row store whole: rows
-        recorded before it and not yet taken are dropped (Context.floor)."""
+        recorded before it and not yet taken are dropped (Context.floor).
+        A song filter (Context.songs, shz_set_song_filter) is not applied by the sharded match: while the context has one
+        set the call raises NotImplementedError."""
+        if self.ctx.song_filter is not None:            # (shz_match_pairs / shz_pairs_vote refuse it too: nothing ignores it)
+            raise NotImplementedError("the context has a song filter set (Context.songs): it takes the unsharded table")
         if delta_tol is not None or floor:
             with self.ctx.tolerance(delta_tol), self.ctx.floor(floor):
                 return self.match(key32, q_off, query_off, topn)

@@ -139,11 +139,15 @@ class StreamRecognizer:
     of the window's peaks paired among themselves, not bit for bit the plain listener's.
 
     delta_tol: the vote tolerance in offset bins of this recogniser's matches, held for its lifetime and set around every push
-    (Context.tolerance); None: whatever the context holds at the push."""
+    (Context.tolerance); None: whatever the context holds at the push.
+
+    songs= / exclude= (song ids; at most one of them): this recogniser's listeners are matched within / without these songs.
+    The lists are held for its lifetime and every push runs inside Context.songs() -- host and device=True alike, a ladder
+    included; both None: whatever filter the context holds at the push.  The unsharded table only."""
 
     def __init__(self, db, n_listeners: int, channels: int = 1, window_seconds: float = 5, topn: int = TOPN,
                  fan_value: int = 5, amp_min=10, device: bool = False, fs_in: int = None, speeds=None, warps=None,
-                 delta_tol: int = None):
+                 delta_tol: int = None, songs=None, exclude=None):
         if speeds is not None and warps is not None:
             raise ValueError("speeds= and warps= exclude each other: a speed is the warp (s, s)")
         if (speeds is not None or warps is not None) and not device:
@@ -151,6 +155,12 @@ class StreamRecognizer:
         self.ladder = None if speeds is None and warps is None else _ladder_of(speeds, warps)
         self.last_best = self.last_profile = None
         self.delta_tol = None if delta_tol is None else int(delta_tol)
+        if songs is not None and exclude is not None:
+            raise ValueError("songs= and exclude= exclude each other")
+        if (songs is not None or exclude is not None) and not hasattr(db.table, "h"):
+            raise NotImplementedError("songs= / exclude= take the unsharded table (shards=1)")
+        self.songs = None if songs is None else _ffi._song_ids(songs)
+        self.exclude = None if exclude is None else _ffi._song_ids(exclude)
         self.db, self.n, self.channels, self.topn = db, int(n_listeners), int(channels), int(topn)
         self.fp = StreamFingerprinter(self.n * self.channels, RATE, fan_value, amp_min, db.ctx, fs_in)
         self.window_frames = int(float(window_seconds) * RATE / self.fp.streams.hop)
@@ -181,7 +191,7 @@ class StreamRecognizer:
         """chunks_per_listener[l]: list of `channels` 1-D int16 arrays (a bare array when channels == 1; None: nothing).
         end: listeners whose channels all end after this chunk.  Returns [(results, w0)] per listener.  speeds / warps:
         this push's ladder, for a recogniser created with one."""
-        with self.db.ctx.tolerance(self.delta_tol):
+        with self.db.ctx.tolerance(self.delta_tol), self.db.ctx.songs(only=self.songs, exclude=self.exclude):
             return self._push(chunks_per_listener, end, speeds, warps)
 
     def _push(self, chunks_per_listener, end, speeds, warps):
