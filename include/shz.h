@@ -509,6 +509,29 @@ int32_t shz_match_batch_sets(shz_ctx* ctx, shz_table* t, const uint32_t* key32, 
                              const uint64_t* query_off, uint32_t n_queries, uint32_t topn, uint32_t flags,
                              uint32_t* out_sid, int32_t* out_delta, uint32_t* out_aligned, uint32_t* out_dedup,
                              uint32_t* out_nres, uint32_t* out_nhash, uint64_t* out_npairs, const uint32_t* set_of_query);
+/* The key cap, a setting of the context that holds for its later calls (default 0: off): keys that hold too many table rows
+ * vote for nobody.  WITH CAP c >= 1 A MATCH GIVES THE ARRAYS THAT THE PLAIN MATCH GIVES ON A TABLE LACKING EVERY ROW WHOSE KEY
+ * HOLDS MORE THAN c ROWS.  The rows of a key are counted over all segments together (the distinct (key, song, offset) rows
+ * that shz_table_export shows); a key with exactly c rows stays.  The cap is a property of table and cap, not of the query:
+ * a key is dropped for every query or for none.  out_sid / delta / aligned / dedup / nres / npairs and the vote floor's
+ * histograms describe the kept votes; out_nhash is the query's alone, as ever.  It is decided at the probe: one kernel
+ * between the probe and the scan of its counts zeroes the counts of the dropped (query, key) groups, so the expand, the
+ * sort and the fold never see their votes, on every route, and no host round trip is added.  shz_match_stats: pairs are
+ * those expanded (after the cap), rows_scanned stay as probed.  Every call that matches inside the library follows it (the
+ * list at shz_set_vote_tolerance), and so do shz_match_pairs -- a key lives on one shard, so the sharded match applies the
+ * cap exactly -- and shz_match_extents / _fit, whose counts, frames, histograms and moments then cover kept pairs only.
+ * With the cap off every call launches the kernels it launched before.  Changing the cap forgets the context's estimate of
+ * votes per hash that sizes the next sub-batch.
+ * shz_key_cap_stats: the (query, key) groups and the pairs dropped by the last match call, over all its sub-batches (both
+ * 0 with the cap off; each pointer may be NULL).
+ * shz_table_key_hist: the key sizes of a table's finalized rows (SHZ_E_STATE with staged rows): keys[b] = the distinct keys
+ * whose row count falls into bucket b of shz_vote_bucket (1 .. 16 exact, then powers of two), rows[b] = the rows they hold,
+ * *max_rows = the largest key, *n_keys = the distinct keys (both may be NULL).  An empty table gives zeros.  One kernel per
+ * segment over its sorted key column; a key that several segments hold is counted once, with the rows of all. */
+int32_t shz_set_key_cap(shz_ctx* ctx, uint64_t rows);
+int32_t shz_get_key_cap(shz_ctx* ctx, uint64_t* rows);
+int32_t shz_key_cap_stats(shz_ctx* ctx, uint64_t* groups_dropped, uint64_t* pairs_dropped);
+int32_t shz_table_key_hist(shz_table* t, uint64_t keys[32], uint64_t rows[32], uint64_t* max_rows, uint64_t* n_keys);
 int32_t shz_match_vt_redo(shz_ctx* ctx, uint64_t* count);
 /* A single query of at most 8,192 hashes handed over in host memory has its vote kernels queued before the number of its
  * votes is known (they do nothing when it exceeds 32,768; the call then continues as for any other query): how many

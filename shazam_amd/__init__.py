@@ -19,7 +19,7 @@ from time import time
 import numpy as np
 
 from . import _ffi
-from ._ffi import HOP, NFFT, Context, ShzError, Table, takes_delta_tol, takes_song_filter  # noqa: F401
+from ._ffi import HOP, NFFT, Context, ShzError, Table, takes_delta_tol, takes_key_cap, takes_song_filter  # noqa: F401
 
 # reference constants (__init__.py:41-51, recognizer.py:21-38,40-58,68)
 RATE = 44100
@@ -340,6 +340,7 @@ def _recognize_fused(queries, chans, owner, db, Fs, topn, resample_to=None, floo
                      "n_matches": res["npairs"], "n_hashes": res["nhash"]}
 
 
+@takes_key_cap(lambda *a, **k: (k["db"] if "db" in k else a[1]).ctx)
 @takes_song_filter(lambda *a, **k: (k["db"] if "db" in k else a[1]).ctx)
 @takes_delta_tol(lambda *a, **k: (k["db"] if "db" in k else a[1]).ctx)
 def recognize_batch(queries, db, Fs: int = RATE, topn: int = TOPN, fused: bool = False, resample_to: int = None,
@@ -362,7 +363,11 @@ def recognize_batch(queries, db, Fs: int = RATE, topn: int = TOPN, fused: bool =
     do not change; either path, with resample_to and delta_tol.
     songs= / exclude= (keywords, song ids): the queries are matched within / without these songs (Context.songs,
     Table.match(songs=)): the results of the same call on a database holding only the allowed songs, "n_matches" counting
-    the kept pairs; either path; the unsharded table only (a sharded database: NotImplementedError)."""
+    the kept pairs; either path; the unsharded table only (a sharded database: NotImplementedError).
+    max_key_rows= (keyword): the key cap of this call (Context.key_cap: keys that hold more table rows vote for nobody;
+    shazam_amd.keycap.cap_for picks one from Table.key_hist()); either path, sharded or not; with extents, the extents cover
+    the kept pairs.  None: the context's.  recognize_speeds / recognize_warps, find_duplicates / match_songs, the listeners
+    and match_extents have no such keyword: run them inside `with ctx.key_cap(rows):`."""
     if extents and fused:
         raise ValueError("extents=True needs the query's hashes on the host: not with fused=True")
     ctx = db.ctx
@@ -396,15 +401,15 @@ def recognize_batch(queries, db, Fs: int = RATE, topn: int = TOPN, fused: bool =
 
 
 def recognize(channels_or_samples, db=None, Fs: int = RATE, topn: int = TOPN, fused: bool = False, resample_to: int = None,
-              delta_tol: int = None, extents: bool = False, floor: bool = False, songs=None, exclude=None):
+              delta_tol: int = None, extents: bool = False, floor: bool = False, songs=None, exclude=None, max_key_rows=None):
     """recognizer.py:377-396: (final_results, fingerprint_time, query_time, align_time).  fused, resample_to, delta_tol,
-    extents, floor, songs, exclude: see recognize_batch."""
+    extents, floor, songs, exclude, max_key_rows: see recognize_batch."""
     if db is None:
         raise ValueError("recognize() needs the HipFingerprintDB holding the fingerprints")
     x = channels_or_samples
     q = [np.asarray(x)] if (not isinstance(x, (list, tuple)) or (len(x) and np.isscalar(x[0]))) else list(x)
     results, tm = recognize_batch([q], db, Fs, topn, fused, resample_to, extents, floor, delta_tol=delta_tol, songs=songs,
-                                  exclude=exclude)
+                                  exclude=exclude, max_key_rows=max_key_rows)
     return results[0], tm["fingerprint_time"], tm["query_time"], tm["align_time"]
 
 
@@ -417,6 +422,8 @@ from .scan import scan, scan_windows  # noqa: E402,F401
 # queries played fast or slow (csrc/shz_speed.hip): the peaks warped for every factor of a ladder, all variants in one match
 from .speed import (pitch_ladder, recognize_speeds, recognize_warps, speed_ladder, tempo_ladder, warp_grid,  # noqa: E402,F401
                     warp_hashes, warp_hashes_tf)
+# the key cap's arithmetic on a table's key-size histogram (Table.key_hist)
+from . import keycap  # noqa: E402,F401
 # the catalogue against itself (csrc/shz_catalog.hip): the rows of listed songs as queries, duplicates and excerpts among them
 from .catalog import find_duplicates, fold_pairs, fold_pairs_warps, match_songs  # noqa: E402,F401
 # repeated content inside recordings, no catalogue (csrc/shz_repeat.hip): the lag histogram of a recording against itself

@@ -140,6 +140,10 @@ SIGNATURES = {
     "shz_recognize_estimate": (C.c_uint64, [C.c_uint64, C.c_uint32]),
     "shz_match_stats": (C.c_int32, [vp, u64p, u64p, u64p]),
     "shz_set_debug": (C.c_int32, [vp, C.c_uint32]),
+    "shz_set_key_cap": (C.c_int32, [vp, C.c_uint64]),
+    "shz_get_key_cap": (C.c_int32, [vp, u64p]),
+    "shz_key_cap_stats": (C.c_int32, [vp, u64p, u64p]),
+    "shz_table_key_hist": (C.c_int32, [vp, vp, vp, u64p, u64p]),
     "shz_match_vt_redo": (C.c_int32, [vp, u64p]),
     "shz_match_spec_stats": (C.c_int32, [vp, u64p, u64p]),
     "shz_comm_unique_id": (C.c_int32, [vp]),
@@ -336,6 +340,43 @@ def takes_song_filter(ctx_of):
     return deco
 
 
+def takes_key_cap(ctx_of):
+    """Decorator: the function gains the keyword max_key_rows=None -- the key cap that holds while it runs (Context.key_cap:
+    keys that hold more table rows vote for nobody; 0: off; None: the context stays as it is).  ctx_of(*args, **kw) finds the
+    Context among its arguments."""
+    def deco(fn):
+        @functools.wraps(fn)
+        def run(*args, max_key_rows=None, **kw):
+            if max_key_rows is None:
+                return fn(*args, **kw)
+            with ctx_of(*args, **kw).key_cap(max_key_rows):
+                return fn(*args, **kw)
+        return run
+    return deco
+
+
+class _KeyCap(int):
+    """Context.key_cap: the cap in force as an int, and -- called with a cap -- the block that sets it for a while."""
+
+    def __new__(cls, ctx, rows):
+        self = super().__new__(cls, rows)
+        self._ctx = ctx
+        return self
+
+    @contextlib.contextmanager
+    def __call__(self, rows):
+        ctx = self._ctx
+        if rows is None:
+            yield ctx
+            return
+        before = int(ctx.key_cap)
+        ctx.set_key_cap(rows)
+        try:
+            yield ctx
+        finally:
+            ctx.set_key_cap(before)
+
+
 class ShzError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"libshz error {code}: {msg}")
@@ -481,6 +522,33 @@ class Context:
             yield self
         finally:
             self.set_vote_tolerance(before)
+
+    # ---- the key cap (shz_set_key_cap) -----------------------------------------------------
+    def set_key_cap(self, rows: int):
+        """Every later match of this context leaves out the keys that hold more than `rows` table rows, counted over all
+        segments (shz_set_key_cap): the result arrays are those of the plain match on a table lacking those keys' rows.
+        0: off, the default.  A key with exactly `rows` rows stays.  Decided at the probe, so a dropped key costs neither
+        expand, sort nor fold; the sharded table applies it exactly (a key lives on one shard)."""
+        if not 0 <= int(rows) < 1 << 64:
+            raise ShzError(E_INVALID, f"key cap {rows}")
+        self.check(lib().shz_set_key_cap(self.h, int(rows)))
+
+    @property
+    def key_cap(self):
+        """The key cap in force (an int; 0: off).  with ctx.key_cap(rows): the cap inside the block, the previous one after
+        it (also after an exception; blocks nest).  rows None: the context stays as it is.  Every call that matches inside
+        the block follows it: recognize_speeds / recognize_warps, find_duplicates / match_songs, the listeners,
+        match_extents and the scans included."""
+        n = C.c_uint64()
+        self.check(lib().shz_get_key_cap(self.h, C.byref(n)))
+        return _KeyCap(self, n.value)
+
+    def key_cap_stats(self) -> dict:
+        """{"groups", "pairs"}: the (query, key) groups and the pairs the key cap dropped in the last match call (0 with the
+        cap off)."""
+        g, p = C.c_uint64(), C.c_uint64()
+        self.check(lib().shz_key_cap_stats(self.h, C.byref(g), C.byref(p)))
+        return {"groups": g.value, "pairs": p.value}
 
     # ---- the vote floor (shz_set_vote_floor) ----------------------------------------------
     def set_vote_floor(self, on: bool):
@@ -1955,7 +2023,8 @@ class Table:
         [n, ncand], hist [n, ncand, 64] (pairs per bucket q_off >> shift; None with hist false), shift [n].  Candidates are
         [n, ncand] arrays, of which query q uses the first cand_n[q] (None: all); everything past them is zero.
         fit (shz_match_extents_fit): the moments of every candidate's pairs too -- sum_q, sum_u, sum_qq, sum_qu [n, ncand]
-        (uint64, modulo 2^64) with q = q_off and u = (off - q_off) - d_lo; a used candidate must span less than 4,096 bins."""
+        (uint64, modulo 2^64) with q = q_off and u = (off - q_off) - d_lo; a used candidate must span less than 4,096 bins.
+        The key cap is taken from the context: inside `with ctx.key_cap(rows):` every output covers the kept pairs only."""
         k = np.ascontiguousarray(key32, np.uint32)
         o = np.ascontiguousarray(q_off, np.uint32)
         qo = np.ascontiguousarray(query_off, np.uint64)
@@ -2068,7 +2137,7 @@ class Table:
         return dict(sets=list(song_sets), exclude=bool(exclude)), m
 
     def match(self, key32, q_off, query_off, topn=2, full_sort=False, delta_tol=None, floor=False, songs=None, exclude=None,
-              song_sets=None, set_of=None):
+              song_sets=None, set_of=None, max_key_rows=None):
         """Batched return_matches + align_matches.  Returns dict of arrays (see shz.h).  full_sort: the vote as one
         sort of 8-byte votes + record chain (SHZ_MATCH_FULL_SORT), the form the faster vote paths are tested against.
         delta_tol: the vote tolerance of this call (Context.tolerance); None: the context's.  floor: the result gains
@@ -2077,14 +2146,16 @@ class Table:
         songs= / exclude= (song ids): the match within / without these songs, one set for all queries (Context.songs; the
         arrays of a plain match on a table of the allowed songs' rows only; npairs counts the kept pairs).  song_sets= (a
         list of id lists) with set_of= (a set index per query): per-query sets (shz_match_batch_sets); exclude=True bars
-        the listed songs.  The context's own filter is back in force afterwards."""
+        the listed songs.  The context's own filter is back in force afterwards.
+        max_key_rows: the key cap of this call (Context.key_cap: keys that hold more table rows vote for nobody; the arrays
+        of a plain match on a table lacking those keys' rows; 0: off); None: the context's."""
         k = np.ascontiguousarray(key32, np.uint32)
         o = np.ascontiguousarray(q_off, np.uint32)
         qo = np.ascontiguousarray(query_off, np.uint64)
         nq = len(qo) - 1
         res = _match_result(nq, topn)
         filt, smap = self._filter_of(nq, songs, exclude, song_sets, set_of)
-        with self.ctx.tolerance(delta_tol), self.ctx.floor(floor), self.ctx.songs(**filt):
+        with self.ctx.tolerance(delta_tol), self.ctx.floor(floor), self.ctx.songs(**filt), self.ctx.key_cap(max_key_rows):
             before = self.ctx.floor_rows() if floor else 0
             args = (self.ctx.h, self.h, ptr(k), ptr(o), qo.ctypes.data_as(u64p), nq, topn, MATCH_FULL_SORT if full_sort else 0,
                     ptr(res["sid"]), ptr(res["delta"]), ptr(res["aligned"]), ptr(res["dedup"]), ptr(res["nres"]), ptr(res["nhash"]),
@@ -2098,17 +2169,18 @@ class Table:
         return res
 
     def match_device(self, key32, q_off, query_off, topn=2, full_sort=False, bias_bound=-1, floor=False, songs=None, exclude=None,
-                     song_sets=None, set_of=None, delta_tol=None):
+                     song_sets=None, set_of=None, delta_tol=None, max_key_rows=None):
         """match() the way the fused calls and the listeners run it (shz_match_device_host): the two columns are put on the
         device first and matched there, with the caller's bound of the query offsets (below 0 or >= 2^32: none).  For tests
-        and tools; same result arrays as match() (floor, songs, exclude, song_sets, set_of, delta_tol: as there)."""
+        and tools; same result arrays as match() (floor, songs, exclude, song_sets, set_of, delta_tol, max_key_rows: as
+        there)."""
         k = np.ascontiguousarray(key32, np.uint32)
         o = np.ascontiguousarray(q_off, np.uint32)
         qo = np.ascontiguousarray(query_off, np.uint64)
         nq = len(qo) - 1
         res = _match_result(nq, topn)
         filt, smap = self._filter_of(nq, songs, exclude, song_sets, set_of)
-        with self.ctx.tolerance(delta_tol), self.ctx.floor(floor), self.ctx.songs(**filt):
+        with self.ctx.tolerance(delta_tol), self.ctx.floor(floor), self.ctx.songs(**filt), self.ctx.key_cap(max_key_rows):
             before = self.ctx.floor_rows() if floor else 0
             args = (self.ctx.h, self.h, ptr(k), ptr(o), qo.ctypes.data_as(u64p), nq, topn, MATCH_FULL_SORT if full_sort else 0,
                     int(bias_bound), ptr(res["sid"]), ptr(res["delta"]), ptr(res["aligned"]), ptr(res["dedup"]), ptr(res["nres"]),
@@ -2120,6 +2192,15 @@ class Table:
             if floor:
                 _floor_into(self.ctx, res, before, nq)
         return res
+
+    def key_hist(self) -> dict:
+        """The key sizes of the finalized rows (shz_table_key_hist): {"keys": uint64[32] -- the distinct keys whose row count
+        falls into each bucket of shazam_amd.floor.bucket_of (1 .. 16 exact, then powers of two) --, "rows": uint64[32] --
+        the rows they hold --, "max_rows": the largest key, "n_keys": the distinct keys}.  shazam_amd.keycap turns it into
+        a cap (Context.key_cap)."""
+        keys, rows, mx, nk = np.zeros(32, np.uint64), np.zeros(32, np.uint64), C.c_uint64(), C.c_uint64()
+        self.ctx.check(lib().shz_table_key_hist(self.h, ptr(keys), ptr(rows), C.byref(mx), C.byref(nk)))
+        return {"keys": keys, "rows": rows, "max_rows": int(mx.value), "n_keys": int(nk.value)}
 
     def match_stats(self):
         a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()

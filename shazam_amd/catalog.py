@@ -121,7 +121,9 @@ def match_songs(db_or_table, sids, topn: int = 5, full_sort: bool = False, speed
     and delta is the found song's frame under the listed song's WARPED frame 0.
     delta_tol= (keyword): the vote tolerance in offset bins while the call runs (Context.tolerance); None: the context's.
     A song filter is taken from the context: run the call inside `with ctx.songs(only=...)` / `ctx.songs(exclude=...)` to match
-    within / without a set of songs (every variant, every listed song uses the one set)."""
+    within / without a set of songs (every variant, every listed song uses the one set).
+    The key cap is taken from the context too: run the call inside `with ctx.key_cap(rows):` to leave out the keys that hold
+    more than `rows` table rows (Context.key_cap)."""
     table, _ = _table_of(db_or_table)
     lad = _ladder_of(speeds, tempos, pitches, warps)
     if lad is None:
@@ -466,6 +468,8 @@ def find_duplicates(db_or_table, sids=None, topn: int = 5, min_aligned: int = No
     delta_tol= (keyword): the vote tolerance in offset bins while the call runs (Context.tolerance); None: the context's.
     A song filter is taken from the context: run the call inside `with ctx.songs(only=...)` / `ctx.songs(exclude=...)` to match
     within / without a set of songs (every variant, every listed song uses the one set).
+    The key cap is taken from the context too: run the call inside `with ctx.key_cap(rows):` to leave out the keys that hold
+    more than `rows` table rows (Context.key_cap).
     extents: "pairs" gains a_first, a_last, b_first, b_last (EXTENT_PAIR_FIELDS; pair_extents): where in a and where in b the
     aligned rows lie -- the position of an excerpt inside the longer track, the length of an overlap.  extents=True does not
     take a ladder.

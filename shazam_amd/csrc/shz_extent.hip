@@ -444,6 +444,8 @@ int32_t ex_device(shz_ctx* ctx, shz_table* t, const char* who, const uint32_t* d
     hipLaunchKernelGGL(ex_probe_kernel, dim3(nblk(bound)), dim3(256), 0, ctx->stream, (const uint64_t*)E, &ctl->mu, bound,
                        (const shz_seg_dev*)d_segs, nseg, (uint32_t*)lo, (uint64_t*)rows);
     SHZ_HIP(ctx, hipGetLastError());
+    if (ctx->key_cap)   // (shz_set_key_cap: an element is a group of its own here, its slots hold rows)
+      SHZ_TRY(shz_key_cap_apply(ctx, (uint64_t*)rows, nullptr, (const unsigned long long*)&ctl->mu, m, nseg, nullptr));
     SHZ_TRY(shz_scan_u64(ctx, (const uint64_t*)rows, (uint64_t*)po, bound, (uint64_t*)&ctl->P));
     exctl h;
     SHZ_HIP(ctx, shz_memcpy(ctx, &h, ctl, sizeof(exctl), hipMemcpyDeviceToHost));

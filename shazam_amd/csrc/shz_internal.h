@@ -165,6 +165,8 @@ struct shz_ctx {
   uint64_t st_rows = 0, st_pairs = 0, st_keys = 0;
   uint64_t st_spec_queued = 0, st_spec_used = 0;   // single small queries whose votes were queued ahead of the count / whose results that gave
   uint64_t st_vt_redo = 0;      // sub-batches whose vote tiles flagged an overflow and were voted again by the full sort
+  uint64_t key_cap = 0;         // shz_set_key_cap: a key that holds more table rows votes for nobody (0: off)
+  uint64_t st_cap_groups = 0, st_cap_pairs = 0;   // ... the (query, key) groups and the pairs it dropped in the last match call
   uint32_t debug = 0;           // SHZ_DEBUG_* (shz_set_debug): switches that force rare paths, for tests
   uint32_t vote_tol = 0;        // shz_set_vote_tolerance: neighbouring offset bins a song's aligned count sums over (0 .. 31)
   uint32_t vote_floor = 0;      // shz_set_vote_floor: every query handed to the match records a row of two histograms
@@ -270,6 +272,12 @@ int32_t shz_match_device(shz_ctx* ctx, shz_table* t, const uint32_t* d_key32, co
                          int32_t* out_delta, uint32_t* out_aligned, uint32_t* out_dedup, uint32_t* out_nres, uint32_t* out_nhash,
                          uint64_t* out_npairs, const uint32_t* set_of_query = nullptr);   // (host; NULL: set 0 of a song filter)
 int32_t shz_match_ready(shz_ctx* ctx, shz_table* t, uint32_t topn);
+// the key cap (shz_set_key_cap) on the counts of a probe, before their scan: d_vals[g * nseg + sg] of the groups g < *d_n
+// (<= bound) are zeroed where the group's key holds more rows than the cap.  d_gs: first element of every group, one more
+// entry behind the last (the values are rows x elements), or NULL (the values are rows).  d_ctr (or NULL): the dropped
+// groups and pairs, striped (M_CAP_STRIPES in shz_table.hip).  Launches nothing while no cap is set.
+int32_t shz_key_cap_apply(shz_ctx* ctx, uint64_t* d_vals, const uint32_t* d_gs, const unsigned long long* d_n, uint64_t bound,
+                          uint32_t nseg, unsigned long long* d_ctr);
 // the vote floor (shz_set_vote_floor): n zero rows, for a caller that skips the match because nothing is to be looked up (its
 // rows must line up with its result arrays).  Nothing while the floor is off
 void shz_floor_zero_rows(shz_ctx* ctx, uint64_t n);

@@ -72,6 +72,11 @@ struct mctl {
 // rows under the probed keys: striped over the 8-byte words [16, 16 + M_ROW_STRIPES) of the 256-byte control block
 #define M_ROW_STRIPES 16
 static_assert(sizeof(mctl) <= 128 && 128 + M_ROW_STRIPES * 8 <= 256, "the stripes sit in the second half of the control block");
+// the key cap (shz_set_key_cap): groups dropped in the words [M_CAP_WORD, M_CAP_WORD + M_CAP_STRIPES), their pairs in the
+// M_CAP_STRIPES words behind them -- between mctl and the row stripes, zero while no cap is set
+#define M_CAP_WORD 10
+#define M_CAP_STRIPES 3
+static_assert(sizeof(mctl) <= M_CAP_WORD * 8 && (M_CAP_WORD + 2 * M_CAP_STRIPES) * 8 <= 128, "the cap's counters sit behind mctl");
 // the filler element that stands for the hashes other shards own sorts last: it is not an element
 __global__ void m_fix_mu_kernel(mctl* c, unsigned long long m) {
   if (c->err[2] && c->mu) --c->mu;
@@ -369,6 +374,58 @@ __global__ void m_probe_kernel(const uint64_t* __restrict__ E, const uint32_t* _
   // (statistics only.  One word for all waves cost more than the searches: 31,000 atomics on one address per call; the
   // count is kept in M_ROW_STRIPES words of the control block instead and summed on the host)
   if ((threadIdx.x & 63) == 0 && s) atomicAdd(rows_total + (blockIdx.x & (M_ROW_STRIPES - 1)), s);
+}
+
+// ---- the key cap (shz_set_key_cap): a key that holds more than `cap` table rows over all segments votes for nobody.  Between
+// the probe and the scan of its counts, one thread per group g < *n_dev sums the rows of the group's nseg sub-groups --
+// vals[g * nseg + sg] / (elements of the group) -- and zeroes all nseg entries where the sum exceeds the cap: the scan, and
+// with it the expand, the tiles, the queued fold, the per-query counts and the sink, then never see the key.  gs == NULL (the
+// extent pass, whose slots are (element, segment) and hold rows): one element a group.  ctr (NULL: not counted): dropped
+// groups and dropped pairs, reduced over the wave, one atomic a wave and counter into M_CAP_STRIPES striped words each.
+__device__ __forceinline__ bool key_cap_drop(uint64_t* __restrict__ vals, uint32_t nseg, uint32_t elems, uint64_t cap,
+                                             unsigned long long* pairs) {
+  unsigned long long rows = 0, p = 0;
+  for (uint32_t sg = 0; sg < nseg; ++sg) {
+    const uint64_t v = vals[sg];
+    p += v;
+    rows += v / elems;
+  }
+  *pairs = p;
+  if (rows <= cap) return false;
+  for (uint32_t sg = 0; sg < nseg; ++sg) vals[sg] = 0;
+  return true;
+}
+__global__ void key_cap_kernel(uint64_t* __restrict__ vals, const uint32_t* __restrict__ gs,
+                               const unsigned long long* __restrict__ n_dev, uint64_t bound, uint32_t nseg, uint64_t cap,
+                               unsigned long long* __restrict__ ctr) {
+  const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const uint64_t n = *n_dev < bound ? *n_dev : bound;   // (the launch and the buffers are sized by the bound)
+  unsigned long long dg = 0, dp = 0;
+  if (g < n) {
+    unsigned long long p;
+    if (key_cap_drop(vals + g * nseg, nseg, gs ? gs[g + 1] - gs[g] : 1u, cap, &p)) {
+      dg = 1;
+      dp = p;
+    }
+  }
+  if (!ctr) return;
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    dg += __shfl_xor((long long)dg, d, 64);
+    dp += __shfl_xor((long long)dp, d, 64);
+  }
+  if ((threadIdx.x & 63) == 0 && dg) {
+    atomicAdd(ctr + blockIdx.x % M_CAP_STRIPES, dg);
+    atomicAdd(ctr + M_CAP_STRIPES + blockIdx.x % M_CAP_STRIPES, dp);
+  }
+}
+int32_t shz_key_cap_apply(shz_ctx* ctx, uint64_t* d_vals, const uint32_t* d_gs, const unsigned long long* d_n, uint64_t bound,
+                          uint32_t nseg, unsigned long long* d_ctr) {
+  if (!ctx->key_cap || bound == 0) return SHZ_OK;
+  hipLaunchKernelGGL(key_cap_kernel, dim3(nblk(bound)), dim3(256), 0, ctx->stream, d_vals, d_gs, d_n, bound, nseg, ctx->key_cap,
+                     d_ctr);
+  SHZ_HIP(ctx, hipGetLastError());
+  return SHZ_OK;
 }
 
 __global__ void m_query_stats_kernel(const uint64_t* __restrict__ E, const mctl* __restrict__ ctl,
@@ -2672,6 +2729,7 @@ struct match_sub {
   void* mail;                // control block | votes per query | result block of a queued fold
   uint64_t mu, P, nx, rows_total;
   uint64_t kept;             // the votes that were folded: P, or what the song filter left of them
+  uint64_t cap_groups, cap_pairs;   // what the key cap dropped at the probe (shz_set_key_cap; P counts the pairs it left)
   uint32_t ng;
   std::vector<uint64_t> votes;   // per query
   double tr[4];              // SHZ_TRACE_MATCH: start, head queued, counts back, votes queued
@@ -2844,6 +2902,9 @@ static int32_t sub_head(match_call& mc, match_sub& s, sub_next* next) {
                      (const uint32_t*)s.gs, &s.d_ctl->ng, s.nx_bound, mc.d_segs, mc.nseg, s.glo, (uint64_t*)gpairs,
                      (unsigned long long*)s.d_ctl + 16, (uint32_t*)s.rb, (uint32_t)((s.rb_bytes + 3) / 4));
   SHZ_HIP(ctx, hipGetLastError());
+  if (ctx->key_cap)   // groups <= m; the sentinel behind the last sub-group stays 0
+    SHZ_TRY(shz_key_cap_apply(ctx, (uint64_t*)gpairs, (const uint32_t*)s.gs, &s.d_ctl->ng, m, mc.nseg,
+                              (unsigned long long*)s.d_ctl + M_CAP_WORD));
   SHZ_TRY(shz_scan_u64(ctx, (const uint64_t*)gpairs, s.po, s.nx_bound, (uint64_t*)&s.d_ctl->P));
   return SHZ_OK;
 }
@@ -2935,6 +2996,11 @@ static int32_t sub_read_counts(const match_call& mc, match_sub& s, sub_next* nex
   s.P = s.kept = h.P;
   s.rows_total = 0;
   for (int i = 0; i < M_ROW_STRIPES; ++i) s.rows_total += ((const uint64_t*)mail)[16 + i];
+  s.cap_groups = s.cap_pairs = 0;
+  for (int i = 0; i < M_CAP_STRIPES; ++i) {
+    s.cap_groups += ((const uint64_t*)mail)[M_CAP_WORD + i];
+    s.cap_pairs += ((const uint64_t*)mail)[M_CAP_WORD + M_CAP_STRIPES + i];
+  }
   ctx->m_votes_per_hash = mc.t->votes_per_hash = (double)s.P / (double)s.mu;
   if (s.P > mc.sub_budget && nq > 1) { *next = SUB_FEWER; return SHZ_OK; }   // too many votes for one sub-batch
   if (s.P >= (1ull << 32)) SHZ_FAIL(ctx, SHZ_E_UNSUPPORTED, "query %u alone produces %llu matches (limit 2^32)", s.q0, (unsigned long long)s.P);
@@ -3152,6 +3218,8 @@ static int32_t sub_commit(match_call& mc, const match_sub& s, vote_route route, 
   ctx->st_rows += s.rows_total;
   ctx->st_pairs += s.P;
   ctx->st_keys += s.ng;
+  ctx->st_cap_groups += s.cap_groups;
+  ctx->st_cap_pairs += s.cap_pairs;
   if (nq == 1) {
     if (mc.out_npairs) mc.out_npairs[q0] = s.kept;   // (P but under a song filter)
     if (mc.out_nhash) mc.out_nhash[q0] = (uint32_t)s.mu;
@@ -3210,7 +3278,7 @@ static int32_t match_core(match_call& mc) {
     SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_match_batch: NULL buffer");
   if (!mc.sink && (mc.topn < 1 || mc.topn > 64)) SHZ_FAIL(ctx, SHZ_E_INVALID, "topn must be in [1,64]");
   SHZ_HIP(ctx, hipSetDevice(ctx->device));
-  ctx->st_rows = ctx->st_pairs = ctx->st_keys = 0;
+  ctx->st_rows = ctx->st_pairs = ctx->st_keys = ctx->st_cap_groups = ctx->st_cap_pairs = 0;
   // votes of one sub-batch of queries (one head: compose, sort, probe, one round trip): up to 2^30 where the device has
   // the memory for it (a sub-batch that ends up on the 8-byte path needs ~32 bytes per vote of workspace)
   mc.sub_budget = VOTE_PASS_MAX;
@@ -3407,6 +3475,25 @@ extern "C" int32_t shz_get_vote_tolerance(shz_ctx* ctx, uint32_t* bins) {
   *bins = ctx->vote_tol;
   return SHZ_OK;
 }
+// the key cap: a setting of the context; the yield of a hash depends on it, so the estimate that sizes the next sub-batch
+// (m_votes_per_hash) is forgotten when it changes
+extern "C" int32_t shz_set_key_cap(shz_ctx* ctx, uint64_t rows) {
+  if (!ctx) return SHZ_E_INVALID;
+  if (rows != ctx->key_cap) ctx->m_votes_per_hash = 0.0;
+  ctx->key_cap = rows;
+  return SHZ_OK;
+}
+extern "C" int32_t shz_get_key_cap(shz_ctx* ctx, uint64_t* rows) {
+  if (!ctx || !rows) return SHZ_E_INVALID;
+  *rows = ctx->key_cap;
+  return SHZ_OK;
+}
+extern "C" int32_t shz_key_cap_stats(shz_ctx* ctx, uint64_t* groups_dropped, uint64_t* pairs_dropped) {
+  if (!ctx) return SHZ_E_INVALID;
+  if (groups_dropped) *groups_dropped = ctx->st_cap_groups;
+  if (pairs_dropped) *pairs_dropped = ctx->st_cap_pairs;
+  return SHZ_OK;
+}
 extern "C" int32_t shz_set_vote_floor(shz_ctx* ctx, uint32_t on) {
   if (!ctx) return SHZ_E_INVALID;
   ctx->vote_floor = on ? 1u : 0u;
@@ -3521,6 +3608,133 @@ extern "C" int32_t shz_match_stats(shz_ctx* ctx, uint64_t* rows_scanned, uint64_
   if (rows_scanned) *rows_scanned = ctx->st_rows;
   if (pairs) *pairs = ctx->st_pairs;
   if (distinct_keys) *distinct_keys = ctx->st_keys;
+  return SHZ_OK;
+}
+
+// ---- the key sizes of a table (shz_table_key_hist): how many rows its keys hold.  One launch per segment s over its sorted
+// key column, a workgroup owns KH_CHUNK consecutive rows (KH_PER rounds of 256 coalesced loads; the predecessor comes from the
+// same cache lines).  A run head (key[i] != key[i - 1]) finds the end of its run in its bucket of the directory, then asks
+// every other segment the way the probe does (range test, bucket, lower and upper bound); a key that a lower-numbered segment
+// holds is that segment's to count.  Buckets: shz_vote_bucket's.  A wave adds the heads of an exact bucket (1 .. 16 rows: the
+// rows follow from the count) with one LDS atomic pair per bucket present, the rare larger keys one by one; the workgroup's
+// 64-bit LDS table goes to the global one once, in the words keys[32] | rows[32] | largest key | keys.
+#define KH_PER 16
+#define KH_CHUNK (256 * KH_PER)
+#define KH_WORDS (2 * FH_BUCKETS + 2)
+__device__ __forceinline__ uint32_t kh_rows_in(const shz_seg_dev& g, uint32_t key) {
+  const uint64_t b = key >> 8;
+  if (!(b < g.nbuckets && key >= g.key_lo && g.n)) return 0;
+  uint32_t l = g.bucket[b], h = g.bucket[b + 1];
+  const uint32_t h0 = h;
+  while (l < h) {   // lower_bound(key)
+    const uint32_t mid = l + ((h - l) >> 1);
+    if (g.key[mid] < key) l = mid + 1; else h = mid;
+  }
+  const uint32_t lo = l;
+  h = h0;
+  while (l < h) {   // upper_bound(key)
+    const uint32_t mid = l + ((h - l) >> 1);
+    if (g.key[mid] <= key) l = mid + 1; else h = mid;
+  }
+  return l - lo;
+}
+__global__ __launch_bounds__(256) void key_hist_kernel(const shz_seg_dev* __restrict__ segs, uint32_t nseg, uint32_t s,
+                                                       unsigned long long* __restrict__ out /*[KH_WORDS]*/) {
+  __shared__ unsigned long long sh[KH_WORDS];
+  if (threadIdx.x < KH_WORDS) sh[threadIdx.x] = 0;
+  __syncthreads();
+  const shz_seg_dev me = segs[s];
+  const uint32_t* __restrict__ key = me.key;
+  const uint32_t lane = threadIdx.x & 63;
+  const uint64_t base = (uint64_t)blockIdx.x * KH_CHUNK;
+  unsigned long long top = 0;
+  for (int r = 0; r < KH_PER; ++r) {
+    const uint64_t i = base + (uint64_t)r * 256 + threadIdx.x;
+    if (base + (uint64_t)r * 256 >= me.n) break;   // uniform
+    bool head = false;
+    uint32_t b = 0;
+    unsigned long long rows = 0;
+    if (i < me.n) {
+      const uint32_t k = key[i];
+      if (i == 0 || key[i - 1] != k) {
+        uint32_t l = (uint32_t)i + 1, h = me.bucket[(k >> 8) + 1];   // upper_bound(k) behind the head, inside its bucket
+        while (l < h) {
+          const uint32_t mid = l + ((h - l) >> 1);
+          if (key[mid] <= k) l = mid + 1; else h = mid;
+        }
+        rows = l - (uint32_t)i;
+        head = true;
+        for (uint32_t o = 0; o < nseg; ++o) {
+          if (o == s) continue;
+          const uint32_t ro = kh_rows_in(segs[o], k);
+          if (ro && o < s) { head = false; break; }   // counted at the lowest segment that holds the key
+          rows += ro;
+        }
+        if (head) b = rows >> 19 ? (uint32_t)FH_BUCKETS - 1u : vote_bucket((uint32_t)rows);
+      }
+    }
+    const uint64_t heads = __ballot(head);
+    if (heads == 0) continue;   // uniform
+    if (lane == 0) atomicAdd(&sh[2 * FH_BUCKETS + 1], (unsigned long long)__popcll(heads));
+    if (head && rows > top) top = rows;
+    uint64_t todo = __ballot(head && b < 16u);
+    while (todo) {   // uniform
+      const int l = __ffsll((unsigned long long)todo) - 1;
+      const uint32_t bb = (uint32_t)__shfl((int)b, l, 64);
+      const uint64_t m = __ballot(head && b == bb);
+      if ((int)lane == l) {
+        atomicAdd(&sh[bb], (unsigned long long)__popcll(m));
+        atomicAdd(&sh[FH_BUCKETS + bb], (unsigned long long)__popcll(m) * (bb + 1u));
+      }
+      todo &= ~m;
+    }
+    if (head && b >= 16u) {
+      atomicAdd(&sh[b], 1ull);
+      atomicAdd(&sh[FH_BUCKETS + b], rows);
+    }
+  }
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    const unsigned long long o = (unsigned long long)__shfl_xor((long long)top, d, 64);
+    top = o > top ? o : top;
+  }
+  if (lane == 0 && top) atomicMax(&sh[2 * FH_BUCKETS], top);
+  __syncthreads();
+  if (threadIdx.x < KH_WORDS && sh[threadIdx.x]) {
+    if (threadIdx.x == 2 * FH_BUCKETS) atomicMax(out + threadIdx.x, sh[threadIdx.x]);
+    else atomicAdd(out + threadIdx.x, sh[threadIdx.x]);
+  }
+}
+extern "C" int32_t shz_table_key_hist(shz_table* t, uint64_t* keys, uint64_t* rows, uint64_t* max_rows, uint64_t* n_keys) {
+  if (!t) return SHZ_E_INVALID;
+  shz_ctx* ctx = t->ctx;
+  if (!keys || !rows) SHZ_FAIL(ctx, SHZ_E_INVALID, "shz_table_key_hist: NULL histogram");
+  if (pending_rows(t)) SHZ_FAIL(ctx, SHZ_E_STATE, "table has %llu staged rows; call shz_table_finalize first", (unsigned long long)pending_rows(t));
+  uint64_t h[KH_WORDS] = {0};
+  const std::vector<shz_seg> segs = all_segs(t);
+  if (!segs.empty()) {
+    SHZ_HIP(ctx, hipSetDevice(ctx->device));
+    std::vector<shz_seg_dev> hsegs;
+    for (const shz_seg& g : segs) hsegs.push_back(seg_dev_of(g));
+    const uint64_t seg_bytes = (sizeof(shz_seg_dev) * hsegs.size() + 255) & ~255ull;
+    void* d;
+    SHZ_TRY(shz_ws_reserve(ctx, SHZ_WS_MISC1, seg_bytes + KH_WORDS * 8, &d));
+    unsigned long long* d_out = (unsigned long long*)((char*)d + seg_bytes);
+    SHZ_HIP(ctx, shz_memcpy(ctx, d, hsegs.data(), sizeof(shz_seg_dev) * hsegs.size(), hipMemcpyHostToDevice));
+    SHZ_HIP(ctx, hipMemsetAsync(d_out, 0, KH_WORDS * 8, ctx->stream));
+    for (uint32_t s = 0; s < hsegs.size(); ++s) {
+      if (!hsegs[s].n) continue;
+      hipLaunchKernelGGL(key_hist_kernel, dim3((unsigned)(((uint64_t)hsegs[s].n + KH_CHUNK - 1) / KH_CHUNK)), dim3(256), 0,
+                         ctx->stream, (const shz_seg_dev*)d, (uint32_t)hsegs.size(), s, d_out);
+      SHZ_HIP(ctx, hipGetLastError());
+    }
+    SHZ_HIP(ctx, shz_memcpy(ctx, h, d_out, KH_WORDS * 8, hipMemcpyDeviceToHost));
+    SHZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  memcpy(keys, h, FH_BUCKETS * 8);
+  memcpy(rows, h + FH_BUCKETS, FH_BUCKETS * 8);
+  if (max_rows) *max_rows = h[2 * FH_BUCKETS];
+  if (n_keys) *n_keys = h[2 * FH_BUCKETS + 1];
   return SHZ_OK;
 }
 

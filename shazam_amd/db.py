@@ -175,16 +175,22 @@ class HipFingerprintDB:
         return [(h.upper(), int(a), int(b)) for h, a, b in zip(hexes, s.tolist(), o.tolist())]  # HEX() upper-cases
 
     def match(self, key32, q_off, query_off, topn=2, delta_tol=None, floor=False, songs=None, exclude=None, song_sets=None,
-              set_of=None):
+              set_of=None, max_key_rows=None):
         """Table.match / ShardedTable.match of the finalized table.  delta_tol: the vote tolerance of this call, None: the
         context's.  floor: the result gains song_hist / bin_hist (Table.match).  songs / exclude / song_sets / set_of: the
-        match within a set of songs (Table.match); the unsharded table only (a sharded database: NotImplementedError)."""
+        match within a set of songs (Table.match); the unsharded table only (a sharded database: NotImplementedError).
+        max_key_rows: the key cap of this call (Context.key_cap), sharded or not; None: the context's."""
         self.finalize()
         filt = {k: v for k, v in (("songs", songs), ("exclude", exclude), ("song_sets", song_sets), ("set_of", set_of)) if v is not None}
         if filt and not hasattr(self.table, "h"):
             raise NotImplementedError("songs= / exclude= / song_sets= take the unsharded table (shards=1)")
-        with self.ctx.tolerance(delta_tol):
+        with self.ctx.tolerance(delta_tol), self.ctx.key_cap(max_key_rows):
             return self.table.match(key32, q_off, query_off, topn, floor=floor, **filt)
+
+    def key_hist(self):
+        """Table.key_hist / ShardedTable.key_hist of the finalized table: how many rows its keys hold."""
+        self.finalize()
+        return self.table.key_hist()
 
     def match_extents(self, key32, q_off, query_off, cand_sid, d_lo, d_hi, cand_n=None, hist=True):
         """Table.match_extents of the finalized table: where the aligned hashes of the candidates lie; one table only."""

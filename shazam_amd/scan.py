@@ -18,7 +18,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import _ffi
-from ._ffi import HOP, takes_delta_tol, takes_song_filter
+from ._ffi import HOP, takes_delta_tol, takes_key_cap, takes_song_filter
 
 TOPN = 2                 # recognizer.py:68, as the package has it
 DEFAULT_FS = 44100       # recognizer.py:21-38
@@ -134,6 +134,7 @@ def _scan_warp_windows(run, tl, pl, t16, f16, row, search):
     return res, win_off, ms
 
 
+@takes_key_cap(lambda *a, **k: (k["db"] if "db" in k else a[1]).ctx)
 @takes_song_filter(lambda *a, **k: (k["db"] if "db" in k else a[1]).ctx)
 @takes_delta_tol(lambda *a, **k: (k["db"] if "db" in k else a[1]).ctx)
 def scan_windows(recordings, db, Fs: int = 44100, window_seconds: float = 5, step_seconds: float = 1, topn: int = TOPN,
@@ -167,6 +168,8 @@ def scan_windows(recordings, db, Fs: int = 44100, window_seconds: float = 5, ste
     shazam_amd.floor); the other arrays do not change.
     songs= / exclude= (keywords, song ids): every window is matched within / without these songs (Context.songs): the arrays
     of the same scan on a database holding only the allowed songs, npairs counting the kept pairs; any kind of scan.
+    max_key_rows= (keyword): the key cap while the call runs (Context.key_cap: keys that hold more table rows vote for
+    nobody); None: the context's; any kind of scan.
     _fit (scan(extents="fit")): the plays stage of a warped scan runs behind the scan on the same prepared audio -- with
     resample_to= the same device buffer, before it is freed -- and the dict gains "plays" (_play_stage)."""
     from . import DEFAULT_AMP_MIN, DEFAULT_FAN_VALUE, resample_to_device
@@ -323,6 +326,7 @@ def _segment(db, w, seg, i):
     }
 
 
+@takes_key_cap(lambda *a, **k: (k["db"] if "db" in k else a[1]).ctx)
 @takes_song_filter(lambda *a, **k: (k["db"] if "db" in k else a[1]).ctx)
 @takes_delta_tol(lambda *a, **k: (k["db"] if "db" in k else a[1]).ctx)
 def scan(recordings, db, Fs: int = 44100, window_seconds: float = 5, step_seconds: float = 1, topn: int = TOPN,
@@ -353,6 +357,7 @@ def scan(recordings, db, Fs: int = 44100, window_seconds: float = 5, step_second
     delta_tol= (keyword): the vote tolerance in offset bins while the call runs (Context.tolerance); None: the context's.
     songs= / exclude= (keywords, song ids): the windows are matched within / without these songs (Context.songs,
     scan_windows): exclude=[a station's jingles] leaves their segments out of the timeline.
+    max_key_rows= (keyword): the key cap while the call runs (Context.key_cap, scan_windows); None: the context's.
     extents=True (the plain scan only: ValueError with speeds=, tempos=, pitches=, warps= or another search;
     NotImplementedError on a sharded table): start_seconds / end_seconds are only as fine as the windows, so every segment also
     says where its aligned hashes really lie (shz_scan_extents, DESIGN.md 3.7l: the extent pass on three zones of the

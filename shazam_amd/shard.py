@@ -204,7 +204,7 @@ class ShardedTable:
             self._pbuf.free()
         self._pbuf, self._pcap = self.ctx.alloc(cap * 8), cap
 
-    def match(self, key32, q_off, query_off, topn=2, delta_tol=None, floor=False):
+    def match(self, key32, q_off, query_off, topn=2, delta_tol=None, floor=False, max_key_rows=None):
         """Same result dict as ``Table.match`` on the union of all shards.  Like ``Table.match``, queries whose votes do
         not fit one 64-bit key together are matched in halves; a query with hashes that does not fit alone raises.
         delta_tol: the vote tolerance of this call (the gathered votes are folded by it), None: the context's.
@@ -213,11 +213,13 @@ class ShardedTable:
         With the floor on (this argument, or Context.set_vote_floor by hand) the call takes the context's row store whole: rows
         recorded before it and not yet taken are dropped (Context.floor).
         A song filter (Context.songs, shz_set_song_filter) is not applied by the sharded match: while the context has one
-        set the call raises NotImplementedError."""
+        set the call raises NotImplementedError.
+        max_key_rows: the key cap of this call (Context.key_cap), None: the context's.  A key lives on one shard, so every
+        shard's probe sees all its rows and the result equals the unsharded table's under the same cap."""
         if self.ctx.song_filter is not None:            # (shz_match_pairs / shz_pairs_vote refuse it too: nothing ignores it)
             raise NotImplementedError("the context has a song filter set (Context.songs): it takes the unsharded table")
-        if delta_tol is not None or floor:
-            with self.ctx.tolerance(delta_tol), self.ctx.floor(floor):
+        if delta_tol is not None or floor or max_key_rows is not None:
+            with self.ctx.tolerance(delta_tol), self.ctx.floor(floor), self.ctx.key_cap(max_key_rows):
                 return self.match(key32, q_off, query_off, topn)
         k = np.ascontiguousarray(key32, np.uint32)
         o = np.ascontiguousarray(q_off, np.uint32)
@@ -321,6 +323,14 @@ class ShardedTable:
         k, s, o = (np.concatenate([p[i] for p in parts]) for i in range(3))
         order = np.lexsort((o, s, k))
         return k[order], s[order], o[order]
+
+    def key_hist(self):
+        """Table.key_hist over the shards held here: keys are disjoint across shards, so the histograms and the key counts
+        add up and the largest key is the largest of the shards'."""
+        hs = [t.key_hist() for t in self.tables]
+        return {"keys": np.sum([h["keys"] for h in hs], axis=0, dtype=np.uint64),
+                "rows": np.sum([h["rows"] for h in hs], axis=0, dtype=np.uint64),
+                "max_rows": max(h["max_rows"] for h in hs), "n_keys": sum(h["n_keys"] for h in hs)}
 
     def song_rows(self, sid) -> int:
         self._local_only("song_rows")

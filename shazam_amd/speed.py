@@ -176,6 +176,8 @@ def recognize_speeds(queries, db, speeds=None, Fs: int = 44100, topn: int = 2, r
     delta_tol= (keyword): the vote tolerance in offset bins while the call runs (Context.tolerance); None: the context's.
     A song filter is taken from the context: run the call inside `with ctx.songs(only=...)` / `ctx.songs(exclude=...)` to match
     within / without a set of songs (every variant, every listed song uses the one set).
+    The key cap is taken from the context too: run the call inside `with ctx.key_cap(rows):` to leave out the keys that hold
+    more than `rows` table rows (Context.key_cap).
     extents / drift_bins: as recognize_warps' -- the chosen speed is the rung of both axes, "tempo_fit" the fitted TIME factor."""
     from . import DEFAULT_AMP_MIN, DEFAULT_FAN_VALUE, _as_pcm, _result_dicts, resample_to_device
     if not hasattr(db.table, "h"):
@@ -331,6 +333,8 @@ def recognize_warps(queries, db, tempos=None, pitches=None, warps=None, search: 
     delta_tol= (keyword): the vote tolerance in offset bins while the call runs (Context.tolerance); None: the context's.
     A song filter is taken from the context: run the call inside `with ctx.songs(only=...)` / `ctx.songs(exclude=...)` to match
     within / without a set of songs (every variant, every listed song uses the one set).
+    The key cap is taken from the context too: run the call inside `with ctx.key_cap(rows):` to leave out the keys that hold
+    more than `rows` table rows (Context.key_cap).
     extents: every result dict also says WHERE the match holds and what tempo its pairs fit (shz_recognize_warps_extents,
     DESIGN.md 3.7m): the keys of recognize_batch(extents=True) -- "query_first" / "query_last" and the "query_*_secs" in the
     QUERY's own frames (extent.own_frames at the chosen time factor), "song_*", "extent_hist", "extent_shift" as the extent

@@ -143,7 +143,9 @@ class StreamRecognizer:
 
     songs= / exclude= (song ids; at most one of them): this recogniser's listeners are matched within / without these songs.
     The lists are held for its lifetime and every push runs inside Context.songs() -- host and device=True alike, a ladder
-    included; both None: whatever filter the context holds at the push.  The unsharded table only."""
+    included; both None: whatever filter the context holds at the push.  The unsharded table only.
+
+    The key cap is taken from the context at the push: run push() inside `with ctx.key_cap(rows):` (Context.key_cap)."""
 
     def __init__(self, db, n_listeners: int, channels: int = 1, window_seconds: float = 5, topn: int = TOPN,
                  fan_value: int = 5, amp_min=10, device: bool = False, fs_in: int = None, speeds=None, warps=None,
